@@ -3,6 +3,8 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: spawns its own N rank processes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+    python bench.py ... --full                             (also everything under "Extra objects" below)
+    python bench.py ... --dump-outputs DIR                 (DIR/latents.npy: what the last timed step returned)
 
 One "step" = one pass of the hot path over one batch of synthetic input = ONE fully denoised video
 latent [4,16,40,64] per GPU: 50 DDPM steps x (CFG UNet forward at batch 2 + fused CFG/DDPM update)
@@ -10,7 +12,9 @@ latent [4,16,40,64] per GPU: 50 DDPM steps x (CFG UNet forward at batch 2 + fuse
 parallelism: every rank denoises its own prompts (weak scaling), weights are broadcast once from
 rank 0, finished latents are all-gathered inside the timed region.  Prints ONE JSON line on rank 0.
 
-Extra objects on that line:
+A plain run does only what the headline needs: set-up, --warmup untimed videos, the --steps timed ones, the JSON line
+(metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed video).  Extra objects on that line,
+measured with --full only:
   roofline          the dominant kernel by device time, igemm_patch_kernel (halo-patch 3x3 convolution): algorithmic
                     FLOP per launch / average launch duration, both measured live with HIP events on the launch
                     stream around exactly that kernel inside the timed region, against the 2.5 PFLOP/s dense fp16
@@ -75,6 +79,29 @@ def synth_inputs(idx, device):
     ne = torch.randn(1, CTX_LEN, CTX_DIM, generator=g)
     lat = torch.randn(1, 4, FRAMES, LAT_H, LAT_W, generator=torch.Generator().manual_seed(2000 + idx))
     return pe.to(device), ne.to(device), lat.to(device)
+
+
+def synth_weights(shapes, seed):
+    """weights.synth_state_dict(shapes, seed), its tensors drawn on a thread pool, one group of modules per task.  Every tensor
+    has its own seeded generator (lavie_amd/weights.py), so the values are those of the serial call, which takes 7-15 s of
+    CPU time for the 909 M parameters."""
+    from concurrent.futures import ThreadPoolExecutor
+    from lavie_amd import weights
+    groups = sorted({".".join(k.split(".")[:-1][:4]) + "." for k in shapes})
+    assert not any(a != b and a.startswith(b) for a in groups for b in groups), "module groups must not nest"
+    with ThreadPoolExecutor(host_cores()) as ex:
+        parts = list(ex.map(lambda p: weights.synth_state_dict(shapes, seed, only_prefix=p), groups))
+    merged = {k: v for part in parts for k, v in part.items()}
+    return {k: merged[k] for k in sorted(shapes)}
+
+
+def dump_outputs(path, gathered):
+    """--dump-outputs: the video latents the last timed step returned, one per rank in rank order, [n_gpus, 4, 16, 40, 64]
+    float32 (640 KiB per GPU) in path/latents.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    last = torch.stack([g[-1] for g in gathered]).float().cpu().numpy()
+    np.save(os.path.join(path, "latents.npy"), last)
 
 
 def profile_begin(lib, mask, max_events):
@@ -342,13 +369,19 @@ def vsr_leg(lib, device, iters=2):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3, help="timed video-latents per GPU")
+    ap.add_argument("--steps", type=int, default=3, help="timed video-latents per GPU (one step = one video-latent)")
     ap.add_argument("--warmup", type=int, default=1, help="untimed video-latents per GPU")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--cpu-steps", type=int, default=2, help="timed CFG denoise steps of the CPU baseline after 1 warm-up (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline as well: HIP-event roofline instrumentation, the legs timed after "
+                         "the headline region, the per-class kernel breakdown, the CPU baseline (the options below marked --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to DIR/latents.npy (float32)")
+    ap.add_argument("--cpu-steps", type=int, default=2,
+                    help="--full: timed CFG denoise steps of the CPU baseline after 1 warm-up (0 = skip)")
     ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)      # CPU test of the rank plumbing
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads for the CPU baseline (0 = cgroup/affinity share)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event roofline instrumentation")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the HIP-event roofline instrumentation")
     ap.add_argument("--graph", action="store_true",
                     help="replay the UNet forward from a hipGraph (A/B switch; implies --no-profile: events cannot be captured)")
     ap.add_argument("--ddpm-steps", type=int, default=DDPM_STEPS, help=argparse.SUPPRESS)   # debugging only
@@ -359,15 +392,20 @@ def main():
                     help="run the three Upsample3D convs as 9-tap convs over the (virtual) upsampled image, as the reference computes "
                          "them (default: four 2x2 convs on the source image with pre-summed weights, 2.25x fewer FLOP)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the legs timed after the headline region (both CFG halves computed; k prompts per forward): what "
+                    help="--full: skip the legs timed after the headline region (both CFG halves computed; k prompts per forward): what "
                          "tools/collect_profiles.sh traces, so that per-kernel averages are those of the headline configuration")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the interpolation (configs[3]) and VSR (configs[4]) regression-guard legs that rank 0 runs after the headline")
+                    help="--full: skip the interpolation (configs[3]) and VSR (configs[4]) regression-guard legs that rank 0 runs after "
+                         "the headline")
     ap.add_argument("--prompts-per-forward", type=int, default=4,
-                    help="after the headline (single-prompt) measurement, also time k prompts batched into ONE UNet forward "
+                    help="--full: after the headline (single-prompt) measurement, also time k prompts batched into ONE UNet forward "
                          "(batch 2k; SURVEY §8e 'batched B = 2k if memory-profitable'; BASELINE.json configs[2] readiness) and "
                          "report it as the extra object `batched`; 1 = skip")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:                # a plain run: set-up, warm-up, the timed steps and the headline line, nothing else
+        args.no_profile, args.headline_only, args.no_extra_legs, args.cpu_steps = True, True, True, 0
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: become one (before anything touches the GPU)
@@ -394,7 +432,7 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=device)
 
-    from lavie_amd import _lib, prompt_dp, spec, weights
+    from lavie_amd import _lib, prompt_dp, spec
     from lavie_amd.pipeline_videogen import VideoGenPipeline
     from lavie_amd.scheduling_ddpm import DDPMScheduler
     from lavie_amd.unet import UNet3DConditionModel
@@ -405,7 +443,7 @@ def main():
     # ---- model: random-init weights of the full architecture (909 M parameters), rank 0 -> RCCL broadcast
     shapes = spec.param_shapes()
     t_setup = time.perf_counter()
-    sd32 = weights.synth_state_dict(shapes, args.seed) if rank == 0 else None
+    sd32 = synth_weights(shapes, args.seed) if rank == 0 else None
     views = prompt_dp.broadcast_weights(shapes, sd32, device)
     net = UNet3DConditionModel(sample_size=64, cross_attention_dim=CTX_DIM, init_weights=False)
     for name, p in net.named_parameters():
@@ -461,6 +499,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     finite = all(bool(torch.isfinite(g).all()) for g in gathered)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, gathered)
 
     # ---- extra: k prompts per UNet forward (batch 2k), what a rank of configs[2] (8 prompts per GPU) would run.  Separate
     # from the headline: the metric's configuration is ONE prompt at a time (configs[1]).
@@ -554,6 +594,7 @@ def main():
                    "collectives": "1 weight broadcast (setup), 1 latent all_gather (timed)"},
         "outputs_finite": finite,
         "hip_graph": bool(args.graph),
+        "full": bool(args.full),
         "setup_seconds": setup_s,
         "achieved_tflops_whole_path": video_tflop * total_videos / elapsed / world,
         "mfma_fraction_whole_path": video_tflop * total_videos / elapsed / world / PEAK_MFMA_TFLOPS,

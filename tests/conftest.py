@@ -11,17 +11,6 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run by the driver with -m gpu)")
-    config.addinivalue_line("markers", "reference: needs /root/reference (build container only)")
-
-
-def pytest_collection_modifyitems(config, items):
-    import refimport
-    if refimport.available():
-        return
-    skip = pytest.mark.skip(reason="/root/reference not present (GPU box)")
-    for item in items:
-        if "reference" in item.keywords:
-            item.add_marker(skip)
 
 
 @pytest.fixture(scope="session", autouse=True)

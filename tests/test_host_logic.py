@@ -357,7 +357,8 @@ def test_pipeline_object_walks_the_reference_callers_sequence(monkeypatch):
 
 def test_from_sample_yaml_maps_the_reference_config_keys(tmp_path):
     """base/configs/sample.yaml:16-40: the keys sample.py reads become the scheduler (sample_method + beta_*) and the call
-    keywords (video_length, image_size, num_sampling_steps, guidance_scale); the reference's own file is used when present."""
+    keywords (video_length, image_size, num_sampling_steps, guidance_scale); the reference's own file is read too, as stored in
+    tests/golden/base_sample.yaml."""
     from lavie_amd.pipeline_videogen import VideoGenPipeline
     from lavie_amd.scheduling_ddim import DDIMScheduler
     from lavie_amd.scheduling_euler_discrete import EulerDiscreteScheduler
@@ -366,10 +367,7 @@ def test_from_sample_yaml_maps_the_reference_config_keys(tmp_path):
             "seed: null\nguidance_scale: 7.5\nsample_method: 'ddpm'\nnum_sampling_steps: 50\n")
     path = tmp_path / "sample.yaml"
     path.write_text(text)
-    sources = [str(path)]
-    ref = "/root/reference/base/configs/sample.yaml"
-    if os.path.isfile(ref):
-        sources.append(ref)
+    sources = [str(path), os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "base_sample.yaml")]
     for src in sources:
         pipe, kw, cfg = VideoGenPipeline.from_sample_yaml(src, unet=_StubUNet())
         assert isinstance(pipe.scheduler, DDPMScheduler)

@@ -10,9 +10,9 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 if [ -z "$PMC_ONLY" ]; then
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 echo "bench done: $(head -c 200 $OUT/bench.json)"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 1 --warmup 1 --cpu-steps 0 --headline-only > $OUT/bench_traced.json 2> $OUT/trace.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --steps 1 --warmup 1 --cpu-steps 0 --headline-only > $OUT/bench_traced.json 2> $OUT/trace.err || exit 1
 python3 tools/summarize_trace.py $OUT/trace > $OUT/kernel_summary.md
 cp $(find $OUT/trace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv 2>/dev/null
 echo "trace done"
