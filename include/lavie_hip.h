@@ -82,6 +82,12 @@ int lavie_linear_lnfold_f16(const void* A, const void* Wf, const float* bias, co
 /* GEGLU projection [2*inner, K] (+ bias) -> 16-row value/gate interleave expected by lavie_linear_f16(geglu=1). */
 int lavie_pack_geglu_f16(const void* w, const void* bias_f16, void* w_out, float* bias_out, int N, int K, void* stream);
 
+/* Low-rank adapter merge (LoRA on the attention projections; the fork's fine-tuning wraps to_q / to_k / to_v / to_out.0 with a
+ * peft LoraConfig, base/pipelines/fine_tuning.py:296-307): out[n, k] = fp16_rne(float(W0[n, k]) + scale * sum_{j < r} B[n, j] A[j, k]).
+ * W0 / out fp16 [N, K]; A fp32 [r, K] (lora_A / lora_down); B fp32 [N, r] (lora_B / lora_up).  fp32 accumulation with fmaf in
+ * ascending j, one rounding, no atomics: deterministic.  1 <= r <= 128, K %% 8 == 0, W0 / out / A 16-byte aligned, finite scale. */
+int lavie_lora_merge_f16(const void* W0, const float* A, const float* B, void* out, int N, int K, int r, float scale, void* stream);
+
 /* Fused feed-forward sub-block (ABI 5): y = x + W2 (h * gelu(g)) + b2 with (h, g) = W1 LayerNorm(x) + b1 — the
  * `hidden_states = self.ff(self.norm3(hidden_states)) + hidden_states` line of BasicTransformerBlock
  * (/root/reference/base/models/attention.py:558; FeedForward / GEGLU spec /root/reference/vsr/models/diffusers_attention.py:
@@ -341,6 +347,25 @@ int lavie_unet_set_ln_fold(lavie_unet_t h, int on);
  * half of the batch only and copied.  Outputs equal the plain forward's to rounding (a half-batch launch may pick another tile).
  * Base UNet configuration only; ignored (plain forward) where it does not apply.  Default off. */
 int lavie_unet_set_cfg_shared_input(lavie_unet_t h, int on);
+/* Low-rank adapters (LoRA) on the attention projections: the to_q / to_k / to_v / to_out.0 weight of attn1, attn2 and attn_temp
+ * (attn_temporal in the VSR model) of every transformer block — the target_modules of the fork's LoraConfig
+ * (base/pipelines/fine_tuning.py:296-307).  Served merged: W = W0 + global_scale * scale * B A (lavie_lora_merge_f16), written into
+ * the packed weights and every image derived from them (fused q|k|v, LayerNorm folds, the row-resident kernels' images and a cached
+ * context's text K / V) IN PLACE, so device addresses never change and a captured forward graph stays valid.
+ * All four need a finalized handle; every argument is checked before any HIP call.
+ *   lora_set: registers (or replaces) the adapter of one target.  `name` is the state-dict key of the weight; base_f16 [N, K] is the
+ *     base weight (copied now: the handle never reads it again), A fp32 [r, K], B fp32 [N, r] (copied now), 1 <= r <= 128,
+ *     `scale` (finite) the per-target factor, peft's lora_alpha / r.  Stream-ordered on `stream`; takes effect at the next apply.
+ *   lora_clear: drops the adapter of `name`, or of every target for name = NULL; the next apply restores the base weights.
+ *     Synchronises `stream` before freeing the adapter's buffers.
+ *   lora_set_scale: the global factor (diffusers' cross_attention_kwargs={"scale": s}), default 1; 0 gives the base weights exactly.
+ *   lora_apply: merges every target of the blocks touched since the last apply, re-derives those blocks and, if a context is cached
+ *     (lavie_unet_cache_context), recomputes its K / V from the same ctx tensor.  Nothing to do = no launch. */
+int lavie_unet_lora_set(lavie_unet_t h, const char* name, const void* base_f16, const float* A, const float* B, int r, float scale,
+                        void* stream);
+int lavie_unet_lora_clear(lavie_unet_t h, const char* name, void* stream);
+int lavie_unet_lora_set_scale(lavie_unet_t h, float scale);
+int lavie_unet_lora_apply(lavie_unet_t h, void* stream);
 long long lavie_unet_weight_bytes(lavie_unet_t h);
 long long lavie_unet_workspace_bytes(lavie_unet_t h);
 /* sample [B, Cin, F, H, W] fp16 (NCFHW, as the reference passes it), timesteps [B] fp32,

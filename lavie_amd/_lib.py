@@ -43,6 +43,7 @@ SIGNATURES = {
                                          c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "lavie_pack_temporal_conv_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "lavie_pack_geglu_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_float_p, c_int, c_int, c_void_p]),
+    "lavie_lora_merge_f16": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "lavie_geglu_mlp_image_bytes": (c_ll, [c_int]),
     "lavie_geglu_mlp_bias_floats": (c_ll, [c_int]),
     "lavie_pack_geglu_mlp_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float_p, c_void_p]),
@@ -110,6 +111,10 @@ SIGNATURES = {
     "lavie_unet_prepare": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
     "lavie_unet_cache_context": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "lavie_unet_set_ln_fold": (c_int, [c_void_p, c_int]),
+    "lavie_unet_lora_set": (c_int, [c_void_p, c_char_p, c_void_p, c_float_p, c_float_p, c_int, c_float, c_void_p]),
+    "lavie_unet_lora_clear": (c_int, [c_void_p, c_char_p, c_void_p]),
+    "lavie_unet_lora_set_scale": (c_int, [c_void_p, c_float]),
+    "lavie_unet_lora_apply": (c_int, [c_void_p, c_void_p]),
     "lavie_unet_set_cfg_shared_input": (c_int, [c_void_p, c_int]),
     "lavie_unet_weight_bytes": (c_ll, [c_void_p]),
     "lavie_unet_workspace_bytes": (c_ll, [c_void_p]),

@@ -70,6 +70,10 @@ int lavie_linear_lnfold_f16(const void* A, const void* Wf, const float* bias, co
     return launch_igemm(p, false, EPI_LINEAR, S(stream));
 }
 
+int lavie_lora_merge_f16(const void* W0, const float* A, const float* B, void* out, int N, int K, int r, float scale, void* stream) {
+    return launch_lora_merge(H(W0), A, B, H(out), N, K, r, scale, S(stream));
+}
+
 long long lavie_geglu_mlp_image_bytes(int C) { return geglu_mlp_supported(C) ? (long long)geglu_mlp_image_bytes(C) : 0; }
 long long lavie_geglu_mlp_bias_floats(int C) { return geglu_mlp_supported(C) ? (long long)geglu_mlp_bias_floats(C) : 0; }
 int lavie_pack_geglu_mlp_f16(const void* w1, const void* b1_f16, const void* w2, int C, void* img, float* b1img, void* stream) {
@@ -402,6 +406,24 @@ int lavie_unet_prepare(lavie_unet_t h, int B, int F, int Hh, int W, int ctx_len)
 int lavie_unet_cache_context(lavie_unet_t h, const void* ctx, int B, int ctx_len, void* stream) {
     LAVIE_CHECK(h, "cache_context: null handle");
     return h->net.cache_context(H(ctx), B, ctx_len, S(stream));
+}
+
+int lavie_unet_lora_set(lavie_unet_t h, const char* name, const void* base_f16, const float* A, const float* B, int r, float scale,
+                        void* stream) {
+    LAVIE_CHECK(h, "lora_set: null handle");
+    return h->net.lora_set(name, H(base_f16), A, B, r, scale, S(stream));
+}
+int lavie_unet_lora_clear(lavie_unet_t h, const char* name, void* stream) {
+    LAVIE_CHECK(h, "lora_clear: null handle");
+    return h->net.lora_clear(name, S(stream));
+}
+int lavie_unet_lora_set_scale(lavie_unet_t h, float scale) {
+    LAVIE_CHECK(h, "lora_set_scale: null handle");
+    return h->net.lora_set_scale(scale);
+}
+int lavie_unet_lora_apply(lavie_unet_t h, void* stream) {
+    LAVIE_CHECK(h, "lora_apply: null handle");
+    return h->net.lora_apply(S(stream));
 }
 
 int lavie_unet_set_cfg_shared_input(lavie_unet_t h, int on) {

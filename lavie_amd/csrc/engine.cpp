@@ -100,6 +100,7 @@ UNet::~UNet() {
     drop_graph();
     if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
     if (kv_block_) (void)hipFree(kv_block_);
+    for (auto& kv : lora_) lora_free(kv.second, true);
 }
 
 int UNet::validate_config() {
@@ -403,31 +404,14 @@ int UNet::pack_transformer(TransformerW* t, hipStream_t s) {
         RUN(launch_pack_geglu_bias(bias, t->ff1.b, 8 * C, s));
     }
     RUN(pack_linear(b + ".ff.net.2", C, 4 * C, true, &t->ff2, s));
-    if (!cfg_.temporal_plain && !cfg_.vsr_blocks && temporal_block_supported(C, cfg_.heads, 16, cfg_.rotary_dim)) {
-        // fused temporal sub-block (clips of 16 frames): q / k / v / to_out weights in MFMA-fragment order
-        const half_t* wq = given(b + ".attn_" + tname + ".to_q.weight");
-        const half_t* wk = given(b + ".attn_" + tname + ".to_k.weight");
-        const half_t* wv = given(b + ".attn_" + tname + ".to_v.weight");
-        const half_t* wo = given(b + ".attn_" + tname + ".to_out.0.weight");
-        WALLOC(t->tb_img, half_t, temporal_block_image_bytes(C) / sizeof(half_t));
-        RUN(pack_temporal_block(wq, wk, wv, wo, C, t->tb_img, s));
-    }
-    if (!t->attn1_cross && !cfg_.vsr_blocks && cross_block_supported(C, cfg_.heads, 1, 16)) {
-        // fused text cross-attention sub-block: attn1.to_out / attn2.to_q / attn2.to_out in MFMA-fragment order; the K / V pieces
-        // of the image are bound per context (cache_context)
-        const half_t* wo1 = given(b + ".attn1.to_out.0.weight");
-        const half_t* wq2 = given(b + ".attn2.to_q.weight");
-        const half_t* wo2 = given(b + ".attn2.to_out.0.weight");
-        NEED(wo1, b + ".attn1.to_out.0.weight"); NEED(wq2, b + ".attn2.to_q.weight"); NEED(wo2, b + ".attn2.to_out.0.weight");
-        WALLOC(t->xb_tmpl, half_t, cross_block_image_bytes(C) / sizeof(half_t));
-        RUN(pack_cross_block(wo1, wq2, wo2, C, t->xb_tmpl, s));
-    }
-    if (!t->attn1_cross && !cfg_.vsr_blocks && proj_qkv_supported(C)) {     // fused GroupNorm -> proj_in -> norm1 -> q|k|v kernel
-        const half_t* wpin = given(p + ".proj_in.weight");
-        NEED(wpin, p + ".proj_in.weight");
+    // derived images and LayerNorm folds of the attention projections: allocated here, filled by derive_transformer() from the
+    // packed copies above, which lora_apply() rewrites in place and fills again through the same function
+    if (!cfg_.temporal_plain && !cfg_.vsr_blocks && temporal_block_supported(C, cfg_.heads, 16, cfg_.rotary_dim))
+        WALLOC(t->tb_img, half_t, temporal_block_image_bytes(C) / sizeof(half_t));     // fused temporal sub-block (clips of 16 frames)
+    if (!t->attn1_cross && !cfg_.vsr_blocks && cross_block_supported(C, cfg_.heads, 1, 16))
+        WALLOC(t->xb_tmpl, half_t, cross_block_image_bytes(C) / sizeof(half_t));       // fused text cross-attention sub-block
+    if (!t->attn1_cross && !cfg_.vsr_blocks && proj_qkv_supported(C))                  // fused GroupNorm -> proj_in -> norm1 -> q|k|v
         WALLOC(t->pq_img, half_t, proj_qkv_image_bytes(C) / sizeof(half_t));
-        RUN(pack_proj_qkv(wpin, t->wqkv1, C, t->pq_img, s));        // wqkv1: to_q | to_k | to_v rows, fused above
-    }
     if (geglu_mlp_supported(C)) {      // fused norm3 -> feed-forward -> residual kernel: weight image in MFMA-fragment order
         const half_t* w1 = given(b + ".ff.net.0.proj.weight");
         const half_t* b1 = given(b + ".ff.net.0.proj.bias");
@@ -439,16 +423,21 @@ int UNet::pack_transformer(TransformerW* t, hipStream_t s) {
     }
 
     // LayerNorm-folded projections (norm1 -> attn1 qkv, norm2 -> attn2 q, norm_temp -> attn_temp qkv, norm3 -> GEGLU)
-    auto fold = [&](const half_t* W, const NormW& ln, const half_t* bias, int N, half_t** Wf, float** sv, float** bv) -> int {
+    auto fold_alloc = [&](int N, half_t** Wf, float** sv, float** bv) -> int {
         WALLOC(*Wf, half_t, (size_t)N * C);
         WALLOC(*sv, float, N);
         WALLOC(*bv, float, N);
+        return 0;
+    };
+    auto fold = [&](const half_t* W, const NormW& ln, const half_t* bias, int N, half_t** Wf, float** sv, float** bv) -> int {
+        RUN(fold_alloc(N, Wf, sv, bv));
         return launch_ln_fold(W, ln.g, ln.b, bias, *Wf, *sv, *bv, N, C, s);
     };
-    if (t->attn1_cross) RUN(fold(t->wq1, t->ln1, nullptr, C, &t->f_q1, &t->s_q1, &t->b_q1));
-    else RUN(fold(t->wqkv1, t->ln1, nullptr, 3 * C, &t->f_qkv1, &t->s_qkv1, &t->b_qkv1));
-    RUN(fold(t->wq2, t->ln2, nullptr, C, &t->f_q2, &t->s_q2, &t->b_q2));
-    RUN(fold(t->wqkvt, t->lnt, nullptr, 3 * C, &t->f_qkvt, &t->s_qkvt, &t->b_qkvt));
+    if (t->attn1_cross) RUN(fold_alloc(C, &t->f_q1, &t->s_q1, &t->b_q1));
+    else RUN(fold_alloc(3 * C, &t->f_qkv1, &t->s_qkv1, &t->b_qkv1));
+    RUN(fold_alloc(C, &t->f_q2, &t->s_q2, &t->b_q2));
+    RUN(fold_alloc(3 * C, &t->f_qkvt, &t->s_qkvt, &t->b_qkvt));
+    RUN(derive_transformer(*t, s));
     {
         // GEGLU: fold in the checkpoint's row order, then apply the value/gate interleave to W', s and b'
         const half_t* w = given(b + ".ff.net.0.proj.weight");
@@ -462,6 +451,22 @@ int UNet::pack_transformer(TransformerW* t, hipStream_t s) {
         RUN(launch_pack_geglu_vec(tmps, t->s_ff1, 8 * C, s));
         RUN(launch_pack_geglu_vec(tmpb, t->b_ff1, 8 * C, s));
     }
+    return 0;
+}
+
+// Everything of a transformer block that is computed from its attention projections, written into the allocations of
+// pack_transformer() from the packed copies (wqkv1 / wq1 / wkv1, o1, wq2, o2, wqkvt, ot, and proj_in for the GroupNorm -> q|k|v
+// image): finalize() and lora_apply() share it, so an in-place re-derivation is the fresh build's sequence of kernels.
+int UNet::derive_transformer(const TransformerW& t, hipStream_t s) {
+    const int C = t.C;
+    const size_t CC = (size_t)C * C;
+    if (t.tb_img) RUN(pack_temporal_block(t.wqkvt, t.wqkvt + CC, t.wqkvt + 2 * CC, t.ot.w, C, t.tb_img, s));
+    if (t.xb_tmpl) RUN(pack_cross_block(t.o1.w, t.wq2, t.o2.w, C, t.xb_tmpl, s));
+    if (t.pq_img) RUN(pack_proj_qkv(t.pin.w, t.wqkv1, C, t.pq_img, s));      // wqkv1: to_q | to_k | to_v rows
+    if (t.attn1_cross) RUN(launch_ln_fold(t.wq1, t.ln1.g, t.ln1.b, nullptr, t.f_q1, t.s_q1, t.b_q1, C, C, s));
+    else RUN(launch_ln_fold(t.wqkv1, t.ln1.g, t.ln1.b, nullptr, t.f_qkv1, t.s_qkv1, t.b_qkv1, 3 * C, C, s));
+    RUN(launch_ln_fold(t.wq2, t.ln2.g, t.ln2.b, nullptr, t.f_q2, t.s_q2, t.b_q2, C, C, s));
+    RUN(launch_ln_fold(t.wqkvt, t.lnt.g, t.lnt.b, nullptr, t.f_qkvt, t.s_qkvt, t.b_qkvt, 3 * C, C, s));
     return 0;
 }
 
@@ -558,6 +563,7 @@ int UNet::finalize(hipStream_t s) {
         RUN(pack_sampler("down_blocks." + std::to_string(l) + ".downsamplers.0.conv", c.block_out_channels[l], &downs_[l], s));
     for (int i = 0; i + 1 < L; ++i)
         RUN(pack_sampler("up_blocks." + std::to_string(i) + ".upsamplers.0.conv", c.block_out_channels[L - 1 - i], &ups_[i], s, /*up=*/true));
+    lora_dirty_.assign(transformers_.size(), 0);
     finalized_ = true;
     return 0;
 }
@@ -1540,6 +1546,135 @@ int UNet::cache_context(const half_t* ctx, int B, int ctx_len, hipStream_t strea
     kv_ctx_ = ctx;
     kv_B_ = B;
     kv_len_ = ctx_len;
+    return 0;
+}
+
+// ------------------------------------------------------------------ low-rank adapters
+// `name` is `<transformer>.transformer_blocks.0.<attn1 | attn2 | attn_temp(oral)>.<to_q | to_k | to_v | to_out.0>.weight`: attn = 0 / 1 / 2,
+// proj = 0 .. 3.  Host only: the C ABI refuses a bad name before any HIP call.
+int UNet::lora_target(const char* name, int* ti, int* attn, int* proj) const {
+    LAVIE_CHECK(index_.count(name) != 0, "lora: unknown state-dict key '%s'", name);
+    const std::string tname = cfg_.vsr_blocks ? "attn_temporal" : "attn_temp";
+    const char* const attns[3] = {"attn1", "attn2", tname.c_str()};
+    static const char* const projs[4] = {"to_q", "to_k", "to_v", "to_out.0"};
+    const std::string n = name;
+    for (size_t i = 0; i < transformers_.size(); ++i) {
+        const std::string p = transformers_[i].prefix + ".transformer_blocks.0.";
+        if (n.compare(0, p.size(), p) != 0) continue;
+        for (int a = 0; a < 3; ++a)
+            for (int j = 0; j < 4; ++j)
+                if (n.compare(p.size(), std::string::npos, std::string(attns[a]) + "." + projs[j] + ".weight") == 0) {
+                    *ti = (int)i; *attn = a; *proj = j;
+                    return 0;
+                }
+    }
+    LAVIE_CHECK(false, "lora: '%s' is not a LoRA target (only the to_q / to_k / to_v / to_out.0 weights of attn1 / attn2 / %s)",
+                name, tname.c_str());
+}
+
+void UNet::lora_free(LoraEntry& e, bool base) {
+    if (e.A) (void)hipFree(e.A);
+    if (e.B) (void)hipFree(e.B);
+    e.A = e.B = nullptr;
+    if (base && e.base) { (void)hipFree(e.base); e.base = nullptr; }
+}
+
+int UNet::lora_set(const char* name, const half_t* base, const float* A, const float* B, int r, float scale, hipStream_t stream) {
+    LAVIE_CHECK(name && base && A && B, "lora_set: null argument");
+    LAVIE_CHECK(r >= 1 && r <= kLoraMaxRank, "lora_set: rank %d outside 1..%d", r, kLoraMaxRank);
+    LAVIE_CHECK(__builtin_isfinite(scale), "lora_set: scale %g is not finite", (double)scale);
+    int ti = 0, attn = 0, proj = 0;
+    RUN(lora_target(name, &ti, &attn, &proj));
+    LAVIE_CHECK(finalized_, "lora_set: call lavie_unet_finalize first");
+    auto found = lora_.find(name);
+    if (found == lora_.end()) {
+        const TransformerW& t = transformers_[ti];
+        const ParamInfo& pi = params_[index_.at(name)];
+        LoraEntry e;
+        e.ti = ti;
+        e.N = pi.shape[0];
+        e.K = pi.shape[1];
+        const size_t nk = (size_t)e.N * e.K;
+        if (proj == 3) e.dst = attn == 0 ? t.o1.w : attn == 1 ? t.o2.w : t.ot.w;
+        else if (attn == 0 && t.attn1_cross) e.dst = proj == 0 ? t.wq1 : t.wkv1 + (proj - 1) * nk;
+        else if (attn == 0) e.dst = t.wqkv1 + proj * nk;
+        else if (attn == 1) e.dst = proj == 0 ? t.wq2 : t.wkv2 + (proj - 1) * nk;
+        else e.dst = t.wqkvt + proj * nk;
+        LAVIE_HIP(hipMalloc((void**)&e.base, nk * sizeof(half_t)));
+        found = lora_.emplace(name, e).first;
+    }
+    LoraEntry& e = found->second;
+    if (e.r != r) {
+        if (e.A || e.B) {       // an earlier apply may still read them
+            LAVIE_HIP(hipStreamSynchronize(stream));
+            lora_free(e, false);
+        }
+        e.r = 0;
+        LAVIE_HIP(hipMalloc((void**)&e.A, (size_t)r * e.K * sizeof(float)));
+        LAVIE_HIP(hipMalloc((void**)&e.B, (size_t)e.N * r * sizeof(float)));
+    }
+    LAVIE_HIP(hipMemcpyAsync(e.base, base, (size_t)e.N * e.K * sizeof(half_t), hipMemcpyDeviceToDevice, stream));
+    LAVIE_HIP(hipMemcpyAsync(e.A, A, (size_t)r * e.K * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    LAVIE_HIP(hipMemcpyAsync(e.B, B, (size_t)e.N * r * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    e.r = r;
+    e.scale = scale;
+    lora_dirty_[ti] = 1;
+    return 0;
+}
+
+int UNet::lora_clear(const char* name, hipStream_t stream) {
+    int ti = 0, attn = 0, proj = 0;
+    if (name) RUN(lora_target(name, &ti, &attn, &proj));
+    LAVIE_CHECK(finalized_, "lora_clear: call lavie_unet_finalize first");
+    bool synced = false;
+    for (auto& kv : lora_) {
+        LoraEntry& e = kv.second;
+        if ((name && kv.first != name) || e.r == 0) continue;
+        if (!synced) { LAVIE_HIP(hipStreamSynchronize(stream)); synced = true; }
+        lora_free(e, false);
+        e.r = 0;                // the base copy stays until the next apply has written it back
+        lora_dirty_[e.ti] = 1;
+    }
+    return 0;
+}
+
+int UNet::lora_set_scale(float scale) {
+    LAVIE_CHECK(__builtin_isfinite(scale), "lora_set_scale: scale %g is not finite", (double)scale);
+    LAVIE_CHECK(finalized_, "lora_set_scale: call lavie_unet_finalize first");
+    if (scale == lora_scale_) return 0;
+    lora_scale_ = scale;
+    for (const auto& kv : lora_) lora_dirty_[kv.second.ti] = 1;
+    return 0;
+}
+
+int UNet::lora_apply(hipStream_t stream) {
+    LAVIE_CHECK(finalized_, "lora_apply: call lavie_unet_finalize first");
+    bool any = false;
+    for (char d : lora_dirty_) any = any || d;
+    if (!any) return 0;
+    bool drop = false;
+    for (auto& kv : lora_) {
+        const LoraEntry& e = kv.second;
+        if (!lora_dirty_[e.ti]) continue;
+        const float eff = lora_scale_ * e.scale;
+        if (e.r > 0 && eff != 0.f) RUN(launch_lora_merge(e.base, e.A, e.B, e.dst, e.N, e.K, e.r, eff, stream));
+        else LAVIE_HIP(hipMemcpyAsync(e.dst, e.base, (size_t)e.N * e.K * sizeof(half_t), hipMemcpyDeviceToDevice, stream));
+        drop = drop || e.r == 0;
+    }
+    for (size_t i = 0; i < transformers_.size(); ++i)
+        if (lora_dirty_[i]) RUN(derive_transformer(transformers_[i], stream));
+    if (drop) {                 // cleared entries: their base is back in place
+        LAVIE_HIP(hipStreamSynchronize(stream));
+        for (auto it = lora_.begin(); it != lora_.end();) {
+            if (it->second.r == 0) { lora_free(it->second, true); it = lora_.erase(it); }
+            else ++it;
+        }
+    }
+    lora_dirty_.assign(transformers_.size(), 0);
+    ++graph_gen_;
+    // a cached context holds text K / V (and the fused kernel's per-video images) computed from the old attn2 weights: recompute
+    // them into the same buffers from the tensor the cache_context contract keeps alive and unmodified
+    if (kv_ctx_) RUN(cache_context(kv_ctx_, kv_B_, kv_len_, stream));
     return 0;
 }
 

@@ -1,5 +1,6 @@
 // Host-side denoiser: owns packed weights + workspace and enqueues one UNet forward on a stream.
 #pragma once
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -103,6 +104,19 @@ struct TemporalModuleW {
 
 struct FwdCtx;   // per-call state (engine.cpp)
 
+// One registered low-rank adapter target (lavie_unet_lora_*): the projection's rows inside the packed weights and what they are
+// rebuilt from.  Every buffer is the engine's own: the caller's base tensor is copied at registration.
+struct LoraEntry {
+    int ti = -1;                                    // transformer block
+    half_t* dst = nullptr;                          // the projection's [N][K] rows inside wqkv1 / wq1 / wkv1 / o1 / wq2 / wkv2 / o2 / wqkvt / ot
+    int N = 0, K = 0;
+    half_t* base = nullptr;                         // copy of the base weight
+    float* A = nullptr;                             // [r][K] fp32
+    float* B = nullptr;                             // [N][r] fp32
+    int r = 0;                                      // 0: cleared, the next apply writes the base back and drops the entry
+    float scale = 1.f;                              // per-target scale (alpha / r); the effective scale is this * the global one
+};
+
 class UNet {
 public:
     explicit UNet(const lavie_unet_config& cfg);
@@ -131,6 +145,13 @@ public:
     long long workspace_bytes() const { return (long long)ws_.total_bytes(); }
     void set_ln_fold(bool on) { ln_fold_ = on; ++graph_gen_; }
     void set_cfg_shared_input(bool on) { cfg_shared_input_ = on; ++graph_gen_; }
+    // Low-rank adapters on the attention projections (to_q / to_k / to_v / to_out.0 of attn1 / attn2 / attn_temp).  set / clear /
+    // set_scale only record (the set copies the caller's tensors on `stream`); apply merges every target of the blocks touched since
+    // the last apply and re-derives those blocks' images in place: device addresses never change, captured graphs stay valid.
+    int lora_set(const char* name, const half_t* base, const float* A, const float* B, int r, float scale, hipStream_t stream);
+    int lora_clear(const char* name, hipStream_t stream);
+    int lora_set_scale(float scale);
+    int lora_apply(hipStream_t stream);
 
 private:
     void build_param_list();
@@ -139,6 +160,9 @@ private:
     int pack_linear(const std::string& prefix, int N, int K, bool bias, LinW* out, hipStream_t s);
     int pack_resnet(ResnetW* r, hipStream_t s);
     int pack_transformer(TransformerW* t, hipStream_t s);
+    int derive_transformer(const TransformerW& t, hipStream_t s);
+    int lora_target(const char* name, int* ti, int* attn, int* proj) const;
+    void lora_free(LoraEntry& e, bool base);
     int pack_temporal_res(const std::string& prefix, int C, int taps1, TemporalResW* out, hipStream_t s);
     int run_temporal_res(FwdCtx& c, const TemporalResW& r, const half_t* x, half_t* y, int C, int D, const float* bias2, int ldb2,
                          const GnColStat* x_cs = nullptr, float* y_csbuf = nullptr, GnColStat* y_cs = nullptr);
@@ -216,6 +240,10 @@ private:
     void* kv_block_ = nullptr;                      // ONE hipMalloc'd block behind every K/V cache buffer: freed and reallocated on growth
     const half_t* kv_ctx_ = nullptr;
     int kv_B_ = 0, kv_len_ = 0;
+    // low-rank adapter registry (lora_*), ordered by name so apply enqueues the same sequence every time
+    std::map<std::string, LoraEntry> lora_;
+    float lora_scale_ = 1.f;                        // global adapter scale
+    std::vector<char> lora_dirty_;                  // per transformer: touched since the last apply
     // spatial size of the running call (set by prepare()/forward() before run())
     int prep_H_ = 0, prep_W_ = 0;
 };

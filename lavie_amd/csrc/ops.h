@@ -146,6 +146,12 @@ int launch_cross_block(const half_t* att, const half_t* x, half_t* y, int M, int
                        const float* bo1, const float* gamma, const float* beta, const float* bo2, int L, float scale, float eps,
                        hipStream_t stream);
 
+// ---- lora.hip: out[n, k] = fp16_rne(W0[n, k] + scale * sum_{j < r} B[n, j] A[j, k]), W0 / out fp16 [N, K], A fp32 [r, K], B fp32 [N, r];
+// fp32 accumulation in ascending j, no atomics (deterministic); K % 8 == 0, W0 / out / A 16-byte aligned; out may alias W0
+constexpr int kLoraMaxRank = 128;
+int launch_lora_merge(const half_t* W0, const float* A, const float* B, half_t* out, int N, int K, int r, float scale,
+                      hipStream_t stream);
+
 // host-only helper (no GPU): T5-style bucket of (query i, key j), attention.py:681-699
 void relpos_bucket_table(int F, int num_buckets, int max_distance, int* out);
 

@@ -441,3 +441,18 @@ def unet_transformer(net, prefix: str, x, ctx, b: int, f: int, h: int, w: int):
     _lib.check(_lib.load().lavie_unet_transformer_forward(handle, prefix.encode(), _p(x), _p(ctx), b, f, h, w,
                                                           ctx.shape[1], _stream()), "lavie_unet_transformer_forward")
     return x
+
+
+def lora_merge(w0: torch.Tensor, a: torch.Tensor, b: torch.Tensor, scale: float = 1.0, out: Optional[torch.Tensor] = None):
+    """fp16_rne(w0[N,K] + scale * b[N,r] @ a[r,K]) with a / b fp32 (lavie_lora_merge_f16: fp32 fmaf in ascending j, deterministic)."""
+    _chk16(w0, out)
+    _chk32(a, b)
+    N, K = w0.shape
+    r = a.shape[0]
+    if a.shape != (r, K) or b.shape != (N, r):
+        raise ValueError(f"lora_merge: w0 {tuple(w0.shape)}, a {tuple(a.shape)}, b {tuple(b.shape)} do not fit")
+    if out is None:
+        out = torch.empty_like(w0)
+    lib = _lib.load()
+    _lib.check(lib.lavie_lora_merge_f16(_p(w0), _p(a), _p(b), _p(out), N, K, r, float(scale), _stream()), "lavie_lora_merge_f16")
+    return out

@@ -51,6 +51,14 @@ class VideoGenPipeline:
     # offers attention slicing and the pipeline VAE slicing / tiling (pipeline_videogen.py:174-204).  They trade speed for memory in
     # the stock attention (`_sliced_attention`, xformers) and the stock VAE; here attention is always the fused flash-style HIP
     # kernel (scores are never materialised) and 288 GB of HBM make the VAE knobs moot, so they are accepted and change nothing.
+    def load_lora_weights(self, sd_or_path, scale: float = 1.0, alpha=None):
+        """The fork's saved adapter (save_lora_weights: `unet.`-prefixed peft keys, fine_tuning.py:689-698) onto the UNet
+        (UNet3DConditionModel.load_lora)."""
+        self.unet.load_lora(sd_or_path, scale=scale, alpha=alpha)
+
+    def unload_lora_weights(self):
+        self.unet.unload_lora()
+
     def enable_xformers_memory_efficient_attention(self, attention_op=None):
         """No-op: attn1 / attn2 always run the fused online-softmax kernel (attention.hip); nothing to switch on."""
         return None
@@ -330,7 +338,17 @@ class VideoGenPipeline:
                                   negative_prompt_embeds).to(torch.float16).contiguous()
         latents = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.config.in_channels, video_length,
                                        height, width, torch.float32, device, generator, latents)
-        latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta)
+        lora_scale = (cross_attention_kwargs or {}).get("scale")
+        if lora_scale is None:
+            latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta)
+        else:                              # diffusers' LoRA strength for this call only, restored also on an exception
+            prev = self.unet.lora_scale
+            self.unet.set_lora_scale(lora_scale)
+            try:
+                latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps,
+                                       eta)
+            finally:
+                self.unet.set_lora_scale(prev)
         if output_type == "latent":
             video = latents
         else:

@@ -6,15 +6,17 @@ surface (unet.py:366-375, 509-512) — but the module holds no compute of its ow
 fp16 parameters and inputs to the gfx950 engine in liblavie_hip.so.  There is no eager/CPU path."""
 import ctypes
 import json
+import math
 import os
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Optional, Tuple, Union
 
+import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, spec
+from . import _lib, lora as _lora, spec
 from .config import UNetConfig
 from .weights import rotary_freqs
 
@@ -43,6 +45,7 @@ class UNet3DConditionModel(nn.Module):
     _block_variant = dict(sparse_causal_attn1=False, temporal_plain=False, ff_before_temporal=False)
     _allow_first_frame = False
     _allow_vsr_options = False            # only_cross_attention tuples / use_linear_projection (lavie_amd.vsr.unet)
+    _lora_supported = True                # load_lora(); lavie_amd.vsr.unet refuses it
 
     def __init__(
         self,
@@ -135,6 +138,10 @@ class UNet3DConditionModel(nn.Module):
         self._cached_ctx = None
         self._graph = False
         self._graph_io = {}
+        # the loaded adapter (load_lora): {target weight name: (A fp32 [r, K], B fp32 [N, r], per-target scale)} on the host, and
+        # the global scale; every engine build registers it again, only unload_lora() / fuse_lora() remove it
+        self._lora = {}
+        self._lora_scale = 1.0
 
     def _vsr_config(self, only_cross_attention, use_linear_projection, levels: int) -> dict:
         """UNetConfig fields of the VSR block variant; the base and interpolation models have none."""
@@ -233,6 +240,8 @@ class UNet3DConditionModel(nn.Module):
                     _lib.check(lib.lavie_unet_set_param(handle, name.encode(), ctypes.c_void_p(t.data_ptr()), t.numel()),
                                f"lavie_unet_set_param({name})")
                 _lib.check(lib.lavie_unet_finalize(handle, stream), "lavie_unet_finalize")
+                if self._lora:
+                    self._lora_register(handle, stream)
                 torch.cuda.current_stream().synchronize()
             except Exception:
                 lib.lavie_unet_destroy(handle)
@@ -249,6 +258,105 @@ class UNet3DConditionModel(nn.Module):
         """Re-packs the weights after parameters were modified in place."""
         self._drop_engine()
         return self._ensure_engine()
+
+    # ------------------------------------------------------------------ LoRA adapters (served merged: lavie_unet_lora_*)
+    def _lora_register(self, handle, stream) -> None:
+        """Registers self._lora on `handle` (base = the module's own weights) and applies it; the caller synchronises."""
+        lib = _lib.load()
+        params = dict(self.named_parameters())
+        keep = []             # device copies stay alive until the engine's copies of them have run (the caller's sync)
+        for name, (a, b, s) in self._lora.items():
+            w = params[name].data.contiguous()
+            ad = a.to(self.device, torch.float32).contiguous()
+            bd = b.to(self.device, torch.float32).contiguous()
+            keep += [w, ad, bd]
+            _lib.check(lib.lavie_unet_lora_set(handle, name.encode(), ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(ad.data_ptr()),
+                                               ctypes.c_void_p(bd.data_ptr()), a.shape[0], float(s), stream),
+                       f"lavie_unet_lora_set({name})")
+        _lib.check(lib.lavie_unet_lora_set_scale(handle, float(self._lora_scale)), "lavie_unet_lora_set_scale")
+        _lib.check(lib.lavie_unet_lora_apply(handle, stream), "lavie_unet_lora_apply")
+        torch.cuda.current_stream().synchronize()
+
+    def load_lora(self, sd_or_path, scale: float = 1.0, alpha: Optional[float] = None) -> None:
+        """Loads a LoRA adapter (state dict, `.safetensors` / `.bin` / `.pt` file, or a directory holding
+        `pytorch_lora_weights.safetensors`) onto the to_q / to_k / to_v / to_out.0 projections, replacing any loaded one.
+        Per-target factor alpha / r (peft's scaling; 1.0 without alpha, the fork's lora_alpha = r), `alpha` overrides; `scale` is
+        the global strength (set_lora_scale).  The module parameters stay the base weights (fuse_lora() writes the merge in)."""
+        if not self._lora_supported:
+            raise NotImplementedError(f"{type(self).__name__}: LoRA adapters are not supported on this model")
+        cfg_alpha = None
+        if isinstance(sd_or_path, (str, os.PathLike)):
+            sd_or_path, cfg_alpha = _lora.load_lora_file(os.fspath(sd_or_path))
+        shapes = {n: tuple(p.shape) for n, p in self.named_parameters()}
+        tensors = _lora.normalize_lora_state_dict(sd_or_path, shapes)
+        if not tensors:
+            raise ValueError("load_lora: the state dict holds no LoRA matrices")
+        scales = _lora.target_scales(tensors, alpha if alpha is not None else cfg_alpha)
+        scale = float(scale)
+        if not math.isfinite(scale):
+            raise ValueError(f"load_lora: scale {scale} is not finite")
+        new = {n: (a, b, scales[n]) for n, (a, b, _) in tensors.items()}
+        handle = self.__dict__.get("_engine")
+        self.__dict__["_lora"] = new
+        self.__dict__["_lora_scale"] = scale
+        if handle:
+            lib = _lib.load()
+            with torch.cuda.device(self.device):
+                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                _lib.check(lib.lavie_unet_lora_clear(handle, None, stream), "lavie_unet_lora_clear")
+                self._lora_register(handle, stream)
+
+    def set_lora_scale(self, scale: float) -> None:
+        """Global adapter strength (diffusers' cross_attention_kwargs={"scale": s}); 0 gives the base model's outputs exactly."""
+        scale = float(scale)
+        if not math.isfinite(scale):
+            raise ValueError(f"set_lora_scale: scale {scale} is not finite")
+        self.__dict__["_lora_scale"] = scale
+        handle = self.__dict__.get("_engine")
+        if handle:
+            lib = _lib.load()
+            with torch.cuda.device(self.device):
+                _lib.check(lib.lavie_unet_lora_set_scale(handle, scale), "lavie_unet_lora_set_scale")
+                _lib.check(lib.lavie_unet_lora_apply(handle, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                           "lavie_unet_lora_apply")
+
+    @property
+    def lora_scale(self) -> float:
+        return self._lora_scale
+
+    def unload_lora(self) -> None:
+        """Removes the adapter: the engine goes back to the base weights (bit-identical to a model that never had one)."""
+        self.__dict__["_lora"] = {}
+        self.__dict__["_lora_scale"] = 1.0
+        handle = self.__dict__.get("_engine")
+        if handle:
+            lib = _lib.load()
+            with torch.cuda.device(self.device):
+                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                _lib.check(lib.lavie_unet_lora_clear(handle, None, stream), "lavie_unet_lora_clear")
+                _lib.check(lib.lavie_unet_lora_set_scale(handle, 1.0), "lavie_unet_lora_set_scale")
+                _lib.check(lib.lavie_unet_lora_apply(handle, stream), "lavie_unet_lora_apply")
+
+    @torch.no_grad()
+    def fuse_lora(self) -> None:
+        """Writes the merged weights the engine serves (lavie_lora_merge_f16, the same kernel and inputs) into the module
+        parameters and removes the adapter; the engine is rebuilt from them on next use."""
+        if not self._lora:
+            return
+        if self.device.type != "cuda" or self.dtype != torch.float16:
+            raise RuntimeError("fuse_lora: the model must be on a HIP device in fp16")
+        from . import ops
+        params = dict(self.named_parameters())
+        with torch.cuda.device(self.device):
+            for name, (a, b, s) in self._lora.items():
+                p = params[name]
+                eff = float(np.float32(self._lora_scale) * np.float32(s))        # the engine's fp32 product
+                merged = ops.lora_merge(p.data.contiguous(), a.to(self.device, torch.float32).contiguous(),
+                                        b.to(self.device, torch.float32).contiguous(), eff)
+                p.data.copy_(merged)
+        self.__dict__["_lora"] = {}
+        self.__dict__["_lora_scale"] = 1.0
+        self._drop_engine()
 
     def engine_handle(self):
         """The `lavie_unet_t` behind this module (built on first use)."""

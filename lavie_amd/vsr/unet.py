@@ -23,6 +23,7 @@ from ..unet import UNet3DConditionOutput
 
 class UNet3DVSRModel(_BaseUNet):
     _allow_vsr_options = True
+    _lora_supported = False               # load_lora() raises NotImplementedError: no LoRA-fine-tuned VSR model in the fork
 
     def __init__(self, sample_size: Optional[int] = None, in_channels: int = 7, out_channels: int = 4,
                  down_block_types: Tuple[str, ...] = ("DownBlock3D", "CrossAttnDownBlock3D", "CrossAttnDownBlock3D", "CrossAttnDownBlock3D"),
