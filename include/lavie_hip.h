@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LAVIE_ABI_VERSION 7
+#define LAVIE_ABI_VERSION 8
 #define LAVIE_MAX_LEVELS 8
 
 const char* lavie_last_error(void);
@@ -234,43 +234,26 @@ int lavie_latents_to_scaled_model_input1(const float* x, void* model_in, long lo
 #define LAVIE_PROFILE_CLASSES 11
 /* Which optional engine paths lavie_unet_forward takes (A/B timing, parity cross-checks).  Bits: 0 = fused feed-forward kernel
  * (lavie_geglu_mlp_f16), 1 = fused temporal-attention sub-block (lavie_temporal_block_f16), 2 = fused text cross-attention
- * sub-block (lavie_cross_block_f16), 3 = conv_shortcut as its own GEMM in front of a halo-patch conv2 (measured slower: OFF by
- * default), 4 = parity form of the Upsample3D convs (lavie_upsample_conv3x3_f16), 5 = GroupNorm statistics taken from the
- * producing kernel's epilogue instead of a statistics pass (round 4).  Bit 6 (debug, off): every GroupNorm that takes producer statistics ALSO runs
- * the statistics pass and compares the two on the host.  Bit 7: a LayerNorm-folded GEMM on a kernel with the shared epilogue folds its producer's row-statistics partials itself (no
- * rowstat_finalize launch; the persistent kernel's consumers still finalize, once) — measured SLOWER (every N tile of the consumer
- * repeats the fold: linear class 7.23 -> 7.89 ms per forward, profiles/r04_ab_rowstat_fold_in_consumer.txt): off.  Bit 8: the fused block head
- * (lavie_proj_qkv_f16: GroupNorm -> proj_in -> norm1 -> q|k|v in one kernel).  Default 0x137 (bits 0, 1, 2, 4, 5, 8); 0 = the one-GEMM-per-launch path of round 2. */
+ * sub-block (lavie_cross_block_f16), 4 = parity form of the Upsample3D convs (lavie_upsample_conv3x3_f16), 5 = GroupNorm statistics
+ * taken from the producing kernel's epilogue instead of a statistics pass (round 4).  Bit 6 (debug, off): every GroupNorm that takes
+ * producer statistics ALSO runs the statistics pass and compares the two on the host.  Bit 8: the fused block head
+ * (lavie_proj_qkv_f16: GroupNorm -> proj_in -> norm1 -> q|k|v in one kernel).  Default 0x137 (bits 0, 1, 2, 4, 5, 8); 0 = the
+ * one-GEMM-per-launch path of round 2.  Any other bit (3, 7, 9 and up) is an error and leaves the mask unchanged. */
 int lavie_debug_fused_mask(int mask);
 /* Test hook: GroupNorm launches so far (process-wide) that took their statistics from the producers' epilogues.  Bit 6 of the mask
  * above makes every such launch ALSO run the statistics pass and compare the two on the host (synchronises; an error names the
  * first (batch, group) that differs). */
 long long lavie_debug_gn_producer_count(void);
-int lavie_debug_temporal_block_dump(float* buf);   /* development aid: device buffer of 100 * 64 floats, or NULL */
-int lavie_debug_rowfuse_stamps(unsigned long long* buf);   /* stamp build (variant 7): device buffer of 64 u64, or NULL */
-int lavie_debug_rowfuse_variant(int v);   /* tuning: LDS read-ahead depth of the fused kernels (0 = default) */
-/* Test/tuning knob for the implicit-GEMM kernel choice.  Low nibble: 0 automatic, 1 128-row kernel with the widest tile,
+/* Test/tuning knob for the implicit-GEMM kernel choice: 0 automatic, 1 128-row kernel with the widest tile,
  * 3 160x320 ping-pong kernel wherever N % 320 == 0, 4 automatic without the ping-pong
  * kernel, 5 halo-patch conv kernel wherever the conv is eligible, 6 automatic without the halo-patch kernel,
  * 7 persistent ping-pong kernel for every eligible plain GEMM, 8 automatic without it, 9 automatic without the GEGLU GEMMs on it.
- * High nibble: diagnostic ablation build of the forced kernel (results wrong), except 0xC: the halo-patch kernel's ping-pong K loop. */
+ * Any other value is an error and leaves the mode unchanged. */
 int lavie_debug_force_tile(int mode);
 /* Test/tuning knob: force the split-K factor of the implicit GEMM (0 = automatic). */
 int lavie_debug_force_splits(int s);
-/* Diagnostic: op-level conv3x3 + pack use the K order (tap, slab) instead of (slab, tap). */
-int lavie_debug_conv_tap_major(int on);
-/* Tuning knob: 16-row query tiles per wave in the attention kernel for head dims <= 64 (0 = automatic).  A/B switches: 0x50 = the
- * register-staged kernels instead of the LDS-DMA ones, 0x40 = row sums on the VALU, 0x60 = the LDS-DMA kernels with the round-3
- * softmax (scale and running maximum applied by v_fma) instead of the round-4 one (both on the matrix pipe). */
-int lavie_debug_attention_qt(int qt);
 /* Tuning knob: LDS bytes one temporal-attention workgroup may stage (smaller = more workgroups per CU). */
 int lavie_debug_temporal_budget(int bytes);
-/* Diagnostic: per-wave phase-segment cycle sums [8 waves][16] of the last halo-patch conv launched in stamp mode
- * (lavie_debug_force_tile(0x75)); layout in igemm_patch.hip. */
-int lavie_debug_patch_stamps(unsigned long long* out128);
-/* Diagnostic: per-wave segment cycle sums [8 waves][32] of the last persistent ping-pong GEMM launched in stamp mode
- * (lavie_debug_force_tile(0x37)); layout in igemm_ppx.hip. */
-int lavie_debug_ppx_stamps(unsigned long long* out256);
 int lavie_profile_begin(unsigned mask, int max_events);
 int lavie_profile_end(void* stream, long long* launches_host, double* ms_host, double* flops_host, double* bytes_host);
 

@@ -7,7 +7,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LAVIE_HIP_LIB") or os.path.join(_HERE, "liblavie_hip.so")   # env override: A/B builds
-ABI_VERSION = 7
+ABI_VERSION = 8
 FUSED_DEFAULT = 0x137    # lavie_debug_fused_mask: bits 0, 1, 2, 4, 5, 8 (include/lavie_hip.h)
 MAX_LEVELS = 8
 
@@ -90,14 +90,7 @@ SIGNATURES = {
     "lavie_debug_force_splits": (c_int, [c_int]),
     "lavie_debug_fused_mask": (c_int, [c_int]),
     "lavie_debug_gn_producer_count": (c_ll, []),
-    "lavie_debug_temporal_block_dump": (c_int, [c_void_p]),
-    "lavie_debug_rowfuse_variant": (c_int, [c_int]),
-    "lavie_debug_rowfuse_stamps": (c_int, [c_void_p]),
-    "lavie_debug_conv_tap_major": (c_int, [c_int]),
-    "lavie_debug_attention_qt": (c_int, [c_int]),
     "lavie_debug_temporal_budget": (c_int, [c_int]),
-    "lavie_debug_patch_stamps": (c_int, [c_void_p]),
-    "lavie_debug_ppx_stamps": (c_int, [c_void_p]),
     "lavie_profile_begin": (c_int, [C.c_uint, c_int]),
     "lavie_profile_end": (c_int, [c_void_p, C.POINTER(c_ll), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                    C.POINTER(C.c_double)]),

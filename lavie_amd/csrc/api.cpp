@@ -17,7 +17,6 @@ static inline hipStream_t S(void* s) { return (hipStream_t)s; }
 
 // Operator-level entry points have no workspace argument: the split-K slab comes from a grow-only scratch
 // buffer owned by the library (allocated outside any stream capture; the engine uses its own workspace).
-static int g_tap_major = 0;   // diagnostic K-order switch for the op-level conv (pack + launch)
 static float* g_slab = nullptr;
 static size_t g_slab_bytes = 0;
 static int op_slab(IgemmParams& p, int epilogue, bool gather = false) {
@@ -153,7 +152,7 @@ int lavie_conv3x3_f16(const void* x1, int C1, const void* x2, int C2, const void
         sg.src = sc[i]; sg.C = scC[i]; sg.c0 = 0; sg.nchunks = scC[i] / IGEMM_BK; sg.ntaps = 1;
         nk += sg.nchunks;
     }
-    p.nseg = ns; p.nk = nk; p.ldw = nk * IGEMM_BK; p.tap_major = g_tap_major;
+    p.nseg = ns; p.nk = nk; p.ldw = nk * IGEMM_BK;
     if (int rc = op_slab(p, EPI_LINEAR, true)) return rc;
     return launch_igemm(p, true, EPI_LINEAR, S(stream));
 }
@@ -186,7 +185,7 @@ int lavie_upsample_conv3x3_f16(const void* x, const void* wpar, const float* bia
 
 int lavie_pack_conv3x3_f16(const void* w, void* out, int Cout, int Cin, int ld_out, int col0, void* stream) {
     LAVIE_CHECK(w && out && ld_out >= col0 + 9 * Cin, "pack_conv3x3: bad arguments");
-    return launch_pack_conv3x3(H(w), H(out), Cout, Cin, ld_out, col0, g_tap_major == 0, S(stream));
+    return launch_pack_conv3x3(H(w), H(out), Cout, Cin, ld_out, col0, true, S(stream));
 }
 
 int lavie_temporal_conv_f16(const void* x, int C, const void* Wp, const float* bias, const float* bias2, int ldb2,
@@ -207,7 +206,7 @@ int lavie_temporal_conv_f16(const void* x, int C, const void* Wp, const float* b
     p.M = B * F * D; p.N = Cout; p.zero = H(zero_page);
     IgemmSeg& sg = p.seg[0];
     sg.src = H(x); sg.C = C; sg.c0 = 0; sg.nchunks = C / IGEMM_BK; sg.ntaps = taps;
-    p.nseg = 1; p.nk = taps * sg.nchunks; p.ldw = p.nk * IGEMM_BK; p.tap_major = 0;
+    p.nseg = 1; p.nk = taps * sg.nchunks; p.ldw = p.nk * IGEMM_BK;
     if (int rc = op_slab(p, EPI_LINEAR, true)) return rc;
     return launch_igemm(p, true, EPI_LINEAR, S(stream));
 }
@@ -328,25 +327,20 @@ int lavie_latents_to_scaled_model_input(const float* x, void* model_in2, long lo
 
 // Every switch below changes which kernels a forward enqueues: each bumps the process-wide debug epoch, which is part of
 // the captured graph's key (engine.h GraphKey::debug_epoch), so a replay never runs a selection made under other switches.
-int lavie_debug_force_tile(int mode) { bump_debug_epoch(); igemm_force_tile(mode); return 0; }
+int lavie_debug_force_tile(int mode) {
+    if (int rc = igemm_force_tile(mode)) return rc;     // a rejected mode changes nothing
+    bump_debug_epoch();
+    return 0;
+}
 int lavie_debug_force_splits(int s) { bump_debug_epoch(); igemm_force_splits(s); return 0; }
-int lavie_debug_conv_tap_major(int on) { bump_debug_epoch(); g_tap_major = on; return 0; }
-int lavie_debug_attention_qt(int qt) { bump_debug_epoch(); attention_force_qt(qt); return 0; }
-int lavie_debug_rowfuse_stamps(unsigned long long* buf) { rowfuse_set_stamp_buffer(buf); return 0; }
-int lavie_debug_rowfuse_variant(int v) { bump_debug_epoch(); rowfuse_set_variant(v); return 0; }
-int lavie_debug_temporal_block_dump(float* buf) { temporal_block_set_debug(buf); return 0; }
-int lavie_debug_fused_mask(int mask) { bump_debug_epoch(); set_fused_mask(mask); return 0; }
+int lavie_debug_fused_mask(int mask) {
+    LAVIE_CHECK((mask & ~0x177) == 0, "fused_mask: 0x%x sets a bit other than 0, 1, 2, 4, 5, 6, 8", mask);
+    bump_debug_epoch();
+    set_fused_mask(mask);
+    return 0;
+}
 int lavie_debug_temporal_budget(int bytes) { bump_debug_epoch(); temporal_set_budget(bytes); return 0; }
-int lavie_debug_ppx_stamps(unsigned long long* out256) {
-    LAVIE_CHECK(out256, "ppx_stamps: null output");
-    return igemm_ppx_read_stamps(out256);
-}
 long long lavie_debug_gn_producer_count(void) { return (long long)lavie::gn_producer_count(); }
-
-int lavie_debug_patch_stamps(unsigned long long* out128) {
-    LAVIE_CHECK(out128, "patch_stamps: null output");
-    return igemm_patch_read_stamps(out128);
-}
 
 int lavie_profile_begin(unsigned mask, int max_events) { return profile_begin(mask, max_events); }
 

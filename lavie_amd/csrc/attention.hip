@@ -37,17 +37,16 @@ struct AttTile {
     static constexpr int MAXPIECE = (ATT_KEYS * (DHP / 8) + 255) / 256;
 };
 
-// ABL (diagnostic, wrong results): 1 = no softmax VALU (P := S), 2 = no MFMA, 3 = staging + barriers only
 // LSUM: the softmax row sums come out of the P V product itself: column `dh` of every V row in LDS (padding that the
 // staging never writes; it lies inside the last 16-wide output tile whenever dh % 16 != 0) holds 1.0, so output
 // dimension dh accumulates sum_k p[q, k] on the matrix pipe and is rescaled together with O — 16 v_add_f32 per query
 // tile and key tile less on the VALU, which paces this kernel at head dim 40.
 // SC: sparse-causal key/value addressing (AttnParams::sc_frames): key j of batch entry (b, f) is token j % D of frame
 // (b, 0) for j < D and of frame (b, max(f-1, 0)) for j >= D — a per-piece row lookup in the staging loads, nothing else.
-// NDT: number of 16-wide output-dimension tiles that exist ((dh + 15) / 16) as a compile-time constant for the model's head
-// dims (40 -> 3, 80 -> 5, 160 -> 10); 0 = decided at run time.  The run-time test put a branch and an exposed
+// NDT: number of 16-wide output-dimension tiles that exist ((dh + 15) / 16) as a compile-time constant (head dim 64 -> 4);
+// 0 = decided at run time.  The run-time test put a branch and an exposed
 // ds_read -> wait -> MFMA chain around every output tile of the P V product.
-template <int DHP, int QT, int ABL = 0, bool LSUM = false, bool SC = false, int NDT = 0>
+template <int DHP, int QT, bool LSUM = false, bool SC = false, int NDT = 0>
 __global__ __launch_bounds__(256, (DHP == 64 && QT == 2) ? 3 : 1) void attention_kernel(const AttnParams p) {
     using T = AttTile<DHP>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -185,10 +184,7 @@ __global__ __launch_bounds__(256, (DHP == 64 && QT == 2) ? 3 : 1) void attention
             for (int kt = 0; kt < 4; ++kt) {
                 const half8_t kf = *reinterpret_cast<const half8_t*>(cK + (kt * 16 + li) * T::STRIDE + (ks * 4 + g) * 16);
 #pragma unroll
-                for (int qt = 0; qt < QT; ++qt) {
-                    if constexpr (ABL >= 2) asm volatile("" ::"v"(kf));
-                    else s[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[qt][ks], s[kt][qt], 0, 0, 0);
-                }
+                for (int qt = 0; qt < QT; ++qt) s[kt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[qt][ks], s[kt][qt], 0, 0, 0);
             }
         }
 
@@ -205,14 +201,6 @@ __global__ __launch_bounds__(256, (DHP == 64 && QT == 2) ? 3 : 1) void attention
         }
 
         half8_t pb[2][QT];
-        if constexpr (ABL == 1 || ABL == 3) {
-#pragma unroll
-            for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) pb[kt >> 1][qt][(kt & 1) * 4 + r] = (half_t)s[kt][qt][r];
-        } else {
         // ---- online softmax per query column (lane li of each 16-lane group), deferred rescale (T13):
         // the running max only moves when some row grew by more than 2^RESCALE_THR, so p <= 2^THR (fine in fp16,
         // sums and O stay in fp32) and the O-wide rescale runs on a handful of tiles instead of every tile.
@@ -259,8 +247,6 @@ __global__ __launch_bounds__(256, (DHP == 64 && QT == 2) ? 3 : 1) void attention
             }
             if constexpr (!LSUM) l_run[qt] += psum;           // per-lane partial; reduced over g at the end
         }
-
-        }
         // ---- O^T[dim, q] += V^T P^T  (V^T fragments by hardware-transposed LDS reads)
 #pragma unroll
         for (int kt2 = 0; kt2 < 2; ++kt2) {
@@ -274,10 +260,7 @@ __global__ __launch_bounds__(256, (DHP == 64 && QT == 2) ? 3 : 1) void attention
                     __builtin_memcpy(&vf, &lo, 8);
                     __builtin_memcpy(reinterpret_cast<char*>(&vf) + 8, &hi, 8);
 #pragma unroll
-                    for (int qt = 0; qt < QT; ++qt) {
-                        if constexpr (ABL >= 2) asm volatile("" ::"v"(vf), "v"(pb[kt2][qt]));
-                        else o[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pb[kt2][qt], o[dt][qt], 0, 0, 0);
-                    }
+                    for (int qt = 0; qt < QT; ++qt) o[dt][qt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pb[kt2][qt], o[dt][qt], 0, 0, 0);
                 }
             }
         }
@@ -360,7 +343,7 @@ __device__ __forceinline__ void att_wait_lds(u32x2_t (&lo)[N], u32x2_t (&hi)[N],
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// LDS-DMA variant (round 2).  tools/attn_ablate.py put ~290 of the 565 us of L0 self-attention in the register-staged
+// LDS-DMA variant (round 2).  An ablation of the register-staged kernel put ~290 of the 565 us of L0 self-attention in the register-staged
 // load -> ds_write -> barrier chain: each tile's global loads had ONE tile of compute to come back in, and an L2 round
 // trip under load is longer than that even with three workgroups per CU.  Here K / V tiles go HBM / L2 -> LDS with
 // global_load_lds_dwordx4 (no VGPR round trip, no ds_write), THREE tile buffers deep: tile t+2 is issued while tile t is
@@ -761,21 +744,20 @@ __global__ __launch_bounds__(64 * NW, (NCH == 5 && QT == 2) ? ATT_DMA_OCC5 : 1) 
     }
 }
 
-static int g_force_qt = 0;
 template <int NCH, int QT, int NBUF, bool LSUM, bool SC>
 static int launch_att_dma(const AttnParams& p, hipStream_t stream) {
     using T = AttDmaTile<NCH, LSUM>;
     constexpr int lds = NBUF * 2 * T::TILE_BYTES + 1024;     // + slack: the last row's MFMA-width reads run past the tile
-    // 0x60: A/B switch, the round-2/3 softmax (scale + maximum applied by v_fma, cross-lane maximum every tile)
-    // (head dims 128 / 160 keep it: they are MFMA-bound, and the four initialiser registers per query tile would push the
+    // V2 = the round-4 softmax; V2 false = the round-2/3 one (scale + maximum applied by v_fma, cross-lane maximum every tile)
+    // (head dims 128 / 160 keep that: they are MFMA-bound, and the four initialiser registers per query tile would push the
     // 32-row instantiations past 256 VGPRs = from two waves per SIMD to one)
     constexpr bool V2_OK = NCH <= 10;
     // (and the 77-key text cross-attention at head dim 40: two key tiles, the first of which always takes the rescale branch —
-    // measured 41 -> 46 us at level 0, tools/ab_attn_v2.py)
+    // measured 41 -> 46 us at level 0, round 4)
     const bool short_keys = NCH == 5 && p.Lk <= 2 * ATT_KEYS;
     if constexpr (NCH == 5 && QT == 2) {
-        // level-0 self-attention (2560 keys): 8 waves = 256 queries per workgroup (0x70: A/B switch back to 4 waves)
-        if (g_force_qt != 0x60 && g_force_qt != 0x70 && !short_keys && p.Lq % (8 * QT * 16) == 0) {
+        // level-0 self-attention (2560 keys): 8 waves = 256 queries per workgroup
+        if (!short_keys && p.Lq % (8 * QT * 16) == 0) {
             auto kern8 = attention_dma_kernel<NCH, QT, NBUF, LSUM, SC, true, 8>;
             if (int rc = ensure_dynamic_lds((const void*)kern8, lds)) return rc;
             hipLaunchKernelGGL(kern8, dim3(p.Lq / (8 * QT * 16), p.heads, p.NBq), dim3(512), lds, stream, p);
@@ -783,8 +765,8 @@ static int launch_att_dma(const AttnParams& p, hipStream_t stream) {
             return 0;
         }
     }
-    auto kern = (g_force_qt == 0x60 || !V2_OK || short_keys) ? attention_dma_kernel<NCH, QT, NBUF, LSUM, SC, false>
-                                                : attention_dma_kernel<NCH, QT, NBUF, LSUM, SC, V2_OK>;
+    auto kern = (!V2_OK || short_keys) ? attention_dma_kernel<NCH, QT, NBUF, LSUM, SC, false>
+                                       : attention_dma_kernel<NCH, QT, NBUF, LSUM, SC, V2_OK>;
     if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc;
     dim3 grid(cdiv(p.Lq, 4 * QT * 16), p.heads, p.NBq);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, p);
@@ -792,10 +774,10 @@ static int launch_att_dma(const AttnParams& p, hipStream_t stream) {
     return 0;
 }
 
-template <int DHP, int QT, int ABL = 0, bool LSUM = false, bool SC = false, int NDT = 0>
+template <int DHP, int QT, bool LSUM = false, bool SC = false, int NDT = 0>
 static int launch_att(const AttnParams& p, hipStream_t stream) {
     using T = AttTile<DHP>;
-    auto kern = attention_kernel<DHP, QT, ABL, LSUM, SC, NDT>;
+    auto kern = attention_kernel<DHP, QT, LSUM, SC, NDT>;
     static bool attr_set = false;
     if (!attr_set) {
         LAVIE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
@@ -807,36 +789,28 @@ static int launch_att(const AttnParams& p, hipStream_t stream) {
     return 0;
 }
 
-// Kernel choice by head dim: the model's head dims (40, 80, 160; 64 for completeness) get the compile-time output-tile count.
-void attention_force_qt(int qt) { g_force_qt = qt; }
-
+// Kernel choice by head dim: LDS-DMA staging for the model's head dims (and the VSR stage's); the register-staged kernels take
+// the others (head dim 64 of sparse-causal attention with a compile-time output-tile count).
 template <bool SC>
 static int dispatch_att(const AttnParams& p, bool big, bool lsum, hipStream_t stream) {
-    if (g_force_qt != 0x50) {      // LDS-DMA staging for the model's head dims (0x50: A/B switch, register-staged kernels)
-        if (p.dh == 40 && lsum) return big ? launch_att_dma<5, 2, 3, true, SC>(p, stream) : launch_att_dma<5, 1, 3, true, SC>(p, stream);
-        if (p.dh == 80) return big ? launch_att_dma<10, 2, 3, false, SC>(p, stream) : launch_att_dma<10, 1, 3, false, SC>(p, stream);
-        if (p.dh == 160) return big ? launch_att_dma<20, 2, 2, false, SC>(p, stream) : launch_att_dma<20, 1, 2, false, SC>(p, stream);
-        if constexpr (!SC) {           // the VSR stage's head dims (no sparse-causal attention there)
-            if (p.dh == 32) return big ? launch_att_dma<4, 2, 3, false, false>(p, stream) : launch_att_dma<4, 1, 3, false, false>(p, stream);
-            if (p.dh == 64) return big ? launch_att_dma<8, 2, 3, false, false>(p, stream) : launch_att_dma<8, 1, 3, false, false>(p, stream);
-            if (p.dh == 128) return big ? launch_att_dma<16, 2, 2, false, false>(p, stream) : launch_att_dma<16, 1, 2, false, false>(p, stream);
-        }
+    if (p.dh == 40 && lsum) return big ? launch_att_dma<5, 2, 3, true, SC>(p, stream) : launch_att_dma<5, 1, 3, true, SC>(p, stream);
+    if (p.dh == 80) return big ? launch_att_dma<10, 2, 3, false, SC>(p, stream) : launch_att_dma<10, 1, 3, false, SC>(p, stream);
+    if (p.dh == 160) return big ? launch_att_dma<20, 2, 2, false, SC>(p, stream) : launch_att_dma<20, 1, 2, false, SC>(p, stream);
+    if constexpr (!SC) {           // the VSR stage's head dims (no sparse-causal attention there)
+        if (p.dh == 32) return big ? launch_att_dma<4, 2, 3, false, false>(p, stream) : launch_att_dma<4, 1, 3, false, false>(p, stream);
+        if (p.dh == 64) return big ? launch_att_dma<8, 2, 3, false, false>(p, stream) : launch_att_dma<8, 1, 3, false, false>(p, stream);
+        if (p.dh == 128) return big ? launch_att_dma<16, 2, 2, false, false>(p, stream) : launch_att_dma<16, 1, 2, false, false>(p, stream);
     }
     if (p.dh <= 64) {
-        if (lsum) {
-            if (p.dh == 40) return big ? launch_att<64, 2, 0, true, SC, 3>(p, stream) : launch_att<64, 1, 0, true, SC, 3>(p, stream);
-            return big ? launch_att<64, 2, 0, true, SC>(p, stream) : launch_att<64, 1, 0, true, SC>(p, stream);
-        }
-        if (p.dh == 64) return big ? launch_att<64, 2, 0, false, SC, 4>(p, stream) : launch_att<64, 1, 0, false, SC, 4>(p, stream);
-        return big ? launch_att<64, 2, 0, false, SC>(p, stream) : launch_att<64, 1, 0, false, SC>(p, stream);
+        if (lsum) return big ? launch_att<64, 2, true, SC>(p, stream) : launch_att<64, 1, true, SC>(p, stream);
+        if (p.dh == 64) return big ? launch_att<64, 2, false, SC, 4>(p, stream) : launch_att<64, 1, false, SC, 4>(p, stream);
+        return big ? launch_att<64, 2, false, SC>(p, stream) : launch_att<64, 1, false, SC>(p, stream);
     }
     if (p.dh <= 96) {
-        if (lsum) return big ? launch_att<96, 2, 0, true, SC>(p, stream) : launch_att<96, 1, 0, true, SC>(p, stream);
-        if (p.dh == 80) return big ? launch_att<96, 2, 0, false, SC, 5>(p, stream) : launch_att<96, 1, 0, false, SC, 5>(p, stream);
-        return big ? launch_att<96, 2, 0, false, SC>(p, stream) : launch_att<96, 1, 0, false, SC>(p, stream);
+        if (lsum) return big ? launch_att<96, 2, true, SC>(p, stream) : launch_att<96, 1, true, SC>(p, stream);
+        return big ? launch_att<96, 2, false, SC>(p, stream) : launch_att<96, 1, false, SC>(p, stream);
     }
-    if (p.dh == 160) return big ? launch_att<160, 2, 0, false, SC, 10>(p, stream) : launch_att<160, 1, 0, false, SC, 10>(p, stream);
-    return big ? launch_att<160, 2, 0, false, SC>(p, stream) : launch_att<160, 1, 0, false, SC>(p, stream);
+    return big ? launch_att<160, 2, false, SC>(p, stream) : launch_att<160, 1, false, SC>(p, stream);
 }
 
 int launch_attention(const AttnParams& p, hipStream_t stream) {
@@ -853,13 +827,7 @@ int launch_attention(const AttnParams& p, hipStream_t stream) {
                     p.Lq, p.Lk, p.NBq, p.sc_frames);
         return dispatch_att<true>(p, big, p.dh % 16 != 0, stream);
     }
-    if (g_force_qt == 0x12 && p.dh <= 64) return launch_att<64, 2, 1>(p, stream);
-    if (g_force_qt == 0x22 && p.dh <= 64) return launch_att<64, 2, 2>(p, stream);
-    if (g_force_qt == 0x32 && p.dh <= 64) return launch_att<64, 2, 3>(p, stream);
-    if (g_force_qt == 1 && p.dh <= 64) return launch_att<64, 1>(p, stream);
-    if (g_force_qt == 4 && p.dh <= 64) return launch_att<64, 4>(p, stream);
-    const bool lsum = p.dh % 16 != 0 && g_force_qt != 0x40;     // row sums on the matrix pipe (0x40: A/B switch, VALU sums)
-    return dispatch_att<false>(p, big, lsum, stream);
+    return dispatch_att<false>(p, big, p.dh % 16 != 0, stream);     // head dims off the 16 grid: row sums on the matrix pipe
 }
 
 }  // namespace lavie

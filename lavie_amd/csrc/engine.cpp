@@ -23,7 +23,7 @@ void set_error(const char* fmt, ...) {
 const char* get_error() { return g_err; }
 
 static unsigned long g_debug_epoch = 0;
-static int g_fused_mask = 0x137;        // bit 0: fused feed-forward, 1: fused temporal sub-block, 2: fused text cross-attention, 3: conv_shortcut as its own GEMM in front of a halo-patch conv2 (off), 4: parity form of the upsample convs, 5: GroupNorm statistics from the producers' epilogues (A/B switches); 6: debug verification of those statistics against the statistics pass (off); 7: LayerNorm row statistics folded in the consuming GEMM's epilogue instead of a finalize launch (measured slower: off); 8: GroupNorm -> proj_in -> norm1 -> q|k|v as one row-resident kernel
+static int g_fused_mask = 0x137;        // bit 0: fused feed-forward, 1: fused temporal sub-block, 2: fused text cross-attention, 4: parity form of the upsample convs, 5: GroupNorm statistics from the producers' epilogues (A/B switches); 6: debug verification of those statistics against the statistics pass (off); 8: GroupNorm -> proj_in -> norm1 -> q|k|v as one row-resident kernel
 void set_fused_mask(int m) { g_fused_mask = m; }
 int fused_mask() { return g_fused_mask; }
 void bump_debug_epoch() { ++g_debug_epoch; }
@@ -680,8 +680,7 @@ static int trace_halves(const FwdCtx& c, const char* what, const void* p, size_t
 struct LnFold {            // consumer side of a folded LayerNorm
     float* stats;          // [M, 2] (mean, rstd) of the rows
     const float* s;        // row sums of the folded weights
-    // round 4: the producer leaves its partials un-finalized; a consumer on a kernel with the shared epilogue folds them itself
-    // (IgemmParams::ln_partials), the persistent kernel's consumers finalize on demand, once
+    // round 4: the producer leaves its partials un-finalized; the first consumer finalizes them on demand, once
     const float* partials = nullptr;   // [M, slots, 2] of the rows' latest producer, or nullptr when `stats` was written directly
     int slots = 0, row_len = 0, rows = 0;
     bool final_ok = false;             // `stats` holds the finalized (mean, rstd) of the current rows
@@ -740,16 +739,11 @@ static int linear(FwdCtx& c, const half_t* A, int lda, const half_t* W, const fl
     p.rowstat_cols = rowstat ? N / rowstat->slots : 0;
     if (fold) {
         p.ln_s = fold->s;
-        const bool ppx = igemm_takes_ppx(M, N, p.nk, epilogue);
-        if (fold->partials && !fold->final_ok && !ppx && fold->rows >= M && (fused_mask() & 128)) {          // fold in this GEMM's epilogue: no finalize launch
-            p.ln_partials = fold->partials; p.ln_slots = fold->slots; p.ln_inv_len = 1.0f / (float)fold->row_len; p.ln_eps = 1e-5f;
-        } else {
-            if (fold->partials && !fold->final_ok) {       // the persistent kernel stages finished rows: finalize now, once
-                RUN(launch_rowstat_finalize(fold->partials, fold->slots, fold->rows, fold->row_len, 1e-5f, fold->stats, c.s));
-                fold->final_ok = true;
-            }
-            p.ln_stats = fold->stats;
+        if (fold->partials && !fold->final_ok) {           // the producer left its partials: finalize now, once
+            RUN(launch_rowstat_finalize(fold->partials, fold->slots, fold->rows, fold->row_len, 1e-5f, fold->stats, c.s));
+            fold->final_ok = true;
         }
+        p.ln_stats = fold->stats;
     }
     if (epilogue == EPI_LINEAR && ldc == N) colstat_plan(p, false, cs_buf, cs_out);
     const size_t mark = c.ws->mark();
@@ -812,18 +806,6 @@ static int conv3x3(FwdCtx& c, const half_t* const* src, const int* srcC, int nsr
     const int rc = c.dry ? 0 : launch_igemm(p, true, EPI_LINEAR, c.s);
     c.ws->release(mark);
     return rc;
-}
-
-// Whether a plain 3x3 conv Cin -> Cout (stride 1, one source) at this geometry goes to the halo-patch kernel (the planner's rule)
-static bool conv3x3_takes_patch_kernel(int NI, int H, int W, int Cin, int Cout) {
-    IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.Hi = p.Ho = H; p.Wi = p.Wo = W; p.stride = 1;
-    p.M = NI * H * W; p.N = Cout; p.nseg = 1;
-    p.seg[0].C = Cin; p.seg[0].nchunks = Cin / IGEMM_BK; p.seg[0].ntaps = 9;
-    p.nk = 9 * p.seg[0].nchunks;
-    p.splits = igemm_plan_splits_gather(p);
-    return igemm_patch_planned(p);
 }
 
 // (taps,1,1) temporal conv over the frame axis of token rows [(b f d), C] (IgemmParams temporal mode; 128-row kernel).
@@ -935,23 +917,10 @@ int UNet::run_resnet(FwdCtx& c, const ResnetW& r, const half_t* x1, int C1, cons
         const int scC[2] = {C1, C2};
         const int nsc = r.shortcut ? (x2 ? 2 : 1) : 0;
         // The 1x1 conv_shortcut rides in conv2 as extra centre-tap K segments — which keeps conv2 off the halo-patch kernel (it
-        // takes 9-tap segments only; the ping-pong kernel stages 60 LDS-DMA pieces per K-tile against 26).  Where the planner
-        // would give the 3x3 part to the patch kernel, the shortcut can run as its own GEMM on the same packed weight rows (a
-        // column window) and come back through conv2's residual operand.  Measured (round 3, profiles/r03_ab_split_shortcut.txt):
-        // forward 21.33 -> 21.41 ms, i.e. the extra [M, Cout] round trip and launch cost more than the patch kernel gains:
-        // OFF by default (bit 3 of lavie_debug_fused_mask turns it on for A/B).
-        const bool split_sc = r.shortcut && (fused_mask() & 8) && conv3x3_takes_patch_kernel(NI, H, W, r.cout, r.cout);
-        if (split_sc) {
-            WS(scy, half_t, M * r.cout);
-            const half_t* wsc = r.w2 + 9 * r.cout;
-            if (nsc == 1) RUN(linear(c, x1, C1, wsc, nullptr, r.cout, C1, nullptr, scy, r.cout, (int)M, EPI_LINEAR, nullptr, nullptr, r.ldw2));
-            else RUN(conv3x3(c, nullptr, nullptr, 0, sc, scC, nsc, wsc, r.ldw2, nullptr, nullptr, 0, 1, nullptr, scy, NI, H, W, r.cout, 1, 0, zero_page_));
-            RUN(conv3x3(c, src, srcC, 1, nullptr, nullptr, 0, r.w2, r.ldw2, r.b2, nullptr, 0, 1, scy, y, NI, H, W, r.cout, 1, 0, zero_page_,
-                        y_csbuf, y_cs));
-        } else {
+        // takes 9-tap segments only).  Running the shortcut as its own GEMM in front of a halo-patch conv2 was measured slower
+        // (round 3, profiles/r03_ab_split_shortcut.txt: forward 21.33 -> 21.41 ms) and is not built.
         RUN(conv3x3(c, src, srcC, 1, sc, scC, nsc, r.w2, r.ldw2, r.b2, nullptr, 0, 1, r.shortcut ? nullptr : x1, y, NI, H, W,
                     r.cout, 1, 0, zero_page_, y_csbuf, y_cs));
-        }
     }
     TRACE("resnet.conv2", y, M, r.cout);
     c.ws->release(mark);
@@ -1409,8 +1378,8 @@ int UNet::prepare(int B, int F, int H, int W, int ctx_len) {
     const int mask_was = fused_mask();
     int rc = 0;
     // masks: the current one; without the row-resident kernels (bits 0 - 2, 8: their GEMMs and row-statistics buffers appear); and both
-    // again with every workspace-consuming option on (bit 3: the shortcut's own output, 4: the parity form's slabs, 5: statistics buffers)
-    const int masks[4] = {mask_was, mask_was & ~0x107, mask_was | 0x38, (mask_was | 0x38) & ~0x107};
+    // again with every workspace-consuming option on (bit 4: the parity form's slabs, 5: statistics buffers)
+    const int masks[4] = {mask_was, mask_was & ~0x107, mask_was | 0x30, (mask_was | 0x30) & ~0x107};
     for (int variant = 0; variant < 8 && rc == 0; ++variant) {
         if ((variant & 1) && B % 2 != 0) continue;
         cfg_shared_input_ = (variant & 1) != 0;

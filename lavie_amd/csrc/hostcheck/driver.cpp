@@ -32,7 +32,7 @@ static lavie_unet_config base_config() {
     return c;
 }
 
-static void run_model(const lavie_unet_config& cfg, int B, int F, int H, int W, bool labels) {
+static void run_model(const lavie_unet_config& cfg, int B, int F, int H, int W, bool labels, bool check_switches = false) {
     lavie_unet_t h = nullptr;
     REQUIRE(lavie_unet_create(&cfg, &h) == 0);
     const int n = lavie_unet_num_params(h);
@@ -84,6 +84,29 @@ static void run_model(const lavie_unet_config& cfg, int B, int F, int H, int W, 
         REQUIRE(lavie_unet_cache_context(h, nullptr, 0, 0, nullptr) == 0);
     }
     REQUIRE(lavie_hostcheck_launches() > before + 50);
+    if (check_switches) {   // a rejected switch value leaves the one in force: the launch count of a forward tells them apart
+        auto launches = [&]() {
+            const long b = lavie_hostcheck_launches();
+            REQUIRE(lavie_unet_forward(h, x, t, ctx, y, B, F, H, W, 77, nullptr) == 0);
+            return lavie_hostcheck_launches() - b;
+        };
+        const long def = launches();
+        REQUIRE(lavie_debug_fused_mask(0x30) == 0);                  // without the row-resident kernels (a combination prepare() plans)
+        const long plain = launches();
+        REQUIRE(plain != def);
+        REQUIRE(lavie_debug_fused_mask(0x08) != 0 && lavie_debug_fused_mask(0x30 | 0x80) != 0 && lavie_debug_fused_mask(0x200) != 0);
+        REQUIRE(launches() == plain);
+        REQUIRE(lavie_debug_fused_mask(0x137) == 0);
+        REQUIRE(launches() == def);
+        REQUIRE(lavie_debug_force_tile(3) == 0);                     // ping-pong kernel wherever N % 320 == 0: other split-K plans
+        REQUIRE(lavie_unet_prepare(h, B, F, H, W, 77) == 0);
+        const long pp = launches();
+        REQUIRE(pp != def);
+        REQUIRE(lavie_debug_force_tile(0x75) != 0 && lavie_debug_force_tile(10) != 0 && lavie_debug_force_tile(-1) != 0);
+        REQUIRE(launches() == pp);
+        REQUIRE(lavie_debug_force_tile(0) == 0);
+        REQUIRE(launches() == def);
+    }
     REQUIRE(lavie_unet_forward(h, x, t, ctx, y, B, F, H * 2, W * 2, 77, nullptr) != 0);    // larger than prepared: workspace refuses
     REQUIRE(lavie_unet_forward(h, nullptr, t, ctx, y, B, F, H, W, 77, nullptr) != 0);
     REQUIRE(lavie_unet_forward(h, x, t, ctx, y, 9, F, H, W, 77, nullptr) != 0);
@@ -107,7 +130,7 @@ int main() {
         c.block_out_channels[0] = 100;
         REQUIRE(lavie_unet_create(&c, &h) != 0);
     }
-    run_model(base_config(), 2, 16, 16, 16, false);                  // base block order, fused level-0 kernels in reach (C = 320, F = 16)
+    run_model(base_config(), 2, 16, 16, 16, false, true);            // base block order, fused level-0 kernels in reach (C = 320, F = 16)
     run_model(base_config(), 1, 4, 8, 8, false);                     // odd batch, ragged tiles
     {
         lavie_unet_config c = base_config();                         // interpolation variant

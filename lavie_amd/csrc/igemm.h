@@ -42,12 +42,6 @@ struct IgemmParams {
     int rowstat_cols;          // columns per slot the caller sized rowstat_out for (igemm_rowstat_cols); launch_igemm checks that
                                // the kernel it selects writes slots of exactly this width (0 = unchecked)
     const float* ln_stats;     // [M, 2] (mean, rstd) of the A rows (launch_rowstat_finalize), or nullptr
-    // ... or (round 4) the producer's partials themselves: the epilogue folds the ln_slots pairs of a row with rowstat_finalize's
-    // arithmetic, and the finalize launch disappears.  Kernels with the shared epilogue only (the persistent kernel stages finished
-    // (mean, rstd) rows through LDS and has no room for the partials): launch_igemm refuses the combination.
-    const float* ln_partials;  // [M, ln_slots, 2] (sum, sum of squares) or nullptr (then ln_stats)
-    int ln_slots;
-    float ln_inv_len, ln_eps;  // 1 / row length of the normalised rows, epsilon
     const float* ln_s;         // [N]: s_n = sum_k W'[n, k]
     // GroupNorm statistics from the producer (round 4): per (row block, channel) sum and sum of squares of the ROUNDED fp16 output,
     // written by the epilogue that stores the tensor (or by the split-K reduce), so that the consuming GroupNorm needs no statistics
@@ -68,7 +62,6 @@ struct IgemmParams {
     int nseg;
     int par_ups;          // halo-patch kernel only: parity form of the 3x3 conv of a nearest-x2 upsampled image (igemm_patch.hip MODE 3):
                           // W = four [N][ldw] matrices (parity py * 2 + px), one 4-tap segment, M = OUTPUT rows, Hi x Wi = source grid
-    int tap_major;        // diagnostic: K order tap > slab instead of slab > tap (needs weights packed to match)
     IgemmSeg seg[IGEMM_MAX_SEG];
     const half_t* zero;   // >= 128 B of zeros: source of out-of-image taps
 };
@@ -84,7 +77,6 @@ int launch_igemm_pp_geglu(const IgemmParams& p, hipStream_t stream);   // 160x25
 // the LDS-DMA stream running across tile boundaries.  EPI_LINEAR (N %% 320 == 0 or N %% 256 == 0) and EPI_GEGLU (N %% 256 == 0).
 bool igemm_ppx_eligible(const IgemmParams& p, int epilogue);
 int launch_igemm_ppx(const IgemmParams& p, int epilogue, hipStream_t stream);
-int igemm_ppx_read_stamps(unsigned long long* out);   // diagnostic stamp build (mode 0x37): [8 waves][32] cycle sums of workgroup 0
 // 320x160 halo-patch 3x3 conv kernel (igemm_patch.hip): stride 1, 9-tap segments only; the caller runs the split-K reduce.
 bool igemm_patch_eligible(const IgemmParams& p);
 int igemm_patch_bn(int N);                        // 160 / 128 / 0: column-tile width of the halo-patch kernel for N channels
@@ -92,18 +84,13 @@ int launch_igemm_patch(const IgemmParams& p, hipStream_t stream);
 // parity form of conv3x3(nearest_x2(x)) (igemm_patch.hip MODE 3): fills p (incl. splits; the caller sets p->slab), false = not this geometry
 bool igemm_setup_parity_upsample(IgemmParams* p, const half_t* x, int C, const half_t* wpar, const float* bias, half_t* y, int NI, int Hi,
                                  int Wi, const half_t* zero);
-int igemm_patch_read_stamps(unsigned long long* out);   // diagnostic stamp build: [8 waves][16] cycle sums of workgroup 0
 // Split-K factor the launcher would like for this problem (1 = none); slab size = splits * M * N floats.
 int igemm_plan_splits(int M, int N, int nk, int epilogue);
 // Same for a gathered conv whose geometry and K segments are filled in (M, N, nk, Ho, Wo, stride, ups, seg[], nseg):
 // also considers the halo-patch kernel.
 int igemm_plan_splits_gather(const IgemmParams& p);
-// whether launch_igemm would hand this gathered conv (p.splits filled in) to the halo-patch kernel
-bool igemm_patch_planned(const IgemmParams& p);
 // wave-tile width (16*NT) launch_igemm will pick for a plain, unsplit EPI_LINEAR GEMM: the row-statistics slot width
 int igemm_rowstat_cols(int M, int N, int nk);
-// whether launch_igemm hands a plain GEMM of this shape (unsplit) to the persistent ping-pong kernel
-bool igemm_takes_ppx(int M, int N, int nk, int epilogue);
 // rows per column-statistics block of the kernel launch_igemm will run for `p` (geometry, segments and p.splits filled in):
 // 80 (halo-patch, ping-pong and persistent kernels), 64 (128-row kernel), 32 (split-K: the reduce kernel writes them),
 // 0 = this launch cannot emit them (2-D patch tiles, GEGLU)
@@ -122,10 +109,9 @@ int launch_rowstat_finalize(const float* partials, int slots, int M, int row_len
 // Low nibble: 0 = automatic kernel / tile choice, 1 = 128-row kernel with the widest tile,
 // 3 = 160x320 ping-pong kernel whenever N %% 320 == 0, 4 = automatic but never the ping-pong kernel (A/B timing),
 // 5 = halo-patch conv kernel whenever the conv is eligible, 6 = automatic but never the halo-patch kernel,
-// 7 = persistent ping-pong kernel for every eligible plain GEMM, 8 = automatic but never the persistent kernel.
-// High nibble: diagnostic ablation build of the forced kernel (results wrong) — except 0xC (0xC0 / 0xC5): the halo-patch kernel's
-// ping-pong K loop instead of the shipped software-pipelined one (same results; A/B timing).
-void igemm_force_tile(int mode);
+// 7 = persistent ping-pong kernel for every eligible plain GEMM, 8 = automatic but never the persistent kernel,
+// 9 = automatic but without the GEGLU GEMMs on the persistent kernel.  Any other value: error, the mode stays as it was.
+int igemm_force_tile(int mode);
 void igemm_force_splits(int s);   // 0 = automatic
 
 }  // namespace lavie

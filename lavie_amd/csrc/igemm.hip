@@ -49,9 +49,7 @@ struct IgemmTile {
     static_assert(LDS_BYTES <= 160 * 1024, "tile does not fit LDS");
 };
 
-// ABL (diagnostic builds only, results are wrong): 1 = no MFMA, 2 = no global loads after the prologue,
-// 3 = loads + barriers only.  Used by tools/bench_ops.py to find which pipeline paces the loop.
-template <int WM, int WN, int MT, int NT, int NSTAGE, bool GATHER, int EPI, int ABL = 0>
+template <int WM, int WN, int MT, int NT, int NSTAGE, bool GATHER, int EPI>
 __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParams p) {
     using T = IgemmTile<WM, WN, MT, NT, NSTAGE>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -182,7 +180,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
     const half_t* const zero_page = reinterpret_cast<const half_t*>(
         ((unsigned long long)(unsigned)sgpr((int)(unsigned)(reinterpret_cast<unsigned long long>(p.zero) >> 32)) << 32) |
         (unsigned)sgpr((int)(unsigned)reinterpret_cast<unsigned long long>(p.zero)));
-    const int nseg = sgpr(p.nseg), tap_major = sgpr(p.tap_major);
+    const int nseg = sgpr(p.nseg);
     int seg = 0, cchunk = 0, tap = 0;
     IgemmSeg sg = GATHER ? load_seg(0) : IgemmSeg{nullptr, 0, 0, 0, 1};
     if constexpr (GATHER) {
@@ -191,13 +189,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
             skip -= sg.nchunks * sg.ntaps;
             sg = load_seg(++seg);
         }
-        if (tap_major) {
-            tap = skip / sg.nchunks;
-            cchunk = skip - tap * sg.nchunks;
-        } else {
-            cchunk = skip / sg.ntaps;
-            tap = skip - cchunk * sg.ntaps;
-        }
+        cchunk = skip / sg.ntaps;
+        tap = skip - cchunk * sg.ntaps;
     }
 
     // Source pointers of the NEXT tile to be issued are computed one step ahead, in two halves: `prepare_read` only
@@ -222,15 +215,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
                 const half_t* inside = sg.src + ((unsigned)pv[i] * (unsigned)sg.C + cofs);
                 nptr[i] = pv[i] >= 0 ? inside : zero_page + kofs;
             }
-            if (tap_major) {                        // diagnostic K order: tap outer, channel slab inner
-                if (++cchunk == sg.nchunks) {
-                    cchunk = 0;
-                    if (++tap == sg.ntaps) {
-                        tap = 0;
-                        if (seg + 1 < nseg) sg = load_seg(++seg);
-                    }
-                }
-            } else if (++tap == sg.ntaps) {
+            if (++tap == sg.ntaps) {
                 tap = 0;
                 if (++cchunk == sg.nchunks) {
                     cchunk = 0;
@@ -244,7 +229,6 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
     };
     auto prepare = [&](int t) { prepare_read(); prepare_finish(t); };
     auto issue = [&](int t, int buf) {
-        if (ABL == 2 && t > t_begin + 1) return;
         char* base = smem + buf * T::STAGE_BYTES;
 #pragma unroll
         for (int i = 0; i < T::AP; ++i)
@@ -283,11 +267,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
-                if constexpr (ABL == 1) {
-                    asm volatile("" ::"v"(wf[nt]), "v"(af[mt]));      // keep the LDS reads alive
-                } else {
-                    acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt], af[mt], acc[nt][mt], 0, 0, 0);
-                }
+                acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt], af[mt], acc[nt][mt], 0, 0, 0);
             }
     };
     // one K-tile: fragment + table reads -> LDS-DMA issue of a later tile -> MFMAs(k-step 0) -> pointer arithmetic for
@@ -295,16 +275,14 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
     auto tile_step = [&](int buf, auto&& issue_next, int t_prep) {
         const char* base = smem + buf * T::STAGE_BYTES;
         half8_t af0[MT], wf0[NT], af1[MT], wf1[NT];
-        if (ABL != 3) {
-            read_frags(base, 0, af0, wf0);
-            read_frags(base, 1, af1, wf1);
-        }
+        read_frags(base, 0, af0, wf0);
+        read_frags(base, 1, af1, wf1);
         const bool prep = t_prep < t_end;
         if (prep) prepare_read();
         issue_next();
-        if (ABL != 3) mfma_block(af0, wf0);
+        mfma_block(af0, wf0);
         if (prep) prepare_finish(t_prep);
-        if (ABL != 3) mfma_block(af1, wf1);
+        mfma_block(af1, wf1);
     };
     if constexpr (NSTAGE == 2) {
         // one tile in flight: loads of tile t+1 run under the MFMAs of tile t
@@ -416,7 +394,7 @@ static int launch_splitk_reduce(const IgemmParams& p, hipStream_t stream) {
 static int g_force_tile = 0;   // see igemm_force_tile() in igemm.h
 // measured: at 5 K-tiles (K = 320) the GEGLU epilogue, with no second workgroup to hide it, loses; from 8 K-tiles on the
 // ping-pong variant wins or ties (K = 640 of the base model: +0.2 %, K = 512 of the VSR UNet: GEMM class -3.5 %)
-static int g_geglu_pp_min_nk = 8;
+constexpr int GEGLU_PP_MIN_NK = 8;
 static int g_force_splits = 0;
 void igemm_force_splits(int s) { g_force_splits = s; }
 
@@ -473,13 +451,7 @@ int igemm_plan_splits_gather(const IgemmParams& p) {
     return plan_splits(p.M, p.N, p.nk, EPI_LINEAR, false);
 }
 
-bool igemm_patch_planned(const IgemmParams& p) {
-    const int lo = ((g_force_tile & 0xF) == 8 || (g_force_tile & 0xF) == 9) ? 0 : (g_force_tile & 0xF);
-    return igemm_patch_eligible(p) && (lo == 5 || (lo == 0 && patch_fits(p.M, p.N, p.nk, p.splits, p.tframes > 0 ? p.seg[0].ntaps : 9)));
-}
-
 int igemm_plan_splits(int M, int N, int nk, int epilogue) { return plan_splits(M, N, nk, epilogue, true); }
-bool igemm_takes_ppx(int M, int N, int nk, int epilogue) { return ppx_plan_shape(M, N, nk, epilogue); }
 
 static int plan_splits(int M, int N, int nk, int epilogue, bool plain) {
     if (epilogue != EPI_LINEAR || N % 64 != 0) return 1;
@@ -529,10 +501,10 @@ static bool ppx_plan(const IgemmParams& p, int epilogue) {
     return p.splits == 1 && igemm_ppx_eligible(p, epilogue) && ppx_plan_shape(p.M, p.N, p.nk, epilogue);
 }
 
-template <int WM, int WN, int MT, int NT, int NSTAGE, bool GATHER, int EPI, int ABL = 0>
+template <int WM, int WN, int MT, int NT, int NSTAGE, bool GATHER, int EPI>
 static int launch_tile(const IgemmParams& p, hipStream_t stream) {
     using T = IgemmTile<WM, WN, MT, NT, NSTAGE>;
-    auto kern = igemm_kernel<WM, WN, MT, NT, NSTAGE, GATHER, EPI, ABL>;
+    auto kern = igemm_kernel<WM, WN, MT, NT, NSTAGE, GATHER, EPI>;
     constexpr int lds = T::LDS_BYTES + (GATHER ? T::TAB_BYTES : 0);
     static_assert(lds <= 160 * 1024, "tile + pixel table do not fit LDS");
     static bool attr_set = false;   // one per instantiation
@@ -560,7 +532,7 @@ static int igemm_pick_bn(int M, int N, int splits) {
         if (cost < best * 0.97) { best = cost; bn = cand[i]; }
     }
     const int lo = g_force_tile & 0xF;
-    if ((lo == 1 || lo == 3 || g_force_tile >= 0x10) && N % 160 == 0) bn = 160;   // forced modes: widest
+    if ((lo == 1 || lo == 3) && N % 160 == 0) bn = 160;   // forced modes: widest
     return bn;
 }
 
@@ -630,8 +602,7 @@ int launch_igemm(const IgemmParams& p, bool gather, int epilogue, hipStream_t st
     ProfileScope prof(gather ? KC_CONV3X3 : KC_LINEAR, stream, 2.0 * p.M * p.N * K,
                       2.0 * ((double)p.M * K / (gather ? 9.0 : 1.0) + (double)p.N * K + (double)p.M * p.N));
     LAVIE_CHECK(p.N % 4 == 0 && p.ldc % 4 == 0, "igemm: N and ldc must be multiples of 4");
-    LAVIE_CHECK(!(p.rowstat_out || p.ln_stats || p.ln_partials) || (p.splits == 1 && !gather), "igemm: LayerNorm folding needs a plain, unsplit GEMM");
-    LAVIE_CHECK(!p.ln_partials || (p.ln_slots >= 1 && !ppx_plan(p, epilogue)), "igemm: row-statistics partials cannot feed the persistent kernel (finalize them)");
+    LAVIE_CHECK(!(p.rowstat_out || p.ln_stats) || (p.splits == 1 && !gather), "igemm: LayerNorm folding needs a plain, unsplit GEMM");
     LAVIE_CHECK(p.splits >= 1 && p.splits <= p.nk && (p.splits == 1 || (p.slab && epilogue == EPI_LINEAR)),
                 "igemm: bad split-K setup (splits=%d)", p.splits);
     const int lo = ((g_force_tile & 0xF) == 8 || (g_force_tile & 0xF) == 9) ? 0 : (g_force_tile & 0xF);      // 8 = automatic without the persistent kernel
@@ -651,9 +622,9 @@ int launch_igemm(const IgemmParams& p, bool gather, int epilogue, hipStream_t st
         LAVIE_CHECK(!p.R && !p.bias2, "igemm: GEGLU epilogue takes no residual / per-batch bias");
         LAVIE_CHECK(!gather, "igemm: GEGLU epilogue is only built for plain A rows");
         if (ppx_plan(p, epilogue)) return launch_igemm_ppx(p, epilogue, stream);
-        // 160x256 ping-pong variant: same grid rule as the 160x320 kernel, from g_geglu_pp_min_nk K-tiles on
+        // 160x256 ping-pong variant: same grid rule as the 160x320 kernel, from GEGLU_PP_MIN_NK K-tiles on
         const double r = (double)cdiv(p.M, 160) * (p.N / 256) / 256.0;
-        if (p.N % 256 == 0 && (lo == 3 || ((lo == 0 || lo == 6) && p.nk >= g_geglu_pp_min_nk && r / ceil(r) >= 0.85)))
+        if (p.N % 256 == 0 && (lo == 3 || ((lo == 0 || lo == 6) && p.nk >= GEGLU_PP_MIN_NK && r / ceil(r) >= 0.85)))
             return launch_igemm_pp_geglu(p, stream);
         return launch_tile<2, 2, 4, 4, 2, false, EPI_GEGLU>(p, stream);
     }
@@ -679,21 +650,9 @@ int launch_igemm(const IgemmParams& p, bool gather, int epilogue, hipStream_t st
     const int bn = igemm_pick_bn(p.M, p.N, p.splits);
     LAVIE_CHECK(bn != 0, "igemm: N=%d is not a multiple of 64", p.N);
     LAVIE_CHECK(slots_ok(bn / 2), "igemm: row-statistics slots sized for %d columns, 128-row kernel writes %d", p.rowstat_cols, bn / 2);
-    if (bn == 160) {
-        if (g_force_tile >= 0x10 && lo == 1) {          // diagnostic ablations of the 128x160 tile (results wrong)
-            const int abl = g_force_tile >> 4;
-            if (gather) {
-                if (abl == 1) return launch_tile<2, 2, 4, 5, 2, true, EPI_LINEAR, 1>(p, stream);
-                if (abl == 2) return launch_tile<2, 2, 4, 5, 2, true, EPI_LINEAR, 2>(p, stream);
-                return launch_tile<2, 2, 4, 5, 2, true, EPI_LINEAR, 3>(p, stream);
-            }
-            if (abl == 1) return launch_tile<2, 2, 4, 5, 2, false, EPI_LINEAR, 1>(p, stream);
-            if (abl == 2) return launch_tile<2, 2, 4, 5, 2, false, EPI_LINEAR, 2>(p, stream);
-            return launch_tile<2, 2, 4, 5, 2, false, EPI_LINEAR, 3>(p, stream);
-        }
+    if (bn == 160)
         return gather ? launch_tile<2, 2, 4, 5, 2, true, EPI_LINEAR>(p, stream)
                       : launch_tile<2, 2, 4, 5, 2, false, EPI_LINEAR>(p, stream);
-    }
     if (bn == 128)
         return gather ? launch_tile<2, 2, 4, 4, 2, true, EPI_LINEAR>(p, stream)
                       : launch_tile<2, 2, 4, 4, 2, false, EPI_LINEAR>(p, stream);
@@ -701,15 +660,10 @@ int launch_igemm(const IgemmParams& p, bool gather, int epilogue, hipStream_t st
                   : launch_tile<2, 2, 4, 2, 2, false, EPI_LINEAR>(p, stream);
 }
 
-void igemm_pp_ablate(int a);
-void igemm_ppx_ablate(int a);
-void igemm_patch_set_stamp(int mode);
-void igemm_force_tile(int mode) {
+int igemm_force_tile(int mode) {
+    LAVIE_CHECK(mode >= 0 && mode <= 9, "force_tile: mode %d is not one of 0 - 9", mode);
     g_force_tile = mode;
-    igemm_ppx_ablate((mode & 0xF) == 7 ? mode >> 4 : 0);
-    igemm_pp_ablate((mode & 0xF) == 3 ? mode >> 4 : 0);
-    igemm_patch_set_stamp(mode == 0x75 ? 1 : mode == 0x85 ? 2 : mode == 0x95 ? 3 : mode == 0xA5 ? 4 : mode == 0xB5 ? 5 : (mode >> 4) == 0xC ? 6 : 0);
-    if ((mode >> 4) == 0xC) g_force_tile = mode & 0xF;      // 0xC0 / 0xC5: the halo-patch kernel's ping-pong K loop (A/B against the shipped software-pipelined one), kernel choice as the low nibble says
+    return 0;
 }
 
 }  // namespace lavie

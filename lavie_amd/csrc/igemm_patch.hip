@@ -10,19 +10,17 @@
 // 26 pieces per K-tile for the same 2 x 320 x 160 x 64 flop.  Column wrap-around (x-1 at x = 0, x+1 at x = W-1) is the
 // only case the patch cannot express; those lanes read a 128-B row of zeros instead.
 //
-// K loop, shipped build (round 3; template value STAMP = 6): software-pipelined.  Every wave interleaves the ten fragment reads
+// K loop (round 3): software-pipelined.  Every wave interleaves the ten fragment reads
 // of the NEXT k-step (inline-asm ds_read_b128, one per two MFMAs) with the 25 in-place inline-asm MFMAs of this k-step; one
 // lgkmcnt(0) per k-step, ONE barrier per K-tile (in its middle: weight stage hand-over), weights two K-tiles ahead.
 // tools/probes/pipe_probe.hip (profiles/r03_pipe_probe.txt) priced the loop structures with the same work per K-tile: without
 // LDS-DMA both reach the MFMA ceiling of the held clock (0.83-0.86 of the 2.4 GHz peak); with the 26 LDS-DMA pieces per K-tile the
 // ping-pong skeleton drops to 0.63 and this one to 0.67, wherever the pieces come from (L2, MALL, HBM: same) — the LDS-DMA
 // writes themselves are what costs, and register-staged copies (global_load + ds_write_b128) cost more (0.53 / 0.61).
-// K loop, first build (STAMP 0-5, kept for A/B and for the stamp diagnostics) = igemm_pp.hip:
-// 8 waves, wave tile 80x80 (4 waves along M, 2 along N), two groups (waves 0-3 / 4-7 = the SIMD
-// partners) half a k-step apart, R phase (fragment reads + LDS-DMA issue) opposite the partner's M phase (25 MFMAs).
-// Group g owns output columns [80 g, 80 g + 80) and alone reads its half of the weight tile.  Per K-tile t:
-//   G0 R(t,0): W rows  0-79  of K-tile t+1 (10 pieces over 4 waves)      G1 R(t,0): W rows 80-159 of K-tile t+1
-//   G0 R(t,1), G1 R(t,1): one piece per wave of the NEXT slab's patch (8 per K-tile, done after 7 of the 9 K-tiles)
+// 8 waves, wave tile 80x80 (4 waves along M, 2 along N); wave group g (waves 4g .. 4g+3) owns output columns [80 g, 80 g + 80)
+// and stages its half of the weight tile.  During each K-tile every wave stages its share of the NEXT slab's patch (one piece
+// per wave and K-tile for the 3x3 conv: 56 pieces, done after 7 of the 9 K-tiles).  (The first build of this kernel, a
+// ping-pong K loop in the style of igemm_pp.hip, is in the history; profiles/ keeps its measurements.)
 // LDS: 2 x (patch 56 KiB + zero row) + 2 weight stages x 20 KiB + pixel table + tap table = 159.7 KiB.
 // Restrictions (the launcher falls back otherwise): every K segment has 9 taps (a fused 1x1 shortcut runs as its own
 // GEMM whose result comes back through the residual operand), stride 1, no upsample, M % 320 == 0, W % 8 == 0,
@@ -56,12 +54,6 @@ constexpr int T2_W = 32, T2_H = 10, T2_PW = T2_W + 2, T2_ROWS = (T2_H + 2) * T2_
 static_assert(T2_W * T2_H == BM && T2_ROWS <= PATCH_ROWS && T2_W % 16 == 0, "2-D tile geometry");
 }  // namespace pt
 
-// STAMP (diagnostic build, forced with lavie_debug_force_tile(0x75)): s_memtime at every phase boundary; the per-wave sums
-// of workgroup 0 go to g_patch_stamps[wave][segment] (read back with lavie_debug_patch_stamps).  Segments per K-tile:
-// 1 R(t,0) (issue + LDS wait), 2 barrier, 3 M(t,0), 4 barrier, 6 R(t,1), 7 barrier, 8 M(t,1) with the next tap's address
-// arithmetic, 9 LDS-DMA wait, 10 barrier; [11] = K-tiles.  Read the SHARES, never the run time of this build (guide section 7, In-kernel stamps).
-__device__ unsigned long long g_patch_stamps[8 * 16];
-
 // NT = 16-column blocks per wave: 5 -> 320x160 tile (every channel count of the base model), 4 -> 320x128 (the VSR widths)
 // MODE 0: tiles of whole image rows; 1: 2-D tiles (10 rows x 32 columns); 2: temporal (T,1,1) convolution, tile = every frame of
 // 320 / F pixels (no halo at all: tap t of a row is the same pixel t - T/2 frames away, inside the tile or outside the clip)
@@ -71,7 +63,7 @@ __device__ unsigned long long g_patch_stamps[8 * 16];
 // time (launch_pack_conv3x3_parity: fp32 sums, one rounding) and K shrinks from 9 C to 4 C — 2.25x fewer FLOP for the same
 // result up to that one rounding.  Tiles run over SOURCE pixels (whole source rows, as MODE 0), four K-tiles per slab, the
 // epilogue scatters a tile row to output row ((n 2H + 2y + py) 2W + 2x + px); p.M counts OUTPUT rows.
-template <int EPI, int STAMP = 0, int NT = 5, int MODE = 0>
+template <int EPI, int NT = 5, int MODE = 0>
 __global__ __launch_bounds__(pt::THREADS, 2) void igemm_patch_kernel(const IgemmParams p) {
     using namespace pt;
     constexpr int BN = 2 * NT * 16, W_BYTES = BN * 128;
@@ -249,7 +241,7 @@ __global__ __launch_bounds__(pt::THREADS, 2) void igemm_patch_kernel(const Igemm
     };
 
     // ---- fragment rows of this lane: tile row r = 80 wm + 16 mt + (lane & 15); the patch row it reads at a tap comes from
-    // the tap table (two VALU per fragment and K-tile instead of ~10: measured with the stamp build, the address
+    // the tap table (two VALU per fragment and K-tile instead of ~10: measured with in-kernel stamps, the address
     // arithmetic was a quarter of the loop)
     const int frow = lane & 15, fg = lane >> 4;
     const int tap_lane = TAPTAB + (wm * (MT * 16) + frow) * 2;       // + tap * 640 + mt * 32
@@ -260,7 +252,6 @@ __global__ __launch_bounds__(pt::THREADS, 2) void igemm_patch_kernel(const Igemm
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    half8_t af0[MT], wf0[NT];
     int aaddr[MT];                                  // LDS byte address of this K-tile's A fragments (k-step 0)
 
     // A-fragment addresses of a tap in patch buffer pb: tap_read issues the table reads, tap_finish turns them into addresses
@@ -275,32 +266,13 @@ __global__ __launch_bounds__(pt::THREADS, 2) void igemm_patch_kernel(const Igemm
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) aaddr[mt] = ((tv[mt] ^ fg) << 4) + base;
     };
-    auto read_frags = [&](int wst, int ks, half8_t (&af)[MT], half8_t (&wf)[NT]) {
-        const int kx = ks << 6;
-        if (STAMP != 5) {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) af[mt] = *reinterpret_cast<const half8_t*>(smem + (aaddr[mt] ^ kx));
-        }
-        if (STAMP != 4) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                wf[nt] = *reinterpret_cast<const half8_t*>(smem + ((w_frag + wst * W_BYTES + nt * 16 * 128) ^ kx));
-        }
-    };
-    auto mfma_block = [&](half8_t (&af)[MT], half8_t (&wf)[NT]) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-                acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt], af[mt], acc[nt][mt], 0, 0, 0);
-    };
     auto bar = [&]() {
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     };
 
-    // ---- prologue: patch of the first slab (7 pieces per wave), weight tile of the first K-tile
+    // ---- prologue: patch of the first slab (7 pieces per wave), weight tiles of the first two K-tiles
 #pragma unroll 1
     for (int j = 0; j < PATCH_PIECES / 8; ++j) {
         const int i = wave + 8 * j;
@@ -309,202 +281,110 @@ __global__ __launch_bounds__(pt::THREADS, 2) void igemm_patch_kernel(const Igemm
     advance_slab();                                 // the cursor now names the slab to prefetch
     issue_w01(t_begin, 0);
     issue_w2(t_begin, 0);
-    if constexpr (STAMP == 6) {                     // the interleaved loop keeps the weight tiles two K-tiles ahead
-        if (t_begin + 1 < t_end) {
-            issue_w01(t_begin + 1, 1);
-            issue_w2(t_begin + 1, 1);
-        }
+    if (t_begin + 1 < t_end) {                      // the weight tiles run two K-tiles ahead
+        issue_w01(t_begin + 1, 1);
+        issue_w2(t_begin + 1, 1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     bar();
-    unsigned long long st_sum[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_prev = 0;
-    auto stamp = [&](int seg_id) {
-        if constexpr (STAMP != 0) {
-            unsigned long long tnow;
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tnow)::"memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if (seg_id >= 0) st_sum[seg_id] += tnow - st_prev;
-            st_prev = tnow;
-        }
-    };
-    if constexpr (STAMP == 6) {
-        // ---- software-pipelined K loop (tools/probes/pipe_probe.hip: +5 % over the ping-pong skeleton with the same LDS-DMA load):
-        // every wave interleaves the NEXT k-step's ten fragment reads (inline asm, one per two MFMAs) with the 25 in-place MFMAs
-        // of this k-step; one lgkmcnt(0) per k-step, ONE barrier per K-tile, in its middle: behind it every wave's reads of this
-        // tile's weight stage are over (the stage takes tile t + 2) and the weights of tile t + 1, issued one tile ago, have landed
-        // for everyone (the reads of (t + 1, 0) start right behind the barrier).  Table reads (tap table, pixel table) ride in the
-        // same lgkmcnt window as asm reads; compiler-visible LDS reads do not occur inside the loop.
-        const unsigned lbase = (unsigned)(size_t)LDS_PTR(smem);
-        half8_t fa[2][MT], fw[2][NT];
-        tap_read(0);
-        tap_finish(0);
-        auto lds128 = [](half8_t& d, unsigned addr) { asm volatile("ds_read_b128 %0, %1" : "=v"(d) : "v"(addr) : "memory"); };
-        auto mfma_ip = [](f32x4& c, const half8_t& a, const half8_t& b) {
-            asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-        };
-        unsigned wb = lbase + w_frag;               // weight fragment base of the current K-tile's stage (k-step 0)
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) lds128(fa[0][mt], lbase + aaddr[mt]);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) lds128(fw[0][nt], wb + nt * 2048);
-        int pb = 0, kt = 0, slab = slab_begin, nissue_prev = 0;
-        for (int t = t_begin; t < t_end; ++t) {
-            const int wst = (t - t_begin) & 1;
-            const bool next_slab = slab + 1 < slab_end;
-            const bool wrap = kt == ntap - 1;
-            int piece[3];
-            unsigned pix[3] = {0u, 0u, 0u};
-            bool pissue[3];
-            int nissue = 0;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                piece[j] = (kt * ppk + j) * 8 + wave;
-                pissue[j] = (MODE >= 2 || j == 0) && j < ppk && next_slab && piece[j] < npieces;
-                nissue += pissue[j] ? 1 : 0;
-            }
-            // ---- k-step 0: MFMAs on set 0, reads of (t, 1) into set 1, then the table entries of the next tap / patch pieces
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            {
-                const unsigned wb1 = wb ^ 64u;
-                unsigned a1[MT];
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) a1[mt] = lbase + (aaddr[mt] ^ 64);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        mfma_ip(acc[nt][mt], fw[0][nt], fa[0][mt]);
-                        const int m = nt * MT + mt;
-                        if (m >= 2 && m % 2 == 0 && (m - 2) / 2 < MT + NT) {
-                            const int i = (m - 2) / 2;
-                            if (i < MT) lds128(fa[1][i], a1[i]);
-                            else lds128(fw[1][i - MT], wb1 + (i - MT) * 2048);
-                        }
-                    }
-                const unsigned tapa = lbase + tap_lane + (wrap ? 0 : kt + 1) * (BM * 2);
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) asm volatile("ds_read_u16 %0, %1 offset:%2" : "=v"(tv[mt]) : "v"(tapa), "n"(mt * 32) : "memory");
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-                    if (pissue[j]) asm volatile("ds_read_b32 %0, %1" : "=v"(pix[j]) : "v"(lbase + PTAB + (piece[j] * 8 + lr) * 4) : "memory");
-            }
-            // ---- middle of the K-tile
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]), "+v"(tv[3]), "+v"(tv[4]), "+v"(pix[0]), "+v"(pix[1]), "+v"(pix[2])::"memory");
-            if (wrap || nissue_prev == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (nissue_prev == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-            else if (nissue_prev == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-            bar();
-            if (t + 2 < t_end) {
-                issue_w01(t + 2, wst);
-                issue_w2(t + 2, wst);
-            }
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-                if (pissue[j]) issue_patch(piece[j], pb ^ 1, (int)pix[j]);
-            nissue_prev = nissue;
-            tap_finish(wrap ? pb ^ 1 : pb);           // fragment addresses of K-tile t + 1
-            // ---- k-step 1: MFMAs on set 1, reads of (t + 1, 0) into set 0
-            {
-                const unsigned wbn = lbase + w_frag + (wst ^ 1) * W_BYTES;
-                unsigned a0[MT];
-#pragma unroll
-                for (int mt = 0; mt < MT; ++mt) a0[mt] = lbase + aaddr[mt];
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        mfma_ip(acc[nt][mt], fw[1][nt], fa[1][mt]);
-                        const int m = nt * MT + mt;
-                        if (m >= 2 && m % 2 == 0 && (m - 2) / 2 < MT + NT) {
-                            const int i = (m - 2) / 2;
-                            if (i < MT) lds128(fa[0][i], a0[i]);
-                            else lds128(fw[0][i - MT], wbn + (i - MT) * 2048);
-                        }
-                    }
-                wb = wbn;
-            }
-            if (++kt == ntap) {
-                kt = 0;
-                pb ^= 1;
-                ++slab;
-                advance_slab();
-            }
-        }
-        // the accumulators pass through the wait states of the last MFMAs before compiler code (the epilogue) reads them
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-            asm volatile("" : "+v"(acc[nt][0]), "+v"(acc[nt][1]), "+v"(acc[nt][2]), "+v"(acc[nt][3]), "+v"(acc[nt][4]));
-    } else {
-    if (grp == 1) bar();                            // the trailing group runs one barrier behind
-
-    int pb = 0, kt = 0;                             // patch buffer of the current slab, tap index inside it
-    int slab = slab_begin;
-    // (Measured and rejected: reading a phase's fragments during the previous M phase of the same wave.  The reads then
-    // sit beside the wave's own MFMAs and the M phase grows by more than the R phase shrinks: LDS returns and MFMA
-    // operand traffic share the SIMD's register ports.)
+    // ---- software-pipelined K loop (tools/probes/pipe_probe.hip: +5 % over the ping-pong skeleton with the same LDS-DMA load):
+    // every wave interleaves the NEXT k-step's ten fragment reads (inline asm, one per two MFMAs) with the 25 in-place MFMAs
+    // of this k-step; one lgkmcnt(0) per k-step, ONE barrier per K-tile, in its middle: behind it every wave's reads of this
+    // tile's weight stage are over (the stage takes tile t + 2) and the weights of tile t + 1, issued one tile ago, have landed
+    // for everyone (the reads of (t + 1, 0) start right behind the barrier).  Table reads (tap table, pixel table) ride in the
+    // same lgkmcnt window as asm reads; compiler-visible LDS reads do not occur inside the loop.
+    const unsigned lbase = (unsigned)(size_t)LDS_PTR(smem);
+    half8_t fa[2][MT], fw[2][NT];
     tap_read(0);
     tap_finish(0);
-    stamp(-1);
+    auto lds128 = [](half8_t& d, unsigned addr) { asm volatile("ds_read_b128 %0, %1" : "=v"(d) : "v"(addr) : "memory"); };
+    auto mfma_ip = [](f32x4& c, const half8_t& a, const half8_t& b) {
+        asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
+    };
+    unsigned wb = lbase + w_frag;               // weight fragment base of the current K-tile's stage (k-step 0)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) lds128(fa[0][mt], lbase + aaddr[mt]);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) lds128(fw[0][nt], wb + nt * 2048);
+    int pb = 0, kt = 0, slab = slab_begin, nissue_prev = 0;
     for (int t = t_begin; t < t_end; ++t) {
         const int wst = (t - t_begin) & 1;
-        const bool more = t + 1 < t_end;
         const bool next_slab = slab + 1 < slab_end;
-        // patch pieces of the next slab this wave stages during this K-tile: (kt * ppk + j) * 8 + wave, j < ppk
-        int piece[3], pix[3];
+        const bool wrap = kt == ntap - 1;
+        int piece[3];
+        unsigned pix[3] = {0u, 0u, 0u};
         bool pissue[3];
-        int nissue = 0;                             // wave-uniform AND the same for all eight waves (npieces % 8 == 0)
+        int nissue = 0;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             piece[j] = (kt * ppk + j) * 8 + wave;
             pissue[j] = (MODE >= 2 || j == 0) && j < ppk && next_slab && piece[j] < npieces;
             nissue += pissue[j] ? 1 : 0;
         }
-        // ---- R(t, 0): fragments, two weight pieces of K-tile t+1, the pixels of this K-tile's patch pieces
-        read_frags(wst, 0, af0, wf0);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            pix[j] = -1;
-            if (pissue[j]) pix[j] = ptab[piece[j] * 8 + lr];
-        }
-        if (more && STAMP != 2) issue_w01(t + 1, wst ^ 1);
+        // ---- k-step 0: MFMAs on set 0, reads of (t, 1) into set 1, then the table entries of the next tap / patch pieces
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        stamp(1);
+        {
+            const unsigned wb1 = wb ^ 64u;
+            unsigned a1[MT];
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) a1[mt] = lbase + (aaddr[mt] ^ 64);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    mfma_ip(acc[nt][mt], fw[0][nt], fa[0][mt]);
+                    const int m = nt * MT + mt;
+                    if (m >= 2 && m % 2 == 0 && (m - 2) / 2 < MT + NT) {
+                        const int i = (m - 2) / 2;
+                        if (i < MT) lds128(fa[1][i], a1[i]);
+                        else lds128(fw[1][i - MT], wb1 + (i - MT) * 2048);
+                    }
+                }
+            const unsigned tapa = lbase + tap_lane + (wrap ? 0 : kt + 1) * (BM * 2);
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) asm volatile("ds_read_u16 %0, %1 offset:%2" : "=v"(tv[mt]) : "v"(tapa), "n"(mt * 32) : "memory");
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (pissue[j]) asm volatile("ds_read_b32 %0, %1" : "=v"(pix[j]) : "v"(lbase + PTAB + (piece[j] * 8 + lr) * 4) : "memory");
+        }
+        // ---- middle of the K-tile
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tv[0]), "+v"(tv[1]), "+v"(tv[2]), "+v"(tv[3]), "+v"(tv[4]), "+v"(pix[0]), "+v"(pix[1]), "+v"(pix[2])::"memory");
+        if (wrap || nissue_prev == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else if (nissue_prev == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+        else if (nissue_prev == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         bar();
-        stamp(2);
-        // ---- M(t, 0)
-        mfma_block(af0, wf0);
-        stamp(3);
-        bar();
-        stamp(4);
-        // ---- R(t, 1): fragments, the third weight piece, the patch pieces of the next slab, next tap's table entries
-        read_frags(wst, 1, af0, wf0);
-        const bool wrap = kt == ntap - 1;
-        tap_read(wrap ? 0 : kt + 1);
-        if (more && STAMP != 2) issue_w2(t + 1, wst ^ 1);
+        if (t + 2 < t_end) {
+            issue_w01(t + 2, wst);
+            issue_w2(t + 2, wst);
+        }
 #pragma unroll
         for (int j = 0; j < 3; ++j)
-            if (pissue[j] && STAMP != 3) issue_patch(piece[j], pb ^ 1, pix[j]);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        tap_finish(wrap ? pb ^ 1 : pb);
-        stamp(6);
-        bar();
-        stamp(7);
-        // ---- M(t, 1)
-        mfma_block(af0, wf0);
-        stamp(8);
-        // this wave's weight pieces of K-tile t+1 have landed (the patch pieces issued after them may still fly)
-        if (nissue == 0 || STAMP == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (nissue == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        else if (nissue == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        stamp(9);
-        if (!(grp == 1 && !more)) bar();
-        stamp(10);
+            if (pissue[j]) issue_patch(piece[j], pb ^ 1, (int)pix[j]);
+        nissue_prev = nissue;
+        tap_finish(wrap ? pb ^ 1 : pb);           // fragment addresses of K-tile t + 1
+        // ---- k-step 1: MFMAs on set 1, reads of (t + 1, 0) into set 0
+        {
+            const unsigned wbn = lbase + w_frag + (wst ^ 1) * W_BYTES;
+            unsigned a0[MT];
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt) a0[mt] = lbase + aaddr[mt];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    mfma_ip(acc[nt][mt], fw[1][nt], fa[1][mt]);
+                    const int m = nt * MT + mt;
+                    if (m >= 2 && m % 2 == 0 && (m - 2) / 2 < MT + NT) {
+                        const int i = (m - 2) / 2;
+                        if (i < MT) lds128(fa[0][i], a0[i]);
+                        else lds128(fw[0][i - MT], wbn + (i - MT) * 2048);
+                    }
+                }
+            wb = wbn;
+        }
         if (++kt == ntap) {
             kt = 0;
             pb ^= 1;
@@ -512,15 +392,11 @@ __global__ __launch_bounds__(pt::THREADS, 2) void igemm_patch_kernel(const Igemm
             advance_slab();
         }
     }
-
-    }   // ping-pong loop
-    if constexpr (STAMP != 0 && STAMP != 6) {
-        if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0) {
+    // the accumulators pass through the wait states of the last MFMAs before compiler code (the epilogue) reads them
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" ::: "memory");
 #pragma unroll
-            for (int i = 0; i < 11; ++i) g_patch_stamps[wave * 16 + i] = st_sum[i];
-            g_patch_stamps[wave * 16 + 11] = (unsigned long long)(t_end - t_begin);
-        }
-    }
+    for (int nt = 0; nt < NT; ++nt)
+        asm volatile("" : "+v"(acc[nt][0]), "+v"(acc[nt][1]), "+v"(acc[nt][2]), "+v"(acc[nt][3]), "+v"(acc[nt][4]));
     if constexpr (MODE == 3) {         // scatter: source pixel (n, y, x) of this lane -> output pixel (n, 2y + py, 2x + px)
         igemm_epilogue_rows<MT, NT, EPI>(p, acc, [&](int mt) {
             const int m = m0 + wm * (MT * 16) + mt * 16 + (lane & 15);
@@ -542,13 +418,6 @@ __global__ __launch_bounds__(pt::THREADS, 2) void igemm_patch_kernel(const Igemm
         igemm_epilogue<MT, NT, EPI>(p, acc, m0 + wm * (MT * 16) + (lane & 15), n0 + wn * (NT * 16) + (lane >> 4) * 4,
                                     n0 + wn * (NT * 16), lane, split);
     }
-}
-
-static int g_patch_stamp = 0;      // 0 shipped kernel, 1 stamps, 2 stamps without the weight LDS-DMA (wrong results), 3 stamps without the patch LDS-DMA, 6 ping-pong K loop
-void igemm_patch_set_stamp(int mode) { g_patch_stamp = mode; }
-int igemm_patch_read_stamps(unsigned long long* out) {
-    LAVIE_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_patch_stamps), sizeof(unsigned long long) * 8 * 16));
-    return 0;
 }
 
 // Column-tile width the halo-patch kernel uses for N output channels: 160 (base widths), 128 (VSR widths), 0 = none.
@@ -618,10 +487,10 @@ bool igemm_patch_eligible(const IgemmParams& p) {
     return p.splits >= 1 && p.splits <= p.nk / 9;
 }
 
-// MODE 3 (parity form of the upsample conv): shipped K loop only, four parities on gridDim.z
+// MODE 3 (parity form of the upsample conv): four parities on gridDim.z
 static int launch_patch_parity(const IgemmParams& p, hipStream_t stream) {
     using namespace pt;
-    auto kern = igemm_patch_kernel<EPI_LINEAR, 6, 5, 3>;
+    auto kern = igemm_patch_kernel<EPI_LINEAR, 5, 3>;
     static bool attr_set = false;
     if (!attr_set) {
         LAVIE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
@@ -629,7 +498,7 @@ static int launch_patch_parity(const IgemmParams& p, hipStream_t stream) {
     }
     const int grid = (p.M / 4 / BM) * (p.N / 160);
     // counted in the conv class by launch_igemm's scope (executed work: K = 4 Cin per output element); profile class 7 stays the
-    // 3x3 instances alone, so that bench.py's `roofline` and rocprofv3's row of igemm_patch_kernel<0, 6, 5, 0> describe the same launches
+    // 3x3 instances alone, so that bench.py's `roofline` and rocprofv3's row of igemm_patch_kernel<0, 5, 0> describe the same launches
     hipLaunchKernelGGL(kern, dim3(grid, p.splits, 4), dim3(THREADS), LDS_BYTES, stream, p);
     LAVIE_HIP(hipGetLastError());
     return 0;
@@ -639,19 +508,10 @@ template <int NT, int MODE>
 static int launch_patch_nt(const IgemmParams& p, hipStream_t stream) {
     using namespace pt;
     constexpr int BN = 2 * NT * 16;
-    auto kern = g_patch_stamp == 1 ? igemm_patch_kernel<EPI_LINEAR, 1, NT, MODE> : g_patch_stamp == 2 ? igemm_patch_kernel<EPI_LINEAR, 2, NT, MODE>
-                : g_patch_stamp == 3 ? igemm_patch_kernel<EPI_LINEAR, 3, NT, MODE> : g_patch_stamp == 4 ? igemm_patch_kernel<EPI_LINEAR, 4, NT, MODE>
-                : g_patch_stamp == 5 ? igemm_patch_kernel<EPI_LINEAR, 5, NT, MODE> : g_patch_stamp == 6 ? igemm_patch_kernel<EPI_LINEAR, 0, NT, MODE>
-                : igemm_patch_kernel<EPI_LINEAR, 6, NT, MODE>;      // shipped: the software-pipelined K loop (template value 6); 6 here = the ping-pong loop
+    auto kern = igemm_patch_kernel<EPI_LINEAR, NT, MODE>;
     static bool attr_set = false;
     if (!attr_set) {
-        LAVIE_HIP(hipFuncSetAttribute((const void*)igemm_patch_kernel<EPI_LINEAR, 0, NT, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        LAVIE_HIP(hipFuncSetAttribute((const void*)igemm_patch_kernel<EPI_LINEAR, 1, NT, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        LAVIE_HIP(hipFuncSetAttribute((const void*)igemm_patch_kernel<EPI_LINEAR, 2, NT, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        LAVIE_HIP(hipFuncSetAttribute((const void*)igemm_patch_kernel<EPI_LINEAR, 3, NT, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        LAVIE_HIP(hipFuncSetAttribute((const void*)igemm_patch_kernel<EPI_LINEAR, 4, NT, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        LAVIE_HIP(hipFuncSetAttribute((const void*)igemm_patch_kernel<EPI_LINEAR, 5, NT, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        LAVIE_HIP(hipFuncSetAttribute((const void*)igemm_patch_kernel<EPI_LINEAR, 6, NT, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+        LAVIE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
         attr_set = true;
     }
     const int grid = (p.M / BM) * (p.N / BN);

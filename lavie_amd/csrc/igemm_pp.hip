@@ -49,9 +49,7 @@ struct Geo {
 };
 }  // namespace pp
 
-// ABL (diagnostic builds, wrong results): 1 = no MFMA, 2 = no LDS-DMA after the prologue, 3 = MFMAs and barriers only;
-// 4 = s_setprio 1 around the MFMA blocks (results correct; measured 0-10 % slower: it starves the partner's LDS-DMA issue)
-template <bool GATHER, int EPI, int ABL = 0, int NT = 5>
+template <bool GATHER, int EPI, int NT = 5>
 __global__ __launch_bounds__(pp::THREADS, 2) void igemm_pp_kernel(const IgemmParams p) {
     using namespace pp;
     using G = Geo<NT>;
@@ -213,10 +211,8 @@ __global__ __launch_bounds__(pp::THREADS, 2) void igemm_pp_kernel(const IgemmPar
         }
     };
 
-    bool abl_skip = false;                          // ablation builds: set after the prologue
     // LDS-DMA issue helpers (1 KiB per wave instruction; destination = wave-uniform base + lane * 16)
     auto issue_a = [&](int ast, int j0, int j1) {   // A pieces j0..j1-1 of the prepared tile -> A stage `ast`
-        if ((ABL == 2 || ABL == 3) && abl_skip) return;
         char* base = smem + ast * A_BYTES;
 #pragma unroll
         for (int j = 0; j < 5; ++j)
@@ -224,14 +220,13 @@ __global__ __launch_bounds__(pp::THREADS, 2) void igemm_pp_kernel(const IgemmPar
                 __builtin_amdgcn_global_load_lds(GLB_PTR(nptr[j]), LDS_PTR(base + (q + 4 * j) * 1024), 16, 0, 0);
     };
     auto issue_w_g0 = [&](int t, int wst, int half) {   // group 0: four pieces of W_lo (half 0) or W_hi (half 1)
-        if ((ABL == 2 || ABL == 3) && abl_skip) return;
         char* base = smem + W_BASE + wst * W_BYTES + half * (HALF_ROWS * 128);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             __builtin_amdgcn_global_load_lds(GLB_PTR((half ? wp2[j] : wp[j]) + t * IGEMM_BK), LDS_PTR(base + (q + 4 * j) * 1024), 16, 0, 0);
     };
     auto issue_w_g1 = [&](int t, int wst) {             // group 1: piece 16 + q of W_lo and of W_hi
-        if (((ABL == 2 || ABL == 3) && abl_skip) || !G1_W) return;
+        if (!G1_W) return;
         char* base = smem + W_BASE + wst * W_BYTES;
         __builtin_amdgcn_global_load_lds(GLB_PTR(wp[0] + t * IGEMM_BK), LDS_PTR(base + (16 + q) * 1024), 16, 0, 0);
         __builtin_amdgcn_global_load_lds(GLB_PTR(wp2[0] + t * IGEMM_BK), LDS_PTR(base + HALF_ROWS * 128 + (16 + q) * 1024), 16, 0, 0);
@@ -249,7 +244,6 @@ __global__ __launch_bounds__(pp::THREADS, 2) void igemm_pp_kernel(const IgemmPar
     half8_t af[MT], wf[NT];
 
     auto read_frags = [&](int ast, int wst, int ks) {
-        if (ABL == 3) return;
         const char* abase = smem + ast * A_BYTES + a_frag;
         const char* wbase = smem + wst * W_BYTES + w_frag;
         const int slot = ((ks * 4 + fg) ^ fsw) * 16;
@@ -259,20 +253,11 @@ __global__ __launch_bounds__(pp::THREADS, 2) void igemm_pp_kernel(const IgemmPar
         for (int nt = 0; nt < NT; ++nt) wf[nt] = *reinterpret_cast<const half8_t*>(wbase + nt * 16 * 128 + slot);
     };
     auto mfma_block = [&]() {
-        if constexpr (ABL == 1) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) asm volatile("" ::"v"(wf[nt]));
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) asm volatile("" ::"v"(af[mt]));
-            return;
-        }
-        if constexpr (ABL == 4) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
                 acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt], af[mt], acc[nt][mt], 0, 0, 0);
-        if constexpr (ABL == 4) __builtin_amdgcn_s_setprio(0);
     };
     // phase boundary: nothing is scheduled across it
     auto bar = [&]() {
@@ -308,7 +293,6 @@ __global__ __launch_bounds__(pp::THREADS, 2) void igemm_pp_kernel(const IgemmPar
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     bar();
     if (grp == 1) bar();                               // the trailing group runs one barrier behind
-    abl_skip = true;
 
     int ast = 0;                                       // A stage of tile t; tile t+2 goes to stage ast2
     for (int t = t_begin; t < t_end; ++t) {
@@ -354,12 +338,12 @@ __global__ __launch_bounds__(pp::THREADS, 2) void igemm_pp_kernel(const IgemmPar
                                 n0 + wn * (NT * 16), lane, split);
 }
 
-template <bool GATHER, int ABL = 0, int EPI = EPI_LINEAR, int NT = 5>
+template <bool GATHER, int EPI = EPI_LINEAR, int NT = 5>
 static int launch_pp_t(const IgemmParams& p, hipStream_t stream) {
     using namespace pp;
     constexpr int BN = Geo<NT>::BN;
     constexpr int lds = Geo<NT>::LDS_BYTES + (GATHER ? TAB_BYTES : 0);
-    auto kern = igemm_pp_kernel<GATHER, EPI, ABL, NT>;
+    auto kern = igemm_pp_kernel<GATHER, EPI, NT>;
     static bool attr_set = false;
     if (!attr_set) {
         LAVIE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -371,13 +355,10 @@ static int launch_pp_t(const IgemmParams& p, hipStream_t stream) {
     return 0;
 }
 
-static int g_pp_abl = 0;
-void igemm_pp_ablate(int a) { g_pp_abl = a; }
-
 // 160x256 variant with the GEGLU epilogue (plain A rows, no split-K).  N % 256 == 0.
 int launch_igemm_pp_geglu(const IgemmParams& p, hipStream_t stream) {
     LAVIE_CHECK(p.N % 256 == 0 && p.splits == 1, "igemm_pp_geglu: N=%d must be a multiple of 256, no split-K", p.N);
-    return launch_pp_t<false, 0, EPI_GEGLU, 4>(p, stream);
+    return launch_pp_t<false, EPI_GEGLU, 4>(p, stream);
 }
 
 // Launches the 160x320 ping-pong kernel (EPI_LINEAR only; the caller runs the split-K reduce).  N % 320 == 0, or — the
@@ -385,12 +366,8 @@ int launch_igemm_pp_geglu(const IgemmParams& p, hipStream_t stream) {
 int launch_igemm_pp(const IgemmParams& p, bool gather, hipStream_t stream) {
     if (p.N % 320 != 0) {
         LAVIE_CHECK(p.N % 256 == 0, "igemm_pp: N=%d is not a multiple of 320 or 256", p.N);
-        return gather ? launch_pp_t<true, 0, EPI_LINEAR, 4>(p, stream) : launch_pp_t<false, 0, EPI_LINEAR, 4>(p, stream);
+        return gather ? launch_pp_t<true, EPI_LINEAR, 4>(p, stream) : launch_pp_t<false, EPI_LINEAR, 4>(p, stream);
     }
-    if (gather && g_pp_abl == 1) return launch_pp_t<true, 1>(p, stream);
-    if (gather && g_pp_abl == 2) return launch_pp_t<true, 2>(p, stream);
-    if (gather && g_pp_abl == 3) return launch_pp_t<true, 3>(p, stream);
-    if (g_pp_abl == 4) return gather ? launch_pp_t<true, 4>(p, stream) : launch_pp_t<false, 4>(p, stream);   // correct results: with s_setprio
     return gather ? launch_pp_t<true>(p, stream) : launch_pp_t<false>(p, stream);
 }
 

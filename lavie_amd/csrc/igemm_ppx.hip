@@ -2,9 +2,9 @@
 // igemm_pp.hip with the TILE LOOP FLATTENED INTO THE K LOOP and an epilogue built around what the memory pipe of ONE
 // workgroup per CU can take, gfx950.
 //
-// Why (tools/check_ppx.py, tools/stamps_ppx.py, tools/probes/store_probe.hip; profiles/r02_ppx_*.txt):
+// Why (tools/check_ppx.py, tools/probes/store_probe.hip; profiles/r02_ppx_*.txt):
 //   * the transformer blocks' GEMMs have short K loops (K = C or 4C: 5 - 80 K-tiles) and large M.  With the epilogue
-//     removed (ablation 0x17) this loop runs every such shape at 1000 - 1180 TFLOP/s, also at 5 K-tiles; with an epilogue
+//     removed (a since-retired ablation build) this loop runs every such shape at 1000 - 1180 TFLOP/s, also at 5 K-tiles; with an epilogue
 //     in the usual place the same shapes ran at 300 - 750: half of the time of these GEMMs was their EPILOGUE.
 //   * vmcnt retires in order, so every ordinary global load in an epilogue (bias, LayerNorm statistics, five serialised
 //     batches of residual rows) first waits for the youngest prefetched A pieces: a full HBM round trip each.
@@ -72,14 +72,9 @@ __device__ __forceinline__ void asm_load_b64(unsigned long long& dst, unsigned v
     // s_nop 4: the scalar base may have been written by a VALU instruction just before the statement (hipcc spills SGPRs to VGPR
     // lanes and reloads them with v_readlane right in front of their use); a VMEM instruction that reads such an SGPR as its base
     // needs 5 wait states, and hipcc pads nothing inside an asm statement (guide 5.7 item 2).  Round 4: exactly that reload in
-    // front of the column-statistics store of igemm_ppx_kernel<0, 4, 1, 0> sent the store to a stale base (memory aperture fault).
+    // front of the column-statistics store of igemm_ppx_kernel<0, 4, 1> sent the store to a stale base (memory aperture fault).
     asm volatile("s_nop 4\n\tglobal_load_dwordx2 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(voff), "s"(sbase), "n"(IMM) : "memory");
 }
-// stamp build (ABL 3): per-wave cycle sums of workgroup 0, [wave][32]: segments 0..9 of ordinary K-tile steps, 16..25 of
-// the steps that carry an epilogue, [10] K-tile steps, [11] epilogue steps, [12] whole loop.  Segments: 0 DMA batch,
-// 1 epilogue, 2 R(g,0) reads + waits, 3 barrier, 4 M(g,0), 5 barrier, 6 R(g,1), 7 barrier, 8 M(g,1) + wait, 9 barrier.
-__device__ unsigned long long g_ppx_stamps[8 * 32];
-
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 template <int IMM>
@@ -134,8 +129,7 @@ __device__ __forceinline__ void vmwait(int n) {
 
 // MODE: 0 = bias / row statistics only, 1 = + residual rows (prefetched into the output registers), 2 = + folded LayerNorm
 // of the A rows; residual and fold never meet in one GEMM of the model.
-// ABL (diagnostic builds): 1 = no epilogue at all (mainloop + tile switches only; wrong results), 3 = in-kernel stamps
-template <int EPI, int NT, int MODE, int ABL = 0>
+template <int EPI, int NT, int MODE>
 __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmParams p, const int tiles_total) {
     using namespace ppx;
     using G = Geo<NT>;
@@ -571,33 +565,6 @@ __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmP
     bar();
     if (grp == 1) bar();                               // the trailing group runs one barrier behind
 
-    unsigned long long st_sum[32], st_prev = 0, st_begin = 0;
-    if constexpr (ABL == 3) {
-#pragma unroll
-        for (int i = 0; i < 32; ++i) st_sum[i] = 0;
-    }
-    int st_base_idx = 0;
-    auto stamp = [&](int seg_id) {
-        if constexpr (ABL == 3) {
-            unsigned long long tnow;
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tnow)::"memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if (seg_id >= 0) {
-#pragma unroll
-                for (int i = 0; i < 10; ++i) {           // static indices only (runtime-indexed arrays go to scratch)
-                    if (i == seg_id) {
-                        if (st_base_idx) st_sum[16 + i] += tnow - st_prev;
-                        else st_sum[i] += tnow - st_prev;
-                    }
-                }
-            } else {
-                st_begin = tnow;
-            }
-            st_prev = tnow;
-        }
-    };
-    stamp(-1);
     int ast = 0;                                       // A stage of the current K-tile; K-tile g+2 goes to stage ast2
     int kcur = 0, ord = 0;                             // position of the current K-tile inside its output tile
     int cm0 = sgpr(tile_m0(0)), cn0 = sgpr(tile_n0(0));      // current tile
@@ -611,9 +578,8 @@ __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmP
         const bool more1 = g + 1 < total, more2 = g + 2 < total;
         const bool tfirst = kcur == 0, tlast = kcur == nk - 1;
         const bool ep_now = pend;                      // this step finishes the previous tile
-        if constexpr (ABL == 3) { st_base_idx = ep_now ? 1 : 0; if (ep_now) st_sum[11] += 1; else st_sum[10] += 1; }
         // ---- R(g, 0): residual prefetch of a tile's last step, the DMA batch, the deferred finish, this phase's stores
-        if (ABL != 1 && tlast && has_res) issue_residual(cm0, cn0);
+        if (tlast && has_res) issue_residual(cm0, cn0);
         if (grp == 0) {
             if (more1) issue_w_g0(wst ^ 1, 0);
         } else {
@@ -621,55 +587,41 @@ __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmP
             if (tfirst) issue_aux(ord & 1, cm0, cn0);
             if (more2) issue_a(ast2, 0, 2);
         }
-        stamp(0);
         int n_extra = 0;                               // row-statistics stores of the finish (MT asm stores)
         if (ep_now) {
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (ABL != 1) {
-                if (has_res) wait_residual(more2);
-                finish_tile(pm0, pn0, (ord - 1) & 1);  // leaves the accumulators zeroed
-                if constexpr (DIRECT) {
-                    n_extra = ND;                      // its stores are out already: this step's waits skip over them
-                } else {
-                    st_base = p.C + (LIN ? (size_t)pm0 * p.ldc + pn0 : (size_t)pm0 * p.ldc + pn0 / 2);
-                    st_live = true;
-                }
-                if (has_rs) n_extra += MT;
-                if (has_cs) n_extra += NT;
+            if (has_res) wait_residual(more2);
+            finish_tile(pm0, pn0, (ord - 1) & 1);      // leaves the accumulators zeroed
+            if constexpr (DIRECT) {
+                n_extra = ND;                          // its stores are out already: this step's waits skip over them
             } else {
-                if (pm0 < 0) finish_tile(pm0, pn0, 0); // never taken: keeps the accumulators live
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) acc[nt][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                st_base = p.C + (LIN ? (size_t)pm0 * p.ldc + pn0 : (size_t)pm0 * p.ldc + pn0 / 2);
+                st_live = true;
             }
+            if (has_rs) n_extra += MT;
+            if (has_cs) n_extra += NT;
             pend = false;
             __builtin_amdgcn_sched_barrier(0);
         }
         // trickled stores of this step: phases 2 kcur (R0) and 2 kcur + 1 (R1) of the tile finished above / earlier
         const int ph0 = 2 * kcur;
         int n0 = 0, n1 = 0;
-        if (st_live && ABL != 1) {
+        if (st_live) {
             const int lo0 = ph0 * TRICKLE, lo1 = lo0 + TRICKLE, lo2 = lo1 + TRICKLE;
             n0 = lo0 >= NS ? 0 : (lo1 <= NS ? TRICKLE : NS - lo0);
             n1 = lo1 >= NS ? 0 : (lo2 <= NS ? TRICKLE : NS - lo1);
             if (n0) issue_stores(lo0, lo0 + n0);
         }
-        stamp(1);
         read_frags(ast, wst, 0);
         if (grp == 0) {                                // W_hi(g), issued in R(g-1,1) ahead of that phase's stores, has landed
             if (more1) vmwait(4 + n1_prev + n_extra + n0);
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        stamp(2);
         bar();
-        stamp(3);
         // ---- M(g, 0)
         mfma_block();
-        stamp(4);
         bar();
-        stamp(5);
         // ---- R(g, 1)
         read_frags(ast, wst, 1);
         if (grp == 0) {
@@ -686,9 +638,7 @@ __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmP
         }
         if (more1) advance_w();
         if (more2) advance_a();
-        stamp(6);
         bar();
-        stamp(7);
         // ---- M(g, 1)
         mfma_block();
         if (grp == 0) {                                // W_lo(g+1), issued in R(g,0), has landed
@@ -696,9 +646,7 @@ __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmP
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         n1_prev = n1;
-        stamp(8);
         if (!(grp == 1 && !more1)) bar();
-        stamp(9);
         ast = ast == 2 ? 0 : ast + 1;
         if (++kcur == nk) {                            // tile finished: its accumulators are dealt with inside the next step
             kcur = 0;
@@ -709,32 +657,22 @@ __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmP
             if (more1) { cm0 = sgpr(tile_m0(ord)); cn0 = sgpr(tile_n0(ord)); }
         }
     }
-    if constexpr (ABL == 3) {
-        if (blockIdx.x == 0 && lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 32; ++i) g_ppx_stamps[wave * 32 + i] = i == 12 ? st_prev - st_begin : st_sum[i];
-        }
-    }
     // ---- the last tile: nothing left to overlap; finish, store, done
-    if constexpr (ABL != 1) {
-        if (has_res) wait_residual(false);
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        finish_tile(pm0, pn0, (ord - 1) & 1);
-        if constexpr (!DIRECT) {
-            st_base = p.C + (LIN ? (size_t)pm0 * p.ldc + pn0 : (size_t)pm0 * p.ldc + pn0 / 2);
-            issue_stores(0, NS);
-        }
-    } else {
-        if (pm0 < 0) finish_tile(pm0, pn0, 0);
+    if (has_res) wait_residual(false);
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    finish_tile(pm0, pn0, (ord - 1) & 1);
+    if constexpr (!DIRECT) {
+        st_base = p.C + (LIN ? (size_t)pm0 * p.ldc + pn0 : (size_t)pm0 * p.ldc + pn0 / 2);
+        issue_stores(0, NS);
     }
 }
 
-template <int EPI, int NT, int MODE, int ABL = 0>
+template <int EPI, int NT, int MODE>
 static int launch_ppx_t(const IgemmParams& p, hipStream_t stream) {
     using namespace ppx;
     constexpr int BN = Geo<NT>::BN;
     constexpr int lds = Geo<NT>::LDS_BYTES;
-    auto kern = igemm_ppx_kernel<EPI, NT, MODE, ABL>;
+    auto kern = igemm_ppx_kernel<EPI, NT, MODE>;
     static bool attr_set = false;
     if (!attr_set) {
         LAVIE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -759,17 +697,8 @@ bool igemm_ppx_eligible(const IgemmParams& p, int epilogue) {
     return p.N % 320 == 0 || p.N % 256 == 0;
 }
 
-static int g_ppx_abl = 0;
-void igemm_ppx_ablate(int a) { g_ppx_abl = a; }
-int igemm_ppx_read_stamps(unsigned long long* out) {
-    LAVIE_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(ppx::g_ppx_stamps), sizeof(unsigned long long) * 8 * 32));
-    return 0;
-}
-
 template <int EPI, int NT>
 static int launch_ppx_mode(const IgemmParams& p, hipStream_t stream) {
-    if (g_ppx_abl == 1) return launch_ppx_t<EPI, NT, 0, 1>(p, stream);
-    if (g_ppx_abl == 3 && EPI == EPI_LINEAR && NT == 5) return p.R ? launch_ppx_t<EPI_LINEAR, 5, 1, 3>(p, stream) : launch_ppx_t<EPI_LINEAR, 5, 0, 3>(p, stream);
     if (p.ln_stats) return launch_ppx_t<EPI, NT, 2>(p, stream);
     if (EPI == EPI_LINEAR && p.R) return launch_ppx_t<EPI, NT, 1>(p, stream);
     return launch_ppx_t<EPI, NT, 0>(p, stream);

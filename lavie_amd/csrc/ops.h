@@ -49,7 +49,6 @@ struct AttnParams {
     int sc_frames = 0;
 };
 int launch_attention(const AttnParams& p, hipStream_t stream);
-void attention_force_qt(int qt);   // tuning knob: query tiles per wave for head dims <= 64 (0 = automatic)
 
 // ---- temporal_attention.hip
 struct TemporalParams {
@@ -108,8 +107,6 @@ int launch_ln_fold(const half_t* W, const float* gamma, const float* beta, const
 int launch_pack_geglu_vec(const float* in, float* out, int N, hipStream_t stream);
 
 // ---- rowfuse.hip : row-resident fused transformer sub-blocks (weights streamed through LDS, rows in registers)
-void rowfuse_set_stamp_buffer(unsigned long long* buf);   // stamp build (variant 7): [8 waves][8] cycle sums, or nullptr
-void rowfuse_set_variant(int v);   // tuning knob: LDS read-ahead depth (0 = default)
 bool geglu_mlp_supported(int C);
 size_t geglu_mlp_image_bytes(int C);
 size_t geglu_mlp_bias_floats(int C);
@@ -120,7 +117,6 @@ int launch_geglu_mlp(const half_t* x, half_t* y, int M, int C, const half_t* img
                      const float* beta, const float* b2, float eps, hipStream_t stream, float* stats_out = nullptr);
 
 // x' = x + to_out(attn_temp(LN(x))) for clips of exactly 16 frames, rows in (b f) d order; y may alias x
-void temporal_block_set_debug(float* buf);   // development aid: register-tile dump of workgroup 0 (nullptr = off)
 bool temporal_block_supported(int C, int heads, int F, int rot_dim);
 size_t temporal_block_image_bytes(int C);
 int pack_temporal_block(const half_t* wq, const half_t* wk, const half_t* wv, const half_t* wo, int C, half_t* img, hipStream_t stream);

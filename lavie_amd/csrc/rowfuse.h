@@ -89,7 +89,7 @@ template <int CNT>
 __device__ __forceinline__ void rf_lds_wait(half8_t& v) {
     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(CNT) : "memory");
 }
-template <int N, int PF, int ABL, class Fn, int... Ms>
+template <int N, int PF, class Fn, int... Ms>
 __device__ __forceinline__ void rf_run_impl(unsigned addr, Fn&& fn, std::integer_sequence<int, Ms...>) {
     static_assert(PF >= 1 && PF <= 15 && N * 1024 <= 65536, "read-ahead depth / immediate offset range");
     half8_t fa[PF];
@@ -103,25 +103,13 @@ __device__ __forceinline__ void rf_run_impl(unsigned addr, Fn&& fn, std::integer
         constexpr int LEFT = (N - M < PF ? N - M : PF) - 1;      // reads younger than fragment M still allowed in flight
         rf_lds_wait<LEFT>(fa[M % PF]);
         fn(m_, fa[M % PF]);
-        // ABL 1 (timing-only build, wrong results): every second fragment read is dropped (the stale fragment is reused)
-        if constexpr (M + PF < N && !(ABL == 1 && ((M + PF) & 1))) rf_lds_read<(M + PF) * 1024>(fa[M % PF], addr);
+        if constexpr (M + PF < N) rf_lds_read<(M + PF) * 1024>(fa[M % PF], addr);
     };
     (step(std::integral_constant<int, Ms>{}), ...);
 }
-template <int N, int PF, int ABL = 0, class Fn>
+template <int N, int PF, class Fn>
 __device__ __forceinline__ void rf_run(unsigned addr, Fn&& fn) {
-    rf_run_impl<N, PF, ABL>(addr, fn, std::make_integer_sequence<int, N>{});
-}
-
-// ABL: timing-only ablation builds (results wrong): 1 = half the LDS fragment reads, 2 = no GELU arithmetic, 3 = no LDS-DMA
-// after the first two groups, 4 = no barriers inside the pass
-// ABL 5: stamp build (s_memtime around the phases of the chunk loop; sums per wave of workgroup 0 go to p.stamps; read the SHARES)
-__device__ __forceinline__ unsigned long long rf_stamp() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
+    rf_run_impl<N, PF>(addr, fn, std::make_integer_sequence<int, N>{});
 }
 
 namespace tb { constexpr int SEG = 20; }     // pieces per ring segment: the granularity of the sync points inside a pass
@@ -156,22 +144,9 @@ __device__ __forceinline__ void tb_run_impl(unsigned lo, unsigned hi, Fn&& fn, S
     };
     (step(std::integral_constant<int, Ms>{}), ...);
 }
-// PLAIN (development aid): compiler-scheduled reads, one per MFMA, no read-ahead
-template <int S0, int N, class Fn, class SyncFn, int... Ms>
-__device__ __forceinline__ void tb_run_plain_impl(const char* ringp, Fn&& fn, SyncFn&& syncfn, std::integer_sequence<int, Ms...>) {
-    auto step = [&](auto m_) {
-        constexpr int M = decltype(m_)::value;
-        constexpr int SP = S0 + M;
-        if constexpr (SP % tb::SEG == 0 && SP != 0) syncfn(std::integral_constant<int, SP / tb::SEG>{});
-        const half8_t a = *reinterpret_cast<const half8_t*>(ringp + ((SP % rf::RING_PIECES) << 10));
-        fn(m_, a);
-    };
-    (step(std::integral_constant<int, Ms>{}), ...);
-}
-template <int S0, int N, int PF, bool PLAIN = false, class Fn, class SyncFn>
-__device__ __forceinline__ void tb_run(unsigned lo, unsigned hi, const char* ringp, Fn&& fn, SyncFn&& syncfn) {
-    if constexpr (PLAIN) tb_run_plain_impl<S0, N>(ringp, fn, syncfn, std::make_integer_sequence<int, N>{});
-    else tb_run_impl<S0, N, PF>(lo, hi, fn, syncfn, std::make_integer_sequence<int, N>{});
+template <int S0, int N, int PF, class Fn, class SyncFn>
+__device__ __forceinline__ void tb_run(unsigned lo, unsigned hi, Fn&& fn, SyncFn&& syncfn) {
+    tb_run_impl<S0, N, PF>(lo, hi, fn, syncfn, std::make_integer_sequence<int, N>{});
 }
 
 // MFMAs of the fused temporal kernel are inline asm, accumulating IN PLACE (vDst = SrcC), in program order.  Reason (found the
@@ -197,7 +172,5 @@ __device__ __forceinline__ half8_t rf_cat(const half4_t& a, const half4_t& b) {
 }
 __device__ __forceinline__ half4_t rf_pack(const f32x4& v) { return (half4_t){(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]}; }
 
-
-int rowfuse_variant();      // lavie_debug_rowfuse_variant
 
 }  // namespace lavie

@@ -74,20 +74,14 @@ struct GegluMlpParams {
     int M;
     int tiles;               // 16-row tiles = ceil(M / 16), dealt to the workgroups in contiguous, near-equal runs
     float eps;
-    unsigned long long* stamps;   // stamp build only: [8 waves][8] cycle sums of workgroup 0
     float* stats_out;        // optional [M, 2]: (mean, rstd) of every OUTPUT row (of its rounded fp16 values): what a LayerNorm-folded
                              // GEMM that consumes y needs (IgemmParams::ln_stats) — the interpolation block's norm_temp follows the
                              // feed-forward (interpolation/models/attention.py:592-604); nullptr = not written
 };
 
-template <int C, int PF, int ABL = 0>
+template <int C, int PF>
 __global__ __launch_bounds__(rf::THREADS, 2) void geglu_mlp_kernel(const GegluMlpParams p) {
     using namespace rf;
-    unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0;      // DMA issue, first product, geglu, second product, prologue, store, vmcnt wait, barrier
-    auto mark = [&](int which) {
-        if constexpr (ABL == 5) { const unsigned long long t = rf_stamp(); st[which] += t - t0; t0 = t; }
-    };
-    if constexpr (ABL == 5) t0 = rf_stamp();
     constexpr int NT = C / 16;                    // residual tiles per token tile (20)
     constexpr int KS = C / 32;                    // k-steps of the first product (10)
     constexpr int CHUNKS = C / 8;                 // 32-unit hidden chunks (40)
@@ -120,7 +114,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void geglu_mlp_kernel(const GegluMl
     const int total_groups = my_passes * PASS_GROUPS;
     // group g of the stream = image pieces (g % PASS_GROUPS) * 40 ..., ring pieces (g % 3) * 40 ...; wave w moves pieces w + 8 i
     auto issue_group = [&](int g) {
-        if (g >= total_groups || (ABL == 3 && g >= 2)) return;
+        if (g >= total_groups) return;
         const char* src = reinterpret_cast<const char*>(p.img) + ((size_t)((g % PASS_GROUPS) * GROUP + wave) << 10) + lane * 16;
         char* dst = ring + (((g % RING_GROUPS) * GROUP + wave) << 10);
 #pragma unroll
@@ -130,11 +124,9 @@ __global__ __launch_bounds__(rf::THREADS, 2) void geglu_mlp_kernel(const GegluMl
     // group g + 1 are outstanding; the barrier makes that true for every wave's pieces and ends everyone's reads of g - 1
     auto sync_group = [&](int g) {
         __builtin_amdgcn_sched_barrier(0);
-        if (g + 1 < total_groups && ABL != 3) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+        if (g + 1 < total_groups) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        mark(6);
-        if (ABL != 4) __builtin_amdgcn_s_barrier();
-        mark(7);
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         issue_group(g + 2);
         __builtin_amdgcn_sched_barrier(0);
@@ -219,7 +211,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void geglu_mlp_kernel(const GegluMl
             const unsigned ba = bias_base + chunk * 256;
             if constexpr (T0 == 0) { rf_lds_read_f32x4<0>(acc[0], ba); rf_lds_read_f32x4<64>(acc[1], ba); }
             if constexpr (T1 == 4) { rf_lds_read_f32x4<128>(acc[2], ba); rf_lds_read_f32x4<192>(acc[3], ba); }
-            rf_run<(T1 - T0) * KS, PF, ABL>(rbase + ((T0 * KS) << 10), [&](auto m_, const half8_t& a) {
+            rf_run<(T1 - T0) * KS, PF>(rbase + ((T0 * KS) << 10), [&](auto m_, const half8_t& a) {
                 constexpr int M = decltype(m_)::value;
                 constexpr int TT = T0 + M / KS, S = M % KS;
                 acc[TT] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, xb[S], acc[TT], 0, 0, 0);
@@ -229,13 +221,13 @@ __global__ __launch_bounds__(rf::THREADS, 2) void geglu_mlp_kernel(const GegluMl
             if (!active) return;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                hb[r] = (half_t)(acc[0][r] * (ABL == 2 ? acc[1][r] : gelu_erf_f(acc[1][r])));
-                hb[4 + r] = (half_t)(acc[2][r] * (ABL == 2 ? acc[3][r] : gelu_erf_f(acc[3][r])));
+                hb[r] = (half_t)(acc[0][r] * gelu_erf_f(acc[1][r]));
+                hb[4 + r] = (half_t)(acc[2][r] * gelu_erf_f(acc[3][r]));
             }
         };
         auto second_product = [&](unsigned rbase) {
             if (!active) return;
-            rf_run<NT, PF, ABL>(rbase + ((4 * KS) << 10), [&](auto m_, const half8_t& a) {
+            rf_run<NT, PF>(rbase + ((4 * KS) << 10), [&](auto m_, const half8_t& a) {
                 constexpr int T = decltype(m_)::value;
                 R[T] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, hb, R[T], 0, 0, 0);
             });
@@ -243,28 +235,17 @@ __global__ __launch_bounds__(rf::THREADS, 2) void geglu_mlp_kernel(const GegluMl
         using I0 = std::integral_constant<int, 0>;
         using I2 = std::integral_constant<int, 2>;
         using I4 = std::integral_constant<int, 4>;
-        mark(4);
         for (int cc = 0; cc < CHUNKS; cc += 2) {
             sync_group(g++);                              // ring pieces 0..39: W1 of chunk cc
-            mark(0);
             first_product(accA, cc, ring_lo, I0{}, I4{});
-            mark(1);
             sync_group(g++);                              // 40..79: W2 of chunk cc, v0 g0 of chunk cc + 1
-            mark(0);
             first_product(accB, cc + 1, ring_hi, I0{}, I2{});
-            mark(1);
             geglu(accA);
-            mark(2);
             second_product(ring_lo);
-            mark(3);
             sync_group(g++);                              // 80..119: v1 g1 and W2 of chunk cc + 1
-            mark(0);
             first_product(accB, cc + 1, ring_hi, I2{}, I4{});
-            mark(1);
             geglu(accB);
-            mark(2);
             second_product(ring_hi);
-            mark(3);
         }
         // ---- x' = residual registers, one rounding
         if (active && row < p.M) {
@@ -289,34 +270,6 @@ __global__ __launch_bounds__(rf::THREADS, 2) void geglu_mlp_kernel(const GegluMl
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (ABL == 5) {
-        mark(5);
-        if (blockIdx.x == 0 && lane == 0 && p.stamps) {
-            for (int i = 0; i < 8; ++i) p.stamps[wave * 8 + i] = st[i];
-        }
-    }
-}
-
-static unsigned long long* g_rf_stamps = nullptr;
-void rowfuse_set_stamp_buffer(unsigned long long* buf) { g_rf_stamps = buf; }
-static int g_rf_variant = 0;            // tuning: LDS read-ahead depth of the fused kernels (0 = default)
-void rowfuse_set_variant(int v) { g_rf_variant = v; }
-int rowfuse_variant() { return g_rf_variant; }
-
-template <int PF, int ABL = 0>
-static int launch_geglu_mlp_t(const GegluMlpParams& p, hipStream_t stream, const ProfileScope& prof) {
-    constexpr int lds = rf::RING_BYTES + (320 / 8) * 64 * 4 + 3 * 320 * 4;
-    auto kern = geglu_mlp_kernel<320, PF, ABL>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        LAVIE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr_set = true;
-    }
-    const int grid = p.tiles < 256 ? p.tiles : 256;
-    if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);
-    else hipLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, p);
-    LAVIE_HIP(hipGetLastError());
-    return 0;
 }
 
 int launch_geglu_mlp(const half_t* x, half_t* y, int M, int C, const half_t* img, const float* b1img, const float* gamma,
@@ -327,17 +280,19 @@ int launch_geglu_mlp(const half_t* x, half_t* y, int M, int C, const half_t* img
     ProfileScope prof(KC_FUSED_FF, stream, 2.0 * M * (double)C * 12.0 * C, 2.0 * (2.0 * M * C + 12.0 * C * C), /*kernel_events=*/true);
     GegluMlpParams p;
     p.x = x; p.y = y; p.img = img; p.b1img = b1img; p.gamma = gamma; p.beta = beta; p.b2 = b2;
-    p.M = M; p.tiles = cdiv(M, rf::TOK); p.eps = eps; p.stamps = g_rf_stamps; p.stats_out = stats_out;
-    switch (g_rf_variant) {
-        case 1: return launch_geglu_mlp_t<5>(p, stream, prof);
-        case 2: return launch_geglu_mlp_t<12>(p, stream, prof);
-        case 3: return launch_geglu_mlp_t<8, 1>(p, stream, prof);
-        case 4: return launch_geglu_mlp_t<8, 2>(p, stream, prof);
-        case 5: return launch_geglu_mlp_t<8, 3>(p, stream, prof);
-        case 6: return launch_geglu_mlp_t<8, 4>(p, stream, prof);
-        case 7: return launch_geglu_mlp_t<8, 5>(p, stream, prof);      // stamp build
-        default: return launch_geglu_mlp_t<8>(p, stream, prof);
+    p.M = M; p.tiles = cdiv(M, rf::TOK); p.eps = eps; p.stats_out = stats_out;
+    constexpr int lds = rf::RING_BYTES + (320 / 8) * 64 * 4 + 3 * 320 * 4;
+    auto kern = geglu_mlp_kernel<320, 8>;      // LDS read-ahead depth 8
+    static bool attr_set = false;
+    if (!attr_set) {
+        LAVIE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        attr_set = true;
     }
+    const int grid = p.tiles < 256 ? p.tiles : 256;
+    if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);
+    else hipLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, p);
+    LAVIE_HIP(hipGetLastError());
+    return 0;
 }
 
 
@@ -411,11 +366,9 @@ struct TemporalBlockParams {
     int D;                    // pixels per frame
     int units;                // B * D pixels
     float scale, eps;
-    float* dbg;               // development aid: workgroup 0 / wave 0 / head pair 0 dumps its register tiles (nullptr = off)
 };
 
-constexpr int g_dbg_pair_c = 1;       // development aid: which head pair the register-tile dump shows
-template <int PF, int DBG = 0>      // DBG 1: every sync drains the DMA queue (vmcnt(0)) — protocol check
+template <int PF>
 __global__ __launch_bounds__(rf::THREADS, 2) void temporal_block_kernel(const TemporalBlockParams p) {
     using namespace rf;
     using namespace tb;
@@ -467,7 +420,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void temporal_block_kernel(const Te
         __builtin_amdgcn_sched_barrier(0);
         // need unit (K + 1) / 2 landed; the only younger unit this wave can have in flight is the next one
         constexpr bool younger = (K % 2 == 0) ? (K / 2 + 1 < PASS_UNITS) : ((K + 1) / 2 + 1 < PASS_UNITS);
-        if constexpr (younger && !(DBG & 1)) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+        if constexpr (younger) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -568,12 +521,8 @@ __global__ __launch_bounds__(rf::THREADS, 2) void temporal_block_kernel(const Te
                     if constexpr (W == 0) qp[J] = rf_pack(v);
                     else if constexpr (W == 1) kp[J] = rf_pack(v);
                     else vp[J] = rf_pack(v);
-                    if ((DBG & 8) && HP == g_dbg_pair_c && p.dbg && bid == 0 && wave == 0 && pass == 0) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) p.dbg[(W * 20 + J * 4 + r) * 64 + lane] = W == 2 ? acc[T & 1][r] : (float)rf_pack(v)[r];
-                    }
                 };
-                tb_run<P0, 150, PF, (DBG & 2) != 0>(ring_lo, ring_hi, ring + frag, [&](auto m_, const half8_t& a) {
+                tb_run<P0, 150, PF>(ring_lo, ring_hi, [&](auto m_, const half8_t& a) {
                     constexpr int M = decltype(m_)::value;
                     constexpr int T = M / 10, S = M % 10;
                     if constexpr (T < 10) {                      // q, k: weights are the A operand -> D[channel][frame]
@@ -628,16 +577,6 @@ __global__ __launch_bounds__(rf::THREADS, 2) void temporal_block_kernel(const Te
                     op[TA] = rf_pack(oa * inv);
                     op[TB] = rf_pack(ob * inv);
                     osh[E] = os * inv;
-                    if ((DBG & 8) && HP == g_dbg_pair_c && p.dbg && bid == 0 && wave == 0 && pass == 0) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            p.dbg[((3 + E) * 20 + 0 + r) * 64 + lane] = S[r];
-                            p.dbg[((3 + E) * 20 + 4 + r) * 64 + lane] = e[r] * inv;
-                            p.dbg[((3 + E) * 20 + 8 + r) * 64 + lane] = oa[r] * inv;
-                            p.dbg[((3 + E) * 20 + 12 + r) * 64 + lane] = ob[r] * inv;
-                            p.dbg[((3 + E) * 20 + 16 + r) * 64 + lane] = os[r] * inv;
-                        }
-                    }
                 };
                 attend(std::integral_constant<int, 0>{});
                 attend(std::integral_constant<int, 1>{});
@@ -648,20 +587,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void temporal_block_kernel(const Te
                 half8_t o0 = rf_cat(op[0], op[1]), o1 = rf_cat(op[3], op[4]);
                 half8_t pend;                                    // the 16-deep fragment of the previous group of five pieces
                 asm volatile("s_nop 4" : "+v"(o0), "+v"(o1), "+v"(op[2]));      // fresh VALU results: wait states before the MFMAs read them
-                if ((DBG & 8) && HP == 0 && p.dbg && bid == 0 && wave == 0 && pass == 0) {       // operands and accumulators as the to_out product sees them
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        p.dbg[(420 + j) * 64 + lane] = (float)o0[j];
-                        p.dbg[(428 + j) * 64 + lane] = (float)o1[j];
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) p.dbg[(436 + j) * 64 + lane] = (float)op[2][j];
-#pragma unroll
-                    for (int t = 0; t < NT; ++t)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) p.dbg[(440 + t * 4 + r) * 64 + lane] = R[t][r];
-                }
-                tb_run<P0 + 150, 50, PF, (DBG & 4) != 0>(ring_lo, ring_hi, ring + frag, [&](auto m_, const half8_t& a) {
+                tb_run<P0 + 150, 50, PF>(ring_lo, ring_hi, [&](auto m_, const half8_t& a) {
                     constexpr int M = decltype(m_)::value;
                     constexpr int U = M / 5, I = M % 5;
                     if constexpr (I < 4) {
@@ -687,12 +613,6 @@ __global__ __launch_bounds__(rf::THREADS, 2) void temporal_block_kernel(const Te
                              : "+v"(R[0]), "+v"(R[1]), "+v"(R[2]), "+v"(R[3]), "+v"(R[4]), "+v"(R[5]), "+v"(R[6]), "+v"(R[7]), "+v"(R[8]), "+v"(R[9]),
                                "+v"(R[10]), "+v"(R[11]), "+v"(R[12]), "+v"(R[13]), "+v"(R[14]), "+v"(R[15]), "+v"(R[16]), "+v"(R[17]), "+v"(R[18]),
                                "+v"(R[19]));
-                if ((DBG & 8) && p.dbg && bid == 0 && wave == 0 && pass == 0) {
-#pragma unroll
-                    for (int t = 0; t < NT; ++t)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) p.dbg[(100 + HP * 80 + t * 4 + r) * 64 + lane] = R[t][r];
-                }
             } else {
                 // a wave without a pixel in this pass still moves weights and meets every barrier of the pair
                 auto idle = [&](auto... ks) { (sync(std::integral_constant<int, decltype(ks)::value>{}), ...); };
@@ -724,9 +644,6 @@ __global__ __launch_bounds__(rf::THREADS, 2) void temporal_block_kernel(const Te
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-static float* g_tb_dbg = nullptr;
-void temporal_block_set_debug(float* buf) { g_tb_dbg = buf; }
-
 int launch_temporal_block(const half_t* x, half_t* y, int B, int F, int D, int C, int heads, const half_t* img,
                           const float* gamma, const float* beta, const float* bo, const float* relbias, const float* rot_cos,
                           const float* rot_sin, int rot_dim, float scale, float eps, hipStream_t stream) {
@@ -737,25 +654,15 @@ int launch_temporal_block(const half_t* x, half_t* y, int B, int F, int D, int C
     ProfileScope prof(KC_FUSED_TEMPORAL, stream, 2.0 * tok * C * 4.0 * C + 4.0 * tok * F * C, 2.0 * (2.0 * tok * C + 4.0 * C * C), /*kernel_events=*/true);
     TemporalBlockParams p;
     p.x = x; p.y = y; p.img = img; p.gamma = gamma; p.beta = beta; p.bo = bo; p.relbias = relbias; p.rot_cos = rot_cos;
-    p.rot_sin = rot_sin; p.D = D; p.units = B * D; p.scale = scale; p.eps = eps; p.dbg = g_tb_dbg;
+    p.rot_sin = rot_sin; p.D = D; p.units = B * D; p.scale = scale; p.eps = eps;
     constexpr int lds = rf::RING_BYTES + tb::TAB_BYTES;
     const int grid = p.units < 256 ? p.units : 256;
-    auto go = [&](auto kern) -> int {
-        if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc;     // once per kernel address, not per launch
-        if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);
-        else hipLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, p);
-        LAVIE_HIP(hipGetLastError());
-        return 0;
-    };
-    switch (g_rf_variant) {
-        case 1: return go(temporal_block_kernel<8, 1>);
-        case 2: return go(temporal_block_kernel<8, 6>);      // plain reads everywhere
-        case 3: return go(temporal_block_kernel<8, 4>);      // plain reads in the to_out product only
-        case 4: return go(temporal_block_kernel<8, 2>);      // plain reads in the q / k / v products only
-        case 5: return go(temporal_block_kernel<4, 0>);
-        case 6: return go(temporal_block_kernel<8, 8>);      // with the register-tile dump (lavie_debug_temporal_block_dump)
-        default: return go(temporal_block_kernel<8, 0>);
-    }
+    auto kern = temporal_block_kernel<8>;      // LDS read-ahead depth 8
+    if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc;     // once per kernel address, not per launch
+    if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);
+    else hipLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, p);
+    LAVIE_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace lavie

@@ -283,7 +283,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
 
         if (active) {
             // ---- x' = x + bo1 + Wo1 att
-            tb_run<0, O1_PIECES, PF>(ring_lo, ring_hi, ring + frag, [&](auto m_, const half8_t& a) {
+            tb_run<0, O1_PIECES, PF>(ring_lo, ring_hi, [&](auto m_, const half8_t& a) {
                 constexpr int M = decltype(m_)::value;
                 rf_mfma32(R[M / KS], a, xa[M % KS]);
             }, sync);
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
                         constexpr int T = decltype(t_)::value;
                         qp[T] = rf_pack(acc[T & 1] * p.scale);
                     };
-                    tb_run<P0 + Q_OFF, 50, PF>(ring_lo, ring_hi, ring + frag, [&](auto m_, const half8_t& a) {
+                    tb_run<P0 + Q_OFF, 50, PF>(ring_lo, ring_hi, [&](auto m_, const half8_t& a) {
                         constexpr int M = decltype(m_)::value;
                         constexpr int T = M / 10, S = M % 10;
                         if constexpr (S == 0) rf_mfma32_first(acc[T & 1], a, xbf[S]);
@@ -364,7 +364,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
                     half4_t qm0 = q < 2 ? qp[2] : z, qm1 = q < 2 ? z : qp[2];       // rows of the shared tile that belong to each head
                     half8_t pend;
                     asm volatile("s_nop 4" : "+v"(qc0), "+v"(qc1), "+v"(qm0), "+v"(qm1));
-                    tb_run<P0 + K_OFF, 15, PF>(ring_lo, ring_hi, ring + frag, [&](auto m_, const half8_t& a) {
+                    tb_run<P0 + K_OFF, 15, PF>(ring_lo, ring_hi, [&](auto m_, const half8_t& a) {
                         constexpr int M = decltype(m_)::value;
                         constexpr int KT = M / 3, I = M % 3;
                         if constexpr (I == 0) rf_mfma32_first(S[0][KT], a, qc0);
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
                 {
                     f32x4 O[5], osh[2];
                     asm volatile("s_nop 4" : "+v"(pc[0][0]), "+v"(pc[0][1]), "+v"(pc[1][0]), "+v"(pc[1][1]), "+v"(p4[0]), "+v"(p4[1]));
-                    tb_run<P0 + V_OFF, 13, PF>(ring_lo, ring_hi, ring + frag, [&](auto m_, const half8_t& a) {
+                    tb_run<P0 + V_OFF, 13, PF>(ring_lo, ring_hi, [&](auto m_, const half8_t& a) {
                         constexpr int M = decltype(m_)::value;
                         if constexpr (M < 10) {
                             constexpr int J = M / 2, SS = M % 2;
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
                 half8_t o0 = rf_cat(op[0], op[1]), o1 = rf_cat(op[3], op[4]);
                 half8_t pend;
                 asm volatile("s_nop 4" : "+v"(o0), "+v"(o1), "+v"(op[2]));
-                tb_run<P0 + O_OFF, 50, PF>(ring_lo, ring_hi, ring + frag, [&](auto m_, const half8_t& a) {
+                tb_run<P0 + O_OFF, 50, PF>(ring_lo, ring_hi, [&](auto m_, const half8_t& a) {
                     constexpr int M = decltype(m_)::value;
                     constexpr int U = M / 5, I = M % 5;
                     if constexpr (I < 4) {
@@ -528,17 +528,12 @@ int launch_cross_block(const half_t* att, const half_t* x, half_t* y, int M, int
     p.tiles = M / rf::TOK; p.tiles_per_batch = rows_per_batch / rf::TOK; p.L = L; p.scale = scale; p.eps = eps;
     constexpr int lds = rf::RING_BYTES + xb::VEC_BYTES;
     const int grid = p.tiles < 256 ? p.tiles : 256;
-    auto go = [&](auto kern) -> int {
-        if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc;     // once per kernel address, not per launch
-        if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);
-        else hipLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, p);
-        LAVIE_HIP(hipGetLastError());
-        return 0;
-    };
-    switch (rowfuse_variant()) {
-        case 5: return go(cross_block_kernel<4>);
-        default: return go(cross_block_kernel<8>);
-    }
+    auto kern = cross_block_kernel<8>;      // LDS read-ahead depth 8
+    if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc;     // once per kernel address, not per launch
+    if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);
+    else hipLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, p);
+    LAVIE_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace lavie

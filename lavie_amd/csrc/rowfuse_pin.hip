@@ -176,7 +176,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void proj_qkv_kernel(const ProjQkvP
             rf_lds_read_f32x4<(4 * GA + 2) * 64>(T[4 * GA + 2], bias_base);
             rf_lds_read_f32x4<(4 * GA + 3) * 64>(T[4 * GA + 3], bias_base);
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(T[4 * GA]), "+v"(T[4 * GA + 1]), "+v"(T[4 * GA + 2]), "+v"(T[4 * GA + 3])::"memory");
-            rf_run<4 * KS, PF, 0>(rbase, [&](auto m_, const half8_t& a) {
+            rf_run<4 * KS, PF>(rbase, [&](auto m_, const half8_t& a) {
                 constexpr int M = decltype(m_)::value;
                 constexpr int TT = 4 * GA + M / KS, S = M % KS;
                 T[TT] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, xb[S], T[TT], 0, 0, 0);
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void proj_qkv_kernel(const ProjQkvP
             f32x4 acc[4];
 #pragma unroll
             for (int tt = 0; tt < 4; ++tt) acc[tt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            rf_run<4 * KS, PF, 0>(rbase, [&](auto m_, const half8_t& a) {
+            rf_run<4 * KS, PF>(rbase, [&](auto m_, const half8_t& a) {
                 constexpr int M = decltype(m_)::value;
                 constexpr int TT = M / KS, S = M % KS;
                 acc[TT] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, xb2[S], acc[TT], 0, 0, 0);

@@ -825,7 +825,7 @@ def test_workspace_plan_covers_every_switch_combination(full):
     net.prepare(2, bench.FRAMES, bench.LAT_H, bench.LAT_W, bench.CTX_LEN)             # once, under the default switches
     ref = net(x, 500, encoder_hidden_states=ctx).sample.clone()
     try:
-        for mask in (0, 0x08, 0x10, 0x20, 0x38, DEF | 0x08, DEF & ~0x107, DEF & ~0x20, DEF & ~0x10, 0x1FF & ~0xC0):
+        for mask in (0, 0x10, 0x20, 0x30, DEF, DEF & ~0x107, DEF & ~0x20, DEF & ~0x10):
             for shared in (False, True):
                 for cached in (False, True):
                     _lib.check(lib.lavie_debug_fused_mask(mask), "lavie_debug_fused_mask")

@@ -164,11 +164,12 @@ def test_conv3x3_concat_shortcut_temb(ops):
     (1, 64, 0, 160, 30, 32, 0),      # 2-D geometry is not needed here (W = 32 divides 320): still the row tiles
     (1, 64, 0, 320, 10, 512, 0),     # the VSR stage's 512-pixel rows, 160-wide column tiles
 ])
-@pytest.mark.parametrize("force", [5, 0xC5], ids=["pipelined-loop", "pingpong-loop"])
+@pytest.mark.parametrize("force", [5, 3], ids=["pipelined-loop", "pingpong-loop"])
 def test_conv3x3_halo_patch_kernel(ops, n, c1, c2, cout, h, w, splits, force):
-    """The 320x160 halo-patch conv kernel (igemm_patch.hip) forced on shapes it accepts, with bias, per-video bias
-    and residual, in both of its K-loop builds (ping-pong groups; software-pipelined reads between in-place MFMAs);
-    the same call through the default kernels must agree with it to rounding."""
+    """The halo-patch conv shapes, with bias, per-video bias and residual, must agree with F.conv2d to rounding under both
+    K-loop structures of the conv kernels: the 320x160 halo-patch kernel's software-pipelined loop (igemm_patch.hip, forced
+    with mode 5), and the two-group ping-pong loop, which the halo-patch kernel no longer builds and the 160x320 ping-pong
+    kernel runs (igemm_pp.hip, forced with mode 3 where N % 320 == 0; the other widths take the 128-row kernel)."""
     from lavie_amd import _lib
     lib = _lib.load()
     g = gen(n * 7 + c1 + cout + h)
@@ -183,7 +184,7 @@ def test_conv3x3_halo_patch_kernel(ops, n, c1, c2, cout, h, w, splits, force):
     wp = ops.pack_conv3x3(h16(wt))
     args = dict(x2=h16(rows(x2)) if c2 else None, bias2=f32(b2), rows_per_batch=h * w, residual=h16(rows(r)))
     try:
-        lib.lavie_debug_force_tile(force)
+        _lib.check(lib.lavie_debug_force_tile(force), "lavie_debug_force_tile")
         lib.lavie_debug_force_splits(splits)
         y = ops.conv3x3(h16(rows(x1)), wp, f32(b), n, h, w, **args)
     finally:

@@ -91,7 +91,30 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
     for name in declared:
         assert hasattr(lib, name)
-    assert lib.lavie_abi_version() == _lib.ABI_VERSION == 7
+    assert lib.lavie_abi_version() == _lib.ABI_VERSION == 8
+
+
+def test_debug_switches_reject_retired_modes():
+    """lavie_debug_force_tile takes modes 0 - 9 and lavie_debug_fused_mask bits 0, 1, 2, 4, 5, 6, 8 only: anything else is an
+    error that leaves the current setting in place (no GPU needed: both switches are host state).  That the setting in force
+    really survives a rejected value is checked by `make asan` (hostcheck/driver.cpp: launch counts of a forward)."""
+    lib = _lib.load()
+    DEF = _lib.FUSED_DEFAULT
+    try:
+        assert lib.lavie_debug_force_tile(3) == 0
+        assert lib.lavie_debug_force_tile(0x75) != 0
+        assert b"force_tile" in lib.lavie_last_error()
+        assert lib.lavie_debug_force_tile(10) != 0 and lib.lavie_debug_force_tile(-1) != 0
+        assert lib.lavie_debug_fused_mask(DEF & ~0x20) == 0
+        assert lib.lavie_debug_fused_mask(0x08) != 0
+        assert b"fused_mask" in lib.lavie_last_error()
+        assert lib.lavie_debug_fused_mask(DEF | 0x80) != 0 and lib.lavie_debug_fused_mask(0x200) != 0
+        for mask in (0, 0x177, DEF):
+            assert lib.lavie_debug_fused_mask(mask) == 0
+        assert lib.lavie_debug_fused_mask(0x08) != 0
+    finally:
+        lib.lavie_debug_force_tile(0)
+        lib.lavie_debug_fused_mask(DEF)
 
 
 def test_relpos_buckets_host_function():

@@ -1,7 +1,7 @@
 """A/B of the row-resident fused sub-block kernels inside the full UNet forward (bench shape), one process, interleaved
 rounds (guide rule 24): lavie_debug_fused_mask 0 = one GEMM per launch, 1 = fused feed-forward, 2 = fused temporal sub-block,
 3 = both, 7 = those and the fused text cross-attention sub-block (needs the cached context, as the pipeline runs), 23 = those and the parity form of the
-upsample convs (bit 4; bit 3 = conv_shortcut as its own GEMM, measured slower, off)."""
+upsample convs (bit 4)."""
 import sys
 
 import torch

@@ -1,7 +1,7 @@
 """A/B of lavie_debug_fused_mask settings inside the full UNet forward at the bench shape (cached context, shared CFG prefix, as the
 guided loop runs it), one process, interleaved rounds (guide rule 24): per-forward wall time, output difference against the first
 mask, and the per-class device time of one instrumented forward each.
-Usage: python tools/ab_mask.py 0xB7 0x37 [...]      (bits: include/lavie_hip.h)"""
+Usage: python tools/ab_mask.py 0x137 0x117 [...]      (bits: include/lavie_hip.h)"""
 import sys
 
 import torch
@@ -13,7 +13,7 @@ from lavie_amd.unet import UNet3DConditionModel  # noqa: E402
 
 
 def main():
-    masks = [int(a, 0) for a in sys.argv[1:]] or [_lib.FUSED_DEFAULT, _lib.FUSED_DEFAULT & ~0x80]
+    masks = [int(a, 0) for a in sys.argv[1:]] or [_lib.FUSED_DEFAULT, _lib.FUSED_DEFAULT & ~0x20]
     lib = _lib.load()
     dev = torch.device("cuda", 0)
     sd = weights.synth_state_dict(spec.param_shapes(), 0)

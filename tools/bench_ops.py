@@ -77,17 +77,7 @@ def bench_conv():
     _lib.load().lavie_debug_force_tile(0)
 
 
-def bench_attn_qt():
-    qkv = rnd(32 * 2560, 960)
-    for qt in (0, 0x40, 0, 0x40, 0x12, 0x22, 0x32):
-        _lib.load().lavie_debug_attention_qt(qt)
-        us = timeit(lambda: ops.attention(qkv[:, :320], qkv[:, 320:640], qkv[:, 640:], nb=32, lq=2560, lk=2560, heads=8))
-        print(f"L0 self-attention QT/ABL={qt:#x}: {us:8.1f} us {4.0 * 32 * 2560 * 2560 * 320 / us / 1e6:6.0f} TF/s")
-    _lib.load().lavie_debug_attention_qt(0)
-
-
 def bench_attn():
-    bench_attn_qt()
     print("attention: nb heads L dh | us TF/s")
     for nb, l, c, lk, div in ((32, 2560, 320, 2560, 1), (32, 640, 640, 640, 1), (32, 160, 1280, 160, 1), (32, 2560, 320, 77, 16)):
         if lk == l:
@@ -120,39 +110,6 @@ if __name__ == "__main__":
         bench_conv()
     if what in ("attn", "all"):
         bench_attn()
-
-
-def bench_ablate():
-    """Diagnostic: which pipeline paces the conv K loop (results are wrong in ablated modes)."""
-    for ni, h, w, c1, c2, cout in ((32, 40, 64, 640, 320, 320), (32, 10, 16, 1280, 0, 1280), (32, 5, 8, 1280, 0, 1280)):
-        x1 = rnd(ni * h * w, c1)
-        x2 = rnd(ni * h * w, c2) if c2 else None
-        wp = ops.pack_conv3x3(rnd(cout, c1 + c2, 3, 3) / math.sqrt(9 * (c1 + c2)))
-        bias = torch.randn(cout, device=dev)
-        row = f"{ni} {h}x{w} {c1}+{c2}->{cout} | "
-        for mode, name in ((1, "full"), (0x11, "noMFMA"), (0x21, "noLoads"), (0x31, "loadsOnly")):
-            _lib.load().lavie_debug_force_tile(mode)
-            us = timeit(lambda: ops.conv3x3(x1, wp, bias, ni, h, w, x2=x2))
-            row += f"{name} {us:8.1f} us | "
-        print(row)
-    _lib.load().lavie_debug_force_tile(0)
-
-
-def bench_ablate_pp():
-    """Which phase paces the 160x320 ping-pong kernel (results are wrong in ablated modes)."""
-    for ni, h, w, c1, c2, cout in ((32, 40, 64, 640, 320, 320), (32, 20, 32, 640, 0, 640), (32, 40, 64, 320, 0, 320)):
-        x1 = rnd(ni * h * w, c1)
-        x2 = rnd(ni * h * w, c2) if c2 else None
-        wp = ops.pack_conv3x3(rnd(cout, c1 + c2, 3, 3) / math.sqrt(9 * (c1 + c2)))
-        bias = torch.randn(cout, device=dev)
-        row = f"pp {ni} {h}x{w} {c1}+{c2}->{cout} | "
-        for rnd_ in range(2):
-            for mode, name in ((0x03, "full"), (0x43, "noSetprio"), (0x13, "noMFMA"), (0x23, "noDMA")):
-                _lib.load().lavie_debug_force_tile(mode)
-                us = timeit(lambda: ops.conv3x3(x1, wp, bias, ni, h, w, x2=x2), iters=30)
-                row += f"{name} {us:8.1f} us | "
-        print(row)
-    _lib.load().lavie_debug_force_tile(0)
 
 
 def bench_pp_splits():
@@ -190,20 +147,6 @@ def bench_pp_splits():
     lib.lavie_debug_force_tile(0); lib.lavie_debug_force_splits(0)
 
 
-def bench_ablate_gemm():
-    for M, N, K in ((20480, 640, 2560), (81920, 320, 1280), (5120, 1280, 5120)):
-        a, w = rnd(M, K), rnd(N, K) / math.sqrt(K)
-        out = torch.empty(M, N, dtype=torch.float16, device=dev)
-        for tile, tname in ((1, "128x160 2-stage"),):
-            row = f"{M}x{N}x{K} {tname:24s} | "
-            for abl, name in ((0, "full"), (1, "noMFMA"), (2, "noLoads"), (3, "loadsOnly")):
-                _lib.load().lavie_debug_force_tile(abl * 16 + tile)
-                us = timeit(lambda: ops.linear(a, w, out=out))
-                row += f"{name} {us:8.1f} us | "
-            print(row)
-    _lib.load().lavie_debug_force_tile(0)
-
-
 def bench_splits():
     """Split-K sweep on the under-filled conv / linear grids."""
     lib = _lib.load()
@@ -237,44 +180,11 @@ def bench_splits():
         print(row)
 
 
-def bench_order():
-    lib = _lib.load()
-    lib.lavie_debug_force_splits(1)
-    print("conv K order: shape | slab>tap us | tap>slab us")
-    for ni, h, w, c1, c2, cout in ((32, 40, 64, 320, 0, 320), (32, 40, 64, 640, 320, 320), (32, 20, 32, 640, 0, 640),
-                                   (32, 20, 32, 1280, 640, 640), (32, 10, 16, 1280, 0, 1280), (32, 5, 8, 1280, 0, 1280)):
-        x1 = rnd(ni * h * w, c1)
-        x2 = rnd(ni * h * w, c2) if c2 else None
-        wt = rnd(cout, c1 + c2, 3, 3) / math.sqrt(9 * (c1 + c2))
-        bias = torch.randn(cout, device=dev)
-        row = f"{ni} {h}x{w} {c1}+{c2}->{cout} | "
-        outs = []
-        for tm in (0, 1):
-            lib.lavie_debug_conv_tap_major(tm)
-            wp = ops.pack_conv3x3(wt)
-            row += f"{timeit(lambda: ops.conv3x3(x1, wp, bias, ni, h, w, x2=x2)):8.1f} | "
-            outs.append(ops.conv3x3(x1, wp, bias, ni, h, w, x2=x2).float())
-        row += f"max diff {float((outs[0] - outs[1]).abs().max()):.3g}"
-        print(row)
-    lib.lavie_debug_conv_tap_major(0)
-    lib.lavie_debug_force_splits(0)
-
-
-if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "order":
-    bench_order()
-
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "splits":
     bench_splits()
 
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "pp_splits":
     bench_pp_splits()
-
-if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "ablate_pp":
-    bench_ablate_pp()
-
-if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "ablate":
-    bench_ablate()
-    bench_ablate_gemm()
 
 
 def bench_tconv():

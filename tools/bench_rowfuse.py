@@ -44,20 +44,11 @@ def main():
         fused()
         unfused()
     flop = 2.0 * M * C * 12 * C
-    from lavie_amd import _lib
-    lib = _lib.load()
     for r in range(3):
-        line = f"round {r}:"
-        for v in (0, 1, 2):
-            lib.lavie_debug_rowfuse_variant(v)
-            fused()
-            tf = timeit(fused)
-            line += f"  fused[v{v}] {tf:7.1f} us ({flop / tf / 1e6:6.1f} TF/s)"
+        tf = timeit(fused)
         tu = timeit(unfused)
-        if r == 0:
-            print("feed-forward variants: 0 = read-ahead 8 (shipped), 1 = 5, 2 = 12")
-        print(line + f"   ff1 + ff2 unfused (no LN fold) {tu:7.1f} us ({flop / tu / 1e6:6.1f} TF/s)", flush=True)
-    lib.lavie_debug_rowfuse_variant(0)
+        print(f"round {r}:  fused {tf:7.1f} us ({flop / tf / 1e6:6.1f} TF/s)   ff1 + ff2 unfused (no LN fold) {tu:7.1f} us "
+              f"({flop / tu / 1e6:6.1f} TF/s)", flush=True)
 
     # ---- temporal sub-block: fused kernel vs LN-folded-free q|k|v GEMM + temporal attention kernel + to_out GEMM (+ residual)
     B, Fr, D, heads = 2, 16, 2560, 8
@@ -88,12 +79,8 @@ def main():
             tunfused()
     tflop = 2.0 * M * C * 4 * C
     for r in range(3):
-        lib.lavie_debug_rowfuse_variant(0)
         t8 = timeit(tfused)
-        lib.lavie_debug_rowfuse_variant(5)
-        t4 = timeit(tfused)
-        lib.lavie_debug_rowfuse_variant(0)
-        line = f"temporal round {r}: fused PF8 {t8:7.1f} us ({tflop / t8 / 1e6:6.1f} TF/s)  fused PF4 {t4:7.1f} us"
+        line = f"temporal round {r}: fused {t8:7.1f} us ({tflop / t8 / 1e6:6.1f} TF/s)"
         if have_unfused:
             tu = timeit(tunfused)
             line += f"   qkv GEMM + temporal kernel + to_out GEMM {tu:7.1f} us"
@@ -130,20 +117,14 @@ def cross():
         a = ops.attention(q, k, v, B * 16, P // 16, L, heads, kv_batch_div=16, scale=scale)
         ops.linear(a, wo2, bias=bo2, residual=out, out=o)
 
-    from lavie_amd import _lib
-    lib = _lib.load()
     for _ in range(3):
         fused()
         unfused()
     flop = 2.0 * M * C * 3 * C + 4.0 * M * L * C
     for r in range(3):
-        lib.lavie_debug_rowfuse_variant(0)
         t8 = timeit(fused)
-        lib.lavie_debug_rowfuse_variant(5)
-        t4 = timeit(fused)
-        lib.lavie_debug_rowfuse_variant(0)
         tu = timeit(unfused)
-        print(f"cross round {r}: fused PF8 {t8:7.1f} us ({flop / t8 / 1e6:6.1f} TF/s)  fused PF4 {t4:7.1f} us   to_out + to_q + attention + to_out "
+        print(f"cross round {r}: fused {t8:7.1f} us ({flop / t8 / 1e6:6.1f} TF/s)   to_out + to_q + attention + to_out "
               f"{tu:7.1f} us", flush=True)
 
 
