@@ -19,18 +19,20 @@ static inline hipStream_t S(void* s) { return (hipStream_t)s; }
 // buffer owned by the library (allocated outside any stream capture; the engine uses its own workspace).
 static float* g_slab = nullptr;
 static size_t g_slab_bytes = 0;
-static int op_slab(IgemmParams& p, int epilogue, bool gather = false) {
-    p.splits = gather ? igemm_plan_splits_gather(p) : igemm_plan_splits(p.M, p.N, p.nk, epilogue);
+static int op_launch(IgemmParams& p, bool gather, int epilogue, hipStream_t stream) {
+    const IgemmPlan plan = igemm_plan(p, gather, epilogue);
+    p.splits = plan.splits;
     p.slab = nullptr;
-    if (p.splits <= 1) return 0;
-    const size_t need = (size_t)p.splits * p.M * p.N * sizeof(float);
-    if (need > g_slab_bytes) {
-        if (g_slab) { LAVIE_HIP(hipDeviceSynchronize()); LAVIE_HIP(hipFree(g_slab)); g_slab = nullptr; g_slab_bytes = 0; }
-        LAVIE_HIP(hipMalloc((void**)&g_slab, need));
-        g_slab_bytes = need;
+    if (p.splits > 1) {
+        const size_t need = (size_t)p.splits * p.M * p.N * sizeof(float);
+        if (need > g_slab_bytes) {
+            if (g_slab) { LAVIE_HIP(hipDeviceSynchronize()); LAVIE_HIP(hipFree(g_slab)); g_slab = nullptr; g_slab_bytes = 0; }
+            LAVIE_HIP(hipMalloc((void**)&g_slab, need));
+            g_slab_bytes = need;
+        }
+        p.slab = g_slab;
     }
-    p.slab = g_slab;
-    return 0;
+    return launch_igemm(p, plan, stream);
 }
 static inline const half_t* H(const void* p) { return (const half_t*)p; }
 static inline half_t* H(void* p) { return (half_t*)p; }
@@ -51,8 +53,7 @@ int lavie_linear_f16(const void* A, int lda, const void* W, const float* bias, c
     p.A = H(A); p.lda = lda; p.W = H(W); p.ldw = K; p.C = H(C); p.ldc = ldc; p.bias = bias;
     p.bias2 = bias2; p.ldb2 = ldb2; p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
     p.R = H(R); p.ldr = ldr; p.M = M; p.N = N; p.nk = K / IGEMM_BK;
-    if (int rc = op_slab(p, geglu ? EPI_GEGLU : EPI_LINEAR)) return rc;
-    return launch_igemm(p, false, geglu ? EPI_GEGLU : EPI_LINEAR, S(stream));
+    return op_launch(p, false, geglu ? EPI_GEGLU : EPI_LINEAR, S(stream));
 }
 
 // The consumer side of a folded LayerNorm at operator level (engine.cpp's `LnFold`): C = rstd_m (A W'^T - mean_m s) + bias with
@@ -64,9 +65,9 @@ int lavie_linear_lnfold_f16(const void* A, const void* Wf, const float* bias, co
     IgemmParams p;
     memset(&p, 0, sizeof(p));
     p.A = H(A); p.lda = K; p.W = H(Wf); p.ldw = K; p.C = H(C); p.ldc = N; p.bias = bias; p.rows_per_batch = 1;
-    p.M = M; p.N = N; p.nk = K / IGEMM_BK; p.splits = 1;
+    p.M = M; p.N = N; p.nk = K / IGEMM_BK;
     p.ln_s = ln_s; p.ln_stats = ln_stats;
-    return launch_igemm(p, false, EPI_LINEAR, S(stream));
+    return op_launch(p, false, EPI_LINEAR, S(stream));      // (unsplit: a LayerNorm fold)
 }
 
 int lavie_lora_merge_f16(const void* W0, const float* A, const float* B, void* out, int N, int K, int r, float scale, void* stream) {
@@ -126,35 +127,16 @@ int lavie_conv3x3_f16(const void* x1, int C1, const void* x2, int C2, const void
                 "conv3x3: channel counts must be multiples of %d", IGEMM_BK);
     LAVIE_CHECK((!SC1 && !SC2) || (stride == 1 && !ups), "conv3x3: fused shortcut needs stride 1, no upsample");
     LAVIE_CHECK(!bias2 || rows_per_batch > 0, "conv3x3: bias2 needs rows_per_batch > 0");
-    IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.W = H(Wp); p.C = H(y); p.ldc = Cout; p.bias = bias; p.bias2 = bias2; p.ldb2 = ldb2;
-    p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
-    p.R = H(R); p.ldr = Cout;
-    p.Hi = Hi; p.Wi = Wi; p.stride = stride; p.ups = ups;
-    p.Ho = ups ? Hi * 2 : (Hi - 1) / stride + 1;
-    p.Wo = ups ? Wi * 2 : (Wi - 1) / stride + 1;
-    p.M = NI * p.Ho * p.Wo; p.N = Cout; p.zero = H(zero_page);
-    int ns = 0, nk = 0;
     const half_t* src[2] = {H(x1), H(x2)};
     const int srcC[2] = {C1, x2 ? C2 : 0};
-    for (int i = 0; i < 2; ++i) {
-        if (!srcC[i]) continue;
-        IgemmSeg& sg = p.seg[ns++];
-        sg.src = src[i]; sg.C = srcC[i]; sg.c0 = 0; sg.nchunks = srcC[i] / IGEMM_BK; sg.ntaps = 9;
-        nk += 9 * sg.nchunks;
-    }
     const half_t* sc[2] = {H(sc1), H(sc2)};
     const int scC[2] = {sc1 ? SC1 : 0, sc2 ? SC2 : 0};
-    for (int i = 0; i < 2; ++i) {
-        if (!scC[i]) continue;
-        IgemmSeg& sg = p.seg[ns++];
-        sg.src = sc[i]; sg.C = scC[i]; sg.c0 = 0; sg.nchunks = scC[i] / IGEMM_BK; sg.ntaps = 1;
-        nk += sg.nchunks;
-    }
-    p.nseg = ns; p.nk = nk; p.ldw = nk * IGEMM_BK;
-    if (int rc = op_slab(p, EPI_LINEAR, true)) return rc;
-    return launch_igemm(p, true, EPI_LINEAR, S(stream));
+    IgemmParams p;
+    if (int rc = igemm_setup_conv3x3(&p, src, srcC, 2, sc, scC, 2, H(Wp), 9 * (srcC[0] + srcC[1]) + scC[0] + scC[1], H(y), NI, Hi, Wi,
+                                     Cout, stride, ups, H(zero_page)))
+        return rc;
+    p.bias = bias; p.bias2 = bias2; p.ldb2 = ldb2; p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1; p.R = H(R);
+    return op_launch(p, true, EPI_LINEAR, S(stream));
 }
 
 int lavie_pack_conv3x3_parity_f16(const void* w, void* out, int Cout, int Cin, void* stream) {
@@ -171,16 +153,7 @@ int lavie_upsample_conv3x3_f16(const void* x, const void* wpar, const float* bia
     IgemmParams p;
     LAVIE_CHECK(igemm_setup_parity_upsample(&p, H(x), C, H(wpar), bias, H(y), NI, Hi, Wi, H(zero_page)),
                 "upsample_conv3x3: NI=%d %dx%d C=%d is outside the parity kernel's geometry (lavie_upsample_conv3x3_supported)", NI, Hi, Wi, C);
-    if (p.splits > 1) {
-        const size_t need = (size_t)p.splits * p.M * p.N * sizeof(float);
-        if (need > g_slab_bytes) {
-            if (g_slab) { LAVIE_HIP(hipDeviceSynchronize()); LAVIE_HIP(hipFree(g_slab)); g_slab = nullptr; g_slab_bytes = 0; }
-            LAVIE_HIP(hipMalloc((void**)&g_slab, need));
-            g_slab_bytes = need;
-        }
-        p.slab = g_slab;
-    }
-    return launch_igemm(p, true, EPI_LINEAR, S(stream));
+    return op_launch(p, true, EPI_LINEAR, S(stream));
 }
 
 int lavie_pack_conv3x3_f16(const void* w, void* out, int Cout, int Cin, int ld_out, int col0, void* stream) {
@@ -207,8 +180,7 @@ int lavie_temporal_conv_f16(const void* x, int C, const void* Wp, const float* b
     IgemmSeg& sg = p.seg[0];
     sg.src = H(x); sg.C = C; sg.c0 = 0; sg.nchunks = C / IGEMM_BK; sg.ntaps = taps;
     p.nseg = 1; p.nk = taps * sg.nchunks; p.ldw = p.nk * IGEMM_BK;
-    if (int rc = op_slab(p, EPI_LINEAR, true)) return rc;
-    return launch_igemm(p, true, EPI_LINEAR, S(stream));
+    return op_launch(p, true, EPI_LINEAR, S(stream));
 }
 
 int lavie_pack_temporal_conv_f16(const void* w, void* out, int Cout, int Cin, int taps, void* stream) {

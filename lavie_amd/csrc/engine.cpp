@@ -685,10 +685,9 @@ struct LnFold {            // consumer side of a folded LayerNorm
     int slots = 0, row_len = 0, rows = 0;
     bool final_ok = false;             // `stats` holds the finalized (mean, rstd) of the current rows
 };
-struct RowStat {           // producer side: partials [M, slots, 2] -> (mean, rstd) [M, 2]
+struct RowStat {           // producer side: partials [M, slots, 2] -> (mean, rstd) [M, 2]; slots = one per wave tile of the producer's plan
     float* partials;
     float* mean_rstd;
-    int slots;
     LnFold* sink = nullptr;            // told where the partials are (no finalize launch); nullptr = finalize at once
 };
 
@@ -697,71 +696,63 @@ struct RowStat {           // producer side: partials [M, slots, 2] -> (mean, rs
 // travels WITH the tensor through the wiring below (explicitly, never keyed by address: workspace addresses are reused).
 static size_t colstat_floats(size_t M, int C) { return (M / COLSTAT_REDUCE_ROWS + 8) * (size_t)C * 2; }
 static bool colstat_on() { return (fused_mask() & 32) != 0; }
-// plan: which block height will the launch of `p` write (0 = none), and describe the result
-static void colstat_plan(IgemmParams& p, bool gather, float* buf, GnColStat* out) {
-    if (out) *out = GnColStat();
+// One implicit GEMM on the forward's stream: plan it, describe its column statistics (cs_buf / cs_out, when asked for), take the
+// split-K slab from the workspace, launch unless this is the dry run.  The dry run passes placeholder addresses and so gets the
+// plan of the real call.  *plan_out (optional) receives the plan.
+static int run_igemm(FwdCtx& c, IgemmParams& p, bool gather, int epilogue, float* cs_buf, GnColStat* cs_out, IgemmPlan* plan_out = nullptr) {
+    const IgemmPlan plan = igemm_plan(p, gather, epilogue);
+    p.splits = plan.splits;
     p.colstat_out = nullptr;
-    p.colstat_rows = 0;
-    if (!buf || !out || !colstat_on()) return;
-    const int rows = igemm_colstat_rows(p, gather, EPI_LINEAR);
-    if (rows <= 0) return;
-    p.colstat_out = buf;
-    p.colstat_rows = rows;
-    out->partials = buf;
-    out->C = p.N;
-    out->rows = rows;
-    out->span = igemm_colstat_span(p, gather, rows);
-    if (p.par_ups && p.splits == 1) { out->nsets = 4; out->set_blocks = p.M / 4 / rows; }     // source-row blocks per output parity
-    else { out->nsets = 1; out->set_blocks = cdiv(p.M, rows); }                               // (split-K: the reduce kernel walks output rows)
+    if (cs_out) *cs_out = GnColStat();
+    if (cs_buf && cs_out && colstat_on() && plan.colstat_rows > 0) {
+        p.colstat_out = cs_buf;
+        cs_out->partials = cs_buf;
+        cs_out->C = p.N;
+        cs_out->rows = plan.colstat_rows;
+        cs_out->span = plan.colstat_span;
+        if (p.par_ups && p.splits == 1) { cs_out->nsets = 4; cs_out->set_blocks = p.M / 4 / plan.colstat_rows; }   // source-row blocks per output parity
+        else { cs_out->nsets = 1; cs_out->set_blocks = cdiv(p.M, plan.colstat_rows); }                            // (split-K: the reduce kernel walks output rows)
+    }
+    const size_t mark = c.ws->mark();
+    if (p.splits > 1) {
+        p.slab = (float*)c.ws->alloc((size_t)p.splits * p.M * p.N * sizeof(float));
+        LAVIE_CHECK(c.dry || p.slab != nullptr, "workspace exhausted (split-K slab)");
+    }
+    const int rc = c.dry ? 0 : launch_igemm(p, plan, c.s);
+    c.ws->release(mark);
+    if (plan_out) *plan_out = plan;
+    return rc;
 }
 
 static int linear(FwdCtx& c, const half_t* A, int lda, const half_t* W, const float* bias, int N, int K, const half_t* R,
                   half_t* C, int ldc, int M, int epilogue = EPI_LINEAR, LnFold* fold = nullptr,
                   const RowStat* rowstat = nullptr, int ldw = 0, float* cs_buf = nullptr, GnColStat* cs_out = nullptr) {
-    const bool unsplit = fold != nullptr || rowstat != nullptr;
-    if (cs_out) *cs_out = GnColStat();
-    if (c.dry) {   // plan the split-K slab so that prepare() sizes the workspace for it
-        const int s = unsplit ? 1 : igemm_plan_splits(M, N, K / IGEMM_BK, epilogue);
-        if (s > 1) {
-            const size_t mark = c.ws->mark();
-            (void)c.ws->alloc((size_t)s * M * N * sizeof(float));
-            c.ws->release(mark);
-        }
-        return 0;
-    }
+    LAVIE_CHECK(K % IGEMM_BK == 0, "linear: K=%d must be a multiple of %d", K, IGEMM_BK);
     IgemmParams p;
     memset(&p, 0, sizeof(p));
     p.A = A; p.lda = lda; p.W = W; p.ldw = ldw > 0 ? ldw : K; p.C = C; p.ldc = ldc; p.bias = bias; p.R = R; p.ldr = ldc;
     p.M = M; p.N = N; p.nk = K / IGEMM_BK;
-    LAVIE_CHECK(K % IGEMM_BK == 0, "linear: K=%d must be a multiple of %d", K, IGEMM_BK);
-    p.splits = unsplit ? 1 : igemm_plan_splits(M, N, p.nk, epilogue);
     p.rowstat_out = rowstat ? rowstat->partials : nullptr;
-    p.rowstat_cols = rowstat ? N / rowstat->slots : 0;
     if (fold) {
         p.ln_s = fold->s;
         if (fold->partials && !fold->final_ok) {           // the producer left its partials: finalize now, once
-            RUN(launch_rowstat_finalize(fold->partials, fold->slots, fold->rows, fold->row_len, 1e-5f, fold->stats, c.s));
+            LAUNCH(launch_rowstat_finalize(fold->partials, fold->slots, fold->rows, fold->row_len, 1e-5f, fold->stats, c.s));
             fold->final_ok = true;
         }
         p.ln_stats = fold->stats;
     }
-    if (epilogue == EPI_LINEAR && ldc == N) colstat_plan(p, false, cs_buf, cs_out);
-    const size_t mark = c.ws->mark();
-    if (p.splits > 1) {
-        p.slab = (float*)c.ws->alloc((size_t)p.splits * M * N * sizeof(float));
-        LAVIE_CHECK(p.slab != nullptr, "workspace exhausted (split-K slab)");
-    }
-    int rc = launch_igemm(p, false, epilogue, c.s);
-    if (rc == 0 && rowstat) {
+    IgemmPlan plan;
+    RUN(run_igemm(c, p, false, epilogue, epilogue == EPI_LINEAR && ldc == N ? cs_buf : nullptr, cs_out, &plan));
+    if (rowstat) {
+        const int slots = N / plan.rowstat_cols;      // one slot per wave tile of the kernel that ran
         if (rowstat->sink) {       // deferred: the consumer decides (see above)
-            rowstat->sink->partials = rowstat->partials; rowstat->sink->slots = rowstat->slots; rowstat->sink->row_len = N;
+            rowstat->sink->partials = rowstat->partials; rowstat->sink->slots = slots; rowstat->sink->row_len = N;
             rowstat->sink->rows = M; rowstat->sink->final_ok = false;
         } else {
-            rc = launch_rowstat_finalize(rowstat->partials, rowstat->slots, M, N, 1e-5f, rowstat->mean_rstd, c.s);
+            LAUNCH(launch_rowstat_finalize(rowstat->partials, slots, M, N, 1e-5f, rowstat->mean_rstd, c.s));
         }
     }
-    c.ws->release(mark);
-    return rc;
+    return 0;
 }
 
 // 3x3 conv (pad 1) over `nsrc` channel-concatenated sources, plus optional centre-tap shortcut sources.
@@ -770,42 +761,9 @@ static int conv3x3(FwdCtx& c, const half_t* const* src, const int* srcC, int nsr
                    const half_t* R, half_t* y, int NI, int Hi, int Wi, int Cout, int stride, int ups, const half_t* zero,
                    float* cs_buf = nullptr, GnColStat* cs_out = nullptr) {
     IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.W = W; p.ldw = ldw; p.C = y; p.ldc = Cout; p.bias = bias; p.bias2 = bias2; p.ldb2 = ldb2;
-    p.rows_per_batch = rows_per_batch; p.R = R; p.ldr = Cout;
-    p.Hi = Hi; p.Wi = Wi; p.stride = stride; p.ups = ups;
-    p.Ho = ups ? Hi * 2 : (Hi - 1) / stride + 1;
-    p.Wo = ups ? Wi * 2 : (Wi - 1) / stride + 1;
-    p.M = NI * p.Ho * p.Wo;
-    p.N = Cout;
-    p.zero = zero;
-    int ns = 0, nk = 0;
-    LAVIE_CHECK(nsrc + nsc <= IGEMM_MAX_SEG, "conv3x3: too many K segments");
-    for (int i = 0; i < nsrc; ++i) {
-        LAVIE_CHECK(srcC[i] % IGEMM_BK == 0, "conv3x3: channel count %d must be a multiple of %d", srcC[i], IGEMM_BK);
-        IgemmSeg& sg = p.seg[ns++];
-        sg.src = src[i]; sg.C = srcC[i]; sg.c0 = 0; sg.nchunks = srcC[i] / IGEMM_BK; sg.ntaps = 9;
-        nk += 9 * sg.nchunks;
-    }
-    for (int i = 0; i < nsc; ++i) {
-        LAVIE_CHECK(scC[i] % IGEMM_BK == 0 && stride == 1 && ups == 0, "conv3x3: bad shortcut source");
-        IgemmSeg& sg = p.seg[ns++];
-        sg.src = sc[i]; sg.C = scC[i]; sg.c0 = 0; sg.nchunks = scC[i] / IGEMM_BK; sg.ntaps = 1;
-        nk += sg.nchunks;
-    }
-    LAVIE_CHECK(nk * IGEMM_BK <= ldw, "conv3x3: weight row length %d is shorter than the gathered K %d", ldw, nk * IGEMM_BK);
-    p.nseg = ns;
-    p.nk = nk;
-    p.splits = igemm_plan_splits_gather(p);        // also picks the kernel: same inputs -> same choice in the dry run
-    colstat_plan(p, true, cs_buf, cs_out);
-    const size_t mark = c.ws->mark();
-    if (p.splits > 1) {
-        p.slab = (float*)c.ws->alloc((size_t)p.splits * p.M * p.N * sizeof(float));
-        if (!c.dry) LAVIE_CHECK(p.slab != nullptr, "workspace exhausted (split-K slab)");
-    }
-    const int rc = c.dry ? 0 : launch_igemm(p, true, EPI_LINEAR, c.s);
-    c.ws->release(mark);
-    return rc;
+    RUN(igemm_setup_conv3x3(&p, src, srcC, nsrc, sc, scC, nsc, W, ldw, y, NI, Hi, Wi, Cout, stride, ups, zero));
+    p.bias = bias; p.bias2 = bias2; p.ldb2 = ldb2; p.rows_per_batch = rows_per_batch; p.R = R;
+    return run_igemm(c, p, true, EPI_LINEAR, cs_buf, cs_out);
 }
 
 // (taps,1,1) temporal conv over the frame axis of token rows [(b f d), C] (IgemmParams temporal mode; 128-row kernel).
@@ -824,16 +782,7 @@ static int tconv(FwdCtx& c, const half_t* x, int C, const half_t* W, const float
     sg.src = x; sg.C = C; sg.c0 = 0; sg.nchunks = C / IGEMM_BK; sg.ntaps = taps;
     p.nseg = 1;
     p.nk = taps * sg.nchunks;
-    p.splits = igemm_plan_splits_gather(p);
-    colstat_plan(p, true, cs_buf, cs_out);          // (round 4) the GroupNorm behind a temporal conv folds its epilogue's sums too
-    const size_t mark = c.ws->mark();
-    if (p.splits > 1) {
-        p.slab = (float*)c.ws->alloc((size_t)p.splits * p.M * p.N * sizeof(float));
-        if (!c.dry) LAVIE_CHECK(p.slab != nullptr, "workspace exhausted (split-K slab)");
-    }
-    const int rc = c.dry ? 0 : launch_igemm(p, true, EPI_LINEAR, c.s);
-    c.ws->release(mark);
-    return rc;
+    return run_igemm(c, p, true, EPI_LINEAR, cs_buf, cs_out);      // (round 4) the GroupNorm behind a temporal conv folds its epilogue's sums too
 }
 
 // ResnetBlock3DCNN (vsr/models/resnet.py:283-315): y = x + conv2(silu(gn(conv1(silu(gn(x))) + temb))); GroupNorm statistics
@@ -986,7 +935,7 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
     const bool fused_x = t.xb_tmpl != nullptr && kv_cached && xb_bound_ && xb_img_[ti] != nullptr && (ff_first ? fused_ff : fused_t) &&
                          !t.attn1_cross && (fused_mask() & 4) && cross_block_supported(C, heads, c.ctx_len, c.F * D);
     LnFold lf{nullptr, nullptr};
-    RowStat rsd{nullptr, nullptr, C / igemm_rowstat_cols(T, C, C / IGEMM_BK), &lf};
+    RowStat rsd{nullptr, nullptr, &lf};
     const RowStat* rowstat = nullptr;
     if (fold) {
         WS(rsp, float, (size_t)T * (C / 32) * 2);
@@ -996,9 +945,7 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
         lf.stats = rsm;
         rowstat = &rsd;
     }
-    RowStat rsd_pin = rsd;                 // the producer's slot width follows the kernel the planner picks for ITS row count
-    rsd_pin.slots = C / igemm_rowstat_cols(Tp, C, C / IGEMM_BK);
-    if (!fused_pq) RUN(linear(c, ln, C, t.pin.w, t.pin.b, C, C, nullptr, tx, C, Tp, EPI_LINEAR, nullptr, rowstat ? &rsd_pin : nullptr));
+    if (!fused_pq) RUN(linear(c, ln, C, t.pin.w, t.pin.b, C, C, nullptr, tx, C, Tp, EPI_LINEAR, nullptr, rowstat));
     if (!shared_prefix) TRACE("block.proj_in", tx, T, C);
 
     if (t.attn1_cross) {
@@ -1078,9 +1025,6 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
 
     // base block order: temporal -> feed-forward (attention.py:548-560); interpolation block: feed-forward -> temporal
     // (interpolation/models/attention.py:592-604)
-    RowStat rsd_ff2 = rsd;
-    rsd_ff2.slots = C / igemm_rowstat_cols(T, C, 4 * C / IGEMM_BK);
-    const RowStat* rowstat_ff2 = rowstat ? &rsd_ff2 : nullptr;
     auto temporal = [&]() -> int {
         // temporal self-attention over frames, tokens stay in (b f) d order (attention.py:548-555)
         if (fused_t) {         // norm_temp -> q|k|v -> rotary / bias / softmax / PV -> to_out -> + residual in ONE kernel, in place
@@ -1129,7 +1073,7 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
         }
         // interpolation order: norm_temp consumes this GEMM's output, so it emits the row statistics (K = 4C: the
         // planner may pick another kernel than for the K = C producers, hence its own slot count)
-        RUN(linear(c, wide, 4 * C, t.ff2.w, t.ff2.b, C, 4 * C, tx, tx, C, T, EPI_LINEAR, nullptr, ff_first ? rowstat_ff2 : nullptr));
+        RUN(linear(c, wide, 4 * C, t.ff2.w, t.ff2.b, C, 4 * C, tx, tx, C, T, EPI_LINEAR, nullptr, ff_first ? rowstat : nullptr));
         return 0;
     };
     if (ff_first) {
@@ -1161,17 +1105,7 @@ int UNet::run_conv(FwdCtx& c, const half_t* x, int C, const SamplerW& w, half_t*
         // Upsample3D (resnet.py:44-79): the 3x3 conv of the nearest-x2 image as four 2x2 convs on the source image, one per
         // output parity, on the halo-patch kernel (igemm_patch.hip MODE 3): 4 C instead of 9 C multiply-adds per output element
         IgemmParams p;
-        if (igemm_setup_parity_upsample(&p, x, C, w.wpar, w.b, y, c.B * c.F, Hi, Wi, zero_page_)) {
-            colstat_plan(p, true, cs_buf, cs_out);
-            const size_t mark = c.ws->mark();
-            if (p.splits > 1) {
-                p.slab = (float*)c.ws->alloc((size_t)p.splits * p.M * p.N * sizeof(float));
-                if (!c.dry) LAVIE_CHECK(p.slab != nullptr, "workspace exhausted (split-K slab)");
-            }
-            const int rc = c.dry ? 0 : launch_igemm(p, true, EPI_LINEAR, c.s);
-            c.ws->release(mark);
-            return rc;
-        }
+        if (igemm_setup_parity_upsample(&p, x, C, w.wpar, w.b, y, c.B * c.F, Hi, Wi, zero_page_)) return run_igemm(c, p, true, EPI_LINEAR, cs_buf, cs_out);
     }
     return conv3x3(c, src, srcC, 1, nullptr, nullptr, 0, w.w, 9 * C, w.b, nullptr, 0, 1, nullptr, y, c.B * c.F, Hi, Wi, C, stride,
                    ups, zero_page_, cs_buf, cs_out);

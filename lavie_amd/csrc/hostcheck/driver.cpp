@@ -2,6 +2,8 @@
 // create -> parameter inventory -> set_param -> finalize (weight packing, arena carving) -> prepare (workspace dry run over every
 // switch combination) -> cache_context -> forward (sequencing + every launcher's host side) -> error paths -> destroy, for the
 // base, interpolation and VSR variants of the engine at reduced widths.  Exit code 0 and a silent sanitizer = pass.
+// `hostcheck trace FILE` instead writes the launch trace of the cases in run_traces() to FILE (tests/golden/make_golden_trace.py).
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -11,6 +13,7 @@
 #include "../../../include/lavie_hip.h"
 
 extern "C" long lavie_hostcheck_launches();
+extern "C" void lavie_hostcheck_trace_to(FILE* f);
 
 #define REQUIRE(cond)                                                                          \
     do {                                                                                       \
@@ -115,7 +118,173 @@ static void run_model(const lavie_unet_config& cfg, int B, int F, int H, int W, 
     for (void* p : bufs) free(p);
 }
 
-int main() {
+// ---- launch trace (hip_stub.cpp): every launch of the cases below, each case headed by a "== name" line
+static FILE* g_out = nullptr;
+__attribute__((format(printf, 1, 2))) static void trace_case(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    fprintf(g_out, "== ");
+    vfprintf(g_out, fmt, ap);
+    fprintf(g_out, "\n");
+    va_end(ap);
+}
+
+struct Model {      // a finalized engine with zero weights
+    lavie_unet_t h = nullptr;
+    std::vector<void*> bufs;
+    explicit Model(const lavie_unet_config& cfg) {
+        REQUIRE(lavie_unet_create(&cfg, &h) == 0);
+        const int n = lavie_unet_num_params(h);
+        for (int i = 0; i < n; ++i) {
+            const char* name = nullptr;
+            long long numel = 0;
+            REQUIRE(lavie_unet_param_info(h, i, &name, &numel) == 0);
+            bufs.push_back(calloc((size_t)numel, 2));
+            REQUIRE(lavie_unet_set_param(h, name, bufs.back(), numel) == 0);
+        }
+        REQUIRE(lavie_unet_finalize(h, nullptr) == 0);
+    }
+    ~Model() {
+        REQUIRE(lavie_unet_destroy(h) == 0);
+        for (void* p : bufs) free(p);
+    }
+};
+
+// prepare for the shape (the switches in force decide the workspace plan), then one forward: cached context and shared
+// classifier-free-guidance prefix where the variant allows them, labels for a class-embedded model
+static void trace_forward(const lavie_unet_config& cfg, Model& m, int B, int F, int H, int W, bool cached, bool shared) {
+    REQUIRE(lavie_unet_prepare(m.h, B, F, H, W, 77) == 0);
+    std::vector<unsigned short> x((size_t)B * cfg.in_channels * F * H * W), y((size_t)B * cfg.out_channels * F * H * W);
+    std::vector<unsigned short> ctx((size_t)B * 77 * cfg.cross_attention_dim);
+    std::vector<float> t(B, 500.f);
+    std::vector<int> lab(B, 3);
+    if (cached) REQUIRE(lavie_unet_cache_context(m.h, ctx.data(), B, 77, nullptr) == 0);
+    REQUIRE(lavie_unet_set_cfg_shared_input(m.h, shared ? 1 : 0) == 0);
+    const int rc = cfg.num_class_embeds
+                       ? lavie_unet_forward_labels(m.h, x.data(), t.data(), ctx.data(), lab.data(), y.data(), B, F, H, W, 77, nullptr)
+                       : lavie_unet_forward(m.h, x.data(), t.data(), ctx.data(), y.data(), B, F, H, W, 77, nullptr);
+    if (rc != 0) {       // a launch the library refuses ends the forward: recorded, the message goes to stderr
+        fprintf(g_out, "!! forward refused\n");
+        fprintf(stderr, "hostcheck trace: forward refused: %s\n", lavie_last_error());
+    }
+    REQUIRE(lavie_unet_set_cfg_shared_input(m.h, 0) == 0);
+    if (cached) REQUIRE(lavie_unet_cache_context(m.h, nullptr, 0, 0, nullptr) == 0);
+}
+
+// the operator entry points at level shapes of the base model (B * F = 32 frames of 40 x 64 latents); tensors are never read
+static void trace_operators() {
+    static std::vector<unsigned short> buf(64);
+    void* d = buf.data();
+    const int lin[][3] = {{81920, 320, 320}, {81920, 960, 320}, {81920, 320, 1280}, {20480, 640, 640}, {20480, 640, 2560},
+                          {5120, 1280, 1280}, {5120, 3840, 1280}, {5120, 1280, 5120}, {2464, 1280, 768}};
+    for (const auto& s : lin) {
+        trace_case("op linear M=%d N=%d K=%d", s[0], s[1], s[2]);
+        REQUIRE(lavie_linear_f16(d, s[2], d, nullptr, nullptr, 0, 0, nullptr, 0, d, s[1], s[0], s[1], s[2], 0, nullptr) == 0);
+        REQUIRE(lavie_linear_f16(d, s[2], d, nullptr, nullptr, 0, 0, d, s[1], d, s[1], s[0], s[1], s[2], 0, nullptr) == 0);
+    }
+    const int geglu[][3] = {{81920, 2560, 320}, {20480, 5120, 640}, {5120, 10240, 1280}};
+    for (const auto& s : geglu) {
+        trace_case("op geglu M=%d N=%d K=%d", s[0], s[1], s[2]);
+        REQUIRE(lavie_linear_f16(d, s[2], d, nullptr, nullptr, 0, 0, nullptr, 0, d, s[1] / 2, s[0], s[1], s[2], 1, nullptr) == 0);
+    }
+    // {H, W, C1, C2 (skip), SC1 (shortcut), Cout, stride, ups}
+    const int conv[][8] = {{40, 64, 320, 0, 0, 320, 1, 0},   {40, 64, 320, 320, 0, 320, 1, 0}, {40, 64, 640, 320, 640, 320, 1, 0},
+                           {40, 64, 320, 0, 0, 320, 2, 0},   {20, 32, 640, 0, 0, 640, 1, 0},   {20, 32, 1280, 640, 0, 640, 1, 0},
+                           {10, 16, 1280, 0, 0, 1280, 1, 0}, {10, 16, 1280, 0, 0, 1280, 2, 0}, {5, 8, 1280, 0, 0, 1280, 1, 0},
+                           {5, 8, 1280, 0, 0, 1280, 1, 1},   {20, 32, 640, 0, 0, 640, 1, 1}};
+    for (const auto& s : conv) {
+        trace_case("op conv3x3 %dx%d C=%d+%d shortcut=%d Cout=%d stride=%d ups=%d", s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7]);
+        REQUIRE(lavie_conv3x3_f16(d, s[2], s[3] ? d : nullptr, s[3], s[4] ? d : nullptr, s[4], nullptr, 0, d, nullptr, nullptr, 0, 1,
+                                  nullptr, d, 32, s[0], s[1], s[5], s[6], s[7], d, nullptr) == 0);
+    }
+    const int ups[][3] = {{5, 8, 1280}, {10, 16, 1280}, {20, 32, 640}};
+    for (const auto& s : ups) {
+        trace_case("op upsample_conv3x3 %dx%d C=%d", s[0], s[1], s[2]);
+        REQUIRE(lavie_upsample_conv3x3_f16(d, d, nullptr, d, 32, s[0], s[1], s[2], d, nullptr) == 0);
+    }
+}
+
+static lavie_unet_config production_config() {        // the base model: 4 levels 320 / 640 / 1280 / 1280
+    lavie_unet_config c = base_config();
+    c.num_levels = 4;
+    const int w[4] = {320, 640, 1280, 1280}, a[4] = {1, 1, 1, 0};
+    for (int i = 0; i < 4; ++i) { c.block_out_channels[i] = w[i]; c.attn_levels[i] = a[i]; }
+    c.cross_attention_dim = 768;
+    return c;
+}
+
+static void run_traces(const char* path) {
+    g_out = fopen(path, "w");
+    REQUIRE(g_out != nullptr);
+    lavie_hostcheck_trace_to(g_out);
+    {   // base model at the production shape: every force_tile mode, forced split-K, fused mask 0x30 besides the default
+        const lavie_unet_config cfg = production_config();
+        trace_case("base finalize");
+        Model m(cfg);
+        for (int mode = 0; mode <= 9; ++mode) {
+            REQUIRE(lavie_debug_force_tile(mode) == 0);
+            trace_case("base force_tile=%d", mode);
+            trace_forward(cfg, m, 2, 16, 40, 64, true, true);
+        }
+        REQUIRE(lavie_debug_force_tile(0) == 0);
+        for (int s = 2; s <= 3; ++s) {
+            REQUIRE(lavie_debug_force_splits(s) == 0);
+            trace_case("base force_splits=%d", s);
+            trace_forward(cfg, m, 2, 16, 40, 64, true, true);
+        }
+        REQUIRE(lavie_debug_force_splits(0) == 0);
+        REQUIRE(lavie_debug_fused_mask(0x30) == 0);
+        trace_case("base fused_mask=0x30");
+        trace_forward(cfg, m, 2, 16, 40, 64, true, true);
+        REQUIRE(lavie_debug_fused_mask(0x137) == 0);
+    }
+    {   // interpolation model: 61 frames, eight input channels
+        lavie_unet_config cfg = production_config();
+        cfg.in_channels = 8; cfg.sparse_causal_attn1 = 1; cfg.temporal_plain = 1; cfg.ff_before_temporal = 1;
+        trace_case("interpolation");
+        Model m(cfg);
+        trace_forward(cfg, m, 2, 61, 40, 64, true, false);
+    }
+    {   // VSR UNet: 256 / 512 / 512 / 1024, noise-level labels, 8 frames at 320 x 512
+        lavie_unet_config cfg = production_config();
+        const int w[4] = {256, 512, 512, 1024}, a[4] = {0, 1, 1, 1}, oc[4] = {1, 1, 1, 0};
+        for (int i = 0; i < 4; ++i) { cfg.block_out_channels[i] = w[i]; cfg.attn_levels[i] = a[i]; cfg.only_cross_attention[i] = oc[i]; }
+        cfg.in_channels = 8; cfg.cross_attention_dim = 1024; cfg.vsr_blocks = 1; cfg.vsr_temporal_modules = 1; cfg.num_class_embeds = 1000;
+        trace_case("vsr 8 frames 320x512");
+        Model m(cfg);
+        trace_forward(cfg, m, 2, 8, 320, 512, false, false);
+    }
+    {   // the reduced variants of the sanitizer run
+        lavie_unet_config interp = base_config();
+        interp.in_channels = 8; interp.sparse_causal_attn1 = 1; interp.temporal_plain = 1; interp.ff_before_temporal = 1;
+        lavie_unet_config vsr = base_config();
+        vsr.in_channels = 8; vsr.block_out_channels[0] = 256; vsr.block_out_channels[1] = 512; vsr.attn_levels[1] = 1;
+        vsr.vsr_blocks = 1; vsr.only_cross_attention[0] = 1; vsr.vsr_temporal_modules = 1; vsr.num_class_embeds = 10;
+        struct { const char* name; lavie_unet_config cfg; int B, F, H, W; bool cached, shared; } cases[] = {
+            {"reduced base", base_config(), 2, 16, 16, 16, true, true}, {"reduced base odd batch", base_config(), 1, 4, 8, 8, false, false},
+            {"reduced interpolation", interp, 2, 7, 8, 8, true, false}, {"reduced vsr", vsr, 2, 4, 8, 8, false, false}};
+        for (auto& c : cases) {
+            trace_case("%s", c.name);
+            Model m(c.cfg);
+            trace_forward(c.cfg, m, c.B, c.F, c.H, c.W, c.cached, c.shared);
+        }
+    }
+    for (int mode = 0; mode <= 9; ++mode) {
+        REQUIRE(lavie_debug_force_tile(mode) == 0);
+        trace_case("operators force_tile=%d", mode);
+        trace_operators();
+    }
+    REQUIRE(lavie_debug_force_tile(0) == 0);
+    lavie_hostcheck_trace_to(nullptr);
+    fclose(g_out);
+    printf("hostcheck: trace written (%ld stubbed kernel launches)\n", lavie_hostcheck_launches());
+}
+
+int main(int argc, char** argv) {
+    if (argc == 3 && strcmp(argv[1], "trace") == 0) {
+        run_traces(argv[2]);
+        return 0;
+    }
     REQUIRE(lavie_abi_version() == LAVIE_ABI_VERSION);
     {   // argument checks of create
         lavie_unet_config c = base_config();

@@ -5,9 +5,13 @@
 // hipMemcpy* bounds-checked by ASan against the exact-size heap blocks behind it.  Never linked into liblavie_hip.so.
 #include <hip/hip_runtime_api.h>
 
+#include <cxxabi.h>
+
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <string>
 
 extern "C" {
 
@@ -49,22 +53,56 @@ hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* shmem, hip
     *grid = g_cfg.grid; *block = g_cfg.block; *shmem = g_cfg.shmem; *stream = g_cfg.stream;
     return hipSuccess;
 }
+// Launch trace: one line per launch (kernel, grid, block, dynamic LDS) to g_trace.  The driver's `trace` mode points it at a file;
+// LAVIE_HOSTCHECK_TRACE=1 sends it to stderr.  Kernel names come from clang's registration calls.
 static long g_launches = 0;
+static FILE* g_trace = getenv("LAVIE_HOSTCHECK_TRACE") ? stderr : nullptr;
+static std::map<const void*, std::string>& kernel_names() { static std::map<const void*, std::string> m; return m; }
+static const char* kernel_name(const void* f) {
+    auto it = kernel_names().find(f);
+    return it == kernel_names().end() ? "?" : it->second.c_str();
+}
 hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void**, size_t shmem, hipStream_t) {
     // the launch geometry itself is host logic worth checking
-    if (grid.x == 0 || grid.y == 0 || grid.z == 0 || block.x * block.y * block.z == 0 || block.x * block.y * block.z > 1024 ||
-        shmem > 160 * 1024) abort();
+    const char* bad = grid.x == 0 || grid.y == 0 || grid.z == 0          ? "empty grid"
+                      : block.x * block.y * block.z == 0               ? "empty block"
+                      : block.x * block.y * block.z > 1024             ? "more than 1024 threads per block"
+                      : shmem > 160 * 1024                             ? "dynamic LDS above 160 KiB"
+                                                                       : nullptr;
+    if (bad) {
+        fprintf(stderr, "hip_stub: launch of %s refused (%s): grid %u,%u,%u block %u,%u,%u lds %zu\n", kernel_name(f), bad, grid.x, grid.y,
+                grid.z, block.x, block.y, block.z, shmem);
+        abort();
+    }
     ++g_launches;
-    if (getenv("LAVIE_HOSTCHECK_TRACE")) fprintf(stderr, "launch %p\n", f);
+    if (g_trace) fprintf(g_trace, "%s %u,%u,%u %u,%u,%u %zu\n", kernel_name(f), grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
     return hipSuccess;
 }
 hipError_t hipExtLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, size_t shmem, hipStream_t s, hipEvent_t, hipEvent_t, int) {
     return hipLaunchKernel(f, grid, block, args, shmem, s);
 }
 long lavie_hostcheck_launches() { return g_launches; }
+void lavie_hostcheck_trace_to(FILE* f) { g_trace = f; }
 void** __hipRegisterFatBinary(const void*) { static void* h; return &h; }
 void __hipUnregisterFatBinary(void**) {}
-void __hipRegisterFunction(void**, const void*, char*, const char*, unsigned, void*, void*, void*, void*, int*) {}
+// kernel names: the demangled name without namespace, return type and parameter list, e.g. igemm_kernel<2, 2, 4, 5, 2, true, 0>
+void __hipRegisterFunction(void**, const void* f, char*, const char* mangled, unsigned, void*, void*, void*, void*, int*) {
+    std::string m = mangled;                         // the demangler does not know _Float16 (DF16_): spell it as half (Dh)
+    for (size_t i; (i = m.find("DF16_")) != std::string::npos;) m.replace(i, 5, "Dh");
+    int st = 0;
+    char* d = abi::__cxa_demangle(m.c_str(), nullptr, nullptr, &st);
+    std::string n = st == 0 && d ? d : mangled;
+    free(d);
+    if (n.compare(0, 5, "void ") == 0) n.erase(0, 5);
+    if (n.compare(0, 7, "lavie::") == 0) n.erase(0, 7);
+    int depth = 0;                                   // cut the parameter list: the first '(' outside template brackets
+    for (size_t i = 0; i < n.size(); ++i) {
+        if (n[i] == '<') ++depth;
+        else if (n[i] == '>') --depth;
+        else if (n[i] == '(' && depth == 0) { n.resize(i); break; }
+    }
+    kernel_names()[f] = n;
+}
 void __hipRegisterVar(void**, void*, char*, const char*, int, size_t, int, int) {}
 void __hipRegisterManagedVar(void*, void*, void*, const char*, size_t, unsigned) {}
 }

@@ -38,18 +38,15 @@ struct IgemmParams {
     // LayerNorm folding: a producer GEMM writes per-row partial (sum, sum of squares) of its fp16 output,
     // one pair per 16*NT-column wave tile: rowstat_out[m * rowstat_slots + slot]; the consumer GEMM runs on the RAW
     // rows with gamma folded into W and finishes  y = rstd_m (acc - mean_m s_n) + bias_n  in its epilogue.
-    float* rowstat_out;        // [M, N / rowstat_cols, 2] or nullptr (EPI_LINEAR, splits == 1 only)
-    int rowstat_cols;          // columns per slot the caller sized rowstat_out for (igemm_rowstat_cols); launch_igemm checks that
-                               // the kernel it selects writes slots of exactly this width (0 = unchecked)
+    float* rowstat_out;        // [M, N / IgemmPlan::rowstat_cols, 2] or nullptr (EPI_LINEAR, splits == 1 only)
     const float* ln_stats;     // [M, 2] (mean, rstd) of the A rows (launch_rowstat_finalize), or nullptr
     const float* ln_s;         // [N]: s_n = sum_k W'[n, k]
     // GroupNorm statistics from the producer (round 4): per (row block, channel) sum and sum of squares of the ROUNDED fp16 output,
     // written by the epilogue that stores the tensor (or by the split-K reduce), so that the consuming GroupNorm needs no statistics
     // pass over the tensor (resnet.py:180,191; attention.py:369; unet.py:504).  Layout (cs_index below): per block and channel quad
-    // four sums then four sums of squares.  A block = the rows of one wave tile (colstat_rows = 16 * MT of the kernel that runs, 32
-    // for the split-K reduce); the parity-form upsample conv writes four sets of source-row blocks (one per output parity).
+    // four sums then four sums of squares.  A block = the rows of one wave tile (IgemmPlan::colstat_rows = 16 * MT of the kernel that
+    // runs, 32 for the split-K reduce); the parity-form upsample conv writes four sets of source-row blocks (one per output parity).
     float* colstat_out;        // [sets][ceil(rows / colstat_rows)][N / 4][2][4] or nullptr (EPI_LINEAR only)
-    int colstat_rows;          // rows per block the caller planned for (igemm_colstat_rows); launch_igemm checks the kernel it picks
     int splits;           // split-K factor (1 = none); > 1 needs `slab`
     float* slab;          // [splits, M, N] fp32 partial sums
     // Gather geometry (GATHER = true): output pixel grid [NI, Ho, Wo], source grid [NI, Hi, Wi],
@@ -68,8 +65,37 @@ struct IgemmParams {
 
 enum IgemmEpilogue { EPI_LINEAR = 0, EPI_GEGLU = 1 };
 
-// Picks a tile and launches.  Returns 0 or a negative status with lavie::set_error().
-int launch_igemm(const IgemmParams& p, bool gather, int epilogue, hipStream_t stream);
+// The kernels of the family; the halo-patch kernel by its mode (igemm_patch.hip MODE 0 - 3).
+enum IgemmKernel {
+    IGEMM_TILE,              // 128-row kernel (this file's igemm_kernel), bn = 160 / 128 / 64; GEGLU: 128
+    IGEMM_PP,                // 160x320 ping-pong kernel (igemm_pp.hip), bn = 320, or 256 for the power-of-two widths
+    IGEMM_PP_GEGLU,          // its 160x256 GEGLU variant
+    IGEMM_PPX,               // persistent ping-pong kernel (igemm_ppx.hip), bn = 320 / 256
+    IGEMM_PATCH_ROWS,        // halo-patch 3x3 conv kernel, tiles of whole image rows
+    IGEMM_PATCH_2D,          // ... 2-D tiles (10 image rows x 32 columns)
+    IGEMM_PATCH_TEMPORAL,    // ... temporal (T,1,1) conv
+    IGEMM_PATCH_PARITY,      // ... parity form of the 3x3 conv of a nearest-x2 upsampled image
+};
+
+// Everything launch_igemm will do for one GEMM, decided once by igemm_plan.  The plan reads the shape, strides and segments of the
+// parameters, which optional operands are present (R, bias2, ln_stats, rowstat_out; never their addresses) and the force switches:
+// the workspace dry run, which passes placeholder addresses, gets the plan of the real call.
+struct IgemmPlan {
+    IgemmKernel kernel;
+    int bn;              // column-tile width of the kernel (0: N is not a multiple of 64, the launch is refused)
+    int splits;          // split-K factor: the caller sets p.splits to it and, when > 1, p.slab to splits * M * N floats
+    int rowstat_cols;    // columns per row-statistics slot: rowstat_out holds N / rowstat_cols slots per row
+    int colstat_rows;    // rows per column-statistics block: 80 (halo-patch, ping-pong and persistent kernels), 64 (128-row kernel),
+                         // 32 (split-K: the reduce kernel writes them), 0 = this launch cannot emit them (GEGLU)
+    int colstat_span;    // the aligned run of output rows inside which the rows of one block lie (GnColStat::span): the block height
+                         // for kernels whose wave tiles are contiguous rows; one frame for the halo-patch kernel's 2-D tiles and for
+                         // the parity-form upsample conv; one video for its temporal-conv tiles
+    bool gather;
+    int epilogue;
+};
+IgemmPlan igemm_plan(const IgemmParams& p, bool gather, int epilogue);
+// Launches the planned kernel (+ the split-K reduce).  Returns 0 or a negative status with lavie::set_error().
+int launch_igemm(const IgemmParams& p, const IgemmPlan& plan, hipStream_t stream);
 // 160x320 two-group ping-pong kernel (igemm_pp.hip); EPI_LINEAR only, N %% 320 == 0, the caller runs the split-K reduce.
 int launch_igemm_pp(const IgemmParams& p, bool gather, hipStream_t stream);
 int launch_igemm_pp_geglu(const IgemmParams& p, hipStream_t stream);   // 160x256 variant, GEGLU epilogue, N %% 256 == 0
@@ -81,24 +107,16 @@ int launch_igemm_ppx(const IgemmParams& p, int epilogue, hipStream_t stream);
 bool igemm_patch_eligible(const IgemmParams& p);
 int igemm_patch_bn(int N);                        // 160 / 128 / 0: column-tile width of the halo-patch kernel for N channels
 int launch_igemm_patch(const IgemmParams& p, hipStream_t stream);
-// parity form of conv3x3(nearest_x2(x)) (igemm_patch.hip MODE 3): fills p (incl. splits; the caller sets p->slab), false = not this geometry
+// Geometry of a 3x3 conv (pad 1, stride 1 / 2, `ups` = folded nearest-x2 upsample) y [NI, Ho, Wo, Cout] over the channel-concatenated
+// sources src[0..nsrc) (9-tap segments) and the centre-tap shortcut sources sc[0..nsc) (stride 1 only), sources of 0 channels
+// skipped; W rows of ldw halfs.  Fills p (zeroed first; rows_per_batch = 1, the caller adds bias, bias2, R).  0 or an error.
+int igemm_setup_conv3x3(IgemmParams* p, const half_t* const* src, const int* srcC, int nsrc, const half_t* const* sc, const int* scC,
+                        int nsc, const half_t* W, int ldw, half_t* y, int NI, int Hi, int Wi, int Cout, int stride, int ups,
+                        const half_t* zero);
+// parity form of conv3x3(nearest_x2(x)) (igemm_patch.hip MODE 3): fills p (geometry only; the caller sets p->slab), false = not this
+// geometry
 bool igemm_setup_parity_upsample(IgemmParams* p, const half_t* x, int C, const half_t* wpar, const float* bias, half_t* y, int NI, int Hi,
                                  int Wi, const half_t* zero);
-// Split-K factor the launcher would like for this problem (1 = none); slab size = splits * M * N floats.
-int igemm_plan_splits(int M, int N, int nk, int epilogue);
-// Same for a gathered conv whose geometry and K segments are filled in (M, N, nk, Ho, Wo, stride, ups, seg[], nseg):
-// also considers the halo-patch kernel.
-int igemm_plan_splits_gather(const IgemmParams& p);
-// wave-tile width (16*NT) launch_igemm will pick for a plain, unsplit EPI_LINEAR GEMM: the row-statistics slot width
-int igemm_rowstat_cols(int M, int N, int nk);
-// rows per column-statistics block of the kernel launch_igemm will run for `p` (geometry, segments and p.splits filled in):
-// 80 (halo-patch, ping-pong and persistent kernels), 64 (128-row kernel), 32 (split-K: the reduce kernel writes them),
-// 0 = this launch cannot emit them (2-D patch tiles, GEGLU)
-int igemm_colstat_rows(const IgemmParams& p, bool gather, int epilogue);
-// ... and the aligned run of output rows inside which the rows of one such block lie (GnColStat::span): the block height itself
-// for kernels whose wave tiles are contiguous rows; one frame for the halo-patch kernel's 2-D tiles and for the parity-form
-// upsample conv; one video for its temporal-conv tiles (call after igemm_colstat_rows returned > 0)
-int igemm_colstat_span(const IgemmParams& p, bool gather, int rows);
 constexpr int COLSTAT_REDUCE_ROWS = 32;
 // float index of (block, channel c, which = 0 sum / 1 sum of squares) in a column-statistics buffer of a C-channel tensor
 __host__ __device__ inline size_t cs_index(size_t block, int c, int which, int C) {

@@ -389,14 +389,32 @@ static int launch_splitk_reduce(const IgemmParams& p, hipStream_t stream) {
     return 0;
 }
 
-// Split-K factor for an under-filled grid.  The 128-row tiles run 2 workgroups per CU (512 slots); a grid of
-// `blocks` tiles takes ceil(blocks*S/512) rounds of (nk/S + fixed) K-steps plus a reduce pass over S slabs.
+// ---- planner (igemm_plan): the force switches are decoded once, into the policy every rule below reads
 static int g_force_tile = 0;   // see igemm_force_tile() in igemm.h
+static int g_force_splits = 0;
+void igemm_force_splits(int s) { g_force_splits = s; }
+struct Policy {
+    bool widest;        // 1, 3: the 128-row kernel takes the widest tile
+    bool pp_split;      // all but 1, 4: the ping-pong grid rule proposes the split factor
+    bool pp_rule;       // 0, 6, 8, 9: the ping-pong kernels run where their grid rule holds
+    bool pp_force;      // 3: the ping-pong kernels run wherever N % 320 == 0 (GEGLU: N % 256 == 0)
+    bool patch_split;   // 0, 5, 8, 9: the halo-patch grid rule proposes the split factor
+    bool patch_rule;    // 0, 8, 9: the halo-patch kernel runs where its grid rule holds
+    bool patch_force;   // 5: the halo-patch kernel runs wherever the conv is eligible
+    bool ppx_rule;      // 0, 6, 9: the persistent kernel runs where its rule holds
+    bool ppx_geglu;     // 0: ... for the GEGLU GEMMs too
+    bool ppx_force;     // 7: the persistent kernel runs for every plain GEMM of its shape
+    int splits;         // force_splits, 0 = automatic
+};
+static Policy policy() {
+    const int m = g_force_tile;
+    return Policy{m == 1 || m == 3, m != 1 && m != 4, m == 0 || m == 6 || m == 8 || m == 9, m == 3, m == 0 || m == 5 || m == 8 || m == 9,
+                  m == 0 || m == 8 || m == 9, m == 5, m == 0 || m == 6 || m == 9, m == 0, m == 7, g_force_splits};
+}
+
 // measured: at 5 K-tiles (K = 320) the GEGLU epilogue, with no second workgroup to hide it, loses; from 8 K-tiles on the
 // ping-pong variant wins or ties (K = 640 of the base model: +0.2 %, K = 512 of the VSR UNet: GEMM class -3.5 %)
 constexpr int GEGLU_PP_MIN_NK = 8;
-static int g_force_splits = 0;
-void igemm_force_splits(int s) { g_force_splits = s; }
 
 // ---- 160x320 ping-pong kernel (igemm_pp.hip): when it is used.  Measured on this model's shapes (tools/bench_ops.py
 // pp_splits, check_pp): it is 15-25 % faster than the 128-row kernel whenever its grid quantises onto the 256 CUs
@@ -413,8 +431,8 @@ static bool pp_fits(int M, int N, int nk, int s) {
     return r / ceil(r) >= 0.85;
 }
 // split-K factor with which the ping-pong kernel should run this problem, 0 = do not use it
-static int pp_plan(int M, int N, int nk, int epilogue) {
-    if (epilogue != EPI_LINEAR || (g_force_tile & 0xF) == 4 || (g_force_tile & 0xF) == 1) return 0;
+static int pp_plan(const Policy& q, int M, int N, int nk, int epilogue) {
+    if (epilogue != EPI_LINEAR || !q.pp_split) return 0;
     for (int s = 1; s <= 4; ++s)
         if (pp_fits(M, N, nk, s)) return s;
     return 0;
@@ -435,53 +453,12 @@ static bool patch_fits(int M, int N, int nk, int s, int ntaps = 9) {
     return r / ceil(r) >= 0.85;
 }
 static int pt_bm_rows() { return 320; }      // the halo-patch kernel's tile height (igemm_patch.hip pt::BM)
-static bool patch_allowed() { const int lo = g_force_tile & 0xF; return lo == 0 || lo == 5 || lo == 8 || lo == 9; }
 
-static int plan_splits(int M, int N, int nk, int epilogue, bool plain);
-static bool ppx_plan_shape(int M, int N, int nk, int epilogue);
-
-int igemm_plan_splits_gather(const IgemmParams& p) {
-    if (g_force_splits == 0 && patch_allowed()) {
-        IgemmParams q = p;
-        for (int s = 1; s <= 4; ++s) {
-            q.splits = s;
-            if (patch_fits(p.M, p.N, p.nk, s, p.tframes > 0 ? p.seg[0].ntaps : 9) && igemm_patch_eligible(q)) return s;
-        }
-    }
-    return plan_splits(p.M, p.N, p.nk, EPI_LINEAR, false);
-}
-
-int igemm_plan_splits(int M, int N, int nk, int epilogue) { return plan_splits(M, N, nk, epilogue, true); }
-
-static int plan_splits(int M, int N, int nk, int epilogue, bool plain) {
-    if (epilogue != EPI_LINEAR || N % 64 != 0) return 1;
-    if (plain && g_force_splits == 0 && ppx_plan_shape(M, N, nk, epilogue)) return 1;     // the persistent kernel never splits K
-    if (g_force_splits > 0) return g_force_splits <= nk ? g_force_splits : 1;
-    if (const int s = pp_plan(M, N, nk, epilogue)) return s;
-    const long blocks = (long)cdiv(M, 128) * cdiv(N, 160);
-    if (blocks >= 1024) return 1;
-    double best = 1e30;
-    int best_s = 1;
-    for (int s = 1; s <= 8; ++s) {
-        if (s > 1 && nk / s < 12) break;
-        const double rounds = (double)((blocks * s + 511) / 512);
-        double cost = rounds * ((double)nk / s + 6.0);
-        if (s > 1) cost += 1.5e-6 * s * (double)M * N;     // slab write + read (~8 s M N bytes at ~4 TB/s) in K-step units of ~1.3 us
-        if (cost < best * 0.93) { best = cost; best_s = s; }
-    }
-    return best_s;
-}
-
-// ---- persistent ping-pong kernel (igemm_ppx.hip) for plain GEMMs: forced (mode 7) or by the measured rule
-static bool ppx_plan_shape(int M, int N, int nk, int epilogue) {
-    const int lo = g_force_tile & 0xF;
+// ---- persistent ping-pong kernel (igemm_ppx.hip) for plain GEMMs: forced (mode 7) or by the measured rule; shape only
+static bool ppx_shape(const Policy& q, int M, int N, int nk, int epilogue) {
     if (M % 160 != 0 || nk < 5 || (epilogue == EPI_GEGLU ? N % 256 != 0 : (N % 320 != 0 && N % 256 != 0))) return false;   // = igemm_ppx_eligible's shape part
-    if (lo == 7) return true;
-    if (lo == 9) {      // A/B switch (round 4): the automatic rule WITHOUT the GEGLU GEMMs on the persistent kernel
-        const long tiles9 = (long)(M / 160) * (N / pp_bn(N));
-        return tiles9 >= 256 && nk <= 10 && epilogue == EPI_LINEAR;
-    }
-    if (lo != 0 && lo != 6) return false;
+    if (q.ppx_force) return true;
+    if (!q.ppx_rule) return false;
     // Measured (tools/check_ppx.py, profiles/r02_ppx_shapes.txt): the persistent kernel wins where the K loop is short and
     // every CU gets at least one whole tile — the L0 GEMMs with K = 320 (N = 320: -14 .. -23 %, QKV -7 %, GEGLU -10 %) and
     // the L1 K = 640 linear ones (-3 .. -10 %); it loses on long K loops (the one-tile kernels' second workgroup per CU
@@ -495,10 +472,121 @@ static bool ppx_plan_shape(int M, int N, int nk, int epilogue) {
     // belongs here and not on the one-tile kernel, although that is 11 % faster in isolation.
     const long tiles = (long)(M / 160) * (N / pp_bn(N));
     if (tiles < 256 || nk > 10) return false;
-    return epilogue == EPI_LINEAR || lo == 0;
+    return epilogue == EPI_LINEAR || q.ppx_geglu;
 }
-static bool ppx_plan(const IgemmParams& p, int epilogue) {
-    return p.splits == 1 && igemm_ppx_eligible(p, epilogue) && ppx_plan_shape(p.M, p.N, p.nk, epilogue);
+
+// Tile width by grid quantisation: the 4-wave tiles run 2 workgroups per CU (512 slots per round); a narrower
+// tile is a little less efficient per flop (exponent 0.9) but can save a whole round on short grids.
+static int igemm_pick_bn(const Policy& q, int M, int N, int splits) {
+    double best = 1e30;
+    int bn = 0;
+    const int cand[3] = {160, 128, 64};
+    for (int i = 0; i < 3; ++i) {
+        if (N % cand[i] != 0) continue;
+        const long blocks = (long)cdiv(M, 128) * (N / cand[i]) * splits;
+        const double cost = (double)((blocks + 511) / 512) * pow(cand[i] / 160.0, 0.9);
+        if (cost < best * 0.97) { best = cost; bn = cand[i]; }
+    }
+    if (q.widest && N % 160 == 0) bn = 160;   // forced modes: widest
+    return bn;
+}
+
+// Split-K factor.  The 128-row tiles run 2 workgroups per CU (512 slots); a grid of `blocks` tiles takes ceil(blocks*S/512)
+// rounds of (nk/S + fixed) K-steps plus a reduce pass over S slabs.
+static int plan_splits(const Policy& q, const IgemmParams& p, bool gather, int epilogue) {
+    if (p.ln_stats || p.rowstat_out) return 1;                     // LayerNorm folding: a plain, unsplit GEMM
+    if (p.par_ups) {
+        // parity upsample: one workgroup per CU and 85 % of a round as everywhere in the family; split-K over whole slabs when the
+        // grid is short.  Quirk: force_splits does not apply here.
+        const int nchunks = p.seg[0].nchunks;
+        const long wgs = (long)(p.M / 4 / pt_bm_rows()) * (p.N / 160) * 4;
+        return wgs >= 218 ? 1 : (2 * wgs >= 218 && nchunks >= 10) ? 2 : (nchunks >= 20 ? 4 : 1);
+    }
+    if (gather) {
+        if (q.splits == 0 && q.patch_split) {
+            IgemmParams t = p;
+            for (int s = 1; s <= 4; ++s) {
+                t.splits = s;
+                if (patch_fits(p.M, p.N, p.nk, s, p.tframes > 0 ? p.seg[0].ntaps : 9) && igemm_patch_eligible(t)) return s;
+            }
+        }
+        epilogue = EPI_LINEAR;
+    }
+    if (epilogue != EPI_LINEAR || p.N % 64 != 0) return 1;
+    // quirk: the persistent kernel's shape, not its eligibility, makes a plain GEMM unsplit (where it refuses, another kernel runs)
+    if (!gather && q.splits == 0 && ppx_shape(q, p.M, p.N, p.nk, epilogue)) return 1;
+    if (q.splits > 0) return q.splits <= p.nk ? q.splits : 1;
+    // quirk: modes 2, 5 and 7 take the ping-pong rule's split factor, though the ping-pong kernel does not run under them
+    if (const int s = pp_plan(q, p.M, p.N, p.nk, epilogue)) return s;
+    const long blocks = (long)cdiv(p.M, 128) * cdiv(p.N, 160);
+    if (blocks >= 1024) return 1;
+    double best = 1e30;
+    int best_s = 1;
+    for (int s = 1; s <= 8; ++s) {
+        if (s > 1 && p.nk / s < 12) break;
+        const double rounds = (double)((blocks * s + 511) / 512);
+        double cost = rounds * ((double)p.nk / s + 6.0);
+        if (s > 1) cost += 1.5e-6 * s * (double)p.M * p.N;     // slab write + read (~8 s M N bytes at ~4 TB/s) in K-step units of ~1.3 us
+        if (cost < best * 0.93) { best = cost; best_s = s; }
+    }
+    return best_s;
+}
+
+// the kernel for `p` at split factor p.splits
+static void plan_kernel(const Policy& q, const IgemmParams& p, bool gather, int epilogue, IgemmPlan* r) {
+    const bool ppx = !gather && p.splits == 1 && igemm_ppx_eligible(p, epilogue) && ppx_shape(q, p.M, p.N, p.nk, epilogue);
+    if (p.par_ups) {                       // parity form of an upsample conv: the halo-patch kernel is the only one that runs it
+        *r = {IGEMM_PATCH_PARITY, 160};
+    } else if (epilogue == EPI_GEGLU) {    // 160x256 ping-pong variant: the 160x320 kernel's grid rule, from GEGLU_PP_MIN_NK K-tiles on
+        const double f = (double)cdiv(p.M, 160) * (p.N / 256) / 256.0;
+        if (ppx) *r = {IGEMM_PPX, 256};
+        else if (p.N % 256 == 0 && (q.pp_force || (q.pp_rule && p.nk >= GEGLU_PP_MIN_NK && f / ceil(f) >= 0.85))) *r = {IGEMM_PP_GEGLU, 256};
+        else *r = {IGEMM_TILE, 128};
+    } else if (ppx) {
+        *r = {IGEMM_PPX, pp_bn(p.N)};
+    } else if (gather && igemm_patch_eligible(p) &&
+               (q.patch_force || (q.patch_rule && patch_fits(p.M, p.N, p.nk, p.splits, p.tframes > 0 ? p.seg[0].ntaps : 9)))) {
+        if (p.tframes > 0) *r = {IGEMM_PATCH_TEMPORAL, 128};
+        else *r = {pt_bm_rows() % p.Wo != 0 ? IGEMM_PATCH_2D : IGEMM_PATCH_ROWS, igemm_patch_bn(p.N)};
+    } else if ((q.pp_force && p.N % 320 == 0) || (q.pp_rule && pp_fits(p.M, p.N, p.nk, p.splits))) {
+        *r = {IGEMM_PP, pp_bn(p.N)};
+    } else {                               // 128-row kernel: two independent workgroups per CU, tile width by grid quantisation
+        *r = {IGEMM_TILE, igemm_pick_bn(q, p.M, p.N, p.splits)};
+    }
+}
+
+IgemmPlan igemm_plan(const IgemmParams& p0, bool gather, int epilogue) {
+    const Policy q = policy();
+    IgemmParams p = p0;
+    p.splits = plan_splits(q, p0, gather, epilogue);
+    IgemmPlan r;
+    plan_kernel(q, p, gather, epilogue, &r);
+    r.gather = gather;
+    r.epilogue = epilogue;
+    r.splits = p.splits;
+    // quirk: row-statistics slots follow the shape rules alone (the persistent kernel's shape without its eligibility, the ping-pong
+    // split rule, mode 3 by N % 320); launch_igemm refuses a launch whose kernel writes other slots
+    if (ppx_shape(q, p.M, p.N, p.nk, EPI_LINEAR) || (q.pp_force ? p.N % 320 == 0 : pp_plan(q, p.M, p.N, p.nk, EPI_LINEAR) == 1))
+        r.rowstat_cols = pp_bn(p.N) / 4;
+    else
+        r.rowstat_cols = igemm_pick_bn(q, p.M, p.N, 1) / 2;
+    // column statistics: 16 * MT rows of the kernel that runs; the split-K reduce writes them when there are slabs
+    r.colstat_rows = epilogue != EPI_LINEAR ? 0 : p.splits > 1 ? COLSTAT_REDUCE_ROWS : r.kernel != IGEMM_TILE ? 80 : r.bn != 0 ? 64 : 0;
+    r.colstat_span = r.colstat_rows;
+    if (r.colstat_rows > 0 && p.splits == 1) {
+        const int rows = r.colstat_rows, hw = p.Ho * p.Wo;
+        if (r.kernel == IGEMM_PATCH_PARITY) {           // 80 source rows -> their 4 output parities, one set each
+            const int shw = p.Hi * p.Wi;
+            r.colstat_span = 4 * (shw % rows == 0 ? shw : (rows % shw == 0 ? rows : 320));
+        } else if (r.kernel == IGEMM_PATCH_TEMPORAL) {  // a tile = every frame of 320 / F pixels of ONE video
+            r.colstat_span = p.tframes * p.tpix;
+        } else if (r.kernel == IGEMM_PATCH_2D) {        // 2-D tile: 10 rows x 32 columns of ONE frame
+            r.colstat_span = hw;
+        } else if (r.kernel == IGEMM_PATCH_ROWS) {      // whole image rows: contiguous; frames smaller than a wave tile nest
+            r.colstat_span = hw % rows == 0 || rows % hw == 0 ? rows : 320;
+        }
+    }
+    return r;
 }
 
 template <int WM, int WN, int MT, int NT, int NSTAGE, bool GATHER, int EPI>
@@ -517,23 +605,6 @@ static int launch_tile(const IgemmParams& p, hipStream_t stream) {
     LAVIE_HIP(hipGetLastError());
     if (p.splits > 1) return launch_splitk_reduce(p, stream);
     return 0;
-}
-
-// Tile width by grid quantisation: the 4-wave tiles run 2 workgroups per CU (512 slots per round); a narrower
-// tile is a little less efficient per flop (exponent 0.9) but can save a whole round on short grids.
-static int igemm_pick_bn(int M, int N, int splits) {
-    double best = 1e30;
-    int bn = 0;
-    const int cand[3] = {160, 128, 64};
-    for (int i = 0; i < 3; ++i) {
-        if (N % cand[i] != 0) continue;
-        const long blocks = (long)cdiv(M, 128) * (N / cand[i]) * splits;
-        const double cost = (double)((blocks + 511) / 512) * pow(cand[i] / 160.0, 0.9);
-        if (cost < best * 0.97) { best = cost; bn = cand[i]; }
-    }
-    const int lo = g_force_tile & 0xF;
-    if ((lo == 1 || lo == 3) && N % 160 == 0) bn = 160;   // forced modes: widest
-    return bn;
 }
 
 __global__ void rowstat_finalize_kernel(const float* __restrict__ partials, int slots, int M, float inv_len, float eps,
@@ -555,47 +626,9 @@ int launch_rowstat_finalize(const float* partials, int slots, int M, int row_len
     return 0;
 }
 
-// Columns per row-statistics slot (= the wave tile width 16*NT) launch_igemm uses for a plain, unsplit EPI_LINEAR
-// GEMM; two waves share a tile's columns.
-int igemm_rowstat_cols(int M, int N, int nk) {
-    if (ppx_plan_shape(M, N, nk, EPI_LINEAR)) return pp_bn(N) / 4;                                              // persistent ping-pong wave tile
-    if ((g_force_tile & 0xF) == 3 ? N % 320 == 0 : (pp_plan(M, N, nk, EPI_LINEAR) == 1)) return pp_bn(N) / 4;   // ping-pong wave tile
-    return igemm_pick_bn(M, N, 1) / 2;
-}
-
-// Mirror of launch_igemm's kernel choice (same tests in the same order): rows per column-statistics block, 0 = none.
-int igemm_colstat_rows(const IgemmParams& p, bool gather, int epilogue) {
-    if (epilogue != EPI_LINEAR || p.N % 4 != 0) return 0;
-    if (p.splits > 1) return COLSTAT_REDUCE_ROWS;                 // whatever kernel fills the slabs, the reduce kernel writes the statistics
-    const int lo = ((g_force_tile & 0xF) == 8 || (g_force_tile & 0xF) == 9) ? 0 : (g_force_tile & 0xF);
-    if (p.par_ups) return 80;                                     // source-row blocks, one set per parity
-    if (!gather && ppx_plan(p, epilogue)) return 80;
-    if (gather && igemm_patch_eligible(p) && (lo == 5 || (lo == 0 && patch_fits(p.M, p.N, p.nk, p.splits, p.tframes > 0 ? p.seg[0].ntaps : 9)))) {
-        // tiles of whole image rows (MODE 0): a wave tile = 80 contiguous rows.  2-D tiles (MODE 1) and temporal-conv tiles (MODE 2):
-        // 80 scattered rows of one frame / one video, numbered tile * 4 + wave (igemm_colstat_span)
-        return 80;
-    }
-    if ((lo == 3 && p.N % 320 == 0) || ((lo == 0 || lo == 6) && pp_fits(p.M, p.N, p.nk, p.splits))) return 80;
-    return igemm_pick_bn(p.M, p.N, p.splits) != 0 ? 64 : 0;
-}
-
-int igemm_colstat_span(const IgemmParams& p, bool gather, int rows) {
-    if (p.splits > 1) return rows;                                 // the reduce kernel walks contiguous output rows
-    const int lo = ((g_force_tile & 0xF) == 8 || (g_force_tile & 0xF) == 9) ? 0 : (g_force_tile & 0xF);
-    const bool patch = gather && igemm_patch_eligible(p) &&
-                       (p.par_ups || lo == 5 || (lo == 0 && patch_fits(p.M, p.N, p.nk, p.splits, p.tframes > 0 ? p.seg[0].ntaps : 9)));
-    if (!patch) return rows;
-    if (p.par_ups) {                                               // 80 source rows -> their 4 output parities, one set each
-        const int hw = p.Hi * p.Wi;
-        return 4 * (hw % rows == 0 ? hw : (rows % hw == 0 ? rows : 320));
-    }
-    if (p.tframes > 0) return p.tframes * p.tpix;                  // a tile = every frame of 320 / F pixels of ONE video
-    if (pt_bm_rows() % p.Wo != 0) return p.Ho * p.Wo;              // 2-D tile: 10 rows x 32 columns of ONE frame
-    const int hw = p.Ho * p.Wo;                                    // whole image rows: contiguous; frames smaller than a wave tile nest
-    return hw % rows == 0 ? rows : (rows % hw == 0 ? rows : 320);
-}
-
-int launch_igemm(const IgemmParams& p, bool gather, int epilogue, hipStream_t stream) {
+int launch_igemm(const IgemmParams& p, const IgemmPlan& plan, hipStream_t stream) {
+    const bool gather = plan.gather;
+    const int epilogue = plan.epilogue;
     LAVIE_CHECK(p.M > 0 && p.N > 0 && p.nk > 0, "igemm: empty problem M=%d N=%d nk=%d", p.M, p.N, p.nk);
     const double K = (double)p.nk * IGEMM_BK;
     // algorithmic work: 2 M N K flops; bytes = every operand element once (A incl. im2col reuse counted once)
@@ -603,61 +636,38 @@ int launch_igemm(const IgemmParams& p, bool gather, int epilogue, hipStream_t st
                       2.0 * ((double)p.M * K / (gather ? 9.0 : 1.0) + (double)p.N * K + (double)p.M * p.N));
     LAVIE_CHECK(p.N % 4 == 0 && p.ldc % 4 == 0, "igemm: N and ldc must be multiples of 4");
     LAVIE_CHECK(!(p.rowstat_out || p.ln_stats) || (p.splits == 1 && !gather), "igemm: LayerNorm folding needs a plain, unsplit GEMM");
-    LAVIE_CHECK(p.splits >= 1 && p.splits <= p.nk && (p.splits == 1 || (p.slab && epilogue == EPI_LINEAR)),
-                "igemm: bad split-K setup (splits=%d)", p.splits);
-    const int lo = ((g_force_tile & 0xF) == 8 || (g_force_tile & 0xF) == 9) ? 0 : (g_force_tile & 0xF);      // 8 = automatic without the persistent kernel
-    auto reduce_splits = [&]() -> int {          // fixed-order sum of the split-K slabs + bias / residual / rounding
-        return p.splits > 1 ? launch_splitk_reduce(p, stream) : 0;
-    };
-    // the block height the caller sized the column-statistics buffer for must be the one the kernel chosen below writes
-    LAVIE_CHECK(!p.colstat_out || (epilogue == EPI_LINEAR && p.colstat_rows > 0 && p.colstat_rows == igemm_colstat_rows(p, gather, epilogue)),
-                "igemm: column statistics planned for %d-row blocks, this launch writes %d", p.colstat_rows, igemm_colstat_rows(p, gather, epilogue));
-    if (p.par_ups) {             // parity form of an upsample conv: the halo-patch kernel is the only one that runs it
+    LAVIE_CHECK(p.splits == plan.splits && p.splits >= 1 && p.splits <= p.nk && (p.splits == 1 || (p.slab && epilogue == EPI_LINEAR)),
+                "igemm: bad split-K setup (splits=%d, planned %d)", p.splits, plan.splits);
+    LAVIE_CHECK(!p.colstat_out || plan.colstat_rows > 0, "igemm: column statistics asked of a launch that writes none");
+    if (p.par_ups)
         LAVIE_CHECK(gather && epilogue == EPI_LINEAR && igemm_patch_eligible(p), "igemm: parity upsample conv outside the halo-patch kernel's geometry");
-        if (int rc = launch_igemm_patch(p, stream)) return rc;
-        return reduce_splits();
-    }
     if (epilogue == EPI_GEGLU) {
         LAVIE_CHECK(p.N % 128 == 0, "igemm: GEGLU needs N %% 128 == 0 (N=%d)", p.N);
         LAVIE_CHECK(!p.R && !p.bias2, "igemm: GEGLU epilogue takes no residual / per-batch bias");
         LAVIE_CHECK(!gather, "igemm: GEGLU epilogue is only built for plain A rows");
-        if (ppx_plan(p, epilogue)) return launch_igemm_ppx(p, epilogue, stream);
-        // 160x256 ping-pong variant: same grid rule as the 160x320 kernel, from GEGLU_PP_MIN_NK K-tiles on
-        const double r = (double)cdiv(p.M, 160) * (p.N / 256) / 256.0;
-        if (p.N % 256 == 0 && (lo == 3 || ((lo == 0 || lo == 6) && p.nk >= GEGLU_PP_MIN_NK && r / ceil(r) >= 0.85)))
-            return launch_igemm_pp_geglu(p, stream);
-        return launch_tile<2, 2, 4, 4, 2, false, EPI_GEGLU>(p, stream);
+    } else {
+        // row statistics: one slot per wave tile (16 * NT columns) of the kernel that runs
+        const int cols = plan.kernel == IGEMM_TILE ? plan.bn / 2 : plan.bn / 4;
+        LAVIE_CHECK(!p.rowstat_out || plan.rowstat_cols == cols, "igemm: row-statistics slots planned for %d columns, the kernel writes %d",
+                    plan.rowstat_cols, cols);
     }
-    // the row-statistics slot width the caller allocated for must be the wave-tile width of the kernel chosen below (the shape
-    // rule of igemm_rowstat_cols and the eligibility tests here are separate code: a mismatch would write out of range)
-    auto slots_ok = [&](int cols) { return !p.rowstat_out || p.rowstat_cols == 0 || p.rowstat_cols == cols; };
-    if (!gather && ppx_plan(p, epilogue)) {
-        LAVIE_CHECK(slots_ok(pp_bn(p.N) / 4), "igemm: row-statistics slots sized for %d columns, persistent kernel writes %d", p.rowstat_cols, pp_bn(p.N) / 4);
-        return launch_igemm_ppx(p, epilogue, stream);
+    int rc = 0;
+    switch (plan.kernel) {
+    case IGEMM_PPX: return launch_igemm_ppx(p, epilogue, stream);
+    case IGEMM_PP_GEGLU: return launch_igemm_pp_geglu(p, stream);
+    case IGEMM_PP: rc = launch_igemm_pp(p, gather, stream); break;
+    case IGEMM_TILE:        // (launch_tile runs the split-K reduce itself)
+        if (epilogue == EPI_GEGLU) return launch_tile<2, 2, 4, 4, 2, false, EPI_GEGLU>(p, stream);
+        LAVIE_CHECK(plan.bn != 0, "igemm: N=%d is not a multiple of 64", p.N);
+        if (plan.bn == 160)
+            return gather ? launch_tile<2, 2, 4, 5, 2, true, EPI_LINEAR>(p, stream) : launch_tile<2, 2, 4, 5, 2, false, EPI_LINEAR>(p, stream);
+        if (plan.bn == 128)
+            return gather ? launch_tile<2, 2, 4, 4, 2, true, EPI_LINEAR>(p, stream) : launch_tile<2, 2, 4, 4, 2, false, EPI_LINEAR>(p, stream);
+        return gather ? launch_tile<2, 2, 4, 2, 2, true, EPI_LINEAR>(p, stream) : launch_tile<2, 2, 4, 2, 2, false, EPI_LINEAR>(p, stream);
+    default: rc = launch_igemm_patch(p, stream); break;
     }
-    // halo-patch conv kernel: forced (mode 5) or whenever its grid rule holds at this split factor
-    if (gather && igemm_patch_eligible(p) && (lo == 5 || (lo == 0 && patch_fits(p.M, p.N, p.nk, p.splits, p.tframes > 0 ? p.seg[0].ntaps : 9)))) {
-        if (int rc = launch_igemm_patch(p, stream)) return rc;
-        return reduce_splits();
-    }
-    // 160x320 ping-pong kernel: forced (mode 3) or whenever the planner's rule holds for this problem at its split factor
-    if ((lo == 3 && p.N % 320 == 0) || ((lo == 0 || lo == 6) && pp_fits(p.M, p.N, p.nk, p.splits))) {
-        LAVIE_CHECK(slots_ok(pp_bn(p.N) / 4), "igemm: row-statistics slots sized for %d columns, ping-pong kernel writes %d", p.rowstat_cols, pp_bn(p.N) / 4);
-        if (int rc = launch_igemm_pp(p, gather, stream)) return rc;
-        return reduce_splits();
-    }
-    // 128-row kernel: two independent workgroups per CU, tile width by grid quantisation
-    const int bn = igemm_pick_bn(p.M, p.N, p.splits);
-    LAVIE_CHECK(bn != 0, "igemm: N=%d is not a multiple of 64", p.N);
-    LAVIE_CHECK(slots_ok(bn / 2), "igemm: row-statistics slots sized for %d columns, 128-row kernel writes %d", p.rowstat_cols, bn / 2);
-    if (bn == 160)
-        return gather ? launch_tile<2, 2, 4, 5, 2, true, EPI_LINEAR>(p, stream)
-                      : launch_tile<2, 2, 4, 5, 2, false, EPI_LINEAR>(p, stream);
-    if (bn == 128)
-        return gather ? launch_tile<2, 2, 4, 4, 2, true, EPI_LINEAR>(p, stream)
-                      : launch_tile<2, 2, 4, 4, 2, false, EPI_LINEAR>(p, stream);
-    return gather ? launch_tile<2, 2, 4, 2, 2, true, EPI_LINEAR>(p, stream)
-                  : launch_tile<2, 2, 4, 2, 2, false, EPI_LINEAR>(p, stream);
+    if (rc) return rc;
+    return p.splits > 1 ? launch_splitk_reduce(p, stream) : 0;      // fixed-order sum of the split-K slabs + bias / residual / rounding
 }
 
 int igemm_force_tile(int mode) {

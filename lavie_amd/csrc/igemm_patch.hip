@@ -448,8 +448,8 @@ static bool patch_parity_ok(const IgemmParams& p) {
 }
 
 // Fills `p` for y = conv3x3(nearest_x2(x)) + bias in parity form (x [NI, Hi, Wi, C] rows, y [NI, 2Hi, 2Wi, C] rows, wpar from
-// launch_pack_conv3x3_parity) including the split-K factor (the caller provides p->slab when splits > 1); false = the halo-patch
-// kernel's geometry does not hold and the caller runs the 9-tap gather conv with ups = 1 instead.
+// launch_pack_conv3x3_parity), unsplit (igemm_plan picks the split factor); false = the halo-patch kernel's geometry does not hold
+// and the caller runs the 9-tap gather conv with ups = 1 instead.
 bool igemm_setup_parity_upsample(IgemmParams* p, const half_t* x, int C, const half_t* wpar, const float* bias, half_t* y, int NI, int Hi,
                                  int Wi, const half_t* zero) {
     memset(p, 0, sizeof(*p));
@@ -460,10 +460,34 @@ bool igemm_setup_parity_upsample(IgemmParams* p, const half_t* x, int C, const h
     p->nseg = 1;
     p->seg[0].src = x; p->seg[0].C = C; p->seg[0].c0 = 0; p->seg[0].nchunks = C / IGEMM_BK; p->seg[0].ntaps = 4;
     p->nk = 4 * p->seg[0].nchunks;
-    // one workgroup per CU and 85 % of a round as everywhere in the family; split-K over whole slabs when the grid is short
-    const long wgs = (long)(p->M / 4 / pt::BM) * (C / 160) * 4;
-    p->splits = wgs >= 218 ? 1 : (2 * wgs >= 218 && p->seg[0].nchunks >= 10) ? 2 : (p->seg[0].nchunks >= 20 ? 4 : 1);
+    p->splits = 1;
     return patch_parity_ok(*p);
+}
+
+int igemm_setup_conv3x3(IgemmParams* p, const half_t* const* src, const int* srcC, int nsrc, const half_t* const* sc, const int* scC,
+                        int nsc, const half_t* W, int ldw, half_t* y, int NI, int Hi, int Wi, int Cout, int stride, int ups,
+                        const half_t* zero) {
+    memset(p, 0, sizeof(*p));
+    p->W = W; p->ldw = ldw; p->C = y; p->ldc = Cout; p->rows_per_batch = 1; p->ldr = Cout;
+    p->Hi = Hi; p->Wi = Wi; p->stride = stride; p->ups = ups;
+    p->Ho = ups ? Hi * 2 : (Hi - 1) / stride + 1;
+    p->Wo = ups ? Wi * 2 : (Wi - 1) / stride + 1;
+    p->M = NI * p->Ho * p->Wo;
+    p->N = Cout;
+    p->zero = zero;
+    for (int i = 0; i < nsrc + nsc; ++i) {
+        const bool shortcut = i >= nsrc;
+        const int C = shortcut ? scC[i - nsrc] : srcC[i];
+        if (C == 0) continue;
+        LAVIE_CHECK(p->nseg < IGEMM_MAX_SEG, "conv3x3: too many K segments");
+        LAVIE_CHECK(C % IGEMM_BK == 0, "conv3x3: channel count %d must be a multiple of %d", C, IGEMM_BK);
+        LAVIE_CHECK(!shortcut || (stride == 1 && ups == 0), "conv3x3: a fused shortcut needs stride 1, no upsample");
+        IgemmSeg& sg = p->seg[p->nseg++];
+        sg.src = shortcut ? sc[i - nsrc] : src[i]; sg.C = C; sg.c0 = 0; sg.nchunks = C / IGEMM_BK; sg.ntaps = shortcut ? 1 : 9;
+        p->nk += sg.ntaps * sg.nchunks;
+    }
+    LAVIE_CHECK(p->nk * IGEMM_BK <= ldw, "conv3x3: weight row length %d is shorter than the gathered K %d", ldw, p->nk * IGEMM_BK);
+    return 0;
 }
 
 // Whether the halo-patch kernel can run this conv (geometry only; the caller decides on grid fill and split-K).

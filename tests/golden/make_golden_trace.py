@@ -1,0 +1,50 @@
+"""Generates tests/golden/gemm_plan_trace.txt.gz: the launch trace of the host-only sanitizer build (lavie_amd/csrc/hostcheck,
+`hostcheck trace FILE`), one line per kernel launch (kernel, grid, block, dynamic LDS bytes) under a "== case" line per case of
+driver.cpp's run_traces(): the base model at the production shape (B = 2, F = 16, 40 x 64, cached context, shared prefix) under
+every force_tile mode, forced split-K 2 and 3 and fused mask 0x30; the interpolation model (F = 61) and the VSR UNet (F = 8 at
+320 x 512); the reduced variants of `make asan`; lavie_linear_f16 / lavie_conv3x3_f16 / lavie_upsample_conv3x3_f16 at level shapes.
+
+It pins every kernel choice, grid (split-K factor = grid.y of the GEMM launches) and tile of the implicit-GEMM planner:
+tests/test_gemm_plan_trace.py regenerates the trace and compares.  A change that means to pick another kernel regenerates this
+file, so that the change shows in its diff.  CPU only, needs hipcc.  Run from the repo root:  python tests/golden/make_golden_trace.py"""
+import gzip
+import os
+import subprocess
+import tempfile
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+CSRC = os.path.join(ROOT, "lavie_amd", "csrc")
+FIXTURE = os.path.join(HERE, "gemm_plan_trace.txt.gz")
+
+
+def trace_lines():
+    """Builds the host-only driver and returns the lines of a fresh trace."""
+    r = subprocess.run(["make", "-C", CSRC, "-j", "8", "build_asan/hostcheck"], capture_output=True, text=True, timeout=900)
+    if r.returncode != 0:
+        raise RuntimeError("building the host-only driver failed:\n" + r.stdout[-3000:] + r.stderr[-3000:])
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "trace.txt")
+        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
+        r = subprocess.run([os.path.join(CSRC, "build_asan", "hostcheck"), "trace", out], cwd=CSRC, capture_output=True, text=True,
+                           env=env, timeout=900)
+        if r.returncode != 0 or "trace written" not in r.stdout:
+            raise RuntimeError("hostcheck trace failed:\n" + r.stdout[-3000:] + r.stderr[-3000:])
+        with open(out) as f:
+            return f.read().splitlines()
+
+
+def fixture_lines():
+    with gzip.open(FIXTURE, "rt") as f:
+        return f.read().splitlines()
+
+
+def main():
+    lines = trace_lines()
+    with open(FIXTURE, "wb") as f, gzip.GzipFile(filename="", mode="wb", fileobj=f, mtime=0, compresslevel=9) as g:
+        g.write(("\n".join(lines) + "\n").encode())
+    print(f"{FIXTURE}: {len(lines)} lines, {os.path.getsize(FIXTURE)} bytes")
+
+
+if __name__ == "__main__":
+    main()
