@@ -135,6 +135,16 @@ int lavie_bind_cross_block_f16(const void* tmpl, const void* kv, int B, int ctx_
 int lavie_cross_block_f16(const void* att, const void* x, void* y, int M, int rows_per_batch, int C, int heads, const void* img,
                           const float* bo1, const float* gamma, const float* beta, const float* bo2, int ctx_len, float scale,
                           float eps, void* stream);
+/* The long variant (additive in ABI 8): the same sub-block for 81 <= ctx_len <= 160 (a text context widened with mapped image
+ * tokens), with images of its own layout and size: a template from lavie_pack_cross_block_long_f16, per-video images from
+ * lavie_bind_cross_block_long_f16, launched by lavie_cross_block_long_f16.  Arguments as above; C = 320, 8 heads;
+ * lavie_cross_block_long_image_bytes returns 0 for any other width or head count.  Images of the two variants do not mix. */
+long long lavie_cross_block_long_image_bytes(int C, int heads);
+int lavie_pack_cross_block_long_f16(const void* wo1, const void* wq2, const void* wo2, int C, void* tmpl, void* stream);
+int lavie_bind_cross_block_long_f16(const void* tmpl, const void* kv, int B, int ctx_len, int C, void* img, void* stream);
+int lavie_cross_block_long_f16(const void* att, const void* x, void* y, int M, int rows_per_batch, int C, int heads, const void* img,
+                               const float* bo1, const float* gamma, const float* beta, const float* bo2, int ctx_len, float scale,
+                               float eps, void* stream);
 
 /* Upsample3D (ABI 6, /root/reference/base/models/resnet.py:44-79: F.interpolate(scale_factor=2, mode="nearest") then the 3x3
  * conv): y = conv3x3(nearest_x2(x)) + bias as FOUR 2x2 convs on x, one per output parity — the nine taps of an output pixel

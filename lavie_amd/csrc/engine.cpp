@@ -100,6 +100,7 @@ UNet::~UNet() {
     drop_graph();
     if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
     if (kv_block_) (void)hipFree(kv_block_);
+    if (xbl_block_) (void)hipFree(xbl_block_);
     for (auto& kv : lora_) lora_free(kv.second, true);
 }
 
@@ -462,6 +463,7 @@ int UNet::derive_transformer(const TransformerW& t, hipStream_t s) {
     const size_t CC = (size_t)C * C;
     if (t.tb_img) RUN(pack_temporal_block(t.wqkvt, t.wqkvt + CC, t.wqkvt + 2 * CC, t.ot.w, C, t.tb_img, s));
     if (t.xb_tmpl) RUN(pack_cross_block(t.o1.w, t.wq2, t.o2.w, C, t.xb_tmpl, s));
+    if (t.xbl_tmpl) RUN(pack_cross_block_long(t.o1.w, t.wq2, t.o2.w, C, t.xbl_tmpl, s));
     if (t.pq_img) RUN(pack_proj_qkv(t.pin.w, t.wqkv1, C, t.pq_img, s));      // wqkv1: to_q | to_k | to_v rows
     if (t.attn1_cross) RUN(launch_ln_fold(t.wq1, t.ln1.g, t.ln1.b, nullptr, t.f_q1, t.s_q1, t.b_q1, C, C, s));
     else RUN(launch_ln_fold(t.wqkv1, t.ln1.g, t.ln1.b, nullptr, t.f_qkv1, t.s_qkv1, t.b_qkv1, 3 * C, C, s));
@@ -932,8 +934,10 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
     // attn1.to_out -> + residual -> norm2 -> attn2 -> to_out -> + residual in one kernel: needs this context's K / V image, and
     // (it emits no row statistics) behind it a kernel that takes its LayerNorm statistics from the rows it holds: the fused temporal
     // kernel in the base order, the fused feed-forward kernel in the interpolation order
+    // 81..160 keys (a text context widened with mapped image tokens): the long variant of the same kernel, under the same conditions
+    const bool xb_long = cross_block_long_supported(C, heads, c.ctx_len, c.F * D);
     const bool fused_x = t.xb_tmpl != nullptr && kv_cached && xb_bound_ && xb_img_[ti] != nullptr && (ff_first ? fused_ff : fused_t) &&
-                         !t.attn1_cross && (fused_mask() & 4) && cross_block_supported(C, heads, c.ctx_len, c.F * D);
+                         !t.attn1_cross && (fused_mask() & 4) && (cross_block_supported(C, heads, c.ctx_len, c.F * D) || xb_long);
     LnFold lf{nullptr, nullptr};
     RowStat rsd{nullptr, nullptr, &lf};
     const RowStat* rowstat = nullptr;
@@ -995,7 +999,10 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
         LAVIE_HIP(hipMemcpyAsync(att + (size_t)Tp * C, att, (size_t)Tp * C * sizeof(half_t), hipMemcpyDeviceToDevice, c.s));
     }
     if (fused_x) {
-        if (!c.dry)
+        if (!c.dry && xb_long)
+            RUN(launch_cross_block_long(att, tx, tx, T, c.F * D, C, heads, xb_img_[ti], t.o1.b, t.ln2.g, t.ln2.b, t.o2.b, c.ctx_len, scale, 1e-5f,
+                                        c.s));
+        else if (!c.dry)
             RUN(launch_cross_block(att, tx, tx, T, c.F * D, C, heads, xb_img_[ti], t.o1.b, t.ln2.g, t.ln2.b, t.o2.b, c.ctx_len, scale, 1e-5f, c.s));
     } else {
     RUN(linear(c, att, C, t.o1.w, t.o1.b, C, C, tx, tx, C, T, EPI_LINEAR, nullptr, rowstat));
@@ -1405,12 +1412,18 @@ int UNet::cache_context(const half_t* ctx, int B, int ctx_len, hipStream_t strea
     LAVIE_CHECK(ws_.total_bytes() > 0, "cache_context: call lavie_unet_prepare first (split-K slabs come from the workspace)");
     const size_t rows = (size_t)B * ctx_len;
     const int X = cfg_.cross_attention_dim;
-    if (rows > kv_cache_rows_ || B > kv_cache_B_ || kv2_cache_.size() != transformers_.size()) {
+    const int C0 = cfg_.block_out_channels[0];
+    const bool xb_long = cross_block_long_supported(C0, cfg_.heads, ctx_len, 16);
+    if (xb_long) RUN(ensure_long_templates(stream));
+    const size_t img_bytes = xb_long ? cross_block_long_image_bytes(C0) : cross_block_image_bytes(C0);
+    if (rows > kv_cache_rows_ || B > kv_cache_B_ || kv2_cache_.size() != transformers_.size() || img_bytes > xb_img_bytes_) {
         // the cache lives in a block of its own: a longer context frees the old block instead of stranding it in the
         // grow-only weights arena.  Earlier forwards that read the old block are ordered before the free by the sync.
         size_t total = 0;
         auto span = [&](size_t i) { return (rows * 2 * transformers_[i].C * sizeof(half_t) + 255) & ~(size_t)255; };
-        auto img_span = [&](size_t i) { return transformers_[i].xb_tmpl ? (size_t)B * cross_block_image_bytes(transformers_[i].C) : 0; };
+        // a long context lays the images out for the long layout; a short one after it keeps (and uses the front of) the larger ones
+        const size_t xb_bytes = img_bytes > xb_img_bytes_ ? img_bytes : xb_img_bytes_;
+        auto img_span = [&](size_t i) { return transformers_[i].xb_tmpl ? (size_t)B * xb_bytes : 0; };
         for (size_t i = 0; i < transformers_.size(); ++i) total += span(i) * (transformers_[i].attn1_cross ? 2 : 1) + img_span(i);
         if (kv_block_) {
             LAVIE_HIP(hipStreamSynchronize(stream));
@@ -1418,6 +1431,7 @@ int UNet::cache_context(const half_t* ctx, int B, int ctx_len, hipStream_t strea
             kv_block_ = nullptr;
             kv_cache_rows_ = 0;
             kv_cache_B_ = 0;
+            xb_img_bytes_ = 0;
         }
         LAVIE_HIP(hipMalloc(&kv_block_, total));
         kv2_cache_.assign(transformers_.size(), nullptr);
@@ -1431,6 +1445,7 @@ int UNet::cache_context(const half_t* ctx, int B, int ctx_len, hipStream_t strea
         }
         kv_cache_rows_ = rows;
         kv_cache_B_ = B;
+        xb_img_bytes_ = xb_bytes;
     }
     ws_.release(0);
     FwdCtx c{stream, &ws_, false, B, 1, ctx_len, nullptr};
@@ -1441,14 +1456,38 @@ int UNet::cache_context(const half_t* ctx, int B, int ctx_len, hipStream_t strea
     }
     // the fused cross-attention kernel streams K / V with its weights: one image per video, written here once per context
     xb_bound_ = false;
-    if (cross_block_supported(cfg_.block_out_channels[0], cfg_.heads, ctx_len, 16)) {
+    if (cross_block_supported(C0, cfg_.heads, ctx_len, 16)) {
         for (size_t i = 0; i < transformers_.size(); ++i)
             if (xb_img_[i]) RUN(bind_cross_block(transformers_[i].xb_tmpl, kv2_cache_[i], B, ctx_len, transformers_[i].C, xb_img_[i], stream));
+        xb_bound_ = true;
+    } else if (xb_long) {
+        for (size_t i = 0; i < transformers_.size(); ++i)
+            if (xb_img_[i]) RUN(bind_cross_block_long(transformers_[i].xbl_tmpl, kv2_cache_[i], B, ctx_len, transformers_[i].C, xb_img_[i], stream));
         xb_bound_ = true;
     }
     kv_ctx_ = ctx;
     kv_B_ = B;
     kv_len_ = ctx_len;
+    return 0;
+}
+
+// Long templates (the 81..160-key variant of the fused text cross-attention) are built on the first long context, not at finalize:
+// a text-only model never pays for them (one 840 KiB template per level-0 transformer: 4.1 MiB at the production config, 5 blocks).
+// Once built, derive_transformer() re-derives them with the short ones, so an adapter change keeps them current.
+int UNet::ensure_long_templates(hipStream_t stream) {
+    if (xbl_block_) return 0;
+    size_t n = 0;
+    for (const TransformerW& t : transformers_) n += t.xb_tmpl ? 1 : 0;
+    if (n == 0) return 0;
+    const size_t bytes = cross_block_long_image_bytes(cfg_.block_out_channels[0]);
+    LAVIE_HIP(hipMalloc(&xbl_block_, n * bytes));
+    char* cur = (char*)xbl_block_;
+    for (TransformerW& t : transformers_) {
+        if (!t.xb_tmpl) continue;
+        t.xbl_tmpl = (half_t*)cur;
+        cur += bytes;
+        RUN(pack_cross_block_long(t.o1.w, t.wq2, t.o2.w, t.C, t.xbl_tmpl, stream));
+    }
     return 0;
 }
 

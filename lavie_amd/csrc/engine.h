@@ -86,6 +86,7 @@ struct TransformerW {
     half_t* ff_img = nullptr; float* ff_b1img = nullptr;    // norm3 -> GEGLU feed-forward -> + residual in one kernel
     half_t* tb_img = nullptr;                               // norm_temp -> q|k|v -> temporal attention -> to_out -> + residual
     half_t* xb_tmpl = nullptr;                              // attn1.to_out -> norm2 -> attn2 -> + residual: weight part of the image (rowfuse_cross.hip)
+    half_t* xbl_tmpl = nullptr;                             // the same for the long variant (81..160 keys): built by the first long cache_context
     half_t* pq_img = nullptr;                               // GroupNorm -> proj_in -> norm1 -> q|k|v (rowfuse_pin.hip, round 4)
 };
 
@@ -237,6 +238,9 @@ private:
     std::vector<half_t*> xb_img_;
     int kv_cache_B_ = 0;                            // videos the image buffers were allocated for
     bool xb_bound_ = false;                         // images hold the cached context (its length fits the kernel)
+    size_t xb_img_bytes_ = 0;                       // bytes per video the image buffers were laid out for (short or long layout)
+    void* xbl_block_ = nullptr;                     // ONE hipMalloc'd block behind every long template (xbl_tmpl), kept for the model's life
+    int ensure_long_templates(hipStream_t stream);
     void* kv_block_ = nullptr;                      // ONE hipMalloc'd block behind every K/V cache buffer: freed and reallocated on growth
     const half_t* kv_ctx_ = nullptr;
     int kv_B_ = 0, kv_len_ = 0;

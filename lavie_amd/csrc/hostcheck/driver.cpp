@@ -85,6 +85,17 @@ static void run_model(const lavie_unet_config& cfg, int B, int F, int H, int W, 
             REQUIRE(lavie_unet_set_cfg_shared_input(h, 0) == 0);
         }
         REQUIRE(lavie_unet_cache_context(h, nullptr, 0, 0, nullptr) == 0);
+        // a 154-token context (77 text + 77 mapped image tokens): long templates built on first use, long images bound, the
+        // long fused text cross-attention where level 0 has it; then back to 77 tokens on the same buffers
+        void* ctx2 = calloc((size_t)B * 154 * cfg.cross_attention_dim, 2);
+        REQUIRE(lavie_unet_prepare(h, B, F, H, W, 154) == 0);
+        REQUIRE(lavie_unet_cache_context(h, ctx2, B, 154, nullptr) == 0);
+        REQUIRE(lavie_unet_forward(h, x, t, ctx2, y, B, F, H, W, 154, nullptr) == 0);
+        REQUIRE(lavie_unet_cache_context(h, ctx, B, 77, nullptr) == 0);
+        REQUIRE(lavie_unet_prepare(h, B, F, H, W, 77) == 0);
+        REQUIRE(lavie_unet_forward(h, x, t, ctx, y, B, F, H, W, 77, nullptr) == 0);
+        REQUIRE(lavie_unet_cache_context(h, nullptr, 0, 0, nullptr) == 0);
+        free(ctx2);
     }
     REQUIRE(lavie_hostcheck_launches() > before + 50);
     if (check_switches) {   // a rejected switch value leaves the one in force: the launch count of a forward tells them apart
@@ -315,6 +326,22 @@ int main(int argc, char** argv) {
     // operator-level argument checks
     REQUIRE(lavie_linear_f16(nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, 0, 16, 64, 63, 0, nullptr) != 0);
     REQUIRE(lavie_geglu_mlp_image_bytes(123) == 0);
+    {   // the long fused text cross-attention (81..160 keys): sizes, and lengths / widths refused before any HIP call
+        REQUIRE(lavie_cross_block_long_image_bytes(320, 8) == 840 * 1024 && lavie_cross_block_long_image_bytes(256, 8) == 0);
+        std::vector<unsigned short> w(320 * 320), tmpl(840 * 512), kv(161 * 640), img(840 * 512), x(128 * 320);
+        std::vector<float> v(320, 1.f);
+        REQUIRE(lavie_pack_cross_block_long_f16(w.data(), w.data(), w.data(), 256, tmpl.data(), nullptr) != 0);
+        REQUIRE(lavie_pack_cross_block_long_f16(w.data(), w.data(), w.data(), 320, tmpl.data(), nullptr) == 0);
+        REQUIRE(lavie_bind_cross_block_long_f16(tmpl.data(), kv.data(), 1, 161, 320, img.data(), nullptr) != 0);
+        REQUIRE(lavie_bind_cross_block_long_f16(tmpl.data(), kv.data(), 1, 80, 320, img.data(), nullptr) != 0);
+        REQUIRE(lavie_bind_cross_block_long_f16(tmpl.data(), nullptr, 1, 154, 320, img.data(), nullptr) != 0);
+        REQUIRE(lavie_bind_cross_block_long_f16(tmpl.data(), kv.data(), 1, 154, 320, img.data(), nullptr) == 0);
+        REQUIRE(lavie_cross_block_long_f16(x.data(), x.data(), x.data(), 128, 128, 320, 8, img.data(), v.data(), v.data(), v.data(), v.data(),
+                                           161, 0.1f, 1e-5f, nullptr) != 0);
+        REQUIRE(lavie_cross_block_long_f16(x.data(), x.data(), x.data(), 128, 128, 320, 8, img.data(), v.data(), v.data(), v.data(), v.data(),
+                                           154, 0.1f, 1e-5f, nullptr) == 0);
+        REQUIRE(lavie_bind_cross_block_f16(tmpl.data(), kv.data(), 1, 81, 320, img.data(), nullptr) != 0);     // the short kernel: <= 80
+    }
     {   // round 4 operators: widths that are not built, null tensors, a frame height that is not a whole number of 16-row tiles
         REQUIRE(lavie_proj_qkv_image_bytes(256) == 0 && lavie_proj_qkv_image_bytes(320) > 0);
         std::vector<unsigned short> x(64 * 320), wq(3 * 320 * 320), wp(320 * 320), tx(64 * 320), qkv(64 * 960);

@@ -141,6 +141,14 @@ int bind_cross_block(const half_t* tmpl, const half_t* kv, int B, int L, int C, 
 int launch_cross_block(const half_t* att, const half_t* x, half_t* y, int M, int rows_per_batch, int C, int heads, const half_t* img,
                        const float* bo1, const float* gamma, const float* beta, const float* bo2, int L, float scale, float eps,
                        hipStream_t stream);
+// the long variant (81..160 keys): the same sub-block with images of its own layout (ten key tiles per head)
+bool cross_block_long_supported(int C, int heads, int ctx_len, int rows_per_batch);
+size_t cross_block_long_image_bytes(int C);
+int pack_cross_block_long(const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, hipStream_t stream);
+int bind_cross_block_long(const half_t* tmpl, const half_t* kv, int B, int L, int C, half_t* img, hipStream_t stream);
+int launch_cross_block_long(const half_t* att, const half_t* x, half_t* y, int M, int rows_per_batch, int C, int heads, const half_t* img,
+                            const float* bo1, const float* gamma, const float* beta, const float* bo2, int L, float scale, float eps,
+                            hipStream_t stream);
 
 // ---- lora.hip: out[n, k] = fp16_rne(W0[n, k] + scale * sum_{j < r} B[n, j] A[j, k]), W0 / out fp16 [N, K], A fp32 [r, K], B fp32 [N, r];
 // fp32 accumulation in ascending j, no atomics (deterministic); K % 8 == 0, W0 / out / A 16-byte aligned; out may alias W0

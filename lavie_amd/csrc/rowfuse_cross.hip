@@ -17,6 +17,15 @@
 //   operand of the to_out product, which accumulates into the residual registers.  q, the attention output, LN2(x') and x'
 //   itself never exist in memory: the sub-block reads att and x once and writes x'' once (was: 12 tensor crossings in 4 launches).
 // Built for C = 320, 8 heads of 40 channels, context length <= 80.
+//
+// Long variant (81..160 keys: the image-conditioned context of 77 text + 77 mapped image tokens): the same kernel with TEN key
+// tiles per head (S[2][10]: one softmax over 40 registers + the two cross-lane steps, no online rescaling) and an image of 840
+// pieces per video:
+//       200        Wo1 (as above)
+//       4 x 155    per head pair:  50 Wq2 | 30 K (10 key tiles x 3, as above) | 25 V^T (5 channel tiles x 5 32-key steps: 160 keys
+//                                  are five full 32-deep steps, no 16-deep tail) | 50 Wo2
+//       20         padding (21 units of 40)
+// Its own instance, templates, images and entry points (cross_block_long_*): the <= 80-key instance is not touched.
 #include <map>
 
 #include "rowfuse.h"
@@ -37,6 +46,24 @@ inline int pair_channel(int h0, int j, int r) {
 }
 }  // namespace xb
 
+// the stream layout of one instance: NKT key tiles per head (5: <= 80 keys, 10: <= 160 keys)
+template <int NKT> struct XbLayout;
+template <> struct XbLayout<5> {
+    static constexpr int MAXL = xb::MAXL, PAIR_PIECES = xb::PAIR_PIECES, K_OFF = xb::K_OFF, V_OFF = xb::V_OFF, O_OFF = xb::O_OFF;
+    static constexpr int V_PIECES = 13, PASS_UNITS = xb::PASS_UNITS, PASS_PIECES = xb::PASS_PIECES;
+};
+template <> struct XbLayout<10> {
+    static constexpr int MAXL = 160, PAIR_PIECES = 155, K_OFF = 50, V_OFF = 80, O_OFF = 105;
+    static constexpr int V_PIECES = 25, PASS_UNITS = 21, PASS_PIECES = 840;
+};
+namespace xbl {
+using Lay = XbLayout<10>;
+constexpr int MINL = xb::MAXL + 1, MAXL = Lay::MAXL;
+constexpr size_t IMG_BYTES = (size_t)Lay::PASS_PIECES * 1024;
+static_assert(xb::O1_PIECES + 4 * Lay::PAIR_PIECES <= Lay::PASS_PIECES && Lay::PASS_PIECES == Lay::PASS_UNITS * xb::UNIT, "long layout");
+static_assert(Lay::K_OFF + 3 * 10 == Lay::V_OFF && Lay::V_OFF + Lay::V_PIECES == Lay::O_OFF && Lay::O_OFF + 50 == Lay::PAIR_PIECES, "long pair");
+}  // namespace xbl
+
 size_t cross_block_image_bytes(int C) { return xb::IMG_BYTES; }
 bool cross_block_supported(int C, int heads, int ctx_len, int rows_per_batch) {
     return C == xb::C && heads == xb::HEADS && ctx_len >= 1 && ctx_len <= xb::MAXL && rows_per_batch > 0 && rows_per_batch % rf::TOK == 0;
@@ -44,10 +71,15 @@ bool cross_block_supported(int C, int heads, int ctx_len, int rows_per_batch) {
 
 // wo1 (attn1.to_out.0), wq2 (attn2.to_q), wo2 (attn2.to_out.0): [C][C] fp16 device tensors -> tmpl (cross_block_image_bytes):
 // the weight pieces of the image; the K / V pieces stay zero until bind_cross_block().  Synchronous (load time).
-int pack_cross_block(const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, hipStream_t stream) {
+// The weight pieces are laid out alike in both instances; only the pair stride and the Wo2 offset differ.
+template <int NKT>
+static int pack_cross_block_impl(const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, size_t img_bytes,
+                                 hipStream_t stream) {
     using namespace xb;
+    using Lay = XbLayout<NKT>;
+    constexpr int PAIR_PIECES = Lay::PAIR_PIECES, O_OFF = Lay::O_OFF;
     LAVIE_CHECK(C == xb::C, "cross_block: width %d is not built (320 only)", C);
-    LAVIE_HIP(hipMemsetAsync(tmpl, 0, IMG_BYTES, stream));
+    LAVIE_HIP(hipMemsetAsync(tmpl, 0, img_bytes, stream));
     std::vector<int2> lists[3];
     for (int t = 0; t < NT; ++t)
         for (int ks = 0; ks < KS; ++ks) {
@@ -79,6 +111,17 @@ int pack_cross_block(const half_t* wo1, const half_t* wq2, const half_t* wo2, in
     }
     const half_t* srcs[3] = {wo1, wq2, wo2};
     return rf_run_gathers(lists, srcs, 3, tmpl, stream);
+}
+
+int pack_cross_block(const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, hipStream_t stream) {
+    return pack_cross_block_impl<5>(wo1, wq2, wo2, C, tmpl, xb::IMG_BYTES, stream);
+}
+size_t cross_block_long_image_bytes(int C) { return xbl::IMG_BYTES; }
+bool cross_block_long_supported(int C, int heads, int ctx_len, int rows_per_batch) {
+    return C == xb::C && heads == xb::HEADS && ctx_len >= xbl::MINL && ctx_len <= xbl::MAXL && rows_per_batch > 0 && rows_per_batch % rf::TOK == 0;
+}
+int pack_cross_block_long(const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, hipStream_t stream) {
+    return pack_cross_block_impl<10>(wo1, wq2, wo2, C, tmpl, xbl::IMG_BYTES, stream);
 }
 
 // Batched gathers of the K (8-byte chunks) and V^T (single halfs: a transpose) pieces: blockIdx.y = video
@@ -171,6 +214,63 @@ int bind_cross_block(const half_t* tmpl, const half_t* kv, int B, int L, int C, 
     return 0;
 }
 
+// The long image: K pieces as above for ten key tiles; V^T as five full 32-key steps per channel tile (keys past L are zero).
+// Plans are kept by context length next to the short ones (the lengths do not overlap).
+static int bind_plan_long(int L, BindPlan** out) {
+    using namespace xb;
+    using Lay = XbLayout<10>;
+    auto it = g_bind_plans.find(L);
+    if (it != g_bind_plans.end()) { *out = &it->second; return 0; }
+    std::vector<int2> kl, vl;
+    const int ld = 2 * C;
+    for (int hp = 0; hp < 4; ++hp) {
+        const int h0 = 2 * hp, h1 = h0 + 1, P0 = O1_PIECES + Lay::PAIR_PIECES * hp;
+        for (int kt = 0; kt < 10; ++kt)
+            for (int slot = 0; slot < 64; ++slot) {
+                const int r = slot >> 2, q = (slot & 3) ^ rf::swz(r), key = 16 * kt + r;
+                for (int e = 0; e < 2; ++e)
+                    for (int half = 0; half < 2; ++half)
+                        kl.push_back(make_int2((P0 + Lay::K_OFF + 3 * kt + e) * 128 + slot * 2 + half,
+                                               key < L ? (key * ld + (e ? h1 : h0) * DH + 16 * half + 4 * q) / 4 : -1));
+                kl.push_back(make_int2((P0 + Lay::K_OFF + 3 * kt + 2) * 128 + slot * 2 + 0, (key < L && q < 2) ? (key * ld + h0 * DH + 32 + 4 * q) / 4 : -1));
+                kl.push_back(make_int2((P0 + Lay::K_OFF + 3 * kt + 2) * 128 + slot * 2 + 1, (key < L && q >= 2) ? (key * ld + h1 * DH + 32 + 4 * (q - 2)) / 4 : -1));
+            }
+        for (int j = 0; j < 5; ++j)
+            for (int s = 0; s < 5; ++s)
+                for (int slot = 0; slot < 64; ++slot) {
+                    const int r = slot >> 2, q = (slot & 3) ^ rf::swz(r), ch = pair_channel(h0, j, r);
+                    for (int jj = 0; jj < 8; ++jj) {
+                        const int key = 32 * s + 16 * (jj >> 2) + 4 * q + (jj & 3);
+                        vl.push_back(make_int2((P0 + Lay::V_OFF + 5 * j + s) * 512 + slot * 8 + jj, key < L ? key * ld + C + ch : -1));
+                    }
+                }
+    }
+    BindPlan plan;
+    plan.nk = (int)kl.size();
+    plan.nv = (int)vl.size();
+    LAVIE_HIP(hipMalloc(&plan.k_pairs, kl.size() * sizeof(int2)));
+    LAVIE_HIP(hipMalloc(&plan.v_pairs, vl.size() * sizeof(int2)));
+    LAVIE_HIP(hipMemcpy(plan.k_pairs, kl.data(), kl.size() * sizeof(int2), hipMemcpyHostToDevice));
+    LAVIE_HIP(hipMemcpy(plan.v_pairs, vl.data(), vl.size() * sizeof(int2), hipMemcpyHostToDevice));
+    *out = &(g_bind_plans[L] = plan);
+    return 0;
+}
+
+int bind_cross_block_long(const half_t* tmpl, const half_t* kv, int B, int L, int C, half_t* img, hipStream_t stream) {
+    LAVIE_CHECK(C == xb::C && L >= xbl::MINL && L <= xbl::MAXL && B >= 1, "cross_block_long: C=%d L=%d B=%d is not built", C, L, B);
+    BindPlan* plan = nullptr;
+    if (int rc = bind_plan_long(L, &plan)) return rc;
+    const size_t IMG = xbl::IMG_BYTES;
+    for (int b = 0; b < B; ++b)
+        LAVIE_HIP(hipMemcpyAsync(reinterpret_cast<char*>(img) + b * IMG, tmpl, IMG, hipMemcpyDeviceToDevice, stream));
+    hipLaunchKernelGGL(xb_gather8_kernel, dim3(cdiv(plan->nk, 256), B), dim3(256), 0, stream, (const uint2*)kv, (uint2*)img, plan->k_pairs,
+                       plan->nk, (size_t)L * 2 * C / 4, IMG / 8);
+    hipLaunchKernelGGL(xb_gather2_kernel, dim3(cdiv(plan->nv, 256), B), dim3(256), 0, stream, kv, img, plan->v_pairs, plan->nv,
+                       (size_t)L * 2 * C, IMG / 2);
+    LAVIE_HIP(hipGetLastError());
+    return 0;
+}
+
 struct CrossBlockParams {
     const half_t* att;        // [M, C] attn1 output (before its to_out projection)
     const half_t* x;          // [M, C] residual stream
@@ -191,10 +291,22 @@ __device__ __forceinline__ void xb_idle(SyncFn&& sync, std::integer_sequence<int
     (sync(std::integral_constant<int, Ks + 1>{}), ...);
 }
 
-template <int PF>
+// One kernel template for both instances: ARG = the LDS read-ahead depth (1..15), plus XB_LONG for the long variant's layout
+// (NKT = 10 key tiles per head).  Everything that depends on NKT is a compile-time branch, so cross_block_kernel<8> is the code
+// (and the symbol) it was before the long variant existed; the long instance is cross_block_kernel<8 + XB_LONG>.  (A wrapper
+// kernel around an inlined body renumbers the short instance's registers; a second template parameter renames its symbol.)
+constexpr int XB_LONG = 32;
+template <int ARG>
 __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const CrossBlockParams p) {
+    constexpr int PF = ARG & 15, NKT = (ARG & XB_LONG) ? 10 : 5;
     using namespace rf;
     using namespace xb;
+    using Lay = XbLayout<NKT>;
+    constexpr int PASS_UNITS = Lay::PASS_UNITS, PASS_PIECES = Lay::PASS_PIECES, PAIR_PIECES = Lay::PAIR_PIECES;
+    constexpr int K_OFF = Lay::K_OFF, V_OFF = Lay::V_OFF, O_OFF = Lay::O_OFF;
+    constexpr size_t IMG_BYTES = (size_t)PASS_PIECES * 1024;
+    // syncs an idle wave meets: those in front of every segment a working wave consumes (the padding is never read)
+    constexpr int IDLE_SYNCS = (O1_PIECES + 4 * PAIR_PIECES - 1) / tb::SEG;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const ring = smem;
     float* const vec = reinterpret_cast<float*>(smem + RING_BYTES);           // bo1 | gamma | beta | bo2
@@ -356,15 +468,17 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
                 }
                 __builtin_amdgcn_sched_barrier(0);
 
-                // ---- S^T[key][token] of both heads: 5 key tiles each
-                f32x4 S[2][5];
+                // ---- S^T[key][token] of both heads: NKT key tiles each
+                f32x4 S[2][NKT];
                 {
                     const half4_t z = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
                     half8_t qc0 = rf_cat(qp[0], qp[1]), qc1 = rf_cat(qp[3], qp[4]);
                     half4_t qm0 = q < 2 ? qp[2] : z, qm1 = q < 2 ? z : qp[2];       // rows of the shared tile that belong to each head
                     half8_t pend;
                     asm volatile("s_nop 4" : "+v"(qc0), "+v"(qc1), "+v"(qm0), "+v"(qm1));
-                    tb_run<P0 + K_OFF, 15, PF>(ring_lo, ring_hi, [&](auto m_, const half8_t& a) {
+                    // (the long variant reads K four pieces ahead: S[2][10] leaves no room for eight fragments in flight)
+                    constexpr int PFK = NKT == 5 ? PF : 4;
+                    tb_run<P0 + K_OFF, 3 * NKT, PFK>(ring_lo, ring_hi, [&](auto m_, const half8_t& a) {
                         constexpr int M = decltype(m_)::value;
                         constexpr int KT = M / 3, I = M % 3;
                         if constexpr (I == 0) rf_mfma32_first(S[0][KT], a, qc0);
@@ -377,27 +491,35 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
                             }
                         } else {
                             pend = a;
-                            if constexpr (KT == 4) {
+                            if constexpr (KT == NKT - 1) {
                                 rf_mfma_drain();
                                 const half4_t alo = {pend[0], pend[1], pend[2], pend[3]}, ahi = {pend[4], pend[5], pend[6], pend[7]};
-                                rf_mfma16(S[0][4], alo, qm0);
-                                rf_mfma16(S[1][4], ahi, qm1);
+                                rf_mfma16(S[0][NKT - 1], alo, qm0);
+                                rf_mfma16(S[1][NKT - 1], ahi, qm1);
                             }
                         }
                     }, sync);
+                    if constexpr (NKT == 5)
                     asm volatile("s_nop 15\n\ts_nop 15"
                                  : "+v"(S[0][0]), "+v"(S[0][1]), "+v"(S[0][2]), "+v"(S[0][3]), "+v"(S[0][4]), "+v"(S[1][0]), "+v"(S[1][1]),
                                    "+v"(S[1][2]), "+v"(S[1][3]), "+v"(S[1][4]));
+                    else
+                    asm volatile("s_nop 15\n\ts_nop 15"
+                                 : "+v"(S[0][0]), "+v"(S[0][1]), "+v"(S[0][2]), "+v"(S[0][3]), "+v"(S[0][4]), "+v"(S[0][5]), "+v"(S[0][6]),
+                                   "+v"(S[0][7]), "+v"(S[0][8]), "+v"(S[0][9]), "+v"(S[1][0]), "+v"(S[1][1]), "+v"(S[1][2]), "+v"(S[1][3]),
+                                   "+v"(S[1][4]), "+v"(S[1][5]), "+v"(S[1][6]), "+v"(S[1][7]), "+v"(S[1][8]), "+v"(S[1][9]));
                 }
                 // ---- softmax over the keys (registers x the four q lanes of a token), P^T packed as B fragments
-                half8_t pc[2][2];
+                // (5 tiles: two 32-deep fragments + a 16-deep one per head; 10 tiles: five 32-deep fragments)
+                constexpr int NPC = NKT == 5 ? 2 : 5;
+                half8_t pc[2][NPC];
                 half4_t p4[2];
                 float inv[2];
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                     float m = -INFINITY;
 #pragma unroll
-                    for (int kt = 0; kt < 5; ++kt)
+                    for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             if (16 * kt + 4 * q + r >= p.L) S[e][kt][r] = -INFINITY;
@@ -406,9 +528,9 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
                     m = fmaxf(m, __shfl_xor(m, 16, 64));
                     m = fmaxf(m, __shfl_xor(m, 32, 64));
                     float l = 0.f;
-                    half4_t pk[5];
+                    half4_t pk[NKT];
 #pragma unroll
-                    for (int kt = 0; kt < 5; ++kt) {
+                    for (int kt = 0; kt < NKT; ++kt) {
                         f32x4 ev;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) { ev[r] = __builtin_amdgcn_exp2f((S[e][kt][r] - m) * LOG2E); l += ev[r]; }
@@ -417,15 +539,21 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
                     l += __shfl_xor(l, 16, 64);
                     l += __shfl_xor(l, 32, 64);
                     inv[e] = __builtin_amdgcn_rcpf(l);
-                    pc[e][0] = rf_cat(pk[0], pk[1]);
-                    pc[e][1] = rf_cat(pk[2], pk[3]);
-                    p4[e] = pk[4];
+                    if constexpr (NKT == 5) {
+                        pc[e][0] = rf_cat(pk[0], pk[1]);
+                        pc[e][1] = rf_cat(pk[2], pk[3]);
+                        p4[e] = pk[4];
+                    } else {
+#pragma unroll
+                        for (int s2 = 0; s2 < NPC; ++s2) pc[e][s2] = rf_cat(pk[2 * s2], pk[2 * s2 + 1]);
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
 
                 // ---- O[channel][token] = V^T P^T: five channel tiles (the shared one once per head)
                 {
                     f32x4 O[5], osh[2];
+                    if constexpr (NKT == 5) {
                     asm volatile("s_nop 4" : "+v"(pc[0][0]), "+v"(pc[0][1]), "+v"(pc[1][0]), "+v"(pc[1][1]), "+v"(p4[0]), "+v"(p4[1]));
                     tb_run<P0 + V_OFF, 13, PF>(ring_lo, ring_hi, [&](auto m_, const half8_t& a) {
                         constexpr int M = decltype(m_)::value;
@@ -446,6 +574,23 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
                             else rf_mfma16(O[4], alo, p4[1]);
                         }
                     }, sync);
+                    } else {
+                    asm volatile("s_nop 4" : "+v"(pc[0][0]), "+v"(pc[0][1]), "+v"(pc[0][2]), "+v"(pc[0][3]), "+v"(pc[0][4]), "+v"(pc[1][0]),
+                                             "+v"(pc[1][1]), "+v"(pc[1][2]), "+v"(pc[1][3]), "+v"(pc[1][4]));
+                    // 25 pieces: channel tile J = M / 5, 32-key step SS = M % 5; in-place 32-deep chains only
+                    tb_run<P0 + V_OFF, 25, PF>(ring_lo, ring_hi, [&](auto m_, const half8_t& a) {
+                        constexpr int M = decltype(m_)::value;
+                        constexpr int J = M / 5, SS = M % 5;
+                        if constexpr (J == 2) {
+                            if constexpr (SS == 0) { rf_mfma32_first(osh[0], a, pc[0][0]); rf_mfma32_first(osh[1], a, pc[1][0]); }
+                            else { rf_mfma32(osh[0], a, pc[0][SS]); rf_mfma32(osh[1], a, pc[1][SS]); }
+                        } else {
+                            constexpr int E = J < 2 ? 0 : 1;
+                            if constexpr (SS == 0) rf_mfma32_first(O[J], a, pc[E][0]);
+                            else rf_mfma32(O[J], a, pc[E][SS]);
+                        }
+                    }, sync);
+                    }
                     asm volatile("s_nop 15\n\ts_nop 15" : "+v"(O[0]), "+v"(O[1]), "+v"(O[3]), "+v"(O[4]), "+v"(osh[0]), "+v"(osh[1]));
                     op[0] = rf_pack(O[0] * inv[0]);
                     op[1] = rf_pack(O[1] * inv[0]);
@@ -491,7 +636,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
             pair_body(std::integral_constant<int, 3>{});
         } else {
             // a wave without a tile in this pass still moves its share of the stream and meets every barrier
-            xb_idle(sync, std::make_integer_sequence<int, PASS_PIECES / tb::SEG - 1>{});
+            xb_idle(sync, std::make_integer_sequence<int, IDLE_SYNCS>{});
         }
 
         // end of pass: every wave is past the last segment, so the ring's first two slots may take the next pass's first units
@@ -513,6 +658,7 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+
 int launch_cross_block(const half_t* att, const half_t* x, half_t* y, int M, int rows_per_batch, int C, int heads, const half_t* img,
                        const float* bo1, const float* gamma, const float* beta, const float* bo2, int L, float scale, float eps,
                        hipStream_t stream) {
@@ -530,6 +676,28 @@ int launch_cross_block(const half_t* att, const half_t* x, half_t* y, int M, int
     const int grid = p.tiles < 256 ? p.tiles : 256;
     auto kern = cross_block_kernel<8>;      // LDS read-ahead depth 8
     if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc;     // once per kernel address, not per launch
+    if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);
+    else hipLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, p);
+    LAVIE_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_cross_block_long(const half_t* att, const half_t* x, half_t* y, int M, int rows_per_batch, int C, int heads, const half_t* img,
+                            const float* bo1, const float* gamma, const float* beta, const float* bo2, int L, float scale, float eps,
+                            hipStream_t stream) {
+    LAVIE_CHECK(cross_block_long_supported(C, heads, L, rows_per_batch), "cross_block_long: C=%d heads=%d L=%d rows_per_batch=%d is not built",
+                C, heads, L, rows_per_batch);
+    LAVIE_CHECK(att && x && y && img && bo1 && gamma && beta && bo2 && M > 0 && M % rows_per_batch == 0, "cross_block_long: bad arguments");
+    const double tok = (double)M;
+    ProfileScope prof(KC_FUSED_CROSS, stream, 2.0 * tok * C * 3.0 * C + 4.0 * tok * L * C,
+                      2.0 * 3.0 * tok * C + (double)(M / rows_per_batch) * xbl::IMG_BYTES, /*kernel_events=*/true);
+    CrossBlockParams p;
+    p.att = att; p.x = x; p.y = y; p.img = img; p.bo1 = bo1; p.gamma = gamma; p.beta = beta; p.bo2 = bo2;
+    p.tiles = M / rf::TOK; p.tiles_per_batch = rows_per_batch / rf::TOK; p.L = L; p.scale = scale; p.eps = eps;
+    constexpr int lds = rf::RING_BYTES + xb::VEC_BYTES;
+    const int grid = p.tiles < 256 ? p.tiles : 256;
+    auto kern = cross_block_kernel<8 + XB_LONG>;      // LDS read-ahead depth 8, ten key tiles
+    if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc;
     if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);
     else hipLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, p);
     LAVIE_HIP(hipGetLastError());

@@ -176,6 +176,44 @@ def cross_block(att, x, img, bo1, gamma, beta, bo2, rows_per_batch, ctx_len, hea
     return out
 
 
+def pack_cross_block_long(wo1, wq2, wo2, heads=8):
+    """As pack_cross_block, for the long variant (81..160 keys, lavie_cross_block_long_f16): its own template layout."""
+    _chk16(wo1, wq2, wo2)
+    C = wo1.shape[0]
+    lib = _lib.load()
+    nbytes = lib.lavie_cross_block_long_image_bytes(C, heads)
+    if nbytes == 0:
+        raise RuntimeError(f"cross_block_long: C={C} heads={heads} is not built")
+    tmpl = torch.empty(nbytes // 2, dtype=torch.float16, device=wo1.device)
+    _lib.check(lib.lavie_pack_cross_block_long_f16(_p(wo1), _p(wq2), _p(wo2), C, _p(tmpl), _stream()), "lavie_pack_cross_block_long_f16")
+    return tmpl
+
+
+def bind_cross_block_long(tmpl, kv, B, ctx_len):
+    """As bind_cross_block, for a long template and 81 <= ctx_len <= 160."""
+    _chk16(tmpl, kv)
+    C = kv.shape[1] // 2
+    if tuple(kv.shape) != (B * ctx_len, 2 * C):
+        raise RuntimeError("cross_block_long: kv must be [B * ctx_len, 2C]")
+    img = torch.empty(B * tmpl.numel(), dtype=torch.float16, device=tmpl.device)
+    _lib.check(_lib.load().lavie_bind_cross_block_long_f16(_p(tmpl), _p(kv), B, ctx_len, C, _p(img), _stream()),
+               "lavie_bind_cross_block_long_f16")
+    return img
+
+
+def cross_block_long(att, x, img, bo1, gamma, beta, bo2, rows_per_batch, ctx_len, heads, scale, eps=1e-5, out=None):
+    """cross_block over 81..160 keys with long images (bind_cross_block_long); `out` may be x itself."""
+    _chk16(att, x, img, out)
+    _chk32(bo1, gamma, beta, bo2)
+    M, C = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    _lib.check(_lib.load().lavie_cross_block_long_f16(_p(att), _p(x), _p(out), M, rows_per_batch, C, heads, _p(img), _p(bo1),
+                                                      _p(gamma), _p(beta), _p(bo2), ctx_len, scale, eps, _stream()),
+               "lavie_cross_block_long_f16")
+    return out
+
+
 def pack_conv3x3(weight, shortcut_weight=None):
     """[Cout, Cin, 3, 3] (+ optional 1x1 shortcut [Cout, Csc, 1, 1]) -> [Cout, 9*Cin (+ Csc)]."""
     _chk16(weight, shortcut_weight)

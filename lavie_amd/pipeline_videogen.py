@@ -6,7 +6,12 @@ Keeps the reference call surface (`__call__` keywords, `prompt_embeds=` / `negat
 on the MI355X: the UNet through liblavie_hip.so and CFG + scheduler step as one fused kernel.
 CLIP text encoding and VAE decoding are NOT part of this package's compute path: pass any stock
 PyTorch-ROCm `tokenizer`/`text_encoder`/`vae` objects to use them, or work with embeddings and
-`output_type="latent"` (what the benchmark measures: video-latents/s)."""
+`output_type="latent"` (what the benchmark measures: video-latents/s).
+
+Image conditioning (the fork's inference.py:248-353): with a `mapper` (lavie_amd.mapping.MappingNetwork) attached, an image
+widens each CFG half's context to `cat([text, mapper(image, text)], 1)`: 154 tokens for a 77-token prompt.  The image comes
+as `image_tensor` (through `clip_processor` + `clip_model.vision_model`, stock PyTorch) or as precomputed vision features
+`image_embeds`.  Without a mapper `image_tensor` is accepted and ignored, as before."""
 from dataclasses import dataclass
 import inspect
 import os
@@ -30,10 +35,11 @@ class VideoGenPipeline:
     cfg_shared_prefix = True
 
     def __init__(self, vae=None, text_encoder=None, tokenizer=None, unet=None, scheduler=None, clip_model=None,
-                 clip_processor=None):
+                 clip_processor=None, mapper=None):
         if unet is None:
             raise ValueError("unet is required")
         self.vae, self.text_encoder, self.tokenizer = vae, text_encoder, tokenizer
+        self.clip_model, self.clip_processor, self.mapper = clip_model, clip_processor, mapper
         self.unet = unet
         self.scheduler = scheduler or DDPMScheduler()
         self.vae_scale_factor = 8                        # 2 ** (len(vae.config.block_out_channels) - 1) for SD-1.x
@@ -41,8 +47,8 @@ class VideoGenPipeline:
 
     def to(self, device):
         self.unet.to(device)
-        for m in (self.vae, self.text_encoder):
-            if m is not None:
+        for m in (self.vae, self.text_encoder, self.clip_model, self.mapper):
+            if m is not None and hasattr(m, "to"):          # (callers may hand in placeholders for the CLIP objects)
                 m.to(device)
         return self
 
@@ -58,6 +64,13 @@ class VideoGenPipeline:
 
     def unload_lora_weights(self):
         self.unet.unload_lora()
+
+    def load_mapper(self, path_or_sd, num_heads: int = 12):
+        """The fork's saved image mapper (`mapper.pt`, fine_tuning.py:701) -> self.mapper on the pipeline's device, eval mode.
+        Works with a LoRA adapter loaded as well: that pair is the fork's sampling configuration."""
+        from .mapping import MappingNetwork
+        self.mapper = MappingNetwork.from_checkpoint(path_or_sd, num_heads=num_heads).to(self.device)
+        return self.mapper
 
     def enable_xformers_memory_efficient_attention(self, attention_op=None):
         """No-op: attn1 / attn2 always run the fused online-softmax kernel (attention.hip); nothing to switch on."""
@@ -133,8 +146,32 @@ class VideoGenPipeline:
         return self.unet.device
 
     # ------------------------------------------------------------------ prompt handling (273-420)
+    def _image_features(self, image_tensor, image_embeds, device):
+        """CLIP vision features [1 or B, 257, input_dim] for the mapper (inference.py:286-290), or None without an image."""
+        if image_embeds is not None:
+            return image_embeds.to(device=device)
+        if image_tensor is None:
+            return None
+        if self.clip_model is None or self.clip_processor is None:
+            raise ValueError("a mapper is attached and an image given, but there is no clip_model / clip_processor: "
+                             "attach them or pass image_embeds")
+        pixels = self.clip_processor(images=image_tensor, return_tensors="pt").pixel_values
+        # a CLIPModel (the fork's object) holds the tower as .vision_model; a CLIPVisionModel may be the tower itself
+        vision = getattr(self.clip_model, "vision_model", self.clip_model)
+        pixels = pixels.to(device=next(vision.parameters()).device, dtype=next(vision.parameters()).dtype)
+        return vision(pixel_values=pixels).last_hidden_state.to(device=device)
+
+    def _widen(self, embeds, image_features):
+        """cat([embeds, mapper(image, embeds)], 1) (inference.py:299-306, 339-345); one image broadcasts over the prompts."""
+        if image_features.shape[0] not in (1, embeds.shape[0]):
+            raise ValueError(f"got {image_features.shape[0]} images for {embeds.shape[0]} prompts (expected 1 or one per prompt)")
+        img = image_features.expand(embeds.shape[0], -1, -1)
+        param = next(self.mapper.parameters())
+        mapped = self.mapper(img.to(device=param.device, dtype=param.dtype), embeds.to(device=param.device, dtype=param.dtype))
+        return torch.cat([embeds, mapped.to(device=embeds.device, dtype=embeds.dtype)], dim=1)
+
     def _encode_prompt(self, prompt, device, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds,
-                       negative_prompt_embeds):
+                       negative_prompt_embeds, image_features=None):
         if prompt_embeds is None:
             if self.tokenizer is None or self.text_encoder is None:
                 raise ValueError("no tokenizer/text_encoder attached: pass prompt_embeds / negative_prompt_embeds")
@@ -143,7 +180,10 @@ class VideoGenPipeline:
             prompt_embeds = self.text_encoder(ids.to(device))[0]
         prompt_embeds = prompt_embeds.to(device=device)
         bs, n, _ = prompt_embeds.shape
-        prompt_embeds = prompt_embeds.repeat(1, num_images_per_prompt, 1).view(bs * num_images_per_prompt, n, -1)
+        if image_features is not None:
+            prompt_embeds = self._widen(prompt_embeds, image_features)
+        n_ctx = prompt_embeds.shape[1]
+        prompt_embeds = prompt_embeds.repeat(1, num_images_per_prompt, 1).view(bs * num_images_per_prompt, n_ctx, -1)
         if not do_cfg:
             return prompt_embeds
         if negative_prompt_embeds is None:
@@ -153,7 +193,9 @@ class VideoGenPipeline:
             ids = self.tokenizer(neg, padding="max_length", max_length=n, truncation=True, return_tensors="pt").input_ids
             negative_prompt_embeds = self.text_encoder(ids.to(device))[0]
         negative_prompt_embeds = negative_prompt_embeds.to(device=device)
-        negative_prompt_embeds = negative_prompt_embeds.repeat(1, num_images_per_prompt, 1).view(bs * num_images_per_prompt, n, -1)
+        if image_features is not None:
+            negative_prompt_embeds = self._widen(negative_prompt_embeds, image_features)
+        negative_prompt_embeds = negative_prompt_embeds.repeat(1, num_images_per_prompt, 1).view(bs * num_images_per_prompt, n_ctx, -1)
         return torch.cat([negative_prompt_embeds, prompt_embeds])           # line 418: unconditional half first
 
     def check_inputs(self, prompt, height, width, callback_steps, negative_prompt=None, prompt_embeds=None,
@@ -322,7 +364,7 @@ class VideoGenPipeline:
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None,
                  prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
                  output_type: Optional[str] = "pil", return_dict: bool = True, callback=None, callback_steps: int = 1,
-                 cross_attention_kwargs=None):
+                 cross_attention_kwargs=None, image_embeds: Optional[torch.Tensor] = None):
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
@@ -334,8 +376,10 @@ class VideoGenPipeline:
             batch_size = prompt_embeds.shape[0]
         device = self.device
         do_cfg = guidance_scale > 1.0
+        # image conditioning only with a mapper attached; without one the image is ignored, as the upstream pipeline does
+        image_features = self._image_features(image_tensor, image_embeds, device) if self.mapper is not None else None
         ctx = self._encode_prompt(prompt, device, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds,
-                                  negative_prompt_embeds).to(torch.float16).contiguous()
+                                  negative_prompt_embeds, image_features).to(torch.float16).contiguous()
         latents = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.config.in_channels, video_length,
                                        height, width, torch.float32, device, generator, latents)
         lora_scale = (cross_attention_kwargs or {}).get("scale")
