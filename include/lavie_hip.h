@@ -231,6 +231,22 @@ int lavie_latents_to_scaled_model_input(const float* x, void* model_in2, long lo
 int lavie_sampler_step(const void* eps, float* x, const float* noise, void* model_in, long long n, float k_x, float k_eps,
                        float c_x0, float c_xt, float sigma, float next_input_scale, void* stream);
 int lavie_latents_to_scaled_model_input1(const float* x, void* model_in, long long n, float input_scale, void* stream);
+/* Guidance + multistep step (DPM-Solver++ 2M, lavie_amd/scheduling_dpmsolver_multistep.py), one launch per denoising step.
+ * The five-coefficient form above cannot express a second-order multistep update: it needs the previous step's x0 prediction.
+ * Per element, fp32, in this order:
+ *   eps = eps_u + guidance (eps_c - eps_u)        (cfg variant only)
+ *   x0  = k_x x - k_eps eps
+ *   D   = c_prev != 0 ? x0 + c_prev (x0 - x0_prev) : x0
+ *   x'  = c_xt x + c_x0 D;   x0_prev <- x0;  x <- x';  model_in <- fp16(x' next_input_scale)   ([x' | x'] for the cfg variant)
+ * x0_prev: fp32 device buffer of the caller, n elements, updated in place.  With c_prev == 0 (first step, final step, order 1) it
+ * is written and NEVER read: it may be uninitialised.  No noise operand (the solver is deterministic), no atomics: bit-reproducible.
+ * No host synchronisation and no allocation: safe inside a stream capture.  Checked on the host before any HIP call: non-null
+ * tensors, n >= 1, finite scalars, eps / x / x0_prev / model_in 16-byte aligned (the kernel uses 16-byte accesses; under guidance
+ * with n % 8 != 0 the cond halves are not aligned and the launch takes a one-element-per-lane form, same arithmetic). */
+int lavie_cfg_multistep_step(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, float guidance, float k_x,
+                             float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream);
+int lavie_multistep_step(const void* eps, float* x, float* x0_prev, void* model_in, long long n, float k_x, float k_eps,
+                         float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Measurement hook: HIP-event timing per kernel class on the launch stream (bench.py's roofline leg).

@@ -91,6 +91,10 @@ SIGNATURES = {
     "lavie_sampler_step": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float,
                                     c_float, c_void_p]),
     "lavie_latents_to_scaled_model_input1": (c_int, [c_float_p, c_void_p, c_ll, c_float, c_void_p]),
+    "lavie_cfg_multistep_step": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float,
+                                          c_float, c_float, c_float, c_void_p]),
+    "lavie_multistep_step": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float,
+                                      c_float, c_void_p]),
     "lavie_debug_force_tile": (c_int, [c_int]),
     "lavie_debug_force_splits": (c_int, [c_int]),
     "lavie_debug_fused_mask": (c_int, [c_int]),

@@ -43,9 +43,32 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
                           vsr_prompt_embeds, vsr_negative_prompt_embeds, interp_prompt_embeds, interp_negative_prompt_embeds,
                           height: int = 320, width: int = 512, base_steps: int = 50, guidance_scale: float = 7.5,
                           interp_frames: int = 61, interp_cfg_scale: float = 4.0, vsr_steps: int = 50,
-                          vsr_guidance_scale: float = 7.5, noise_level: int = 150, generator=None, decode_final: bool = True):
+                          vsr_guidance_scale: float = 7.5, noise_level: int = 150, generator=None, decode_final: bool = True,
+                          base_scheduler=None, vsr_scheduler=None):
     """Returns (base_latents, interp_latents, vsr_latents, frames or None).  Text embeddings are passed per stage (the base
-    and interpolation stages use SD-1.4's CLIP, 768 wide; the VSR stage the x4-upscaler's, 1024 wide)."""
+    and interpolation stages use SD-1.4's CLIP, 768 wide; the VSR stage the x4-upscaler's, 1024 wide).
+    `base_scheduler` / `vsr_scheduler` replace the two diffusers-style stages' schedulers for this call (for instance a
+    DPMSolverMultistepScheduler with fewer `base_steps` / `vsr_steps`); the pipelines get their own back afterwards.  The
+    interpolation stage samples with its SpacedDiffusion object and has no such switch."""
+    swapped = [(pipe, pipe.scheduler) for pipe, sch in ((base_pipe, base_scheduler), (vsr_pipe, vsr_scheduler)) if sch is not None]
+    if base_scheduler is not None:
+        base_pipe.scheduler = base_scheduler
+    if vsr_scheduler is not None:
+        vsr_pipe.scheduler = vsr_scheduler
+    try:
+        return _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, prompt_embeds, negative_prompt_embeds,
+                        vsr_prompt_embeds, vsr_negative_prompt_embeds, interp_prompt_embeds, interp_negative_prompt_embeds, height,
+                        width, base_steps, guidance_scale, interp_frames, interp_cfg_scale, vsr_steps, vsr_guidance_scale,
+                        noise_level, generator, decode_final)
+    finally:
+        for pipe, own in swapped:
+            pipe.scheduler = own
+
+
+def _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, prompt_embeds, negative_prompt_embeds,
+             vsr_prompt_embeds, vsr_negative_prompt_embeds, interp_prompt_embeds, interp_negative_prompt_embeds, height, width,
+             base_steps, guidance_scale, interp_frames, interp_cfg_scale, vsr_steps, vsr_guidance_scale, noise_level, generator,
+             decode_final):
     dev = base_pipe.device
     # 1. base T2V (base/pipelines/sample.py:78-91)
     base = base_pipe(prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, height=height, width=width,

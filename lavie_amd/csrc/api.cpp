@@ -299,6 +299,34 @@ int lavie_sampler_step(const void* eps, float* x, const float* noise, void* mode
     return launch_sampler_step(H(eps), x, noise, H(model_in), n, k_x, k_eps, c_x0, c_xt, sigma, next_input_scale, S(stream));
 }
 
+// Host-side argument check of the two multistep entries, before any HIP call: the kernel uses 16-byte accesses on all four tensors.
+static int multistep_args(const char* who, const void* eps, const float* x, const float* x0_prev, const void* model_in,
+                          long long n, const float* scalars, int nscalars) {
+    LAVIE_CHECK(eps && x && x0_prev && model_in, "%s: null argument", who);
+    LAVIE_CHECK(n >= 1, "%s: n=%lld must be >= 1", who, n);
+    for (int i = 0; i < nscalars; ++i)
+        LAVIE_CHECK(__builtin_isfinite(scalars[i]), "%s: scalar argument %d (%g) is not finite", who, i, (double)scalars[i]);
+    const void* ptrs[4] = {eps, x, x0_prev, model_in};
+    for (const void* p : ptrs)
+        LAVIE_CHECK(((uintptr_t)p & 15) == 0, "%s: tensor at %p is not 16-byte aligned", who, p);
+    return 0;
+}
+
+int lavie_cfg_multistep_step(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, float guidance, float k_x,
+                             float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream) {
+    const float s[7] = {guidance, k_x, k_eps, c_x0, c_xt, c_prev, next_input_scale};
+    if (int rc = multistep_args("cfg_multistep_step", eps2, x, x0_prev, model_in2, n, s, 7)) return rc;
+    return launch_cfg_multistep_step(H(eps2), x, x0_prev, H(model_in2), n, guidance, k_x, k_eps, c_x0, c_xt, c_prev,
+                                     next_input_scale, S(stream));
+}
+
+int lavie_multistep_step(const void* eps, float* x, float* x0_prev, void* model_in, long long n, float k_x, float k_eps,
+                         float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream) {
+    const float s[6] = {k_x, k_eps, c_x0, c_xt, c_prev, next_input_scale};
+    if (int rc = multistep_args("multistep_step", eps, x, x0_prev, model_in, n, s, 6)) return rc;
+    return launch_multistep_step(H(eps), x, x0_prev, H(model_in), n, k_x, k_eps, c_x0, c_xt, c_prev, next_input_scale, S(stream));
+}
+
 int lavie_latents_to_scaled_model_input1(const float* x, void* model_in, long long n, float input_scale, void* stream) {
     LAVIE_CHECK(x && model_in && n > 0, "latents_to_scaled_model_input1: bad arguments");
     return launch_f32_to_f16_scaled(x, H(model_in), n, input_scale, S(stream));

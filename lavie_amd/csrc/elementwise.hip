@@ -376,6 +376,114 @@ int launch_sampler_step(const half_t* eps, float* x, const float* noise, half_t*
     return 0;
 }
 
+// ------------------------------------------------------------------ CFG + multistep step (DPM-Solver++ 2M)
+// The five-coefficient step above plus one history operand: the previous step's x0 prediction, an fp32 buffer of the caller
+// that this kernel reads (HIST) and always rewrites.  Per element, fp32, in this order (scheduling_dpmsolver_multistep.py):
+//   eps = eps_u + g (eps_c - eps_u);  x0 = kx x - ke eps;  D = x0 + cp (x0 - x0_prev)  [HIST]  or  x0;  x' = c0 D + ct x
+//   x0_prev <- x0;  x <- x';  model_in <- fp16(x' in_scale)  (both CFG halves)
+// HIST = false (cp == 0: first step, final step, order 1) has no load of x0_prev at all: whatever the buffer holds, NaN
+// included, cannot reach the output.
+// The rounding points are fixed in the source (contraction off, the two fused multiply-adds spelled out) instead of left to the
+// compiler's contraction of a * b + c * d, which it may resolve either way: eps and D are one fma each, x0 = fma(-ke, eps,
+// round(kx x)), x' = round(ct x) + round(c0 D).  These are the instructions sampler_step_kernel<true> compiles to, so with
+// cp == 0 and sigma == 0 the two kernels give the same x, and the same model input when in_scale == 1 (scaled_f16 below;
+// tests/test_gpu_dpmsolver.py).
+// HBM-bound: 16-byte accesses, eight elements per lane (one half8 per eps half, two float4 per fp32 tensor); lanes past the
+// vector body take one element each (n % 8 of them, or all n when the cond half of eps2 / model_in2 is not 16-byte
+// aligned because n % 8 != 0 under guidance).
+template <bool CFG, bool HIST>
+__device__ __forceinline__ void multistep_element(float eu, float ec, float guidance, float xt, float x0p, float kx, float ke,
+                                                  float c0, float ct, float cp, float& x0, float& xn) {
+#pragma clang fp contract(off)
+    const float eps = CFG ? __builtin_fmaf(guidance, ec - eu, eu) : eu;
+    x0 = __builtin_fmaf(-ke, eps, kx * xt);
+    const float d = HIST ? __builtin_fmaf(cp, x0 - x0p, x0) : x0;
+    xn = ct * xt + c0 * d;
+}
+
+// fp16(fp32(v s)): the product is rounded to fp32 and that value converted, what torch's (x * s).half() gives.  Left alone the
+// compiler folds the pair into one v_fma_mixlo_f16 in the one-element form only (as in sampler_step_kernel), which rounds the
+// exact product once: the two forms of this kernel would then differ in the last fp16 bit on rare elements when s != 1.
+__device__ __forceinline__ half_t scaled_f16(float v, float s) {
+    float p = v * s;
+    asm("" : "+v"(p));
+    return (half_t)p;
+}
+
+template <bool CFG, bool HIST>
+__global__ __launch_bounds__(256) void multistep_step_kernel(const half_t* __restrict__ eps2, float* __restrict__ x,
+                                                             float* __restrict__ x0_prev, half_t* __restrict__ model_in2,
+                                                             long n, long nvec, float guidance, float kx, float ke, float c0,
+                                                             float ct, float cp, float in_scale) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < nvec) {
+        const long i = t * 8;
+        const half8_t eu = *reinterpret_cast<const half8_t*>(eps2 + i);
+        half8_t ec = eu;
+        if (CFG) ec = *reinterpret_cast<const half8_t*>(eps2 + n + i);
+        const f32x4 xa = *reinterpret_cast<const f32x4*>(x + i), xb = *reinterpret_cast<const f32x4*>(x + i + 4);
+        f32x4 pa = {0.f, 0.f, 0.f, 0.f}, pb = pa;
+        if (HIST) {
+            pa = *reinterpret_cast<const f32x4*>(x0_prev + i);
+            pb = *reinterpret_cast<const f32x4*>(x0_prev + i + 4);
+        }
+        f32x4 na, nb, oa, ob;
+        half8_t h;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float xt = j < 4 ? xa[j & 3] : xb[j & 3];
+            const float x0p = j < 4 ? pa[j & 3] : pb[j & 3];
+            float x0, xn;
+            multistep_element<CFG, HIST>((float)eu[j], (float)ec[j], guidance, xt, x0p, kx, ke, c0, ct, cp, x0, xn);
+            if (j < 4) { oa[j & 3] = x0; na[j & 3] = xn; } else { ob[j & 3] = x0; nb[j & 3] = xn; }
+            h[j] = scaled_f16(xn, in_scale);
+        }
+        *reinterpret_cast<f32x4*>(x0_prev + i) = oa;
+        *reinterpret_cast<f32x4*>(x0_prev + i + 4) = ob;
+        *reinterpret_cast<f32x4*>(x + i) = na;
+        *reinterpret_cast<f32x4*>(x + i + 4) = nb;
+        *reinterpret_cast<half8_t*>(model_in2 + i) = h;
+        if (CFG) *reinterpret_cast<half8_t*>(model_in2 + n + i) = h;
+        return;
+    }
+    const long i = nvec * 8 + (t - nvec);
+    if (i >= n) return;
+    float x0, xn;
+    multistep_element<CFG, HIST>((float)eps2[i], CFG ? (float)eps2[n + i] : 0.f, guidance, x[i], HIST ? x0_prev[i] : 0.f, kx, ke,
+                                 c0, ct, cp, x0, xn);
+    x0_prev[i] = x0;
+    x[i] = xn;
+    const half_t h = scaled_f16(xn, in_scale);
+    model_in2[i] = h;
+    if (CFG) model_in2[n + i] = h;
+}
+
+template <bool CFG>
+static int launch_multistep(const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n, float guidance,
+                            float kx, float ke, float c0, float ct, float cp, float in_scale, hipStream_t stream) {
+    // under guidance the cond halves start n elements in: 16-byte aligned only when n % 8 == 0 (every latent shape of the
+    // pipelines); otherwise every lane takes one element
+    const long nvec = (!CFG || n % 8 == 0) ? (long)(n / 8) : 0;
+    const int64_t lanes = nvec + (n - nvec * 8);
+    const int64_t blocks = (lanes + 255) / 256;
+    LAVIE_CHECK(blocks <= 0x7fffffff, "multistep step: n=%lld does not fit one launch", (long long)n);
+    auto kern = cp != 0.f ? multistep_step_kernel<CFG, true> : multistep_step_kernel<CFG, false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, stream, eps2, x, x0_prev, model_in2, (long)n, nvec,
+                       guidance, kx, ke, c0, ct, cp, in_scale);
+    LAVIE_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_cfg_multistep_step(const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n, float guidance,
+                              float kx, float ke, float c0, float ct, float cp, float in_scale, hipStream_t stream) {
+    return launch_multistep<true>(eps2, x, x0_prev, model_in2, n, guidance, kx, ke, c0, ct, cp, in_scale, stream);
+}
+
+int launch_multistep_step(const half_t* eps, float* x, float* x0_prev, half_t* model_in, int64_t n, float kx, float ke,
+                          float c0, float ct, float cp, float in_scale, hipStream_t stream) {
+    return launch_multistep<false>(eps, x, x0_prev, model_in, n, 1.0f, kx, ke, c0, ct, cp, in_scale, stream);
+}
+
 template <bool DUP>
 __global__ void f32_to_f16_kernel(const float* __restrict__ x, half_t* __restrict__ out2, long n, float in_scale) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

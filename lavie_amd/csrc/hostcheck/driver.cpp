@@ -359,6 +359,34 @@ int main(int argc, char** argv) {
         REQUIRE(lavie_linear_lnfold_f16(x.data(), wq.data(), v.data(), nullptr, st.data(), qkv.data(), 64, 960, 320, nullptr) != 0);
         REQUIRE(lavie_linear_lnfold_f16(x.data(), wq.data(), v.data(), s3.data(), st.data(), qkv.data(), 64, 960, 300, nullptr) != 0);
     }
+    {   // the multistep sampler step: every refusal comes before a HIP call; accepted calls reach the (stubbed) launch, vector body,
+        // ragged tail and the one-element-per-lane form under guidance with n % 8 != 0
+        alignas(16) static unsigned short eps[2 * 40], min2[2 * 40];
+        alignas(16) static float x[40], hist[40];
+        const float nan = __builtin_nanf(""), inf = __builtin_inff();
+        const long before = lavie_hostcheck_launches();
+        REQUIRE(lavie_cfg_multistep_step(eps, x, hist, min2, 40, 7.5f, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) == 0);
+        REQUIRE(lavie_cfg_multistep_step(eps, x, hist, min2, 37, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 1.f, nullptr) == 0);
+        REQUIRE(lavie_multistep_step(eps, x, hist, min2, 37, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 0.9f, nullptr) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 3);
+        REQUIRE(lavie_cfg_multistep_step(nullptr, x, hist, min2, 40, 7.5f, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_cfg_multistep_step(eps, nullptr, hist, min2, 40, 7.5f, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_cfg_multistep_step(eps, x, nullptr, min2, 40, 7.5f, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_cfg_multistep_step(eps, x, hist, nullptr, 40, 7.5f, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_cfg_multistep_step(eps, x, hist, min2, 0, 7.5f, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_cfg_multistep_step(eps, x, hist, min2, -8, 7.5f, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_cfg_multistep_step(eps, x, hist, min2, 40, nan, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_cfg_multistep_step(eps, x, hist, min2, 40, 7.5f, 1.f, 0.5f, 1.f, 0.f, inf, 1.f, nullptr) != 0);
+        REQUIRE(lavie_cfg_multistep_step(eps, x, hist, min2, 40, 7.5f, 1.f, 0.5f, 1.f, 0.f, 0.f, nan, nullptr) != 0);
+        REQUIRE(lavie_cfg_multistep_step(eps + 1, x, hist, min2, 32, 7.5f, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_cfg_multistep_step(eps, x + 1, hist, min2, 32, 7.5f, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_multistep_step(eps, x, hist + 2, min2, 32, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_multistep_step(eps, x, hist, min2 + 4, 32, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_multistep_step(nullptr, x, hist, min2, 32, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_multistep_step(eps, x, hist, min2, 0, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_multistep_step(eps, x, hist, min2, 32, 1.f, -inf, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 3);
+    }
     REQUIRE(lavie_upsample_conv3x3_supported(320, 32, 20, 32) >= 0);
     int buckets[16 * 16];
     REQUIRE(lavie_relpos_buckets(16, 32, 32, buckets) == 0);

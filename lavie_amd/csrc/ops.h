@@ -85,6 +85,13 @@ int launch_f32_to_f16_dup2(const float* x, half_t* out2, int64_t n, float in_sca
 int launch_sampler_step(const half_t* eps, float* x, const float* noise, half_t* model_in, int64_t n, float kx, float ke,
                         float c0, float ct, float sigma, float in_scale, hipStream_t stream);
 int launch_f32_to_f16_scaled(const float* x, half_t* out, int64_t n, float in_scale, hipStream_t stream);
+// Guidance + multistep (DPM-Solver++ 2M) step: the five-coefficient form with the previous x0 prediction as history:
+//   x0 = kx x - ke eps; D = cp != 0 ? x0 + cp (x0 - x0_prev) : x0; x' = c0 D + ct x; x0_prev <- x0 (never read when cp == 0).
+//   eps2 / x / x0_prev / model_in2 must be 16-byte aligned (checked by the C entry points).
+int launch_cfg_multistep_step(const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n, float guidance,
+                              float kx, float ke, float c0, float ct, float cp, float in_scale, hipStream_t stream);
+int launch_multistep_step(const half_t* eps, float* x, float* x0_prev, half_t* model_in, int64_t n, float kx, float ke,
+                          float c0, float ct, float cp, float in_scale, hipStream_t stream);
 int launch_fill_relpos_bias(const half_t* emb, const int* buckets, float* out, int heads, int F, hipStream_t stream);
 
 // ---- pack.hip : one-off weight repacking at load time

@@ -451,6 +451,34 @@ def sampler_step(eps, x, noise, model_in, coeffs, next_input_scale: float = 1.0)
                "lavie_sampler_step")
 
 
+def cfg_multistep_step(eps2, x, x0_prev, model_in2, guidance, coeffs, next_input_scale: float = 1.0):
+    """Fused CFG + multistep (DPM-Solver++ 2M) update; `coeffs` = (k_x, k_eps, c_x0, c_xt, c_prev) from a multistep scheduler's
+    `coefficients`; `x0_prev` = fp32 history of x's size, rewritten every step and read only when c_prev != 0."""
+    _chk16(eps2, model_in2)
+    _chk32(x, x0_prev)
+    n = x.numel()
+    if eps2.numel() != 2 * n or model_in2.numel() != 2 * n or x0_prev.numel() != n:
+        raise ValueError("cfg_multistep_step: eps2 / model_in2 must have twice, x0_prev as many elements as x")
+    k_x, k_e, c_x0, c_xt, c_prev = coeffs
+    _lib.check(_lib.load().lavie_cfg_multistep_step(_p(eps2), _p(x), _p(x0_prev), _p(model_in2), n, float(guidance), float(k_x),
+                                                    float(k_e), float(c_x0), float(c_xt), float(c_prev),
+                                                    float(next_input_scale), _stream()),
+               "lavie_cfg_multistep_step")
+
+
+def multistep_step(eps, x, x0_prev, model_in, coeffs, next_input_scale: float = 1.0):
+    """The multistep update without classifier-free guidance (guidance_scale <= 1): eps / model_in are fp16 of x's size."""
+    _chk16(eps, model_in)
+    _chk32(x, x0_prev)
+    n = x.numel()
+    if eps.numel() != n or model_in.numel() != n or x0_prev.numel() != n:
+        raise ValueError("multistep_step: eps / model_in / x0_prev must have as many elements as x")
+    k_x, k_e, c_x0, c_xt, c_prev = coeffs
+    _lib.check(_lib.load().lavie_multistep_step(_p(eps), _p(x), _p(x0_prev), _p(model_in), n, float(k_x), float(k_e),
+                                                float(c_x0), float(c_xt), float(c_prev), float(next_input_scale), _stream()),
+               "lavie_multistep_step")
+
+
 def latents_to_model_input1(x, model_in, input_scale: float = 1.0):
     _chk32(x)
     _chk16(model_in)

@@ -132,6 +132,9 @@ class VideoGenPipeline:
         elif method == "eulerdiscrete":
             from .scheduling_euler_discrete import EulerDiscreteScheduler
             scheduler = EulerDiscreteScheduler(**betas)
+        elif method == "dpmsolver++":          # not a branch of sample.py: the second-order multistep sampler of this package
+            from .scheduling_dpmsolver_multistep import DPMSolverMultistepScheduler
+            scheduler = DPMSolverMultistepScheduler(**betas)
         else:
             raise NotImplementedError(f"sample_method {method!r} (sample.py:44-63 knows ddim / eulerdiscrete / ddpm)")
         size = cfg.get("image_size", [320, 512])
@@ -257,8 +260,12 @@ class VideoGenPipeline:
         # `eta` goes to the scheduler only if its step takes one (DDIM), as prepare_extra_step_kwargs does
         # (pipeline_videogen.py:431-446); DDPM ignores it
         takes_eta = "eta" in inspect.signature(sch.coefficients).parameters
+        # a multistep scheduler says so itself (DPMSolverMultistepScheduler.multistep): its fifth coefficient is c_prev, not a
+        # noise sigma, and the step kernel keeps the previous x0 prediction in a buffer beside the fp32 latents
+        multistep = bool(getattr(sch, "multistep", False))
         do_cfg = guidance_scale > 1.0
         x = latents.to(torch.float32).contiguous().clone()
+        x0_prev = torch.empty_like(x) if multistep else None      # never read before the first step has written it (c_prev = 0)
         p = x.shape[0]
         nb = 2 * p if do_cfg else p                        # model batch (:666)
         if ctx.shape[0] != nb:
@@ -307,7 +314,7 @@ class VideoGenPipeline:
                 coeffs = sch.coefficients(t, eta) if takes_eta else sch.coefficients(t)
                 noise = None
                 slot = i & 1
-                if coeffs[4] != 0.0:            # the step adds noise (DDPM: every step but the last; DDIM: only with eta > 0)
+                if not multistep and coeffs[4] != 0.0:   # the step adds noise (DDPM: every step but the last; DDIM: only with eta > 0)
                     if host_noise:
                         if copy_done[slot] is not None:
                             copy_done[slot].synchronize()
@@ -331,11 +338,16 @@ class VideoGenPipeline:
                     else:
                         noise = noise_dev.normal_(generator=generator) if generator is not None else noise_dev.normal_()
                 next_scale = in_scale(timesteps[i + 1]) if in_scale and i + 1 < len(timesteps) else 1.0
-                if do_cfg:
+                if multistep:
+                    if do_cfg:
+                        ops.cfg_multistep_step(eps, x, x0_prev, model_in, guidance_scale, coeffs, next_scale)
+                    else:
+                        ops.multistep_step(eps, x, x0_prev, model_in, coeffs, next_scale)
+                elif do_cfg:
                     ops.cfg_ddpm_step(eps, x, noise, model_in, guidance_scale, coeffs, next_scale)   # lines 667, 679-683 fused
                 else:
                     ops.sampler_step(eps, x, noise, model_in, coeffs, next_scale)                    # lines 667, 683
-                if host_noise and coeffs[4] != 0.0:
+                if host_noise and noise is not None:
                     step_done[slot] = torch.cuda.Event()
                     step_done[slot].record(main)
                 if callback is not None and i % callback_steps == 0:

@@ -5,7 +5,8 @@ loop of the VSR stage, and the 8-frame chunk driver of `vsr/sample.py:104-123`.
 negative_prompt / eta / generator / latents / prompt_embeds / negative_prompt_embeds / output_type / callback).  The loop
 (:706-735) runs the engine with the fused guidance + scheduler-step kernel: per step the UNet sees
 [latents | noised low-res frames | 0] for the [negative | prompt] halves, then `lavie_cfg_sampler_step` applies guidance, the
-scheduler update in its five-coefficient form and writes the next fp16 model input.  Text encoder and VAE are stock
+scheduler update in its five-coefficient form and writes the next fp16 model input (a multistep scheduler, `multistep = True`:
+`lavie_cfg_multistep_step` with an x0 history that lives for one call, so for one chunk).  Text encoder and VAE are stock
 PyTorch-ROCm objects a caller may attach (outside the latents metric): without them pass `prompt_embeds` and use
 `output_type="latent"`."""
 import inspect
@@ -80,7 +81,9 @@ class VideoUpscalePipeline:
         timesteps = [float(t) if fractional else int(t) for t in sch.timesteps]
         takes_eta = "eta" in inspect.signature(sch.coefficients).parameters
         in_scale = getattr(sch, "model_input_scale", None)
+        multistep = bool(getattr(sch, "multistep", False))      # DPM-Solver++: coeffs[4] is c_prev and the kernel keeps an x0 history
         x = latents.to(torch.float32).contiguous().clone()
+        x0_prev = torch.empty_like(x) if multistep else None    # per call, so per chunk: the first step (c_prev = 0) never reads it
         p = x.shape[0]
         model_in = torch.empty((2 * p,) + tuple(x.shape[1:]), dtype=torch.float16, device=dev)
         ops.latents_to_model_input(x, model_in, in_scale(timesteps[0]) if in_scale else 1.0)
@@ -95,10 +98,13 @@ class VideoUpscalePipeline:
                 eps = self.unet(model_in, t_dev[i], low, encoder_hidden_states=ctx, class_labels=labels).sample        # :716-718
                 coeffs = sch.coefficients(t, eta) if takes_eta else sch.coefficients(t)
                 noise = None
-                if coeffs[4] != 0.0:
+                if not multistep and coeffs[4] != 0.0:
                     noise = noise_dev.copy_(randn_tensor(x.shape, generator=generator, device=dev, dtype=torch.float32))
                 next_scale = in_scale(timesteps[i + 1]) if in_scale and i + 1 < len(timesteps) else 1.0
-                ops.cfg_ddpm_step(eps, x, noise, model_in, guidance_scale, coeffs, next_scale)                          # :721-726
+                if multistep:
+                    ops.cfg_multistep_step(eps, x, x0_prev, model_in, guidance_scale, coeffs, next_scale)
+                else:
+                    ops.cfg_ddpm_step(eps, x, noise, model_in, guidance_scale, coeffs, next_scale)                      # :721-726
                 if callback is not None and i % callback_steps == 0:
                     callback(i, t, x)
         finally:
