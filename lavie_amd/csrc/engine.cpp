@@ -616,10 +616,19 @@ int UNet::ensure_tables(int F, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------ forward
+// The switches that decide which kernels a call runs, as one value: read once at the entry point (forward, cache_context,
+// resnet_forward, transformer_forward) or enumerated by prepare() for its dry runs; nothing below reads the switches themselves
+struct Route {
+    int mask;               // fused_mask(): bits 0, 1, 2, 8 the row-resident kernels, 4 the parity upsample convs, 5 producer-side GroupNorm statistics
+    bool shared;            // set_cfg_shared_input: the layers in front of the first text cross-attention run on half the batch
+    bool ln_fold;           // set_ln_fold: LayerNorm folded into the producer / consumer GEMM epilogues
+};
+
 struct FwdCtx {
     hipStream_t s;
     DeviceArena* ws;
     bool dry;               // plan only: allocate, launch nothing
+    Route route;
     int B, F, ctx_len;
     float* gn_ws;           // GroupNorm scratch, gn_workspace_floats(B*F, groups) floats
     const int* labels = nullptr;   // VSR noise level per video (host), num_class_embeds > 0
@@ -679,25 +688,19 @@ static int trace_halves(const FwdCtx& c, const char* what, const void* p, size_t
     LAVIE_CHECK(var != nullptr, "workspace exhausted: call lavie_unet_prepare for this shape (needed %zu more B)", \
                 (size_t)(count) * sizeof(type))
 
-struct LnFold {            // consumer side of a folded LayerNorm
+// LayerNorm row statistics of a block's residual stream, between the GEMM whose epilogue emits them and the LayerNorm-folded GEMMs
+// that consume them.  The producer leaves per-wave-tile partials; the first consumer finalizes them on demand, once (round 4).
+struct RowStats {
+    float* partials;       // [M, slots, 2] (sum, sum^2): slots = one per wave tile of the producer's plan
     float* stats;          // [M, 2] (mean, rstd) of the rows
-    const float* s;        // row sums of the folded weights
-    // round 4: the producer leaves its partials un-finalized; the first consumer finalizes them on demand, once
-    const float* partials = nullptr;   // [M, slots, 2] of the rows' latest producer, or nullptr when `stats` was written directly
-    int slots = 0, row_len = 0, rows = 0;
-    bool final_ok = false;             // `stats` holds the finalized (mean, rstd) of the current rows
-};
-struct RowStat {           // producer side: partials [M, slots, 2] -> (mean, rstd) [M, 2]; slots = one per wave tile of the producer's plan
-    float* partials;
-    float* mean_rstd;
-    LnFold* sink = nullptr;            // told where the partials are (no finalize launch); nullptr = finalize at once
+    int slots = 0, row_len = 0, rows = 0;      // of the latest producer
+    bool pending = false;  // `partials` are newer than `stats`
 };
 
 // GroupNorm statistics from the producing kernel (igemm.h colstat_out, round 4).  Every tensor a GroupNorm may read gets a small
 // buffer next to it (same workspace lifetime); the launcher that writes the tensor fills it and describes it in a GnColStat that
 // travels WITH the tensor through the wiring below (explicitly, never keyed by address: workspace addresses are reused).
 static size_t colstat_floats(size_t M, int C) { return (M / COLSTAT_REDUCE_ROWS + 8) * (size_t)C * 2; }
-static bool colstat_on() { return (fused_mask() & 32) != 0; }
 // One implicit GEMM on the forward's stream: plan it, describe its column statistics (cs_buf / cs_out, when asked for), take the
 // split-K slab from the workspace, launch unless this is the dry run.  The dry run passes placeholder addresses and so gets the
 // plan of the real call.  *plan_out (optional) receives the plan.
@@ -706,7 +709,7 @@ static int run_igemm(FwdCtx& c, IgemmParams& p, bool gather, int epilogue, float
     p.splits = plan.splits;
     p.colstat_out = nullptr;
     if (cs_out) *cs_out = GnColStat();
-    if (cs_buf && cs_out && colstat_on() && plan.colstat_rows > 0) {
+    if (cs_buf && cs_out && (c.route.mask & 32) && plan.colstat_rows > 0) {
         p.colstat_out = cs_buf;
         cs_out->partials = cs_buf;
         cs_out->C = p.N;
@@ -726,33 +729,30 @@ static int run_igemm(FwdCtx& c, IgemmParams& p, bool gather, int epilogue, float
     return rc;
 }
 
+// rs with fold_s (the row sums of LayerNorm-folded weights W): the GEMM consumes the rows' statistics; rs alone: its epilogue emits them
 static int linear(FwdCtx& c, const half_t* A, int lda, const half_t* W, const float* bias, int N, int K, const half_t* R,
-                  half_t* C, int ldc, int M, int epilogue = EPI_LINEAR, LnFold* fold = nullptr,
-                  const RowStat* rowstat = nullptr, int ldw = 0, float* cs_buf = nullptr, GnColStat* cs_out = nullptr) {
+                  half_t* C, int ldc, int M, int epilogue = EPI_LINEAR, RowStats* rs = nullptr, const float* fold_s = nullptr,
+                  int ldw = 0, float* cs_buf = nullptr, GnColStat* cs_out = nullptr) {
     LAVIE_CHECK(K % IGEMM_BK == 0, "linear: K=%d must be a multiple of %d", K, IGEMM_BK);
     IgemmParams p;
     memset(&p, 0, sizeof(p));
     p.A = A; p.lda = lda; p.W = W; p.ldw = ldw > 0 ? ldw : K; p.C = C; p.ldc = ldc; p.bias = bias; p.R = R; p.ldr = ldc;
     p.M = M; p.N = N; p.nk = K / IGEMM_BK;
-    p.rowstat_out = rowstat ? rowstat->partials : nullptr;
-    if (fold) {
-        p.ln_s = fold->s;
-        if (fold->partials && !fold->final_ok) {           // the producer left its partials: finalize now, once
-            LAUNCH(launch_rowstat_finalize(fold->partials, fold->slots, fold->rows, fold->row_len, 1e-5f, fold->stats, c.s));
-            fold->final_ok = true;
+    const bool emit = rs && !fold_s;
+    p.rowstat_out = emit ? rs->partials : nullptr;
+    if (fold_s) {
+        p.ln_s = fold_s;
+        if (rs->pending) {           // the producer left its partials: finalize now, once
+            LAUNCH(launch_rowstat_finalize(rs->partials, rs->slots, rs->rows, rs->row_len, 1e-5f, rs->stats, c.s));
+            rs->pending = false;
         }
-        p.ln_stats = fold->stats;
+        p.ln_stats = rs->stats;
     }
     IgemmPlan plan;
     RUN(run_igemm(c, p, false, epilogue, epilogue == EPI_LINEAR && ldc == N ? cs_buf : nullptr, cs_out, &plan));
-    if (rowstat) {
-        const int slots = N / plan.rowstat_cols;      // one slot per wave tile of the kernel that ran
-        if (rowstat->sink) {       // deferred: the consumer decides (see above)
-            rowstat->sink->partials = rowstat->partials; rowstat->sink->slots = slots; rowstat->sink->row_len = N;
-            rowstat->sink->rows = M; rowstat->sink->final_ok = false;
-        } else {
-            LAUNCH(launch_rowstat_finalize(rowstat->partials, slots, M, N, 1e-5f, rowstat->mean_rstd, c.s));
-        }
+    if (emit) {
+        rs->slots = N / plan.rowstat_cols;      // one slot per wave tile of the kernel that ran
+        rs->row_len = N; rs->rows = M; rs->pending = true;
     }
     return 0;
 }
@@ -878,6 +878,46 @@ int UNet::run_resnet(FwdCtx& c, const ResnetW& r, const half_t* x1, int C1, cons
     return 0;
 }
 
+// The route of one transformer block: which kernel runs each sub-block and which producers of the residual stream `tx` emit
+// LayerNorm row statistics.  Host arithmetic only; run_transformer() sequences launches from it and decides nothing itself.
+struct BlockRoute {
+    bool ff_first;          // interpolation block order: feed-forward -> temporal (base: temporal -> feed-forward)
+    bool fused_head;        // GroupNorm -> proj_in -> norm1 -> q|k|v as one row-resident kernel (rowfuse_pin.hip)
+    enum { TEXT_GEMMS, TEXT_FUSED, TEXT_FUSED_LONG } text;      // attn1.to_out .. attn2.to_out + residual: GEMMs, or one kernel for <= 80 / 81..160 keys
+    bool fused_t, fused_ff; // the temporal / feed-forward sub-block as one row-resident kernel (rowfuse.hip)
+    bool fold_t, fold_ff;   // else: its first GEMM is LayerNorm-folded (false: an explicit LayerNorm in front of it)
+    bool emit_pin, emit_o1, emit_o2, emit_ot, emit_ff2;        // proj_in, attn1 / attn2 / temporal to_out, ff2: row statistics from the epilogue
+};
+// text_bound: the text K / V of this block are cached and bound into its fused-kernel image for this very context
+static BlockRoute block_route(const lavie_unet_config& cfg, const TransformerW& t, const Route& r, int F, int D, int ctx_len, bool text_bound) {
+    const int heads = cfg.heads;
+    const bool fold = r.ln_fold;
+    BlockRoute b;
+    b.ff_first = cfg.ff_before_temporal != 0;
+    b.fused_head = t.pq_img != nullptr && !t.tres.present && !t.attn1_cross && (r.mask & 256) && D % 16 == 0;
+    // The row-resident kernels take their LayerNorm statistics from the rows they hold.  The feed-forward kernel fits both block orders:
+    // in the interpolation order it also writes the finished (mean, rstd) rows that the folded temporal q|k|v projection behind it reads
+    b.fused_ff = t.ff_img != nullptr && (r.mask & 1) && (!b.ff_first || fold);
+    b.fused_t = t.tb_img != nullptr && !b.ff_first && F == 16 && (r.mask & 2);
+    // The fused text kernel emits no row statistics, so the sub-block behind it must be one that needs none
+    const bool long_ctx = cross_block_long_supported(t.C, heads, ctx_len, F * D);
+    const bool fused_x = t.xb_tmpl != nullptr && text_bound && (b.ff_first ? b.fused_ff : b.fused_t) && !t.attn1_cross && (r.mask & 4) &&
+                         (cross_block_supported(t.C, heads, ctx_len, F * D) || long_ctx);
+    b.text = !fused_x ? BlockRoute::TEXT_GEMMS : long_ctx ? BlockRoute::TEXT_FUSED_LONG : BlockRoute::TEXT_FUSED;
+    // A GEMM behind a LayerNorm is folded when its producer can emit the statistics: the fused temporal kernel cannot
+    b.fold_t = fold && !b.fused_t;
+    b.fold_ff = fold && !b.fused_ff && !b.fused_t;
+    // THE emission rule: a producer emits row statistics exactly when the next consumer of the residual stream is a LayerNorm-folded
+    // GEMM.  The consumers, in order: attn1 q(kv), attn2 q, then temporal q|k|v and ff1 in the block's order, then proj_out (no LayerNorm)
+    const bool gemms = b.text == BlockRoute::TEXT_GEMMS;
+    b.emit_pin = !b.fused_head && fold;
+    b.emit_o1 = gemms && fold;
+    b.emit_o2 = gemms && (b.ff_first ? b.fold_ff : b.fold_t);
+    b.emit_ot = !b.fused_t && !b.ff_first && b.fold_ff;
+    b.emit_ff2 = !b.fused_ff && b.ff_first && b.fold_t;
+    return b;
+}
+
 int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const half_t* ctx, int H, int W, bool shared_prefix,
                           GnColStat* x_cs, float* x_csbuf) {
     const int C = t.C, G = cfg_.norm_groups, heads = cfg_.heads, dh = C / heads;
@@ -894,6 +934,8 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
     const size_t ti = &t - transformers_.data();
     // text K/V computed once per context by cache_context(): valid for this very ctx tensor and shape only
     const bool kv_cached = !c.dry && kv_ctx_ != nullptr && kv_ctx_ == ctx && kv_B_ == c.B && kv_len_ == c.ctx_len && ti < kv2_cache_.size();
+    const BlockRoute br = block_route(cfg_, t, c.route, c.F, D, c.ctx_len, kv_cached && xb_bound_ && xb_img_[ti] != nullptr);
+    const bool fold = c.route.ln_fold;
 
     // VSR: ResnetBlock3DCNN (3,1,1) on the block input, before the residual is taken (vsr/models/attention.py:395-400)
     if (t.tres.present) {
@@ -907,56 +949,33 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
     // Tp rows) and `tx` / `att` are copied to the second
     const int NIp = shared_prefix ? NI / 2 : NI, Tp = shared_prefix ? T / 2 : T;
     LAVIE_CHECK(!shared_prefix || (!t.tres.present && !t.attn1_cross && c.B % 2 == 0), "transformer: shared prefix on an unsupported block");
-    // Round 4: GroupNorm -> proj_in -> norm1 -> q|k|v as ONE row-resident kernel (rowfuse_pin.hip; bit 8 of the mask): the norm's
-    // statistics become per-(frame, channel) scale / shift pairs and nothing between x and (tx, qkv) touches memory
-    const bool fused_pq = t.pq_img != nullptr && !t.tres.present && !t.attn1_cross && (fused_mask() & 256) && D % 16 == 0;
-    WS(gn_ab, float, (size_t)NI * C * 2);        // (planned whether or not the switch is on: the plan must not depend on it)
-    if (fused_pq) {
-        LAUNCH(launch_group_norm(x, C, nullptr, 0, NIp, D, G, t.gn.g, t.gn.b, 1e-6f, false, c.gn_ws, nullptr, c.s, x_cs, nullptr, gn_ab));
-        LAUNCH(launch_proj_qkv(x, gn_ab, D, t.pq_img, t.pin.b, t.ln1.g, t.ln1.b, 1e-5f, tx, wide, Tp, C, c.s));
-    } else {
-    // per-frame GroupNorm (eps 1e-6) + 1x1 proj_in (attention.py:369-373)
-    LAUNCH(launch_group_norm(x, C, nullptr, 0, NIp, D, G, t.gn.g, t.gn.b, 1e-6f, false, c.gn_ws, ln, c.s, x_cs));
-    }
+    WS(gn_ab, float, (size_t)NI * C * 2);        // (planned whether or not the fused head runs: the plan must not depend on it)
     // LayerNorm folding: the GEMM that produces the residual stream `tx` also emits per-row (sum, sum^2) partials of
     // its fp16 output, and the projection that consumes LN(tx) runs on raw `tx` with gamma folded into its weights,
     // finishing rstd * (acc - mean * s) + b' in its epilogue — no LayerNorm kernel, no normalised copy in HBM.
-    const bool fold = ln_fold_;
-    // base block order: temporal -> feed-forward (attention.py:548-560); interpolation block: feed-forward -> temporal
-    // (interpolation/models/attention.py:592-604)
-    const bool ff_first = cfg_.ff_before_temporal != 0;
-    // row-resident fused sub-blocks (rowfuse.hip), base block order only: they take their LayerNorm statistics from the rows
-    // they hold, so their producers emit none
-    // (round 4) the feed-forward and text cross-attention kernels do not depend on the block order: in the interpolation order the
-    // feed-forward kernel ALSO writes the (mean, rstd) rows its consumer, the LayerNorm-folded temporal qkv projection, needs
-    const bool fused_ff = t.ff_img != nullptr && (fused_mask() & 1) && (!ff_first || fold);
-    const bool fused_t = t.tb_img != nullptr && !ff_first && c.F == 16 && (fused_mask() & 2);
-    // attn1.to_out -> + residual -> norm2 -> attn2 -> to_out -> + residual in one kernel: needs this context's K / V image, and
-    // (it emits no row statistics) behind it a kernel that takes its LayerNorm statistics from the rows it holds: the fused temporal
-    // kernel in the base order, the fused feed-forward kernel in the interpolation order
-    // 81..160 keys (a text context widened with mapped image tokens): the long variant of the same kernel, under the same conditions
-    const bool xb_long = cross_block_long_supported(C, heads, c.ctx_len, c.F * D);
-    const bool fused_x = t.xb_tmpl != nullptr && kv_cached && xb_bound_ && xb_img_[ti] != nullptr && (ff_first ? fused_ff : fused_t) &&
-                         !t.attn1_cross && (fused_mask() & 4) && (cross_block_supported(C, heads, c.ctx_len, c.F * D) || xb_long);
-    LnFold lf{nullptr, nullptr};
-    RowStat rsd{nullptr, nullptr, &lf};
-    const RowStat* rowstat = nullptr;
+    RowStats rs{nullptr, nullptr};
     if (fold) {
         WS(rsp, float, (size_t)T * (C / 32) * 2);
         WS(rsm, float, (size_t)T * 2);
-        rsd.partials = rsp;
-        rsd.mean_rstd = rsm;
-        lf.stats = rsm;
-        rowstat = &rsd;
+        rs.partials = rsp;
+        rs.stats = rsm;
     }
-    if (!fused_pq) RUN(linear(c, ln, C, t.pin.w, t.pin.b, C, C, nullptr, tx, C, Tp, EPI_LINEAR, nullptr, rowstat));
+    auto emit = [&](bool on) { return on ? &rs : nullptr; };
+    if (br.fused_head) {
+        // Round 4: the norm's statistics become per-(frame, channel) scale / shift pairs and nothing between x and (tx, qkv) touches memory
+        LAUNCH(launch_group_norm(x, C, nullptr, 0, NIp, D, G, t.gn.g, t.gn.b, 1e-6f, false, c.gn_ws, nullptr, c.s, x_cs, nullptr, gn_ab));
+        LAUNCH(launch_proj_qkv(x, gn_ab, D, t.pq_img, t.pin.b, t.ln1.g, t.ln1.b, 1e-5f, tx, wide, Tp, C, c.s));
+    } else {
+        // per-frame GroupNorm (eps 1e-6) + 1x1 proj_in (attention.py:369-373)
+        LAUNCH(launch_group_norm(x, C, nullptr, 0, NIp, D, G, t.gn.g, t.gn.b, 1e-6f, false, c.gn_ws, ln, c.s, x_cs));
+        RUN(linear(c, ln, C, t.pin.w, t.pin.b, C, C, nullptr, tx, C, Tp, EPI_LINEAR, emit(br.emit_pin)));
+    }
     if (!shared_prefix) TRACE("block.proj_in", tx, T, C);
 
     if (t.attn1_cross) {
         // VSR only_cross_attention levels: attn1 attends to the text context (vsr/models/attention.py:558-561)
         if (fold) {
-            lf.s = t.s_q1;
-            RUN(linear(c, tx, C, t.f_q1, t.b_q1, C, C, nullptr, wide, C, T, EPI_LINEAR, &lf));
+            RUN(linear(c, tx, C, t.f_q1, t.b_q1, C, C, nullptr, wide, C, T, EPI_LINEAR, &rs, t.s_q1));
         } else {
             LAUNCH(launch_layernorm(tx, t.ln1.g, t.ln1.b, ln, T, C, 1e-5f, c.s));
             RUN(linear(c, ln, C, t.wq1, nullptr, C, C, nullptr, wide, C, T));
@@ -972,11 +991,10 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
         }
     } else {
         // spatial self-attention (attention.py:513-522)
-        if (fused_pq) {
+        if (br.fused_head) {
             // q | k | v already in `wide`
         } else if (fold) {
-            lf.s = t.s_qkv1;
-            RUN(linear(c, tx, C, t.f_qkv1, t.b_qkv1, 3 * C, C, nullptr, wide, 3 * C, Tp, EPI_LINEAR, &lf));
+            RUN(linear(c, tx, C, t.f_qkv1, t.b_qkv1, 3 * C, C, nullptr, wide, 3 * C, Tp, EPI_LINEAR, &rs, t.s_qkv1));
         } else {
             LAUNCH(launch_layernorm(tx, t.ln1.g, t.ln1.b, ln, Tp, C, 1e-5f, c.s));
             RUN(linear(c, ln, C, t.wqkv1, nullptr, 3 * C, C, nullptr, wide, 3 * C, Tp));
@@ -998,52 +1016,46 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
         LAVIE_HIP(hipMemcpyAsync(tx + (size_t)Tp * C, tx, (size_t)Tp * C * sizeof(half_t), hipMemcpyDeviceToDevice, c.s));
         LAVIE_HIP(hipMemcpyAsync(att + (size_t)Tp * C, att, (size_t)Tp * C * sizeof(half_t), hipMemcpyDeviceToDevice, c.s));
     }
-    if (fused_x) {
-        if (!c.dry && xb_long)
-            RUN(launch_cross_block_long(att, tx, tx, T, c.F * D, C, heads, xb_img_[ti], t.o1.b, t.ln2.g, t.ln2.b, t.o2.b, c.ctx_len, scale, 1e-5f,
-                                        c.s));
-        else if (!c.dry)
-            RUN(launch_cross_block(att, tx, tx, T, c.F * D, C, heads, xb_img_[ti], t.o1.b, t.ln2.g, t.ln2.b, t.o2.b, c.ctx_len, scale, 1e-5f, c.s));
-    } else {
-    RUN(linear(c, att, C, t.o1.w, t.o1.b, C, C, tx, tx, C, T, EPI_LINEAR, nullptr, rowstat));
-    TRACE("block.attn1.to_out", tx, T, C);
+    // attn1.to_out -> + residual -> norm2 -> attn2 -> to_out -> + residual: one kernel on this context's K / V image ...
+    if (br.text == BlockRoute::TEXT_FUSED_LONG) {
+        LAUNCH(launch_cross_block_long(att, tx, tx, T, c.F * D, C, heads, xb_img_[ti], t.o1.b, t.ln2.g, t.ln2.b, t.o2.b, c.ctx_len, scale, 1e-5f, c.s));
+    } else if (br.text == BlockRoute::TEXT_FUSED) {
+        LAUNCH(launch_cross_block(att, tx, tx, T, c.F * D, C, heads, xb_img_[ti], t.o1.b, t.ln2.g, t.ln2.b, t.o2.b, c.ctx_len, scale, 1e-5f, c.s));
+    } else {       // ... or GEMMs
+        RUN(linear(c, att, C, t.o1.w, t.o1.b, C, C, tx, tx, C, T, EPI_LINEAR, emit(br.emit_o1)));
+        TRACE("block.attn1.to_out", tx, T, C);
 
-    // text cross-attention (attention.py:524-534); K/V once per video instead of once per frame (364)
-    if (fold) {
-        lf.s = t.s_q2;
-        RUN(linear(c, tx, C, t.f_q2, t.b_q2, C, C, nullptr, wide, C, T, EPI_LINEAR, &lf));
-    } else {
-        LAUNCH(launch_layernorm(tx, t.ln2.g, t.ln2.b, ln, T, C, 1e-5f, c.s));
-        RUN(linear(c, ln, C, t.wq2, nullptr, C, C, nullptr, wide, C, T));
-    }
-    const half_t* kvc2 = kv2;
-    if (kv_cached) kvc2 = kv2_cache_[ti];
-    else RUN(linear(c, ctx, X, t.wkv2, nullptr, 2 * C, X, nullptr, kv2, 2 * C, c.B * c.ctx_len));
-    if (!c.dry) {
-        AttnParams a;
-        a.q = wide; a.ldq = C; a.k = kvc2; a.ldk = 2 * C; a.v = kvc2 + C; a.ldv = 2 * C;
-        a.o = att; a.ldo = C; a.NBq = NI; a.Lq = D; a.Lk = c.ctx_len; a.heads = heads; a.dh = dh; a.kv_batch_div = c.F; a.scale = scale;
-        RUN(launch_attention(a, c.s));
-    }
-    TRACE("block.attn2", att, T, C);
-    RUN(linear(c, att, C, t.o2.w, t.o2.b, C, C, tx, tx, C, T, EPI_LINEAR, nullptr, (ff_first ? fused_ff : fused_t) ? nullptr : rowstat));
+        // text cross-attention (attention.py:524-534); K/V once per video instead of once per frame (364)
+        if (fold) {
+            RUN(linear(c, tx, C, t.f_q2, t.b_q2, C, C, nullptr, wide, C, T, EPI_LINEAR, &rs, t.s_q2));
+        } else {
+            LAUNCH(launch_layernorm(tx, t.ln2.g, t.ln2.b, ln, T, C, 1e-5f, c.s));
+            RUN(linear(c, ln, C, t.wq2, nullptr, C, C, nullptr, wide, C, T));
+        }
+        const half_t* kvc2 = kv2;
+        if (kv_cached) kvc2 = kv2_cache_[ti];
+        else RUN(linear(c, ctx, X, t.wkv2, nullptr, 2 * C, X, nullptr, kv2, 2 * C, c.B * c.ctx_len));
+        if (!c.dry) {
+            AttnParams a;
+            a.q = wide; a.ldq = C; a.k = kvc2; a.ldk = 2 * C; a.v = kvc2 + C; a.ldv = 2 * C;
+            a.o = att; a.ldo = C; a.NBq = NI; a.Lq = D; a.Lk = c.ctx_len; a.heads = heads; a.dh = dh; a.kv_batch_div = c.F; a.scale = scale;
+            RUN(launch_attention(a, c.s));
+        }
+        TRACE("block.attn2", att, T, C);
+        RUN(linear(c, att, C, t.o2.w, t.o2.b, C, C, tx, tx, C, T, EPI_LINEAR, emit(br.emit_o2)));
     }
     TRACE("block.after text", tx, T, C);
 
-    // base block order: temporal -> feed-forward (attention.py:548-560); interpolation block: feed-forward -> temporal
-    // (interpolation/models/attention.py:592-604)
     auto temporal = [&]() -> int {
         // temporal self-attention over frames, tokens stay in (b f) d order (attention.py:548-555)
-        if (fused_t) {         // norm_temp -> q|k|v -> rotary / bias / softmax / PV -> to_out -> + residual in ONE kernel, in place
-            if (!c.dry)
-                RUN(launch_temporal_block(tx, tx, c.B, c.F, D, C, heads, t.tb_img, t.lnt.g, t.lnt.b, t.ot.b, cur_tables_->relbias[ti],
-                                          cur_tables_->rot_cos, cur_tables_->rot_sin, cfg_.rotary_dim, scale, 1e-5f, c.s));
+        if (br.fused_t) {      // norm_temp -> q|k|v -> rotary / bias / softmax / PV -> to_out -> + residual in ONE kernel, in place
+            LAUNCH(launch_temporal_block(tx, tx, c.B, c.F, D, C, heads, t.tb_img, t.lnt.g, t.lnt.b, t.ot.b, cur_tables_->relbias[ti],
+                                         cur_tables_->rot_cos, cur_tables_->rot_sin, cfg_.rotary_dim, scale, 1e-5f, c.s));
             return 0;
         }
-        if (fold) {
-            lf.s = t.s_qkvt;
-            RUN(linear(c, tx, C, t.f_qkvt, t.b_qkvt, 3 * C, C, nullptr, wide, 3 * C, T, EPI_LINEAR, &lf));
-            TRACE("temporal.row statistics", lf.stats, T, 2);
+        if (br.fold_t) {
+            RUN(linear(c, tx, C, t.f_qkvt, t.b_qkvt, 3 * C, C, nullptr, wide, 3 * C, T, EPI_LINEAR, &rs, t.s_qkvt));
+            TRACE("temporal.row statistics", rs.stats, T, 2);
         } else {
             LAUNCH(launch_layernorm(tx, t.lnt.g, t.lnt.b, ln, T, C, 1e-5f, c.s));
             RUN(linear(c, ln, C, t.wqkvt, nullptr, 3 * C, C, nullptr, wide, 3 * C, T));
@@ -1057,33 +1069,31 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
         }
         TRACE("temporal.qkv", wide, T, 3 * C);
         TRACE("temporal.attention", att, T, C);
-        // its output feeds norm3 only in the base order; in the interpolation order proj_out follows (no LayerNorm).
-        // The fused feed-forward kernel takes its LayerNorm statistics from the rows it holds: no partials needed.
-        RUN(linear(c, att, C, t.ot.w, t.ot.b, C, C, tx, tx, C, T, EPI_LINEAR, nullptr, (ff_first || fused_ff) ? nullptr : rowstat));
+        RUN(linear(c, att, C, t.ot.w, t.ot.b, C, C, tx, tx, C, T, EPI_LINEAR, emit(br.emit_ot)));
         return 0;
     };
     auto feed_forward = [&]() -> int {
         // GEGLU feed-forward (attention.py:558)
-        if (fused_ff) {        // norm3 -> ff1 -> GEGLU -> ff2 -> + residual in ONE kernel, in place on the residual stream
+        if (br.fused_ff) {     // norm3 -> ff1 -> GEGLU -> ff2 -> + residual in ONE kernel, in place on the residual stream
             // interpolation order: norm_temp consumes this output; the kernel writes its (mean, rstd) rows where ff2's epilogue +
-            // rowstat_finalize would have put them
-            LAUNCH(launch_geglu_mlp(tx, tx, T, C, t.ff_img, t.ff_b1img, t.ln3.g, t.ln3.b, t.ff2.b, 1e-5f, c.s, ff_first ? lf.stats : nullptr));
-            if (ff_first) { lf.partials = nullptr; lf.final_ok = true; }       // finished rows, written by the kernel itself
+            // rowstat_finalize would have put them: finished rows, nothing pending
+            LAUNCH(launch_geglu_mlp(tx, tx, T, C, t.ff_img, t.ff_b1img, t.ln3.g, t.ln3.b, t.ff2.b, 1e-5f, c.s, br.ff_first ? rs.stats : nullptr));
+            if (br.ff_first) rs.pending = false;
             return 0;
         }
-        if (fold && !fused_t) {       // (the fused temporal kernel emits no row statistics: explicit LayerNorm behind it)
-            lf.s = t.s_ff1;
-            RUN(linear(c, tx, C, t.f_ff1, t.b_ff1, 8 * C, C, nullptr, wide, 4 * C, T, EPI_GEGLU, &lf));
+        if (br.fold_ff) {
+            RUN(linear(c, tx, C, t.f_ff1, t.b_ff1, 8 * C, C, nullptr, wide, 4 * C, T, EPI_GEGLU, &rs, t.s_ff1));
         } else {
             LAUNCH(launch_layernorm(tx, t.ln3.g, t.ln3.b, ln, T, C, 1e-5f, c.s));
             RUN(linear(c, ln, C, t.ff1.w, t.ff1.b, 8 * C, C, nullptr, wide, 4 * C, T, EPI_GEGLU));
         }
-        // interpolation order: norm_temp consumes this GEMM's output, so it emits the row statistics (K = 4C: the
-        // planner may pick another kernel than for the K = C producers, hence its own slot count)
-        RUN(linear(c, wide, 4 * C, t.ff2.w, t.ff2.b, C, 4 * C, tx, tx, C, T, EPI_LINEAR, nullptr, ff_first ? rowstat : nullptr));
+        // (K = 4C: the planner may pick another kernel than for the K = C producers, hence a slot count per producer)
+        RUN(linear(c, wide, 4 * C, t.ff2.w, t.ff2.b, C, 4 * C, tx, tx, C, T, EPI_LINEAR, emit(br.emit_ff2)));
         return 0;
     };
-    if (ff_first) {
+    // base block order: temporal -> feed-forward (attention.py:548-560); interpolation block: feed-forward -> temporal
+    // (interpolation/models/attention.py:592-604)
+    if (br.ff_first) {
         RUN(feed_forward());
         TRACE("block.feed-forward", tx, T, C);
         RUN(temporal());
@@ -1108,7 +1118,7 @@ int UNet::run_conv(FwdCtx& c, const half_t* x, int C, const SamplerW& w, half_t*
     if (cs_out) *cs_out = GnColStat();
     const half_t* src[1] = {x};
     const int srcC[1] = {C};
-    if (ups && stride == 1 && w.wpar && (fused_mask() & 16)) {
+    if (ups && stride == 1 && w.wpar && (c.route.mask & 16)) {
         // Upsample3D (resnet.py:44-79): the 3x3 conv of the nearest-x2 image as four 2x2 convs on the source image, one per
         // output parity, on the halo-patch kernel (igemm_patch.hip MODE 3): 4 C instead of 9 C multiply-adds per output element
         IgemmParams p;
@@ -1163,9 +1173,10 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
     // prep_H_/prep_W_ hold the CURRENT call's size while run() executes (set by forward()/prepare())
     auto rows = [&](int l) { return (size_t)NI * Hs[l] * Ws[l]; };
 
-    struct Skip { half_t* p; int C; GnColStat cs; };     // a skip tensor travels with the statistics its producer left
-    GnColStat x_cs;                                      // ... and so does the running activation x
-    std::vector<Skip> skips;
+    // An activation travels with the GroupNorm statistics its producer left (and the buffer they are in): the running one and the skips
+    struct Act { half_t* p; int C; GnColStat cs; float* csbuf; };
+    Act x{};
+    std::vector<Act> skips;
     size_t ri = 0, ti = 0, mi = 0;
     const bool tmod = cfg.vsr_temporal_modules != 0;
 
@@ -1176,9 +1187,9 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
     const bool shared_ok = c.B % 2 == 0 && cfg.attn_levels[0] && cfg.layers_per_block >= 1 && !tmod && !cfg.vsr_blocks &&
                            cfg.num_class_embeds == 0 && !cfg.sparse_causal_attn1 && !transformers_[0].attn1_cross && !transformers_[0].tres.present;
     // a caller that left the switch on for a batch or model it cannot apply to gets an error, not a silently different amount of work
-    LAVIE_CHECK(!cfg_shared_input_ || shared_ok || c.dry, "forward: set_cfg_shared_input(1) needs an even batch (B=%d) and the base UNet "
+    LAVIE_CHECK(!c.route.shared || shared_ok || c.dry, "forward: set_cfg_shared_input(1) needs an even batch (B=%d) and the base UNet "
                 "(attention in the first down block, no VSR / interpolation variants)", c.B);
-    const bool shared = cfg_shared_input_ && shared_ok;
+    const bool shared = c.route.shared && shared_ok;
     if (shared && !c.dry && debug_check_shared()) {
         // LAVIE_DEBUG_CHECK_SHARED=1: verify the caller's promise (sample[b] == sample[b + B/2], equal timesteps) before trusting it
         const size_t half_bytes = (size_t)(c.B / 2) * cfg.in_channels * c.F * prep_H_ * prep_W_ * sizeof(half_t);
@@ -1199,101 +1210,80 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
             LAVIE_HIP(hipMemcpyAsync(p + rows_full / 2 * ch_count, p, rows_full / 2 * ch_count * sizeof(half_t), hipMemcpyDeviceToDevice, c.s));
         return 0;
     };
+    // The steps of the walk below: each takes a new tensor and its statistics buffer from the workspace, runs on x, and advances x
+    auto resnet = [&](FwdCtx& cc, int l, const Act* skip) -> int {
+        const ResnetW& r = resnets_[ri++];
+        WS(y, half_t, rows(l) * r.cout);
+        WS(ycs, float, colstat_floats(rows(l), r.cout));
+        Act ny{y, r.cout, GnColStat(), ycs};
+        RUN(run_resnet(cc, r, x.p, x.C, skip ? skip->p : nullptr, skip ? skip->C : 0, tproj + r.temb_off, tproj_.N, y, Hs[l], Ws[l], &x.cs,
+                       skip ? &skip->cs : nullptr, ycs, &ny.cs));
+        x = ny;
+        return 0;
+    };
+    auto transformer = [&](int l, bool shared_prefix) {      // in place on x
+        return run_transformer(c, transformers_[ti++], x.p, ctx, Hs[l], Ws[l], shared_prefix, &x.cs, x.csbuf);
+    };
+    auto resample = [&](const SamplerW& w, int l, int l_out) -> int {      // down: stride 2; up: nearest x2 in front of the conv
+        WS(y, half_t, rows(l_out) * x.C);
+        WS(ycs, float, colstat_floats(rows(l_out), x.C));
+        Act ny{y, x.C, GnColStat(), ycs};
+        RUN(run_conv(c, x.p, x.C, w, y, Hs[l], Ws[l], l_out > l ? 2 : 1, l_out < l ? 1 : 0, ycs, &ny.cs));
+        x = ny;
+        return 0;
+    };
+    auto temporal_module = [&](int l) -> int {      // VSR; into a NEW buffer: x itself may stay alive as a skip
+        WS(yt, half_t, rows(l) * x.C);
+        WS(ytcs, float, colstat_floats(rows(l), x.C));
+        Act ny{yt, x.C, GnColStat(), ytcs};
+        RUN(run_temporal_module(c, tmods_[mi++], x.p, yt, tproj, tproj_.N, Hs[l], Ws[l], &x.cs, ytcs, &ny.cs));
+        x = ny;
+        return 0;
+    };
 
     WS(x0, half_t, rows(0) * C0);
     LAUNCH(launch_conv_in(sample, conv_in_w_, conv_in_b_, x0, ch.B, cfg.in_channels, c.F, Hs[0], Ws[0], C0, c.s));
     RUN(dup_half(x0, rows(0), C0));
-    half_t* x = x0;
-    int C = C0;
-    skips.push_back({x, C, x_cs});                      // conv_in leaves no statistics: its two consumers run the statistics pass
+    x = Act{x0, C0, GnColStat(), nullptr};           // conv_in leaves no statistics: its two consumers run the statistics pass
+    skips.push_back(x);
 
     for (int l = 0; l < L; ++l) {
         for (int j = 0; j < cfg.layers_per_block; ++j) {
-            const ResnetW& r = resnets_[ri++];
-            WS(y, half_t, rows(l) * r.cout);
-            WS(ycs, float, colstat_floats(rows(l), r.cout));
-            GnColStat y_cs;
+            // the shared prefix: the first resnet runs on the first half of the batch and its output is copied to the second; x.cs then
+            // describes the first half, which is all its one consumer, the half-batch GroupNorm of the first transformer block, reads
             const bool first = shared && l == 0 && j == 0;
-            RUN(run_resnet(first ? ch : c, r, x, C, nullptr, 0, tproj + r.temb_off, tproj_.N, y, Hs[l], Ws[l], &x_cs, nullptr, ycs, &y_cs));
-            if (first) RUN(dup_half(y, rows(l), r.cout));     // (y_cs describes the first half: all its one consumer, the half-batch GroupNorm below, reads)
-            x = y; C = r.cout; x_cs = y_cs;
-            if (cfg.attn_levels[l]) RUN(run_transformer(c, transformers_[ti++], x, ctx, Hs[l], Ws[l], first, &x_cs, ycs));
-            else if (first) x_cs = GnColStat();
-            skips.push_back({x, C, x_cs});
+            RUN(resnet(first ? ch : c, l, nullptr));
+            if (first) RUN(dup_half(x.p, rows(l), x.C));
+            if (cfg.attn_levels[l]) RUN(transformer(l, first));
+            else if (first) x.cs = GnColStat();
+            skips.push_back(x);
         }
         if (l + 1 < L) {
-            WS(y, half_t, rows(l + 1) * C);
-            WS(ycs, float, colstat_floats(rows(l + 1), C));
-            GnColStat y_cs;
-            RUN(run_conv(c, x, C, downs_[l], y, Hs[l], Ws[l], 2, 0, ycs, &y_cs));
-            x = y; x_cs = y_cs;
-            skips.push_back({x, C, x_cs});
+            RUN(resample(downs_[l], l, l + 1));
+            skips.push_back(x);
         }
-        if (tmod) {       // after the downsampler, into a NEW buffer: x itself stays alive as a skip (vsr/models/unet.py:523-533)
-            const int ll = l + 1 < L ? l + 1 : l;
-            WS(yt, half_t, rows(ll) * C);
-            WS(ytcs, float, colstat_floats(rows(ll), C));
-            GnColStat yt_cs;
-            RUN(run_temporal_module(c, tmods_[mi++], x, yt, tproj, tproj_.N, Hs[ll], Ws[ll], &x_cs, ytcs, &yt_cs));
-            x = yt; x_cs = yt_cs;
-        }
+        if (tmod) RUN(temporal_module(l + 1 < L ? l + 1 : l));      // after the downsampler (vsr/models/unet.py:523-533)
     }
-    {
-        const int l = L - 1;
-        const ResnetW& r0 = resnets_[ri++];
-        WS(y0, half_t, rows(l) * r0.cout);
-        WS(y0cs, float, colstat_floats(rows(l), r0.cout));
-        GnColStat y_cs;
-        RUN(run_resnet(c, r0, x, C, nullptr, 0, tproj + r0.temb_off, tproj_.N, y0, Hs[l], Ws[l], &x_cs, nullptr, y0cs, &y_cs));
-        x = y0; C = r0.cout; x_cs = y_cs;
-        RUN(run_transformer(c, transformers_[ti++], x, ctx, Hs[l], Ws[l], false, &x_cs, y0cs));
-        const ResnetW& r1 = resnets_[ri++];
-        WS(y1, half_t, rows(l) * r1.cout);
-        WS(y1cs, float, colstat_floats(rows(l), r1.cout));
-        RUN(run_resnet(c, r1, x, C, nullptr, 0, tproj + r1.temb_off, tproj_.N, y1, Hs[l], Ws[l], &x_cs, nullptr, y1cs, &y_cs));
-        x = y1; C = r1.cout; x_cs = y_cs;
-        if (tmod) {
-            WS(yt, half_t, rows(l) * C);
-            WS(ytcs, float, colstat_floats(rows(l), C));
-            GnColStat yt_cs;
-            RUN(run_temporal_module(c, tmods_[mi++], x, yt, tproj, tproj_.N, Hs[l], Ws[l], &x_cs, ytcs, &yt_cs));
-            x = yt; x_cs = yt_cs;
-        }
-    }
+    RUN(resnet(c, L - 1, nullptr));
+    RUN(transformer(L - 1, false));
+    RUN(resnet(c, L - 1, nullptr));
+    if (tmod) RUN(temporal_module(L - 1));
     for (int i = 0; i < L; ++i) {
         const int l = L - 1 - i;
         for (int j = 0; j < cfg.layers_per_block + 1; ++j) {
-            const Skip sk = skips.back();
+            const Act sk = skips.back();
             skips.pop_back();
-            const ResnetW& r = resnets_[ri++];
-            WS(y, half_t, rows(l) * r.cout);
-            WS(ycs, float, colstat_floats(rows(l), r.cout));
-            GnColStat y_cs;
-            RUN(run_resnet(c, r, x, C, sk.p, sk.C, tproj + r.temb_off, tproj_.N, y, Hs[l], Ws[l], &x_cs, &sk.cs, ycs, &y_cs));
-            x = y; C = r.cout; x_cs = y_cs;
-            if (cfg.attn_levels[l]) RUN(run_transformer(c, transformers_[ti++], x, ctx, Hs[l], Ws[l], false, &x_cs, ycs));
+            RUN(resnet(c, l, &sk));
+            if (cfg.attn_levels[l]) RUN(transformer(l, false));
         }
-        if (i + 1 < L) {
-            WS(y, half_t, rows(l - 1) * C);
-            WS(ycs, float, colstat_floats(rows(l - 1), C));
-            GnColStat y_cs;
-            RUN(run_conv(c, x, C, ups_[i], y, Hs[l], Ws[l], 1, 1, ycs, &y_cs));
-            x = y; x_cs = y_cs;
-        }
-        if (tmod) {       // after the upsampler (vsr/models/unet.py:575-590)
-            const int ll = i + 1 < L ? l - 1 : l;
-            WS(yt, half_t, rows(ll) * C);
-            WS(ytcs, float, colstat_floats(rows(ll), C));
-            GnColStat yt_cs;
-            RUN(run_temporal_module(c, tmods_[mi++], x, yt, tproj, tproj_.N, Hs[ll], Ws[ll], &x_cs, ytcs, &yt_cs));
-            x = yt; x_cs = yt_cs;
-        }
+        if (i + 1 < L) RUN(resample(ups_[i], l, l - 1));
+        if (tmod) RUN(temporal_module(i + 1 < L ? l - 1 : l));      // after the upsampler (vsr/models/unet.py:575-590)
     }
     // conv_norm_out + SiLU + conv_out (unet.py:504-506), back to the caller's NCFHW layout
     {
         WS(nrm, half_t, rows(0) * C0);
         const int P = c.F * Hs[0] * Ws[0];
-        LAUNCH(launch_group_norm(x, C0, nullptr, 0, c.B, P, G, norm_out_.g, norm_out_.b, cfg.norm_eps, true, c.gn_ws, nrm, c.s, &x_cs));
+        LAUNCH(launch_group_norm(x.p, C0, nullptr, 0, c.B, P, G, norm_out_.g, norm_out_.b, cfg.norm_eps, true, c.gn_ws, nrm, c.s, &x.cs));
         LAUNCH(launch_conv_out(nrm, conv_out_w_, conv_out_b_, out, c.B, C0, c.F, Hs[0], Ws[0], cfg.out_channels, c.s));
     }
     return 0;
@@ -1314,27 +1304,21 @@ int UNet::prepare(int B, int F, int H, int W, int ctx_len) {
     // The forward may run under other switches than the ones current now (the guided loop turns the shared CFG prefix on AFTER
     // prepare(); lavie_debug_fused_mask and the text cache change which GEMMs run, and a half-batch launch may plan another
     // split-K slab): the plan is the maximum over every combination of them, so none of those switches can outgrow the workspace.
+    // Each combination is a Route value handed to a dry run: no switch is touched.
     size_t peak = 0;
-    const bool shared_was = cfg_shared_input_;
-    const int mask_was = fused_mask();
-    int rc = 0;
+    const int mask = fused_mask();
     // masks: the current one; without the row-resident kernels (bits 0 - 2, 8: their GEMMs and row-statistics buffers appear); and both
     // again with every workspace-consuming option on (bit 4: the parity form's slabs, 5: statistics buffers)
-    const int masks[4] = {mask_was, mask_was & ~0x107, mask_was | 0x30, (mask_was | 0x30) & ~0x107};
-    for (int variant = 0; variant < 8 && rc == 0; ++variant) {
+    const int masks[4] = {mask, mask & ~0x107, mask | 0x30, (mask | 0x30) & ~0x107};
+    for (int variant = 0; variant < 8; ++variant) {
         if ((variant & 1) && B % 2 != 0) continue;
-        cfg_shared_input_ = (variant & 1) != 0;
-        set_fused_mask(masks[variant >> 1]);
         DeviceArena plan;
         plan.init_virtual();
-        FwdCtx c{nullptr, &plan, true, B, F, ctx_len, nullptr};
+        FwdCtx c{nullptr, &plan, true, Route{masks[variant >> 1], (variant & 1) != 0, ln_fold_}, B, F, ctx_len, nullptr};
         prep_H_ = H; prep_W_ = W;
-        rc = run(c, nullptr, nullptr, nullptr, nullptr);
+        RUN(run(c, nullptr, nullptr, nullptr, nullptr));
         if (plan.peak() > peak) peak = plan.peak();
     }
-    cfg_shared_input_ = shared_was;
-    set_fused_mask(mask_was);
-    RUN(rc);
     const size_t need = peak + (1 << 20);
     if (need > ws_.total_bytes()) {
         drop_graph();                               // the captured addresses die with the old workspace
@@ -1397,7 +1381,7 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* ct
     LAVIE_CHECK(ws_.total_bytes() > 0, "forward: call lavie_unet_prepare first");
     RUN(ensure_tables(F, stream));
     ws_.release(0);
-    FwdCtx c{stream, &ws_, false, B, F, ctx_len, nullptr};
+    FwdCtx c{stream, &ws_, false, Route{fused_mask(), cfg_shared_input_, ln_fold_}, B, F, ctx_len, nullptr};
     c.labels = class_labels_host;
     prep_H_ = H; prep_W_ = W;
     return run(c, sample, timesteps, ctx, out);
@@ -1448,7 +1432,7 @@ int UNet::cache_context(const half_t* ctx, int B, int ctx_len, hipStream_t strea
         xb_img_bytes_ = xb_bytes;
     }
     ws_.release(0);
-    FwdCtx c{stream, &ws_, false, B, 1, ctx_len, nullptr};
+    FwdCtx c{stream, &ws_, false, Route{fused_mask(), cfg_shared_input_, ln_fold_}, B, 1, ctx_len, nullptr};
     for (size_t i = 0; i < transformers_.size(); ++i) {
         const TransformerW& t = transformers_[i];
         RUN(linear(c, ctx, X, t.wkv2, nullptr, 2 * t.C, X, nullptr, kv2_cache_[i], 2 * t.C, (int)rows));
@@ -1630,7 +1614,7 @@ int UNet::resnet_forward(const char* prefix, const half_t* x1, int C1, const hal
     DeviceArena local;
     const size_t M = (size_t)B * F * H * W;
     RUN(local.init_fixed((M * (r->cin + 2 * r->cout)) * sizeof(half_t) + (size_t)B * r->cout * 4 + colstat_floats(M, r->cout) * sizeof(float) + (4 << 20)));
-    FwdCtx c{stream, &local, false, B, F, 0, nullptr};
+    FwdCtx c{stream, &local, false, Route{fused_mask(), cfg_shared_input_, ln_fold_}, B, F, 0, nullptr};
     c.gn_ws = (float*)local.alloc(gn_workspace_floats(B * F, cfg_.norm_groups) * sizeof(float));
     float* tproj = (float*)local.alloc((size_t)B * r->cout * sizeof(float));
     RUN(launch_gemv(temb, tproj_.w + (size_t)r->temb_off * tproj_.K, tproj_.b + r->temb_off, tproj, B, r->cout, tproj_.K, 1, 0, stream));
@@ -1650,7 +1634,7 @@ int UNet::transformer_forward(const char* prefix, half_t* x, const half_t* ctx, 
     DeviceArena local;
     const size_t T = (size_t)B * F * H * W;
     RUN(local.init_fixed(T * t->C * 7 * sizeof(half_t) + (size_t)B * ctx_len * 2 * t->C * sizeof(half_t) + (4 << 20)));
-    FwdCtx c{stream, &local, false, B, F, ctx_len, nullptr};
+    FwdCtx c{stream, &local, false, Route{fused_mask(), cfg_shared_input_, ln_fold_}, B, F, ctx_len, nullptr};
     c.gn_ws = (float*)local.alloc(gn_workspace_floats(B * F, cfg_.norm_groups) * sizeof(float));
     RUN(run_transformer(c, *t, x, ctx, H, W));
     LAVIE_HIP(hipStreamSynchronize(stream));

@@ -103,7 +103,7 @@ struct TemporalModuleW {
     LinW shift;
 };
 
-struct FwdCtx;   // per-call state (engine.cpp)
+struct FwdCtx;   // per-call state (engine.cpp), the call's Route (its switches, as one value) among it
 
 // One registered low-rank adapter target (lavie_unet_lora_*): the projection's rows inside the packed weights and what they are
 // rebuilt from.  Every buffer is the engine's own: the caller's base tensor is copied at registration.
@@ -178,7 +178,9 @@ private:
     int run_resnet(FwdCtx& c, const ResnetW& r, const half_t* x1, int C1, const half_t* x2, int C2, const float* tproj,
                    int ld_tproj, half_t* y, int H, int W, const GnColStat* cs1 = nullptr, const GnColStat* cs2 = nullptr,
                    float* y_csbuf = nullptr, GnColStat* y_cs = nullptr);
-    // x_cs: in = statistics of the block input (for its per-frame GroupNorm), out = statistics of the block output (proj_out's epilogue)
+    // Sequences the launches of one block from its route (engine.cpp block_route(): decided once per call from c.route, the shape and
+    // whether the text K / V are cached and bound).  shared_prefix: the part in front of the text cross-attention runs on the first half
+    // of the batch.  x_cs: in = statistics of the block input (for its per-frame GroupNorm), out = of the block output (proj_out's epilogue)
     int run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const half_t* ctx, int H, int W, bool shared_prefix = false,
                         GnColStat* x_cs = nullptr, float* x_csbuf = nullptr);
     int run_conv(FwdCtx& c, const half_t* x, int C, const SamplerW& w, half_t* y, int Hi, int Wi, int stride, int ups,
@@ -207,6 +209,8 @@ private:
     std::unordered_map<std::string, size_t> index_;
     std::vector<const half_t*> given_;
     bool finalized_ = false;
+    // The two per-handle switches of a call's Route: read where a call enters (forward, cache_context, resnet_forward,
+    // transformer_forward) and by prepare(), nowhere below.
     // the caller promises sample[b] == sample[b + B/2] (classifier-free guidance on duplicated latents): the layers in front of
     // the first text cross-attention are computed for the first half and copied
     bool cfg_shared_input_ = false;

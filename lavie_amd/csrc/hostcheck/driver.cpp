@@ -161,19 +161,20 @@ struct Model {      // a finalized engine with zero weights
     }
 };
 
-// prepare for the shape (the switches in force decide the workspace plan), then one forward: cached context and shared
-// classifier-free-guidance prefix where the variant allows them, labels for a class-embedded model
-static void trace_forward(const lavie_unet_config& cfg, Model& m, int B, int F, int H, int W, bool cached, bool shared) {
-    REQUIRE(lavie_unet_prepare(m.h, B, F, H, W, 77) == 0);
+// prepare for the shape (the switches in force decide the workspace plan; its size is recorded), then one forward: cached context
+// and shared classifier-free-guidance prefix where the variant allows them, labels for a class-embedded model
+static void trace_forward(const lavie_unet_config& cfg, Model& m, int B, int F, int H, int W, bool cached, bool shared, int ctx_len = 77) {
+    REQUIRE(lavie_unet_prepare(m.h, B, F, H, W, ctx_len) == 0);
+    fprintf(g_out, "workspace %lld\n", lavie_unet_workspace_bytes(m.h));
     std::vector<unsigned short> x((size_t)B * cfg.in_channels * F * H * W), y((size_t)B * cfg.out_channels * F * H * W);
-    std::vector<unsigned short> ctx((size_t)B * 77 * cfg.cross_attention_dim);
+    std::vector<unsigned short> ctx((size_t)B * ctx_len * cfg.cross_attention_dim);
     std::vector<float> t(B, 500.f);
     std::vector<int> lab(B, 3);
-    if (cached) REQUIRE(lavie_unet_cache_context(m.h, ctx.data(), B, 77, nullptr) == 0);
+    if (cached) REQUIRE(lavie_unet_cache_context(m.h, ctx.data(), B, ctx_len, nullptr) == 0);
     REQUIRE(lavie_unet_set_cfg_shared_input(m.h, shared ? 1 : 0) == 0);
     const int rc = cfg.num_class_embeds
-                       ? lavie_unet_forward_labels(m.h, x.data(), t.data(), ctx.data(), lab.data(), y.data(), B, F, H, W, 77, nullptr)
-                       : lavie_unet_forward(m.h, x.data(), t.data(), ctx.data(), y.data(), B, F, H, W, 77, nullptr);
+                       ? lavie_unet_forward_labels(m.h, x.data(), t.data(), ctx.data(), lab.data(), y.data(), B, F, H, W, ctx_len, nullptr)
+                       : lavie_unet_forward(m.h, x.data(), t.data(), ctx.data(), y.data(), B, F, H, W, ctx_len, nullptr);
     if (rc != 0) {       // a launch the library refuses ends the forward: recorded, the message goes to stderr
         fprintf(g_out, "!! forward refused\n");
         fprintf(stderr, "hostcheck trace: forward refused: %s\n", lavie_last_error());
@@ -228,7 +229,7 @@ static void run_traces(const char* path) {
     g_out = fopen(path, "w");
     REQUIRE(g_out != nullptr);
     lavie_hostcheck_trace_to(g_out);
-    {   // base model at the production shape: every force_tile mode, forced split-K, fused mask 0x30 besides the default
+    {   // base model at the production shape (cached context, shared prefix): every force_tile mode, forced split-K, fused mask 0x30
         const lavie_unet_config cfg = production_config();
         trace_case("base finalize");
         Model m(cfg);
@@ -249,12 +250,45 @@ static void run_traces(const char* path) {
         trace_forward(cfg, m, 2, 16, 40, 64, true, true);
         REQUIRE(lavie_debug_fused_mask(0x137) == 0);
     }
-    {   // interpolation model: 61 frames, eight input channels
+    {   // the routes of a forward, on a fresh base model (its workspace has not grown under the forced modes above; its finalize is
+        // the one traced above): 8 frames, where the fused temporal block does not apply; no fused kernel at all and the default mask
+        // with each of bits 0, 1, 2, 4, 5, 8 off in turn, each with and without the context cache and the shared prefix; explicit
+        // LayerNorms; the long fused text cross-attention
+        const lavie_unet_config cfg = production_config();
+        lavie_hostcheck_trace_to(nullptr);
+        Model m(cfg);
+        lavie_hostcheck_trace_to(g_out);
+        trace_case("base F=8");
+        trace_forward(cfg, m, 2, 8, 40, 64, true, true);
+        const int masks[] = {0, 0x136, 0x135, 0x133, 0x127, 0x117, 0x037};
+        for (int mask : masks) {
+            REQUIRE(lavie_debug_fused_mask(mask) == 0);
+            for (int v = 0; v < 4; ++v) {
+                trace_case("base fused_mask=0x%03x cached=%d shared=%d", mask, v >> 1, v & 1);
+                trace_forward(cfg, m, 2, 16, 40, 64, (v >> 1) != 0, (v & 1) != 0);
+            }
+        }
+        REQUIRE(lavie_debug_fused_mask(0x137) == 0);
+        REQUIRE(lavie_unet_set_ln_fold(m.h, 0) == 0);
+        trace_case("base ln_fold=0");
+        trace_forward(cfg, m, 2, 16, 40, 64, true, true);
+        REQUIRE(lavie_unet_set_ln_fold(m.h, 1) == 0);
+        trace_case("base 154-token context");
+        trace_forward(cfg, m, 2, 16, 40, 64, true, true, 154);
+    }
+    {   // interpolation model (feed-forward before temporal): 61 frames, eight input channels; without the fused feed-forward, and
+        // without the fused text cross-attention
         lavie_unet_config cfg = production_config();
         cfg.in_channels = 8; cfg.sparse_causal_attn1 = 1; cfg.temporal_plain = 1; cfg.ff_before_temporal = 1;
         trace_case("interpolation");
         Model m(cfg);
         trace_forward(cfg, m, 2, 61, 40, 64, true, false);
+        for (int mask : {0x136, 0x133}) {
+            REQUIRE(lavie_debug_fused_mask(mask) == 0);
+            trace_case("interpolation fused_mask=0x%03x", mask);
+            trace_forward(cfg, m, 2, 61, 40, 64, true, false);
+        }
+        REQUIRE(lavie_debug_fused_mask(0x137) == 0);
     }
     {   // VSR UNet: 256 / 512 / 512 / 1024, noise-level labels, 8 frames at 320 x 512
         lavie_unet_config cfg = production_config();

@@ -1,12 +1,21 @@
 """Generates tests/golden/gemm_plan_trace.txt.gz: the launch trace of the host-only sanitizer build (lavie_amd/csrc/hostcheck,
 `hostcheck trace FILE`), one line per kernel launch (kernel, grid, block, dynamic LDS bytes) under a "== case" line per case of
-driver.cpp's run_traces(): the base model at the production shape (B = 2, F = 16, 40 x 64, cached context, shared prefix) under
-every force_tile mode, forced split-K 2 and 3 and fused mask 0x30; the interpolation model (F = 61) and the VSR UNet (F = 8 at
-320 x 512); the reduced variants of `make asan`; lavie_linear_f16 / lavie_conv3x3_f16 / lavie_upsample_conv3x3_f16 at level shapes.
+driver.cpp's run_traces(), and one "workspace BYTES" line after every lavie_unet_prepare.  The cases:
+* the base model at the production shape (B = 2, F = 16, 40 x 64, cached 77-token context, shared prefix) under every force_tile
+  mode, forced split-K 2 and 3 and fused mask 0x30;
+* the routes of a forward, on a second base model at that shape: F = 8 (no fused temporal block); fused masks 0, 0x136, 0x135,
+  0x133, 0x127, 0x117 and 0x037 (nothing fused; the default with each of bits 0, 1, 2, 4, 5, 8 off in turn), each with
+  {uncached, cached context} x {shared prefix off, on}; lavie_unet_set_ln_fold(0); a cached 154-token context (the long fused
+  text cross-attention);
+* the interpolation model (F = 61; feed-forward before temporal) under the default mask, 0x136 and 0x133, and the VSR UNet (F = 8 at
+  320 x 512);
+* the reduced variants of `make asan`;
+* lavie_linear_f16 / lavie_conv3x3_f16 / lavie_upsample_conv3x3_f16 at level shapes under every force_tile mode.
 
-It pins every kernel choice, grid (split-K factor = grid.y of the GEMM launches) and tile of the implicit-GEMM planner:
-tests/test_gemm_plan_trace.py regenerates the trace and compares.  A change that means to pick another kernel regenerates this
-file, so that the change shows in its diff.  CPU only, needs hipcc.  Run from the repo root:  python tests/golden/make_golden_trace.py"""
+It pins every kernel choice, grid (split-K factor = grid.y of the GEMM launches) and tile of the implicit-GEMM planner, which
+launches a forward sequences under each of its switches, and the workspace prepare() plans for them: tests/test_gemm_plan_trace.py
+regenerates the trace and compares.  A change that means to pick another kernel regenerates this file, so that the change shows in
+its diff.  CPU only, needs hipcc.  Run from the repo root:  python tests/golden/make_golden_trace.py"""
 import gzip
 import os
 import subprocess
