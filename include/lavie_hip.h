@@ -190,7 +190,10 @@ int lavie_layer_norm_f16(const void* x, const float* gamma, const float* beta, v
 
 /* softmax(scale q k^T) v with heads packed along channels; replaces CrossAttention._attention
  * (attention.py:209-239) and reshape_heads_to_batch_dim / reshape_batch_dim_to_heads (112-124).
- * q: [NB*Lq, ldq], k/v: [(NB/kv_batch_div)*Lk, ld], o: [NB*Lq, ldo]; head h at columns h*dh. */
+ * q: [NB*Lq, ldq], k/v: [(NB/kv_batch_div)*Lk, ld], o: [NB*Lq, ldo]; head h at columns h*dh.
+ * Head dims: every multiple of 8 up to 160 (the UNets), and 256 / 512 (attention_wide.hip: the single head of the
+ * AutoencoderKL mid block, e.g. NB 1, Lq = Lk = 163,840, dh 512); any other head dim is refused with a message that
+ * names this set. */
 int lavie_attention_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int NB,
                         int Lq, int Lk, int heads, int dh, int kv_batch_div, float scale, void* stream);
 

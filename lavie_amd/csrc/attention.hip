@@ -814,12 +814,18 @@ static int dispatch_att(const AttnParams& p, bool big, bool lsum, hipStream_t st
 }
 
 int launch_attention(const AttnParams& p, hipStream_t stream) {
-    LAVIE_CHECK(p.dh % 8 == 0 && p.dh >= 8 && p.dh <= 160, "attention: head dim %d unsupported (multiple of 8, <= 160)", p.dh);
+    const bool wide = p.dh == 256 || p.dh == 512;      // attention_wide.hip (the VAE mid block's single head)
+    LAVIE_CHECK((p.dh % 8 == 0 && p.dh >= 8 && p.dh <= 160) || wide,
+                "attention: head dim %d unsupported (multiple of 8 up to 160, or 256, or 512)", p.dh);
     LAVIE_CHECK(p.Lq > 0 && p.Lk > 0 && p.NBq > 0 && p.heads > 0 && p.kv_batch_div > 0, "attention: empty problem");
     LAVIE_CHECK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldo % 4 == 0, "attention: row strides must keep 16-B alignment");
     const double tok_q = (double)p.NBq * p.Lq, width = (double)p.heads * p.dh;
     ProfileScope prof(KC_ATTENTION, stream, 4.0 * tok_q * p.Lk * width,
                       2.0 * (2.0 * tok_q * width + 2.0 * ((double)p.NBq / p.kv_batch_div) * p.Lk * width));
+    if (wide) {
+        LAVIE_CHECK(p.sc_frames == 0, "sparse-causal attention: head dim %d unsupported (multiple of 8, <= 160)", p.dh);
+        return launch_attention_wide(p, stream);
+    }
     const bool big = p.Lq > 64 * 3;     // >= 2 full 128-row blocks: use 32 rows per wave
     if (p.sc_frames > 0) {
         LAVIE_CHECK(p.Lk == 2 * p.Lq && p.kv_batch_div == 1 && p.NBq % p.sc_frames == 0,

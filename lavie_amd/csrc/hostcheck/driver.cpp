@@ -376,6 +376,22 @@ int main(int argc, char** argv) {
                                            154, 0.1f, 1e-5f, nullptr) == 0);
         REQUIRE(lavie_bind_cross_block_f16(tmpl.data(), kv.data(), 1, 81, 320, img.data(), nullptr) != 0);     // the short kernel: <= 80
     }
+    {   // attention head dims: multiples of 8 up to 160, and the wide kernel's 256 / 512; the others are refused before any HIP call
+        std::vector<unsigned short> qkv(64 * 3 * 520), o(64 * 520);
+        const long before = lavie_hostcheck_launches();
+        for (int dh : {40, 160, 256, 512})
+            REQUIRE(lavie_attention_f16(qkv.data(), 3 * dh, qkv.data() + dh, 3 * dh, qkv.data() + 2 * dh, 3 * dh, o.data(), dh, 2, 32, 32, 1,
+                                        dh, 1, 0.05f, nullptr) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 4);
+        for (int dh : {168, 384, 520}) {
+            REQUIRE(lavie_attention_f16(qkv.data(), 3 * dh, qkv.data() + dh, 3 * dh, qkv.data() + 2 * dh, 3 * dh, o.data(), dh, 2, 32, 32, 1,
+                                        dh, 1, 0.05f, nullptr) != 0);
+            REQUIRE(strstr(lavie_last_error(), "512") != nullptr);
+        }
+        REQUIRE(lavie_sparse_causal_attention_f16(qkv.data(), 1536, qkv.data() + 512, 1536, qkv.data() + 1024, 1536, o.data(), 512, 2, 2, 16,
+                                                  1, 512, 0.05f, nullptr) != 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 4);
+    }
     {   // round 4 operators: widths that are not built, null tensors, a frame height that is not a whole number of 16-row tiles
         REQUIRE(lavie_proj_qkv_image_bytes(256) == 0 && lavie_proj_qkv_image_bytes(320) > 0);
         std::vector<unsigned short> x(64 * 320), wq(3 * 320 * 320), wp(320 * 320), tx(64 * 320), qkv(64 * 960);

@@ -49,6 +49,8 @@ struct AttnParams {
     int sc_frames = 0;
 };
 int launch_attention(const AttnParams& p, hipStream_t stream);
+// attention_wide.hip: head dims 256 / 512, called by launch_attention (which checks the arguments and profiles the launch)
+int launch_attention_wide(const AttnParams& p, hipStream_t stream);
 
 // ---- temporal_attention.hip
 struct TemporalParams {

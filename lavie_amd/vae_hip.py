@@ -1,13 +1,20 @@
 """VAE decoder on the engine's operators: the 3x3 convolutions, GroupNorm + SiLU, nearest-x2 upsampling and
 the linear projections of `AutoencoderKL.decode` run through the C-ABI kernels of liblavie_hip.so (`lavie_conv3x3_f16` with the
-fused shortcut / folded upsample, `lavie_group_norm_f16`, `lavie_linear_f16`) on channels-last fp16 rows; only the 4-channel
-input convolutions, the 3-channel output convolution and the mid block's single-head attention (head dim 512 > the kernel's
-160) stay on stock PyTorch ops.
+fused shortcut / folded upsample, `lavie_group_norm_f16`, `lavie_linear_f16`) on channels-last fp16 rows, and the mid block's
+single-head attention product can run through `lavie_attention_f16` (head dims 512 / 256: csrc/attention_wide.hip).  What stays
+on stock PyTorch ops: the 3/4-channel edge convolutions and the encoder's asymmetric stride-2 downsamplers; and, by the
+constructor switch, the attention product.
+
+`HipAutoencoderKL(vae, attention="engine" | "sdpa")`: "engine" takes q | k | v as column slices of the fused projection output
+(one launch, nb = n, lq = lk = h w, heads = 1); "sdpa" is `F.scaled_dot_product_attention`, kept so both can be timed in one
+process (tools/bench_vae_attention.py) and for mid widths the kernel does not serve, where "engine" falls back to it with a
+one-time warning.  The default is the measured faster one at the production shape (profiles/vae_attention.json).
 
 Why: in the full cascade (tools/bench_cascade.py) the stock fp32 decode of 61 frames at 1280x2048 took 321 s of 525 s.
 `HipAutoencoderKL(vae)` wraps a `lavie_amd.autoencoder_kl.AutoencoderKL` (same weights, same `decode(z).sample` /
 `encode` / `config` surface) and can be passed wherever the pipelines take a `vae`.  Parity: against the wrapped stock module
 (tests/test_gpu_cascade.py); the stock module itself is parity-unpinned (see its header)."""
+import warnings
 from types import SimpleNamespace
 
 import torch
@@ -43,22 +50,43 @@ class _Res:
         return ops.conv3x3(a, self.w2, self.c2, n, h, w, residual=x)
 
 
+ENGINE_ATTENTION_WIDTHS = (256, 512)      # head dims lavie_attention_f16 serves beyond its <= 160 range
+DEFAULT_ATTENTION = "engine"              # tools/bench_vae_attention.py at NB 1 x 163,840 x 512: 55.2 ms against 178.6 ms (SDPA)
+
+
 class HipAutoencoderKL(torch.nn.Module):
-    def __init__(self, vae):
+    def __init__(self, vae, attention=None):
         super().__init__()
+        attention = DEFAULT_ATTENTION if attention is None else attention
+        if attention not in ("engine", "sdpa"):
+            raise ValueError(f"HipAutoencoderKL: attention must be 'engine' or 'sdpa', got {attention!r}")
+        self.attention = attention
+        self._warned_widths = set()
         self.vae = vae                                   # the stock module: encode(), the small edge convolutions, config
         self.config = vae.config
         self._packed = None
         self._packed_enc = None
 
     def _mid(self, p, x, n, h, w, c):
-        """mid block: resnet, single-head attention (GroupNorm and the four projections on the engine, the (h w) x (h w)
-        product with head dim C on stock SDPA), resnet."""
+        """mid block: resnet, single-head attention (GroupNorm and the four projections on the engine; the (h w) x (h w)
+        product with head dim C on the engine or on stock SDPA, see the module docstring), resnet."""
         x = p.mid[0](x, n, h, w)
         a = ops.group_norm(x, p.att_g, p.att_b, n, 32, 1e-6, False)
-        qkv = ops.linear(a, p.att_wqkv, bias=p.att_bqkv).reshape(n, h * w, 3, c)
-        o = F.scaled_dot_product_attention(qkv[:, None, :, 0], qkv[:, None, :, 1], qkv[:, None, :, 2])[:, 0]
-        x = ops.linear(o.reshape(n * h * w, c).contiguous(), p.att_wo, bias=p.att_bo, residual=x)
+        qkv = ops.linear(a, p.att_wqkv, bias=p.att_bqkv)
+        engine = self.attention == "engine"
+        if engine and c not in ENGINE_ATTENTION_WIDTHS:
+            if c not in self._warned_widths:
+                self._warned_widths.add(c)
+                warnings.warn(f"HipAutoencoderKL: mid-block width {c} is not served by the engine attention "
+                              f"(head dims {ENGINE_ATTENTION_WIDTHS}); using scaled_dot_product_attention")
+            engine = False
+        if engine:
+            o = ops.attention(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], n, h * w, h * w, 1)
+        else:
+            t = qkv.reshape(n, h * w, 3, c)
+            o = F.scaled_dot_product_attention(t[:, None, :, 0], t[:, None, :, 1], t[:, None, :, 2])[:, 0]
+            o = o.reshape(n * h * w, c).contiguous()
+        x = ops.linear(o, p.att_wo, bias=p.att_bo, residual=x)
         return p.mid[1](x, n, h, w)
 
     @staticmethod
