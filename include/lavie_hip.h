@@ -60,6 +60,35 @@ int lavie_conv3x3_f16(const void* x1, int C1, const void* x2, int C2, const void
                       void* y, int NI, int Hi, int Wi, int Cout, int stride, int ups, const void* zero_page,
                       void* stream);
 
+/* The same convolution with a choice of leading pad (additive in ABI 8): one source, no shortcut, residual or per-video bias,
+ * weights in lavie_pack_conv3x3_f16 order.  pad_lo = 1 is lavie_conv3x3_f16's geometry.  pad_lo = 0 (stride 2 only; with stride 1
+ * the call is refused) is the AutoencoderKL encoder's downsampler, F.pad(x, (0, 1, 0, 1)) followed by a pad-0 stride-2 conv: tap
+ * (ky, kx) of output (y, x) reads input (2y + ky, 2x + kx), zeros outside the image, Ho = (Hi - 2)/2 + 1 (odd Hi / Wi included).
+ * x [NI, Hi, Wi, C] -> y [NI, Ho, Wo, Cout] channels-last rows; C and Cout multiples of 64.  The planner chooses by (M, N, K) as
+ * for pad_lo = 1. */
+int lavie_conv3x3_down_f16(const void* x, int C, const void* Wp, const float* bias, void* y, int NI, int Hi, int Wi, int Cout, int stride,
+                           int pad_lo, const void* zero_page, void* stream);
+
+/* Edge convolutions of a convolutional autoencoder (additive in ABI 8; csrc/conv_edge.hip): 3x3, pad 1, stride 1,
+ * between an NCHW image of at most 8 channels and channels-last fp16 rows.  Both are deterministic (fixed accumulation order, no
+ * atomics).
+ *   lavie_conv_edge_in_f16 : x [N, Cin, H, W] NCHW, 1 <= Cin <= 8, read in place as fp16 (x_dtype 0) or fp32 (x_dtype 1; rounded to
+ *       fp16 on the way in) -> y [N*H*W, Cout] fp16 rows, Cout %% 8 == 0.  bias fp32 [Cout] or NULL.  tap_bias fp32 [9][Cout] or
+ *       NULL: entry [ky*3+kx][co] is added to y[pixel][co] exactly when tap (ky, kx) of that pixel lies inside the image, the form
+ *       the bias of a 1x1 conv in FRONT of this conv takes when that conv is folded into the weights (the pair zero-pads between
+ *       the two).  wp from lavie_pack_conv_edge_in_f16: w [Cout, Cin, 3, 3] fp16 -> 9 * (Cin rounded up to even) * Cout halfs.
+ *   lavie_conv_edge_out_f16: x [N*H*W, Cin] fp16 rows, Cin %% 8 == 0 -> y [N, Cout, H, W] NCHW, 1 <= Cout <= 8, written as fp16
+ *       (y_dtype 0) or fp32 (y_dtype 1) from fp32 accumulators; bias fp32 [Cout] or NULL.  wp from lavie_pack_conv_edge_out_f16:
+ *       w [Cout, Cin, 3, 3] fp16 -> lavie_conv_edge_out_image_halfs(Cin) halfs (0: Cin is not served).
+ * A channel count or dtype flag outside these ranges is refused with a message naming the argument; nothing is launched. */
+int lavie_pack_conv_edge_in_f16(const void* w, void* out, int Cout, int Cin, void* stream);
+int lavie_conv_edge_in_f16(const void* x, int x_dtype, const void* wp, const float* bias, const float* tap_bias, void* y, int N, int Cin,
+                           int H, int W, int Cout, void* stream);
+long long lavie_conv_edge_out_image_halfs(int Cin);
+int lavie_pack_conv_edge_out_f16(const void* w, void* out, int Cout, int Cin, void* stream);
+int lavie_conv_edge_out_f16(const void* x, const void* wp, const float* bias, void* y, int y_dtype, int N, int Cin, int H, int W, int Cout,
+                            void* stream);
+
 /* [Cout, Cin, 3, 3] (PyTorch) -> rows of `ld_out` halfs in the implicit GEMM's K order (64-channel slab, tap,
  * channel): out[co, col0 + ((ci/64)*9 + ky*3+kx)*64 + ci%64].  Cin %% 64 == 0. */
 int lavie_pack_conv3x3_f16(const void* w, void* out, int Cout, int Cin, int ld_out, int col0, void* stream);

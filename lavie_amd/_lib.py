@@ -38,6 +38,14 @@ SIGNATURES = {
     "lavie_conv3x3_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_float_p,
                                    c_float_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                    c_void_p, c_void_p]),
+    "lavie_conv3x3_down_f16": (c_int, [c_void_p, c_int, c_void_p, c_float_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_void_p, c_void_p]),
+    "lavie_pack_conv_edge_in_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "lavie_conv_edge_in_f16": (c_int, [c_void_p, c_int, c_void_p, c_float_p, c_float_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                        c_void_p]),
+    "lavie_conv_edge_out_image_halfs": (c_ll, [c_int]),
+    "lavie_pack_conv_edge_out_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "lavie_conv_edge_out_f16": (c_int, [c_void_p, c_void_p, c_float_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "lavie_pack_conv3x3_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "lavie_temporal_conv_f16": (c_int, [c_void_p, c_int, c_void_p, c_float_p, c_float_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                          c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

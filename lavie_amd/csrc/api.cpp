@@ -156,6 +156,47 @@ int lavie_conv3x3_f16(const void* x1, int C1, const void* x2, int C2, const void
     return op_launch(p, true, EPI_LINEAR, S(stream));
 }
 
+int lavie_conv3x3_down_f16(const void* x, int C, const void* Wp, const float* bias, void* y, int NI, int Hi, int Wi, int Cout, int stride,
+                           int pad_lo, const void* zero_page, void* stream) {
+    LAVIE_CHECK(x && Wp && y && zero_page, "conv3x3_down: null tensor");
+    LAVIE_CHECK(stride == 1 || stride == 2, "conv3x3_down: stride=%d (1 or 2)", stride);
+    LAVIE_CHECK(pad_lo == 0 || pad_lo == 1, "conv3x3_down: pad_lo=%d (0 or 1)", pad_lo);
+    LAVIE_CHECK(pad_lo == 1 || stride == 2, "conv3x3_down: pad_lo=0 needs stride 2 (stride=%d)", stride);
+    LAVIE_CHECK(C > 0 && C % IGEMM_BK == 0 && Cout > 0 && Cout % IGEMM_BK == 0, "conv3x3_down: channel counts must be multiples of %d (C=%d Cout=%d)",
+                IGEMM_BK, C, Cout);
+    LAVIE_CHECK(NI >= 1 && Hi >= 2 - pad_lo && Wi >= 2 - pad_lo && (long long)NI * Hi * Wi * (C > Cout ? C : Cout) < (1ll << 31),
+                "conv3x3_down: bad shape NI=%d %dx%d", NI, Hi, Wi);
+    const half_t* src[1] = {H(x)};
+    const int srcC[1] = {C};
+    IgemmParams p;
+    if (int rc = igemm_setup_conv3x3(&p, src, srcC, 1, nullptr, nullptr, 0, H(Wp), 9 * C, H(y), NI, Hi, Wi, Cout, stride, 0, H(zero_page), pad_lo))
+        return rc;
+    p.bias = bias;
+    return op_launch(p, true, EPI_LINEAR, S(stream));
+}
+
+int lavie_pack_conv_edge_in_f16(const void* w, void* out, int Cout, int Cin, void* stream) {
+    LAVIE_CHECK(w && out, "pack_conv_edge_in: null tensor");
+    return launch_pack_conv_edge_in(H(w), H(out), Cout, Cin, S(stream));
+}
+int lavie_conv_edge_in_f16(const void* x, int x_dtype, const void* wp, const float* bias, const float* tap_bias, void* y, int N, int Cin,
+                           int H_, int W_, int Cout, void* stream) {
+    LAVIE_CHECK(x && wp && y, "conv_edge_in: null tensor");
+    LAVIE_CHECK(x_dtype == 0 || x_dtype == 1, "conv_edge_in: x_dtype=%d (0 = fp16, 1 = fp32)", x_dtype);
+    return launch_conv_edge_in(x, x_dtype == 1, H(wp), bias, tap_bias, H(y), N, Cin, H_, W_, Cout, S(stream));
+}
+long long lavie_conv_edge_out_image_halfs(int Cin) { return conv_edge_out_image_halfs(Cin); }
+int lavie_pack_conv_edge_out_f16(const void* w, void* out, int Cout, int Cin, void* stream) {
+    LAVIE_CHECK(w && out, "pack_conv_edge_out: null tensor");
+    return launch_pack_conv_edge_out(H(w), H(out), Cout, Cin, S(stream));
+}
+int lavie_conv_edge_out_f16(const void* x, const void* wp, const float* bias, void* y, int y_dtype, int N, int Cin, int H_, int W_, int Cout,
+                            void* stream) {
+    LAVIE_CHECK(x && wp && y, "conv_edge_out: null tensor");
+    LAVIE_CHECK(y_dtype == 0 || y_dtype == 1, "conv_edge_out: y_dtype=%d (0 = fp16, 1 = fp32)", y_dtype);
+    return launch_conv_edge_out(H(x), H(wp), bias, y, y_dtype == 1, N, Cin, H_, W_, Cout, S(stream));
+}
+
 int lavie_pack_conv3x3_parity_f16(const void* w, void* out, int Cout, int Cin, void* stream) {
     LAVIE_CHECK(w && out && Cout > 0 && Cin > 0, "pack_conv3x3_parity: bad arguments");
     return launch_pack_conv3x3_parity(H(w), H(out), Cout, Cin, S(stream));

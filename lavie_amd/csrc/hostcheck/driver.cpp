@@ -437,6 +437,45 @@ int main(int argc, char** argv) {
         REQUIRE(lavie_multistep_step(eps, x, hist, min2, 32, 1.f, -inf, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
         REQUIRE(lavie_hostcheck_launches() == before + 3);
     }
+    {   // the VAE's edge convolutions and the asymmetric-pad stride-2 conv: accepted calls reach the (stubbed) launch with exactly
+        // sized buffers (packing, odd Cin, ragged last tile); every refusal comes before a HIP call and names its argument
+        const int N = 2, Hh = 5, Ww = 7, px = N * Hh * Ww;
+        std::vector<unsigned short> w3(128 * 3 * 9), wp3(9 * 4 * 128), x3(N * 3 * Hh * Ww), rows128(px * 128);
+        std::vector<unsigned short> wo(3 * 128 * 9), wpo((size_t)lavie_conv_edge_out_image_halfs(128)), y16(N * 3 * Hh * Ww);
+        std::vector<float> x3f(N * 3 * Hh * Ww), y32(N * 3 * Hh * Ww), b128(128, 0.f), tb(9 * 128, 0.f), b3(3, 0.f);
+        REQUIRE(lavie_conv_edge_out_image_halfs(128) == 9 * 4 * 256 && lavie_conv_edge_out_image_halfs(12) == 0);
+        const long before = lavie_hostcheck_launches();
+        REQUIRE(lavie_pack_conv_edge_in_f16(w3.data(), wp3.data(), 128, 3, nullptr) == 0);
+        REQUIRE(lavie_conv_edge_in_f16(x3.data(), 0, wp3.data(), b128.data(), nullptr, rows128.data(), N, 3, Hh, Ww, 128, nullptr) == 0);
+        REQUIRE(lavie_conv_edge_in_f16(x3f.data(), 1, wp3.data(), b128.data(), tb.data(), rows128.data(), N, 3, Hh, Ww, 128, nullptr) == 0);
+        REQUIRE(lavie_pack_conv_edge_out_f16(wo.data(), wpo.data(), 3, 128, nullptr) == 0);
+        REQUIRE(lavie_conv_edge_out_f16(rows128.data(), wpo.data(), b3.data(), y16.data(), 0, N, 128, Hh, Ww, 3, nullptr) == 0);
+        REQUIRE(lavie_conv_edge_out_f16(rows128.data(), wpo.data(), b3.data(), y32.data(), 1, N, 128, Hh, Ww, 3, nullptr) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 6);
+        std::vector<unsigned short> wd(128 * 9 * 128), yd(N * 2 * 3 * 128), zero(128);      // 5 x 7 -> 2 x 3 output pixels per image
+        REQUIRE(lavie_conv3x3_down_f16(rows128.data(), 128, wd.data(), b128.data(), yd.data(), N, Hh, Ww, 128, 2, 0, zero.data(), nullptr) == 0);
+        const long accepted = lavie_hostcheck_launches();
+        REQUIRE(accepted > before + 6);
+        REQUIRE(lavie_conv_edge_in_f16(x3.data(), 0, wp3.data(), nullptr, nullptr, rows128.data(), N, 9, Hh, Ww, 128, nullptr) != 0);
+        REQUIRE(strstr(lavie_last_error(), "Cin=9") != nullptr);
+        REQUIRE(lavie_conv_edge_in_f16(x3.data(), 0, wp3.data(), nullptr, nullptr, rows128.data(), N, 3, Hh, Ww, 100, nullptr) != 0);
+        REQUIRE(lavie_conv_edge_in_f16(x3.data(), 2, wp3.data(), nullptr, nullptr, rows128.data(), N, 3, Hh, Ww, 128, nullptr) != 0);
+        REQUIRE(strstr(lavie_last_error(), "x_dtype") != nullptr);
+        REQUIRE(lavie_conv_edge_in_f16(nullptr, 0, wp3.data(), nullptr, nullptr, rows128.data(), N, 3, Hh, Ww, 128, nullptr) != 0);
+        REQUIRE(lavie_pack_conv_edge_in_f16(w3.data(), wp3.data(), 128, 9, nullptr) != 0);
+        REQUIRE(lavie_conv_edge_out_f16(rows128.data(), wpo.data(), nullptr, y16.data(), 0, N, 128, Hh, Ww, 9, nullptr) != 0);
+        REQUIRE(strstr(lavie_last_error(), "Cout=9") != nullptr);
+        REQUIRE(lavie_conv_edge_out_f16(rows128.data(), wpo.data(), nullptr, y16.data(), 0, N, 100, Hh, Ww, 3, nullptr) != 0);
+        REQUIRE(lavie_conv_edge_out_f16(rows128.data(), wpo.data(), nullptr, y16.data(), 2, N, 128, Hh, Ww, 3, nullptr) != 0);
+        REQUIRE(strstr(lavie_last_error(), "y_dtype") != nullptr);
+        REQUIRE(lavie_conv_edge_out_f16(rows128.data(), nullptr, nullptr, y16.data(), 0, N, 128, Hh, Ww, 3, nullptr) != 0);
+        REQUIRE(lavie_pack_conv_edge_out_f16(wo.data(), wpo.data(), 9, 128, nullptr) != 0);
+        REQUIRE(lavie_conv3x3_down_f16(rows128.data(), 128, wd.data(), nullptr, yd.data(), N, Hh, Ww, 128, 1, 0, zero.data(), nullptr) != 0);
+        REQUIRE(strstr(lavie_last_error(), "pad_lo") != nullptr);
+        REQUIRE(lavie_conv3x3_down_f16(rows128.data(), 100, wd.data(), nullptr, yd.data(), N, Hh, Ww, 128, 2, 0, zero.data(), nullptr) != 0);
+        REQUIRE(lavie_conv3x3_down_f16(rows128.data(), 128, wd.data(), nullptr, yd.data(), N, Hh, Ww, 128, 2, 0, nullptr, nullptr) != 0);
+        REQUIRE(lavie_hostcheck_launches() == accepted);
+    }
     REQUIRE(lavie_upsample_conv3x3_supported(320, 32, 20, 32) >= 0);
     int buckets[16 * 16];
     REQUIRE(lavie_relpos_buckets(16, 32, 32, buckets) == 0);

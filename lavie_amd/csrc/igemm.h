@@ -52,6 +52,10 @@ struct IgemmParams {
     // Gather geometry (GATHER = true): output pixel grid [NI, Ho, Wo], source grid [NI, Hi, Wi],
     // virtual input grid (Hi << ups, Wi << ups) for the folded nearest-x2 upsample.
     int Ho, Wo, Hi, Wi, stride, ups;
+    // Leading pad of the 3x3 stencil: tap (ky, kx) of output (y, x) reads input (y stride + ky - pad_lo, x stride + kx - pad_lo).
+    // 1 = the symmetric pad-1 conv (every conv of the UNet); 0 with stride 2 = the VAE encoder's downsampler, which pads one
+    // zero row / column at the far side only (F.pad(x, (0, 1, 0, 1)) + a pad-0 conv).  Read by the 9-tap gather alone.
+    int pad_lo;
     // Temporal mode (tframes > 0; GATHER = true; 128-row and ping-pong kernels): rows are tokens (b, f, pixel) with tpix pixels per
     // frame, and tap t of a segment with ntaps = T reads row m + (t - T/2) * tpix, or zeros when frame f + t - T/2 falls
     // outside [0, tframes) — nn.Conv3d with kernel (T, 1, 1), padding (T/2, 0, 0) (vsr/models/resnet.py:258-259, 274).
@@ -107,12 +111,13 @@ int launch_igemm_ppx(const IgemmParams& p, int epilogue, hipStream_t stream);
 bool igemm_patch_eligible(const IgemmParams& p);
 int igemm_patch_bn(int N);                        // 160 / 128 / 0: column-tile width of the halo-patch kernel for N channels
 int launch_igemm_patch(const IgemmParams& p, hipStream_t stream);
-// Geometry of a 3x3 conv (pad 1, stride 1 / 2, `ups` = folded nearest-x2 upsample) y [NI, Ho, Wo, Cout] over the channel-concatenated
+// Geometry of a 3x3 conv (pad 1, stride 1 / 2, `ups` = folded nearest-x2 upsample; pad_lo = 0: stride 2 only, the far-side pad of
+// IgemmParams::pad_lo, Ho = (Hi - 2) / 2 + 1) y [NI, Ho, Wo, Cout] over the channel-concatenated
 // sources src[0..nsrc) (9-tap segments) and the centre-tap shortcut sources sc[0..nsc) (stride 1 only), sources of 0 channels
 // skipped; W rows of ldw halfs.  Fills p (zeroed first; rows_per_batch = 1, the caller adds bias, bias2, R).  0 or an error.
 int igemm_setup_conv3x3(IgemmParams* p, const half_t* const* src, const int* srcC, int nsrc, const half_t* const* sc, const int* scC,
                         int nsc, const half_t* W, int ldw, half_t* y, int NI, int Hi, int Wi, int Cout, int stride, int ups,
-                        const half_t* zero);
+                        const half_t* zero, int pad_lo = 1);
 // parity form of conv3x3(nearest_x2(x)) (igemm_patch.hip MODE 3): fills p (geometry only; the caller sets p->slab), false = not this
 // geometry
 bool igemm_setup_parity_upsample(IgemmParams* p, const half_t* x, int C, const half_t* wpar, const float* bias, half_t* y, int NI, int Hi,

@@ -126,7 +126,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
             const int n = m / hw;
             const int rem = m - n * hw;
             const int y = rem / p.Wo, x = rem - y * p.Wo;
-            const int iy = y * p.stride + tap / 3 - 1, ix = x * p.stride + tap % 3 - 1;
+            const int iy = y * p.stride + tap / 3 - p.pad_lo, ix = x * p.stride + tap % 3 - p.pad_lo;
             const bool ok = (unsigned)iy < (unsigned)Hv && (unsigned)ix < (unsigned)Wv;
             tab[idx] = ok ? (n * p.Hi + (iy >> p.ups)) * p.Wi + (ix >> p.ups) : -1;
         }

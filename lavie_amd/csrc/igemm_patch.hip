@@ -466,12 +466,14 @@ bool igemm_setup_parity_upsample(IgemmParams* p, const half_t* x, int C, const h
 
 int igemm_setup_conv3x3(IgemmParams* p, const half_t* const* src, const int* srcC, int nsrc, const half_t* const* sc, const int* scC,
                         int nsc, const half_t* W, int ldw, half_t* y, int NI, int Hi, int Wi, int Cout, int stride, int ups,
-                        const half_t* zero) {
+                        const half_t* zero, int pad_lo) {
     memset(p, 0, sizeof(*p));
+    LAVIE_CHECK(pad_lo == 1 || (pad_lo == 0 && stride == 2 && ups == 0), "conv3x3: pad_lo=%d needs stride 2, no upsample (stride=%d ups=%d)", pad_lo, stride, ups);
+    LAVIE_CHECK(pad_lo == 1 || (Hi >= 2 && Wi >= 2), "conv3x3: pad_lo=0 needs an image of at least 2x2 (%dx%d)", Hi, Wi);
     p->W = W; p->ldw = ldw; p->C = y; p->ldc = Cout; p->rows_per_batch = 1; p->ldr = Cout;
-    p->Hi = Hi; p->Wi = Wi; p->stride = stride; p->ups = ups;
-    p->Ho = ups ? Hi * 2 : (Hi - 1) / stride + 1;
-    p->Wo = ups ? Wi * 2 : (Wi - 1) / stride + 1;
+    p->Hi = Hi; p->Wi = Wi; p->stride = stride; p->ups = ups; p->pad_lo = pad_lo;
+    p->Ho = ups ? Hi * 2 : (Hi - 2 + pad_lo) / stride + 1;
+    p->Wo = ups ? Wi * 2 : (Wi - 2 + pad_lo) / stride + 1;
     p->M = NI * p->Ho * p->Wo;
     p->N = Cout;
     p->zero = zero;

@@ -77,6 +77,18 @@ int launch_conv_in(const half_t* x, const half_t* wp, const float* bias, half_t*
 // x [(B F) H W, Cin] channels-last -> y [B, Cout, F, H, W] NCFHW fp16, 3x3 pad 1; w packed [Cout][3*3][Cin]
 int launch_conv_out(const half_t* x, const half_t* wp, const float* bias, half_t* y, int B, int Cin, int F, int H, int W,
                     int Cout, hipStream_t stream);
+// ---- conv_edge.hip : the narrow-channel ends of the VAE (operator level only; the engine keeps launch_conv_in / launch_conv_out)
+// x [N, Cin <= 8, H, W] (NCHW, fp16 or fp32) -> y [N H W, Cout] channels-last fp16, 3x3 pad 1; tap_bias [9][Cout] or nullptr: added
+// for the taps inside the image; wp from launch_pack_conv_edge_in (9 * roundup(Cin, 2) * Cout halfs)
+int launch_conv_edge_in(const void* x, bool x_f32, const half_t* wp, const float* bias, const float* tap_bias, half_t* y, int N, int Cin,
+                        int H, int W, int Cout, hipStream_t stream);
+int launch_pack_conv_edge_in(const half_t* w, half_t* out, int Cout, int Cin, hipStream_t stream);
+// x [N H W, Cin] channels-last fp16 -> y [N, Cout <= 8, H, W] (NCHW, fp16 or fp32), 3x3 pad 1; wp from launch_pack_conv_edge_out
+// (conv_edge_out_image_halfs(Cin) halfs; 0 = Cin not served)
+int launch_conv_edge_out(const half_t* x, const half_t* wp, const float* bias, void* y, bool y_f32, int N, int Cin, int H, int W, int Cout,
+                         hipStream_t stream);
+int launch_pack_conv_edge_out(const half_t* w, half_t* out, int Cout, int Cin, hipStream_t stream);
+long long conv_edge_out_image_halfs(int Cin);
 // Classifier-free guidance + DDPM ancestral step (pipeline_videogen.py:679-683):
 //   eps = eps_u + s (eps_c - eps_u); x0 = kx x - ke eps; x' = c0 x0 + ct x + sigma noise
 //   writes x' (fp32, in place allowed) and the duplicated fp16 model input [2, n] for the next step.

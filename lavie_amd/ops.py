@@ -239,11 +239,24 @@ def _zero_page(device):
 
 
 def conv3x3(x1, wp, bias, ni, hi, wi, x2=None, sc1=None, sc2=None, bias2=None, rows_per_batch=0, residual=None,
-            stride=1, ups=0):
-    """Per-frame 3x3 conv, pad 1, on channels-last rows [(ni hi wi), C]; see lavie_conv3x3_f16."""
+            stride=1, ups=0, pad=None):
+    """Per-frame 3x3 conv, pad 1, on channels-last rows [(ni hi wi), C]; see lavie_conv3x3_f16.
+    pad = (lo, hi) chooses the padding instead: (1, 1) is the default geometry, (0, 1) with stride 2 the far-side pad of the
+    AutoencoderKL downsampler (lavie_conv3x3_down_f16: one source, no shortcut / residual / bias2)."""
     _chk16(x1, x2, sc1, sc2, wp, residual)
     _chk32(bias, bias2)
     cout = wp.shape[0]
+    if pad is not None:
+        if tuple(pad) not in ((0, 1), (1, 1)):
+            raise ValueError(f"conv3x3: pad must be (0, 1) or (1, 1), got {pad!r}")
+        if any(t is not None for t in (x2, sc1, sc2, bias2, residual)) or ups:
+            raise ValueError("conv3x3: pad= takes one source and no shortcut, residual, bias2 or upsample")
+        lo = pad[0]
+        ho, wo = (hi - 2 + lo) // stride + 1, (wi - 2 + lo) // stride + 1
+        y = torch.empty(ni * max(ho, 0) * max(wo, 0), cout, dtype=torch.float16, device=x1.device)
+        _lib.check(_lib.load().lavie_conv3x3_down_f16(_p(x1), x1.shape[1], _p(wp), _p(bias), _p(y), ni, hi, wi, cout, stride, lo,
+                                                      _p(_zero_page(x1.device)), _stream()), "lavie_conv3x3_down_f16")
+        return y
     ho = hi * 2 if ups else (hi - 1) // stride + 1
     wo = wi * 2 if ups else (wi - 1) // stride + 1
     y = torch.empty(ni * ho * wo, cout, dtype=torch.float16, device=x1.device)
@@ -252,6 +265,68 @@ def conv3x3(x1, wp, bias, ni, hi, wi, x2=None, sc1=None, sc2=None, bias2=None, r
     _lib.check(lib.lavie_conv3x3_f16(_p(x1), c(x1), _p(x2), c(x2), _p(sc1), c(sc1), _p(sc2), c(sc2), _p(wp), _p(bias),
                                      _p(bias2), cout, rows_per_batch, _p(residual), _p(y), ni, hi, wi, cout, stride, ups,
                                      _p(_zero_page(x1.device)), _stream()), "lavie_conv3x3_f16")
+    return y
+
+
+def _edge_dtype(t, what):
+    if not (t.is_cuda and t.is_contiguous() and t.dtype in (torch.float16, torch.float32)):
+        raise ValueError(f"{what} must be a contiguous fp16 or fp32 device tensor")
+    return 1 if t.dtype == torch.float32 else 0
+
+
+def pack_conv_edge_in(weight):
+    """[Cout, Cin <= 8, 3, 3] (fp16, device) -> the weight image of conv_edge_in (channel pairs interleaved, an odd Cin zero-padded)."""
+    _chk16(weight)
+    cout, cin = weight.shape[:2]
+    out = torch.empty(9 * (cin + (cin & 1)) * cout, dtype=torch.float16, device=weight.device)
+    _lib.check(_lib.load().lavie_pack_conv_edge_in_f16(_p(weight), _p(out), cout, cin, _stream()), "lavie_pack_conv_edge_in_f16")
+    return out
+
+
+def conv_edge_in(x, wp, bias, cout, tap_bias=None):
+    """3x3 conv, pad 1, from an NCHW image x [n, cin <= 8, h, w] (fp16 or fp32, read in place) to channels-last fp16 rows
+    [(n h w), cout]; tap_bias fp32 [9, cout] is added for the taps inside the image; see lavie_conv_edge_in_f16."""
+    _chk16(wp)
+    _chk32(bias, tap_bias)
+    flag = _edge_dtype(x, "conv_edge_in: x")
+    n, cin, h, w = x.shape
+    if 1 <= cin <= 8 and cout % 8 == 0 and wp.numel() != 9 * (cin + (cin & 1)) * cout:      # (other counts: the library refuses them)
+        raise ValueError(f"conv_edge_in: wp has {wp.numel()} halfs, not the pack_conv_edge_in image of Cin={cin} Cout={cout}")
+    if (bias is not None and bias.numel() != cout) or (tap_bias is not None and tuple(tap_bias.shape) != (9, cout)):
+        raise ValueError(f"conv_edge_in: bias must be [{cout}] and tap_bias [9, {cout}]")
+    y = torch.empty(n * h * w, cout, dtype=torch.float16, device=x.device)
+    _lib.check(_lib.load().lavie_conv_edge_in_f16(_p(x), flag, _p(wp), _p(bias), _p(tap_bias), _p(y), n, cin, h, w, cout, _stream()),
+               "lavie_conv_edge_in_f16")
+    return y
+
+
+def pack_conv_edge_out(weight):
+    """[Cout <= 8, Cin, 3, 3] (fp16, device) -> the weight image of conv_edge_out (MFMA fragment order, rows padded to 8)."""
+    _chk16(weight)
+    cout, cin = weight.shape[:2]
+    lib = _lib.load()
+    out = torch.empty(max(lib.lavie_conv_edge_out_image_halfs(cin), 8), dtype=torch.float16, device=weight.device)
+    _lib.check(lib.lavie_pack_conv_edge_out_f16(_p(weight), _p(out), cout, cin, _stream()), "lavie_pack_conv_edge_out_f16")
+    return out
+
+
+def conv_edge_out(x, wp, bias, n, h, w, cout, out_dtype=torch.float16):
+    """3x3 conv, pad 1, from channels-last fp16 rows x [(n h w), cin] to an NCHW image [n, cout <= 8, h, w] written in `out_dtype`
+    (fp16 or fp32) from fp32 accumulators; see lavie_conv_edge_out_f16."""
+    _chk16(x, wp)
+    _chk32(bias)
+    if out_dtype not in (torch.float16, torch.float32):
+        raise ValueError("conv_edge_out: out_dtype must be torch.float16 or torch.float32")
+    if x.dim() != 2 or x.shape[0] != n * h * w:
+        raise ValueError(f"conv_edge_out: x must be [{n * h * w}, cin] rows, got {tuple(x.shape)}")
+    halfs = _lib.load().lavie_conv_edge_out_image_halfs(x.shape[1])
+    if halfs and wp.numel() != halfs:                                                        # (halfs == 0: the library refuses Cin)
+        raise ValueError(f"conv_edge_out: wp has {wp.numel()} halfs, not the pack_conv_edge_out image of Cin={x.shape[1]} ({halfs})")
+    if bias is not None and bias.numel() != cout:
+        raise ValueError(f"conv_edge_out: bias must be [{cout}]")
+    y = torch.empty(n, cout, h, w, dtype=out_dtype, device=x.device)
+    _lib.check(_lib.load().lavie_conv_edge_out_f16(_p(x), _p(wp), _p(bias), _p(y), 1 if out_dtype == torch.float32 else 0, n,
+                                                   x.shape[1], h, w, cout, _stream()), "lavie_conv_edge_out_f16")
     return y
 
 
