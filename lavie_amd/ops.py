@@ -36,6 +36,17 @@ def _chk32(*ts):
             raise ValueError("expected contiguous fp32 device tensors")
 
 
+def _out(out, shape, dtype, device, what):
+    """The caller's output tensor after the checks every `out=` gets (device, dtype, contiguity, exact shape), or a new one."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not (out.is_cuda and out.device == device and out.dtype == dtype and out.is_contiguous()):
+        raise ValueError(f"{what} must be a contiguous {dtype} tensor on {device}")
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{what} must have shape {tuple(shape)}, got {tuple(out.shape)}")
+    return out
+
+
 def to_rows(x: torch.Tensor) -> torch.Tensor:
     """[b, c, f, h, w] -> channels-last rows [(b f h w), c] (a copy)."""
     b, c, f, h, w = x.shape
@@ -54,22 +65,21 @@ def linear(a, weight, bias=None, residual=None, bias2=None, rows_per_batch=0, ge
     M, K = a.shape
     N = weight.shape[0]
     n_out = N // 2 if geglu else N
-    if out is None:
-        out = torch.empty(M, n_out, dtype=torch.float16, device=a.device)
+    out = _out(out, (M, n_out), torch.float16, a.device, "linear: out")
     lib = _lib.load()
     _lib.check(lib.lavie_linear_f16(_p(a), K, _p(weight), _p(bias), _p(bias2), N, rows_per_batch, _p(residual), n_out,
                                     _p(out), n_out, M, N, K, int(geglu), _stream()), "lavie_linear_f16")
     return out
 
 
-def linear_lnfold(a, weight_folded, bias, ln_s, ln_stats):
+def linear_lnfold(a, weight_folded, bias, ln_s, ln_stats, out=None):
     """rstd_m (a @ weight_folded^T - mean_m ln_s) + bias: a projection behind a LayerNorm, the norm folded into the GEMM epilogue
     (weight_folded = W * gamma, ln_s = its row sums, bias = W beta (+ b), ln_stats [M, 2] = (mean, rstd) of the rows of `a`)."""
     _chk16(a, weight_folded)
     _chk32(bias, ln_s, ln_stats)
     M, K = a.shape
     N = weight_folded.shape[0]
-    out = torch.empty(M, N, dtype=torch.float16, device=a.device)
+    out = _out(out, (M, N), torch.float16, a.device, "linear_lnfold: out")
     _lib.check(_lib.load().lavie_linear_lnfold_f16(_p(a), _p(weight_folded), _p(bias), _p(ln_s), _p(ln_stats), _p(out), M, N, K,
                                                    _stream()), "lavie_linear_lnfold_f16")
     return out
@@ -105,8 +115,7 @@ def geglu_mlp(x, img, b1img, gamma, beta, b2, eps=1e-5, out=None):
     _chk16(x, img, out)
     _chk32(b1img, gamma, beta, b2)
     M, C = x.shape
-    if out is None:
-        out = torch.empty_like(x)
+    out = _out(out, x.shape, torch.float16, x.device, "geglu_mlp: out")
     _lib.check(_lib.load().lavie_geglu_mlp_f16(_p(x), _p(out), M, C, _p(img), _p(b1img), _p(gamma), _p(beta), _p(b2), eps,
                                                _stream()), "lavie_geglu_mlp_f16")
     return out
@@ -131,8 +140,7 @@ def temporal_block(x, img, gamma, beta, bo, relbias, rot_cos, rot_sin, B, F, D, 
     _chk16(x, img, out)
     _chk32(gamma, beta, bo, relbias, rot_cos, rot_sin)
     C = x.shape[1]
-    if out is None:
-        out = torch.empty_like(x)
+    out = _out(out, x.shape, torch.float16, x.device, "temporal_block: out")
     _lib.check(_lib.load().lavie_temporal_block_f16(_p(x), _p(out), B, F, D, C, heads, _p(img), _p(gamma), _p(beta), _p(bo),
                                                     _p(relbias), _p(rot_cos), _p(rot_sin), rot_dim, scale, eps, _stream()),
                "lavie_temporal_block_f16")
@@ -169,8 +177,7 @@ def cross_block(att, x, img, bo1, gamma, beta, bo2, rows_per_batch, ctx_len, hea
     _chk16(att, x, img, out)
     _chk32(bo1, gamma, beta, bo2)
     M, C = x.shape
-    if out is None:
-        out = torch.empty_like(x)
+    out = _out(out, x.shape, torch.float16, x.device, "cross_block: out")
     _lib.check(_lib.load().lavie_cross_block_f16(_p(att), _p(x), _p(out), M, rows_per_batch, C, heads, _p(img), _p(bo1), _p(gamma),
                                                  _p(beta), _p(bo2), ctx_len, scale, eps, _stream()), "lavie_cross_block_f16")
     return out
@@ -206,8 +213,7 @@ def cross_block_long(att, x, img, bo1, gamma, beta, bo2, rows_per_batch, ctx_len
     _chk16(att, x, img, out)
     _chk32(bo1, gamma, beta, bo2)
     M, C = x.shape
-    if out is None:
-        out = torch.empty_like(x)
+    out = _out(out, x.shape, torch.float16, x.device, "cross_block_long: out")
     _lib.check(_lib.load().lavie_cross_block_long_f16(_p(att), _p(x), _p(out), M, rows_per_batch, C, heads, _p(img), _p(bo1),
                                                       _p(gamma), _p(beta), _p(bo2), ctx_len, scale, eps, _stream()),
                "lavie_cross_block_long_f16")
@@ -239,7 +245,7 @@ def _zero_page(device):
 
 
 def conv3x3(x1, wp, bias, ni, hi, wi, x2=None, sc1=None, sc2=None, bias2=None, rows_per_batch=0, residual=None,
-            stride=1, ups=0, pad=None):
+            stride=1, ups=0, pad=None, out=None):
     """Per-frame 3x3 conv, pad 1, on channels-last rows [(ni hi wi), C]; see lavie_conv3x3_f16.
     pad = (lo, hi) chooses the padding instead: (1, 1) is the default geometry, (0, 1) with stride 2 the far-side pad of the
     AutoencoderKL downsampler (lavie_conv3x3_down_f16: one source, no shortcut / residual / bias2)."""
@@ -253,13 +259,13 @@ def conv3x3(x1, wp, bias, ni, hi, wi, x2=None, sc1=None, sc2=None, bias2=None, r
             raise ValueError("conv3x3: pad= takes one source and no shortcut, residual, bias2 or upsample")
         lo = pad[0]
         ho, wo = (hi - 2 + lo) // stride + 1, (wi - 2 + lo) // stride + 1
-        y = torch.empty(ni * max(ho, 0) * max(wo, 0), cout, dtype=torch.float16, device=x1.device)
+        y = _out(out, (ni * max(ho, 0) * max(wo, 0), cout), torch.float16, x1.device, "conv3x3: out")
         _lib.check(_lib.load().lavie_conv3x3_down_f16(_p(x1), x1.shape[1], _p(wp), _p(bias), _p(y), ni, hi, wi, cout, stride, lo,
                                                       _p(_zero_page(x1.device)), _stream()), "lavie_conv3x3_down_f16")
         return y
     ho = hi * 2 if ups else (hi - 1) // stride + 1
     wo = wi * 2 if ups else (wi - 1) // stride + 1
-    y = torch.empty(ni * ho * wo, cout, dtype=torch.float16, device=x1.device)
+    y = _out(out, (ni * ho * wo, cout), torch.float16, x1.device, "conv3x3: out")
     c = lambda t: 0 if t is None else t.shape[1]
     lib = _lib.load()
     _lib.check(lib.lavie_conv3x3_f16(_p(x1), c(x1), _p(x2), c(x2), _p(sc1), c(sc1), _p(sc2), c(sc2), _p(wp), _p(bias),
@@ -283,7 +289,7 @@ def pack_conv_edge_in(weight):
     return out
 
 
-def conv_edge_in(x, wp, bias, cout, tap_bias=None):
+def conv_edge_in(x, wp, bias, cout, tap_bias=None, out=None):
     """3x3 conv, pad 1, from an NCHW image x [n, cin <= 8, h, w] (fp16 or fp32, read in place) to channels-last fp16 rows
     [(n h w), cout]; tap_bias fp32 [9, cout] is added for the taps inside the image; see lavie_conv_edge_in_f16."""
     _chk16(wp)
@@ -294,7 +300,7 @@ def conv_edge_in(x, wp, bias, cout, tap_bias=None):
         raise ValueError(f"conv_edge_in: wp has {wp.numel()} halfs, not the pack_conv_edge_in image of Cin={cin} Cout={cout}")
     if (bias is not None and bias.numel() != cout) or (tap_bias is not None and tuple(tap_bias.shape) != (9, cout)):
         raise ValueError(f"conv_edge_in: bias must be [{cout}] and tap_bias [9, {cout}]")
-    y = torch.empty(n * h * w, cout, dtype=torch.float16, device=x.device)
+    y = _out(out, (n * h * w, cout), torch.float16, x.device, "conv_edge_in: out")
     _lib.check(_lib.load().lavie_conv_edge_in_f16(_p(x), flag, _p(wp), _p(bias), _p(tap_bias), _p(y), n, cin, h, w, cout, _stream()),
                "lavie_conv_edge_in_f16")
     return y
@@ -310,7 +316,7 @@ def pack_conv_edge_out(weight):
     return out
 
 
-def conv_edge_out(x, wp, bias, n, h, w, cout, out_dtype=torch.float16):
+def conv_edge_out(x, wp, bias, n, h, w, cout, out_dtype=torch.float16, out=None):
     """3x3 conv, pad 1, from channels-last fp16 rows x [(n h w), cin] to an NCHW image [n, cout <= 8, h, w] written in `out_dtype`
     (fp16 or fp32) from fp32 accumulators; see lavie_conv_edge_out_f16."""
     _chk16(x, wp)
@@ -324,7 +330,7 @@ def conv_edge_out(x, wp, bias, n, h, w, cout, out_dtype=torch.float16):
         raise ValueError(f"conv_edge_out: wp has {wp.numel()} halfs, not the pack_conv_edge_out image of Cin={x.shape[1]} ({halfs})")
     if bias is not None and bias.numel() != cout:
         raise ValueError(f"conv_edge_out: bias must be [{cout}]")
-    y = torch.empty(n, cout, h, w, dtype=out_dtype, device=x.device)
+    y = _out(out, (n, cout, h, w), out_dtype, x.device, "conv_edge_out: out")
     _lib.check(_lib.load().lavie_conv_edge_out_f16(_p(x), _p(wp), _p(bias), _p(y), 1 if out_dtype == torch.float32 else 0, n,
                                                    x.shape[1], h, w, cout, _stream()), "lavie_conv_edge_out_f16")
     return y
@@ -339,13 +345,13 @@ def pack_conv3x3_parity(weight):
     return out
 
 
-def upsample_conv3x3(x, wpar, bias, ni, hi, wi):
+def upsample_conv3x3(x, wpar, bias, ni, hi, wi, out=None):
     """conv3x3(nearest_x2(x)) + bias (Upsample3D, resnet.py:44-79) in parity form: x [ni*hi*wi, C] rows -> [ni*2hi*2wi, C] rows.
     Raises where the kernel's geometry does not hold (use conv3x3(..., ups=1) there)."""
     _chk16(x, wpar)
     _chk32(bias)
     c = x.shape[1]
-    y = torch.empty(ni * 4 * hi * wi, c, dtype=torch.float16, device=x.device)
+    y = _out(out, (ni * 4 * hi * wi, c), torch.float16, x.device, "upsample_conv3x3: out")
     _lib.check(_lib.load().lavie_upsample_conv3x3_f16(_p(x), _p(wpar), _p(bias), _p(y), ni, hi, wi, c, _p(_zero_page(x.device)), _stream()),
                "lavie_upsample_conv3x3_f16")
     return y
@@ -361,13 +367,13 @@ def pack_temporal_conv(weight):
     return out
 
 
-def temporal_conv(x, wp, bias, b, frames, d, taps, bias2=None, residual=None):
+def temporal_conv(x, wp, bias, b, frames, d, taps, bias2=None, residual=None, out=None):
     """Conv3d (taps, 1, 1), padding (taps // 2, 0, 0), over the frame axis of token rows [(b f d), C] (the VSR stage's
     ResnetBlock3DCNN convs); bias2 [b, Cout] = per-video time-embedding projection; see lavie_temporal_conv_f16."""
     _chk16(x, wp, residual)
     _chk32(bias, bias2)
     cout = wp.shape[0]
-    y = torch.empty(b * frames * d, cout, dtype=torch.float16, device=x.device)
+    y = _out(out, (b * frames * d, cout), torch.float16, x.device, "temporal_conv: out")
     _lib.check(_lib.load().lavie_temporal_conv_f16(_p(x), x.shape[1], _p(wp), _p(bias), _p(bias2), cout,
                                                    frames * d if bias2 is not None else 0, _p(residual), _p(y), b, frames, d,
                                                    cout, taps, _p(_zero_page(x.device)), _stream()),
@@ -375,26 +381,26 @@ def temporal_conv(x, wp, bias, b, frames, d, taps, bias2=None, residual=None):
     return y
 
 
-def group_norm(x1, gamma, beta, nb, groups, eps, silu, x2=None):
+def group_norm(x1, gamma, beta, nb, groups, eps, silu, x2=None, out=None):
     """GroupNorm (+SiLU) over rows; `nb` batches share statistics over rows/nb rows each."""
     _chk16(x1, x2)
     _chk32(gamma, beta)
     rows = x1.shape[0]
     c1, c2 = x1.shape[1], 0 if x2 is None else x2.shape[1]
-    y = torch.empty(rows, c1 + c2, dtype=torch.float16, device=x1.device)
+    y = _out(out, (rows, c1 + c2), torch.float16, x1.device, "group_norm: out")
     ws = torch.empty(_lib.load().lavie_group_norm_ws_floats(nb, groups), dtype=torch.float32, device=x1.device)
     _lib.check(_lib.load().lavie_group_norm_f16(_p(x1), c1, _p(x2), c2, nb, rows // nb, groups, _p(gamma), _p(beta),
                                                 float(eps), int(silu), _p(ws), _p(y), _stream()), "lavie_group_norm_f16")
     return y
 
 
-def group_norm_affine(x, gamma, beta, nb, groups, eps):
+def group_norm_affine(x, gamma, beta, nb, groups, eps, out=None):
     """GroupNorm statistics only: the normalisation as per-(batch, channel) pairs (a, b) with norm(x) = a x + b -> [nb, C, 2] fp32
     (lavie_group_norm_affine_f16; consumed by proj_qkv)."""
     _chk16(x)
     _chk32(gamma, beta)
     rows, c = x.shape
-    ab = torch.empty(nb, c, 2, dtype=torch.float32, device=x.device)
+    ab = _out(out, (nb, c, 2), torch.float32, x.device, "group_norm_affine: out")
     ws = torch.empty(_lib.load().lavie_group_norm_ws_floats(nb, groups), dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().lavie_group_norm_affine_f16(_p(x), c, nb, rows // nb, groups, _p(gamma), _p(beta), float(eps), _p(ws),
                                                        _p(ab), _stream()), "lavie_group_norm_affine_f16")
@@ -415,35 +421,35 @@ def pack_proj_qkv(wpin, wqkv):
     return img
 
 
-def proj_qkv(x, gn_ab, rows_per_domain, img, bpin, ln_gamma, ln_beta, eps=1e-5):
+def proj_qkv(x, gn_ab, rows_per_domain, img, bpin, ln_gamma, ln_beta, eps=1e-5, tx=None, qkv=None):
     """tx = proj_in(GroupNorm(x)), qkv = to_qkv(LayerNorm(tx)) in one kernel (attention.py:369-373, 513-516) -> (tx [M, C], qkv [M, 3C])."""
     _chk16(x, img)
     _chk32(gn_ab, bpin, ln_gamma, ln_beta)
     M, C = x.shape
-    tx = torch.empty(M, C, dtype=torch.float16, device=x.device)
-    qkv = torch.empty(M, 3 * C, dtype=torch.float16, device=x.device)
+    tx = _out(tx, (M, C), torch.float16, x.device, "proj_qkv: tx")
+    qkv = _out(qkv, (M, 3 * C), torch.float16, x.device, "proj_qkv: qkv")
     _lib.check(_lib.load().lavie_proj_qkv_f16(_p(x), _p(gn_ab), rows_per_domain, _p(img), _p(bpin), _p(ln_gamma), _p(ln_beta), eps,
                                               _p(tx), _p(qkv), M, C, _stream()), "lavie_proj_qkv_f16")
     return tx, qkv
 
 
-def layer_norm(x, gamma, beta, eps=1e-5):
+def layer_norm(x, gamma, beta, eps=1e-5, out=None):
     _chk16(x)
     _chk32(gamma, beta)
-    y = torch.empty_like(x)
+    y = _out(out, x.shape, torch.float16, x.device, "layer_norm: out")
     _lib.check(_lib.load().lavie_layer_norm_f16(_p(x), _p(gamma), _p(beta), _p(y), x.shape[0], x.shape[1], float(eps),
                                                 _stream()), "lavie_layer_norm_f16")
     return y
 
 
-def attention(q, k, v, nb, lq, lk, heads, kv_batch_div=1, scale=None):
+def attention(q, k, v, nb, lq, lk, heads, kv_batch_div=1, scale=None, out=None):
     """q [nb*lq, *], k/v [(nb/kv_batch_div)*lk, *] may be column slices of wider row-major tensors."""
     for t in (q, k, v):
         if not (t.is_cuda and t.dtype == torch.float16 and t.stride(1) == 1):
             raise ValueError("attention operands must be fp16 device tensors with unit column stride")
     c = q.shape[1]
     dh = c // heads
-    o = torch.empty(nb * lq, c, dtype=torch.float16, device=q.device)
+    o = _out(out, (nb * lq, c), torch.float16, q.device, "attention: out")
     scale = dh ** -0.5 if scale is None else scale
     _lib.check(_lib.load().lavie_attention_f16(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(o), c, nb,
                                                lq, lk, heads, dh, kv_batch_div, float(scale), _stream()),
@@ -451,7 +457,7 @@ def attention(q, k, v, nb, lq, lk, heads, kv_batch_div=1, scale=None):
     return o
 
 
-def sparse_causal_attention(q, k, v, nb, frames, d, heads, scale=None):
+def sparse_causal_attention(q, k, v, nb, frames, d, heads, scale=None, out=None):
     """SparseCausalAttention core (interpolation/models/attention.py:609-665): q/k/v [nb*d, *] per-frame rows (column
     slices of a wider tensor allowed); frame f of a video attends to [first frame || frame max(f-1, 0)] of that video."""
     for t in (q, k, v):
@@ -459,7 +465,7 @@ def sparse_causal_attention(q, k, v, nb, frames, d, heads, scale=None):
             raise ValueError("attention operands must be fp16 device tensors with unit column stride")
     c = q.shape[1]
     dh = c // heads
-    o = torch.empty(nb * d, c, dtype=torch.float16, device=q.device)
+    o = _out(out, (nb * d, c), torch.float16, q.device, "sparse_causal_attention: out")
     scale = dh ** -0.5 if scale is None else scale
     _lib.check(_lib.load().lavie_sparse_causal_attention_f16(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0),
                                                              _p(o), c, nb, frames, d, heads, dh, float(scale), _stream()),
@@ -481,13 +487,13 @@ def rotary_tables(frames: int, rot_dim: int = 32, theta: float = 10000.0, device
     return ang.cos().to(device).contiguous(), ang.sin().to(device).contiguous()
 
 
-def temporal_attention(qkv, b, frames, d, heads, bias, rot_cos, rot_sin, rot_dim=32, scale=None):
+def temporal_attention(qkv, b, frames, d, heads, bias, rot_cos, rot_sin, rot_dim=32, scale=None, out=None):
     """qkv [(b f d), 3C] (q | k | v) in (b, f, pixel) token order -> [(b f d), C]."""
     _chk16(qkv)
     _chk32(bias, *(() if rot_dim == 0 else (rot_cos, rot_sin)))      # rot_dim = 0: no rotary embedding, tables may be None
     c = qkv.shape[1] // 3
     dh = c // heads
-    o = torch.empty(qkv.shape[0], c, dtype=torch.float16, device=qkv.device)
+    o = _out(out, (qkv.shape[0], c), torch.float16, qkv.device, "temporal_attention: out")
     scale = dh ** -0.5 if scale is None else scale
     _lib.check(_lib.load().lavie_temporal_attention_f16(_p(qkv), 3 * c, _p(o), c, b, frames, d, heads, dh, _p(bias),
                                                         _p(rot_cos), _p(rot_sin), rot_dim, float(scale), _stream()),
@@ -592,8 +598,7 @@ def lora_merge(w0: torch.Tensor, a: torch.Tensor, b: torch.Tensor, scale: float 
     r = a.shape[0]
     if a.shape != (r, K) or b.shape != (N, r):
         raise ValueError(f"lora_merge: w0 {tuple(w0.shape)}, a {tuple(a.shape)}, b {tuple(b.shape)} do not fit")
-    if out is None:
-        out = torch.empty_like(w0)
+    out = _out(out, w0.shape, torch.float16, w0.device, "lora_merge: out")
     lib = _lib.load()
     _lib.check(lib.lavie_lora_merge_f16(_p(w0), _p(a), _p(b), _p(out), N, K, r, float(scale), _stream()), "lavie_lora_merge_f16")
     return out

@@ -1,0 +1,956 @@
+"""The operator cases of the per-element checks, shared by tests/test_opcheck_host.py (CPU: the fp32 model of each kernel must
+meet its own bound) and tests/test_gpu_ops_local.py (the kernels).  A case holds its inputs (CPU tensors in the dtypes the
+kernel takes), how to run the operator, a float64 reference with the per-element scale, the constant c of its family, and a
+torch fp32 model of the kernel with fp16 roundings at the counted points.
+
+Shapes are the smallest that cross each kernel's edges; none is a workload shape."""
+import functools
+import math
+import zlib
+
+import torch
+import torch.nn.functional as F
+
+import opcheck as oc
+
+f16, f32t, f64 = torch.float16, torch.float32, torch.float64
+
+
+class Case:
+    def __init__(self, name, inputs, outputs, run, ref, c, model, where, alias=None, regions=None, setup=None):
+        self.name, self.inputs, self.outputs, self.run, self.c, self.model, self.where = name, inputs, outputs, run, c, model, where
+        self.alias = alias or {}
+        self._ref = ref
+        self.regions = regions or {}          # name -> bool mask over output "y": regions asserted on their own as well
+        self.setup = setup                    # optional context manager factory (forced kernels)
+
+    @functools.cached_property
+    def ref(self):
+        """name -> (ref64, scale64)"""
+        return self._ref()
+
+    def check(self, got, label=""):
+        for k, (ref, scale) in self.ref.items():
+            w = self.where[k] if isinstance(self.where, dict) else self.where
+            c = self.c[k] if isinstance(self.c, dict) else self.c
+            oc.assert_elementwise(got[k], ref, scale, c, where=w, label=f"{label}{self.name}:{k}")
+            if k == "y":
+                for rname, mask in self.regions.items():
+                    oc.assert_elementwise(got[k], ref, scale, c, where=w, label=f"{label}{self.name}:{k}:{rname}", mask=mask)
+
+
+def gen(*seed):
+    return torch.Generator().manual_seed(zlib.crc32(repr(seed).encode()))
+
+
+def rnd(g, *shape, s=1.0, dtype=f16):
+    return (torch.randn(*shape, generator=g) * s).to(dtype)
+
+
+def d(t):
+    return None if t is None else t.to(f64)
+
+
+def rows(x):
+    return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1]).contiguous()
+
+
+# ------------------------------------------------------------------ linear family
+LINEAR_SHAPES = [(1, 64, 64), (127, 64, 192), (130, 192, 64), (154, 320, 320), (160, 320, 320), (161, 320, 320),
+                 (320, 256, 320), (480, 640, 320)]
+LINEAR_OPTIONS = ["plain", "bias_residual", "bias2", "residual_in_place"]
+
+
+@functools.lru_cache(maxsize=None)
+def linear_case(M, N, K, opt):
+    g = gen("linear", M, N, K, opt)
+    a, w = rnd(g, M, K), rnd(g, N, K, s=1 / math.sqrt(K))
+    ins = {"a": a, "w": w}
+    rpb = (M + 1) // 2
+    if opt in ("bias_residual", "bias2"):
+        ins["bias"] = rnd(g, N, dtype=f32t)
+    if opt == "bias2":
+        ins["bias2"] = rnd(g, -(-M // rpb), N, dtype=f32t)
+    if opt in ("bias_residual", "residual_in_place"):
+        ins["r"] = rnd(g, M, N)
+    b2rows = torch.arange(M) // rpb
+
+    def run(ops, i, o):
+        ops.linear(i["a"], i["w"], bias=i.get("bias"), residual=i.get("r"), bias2=i.get("bias2"),
+                   rows_per_batch=rpb if "bias2" in i else 0, out=o["y"])
+
+    def terms(cv, absval):
+        p = (lambda t: t.abs()) if absval else (lambda t: t)
+        y = p(cv(a)) @ p(cv(w)).t()
+        if "bias" in ins:
+            y = y + p(cv(ins["bias"]))
+        if "bias2" in ins:
+            y = y + p(cv(ins["bias2"]))[b2rows]
+        if "r" in ins:
+            y = y + p(cv(ins["r"]))
+        return y
+
+    return Case(f"linear[{M}x{N}x{K},{opt}]", ins, {"y": ((M, N), f16)}, run, lambda: {"y": (terms(d, False), terms(d, True))},
+                oc.gemm_c(K + 3), lambda: {"y": terms(lambda t: t.float(), False).half()}, oc.loc_rows(N),
+                alias={"y": "r"} if opt == "residual_in_place" else None)
+
+
+def gelu64(x):
+    return 0.5 * x * (1 + torch.erf(x / math.sqrt(2)))
+
+
+@functools.lru_cache(maxsize=None)
+def geglu_case(M, C):
+    """linear(..., geglu=True): [M, C] -> [M, 4C] = h * gelu(gate).  The output needs h and gate to (K + 8) 2^-23 of their own
+    scales and is stored once in fp16: n = 1 (igemm_epilogue.h:170, the only fp16 conversion of the GEGLU branch)."""
+    g = gen("geglu", M, C)
+    a, w, b = rnd(g, M, C), rnd(g, 8 * C, C, s=1 / math.sqrt(C)), rnd(g, 8 * C, s=0.1)
+    ins = {"a": a, "w": w, "b": b}
+
+    def run(ops, i, o):
+        wp, bp = ops.pack_geglu(i["w"], i["b"])
+        ops.linear(i["a"], wp, bias=bp, geglu=True, out=o["y"])
+
+    def ref():
+        pre = d(a) @ d(w).t() + d(b)
+        sc = d(a).abs() @ d(w).abs().t() + d(b).abs()
+        h, gate = pre.chunk(2, -1)
+        sh, sg = sc.chunk(2, -1)
+        # |d(h gelu(g))| <= |gelu(g)| dh + |h| max|gelu'| dg, max|gelu'| < 1.13
+        return {"y": (h * gelu64(gate), sh * gelu64(gate).abs() + h.abs() * 1.13 * sg)}
+
+    def model():
+        pre = a.float() @ w.float().t() + b.float()
+        h, gate = pre.chunk(2, -1)
+        return {"y": (h * F.gelu(gate)).half()}
+
+    return Case(f"geglu[{M}x{C}]", ins, {"y": ((M, 4 * C), f16)}, run, ref, oc.round_c(1), model, oc.loc_rows(4 * C))
+
+
+@functools.lru_cache(maxsize=None)
+def lnfold_case(M, N, K):
+    g = gen("lnfold", M, N, K)
+    a = (torch.randn(M, K, generator=g) * (0.5 + torch.rand(M, 1, generator=g)) + torch.randn(M, 1, generator=g)).half()
+    gamma, beta = 1 + 0.2 * torch.randn(K, generator=g), 0.1 * torch.randn(K, generator=g)
+    w = torch.randn(N, K, generator=g) / math.sqrt(K)
+    wf = (w * gamma).half()
+    s = wf.float().sum(1)
+    bf = (w @ beta + torch.randn(N, generator=g))
+    af = a.float()
+    stats = torch.stack([af.mean(1), (af.var(1, unbiased=False) + 1e-5).rsqrt()], 1).contiguous()
+    ins = {"a": a, "wf": wf, "bias": bf, "s": s, "stats": stats}
+
+    def run(ops, i, o):
+        ops.linear_lnfold(i["a"], i["wf"], i["bias"], i["s"], i["stats"], out=o["y"])
+
+    def ref():
+        mean, rstd = d(stats[:, :1]), d(stats[:, 1:])
+        acc = d(a) @ d(wf).t()
+        y = rstd * (acc - mean * d(s)) + d(bf)
+        sc = rstd.abs() * (d(a).abs() @ d(wf).abs().t() + (mean * d(s)).abs()) + d(bf).abs()
+        return {"y": (y, sc)}
+
+    def model():
+        acc = af @ wf.float().t()
+        return {"y": (stats[:, 1:] * (acc - stats[:, :1] * s) + bf).half()}
+
+    return Case(f"lnfold[{M}x{N}x{K}]", ins, {"y": ((M, N), f16)}, run, ref, oc.gemm_c(K + 2), model, oc.loc_rows(N))
+
+
+# ------------------------------------------------------------------ 3x3 convolution family
+class forced:
+    """lavie_debug_force_tile / force_splits for the duration of a case, then back to what the fixture set."""
+
+    def __init__(self, tile, splits, restore):
+        self.tile, self.splits, self.restore = tile, splits, restore
+
+    def __enter__(self):
+        from lavie_amd import _lib
+        lib = _lib.load()
+        _lib.check(lib.lavie_debug_force_tile(self.tile), "lavie_debug_force_tile")
+        lib.lavie_debug_force_splits(self.splits)
+
+    def __exit__(self, *exc):
+        from lavie_amd import _lib
+        lib = _lib.load()
+        lib.lavie_debug_force_tile(self.restore[0])
+        lib.lavie_debug_force_splits(self.restore[1])
+
+
+def conv2d_any(x, w, b, stride, ups, pad):
+    if ups:
+        x = x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+    if pad == (0, 1):
+        return F.conv2d(F.pad(x, (0, 1, 0, 1)), w, b, stride=stride)
+    return F.conv2d(x, w, b, stride=stride, padding=1)
+
+
+def border_mask(n, h, w, c):
+    m = torch.ones(n, h, w, c, dtype=torch.bool)
+    if h > 2 and w > 2:
+        m[:, 1:-1, 1:-1] = False
+    return m.reshape(-1)
+
+
+def lines_mask(n, h, w, c, ys, xs):
+    m = torch.zeros(n, h, w, c, dtype=torch.bool)
+    for y in ys:
+        if 0 <= y < h:
+            m[:, y] = True
+    for x in xs:
+        if 0 <= x < w:
+            m[:, :, x] = True
+    return m.reshape(-1)
+
+
+@functools.lru_cache(maxsize=None)
+def conv_case(n, c1, cout, h, w, stride=1, ups=0, pad=None, c2=0, csc=0, extras=False, force=None, splits=0, parity=False):
+    """extras: per-frame bias2 + residual (the halo-patch test's form); csc: fused 1x1 shortcut over two raw sources of csc
+    channels each + bias2 (the ResnetBlock3D form); force: (tile mode, splits) forced around the launch."""
+    g = gen("conv", n, c1, cout, h, w, stride, ups, pad, c2, csc, extras, parity)
+    cin = c1 + c2
+    x1 = rnd(g, n, c1, h, w)
+    x2 = rnd(g, n, c2, h, w) if c2 else None
+    wt = rnd(g, cout, cin, 3, 3, s=1 / math.sqrt(9 * cin))
+    b = rnd(g, cout, dtype=f32t)
+    ins = {"x1": rows(x1), "wt": wt, "b": b}
+    if c2:
+        ins["x2"] = rows(x2)
+    s1 = s2 = ws = None
+    if csc:
+        s1, s2 = rnd(g, n, csc, h, w), rnd(g, n, csc, h, w)
+        ws = rnd(g, cout, 2 * csc, 1, 1, s=1 / math.sqrt(2 * csc))
+        ins.update(s1=rows(s1), s2=rows(s2), ws=ws)
+    probe = conv2d_any(torch.zeros(1, 1, h, w), torch.zeros(1, 1, 3, 3), None, stride, ups, pad)
+    ho, wo = probe.shape[2:]
+    rpb = ho * wo                                            # one bias2 row per frame
+    if csc or extras:
+        ins["b2"] = rnd(g, n, cout, dtype=f32t)
+    res = None
+    if extras:
+        res = rnd(g, n, cout, ho, wo)
+        ins["r"] = rows(res)
+
+    def run(ops, i, o):
+        if parity:
+            ops.upsample_conv3x3(i["x1"], ops.pack_conv3x3_parity(i["wt"]), i["b"], n, h, w, out=o["y"])
+            return
+        wp = ops.pack_conv3x3(i["wt"], i.get("ws"))
+        if pad is not None:
+            ops.conv3x3(i["x1"], wp, i["b"], n, h, w, stride=stride, pad=pad, out=o["y"])
+        else:
+            ops.conv3x3(i["x1"], wp, i["b"], n, h, w, x2=i.get("x2"), sc1=i.get("s1"), sc2=i.get("s2"), bias2=i.get("b2"),
+                        rows_per_batch=rpb if "b2" in i else 0, residual=i.get("r"), stride=stride, ups=ups, out=o["y"])
+
+    def parity_terms(cv, p):
+        """The four 2x2 convs on x with the tap sums the pack step forms: summed in fp32, rounded to fp16 (elementwise.hip:592-593) —
+        a property of the packed operand, so reference and scale are taken from the same rounded sums."""
+        wf = wt.float()
+        sets = {0: ([0], [1, 2]), 1: ([0, 1], [2])}            # output parity -> kernel rows summed for source offset (-1 | 0), (0 | +1)
+        xp = F.pad(p(cv(x1)), (1, 1, 1, 1))
+        y = torch.zeros(n, cout, 2 * h, 2 * w, dtype=xp.dtype)
+        for py in (0, 1):
+            for px in (0, 1):
+                w2 = torch.stack([torch.stack([wf[:, :, ry][:, :, :, rx].sum((2, 3)) for rx in sets[px]], -1) for ry in sets[py]], -2)
+                w2 = p(cv(w2.half()))                                                  # [cout, cin, 2, 2]
+                y[:, :, py::2, px::2] = F.conv2d(xp[:, :, py:py + h + 1, px:px + w + 1], w2, p(cv(b)))
+        return rows(y)
+
+    def terms(cv, absval):
+        p = (lambda t: t.abs()) if absval else (lambda t: t)
+        if parity:
+            return parity_terms(cv, p)
+        xin = torch.cat([x1, x2], 1) if c2 else x1
+        y = conv2d_any(p(cv(xin)), p(cv(wt)), p(cv(b)), stride, ups, pad)
+        if csc:
+            y = y + F.conv2d(p(cv(torch.cat([s1, s2], 1))), p(cv(ws)))
+        if "b2" in ins:
+            y = y + p(cv(ins["b2"]))[:, :, None, None]
+        if res is not None:
+            y = y + p(cv(res))
+        return rows(y)
+
+    c = oc.gemm_c((4 if parity else 9) * cin + 2 * csc + 3)
+    regions = {"border": border_mask(n, ho, wo, cout)}
+    if parity:
+        for py in (0, 1):
+            for px in (0, 1):
+                m = torch.zeros(n, ho, wo, cout, dtype=torch.bool)
+                m[:, py::2, px::2] = True
+                regions[f"parity{py}{px}"] = m.reshape(-1)
+    if force is not None or parity:
+        # tile seams of the halo-patch geometries: 320 pixels per tile as whole image rows (or 10 x 32 blocks when a row is wider
+        # than a tile): the rows / columns on either side of every tile boundary
+        if w <= 320 and 320 % w == 0:
+            tr, tc = max(320 // w, 1), w
+        else:
+            tr, tc = 10, 32
+        sh, sw = (2, 2) if parity else (1, 1)
+        ys = [y * sh + k for y in range(tr, h, tr) for k in (-1, 0)] if tr < h else []
+        xs = [x * sw + k for x in range(tc, w, tc) for k in (-1, 0)] if tc < w else []
+        regions["seams"] = lines_mask(n, ho, wo, cout, ys, xs) | regions["border"]
+    name = f"conv[{n}x{c1}+{c2}->{cout},{h}x{w},s{stride},u{ups},pad{pad},sc{csc},ex{int(extras)},f{force},k{splits},par{int(parity)}]"
+    setup = (lambda restore: forced(force, splits, restore)) if force is not None else None
+    return Case(name, ins, {"y": ((n * ho * wo, cout), f16)}, run, lambda: {"y": (terms(d, False), terms(d, True))}, c,
+                lambda: {"y": terms(lambda t: t.float(), False).half()}, oc.loc_image(n, ho, wo, cout), regions=regions, setup=setup)
+
+
+CONV_CASES = [dict(n=1, c1=64, cout=64, h=1, w=1), dict(n=1, c1=64, cout=64, h=3, w=3),
+              dict(n=2, c1=64, cout=64, h=5, w=7, stride=2), dict(n=3, c1=64, cout=128, h=4, w=6, ups=1),
+              dict(n=2, c1=64, c2=64, cout=64, h=3, w=5, csc=64),
+              dict(n=1, c1=128, cout=128, h=13, w=18, stride=2, pad=(0, 1)), dict(n=1, c1=128, cout=128, h=2, w=2, stride=2, pad=(0, 1))]
+HALO_CASES = [dict(n=5, c1=64, cout=160, h=8, w=8, extras=True), dict(n=1, c1=64, cout=160, h=40, w=16, extras=True),
+              dict(n=1, c1=128, cout=256, h=20, w=128, extras=True), dict(n=2, c1=64, c2=64, cout=256, h=10, w=96, extras=True, splits=2)]
+# (2, 320, 10, 16) is the smallest geometry lavie_upsample_conv3x3_supported takes: 160 channels, (1, 320, 10, 16), (2, 320, 5, 16),
+# (2, 320, 10, 8) and (1, 320, 5, 8) are all refused (test_upsample_conv3x3_parity asserts it)
+PARITY_CASES = [(2, 320, 10, 16), (32, 320, 5, 8)]
+PARITY_REFUSED = [(2, 160, 10, 16), (1, 320, 10, 16), (2, 320, 5, 16), (2, 320, 10, 8), (1, 320, 5, 8)]
+
+
+@functools.lru_cache(maxsize=None)
+def temporal_conv_case(b, cin, cout, f, dd, taps):
+    g = gen("tconv", b, cin, cout, f, dd, taps)
+    x = rnd(g, b, cin, f, dd)                               # [b, c, f, d]
+    wt = rnd(g, cout, cin, taps, 1, 1, s=1 / math.sqrt(taps * cin))
+    bias, b2 = rnd(g, cout, dtype=f32t), rnd(g, b, cout, dtype=f32t)
+    r = rnd(g, b, cout, f, dd)
+    to_rows = lambda t: t.permute(0, 2, 3, 1).reshape(b * f * dd, -1).contiguous()
+    ins = {"x": to_rows(x), "wt": wt, "bias": bias, "b2": b2, "r": to_rows(r)}
+
+    def run(ops, i, o):
+        ops.temporal_conv(i["x"], ops.pack_temporal_conv(i["wt"]), i["bias"], b, f, dd, taps, bias2=i["b2"], residual=i["r"], out=o["y"])
+
+    def terms(cv, absval):
+        p = (lambda t: t.abs()) if absval else (lambda t: t)
+        y = F.conv3d(p(cv(x))[..., None], p(cv(wt)), p(cv(bias)), padding=(taps // 2, 0, 0))[..., 0]
+        return to_rows(y + p(cv(b2))[:, :, None, None] + p(cv(r)))
+
+    ends = torch.zeros(b, f, dd, cout, dtype=torch.bool)
+    first, last = ends.clone(), ends.clone()
+    first[:, 0] = True
+    last[:, -1] = True
+    return Case(f"temporal_conv[{b}x{cin}->{cout},f{f},d{dd},t{taps}]", ins, {"y": ((b * f * dd, cout), f16)}, run,
+                lambda: {"y": (terms(d, False), terms(d, True))}, oc.gemm_c(taps * cin + 3),
+                lambda: {"y": terms(lambda t: t.float(), False).half()}, oc.loc_image(b * f, dd, 1, cout),
+                regions={"first_frame": first.reshape(-1), "last_frame": last.reshape(-1)})
+
+
+TCONV_SHAPES = [(1, 64, 64, 1, 7), (1, 64, 64, 2, 7), (3, 128, 64, 2, 7), (2, 64, 128, 8, 80)]
+
+
+# ------------------------------------------------------------------ the VAE's edge convs
+EDGE_IN = [(1, 3, 128, 1, 1), (1, 4, 512, 3, 5), (2, 8, 128, 7, 9)]
+EDGE_OUT = [(1, 128, 3, 1, 1), (1, 256, 4, 3, 5), (2, 512, 8, 7, 9)]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_in_case(n, cin, cout, h, w, dtype, tap):
+    """NCHW image (fp16 or fp32) -> channels-last fp16 rows.  fp16 input: GEMM family, K_terms = 9 cin + 10 (bias + nine tap biases).
+    fp32 input: the kernel converts x to fp16 on load (conv_edge.hip:72-73), one deterministic conversion of the operand: reference
+    and scale are taken from x.half(), and the GEMM-family bound holds for both input types."""
+    g = gen("edge_in", n, cin, cout, h, w, dtype, tap)
+    x = rnd(g, n, cin, h, w, dtype=dtype)
+    wt, b = rnd(g, cout, cin, 3, 3, s=1 / math.sqrt(9 * cin)), rnd(g, cout, dtype=f32t, s=0.5)
+    ins = {"x": x, "wt": wt, "b": b}
+    if tap:
+        ins["tb"] = rnd(g, 9, cout, dtype=f32t, s=0.3)
+
+    def run(ops, i, o):
+        ops.conv_edge_in(i["x"], ops.pack_conv_edge_in(i["wt"]), i["b"], cout, tap_bias=i.get("tb"), out=o["y"])
+
+    def terms(cv, absval):
+        p = (lambda t: t.abs()) if absval else (lambda t: t)
+        xx = cv(x.half())
+        y = F.conv2d(p(xx), p(cv(wt)), p(cv(b)), padding=1)
+        if tap:     # the taps of a pixel that fall inside the image add their bias: a conv of an all-ones image
+            y = y + F.conv2d(torch.ones(n, 1, h, w, dtype=y.dtype), p(cv(ins["tb"])).t().reshape(cout, 1, 3, 3).contiguous(), padding=1)
+        return rows(y)
+
+    c = oc.gemm_c(9 * cin + 10)
+    return Case(f"conv_edge_in[{n}x{cin}->{cout},{h}x{w},{str(dtype)[6:]},tap{int(tap)}]", ins, {"y": ((n * h * w, cout), f16)}, run,
+                lambda: {"y": (terms(d, False), terms(d, True))}, c,
+                lambda: {"y": terms(lambda t: t.float(), False).half()}, oc.loc_image(n, h, w, cout),
+                regions={"border": border_mask(n, h, w, cout)})
+
+
+@functools.lru_cache(maxsize=None)
+def edge_out_case(n, cin, cout, h, w, dtype):
+    """channels-last fp16 rows -> NCHW image in fp16 or fp32 from fp32 accumulators: GEMM family, K_terms = 9 cin + 1."""
+    g = gen("edge_out", n, cin, cout, h, w, dtype)
+    x = rnd(g, n, cin, h, w)
+    wt, b = rnd(g, cout, cin, 3, 3, s=1 / math.sqrt(9 * cin)), rnd(g, cout, dtype=f32t, s=0.5)
+    ins = {"x": rows(x), "wt": wt, "b": b}
+
+    def run(ops, i, o):
+        ops.conv_edge_out(i["x"], ops.pack_conv_edge_out(i["wt"]), i["b"], n, h, w, cout, dtype, out=o["y"])
+
+    def terms(cv, absval):
+        p = (lambda t: t.abs()) if absval else (lambda t: t)
+        return F.conv2d(p(cv(x)), p(cv(wt)), p(cv(b)), padding=1)
+
+    border = torch.ones(n, cout, h, w, dtype=torch.bool)
+    if h > 2 and w > 2:
+        border[:, :, 1:-1, 1:-1] = False
+    return Case(f"conv_edge_out[{n}x{cin}->{cout},{h}x{w},{str(dtype)[6:]}]", ins, {"y": ((n, cout, h, w), dtype)}, run,
+                lambda: {"y": (terms(d, False), terms(d, True))}, oc.gemm_c(9 * cin + 1),
+                lambda: {"y": terms(lambda t: t.float(), False).to(dtype)}, oc.loc_nchw(cout, h, w), regions={"border": border.reshape(-1)})
+
+
+# ------------------------------------------------------------------ norms
+def silu64(x):
+    return x * torch.sigmoid(x)
+
+
+@functools.lru_cache(maxsize=None)
+def group_norm_case(nb, P, c1, c2=0, silu=True, eps=1e-5, offset=0.0, affine=False, tag=""):
+    """[nb * P, c1 (+ c2)] rows, 32 groups, statistics over the P rows of a batch.  Rounding points, n = 1: the output store
+    (norm.hip:261); everything before it is fp32, the variance formed as E[x^2] - mean^2 (norm.hip:150) — the model does the same.
+    offset: group means at `offset` standard deviations."""
+    g = gen("gn", nb, P, c1, c2, silu, offset, affine)
+    ctot, groups = c1 + c2, 32
+    x = torch.randn(nb * P, ctot, generator=g)
+    x = x + offset if offset else x * (0.5 + torch.rand(1, ctot, generator=g)) + 0.3
+    x = x.half()
+    gamma, beta = (1 + 0.1 * torch.randn(ctot, generator=g)), 0.1 * torch.randn(ctot, generator=g)
+    ins = {"x1": x[:, :c1].contiguous(), "gamma": gamma, "beta": beta}
+    if c2:
+        ins["x2"] = x[:, c1:].contiguous()
+    cpg = ctot // groups
+
+    def ab(cv, kernel_variance):
+        xg = cv(x).reshape(nb, P, groups, cpg)
+        mean = xg.mean((1, 3))
+        if kernel_variance:            # fp32 sums, var = max(E[x^2] - mean^2, 0)
+            cnt = float(P * cpg)
+            mean = xg.sum((1, 3)) * (1.0 / cnt)
+            var = ((xg * xg).sum((1, 3)) * (1.0 / cnt) - mean * mean).clamp_min(0.0)
+        else:
+            var = xg.var((1, 3), unbiased=False)
+        rstd = (var + eps).rsqrt()                                        # [nb, groups]
+        a = rstd.repeat_interleave(cpg, 1) * cv(gamma)                    # [nb, ctot]
+        bb = cv(beta) - mean.repeat_interleave(cpg, 1) * a
+        return a, bb
+
+    def run(ops, i, o):
+        if affine:
+            ops.group_norm_affine(i["x1"], i["gamma"], i["beta"], nb, groups, eps, out=o["y"])
+        else:
+            ops.group_norm(i["x1"], i["gamma"], i["beta"], nb, groups, eps, silu, x2=i.get("x2"), out=o["y"])
+
+    def ref():
+        a, bb = ab(d, False)
+        if affine:
+            mean_a = (d(beta) - bb).abs()
+            return {"y": (torch.stack([a, bb], -1), torch.stack([a.abs(), mean_a + d(beta).abs()], -1))}
+        xr = d(x).reshape(nb, P, ctot)
+        y = xr * a[:, None] + bb[:, None]
+        sc = (xr * a[:, None]).abs() + bb[:, None].abs()
+        if silu:
+            y, sc = silu64(y), 1.1 * sc                                   # max |silu'| < 1.1
+        return {"y": (y.reshape(nb * P, ctot), sc.reshape(nb * P, ctot))}
+
+    def model():
+        a, bb = ab(lambda t: t.float(), True)
+        if affine:
+            return {"y": torch.stack([a, bb], -1)}
+        y = x.float().reshape(nb, P, ctot) * a[:, None] + bb[:, None]
+        return {"y": (F.silu(y) if silu else y).reshape(nb * P, ctot).half()}
+
+    out = ((nb, ctot, 2), f32t) if affine else ((nb * P, ctot), f16)
+    where = (lambda i: "(batch %d, channel %d, %s)" % (i // (2 * ctot), i // 2 % ctot, "ab"[i % 2])) if affine else oc.loc_rows(ctot)
+    return Case(f"group_norm[{tag}nb{nb},P{P},{c1}+{c2},silu{int(silu)},off{offset},aff{int(affine)}]", ins, {"y": out}, run, ref,
+                oc.round_c(1), model, where)
+
+
+GN_CASES = [dict(nb=1, P=3, c1=64, tag="video:"), dict(nb=2, P=10, c1=320, tag="video:"),
+            dict(nb=3, P=5, c1=320, silu=False, eps=1e-6, tag="frame:"), dict(nb=1, P=6, c1=1280, c2=640, tag="straddle:"),
+            dict(nb=2, P=10, c1=320, affine=True), dict(nb=2, P=10, c1=320, offset=8.0, tag="offset:")]
+
+
+@functools.lru_cache(maxsize=None)
+def layer_norm_case(M, C, offset=0.0):
+    """n = 1: the output store (norm.hip:448); mean and the two-pass variance are fp32 (norm.hip:426-435)."""
+    g = gen("ln", M, C, offset)
+    x = torch.randn(M, C, generator=g)
+    x = (x / x.std(1, keepdim=True) + offset if offset else x * 2 + 0.7).half()
+    gamma, beta = 1 + 0.1 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    ins = {"x": x, "gamma": gamma, "beta": beta}
+
+    def ab(cv):
+        xx = cv(x)
+        mean = xx.mean(1, keepdim=True)
+        a = ((xx - mean).pow(2).mean(1, keepdim=True) + 1e-5).rsqrt() * cv(gamma)
+        return a, mean
+
+    def run(ops, i, o):
+        ops.layer_norm(i["x"], i["gamma"], i["beta"], out=o["y"])
+
+    def ref():
+        a, mean = ab(d)
+        b = d(beta) - mean * a
+        return {"y": (d(x) * a + b, (d(x) * a).abs() + b.abs())}
+
+    def model():
+        a, mean = ab(lambda t: t.float())
+        return {"y": ((x.float() - mean) * a + beta).half()}
+
+    return Case(f"layer_norm[{M}x{C},off{offset}]", ins, {"y": ((M, C), f16)}, run, ref, oc.round_c(1), model, oc.loc_rows(C))
+
+
+LN_CASES = [(1, 320, 0.0), (5, 256, 0.0), (65, 1280, 0.0), (5, 320, 8.0)]
+
+
+# ------------------------------------------------------------------ attention
+LOG2E = 1.4426950408889634
+
+
+def attn_model(q, k, v, scale, n_q_round):
+    """[..., lq, dh] x [..., lk, dh]: the kernels' arithmetic in torch fp32 — Q scaled by scale log2(e) and rounded to fp16 where the
+    kernel does that, exp2 of the shifted scores, P rounded to fp16 before the PV product, the row sum taken over the rounded P
+    (the matrix pipe sums it as an extra V column), one rounding at the store."""
+    qs = (q.float() * (scale * LOG2E))
+    if n_q_round:
+        qs = qs.half().float()
+    s = qs @ k.float().transpose(-1, -2)
+    p = torch.exp2(s - s.max(-1, keepdim=True).values).half().float()
+    return ((p @ v.float()) / p.sum(-1, keepdim=True)).half()
+
+
+def attn_ref(q, k, v, scale):
+    p = torch.softmax(d(q) @ d(k).transpose(-1, -2) * scale, -1)
+    return p @ d(v), p @ d(v).abs()
+
+
+def split_heads(t, nb, heads):
+    return t.reshape(nb, -1, heads, t.shape[-1] // heads).permute(0, 2, 1, 3)
+
+
+def merge_heads(t):
+    nb, heads, l, dh = t.shape
+    return t.permute(0, 2, 1, 3).reshape(nb * l, heads * dh)
+
+
+@functools.lru_cache(maxsize=None)
+def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8):
+    """ops.attention on column slices of wider tensors whose other columns are NaN.  Self-attention (lk None): q | k | v are the
+    thirds of one [nb*lq, 3c + 16] tensor; cross-attention: k | v are halves of a [(nb / kv_div) lk, 2c + 16] tensor.
+    Rounding points: n = 3 at head dims up to 160 — Q' = fp16(Q scale log2 e) (attention.hip:437), P before the PV product
+    (attention.hip:625-626; 241-242 in the register-staged kernel, which has no Q' rounding), the output store (attention.hip:739 /
+    300); n = 2 at head dims 256 / 512 (attention_wide.hip:345-346 and 398)."""
+    g = gen("attn", nb, lq, c, lk, kv_div, heads)
+    dh = c // heads
+    wide = dh > 160
+    cross = lk is not None
+    lk_ = lk if cross else lq
+    nkv = nb // kv_div
+    q, k, v = rnd(g, nb * lq, c), rnd(g, nkv * lk_, c), rnd(g, nkv * lk_, c)
+    nan = lambda r, w: torch.full((r, w), math.nan, dtype=f16)
+    if cross:
+        ins = {"qw": torch.cat([nan(nb * lq, 8), q, nan(nb * lq, 8)], 1), "kvw": torch.cat([k, nan(nkv * lk_, 16), v], 1)}
+    else:
+        ins = {"qkvw": torch.cat([q, nan(nb * lq, 8), k, nan(nb * lq, 8), v], 1)}
+
+    def run(ops, i, o):
+        if cross:
+            qd, kd, vd = i["qw"][:, 8:8 + c], i["kvw"][:, :c], i["kvw"][:, c + 16:]
+        else:
+            qd, kd, vd = i["qkvw"][:, :c], i["qkvw"][:, c + 8:2 * c + 8], i["qkvw"][:, 2 * c + 16:]
+        ops.attention(qd, kd, vd, nb=nb, lq=lq, lk=lk_, heads=heads, kv_batch_div=kv_div, out=o["y"])
+
+    def heads_of():
+        rep = lambda t: split_heads(t.reshape(nkv, lk_, c), nkv, heads).repeat_interleave(kv_div, 0)
+        return split_heads(q.reshape(nb, lq, c), nb, heads), rep(k), rep(v)
+
+    def ref():
+        y, sc = attn_ref(*heads_of(), dh ** -0.5)
+        return {"y": (merge_heads(y), merge_heads(sc))}
+
+    return Case(f"attention[nb{nb},lq{lq},lk{lk},c{c},h{heads},div{kv_div}]", ins, {"y": ((nb * lq, c), f16)}, run, ref,
+                oc.round_c(2 if wide else 3), lambda: {"y": merge_heads(attn_model(*heads_of(), dh ** -0.5, not wide))},
+                oc.loc_heads(heads, dh))
+
+
+SELF_ATTN = [(1, 1, 256), (2, 33, 320), (1, 65, 320), (1, 129, 1280)]
+CROSS_ATTN = [(lk, div) for lk in (1, 10, 77) for div in (1, 3)]
+WIDE_ATTN = [(1, 512), (33, 512), (65, 512), (33, 256)]
+
+
+@functools.lru_cache(maxsize=None)
+def sparse_causal_case(frames, dd, c=320, heads=8, videos=2):
+    """Frame f attends to [frame 0 || frame max(f - 1, 0)] of its video; same kernels and rounding points as attention_case (n = 3)."""
+    g = gen("sc", frames, dd, c)
+    nb, dh = videos * frames, c // heads
+    qkv = rnd(g, nb * dd, 3 * c)
+    ins = {"qkv": qkv}
+    prev = torch.tensor([vi * frames + (0, max(fi - 1, 0))[j] for vi in range(videos) for fi in range(frames) for j in (0, 1)])
+
+    def run(ops, i, o):
+        t = i["qkv"]
+        ops.sparse_causal_attention(t[:, :c], t[:, c:2 * c], t[:, 2 * c:], nb, frames, dd, heads, out=o["y"])
+
+    def heads_of():
+        q, k, v = (t.reshape(nb, dd, c) for t in qkv.split(c, 1))
+        kk, vv = (t[prev].reshape(nb, 2 * dd, c) for t in (k, v))
+        return split_heads(q, nb, heads), split_heads(kk, nb, heads), split_heads(vv, nb, heads)
+
+    def ref():
+        y, sc = attn_ref(*heads_of(), dh ** -0.5)
+        return {"y": (merge_heads(y), merge_heads(sc))}
+
+    return Case(f"sparse_causal[f{frames},d{dd}]", ins, {"y": ((nb * dd, c), f16)}, run, ref, oc.round_c(3),
+                lambda: {"y": merge_heads(attn_model(*heads_of(), dh ** -0.5, True))}, oc.loc_heads(heads, dh))
+
+
+SPARSE_CAUSAL = [(1, 5), (3, 5), (2, 65)]
+
+
+# ------------------------------------------------------------------ temporal attention and the row-resident fused blocks
+def h_(t):
+    """one fp16 rounding point of a model"""
+    return t.half().float()
+
+
+def ident(t):
+    return t
+
+
+def rotary_tables(frames, rot_dim=32):
+    inv = 10000.0 ** (-torch.arange(0, rot_dim, 2, dtype=f32t) / rot_dim)
+    ang = torch.arange(frames, dtype=f32t).reshape(-1, 1) * inv.reshape(1, -1)
+    return ang.cos().contiguous(), ang.sin().contiguous()
+
+
+def rot(t, cos, sin):
+    """rotary embedding on channel pairs (2k, 2k + 1) of the first 2 * cos.shape[1] head dims; t [..., f, dh]"""
+    r = 2 * cos.shape[1]
+    e, o = t[..., 0:r:2], t[..., 1:r:2]
+    out = t.clone()
+    out[..., 0:r:2] = e * cos - o * sin
+    out[..., 1:r:2] = o * cos + e * sin
+    return out
+
+
+def temporal_core(q, k, v, bias, cos, sin, scale, cv, rq, p_before_norm):
+    """[N, heads, f, dh] sequences: softmax(rot(q scale) rot(k)^T + bias) v.  rq = rounding applied where the kernels round
+    (identity for the float64 reference); p_before_norm: the fused block rounds exp() and normalises the product,
+    the standalone kernels round the normalised P.  Returns (out, sum_j p_j |v_j|)."""
+    q, k, v = cv(q) * scale, cv(k), cv(v)
+    if cos is not None:
+        q, k = rot(q, cv(cos), cv(sin)), rot(k, cv(cos), cv(sin))
+    s = rq(q) @ rq(k).transpose(-1, -2) + cv(bias)[None]
+    e = torch.exp(s - s.max(-1, keepdim=True).values)
+    l = e.sum(-1, keepdim=True)
+    if p_before_norm:
+        return (rq(e) @ v) / l, (e / l) @ v.abs()
+    return rq(e / l) @ v, (e / l) @ v.abs()
+
+
+@functools.lru_cache(maxsize=None)
+def temporal_attention_case(b, f, dd, c, tiled, plain=False, heads=8):
+    """ops.temporal_attention on qkv [(b f d), 3c].  Rounding points, n = 4: q scaled (and rotated) to fp16
+    (temporal_attention.hip:162-163 / :169; tiled kernel :472-473 / :477), k rotated to fp16 (:164-165; :440-441), the normalised P
+    (:216; :517), the output (:238; :539).  tiled: the tile kernel through lavie_debug_temporal_budget, else the streaming one."""
+    g = gen("tattn", b, f, dd, c, plain)
+    dh = c // heads
+    qkv = rnd(g, b * f * dd, 3 * c)
+    bias = torch.zeros(heads, f, f) if plain else rnd(g, heads, f, f, dtype=f32t)
+    cos, sin = (None, None) if plain else rotary_tables(f)
+    ins = {"qkv": qkv, "bias": bias}
+    if not plain:
+        ins.update(cos=cos, sin=sin)
+
+    def run(ops, i, o):
+        from lavie_amd import _lib
+        lib = _lib.load()
+        lib.lavie_debug_temporal_budget(33000 if tiled else 0)
+        try:
+            ops.temporal_attention(i["qkv"], b, f, dd, heads, i["bias"], i.get("cos"), i.get("sin"), rot_dim=0 if plain else 32, out=o["y"])
+        finally:
+            lib.lavie_debug_temporal_budget(0)
+
+    seq = lambda: qkv.reshape(b, f, dd, 3, heads, dh).permute(3, 0, 2, 4, 1, 5).reshape(3, b * dd, heads, f, dh)
+    back = lambda t: t.reshape(b, dd, heads, f, dh).permute(0, 3, 1, 2, 4).reshape(b * f * dd, c)
+
+    def ref():
+        y, sc = temporal_core(*seq(), bias, cos, sin, dh ** -0.5, d, ident, False)
+        return {"y": (back(y), back(sc))}
+
+    def model():
+        y, _ = temporal_core(*seq(), bias, cos, sin, dh ** -0.5, lambda t: t.float(), h_, False)
+        return {"y": back(y).half()}
+
+    return Case(f"temporal_attention[b{b},f{f},d{dd},c{c},{'tiled' if tiled else 'stream'},plain{int(plain)}]", ins,
+                {"y": ((b * f * dd, c), f16)}, run, ref, oc.round_c(4), model, oc.loc_heads(heads, dh))
+
+
+TATTN_SHAPES = [(1, 1, 3, 256), (1, 2, 1, 320), (1, 17, 5, 256), (2, 16, 5, 320)]
+
+
+def ln(x, gamma, beta, cv, eps=1e-5):
+    x = cv(x)
+    mean = x.mean(-1, keepdim=True)
+    return (x - mean) * ((x - mean).pow(2).mean(-1, keepdim=True) + eps).rsqrt() * cv(gamma) + cv(beta)
+
+
+def block_case(name, ins, run, chain, n, C, in_place, outs=None, where=None):
+    """A fused block: chain(cv, rq) -> name -> (value, scale); the float64 reference runs it without roundings, the model in
+    fp32 with rq = one fp16 rounding at each counted point (the output store included)."""
+    outs = outs or {"y": ((ins["x"].shape[0], C), f16)}
+
+    def model():
+        return {k: v.half() for k, (v, _) in chain(lambda t: t.float(), h_).items()}
+
+    c = {k: oc.round_c(v) for k, v in n.items()} if isinstance(n, dict) else oc.round_c(n)
+    return Case(f"{name}[inplace{int(in_place)}]", ins, outs, run, lambda: chain(d, ident), c, model,
+                where or oc.loc_rows(C), alias={"y": "x"} if in_place else None)
+
+
+@functools.lru_cache(maxsize=None)
+def geglu_mlp_case(M, in_place, C=320):
+    """x + W2 (h gelu(g)) + b2 with (h | g) = W1 LN(x) + b1.  n = 3: LN(x) (rowfuse.hip:185-186), h gelu(g) (:224-225), the output
+    (:256).  scale = |h gelu(g)| |W2| + |b2| + |x|."""
+    g = gen("geglu_mlp", M)
+    x = (torch.randn(M, C, generator=g) * 1.5 + 0.3 * torch.randn(1, C, generator=g)).half()
+    w1, b1 = rnd(g, 8 * C, C, s=1 / math.sqrt(C)), rnd(g, 8 * C, s=0.2)
+    w2, b2 = rnd(g, C, 4 * C, s=1 / math.sqrt(4 * C)), rnd(g, C, dtype=f32t, s=0.2)
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    ins = {"x": x, "w1": w1, "b1": b1, "w2": w2, "b2": b2, "gamma": gamma, "beta": beta}
+
+    def run(ops, i, o):
+        img, b1img = ops.pack_geglu_mlp(i["w1"], i["b1"], i["w2"])
+        ops.geglu_mlp(i["x"], img, b1img, i["gamma"], i["beta"], i["b2"], out=o["y"])
+
+    def chain(cv, rq):
+        hh, gate = (rq(ln(x, gamma, beta, cv)) @ cv(w1).t() + cv(b1)).chunk(2, -1)
+        hg = rq(hh * gelu64(gate))
+        return {"y": (cv(x) + hg @ cv(w2).t() + cv(b2), hg.abs() @ cv(w2).abs().t() + cv(b2).abs() + cv(x).abs())}
+
+    return block_case(f"geglu_mlp[M{M}]", ins, run, chain, 3, C, in_place)
+
+
+@functools.lru_cache(maxsize=None)
+def cross_block_case(B, P, L, in_place, C=320, heads=8):
+    """x1 = x + Wo1 att + bo1; y = x1 + Wo2 attn2(LN(x1) Wq2, K, V) + bo2, K | V bound per video; the long variant above 80 keys.
+    n = 5: LN(x1) (rowfuse_cross.hip:430-431), q as the MFMA operand (:488 / :496), P (:571), the attention output (:614 / :622), the
+    output store (rowfuse.h:173).  scale = |o| |Wo2| + |bo2| + |att| |Wo1| + |bo1| + |x|."""
+    g = gen("cross_block", B, P, L)
+    M, dh = B * P, C // heads
+    long = L > 80
+    x = (torch.randn(M, C, generator=g) * 1.5 + 0.3 * torch.randn(1, C, generator=g)).half()
+    att = rnd(g, M, C)
+    wo1, wq2, wo2 = (rnd(g, C, C, s=1 / math.sqrt(C)) for _ in range(3))
+    bo1, bo2 = rnd(g, C, dtype=f32t, s=0.2), rnd(g, C, dtype=f32t, s=0.2)
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    kv = rnd(g, B * L, 2 * C)
+    ins = dict(x=x, att=att, wo1=wo1, wq2=wq2, wo2=wo2, bo1=bo1, bo2=bo2, gamma=gamma, beta=beta, kv=kv)
+
+    def run(ops, i, o):
+        pack, bind, op = ((ops.pack_cross_block_long, ops.bind_cross_block_long, ops.cross_block_long) if long else
+                          (ops.pack_cross_block, ops.bind_cross_block, ops.cross_block))
+        img = bind(pack(i["wo1"], i["wq2"], i["wo2"]), i["kv"], B, L)
+        op(i["att"], i["x"], img, i["bo1"], i["gamma"], i["beta"], i["bo2"], P, L, heads, dh ** -0.5, out=o["y"])
+
+    def chain(cv, rq):
+        x1 = cv(x) + cv(att) @ cv(wo1).t() + cv(bo1)
+        s1 = cv(x).abs() + cv(att).abs() @ cv(wo1).abs().t() + cv(bo1).abs()
+        q = rq(rq(ln(x1, gamma, beta, cv)) @ cv(wq2).t()).reshape(B, P, heads, dh).permute(0, 2, 1, 3)
+        k = cv(kv[:, :C]).reshape(B, L, heads, dh).permute(0, 2, 1, 3)
+        v = cv(kv[:, C:]).reshape(B, L, heads, dh).permute(0, 2, 1, 3)
+        s = q @ k.transpose(-1, -2) * dh ** -0.5
+        e = torch.exp(s - s.max(-1, keepdim=True).values)
+        o = rq((rq(e) @ v) / e.sum(-1, keepdim=True)).permute(0, 2, 1, 3).reshape(M, C)
+        return {"y": (x1 + o @ cv(wo2).t() + cv(bo2), s1 + o.abs() @ cv(wo2).abs().t() + cv(bo2).abs())}
+
+    return block_case(f"cross_block{'_long' if long else ''}[B{B},P{P},L{L}]", ins, run, chain, 5, C, in_place)
+
+
+# (videos, rows per video, keys): rows per video must be a multiple of the 16-token wave tile (cross_block_supported); 16 = the
+# smallest, 144 = one 128-row pass and a ragged one per video.  CROSS_REFUSED: one row per video, which both kernels refuse
+CROSS_BLOCKS = [(1, 16, 1), (2, 144, 5), (3, 16, 77), (1, 144, 80), (1, 16, 81), (2, 144, 160)]
+CROSS_REFUSED = [(1, 1, 5), (1, 1, 100)]
+
+
+@functools.lru_cache(maxsize=None)
+def temporal_block_case(B, D, in_place, C=320, heads=8, Fr=16):
+    """x + Wo attn_temp(LN(x)) + bo on rows (b f) d.  n = 7: LN(x) (rowfuse.hip:482-483), q scaled and rotated, k rotated, v
+    (:521-523), exp() of the scores (:572), the attention output (:577-583), the output store (:641).
+    scale = |o| |Wo| + |bo| + |x|."""
+    g = gen("temporal_block", B, D)
+    M, dh = B * Fr * D, C // heads
+    x = (torch.randn(M, C, generator=g) * 1.5 + 0.3 * torch.randn(1, C, generator=g)).half()
+    wq, wk, wv, wo = (rnd(g, C, C, s=1 / math.sqrt(C)) for _ in range(4))
+    bo = rnd(g, C, dtype=f32t, s=0.2)
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    relbias = rnd(g, heads, Fr, Fr, dtype=f32t)
+    cos, sin = rotary_tables(Fr)
+    ins = dict(x=x, wq=wq, wk=wk, wv=wv, wo=wo, bo=bo, gamma=gamma, beta=beta, relbias=relbias, cos=cos, sin=sin)
+
+    def run(ops, i, o):
+        img = ops.pack_temporal_block(i["wq"], i["wk"], i["wv"], i["wo"])
+        ops.temporal_block(i["x"], img, i["gamma"], i["beta"], i["bo"], i["relbias"], i["cos"], i["sin"], B, Fr, D, heads, 32,
+                           dh ** -0.5, out=o["y"])
+
+    def chain(cv, rq):
+        xn = rq(ln(x, gamma, beta, cv))
+        seq = lambda w: (xn @ cv(w).t()).reshape(B, Fr, D, heads, dh).permute(0, 2, 3, 1, 4).reshape(B * D, heads, Fr, dh)
+        # q and k are rounded after scale / rotary (inside temporal_core), v as it leaves its projection
+        o, _ = temporal_core(seq(wq), seq(wk), rq(seq(wv)), relbias, cos, sin, dh ** -0.5, ident, rq, True)
+        o = rq(o).reshape(B, D, heads, Fr, dh).permute(0, 3, 1, 2, 4).reshape(M, C)
+        return {"y": (cv(x) + o @ cv(wo).t() + cv(bo), cv(x).abs() + o.abs() @ cv(wo).abs().t() + cv(bo).abs())}
+
+    return block_case(f"temporal_block[B{B},D{D}]", ins, run, chain, 7, C, in_place)
+
+
+@functools.lru_cache(maxsize=None)
+def proj_qkv_case(NB, D, C=320):
+    """tx = Wpin (a x + b) + bpin with the per-(frame, channel) GroupNorm pairs (a, b) as an input; qkv = Wqkv LN(tx).
+    tx: n = 2 — a x + b (rowfuse_pin.hip:153-160), the store (rowfuse.h:173).  qkv: n = 3 — a x + b, LN(tx) taken from the fp32
+    accumulators (rowfuse_pin.hip:223-224), the store."""
+    g = gen("proj_qkv", NB, D)
+    M, G = NB * D, 32
+    x = (torch.randn(M, C, generator=g) * 1.3 + 0.4 * torch.randn(NB, 1, C, generator=g).repeat_interleave(D, 0).reshape(M, C)).half()
+    gn_g, gn_b = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    wpin, bpin = rnd(g, C, C, s=1 / math.sqrt(C)), rnd(g, C, dtype=f32t, s=0.2)
+    ln_g, ln_b = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    wqkv = rnd(g, 3 * C, C, s=1 / math.sqrt(C))
+    xg = x.float().reshape(NB, D, G, C // G)
+    mean, var = xg.mean((1, 3)), xg.var((1, 3), unbiased=False)
+    a = (var + 1e-6).rsqrt().repeat_interleave(C // G, 1) * gn_g
+    ab = torch.stack([a, gn_b - mean.repeat_interleave(C // G, 1) * a], -1).contiguous()          # [NB, C, 2]
+    ins = dict(x=x, ab=ab, wpin=wpin, wqkv=wqkv, bpin=bpin, ln_g=ln_g, ln_b=ln_b)
+
+    def run(ops, i, o):
+        ops.proj_qkv(i["x"], i["ab"], D, ops.pack_proj_qkv(i["wpin"], i["wqkv"]), i["bpin"], i["ln_g"], i["ln_b"], tx=o["tx"], qkv=o["qkv"])
+
+    def chain(cv, rq):
+        aa, bb = cv(ab[..., 0]).repeat_interleave(D, 0), cv(ab[..., 1]).repeat_interleave(D, 0)
+        xb = rq(cv(x) * aa + bb)
+        tx = xb @ cv(wpin).t() + cv(bpin)
+        xb2 = rq(ln(tx, ln_g, ln_b, cv))
+        return {"tx": (tx, xb.abs() @ cv(wpin).abs().t() + cv(bpin).abs()), "qkv": (xb2 @ cv(wqkv).t(), xb2.abs() @ cv(wqkv).abs().t())}
+
+    return block_case(f"proj_qkv[NB{NB},D{D}]", ins, run, chain, {"tx": 2, "qkv": 3}, C, False, outs={"tx": ((M, C), f16), "qkv": ((M, 3 * C), f16)},
+                      where={"tx": oc.loc_rows(C), "qkv": oc.loc_rows(3 * C)})
+
+
+# ------------------------------------------------------------------ sampler steps and lora_merge
+STEP_KINDS = ["cfg_ddpm_step", "sampler_step", "cfg_multistep_step", "multistep_step", "latents_to_model_input", "latents_to_model_input1"]
+STEP_LENGTHS = [1, 7, 8, 9, 4097]
+
+
+@functools.lru_cache(maxsize=None)
+def step_case(kind, n):
+    """Elementwise fp32 updates; x (and x0_prev) are rewritten in place, model_in is the fp16 output.  Bound: the GEMM family's with
+    K_terms = 6 (at most six fp32 operations per element) on the sum of the absolute terms."""
+    g = gen("step", kind, n)
+    cfg = kind.startswith("cfg") or kind == "latents_to_model_input"
+    multi = "multistep" in kind
+    copy_only = kind.startswith("latents")
+    guidance, in_scale = 7.5, 0.8125
+    kx, ke, c0, ct, last = 1.25, 0.75, 0.375, 0.625, 0.5          # last: sigma (ddpm) or c_prev (multistep)
+    x = rnd(g, n, dtype=f32t)
+    ins = {"x": x}
+    outs = {"model_in": ((2 * n if cfg else n,), f16)}
+    alias = {}
+    if not copy_only:
+        ins["eps"] = rnd(g, 2 * n if cfg else n)
+        ins["aux"] = rnd(g, n, dtype=f32t)                          # noise or x0_prev
+        outs["x"] = ((n,), f32t)
+        alias["x"] = "x"
+        if multi:
+            outs["aux"] = ((n,), f32t)
+            alias["aux"] = "aux"
+
+    def run(ops, i, o):
+        co = (kx, ke, c0, ct, last)
+        if kind == "cfg_ddpm_step":
+            ops.cfg_ddpm_step(i["eps"], i["x"], i["aux"], o["model_in"], guidance, co, in_scale)
+        elif kind == "sampler_step":
+            ops.sampler_step(i["eps"], i["x"], i["aux"], o["model_in"], co, in_scale)
+        elif kind == "cfg_multistep_step":
+            ops.cfg_multistep_step(i["eps"], i["x"], i["aux"], o["model_in"], guidance, co, in_scale)
+        elif kind == "multistep_step":
+            ops.multistep_step(i["eps"], i["x"], i["aux"], o["model_in"], co, in_scale)
+        elif kind == "latents_to_model_input":
+            ops.latents_to_model_input(i["x"], o["model_in"], in_scale)
+        else:
+            ops.latents_to_model_input1(i["x"], o["model_in"], in_scale)
+
+    def compute(cv, absval):
+        p = (lambda t: t.abs()) if absval else (lambda t: t)
+        s = (lambda a, b: a + b) if absval else (lambda a, b: a - b)     # a difference counts with both magnitudes
+        k = abs if absval else (lambda t: t)
+        xt = p(cv(x))
+        res = {}
+        if copy_only:
+            xn = xt
+        else:
+            e = p(cv(ins["eps"]))
+            eps = e[:n] + k(guidance) * s(e[n:], e[:n]) if cfg else e
+            x0 = s(k(kx) * xt, k(ke) * eps)
+            aux = p(cv(ins["aux"]))
+            if multi:
+                xn = k(c0) * (x0 + k(last) * s(x0, aux)) + k(ct) * xt
+                res["aux"] = x0
+            else:
+                xn = k(c0) * x0 + k(ct) * xt + k(last) * aux
+            res["x"] = xn
+        mi = xn * in_scale
+        res["model_in"] = torch.cat([mi, mi]) if cfg else mi
+        return res
+
+    def ref():
+        r, sc = compute(d, False), compute(d, True)
+        return {kk: (r[kk], sc[kk]) for kk in r}
+
+    def model():
+        r = compute(lambda t: t.float(), False)
+        r["model_in"] = r["model_in"].half()
+        return r
+
+    return Case(f"{kind}[{n}]", ins, outs, run, ref, oc.gemm_c(6), model, lambda i: f"element {i}", alias=alias)
+
+
+LORA_SHAPES = [(1, 8, 1), (3, 24, 2), (320, 320, 16)]
+
+
+@functools.lru_cache(maxsize=None)
+def lora_case(N, K, r, in_place):
+    g = gen("lora", N, K, r)
+    w0, a, b = rnd(g, N, K), rnd(g, r, K, dtype=f32t), rnd(g, N, r, dtype=f32t, s=0.1)
+    scale = 0.75
+    ins = {"w0": w0, "a": a, "b": b}
+
+    def run(ops, i, o):
+        ops.lora_merge(i["w0"], i["a"], i["b"], scale, out=o["y"])
+
+    terms = lambda cv, p: p(cv(w0)) + scale * (p(cv(b)) @ p(cv(a)))
+    ident, ab_ = (lambda t: t), (lambda t: t.abs())
+    return Case(f"lora_merge[{N}x{K},r{r},inplace{int(in_place)}]", ins, {"y": ((N, K), f16)}, run,
+                lambda: {"y": (terms(d, ident), terms(d, ab_))}, oc.gemm_c(r + 2),
+                lambda: {"y": terms(lambda t: t.float(), ident).half()}, oc.loc_rows(K), alias={"y": "w0"} if in_place else None)
+
+
+def all_cases():
+    """Every case both test files run (the host file: the model of each against its own bound)."""
+    cs = [linear_case(*s, o) for s in LINEAR_SHAPES for o in LINEAR_OPTIONS]
+    cs += [geglu_case(129, 64), geglu_case(154, 320), lnfold_case(154, 320, 320), lnfold_case(161, 192, 64)]
+    cs += [conv_case(**k) for k in CONV_CASES]
+    cs += [conv_case(**k, force=5) for k in HALO_CASES]            # force = 3 has the same model and reference
+    cs += [conv_case(n=n, c1=c, cout=c, h=h, w=w, ups=1, parity=True) for n, c, h, w in PARITY_CASES]
+    cs += [temporal_conv_case(*s, t) for s in TCONV_SHAPES for t in (3, 5)]
+    cs += [edge_in_case(*e, dt, tap) for e in EDGE_IN for dt in (f16, f32t) for tap in (False, True)]
+    cs += [edge_out_case(*e, dt) for e in EDGE_OUT for dt in (f16, f32t)]
+    cs += [group_norm_case(**k) for k in GN_CASES]
+    cs += [layer_norm_case(*s) for s in LN_CASES]
+    cs += [attention_case(*s) for s in SELF_ATTN]
+    cs += [attention_case(3, 40, 320, lk=lk, kv_div=div) for lk, div in CROSS_ATTN]
+    cs += [attention_case(1, l, c, heads=1) for l, c in WIDE_ATTN]
+    cs += [sparse_causal_case(*s) for s in SPARSE_CAUSAL]
+    cs += [temporal_attention_case(*sh, False) for sh in TATTN_SHAPES] + [temporal_attention_case(1, 17, 5, 256, False, plain=True)]
+    cs += [geglu_mlp_case(M, False) for M in (1, 129)] + [cross_block_case(*sh, False) for sh in CROSS_BLOCKS]
+    cs += [temporal_block_case(1, 1, False), temporal_block_case(2, 13, False)]
+    cs += [proj_qkv_case(nb, dd) for nb in (1, 5) for dd in (16, 48)]
+    cs += [step_case(k, n) for k in STEP_KINDS for n in STEP_LENGTHS]
+    cs += [lora_case(*s, ip) for s in LORA_SHAPES for ip in (False, True)]
+    return cs

@@ -1,0 +1,195 @@
+"""-m gpu: the operators of lavie_amd/ops.py per element (tests/opcheck.py, cases in tests/opcases.py).  Each case runs twice on guarded operands —
+NaN-poisoned outputs between NaN bands, then finite-poisoned outputs with zero bands around the inputs — and must leave every
+band and every input intact, write every output element, give the same bits both times, and meet
+|got - ref64| <= 2^-11 |ref64| + c scale at every element ("Per-element operator checks").  No element is excluded."""
+import pytest
+import torch
+
+import opcases as C
+import opcheck as oc
+
+pytestmark = pytest.mark.gpu
+
+VARIANTS = {"auto": (0, 0), "row128-tiles": (1, 0), "split-k-3": (0, 3), "pingpong": (3, 0), "pingpong-split-k-2": (3, 2),
+            "ppx-persistent": (7, 0)}
+_forced = [0, 0]          # what the fixture set: a case that forces a kernel of its own restores this afterwards
+
+
+@pytest.fixture(scope="module", params=list(VARIANTS))
+def ops(request):
+    """The six kernel choices of test_gpu_ops.py: automatic, the 128-row GEMM forced, split-K = 3, the 160x320 ping-pong kernel alone
+    and with split-K = 2, the persistent ping-pong kernel.  Where a forced variant does not take a shape the planner falls back and
+    the case runs anyway."""
+    assert torch.cuda.is_available(), "gpu tests need a HIP device"
+    from lavie_amd import _lib, ops as o
+    lib = _lib.load()
+    tile, splits = VARIANTS[request.param]
+    lib.lavie_debug_force_tile(tile)
+    lib.lavie_debug_force_splits(splits)
+    _forced[:] = [tile, splits]
+    yield o
+    _forced[:] = [0, 0]
+    lib.lavie_debug_force_tile(0)
+    lib.lavie_debug_force_splits(0)
+
+
+def check(ops, case, refusal=None):
+    """refusal: the case has a shape its kernel is known not to take: the call must raise the RuntimeError with that text (and
+    run_guarded checks every band before it lets the error through).  Without it the call must run."""
+    if refusal is not None:
+        with pytest.raises(RuntimeError, match=refusal):
+            check(ops, case)
+        return
+    def fn(i, o):
+        if case.setup is not None:
+            with case.setup(tuple(_forced)):
+                case.run(ops, i, o)
+        else:
+            case.run(ops, i, o)
+    got = oc.run_guarded(fn, case.inputs, case.outputs, alias=case.alias, sync=torch.cuda.synchronize)
+    case.check(got)
+
+
+@pytest.mark.parametrize("opt", C.LINEAR_OPTIONS)
+@pytest.mark.parametrize("M,N,K", C.LINEAR_SHAPES)
+def test_linear(ops, M, N, K, opt):
+    check(ops, C.linear_case(M, N, K, opt))
+
+
+@pytest.mark.parametrize("M,C_", [(129, 64), (154, 320)])
+def test_geglu(ops, M, C_):
+    check(ops, C.geglu_case(M, C_))
+
+
+@pytest.mark.parametrize("M,N,K", [(154, 320, 320), (161, 192, 64)])
+def test_linear_lnfold(ops, M, N, K):
+    check(ops, C.lnfold_case(M, N, K))
+
+
+@pytest.mark.parametrize("kw", C.CONV_CASES, ids=lambda k: "-".join(f"{a}{b}" for a, b in k.items()))
+def test_conv3x3(ops, kw):
+    check(ops, C.conv_case(**kw))
+
+
+@pytest.mark.parametrize("force", [5, 3], ids=["pipelined-loop", "pingpong-loop"])
+@pytest.mark.parametrize("kw", C.HALO_CASES, ids=lambda k: "-".join(f"{a}{b}" for a, b in k.items()))
+def test_conv3x3_halo_patch(ops, kw, force):
+    check(ops, C.conv_case(**kw, force=force))
+
+
+@pytest.mark.parametrize("n,c,h,w", C.PARITY_CASES)
+def test_upsample_conv3x3_parity(ops, n, c, h, w):
+    from lavie_amd import _lib
+    lib = _lib.load()
+    assert lib.lavie_upsample_conv3x3_supported(n, h, w, c) == 1
+    assert not any(lib.lavie_upsample_conv3x3_supported(n_, h_, w_, c_) for n_, c_, h_, w_ in C.PARITY_REFUSED)      # nothing smaller is taken
+    check(ops, C.conv_case(n=n, c1=c, cout=c, h=h, w=w, ups=1, parity=True))
+
+
+@pytest.mark.parametrize("taps", [3, 5])
+@pytest.mark.parametrize("b,cin,cout,f,d", C.TCONV_SHAPES)
+def test_temporal_conv(ops, b, cin, cout, f, d, taps):
+    check(ops, C.temporal_conv_case(b, cin, cout, f, d, taps))
+
+
+@pytest.mark.parametrize("tap", [False, True])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.float32], ids=["fp16", "fp32"])
+@pytest.mark.parametrize("n,cin,cout,h,w", C.EDGE_IN)
+def test_conv_edge_in(ops, n, cin, cout, h, w, dtype, tap):
+    check(ops, C.edge_in_case(n, cin, cout, h, w, dtype, tap))
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.float32], ids=["fp16", "fp32"])
+@pytest.mark.parametrize("n,cin,cout,h,w", C.EDGE_OUT)
+def test_conv_edge_out(ops, n, cin, cout, h, w, dtype):
+    check(ops, C.edge_out_case(n, cin, cout, h, w, dtype))
+
+
+@pytest.mark.parametrize("kw", C.GN_CASES, ids=lambda k: "-".join(f"{a}{b}" for a, b in k.items()))
+def test_group_norm(ops, kw):
+    check(ops, C.group_norm_case(**kw))
+
+
+@pytest.mark.parametrize("M,C_,offset", C.LN_CASES)
+def test_layer_norm(ops, M, C_, offset):
+    check(ops, C.layer_norm_case(M, C_, offset))
+
+
+@pytest.mark.parametrize("nb,l,c", C.SELF_ATTN)
+def test_self_attention(ops, nb, l, c):
+    check(ops, C.attention_case(nb, l, c))
+
+
+@pytest.mark.parametrize("lk,div", C.CROSS_ATTN)
+def test_cross_attention(ops, lk, div):
+    check(ops, C.attention_case(3, 40, 320, lk=lk, kv_div=div))
+
+
+@pytest.mark.parametrize("l,c", C.WIDE_ATTN)
+def test_wide_head_attention(ops, l, c):
+    check(ops, C.attention_case(1, l, c, heads=1))
+
+
+@pytest.mark.parametrize("frames,d", C.SPARSE_CAUSAL)
+def test_sparse_causal_attention(ops, frames, d):
+    check(ops, C.sparse_causal_case(frames, d))
+
+
+@pytest.mark.parametrize("tiled", [False, True], ids=["streaming", "tiled"])
+@pytest.mark.parametrize("b,f,d,c", C.TATTN_SHAPES)
+def test_temporal_attention(ops, b, f, d, c, tiled):
+    check(ops, C.temporal_attention_case(b, f, d, c, tiled))
+
+
+@pytest.mark.parametrize("tiled", [False, True], ids=["streaming", "tiled"])
+def test_temporal_attention_plain(ops, tiled):
+    check(ops, C.temporal_attention_case(1, 17, 5, 256, tiled, plain=True))
+
+
+# the row-resident fused blocks: the smallest shapes their predicates take and one past a tile, out of place and with y aliasing
+# x; a shape a predicate does not take (rows per video / frame that are no multiple of the 16-token tile) must be refused with the
+# kernel's own message and nothing touched
+@pytest.mark.parametrize("in_place", [False, True])
+@pytest.mark.parametrize("M", [1, 129])
+def test_geglu_mlp(ops, M, in_place):
+    check(ops, C.geglu_mlp_case(M, in_place))
+
+
+@pytest.mark.parametrize("in_place", [False, True])
+@pytest.mark.parametrize("B,D", [(1, 1), (2, 13)])
+def test_temporal_block(ops, B, D, in_place):
+    check(ops, C.temporal_block_case(B, D, in_place))
+
+
+@pytest.mark.parametrize("in_place", [False, True])
+@pytest.mark.parametrize("B,P,L", C.CROSS_BLOCKS)
+def test_cross_block(ops, B, P, L, in_place):
+    check(ops, C.cross_block_case(B, P, L, in_place))
+
+
+@pytest.mark.parametrize("B,P,L", C.CROSS_REFUSED)
+def test_cross_block_refuses_ragged_videos(ops, B, P, L):
+    check(ops, C.cross_block_case(B, P, L, False), refusal="rows_per_batch=1 is not built")
+
+
+@pytest.mark.parametrize("D", [16, 48])
+@pytest.mark.parametrize("NB", [1, 5])
+def test_proj_qkv(ops, NB, D):
+    check(ops, C.proj_qkv_case(NB, D))
+
+
+@pytest.mark.parametrize("NB", [1, 5])
+def test_proj_qkv_refuses_ragged_frames(ops, NB):
+    check(ops, C.proj_qkv_case(NB, 1), refusal="1 rows per GroupNorm domain")
+
+
+@pytest.mark.parametrize("n", C.STEP_LENGTHS)
+@pytest.mark.parametrize("kind", C.STEP_KINDS)
+def test_sampler_steps(ops, kind, n):
+    check(ops, C.step_case(kind, n))
+
+
+@pytest.mark.parametrize("in_place", [False, True])
+@pytest.mark.parametrize("N,K,r", C.LORA_SHAPES)
+def test_lora_merge(ops, N, K, r, in_place):
+    check(ops, C.lora_case(N, K, r, in_place))

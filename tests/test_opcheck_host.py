@@ -1,0 +1,205 @@
+"""The per-element operator check (tests/opcheck.py) before a GPU is involved: the torch fp32 model of every kernel — fp16 roundings
+at the points counted in the kernel's source — meets the bound of its own case with zero offenders; injected defects are caught
+and located where the whole-tensor rel-L2 criterion of the older operator tests passes them; the guard-band and poison logic
+works on CPU tensors."""
+import pytest
+import torch
+
+import opcases as C
+import opcheck as oc
+from gpu_util import TOL_OP, rel_l2
+
+CASES = C.all_cases()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.name for c in CASES])
+def test_fp32_model_meets_its_bound(case):
+    """If this fails the rounding-point count n (or K_terms) of the case is wrong: fix the count, not the bound."""
+    case.check(case.model(), label="model ")
+
+
+# ------------------------------------------------------------------ injected defects
+def fails_at(case, got, where_text):
+    with pytest.raises(AssertionError) as e:
+        case.check({"y": got})
+    assert where_text in str(e.value), str(e.value)
+    assert rel_l2(got, case.ref["y"][0]) < TOL_OP, "the whole-tensor criterion was expected to pass this defect"
+
+
+def ulps16(v, n):
+    """v moved by n fp16 units in the last place, away from zero"""
+    bits = v.reshape(1).clone().view(torch.int16)
+    return (bits + n).view(torch.float16)[0]
+
+
+def worst_ref(case):
+    return int(case.ref["y"][0].abs().reshape(-1).argmax())
+
+
+@pytest.fixture(scope="module")
+def gemm():
+    case = C.linear_case(120001, 64, 128, "bias_residual")      # tall enough for the old criterion to miss one row
+    return case, case.model()["y"]
+
+
+def test_gemm_one_element_off_by_4_ulps(gemm):
+    case, y = gemm
+    i = worst_ref(case)
+    bad = y.clone()
+    bad.view(-1)[i] = ulps16(bad.view(-1)[i], 4)
+    fails_at(case, bad, "1 of %d elements" % y.numel())
+    fails_at(case, bad, "(row %d, column %d)" % divmod(i, 64))
+
+
+def test_gemm_last_row_without_bias(gemm):
+    case, y = gemm
+    i = case.inputs
+    bad = y.clone()
+    bad[-1] = (i["a"][-1].float() @ i["w"].float().t() + i["r"][-1].float()).half()
+    fails_at(case, bad, "(row 120000, column")
+
+
+def test_gemm_dropped_k_tile(gemm):
+    """the second 64-wide K-tile missing from the four columns one lane holds, in one row"""
+    case, y = gemm
+    i = case.inputs
+    row, cols = 77777, slice(20, 24)
+    bad = y.clone()
+    bad[row, cols] = (i["a"][row, :64].float() @ i["w"][cols, :64].float().t() + i["bias"][cols] + i["r"][row, cols].float()).half()
+    fails_at(case, bad, "(row 77777, column 2")
+
+
+@pytest.fixture(scope="module")
+def conv():
+    case = C.conv_case(n=1, c1=64, cout=64, h=200, w=200)
+    return case, case.model()["y"]
+
+
+def test_conv_one_element_off_by_4_ulps(conv):
+    case, y = conv
+    i = worst_ref(case)
+    bad = y.clone()
+    bad.view(-1)[i] = ulps16(bad.view(-1)[i], 4)
+    p, ch = divmod(i, 64)
+    fails_at(case, bad, "(frame 0, y %d, x %d, channel %d)" % (p // 200, p % 200, ch))
+
+
+def test_conv_corner_tap_from_wrong_neighbour(conv):
+    """at pixel (0, 0) the tap (dy 0, dx +1) reads pixel (1, 1) instead of (0, 1)"""
+    case, y = conv
+    x, wt = case.inputs["x1"].float(), case.inputs["wt"].float()
+    tap = wt[:, :, 1, 2]
+    bad = y.clone()
+    bad[0] = (y[0].float() - tap @ x[1] + tap @ x[200 + 1]).half()
+    fails_at(case, bad, "(frame 0, y 0, x 0, channel")
+    with pytest.raises(AssertionError, match=":border"):           # and the border region on its own names it too
+        oc.assert_elementwise(bad, *case.ref["y"], case.c, where=case.where, label="x:border", mask=case.regions["border"])
+
+
+def test_attention_one_element_off_by_4_ulps():
+    case = C.attention_case(1, 1, 256)
+    y = case.model()["y"]
+    i = worst_ref(case)
+    bad = y.clone()
+    bad.view(-1)[i] = ulps16(bad.view(-1)[i], 4)
+    fails_at(case, bad, "(token 0, head %d, dim %d)" % divmod(i, 32))
+
+
+def test_attention_one_dropped_key():
+    """query 5 of head 3 never sees the last key (a mask wrong for one key of the ragged last tile); host-only shape, long
+    enough for the whole-tensor criterion to miss it"""
+    case = C.attention_case(2, 300, 1280)
+    bad = case.model()["y"].clone()
+    dh = 160
+    qkv = case.inputs["qkvw"].float()
+    q, k, v = qkv[:, :1280], qkv[:, 1288:2568], qkv[:, 2576:]
+    hs = slice(3 * dh, 4 * dh)
+    s = (q[5, hs] * dh ** -0.5) @ k[:, hs].t()
+    s = s[:300]
+    s[299] = -float("inf")
+    bad[5, hs] = (torch.softmax(s, 0) @ v[:300, hs]).half()
+    fails_at(case, bad, "(token 5, head 3, dim")
+
+
+# ------------------------------------------------------------------ bands and poison, on CPU tensors
+def test_guard_geometry_and_patterns():
+    for dtype, pattern in ((torch.float16, oc.NAN16), (torch.float32, oc.NAN32)):
+        g = oc.guarded((3, 5), dtype, fill="nan", device="cpu")
+        esz = g.t.element_size()
+        assert g.lo * esz >= 64 * 1024 and g.lo * esz % 512 == 0 and g.hi * esz >= 64 * 1024 and g.hi * esz % 512 == 0
+        assert g.t.is_contiguous() and g.t.shape == (3, 5) and g.t.isnan().all() and g.unwritten().numel() == 15
+        assert int(g.buf[0]) & (0xFFFF if esz == 2 else 0xFFFFFFFF) == pattern
+        g.check_bands()
+        g.poison("finite")
+        assert (g.t == torch.tensor(oc.SENTINEL, dtype=dtype)).all() and g.unwritten().numel() == 0
+    x = torch.arange(6, dtype=torch.float32).reshape(2, 3)
+    gi = oc.guarded_like(x, band="zero", device="cpu")
+    assert torch.equal(gi.t, x) and int(gi.buf[0]) == 0
+    gi.check_unchanged()
+    gi.t[1, 2] = 7
+    with pytest.raises(AssertionError, match="row 1, column 2"):
+        gi.check_unchanged("x")
+
+
+def test_band_damage_is_located():
+    g = oc.guarded((4, 8), torch.float16, device="cpu")
+    g.buf[g.lo + 32 + 3] = 0                     # three elements past the end: "row 4, column 3"
+    with pytest.raises(AssertionError, match=r"offset 35 .*row 4, column 3"):
+        g.check_bands("y")
+    g = oc.guarded((4, 8), torch.float16, device="cpu")
+    g.buf[g.lo - 2] = 0
+    with pytest.raises(AssertionError, match="offset -2 "):
+        g.check_bands("y")
+
+
+def run_cpu(fn, alias=None):
+    x = torch.arange(12, dtype=torch.float16).reshape(3, 4)
+    return oc.run_guarded(fn, {"x": x}, {"y": ((3, 4), torch.float16)}, alias=alias, device="cpu")
+
+
+def test_run_guarded_accepts_a_correct_op_and_an_in_place_one():
+    assert torch.equal(run_cpu(lambda i, o: o["y"].copy_(i["x"] * 2))["y"], torch.arange(12).reshape(3, 4) * 2.0)
+    assert torch.equal(run_cpu(lambda i, o: o["y"].mul_(2), alias={"y": "x"})["y"], torch.arange(12).reshape(3, 4) * 2.0)
+
+
+def test_run_guarded_catches_unwritten_rows_stray_stores_and_stray_reads():
+    with pytest.raises(AssertionError, match="4 elements never written, first at offset 8 .*row 2, column 0"):
+        run_cpu(lambda i, o: o["y"][:2].copy_(i["x"][:2]))
+
+    def store_past_the_end(i, o):
+        o["y"].copy_(i["x"])
+        torch.as_strided(o["y"], (13,), (1,))[12] = 1.0
+    with pytest.raises(AssertionError, match="y .*guard band damaged in 1 elements, first at offset 12 .*row 3, column 0"):
+        run_cpu(store_past_the_end)
+
+    def clobbers_its_input(i, o):
+        o["y"].copy_(i["x"])
+        i["x"][0, 1] = 9
+    with pytest.raises(AssertionError, match="x: input changed in 1 elements, first at offset 1 "):
+        run_cpu(clobbers_its_input)
+
+    def reads_past_the_input(i, o):            # a halo read that should have been masked: the result depends on the band
+        o["y"].copy_(i["x"])
+        past = torch.as_strided(i["x"], (13,), (1,))[12]
+        o["y"][2, 3] += 0.0 if past.isnan() else 1.0
+    with pytest.raises(AssertionError, match="depend on what surrounds the operands.*row 2, column 3"):
+        run_cpu(reads_past_the_input)
+
+    def accumulates_into_its_output(i, o):     # a split-K slab that was never zeroed
+        o["y"].add_(i["x"])
+    with pytest.raises(AssertionError):
+        run_cpu(accumulates_into_its_output)
+
+
+def test_assert_elementwise_reports_count_and_worst_and_rejects_nan():
+    ref = torch.ones(2, 3, dtype=torch.float64)
+    got = ref.clone().half()
+    oc.assert_elementwise(got, ref, ref, 0.0)
+    got[1, 2] = 1.01
+    got[0, 1] = 1.001
+    with pytest.raises(AssertionError, match=r"2 of 6 elements.*\(row 1, column 2\)"):
+        oc.assert_elementwise(got, ref, ref, 0.0, where=oc.loc_rows(3))
+    got = ref.clone().half()
+    got[0, 0] = float("nan")
+    with pytest.raises(AssertionError, match=r"1 of 6 elements.*\(row 0, column 0\)"):
+        oc.assert_elementwise(got, ref, ref, 1.0, where=oc.loc_rows(3))
