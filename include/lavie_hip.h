@@ -116,6 +116,24 @@ int lavie_pack_geglu_f16(const void* w, const void* bias_f16, void* w_out, float
  * W0 / out fp16 [N, K]; A fp32 [r, K] (lora_A / lora_down); B fp32 [N, r] (lora_B / lora_up).  fp32 accumulation with fmaf in
  * ascending j, one rounding, no atomics: deterministic.  1 <= r <= 128, K %% 8 == 0, W0 / out / A 16-byte aligned, finite scale. */
 int lavie_lora_merge_f16(const void* W0, const float* A, const float* B, void* out, int N, int K, int r, float scale, void* stream);
+/* Several adapters blended in one pass (additive in ABI 8).  A term with scale 0 is dropped from the list first.  With t_0 =
+ * float(W0[n, k]) and, for the remaining terms i = 1 .. T in list order, t_i = fmaf(scale_i, acc_i[n, k], t_{i-1}), where acc_i is the
+ * chain of the single merge (fmaf in ascending j over B_i, A_i): out[n, k] = fp16_rne(t_T), one conversion of the finished fp32 sum.
+ * W0 is read and out written once per element however many terms there are; no atomics; out may alias W0.  T = 0: out = W0.
+ * T = 1: the call is lavie_lora_merge_f16 with that term, so it gives that function's bits.  T >= 2: a further term with A = 0 or
+ * B = 0 has acc = +0 and leaves every t_i as it was, so it changes no bit; two runs give the same bits.  (Such a term next to exactly ONE
+ * other makes T = 2, and fp16_rne(t_1) may differ in the last bit, in about one element in 10^4, from what the single merge's own last
+ * step gives when the compiler fuses its fmaf with the conversion; with scale 0 instead it is dropped and the bits are the single's.)
+ * 1 <= n_terms <= LAVIE_LORA_MAX_TERMS; per term 1 <= r <= 128, A 16-byte aligned, finite scale; K %% 8 == 0, W0 / out 16-byte aligned.
+ * `terms` is host memory, read before the call returns. */
+#define LAVIE_LORA_MAX_TERMS 8
+typedef struct lavie_lora_term {
+    const float* A;     /* fp32 [r, K] device */
+    const float* B;     /* fp32 [N, r] device */
+    int r;
+    float scale;
+} lavie_lora_term;
+int lavie_lora_merge_multi_f16(const void* W0, const lavie_lora_term* terms, int n_terms, void* out, int N, int K, void* stream);
 
 /* Fused feed-forward sub-block (ABI 5): y = x + W2 (h * gelu(g)) + b2 with (h, g) = W1 LayerNorm(x) + b1 — the
  * `hidden_states = self.ff(self.norm3(hidden_states)) + hidden_states` line of BasicTransformerBlock
@@ -401,12 +419,27 @@ int lavie_unet_set_cfg_shared_input(lavie_unet_t h, int on);
  *     Synchronises `stream` before freeing the adapter's buffers.
  *   lora_set_scale: the global factor (diffusers' cross_attention_kwargs={"scale": s}), default 1; 0 gives the base weights exactly.
  *   lora_apply: merges every target of the blocks touched since the last apply, re-derives those blocks and, if a context is cached
- *     (lavie_unet_cache_context), recomputes its K / V from the same ctx tensor.  Nothing to do = no launch. */
+ *     (lavie_unet_cache_context), recomputes its K / V from the same ctx tensor.  Nothing to do = no launch.
+ * Several adapters at once: the registry has LAVIE_LORA_MAX_TERMS slots, each holding one adapter (its targets' A / B / r / scale)
+ * and one blend weight (default 1).  A target is served as
+ *     W = W0 + sum over slots (global_scale * weight_slot * scale_slot,target) * B A
+ * over the slots that hold an entry for the target, in ascending slot order, in ONE pass (lavie_lora_merge_multi_f16: fp32 sum, one
+ * rounding).  The factor of a term is computed in fp32, left to right, as (global_scale * weight) * scale; a slot whose factor is 0
+ * is not a term; with no terms the base copy goes back.  So the served weights depend on the registry's state only, never on the
+ * order of the calls that led to it.  lora_set / lora_clear above act on slot 0; the global scale multiplies every slot.
+ *   lora_set_slot / lora_clear_slot: lora_set / lora_clear for one slot, 0 <= slot < LAVIE_LORA_MAX_TERMS.  A target keeps one base
+ *     copy for all of its slots; it goes away, after the next apply has written the base back, when its last slot is cleared.
+ *   lora_set_slot_weight: the slot's blend weight (finite); 0 switches the adapter off and keeps it resident.  Marks the blocks in
+ *     which the slot has an entry; takes effect at the next apply. */
 int lavie_unet_lora_set(lavie_unet_t h, const char* name, const void* base_f16, const float* A, const float* B, int r, float scale,
                         void* stream);
 int lavie_unet_lora_clear(lavie_unet_t h, const char* name, void* stream);
 int lavie_unet_lora_set_scale(lavie_unet_t h, float scale);
 int lavie_unet_lora_apply(lavie_unet_t h, void* stream);
+int lavie_unet_lora_set_slot(lavie_unet_t h, int slot, const char* name, const void* base_f16, const float* A, const float* B, int r,
+                             float scale, void* stream);
+int lavie_unet_lora_clear_slot(lavie_unet_t h, int slot, const char* name, void* stream);
+int lavie_unet_lora_set_slot_weight(lavie_unet_t h, int slot, float weight);
 long long lavie_unet_weight_bytes(lavie_unet_t h);
 long long lavie_unet_workspace_bytes(lavie_unet_t h);
 /* sample [B, Cin, F, H, W] fp16 (NCFHW, as the reference passes it), timesteps [B] fp32,

@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("LAVIE_HIP_LIB") or os.path.join(_HERE, "liblavie_hip.
 ABI_VERSION = 8
 FUSED_DEFAULT = 0x137    # lavie_debug_fused_mask: bits 0, 1, 2, 4, 5, 8 (include/lavie_hip.h)
 MAX_LEVELS = 8
+LORA_MAX_TERMS = 8       # LAVIE_LORA_MAX_TERMS: adapters blended in one merge = slots of the engine's registry
 
 c_void_p, c_int, c_float, c_ll, c_char_p = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_char_p
 c_float_p = C.c_void_p      # fp32 device pointers are passed as raw addresses
@@ -26,6 +27,10 @@ class UNetConfigC(C.Structure):
         ("vsr_blocks", c_int), ("only_cross_attention", c_int * MAX_LEVELS),
         ("vsr_temporal_modules", c_int), ("num_class_embeds", c_int),
     ]
+
+
+class LoraTermC(C.Structure):         # lavie_lora_term
+    _fields_ = [("A", c_float_p), ("B", c_float_p), ("r", c_int), ("scale", c_float)]
 
 
 # name -> (restype, argtypes); every symbol declared in include/lavie_hip.h
@@ -52,6 +57,7 @@ SIGNATURES = {
     "lavie_pack_temporal_conv_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "lavie_pack_geglu_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_float_p, c_int, c_int, c_void_p]),
     "lavie_lora_merge_f16": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    "lavie_lora_merge_multi_f16": (c_int, [c_void_p, C.POINTER(LoraTermC), c_int, c_void_p, c_int, c_int, c_void_p]),
     "lavie_geglu_mlp_image_bytes": (c_ll, [c_int]),
     "lavie_geglu_mlp_bias_floats": (c_ll, [c_int]),
     "lavie_pack_geglu_mlp_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float_p, c_void_p]),
@@ -125,6 +131,9 @@ SIGNATURES = {
     "lavie_unet_lora_clear": (c_int, [c_void_p, c_char_p, c_void_p]),
     "lavie_unet_lora_set_scale": (c_int, [c_void_p, c_float]),
     "lavie_unet_lora_apply": (c_int, [c_void_p, c_void_p]),
+    "lavie_unet_lora_set_slot": (c_int, [c_void_p, c_int, c_char_p, c_void_p, c_float_p, c_float_p, c_int, c_float, c_void_p]),
+    "lavie_unet_lora_clear_slot": (c_int, [c_void_p, c_int, c_char_p, c_void_p]),
+    "lavie_unet_lora_set_slot_weight": (c_int, [c_void_p, c_int, c_float]),
     "lavie_unet_set_cfg_shared_input": (c_int, [c_void_p, c_int]),
     "lavie_unet_weight_bytes": (c_ll, [c_void_p]),
     "lavie_unet_workspace_bytes": (c_ll, [c_void_p]),

@@ -73,6 +73,14 @@ int lavie_linear_lnfold_f16(const void* A, const void* Wf, const float* bias, co
 int lavie_lora_merge_f16(const void* W0, const float* A, const float* B, void* out, int N, int K, int r, float scale, void* stream) {
     return launch_lora_merge(H(W0), A, B, H(out), N, K, r, scale, S(stream));
 }
+static_assert(kLoraMaxTerms == LAVIE_LORA_MAX_TERMS, "lavie_lora_term list length");
+int lavie_lora_merge_multi_f16(const void* W0, const lavie_lora_term* terms, int n_terms, void* out, int N, int K, void* stream) {
+    LAVIE_CHECK(terms, "lora_merge_multi: null term list");
+    LAVIE_CHECK(n_terms >= 1 && n_terms <= kLoraMaxTerms, "lora_merge_multi: %d terms outside 1..%d", n_terms, kLoraMaxTerms);
+    LoraTerm t[kLoraMaxTerms];
+    for (int i = 0; i < n_terms; ++i) t[i] = LoraTerm{terms[i].A, terms[i].B, terms[i].r, terms[i].scale};
+    return launch_lora_merge_multi(H(W0), t, n_terms, H(out), N, K, S(stream));
+}
 
 long long lavie_geglu_mlp_image_bytes(int C) { return geglu_mlp_supported(C) ? (long long)geglu_mlp_image_bytes(C) : 0; }
 long long lavie_geglu_mlp_bias_floats(int C) { return geglu_mlp_supported(C) ? (long long)geglu_mlp_bias_floats(C) : 0; }
@@ -468,6 +476,19 @@ int lavie_unet_lora_set(lavie_unet_t h, const char* name, const void* base_f16, 
 int lavie_unet_lora_clear(lavie_unet_t h, const char* name, void* stream) {
     LAVIE_CHECK(h, "lora_clear: null handle");
     return h->net.lora_clear(name, S(stream));
+}
+int lavie_unet_lora_set_slot(lavie_unet_t h, int slot, const char* name, const void* base_f16, const float* A, const float* B, int r,
+                             float scale, void* stream) {
+    LAVIE_CHECK(h, "lora_set_slot: null handle");
+    return h->net.lora_set_slot(slot, name, H(base_f16), A, B, r, scale, S(stream));
+}
+int lavie_unet_lora_clear_slot(lavie_unet_t h, int slot, const char* name, void* stream) {
+    LAVIE_CHECK(h, "lora_clear_slot: null handle");
+    return h->net.lora_clear_slot(slot, name, S(stream));
+}
+int lavie_unet_lora_set_slot_weight(lavie_unet_t h, int slot, float weight) {
+    LAVIE_CHECK(h, "lora_set_slot_weight: null handle");
+    return h->net.lora_set_slot_weight(slot, weight);
 }
 int lavie_unet_lora_set_scale(lavie_unet_t h, float scale) {
     LAVIE_CHECK(h, "lora_set_scale: null handle");

@@ -101,7 +101,10 @@ UNet::~UNet() {
     if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
     if (kv_block_) (void)hipFree(kv_block_);
     if (xbl_block_) (void)hipFree(xbl_block_);
-    for (auto& kv : lora_) lora_free(kv.second, true);
+    for (auto& kv : lora_) {
+        for (LoraSlot& s : kv.second.slot) lora_free(s);
+        if (kv.second.base) (void)hipFree(kv.second.base);
+    }
 }
 
 int UNet::validate_config() {
@@ -1498,14 +1501,20 @@ int UNet::lora_target(const char* name, int* ti, int* attn, int* proj) const {
                 name, tname.c_str());
 }
 
-void UNet::lora_free(LoraEntry& e, bool base) {
-    if (e.A) (void)hipFree(e.A);
-    if (e.B) (void)hipFree(e.B);
-    e.A = e.B = nullptr;
-    if (base && e.base) { (void)hipFree(e.base); e.base = nullptr; }
+void UNet::lora_free(LoraSlot& s) {
+    if (s.A) (void)hipFree(s.A);
+    if (s.B) (void)hipFree(s.B);
+    s.A = s.B = nullptr;
+    s.r = 0;
 }
 
 int UNet::lora_set(const char* name, const half_t* base, const float* A, const float* B, int r, float scale, hipStream_t stream) {
+    return lora_set_slot(0, name, base, A, B, r, scale, stream);
+}
+
+int UNet::lora_set_slot(int slot, const char* name, const half_t* base, const float* A, const float* B, int r, float scale,
+                        hipStream_t stream) {
+    LAVIE_CHECK(slot >= 0 && slot < kLoraMaxTerms, "lora_set: slot %d outside 0..%d", slot, kLoraMaxTerms - 1);
     LAVIE_CHECK(name && base && A && B, "lora_set: null argument");
     LAVIE_CHECK(r >= 1 && r <= kLoraMaxRank, "lora_set: rank %d outside 1..%d", r, kLoraMaxRank);
     LAVIE_CHECK(__builtin_isfinite(scale), "lora_set: scale %g is not finite", (double)scale);
@@ -1530,35 +1539,39 @@ int UNet::lora_set(const char* name, const half_t* base, const float* A, const f
         found = lora_.emplace(name, e).first;
     }
     LoraEntry& e = found->second;
-    if (e.r != r) {
-        if (e.A || e.B) {       // an earlier apply may still read them
+    LoraSlot& s = e.slot[slot];
+    lora_dirty_[ti] = 1;        // from here on the entry may change; should an allocation below fail, the next apply still visits
+                                // the block and drops an entry that was left without a slot
+    if (s.r != r) {
+        if (s.A || s.B) {       // an earlier apply may still read them
             LAVIE_HIP(hipStreamSynchronize(stream));
-            lora_free(e, false);
+            lora_free(s);
         }
-        e.r = 0;
-        LAVIE_HIP(hipMalloc((void**)&e.A, (size_t)r * e.K * sizeof(float)));
-        LAVIE_HIP(hipMalloc((void**)&e.B, (size_t)e.N * r * sizeof(float)));
+        LAVIE_HIP(hipMalloc((void**)&s.A, (size_t)r * e.K * sizeof(float)));
+        LAVIE_HIP(hipMalloc((void**)&s.B, (size_t)e.N * r * sizeof(float)));
     }
+    // the base of a target is the same tensor whichever slot registers it: copying it again is idempotent
     LAVIE_HIP(hipMemcpyAsync(e.base, base, (size_t)e.N * e.K * sizeof(half_t), hipMemcpyDeviceToDevice, stream));
-    LAVIE_HIP(hipMemcpyAsync(e.A, A, (size_t)r * e.K * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    LAVIE_HIP(hipMemcpyAsync(e.B, B, (size_t)e.N * r * sizeof(float), hipMemcpyDeviceToDevice, stream));
-    e.r = r;
-    e.scale = scale;
-    lora_dirty_[ti] = 1;
+    LAVIE_HIP(hipMemcpyAsync(s.A, A, (size_t)r * e.K * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    LAVIE_HIP(hipMemcpyAsync(s.B, B, (size_t)e.N * r * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    s.r = r;
+    s.scale = scale;
     return 0;
 }
 
-int UNet::lora_clear(const char* name, hipStream_t stream) {
+int UNet::lora_clear(const char* name, hipStream_t stream) { return lora_clear_slot(0, name, stream); }
+
+int UNet::lora_clear_slot(int slot, const char* name, hipStream_t stream) {
+    LAVIE_CHECK(slot >= 0 && slot < kLoraMaxTerms, "lora_clear: slot %d outside 0..%d", slot, kLoraMaxTerms - 1);
     int ti = 0, attn = 0, proj = 0;
     if (name) RUN(lora_target(name, &ti, &attn, &proj));
     LAVIE_CHECK(finalized_, "lora_clear: call lavie_unet_finalize first");
     bool synced = false;
     for (auto& kv : lora_) {
         LoraEntry& e = kv.second;
-        if ((name && kv.first != name) || e.r == 0) continue;
+        if ((name && kv.first != name) || e.slot[slot].r == 0) continue;
         if (!synced) { LAVIE_HIP(hipStreamSynchronize(stream)); synced = true; }
-        lora_free(e, false);
-        e.r = 0;                // the base copy stays until the next apply has written it back
+        lora_free(e.slot[slot]);    // the base copy stays: with no slot left, until the next apply has written it back
         lora_dirty_[e.ti] = 1;
     }
     return 0;
@@ -1573,6 +1586,17 @@ int UNet::lora_set_scale(float scale) {
     return 0;
 }
 
+int UNet::lora_set_slot_weight(int slot, float weight) {
+    LAVIE_CHECK(slot >= 0 && slot < kLoraMaxTerms, "lora_set_slot_weight: slot %d outside 0..%d", slot, kLoraMaxTerms - 1);
+    LAVIE_CHECK(__builtin_isfinite(weight), "lora_set_slot_weight: weight %g is not finite", (double)weight);
+    LAVIE_CHECK(finalized_, "lora_set_slot_weight: call lavie_unet_finalize first");
+    if (weight == lora_weight_[slot]) return 0;
+    lora_weight_[slot] = weight;
+    for (const auto& kv : lora_)
+        if (kv.second.slot[slot].r) lora_dirty_[kv.second.ti] = 1;
+    return 0;
+}
+
 int UNet::lora_apply(hipStream_t stream) {
     LAVIE_CHECK(finalized_, "lora_apply: call lavie_unet_finalize first");
     bool any = false;
@@ -1582,17 +1606,31 @@ int UNet::lora_apply(hipStream_t stream) {
     for (auto& kv : lora_) {
         const LoraEntry& e = kv.second;
         if (!lora_dirty_[e.ti]) continue;
-        const float eff = lora_scale_ * e.scale;
-        if (e.r > 0 && eff != 0.f) RUN(launch_lora_merge(e.base, e.A, e.B, e.dst, e.N, e.K, e.r, eff, stream));
+        // the terms of this target: its slots in ascending order, factor (global * weight) * scale in fp32; a zero factor is no term
+        LoraTerm terms[kLoraMaxTerms];
+        int n = 0;
+        for (int i = 0; i < kLoraMaxTerms; ++i) {
+            const LoraSlot& s = e.slot[i];
+            if (s.r == 0) continue;
+            const float gw = lora_scale_ * lora_weight_[i];
+            const float eff = gw * s.scale;
+            if (eff != 0.f) terms[n++] = LoraTerm{s.A, s.B, s.r, eff};
+        }
+        if (n == 1) RUN(launch_lora_merge(e.base, terms[0].A, terms[0].B, e.dst, e.N, e.K, terms[0].r, terms[0].scale, stream));
+        else if (n > 1) RUN(launch_lora_merge_multi(e.base, terms, n, e.dst, e.N, e.K, stream));
         else LAVIE_HIP(hipMemcpyAsync(e.dst, e.base, (size_t)e.N * e.K * sizeof(half_t), hipMemcpyDeviceToDevice, stream));
-        drop = drop || e.r == 0;
+        drop = drop || e.empty();
     }
     for (size_t i = 0; i < transformers_.size(); ++i)
         if (lora_dirty_[i]) RUN(derive_transformer(transformers_[i], stream));
     if (drop) {                 // cleared entries: their base is back in place
         LAVIE_HIP(hipStreamSynchronize(stream));
         for (auto it = lora_.begin(); it != lora_.end();) {
-            if (it->second.r == 0) { lora_free(it->second, true); it = lora_.erase(it); }
+            if (it->second.empty()) {
+                for (LoraSlot& s : it->second.slot) lora_free(s);      // a buffer a failed registration left behind
+                (void)hipFree(it->second.base);
+                it = lora_.erase(it);
+            }
             else ++it;
         }
     }

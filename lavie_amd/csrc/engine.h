@@ -106,16 +106,24 @@ struct TemporalModuleW {
 struct FwdCtx;   // per-call state (engine.cpp), the call's Route (its switches, as one value) among it
 
 // One registered low-rank adapter target (lavie_unet_lora_*): the projection's rows inside the packed weights and what they are
-// rebuilt from.  Every buffer is the engine's own: the caller's base tensor is copied at registration.
+// rebuilt from: one base copy, and per registry slot the adapter that slot holds on this target.  Every buffer is the engine's own:
+// the caller's tensors are copied at registration.
+struct LoraSlot {
+    float* A = nullptr;                             // [r][K] fp32
+    float* B = nullptr;                             // [N][r] fp32
+    int r = 0;                                      // 0: the slot has no entry here
+    float scale = 1.f;                              // per-target scale (alpha / r); the factor is (global * slot weight) * this
+};
 struct LoraEntry {
     int ti = -1;                                    // transformer block
     half_t* dst = nullptr;                          // the projection's [N][K] rows inside wqkv1 / wq1 / wkv1 / o1 / wq2 / wkv2 / o2 / wqkvt / ot
     int N = 0, K = 0;
     half_t* base = nullptr;                         // copy of the base weight
-    float* A = nullptr;                             // [r][K] fp32
-    float* B = nullptr;                             // [N][r] fp32
-    int r = 0;                                      // 0: cleared, the next apply writes the base back and drops the entry
-    float scale = 1.f;                              // per-target scale (alpha / r); the effective scale is this * the global one
+    LoraSlot slot[kLoraMaxTerms];
+    bool empty() const {                            // no slot left: the next apply writes the base back and drops the entry
+        for (const LoraSlot& s : slot) if (s.r) return false;
+        return true;
+    }
 };
 
 class UNet {
@@ -152,6 +160,12 @@ public:
     int lora_set(const char* name, const half_t* base, const float* A, const float* B, int r, float scale, hipStream_t stream);
     int lora_clear(const char* name, hipStream_t stream);
     int lora_set_scale(float scale);
+    // The same per registry slot (set / clear above are slot 0) and the slot's blend weight: apply serves, per target, the slots that
+    // hold an entry for it in ascending order in one merge, W0 + sum (global * weight_slot * scale) B A
+    int lora_set_slot(int slot, const char* name, const half_t* base, const float* A, const float* B, int r, float scale,
+                      hipStream_t stream);
+    int lora_clear_slot(int slot, const char* name, hipStream_t stream);
+    int lora_set_slot_weight(int slot, float weight);
     int lora_apply(hipStream_t stream);
 
 private:
@@ -163,7 +177,7 @@ private:
     int pack_transformer(TransformerW* t, hipStream_t s);
     int derive_transformer(const TransformerW& t, hipStream_t s);
     int lora_target(const char* name, int* ti, int* attn, int* proj) const;
-    void lora_free(LoraEntry& e, bool base);
+    void lora_free(LoraSlot& s);
     int pack_temporal_res(const std::string& prefix, int C, int taps1, TemporalResW* out, hipStream_t s);
     int run_temporal_res(FwdCtx& c, const TemporalResW& r, const half_t* x, half_t* y, int C, int D, const float* bias2, int ldb2,
                          const GnColStat* x_cs = nullptr, float* y_csbuf = nullptr, GnColStat* y_cs = nullptr);
@@ -251,6 +265,7 @@ private:
     // low-rank adapter registry (lora_*), ordered by name so apply enqueues the same sequence every time
     std::map<std::string, LoraEntry> lora_;
     float lora_scale_ = 1.f;                        // global adapter scale
+    float lora_weight_[kLoraMaxTerms] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};    // per-slot blend weight
     std::vector<char> lora_dirty_;                  // per transformer: touched since the last apply
     // spatial size of the running call (set by prepare()/forward() before run())
     int prep_H_ = 0, prep_W_ = 0;

@@ -121,6 +121,58 @@ static void run_model(const lavie_unet_config& cfg, int B, int F, int H, int W, 
         REQUIRE(lavie_debug_force_tile(0) == 0);
         REQUIRE(launches() == def);
     }
+    {   // the adapter registry's slots on two square targets: two adapters of different rank share one target and one base copy, a
+        // re-weight, a slot replaced by another rank, slots cleared one by one (the entry and its base go with the last), the
+        // refusals; exactly sized buffers, so an over-long copy or a leaked / twice-freed slot is the sanitizers' to find
+        std::string tq, to;
+        long long nq = 0;
+        for (int i = 0; i < n; ++i) {
+            const char* name = nullptr;
+            long long numel = 0;
+            REQUIRE(lavie_unet_param_info(h, i, &name, &numel) == 0);
+            const std::string s = name;
+            const auto ends = [&](const char* e) { return s.size() > strlen(e) && s.compare(s.size() - strlen(e), strlen(e), e) == 0; };
+            if (tq.empty() && ends("attn1.to_q.weight")) { tq = s; nq = numel; }
+            if (to.empty() && ends("attn1.to_out.0.weight")) to = s;
+        }
+        REQUIRE(!tq.empty() && !to.empty());
+        int C = 1;
+        while ((long long)C * C < nq) ++C;
+        REQUIRE((long long)C * C == nq);
+        std::vector<unsigned short> w0((size_t)C * C);
+        std::vector<float> a16((size_t)16 * C), b16((size_t)C * 16), a3((size_t)3 * C), b3((size_t)C * 3);
+        const long b0 = lavie_hostcheck_launches();
+        REQUIRE(lavie_unet_lora_apply(h, nullptr) == 0 && lavie_hostcheck_launches() == b0);       // nothing to do: no launch
+        REQUIRE(lavie_unet_lora_set(h, tq.c_str(), w0.data(), a16.data(), b16.data(), 16, 1.f, nullptr) == 0);      // slot 0
+        REQUIRE(lavie_unet_lora_set_slot(h, 3, tq.c_str(), w0.data(), a3.data(), b3.data(), 3, 0.5f, nullptr) == 0);
+        REQUIRE(lavie_unet_lora_set_slot(h, 3, to.c_str(), w0.data(), a3.data(), b3.data(), 3, 0.5f, nullptr) == 0);
+        REQUIRE(lavie_unet_lora_set_slot_weight(h, 3, -0.5f) == 0);
+        REQUIRE(lavie_unet_lora_apply(h, nullptr) == 0);
+        const long per_apply = lavie_hostcheck_launches() - b0;
+        REQUIRE(per_apply >= 2);
+        REQUIRE(lavie_unet_lora_apply(h, nullptr) == 0 && lavie_hostcheck_launches() == b0 + per_apply);
+        REQUIRE(lavie_unet_lora_set_slot_weight(h, 3, -0.5f) == 0);                                  // unchanged: nothing dirty
+        REQUIRE(lavie_unet_lora_apply(h, nullptr) == 0 && lavie_hostcheck_launches() == b0 + per_apply);
+        REQUIRE(lavie_unet_lora_set_slot_weight(h, 5, 2.f) == 0);                                    // an empty slot: nothing dirty
+        REQUIRE(lavie_unet_lora_apply(h, nullptr) == 0 && lavie_hostcheck_launches() == b0 + per_apply);
+        REQUIRE(lavie_unet_lora_set_slot_weight(h, 3, 0.f) == 0);                                    // off, resident: one term on tq
+        REQUIRE(lavie_unet_lora_apply(h, nullptr) == 0 && lavie_hostcheck_launches() > b0 + per_apply);
+        REQUIRE(lavie_unet_lora_set_slot(h, 3, tq.c_str(), w0.data(), a16.data(), b16.data(), 16, 1.f, nullptr) == 0);   // another rank
+        REQUIRE(lavie_unet_lora_set_slot_weight(h, 3, 1.f) == 0);
+        REQUIRE(lavie_unet_lora_apply(h, nullptr) == 0);
+        REQUIRE(lavie_unet_lora_set_slot(h, -1, tq.c_str(), w0.data(), a3.data(), b3.data(), 3, 1.f, nullptr) != 0);
+        REQUIRE(lavie_unet_lora_set_slot(h, 8, tq.c_str(), w0.data(), a3.data(), b3.data(), 3, 1.f, nullptr) != 0);
+        REQUIRE(lavie_unet_lora_set_slot(h, 1, tq.c_str(), w0.data(), a3.data(), b3.data(), 129, 1.f, nullptr) != 0);
+        REQUIRE(lavie_unet_lora_set_slot(h, 1, "conv_in.weight", w0.data(), a3.data(), b3.data(), 3, 1.f, nullptr) != 0);
+        REQUIRE(lavie_unet_lora_set_slot_weight(h, 8, 1.f) != 0 && lavie_unet_lora_set_slot_weight(h, 1, __builtin_nanf("")) != 0);
+        REQUIRE(lavie_unet_lora_clear_slot(h, 8, nullptr, nullptr) != 0);
+        REQUIRE(lavie_unet_lora_clear(h, nullptr, nullptr) == 0);                                    // slot 0 only
+        REQUIRE(lavie_unet_lora_apply(h, nullptr) == 0);
+        REQUIRE(lavie_unet_lora_clear_slot(h, 3, tq.c_str(), nullptr) == 0);                         // tq's last slot: its entry goes
+        REQUIRE(lavie_unet_lora_apply(h, nullptr) == 0);
+        if (!labels) REQUIRE(lavie_unet_forward(h, x, t, ctx, y, B, F, H, W, 77, nullptr) == 0);
+        // slot 3 still holds `to`: the destructor frees what is left
+    }
     REQUIRE(lavie_unet_forward(h, x, t, ctx, y, B, F, H * 2, W * 2, 77, nullptr) != 0);    // larger than prepared: workspace refuses
     REQUIRE(lavie_unet_forward(h, nullptr, t, ctx, y, B, F, H, W, 77, nullptr) != 0);
     REQUIRE(lavie_unet_forward(h, x, t, ctx, y, 9, F, H, W, 77, nullptr) != 0);

@@ -176,6 +176,18 @@ int launch_cross_block_long(const half_t* att, const half_t* x, half_t* y, int M
 constexpr int kLoraMaxRank = 128;
 int launch_lora_merge(const half_t* W0, const float* A, const float* B, half_t* out, int N, int K, int r, float scale,
                       hipStream_t stream);
+// Several adapters in one pass: t = float(W0); t = fmaf(scale_i, (B_i A_i)[n, k], t) for the terms in list order, each B_i A_i by the
+// chain above; out = fp16_rne(t), a conversion of the finished fp32 sum.  A term with scale 0 is skipped; with none left out = W0, with
+// one left the call IS launch_lora_merge.  W0 read and out written once per element whatever n_terms is; same constraints per term;
+// out may alias W0
+constexpr int kLoraMaxTerms = 8;
+struct LoraTerm {
+    const float* A;     // [r, K]
+    const float* B;     // [N, r]
+    int r;
+    float scale;
+};
+int launch_lora_merge_multi(const half_t* W0, const LoraTerm* terms, int n_terms, half_t* out, int N, int K, hipStream_t stream);
 
 // host-only helper (no GPU): T5-style bucket of (query i, key j), attention.py:681-699
 void relpos_bucket_table(int F, int num_buckets, int max_distance, int* out);

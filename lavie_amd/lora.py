@@ -4,7 +4,7 @@ The fork fine-tunes the base UNet with a peft `LoraConfig(r=rank, lora_alpha=ran
 "to_out.0"])` (base/pipelines/fine_tuning.py:296-307) and saves the adapter with `save_lora_weights(..., safe_serialization=True)`
 (:689-698).  `target_modules` matches on the name suffix, so every attn1 / attn2 / attn_temp projection of every transformer block
 carries an adapter.  The engine serves it merged (`lavie_unet_lora_*`, `lavie_lora_merge_f16`): W = W0 + scale * B A with peft's
-`scaling = lora_alpha / r`.
+`scaling = lora_alpha / r`; up to `MAX_ADAPTERS` named adapters are blended in one fixed-order merge (`lavie_lora_merge_multi_f16`).
 
 `normalize_lora_state_dict` maps the spellings in use to `{target weight name: (A [r, K], B [N, r], alpha or None)}` and refuses,
 naming the key, what the engine could not serve exactly."""
@@ -18,6 +18,7 @@ import torch
 PREFIXES = ("base_model.model.", "unet.")
 ADAPTER_FILES = ("pytorch_lora_weights.safetensors", "adapter_model.safetensors", "pytorch_lora_weights.bin", "adapter_model.bin")
 MAX_RANK = 128
+MAX_ADAPTERS = 8       # LAVIE_LORA_MAX_TERMS: the engine registry's slots
 
 # <transformer>.transformer_blocks.0.<attn1 | attn2 | attn_temp | attn_temporal>.<to_q | to_k | to_v | to_out.0>
 _TARGET = re.compile(r"^.+\.transformer_blocks\.0\.(attn1|attn2|attn_temp|attn_temporal)\.(to_q|to_k|to_v|to_out\.0)$")
@@ -107,6 +108,37 @@ def normalize_lora_state_dict(sd: Mapping[str, torch.Tensor], model_shapes: Opti
         key = next(iter(alphas.values()))[0]
         raise ValueError(f"LoRA state dict: '{key}' is an alpha without lora matrices")
     return out
+
+
+_ADAPTER_KEY = re.compile(r"^.+\.lora_[AB]\.([^.]+)\.weight$")
+_ADAPTER_ALPHA = re.compile(r"^(.+\.alpha)\.([^.]+)$")
+DEFAULT_ADAPTER = "default"
+
+
+def split_adapters(sd: Mapping[str, torch.Tensor]) -> Dict[str, Dict[str, torch.Tensor]]:
+    """{adapter name: state dict} from a peft state dict that carries several adapters side by side
+    (`<module>.lora_A.<adapter>.weight` / `lora_B.<adapter>.weight`, any prefix): each value goes through
+    `normalize_lora_state_dict` on its own.  A per-adapter alpha is spelled `<module>.alpha.<adapter>` and comes out as
+    `<module>.alpha`.  Keys without an adapter segment (`lora_A.weight`, `lora.down.weight`, `<module>.alpha`, ...) go under
+    "default".  Adapters come out in the order of their first key; nothing is checked here."""
+    out: Dict[str, Dict[str, torch.Tensor]] = {}
+    for key, value in sd.items():
+        m = _ADAPTER_KEY.match(key)
+        if m:
+            out.setdefault(m.group(1), {})[key] = value
+            continue
+        m = _ADAPTER_ALPHA.match(key)
+        if m:
+            out.setdefault(m.group(2), {})[m.group(1)] = value
+            continue
+        out.setdefault(DEFAULT_ADAPTER, {})[key] = value
+    return out
+
+
+def blend_factor(global_scale: float, weight: float, scale: float) -> float:
+    """The factor the engine gives one adapter on one target: fp32, left to right, (global * weight) * scale."""
+    import numpy as np
+    return float(np.float32(np.float32(global_scale) * np.float32(weight)) * np.float32(scale))
 
 
 def target_scales(lora: LoraTensors, alpha: Optional[float] = None) -> Dict[str, float]:

@@ -602,3 +602,23 @@ def lora_merge(w0: torch.Tensor, a: torch.Tensor, b: torch.Tensor, scale: float 
     lib = _lib.load()
     _lib.check(lib.lavie_lora_merge_f16(_p(w0), _p(a), _p(b), _p(out), N, K, r, float(scale), _stream()), "lavie_lora_merge_f16")
     return out
+
+
+def lora_merge_multi(w0: torch.Tensor, terms, out: Optional[torch.Tensor] = None):
+    """fp16_rne(w0[N,K] + sum_i scale_i * b_i[N,r_i] @ a_i[r_i,K]) for `terms` = [(a, b, scale), ...] (1..8 of them, a / b fp32), in
+    one pass (lavie_lora_merge_multi_f16): fp32 sum in list order, each b_i a_i by lora_merge's chain, one rounding.  One term gives
+    lora_merge's bits; a term with scale 0 is skipped."""
+    _chk16(w0, out)
+    N, K = w0.shape
+    terms = list(terms)
+    arr = (_lib.LoraTermC * max(1, len(terms)))()
+    for i, (a, b, scale) in enumerate(terms):
+        _chk32(a, b)
+        r = a.shape[0]
+        if a.shape != (r, K) or b.shape != (N, r):
+            raise ValueError(f"lora_merge_multi: term {i}: w0 {tuple(w0.shape)}, a {tuple(a.shape)}, b {tuple(b.shape)} do not fit")
+        arr[i].A, arr[i].B, arr[i].r, arr[i].scale = a.data_ptr(), b.data_ptr(), r, float(scale)
+    out = _out(out, w0.shape, torch.float16, w0.device, "lora_merge_multi: out")
+    lib = _lib.load()
+    _lib.check(lib.lavie_lora_merge_multi_f16(_p(w0), arr, len(terms), _p(out), N, K, _stream()), "lavie_lora_merge_multi_f16")
+    return out

@@ -57,12 +57,27 @@ class VideoGenPipeline:
     # offers attention slicing and the pipeline VAE slicing / tiling (pipeline_videogen.py:174-204).  They trade speed for memory in
     # the stock attention (`_sliced_attention`, xformers) and the stock VAE; here attention is always the fused flash-style HIP
     # kernel (scores are never materialised) and 288 GB of HBM make the VAE knobs moot, so they are accepted and change nothing.
-    def load_lora_weights(self, sd_or_path, scale: float = 1.0, alpha=None):
+    def load_lora_weights(self, sd_or_path, scale: float = 1.0, alpha=None, adapter_name=None):
         """The fork's saved adapter (save_lora_weights: `unet.`-prefixed peft keys, fine_tuning.py:689-698) onto the UNet
-        (UNet3DConditionModel.load_lora)."""
-        self.unet.load_lora(sd_or_path, scale=scale, alpha=alpha)
+        (UNet3DConditionModel.load_lora).  Without `adapter_name` it replaces whatever is loaded; with one it is added to (or
+        replaced among) the named adapters, which set_adapters blends."""
+        self.unet.load_lora(sd_or_path, scale=scale, alpha=alpha, adapter_name=adapter_name)
+
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        """diffusers' set_adapters: the active adapters and their blend weights (UNet3DConditionModel.set_adapters)."""
+        self.unet.set_adapters(adapter_names, adapter_weights)
+
+    def delete_adapters(self, adapter_names):
+        self.unet.delete_adapters(adapter_names)
+
+    def get_list_adapters(self):
+        return {"unet": self.unet.get_list_adapters()}
+
+    def get_active_adapters(self):
+        return self.unet.get_active_adapters()
 
     def unload_lora_weights(self):
+        """Removes every adapter."""
         self.unet.unload_lora()
 
     def load_mapper(self, path_or_sd, num_heads: int = 12):

@@ -138,9 +138,11 @@ class UNet3DConditionModel(nn.Module):
         self._cached_ctx = None
         self._graph = False
         self._graph_io = {}
-        # the loaded adapter (load_lora): {target weight name: (A fp32 [r, K], B fp32 [N, r], per-target scale)} on the host, and
-        # the global scale; every engine build registers it again, only unload_lora() / fuse_lora() remove it
+        # the loaded adapters (load_lora), on the host: {target weight name: {adapter name: (A fp32 [r, K], B fp32 [N, r],
+        # per-target scale)}} ({} without one), per adapter its engine slot, blend weight and whether it is active (set_adapters),
+        # and the global scale; every engine build registers them again, only unload_lora() / delete_adapters() / fuse_lora() remove
         self._lora = {}
+        self._lora_adapters = {}
         self._lora_scale = 1.0
 
     def _vsr_config(self, only_cross_attention, use_linear_projection, levels: int) -> dict:
@@ -241,7 +243,9 @@ class UNet3DConditionModel(nn.Module):
                                f"lavie_unet_set_param({name})")
                 _lib.check(lib.lavie_unet_finalize(handle, stream), "lavie_unet_finalize")
                 if self._lora:
-                    self._lora_register(handle, stream)
+                    keep += self._lora_register(handle, stream)
+                    _lib.check(lib.lavie_unet_lora_set_scale(handle, float(self._lora_scale)), "lavie_unet_lora_set_scale")
+                    _lib.check(lib.lavie_unet_lora_apply(handle, stream), "lavie_unet_lora_apply")
                 torch.cuda.current_stream().synchronize()
             except Exception:
                 lib.lavie_unet_destroy(handle)
@@ -260,28 +264,79 @@ class UNet3DConditionModel(nn.Module):
         return self._ensure_engine()
 
     # ------------------------------------------------------------------ LoRA adapters (served merged: lavie_unet_lora_*)
-    def _lora_register(self, handle, stream) -> None:
-        """Registers self._lora on `handle` (base = the module's own weights) and applies it; the caller synchronises."""
+    def _lora_slots(self):
+        """[(adapter name, slot, weight the engine gets)] in ascending slot order = the order of the terms of the blend."""
+        return sorted(((n, st["slot"], st["weight"] if st["active"] else 0.0) for n, st in self._lora_adapters.items()),
+                      key=lambda e: e[1])
+
+    def _lora_names(self, names, what):
+        names = [names] if isinstance(names, str) else list(names)
+        for n in names:
+            if n not in self._lora_adapters:
+                raise ValueError(f"{what}: no adapter named {n!r} (loaded: {self.get_list_adapters()})")
+        if len(set(names)) != len(names):
+            raise ValueError(f"{what}: an adapter is named twice in {names}")
+        return names
+
+    def _lora_forget(self, name) -> None:
+        """Drops adapter `name` from the host-side state."""
+        for target in [t for t, per in self._lora.items() if name in per]:
+            del self._lora[target][name]
+            if not self._lora[target]:
+                del self._lora[target]
+        del self._lora_adapters[name]
+
+    def _lora_engine(self, fn) -> None:
+        """Runs fn(lib, handle, stream) on the built engine, if there is one, then applies and synchronises."""
+        handle = self.__dict__.get("_engine")
+        if not handle:
+            return
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            keep = fn(lib, handle, stream)       # device copies stay alive until the engine's copies of them have run
+            _lib.check(lib.lavie_unet_lora_set_scale(handle, float(self._lora_scale)), "lavie_unet_lora_set_scale")
+            _lib.check(lib.lavie_unet_lora_apply(handle, stream), "lavie_unet_lora_apply")
+            torch.cuda.current_stream().synchronize()
+            del keep
+
+    def _lora_register(self, handle, stream, only=None) -> list:
+        """Registers the adapters (all, or the one named `only`) in their slots on `handle` with base = the module's own weights
+        and sets the slots' weights; the caller applies and synchronises.  Returns the device tensors to keep alive until then."""
         lib = _lib.load()
         params = dict(self.named_parameters())
-        keep = []             # device copies stay alive until the engine's copies of them have run (the caller's sync)
-        for name, (a, b, s) in self._lora.items():
-            w = params[name].data.contiguous()
-            ad = a.to(self.device, torch.float32).contiguous()
-            bd = b.to(self.device, torch.float32).contiguous()
-            keep += [w, ad, bd]
-            _lib.check(lib.lavie_unet_lora_set(handle, name.encode(), ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(ad.data_ptr()),
-                                               ctypes.c_void_p(bd.data_ptr()), a.shape[0], float(s), stream),
-                       f"lavie_unet_lora_set({name})")
-        _lib.check(lib.lavie_unet_lora_set_scale(handle, float(self._lora_scale)), "lavie_unet_lora_set_scale")
-        _lib.check(lib.lavie_unet_lora_apply(handle, stream), "lavie_unet_lora_apply")
-        torch.cuda.current_stream().synchronize()
+        keep = []
+        for adapter, slot, weight in self._lora_slots():
+            if only is not None and adapter != only:
+                continue
+            for name, per in self._lora.items():
+                if adapter not in per:
+                    continue
+                a, b, s = per[adapter]
+                w = params[name].data.contiguous()
+                ad = a.to(self.device, torch.float32).contiguous()
+                bd = b.to(self.device, torch.float32).contiguous()
+                keep += [w, ad, bd]
+                _lib.check(lib.lavie_unet_lora_set_slot(handle, slot, name.encode(), ctypes.c_void_p(w.data_ptr()),
+                                                        ctypes.c_void_p(ad.data_ptr()), ctypes.c_void_p(bd.data_ptr()), a.shape[0],
+                                                        float(s), stream), f"lavie_unet_lora_set_slot({slot}, {name})")
+            _lib.check(lib.lavie_unet_lora_set_slot_weight(handle, slot, float(weight)), "lavie_unet_lora_set_slot_weight")
+        return keep
 
-    def load_lora(self, sd_or_path, scale: float = 1.0, alpha: Optional[float] = None) -> None:
+    @staticmethod
+    def _lora_clear_slots(lib, handle, stream, slots) -> None:
+        for slot in slots:
+            _lib.check(lib.lavie_unet_lora_clear_slot(handle, slot, None, stream), "lavie_unet_lora_clear_slot")
+            _lib.check(lib.lavie_unet_lora_set_slot_weight(handle, slot, 1.0), "lavie_unet_lora_set_slot_weight")
+
+    def load_lora(self, sd_or_path, scale: float = 1.0, alpha: Optional[float] = None, adapter_name: Optional[str] = None) -> None:
         """Loads a LoRA adapter (state dict, `.safetensors` / `.bin` / `.pt` file, or a directory holding
-        `pytorch_lora_weights.safetensors`) onto the to_q / to_k / to_v / to_out.0 projections, replacing any loaded one.
-        Per-target factor alpha / r (peft's scaling; 1.0 without alpha, the fork's lora_alpha = r), `alpha` overrides; `scale` is
-        the global strength (set_lora_scale).  The module parameters stay the base weights (fuse_lora() writes the merge in)."""
+        `pytorch_lora_weights.safetensors`) onto the to_q / to_k / to_v / to_out.0 projections.  Per-target factor alpha / r
+        (peft's scaling; 1.0 without alpha, the fork's lora_alpha = r), `alpha` overrides.
+        adapter_name=None: replaces every loaded adapter with this one; `scale` is the global strength (set_lora_scale).
+        With a name: adds the adapter, or replaces the one of that name, and keeps the others (up to 8 in all, blended in one merge in
+        the order of their slots: the lowest free one is taken); it is active and `scale` is its blend weight (set_adapters); the
+        global strength stays.  The module parameters stay the base weights (fuse_lora() writes the merge in)."""
         if not self._lora_supported:
             raise NotImplementedError(f"{type(self).__name__}: LoRA adapters are not supported on this model")
         cfg_alpha = None
@@ -295,19 +350,80 @@ class UNet3DConditionModel(nn.Module):
         scale = float(scale)
         if not math.isfinite(scale):
             raise ValueError(f"load_lora: scale {scale} is not finite")
-        new = {n: (a, b, scales[n]) for n, (a, b, _) in tensors.items()}
-        handle = self.__dict__.get("_engine")
-        self.__dict__["_lora"] = new
-        self.__dict__["_lora_scale"] = scale
-        if handle:
-            lib = _lib.load()
-            with torch.cuda.device(self.device):
-                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-                _lib.check(lib.lavie_unet_lora_clear(handle, None, stream), "lavie_unet_lora_clear")
-                self._lora_register(handle, stream)
+        if adapter_name is None:
+            name, slot, weight = _lora.DEFAULT_ADAPTER, 0, 1.0
+            stale = [st["slot"] for st in self._lora_adapters.values()]
+            self.__dict__["_lora"] = {}
+            self.__dict__["_lora_adapters"] = {}
+            self.__dict__["_lora_scale"] = scale
+        else:
+            name, weight = str(adapter_name), scale
+            if not name:
+                raise ValueError("load_lora: adapter_name is empty")
+            if name in self._lora_adapters:
+                slot = self._lora_adapters[name]["slot"]
+                stale = [slot]
+                self._lora_forget(name)
+            else:
+                if len(self._lora_adapters) >= _lora.MAX_ADAPTERS:
+                    raise ValueError(f"load_lora: {_lora.MAX_ADAPTERS} adapters are loaded already, the most the engine blends "
+                                     f"({self.get_list_adapters()}); delete one first")
+                used = {st["slot"] for st in self._lora_adapters.values()}
+                slot = min(i for i in range(_lora.MAX_ADAPTERS) if i not in used)
+                stale = []
+        self._lora_adapters[name] = {"slot": slot, "weight": weight, "active": True}
+        for n, (a, b, _) in tensors.items():
+            self._lora.setdefault(n, {})[name] = (a, b, scales[n])
+
+        def on_engine(lib, handle, stream):
+            self._lora_clear_slots(lib, handle, stream, stale)
+            return self._lora_register(handle, stream, only=name)
+        self._lora_engine(on_engine)
+
+    def set_adapters(self, names, weights=None) -> None:
+        """The active set of the loaded adapters and their blend weights (finite floats, default 1.0; one number goes to all):
+        W = W0 + sum (global scale * weight * alpha / r) B A over the active ones.  Loaded adapters that are not named stay resident
+        and contribute nothing."""
+        names = self._lora_names(names, "set_adapters")
+        if weights is None:
+            weights = [1.0] * len(names)
+        elif isinstance(weights, (int, float)):
+            weights = [weights] * len(names)
+        weights = [float(w) for w in weights]
+        if len(weights) != len(names):
+            raise ValueError(f"set_adapters: {len(names)} names, {len(weights)} weights")
+        for n, w in zip(names, weights):
+            if not math.isfinite(w):
+                raise ValueError(f"set_adapters: weight {w} of {n!r} is not finite")
+        for n, st in self._lora_adapters.items():
+            st["active"] = n in names
+        for n, w in zip(names, weights):
+            self._lora_adapters[n]["weight"] = w
+
+        def on_engine(lib, handle, stream):
+            for _, slot, weight in self._lora_slots():
+                _lib.check(lib.lavie_unet_lora_set_slot_weight(handle, slot, float(weight)), "lavie_unet_lora_set_slot_weight")
+        self._lora_engine(on_engine)
+
+    def delete_adapters(self, names) -> None:
+        """Removes the named adapters; the others keep their slots, weights and state."""
+        names = self._lora_names(names, "delete_adapters")
+        slots = [self._lora_adapters[n]["slot"] for n in names]
+        for n in names:
+            self._lora_forget(n)
+        self._lora_engine(lambda lib, handle, stream: self._lora_clear_slots(lib, handle, stream, slots))
+
+    def get_list_adapters(self) -> list:
+        """Names of the loaded adapters, in blend (slot) order."""
+        return [n for n, _, _ in self._lora_slots()]
+
+    def get_active_adapters(self) -> list:
+        """Names of the adapters that contribute, in blend (slot) order."""
+        return [n for n, _, _ in self._lora_slots() if self._lora_adapters[n]["active"]]
 
     def set_lora_scale(self, scale: float) -> None:
-        """Global adapter strength (diffusers' cross_attention_kwargs={"scale": s}); 0 gives the base model's outputs exactly."""
+        """Global adapter strength over the whole blend (diffusers' cross_attention_kwargs={"scale": s}); 0 gives the base model's
+        outputs exactly."""
         scale = float(scale)
         if not math.isfinite(scale):
             raise ValueError(f"set_lora_scale: scale {scale} is not finite")
@@ -325,36 +441,34 @@ class UNet3DConditionModel(nn.Module):
         return self._lora_scale
 
     def unload_lora(self) -> None:
-        """Removes the adapter: the engine goes back to the base weights (bit-identical to a model that never had one)."""
+        """Removes every adapter: the engine goes back to the base weights (bit-identical to a model that never had one)."""
+        slots = [st["slot"] for st in self._lora_adapters.values()]
         self.__dict__["_lora"] = {}
+        self.__dict__["_lora_adapters"] = {}
         self.__dict__["_lora_scale"] = 1.0
-        handle = self.__dict__.get("_engine")
-        if handle:
-            lib = _lib.load()
-            with torch.cuda.device(self.device):
-                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-                _lib.check(lib.lavie_unet_lora_clear(handle, None, stream), "lavie_unet_lora_clear")
-                _lib.check(lib.lavie_unet_lora_set_scale(handle, 1.0), "lavie_unet_lora_set_scale")
-                _lib.check(lib.lavie_unet_lora_apply(handle, stream), "lavie_unet_lora_apply")
+        self._lora_engine(lambda lib, handle, stream: self._lora_clear_slots(lib, handle, stream, sorted(set(slots + [0]))))
 
     @torch.no_grad()
     def fuse_lora(self) -> None:
-        """Writes the merged weights the engine serves (lavie_lora_merge_f16, the same kernel and inputs) into the module
-        parameters and removes the adapter; the engine is rebuilt from them on next use."""
+        """Writes the merged weights the engine serves (the same kernels, inputs and fp32 factors: lavie_lora_merge_multi_f16 over
+        the adapters in slot order) into the module parameters and removes every adapter; the engine is rebuilt from them on next
+        use."""
         if not self._lora:
             return
         if self.device.type != "cuda" or self.dtype != torch.float16:
             raise RuntimeError("fuse_lora: the model must be on a HIP device in fp16")
         from . import ops
         params = dict(self.named_parameters())
+        order = self._lora_slots()
         with torch.cuda.device(self.device):
-            for name, (a, b, s) in self._lora.items():
+            for name, per in self._lora.items():
                 p = params[name]
-                eff = float(np.float32(self._lora_scale) * np.float32(s))        # the engine's fp32 product
-                merged = ops.lora_merge(p.data.contiguous(), a.to(self.device, torch.float32).contiguous(),
-                                        b.to(self.device, torch.float32).contiguous(), eff)
-                p.data.copy_(merged)
+                terms = [(per[ad][0].to(self.device, torch.float32).contiguous(), per[ad][1].to(self.device, torch.float32).contiguous(),
+                          _lora.blend_factor(self._lora_scale, weight, per[ad][2]))       # the engine's fp32 product
+                         for ad, _, weight in order if ad in per]
+                p.data.copy_(ops.lora_merge_multi(p.data.contiguous(), terms))
         self.__dict__["_lora"] = {}
+        self.__dict__["_lora_adapters"] = {}
         self.__dict__["_lora_scale"] = 1.0
         self._drop_engine()
 

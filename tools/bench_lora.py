@@ -4,9 +4,14 @@
 denoise loop runs it.  Times lavie_unet_lora_apply after the first registration, after a re-scale and after a clear,
 refresh_engine() (destroy + full re-pack, adapter registered again), and one forward with and without the adapter.
 Prints one JSON line (and writes it to --out).  Not the driver's bench; same measurement rules (device events, medians).
-Usage: python tools/bench_lora.py [--rank 16] [--iters 5] [--out profiles/lora_apply.json]"""
+With --adapters N [N ...] it measures the blend instead (profiles/lora_multi.json): the apply after a re-weight with N adapters of
+that rank on every target against the one-adapter apply of the same build, in one process in the order one / N / N / one, and one
+forward with the blend next to one without.
+Usage: python tools/bench_lora.py [--rank 16] [--iters 5] [--out profiles/lora_apply.json]
+       python tools/bench_lora.py --adapters 2 4 [--rank 16] [--iters 5] [--out profiles/lora_multi.json]"""
 import argparse
 import ctypes
+import itertools
 import json
 import os
 import statistics
@@ -41,7 +46,10 @@ def main():
     ap.add_argument("--rank", type=int, default=16)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--adapters", type=int, nargs="+", default=None, help="measure the blend of N adapters (one run per N)")
     a = ap.parse_args()
+    if a.adapters and not all(2 <= n <= lora.MAX_ADAPTERS for n in a.adapters):
+        ap.error(f"--adapters takes values in 2..{lora.MAX_ADAPTERS}")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     lib = _lib.load()
@@ -53,11 +61,15 @@ def main():
     del sd
     g = torch.Generator().manual_seed(1)
     targets = [n for n in shapes if lora.is_target(n)]
-    ad = {}
-    for n in targets:
-        rows, cols = shapes[n]
-        ad[f"unet.{n[:-7]}.lora_A.weight"] = torch.randn(a.rank, cols, generator=g) / cols ** 0.5
-        ad[f"unet.{n[:-7]}.lora_B.weight"] = torch.randn(rows, a.rank, generator=g) * 0.01
+
+    def make_adapter():
+        ad = {}
+        for n in targets:
+            rows, cols = shapes[n]
+            ad[f"unet.{n[:-7]}.lora_A.weight"] = torch.randn(a.rank, cols, generator=g) / cols ** 0.5
+            ad[f"unet.{n[:-7]}.lora_B.weight"] = torch.randn(rows, a.rank, generator=g) * 0.01
+        return ad
+    ad = make_adapter()
     target_params = sum(shapes[n][0] * shapes[n][1] for n in targets)
     pe, ne, lat = bench.synth_inputs(0, dev)
     ctx = torch.cat([ne, pe]).half().contiguous()
@@ -76,6 +88,44 @@ def main():
     res = {"metric": "lora_apply_ms", "rank": a.rank, "targets": len(targets), "target_params": target_params,
            "shape": "B2 F16 40x64 ctx77, context cached, CFG shared prefix", "iters": a.iters}
     res["forward_base_ms"] = timed(fwd, a.iters)[0]
+    if a.adapters:
+        res["metric"] = "lora_multi_apply_ms"
+        res["order"] = "one / N / N / one adapters loaded, per N; each figure the median of `iters` set_adapters calls (re-weight + apply + sync)"
+        ads = [ad] + [make_adapter() for _ in range(max(a.adapters) - 1)]
+        weights = itertools.cycle([0.5, 1.0])
+
+        def reweight():                                  # what a user does: every loaded adapter re-weighted, one apply
+            names = net.get_list_adapters()
+            net.set_adapters(names, [next(weights)] * len(names))
+        res["blend"] = {}
+        for n in a.adapters:
+            runs = {1: [], n: []}
+            fwd_ms = {}
+            for count in (1, n, n, 1):
+                have = net.get_list_adapters()
+                for i in range(len(have), count):
+                    net.load_lora(ads[i], adapter_name=f"a{i}")
+                if len(have) > count:
+                    net.delete_adapters(have[count:])
+                torch.cuda.synchronize()
+                reweight()                               # warm: the kernel of this term count has run
+                runs[count].append(timed(reweight, a.iters)[0])
+                net.set_adapters(net.get_list_adapters())
+                fwd_ms[count] = timed(fwd, a.iters)[0]
+            one, blend = statistics.mean(runs[1]), statistics.mean(runs[n])
+            res["blend"][str(n)] = {"apply_one_ms": runs[1], "apply_blend_ms": runs[n], "blend_over_one": blend / one,
+                                    "blend_over_n_single_applies": blend / (n * one), "forward_one_ms": fwd_ms[1],
+                                    "forward_blend_ms": fwd_ms[n]}
+            net.unload_lora()
+        net.cache_context(None)
+        net.set_cfg_shared_input(False)
+        res["device"] = torch.cuda.get_device_name(dev)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     # first registration (host copies -> device, lavie_unet_lora_set x targets) + apply, as load_lora does it
     t0 = time.perf_counter()
     net.load_lora(ad)
