@@ -107,39 +107,40 @@ int lavie_temporal_block_f16(const void* x, void* y, int B, int F, int D, int C,
                                  scale, eps, S(stream));
 }
 
+// the two cross-block families of the C ABI: one set of functions (rowfuse_cross.hip), the variant fixed by the entry point's name
 long long lavie_cross_block_image_bytes(int C, int heads) {
-    return cross_block_supported(C, heads, 1, 16) ? (long long)cross_block_image_bytes(C) : 0;
+    return cross_block_variant(C, heads, 1, 16) == CROSS_SHORT ? (long long)cross_block_image_bytes(CROSS_SHORT) : 0;
 }
 int lavie_pack_cross_block_f16(const void* wo1, const void* wq2, const void* wo2, int C, void* tmpl, void* stream) {
     LAVIE_CHECK(wo1 && wq2 && wo2 && tmpl, "pack_cross_block: null tensor");
-    return pack_cross_block(H(wo1), H(wq2), H(wo2), C, (half_t*)tmpl, S(stream));
+    return pack_cross_block(CROSS_SHORT, H(wo1), H(wq2), H(wo2), C, (half_t*)tmpl, S(stream));
 }
 int lavie_bind_cross_block_f16(const void* tmpl, const void* kv, int B, int ctx_len, int C, void* img, void* stream) {
     LAVIE_CHECK(tmpl && kv && img, "bind_cross_block: null tensor");
-    return bind_cross_block(H(tmpl), H(kv), B, ctx_len, C, (half_t*)img, S(stream));
+    return bind_cross_block(CROSS_SHORT, H(tmpl), H(kv), B, ctx_len, C, (half_t*)img, S(stream));
 }
 int lavie_cross_block_f16(const void* att, const void* x, void* y, int M, int rows_per_batch, int C, int heads, const void* img,
                           const float* bo1, const float* gamma, const float* beta, const float* bo2, int ctx_len, float scale,
                           float eps, void* stream) {
-    return launch_cross_block(H(att), H(x), (half_t*)y, M, rows_per_batch, C, heads, H(img), bo1, gamma, beta, bo2, ctx_len, scale, eps,
-                              S(stream));
+    return launch_cross_block(CROSS_SHORT, H(att), H(x), (half_t*)y, M, rows_per_batch, C, heads, H(img), bo1, gamma, beta, bo2, ctx_len,
+                              scale, eps, S(stream));
 }
 long long lavie_cross_block_long_image_bytes(int C, int heads) {
-    return cross_block_long_supported(C, heads, 81, 16) ? (long long)cross_block_long_image_bytes(C) : 0;
+    return cross_block_variant(C, heads, 81, 16) == CROSS_LONG ? (long long)cross_block_image_bytes(CROSS_LONG) : 0;
 }
 int lavie_pack_cross_block_long_f16(const void* wo1, const void* wq2, const void* wo2, int C, void* tmpl, void* stream) {
     LAVIE_CHECK(wo1 && wq2 && wo2 && tmpl, "pack_cross_block_long: null tensor");
-    return pack_cross_block_long(H(wo1), H(wq2), H(wo2), C, (half_t*)tmpl, S(stream));
+    return pack_cross_block(CROSS_LONG, H(wo1), H(wq2), H(wo2), C, (half_t*)tmpl, S(stream));
 }
 int lavie_bind_cross_block_long_f16(const void* tmpl, const void* kv, int B, int ctx_len, int C, void* img, void* stream) {
     LAVIE_CHECK(tmpl && kv && img, "bind_cross_block_long: null tensor");
-    return bind_cross_block_long(H(tmpl), H(kv), B, ctx_len, C, (half_t*)img, S(stream));
+    return bind_cross_block(CROSS_LONG, H(tmpl), H(kv), B, ctx_len, C, (half_t*)img, S(stream));
 }
 int lavie_cross_block_long_f16(const void* att, const void* x, void* y, int M, int rows_per_batch, int C, int heads, const void* img,
                                const float* bo1, const float* gamma, const float* beta, const float* bo2, int ctx_len, float scale,
                                float eps, void* stream) {
-    return launch_cross_block_long(H(att), H(x), (half_t*)y, M, rows_per_batch, C, heads, H(img), bo1, gamma, beta, bo2, ctx_len, scale,
-                                   eps, S(stream));
+    return launch_cross_block(CROSS_LONG, H(att), H(x), (half_t*)y, M, rows_per_batch, C, heads, H(img), bo1, gamma, beta, bo2, ctx_len,
+                              scale, eps, S(stream));
 }
 
 int lavie_conv3x3_f16(const void* x1, int C1, const void* x2, int C2, const void* sc1, int SC1, const void* sc2, int SC2,

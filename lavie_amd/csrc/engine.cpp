@@ -375,17 +375,18 @@ int UNet::pack_transformer(TransformerW* t, hipStream_t s) {
     static const char* const qkv[] = {"to_q", "to_k", "to_v"};
     static const char* const kv[] = {"to_k", "to_v"};
     static const char* const qonly[] = {"to_q"};
+    t->qkv1.N = t->attn1_cross ? C : 3 * C; t->q2.N = C; t->qkvt.N = 3 * C; t->ff1.N = 8 * C;
     if (t->attn1_cross) {
-        RUN(fuse(b + ".attn1", qonly, 1, C, &t->wq1));
+        RUN(fuse(b + ".attn1", qonly, 1, C, &t->qkv1.w));
         RUN(fuse(b + ".attn1", kv, 2, X, &t->wkv1));
     } else {
-        RUN(fuse(b + ".attn1", qkv, 3, C, &t->wqkv1));
+        RUN(fuse(b + ".attn1", qkv, 3, C, &t->qkv1.w));
     }
     RUN(pack_linear(b + ".attn1.to_out.0", C, C, true, &t->o1, s));
-    RUN(fuse(b + ".attn2", qonly, 1, C, &t->wq2));
+    RUN(fuse(b + ".attn2", qonly, 1, C, &t->q2.w));
     RUN(fuse(b + ".attn2", kv, 2, X, &t->wkv2));
     RUN(pack_linear(b + ".attn2.to_out.0", C, C, true, &t->o2, s));
-    RUN(fuse(b + ".attn_" + tname, qkv, 3, C, &t->wqkvt));
+    RUN(fuse(b + ".attn_" + tname, qkv, 3, C, &t->qkvt.w));
     RUN(pack_linear(b + ".attn_" + tname + ".to_out.0", C, C, true, &t->ot, s));
     if (!cfg_.temporal_plain) {
         const std::string key = b + ".attn_" + tname + ".time_rel_pos_bias.relative_attention_bias.weight";
@@ -401,7 +402,6 @@ int UNet::pack_transformer(TransformerW* t, hipStream_t s) {
         const half_t* w = given(b + ".ff.net.0.proj.weight");
         const half_t* bias = given(b + ".ff.net.0.proj.bias");
         NEED(w, b + ".ff.net.0.proj.weight"); NEED(bias, b + ".ff.net.0.proj.bias");
-        t->ff1.N = 8 * C; t->ff1.K = C;
         WALLOC(t->ff1.w, half_t, (size_t)8 * C * C);
         WALLOC(t->ff1.b, float, 8 * C);
         RUN(launch_pack_geglu_rows(w, t->ff1.w, 8 * C, C, s));
@@ -412,8 +412,8 @@ int UNet::pack_transformer(TransformerW* t, hipStream_t s) {
     // packed copies above, which lora_apply() rewrites in place and fills again through the same function
     if (!cfg_.temporal_plain && !cfg_.vsr_blocks && temporal_block_supported(C, cfg_.heads, 16, cfg_.rotary_dim))
         WALLOC(t->tb_img, half_t, temporal_block_image_bytes(C) / sizeof(half_t));     // fused temporal sub-block (clips of 16 frames)
-    if (!t->attn1_cross && !cfg_.vsr_blocks && cross_block_supported(C, cfg_.heads, 1, 16))
-        WALLOC(t->xb_tmpl, half_t, cross_block_image_bytes(C) / sizeof(half_t));       // fused text cross-attention sub-block
+    if (!t->attn1_cross && !cfg_.vsr_blocks && cross_block_variant(C, cfg_.heads, 1, 16) == CROSS_SHORT)
+        WALLOC(t->xb_tmpl[CROSS_SHORT], half_t, cross_block_image_bytes(CROSS_SHORT) / sizeof(half_t));       // fused text cross-attention sub-block
     if (!t->attn1_cross && !cfg_.vsr_blocks && proj_qkv_supported(C))                  // fused GroupNorm -> proj_in -> norm1 -> q|k|v
         WALLOC(t->pq_img, half_t, proj_qkv_image_bytes(C) / sizeof(half_t));
     if (geglu_mlp_supported(C)) {      // fused norm3 -> feed-forward -> residual kernel: weight image in MFMA-fragment order
@@ -427,51 +427,41 @@ int UNet::pack_transformer(TransformerW* t, hipStream_t s) {
     }
 
     // LayerNorm-folded projections (norm1 -> attn1 qkv, norm2 -> attn2 q, norm_temp -> attn_temp qkv, norm3 -> GEGLU)
-    auto fold_alloc = [&](int N, half_t** Wf, float** sv, float** bv) -> int {
-        WALLOC(*Wf, half_t, (size_t)N * C);
-        WALLOC(*sv, float, N);
-        WALLOC(*bv, float, N);
+    auto fold_alloc = [&](LnProj* p) -> int {
+        WALLOC(p->fw, half_t, (size_t)p->N * C);
+        WALLOC(p->fs, float, p->N);
+        WALLOC(p->fb, float, p->N);
         return 0;
     };
-    auto fold = [&](const half_t* W, const NormW& ln, const half_t* bias, int N, half_t** Wf, float** sv, float** bv) -> int {
-        RUN(fold_alloc(N, Wf, sv, bv));
-        return launch_ln_fold(W, ln.g, ln.b, bias, *Wf, *sv, *bv, N, C, s);
-    };
-    if (t->attn1_cross) RUN(fold_alloc(C, &t->f_q1, &t->s_q1, &t->b_q1));
-    else RUN(fold_alloc(3 * C, &t->f_qkv1, &t->s_qkv1, &t->b_qkv1));
-    RUN(fold_alloc(C, &t->f_q2, &t->s_q2, &t->b_q2));
-    RUN(fold_alloc(3 * C, &t->f_qkvt, &t->s_qkvt, &t->b_qkvt));
+    for (LnProj* p : {&t->qkv1, &t->q2, &t->qkvt}) RUN(fold_alloc(p));      // filled by derive_transformer()
     RUN(derive_transformer(*t, s));
     {
         // GEGLU: fold in the checkpoint's row order, then apply the value/gate interleave to W', s and b'
         const half_t* w = given(b + ".ff.net.0.proj.weight");
         const half_t* bias = given(b + ".ff.net.0.proj.bias");
-        half_t* tmpW; float* tmps; float* tmpb;
-        RUN(fold(w, t->ln3, bias, 8 * C, &tmpW, &tmps, &tmpb));
-        WALLOC(t->f_ff1, half_t, (size_t)8 * C * C);
-        WALLOC(t->s_ff1, float, 8 * C);
-        WALLOC(t->b_ff1, float, 8 * C);
-        RUN(launch_pack_geglu_rows(tmpW, t->f_ff1, 8 * C, C, s));
-        RUN(launch_pack_geglu_vec(tmps, t->s_ff1, 8 * C, s));
-        RUN(launch_pack_geglu_vec(tmpb, t->b_ff1, 8 * C, s));
+        LnProj tmp = t->ff1;
+        RUN(fold_alloc(&tmp));
+        RUN(launch_ln_fold(w, t->ln3.g, t->ln3.b, bias, tmp.fw, tmp.fs, tmp.fb, 8 * C, C, s));
+        RUN(fold_alloc(&t->ff1));
+        RUN(launch_pack_geglu_rows(tmp.fw, t->ff1.fw, 8 * C, C, s));
+        RUN(launch_pack_geglu_vec(tmp.fs, t->ff1.fs, 8 * C, s));
+        RUN(launch_pack_geglu_vec(tmp.fb, t->ff1.fb, 8 * C, s));
     }
     return 0;
 }
 
 // Everything of a transformer block that is computed from its attention projections, written into the allocations of
-// pack_transformer() from the packed copies (wqkv1 / wq1 / wkv1, o1, wq2, o2, wqkvt, ot, and proj_in for the GroupNorm -> q|k|v
+// pack_transformer() from the packed copies (qkv1, wkv1, o1, q2, o2, qkvt, ot, and proj_in for the GroupNorm -> q|k|v
 // image): finalize() and lora_apply() share it, so an in-place re-derivation is the fresh build's sequence of kernels.
 int UNet::derive_transformer(const TransformerW& t, hipStream_t s) {
     const int C = t.C;
     const size_t CC = (size_t)C * C;
-    if (t.tb_img) RUN(pack_temporal_block(t.wqkvt, t.wqkvt + CC, t.wqkvt + 2 * CC, t.ot.w, C, t.tb_img, s));
-    if (t.xb_tmpl) RUN(pack_cross_block(t.o1.w, t.wq2, t.o2.w, C, t.xb_tmpl, s));
-    if (t.xbl_tmpl) RUN(pack_cross_block_long(t.o1.w, t.wq2, t.o2.w, C, t.xbl_tmpl, s));
-    if (t.pq_img) RUN(pack_proj_qkv(t.pin.w, t.wqkv1, C, t.pq_img, s));      // wqkv1: to_q | to_k | to_v rows
-    if (t.attn1_cross) RUN(launch_ln_fold(t.wq1, t.ln1.g, t.ln1.b, nullptr, t.f_q1, t.s_q1, t.b_q1, C, C, s));
-    else RUN(launch_ln_fold(t.wqkv1, t.ln1.g, t.ln1.b, nullptr, t.f_qkv1, t.s_qkv1, t.b_qkv1, 3 * C, C, s));
-    RUN(launch_ln_fold(t.wq2, t.ln2.g, t.ln2.b, nullptr, t.f_q2, t.s_q2, t.b_q2, C, C, s));
-    RUN(launch_ln_fold(t.wqkvt, t.lnt.g, t.lnt.b, nullptr, t.f_qkvt, t.s_qkvt, t.b_qkvt, 3 * C, C, s));
+    if (t.tb_img) RUN(pack_temporal_block(t.qkvt.w, t.qkvt.w + CC, t.qkvt.w + 2 * CC, t.ot.w, C, t.tb_img, s));
+    for (int v = 0; v < kCrossVariants; ++v)
+        if (t.xb_tmpl[v]) RUN(pack_cross_block((CrossVariant)v, t.o1.w, t.q2.w, t.o2.w, C, t.xb_tmpl[v], s));
+    if (t.pq_img) RUN(pack_proj_qkv(t.pin.w, t.qkv1.w, C, t.pq_img, s));
+    for (const LnProj* p : {&t.qkv1, &t.q2, &t.qkvt})
+        RUN(launch_ln_fold(p->w, (t.*p->ln).g, (t.*p->ln).b, nullptr, p->fw, p->fs, p->fb, p->N, C, s));
     return 0;
 }
 
@@ -886,7 +876,7 @@ int UNet::run_resnet(FwdCtx& c, const ResnetW& r, const half_t* x1, int C1, cons
 struct BlockRoute {
     bool ff_first;          // interpolation block order: feed-forward -> temporal (base: temporal -> feed-forward)
     bool fused_head;        // GroupNorm -> proj_in -> norm1 -> q|k|v as one row-resident kernel (rowfuse_pin.hip)
-    enum { TEXT_GEMMS, TEXT_FUSED, TEXT_FUSED_LONG } text;      // attn1.to_out .. attn2.to_out + residual: GEMMs, or one kernel for <= 80 / 81..160 keys
+    CrossVariant text;      // attn1.to_out .. attn2.to_out + residual: GEMMs (CROSS_NONE), or one kernel, of this variant
     bool fused_t, fused_ff; // the temporal / feed-forward sub-block as one row-resident kernel (rowfuse.hip)
     bool fold_t, fold_ff;   // else: its first GEMM is LayerNorm-folded (false: an explicit LayerNorm in front of it)
     bool emit_pin, emit_o1, emit_o2, emit_ot, emit_ff2;        // proj_in, attn1 / attn2 / temporal to_out, ff2: row statistics from the epilogue
@@ -903,16 +893,14 @@ static BlockRoute block_route(const lavie_unet_config& cfg, const TransformerW& 
     b.fused_ff = t.ff_img != nullptr && (r.mask & 1) && (!b.ff_first || fold);
     b.fused_t = t.tb_img != nullptr && !b.ff_first && F == 16 && (r.mask & 2);
     // The fused text kernel emits no row statistics, so the sub-block behind it must be one that needs none
-    const bool long_ctx = cross_block_long_supported(t.C, heads, ctx_len, F * D);
-    const bool fused_x = t.xb_tmpl != nullptr && text_bound && (b.ff_first ? b.fused_ff : b.fused_t) && !t.attn1_cross && (r.mask & 4) &&
-                         (cross_block_supported(t.C, heads, ctx_len, F * D) || long_ctx);
-    b.text = !fused_x ? BlockRoute::TEXT_GEMMS : long_ctx ? BlockRoute::TEXT_FUSED_LONG : BlockRoute::TEXT_FUSED;
+    const bool fused_x = t.xb_tmpl[CROSS_SHORT] != nullptr && text_bound && (b.ff_first ? b.fused_ff : b.fused_t) && !t.attn1_cross && (r.mask & 4);
+    b.text = fused_x ? cross_block_variant(t.C, heads, ctx_len, F * D) : CROSS_NONE;
     // A GEMM behind a LayerNorm is folded when its producer can emit the statistics: the fused temporal kernel cannot
     b.fold_t = fold && !b.fused_t;
     b.fold_ff = fold && !b.fused_ff && !b.fused_t;
     // THE emission rule: a producer emits row statistics exactly when the next consumer of the residual stream is a LayerNorm-folded
     // GEMM.  The consumers, in order: attn1 q(kv), attn2 q, then temporal q|k|v and ff1 in the block's order, then proj_out (no LayerNorm)
-    const bool gemms = b.text == BlockRoute::TEXT_GEMMS;
+    const bool gemms = b.text == CROSS_NONE;
     b.emit_pin = !b.fused_head && fold;
     b.emit_o1 = gemms && fold;
     b.emit_o2 = gemms && (b.ff_first ? b.fold_ff : b.fold_t);
@@ -964,6 +952,29 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
         rs.stats = rsm;
     }
     auto emit = [&](bool on) { return on ? &rs : nullptr; };
+    // THE projection behind a LayerNorm, `rows` rows of tx -> wide.  Folded: one GEMM on the raw rows that takes their statistics;
+    // otherwise the LayerNorm into `ln`, then the plain GEMM
+    auto ln_proj = [&](const LnProj& p, bool folded, int rows, int epilogue = EPI_LINEAR) -> int {
+        const int ldc = epilogue == EPI_GEGLU ? p.N / 2 : p.N;
+        if (folded) return linear(c, tx, C, p.fw, p.fb, p.N, C, nullptr, wide, ldc, rows, epilogue, &rs, p.fs);
+        LAUNCH(launch_layernorm(tx, (t.*p.ln).g, (t.*p.ln).b, ln, rows, C, 1e-5f, c.s));
+        return linear(c, ln, C, p.w, p.b, p.N, C, nullptr, wide, ldc, rows, epilogue);
+    };
+    // Text attention through GEMMs (attn2; attn1 of the VSR only_cross_attention levels): q of every token, K | V once per video,
+    // from the cache or computed here
+    auto text_attention = [&](const LnProj& q, const half_t* wkv, const std::vector<half_t*>& cache) -> int {
+        RUN(ln_proj(q, fold, T));
+        const half_t* kvc = kv2;
+        if (kv_cached) kvc = cache[ti];
+        else RUN(linear(c, ctx, X, wkv, nullptr, 2 * C, X, nullptr, kv2, 2 * C, c.B * c.ctx_len));
+        if (!c.dry) {
+            AttnParams a;
+            a.q = wide; a.ldq = C; a.k = kvc; a.ldk = 2 * C; a.v = kvc + C; a.ldv = 2 * C;
+            a.o = att; a.ldo = C; a.NBq = NI; a.Lq = D; a.Lk = c.ctx_len; a.heads = heads; a.dh = dh; a.kv_batch_div = c.F; a.scale = scale;
+            RUN(launch_attention(a, c.s));
+        }
+        return 0;
+    };
     if (br.fused_head) {
         // Round 4: the norm's statistics become per-(frame, channel) scale / shift pairs and nothing between x and (tx, qkv) touches memory
         LAUNCH(launch_group_norm(x, C, nullptr, 0, NIp, D, G, t.gn.g, t.gn.b, 1e-6f, false, c.gn_ws, nullptr, c.s, x_cs, nullptr, gn_ab));
@@ -977,31 +988,10 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
 
     if (t.attn1_cross) {
         // VSR only_cross_attention levels: attn1 attends to the text context (vsr/models/attention.py:558-561)
-        if (fold) {
-            RUN(linear(c, tx, C, t.f_q1, t.b_q1, C, C, nullptr, wide, C, T, EPI_LINEAR, &rs, t.s_q1));
-        } else {
-            LAUNCH(launch_layernorm(tx, t.ln1.g, t.ln1.b, ln, T, C, 1e-5f, c.s));
-            RUN(linear(c, ln, C, t.wq1, nullptr, C, C, nullptr, wide, C, T));
-        }
-        const half_t* kvc1 = kv2;
-        if (kv_cached) kvc1 = kv1_cache_[ti];
-        else RUN(linear(c, ctx, X, t.wkv1, nullptr, 2 * C, X, nullptr, kv2, 2 * C, c.B * c.ctx_len));
-        if (!c.dry) {
-            AttnParams a;
-            a.q = wide; a.ldq = C; a.k = kvc1; a.ldk = 2 * C; a.v = kvc1 + C; a.ldv = 2 * C;
-            a.o = att; a.ldo = C; a.NBq = NI; a.Lq = D; a.Lk = c.ctx_len; a.heads = heads; a.dh = dh; a.kv_batch_div = c.F; a.scale = scale;
-            RUN(launch_attention(a, c.s));
-        }
+        RUN(text_attention(t.qkv1, t.wkv1, kv1_cache_));
     } else {
         // spatial self-attention (attention.py:513-522)
-        if (br.fused_head) {
-            // q | k | v already in `wide`
-        } else if (fold) {
-            RUN(linear(c, tx, C, t.f_qkv1, t.b_qkv1, 3 * C, C, nullptr, wide, 3 * C, Tp, EPI_LINEAR, &rs, t.s_qkv1));
-        } else {
-            LAUNCH(launch_layernorm(tx, t.ln1.g, t.ln1.b, ln, Tp, C, 1e-5f, c.s));
-            RUN(linear(c, ln, C, t.wqkv1, nullptr, 3 * C, C, nullptr, wide, 3 * C, Tp));
-        }
+        if (!br.fused_head) RUN(ln_proj(t.qkv1, fold, Tp));      // (the fused head left q | k | v in `wide`)
         if (!c.dry) {
             AttnParams a;
             a.q = wide; a.ldq = 3 * C; a.k = wide + C; a.ldk = 3 * C; a.v = wide + 2 * C; a.ldv = 3 * C;
@@ -1020,30 +1010,14 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
         LAVIE_HIP(hipMemcpyAsync(att + (size_t)Tp * C, att, (size_t)Tp * C * sizeof(half_t), hipMemcpyDeviceToDevice, c.s));
     }
     // attn1.to_out -> + residual -> norm2 -> attn2 -> to_out -> + residual: one kernel on this context's K / V image ...
-    if (br.text == BlockRoute::TEXT_FUSED_LONG) {
-        LAUNCH(launch_cross_block_long(att, tx, tx, T, c.F * D, C, heads, xb_img_[ti], t.o1.b, t.ln2.g, t.ln2.b, t.o2.b, c.ctx_len, scale, 1e-5f, c.s));
-    } else if (br.text == BlockRoute::TEXT_FUSED) {
-        LAUNCH(launch_cross_block(att, tx, tx, T, c.F * D, C, heads, xb_img_[ti], t.o1.b, t.ln2.g, t.ln2.b, t.o2.b, c.ctx_len, scale, 1e-5f, c.s));
+    if (br.text != CROSS_NONE) {
+        LAUNCH(launch_cross_block(br.text, att, tx, tx, T, c.F * D, C, heads, xb_img_[ti], t.o1.b, t.ln2.g, t.ln2.b, t.o2.b, c.ctx_len, scale, 1e-5f, c.s));
     } else {       // ... or GEMMs
         RUN(linear(c, att, C, t.o1.w, t.o1.b, C, C, tx, tx, C, T, EPI_LINEAR, emit(br.emit_o1)));
         TRACE("block.attn1.to_out", tx, T, C);
 
         // text cross-attention (attention.py:524-534); K/V once per video instead of once per frame (364)
-        if (fold) {
-            RUN(linear(c, tx, C, t.f_q2, t.b_q2, C, C, nullptr, wide, C, T, EPI_LINEAR, &rs, t.s_q2));
-        } else {
-            LAUNCH(launch_layernorm(tx, t.ln2.g, t.ln2.b, ln, T, C, 1e-5f, c.s));
-            RUN(linear(c, ln, C, t.wq2, nullptr, C, C, nullptr, wide, C, T));
-        }
-        const half_t* kvc2 = kv2;
-        if (kv_cached) kvc2 = kv2_cache_[ti];
-        else RUN(linear(c, ctx, X, t.wkv2, nullptr, 2 * C, X, nullptr, kv2, 2 * C, c.B * c.ctx_len));
-        if (!c.dry) {
-            AttnParams a;
-            a.q = wide; a.ldq = C; a.k = kvc2; a.ldk = 2 * C; a.v = kvc2 + C; a.ldv = 2 * C;
-            a.o = att; a.ldo = C; a.NBq = NI; a.Lq = D; a.Lk = c.ctx_len; a.heads = heads; a.dh = dh; a.kv_batch_div = c.F; a.scale = scale;
-            RUN(launch_attention(a, c.s));
-        }
+        RUN(text_attention(t.q2, t.wkv2, kv2_cache_));
         TRACE("block.attn2", att, T, C);
         RUN(linear(c, att, C, t.o2.w, t.o2.b, C, C, tx, tx, C, T, EPI_LINEAR, emit(br.emit_o2)));
     }
@@ -1056,13 +1030,8 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
                                          cur_tables_->rot_cos, cur_tables_->rot_sin, cfg_.rotary_dim, scale, 1e-5f, c.s));
             return 0;
         }
-        if (br.fold_t) {
-            RUN(linear(c, tx, C, t.f_qkvt, t.b_qkvt, 3 * C, C, nullptr, wide, 3 * C, T, EPI_LINEAR, &rs, t.s_qkvt));
-            TRACE("temporal.row statistics", rs.stats, T, 2);
-        } else {
-            LAUNCH(launch_layernorm(tx, t.lnt.g, t.lnt.b, ln, T, C, 1e-5f, c.s));
-            RUN(linear(c, ln, C, t.wqkvt, nullptr, 3 * C, C, nullptr, wide, 3 * C, T));
-        }
+        RUN(ln_proj(t.qkvt, br.fold_t, T));
+        if (br.fold_t) TRACE("temporal.row statistics", rs.stats, T, 2);
         TRACE("temporal.qkv before", wide, T, 3 * C);
         if (!c.dry) {
             TemporalParams tp;
@@ -1084,12 +1053,7 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
             if (br.ff_first) rs.pending = false;
             return 0;
         }
-        if (br.fold_ff) {
-            RUN(linear(c, tx, C, t.f_ff1, t.b_ff1, 8 * C, C, nullptr, wide, 4 * C, T, EPI_GEGLU, &rs, t.s_ff1));
-        } else {
-            LAUNCH(launch_layernorm(tx, t.ln3.g, t.ln3.b, ln, T, C, 1e-5f, c.s));
-            RUN(linear(c, ln, C, t.ff1.w, t.ff1.b, 8 * C, C, nullptr, wide, 4 * C, T, EPI_GEGLU));
-        }
+        RUN(ln_proj(t.ff1, br.fold_ff, T, EPI_GEGLU));
         // (K = 4C: the planner may pick another kernel than for the K = C producers, hence a slot count per producer)
         RUN(linear(c, wide, 4 * C, t.ff2.w, t.ff2.b, C, 4 * C, tx, tx, C, T, EPI_LINEAR, emit(br.emit_ff2)));
         return 0;
@@ -1400,9 +1364,9 @@ int UNet::cache_context(const half_t* ctx, int B, int ctx_len, hipStream_t strea
     const size_t rows = (size_t)B * ctx_len;
     const int X = cfg_.cross_attention_dim;
     const int C0 = cfg_.block_out_channels[0];
-    const bool xb_long = cross_block_long_supported(C0, cfg_.heads, ctx_len, 16);
-    if (xb_long) RUN(ensure_long_templates(stream));
-    const size_t img_bytes = xb_long ? cross_block_long_image_bytes(C0) : cross_block_image_bytes(C0);
+    const CrossVariant xv = cross_block_variant(C0, cfg_.heads, ctx_len, 16);
+    if (xv == CROSS_LONG) RUN(ensure_long_templates(stream));
+    const size_t img_bytes = cross_block_image_bytes(xv);      // (no variant: as the short one)
     if (rows > kv_cache_rows_ || B > kv_cache_B_ || kv2_cache_.size() != transformers_.size() || img_bytes > xb_img_bytes_) {
         // the cache lives in a block of its own: a longer context frees the old block instead of stranding it in the
         // grow-only weights arena.  Earlier forwards that read the old block are ordered before the free by the sync.
@@ -1410,7 +1374,7 @@ int UNet::cache_context(const half_t* ctx, int B, int ctx_len, hipStream_t strea
         auto span = [&](size_t i) { return (rows * 2 * transformers_[i].C * sizeof(half_t) + 255) & ~(size_t)255; };
         // a long context lays the images out for the long layout; a short one after it keeps (and uses the front of) the larger ones
         const size_t xb_bytes = img_bytes > xb_img_bytes_ ? img_bytes : xb_img_bytes_;
-        auto img_span = [&](size_t i) { return transformers_[i].xb_tmpl ? (size_t)B * xb_bytes : 0; };
+        auto img_span = [&](size_t i) { return transformers_[i].xb_tmpl[CROSS_SHORT] ? (size_t)B * xb_bytes : 0; };
         for (size_t i = 0; i < transformers_.size(); ++i) total += span(i) * (transformers_[i].attn1_cross ? 2 : 1) + img_span(i);
         if (kv_block_) {
             LAVIE_HIP(hipStreamSynchronize(stream));
@@ -1443,13 +1407,9 @@ int UNet::cache_context(const half_t* ctx, int B, int ctx_len, hipStream_t strea
     }
     // the fused cross-attention kernel streams K / V with its weights: one image per video, written here once per context
     xb_bound_ = false;
-    if (cross_block_supported(C0, cfg_.heads, ctx_len, 16)) {
+    if (xv != CROSS_NONE) {
         for (size_t i = 0; i < transformers_.size(); ++i)
-            if (xb_img_[i]) RUN(bind_cross_block(transformers_[i].xb_tmpl, kv2_cache_[i], B, ctx_len, transformers_[i].C, xb_img_[i], stream));
-        xb_bound_ = true;
-    } else if (xb_long) {
-        for (size_t i = 0; i < transformers_.size(); ++i)
-            if (xb_img_[i]) RUN(bind_cross_block_long(transformers_[i].xbl_tmpl, kv2_cache_[i], B, ctx_len, transformers_[i].C, xb_img_[i], stream));
+            if (xb_img_[i]) RUN(bind_cross_block(xv, transformers_[i].xb_tmpl[xv], kv2_cache_[i], B, ctx_len, transformers_[i].C, xb_img_[i], stream));
         xb_bound_ = true;
     }
     kv_ctx_ = ctx;
@@ -1464,16 +1424,16 @@ int UNet::cache_context(const half_t* ctx, int B, int ctx_len, hipStream_t strea
 int UNet::ensure_long_templates(hipStream_t stream) {
     if (xbl_block_) return 0;
     size_t n = 0;
-    for (const TransformerW& t : transformers_) n += t.xb_tmpl ? 1 : 0;
+    for (const TransformerW& t : transformers_) n += t.xb_tmpl[CROSS_SHORT] ? 1 : 0;
     if (n == 0) return 0;
-    const size_t bytes = cross_block_long_image_bytes(cfg_.block_out_channels[0]);
+    const size_t bytes = cross_block_image_bytes(CROSS_LONG);
     LAVIE_HIP(hipMalloc(&xbl_block_, n * bytes));
     char* cur = (char*)xbl_block_;
     for (TransformerW& t : transformers_) {
-        if (!t.xb_tmpl) continue;
-        t.xbl_tmpl = (half_t*)cur;
+        if (!t.xb_tmpl[CROSS_SHORT]) continue;
+        t.xb_tmpl[CROSS_LONG] = (half_t*)cur;
         cur += bytes;
-        RUN(pack_cross_block_long(t.o1.w, t.wq2, t.o2.w, t.C, t.xbl_tmpl, stream));
+        RUN(pack_cross_block(CROSS_LONG, t.o1.w, t.q2.w, t.o2.w, t.C, t.xb_tmpl[CROSS_LONG], stream));
     }
     return 0;
 }
@@ -1531,10 +1491,10 @@ int UNet::lora_set_slot(int slot, const char* name, const half_t* base, const fl
         e.K = pi.shape[1];
         const size_t nk = (size_t)e.N * e.K;
         if (proj == 3) e.dst = attn == 0 ? t.o1.w : attn == 1 ? t.o2.w : t.ot.w;
-        else if (attn == 0 && t.attn1_cross) e.dst = proj == 0 ? t.wq1 : t.wkv1 + (proj - 1) * nk;
-        else if (attn == 0) e.dst = t.wqkv1 + proj * nk;
-        else if (attn == 1) e.dst = proj == 0 ? t.wq2 : t.wkv2 + (proj - 1) * nk;
-        else e.dst = t.wqkvt + proj * nk;
+        else if (attn == 0 && t.attn1_cross) e.dst = proj == 0 ? t.qkv1.w : t.wkv1 + (proj - 1) * nk;
+        else if (attn == 0) e.dst = t.qkv1.w + proj * nk;
+        else if (attn == 1) e.dst = proj == 0 ? t.q2.w : t.wkv2 + (proj - 1) * nk;
+        else e.dst = t.qkvt.w + proj * nk;
         LAVIE_HIP(hipMalloc((void**)&e.base, nk * sizeof(half_t)));
         found = lora_.emplace(name, e).first;
     }

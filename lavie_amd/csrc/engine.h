@@ -62,31 +62,36 @@ struct TemporalResW {
     half_t* w2 = nullptr; float* b2 = nullptr;      // [C][3 * C]
 };
 
+// A projection that consumes a LayerNorm of the block's residual stream, in both forms: plain (w, b) behind an explicit LayerNorm,
+// and with the norm folded in: W' = W * gamma (fp16), s = row sums of W', b' = W beta (+ bias)
+struct TransformerW;
+struct LnProj {
+    NormW TransformerW::* ln;                       // the norm it sits behind
+    int N = 0;                                      // output columns ([N][C] weights)
+    half_t* w = nullptr; float* b = nullptr;
+    half_t* fw = nullptr; float* fs = nullptr; float* fb = nullptr;
+};
+
 struct TransformerW {
     std::string prefix;
     int C = 0;
     // VSR variant (lavie_unet_config::vsr_blocks / only_cross_attention)
     TemporalResW tres;                              // `resblock_temporal`, runs before the block's residual is taken
-    bool attn1_cross = false;                       // attn1 attends to the text context
-    half_t* wq1 = nullptr; half_t* wkv1 = nullptr;  // its projections: [C][C], [2C][cross_dim]
-    half_t* f_q1 = nullptr; float* s_q1 = nullptr; float* b_q1 = nullptr;
+    bool attn1_cross = false;                       // attn1 attends to the text context: qkv1 is to_q alone, wkv1 [2C][cross_dim]
+    half_t* wkv1 = nullptr;
     NormW gn, ln1, ln2, lnt, ln3;
     LinW pin, pout;
-    half_t* wqkv1 = nullptr; LinW o1;
-    half_t* wq2 = nullptr; half_t* wkv2 = nullptr; LinW o2;
-    half_t* wqkvt = nullptr; LinW ot;
+    LnProj qkv1{&TransformerW::ln1}; LinW o1;       // to_q | to_k | to_v rows
+    LnProj q2{&TransformerW::ln2}; half_t* wkv2 = nullptr; LinW o2;
+    LnProj qkvt{&TransformerW::lnt}; LinW ot;
     half_t* relemb = nullptr;                       // [buckets][heads] fp16 (state-dict tensor)
-    LinW ff1, ff2;                                  // ff1 in GEGLU-interleaved row order
-    // LayerNorm-folded copies of the four projections that consume a LayerNorm (W * gamma, row sums, W beta + bias)
-    half_t* f_qkv1 = nullptr; float* s_qkv1 = nullptr; float* b_qkv1 = nullptr;
-    half_t* f_q2 = nullptr; float* s_q2 = nullptr; float* b_q2 = nullptr;
-    half_t* f_qkvt = nullptr; float* s_qkvt = nullptr; float* b_qkvt = nullptr;
-    half_t* f_ff1 = nullptr; float* s_ff1 = nullptr; float* b_ff1 = nullptr;
+    LnProj ff1{&TransformerW::ln3}; LinW ff2;       // ff1 in GEGLU-interleaved row order
     // row-resident fused sub-blocks (rowfuse.hip), built where the width has a kernel (level 0: C = 320)
     half_t* ff_img = nullptr; float* ff_b1img = nullptr;    // norm3 -> GEGLU feed-forward -> + residual in one kernel
     half_t* tb_img = nullptr;                               // norm_temp -> q|k|v -> temporal attention -> to_out -> + residual
-    half_t* xb_tmpl = nullptr;                              // attn1.to_out -> norm2 -> attn2 -> + residual: weight part of the image (rowfuse_cross.hip)
-    half_t* xbl_tmpl = nullptr;                             // the same for the long variant (81..160 keys): built by the first long cache_context
+    // attn1.to_out -> norm2 -> attn2 -> + residual: weight part of the image (rowfuse_cross.hip), per variant; the long one (81..160
+    // keys) is built by the first long cache_context
+    half_t* xb_tmpl[kCrossVariants] = {nullptr, nullptr};
     half_t* pq_img = nullptr;                               // GroupNorm -> proj_in -> norm1 -> q|k|v (rowfuse_pin.hip, round 4)
 };
 
@@ -116,7 +121,7 @@ struct LoraSlot {
 };
 struct LoraEntry {
     int ti = -1;                                    // transformer block
-    half_t* dst = nullptr;                          // the projection's [N][K] rows inside wqkv1 / wq1 / wkv1 / o1 / wq2 / wkv2 / o2 / wqkvt / ot
+    half_t* dst = nullptr;                          // the projection's [N][K] rows inside qkv1 / wkv1 / o1 / q2 / wkv2 / o2 / qkvt / ot
     int N = 0, K = 0;
     half_t* base = nullptr;                         // copy of the base weight
     LoraSlot slot[kLoraMaxTerms];
@@ -257,7 +262,7 @@ private:
     int kv_cache_B_ = 0;                            // videos the image buffers were allocated for
     bool xb_bound_ = false;                         // images hold the cached context (its length fits the kernel)
     size_t xb_img_bytes_ = 0;                       // bytes per video the image buffers were laid out for (short or long layout)
-    void* xbl_block_ = nullptr;                     // ONE hipMalloc'd block behind every long template (xbl_tmpl), kept for the model's life
+    void* xbl_block_ = nullptr;                     // ONE hipMalloc'd block behind every long template, kept for the model's life
     int ensure_long_templates(hipStream_t stream);
     void* kv_block_ = nullptr;                      // ONE hipMalloc'd block behind every K/V cache buffer: freed and reallocated on growth
     const half_t* kv_ctx_ = nullptr;

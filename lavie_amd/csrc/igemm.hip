@@ -27,10 +27,6 @@
 #include "igemm_epilogue.h"
 #include "profile.h"
 
-#ifndef LAVIE_SPLITK_MFAST
-#define LAVIE_SPLITK_MFAST 1      // A/B switch of the split-K tile order below
-#endif
-
 namespace lavie {
 
 template <int WM, int WN, int MT, int NT, int NSTAGE>
@@ -62,7 +58,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
     // ---- XCD-aware tile order (bijective for any grid size) ----
     const int n_tiles = p.N / T::BN;
     int tile_m, tile_n, split = 0;
-    if (gridDim.y == 1 || !LAVIE_SPLITK_MFAST) {
+    if (gridDim.y == 1) {
         int bid = blockIdx.x;
         const int nwg = gridDim.x;
         split = blockIdx.y;

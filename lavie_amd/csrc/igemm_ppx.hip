@@ -43,9 +43,8 @@ namespace lavie {
 #define PPX_TRICKLE 0      // 0: a finished tile's stores are issued at once from its finish pass (fastest measured); n > 0: parked in
                            // the output registers and issued n per R phase (measured slower: a queued store delays the wave's own loads)
 #endif
-#ifndef PPX_STAGGER
-#define PPX_STAGGER 0      // 1: workgroups start a quarter tile period apart (measured: no effect)
-#endif
+// (PPX_TRICKLE stays a switch: without its parking branch hipcc allocates the registers of every instance differently; staggering
+// the workgroups' starts by a quarter tile period: measured and rejected)
 
 namespace ppx {
 constexpr int MT = 5;
@@ -538,16 +537,6 @@ __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmP
         maybe(std::integral_constant<int, 12>{}); maybe(std::integral_constant<int, 13>{}); maybe(std::integral_constant<int, 14>{});
     };
 
-    // ---- stagger: the workgroups of an XCD start a quarter of a tile period apart, so that at any moment some CUs are
-    // in their K loops (HBM reads) while others drain a finished tile (HBM writes) instead of the whole chip alternating
-    if (PPX_STAGGER && tiles_total > (int)gridDim.x) {
-        const int ph = (blockIdx.x >> 3) & 3;
-        if (ph) {
-            const unsigned long long ticks = (unsigned long long)ph * (unsigned long long)(nk * 40 + 75);   // 100 MHz ticks: ph/4 of ~(1.6 nk + 3) us
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-        }
-    }
     // ---- prologue (first tile only): W(0), A(0), A(1) by the same roles; everything landed before the first read
     if (grp == 0) {
         issue_w_g0(0, 0);

@@ -155,21 +155,16 @@ int launch_proj_qkv(const half_t* x, const float* gn_ab, int rows_per_domain, co
 
 // ---- rowfuse_cross.hip: x'' = x' + to_out2(attn2(LN2(x'), K, V)), x' = x + to_out1(att), K / V of the text context streamed
 // with the weights (one image per video: pack once per model, bind once per context); y may alias x
-bool cross_block_supported(int C, int heads, int ctx_len, int rows_per_batch);
-size_t cross_block_image_bytes(int C);
-int pack_cross_block(const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, hipStream_t stream);
-int bind_cross_block(const half_t* tmpl, const half_t* kv, int B, int L, int C, half_t* img, hipStream_t stream);
-int launch_cross_block(const half_t* att, const half_t* x, half_t* y, int M, int rows_per_batch, int C, int heads, const half_t* img,
-                       const float* bo1, const float* gamma, const float* beta, const float* bo2, int L, float scale, float eps,
-                       hipStream_t stream);
-// the long variant (81..160 keys): the same sub-block with images of its own layout (ten key tiles per head)
-bool cross_block_long_supported(int C, int heads, int ctx_len, int rows_per_batch);
-size_t cross_block_long_image_bytes(int C);
-int pack_cross_block_long(const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, hipStream_t stream);
-int bind_cross_block_long(const half_t* tmpl, const half_t* kv, int B, int L, int C, half_t* img, hipStream_t stream);
-int launch_cross_block_long(const half_t* att, const half_t* x, half_t* y, int M, int rows_per_batch, int C, int heads, const half_t* img,
-                            const float* bo1, const float* gamma, const float* beta, const float* bo2, int L, float scale, float eps,
-                            hipStream_t stream);
+// Two variants with images of their own layout, told apart by the 16-key tiles per head: short = 5 (1..80 keys), long = 10 (81..160)
+enum CrossVariant { CROSS_NONE = -1, CROSS_SHORT = 0, CROSS_LONG = 1 };
+constexpr int kCrossVariants = 2;
+CrossVariant cross_block_variant(int C, int heads, int ctx_len, int rows_per_batch);     // the variant that serves the shape, or none
+size_t cross_block_image_bytes(CrossVariant v);
+int pack_cross_block(CrossVariant v, const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, hipStream_t stream);
+int bind_cross_block(CrossVariant v, const half_t* tmpl, const half_t* kv, int B, int L, int C, half_t* img, hipStream_t stream);
+int launch_cross_block(CrossVariant v, const half_t* att, const half_t* x, half_t* y, int M, int rows_per_batch, int C, int heads,
+                       const half_t* img, const float* bo1, const float* gamma, const float* beta, const float* bo2, int L, float scale,
+                       float eps, hipStream_t stream);
 
 // ---- lora.hip: out[n, k] = fp16_rne(W0[n, k] + scale * sum_{j < r} B[n, j] A[j, k]), W0 / out fp16 [N, K], A fp32 [r, K], B fp32 [N, r];
 // fp32 accumulation in ascending j, no atomics (deterministic); K % 8 == 0, W0 / out / A 16-byte aligned; out may alias W0

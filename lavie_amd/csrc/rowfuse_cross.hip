@@ -25,7 +25,8 @@
 //       4 x 155    per head pair:  50 Wq2 | 30 K (10 key tiles x 3, as above) | 25 V^T (5 channel tiles x 5 32-key steps: 160 keys
 //                                  are five full 32-deep steps, no 16-deep tail) | 50 Wo2
 //       20         padding (21 units of 40)
-// Its own instance, templates, images and entry points (cross_block_long_*): the <= 80-key instance is not touched.
+// One host path serves both: every function below is a template over the key tiles and reads XbLayout<NKT>; the <= 80-key device
+// instance is not touched.
 #include <map>
 
 #include "rowfuse.h"
@@ -37,7 +38,6 @@ constexpr int C = 320, NT = 20, KS = 10, HEADS = 8, DH = 40, MAXL = 80;
 constexpr int UNIT = 40, PASS_UNITS = 18, PASS_PIECES = 720, O1_PIECES = 200, PAIR_PIECES = 128;
 constexpr int Q_OFF = 0, K_OFF = 50, V_OFF = 65, O_OFF = 78;       // inside a pair's 128 pieces
 constexpr int VEC_BYTES = 4 * C * 4;                                 // bo1 | gamma | beta | bo2
-constexpr size_t IMG_BYTES = (size_t)PASS_PIECES * 1024;
 // channel of row r of tile j of head pair (h0, h1): tiles 0, 1 = channels 0..31 of h0; 3, 4 = of h1; 2 = channels 32..39 of both
 inline int pair_channel(int h0, int j, int r) {
     const int h1 = h0 + 1;
@@ -56,30 +56,35 @@ template <> struct XbLayout<10> {
     static constexpr int MAXL = 160, PAIR_PIECES = 155, K_OFF = 50, V_OFF = 80, O_OFF = 105;
     static constexpr int V_PIECES = 25, PASS_UNITS = 21, PASS_PIECES = 840;
 };
-namespace xbl {
-using Lay = XbLayout<10>;
-constexpr int MINL = xb::MAXL + 1, MAXL = Lay::MAXL;
-constexpr size_t IMG_BYTES = (size_t)Lay::PASS_PIECES * 1024;
-static_assert(xb::O1_PIECES + 4 * Lay::PAIR_PIECES <= Lay::PASS_PIECES && Lay::PASS_PIECES == Lay::PASS_UNITS * xb::UNIT, "long layout");
-static_assert(Lay::K_OFF + 3 * 10 == Lay::V_OFF && Lay::V_OFF + Lay::V_PIECES == Lay::O_OFF && Lay::O_OFF + 50 == Lay::PAIR_PIECES, "long pair");
-}  // namespace xbl
+static_assert(xb::O1_PIECES + 4 * XbLayout<10>::PAIR_PIECES <= XbLayout<10>::PASS_PIECES && XbLayout<10>::PASS_PIECES == XbLayout<10>::PASS_UNITS * xb::UNIT, "long layout");
+static_assert(XbLayout<10>::K_OFF + 3 * 10 == XbLayout<10>::V_OFF && XbLayout<10>::V_OFF + XbLayout<10>::V_PIECES == XbLayout<10>::O_OFF && XbLayout<10>::O_OFF + 50 == XbLayout<10>::PAIR_PIECES, "long pair");
 
-size_t cross_block_image_bytes(int C) { return xb::IMG_BYTES; }
-bool cross_block_supported(int C, int heads, int ctx_len, int rows_per_batch) {
-    return C == xb::C && heads == xb::HEADS && ctx_len >= 1 && ctx_len <= xb::MAXL && rows_per_batch > 0 && rows_per_batch % rf::TOK == 0;
+// host side of a variant: its image size, the shortest context it takes (the short instance serves everything below the long one's)
+// and the prefix of its refusals
+template <int NKT> struct XbHost {
+    static constexpr size_t IMG_BYTES = (size_t)XbLayout<NKT>::PASS_PIECES * 1024;
+    static constexpr int MINL = NKT == 5 ? 1 : xb::MAXL + 1;
+    static constexpr const char* NAME = NKT == 5 ? "cross_block" : "cross_block_long";
+};
+// the instance of variant v
+#define XB_VARIANT(v, fn, ...) ((v) != CROSS_LONG ? fn<5>(__VA_ARGS__) : fn<10>(__VA_ARGS__))
+
+size_t cross_block_image_bytes(CrossVariant v) { return v == CROSS_LONG ? XbHost<10>::IMG_BYTES : XbHost<5>::IMG_BYTES; }
+CrossVariant cross_block_variant(int C, int heads, int ctx_len, int rows_per_batch) {
+    if (C != xb::C || heads != xb::HEADS || rows_per_batch <= 0 || rows_per_batch % rf::TOK != 0) return CROSS_NONE;
+    return ctx_len < 1 ? CROSS_NONE : ctx_len <= XbLayout<5>::MAXL ? CROSS_SHORT : ctx_len <= XbLayout<10>::MAXL ? CROSS_LONG : CROSS_NONE;
 }
 
 // wo1 (attn1.to_out.0), wq2 (attn2.to_q), wo2 (attn2.to_out.0): [C][C] fp16 device tensors -> tmpl (cross_block_image_bytes):
 // the weight pieces of the image; the K / V pieces stay zero until bind_cross_block().  Synchronous (load time).
 // The weight pieces are laid out alike in both instances; only the pair stride and the Wo2 offset differ.
 template <int NKT>
-static int pack_cross_block_impl(const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, size_t img_bytes,
-                                 hipStream_t stream) {
+static int pack_impl(const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, hipStream_t stream) {
     using namespace xb;
     using Lay = XbLayout<NKT>;
     constexpr int PAIR_PIECES = Lay::PAIR_PIECES, O_OFF = Lay::O_OFF;
     LAVIE_CHECK(C == xb::C, "cross_block: width %d is not built (320 only)", C);
-    LAVIE_HIP(hipMemsetAsync(tmpl, 0, img_bytes, stream));
+    LAVIE_HIP(hipMemsetAsync(tmpl, 0, XbHost<NKT>::IMG_BYTES, stream));
     std::vector<int2> lists[3];
     for (int t = 0; t < NT; ++t)
         for (int ks = 0; ks < KS; ++ks) {
@@ -112,16 +117,8 @@ static int pack_cross_block_impl(const half_t* wo1, const half_t* wq2, const hal
     const half_t* srcs[3] = {wo1, wq2, wo2};
     return rf_run_gathers(lists, srcs, 3, tmpl, stream);
 }
-
-int pack_cross_block(const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, hipStream_t stream) {
-    return pack_cross_block_impl<5>(wo1, wq2, wo2, C, tmpl, xb::IMG_BYTES, stream);
-}
-size_t cross_block_long_image_bytes(int C) { return xbl::IMG_BYTES; }
-bool cross_block_long_supported(int C, int heads, int ctx_len, int rows_per_batch) {
-    return C == xb::C && heads == xb::HEADS && ctx_len >= xbl::MINL && ctx_len <= xbl::MAXL && rows_per_batch > 0 && rows_per_batch % rf::TOK == 0;
-}
-int pack_cross_block_long(const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, hipStream_t stream) {
-    return pack_cross_block_impl<10>(wo1, wq2, wo2, C, tmpl, xbl::IMG_BYTES, stream);
+int pack_cross_block(CrossVariant v, const half_t* wo1, const half_t* wq2, const half_t* wo2, int C, half_t* tmpl, hipStream_t stream) {
+    return XB_VARIANT(v, pack_impl, wo1, wq2, wo2, C, tmpl, stream);
 }
 
 // Batched gathers of the K (8-byte chunks) and V^T (single halfs: a transpose) pieces: blockIdx.y = video
@@ -149,40 +146,45 @@ struct BindPlan {
 std::map<int, BindPlan> g_bind_plans;      // by context length; a few hundred KiB of device memory each, kept for the process
 }  // namespace
 
+// K pieces: three per key tile; V^T: per channel tile NKT / 2 full 32-key steps, then (odd NKT) the 16-key steps of two channel tiles
+// per piece.  Keys past L are zero.  One map for both variants: their lengths do not overlap.
+template <int NKT>
 static int bind_plan(int L, BindPlan** out) {
     using namespace xb;
+    using Lay = XbLayout<NKT>;
+    constexpr int FULL = NKT / 2;
     auto it = g_bind_plans.find(L);
     if (it != g_bind_plans.end()) { *out = &it->second; return 0; }
     std::vector<int2> kl, vl;
     const int ld = 2 * C;            // kv rows: [k (C) | v (C)]
     for (int hp = 0; hp < 4; ++hp) {
-        const int h0 = 2 * hp, h1 = h0 + 1, P0 = O1_PIECES + PAIR_PIECES * hp;
-        for (int kt = 0; kt < 5; ++kt)
+        const int h0 = 2 * hp, h1 = h0 + 1, P0 = O1_PIECES + Lay::PAIR_PIECES * hp;
+        for (int kt = 0; kt < NKT; ++kt)
             for (int slot = 0; slot < 64; ++slot) {
                 const int r = slot >> 2, q = (slot & 3) ^ rf::swz(r), key = 16 * kt + r;
                 for (int e = 0; e < 2; ++e)            // channels 0..31 of head e: k-slot 8 q + j <-> channel 16 (j >> 2) + 4 q + (j & 3)
                     for (int half = 0; half < 2; ++half)
-                        kl.push_back(make_int2((P0 + K_OFF + 3 * kt + e) * 128 + slot * 2 + half,
+                        kl.push_back(make_int2((P0 + Lay::K_OFF + 3 * kt + e) * 128 + slot * 2 + half,
                                                key < L ? (key * ld + (e ? h1 : h0) * DH + 16 * half + 4 * q) / 4 : -1));
                 // channels 32..39: 16-deep fragments of head 0 (low half: k-slots of q < 2) and head 1 (high half: q >= 2)
-                kl.push_back(make_int2((P0 + K_OFF + 3 * kt + 2) * 128 + slot * 2 + 0, (key < L && q < 2) ? (key * ld + h0 * DH + 32 + 4 * q) / 4 : -1));
-                kl.push_back(make_int2((P0 + K_OFF + 3 * kt + 2) * 128 + slot * 2 + 1, (key < L && q >= 2) ? (key * ld + h1 * DH + 32 + 4 * (q - 2)) / 4 : -1));
+                kl.push_back(make_int2((P0 + Lay::K_OFF + 3 * kt + 2) * 128 + slot * 2 + 0, (key < L && q < 2) ? (key * ld + h0 * DH + 32 + 4 * q) / 4 : -1));
+                kl.push_back(make_int2((P0 + Lay::K_OFF + 3 * kt + 2) * 128 + slot * 2 + 1, (key < L && q >= 2) ? (key * ld + h1 * DH + 32 + 4 * (q - 2)) / 4 : -1));
             }
         for (int j = 0; j < 5; ++j)
-            for (int s = 0; s < 2; ++s)
+            for (int s = 0; s < FULL; ++s)
                 for (int slot = 0; slot < 64; ++slot) {
                     const int r = slot >> 2, q = (slot & 3) ^ rf::swz(r), ch = pair_channel(h0, j, r);
                     for (int jj = 0; jj < 8; ++jj) {
                         const int key = 32 * s + 16 * (jj >> 2) + 4 * q + (jj & 3);
-                        vl.push_back(make_int2((P0 + V_OFF + 2 * j + s) * 512 + slot * 8 + jj, key < L ? key * ld + C + ch : -1));
+                        vl.push_back(make_int2((P0 + Lay::V_OFF + FULL * j + s) * 512 + slot * 8 + jj, key < L ? key * ld + C + ch : -1));
                     }
                 }
-        for (int n = 0; n < 3; ++n)
+        for (int n = 0; n < (NKT % 2 ? 3 : 0); ++n)
             for (int slot = 0; slot < 64; ++slot) {
                 const int r = slot >> 2, q = (slot & 3) ^ rf::swz(r);
                 for (int jj = 0; jj < 8; ++jj) {
-                    const int j = 2 * n + (jj >> 2), key = 64 + 4 * q + (jj & 3);
-                    vl.push_back(make_int2((P0 + V_OFF + 10 + n) * 512 + slot * 8 + jj, (j < 5 && key < L) ? key * ld + C + pair_channel(h0, j, r) : -1));
+                    const int j = 2 * n + (jj >> 2), key = 32 * FULL + 4 * q + (jj & 3);
+                    vl.push_back(make_int2((P0 + Lay::V_OFF + 5 * FULL + n) * 512 + slot * 8 + jj, (j < 5 && key < L) ? key * ld + C + pair_channel(h0, j, r) : -1));
                 }
             }
     }
@@ -199,68 +201,13 @@ static int bind_plan(int L, BindPlan** out) {
 
 // tmpl (pack_cross_block) + kv [B * L][2C] fp16 (k | v rows of attn2.to_k / to_v applied to the text context of each video)
 // -> img [B] images.  Stream-ordered (no synchronisation once the plan of this L exists).
-int bind_cross_block(const half_t* tmpl, const half_t* kv, int B, int L, int C, half_t* img, hipStream_t stream) {
-    using namespace xb;
-    LAVIE_CHECK(C == xb::C && L >= 1 && L <= MAXL && B >= 1, "cross_block: C=%d L=%d B=%d is not built", C, L, B);
+template <int NKT>
+static int bind_impl(const half_t* tmpl, const half_t* kv, int B, int L, int C, half_t* img, hipStream_t stream) {
+    using Host = XbHost<NKT>;
+    LAVIE_CHECK(C == xb::C && L >= Host::MINL && L <= XbLayout<NKT>::MAXL && B >= 1, "%s: C=%d L=%d B=%d is not built", Host::NAME, C, L, B);
     BindPlan* plan = nullptr;
-    if (int rc = bind_plan(L, &plan)) return rc;
-    for (int b = 0; b < B; ++b)
-        LAVIE_HIP(hipMemcpyAsync(reinterpret_cast<char*>(img) + b * IMG_BYTES, tmpl, IMG_BYTES, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(xb_gather8_kernel, dim3(cdiv(plan->nk, 256), B), dim3(256), 0, stream, (const uint2*)kv, (uint2*)img, plan->k_pairs,
-                       plan->nk, (size_t)L * 2 * C / 4, IMG_BYTES / 8);
-    hipLaunchKernelGGL(xb_gather2_kernel, dim3(cdiv(plan->nv, 256), B), dim3(256), 0, stream, kv, img, plan->v_pairs, plan->nv,
-                       (size_t)L * 2 * C, IMG_BYTES / 2);
-    LAVIE_HIP(hipGetLastError());
-    return 0;
-}
-
-// The long image: K pieces as above for ten key tiles; V^T as five full 32-key steps per channel tile (keys past L are zero).
-// Plans are kept by context length next to the short ones (the lengths do not overlap).
-static int bind_plan_long(int L, BindPlan** out) {
-    using namespace xb;
-    using Lay = XbLayout<10>;
-    auto it = g_bind_plans.find(L);
-    if (it != g_bind_plans.end()) { *out = &it->second; return 0; }
-    std::vector<int2> kl, vl;
-    const int ld = 2 * C;
-    for (int hp = 0; hp < 4; ++hp) {
-        const int h0 = 2 * hp, h1 = h0 + 1, P0 = O1_PIECES + Lay::PAIR_PIECES * hp;
-        for (int kt = 0; kt < 10; ++kt)
-            for (int slot = 0; slot < 64; ++slot) {
-                const int r = slot >> 2, q = (slot & 3) ^ rf::swz(r), key = 16 * kt + r;
-                for (int e = 0; e < 2; ++e)
-                    for (int half = 0; half < 2; ++half)
-                        kl.push_back(make_int2((P0 + Lay::K_OFF + 3 * kt + e) * 128 + slot * 2 + half,
-                                               key < L ? (key * ld + (e ? h1 : h0) * DH + 16 * half + 4 * q) / 4 : -1));
-                kl.push_back(make_int2((P0 + Lay::K_OFF + 3 * kt + 2) * 128 + slot * 2 + 0, (key < L && q < 2) ? (key * ld + h0 * DH + 32 + 4 * q) / 4 : -1));
-                kl.push_back(make_int2((P0 + Lay::K_OFF + 3 * kt + 2) * 128 + slot * 2 + 1, (key < L && q >= 2) ? (key * ld + h1 * DH + 32 + 4 * (q - 2)) / 4 : -1));
-            }
-        for (int j = 0; j < 5; ++j)
-            for (int s = 0; s < 5; ++s)
-                for (int slot = 0; slot < 64; ++slot) {
-                    const int r = slot >> 2, q = (slot & 3) ^ rf::swz(r), ch = pair_channel(h0, j, r);
-                    for (int jj = 0; jj < 8; ++jj) {
-                        const int key = 32 * s + 16 * (jj >> 2) + 4 * q + (jj & 3);
-                        vl.push_back(make_int2((P0 + Lay::V_OFF + 5 * j + s) * 512 + slot * 8 + jj, key < L ? key * ld + C + ch : -1));
-                    }
-                }
-    }
-    BindPlan plan;
-    plan.nk = (int)kl.size();
-    plan.nv = (int)vl.size();
-    LAVIE_HIP(hipMalloc(&plan.k_pairs, kl.size() * sizeof(int2)));
-    LAVIE_HIP(hipMalloc(&plan.v_pairs, vl.size() * sizeof(int2)));
-    LAVIE_HIP(hipMemcpy(plan.k_pairs, kl.data(), kl.size() * sizeof(int2), hipMemcpyHostToDevice));
-    LAVIE_HIP(hipMemcpy(plan.v_pairs, vl.data(), vl.size() * sizeof(int2), hipMemcpyHostToDevice));
-    *out = &(g_bind_plans[L] = plan);
-    return 0;
-}
-
-int bind_cross_block_long(const half_t* tmpl, const half_t* kv, int B, int L, int C, half_t* img, hipStream_t stream) {
-    LAVIE_CHECK(C == xb::C && L >= xbl::MINL && L <= xbl::MAXL && B >= 1, "cross_block_long: C=%d L=%d B=%d is not built", C, L, B);
-    BindPlan* plan = nullptr;
-    if (int rc = bind_plan_long(L, &plan)) return rc;
-    const size_t IMG = xbl::IMG_BYTES;
+    if (int rc = bind_plan<NKT>(L, &plan)) return rc;
+    constexpr size_t IMG = Host::IMG_BYTES;
     for (int b = 0; b < B; ++b)
         LAVIE_HIP(hipMemcpyAsync(reinterpret_cast<char*>(img) + b * IMG, tmpl, IMG, hipMemcpyDeviceToDevice, stream));
     hipLaunchKernelGGL(xb_gather8_kernel, dim3(cdiv(plan->nk, 256), B), dim3(256), 0, stream, (const uint2*)kv, (uint2*)img, plan->k_pairs,
@@ -269,6 +216,9 @@ int bind_cross_block_long(const half_t* tmpl, const half_t* kv, int B, int L, in
                        (size_t)L * 2 * C, IMG / 2);
     LAVIE_HIP(hipGetLastError());
     return 0;
+}
+int bind_cross_block(CrossVariant v, const half_t* tmpl, const half_t* kv, int B, int L, int C, half_t* img, hipStream_t stream) {
+    return XB_VARIANT(v, bind_impl, tmpl, kv, B, L, C, img, stream);
 }
 
 struct CrossBlockParams {
@@ -658,50 +608,34 @@ __global__ __launch_bounds__(rf::THREADS, 2) void cross_block_kernel(const Cross
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-
-int launch_cross_block(const half_t* att, const half_t* x, half_t* y, int M, int rows_per_batch, int C, int heads, const half_t* img,
+template <int NKT>
+static int launch_impl(const half_t* att, const half_t* x, half_t* y, int M, int rows_per_batch, int C, int heads, const half_t* img,
                        const float* bo1, const float* gamma, const float* beta, const float* bo2, int L, float scale, float eps,
                        hipStream_t stream) {
-    LAVIE_CHECK(cross_block_supported(C, heads, L, rows_per_batch), "cross_block: C=%d heads=%d L=%d rows_per_batch=%d is not built", C, heads, L,
-                rows_per_batch);
-    LAVIE_CHECK(att && x && y && img && bo1 && gamma && beta && bo2 && M > 0 && M % rows_per_batch == 0, "cross_block: bad arguments");
+    using Host = XbHost<NKT>;
+    LAVIE_CHECK(cross_block_variant(C, heads, L, rows_per_batch) == (NKT == 5 ? CROSS_SHORT : CROSS_LONG),
+                "%s: C=%d heads=%d L=%d rows_per_batch=%d is not built", Host::NAME, C, heads, L, rows_per_batch);
+    LAVIE_CHECK(att && x && y && img && bo1 && gamma && beta && bo2 && M > 0 && M % rows_per_batch == 0, "%s: bad arguments", Host::NAME);
     const double tok = (double)M;
     // algorithmic work: Wo1, Wq2, Wo2 and the two attention products over L keys; bytes: att and x in, x'' out, the image once
     ProfileScope prof(KC_FUSED_CROSS, stream, 2.0 * tok * C * 3.0 * C + 4.0 * tok * L * C,
-                      2.0 * 3.0 * tok * C + (double)(M / rows_per_batch) * xb::IMG_BYTES, /*kernel_events=*/true);
+                      2.0 * 3.0 * tok * C + (double)(M / rows_per_batch) * Host::IMG_BYTES, /*kernel_events=*/true);
     CrossBlockParams p;
     p.att = att; p.x = x; p.y = y; p.img = img; p.bo1 = bo1; p.gamma = gamma; p.beta = beta; p.bo2 = bo2;
     p.tiles = M / rf::TOK; p.tiles_per_batch = rows_per_batch / rf::TOK; p.L = L; p.scale = scale; p.eps = eps;
     constexpr int lds = rf::RING_BYTES + xb::VEC_BYTES;
     const int grid = p.tiles < 256 ? p.tiles : 256;
-    auto kern = cross_block_kernel<8>;      // LDS read-ahead depth 8
+    auto kern = cross_block_kernel<8 + (NKT == 5 ? 0 : XB_LONG)>;      // LDS read-ahead depth 8
     if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc;     // once per kernel address, not per launch
     if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);
     else hipLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, p);
     LAVIE_HIP(hipGetLastError());
     return 0;
 }
-
-int launch_cross_block_long(const half_t* att, const half_t* x, half_t* y, int M, int rows_per_batch, int C, int heads, const half_t* img,
-                            const float* bo1, const float* gamma, const float* beta, const float* bo2, int L, float scale, float eps,
-                            hipStream_t stream) {
-    LAVIE_CHECK(cross_block_long_supported(C, heads, L, rows_per_batch), "cross_block_long: C=%d heads=%d L=%d rows_per_batch=%d is not built",
-                C, heads, L, rows_per_batch);
-    LAVIE_CHECK(att && x && y && img && bo1 && gamma && beta && bo2 && M > 0 && M % rows_per_batch == 0, "cross_block_long: bad arguments");
-    const double tok = (double)M;
-    ProfileScope prof(KC_FUSED_CROSS, stream, 2.0 * tok * C * 3.0 * C + 4.0 * tok * L * C,
-                      2.0 * 3.0 * tok * C + (double)(M / rows_per_batch) * xbl::IMG_BYTES, /*kernel_events=*/true);
-    CrossBlockParams p;
-    p.att = att; p.x = x; p.y = y; p.img = img; p.bo1 = bo1; p.gamma = gamma; p.beta = beta; p.bo2 = bo2;
-    p.tiles = M / rf::TOK; p.tiles_per_batch = rows_per_batch / rf::TOK; p.L = L; p.scale = scale; p.eps = eps;
-    constexpr int lds = rf::RING_BYTES + xb::VEC_BYTES;
-    const int grid = p.tiles < 256 ? p.tiles : 256;
-    auto kern = cross_block_kernel<8 + XB_LONG>;      // LDS read-ahead depth 8, ten key tiles
-    if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc;
-    if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);
-    else hipLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, p);
-    LAVIE_HIP(hipGetLastError());
-    return 0;
+int launch_cross_block(CrossVariant v, const half_t* att, const half_t* x, half_t* y, int M, int rows_per_batch, int C, int heads,
+                       const half_t* img, const float* bo1, const float* gamma, const float* beta, const float* bo2, int L, float scale,
+                       float eps, hipStream_t stream) {
+    return XB_VARIANT(v, launch_impl, att, x, y, M, rows_per_batch, C, heads, img, bo1, gamma, beta, bo2, L, scale, eps, stream);
 }
 
 }  // namespace lavie

@@ -200,6 +200,35 @@ def test_lora_apply_with_cached_154_token_context_equals_fresh_build(wide):
     del fresh
 
 
+def test_one_engine_serves_77_154_77_tokens_like_fresh_engines(wide):
+    """One engine handle serving context lengths 77 -> 154 -> 77 in turn, each turn cache_context then one forward: the short
+    images, the long templates built by the first long context, then the short layout in the front of the larger images.  Every
+    output equals, bit for bit, that of a fresh engine that only ever saw that length, and the fused text kernel ran each time."""
+    _, sd = wide
+    g = torch.Generator().manual_seed(53)
+    lat = torch.randn(1, 4, 16, 8, 8, generator=g).half()
+    x = torch.cat([lat, lat]).cuda()
+    ctxs = {L: torch.randn(2, L, 768, generator=g).half().cuda() for L in (77, 154)}
+
+    def turn(net, L):
+        net.prepare(2, 16, 8, 8, L)
+        try:
+            y, n = counted(net, x, 600, net.cache_context(ctxs[L]), 1 << KC_FUSED_CROSS, 64)
+        finally:
+            net.cache_context(None)
+        assert n[KC_FUSED_CROSS] == 5, n          # down 0 (x2), up 1 (x3): no silent GEMM route
+        return y
+
+    want = {}
+    for L in (77, 154):
+        fresh = build(sd, **WIDE_KW)
+        want[L] = turn(fresh, L)
+        del fresh
+    net = build(sd, **WIDE_KW)
+    for L in (77, 154, 77):
+        assert torch.equal(turn(net, L), want[L]), L
+
+
 # ------------------------------------------------------------------ 4. the guided pipeline with a mapper
 def test_guided_pipeline_with_mapper_vs_oracle_loop(small):
     """Three guided DDPM steps on the small model with a small random mapper and precomputed image features: the context the
