@@ -598,7 +598,9 @@ __global__ __launch_bounds__(64 * NW, (NCH == 5 && QT == 2) ? ATT_DMA_OCC5 : 1) 
                     // (a fully masked / -inf first tile keeps delta finite: 0)
                     float delta = t == 0 ? mx : fmaxf(mx, 0.f);
                     delta = delta > -1e30f ? delta : 0.f;
-                    const float alpha = __builtin_amdgcn_exp2f(-delta);        // first tile: O and l are still 0
+                    // first tile: O and l are still 0 and stay unscaled — a first tile whose best score is below -128 log2 units
+                    // (-88.7 nats) would make exp2(-delta) = +inf and 0 * inf = NaN for the rest of the row
+                    const float alpha = t == 0 ? 1.f : __builtin_amdgcn_exp2f(-delta);
                     const float nmr = negm[qt][0] - delta;                      // -(running maximum); negm is 0 before the first tile
                     if constexpr (!LSUM) l_run[qt] *= alpha;
 #pragma unroll

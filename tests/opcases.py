@@ -530,13 +530,150 @@ def merge_heads(t):
     return t.permute(0, 2, 1, 3).reshape(nb * l, heads * dh)
 
 
+def attention_route(dh, lq, lk, sc=False):
+    """The instantiation launch_attention picks (attention.hip:818-839 -> dispatch_att :797-816 -> launch_att_dma :750-777), as
+    a name: what the comment tables below and test_opcheck_host.py::test_attention_cases_reach_every_instantiation go by, and what
+    decides whether the model rounds Q' (only the V2 softmax does, attention.hip:432-440).  lk = the keys a query sees."""
+    if dh in (256, 512):
+        return "wide"                                                   # attention.hip:819, :829 -> attention_wide.hip
+    qt = 2 if lq > 64 * 3 else 1                                        # `big`, attention.hip:831
+    tag = ",sc" if sc else ""
+    nch = {40: 5, 80: 10, 160: 20}.get(dh) or (None if sc else {32: 4, 64: 8, 128: 16}.get(dh))      # :798-804
+    if nch:
+        short_keys = nch == 5 and lk <= 2 * 64                          # :759
+        if nch == 5 and qt == 2 and not short_keys and lq % 256 == 0:   # :760-762
+            return f"dma<{nch},QT2,V2,8 waves{tag}>"
+        v2 = nch <= 10 and not short_keys                               # :756, :770
+        return f"dma<{nch},QT{qt},{'V2' if v2 else 'round-3'},4 waves{tag}>"
+    lsum = dh % 16 != 0                                                 # :836 / :838
+    dhp = 64 if dh <= 64 else 96 if dh <= 96 else 160                   # :806-815
+    ndt = ",NDT4" if dh == 64 else ""                                   # :808 (sparse-causal only: plain dh 64 is on the DMA kernel)
+    return f"reg<{dhp},QT{qt},{'lsum' if lsum else 'sum'}{ndt}{tag}>"
+
+
+def rounds_q(dh, lq, lk, sc=False):
+    return "V2" in attention_route(dh, lq, lk, sc)
+
+
+# Every instantiation ops.attention / ops.sparse_causal_attention can reach, at QT 1 and QT 2 where the plain kernels have both and
+# at one of them for the sparse-causal twins off the interpolation model's head dims (40).  Not reachable, so not listed:
+# launch_att<64, *, false, false, 4> (attention.hip:808 without SC: plain head dim 64 is taken by the DMA kernel at :803 first) and
+# dma<5,QT2,round-3,sc> (QT 2 needs lq > 192, sparse-causal has lk = 2 lq, short_keys needs lk <= 128).
+ATT_ROUTES = ([f"dma<{n},QT{qt},V2,4 waves>" for n in (4, 5, 8, 10) for qt in (1, 2)] + ["dma<5,QT2,V2,8 waves>"]
+              + [f"dma<{n},QT{qt},round-3,4 waves>" for n in (5, 16, 20) for qt in (1, 2)]
+              + [f"reg<{dp},QT{qt},{sm}>" for dp, sm in ((64, "lsum"), (64, "sum"), (96, "lsum"), (96, "sum"), (160, "sum")) for qt in (1, 2)]
+              + [f"dma<5,QT{qt},V2,4 waves,sc>" for qt in (1, 2)] + ["dma<5,QT2,V2,8 waves,sc>", "dma<5,QT1,round-3,4 waves,sc>",
+                                                                     "dma<10,QT1,V2,4 waves,sc>", "dma<20,QT1,round-3,4 waves,sc>"]
+              + [f"reg<64,QT{qt},sum,NDT4,sc>" for qt in (1, 2)]
+              + [f"reg<{dp},QT1,{sm},sc>" for dp, sm in ((64, "lsum"), (64, "sum"), (96, "lsum"), (96, "sum"), (160, "sum"))] + ["wide"])
+
+PROFILES = ["far_below", "dominant_last", "creep", "mixed_wave"]
+
+
+def profile_applies(profile, lq, lk):
+    """lk: the keys of one key sequence that can be placed freely (sparse-causal: the d tokens of a frame)."""
+    if profile == "far_below":
+        return lk > 64                       # a whole first key tile below, the matching key behind it
+    if profile == "creep":
+        return lk > 128                      # three key tiles
+    if profile == "mixed_wave":
+        return lk > 65 and lq >= 32          # its matching key is lk - 2 (lk - 1 is the dominant one) and must lie behind the first tile
+    return lk >= 2
+
+
+def hard_rows(lq):
+    """Row 0, row lq - 1 and up to two rows between them, each in a 16-row group of its own (= other waves / query tiles)."""
+    groups = -(-lq // 16)
+    rows = {0, lq - 1}
+    for grp in (1, groups // 2):
+        if 0 < grp < (lq - 1) // 16:
+            rows.add(16 * grp + 5)
+    return sorted(rows)
+
+
+MIXED_ROWS = (18, 27)        # mixed_wave: (the dominant_last row, the far_below row), both in the 16-row group 1
+
+
+def apply_profile(profile, g, q, k, dh, qsrc, first64):
+    """Rewrites rows of q [nbq, lq, c] and k [nbk, lk, c] in place (heads packed along c).  qsrc[b]: the query batch entry whose
+    rows the dominant keys of key batch entry b are copied from; first64: the key batch entries whose keys 0..63 are the first
+    tile of a query.  Every constant is exact in fp16.  Returns what the case asserts on: far / creep rows (in every batch entry),
+    (key batch, row, key) triples of the dominant keys, and the index from the end of the key that matches a far_below row."""
+    lq, lk, c = q.shape[1], k.shape[1], q.shape[2]
+    u = (torch.randint(0, 2, (c,), generator=g) * 2 - 1).to(f16)           # one sign vector per head, side by side
+    hard = {"far": [], "dom": [], "creep": [], "match": 1}
+    rows = hard_rows(lq)
+
+    def far_below(rs, match):
+        for b in first64:
+            k[b, :64] = (-1.25 * u.float() + 0.1 * torch.randn(64, c, generator=g)).half()
+        k[:, lk - match] = u
+        # first-tile logits -20 sqrt(dh) nats (-25 sqrt(dh) below head dim 32, where -20 sqrt(dh) is above -100) as 16 x -1.25, not
+        # 4 x -5: a key of magnitude 5 multiplies the rounding of Q' in the logits of the UNIT rows that see it, and the fp32 model
+        # of sparse_causal[f2,d65,c320,far_below] then missed the bound at one element of a unit row (3.482e-03 > 3.457e-03)
+        q[:, rs] = (16 if dh >= 32 else 20) * u
+        hard["far"], hard["match"] = list(rs), match
+
+    def dominant(pairs):
+        for r, key in pairs:
+            for b in range(k.shape[0]):
+                k[b, key] = 3 * q[qsrc[b], r]
+            hard["dom"].append((r, key))
+
+    if profile == "far_below":
+        far_below(rows, 1)
+    elif profile == "dominant_last":
+        dominant([(rows[-1], lk - 1), (rows[0], lk - 2)])
+    elif profile == "creep":
+        s = torch.tensor(5 / (math.sqrt(dh) * LOG2E)).half()
+        q[:, rows] = u
+        for t in range(-(-lk // 64)):
+            k[:, min(64 * t + 3, lk - 1)] = ((t + 1) * s.float() * u.float()).half()
+        hard["creep"] = rows
+    elif profile == "mixed_wave":
+        far_below([MIXED_ROWS[1]], 2)
+        # the dominant row loses its component along u (per head) first: its key 3 q[r] then scores ~0 for the far_below row, whose
+        # logits are 16 x those of a unit row — against a random 3 q[r] they reach the matching key's, and the rounding of Q'
+        # (2^-12 of a logit of ~130 log2 units) then decides between two keys: the fp32 model missed the bound there at head dim 32
+        qd = q[:, MIXED_ROWS[0]].float().view(-1, c // dh, dh)
+        uu = u.float().view(c // dh, dh)
+        q[:, MIXED_ROWS[0]] = (qd - (qd * uu).sum(-1, keepdim=True) / dh * uu).view(-1, c).half()
+        dominant([(MIXED_ROWS[0], lk - 1)])
+    else:
+        raise ValueError(profile)
+    return hard
+
+
+def assert_profile(hard, qh, kh, scale, dom_batches, creep_tiles, key0=0):
+    """float64, on the values the kernel gets: qh [nb, heads, lq, dh], kh [nb, heads, keys, dh] as a query sees them; dom_batches:
+    the query batch entries whose rows the dominant keys were copied from; key0: where the key sequence apply_profile wrote to
+    starts among the keys a query sees (sparse-causal: the previous-frame half)."""
+    s = d(qh) @ d(kh).transpose(-1, -2) * scale                             # nats
+    if hard["far"]:
+        first, match = s[:, :, hard["far"], :64], s[:, :, hard["far"], s.shape[-1] - hard["match"]]
+        assert first.max() < -100 and match.min() > 0, (first.max().item(), match.min().item())
+    for r, key in hard["dom"]:
+        row = s[dom_batches, :, r]
+        rest = row.clone()
+        rest[..., [kk + o for _, kk in hard["dom"] for o in (0, key0)]] = -math.inf
+        assert (row[..., key0 + key] - rest.max(-1).values).min() > 0, (r, key)      # it is the row's maximum
+    if hard["creep"]:
+        tiles = F.pad(s[:, :, hard["creep"], :64 * creep_tiles], (0, max(64 * creep_tiles - s.shape[-1], 0)), value=-math.inf)
+        tiles = tiles.reshape(*s.shape[:2], len(hard["creep"]), creep_tiles, 64).max(-1).values * LOG2E     # best score per key tile
+        step = tiles[..., 1:] - tiles[..., :-1]
+        assert step.min() > 3.0 and step.max() < 8.0 and (tiles[..., -1] - tiles[..., 0]).min() > 8.0, (step.min().item(), step.max().item())
+
+
 @functools.lru_cache(maxsize=None)
-def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8):
+def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8, profile="unit"):
     """ops.attention on column slices of wider tensors whose other columns are NaN.  Self-attention (lk None): q | k | v are the
     thirds of one [nb*lq, 3c + 16] tensor; cross-attention: k | v are halves of a [(nb / kv_div) lk, 2c + 16] tensor.
     Rounding points: n = 3 at head dims up to 160 — Q' = fp16(Q scale log2 e) (attention.hip:437), P before the PV product
-    (attention.hip:625-626; 241-242 in the register-staged kernel, which has no Q' rounding), the output store (attention.hip:739 /
-    300); n = 2 at head dims 256 / 512 (attention_wide.hip:345-346 and 398)."""
+    (attention.hip:627-628; 241-242 in the register-staged kernel, which has no Q' rounding), the output store (attention.hip:741 /
+    300); n = 2 at head dims 256 / 512 (attention_wide.hip:345-346 and 398).  The round-3 softmax of the DMA kernel
+    (attention.hip:638-687, P at :679-680) has no Q' rounding either: the model rounds Q' where attention_route says V2; the bound
+    is round_c(3) for all of them.
+    profile: "unit" = N(0, 1) operands; the others (PROFILES, apply_profile) rewrite a few query rows and keys of those."""
     g = gen("attn", nb, lq, c, lk, kv_div, heads)
     dh = c // heads
     wide = dh > 160
@@ -544,6 +681,11 @@ def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8):
     lk_ = lk if cross else lq
     nkv = nb // kv_div
     q, k, v = rnd(g, nb * lq, c), rnd(g, nkv * lk_, c), rnd(g, nkv * lk_, c)
+    hard = None
+    if profile != "unit":
+        assert profile_applies(profile, lq, lk_), (profile, lq, lk_)
+        hard = apply_profile(profile, gen("attn-profile", nb, lq, c, lk, kv_div, heads, profile), q.view(nb, lq, c), k.view(nkv, lk_, c),
+                             dh, [b * kv_div for b in range(nkv)], range(nkv))
     nan = lambda r, w: torch.full((r, w), math.nan, dtype=f16)
     if cross:
         ins = {"qw": torch.cat([nan(nb * lq, 8), q, nan(nb * lq, 8)], 1), "kvw": torch.cat([k, nan(nkv * lk_, 16), v], 1)}
@@ -561,28 +703,96 @@ def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8):
         rep = lambda t: split_heads(t.reshape(nkv, lk_, c), nkv, heads).repeat_interleave(kv_div, 0)
         return split_heads(q.reshape(nb, lq, c), nb, heads), rep(k), rep(v)
 
+    if hard:
+        qh, kh, _ = heads_of()
+        assert_profile(hard, qh, kh, dh ** -0.5, [b * kv_div for b in range(nkv)], -(-lk_ // 64))
+
     def ref():
         y, sc = attn_ref(*heads_of(), dh ** -0.5)
         return {"y": (merge_heads(y), merge_heads(sc))}
 
-    return Case(f"attention[nb{nb},lq{lq},lk{lk},c{c},h{heads},div{kv_div}]", ins, {"y": ((nb * lq, c), f16)}, run, ref,
-                oc.round_c(2 if wide else 3), lambda: {"y": merge_heads(attn_model(*heads_of(), dh ** -0.5, not wide))},
-                oc.loc_heads(heads, dh))
+    name = f"attention[nb{nb},lq{lq},lk{lk},c{c},h{heads},div{kv_div}" + ("]" if profile == "unit" else f",{profile}]")
+    case = Case(name, ins, {"y": ((nb * lq, c), f16)}, run, ref, oc.round_c(2 if wide else 3),
+                lambda: {"y": merge_heads(attn_model(*heads_of(), dh ** -0.5, rounds_q(dh, lq, lk_)))}, oc.loc_heads(heads, dh))
+    case.route = attention_route(dh, lq, lk_)
+    case.hard = hard
+    return case
 
 
 SELF_ATTN = [(1, 1, 256), (2, 33, 320), (1, 65, 320), (1, 129, 1280)]
 CROSS_ATTN = [(lk, div) for lk in (1, 10, 77) for div in (1, 3)]
 WIDE_ATTN = [(1, 512), (33, 512), (65, 512), (33, 256)]
 
+# The smallest shape that reaches each instantiation, 8 heads; run under every profile that applies (profile_applies).
+# QT 2 from lq = 193 (attention.hip:831), the 8-wave kernel at lq % 256 == 0 (:762), V2 at head dim 40 from lk = 129 (:759).
+# (nb, lq, c)              head dim   instantiation (attention_route)           decided at
+SELF_HARD = [
+    (1, 129, 320),       # 40         dma<5,QT1,V2,4 waves>   three key tiles, the last holding one key    :798, :759, :770
+    (1, 193, 320),       # 40         dma<5,QT2,V2,4 waves>                                                :831, :762
+    (2, 256, 320),       # 40         dma<5,QT2,V2,8 waves>                                                :762-763
+    (1, 65, 640),        # 80         dma<10,QT1,V2,4 waves>  (every key count: short_keys is head dim 40's)  :799, :756
+    (1, 193, 640),       # 80         dma<10,QT2,V2,4 waves>
+    (1, 129, 256),       # 32         dma<4,QT1,V2,4 waves>                                                :802
+    (1, 193, 256),       # 32         dma<4,QT2,V2,4 waves>
+    (1, 129, 512),       # 64         dma<8,QT1,V2,4 waves>                                                :803
+    (1, 193, 512),       # 64         dma<8,QT2,V2,4 waves>
+    (1, 129, 1024),      # 128        dma<16,QT1,round-3,4 waves>                                          :804, :756
+    (1, 193, 1024),      # 128        dma<16,QT2,round-3,4 waves>
+    (1, 129, 1280),      # 160        dma<20,QT1,round-3,4 waves>   (its unit case is SELF_ATTN's)         :800
+    (1, 193, 1280),      # 160        dma<20,QT2,round-3,4 waves>
+    (1, 65, 192),        # 24         reg<64,QT1,lsum>                                                     :807
+    (1, 193, 192),       # 24         reg<64,QT2,lsum>
+    (1, 65, 384),        # 48         reg<64,QT1,sum>                                                      :809
+    (1, 193, 384),       # 48         reg<64,QT2,sum>
+    (1, 65, 576),        # 72         reg<96,QT1,lsum>                                                     :812
+    (1, 193, 576),       # 72         reg<96,QT2,lsum>   (not in the issue's list: the QT 2 form of the one above)
+    (1, 65, 768),        # 96         reg<96,QT1,sum>                                                      :813
+    (1, 193, 768),       # 96         reg<96,QT2,sum>
+    (1, 65, 1152),       # 144        reg<160,QT1,sum>                                                     :815
+    (1, 193, 1152),      # 144        reg<160,QT2,sum>   (not in the issue's list: the QT 2 form of the one above)
+]
+# (nb, lq, lk, c, kv_div)
+CROSS_HARD = [
+    (3, 40, 128, 320, 1), (3, 40, 128, 320, 3),     # 40   dma<5,QT1,round-3,4 waves>: lk = 2 * 64 is still short_keys       :759
+    (3, 40, 129, 320, 1), (3, 40, 129, 320, 3),     # 40   dma<5,QT1,V2,4 waves>: one key past it
+    (3, 193, 77, 320, 3),                           # 40   dma<5,QT2,round-3,4 waves>: short_keys wins over QT 2 and 8 waves  :762, :770
+    (3, 40, 77, 640, 3),                            # 80   dma<10,QT1,V2,4 waves>: V2 at 77 keys
+    (1, 129, 321, 320, 1), (1, 129, 321, 640, 1),   # 40 / 80  V2, six key tiles: `creep` passes the rescale threshold twice
+]
+# (lq = lk, c), one head: attention_wide.hip (64-key tiles, a running maximum that is always finite)
+WIDE_HARD = [(65, 512), (33, 256)]
+
+
+def with_profiles(shapes, lq_of, lk_of, have_unit=()):
+    """shapes x the profiles that apply; "unit" too, unless the shape already has its unit case in the lists above"""
+    return [(s, p) for s in shapes for p in ["unit"] + PROFILES
+            if (s not in have_unit if p == "unit" else profile_applies(p, lq_of(s), lk_of(s)))]
+
+
+SELF_HARD_CASES = with_profiles(SELF_HARD, lambda s: s[1], lambda s: s[1], SELF_ATTN)
+CROSS_HARD_CASES = with_profiles(CROSS_HARD, lambda s: s[1], lambda s: s[2])
+WIDE_HARD_CASES = with_profiles(WIDE_HARD, lambda s: s[0], lambda s: s[0], WIDE_ATTN)
+
 
 @functools.lru_cache(maxsize=None)
-def sparse_causal_case(frames, dd, c=320, heads=8, videos=2):
-    """Frame f attends to [frame 0 || frame max(f - 1, 0)] of its video; same kernels and rounding points as attention_case (n = 3)."""
+def sparse_causal_case(frames, dd, c=320, heads=8, videos=2, profile="unit"):
+    """Frame f attends to [frame 0 || frame max(f - 1, 0)] of its video; same kernels and rounding points as attention_case (n = 3).
+    Profiles are laid out in token space: the far-below keys are the first 64 tokens of frame 0, the matching / dominant keys the
+    last tokens of every frame (= the end of the previous-frame half), the dominant ones copied from the rows of the frame that
+    sees them there.  With two frames both halves of the key sequence are frame 0, so `creep` climbs over the tiles of the first
+    half only (it needs three: d > 128) and the second half repeats it from below."""
     g = gen("sc", frames, dd, c)
     nb, dh = videos * frames, c // heads
     qkv = rnd(g, nb * dd, 3 * c)
-    ins = {"qkv": qkv}
     prev = torch.tensor([vi * frames + (0, max(fi - 1, 0))[j] for vi in range(videos) for fi in range(frames) for j in (0, 1)])
+    hard = None
+    if profile != "unit":
+        assert profile_applies(profile, dd, dd), (profile, dd)
+        q, k = (qkv.view(nb, dd, 3 * c)[:, :, i * c:(i + 1) * c] for i in (0, 1))
+        nxt = [vi * frames + min(fi + 1, frames - 1) for vi in range(videos) for fi in range(frames)]
+        hard = apply_profile(profile, gen("sc-profile", frames, dd, c, heads, videos, profile), q, k, dh, nxt,
+                             [vi * frames for vi in range(videos)])
+    ins = {"qkv": qkv}
 
     def run(ops, i, o):
         t = i["qkv"]
@@ -593,15 +803,51 @@ def sparse_causal_case(frames, dd, c=320, heads=8, videos=2):
         kk, vv = (t[prev].reshape(nb, 2 * dd, c) for t in (k, v))
         return split_heads(q, nb, heads), split_heads(kk, nb, heads), split_heads(vv, nb, heads)
 
+    if hard:
+        qh, kh, _ = heads_of()
+        # a dominant key is copied from the frame after its own: the rows of that frame see it at the end of their second half
+        seen_by = [b for b in range(nb) if nxt[int(prev[2 * b + 1])] == b]
+        assert_profile(hard, qh, kh, dh ** -0.5, seen_by, -(-dd // 64), key0=dd)
+
     def ref():
         y, sc = attn_ref(*heads_of(), dh ** -0.5)
         return {"y": (merge_heads(y), merge_heads(sc))}
 
-    return Case(f"sparse_causal[f{frames},d{dd}]", ins, {"y": ((nb * dd, c), f16)}, run, ref, oc.round_c(3),
-                lambda: {"y": merge_heads(attn_model(*heads_of(), dh ** -0.5, True))}, oc.loc_heads(heads, dh))
+    name = f"sparse_causal[f{frames},d{dd}]" if (c, profile) == (320, "unit") else f"sparse_causal[f{frames},d{dd},c{c},{profile}]"
+    case = Case(name, ins, {"y": ((nb * dd, c), f16)}, run, ref, oc.round_c(3),
+                lambda: {"y": merge_heads(attn_model(*heads_of(), dh ** -0.5, rounds_q(dh, dd, 2 * dd, True)))}, oc.loc_heads(heads, dh))
+    case.route = attention_route(dh, dd, 2 * dd, True)
+    case.hard = hard
+    return case
 
 
 SPARSE_CAUSAL = [(1, 5), (3, 5), (2, 65)]
+# (frames, d, c)           head dim   instantiation                                   decided at
+SC_HARD = [
+    (2, 65, 320),        # 40         dma<5,QT1,V2,4 waves,sc>  (130 keys; (1, 5) and (3, 5) above: round-3, 10 keys)   :798, :759
+    (2, 193, 320),       # 40         dma<5,QT2,V2,4 waves,sc>                                                         :831
+    (2, 256, 320),       # 40         dma<5,QT2,V2,8 waves,sc>                                                         :762
+    (2, 65, 640),        # 80         dma<10,QT1,V2,4 waves,sc>                                                        :799
+    (2, 65, 1280),       # 160        dma<20,QT1,round-3,4 waves,sc>                                                   :800
+    (2, 65, 512),        # 64         reg<64,QT1,sum,NDT4,sc>   (the DMA kernel's :803 is not compiled for SC)          :808
+    (2, 193, 512),       # 64         reg<64,QT2,sum,NDT4,sc>
+    # not in the issue's list: the sparse-causal twins of the register-staged instantiations, which dispatch_att<true> selects
+    # for head dims the interpolation model does not have (24, 48, 72, 96, 128)                                       :806-815
+    (2, 65, 192),        # 24         reg<64,QT1,lsum,sc>
+    (2, 65, 384),        # 48         reg<64,QT1,sum,sc>
+    (2, 65, 576),        # 72         reg<96,QT1,lsum,sc>
+    (2, 65, 768),        # 96         reg<96,QT1,sum,sc>
+    (2, 65, 1024),       # 128        reg<160,QT1,sum,sc>
+]
+SC_HARD_CASES = with_profiles(SC_HARD, lambda s: s[1], lambda s: s[1], [(f, dd, 320) for f, dd in SPARSE_CAUSAL])
+
+
+def attention_hard_cases():
+    cs = [attention_case(*s, profile=p) for s, p in SELF_HARD_CASES]
+    cs += [attention_case(nb, lq, c, lk=lk, kv_div=div, profile=p) for (nb, lq, lk, c, div), p in CROSS_HARD_CASES]
+    cs += [attention_case(1, l, c, heads=1, profile=p) for (l, c), p in WIDE_HARD_CASES]
+    cs += [sparse_causal_case(f, dd, c=c, profile=p) for (f, dd, c), p in SC_HARD_CASES]
+    return cs
 
 
 # ------------------------------------------------------------------ temporal attention and the row-resident fused blocks
@@ -947,6 +1193,7 @@ def all_cases():
     cs += [attention_case(3, 40, 320, lk=lk, kv_div=div) for lk, div in CROSS_ATTN]
     cs += [attention_case(1, l, c, heads=1) for l, c in WIDE_ATTN]
     cs += [sparse_causal_case(*s) for s in SPARSE_CAUSAL]
+    cs += attention_hard_cases()
     cs += [temporal_attention_case(*sh, False) for sh in TATTN_SHAPES] + [temporal_attention_case(1, 17, 5, 256, False, plain=True)]
     cs += [geglu_mlp_case(M, False) for M in (1, 129)] + [cross_block_case(*sh, False) for sh in CROSS_BLOCKS]
     cs += [temporal_block_case(1, 1, False), temporal_block_case(2, 13, False)]

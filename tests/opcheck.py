@@ -194,3 +194,15 @@ def run_guarded(fn, inputs, outputs, alias=None, device="cuda", sync=None):
             raise AssertionError(f"{k}: {diff.numel()} elements depend on what surrounds the operands (output poison / input bands), "
                                  f"first at {g._where(int(diff[0]))}")
     return res
+
+
+def check_case(ops, case, forced=(0, 0), sync=None, device="cuda"):
+    """One case of tests/opcases.py through run_guarded and its per-element bound.  forced: the (tile, splits) the caller's fixture
+    set, which a case that forces a kernel of its own restores afterwards."""
+    def fn(i, o):
+        if case.setup is not None:
+            with case.setup(tuple(forced)):
+                case.run(ops, i, o)
+        else:
+            case.run(ops, i, o)
+    case.check(run_guarded(fn, case.inputs, case.outputs, alias=case.alias, device=device, sync=sync))

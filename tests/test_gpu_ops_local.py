@@ -40,14 +40,7 @@ def check(ops, case, refusal=None):
         with pytest.raises(RuntimeError, match=refusal):
             check(ops, case)
         return
-    def fn(i, o):
-        if case.setup is not None:
-            with case.setup(tuple(_forced)):
-                case.run(ops, i, o)
-        else:
-            case.run(ops, i, o)
-    got = oc.run_guarded(fn, case.inputs, case.outputs, alias=case.alias, sync=torch.cuda.synchronize)
-    case.check(got)
+    oc.check_case(ops, case, forced=_forced, sync=torch.cuda.synchronize)
 
 
 @pytest.mark.parametrize("opt", C.LINEAR_OPTIONS)

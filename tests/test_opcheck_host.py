@@ -121,6 +121,60 @@ def test_attention_one_dropped_key():
     fails_at(case, bad, "(token 5, head 3, dim")
 
 
+def test_attention_cases_reach_every_instantiation():
+    """the shape tables of opcases.py against the dispatch of attention.hip, as attention_route reads it"""
+    reached = {c.route for c in CASES if hasattr(c, "route")}
+    assert reached == set(C.ATT_ROUTES), (sorted(set(C.ATT_ROUTES) - reached), sorted(reached - set(C.ATT_ROUTES)))
+    for profile in C.PROFILES:          # and each V2 instantiation under each profile it has room for (creep: three key tiles)
+        got = {c.route for c in CASES if hasattr(c, "route") and c.name.endswith(profile + "]")}
+        need = {r for r in C.ATT_ROUTES if "V2" in r and not (profile in ("creep", "mixed_wave") and "QT1" in r and "sc" in r)}
+        # (sparse-causal QT 1 is d = 65: two key tiles a half, and token d - 2 lies in the first of them)
+        assert need <= got, (profile, sorted(need - got))
+
+
+@pytest.fixture(scope="module")
+def far_below():
+    case = C.attention_case(1, 193, 320, profile="far_below")
+    assert case.route == "dma<5,QT2,V2,4 waves>" and case.hard["far"] == [0, 21, 101, 192]
+    return case, case.model()["y"]
+
+
+def test_attention_far_below_rows_nan(far_below):
+    """what 0 * exp2(+huge) in the first key tile leaves in O and l: the hard rows NaN, everything else right"""
+    case, y = far_below
+    bad = y.clone()
+    bad[case.hard["far"]] = float("nan")
+    with pytest.raises(AssertionError) as e:
+        case.check({"y": bad})
+    assert "%d of %d elements" % (4 * 320, y.numel()) in str(e.value), str(e.value)
+    assert any("(token %d, head" % r in str(e.value) for r in case.hard["far"]), str(e.value)
+
+
+@pytest.mark.parametrize("n_rows", [4, 1])
+def test_attention_far_below_rows_never_rescaled(far_below, n_rows):
+    """The hard rows are the softmax over the first key tile alone (a kernel that never moved its running maximum): the check
+    fails at a hard row and names it.  This defect is NOT one the whole-tensor criterion passes, with four hard rows or with one:
+    a hard row's right output is the matching key's V row (|v| ~ 1 per element) and the other 189 rows are averages over ~190
+    keys (~0.1 per element), so the hard rows carry most of the tensor's norm: rel_l2 = 0.81 with four rows, 0.40 with one,
+    against TOL_OP = 2e-3.  rel-L2 never saw the first-tile defect because no input of the suite had such rows; it is asserted
+    here as what it is, far above TOL_OP."""
+    case, y = far_below
+    rows = case.hard["far"][:n_rows]
+    qkv = case.inputs["qkvw"].float()
+    q, k, v = qkv[:, :320], qkv[:, 328:648], qkv[:, 656:]
+    bad = y.clone()
+    for r in rows:
+        for h in range(8):
+            hs = slice(40 * h, 40 * h + 40)
+            bad[r, hs] = (torch.softmax((q[r, hs] * 40 ** -0.5) @ k[:64, hs].t(), 0) @ v[:64, hs]).half()
+    with pytest.raises(AssertionError) as e:
+        case.check({"y": bad})
+    assert any("(token %d, head" % r in str(e.value) for r in rows), str(e.value)
+    bad_tokens = (~((bad.double() - case.ref["y"][0]).abs() <= oc.U16 * case.ref["y"][0].abs() + case.c * case.ref["y"][1])).any(1).nonzero().flatten().tolist()
+    assert bad_tokens == rows, bad_tokens                       # the hard rows and nothing else
+    assert rel_l2(bad, case.ref["y"][0]) > 100 * TOL_OP
+
+
 # ------------------------------------------------------------------ bands and poison, on CPU tensors
 def test_guard_geometry_and_patterns():
     for dtype, pattern in ((torch.float16, oc.NAN16), (torch.float32, oc.NAN32)):
