@@ -108,6 +108,11 @@ int lavie_pack_temporal_conv_f16(const void* w, void* out, int Cout, int Cin, in
  * (mean, rstd) of the rows of A.  Never splits K. */
 int lavie_linear_lnfold_f16(const void* A, const void* Wf, const float* bias, const float* ln_s, const float* ln_stats, void* C,
                             int M, int N, int K, void* stream);
+/* The same with the GEGLU epilogue (the feed-forward's first projection behind a folded LayerNorm; additive in this ABI version):
+ * C [M, N / 2] = h * gelu(gate) of the folded pre-activations.  Wf, bias and ln_s are in lavie_pack_geglu_f16's row order (pack Wf
+ * with it; bias and ln_s take the same row permutation).  N % 128 == 0.  Never splits K. */
+int lavie_linear_lnfold_geglu_f16(const void* A, const void* Wf, const float* bias, const float* ln_s, const float* ln_stats, void* C,
+                                  int M, int N, int K, void* stream);
 /* GEGLU projection [2*inner, K] (+ bias) -> 16-row value/gate interleave expected by lavie_linear_f16(geglu=1). */
 int lavie_pack_geglu_f16(const void* w, const void* bias_f16, void* w_out, float* bias_out, int N, int K, void* stream);
 

@@ -70,6 +70,21 @@ int lavie_linear_lnfold_f16(const void* A, const void* Wf, const float* bias, co
     return op_launch(p, false, EPI_LINEAR, S(stream));      // (unsplit: a LayerNorm fold)
 }
 
+// ... with the GEGLU epilogue: the engine's ff1 behind a folded norm3 (engine.cpp `ln_proj(t.ff1, ..., EPI_GEGLU)`).  Wf, bias and ln_s
+// are in lavie_pack_geglu_f16's row order (the engine packs all three with one permutation); C [M, N / 2]
+int lavie_linear_lnfold_geglu_f16(const void* A, const void* Wf, const float* bias, const float* ln_s, const float* ln_stats, void* C,
+                                  int M, int N, int K, void* stream) {
+    LAVIE_CHECK(A && Wf && C && ln_s && ln_stats, "linear_lnfold_geglu: null tensor");
+    LAVIE_CHECK(K % IGEMM_BK == 0, "linear_lnfold_geglu: K=%d must be a multiple of %d", K, IGEMM_BK);
+    LAVIE_CHECK(N > 0 && N % 128 == 0, "linear_lnfold_geglu: N=%d must be a multiple of 128", N);
+    IgemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.A = H(A); p.lda = K; p.W = H(Wf); p.ldw = K; p.C = H(C); p.ldc = N / 2; p.ldr = N / 2; p.bias = bias; p.rows_per_batch = 1;
+    p.M = M; p.N = N; p.nk = K / IGEMM_BK;
+    p.ln_s = ln_s; p.ln_stats = ln_stats;
+    return op_launch(p, false, EPI_GEGLU, S(stream));
+}
+
 int lavie_lora_merge_f16(const void* W0, const float* A, const float* B, void* out, int N, int K, int r, float scale, void* stream) {
     return launch_lora_merge(H(W0), A, B, H(out), N, K, r, scale, S(stream));
 }

@@ -3,10 +3,14 @@
 // switch combination) -> cache_context -> forward (sequencing + every launcher's host side) -> error paths -> destroy, for the
 // base, interpolation and VSR variants of the engine at reduced widths.  Exit code 0 and a silent sanitizer = pass.
 // `hostcheck trace FILE` instead writes the launch trace of the cases in run_traces() to FILE (tests/golden/make_golden_trace.py).
+// `hostcheck optrace IN OUT` replays the operator calls listed in IN (run_optrace()) and writes their launches to OUT;
+// `hostcheck kernels OUT` lists every registered kernel name (tests/opcases.py: gemm_reach()).
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -14,6 +18,7 @@
 
 extern "C" long lavie_hostcheck_launches();
 extern "C" void lavie_hostcheck_trace_to(FILE* f);
+extern "C" void lavie_hostcheck_kernel_names_to(FILE* f);
 
 #define REQUIRE(cond)                                                                          \
     do {                                                                                       \
@@ -377,9 +382,114 @@ static void run_traces(const char* path) {
     printf("hostcheck: trace written (%ld stubbed kernel launches)\n", lavie_hostcheck_launches());
 }
 
+// ---- operator launch trace: IN holds one operator call per line, "<entry> key=int ..." — the entry point without lavie_ / _f16,
+// its integer arguments under the names of include/lavie_hip.h, 0 / 1 for each optional operand (bias, bias2, R, x2, sc1, sc2) and
+// force_tile / force_splits (default 0).  Tensors are never read.  OUT: "== <line>", then the stub's launch lines of that call, or
+// "!! refused" where the library returns an error (its message goes to stderr).  A line the driver cannot parse ends the run.
+static int run_optrace(const char* in_path, const char* out_path) {
+    FILE* in = fopen(in_path, "r");
+    REQUIRE(in != nullptr);
+    g_out = fopen(out_path, "w");
+    REQUIRE(g_out != nullptr);
+    lavie_hostcheck_trace_to(g_out);
+    static std::vector<unsigned short> buf(64);
+    void* d = buf.data();
+    const float* fd = (const float*)buf.data();
+    char line[1024];
+    int calls = 0;
+    while (fgets(line, sizeof(line), in)) {
+        std::string s = line;
+        while (!s.empty() && (s.back() == '\n' || s.back() == '\r' || s.back() == ' ')) s.pop_back();
+        if (s.empty() || s[0] == '#') continue;
+        std::istringstream is(s);
+        std::string entry, tok;
+        is >> entry;
+        std::map<std::string, long> a;
+        while (is >> tok) {
+            const size_t eq = tok.find('=');
+            if (eq == std::string::npos || eq == 0 || eq + 1 == tok.size()) { fprintf(stderr, "hostcheck optrace: bad token '%s' in '%s'\n", tok.c_str(), s.c_str()); return 2; }
+            char* end = nullptr;
+            a[tok.substr(0, eq)] = strtol(tok.c_str() + eq + 1, &end, 10);
+            if (*end) { fprintf(stderr, "hostcheck optrace: bad value in '%s'\n", tok.c_str()); return 2; }
+        }
+        std::map<std::string, bool> used;
+        bool missing = false;
+        auto I = [&](const char* k) -> int {            // a required integer
+            used[k] = true;
+            auto it = a.find(k);
+            if (it == a.end()) { fprintf(stderr, "hostcheck optrace: '%s' lacks %s\n", s.c_str(), k); missing = true; return 0; }
+            return (int)it->second;
+        };
+        auto O = [&](const char* k) -> int {            // an optional one: 0 when absent
+            used[k] = true;
+            auto it = a.find(k);
+            return it == a.end() ? 0 : (int)it->second;
+        };
+        auto P = [&](const char* k) -> void* { return O(k) ? d : nullptr; };
+        auto F = [&](const char* k) -> const float* { return O(k) ? fd : nullptr; };
+        const int tile = O("force_tile"), splits = O("force_splits");
+        fprintf(g_out, "== %s\n", s.c_str());
+        int rc = lavie_debug_force_tile(tile);
+        lavie_debug_force_splits(splits);
+        if (rc == 0) {
+            if (entry == "linear") {
+                const int lda = I("lda"), ldb2 = I("ldb2"), rpb = I("rows_per_batch"), ldr = I("ldr"), ldc = I("ldc"), M = I("M"), N = I("N"), K = I("K"), g = I("geglu");
+                if (!missing) rc = lavie_linear_f16(d, lda, d, F("bias"), F("bias2"), ldb2, rpb, P("R"), ldr, d, ldc, M, N, K, g, nullptr);
+            } else if (entry == "linear_lnfold" || entry == "linear_lnfold_geglu") {
+                const int M = I("M"), N = I("N"), K = I("K");
+                if (!missing)
+                    rc = entry == "linear_lnfold" ? lavie_linear_lnfold_f16(d, d, F("bias"), fd, fd, d, M, N, K, nullptr)
+                                                  : lavie_linear_lnfold_geglu_f16(d, d, F("bias"), fd, fd, d, M, N, K, nullptr);
+            } else if (entry == "conv3x3") {
+                const int C1 = I("C1"), C2 = I("C2"), SC1 = I("SC1"), SC2 = I("SC2"), ldb2 = I("ldb2"), rpb = I("rows_per_batch"), NI = I("NI"), Hi = I("Hi"),
+                          Wi = I("Wi"), Cout = I("Cout"), stride = I("stride"), ups = I("ups");
+                if (!missing)
+                    rc = lavie_conv3x3_f16(d, C1, P("x2"), C2, P("sc1"), SC1, P("sc2"), SC2, d, F("bias"), F("bias2"), ldb2, rpb, P("R"), d, NI, Hi, Wi,
+                                           Cout, stride, ups, d, nullptr);
+            } else if (entry == "conv3x3_down") {
+                const int C = I("C"), NI = I("NI"), Hi = I("Hi"), Wi = I("Wi"), Cout = I("Cout"), stride = I("stride"), pad_lo = I("pad_lo");
+                if (!missing) rc = lavie_conv3x3_down_f16(d, C, d, F("bias"), d, NI, Hi, Wi, Cout, stride, pad_lo, d, nullptr);
+            } else if (entry == "upsample_conv3x3") {
+                const int NI = I("NI"), Hi = I("Hi"), Wi = I("Wi"), C = I("C");
+                if (!missing) rc = lavie_upsample_conv3x3_f16(d, d, F("bias"), d, NI, Hi, Wi, C, d, nullptr);
+            } else if (entry == "temporal_conv") {
+                const int C = I("C"), ldb2 = I("ldb2"), rpb = I("rows_per_batch"), B = I("B"), Fr = I("F"), D = I("D"), Cout = I("Cout"), taps = I("taps");
+                if (!missing) rc = lavie_temporal_conv_f16(d, C, d, F("bias"), F("bias2"), ldb2, rpb, P("R"), d, B, Fr, D, Cout, taps, d, nullptr);
+            } else {
+                fprintf(stderr, "hostcheck optrace: unknown entry point '%s'\n", entry.c_str());
+                return 2;
+            }
+        }
+        if (missing) return 2;
+        for (const auto& kv : a)
+            if (!used.count(kv.first)) { fprintf(stderr, "hostcheck optrace: '%s' does not take %s\n", entry.c_str(), kv.first.c_str()); return 2; }
+        if (rc != 0) {
+            fprintf(g_out, "!! refused\n");
+            fprintf(stderr, "hostcheck optrace: '%s' refused: %s\n", s.c_str(), lavie_last_error());
+        }
+        ++calls;
+    }
+    REQUIRE(lavie_debug_force_tile(0) == 0);
+    lavie_debug_force_splits(0);
+    lavie_hostcheck_trace_to(nullptr);
+    fclose(g_out);
+    fclose(in);
+    printf("hostcheck: optrace written (%d calls, %ld stubbed kernel launches)\n", calls, lavie_hostcheck_launches());
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc == 3 && strcmp(argv[1], "trace") == 0) {
         run_traces(argv[2]);
+        return 0;
+    }
+    if (argc == 4 && strcmp(argv[1], "optrace") == 0) return run_optrace(argv[2], argv[3]);
+    if (argc == 3 && strcmp(argv[1], "kernels") == 0) {
+        FILE* f = fopen(argv[2], "w");
+        REQUIRE(f != nullptr);
+        lavie_hostcheck_kernel_names_to(f);
+        fclose(f);
+        printf("hostcheck: kernel names written\n");
         return 0;
     }
     REQUIRE(lavie_abi_version() == LAVIE_ABI_VERSION);
@@ -460,6 +570,17 @@ int main(int argc, char** argv) {
         REQUIRE(lavie_linear_lnfold_f16(x.data(), wq.data(), v.data(), s3.data(), st.data(), qkv.data(), 64, 960, 320, nullptr) == 0);
         REQUIRE(lavie_linear_lnfold_f16(x.data(), wq.data(), v.data(), nullptr, st.data(), qkv.data(), 64, 960, 320, nullptr) != 0);
         REQUIRE(lavie_linear_lnfold_f16(x.data(), wq.data(), v.data(), s3.data(), st.data(), qkv.data(), 64, 960, 300, nullptr) != 0);
+        // GEGLU behind the fold: [64, 960 / 2 ... ] needs N % 128 == 0 (640 of the 960 packed rows are used), null operands and a
+        // K off the 64-tile are refused before any HIP call
+        const long lg = lavie_hostcheck_launches();
+        REQUIRE(lavie_linear_lnfold_geglu_f16(x.data(), wq.data(), v.data(), s3.data(), st.data(), qkv.data(), 64, 640, 320, nullptr) == 0);
+        REQUIRE(lavie_hostcheck_launches() == lg + 1);
+        REQUIRE(lavie_linear_lnfold_geglu_f16(x.data(), wq.data(), v.data(), s3.data(), nullptr, qkv.data(), 64, 640, 320, nullptr) != 0);
+        REQUIRE(lavie_linear_lnfold_geglu_f16(x.data(), wq.data(), v.data(), nullptr, st.data(), qkv.data(), 64, 640, 320, nullptr) != 0);
+        REQUIRE(lavie_linear_lnfold_geglu_f16(x.data(), wq.data(), v.data(), s3.data(), st.data(), qkv.data(), 64, 640, 300, nullptr) != 0);
+        REQUIRE(lavie_linear_lnfold_geglu_f16(x.data(), wq.data(), v.data(), s3.data(), st.data(), qkv.data(), 64, 960, 320, nullptr) != 0);
+        REQUIRE(strstr(lavie_last_error(), "128") != nullptr);
+        REQUIRE(lavie_hostcheck_launches() == lg + 1);
     }
     {   // the multistep sampler step: every refusal comes before a HIP call; accepted calls reach the (stubbed) launch, vector body,
         // ragged tail and the one-element-per-lane form under guidance with n % 8 != 0

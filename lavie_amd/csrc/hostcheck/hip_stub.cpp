@@ -83,6 +83,12 @@ hipError_t hipExtLaunchKernel(const void* f, dim3 grid, dim3 block, void** args,
 }
 long lavie_hostcheck_launches() { return g_launches; }
 void lavie_hostcheck_trace_to(FILE* f) { g_trace = f; }
+// every kernel name the registration calls have seen, sorted, one per line (the driver's `kernels` mode)
+void lavie_hostcheck_kernel_names_to(FILE* f) {
+    std::map<std::string, int> names;
+    for (const auto& kv : kernel_names()) names[kv.second] = 1;
+    for (const auto& kv : names) fprintf(f, "%s\n", kv.first.c_str());
+}
 void** __hipRegisterFatBinary(const void*) { static void* h; return &h; }
 void __hipUnregisterFatBinary(void**) {}
 // kernel names: the demangled name without namespace, return type and parameter list, e.g. igemm_kernel<2, 2, 4, 5, 2, true, 0>

@@ -72,16 +72,18 @@ def linear(a, weight, bias=None, residual=None, bias2=None, rows_per_batch=0, ge
     return out
 
 
-def linear_lnfold(a, weight_folded, bias, ln_s, ln_stats, out=None):
+def linear_lnfold(a, weight_folded, bias, ln_s, ln_stats, geglu=False, out=None):
     """rstd_m (a @ weight_folded^T - mean_m ln_s) + bias: a projection behind a LayerNorm, the norm folded into the GEMM epilogue
-    (weight_folded = W * gamma, ln_s = its row sums, bias = W beta (+ b), ln_stats [M, 2] = (mean, rstd) of the rows of `a`)."""
-    _chk16(a, weight_folded)
+    (weight_folded = W * gamma, ln_s = its row sums, bias = W beta (+ b), ln_stats [M, 2] = (mean, rstd) of the rows of `a`).
+    geglu: h * gelu(gate) of that, [M, N / 2]; weight_folded, bias and ln_s in pack_geglu's row order."""
+    _chk16(a, weight_folded, out)
     _chk32(bias, ln_s, ln_stats)
     M, K = a.shape
     N = weight_folded.shape[0]
-    out = _out(out, (M, N), torch.float16, a.device, "linear_lnfold: out")
-    _lib.check(_lib.load().lavie_linear_lnfold_f16(_p(a), _p(weight_folded), _p(bias), _p(ln_s), _p(ln_stats), _p(out), M, N, K,
-                                                   _stream()), "lavie_linear_lnfold_f16")
+    n_out = N // 2 if geglu else N
+    out = _out(out, (M, n_out), torch.float16, a.device, "linear_lnfold: out")
+    name = "lavie_linear_lnfold_geglu_f16" if geglu else "lavie_linear_lnfold_f16"
+    _lib.check(getattr(_lib.load(), name)(_p(a), _p(weight_folded), _p(bias), _p(ln_s), _p(ln_stats), _p(out), M, N, K, _stream()), name)
     return out
 
 

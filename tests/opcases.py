@@ -6,6 +6,9 @@ torch fp32 model of the kernel with fp16 roundings at the counted points.
 Shapes are the smallest that cross each kernel's edges; none is a workload shape."""
 import functools
 import math
+import os
+import subprocess
+import tempfile
 import zlib
 
 import torch
@@ -23,6 +26,9 @@ class Case:
         self._ref = ref
         self.regions = regions or {}          # name -> bool mask over output "y": regions asserted on their own as well
         self.setup = setup                    # optional context manager factory (forced kernels)
+        self.calls = None                     # GEMM family: the C-ABI calls `run` makes (call()), replayed on the host-only build
+        self.force = None                     # (tile, splits) the case forces around its launch, whatever the variant
+        self.variants = None                  # the VARIANTS the case runs under where not all six (restricted(): the reach tables)
 
     @functools.cached_property
     def ref(self):
@@ -37,6 +43,23 @@ class Case:
             if k == "y":
                 for rname, mask in self.regions.items():
                     oc.assert_elementwise(got[k], ref, scale, c, where=w, label=f"{label}{self.name}:{k}:{rname}", mask=mask)
+
+
+# the six kernel choices the GPU operator tests run every case under: name -> (force_tile, force_splits)
+VARIANTS = {"auto": (0, 0), "row128-tiles": (1, 0), "split-k-3": (0, 3), "pingpong": (3, 0), "pingpong-split-k-2": (3, 2),
+            "ppx-persistent": (7, 0)}
+
+
+def call(entry, **ints):
+    """One C-ABI call of a GEMM-family case as lavie_amd/ops.py makes it: the entry point without lavie_ / _f16, its integer
+    arguments under the names of include/lavie_hip.h, 1 for each optional operand that is passed (bias, bias2, R, x2, sc1, sc2).
+    What `hostcheck optrace` replays (gemm_reach)."""
+    return entry, {k: int(v) for k, v in ints.items()}
+
+
+def with_calls(case, calls, force=None):
+    case.calls, case.force = calls, force
+    return case
 
 
 def gen(*seed):
@@ -90,9 +113,11 @@ def linear_case(M, N, K, opt):
             y = y + p(cv(ins["r"]))
         return y
 
-    return Case(f"linear[{M}x{N}x{K},{opt}]", ins, {"y": ((M, N), f16)}, run, lambda: {"y": (terms(d, False), terms(d, True))},
+    case = Case(f"linear[{M}x{N}x{K},{opt}]", ins, {"y": ((M, N), f16)}, run, lambda: {"y": (terms(d, False), terms(d, True))},
                 oc.gemm_c(K + 3), lambda: {"y": terms(lambda t: t.float(), False).half()}, oc.loc_rows(N),
                 alias={"y": "r"} if opt == "residual_in_place" else None)
+    return with_calls(case, [call("linear", lda=K, ldb2=N, rows_per_batch=rpb if "bias2" in ins else 0, ldr=N, ldc=N, M=M, N=N, K=K, geglu=0,
+                                  bias="bias" in ins, bias2="bias2" in ins, R="r" in ins)])
 
 
 def gelu64(x):
@@ -124,7 +149,8 @@ def geglu_case(M, C):
         h, gate = pre.chunk(2, -1)
         return {"y": (h * F.gelu(gate)).half()}
 
-    return Case(f"geglu[{M}x{C}]", ins, {"y": ((M, 4 * C), f16)}, run, ref, oc.round_c(1), model, oc.loc_rows(4 * C))
+    case = Case(f"geglu[{M}x{C}]", ins, {"y": ((M, 4 * C), f16)}, run, ref, oc.round_c(1), model, oc.loc_rows(4 * C))
+    return with_calls(case, [call("linear", lda=C, ldb2=8 * C, rows_per_batch=0, ldr=4 * C, ldc=4 * C, M=M, N=8 * C, K=C, geglu=1, bias=1)])
 
 
 @functools.lru_cache(maxsize=None)
@@ -154,7 +180,133 @@ def lnfold_case(M, N, K):
         acc = af @ wf.float().t()
         return {"y": (stats[:, 1:] * (acc - stats[:, :1] * s) + bf).half()}
 
-    return Case(f"lnfold[{M}x{N}x{K}]", ins, {"y": ((M, N), f16)}, run, ref, oc.gemm_c(K + 2), model, oc.loc_rows(N))
+    case = Case(f"lnfold[{M}x{N}x{K}]", ins, {"y": ((M, N), f16)}, run, ref, oc.gemm_c(K + 2), model, oc.loc_rows(N))
+    return with_calls(case, [call("linear_lnfold", M=M, N=N, K=K, bias=1)])
+
+
+def geglu_perm(N):
+    """lavie_pack_geglu_f16's row order: packed row n holds source row perm[n] — 16-row blocks alternating value / gate
+    (elementwise.hip geglu_src_row)."""
+    n = torch.arange(N)
+    j, i = n >> 5, n & 31
+    return torch.where(i < 16, 16 * j + i, N // 2 + 16 * j + (i - 16))
+
+
+@functools.lru_cache(maxsize=None)
+def lnfold_geglu_case(M, C):
+    """linear_lnfold(..., geglu=True): [M, C] -> [M, 4C], the feed-forward's first projection behind a folded LayerNorm.  lnfold_case's
+    fold (reference and scale of the pre-activations), then geglu_case's h gelu(gate) with its 1.13 slope term and its single fp16
+    rounding (igemm_epilogue.h:170); the folded weight, bias and row sums are formed in natural order and permuted into
+    pack_geglu's row order on the host, as the engine packs all three with one permutation (engine.cpp:446-448)."""
+    g = gen("lnfold_geglu", M, C)
+    N = 8 * C
+    a = (torch.randn(M, C, generator=g) * (0.5 + torch.rand(M, 1, generator=g)) + torch.randn(M, 1, generator=g)).half()
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    w = torch.randn(N, C, generator=g) / math.sqrt(C)
+    wf = (w * gamma).half()
+    s = wf.float().sum(1)
+    bf = (w @ beta + 0.1 * torch.randn(N, generator=g))
+    af = a.float()
+    stats = torch.stack([af.mean(1), (af.var(1, unbiased=False) + 1e-5).rsqrt()], 1).contiguous()
+    perm = geglu_perm(N)
+    ins = {"a": a, "wf": wf[perm].contiguous(), "bias": bf[perm].contiguous(), "s": s[perm].contiguous(), "stats": stats}
+
+    def run(ops, i, o):
+        ops.linear_lnfold(i["a"], i["wf"], i["bias"], i["s"], i["stats"], geglu=True, out=o["y"])
+
+    def ref():
+        mean, rstd = d(stats[:, :1]), d(stats[:, 1:])
+        pre = rstd * (d(a) @ d(wf).t() - mean * d(s)) + d(bf)
+        sc = rstd.abs() * (d(a).abs() @ d(wf).abs().t() + (mean * d(s)).abs()) + d(bf).abs()
+        h, gate = pre.chunk(2, -1)
+        sh, sg = sc.chunk(2, -1)
+        return {"y": (h * gelu64(gate), sh * gelu64(gate).abs() + h.abs() * 1.13 * sg)}
+
+    def model():
+        pre = stats[:, 1:] * (af @ wf.float().t() - stats[:, :1] * s) + bf
+        h, gate = pre.chunk(2, -1)
+        return {"y": (h * F.gelu(gate)).half()}
+
+    case = Case(f"lnfold_geglu[{M}x{C}]", ins, {"y": ((M, 4 * C), f16)}, run, ref, oc.round_c(1), model, oc.loc_rows(4 * C))
+    return with_calls(case, [call("linear_lnfold_geglu", M=M, N=N, K=C, bias=1)])
+
+
+# The smallest shape the planner (igemm.hip igemm_plan) sends to each GEMM-family instantiation that LINEAR_SHAPES, the two GEGLU and
+# the two lnfold shapes of the first tables do not reach, found with `hostcheck optrace` (gemm_reach) and asserted from it by
+# tests/test_gemm_reach_host.py.  Variants: the ones a case runs under — all six where the shape is small, else those whose trace
+# names the target.  "past the cap": more tiles than the persistent kernel's 256 workgroups, so that its deferred-epilogue path runs
+# (a second tile from 257 tiles on; first, steady-state and last tile in one workgroup from 513 on).
+#  instantiation                        case (M x N x K | M x C)            variants              rule that makes it the smallest
+#  igemm_ppx_kernel<0, 5, 2>            lnfold 160x320x320, 320x320x320     all (ppx-persistent)  M % 160 == 0, nk >= 5, N % 320 == 0 (igemm_ppx_eligible)
+#  igemm_ppx_kernel<0, 4, 2>            lnfold 160x256x320, 320x256x320     all (ppx-persistent)  ... N % 256 == 0 and N % 320 != 0
+#  igemm_ppx_kernel<1, 4, 0>            geglu 160x320 (N = 2560, K = 320)   all (ppx-persistent)  GEGLU: N = 8C % 256 == 0, nk = C / 64 >= 5 -> C = 320
+#  igemm_ppx_kernel<1, 4, 2>            lnfold_geglu 160x320                all (ppx-persistent)  the same behind a fold
+#  igemm_kernel<2, 2, 4, 4, 2, false, 1> with ln_stats    lnfold_geglu 129x64, 154x320   all       ragged M: the 128-row kernel everywhere but `pingpong`
+#  igemm_pp_kernel<false, 1, 4> with ln_stats             lnfold_geglu 154x320           pingpong  forced: N % 256 == 0
+#  igemm_pp_kernel<false, 1, 4> by its grid rule          geglu / lnfold_geglu 2233x512  auto      nk >= 8 (GEGLU_PP_MIN_NK) with N = 8C % 256 == 0 -> C = 512,
+#                                                                                                  16 column tiles; >= 85 % of 256 -> 14 row tiles; ragged last
+#  igemm_pp_kernel<false, 0, 4>         linear 34721x256x640                auto                  N % 256 == 0 and % 320 != 0, nk >= 10, 218 tiles of 160x256 (85 % of a
+#                                                                                                  round), not the persistent kernel's (M % 160 != 0): 217 * 160 + 1 rows
+#  igemm_pp_kernel<true, 0, 4>          temporal_conv 1x128->256, f8, d4341, t5   auto          the same rule on a gathered A operand, where K is shortest: nk = taps cin / 64
+#                                                      >= 10 -> 5 taps x 128 channels (a 3x3 conv needs 9 x 128), 8 x 4341 = 34728 rows = 218 tiles (d4340: 217, the
+#                                                      128-row kernel); cout = 256 < 1024 keeps it off the halo-patch kernel (patch_fits).  The temporal gather is what
+#                                                      is covered; the 3x3 gather of this instantiation would need 186x187 pixels and 2.05e10 multiply-adds
+#  igemm_kernel<2, 2, 4, 4, 2, false, 0>   linear 2689x512x192              all (split-k-3)       the 128-wide tile of the 128-row kernel wins only where the 64-wide one
+#                                                      needs a second round of 512 workgroups (igemm_pick_bn): 22 row tiles x 4 x 3 splits = 264 > 256, M = 21 * 128 + 1
+#  igemm_kernel<2, 2, 4, 4, 2, true, 0>    conv 1x64->512, 52x52            all (split-k-3)       the same for a gathered A operand: 2704 pixels = 22 row tiles
+#  igemm_pp_kernel<true, 0, 5>          conv 1x64->320, 5x7                 all (pingpong)        mode 3 forces it wherever cout % 320 == 0
+#  igemm_patch_kernel<0, 4, 0>          conv 1x64->128, 40x8, force 5       forced                cout % 128 == 0 and % 160 != 0, one 320-pixel tile of whole image rows
+#  igemm_patch_kernel<0, 5, 1>          conv 1x64->160, 10x96, force 5      forced                320 % W != 0: 10 x 32 tiles, W % 32 == 0, H % 10 == 0 -> 10 x 96
+#  igemm_patch_kernel<0, 4, 2>          temporal_conv 1x64->128, f8, d40, force 5   forced        F | 320, D % (320 / F) == 0, cout % 128 == 0: one tile
+#  past the cap (igemm_ppx.hip:162-182: 8 XCD chunks, workgroup j of a chunk takes its tiles j, j + 32, j + 64):
+#  igemm_ppx_kernel<0, 5, 1>            linear 20640x1280x320 bias_residual, residual_in_place   auto, ppx-persistent   129 x 4 = 516 tiles >= 513: four
+#                                                                                                  workgroups run three tiles; nk = 5 is the kernel's minimum
+#  igemm_ppx_kernel<0, 4, 1>            linear 20640x1024x320 bias_residual  auto, ppx-persistent  the same on the 256-wide tile: 516 tiles (not in the issue's list)
+#  igemm_ppx_kernel<0, 5, 0> / <0, 4, 0>   linear 20640x640x320 / 20640x512x320 plain            auto, ppx-persistent   129 x 2 = 258 tiles >= 257
+#  igemm_ppx_kernel<0, 5, 2> / <0, 4, 2>   lnfold 13760x960x320 / 20640x512x320                  auto, ppx-persistent   258 tiles; 86 x 3 for <0, 5, 2>, so that a
+#                                                      workgroup's second tile (its first + 32) lies in another column tile and every aux piece differs between the two
+#  igemm_ppx_kernel<1, 4, 0> / <1, 4, 2>   geglu / lnfold_geglu 5120x320                         auto, ppx-persistent   32 x 10 = 320 tiles of 160x256; the automatic
+#                                                      rule counts 320-wide tiles for GEGLU too (ppx_shape: 32 x 8 = 256 >= 256), so M = 4160 (260 tiles) stays on the 128-row kernel
+#  TOO_LARGE: none
+BIG = ("auto", "ppx-persistent")
+# (M, N, K, option, variants or None = all six)
+REACH_LINEAR = [(20640, 1280, 320, "bias_residual", BIG), (20640, 1280, 320, "residual_in_place", BIG), (20640, 1024, 320, "bias_residual", BIG), (20640, 640, 320, "plain", BIG),
+                (20640, 512, 320, "plain", BIG), (34721, 256, 640, "plain", ("auto",)), (2689, 512, 192, "bias_residual", None)]
+REACH_LNFOLD = [(160, 320, 320, None), (160, 256, 320, None), (320, 320, 320, None), (320, 256, 320, None), (13760, 960, 320, BIG), (20640, 512, 320, BIG)]
+REACH_GEGLU = [(160, 320, None), (2233, 512, ("auto",)), (5120, 320, BIG)]
+REACH_LNFOLD_GEGLU = [(129, 64, None), (154, 320, None), (160, 320, None), (2233, 512, ("auto",)), (5120, 320, BIG)]
+# tiles of the persistent kernel each past-the-cap case must have (name prefix -> (tile width, least tile count))
+PAST_CAP = {"linear[20640x1280x320,bias_residual]": (320, 513), "linear[20640x1280x320,residual_in_place]": (320, 513),
+            "linear[20640x1024x320,bias_residual]": (256, 513),
+            "linear[20640x640x320,plain]": (320, 257), "linear[20640x512x320,plain]": (256, 257), "lnfold[13760x960x320]": (320, 257),
+            "lnfold[20640x512x320]": (256, 257), "geglu[5120x320]": (256, 257), "lnfold_geglu[5120x320]": (256, 257)}
+TCONV_FORCED = [(1, 64, 128, 8, 40)]                      # force 5, taps 3 and 5
+REACH_TCONV = [(1, 128, 256, 8, 4341, 5, ("auto",))]      # (b, cin, cout, frames, d, taps, variants)
+
+# instantiations whose smallest reaching shape is above 2^34 multiply-adds for the float64 reference and its scale: name -> shape and count
+TOO_LARGE = {}
+# registered implicit-GEMM instantiations no route of the planner selects (test_gemm_reach_host.py: each is registered and unreached)
+NOT_PLANNED = {}
+# kernels of the launch-trace fixture that no operator entry point launches: name -> the existing test that exercises it
+WHOLE_FORWARD = "tests/test_gpu_engine.py (whole-output rel-L2 of the engine's blocks and forwards against the fp32 oracle)"
+NO_OPERATOR_ENTRY = {
+    "gn_fold_kernel": WHOLE_FORWARD, "gn_finalize_kernel": WHOLE_FORWARD, "rowstat_finalize_kernel": WHOLE_FORWARD, "ln_fold_kernel": WHOLE_FORWARD,
+    "copy_rows_kernel": WHOLE_FORWARD, "gemv_kernel": WHOLE_FORWARD, "conv_in_kernel": WHOLE_FORWARD, "conv_out4_kernel<5>": WHOLE_FORWARD,
+    "conv_out4_kernel<6>": WHOLE_FORWARD, "xb_gather2_kernel": WHOLE_FORWARD, "xb_gather8_kernel": WHOLE_FORWARD, "rf_gather8_kernel": WHOLE_FORWARD,
+    "rf_gather_f16_f32_kernel": WHOLE_FORWARD, "pack_conv3x3_kernel": "tests/test_gpu_ops_local.py::test_conv3x3 (ops.pack_conv3x3 feeds every conv case)",
+    "pack_conv3x3_parity_kernel": "tests/test_gpu_ops_local.py::test_upsample_conv3x3_parity (ops.pack_conv3x3_parity)",
+    "pack_conv_in_kernel": WHOLE_FORWARD, "pack_geglu_bias_kernel": "tests/test_gpu_ops_local.py::test_geglu (ops.pack_geglu)",
+    "pack_geglu_rows_kernel": "tests/test_gpu_ops_local.py::test_geglu (ops.pack_geglu)", "pack_geglu_vec_kernel": WHOLE_FORWARD,
+    "fill_relpos_bias_kernel": WHOLE_FORWARD, "timestep_sinusoid_kernel": WHOLE_FORWARD, "add_class_emb_silu_kernel": WHOLE_FORWARD,
+    "f16_to_f32_kernel": WHOLE_FORWARD,
+    # producer-side statistics: a run-time branch of the reduce that only the engine's colstat_out selects; its sums are covered by the
+    # engine's verify pass alone
+    "splitk_reduce_cs_kernel": WHOLE_FORWARD + "; its column sums only by the engine's verify pass",
+}
+# the fixture's other names, by the prefix of the kernels the attention, norm, row-resident, temporal and elementwise cases launch
+COVERED_ELSEWHERE = ("attention_dma_kernel<", "attention_kernel<", "attention_wide_kernel", "gn_affine_kernel", "gn_apply_kernel<", "gn_stats_kernel<",
+                     "layernorm_kernel", "geglu_mlp_kernel<", "cross_block_kernel<", "temporal_block_kernel<", "proj_qkv_kernel<",
+                     "temporal_stream_kernel<", "temporal_tile_kernel<")
 
 
 # ------------------------------------------------------------------ 3x3 convolution family
@@ -291,16 +443,28 @@ def conv_case(n, c1, cout, h, w, stride=1, ups=0, pad=None, c2=0, csc=0, extras=
         regions["seams"] = lines_mask(n, ho, wo, cout, ys, xs) | regions["border"]
     name = f"conv[{n}x{c1}+{c2}->{cout},{h}x{w},s{stride},u{ups},pad{pad},sc{csc},ex{int(extras)},f{force},k{splits},par{int(parity)}]"
     setup = (lambda restore: forced(force, splits, restore)) if force is not None else None
-    return Case(name, ins, {"y": ((n * ho * wo, cout), f16)}, run, lambda: {"y": (terms(d, False), terms(d, True))}, c,
+    case = Case(name, ins, {"y": ((n * ho * wo, cout), f16)}, run, lambda: {"y": (terms(d, False), terms(d, True))}, c,
                 lambda: {"y": terms(lambda t: t.float(), False).half()}, oc.loc_image(n, ho, wo, cout), regions=regions, setup=setup)
+    if parity:
+        calls = [call("upsample_conv3x3", NI=n, Hi=h, Wi=w, C=c1, bias=1)]
+    elif pad is not None:
+        calls = [call("conv3x3_down", C=c1, NI=n, Hi=h, Wi=w, Cout=cout, stride=stride, pad_lo=pad[0], bias=1)]
+    else:
+        calls = [call("conv3x3", C1=c1, C2=c2, SC1=csc, SC2=csc, ldb2=cout, rows_per_batch=rpb if "b2" in ins else 0, NI=n, Hi=h, Wi=w,
+                      Cout=cout, stride=stride, ups=ups, bias=1, bias2="b2" in ins, R="r" in ins, x2=bool(c2), sc1=bool(csc), sc2=bool(csc))]
+    return with_calls(case, calls, (force, splits) if force is not None else None)
 
 
 CONV_CASES = [dict(n=1, c1=64, cout=64, h=1, w=1), dict(n=1, c1=64, cout=64, h=3, w=3),
               dict(n=2, c1=64, cout=64, h=5, w=7, stride=2), dict(n=3, c1=64, cout=128, h=4, w=6, ups=1),
               dict(n=2, c1=64, c2=64, cout=64, h=3, w=5, csc=64),
-              dict(n=1, c1=128, cout=128, h=13, w=18, stride=2, pad=(0, 1)), dict(n=1, c1=128, cout=128, h=2, w=2, stride=2, pad=(0, 1))]
+              dict(n=1, c1=128, cout=128, h=13, w=18, stride=2, pad=(0, 1)), dict(n=1, c1=128, cout=128, h=2, w=2, stride=2, pad=(0, 1)),
+              # the gathered ping-pong kernel (`pingpong`) and the 128-wide tile of the 128-row kernel (`split-k-3`): the reach table above
+              dict(n=1, c1=64, cout=320, h=5, w=7), dict(n=1, c1=64, cout=512, h=52, w=52)]
 HALO_CASES = [dict(n=5, c1=64, cout=160, h=8, w=8, extras=True), dict(n=1, c1=64, cout=160, h=40, w=16, extras=True),
-              dict(n=1, c1=128, cout=256, h=20, w=128, extras=True), dict(n=2, c1=64, c2=64, cout=256, h=10, w=96, extras=True, splits=2)]
+              dict(n=1, c1=128, cout=256, h=20, w=128, extras=True), dict(n=2, c1=64, c2=64, cout=256, h=10, w=96, extras=True, splits=2),
+              # the 128-wide tile on whole image rows and the 160-wide one on 10 x 32 tiles (the reach table above)
+              dict(n=1, c1=64, cout=128, h=40, w=8, extras=True), dict(n=1, c1=64, cout=160, h=10, w=96, extras=True)]
 # (2, 320, 10, 16) is the smallest geometry lavie_upsample_conv3x3_supported takes: 160 channels, (1, 320, 10, 16), (2, 320, 5, 16),
 # (2, 320, 10, 8) and (1, 320, 5, 8) are all refused (test_upsample_conv3x3_parity asserts it)
 PARITY_CASES = [(2, 320, 10, 16), (32, 320, 5, 8)]
@@ -308,7 +472,8 @@ PARITY_REFUSED = [(2, 160, 10, 16), (1, 320, 10, 16), (2, 320, 5, 16), (2, 320, 
 
 
 @functools.lru_cache(maxsize=None)
-def temporal_conv_case(b, cin, cout, f, dd, taps):
+def temporal_conv_case(b, cin, cout, f, dd, taps, force=None):
+    """force: the tile mode forced around the launch (5: the halo-patch kernel's temporal mode wherever its geometry holds)"""
     g = gen("tconv", b, cin, cout, f, dd, taps)
     x = rnd(g, b, cin, f, dd)                               # [b, c, f, d]
     wt = rnd(g, cout, cin, taps, 1, 1, s=1 / math.sqrt(taps * cin))
@@ -329,10 +494,14 @@ def temporal_conv_case(b, cin, cout, f, dd, taps):
     first, last = ends.clone(), ends.clone()
     first[:, 0] = True
     last[:, -1] = True
-    return Case(f"temporal_conv[{b}x{cin}->{cout},f{f},d{dd},t{taps}]", ins, {"y": ((b * f * dd, cout), f16)}, run,
+    name = f"temporal_conv[{b}x{cin}->{cout},f{f},d{dd},t{taps}" + ("]" if force is None else f",f{force}]")
+    case = Case(name, ins, {"y": ((b * f * dd, cout), f16)}, run,
                 lambda: {"y": (terms(d, False), terms(d, True))}, oc.gemm_c(taps * cin + 3),
                 lambda: {"y": terms(lambda t: t.float(), False).half()}, oc.loc_image(b * f, dd, 1, cout),
-                regions={"first_frame": first.reshape(-1), "last_frame": last.reshape(-1)})
+                regions={"first_frame": first.reshape(-1), "last_frame": last.reshape(-1)},
+                setup=(lambda restore: forced(force, 0, restore)) if force is not None else None)
+    return with_calls(case, [call("temporal_conv", C=cin, ldb2=cout, rows_per_batch=f * dd, B=b, F=f, D=dd, Cout=cout, taps=taps,
+                                  bias=1, bias2=1, R=1)], (force, 0) if force is not None else None)
 
 
 TCONV_SHAPES = [(1, 64, 64, 1, 7), (1, 64, 64, 2, 7), (3, 128, 64, 2, 7), (2, 64, 128, 8, 80)]
@@ -1177,14 +1346,36 @@ def lora_case(N, K, r, in_place):
                 lambda: {"y": terms(lambda t: t.float(), ident).half()}, oc.loc_rows(K), alias={"y": "w0"} if in_place else None)
 
 
+def restricted(case, variants):
+    case.variants = variants
+    return case
+
+
+def reach_cases():
+    """The cases of the reach tables (REACH_*), each with the variants it runs under"""
+    cs = [restricted(linear_case(M, N, K, o), v) for M, N, K, o, v in REACH_LINEAR]
+    cs += [restricted(lnfold_case(M, N, K), v) for M, N, K, v in REACH_LNFOLD]
+    cs += [restricted(geglu_case(M, c), v) for M, c, v in REACH_GEGLU]
+    cs += [restricted(lnfold_geglu_case(M, c), v) for M, c, v in REACH_LNFOLD_GEGLU]
+    cs += [restricted(temporal_conv_case(*s), v) for *s, v in REACH_TCONV]
+    return cs
+
+
+def gemm_family_cases():
+    """Every case that describes its C-ABI calls: what gemm_reach replays (the halo-patch cases under both of their forced loops)"""
+    cs = [c for c in all_cases() if c.calls]
+    return cs + [conv_case(**k, force=3) for k in HALO_CASES]
+
+
 def all_cases():
     """Every case both test files run (the host file: the model of each against its own bound)."""
     cs = [linear_case(*s, o) for s in LINEAR_SHAPES for o in LINEAR_OPTIONS]
     cs += [geglu_case(129, 64), geglu_case(154, 320), lnfold_case(154, 320, 320), lnfold_case(161, 192, 64)]
+    cs += reach_cases()
     cs += [conv_case(**k) for k in CONV_CASES]
     cs += [conv_case(**k, force=5) for k in HALO_CASES]            # force = 3 has the same model and reference
     cs += [conv_case(n=n, c1=c, cout=c, h=h, w=w, ups=1, parity=True) for n, c, h, w in PARITY_CASES]
-    cs += [temporal_conv_case(*s, t) for s in TCONV_SHAPES for t in (3, 5)]
+    cs += [temporal_conv_case(*s, t) for s in TCONV_SHAPES for t in (3, 5)] + [temporal_conv_case(*s, t, force=5) for s in TCONV_FORCED for t in (3, 5)]
     cs += [edge_in_case(*e, dt, tap) for e in EDGE_IN for dt in (f16, f32t) for tap in (False, True)]
     cs += [edge_out_case(*e, dt) for e in EDGE_OUT for dt in (f16, f32t)]
     cs += [group_norm_case(**k) for k in GN_CASES]
@@ -1201,3 +1392,80 @@ def all_cases():
     cs += [step_case(k, n) for k in STEP_KINDS for n in STEP_LENGTHS]
     cs += [lora_case(*s, ip) for s in LORA_SHAPES for ip in (False, True)]
     return cs
+
+
+# ------------------------------------------------------------------ which kernels the GEMM-family cases reach
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lavie_amd", "csrc")
+
+
+def optrace_line(entry, ints, tile, splits):
+    return " ".join([entry] + [f"{k}={v}" for k, v in ints.items()] + [f"force_tile={tile}", f"force_splits={splits}"])
+
+
+def hostcheck(*args):
+    """Builds the host-only driver (lavie_amd/csrc/hostcheck: every kernel launch is a record of name, grid, block and LDS) and
+    runs one of its modes."""
+    r = subprocess.run(["make", "-C", CSRC, "-j", "8", "build_asan/hostcheck"], capture_output=True, text=True, timeout=900)
+    if r.returncode != 0:
+        raise RuntimeError("building the host-only driver failed:\n" + r.stdout[-3000:] + r.stderr[-3000:])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([os.path.join(CSRC, "build_asan", "hostcheck"), *args], cwd=CSRC, capture_output=True, text=True, env=env, timeout=900)
+    if r.returncode != 0 or " written" not in r.stdout:
+        raise RuntimeError(f"hostcheck {args[0]} failed:\n" + r.stdout[-3000:] + r.stderr[-3000:])
+
+
+def registered_kernels():
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "kernels.txt")
+        hostcheck("kernels", out)
+        with open(out) as f:
+            return set(f.read().splitlines())
+
+
+def launch_name(line):
+    """a launch line of the stub: "<kernel name> gx,gy,gz bx,by,bz lds"; the name itself holds blanks"""
+    return line.rsplit(" ", 3)[0]
+
+
+def launch_grid(line):
+    return tuple(int(v) for v in line.rsplit(" ", 3)[1].split(","))
+
+
+def gemm_runs(cases):
+    """(case, variant name, (tile, splits)) of every replay: a case that forces a mode of its own runs under that alone ("forced"),
+    a case with a variant list under those, every other case under all six VARIANTS."""
+    runs = []
+    for c in cases:
+        if c.force is not None:
+            runs.append((c, "forced", c.force))
+        else:
+            runs += [(c, v, VARIANTS[v]) for v in (c.variants or VARIANTS)]
+    return runs
+
+
+def gemm_reach(cases):
+    """{(case name, variant): launch lines, or None where the library refused a call} through `hostcheck optrace`: the library's own
+    planner on the CPU, given the integers each case's `run` passes."""
+    runs = gemm_runs(cases)
+    lines = [optrace_line(e, ints, *fs) for c, _, fs in runs for e, ints in c.calls]
+    with tempfile.TemporaryDirectory() as tmp:
+        inp, out = os.path.join(tmp, "calls.txt"), os.path.join(tmp, "launches.txt")
+        with open(inp, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        hostcheck("optrace", inp, out)
+        with open(out) as f:
+            got = f.read().splitlines()
+    blocks = []
+    for l in got:
+        if l.startswith("== "):
+            blocks.append((l[3:], []))
+        else:
+            blocks[-1][1].append(l)
+    assert [b[0] for b in blocks] == lines, "optrace output does not follow its input"
+    reach, it = {}, iter(blocks)
+    for c, v, _ in runs:
+        launches = []
+        for _ in c.calls:
+            launches += next(it)[1]
+        reach[(c.name, v)] = None if "!! refused" in launches else launches
+    return reach

@@ -1,0 +1,133 @@
+"""Which implicit-GEMM kernels the per-element operator cases reach (tests/opcases.py), computed by the library's own planner: the
+host-only build (lavie_amd/csrc/hostcheck) replays the C-ABI calls of every GEMM-family case under every variant it runs under and
+records each launch.  Every igemm_* / split-K kernel a forward launches (the names of tests/golden/gemm_plan_trace.txt.gz) must be
+among them; what is not reached is written down by name, with its reason.  CPU only, needs hipcc."""
+import gzip
+import os
+import shutil
+
+import pytest
+
+import opcases as C
+
+pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_plan_trace.txt.gz")
+GEMM = ("igemm_", "splitk_reduce")
+
+
+@pytest.fixture(scope="module")
+def cases():
+    return C.gemm_family_cases()
+
+
+@pytest.fixture(scope="module")
+def reach(cases):
+    return C.gemm_reach(cases)
+
+
+@pytest.fixture(scope="module")
+def fixture_names():
+    with gzip.open(FIXTURE, "rt") as f:
+        return {C.launch_name(l) for l in f.read().splitlines() if not l.startswith(("== ", "workspace ", "!! "))}
+
+
+def names(reach, keep=lambda key: True):
+    return {C.launch_name(l) for key, launches in reach.items() if launches and keep(key) for l in launches}
+
+
+def test_every_gemm_kernel_of_a_forward_is_reached_by_a_case(reach, fixture_names):
+    required = {n for n in fixture_names if n.startswith(GEMM)}
+    assert len(required) >= 20
+    allowed = set(C.TOO_LARGE) | {n for n in C.NO_OPERATOR_ENTRY if n.startswith(GEMM)}
+    missing = required - names(reach) - allowed
+    assert missing == set(), "no per-element case reaches: " + "; ".join(sorted(missing))
+    assert allowed <= required and not (allowed & names(reach)), "an exception that is reached, or that no forward launches, is none"
+
+
+def test_no_replayed_call_is_refused(reach):
+    refused = sorted(key for key, launches in reach.items() if launches is None)
+    assert refused == [], refused                       # (no GEMM-family case is a declared refusal)
+    assert all(launches for launches in reach.values())
+
+
+def test_registered_instantiations_are_reached_or_listed(reach):
+    registered = {n for n in C.registered_kernels() if n.startswith("igemm_")}
+    assert len(registered) >= 26
+    reached = names(reach)
+    listed = set(C.NOT_PLANNED) | set(C.TOO_LARGE)
+    assert registered - reached - listed == set(), sorted(registered - reached - listed)
+    assert listed & reached == set(), "listed as unreached, but reached: %s" % sorted(listed & reached)
+    assert listed <= registered, "listed, but no longer registered: %s" % sorted(listed - registered)
+    assert all(len(reason) > 20 for reason in list(C.NOT_PLANNED.values()) + list(C.TOO_LARGE.values()))
+
+
+def test_fixture_names_are_all_accounted_for(reach, fixture_names):
+    required = {n for n in fixture_names if n.startswith(GEMM)}
+    elsewhere = {n for n in fixture_names if n.startswith(C.COVERED_ELSEWHERE)}
+    assert required | elsewhere | set(C.NO_OPERATOR_ENTRY) == fixture_names, sorted(fixture_names - required - elsewhere - set(C.NO_OPERATOR_ENTRY))
+    assert set(C.NO_OPERATOR_ENTRY) <= fixture_names and not (set(C.NO_OPERATOR_ENTRY) & elsewhere)
+    assert not (set(C.NO_OPERATOR_ENTRY) & names(reach)), "a kernel listed as having no operator entry point was launched by one"
+    for name, test in C.NO_OPERATOR_ENTRY.items():
+        path = test.split("::")[0].split(" ")[0]
+        assert os.path.exists(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), path)), (name, path)
+
+
+# what each table entry of opcases.py claims, from the trace: (case name, variant) -> kernel
+TABLE = [
+    ("lnfold[160x320x320]", "ppx-persistent", "igemm_ppx_kernel<0, 5, 2>"), ("lnfold[320x320x320]", "ppx-persistent", "igemm_ppx_kernel<0, 5, 2>"),
+    ("lnfold[160x256x320]", "ppx-persistent", "igemm_ppx_kernel<0, 4, 2>"), ("lnfold[320x256x320]", "ppx-persistent", "igemm_ppx_kernel<0, 4, 2>"),
+    ("geglu[160x320]", "ppx-persistent", "igemm_ppx_kernel<1, 4, 0>"), ("lnfold_geglu[160x320]", "ppx-persistent", "igemm_ppx_kernel<1, 4, 2>"),
+    ("lnfold_geglu[129x64]", "auto", "igemm_kernel<2, 2, 4, 4, 2, false, 1>"), ("lnfold_geglu[154x320]", "auto", "igemm_kernel<2, 2, 4, 4, 2, false, 1>"),
+    ("lnfold_geglu[154x320]", "pingpong", "igemm_pp_kernel<false, 1, 4>"), ("geglu[2233x512]", "auto", "igemm_pp_kernel<false, 1, 4>"),
+    ("lnfold_geglu[2233x512]", "auto", "igemm_pp_kernel<false, 1, 4>"), ("linear[34721x256x640,plain]", "auto", "igemm_pp_kernel<false, 0, 4>"),
+    ("linear[2689x512x192,bias_residual]", "split-k-3", "igemm_kernel<2, 2, 4, 4, 2, false, 0>"),
+    ("linear[2689x512x192,bias_residual]", "split-k-3", "splitk_reduce_kernel"),
+    ("temporal_conv[1x128->256,f8,d4341,t5]", "auto", "igemm_pp_kernel<true, 0, 4>"),
+]
+CONV_TABLE = [
+    (dict(n=1, c1=64, cout=512, h=52, w=52), "split-k-3", "igemm_kernel<2, 2, 4, 4, 2, true, 0>"),
+    (dict(n=1, c1=64, cout=320, h=5, w=7), "pingpong", "igemm_pp_kernel<true, 0, 5>"),
+    (dict(n=1, c1=64, cout=128, h=40, w=8, extras=True, force=5), "forced", "igemm_patch_kernel<0, 4, 0>"),
+    (dict(n=1, c1=64, cout=160, h=10, w=96, extras=True, force=5), "forced", "igemm_patch_kernel<0, 5, 1>"),
+    (dict(n=1, c1=128, cout=256, h=20, w=128, extras=True, force=5), "forced", "igemm_patch_kernel<0, 4, 1>"),
+]
+
+
+def test_reach_table_entries(reach):
+    for case, variant, kernel in TABLE:
+        assert kernel in {C.launch_name(l) for l in reach[(case, variant)]}, (case, variant, reach[(case, variant)])
+    for kw, variant, kernel in CONV_TABLE:
+        name = C.conv_case(**kw).name
+        assert kernel in {C.launch_name(l) for l in reach[(name, variant)]}, (name, variant, reach[(name, variant)])
+    for taps in (3, 5):
+        name = C.temporal_conv_case(*C.TCONV_FORCED[0], taps, force=5).name
+        assert [C.launch_name(l) for l in reach[(name, "forced")]] == ["igemm_patch_kernel<0, 4, 2>"]
+    for n, c, h, w in C.PARITY_CASES:
+        name = C.conv_case(n=n, c1=c, cout=c, h=h, w=w, ups=1, parity=True).name
+        assert all(C.launch_name(reach[(name, v)][0]) == "igemm_patch_kernel<0, 5, 3>" for v in C.VARIANTS)
+
+
+def test_removing_a_new_case_is_noticed(cases):
+    """the reach of the suite without the grid-rule linear case, and without the forced temporal convs, misses exactly their kernels"""
+    for drop, kernel in (("linear[34721x256x640,plain]", "igemm_pp_kernel<false, 0, 4>"), ("temporal_conv[1x64->128,f8,d40", "igemm_patch_kernel<0, 4, 2>")):
+        rest = [c for c in cases if not c.name.startswith(drop)]
+        assert len(rest) < len(cases)
+        assert kernel not in names(C.gemm_reach(rest)), (drop, kernel)
+
+
+def test_persistent_kernel_runs_past_its_workgroup_cap(reach, cases):
+    """Each past-the-cap case launches igemm_ppx_kernel with the full grid of 256 workgroups under `auto` and `ppx-persistent`, and
+    its shape has the tile count its table entry states: >= 257 for a second tile in some workgroup, >= 513 for a workgroup with a
+    first, a steady-state and a last tile."""
+    by_name = {c.name: c for c in cases}
+    assert set(C.PAST_CAP) <= set(by_name)
+    for name, (bn, least) in C.PAST_CAP.items():
+        ints = by_name[name].calls[0][1]
+        tiles = (ints["M"] // 160) * (ints["N"] // bn)
+        assert ints["M"] % 160 == 0 and ints["N"] % bn == 0 and tiles >= least, (name, tiles)
+        assert by_name[name].variants == C.BIG
+        for v in C.BIG:
+            (launch,) = reach[(name, v)]
+            assert C.launch_name(launch).startswith("igemm_ppx_kernel<") and C.launch_grid(launch) == (256, 1, 1), (name, v, launch)
+    modes = {C.launch_name(reach[(name, "auto")][0]) for name in C.PAST_CAP}
+    assert modes == {f"igemm_ppx_kernel<{e}>" for e in ("0, 5, 0", "0, 5, 1", "0, 5, 2", "0, 4, 0", "0, 4, 1", "0, 4, 2", "1, 4, 0", "1, 4, 2")}, sorted(modes)

@@ -10,8 +10,7 @@ import opcheck as oc
 
 pytestmark = pytest.mark.gpu
 
-VARIANTS = {"auto": (0, 0), "row128-tiles": (1, 0), "split-k-3": (0, 3), "pingpong": (3, 0), "pingpong-split-k-2": (3, 2),
-            "ppx-persistent": (7, 0)}
+VARIANTS = C.VARIANTS
 _forced = [0, 0]          # what the fixture set: a case that forces a kernel of its own restores this afterwards
 
 
@@ -57,6 +56,27 @@ def test_geglu(ops, M, C_):
 @pytest.mark.parametrize("M,N,K", [(154, 320, 320), (161, 192, 64)])
 def test_linear_lnfold(ops, M, N, K):
     check(ops, C.lnfold_case(M, N, K))
+
+
+def reach_runs():
+    """(case, variant) of the reach tables of opcases.py: a small case under all six variants, a large one under those whose launch
+    trace names its target kernel (tests/test_gemm_reach_host.py asserts the traces)"""
+    return [pytest.param(c, v, id=f"{c.name}-{v}") for c in C.reach_cases() for v in (c.variants or C.VARIANTS)]
+
+
+@pytest.mark.parametrize("case,variant", reach_runs())
+def test_gemm_reach_case(case, variant):
+    """sets its own variant (and puts back what the `ops` fixture of the surrounding tests had set)"""
+    assert torch.cuda.is_available(), "gpu tests need a HIP device"
+    from lavie_amd import ops as o
+    with C.forced(*C.VARIANTS[variant], tuple(_forced)):
+        oc.check_case(o, case, forced=C.VARIANTS[variant], sync=torch.cuda.synchronize)
+
+
+@pytest.mark.parametrize("taps", [3, 5])
+@pytest.mark.parametrize("b,cin,cout,f,d", C.TCONV_FORCED)
+def test_temporal_conv_halo_patch(ops, b, cin, cout, f, d, taps):
+    check(ops, C.temporal_conv_case(b, cin, cout, f, d, taps, force=5))
 
 
 @pytest.mark.parametrize("kw", C.CONV_CASES, ids=lambda k: "-".join(f"{a}{b}" for a, b in k.items()))

@@ -2,6 +2,9 @@
 at the points counted in the kernel's source — meets the bound of its own case with zero offenders; injected defects are caught
 and located where the whole-tensor rel-L2 criterion of the older operator tests passes them; the guard-band and poison logic
 works on CPU tensors."""
+import os
+import re
+
 import pytest
 import torch
 
@@ -16,6 +19,69 @@ CASES = C.all_cases()
 def test_fp32_model_meets_its_bound(case):
     """If this fails the rounding-point count n (or K_terms) of the case is wrong: fix the count, not the bound."""
     case.check(case.model(), label="model ")
+
+
+# ------------------------------------------------------------------ the call descriptions of the GEMM-family cases
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "lavie_hip.h")
+REPLAYED = ("linear", "linear_lnfold", "linear_lnfold_geglu", "conv3x3", "conv3x3_down", "upsample_conv3x3", "temporal_conv")   # driver.cpp run_optrace
+OPTIONAL = ("bias", "bias2", "R", "x2", "sc1", "sc2")
+
+
+def abi_parameters(entry):
+    """[(name, is_int)] of lavie_<entry>_f16 as include/lavie_hip.h declares it"""
+    with open(HEADER) as f:
+        m = re.search(r"\bint lavie_%s_f16\(([^)]*)\)" % entry, f.read())
+    return [(p.split()[-1].lstrip("*"), p.split()[0] == "int") for p in m.group(1).replace("\n", " ").split(",")]
+
+
+class RecordingLib:
+    """stands in for the loaded library: every entry point records its arguments and succeeds"""
+
+    def __init__(self):
+        self.recorded = []
+
+    def __getattr__(self, name):
+        return lambda *args: self.recorded.append((name, args)) or 0
+
+
+GEMM_CASES = C.gemm_family_cases()
+
+
+@pytest.mark.parametrize("case", GEMM_CASES, ids=[c.name for c in GEMM_CASES])
+def test_call_description_is_what_run_passes(case, monkeypatch):
+    """`case.calls` — what tests/test_gemm_reach_host.py replays on the host-only build — against what `case.run` really hands to
+    the C ABI through lavie_amd/ops.py: the case runs on its CPU tensors with a recording library behind the wrappers (their
+    device checks off, everything that derives an integer left as it is), and every integer and every optional operand of each
+    replayed entry point must be the one the description names, in order."""
+    from lavie_amd import _lib, ops
+    lib = RecordingLib()
+    monkeypatch.setattr(_lib, "load", lambda: lib)
+    monkeypatch.setattr(_lib, "check", lambda rc, *a: None)
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    monkeypatch.setattr(ops, "_chk16", lambda *ts: None)
+    monkeypatch.setattr(ops, "_chk32", lambda *ts: None)
+    monkeypatch.setattr(ops, "_zero_pages", {})
+
+    def out_as_given(out, shape, dtype, device, what):
+        assert out is not None and tuple(out.shape) == tuple(shape) and out.dtype == dtype, what
+        return out
+    monkeypatch.setattr(ops, "_out", out_as_given)
+    case.run(ops, case.inputs, {k: torch.empty(shape, dtype=dt) for k, (shape, dt) in case.outputs.items()})
+    passed = []
+    for name, args in lib.recorded:
+        entry = name[len("lavie_"):-len("_f16")]
+        if entry not in REPLAYED:
+            continue                                   # the pack steps: no launch of the GEMM family
+        params = abi_parameters(entry)
+        assert len(params) == len(args), (name, len(params), len(args))
+        ints = {p: int(a) for (p, is_int), a in zip(params, args) if is_int}
+        ints.update({p: int(a is not None) for (p, _), a in zip(params, args) if p in OPTIONAL})
+        passed.append((entry, ints))
+    assert len(passed) == len(case.calls) >= 1, (passed, case.calls)
+    for (entry, ints), (want_entry, want) in zip(passed, case.calls):
+        assert entry == want_entry
+        assert set(want) <= set(ints), sorted(set(want) - set(ints))
+        assert ints == {**{p: 0 for p in ints if p in OPTIONAL}, **want}, (entry, ints, want)
 
 
 # ------------------------------------------------------------------ injected defects
@@ -173,6 +239,86 @@ def test_attention_far_below_rows_never_rescaled(far_below, n_rows):
     bad_tokens = (~((bad.double() - case.ref["y"][0]).abs() <= oc.U16 * case.ref["y"][0].abs() + case.c * case.ref["y"][1])).any(1).nonzero().flatten().tolist()
     assert bad_tokens == rows, bad_tokens                       # the hard rows and nothing else
     assert rel_l2(bad, case.ref["y"][0]) > 100 * TOL_OP
+
+
+# ------------------------------------------------------------------ the persistent kernel past its first tile
+def ppx_tile_lists(tiles, nwg=256):
+    """The tile ids each workgroup of the persistent GEMM walks, in order: a mirror of igemm_ppx.hip:162-182 (and its header,
+    :32-34) for tiles > nwg.  Tile id = m_tile * n_tiles + n_tile; the ids are cut into 8 contiguous chunks, one per XCD label
+    (blockIdx % 8), and workgroup j = blockIdx / 8 of a chunk takes its tiles j, j + nwg / 8, j + 2 nwg / 8, ..."""
+    assert tiles > nwg and nwg % 8 == 0
+    per, qq, r = nwg // 8, tiles // 8, tiles % 8
+    lists = []
+    for b in range(nwg):
+        xcd, j = b % 8, b // 8
+        start = xcd * (qq + 1) if xcd < r else r * (qq + 1) + (xcd - r) * qq
+        size = qq + (1 if xcd < r else 0)
+        lists.append([start + k for k in range(j, size, per)])
+    assert sorted(t for l in lists for t in l) == list(range(tiles))
+    return lists
+
+
+def offending_tiles(case, got, bn):
+    ref, scale = case.ref["y"]
+    bad = ~((got.double() - ref).abs() <= oc.U16 * ref.abs() + case.c * scale)
+    n_tiles = ref.shape[1] // bn
+    per_tile = bad.reshape(ref.shape[0] // 160, 160, n_tiles, bn).permute(0, 2, 1, 3).reshape(-1, 160 * bn)
+    return {int(t): int(c) for t, c in enumerate(per_tile.sum(1)) if c}
+
+
+def test_ppx_second_tile_with_the_other_aux_parity():
+    """Every workgroup's second tile finished with the bias / ln_s / (mean, rstd) rows of the other aux buffer, which still holds
+    its first tile's: the check fails at those tiles and nowhere else.  lnfold 13760x960x320: 86 x 3 = 258 tiles, so the first
+    workgroup of XCD 0 and of XCD 1 run two tiles each (33 tiles in their chunks) and every other workgroup one.  With three
+    column tiles the second tile (id + 32) is in another row tile and another column tile than the first, so all three pieces
+    of the defect — bias, ln_s and the (mean, rstd) rows — are wrong values, each of which alone must be caught."""
+    case = C.lnfold_case(13760, 960, 320)
+    i, bn, n_tiles = case.inputs, 320, 3
+    lists = ppx_tile_lists(258)
+    second = {l[1]: l[0] for l in lists if len(l) > 1}
+    assert second == {32: 0, 65: 33}
+    assert all(t // n_tiles != p // n_tiles and t % n_tiles != p % n_tiles for t, p in second.items())
+    y = case.model()["y"]
+    for stale in (("bias", "s", "stats"), ("bias",), ("s",), ("stats",)):
+        bad = y.clone()
+        for t, prev in second.items():
+            (m0, n0), (pm0, pn0) = ((x // n_tiles * 160, x % n_tiles * bn) for x in (t, prev))
+            acc = i["a"][m0:m0 + 160].float() @ i["wf"][n0:n0 + bn].float().t()
+            st = i["stats"][pm0:pm0 + 160] if "stats" in stale else i["stats"][m0:m0 + 160]
+            s = i["s"][pn0:pn0 + bn] if "s" in stale else i["s"][n0:n0 + bn]
+            bias = i["bias"][pn0:pn0 + bn] if "bias" in stale else i["bias"][n0:n0 + bn]
+            bad[m0:m0 + 160, n0:n0 + bn] = (st[:, 1:] * (acc - st[:, :1] * s) + bias).half()
+        with pytest.raises(AssertionError):
+            case.check({"y": bad})
+        off = offending_tiles(case, bad, bn)
+        assert set(off) == set(second), (stale, off)
+        assert len(stale) < 3 or all(c > 0.9 * 160 * bn for c in off.values()), off
+
+
+def test_ppx_steady_state_tile_with_the_previous_tiles_residual():
+    """The residual rows of a steady-state tile (neither the first nor the last of its workgroup) are those prefetched for the
+    workgroup's previous tile.  linear 20640x1280x320: 516 tiles, the first workgroup of XCDs 0 - 3 runs three.  Caught at exactly
+    those tiles.  The whole-tensor criterion does NOT pass this defect, not even on one tile: a tile of N(0, 1) residual rows
+    exchanged for another is an error of norm sqrt(2 * 160 * 320) = 320 beside an output of norm sqrt(3 * 20640 * 1280) = 8.9e3:
+    rel_l2 = 3.6e-2 measured on one tile, against TOL_OP = 2e-3 — asserted as what it is."""
+    case = C.linear_case(20640, 1280, 320, "bias_residual")
+    i, bn, n_tiles = case.inputs, 320, 4
+    lists = ppx_tile_lists(516)
+    steady = {l[k]: l[k - 1] for l in lists for k in range(1, len(l) - 1)}
+    assert steady == {32: 0, 97: 65, 162: 130, 227: 195}
+    y = case.model()["y"]
+    ref = case.ref["y"][0]
+    for n_defects in (4, 1):
+        bad = y.clone()
+        for t, prev in list(steady.items())[:n_defects]:
+            (m0, n0), (pm0, pn0) = ((x // n_tiles * 160, x % n_tiles * bn) for x in (t, prev))
+            acc = i["a"][m0:m0 + 160].float() @ i["w"][n0:n0 + bn].float().t() + i["bias"][n0:n0 + bn]
+            bad[m0:m0 + 160, n0:n0 + bn] = (acc + i["r"][pm0:pm0 + 160, pn0:pn0 + bn].float()).half()
+        with pytest.raises(AssertionError):
+            case.check({"y": bad})
+        off = offending_tiles(case, bad, bn)
+        assert set(off) == set(list(steady)[:n_defects]) and all(c > 0.9 * 160 * bn for c in off.values()), off
+    assert 3e-2 < rel_l2(bad, ref) < 4e-2 and rel_l2(bad, ref) > 10 * TOL_OP
 
 
 # ------------------------------------------------------------------ bands and poison, on CPU tensors
