@@ -116,6 +116,46 @@ int lavie_linear_lnfold_geglu_f16(const void* A, const void* Wf, const float* bi
 /* GEGLU projection [2*inner, K] (+ bias) -> 16-row value/gate interleave expected by lavie_linear_f16(geglu=1). */
 int lavie_pack_geglu_f16(const void* w, const void* bias_f16, void* w_out, float* bias_out, int N, int K, void* stream);
 
+/* The forward's end and glue kernels, one entry point per kernel (additive in ABI 8): what the engine launches around the
+ * contraction core, callable on the caller's own operands.  Every one is deterministic; an argument outside the stated range is
+ * refused and nothing is launched.
+ *   lavie_timestep_sinusoid_f32 : Timesteps(dim, flip_sin_to_cos=True, freq_shift=0) (unet.py:153,428): t fp32 [B] -> out fp32
+ *       [B, dim] = [cos(t w_k) | sin(t w_k)], w_k = 10000^(-k / (dim/2)); dim even.
+ *   lavie_gemv_f16 : out[b, n] = act_out(sum_k act_in(in[b, k]) W[n, k] + bias[n]), in fp32 [B, K], W fp16 [N, K], bias fp32 [N] or
+ *       NULL, out fp32 [B, N]; act 0 = none, 1 = SiLU.  TimestepEmbedding and the stacked time_emb_proj (unet.py:434,
+ *       resnet.py:186).  1 <= B <= 8, K %% 8 == 0, B * K * 4 <= 65536.  A batch entry's result does not depend on its index.
+ *   lavie_pack_conv_in_f16 : w [Cout, Cin, 3, 3] -> out[(k / 2) * Cout * 2 + co * 2 + k %% 2], k = (ky*3+kx) * Cin + ci.
+ *   lavie_conv_in_f16 : x [B, Cin, F, H, W] (NCFHW) -> y [(B F) H W, Cout] channels-last rows, 3x3 pad 1 (unet.py:150,454); bias
+ *       fp32 [Cout]; Cout %% 8 == 0, Cin even, 9 * Cin * Cout * 2 <= 65536.
+ *   lavie_pack_conv_out_f16 : w [Cout, Cin, 3, 3] -> out[co, (ky*3+kx) * Cin + ci].
+ *   lavie_conv_out_f16 : x [(B F) H W, Cin] rows -> y [B, Cout, F, H, W] (NCFHW), 3x3 pad 1 (unet.py:290,506); bias fp32 [Cout];
+ *       Cout <= 8, Cin %% 8 == 0, 9 * Cin * Cout * 2 <= 65536.
+ *   lavie_add_class_emb_silu_f32 : emb[b, :] = silu(emb[b, :] + table[label_b, :]) in place (vsr/models/unet.py:494-505); emb fp32
+ *       [B, N], table fp16 [num_classes, N], labels on the host; 1 <= B <= 8, 0 <= label < num_classes.
+ *   lavie_fill_relpos_bias_f32 : out[h, i, j] = emb[buckets[i, j], h] (attention.py:669-707); emb fp16 [num_buckets, heads],
+ *       buckets int32 [F, F] on the device with every entry in [0, num_buckets) (lavie_relpos_buckets), out fp32 [heads, F, F].
+ *   lavie_ln_fold_f16 : the LayerNorm fold lavie_linear_lnfold_f16 consumes: Wout[n, k] = fp16(W[n, k] gamma[k]), s_out[n] = sum_k
+ *       Wout[n, k], b_out[n] = sum_k beta[k] W[n, k] (+ bias_f16[n]); W / Wout fp16 [N, K], s_out / b_out fp32 [N].
+ *   lavie_pack_geglu_vec_f32 : out[n] = in[row(n)], lavie_pack_geglu_f16's row permutation on an fp32 vector; N %% 32 == 0.
+ *   lavie_copy_rows_f16 : dst[r, col0 + c] = src[r, c] for r < rows, c < cols; ld_src >= cols, ld_dst >= col0 + cols.
+ *   lavie_f16_to_f32 : dst[i] = float(a[i]) (+ float(b[i]) when b is not NULL), i < n. */
+int lavie_timestep_sinusoid_f32(const float* t, float* out, int B, int dim, void* stream);
+int lavie_gemv_f16(const float* in, const void* W, const float* bias, float* out, int B, int N, int K, int act_in, int act_out,
+                   void* stream);
+int lavie_pack_conv_in_f16(const void* w, void* out, int Cout, int Cin, void* stream);
+int lavie_conv_in_f16(const void* x_ncfhw, const void* wp, const float* bias, void* y, int B, int Cin, int F, int H, int W, int Cout,
+                      void* stream);
+int lavie_pack_conv_out_f16(const void* w, void* out, int Cout, int Cin, void* stream);
+int lavie_conv_out_f16(const void* x, const void* wp, const float* bias, void* y_ncfhw, int B, int Cin, int F, int H, int W, int Cout,
+                       void* stream);
+int lavie_add_class_emb_silu_f32(float* emb_inout, const void* table, const int* labels_host, int B, int N, int num_classes, void* stream);
+int lavie_fill_relpos_bias_f32(const void* emb, const int* buckets_dev, float* out, int heads, int F, int num_buckets, void* stream);
+int lavie_ln_fold_f16(const void* W, const float* gamma, const float* beta, const void* bias_f16, void* Wout, float* s_out, float* b_out, int N,
+                      int K, void* stream);
+int lavie_pack_geglu_vec_f32(const float* in, float* out, int N, void* stream);
+int lavie_copy_rows_f16(const void* src, int ld_src, void* dst, int ld_dst, int rows, int cols, int col0, void* stream);
+int lavie_f16_to_f32(const void* a, const void* b, float* dst, long long n, void* stream);
+
 /* Low-rank adapter merge (LoRA on the attention projections; the fork's fine-tuning wraps to_q / to_k / to_v / to_out.0 with a
  * peft LoraConfig, base/pipelines/fine_tuning.py:296-307): out[n, k] = fp16_rne(float(W0[n, k]) + scale * sum_{j < r} B[n, j] A[j, k]).
  * W0 / out fp16 [N, K]; A fp32 [r, K] (lora_A / lora_down); B fp32 [N, r] (lora_B / lora_up).  fp32 accumulation with fmaf in

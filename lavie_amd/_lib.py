@@ -57,6 +57,18 @@ SIGNATURES = {
                                          c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "lavie_pack_temporal_conv_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "lavie_pack_geglu_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_float_p, c_int, c_int, c_void_p]),
+    "lavie_timestep_sinusoid_f32": (c_int, [c_float_p, c_float_p, c_int, c_int, c_void_p]),
+    "lavie_gemv_f16": (c_int, [c_float_p, c_void_p, c_float_p, c_float_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "lavie_pack_conv_in_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "lavie_conv_in_f16": (c_int, [c_void_p, c_void_p, c_float_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "lavie_pack_conv_out_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "lavie_conv_out_f16": (c_int, [c_void_p, c_void_p, c_float_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "lavie_add_class_emb_silu_f32": (c_int, [c_float_p, c_void_p, C.POINTER(c_int), c_int, c_int, c_int, c_void_p]),
+    "lavie_fill_relpos_bias_f32": (c_int, [c_void_p, c_void_p, c_float_p, c_int, c_int, c_int, c_void_p]),
+    "lavie_ln_fold_f16": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_void_p, c_float_p, c_float_p, c_int, c_int, c_void_p]),
+    "lavie_pack_geglu_vec_f32": (c_int, [c_float_p, c_float_p, c_int, c_void_p]),
+    "lavie_copy_rows_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "lavie_f16_to_f32": (c_int, [c_void_p, c_void_p, c_float_p, c_ll, c_void_p]),
     "lavie_lora_merge_f16": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "lavie_lora_merge_multi_f16": (c_int, [c_void_p, C.POINTER(LoraTermC), c_int, c_void_p, c_int, c_int, c_void_p]),
     "lavie_geglu_mlp_image_bytes": (c_ll, [c_int]),

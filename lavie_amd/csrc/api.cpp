@@ -345,6 +345,83 @@ int lavie_relpos_buckets(int F, int num_buckets, int max_distance, int* out_host
     return 0;
 }
 
+// ---- the forward's end and glue kernels at operator level: thin wrappers over the launchers of ops.h, so that each kernel can be
+// run on its own operands (tests/opcases.py).  What the engine guarantees by construction is checked here; the launchers' own
+// refusals pass through.
+int lavie_timestep_sinusoid_f32(const float* t, float* out, int B, int dim, void* stream) {
+    LAVIE_CHECK(t && out, "timestep_sinusoid: null tensor");
+    LAVIE_CHECK(B >= 1 && dim >= 2 && dim % 2 == 0 && (long long)B * dim < (1ll << 31), "timestep_sinusoid: B=%d dim=%d (dim even, >= 2)", B, dim);
+    return launch_timestep_sinusoid(t, out, B, dim, S(stream));
+}
+int lavie_gemv_f16(const float* in, const void* W, const float* bias, float* out, int B, int N, int K, int act_in, int act_out,
+                   void* stream) {
+    LAVIE_CHECK(in && W && out, "gemv: null tensor");
+    LAVIE_CHECK(N >= 1 && K >= 1, "gemv: N=%d K=%d", N, K);
+    LAVIE_CHECK((act_in == 0 || act_in == 1) && (act_out == 0 || act_out == 1), "gemv: act_in=%d act_out=%d (0 or 1)", act_in, act_out);
+    return launch_gemv(in, H(W), bias, out, B, N, K, act_in, act_out, S(stream));
+}
+int lavie_pack_conv_in_f16(const void* w, void* out, int Cout, int Cin, void* stream) {
+    LAVIE_CHECK(w && out, "pack_conv_in: null tensor");
+    LAVIE_CHECK(Cout >= 8 && Cout % 8 == 0 && Cin >= 2 && Cin % 2 == 0 && (long long)Cout * Cin * 9 < (1ll << 31),
+                "pack_conv_in: Cout must be a multiple of 8 and Cin even (Cout=%d Cin=%d)", Cout, Cin);
+    return launch_pack_conv_in(H(w), H(out), Cout, Cin, S(stream));
+}
+int lavie_conv_in_f16(const void* x_ncfhw, const void* wp, const float* bias, void* y, int B, int Cin, int F, int H_, int W_, int Cout,
+                      void* stream) {
+    LAVIE_CHECK(x_ncfhw && wp && bias && y, "conv_in: null tensor");
+    LAVIE_CHECK(B >= 1 && F >= 1 && H_ >= 1 && W_ >= 1 && Cin >= 1 && Cout >= 1, "conv_in: bad shape B=%d Cin=%d F=%d %dx%d Cout=%d", B, Cin, F, H_,
+                W_, Cout);
+    return launch_conv_in(H(x_ncfhw), H(wp), bias, H(y), B, Cin, F, H_, W_, Cout, S(stream));
+}
+int lavie_pack_conv_out_f16(const void* w, void* out, int Cout, int Cin, void* stream) {
+    LAVIE_CHECK(w && out, "pack_conv_out: null tensor");
+    LAVIE_CHECK(Cout >= 1 && Cin >= 1 && (long long)Cout * Cin * 9 < (1ll << 31), "pack_conv_out: Cout=%d Cin=%d", Cout, Cin);
+    return launch_pack_conv3x3(H(w), H(out), Cout, Cin, 9 * Cin, 0, false, S(stream));
+}
+int lavie_conv_out_f16(const void* x, const void* wp, const float* bias, void* y_ncfhw, int B, int Cin, int F, int H_, int W_, int Cout,
+                       void* stream) {
+    LAVIE_CHECK(x && wp && bias && y_ncfhw, "conv_out: null tensor");
+    LAVIE_CHECK(B >= 1 && F >= 1 && H_ >= 1 && W_ >= 1 && Cin >= 1 && Cout >= 1, "conv_out: bad shape B=%d Cin=%d F=%d %dx%d Cout=%d", B, Cin, F, H_,
+                W_, Cout);
+    return launch_conv_out(H(x), H(wp), bias, H(y_ncfhw), B, Cin, F, H_, W_, Cout, S(stream));
+}
+int lavie_add_class_emb_silu_f32(float* emb_inout, const void* table, const int* labels_host, int B, int N, int num_classes, void* stream) {
+    LAVIE_CHECK(emb_inout && table && labels_host, "add_class_emb_silu: null argument");
+    LAVIE_CHECK(B >= 1 && B <= 8 && N >= 1 && num_classes >= 1, "add_class_emb_silu: B=%d (1..8) N=%d num_classes=%d", B, N, num_classes);
+    for (int b = 0; b < B; ++b)      // the launcher takes the labels as they come (the engine checks them, engine.cpp forward)
+        LAVIE_CHECK(labels_host[b] >= 0 && labels_host[b] < num_classes, "add_class_emb_silu: class label %d out of range (0..%d)", labels_host[b],
+                    num_classes - 1);
+    return launch_add_class_emb_silu(emb_inout, H(table), labels_host, B, N, S(stream));
+}
+int lavie_fill_relpos_bias_f32(const void* emb, const int* buckets_dev, float* out, int heads, int F, int num_buckets, void* stream) {
+    LAVIE_CHECK(emb && buckets_dev && out, "fill_relpos_bias: null tensor");
+    LAVIE_CHECK(heads >= 1 && F >= 1 && num_buckets >= 1 && (long long)heads * F * F < (1ll << 31), "fill_relpos_bias: heads=%d F=%d num_buckets=%d",
+                heads, F, num_buckets);
+    return launch_fill_relpos_bias(H(emb), buckets_dev, out, heads, F, S(stream));
+}
+int lavie_ln_fold_f16(const void* W, const float* gamma, const float* beta, const void* bias_f16, void* Wout, float* s_out, float* b_out, int N,
+                      int K, void* stream) {
+    LAVIE_CHECK(W && gamma && beta && Wout && s_out && b_out, "ln_fold: null tensor");
+    LAVIE_CHECK(N >= 1 && K >= 1, "ln_fold: N=%d K=%d", N, K);
+    return launch_ln_fold(H(W), gamma, beta, H(bias_f16), H(Wout), s_out, b_out, N, K, S(stream));
+}
+int lavie_pack_geglu_vec_f32(const float* in, float* out, int N, void* stream) {
+    LAVIE_CHECK(in && out, "pack_geglu_vec: null tensor");
+    LAVIE_CHECK(N >= 32 && N % 32 == 0, "pack_geglu_vec: N=%d must be a multiple of 32", N);      // (the launcher does not check the vector form)
+    return launch_pack_geglu_vec(in, out, N, S(stream));
+}
+int lavie_copy_rows_f16(const void* src, int ld_src, void* dst, int ld_dst, int rows, int cols, int col0, void* stream) {
+    LAVIE_CHECK(src && dst, "copy_rows: null tensor");
+    LAVIE_CHECK(rows >= 1 && cols >= 1 && col0 >= 0, "copy_rows: rows=%d cols=%d col0=%d", rows, cols, col0);
+    LAVIE_CHECK(ld_src >= cols && (long long)ld_dst >= (long long)col0 + cols, "copy_rows: ld_src=%d < cols=%d or ld_dst=%d < col0 + cols=%d", ld_src, cols,
+                ld_dst, col0 + cols);
+    return launch_copy_rows(H(src), ld_src, H(dst), ld_dst, rows, cols, col0, S(stream));
+}
+int lavie_f16_to_f32(const void* a, const void* b, float* dst, long long n, void* stream) {
+    LAVIE_CHECK(a && dst && n >= 1, "f16_to_f32: bad arguments");
+    return b ? launch_add_f16_to_f32(H(a), H(b), dst, n, S(stream)) : launch_f16_to_f32(H(a), dst, n, S(stream));
+}
+
 int lavie_cfg_ddpm_step(const void* eps2, float* x, const float* noise, void* model_in2, long long n, float guidance,
                         float k_x, float k_eps, float c_x0, float c_xt, float sigma, void* stream) {
     LAVIE_CHECK(eps2 && x && model_in2 && n > 0, "cfg_ddpm_step: bad arguments");

@@ -686,7 +686,11 @@ __global__ __launch_bounds__(256) void ln_fold_kernel(const half_t* __restrict__
     float s = 0.f, b = 0.f;
     for (int k = lane; k < K; k += 64) {
         const float w = (float)W[(size_t)n * K + k];
-        const half_t wf = (half_t)(w * gamma[k]);
+        // fp16(fp32(w gamma)), what torch's (W.float() * gamma).half() gives: left alone the compiler folds the pair into one
+        // v_fma_mixlo_f16, which rounds the exact product once and differs in the last fp16 bit on rare elements (scaled_f16 above)
+        float wg = w * gamma[k];
+        asm("" : "+v"(wg));
+        const half_t wf = (half_t)wg;
         Wout[(size_t)n * K + k] = wf;
         s += (float)wf;
         b += beta[k] * w;

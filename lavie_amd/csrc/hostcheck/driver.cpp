@@ -384,7 +384,8 @@ static void run_traces(const char* path) {
 
 // ---- operator launch trace: IN holds one operator call per line, "<entry> key=int ..." — the entry point without lavie_ / _f16,
 // its integer arguments under the names of include/lavie_hip.h, 0 / 1 for each optional operand (bias, bias2, R, x2, sc1, sc2) and
-// force_tile / force_splits (default 0).  Tensors are never read.  OUT: "== <line>", then the stub's launch lines of that call, or
+// force_tile / force_splits (default 0); the end and glue kernels' entries (timestep_sinusoid ... f16_to_f32) and the pack / bind steps
+// of the row-resident blocks (pack_geglu_mlp, bind_cross_block[_long]: pack + bind) likewise.  Tensors are never read.  OUT: "== <line>", then the stub's launch lines of that call, or
 // "!! refused" where the library returns an error (its message goes to stderr).  A line the driver cannot parse ends the run.
 static int run_optrace(const char* in_path, const char* out_path) {
     FILE* in = fopen(in_path, "r");
@@ -455,6 +456,60 @@ static int run_optrace(const char* in_path, const char* out_path) {
             } else if (entry == "temporal_conv") {
                 const int C = I("C"), ldb2 = I("ldb2"), rpb = I("rows_per_batch"), B = I("B"), Fr = I("F"), D = I("D"), Cout = I("Cout"), taps = I("taps");
                 if (!missing) rc = lavie_temporal_conv_f16(d, C, d, F("bias"), F("bias2"), ldb2, rpb, P("R"), d, B, Fr, D, Cout, taps, d, nullptr);
+            } else if (entry == "timestep_sinusoid") {
+                const int B = I("B"), dim = I("dim");
+                if (!missing) rc = lavie_timestep_sinusoid_f32(fd, (float*)d, B, dim, nullptr);
+            } else if (entry == "gemv") {
+                const int B = I("B"), N = I("N"), K = I("K"), ai = I("act_in"), ao = I("act_out");
+                if (!missing) rc = lavie_gemv_f16(fd, d, F("bias"), (float*)d, B, N, K, ai, ao, nullptr);
+            } else if (entry == "pack_conv_in" || entry == "pack_conv_out") {
+                const int Cout = I("Cout"), Cin = I("Cin");
+                if (!missing) rc = entry == "pack_conv_in" ? lavie_pack_conv_in_f16(d, d, Cout, Cin, nullptr) : lavie_pack_conv_out_f16(d, d, Cout, Cin, nullptr);
+            } else if (entry == "conv_in" || entry == "conv_out") {
+                const int B = I("B"), Cin = I("Cin"), Fr = I("F"), Hh = I("H"), Ww = I("W"), Cout = I("Cout");
+                if (!missing)
+                    rc = entry == "conv_in" ? lavie_conv_in_f16(d, d, fd, d, B, Cin, Fr, Hh, Ww, Cout, nullptr)
+                                            : lavie_conv_out_f16(d, d, fd, d, B, Cin, Fr, Hh, Ww, Cout, nullptr);
+            } else if (entry == "add_class_emb_silu") {
+                const int B = I("B"), N = I("N"), nc = I("num_classes"), label = O("label");
+                int labels[16];
+                for (int& v : labels) v = label;
+                if (!missing) rc = lavie_add_class_emb_silu_f32((float*)d, d, labels, B, N, nc, nullptr);
+            } else if (entry == "fill_relpos_bias") {
+                const int heads = I("heads"), Fr = I("F"), nb = I("num_buckets");
+                if (!missing) rc = lavie_fill_relpos_bias_f32(d, (const int*)d, (float*)d, heads, Fr, nb, nullptr);
+            } else if (entry == "ln_fold") {
+                const int N = I("N"), K = I("K");
+                if (!missing) rc = lavie_ln_fold_f16(d, fd, fd, P("bias_f16"), d, (float*)d, (float*)d, N, K, nullptr);
+            } else if (entry == "pack_geglu_vec") {
+                const int N = I("N");
+                if (!missing) rc = lavie_pack_geglu_vec_f32(fd, (float*)d, N, nullptr);
+            } else if (entry == "copy_rows") {
+                const int ls = I("ld_src"), ld = I("ld_dst"), rows = I("rows"), cols = I("cols"), col0 = I("col0");
+                if (!missing) rc = lavie_copy_rows_f16(d, ls, d, ld, rows, cols, col0, nullptr);
+            } else if (entry == "f16_to_f32") {
+                const int n = I("n");
+                if (!missing) rc = lavie_f16_to_f32(d, P("b"), (float*)d, n, nullptr);
+            } else if (entry == "pack_geglu_mlp") {         // the pack_* / bind_* steps of the row-resident blocks copy index lists: exactly sized buffers
+                const int C = I("C");
+                const long long ib = lavie_geglu_mlp_image_bytes(C), bf = lavie_geglu_mlp_bias_floats(C);
+                if (!missing) {
+                    std::vector<unsigned short> w1((size_t)8 * C * C), b1((size_t)8 * C), w2((size_t)4 * C * C), img((size_t)(ib > 0 ? ib / 2 : 1));
+                    std::vector<float> b1img((size_t)(bf > 0 ? bf : 1));
+                    rc = ib > 0 ? lavie_pack_geglu_mlp_f16(w1.data(), b1.data(), w2.data(), C, img.data(), b1img.data(), nullptr) : -1;
+                }
+            } else if (entry == "bind_cross_block" || entry == "bind_cross_block_long") {
+                const int B = I("B"), L = I("ctx_len"), C = I("C");
+                const bool lng = entry == "bind_cross_block_long";
+                const long long ib = lng ? lavie_cross_block_long_image_bytes(C, 8) : lavie_cross_block_image_bytes(C, 8);
+                if (!missing) {
+                    std::vector<unsigned short> w((size_t)C * C), tmpl((size_t)(ib > 0 ? ib / 2 : 1)), kv((size_t)B * L * 2 * C), img((size_t)B * (ib > 0 ? ib / 2 : 1));
+                    rc = ib > 0 ? (lng ? lavie_pack_cross_block_long_f16(w.data(), w.data(), w.data(), C, tmpl.data(), nullptr)
+                                       : lavie_pack_cross_block_f16(w.data(), w.data(), w.data(), C, tmpl.data(), nullptr)) : -1;
+                    if (rc == 0)
+                        rc = lng ? lavie_bind_cross_block_long_f16(tmpl.data(), kv.data(), B, L, C, img.data(), nullptr)
+                                 : lavie_bind_cross_block_f16(tmpl.data(), kv.data(), B, L, C, img.data(), nullptr);
+                }
             } else {
                 fprintf(stderr, "hostcheck optrace: unknown entry point '%s'\n", entry.c_str());
                 return 2;
@@ -647,6 +702,51 @@ int main(int argc, char** argv) {
         REQUIRE(strstr(lavie_last_error(), "pad_lo") != nullptr);
         REQUIRE(lavie_conv3x3_down_f16(rows128.data(), 100, wd.data(), nullptr, yd.data(), N, Hh, Ww, 128, 2, 0, zero.data(), nullptr) != 0);
         REQUIRE(lavie_conv3x3_down_f16(rows128.data(), 128, wd.data(), nullptr, yd.data(), N, Hh, Ww, 128, 2, 0, nullptr, nullptr) != 0);
+        REQUIRE(lavie_hostcheck_launches() == accepted);
+    }
+    {   // the end and glue kernels' entry points: accepted calls reach the (stubbed) launch, every refusal comes before a HIP call
+        std::vector<unsigned short> h(4096 * 9);
+        std::vector<float> f(4096, 0.f);
+        int lab[9] = {0, 4, 4, 0, 0, 0, 0, 0, 0}, lab5[2] = {0, 5}, labm[2] = {-1, 0};
+        void* d = h.data();
+        const long before = lavie_hostcheck_launches();
+        REQUIRE(lavie_timestep_sinusoid_f32(f.data(), f.data(), 8, 320, nullptr) == 0);
+        REQUIRE(lavie_gemv_f16(f.data(), d, f.data(), f.data(), 2, 31, 320, 1, 1, nullptr) == 0);
+        REQUIRE(lavie_gemv_f16(f.data(), d, nullptr, f.data(), 8, 32, 2048, 0, 0, nullptr) == 0);
+        REQUIRE(lavie_pack_conv_in_f16(d, d, 8, 4, nullptr) == 0 && lavie_conv_in_f16(d, d, f.data(), d, 2, 4, 3, 3, 5, 8, nullptr) == 0);
+        REQUIRE(lavie_pack_conv_out_f16(d, d, 4, 64, nullptr) == 0 && lavie_conv_out_f16(d, d, f.data(), d, 2, 336, 3, 3, 5, 4, nullptr) == 0);
+        REQUIRE(lavie_conv_out_f16(d, d, f.data(), d, 2, 344, 3, 3, 5, 4, nullptr) == 0 && lavie_conv_out_f16(d, d, f.data(), d, 1, 64, 1, 1, 1, 3, nullptr) == 0);
+        REQUIRE(lavie_add_class_emb_silu_f32(f.data(), d, lab, 3, 1024, 5, nullptr) == 0);
+        REQUIRE(lavie_fill_relpos_bias_f32(d, (const int*)d, f.data(), 5, 17, 32, nullptr) == 0);
+        REQUIRE(lavie_ln_fold_f16(d, f.data(), f.data(), nullptr, d, f.data(), f.data(), 3, 72, nullptr) == 0);
+        REQUIRE(lavie_pack_geglu_vec_f32(f.data(), f.data(), 2560, nullptr) == 0);
+        REQUIRE(lavie_copy_rows_f16(d, 9, d, 31, 5, 7, 11, nullptr) == 0);
+        REQUIRE(lavie_f16_to_f32(d, nullptr, f.data(), 257, nullptr) == 0 && lavie_f16_to_f32(d, d, f.data(), 257, nullptr) == 0);
+        const long accepted = lavie_hostcheck_launches();
+        REQUIRE(accepted == before + 16);
+        REQUIRE(lavie_timestep_sinusoid_f32(f.data(), f.data(), 1, 3, nullptr) != 0 && lavie_timestep_sinusoid_f32(nullptr, f.data(), 1, 2, nullptr) != 0);
+        REQUIRE(lavie_gemv_f16(f.data(), d, nullptr, f.data(), 9, 32, 64, 0, 0, nullptr) != 0);
+        REQUIRE(lavie_gemv_f16(f.data(), d, nullptr, f.data(), 2, 32, 12, 0, 0, nullptr) != 0);
+        REQUIRE(lavie_gemv_f16(f.data(), d, nullptr, f.data(), 8, 32, 2056, 0, 0, nullptr) != 0);
+        REQUIRE(strstr(lavie_last_error(), "LDS") != nullptr);
+        REQUIRE(lavie_gemv_f16(f.data(), d, nullptr, f.data(), 2, 32, 64, 2, 0, nullptr) != 0 && lavie_gemv_f16(f.data(), nullptr, nullptr, f.data(), 2, 32, 64, 0, 0, nullptr) != 0);
+        REQUIRE(lavie_conv_in_f16(d, d, f.data(), d, 1, 7, 1, 1, 2, 8, nullptr) != 0 && lavie_conv_in_f16(d, d, f.data(), d, 1, 4, 1, 1, 2, 12, nullptr) != 0);
+        REQUIRE(lavie_conv_in_f16(d, d, f.data(), d, 1, 8, 1, 1, 2, 512, nullptr) != 0);
+        REQUIRE(strstr(lavie_last_error(), "LDS") != nullptr);
+        REQUIRE(lavie_conv_in_f16(d, d, nullptr, d, 1, 4, 1, 1, 2, 8, nullptr) != 0);
+        REQUIRE(lavie_pack_conv_in_f16(d, d, 8, 7, nullptr) != 0 && lavie_pack_conv_in_f16(d, d, 12, 4, nullptr) != 0);
+        REQUIRE(lavie_conv_out_f16(d, d, f.data(), d, 1, 60, 1, 1, 2, 4, nullptr) != 0 && lavie_conv_out_f16(d, d, f.data(), d, 1, 64, 1, 1, 2, 9, nullptr) != 0);
+        REQUIRE(lavie_conv_out_f16(d, d, f.data(), d, 1, 4096, 1, 1, 2, 8, nullptr) != 0);
+        REQUIRE(strstr(lavie_last_error(), "LDS") != nullptr);
+        REQUIRE(lavie_pack_conv_out_f16(d, nullptr, 4, 64, nullptr) != 0);
+        REQUIRE(lavie_add_class_emb_silu_f32(f.data(), d, lab5, 2, 8, 5, nullptr) != 0 && lavie_add_class_emb_silu_f32(f.data(), d, labm, 2, 8, 5, nullptr) != 0);
+        REQUIRE(strstr(lavie_last_error(), "label") != nullptr);
+        REQUIRE(lavie_add_class_emb_silu_f32(f.data(), d, lab, 9, 8, 5, nullptr) != 0);
+        REQUIRE(lavie_fill_relpos_bias_f32(d, nullptr, f.data(), 8, 16, 32, nullptr) != 0);
+        REQUIRE(lavie_ln_fold_f16(d, f.data(), f.data(), nullptr, d, nullptr, f.data(), 3, 72, nullptr) != 0);
+        REQUIRE(lavie_pack_geglu_vec_f32(f.data(), f.data(), 48, nullptr) != 0);
+        REQUIRE(lavie_copy_rows_f16(d, 7, d, 16, 3, 8, 0, nullptr) != 0 && lavie_copy_rows_f16(d, 8, d, 15, 3, 8, 8, nullptr) != 0);
+        REQUIRE(lavie_f16_to_f32(d, nullptr, f.data(), 0, nullptr) != 0 && lavie_f16_to_f32(nullptr, nullptr, f.data(), 4, nullptr) != 0);
         REQUIRE(lavie_hostcheck_launches() == accepted);
     }
     REQUIRE(lavie_upsample_conv3x3_supported(320, 32, 20, 32) >= 0);

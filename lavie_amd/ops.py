@@ -560,6 +560,148 @@ def latents_to_model_input1(x, model_in, input_scale: float = 1.0):
     _lib.check(_lib.load().lavie_latents_to_scaled_model_input1(_p(x), _p(model_in), x.numel(), float(input_scale), _stream()))
 
 
+# ------------------------------------------------------------------ the forward's end and glue kernels, one wrapper per kernel
+def timestep_sinusoid(t, dim, out=None):
+    """Timesteps(dim, flip_sin_to_cos=True, freq_shift=0): t fp32 [B] -> fp32 [B, dim] = [cos(t w_k) | sin(t w_k)]."""
+    _chk32(t)
+    B = t.shape[0]
+    out = _out(out, (B, dim), torch.float32, t.device, "timestep_sinusoid: out")
+    _lib.check(_lib.load().lavie_timestep_sinusoid_f32(_p(t), _p(out), B, dim, _stream()), "lavie_timestep_sinusoid_f32")
+    return out
+
+
+def gemv(x, weight, bias=None, act_in=False, act_out=False, out=None):
+    """act_out(act_in(x) @ weight^T + bias): x fp32 [B <= 8, K], weight fp16 [N, K], bias fp32 [N] -> fp32 [B, N]; act = SiLU."""
+    _chk32(x, bias)
+    _chk16(weight)
+    B, K = x.shape
+    N = weight.shape[0]
+    if weight.shape[1] != K or (bias is not None and bias.numel() != N):
+        raise ValueError(f"gemv: x {tuple(x.shape)}, weight {tuple(weight.shape)} and bias do not fit")
+    out = _out(out, (B, N), torch.float32, x.device, "gemv: out")
+    _lib.check(_lib.load().lavie_gemv_f16(_p(x), _p(weight), _p(bias), _p(out), B, N, K, int(act_in), int(act_out), _stream()), "lavie_gemv_f16")
+    return out
+
+
+def pack_conv_in(weight, out=None):
+    """[Cout, Cin, 3, 3] (fp16, device) -> the weight image of conv_in: 9 * Cin * Cout halfs, K pairs interleaved."""
+    _chk16(weight)
+    cout, cin = weight.shape[:2]
+    out = _out(out, (9 * cin * cout,), torch.float16, weight.device, "pack_conv_in: out")
+    _lib.check(_lib.load().lavie_pack_conv_in_f16(_p(weight), _p(out), cout, cin, _stream()), "lavie_pack_conv_in_f16")
+    return out
+
+
+def conv_in(x, wp, bias, cout, out=None):
+    """3x3 conv, pad 1, from the NCFHW latent x [b, cin, f, h, w] (fp16) to channels-last rows [(b f h w), cout]; wp from pack_conv_in."""
+    _chk16(x, wp)
+    _chk32(bias)
+    b, cin, f, h, w = x.shape
+    if wp.numel() != 9 * cin * cout or bias is None or bias.numel() != cout:
+        raise ValueError(f"conv_in: wp must be the pack_conv_in image of Cin={cin} Cout={cout} and bias [{cout}]")
+    y = _out(out, (b * f * h * w, cout), torch.float16, x.device, "conv_in: out")
+    _lib.check(_lib.load().lavie_conv_in_f16(_p(x), _p(wp), _p(bias), _p(y), b, cin, f, h, w, cout, _stream()), "lavie_conv_in_f16")
+    return y
+
+
+def pack_conv_out(weight, out=None):
+    """[Cout, Cin, 3, 3] (fp16, device) -> [Cout, 9 * Cin] in (tap, channel) order: the weights of conv_out."""
+    _chk16(weight)
+    cout, cin = weight.shape[:2]
+    out = _out(out, (cout, 9 * cin), torch.float16, weight.device, "pack_conv_out: out")
+    _lib.check(_lib.load().lavie_pack_conv_out_f16(_p(weight), _p(out), cout, cin, _stream()), "lavie_pack_conv_out_f16")
+    return out
+
+
+def conv_out(x, wp, bias, b, f, h, w, out=None):
+    """3x3 conv, pad 1, from channels-last rows x [(b f h w), cin] to the NCFHW output [b, cout <= 8, f, h, w] (fp16); wp from pack_conv_out."""
+    _chk16(x, wp)
+    _chk32(bias)
+    cin, cout = x.shape[1], wp.shape[0]
+    if x.shape[0] != b * f * h * w or tuple(wp.shape) != (cout, 9 * cin) or bias is None or bias.numel() != cout:
+        raise ValueError(f"conv_out: x must be [{b * f * h * w}, cin] rows, wp [cout, 9 cin] and bias [cout]")
+    y = _out(out, (b, cout, f, h, w), torch.float16, x.device, "conv_out: out")
+    _lib.check(_lib.load().lavie_conv_out_f16(_p(x), _p(wp), _p(bias), _p(y), b, cin, f, h, w, cout, _stream()), "lavie_conv_out_f16")
+    return y
+
+
+def add_class_emb_silu(emb, table, labels):
+    """emb[b] = silu(emb[b] + table[labels[b]]) in place: emb fp32 [B <= 8, N], table fp16 [num_classes, N], labels a sequence of ints."""
+    _chk32(emb)
+    _chk16(table)
+    B, N = emb.shape
+    labels = [int(v) for v in labels]
+    if len(labels) != B or table.shape[1] != N:
+        raise ValueError(f"add_class_emb_silu: emb {tuple(emb.shape)}, table {tuple(table.shape)} and {len(labels)} labels do not fit")
+    arr = (ctypes.c_int * max(B, 1))(*labels)
+    _lib.check(_lib.load().lavie_add_class_emb_silu_f32(_p(emb), _p(table), arr, B, N, table.shape[0], _stream()), "lavie_add_class_emb_silu_f32")
+    return emb
+
+
+def fill_relpos_bias(emb, frames, max_distance=128, buckets=None, out=None):
+    """RelativePositionBias: emb fp16 [num_buckets, heads] -> fp32 [heads, F, F] = emb[bucket(i, j), h].  The bucket table is built
+    here (relpos_buckets) and uploaded, so every index the kernel reads is in range; `buckets` (int32 device tensor [F, F]) is
+    where the table is placed when the caller wants to own that buffer — its contents are overwritten with the table."""
+    _chk16(emb)
+    nb, heads = emb.shape
+    table = relpos_buckets(frames, nb, max_distance).to(torch.int32)
+    if buckets is None:
+        buckets = table.to(emb.device)
+    else:
+        if not (buckets.dtype == torch.int32 and buckets.is_contiguous() and tuple(buckets.shape) == (frames, frames) and buckets.device == emb.device):
+            raise ValueError(f"fill_relpos_bias: buckets must be a contiguous int32 [{frames}, {frames}] tensor on {emb.device}")
+        buckets.copy_(table)
+    out = _out(out, (heads, frames, frames), torch.float32, emb.device, "fill_relpos_bias: out")
+    _lib.check(_lib.load().lavie_fill_relpos_bias_f32(_p(emb), _p(buckets), _p(out), heads, frames, nb, _stream()), "lavie_fill_relpos_bias_f32")
+    return out
+
+
+def ln_fold(weight, gamma, beta, bias=None, w_out=None, s_out=None, b_out=None):
+    """The LayerNorm fold linear_lnfold consumes: (fp16(weight * gamma) [N, K], its fp32 row sums [N], weight @ beta (+ bias) [N]);
+    weight fp16 [N, K], gamma / beta fp32 [K], bias fp16 [N] or None."""
+    _chk16(weight, bias)
+    _chk32(gamma, beta)
+    N, K = weight.shape
+    if gamma.numel() != K or beta.numel() != K or (bias is not None and bias.numel() != N):
+        raise ValueError(f"ln_fold: weight {tuple(weight.shape)}, gamma, beta and bias do not fit")
+    w_out = _out(w_out, (N, K), torch.float16, weight.device, "ln_fold: w_out")
+    s_out = _out(s_out, (N,), torch.float32, weight.device, "ln_fold: s_out")
+    b_out = _out(b_out, (N,), torch.float32, weight.device, "ln_fold: b_out")
+    _lib.check(_lib.load().lavie_ln_fold_f16(_p(weight), _p(gamma), _p(beta), _p(bias), _p(w_out), _p(s_out), _p(b_out), N, K, _stream()),
+               "lavie_ln_fold_f16")
+    return w_out, s_out, b_out
+
+
+def pack_geglu_vec(v, out=None):
+    """pack_geglu's row permutation on an fp32 vector [N] (the folded bias and row sums of a GEGLU projection)."""
+    _chk32(v)
+    N = v.numel()
+    out = _out(out, (N,), torch.float32, v.device, "pack_geglu_vec: out")
+    _lib.check(_lib.load().lavie_pack_geglu_vec_f32(_p(v), _p(out), N, _stream()), "lavie_pack_geglu_vec_f32")
+    return out
+
+
+def copy_rows(src, dst, col0, cols=None):
+    """dst[r, col0 + c] = src[r, c] for the first `cols` columns (default: all) of every row of src; fp16 [rows, ld] tensors."""
+    _chk16(src, dst)
+    rows, ld_src = src.shape
+    cols = ld_src if cols is None else cols
+    if dst.dim() != 2 or dst.shape[0] != rows:
+        raise ValueError(f"copy_rows: dst must have the {rows} rows of src")
+    _lib.check(_lib.load().lavie_copy_rows_f16(_p(src), ld_src, _p(dst), dst.shape[1], rows, cols, col0, _stream()), "lavie_copy_rows_f16")
+    return dst
+
+
+def f16_to_f32(a, b=None, out=None):
+    """float(a) (+ float(b)): fp16 tensors -> fp32 of a's shape."""
+    _chk16(a, b)
+    if b is not None and b.shape != a.shape:
+        raise ValueError("f16_to_f32: a and b must have one shape")
+    out = _out(out, a.shape, torch.float32, a.device, "f16_to_f32: out")
+    _lib.check(_lib.load().lavie_f16_to_f32(_p(a), _p(b), _p(out), a.numel(), _stream()), "lavie_f16_to_f32")
+    return out
+
+
 # ------------------------------------------------------------------ engine seams (sub-module forwards)
 def unet_resnet_block(net, prefix: str, x1, x2, temb, b: int, f: int, h: int, w: int):
     """ResnetBlock3D.forward of `net`'s block `prefix` on channels-last rows (x2 = skip half or None).

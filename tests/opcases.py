@@ -20,9 +20,14 @@ f16, f32t, f64 = torch.float16, torch.float32, torch.float64
 
 
 class Case:
-    def __init__(self, name, inputs, outputs, run, ref, c, model, where, alias=None, regions=None, setup=None):
+    def __init__(self, name, inputs, outputs, run, ref, c, model, where, alias=None, regions=None, setup=None, u=oc.U16, partial=None,
+                 exact=None, post=None):
         self.name, self.inputs, self.outputs, self.run, self.c, self.model, self.where = name, inputs, outputs, run, c, model, where
         self.alias = alias or {}
+        self.u = u                            # the relative term's unit roundoff: U16, U32 for an fp32 output (or name -> u)
+        self.partial = partial or {}          # name -> bool mask of the elements the call must write (opcheck.run_guarded)
+        self.exact = exact or {}              # name -> the expected tensor of a pure move / exact conversion, compared bit for bit
+        self.post = post                      # optional further assertion on the outputs (a property the bound does not express)
         self._ref = ref
         self.regions = regions or {}          # name -> bool mask over output "y": regions asserted on their own as well
         self.setup = setup                    # optional context manager factory (forced kernels)
@@ -39,10 +44,15 @@ class Case:
         for k, (ref, scale) in self.ref.items():
             w = self.where[k] if isinstance(self.where, dict) else self.where
             c = self.c[k] if isinstance(self.c, dict) else self.c
-            oc.assert_elementwise(got[k], ref, scale, c, where=w, label=f"{label}{self.name}:{k}")
+            u = self.u[k] if isinstance(self.u, dict) else self.u
+            oc.assert_elementwise(got[k], ref, scale, c, where=w, label=f"{label}{self.name}:{k}", u=u)
             if k == "y":
                 for rname, mask in self.regions.items():
-                    oc.assert_elementwise(got[k], ref, scale, c, where=w, label=f"{label}{self.name}:{k}:{rname}", mask=mask)
+                    oc.assert_elementwise(got[k], ref, scale, c, where=w, label=f"{label}{self.name}:{k}:{rname}", mask=mask, u=u)
+        for k, want in self.exact.items():
+            oc.assert_bits(got[k], want, where=self.where[k] if isinstance(self.where, dict) else self.where, label=f"{label}{self.name}:{k}")
+        if self.post is not None and not label.startswith("model"):      # a property of the kernel's arithmetic, not of torch's
+            self.post(got)
 
 
 # the six kernel choices the GPU operator tests run every case under: name -> (force_tile, force_splits)
@@ -290,19 +300,28 @@ NOT_PLANNED = {}
 # kernels of the launch-trace fixture that no operator entry point launches: name -> the existing test that exercises it
 WHOLE_FORWARD = "tests/test_gpu_engine.py (whole-output rel-L2 of the engine's blocks and forwards against the fp32 oracle)"
 NO_OPERATOR_ENTRY = {
-    "gn_fold_kernel": WHOLE_FORWARD, "gn_finalize_kernel": WHOLE_FORWARD, "rowstat_finalize_kernel": WHOLE_FORWARD, "ln_fold_kernel": WHOLE_FORWARD,
-    "copy_rows_kernel": WHOLE_FORWARD, "gemv_kernel": WHOLE_FORWARD, "conv_in_kernel": WHOLE_FORWARD, "conv_out4_kernel<5>": WHOLE_FORWARD,
-    "conv_out4_kernel<6>": WHOLE_FORWARD, "xb_gather2_kernel": WHOLE_FORWARD, "xb_gather8_kernel": WHOLE_FORWARD, "rf_gather8_kernel": WHOLE_FORWARD,
-    "rf_gather_f16_f32_kernel": WHOLE_FORWARD, "pack_conv3x3_kernel": "tests/test_gpu_ops_local.py::test_conv3x3 (ops.pack_conv3x3 feeds every conv case)",
+    # producer-side statistics: reached only behind the engine's rowstat_out / colstat_out, which no operator entry point sets
+    "gn_fold_kernel": WHOLE_FORWARD, "gn_finalize_kernel": WHOLE_FORWARD, "rowstat_finalize_kernel": WHOLE_FORWARD,
+    # the chunked form of the pack (the unchunked one: pack_conv_out_case) and the packs of the GEGLU / parity operands: bit-moves
+    # whose output every conv / GEGLU / parity case consumes
     "pack_conv3x3_parity_kernel": "tests/test_gpu_ops_local.py::test_upsample_conv3x3_parity (ops.pack_conv3x3_parity)",
-    "pack_conv_in_kernel": WHOLE_FORWARD, "pack_geglu_bias_kernel": "tests/test_gpu_ops_local.py::test_geglu (ops.pack_geglu)",
-    "pack_geglu_rows_kernel": "tests/test_gpu_ops_local.py::test_geglu (ops.pack_geglu)", "pack_geglu_vec_kernel": WHOLE_FORWARD,
-    "fill_relpos_bias_kernel": WHOLE_FORWARD, "timestep_sinusoid_kernel": WHOLE_FORWARD, "add_class_emb_silu_kernel": WHOLE_FORWARD,
-    "f16_to_f32_kernel": WHOLE_FORWARD,
-    # producer-side statistics: a run-time branch of the reduce that only the engine's colstat_out selects; its sums are covered by the
-    # engine's verify pass alone
+    "pack_geglu_bias_kernel": "tests/test_gpu_ops_local.py::test_geglu (ops.pack_geglu)",
+    "pack_geglu_rows_kernel": "tests/test_gpu_ops_local.py::test_geglu (ops.pack_geglu)",
+    # a run-time branch of the reduce that only the engine's colstat_out selects; its sums are covered by the engine's verify pass alone
     "splitk_reduce_cs_kernel": WHOLE_FORWARD + "; its column sums only by the engine's verify pass",
 }
+# gather kernels of the row-resident blocks' pack / bind steps: launched by lavie_pack_geglu_mlp_f16 and lavie_bind_cross_block[_long]_f16
+# (`hostcheck optrace`, asserted by test_gemm_reach_host.py), which the block cases call before the kernel whose output they check
+PACK_STEP_KERNELS = {
+    "rf_gather8_kernel": "tests/test_gpu_ops_local.py::test_geglu_mlp, ::test_cross_block (ops.pack_geglu_mlp, ops.pack_cross_block[_long])",
+    "rf_gather_f16_f32_kernel": "tests/test_gpu_ops_local.py::test_geglu_mlp (ops.pack_geglu_mlp)",
+    "xb_gather2_kernel": "tests/test_gpu_ops_local.py::test_cross_block (ops.bind_cross_block[_long])",
+    "xb_gather8_kernel": "tests/test_gpu_ops_local.py::test_cross_block (ops.bind_cross_block[_long])",
+}
+# the end and glue kernels of tests/test_gpu_ends_local.py: each must be launched by a case of ends_cases() (test_gemm_reach_host.py)
+ENDS_KERNELS = ("timestep_sinusoid_kernel", "gemv_kernel", "add_class_emb_silu_kernel", "conv_in_kernel", "conv_out4_kernel<5>", "conv_out4_kernel<6>",
+                "conv_out_kernel", "ln_fold_kernel", "pack_conv_in_kernel", "pack_conv3x3_kernel", "pack_geglu_vec_kernel", "copy_rows_kernel",
+                "f16_to_f32_kernel", "fill_relpos_bias_kernel")
 # the fixture's other names, by the prefix of the kernels the attention, norm, row-resident, temporal and elementwise cases launch
 COVERED_ELSEWHERE = ("attention_dma_kernel<", "attention_kernel<", "attention_wide_kernel", "gn_affine_kernel", "gn_apply_kernel<", "gn_stats_kernel<",
                      "layernorm_kernel", "geglu_mlp_kernel<", "cross_block_kernel<", "temporal_block_kernel<", "proj_qkv_kernel<",
@@ -1346,6 +1365,488 @@ def lora_case(N, K, r, in_place):
                 lambda: {"y": terms(lambda t: t.float(), ident).half()}, oc.loc_rows(K), alias={"y": "w0"} if in_place else None)
 
 
+# ------------------------------------------------------------------ the forward's ends and glue: time embedding, the NCFHW boundary, load-time packs
+# Every kernel here has one entry point of its own (lavie_amd/ops.py, "end and glue kernels").  fp32 outputs are checked with
+# u = U32.  Pure moves and exact conversions are compared bit for bit (Case.exact) against the index formula of the kernel's header
+# comment written out in torch indexing.
+GEOMS = [(1, 1, 1, 1), (1, 1, 3, 5), (2, 3, 3, 5), (1, 2, 8, 8)]          # (B, F, H, W): M = 1, 15 (< a wave's 16 pixels), 90, 128
+LOG2E32 = torch.tensor(LOG2E, dtype=f32t)
+
+
+def wave_sum32(t):
+    """common.h wave_sum on the last axis (64 lanes): v += shfl_xor(v, o) for o = 32 .. 1, in fp32; lane 0's value"""
+    lanes = torch.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        t = t + t[..., lanes ^ o]
+    return t[..., 0]
+
+
+def silu32(x):
+    """common.h silu_f in torch fp32: x / (1 + exp2(-x log2 e))"""
+    return x / (1.0 + torch.exp2(-x * LOG2E32))
+
+
+def silu_rel(x):
+    """The error of silu_f relative to |silu(x)|, counted in its source (common.h:61, x / (1.0f + __expf(-x)), __expf = exp2 of the
+    product with fp32 log2 e), in units of 2^-23 = one fp32 ulp, with s = e / (1 + e) = sigmoid(-x) <= 1 the factor by which a
+    relative error of e = exp(-x) reaches the quotient:
+      the product -x log2(e): one rounding and the constant's own, 2 * 2^-24 |x log2 e| absolute in the exponent, times ln 2:  |x| s
+      the hardware exp2 (v_exp_f32, 1 ulp):                                                                                    1 s
+      the add 1 + e (half an ulp of the sum):                                                                                  0.5
+      the divide (correctly rounded or not: 1 ulp):                                                                            1
+    = 2.5 + |x| s at first order, counted as 3 + |x| s."""
+    return oc.U32 * (3.0 + x.abs() * torch.sigmoid(-x))
+
+
+def frames_nchw(x5):
+    """[B, C, F, H, W] -> per-frame images [(B F), C, H, W]"""
+    B, Cc, Fr, H, W = x5.shape
+    return x5.permute(0, 2, 1, 3, 4).reshape(B * Fr, Cc, H, W)
+
+
+def im2col(xf, cin):
+    """per-frame images [N, cin, H, W] -> [N H W, 9 cin] in (tap, channel) order, zeros outside the image"""
+    N, _, H, W = xf.shape
+    xp = F.pad(xf, (1, 1, 1, 1))
+    cols = [xp[:, :, ky:ky + H, kx:kx + W].permute(0, 2, 3, 1).reshape(N * H * W, cin) for ky in range(3) for kx in range(3)]
+    return torch.cat(cols, 1)
+
+
+def conv_out_route(cin, cout):
+    """launch_conv_out's choice (elementwise.hip), as the name the launch trace shows"""
+    slots = 9 * (cin // 8)
+    if cout == 4 and slots <= 64 * 6:
+        return "conv_out4_kernel<5>" if slots <= 64 * 5 else "conv_out4_kernel<6>"
+    return "conv_out_kernel"
+
+
+def conv_out_lanes(P, Wk, drop_from=None):
+    """conv_out_kernel / conv_out4_kernel in fp32: P [M, 9 cin] (im2col), Wk [cout, 9 cin]; slot i = (tap, 8-channel vector) belongs
+    to lane i % 64 and is its (i / 64)-th; a lane adds its slots' eight exact products in order (four fdot2, each as two fp32 fmas),
+    then the butterfly.  drop_from: slots from this one on are left out (an injected defect)."""
+    M, K = P.shape
+    slots = K // 8
+    nv = -(-slots // 64)
+    pad = nv * 64 * 8 - K
+    Pp, Wp_ = F.pad(P, (0, pad)).reshape(M, nv, 64, 8), F.pad(Wk, (0, pad)).reshape(-1, nv, 64, 8)
+    if drop_from is not None:
+        keep = (torch.arange(nv * 64) < drop_from).reshape(nv, 64, 1).float()
+        Wp_ = Wp_ * keep
+    acc = torch.zeros(M, Wk.shape[0], 64)
+    for j in range(nv):
+        for e in range(8):
+            acc = acc + Pp[:, None, j, :, e] * Wp_[None, :, j, :, e]
+    return wave_sum32(acc)
+
+
+@functools.lru_cache(maxsize=None)
+def conv_out_case(cin, cout, geom):
+    """channels-last rows [M, cin] -> NCFHW [B, cout, F, H, W]; GEMM family, K_terms = 9 cin (the bias add and the store are in the
+    8 of gemm_c)."""
+    B, Fr, H, W = geom
+    g = gen("conv_out", cin, cout, geom)
+    x5 = rnd(g, B, cin, Fr, H, W)
+    wt, b = rnd(g, cout, cin, 3, 3, s=1 / math.sqrt(9 * cin)), rnd(g, cout, dtype=f32t, s=0.5)
+    ins = {"x": rows(frames_nchw(x5)), "wt": wt, "b": b}
+    back = lambda y: y.reshape(B, Fr, cout, H, W).permute(0, 2, 1, 3, 4).contiguous()
+
+    def run(ops, i, o):
+        wp = ops.pack_conv_out(i["wt"], out=torch.empty(cout, 9 * cin, dtype=f16, device=i["wt"].device))
+        ops.conv_out(i["x"], wp, i["b"], B, Fr, H, W, out=o["y"])
+
+    def terms(cv, absval):
+        p = (lambda t: t.abs()) if absval else (lambda t: t)
+        return back(F.conv2d(p(cv(frames_nchw(x5))), p(cv(wt)), p(cv(b)), padding=1))
+
+    def model(drop_from=None):
+        P = im2col(frames_nchw(x5).float(), cin)
+        Wk = wt.float().permute(0, 2, 3, 1).reshape(cout, 9 * cin)
+        y = (conv_out_lanes(P, Wk, drop_from) + b).half()                       # [M, cout]
+        return {"y": back(y.reshape(B * Fr, H, W, cout).permute(0, 3, 1, 2))}
+
+    border = torch.ones(B, cout, Fr, H, W, dtype=torch.bool)
+    if H > 2 and W > 2:
+        border[..., 1:-1, 1:-1] = False
+    m = torch.arange(B * Fr * H * W)
+    crossed = ((m // 16 * 16) // (H * W) != m // (H * W)).reshape(B, 1, Fr, H, W).expand(B, cout, Fr, H, W)   # a wave's 16-pixel run began in another image
+    case = Case(f"conv_out[{cin}->{cout},{'x'.join(map(str, geom))}]", ins, {"y": ((B, cout, Fr, H, W), f16)}, run,
+                lambda: {"y": (terms(d, False), terms(d, True))}, oc.gemm_c(9 * cin), model,
+                lambda i: "(batch %d, channel %d, frame %d, y %d, x %d)" % (i // (cout * Fr * H * W), i // (Fr * H * W) % cout, i // (H * W) % Fr, i // W % H, i % W),
+                regions={"border": border.reshape(-1), "run_from_another_image": crossed.reshape(-1)})
+    case.kernel = conv_out_route(cin, cout)
+    return with_calls(case, [call("pack_conv_out", Cout=cout, Cin=cin), call("conv_out", B=B, Cin=cin, F=Fr, H=H, W=W, Cout=cout)])
+
+
+# (cin, cout): conv_out4<5> at 288 and 72 slots (lanes above 8 idle in the second register slot), conv_out4<6> at 360 and 378 (the
+# most it takes), the general kernel at the first cin past the register kernel and at cout != 4
+CONV_OUT_SHAPES = [(256, 4), (64, 4), (320, 4), (336, 4), (344, 4), (64, 8), (64, 3)]
+CONV_OUT_REFUSED = [(60, 4), (64, 9), (4096, 8)]          # cin % 8, cout > 8, LDS
+
+
+@functools.lru_cache(maxsize=None)
+def conv_in_case(cin, cout, geom):
+    """NCFHW [B, cin, F, H, W] -> channels-last rows; GEMM family, K_terms = 9 cin.  A thread starts from the bias and adds the
+    taps inside the image in (tap, channel) order, two channels per fdot2."""
+    B, Fr, H, W = geom
+    g = gen("conv_in", cin, cout, geom)
+    x5 = rnd(g, B, cin, Fr, H, W)
+    wt, b = rnd(g, cout, cin, 3, 3, s=1 / math.sqrt(9 * cin)), rnd(g, cout, dtype=f32t, s=0.5)
+    ins = {"x": x5, "wt": wt, "b": b}
+
+    def run(ops, i, o):
+        wp = ops.pack_conv_in(i["wt"], out=torch.empty(9 * cin * cout, dtype=f16, device=i["wt"].device))
+        ops.conv_in(i["x"], wp, i["b"], cout, out=o["y"])
+
+    def terms(cv, absval):
+        p = (lambda t: t.abs()) if absval else (lambda t: t)
+        return rows(F.conv2d(p(cv(frames_nchw(x5))), p(cv(wt)), p(cv(b)), padding=1))
+
+    def model(swap_pair=None):
+        """swap_pair: the K pair whose two channels are exchanged on the activation side (an injected defect)"""
+        P = im2col(frames_nchw(x5).float(), cin)
+        if swap_pair is not None:
+            P = P.clone()
+            P[:, [2 * swap_pair, 2 * swap_pair + 1]] = P[:, [2 * swap_pair + 1, 2 * swap_pair]]
+        Wk = wt.float().permute(0, 2, 3, 1).reshape(cout, 9 * cin)
+        acc = b.float().expand(P.shape[0], cout).clone()
+        for k in range(9 * cin):
+            acc = acc + P[:, k:k + 1] * Wk[None, :, k]
+        return {"y": acc.half()}
+
+    case = Case(f"conv_in[{cin}->{cout},{'x'.join(map(str, geom))}]", ins, {"y": ((B * Fr * H * W, cout), f16)}, run,
+                lambda: {"y": (terms(d, False), terms(d, True))}, oc.gemm_c(9 * cin), model, oc.loc_image(B * Fr, H, W, cout),
+                regions={"border": border_mask(B * Fr, H, W, cout)})
+    return with_calls(case, [call("pack_conv_in", Cout=cout, Cin=cin), call("conv_in", B=B, Cin=cin, F=Fr, H=H, W=W, Cout=cout)])
+
+
+CONV_IN_SHAPES = [(ci, co) for ci in (4, 8, 2) for co in (8, 256, 320)]
+CONV_IN_REFUSED = [(7, 8), (4, 12), (8, 512)]             # cin odd, cout % 8, LDS: 9 * 8 * 512 * 2 > 65536
+
+
+def conv_in_fits(cin, cout):
+    return 9 * cin * cout * 2 <= 65536
+
+
+def move_case(name, ins, outs, run, expect, where=None, partial=None, calls=None):
+    """A pure move or an exact conversion: expect() -> name -> the expected tensor, compared bit for bit (and, trivially, through the
+    bound with u = c = 0).  partial outputs hold the finite poison outside their mask in what run_guarded returns."""
+    def ref():
+        return {k: (v.to(f64), torch.zeros(v.shape, dtype=f64)) for k, v in expect().items()}
+    case = Case(name, ins, outs, run, ref, 0.0, expect, where or (lambda i: f"element {i}"), u=0.0, partial=partial)
+    case.exact = _Lazy(expect)
+    return with_calls(case, calls) if calls else case
+
+
+class _Lazy(dict):
+    """name -> tensor, computed on first use"""
+
+    def __init__(self, fn):
+        super().__init__()
+        self._fn = fn
+
+    def items(self):
+        if not len(self):
+            self.update(self._fn())
+        return super().items()
+
+
+@functools.lru_cache(maxsize=None)
+def pack_conv_in_case(cin, cout):
+    """out[(k / 2) * cout * 2 + co * 2 + k % 2] = w[co, ci, ky, kx], k = (ky * 3 + kx) * cin + ci (elementwise.hip pack_conv_in_kernel)"""
+    w = rnd(gen("pack_conv_in", cin, cout), cout, cin, 3, 3)
+
+    def expect():
+        wk = w.permute(2, 3, 1, 0).reshape(9 * cin, cout)                      # [k, co]
+        return {"y": wk.reshape(9 * cin // 2, 2, cout).permute(0, 2, 1).reshape(-1).contiguous()}
+    return move_case(f"pack_conv_in[{cin}->{cout}]", {"w": w}, {"y": ((9 * cin * cout,), f16)}, lambda ops, i, o: ops.pack_conv_in(i["w"], out=o["y"]),
+                     expect, calls=[call("pack_conv_in", Cout=cout, Cin=cin)])
+
+
+@functools.lru_cache(maxsize=None)
+def pack_conv_out_case(cin, cout):
+    """the unchunked pack_conv3x3: out[co, tap * cin + ci] = w[co, ci, tap]"""
+    w = rnd(gen("pack_conv_out", cin, cout), cout, cin, 3, 3)
+    return move_case(f"pack_conv_out[{cin}->{cout}]", {"w": w}, {"y": ((cout, 9 * cin), f16)}, lambda ops, i, o: ops.pack_conv_out(i["w"], out=o["y"]),
+                     lambda: {"y": w.permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous()}, where=oc.loc_rows(9 * cin),
+                     calls=[call("pack_conv_out", Cout=cout, Cin=cin)])
+
+
+PACK_CONV_OUT_SHAPES = [(64, 4), (320, 4), (8, 3)]
+
+
+@functools.lru_cache(maxsize=None)
+def pack_geglu_vec_case(N):
+    v = rnd(gen("pack_geglu_vec", N), N, dtype=f32t)
+    return move_case(f"pack_geglu_vec[{N}]", {"v": v}, {"y": ((N,), f32t)}, lambda ops, i, o: ops.pack_geglu_vec(i["v"], out=o["y"]),
+                     lambda: {"y": v[geglu_perm(N)].contiguous()}, calls=[call("pack_geglu_vec", N=N)])
+
+
+COPY_ROWS = [(1, 1, 1, 1, 0), (3, 64, 64, 640, 576), (5, 7, 9, 31, 11), (320, 64, 64, 2944, 2880)]        # (rows, cols, ld_src, ld_dst, col0)
+COPY_ROWS_REFUSED = [(3, 8, 7, 16, 0), (3, 8, 8, 15, 8)]                                                   # ld_src < cols, ld_dst < col0 + cols
+
+
+@functools.lru_cache(maxsize=None)
+def copy_rows_case(nrows, cols, ld_src, ld_dst, col0, shift=0):
+    """dst[r, col0 + c] = src[r, c], c < cols: a sub-rectangle of dst — every other element keeps its poison (partial)"""
+    src = rnd(gen("copy_rows", nrows, cols, ld_src, ld_dst, col0), nrows, ld_src)
+    mask = torch.zeros(nrows, ld_dst, dtype=torch.bool)
+    mask[:, col0:col0 + cols] = True
+
+    def expect(shift=shift):
+        y = torch.full((nrows, ld_dst), oc.SENTINEL, dtype=f16)
+        y[:, col0 + shift:col0 + shift + cols] = src[:, :cols]
+        return {"y": y}
+    return move_case(f"copy_rows[{nrows}x{cols},ld{ld_src}->{ld_dst},col{col0}]", {"src": src}, {"y": ((nrows, ld_dst), f16)},
+                     lambda ops, i, o: ops.copy_rows(i["src"], o["y"], col0, cols=cols), expect, where=oc.loc_rows(ld_dst), partial={"y": mask},
+                     calls=[call("copy_rows", ld_src=ld_src, ld_dst=ld_dst, rows=nrows, cols=cols, col0=col0)])
+
+
+@functools.lru_cache(maxsize=None)
+def f16_to_f32_case(n, two):
+    """float(a) (+ float(b)): the sum of two fp16 values is exact in fp32"""
+    g = gen("f16_to_f32", n, two)
+    ins = {"a": rnd(g, n)}
+    if two:
+        ins["b"] = rnd(g, n, s=37.0)
+
+    def expect():
+        return {"y": ins["a"].float() + ins["b"].float() if two else ins["a"].float()}
+    return move_case(f"f16_to_f32[{n},{'a+b' if two else 'a'}]", ins, {"y": ((n,), f32t)}, lambda ops, i, o: ops.f16_to_f32(i["a"], i.get("b"), out=o["y"]),
+                     expect, calls=[call("f16_to_f32", n=n, b=two)])
+
+
+def relpos_table(Fr, num_buckets, max_distance):
+    """relpos_bucket_table (elementwise.hip) in Python: the T5 bucket of (query i, key j)"""
+    half_b = num_buckets // 2
+    exact = half_b // 2
+    out = torch.zeros(Fr, Fr, dtype=torch.int32)
+    for i in range(Fr):
+        for j in range(Fr):
+            n = i - j
+            bkt = half_b if n < 0 else 0
+            n = abs(n)
+            if n < exact:
+                bkt += n
+            else:
+                bkt += min(exact + int(math.floor(math.log(n / exact) / math.log(max_distance / exact) * (half_b - exact) + 1e-9)), half_b - 1)
+            out[i, j] = bkt
+    return out
+
+
+# (heads, F, max distance): 32 buckets.  The fixture tests/golden/relpos_buckets.pt holds F = 16 and 61 at the models' max distance 32,
+# so those two run at 32 against the fixture's table and at 128 like the others, whose table lavie_relpos_buckets builds
+RELPOS = [(8, 1, 128), (8, 16, 128), (8, 61, 128), (5, 17, 128), (8, 16, 32), (8, 61, 32)]
+
+
+@functools.lru_cache(maxsize=None)
+def relpos_case(heads, Fr, max_distance, nb=32):
+    """out[h, i, j] = float(emb[buckets[i, j], h]).  The wrapper builds the table with lavie_relpos_buckets and writes it over the
+    `buckets` operand: the input-unchanged check then says the library's table is the one here (the fixture's where it holds F)."""
+    emb = rnd(gen("relpos", heads, Fr, max_distance), nb, heads)
+    table = relpos_table(Fr, nb, max_distance)
+
+    def expect():
+        if max_distance == 32 and Fr in (16, 61):
+            fx = torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "relpos_buckets.pt"))
+            fx = {int(k): v for k, v in fx.items()}
+            assert torch.equal(fx[Fr].to(torch.int32), table), "the bucket table differs from tests/golden/relpos_buckets.pt"
+        return {"y": emb[table.long()].permute(2, 0, 1).float().contiguous()}
+    return move_case(f"fill_relpos_bias[h{heads},F{Fr},d{max_distance}]", {"emb": emb, "buckets": table}, {"y": ((heads, Fr, Fr), f32t)},
+                     lambda ops, i, o: ops.fill_relpos_bias(i["emb"], Fr, max_distance, buckets=i["buckets"], out=o["y"]), expect,
+                     where=lambda i: "(head %d, query %d, key %d)" % (i // (Fr * Fr), i // Fr % Fr, i % Fr),
+                     calls=[call("fill_relpos_bias", heads=heads, F=Fr, num_buckets=nb)])
+
+
+LN_FOLD = [(1, 64), (5, 320), (130, 320), (64, 1280), (3, 72)]
+
+
+@functools.lru_cache(maxsize=None)
+def ln_fold_case(N, K, with_bias):
+    """Wout = fp16(fp32(W gamma)), bit for bit.  s = sum_k Wout[n, k] and b = sum_k beta[k] W[n, k] (+ bias) in fp32: lane l adds
+    its ceil(K / 64) terms k = l, l + 64, ... serially, then six butterfly levels, so the summation depth is ceil(K / 64) + 6 and
+    c = depth 2^-23 (first order depth 2^-24, doubled); b has one more rounding per term (beta w) and the bias add: depth + 2.
+    gemm_c(K) would be ~30 times looser at K = 320 and pass an s summed from the unrounded W gamma."""
+    g = gen("ln_fold", N, K, with_bias)
+    w = rnd(g, N, K, s=1 / math.sqrt(K))
+    gamma, beta = 1 + 0.2 * torch.randn(K, generator=g), 0.2 * torch.randn(K, generator=g)
+    ins = {"w": w, "gamma": gamma, "beta": beta}
+    if with_bias:
+        ins["bias"] = rnd(g, N, s=0.3)
+    wout = (w.float() * gamma).half()
+    depth = -(-K // 64)
+
+    def run(ops, i, o):
+        ops.ln_fold(i["w"], i["gamma"], i["beta"], i.get("bias"), w_out=o["wout"], s_out=o["s"], b_out=o["b"])
+
+    def ref():
+        bb = (d(w) * d(beta)).sum(1)
+        sb = (d(w) * d(beta)).abs().sum(1)
+        if with_bias:
+            bb, sb = bb + d(ins["bias"]), sb + d(ins["bias"]).abs()
+        return {"wout": (d(wout), torch.zeros(N, K, dtype=f64)), "s": (d(wout).sum(1), d(wout).abs().sum(1)), "b": (bb, sb)}
+
+    def model(unrounded_s=False):
+        """unrounded_s: s summed from the fp32 product before its fp16 rounding (an injected defect)"""
+        pad = depth * 64 - K
+        lanes = lambda t: F.pad(t, (0, pad)).reshape(N, depth, 64)
+        ws = lanes(w.float() * gamma if unrounded_s else wout.float())
+        wb = lanes(beta * w.float())
+        s, b = torch.zeros(N, 64), torch.zeros(N, 64)
+        for t in range(depth):
+            s, b = s + ws[:, t], b + wb[:, t]
+        b = wave_sum32(b)
+        return {"wout": wout, "s": wave_sum32(s), "b": b + ins["bias"].float() if with_bias else b}
+
+    case = Case(f"ln_fold[{N}x{K},bias{int(with_bias)}]", ins, {"wout": ((N, K), f16), "s": ((N,), f32t), "b": ((N,), f32t)}, run, ref,
+                {"wout": 0.0, "s": (depth + 6) * oc.U32, "b": (depth + 8) * oc.U32}, model,
+                {"wout": oc.loc_rows(K), "s": lambda i: f"row {i}", "b": lambda i: f"row {i}"}, u={"wout": 0.0, "s": oc.U32, "b": oc.U32},
+                exact={"wout": wout})
+    return with_calls(case, [call("ln_fold", N=N, K=K, bias_f16=with_bias)])
+
+
+GEMV_SMALL = [(1, 1, 8), (2, 31, 320), (8, 33, 1280), (3, 64, 520), (8, 32, 2048)]
+GEMV_WIDE = (2, 19840, 320)                       # the engine's stacked time_emb_proj width, once, without activations
+GEMV_REFUSED = [(9, 32, 64), (2, 32, 12), (8, 32, 2056)]
+
+
+@functools.lru_cache(maxsize=None)
+def gemv_case(B, N, K, act_in, act_out, with_bias):
+    """out[b, n] = act_out(sum_k act_in(x[b, k]) W[n, k] + bias[n]) in fp32.  c = gemm_c(K) on sum |act_in(x) w| + |bias|; the error of
+    silu_f (silu_rel) enters relative to |silu(x)|: for act_in through the scale (sum_k |w| |silu(x_k)| silu_rel(x_k)), for act_out on
+    the result, whose pre-activation error passes through |silu'| < 1.1.  Batch rows 0 and B - 1 hold the same vector: their
+    outputs must have the same bits (the kernel's fixed fma order)."""
+    g = gen("gemv", B, N, K, act_in, act_out, with_bias)
+    x = rnd(g, B, K, dtype=f32t, s=1.5)
+    x[B - 1] = x[0]
+    w = rnd(g, N, K, s=1 / math.sqrt(K))
+    ins = {"x": x, "w": w}
+    if with_bias:
+        ins["bias"] = rnd(g, N, dtype=f32t, s=0.5)
+    c = oc.gemm_c(K)
+
+    def run(ops, i, o):
+        ops.gemv(i["x"], i["w"], i.get("bias"), act_in=act_in, act_out=act_out, out=o["y"])
+
+    def ref():
+        xa = silu64(d(x)) if act_in else d(x)
+        pre, sc = xa @ d(w).t(), xa.abs() @ d(w).abs().t()
+        extra = (xa.abs() * silu_rel(d(x))) @ d(w).abs().t() if act_in else torch.zeros_like(sc)
+        if with_bias:
+            pre, sc = pre + d(ins["bias"]), sc + d(ins["bias"]).abs()
+        if act_out:
+            y = silu64(pre)
+            return {"y": (y, 1.1 * (sc + extra / c) + y.abs() * silu_rel(pre) / c)}
+        return {"y": (pre, sc + extra / c)}
+
+    def model(row_from=None, clamp_spill=False):
+        """row_from: {b: b'} — batch row b reads row b''s staged vector (an injected defect)"""
+        xs = silu32(x) if act_in else x.clone()
+        for bdst, bsrc in (row_from or {}).items():
+            xs[bdst] = xs[bsrc]
+        trips = -(-K // 512)
+        xl = F.pad(xs, (0, trips * 512 - K)).reshape(B, 1, trips, 64, 8).double()
+        wl = F.pad(w.float(), (0, trips * 512 - K)).reshape(1, N, trips, 64, 8).double()
+        acc = torch.zeros(B, N, 64)
+        for t in range(trips):
+            for j in range(8):
+                acc = (acc.double() + xl[:, :, t, :, j] * wl[:, :, t, :, j]).float()           # one fma: the product is exact in float64
+        y = wave_sum32(acc)
+        if with_bias:
+            y = y + ins["bias"]
+        return {"y": silu32(y) if act_out else y}
+
+    def post(got):
+        if B > 1:
+            y = got["y"].detach().cpu()
+            assert torch.equal(y[0].view(torch.int32), y[B - 1].view(torch.int32)), \
+                f"gemv[{B}x{N}x{K}]: batch rows 0 and {B - 1} hold one input vector but differ in {(y[0] != y[B - 1]).sum()} outputs"
+
+    case = Case(f"gemv[{B}x{N}x{K},in{int(act_in)},out{int(act_out)},bias{int(with_bias)}]", ins, {"y": ((B, N), f32t)}, run, ref, c, model,
+                oc.loc_rows(N), u=oc.U32, post=post)
+    return with_calls(case, [call("gemv", B=B, N=N, K=K, act_in=act_in, act_out=act_out, bias=with_bias)])
+
+
+SINUSOID = [(1, 2), (2, 256), (8, 320)]
+TIMESTEPS = [0.0, 1.0, 999.0, 500.5, 0.001]
+# c_t: the relative error of the fp32 argument a = t w_k, counted in units of 2^-23 from timestep_sinusoid_kernel's source,
+#   w = expf(-logf(10000.0f) * (float)k / (float)half_dim):  z = the exponent, |z| <= ln 10000 = 9.22
+#     logf, 1 ulp in the HIP math API's table, taken as 2:  2        the product with k: 0.5        the divide: 1       -> 3.5 relative in z,
+#     3.5 * 9.22 = 32.3 absolute, which is the relative error it leaves in w;  expf, 1 ulp in the table, taken as 2:  2   -> 34.3
+#   a = t * w: 0.5  -> 34.8, counted as 35; doubled for the second-order terms: c_t = 70 * 2^-23 = 8.3e-6.
+# |cos(a') - cos(a)| <= |a' - a| <= c_t |a|, and cosf / sinf's own 2 ulp of a value <= 1 are below c_t * 1: bound (1 + |a|) c_t + U32 |ref|.
+# A frequency index off by one moves a by 6 % at dim = 320, four orders of magnitude above c_t.
+SINUSOID_CT = 70 * oc.U32
+
+
+@functools.lru_cache(maxsize=None)
+def sinusoid_case(B, dim):
+    half = dim // 2
+    t = torch.tensor([TIMESTEPS[i % len(TIMESTEPS)] for i in range(B)] if B > 1 else [999.0], dtype=f32t)
+    if B == 8:
+        t[5:] = torch.tensor([37.0, 250.25, 980.0])
+
+    def angle(cv, shift=0):
+        k = torch.arange(half) + shift
+        return cv(t)[:, None] * torch.exp(-math.log(10000.0) * cv(k) / half)[None]
+
+    def ref():
+        a = angle(d)
+        return {"y": (torch.cat([a.cos(), a.sin()], 1), torch.cat([1 + a.abs(), 1 + a.abs()], 1))}
+
+    def model(swap=False, shift=0):
+        k = (torch.arange(half) + shift).float()
+        wk = torch.exp(-torch.log(torch.tensor(10000.0)) * k / float(half))
+        a = t[:, None] * wk[None]
+        return {"y": torch.cat([a.sin(), a.cos()] if swap else [a.cos(), a.sin()], 1)}
+
+    case = Case(f"timestep_sinusoid[{B}x{dim}]", {"t": t}, {"y": ((B, dim), f32t)}, lambda ops, i, o: ops.timestep_sinusoid(i["t"], dim, out=o["y"]),
+                ref, SINUSOID_CT, model, oc.loc_rows(dim), u=oc.U32)
+    return with_calls(case, [call("timestep_sinusoid", B=B, dim=dim)])
+
+
+CLASS_EMB = [(1, 8, (4,)), (3, 1024, (0, 4, 4)), (8, 1280, (0, 4, 2, 2, 1, 3, 0, 4))]
+CLASS_EMB_REFUSED = [(2, 8, (0, 5)), (2, 8, (-1, 0)), (9, 8, (0,) * 9)]
+
+
+@functools.lru_cache(maxsize=None)
+def class_emb_case(B, N, labels, classes=5):
+    """emb = silu(emb + table[label]) in place: one fp32 add (2^-24 of the sum, doubled: c = 2^-23 on |emb| + |table|, through
+    |silu'| < 1.1) and silu_f's own error relative to the result."""
+    g = gen("class_emb", B, N, labels)
+    emb, table = rnd(g, B, N, dtype=f32t, s=1.5), rnd(g, classes, N)
+    lab = torch.tensor(labels)
+
+    def ref():
+        x = d(emb) + d(table)[lab]
+        y = silu64(x)
+        return {"y": (y, 1.1 * (d(emb).abs() + d(table)[lab].abs()) + y.abs() * silu_rel(x) / oc.U32)}
+
+    case = Case(f"add_class_emb_silu[{B}x{N}]", {"emb": emb, "table": table}, {"y": ((B, N), f32t)},
+                lambda ops, i, o: ops.add_class_emb_silu(o["y"], i["table"], labels), ref, oc.U32,
+                lambda: {"y": silu32(emb + table.float()[lab])}, oc.loc_rows(N), alias={"y": "emb"}, u=oc.U32)
+    return with_calls(case, [call("add_class_emb_silu", B=B, N=N, num_classes=classes)])
+
+
+def ends_cases():
+    """The cases of tests/test_gpu_ends_local.py, by family"""
+    fam = {}
+    fam["conv_out"] = [conv_out_case(ci, co, gm) for ci, co in CONV_OUT_SHAPES for gm in GEOMS]
+    fam["conv_in"] = [conv_in_case(ci, co, gm) for ci, co in CONV_IN_SHAPES if conv_in_fits(ci, co) for gm in GEOMS]
+    fam["pack"] = ([pack_conv_in_case(ci, co) for ci, co in CONV_IN_SHAPES if conv_in_fits(ci, co)] + [pack_conv_out_case(*s) for s in PACK_CONV_OUT_SHAPES]
+                   + [pack_geglu_vec_case(n) for n in (32, 64, 2560)] + [copy_rows_case(*s) for s in COPY_ROWS]
+                   + [f16_to_f32_case(n, two) for n in (1, 255, 256, 257) for two in (False, True)])
+    fam["ln_fold"] = [ln_fold_case(n, k, wb) for n, k in LN_FOLD for wb in (False, True)]
+    fam["gemv"] = ([gemv_case(*s, ai, ao, wb) for s in GEMV_SMALL for ai in (False, True) for ao in (False, True) for wb in (True, False)]
+                   + [gemv_case(*GEMV_WIDE, False, False, True)])
+    fam["timestep_sinusoid"] = [sinusoid_case(*s) for s in SINUSOID]
+    fam["add_class_emb_silu"] = [class_emb_case(*s) for s in CLASS_EMB]
+    fam["fill_relpos_bias"] = [relpos_case(*s) for s in RELPOS]
+    for cs in fam.values():
+        for c in cs:
+            c.variants = ("auto",)                 # none of these kernels depends on the GEMM choice: replayed once
+    return fam
+
+
 def restricted(case, variants):
     case.variants = variants
     return case
@@ -1391,6 +1892,8 @@ def all_cases():
     cs += [proj_qkv_case(nb, dd) for nb in (1, 5) for dd in (16, 48)]
     cs += [step_case(k, n) for k in STEP_KINDS for n in STEP_LENGTHS]
     cs += [lora_case(*s, ip) for s in LORA_SHAPES for ip in (False, True)]
+    # the forward's ends and glue kernels (tests/test_gpu_ends_local.py)
+    cs += [c for fam in ends_cases().values() for c in fam]
     return cs
 
 
@@ -1448,6 +1951,18 @@ def gemm_reach(cases):
     planner on the CPU, given the integers each case's `run` passes."""
     runs = gemm_runs(cases)
     lines = [optrace_line(e, ints, *fs) for c, _, fs in runs for e, ints in c.calls]
+    blocks = optrace(lines)
+    reach, it = {}, iter(blocks)
+    for c, v, _ in runs:
+        launches = []
+        for _ in c.calls:
+            launches += next(it)[1]
+        reach[(c.name, v)] = None if "!! refused" in launches else launches
+    return reach
+
+
+def optrace(lines):
+    """[(line, launch lines)] of `hostcheck optrace` for the given call lines"""
     with tempfile.TemporaryDirectory() as tmp:
         inp, out = os.path.join(tmp, "calls.txt"), os.path.join(tmp, "launches.txt")
         with open(inp, "w") as f:
@@ -1462,10 +1977,4 @@ def gemm_reach(cases):
         else:
             blocks[-1][1].append(l)
     assert [b[0] for b in blocks] == lines, "optrace output does not follow its input"
-    reach, it = {}, iter(blocks)
-    for c, v, _ in runs:
-        launches = []
-        for _ in c.calls:
-            launches += next(it)[1]
-        reach[(c.name, v)] = None if "!! refused" in launches else launches
-    return reach
+    return blocks

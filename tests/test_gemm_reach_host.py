@@ -64,12 +64,60 @@ def test_registered_instantiations_are_reached_or_listed(reach):
 def test_fixture_names_are_all_accounted_for(reach, fixture_names):
     required = {n for n in fixture_names if n.startswith(GEMM)}
     elsewhere = {n for n in fixture_names if n.startswith(C.COVERED_ELSEWHERE)}
-    assert required | elsewhere | set(C.NO_OPERATOR_ENTRY) == fixture_names, sorted(fixture_names - required - elsewhere - set(C.NO_OPERATOR_ENTRY))
+    ends = (set(C.ENDS_KERNELS) | set(C.PACK_STEP_KERNELS)) & fixture_names
+    assert ends - names(reach) - set(C.PACK_STEP_KERNELS) == set(), "an end or glue kernel of a forward that no case launches"
+    accounted = required | elsewhere | set(C.NO_OPERATOR_ENTRY) | ends
+    assert accounted == fixture_names, sorted(fixture_names - accounted)
     assert set(C.NO_OPERATOR_ENTRY) <= fixture_names and not (set(C.NO_OPERATOR_ENTRY) & elsewhere)
     assert not (set(C.NO_OPERATOR_ENTRY) & names(reach)), "a kernel listed as having no operator entry point was launched by one"
     for name, test in C.NO_OPERATOR_ENTRY.items():
         path = test.split("::")[0].split(" ")[0]
         assert os.path.exists(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), path)), (name, path)
+
+
+def test_end_and_glue_kernels_are_reached(reach, fixture_names):
+    """Every kernel of opcases.ENDS_KERNELS is launched by a case of ends_cases(), each conv_out case by the kernel its shape table
+    names (<5> / <6> / general), and every one but the general conv_out kernel (no model has Cout != 4 or Cin > 336) runs in a forward."""
+    by_family = C.ends_cases()
+    got = {k: {C.launch_name(l) for c in cs for l in reach[(c.name, "auto")]} for k, cs in by_family.items()}
+    assert set().union(*got.values()) == set(C.ENDS_KERNELS), sorted(set().union(*got.values()) ^ set(C.ENDS_KERNELS))
+    assert set(C.ENDS_KERNELS) - fixture_names == {"conv_out_kernel"}
+    assert got["conv_out"] == {"pack_conv3x3_kernel", "conv_out4_kernel<5>", "conv_out4_kernel<6>", "conv_out_kernel"}
+    assert got["gemv"] == {"gemv_kernel"} and got["ln_fold"] == {"ln_fold_kernel"} and got["conv_in"] == {"pack_conv_in_kernel", "conv_in_kernel"}
+    for c in by_family["conv_out"]:
+        assert [C.launch_name(l) for l in reach[(c.name, "auto")]] == ["pack_conv3x3_kernel", c.kernel], c.name
+    routes = {(ci, co): C.conv_out_route(ci, co) for ci, co in C.CONV_OUT_SHAPES}
+    assert routes == {(256, 4): "conv_out4_kernel<5>", (64, 4): "conv_out4_kernel<5>", (320, 4): "conv_out4_kernel<6>", (336, 4): "conv_out4_kernel<6>",
+                      (344, 4): "conv_out_kernel", (64, 8): "conv_out_kernel", (64, 3): "conv_out_kernel"}
+    # without a family, its kernels are missed
+    for fam, kernel in (("gemv", "gemv_kernel"), ("timestep_sinusoid", "timestep_sinusoid_kernel"), ("ln_fold", "ln_fold_kernel"),
+                        ("add_class_emb_silu", "add_class_emb_silu_kernel"), ("fill_relpos_bias", "fill_relpos_bias_kernel"), ("conv_in", "conv_in_kernel")):
+        assert kernel not in set().union(*(v for k, v in got.items() if k != fam)), (fam, kernel)
+    for ci, co in C.CONV_OUT_SHAPES:          # ... and without a conv_out shape pair, where it is the only one of its kernel and slot count
+        rest = {C.conv_out_route(a, b) for a, b in C.CONV_OUT_SHAPES if (a, b) != (ci, co)}
+        assert rest == {"conv_out4_kernel<5>", "conv_out4_kernel<6>", "conv_out_kernel"}      # two shapes per kernel: one at each end of its range
+
+
+def test_refusals_of_the_end_and_glue_entries():
+    """every refusal the GPU tests expect, from the library itself on the host-only build"""
+    lines = [f"conv_out B=1 Cin={ci} F=1 H=1 W=2 Cout={co}" for ci, co in C.CONV_OUT_REFUSED]
+    lines += [f"conv_in B=1 Cin={ci} F=1 H=1 W=2 Cout={co}" for ci, co in C.CONV_IN_REFUSED]
+    lines += [f"gemv B={b} N={n} K={k} act_in=0 act_out=0 bias=1" for b, n, k in C.GEMV_REFUSED]
+    lines += [f"copy_rows ld_src={ls} ld_dst={ld} rows={r} cols={c} col0={c0}" for r, c, ls, ld, c0 in C.COPY_ROWS_REFUSED]
+    lines += ["pack_geglu_vec N=48", "add_class_emb_silu B=2 N=8 num_classes=5 label=5", "add_class_emb_silu B=2 N=8 num_classes=5 label=-1",
+              "add_class_emb_silu B=9 N=8 num_classes=5"]
+    for line, launches in C.optrace(lines):
+        assert launches == ["!! refused"], (line, launches)
+
+
+def test_gather_kernels_belong_to_the_block_cases_pack_steps():
+    """rf_gather8 / rf_gather_f16_f32 / xb_gather2 / xb_gather8 are launched by lavie_pack_geglu_mlp_f16 and lavie_bind_cross_block[_long]_f16
+    (behind their pack), which geglu_mlp_case and cross_block_case call: they have an operator entry point."""
+    blocks = dict(C.optrace(["pack_geglu_mlp C=320", "bind_cross_block B=2 ctx_len=77 C=320", "bind_cross_block_long B=1 ctx_len=154 C=320"]))
+    got = {k: {C.launch_name(l) for l in v} for k, v in blocks.items()}
+    assert got["pack_geglu_mlp C=320"] == {"rf_gather8_kernel", "rf_gather_f16_f32_kernel"}
+    assert got["bind_cross_block B=2 ctx_len=77 C=320"] == got["bind_cross_block_long B=1 ctx_len=154 C=320"] == {"rf_gather8_kernel", "xb_gather2_kernel", "xb_gather8_kernel"}
+    assert set().union(*got.values()) == set(C.PACK_STEP_KERNELS) and not (set(C.PACK_STEP_KERNELS) & set(C.NO_OPERATOR_ENTRY))
 
 
 # what each table entry of opcases.py claims, from the trace: (case name, variant) -> kernel

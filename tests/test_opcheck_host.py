@@ -23,15 +23,18 @@ def test_fp32_model_meets_its_bound(case):
 
 # ------------------------------------------------------------------ the call descriptions of the GEMM-family cases
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "lavie_hip.h")
-REPLAYED = ("linear", "linear_lnfold", "linear_lnfold_geglu", "conv3x3", "conv3x3_down", "upsample_conv3x3", "temporal_conv")   # driver.cpp run_optrace
-OPTIONAL = ("bias", "bias2", "R", "x2", "sc1", "sc2")
+REPLAYED = ("linear", "linear_lnfold", "linear_lnfold_geglu", "conv3x3", "conv3x3_down", "upsample_conv3x3", "temporal_conv",   # driver.cpp run_optrace
+            "timestep_sinusoid", "gemv", "pack_conv_in", "conv_in", "pack_conv_out", "conv_out", "add_class_emb_silu", "fill_relpos_bias", "ln_fold",
+            "pack_geglu_vec", "copy_rows", "f16_to_f32")
+OPTIONAL = ("bias", "bias2", "R", "x2", "sc1", "sc2", "bias_f16", "b")
+ALWAYS = {"conv_in": ("bias",), "conv_out": ("bias",)}          # operands of the new entries that are not optional there
 
 
 def abi_parameters(entry):
     """[(name, is_int)] of lavie_<entry>_f16 as include/lavie_hip.h declares it"""
     with open(HEADER) as f:
-        m = re.search(r"\bint lavie_%s_f16\(([^)]*)\)" % entry, f.read())
-    return [(p.split()[-1].lstrip("*"), p.split()[0] == "int") for p in m.group(1).replace("\n", " ").split(",")]
+        m = re.search(r"\bint lavie_%s(?:_f16|_f32)?\(([^)]*)\)" % entry, f.read())
+    return [(p.split()[-1].lstrip("*"), p.split()[0] in ("int", "long")) for p in m.group(1).replace("\n", " ").split(",")]
 
 
 class RecordingLib:
@@ -69,13 +72,13 @@ def test_call_description_is_what_run_passes(case, monkeypatch):
     case.run(ops, case.inputs, {k: torch.empty(shape, dtype=dt) for k, (shape, dt) in case.outputs.items()})
     passed = []
     for name, args in lib.recorded:
-        entry = name[len("lavie_"):-len("_f16")]
+        entry = re.sub(r"^lavie_|_f16$|_f32$", "", name) if name != "lavie_f16_to_f32" else "f16_to_f32"
         if entry not in REPLAYED:
             continue                                   # the pack steps: no launch of the GEMM family
         params = abi_parameters(entry)
         assert len(params) == len(args), (name, len(params), len(args))
         ints = {p: int(a) for (p, is_int), a in zip(params, args) if is_int}
-        ints.update({p: int(a is not None) for (p, _), a in zip(params, args) if p in OPTIONAL})
+        ints.update({p: int(a is not None) for (p, _), a in zip(params, args) if p in OPTIONAL and p not in ALWAYS.get(entry, ())})
         passed.append((entry, ints))
     assert len(passed) == len(case.calls) >= 1, (passed, case.calls)
     for (entry, ints), (want_entry, want) in zip(passed, case.calls):
@@ -319,6 +322,137 @@ def test_ppx_steady_state_tile_with_the_previous_tiles_residual():
         off = offending_tiles(case, bad, bn)
         assert set(off) == set(list(steady)[:n_defects]) and all(c > 0.9 * 160 * bn for c in off.values()), off
     assert 3e-2 < rel_l2(bad, ref) < 4e-2 and rel_l2(bad, ref) > 10 * TOL_OP
+
+
+# ------------------------------------------------------------------ injected defects of the end and glue kernels
+def offenders(case, got, k="y"):
+    """bool tensor, shaped like the output: the elements outside the case's bound"""
+    ref, scale = case.ref[k]
+    c = case.c[k] if isinstance(case.c, dict) else case.c
+    u = case.u[k] if isinstance(case.u, dict) else case.u
+    return ~((got.double() - ref).abs() <= u * ref.abs() + c * scale)
+
+
+def test_conv_out_without_the_sixth_register_slot():
+    """Cin = 320 computed as conv_out4<5> would: slots 320..359 = the whole tap (+1, +1) dropped.  Caught at every pixel that has
+    that neighbour and nowhere else.  Not a defect the whole-tensor criterion passes: a ninth of the terms is missing."""
+    case = C.conv_out_case(320, 4, (2, 3, 3, 5))
+    bad = case.model(drop_from=320)["y"]
+    with pytest.raises(AssertionError, match="conv_out"):
+        case.check({"y": bad})
+    off = offenders(case, bad).any(1)                                  # [B, F, H, W]: pixels with an offending channel
+    want = torch.zeros(2, 3, 3, 5, dtype=torch.bool)
+    want[:, :, :-1, :-1] = True
+    assert torch.equal(off, want)
+    assert rel_l2(bad, case.ref["y"][0]) > 10 * TOL_OP
+    assert not offenders(case, case.model(drop_from=360)["y"]).any()    # (nothing past slot 359: the same as the model)
+
+
+def test_gemv_clamped_row_stored_past_the_end():
+    """rows 28..31 of the last wave are clamped to row N - 1 = 30; stored unguarded, the clamped row lands at column N: for the
+    last batch entry one element past the tensor.  The values are all right (rel-L2 = 0): only the guard band sees it."""
+    case = C.gemv_case(2, 31, 320, False, False, True)
+    y = case.model()["y"]
+
+    def fn(i, o):
+        o["y"].copy_(y)
+        torch.as_strided(o["y"], (2 * 31 + 1,), (1,))[2 * 31] = y[1, 30]
+    with pytest.raises(AssertionError, match=r"y .*guard band damaged in 1 elements, first at offset 62 .*row 2, column 0"):
+        oc.run_guarded(fn, case.inputs, case.outputs, device="cpu")
+    assert rel_l2(y, case.ref["y"][0]) < TOL_OP
+
+
+def test_gemv_batch_row_reads_another_rows_vector():
+    case = C.gemv_case(3, 64, 520, True, False, True)
+    bad = case.model(row_from={1: 0})["y"]
+    with pytest.raises(AssertionError, match=r"\(row 1, column"):
+        case.check({"y": bad})
+    off = offenders(case, bad)
+    assert not off[0].any() and not off[2].any() and off[1].sum() >= 60         # row 1 and nothing else
+    assert rel_l2(bad, case.ref["y"][0]) > 100 * TOL_OP                          # a whole row of three is wrong: not a defect rel-L2 passes
+
+
+def test_sinusoid_halves_swapped_and_frequency_off_by_one():
+    case = C.sinusoid_case(8, 320)
+    t = case.inputs["t"]
+    assert t[0] == 0
+    swapped = case.model(swap=True)["y"]
+    off = offenders(case, swapped)
+    assert off[0].all()                                                          # t = 0: cos = 1 and sin = 0 everywhere
+    assert off[:, :160].any(1).all() and off[:, 160:].any(1).all() and off.float().mean() > 0.9
+    assert rel_l2(swapped, case.ref["y"][0]) > 100 * TOL_OP
+    shifted = case.model(shift=1)["y"]
+    off = offenders(case, shifted)
+    assert not off[0].any()                                                      # t = 0: the angle is 0 whatever the frequency
+    assert off[1:].any(1).all()                                                  # every other timestep, 0.001 included
+    big = (t >= 1)
+    assert off[big].float().mean() > 0.9
+    assert rel_l2(shifted, case.ref["y"][0]) > 10 * TOL_OP
+    with pytest.raises(AssertionError, match="timestep_sinusoid"):
+        case.check({"y": shifted})
+
+
+def test_ln_fold_row_sums_taken_before_the_fp16_rounding():
+    """s summed from fp32 W gamma instead of the stored fp16 weight: outside the depth-aware bound on nearly every row, inside the
+    GEMM family's (K + 8) 2^-23 on nearly every row, and far inside rel-L2."""
+    case = C.ln_fold_case(130, 320, True)
+    bad = case.model(unrounded_s=True)
+    with pytest.raises(AssertionError, match=r"ln_fold\[130x320,bias1\]:s"):
+        case.check(bad)
+    assert offenders(case, bad["s"], "s").float().mean() > 0.8
+    assert not offenders(case, bad["b"], "b").any() and torch.equal(bad["wout"], case.exact["wout"])
+    ref, scale = case.ref["s"]
+    loose = ~((bad["s"].double() - ref).abs() <= oc.U32 * ref.abs() + oc.gemm_c(320) * scale)
+    assert loose.float().mean() < 0.05                                           # the GEMM family's constant passes nearly every row
+    assert rel_l2(bad["s"], ref) < TOL_OP
+    # the exact product rounded once to fp16 (numpy converts float64 directly) is not the stored weight: what a fused multiply-convert
+    # gives, and what Wout's bit-for-bit comparison tells from fp16(fp32(W gamma)), over the (N, K) of all ln_fold cases
+    diff = total = 0
+    for n, k in C.LN_FOLD:
+        cs = C.ln_fold_case(n, k, True)
+        once = torch.from_numpy((cs.inputs["w"].double() * cs.inputs["gamma"].double()).numpy().astype("float16"))
+        diff, total = diff + int((once != cs.exact["wout"]).sum()), total + once.numel()
+    assert 0 < diff < 0.001 * total, (diff, total)
+
+
+def test_copy_rows_column_offset_off_by_one():
+    case = C.copy_rows_case(5, 7, 9, 31, 11)
+    src = case.inputs["src"]
+
+    def fn(i, o):
+        o["y"][:, 12:19] = i["src"][:, :7]
+    with pytest.raises(AssertionError, match=r"y: 5 elements outside the written region were stored to, first at offset 18 .*row 0, column 18"):
+        oc.run_guarded(fn, case.inputs, case.outputs, device="cpu", partial=case.partial)
+
+    def short(i, o):                                                             # one column too few
+        o["y"][:, 11:17] = i["src"][:, :6]
+    with pytest.raises(AssertionError, match=r"y: 5 elements never written, first at offset 17 .*row 0, column 17"):
+        oc.run_guarded(short, case.inputs, case.outputs, device="cpu", partial=case.partial)
+    got = oc.run_guarded(lambda i, o: o["y"][:, 11:18].copy_(i["src"][:, :7]), case.inputs, case.outputs, device="cpu", partial=case.partial)
+    case.check(got)
+    assert torch.equal(got["y"][:, 11:18], src[:, :7])
+
+
+def test_conv_in_channels_of_one_pair_swapped():
+    """K pair 1 = tap (-1, -1), channels 2 and 3, exchanged on the activation side: wrong at the pixels that have that neighbour"""
+    case = C.conv_in_case(4, 8, (2, 3, 3, 5))
+    bad = case.model(swap_pair=1)["y"]
+    with pytest.raises(AssertionError, match="conv_in"):
+        case.check({"y": bad})
+    off = offenders(case, bad).reshape(6, 3, 5, 8).any(-1)
+    want = torch.zeros(6, 3, 5, dtype=torch.bool)
+    want[:, 1:, 1:] = True
+    assert torch.equal(off, want)
+    assert rel_l2(bad, case.ref["y"][0]) > 10 * TOL_OP
+
+
+def test_every_listed_case_of_the_end_families_is_present():
+    """the shape lists of the issue, as counts: dropping a case changes one of them"""
+    fam = C.ends_cases()
+    assert {k: len(v) for k, v in fam.items()} == {"conv_out": 7 * 4, "conv_in": 9 * 4, "pack": 9 + 3 + 3 + 4 + 8, "ln_fold": 10, "gemv": 5 * 8 + 1,
+                                                  "timestep_sinusoid": 3, "add_class_emb_silu": 3, "fill_relpos_bias": 6}
+    assert len({c.name for cs in fam.values() for c in cs}) == sum(len(v) for v in fam.values())
+    assert {c.name for cs in fam.values() for c in cs} <= {c.name for c in CASES}
 
 
 # ------------------------------------------------------------------ bands and poison, on CPU tensors
