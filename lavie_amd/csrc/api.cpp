@@ -20,19 +20,15 @@ static inline hipStream_t S(void* s) { return (hipStream_t)s; }
 static float* g_slab = nullptr;
 static size_t g_slab_bytes = 0;
 static int op_launch(IgemmParams& p, bool gather, int epilogue, hipStream_t stream) {
-    const IgemmPlan plan = igemm_plan(p, gather, epilogue);
-    p.splits = plan.splits;
-    p.slab = nullptr;
-    if (p.splits > 1) {
-        const size_t need = (size_t)p.splits * p.M * p.N * sizeof(float);
+    return igemm_run(p, gather, epilogue, stream, [](size_t need, float** slab) {
         if (need > g_slab_bytes) {
             if (g_slab) { LAVIE_HIP(hipDeviceSynchronize()); LAVIE_HIP(hipFree(g_slab)); g_slab = nullptr; g_slab_bytes = 0; }
             LAVIE_HIP(hipMalloc((void**)&g_slab, need));
             g_slab_bytes = need;
         }
-        p.slab = g_slab;
-    }
-    return launch_igemm(p, plan, stream);
+        *slab = g_slab;
+        return 0;
+    });
 }
 static inline const half_t* H(const void* p) { return (const half_t*)p; }
 static inline half_t* H(void* p) { return (half_t*)p; }
@@ -49,10 +45,9 @@ int lavie_linear_f16(const void* A, int lda, const void* W, const float* bias, c
     LAVIE_CHECK(K % IGEMM_BK == 0, "linear: K=%d must be a multiple of %d", K, IGEMM_BK);
     LAVIE_CHECK(!bias2 || rows_per_batch > 0, "linear: bias2 needs rows_per_batch > 0");
     IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = H(A); p.lda = lda; p.W = H(W); p.ldw = K; p.C = H(C); p.ldc = ldc; p.bias = bias;
+    if (int rc = igemm_setup_linear(&p, H(A), lda, H(W), K, bias, H(C), ldc, M, N, K)) return rc;
     p.bias2 = bias2; p.ldb2 = ldb2; p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
-    p.R = H(R); p.ldr = ldr; p.M = M; p.N = N; p.nk = K / IGEMM_BK;
+    p.R = H(R); p.ldr = ldr;
     return op_launch(p, false, geglu ? EPI_GEGLU : EPI_LINEAR, S(stream));
 }
 
@@ -63,9 +58,7 @@ int lavie_linear_lnfold_f16(const void* A, const void* Wf, const float* bias, co
     LAVIE_CHECK(A && Wf && C && ln_s && ln_stats, "linear_lnfold: null tensor");
     LAVIE_CHECK(K % IGEMM_BK == 0, "linear_lnfold: K=%d must be a multiple of %d", K, IGEMM_BK);
     IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = H(A); p.lda = K; p.W = H(Wf); p.ldw = K; p.C = H(C); p.ldc = N; p.bias = bias; p.rows_per_batch = 1;
-    p.M = M; p.N = N; p.nk = K / IGEMM_BK;
+    if (int rc = igemm_setup_linear(&p, H(A), K, H(Wf), K, bias, H(C), N, M, N, K)) return rc;
     p.ln_s = ln_s; p.ln_stats = ln_stats;
     return op_launch(p, false, EPI_LINEAR, S(stream));      // (unsplit: a LayerNorm fold)
 }
@@ -78,9 +71,7 @@ int lavie_linear_lnfold_geglu_f16(const void* A, const void* Wf, const float* bi
     LAVIE_CHECK(K % IGEMM_BK == 0, "linear_lnfold_geglu: K=%d must be a multiple of %d", K, IGEMM_BK);
     LAVIE_CHECK(N > 0 && N % 128 == 0, "linear_lnfold_geglu: N=%d must be a multiple of 128", N);
     IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = H(A); p.lda = K; p.W = H(Wf); p.ldw = K; p.C = H(C); p.ldc = N / 2; p.ldr = N / 2; p.bias = bias; p.rows_per_batch = 1;
-    p.M = M; p.N = N; p.nk = K / IGEMM_BK;
+    if (int rc = igemm_setup_linear(&p, H(A), K, H(Wf), K, bias, H(C), N / 2, M, N, K)) return rc;
     p.ln_s = ln_s; p.ln_stats = ln_stats;
     return op_launch(p, false, EPI_GEGLU, S(stream));
 }
@@ -252,16 +243,8 @@ int lavie_temporal_conv_f16(const void* x, int C, const void* Wp, const float* b
     LAVIE_CHECK(B >= 1 && F >= 1 && D >= 1 && (long long)B * F * D * (C > Cout ? C : Cout) < (1ll << 31), "temporal_conv: bad shape");
     LAVIE_CHECK(!bias2 || rows_per_batch > 0, "temporal_conv: bias2 needs rows_per_batch > 0");
     IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.W = H(Wp); p.C = H(y); p.ldc = Cout; p.bias = bias; p.bias2 = bias2; p.ldb2 = ldb2;
-    p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
-    p.R = H(R); p.ldr = Cout;
-    p.tframes = F; p.tpix = D;
-    p.Hi = p.Ho = 1; p.Wi = p.Wo = 1; p.stride = 1;          // unused in temporal mode (kept valid)
-    p.M = B * F * D; p.N = Cout; p.zero = H(zero_page);
-    IgemmSeg& sg = p.seg[0];
-    sg.src = H(x); sg.C = C; sg.c0 = 0; sg.nchunks = C / IGEMM_BK; sg.ntaps = taps;
-    p.nseg = 1; p.nk = taps * sg.nchunks; p.ldw = p.nk * IGEMM_BK;
+    if (int rc = igemm_setup_temporal_conv(&p, H(x), C, H(Wp), bias, H(y), B, F, D, Cout, taps, H(zero_page))) return rc;
+    p.bias2 = bias2; p.ldb2 = ldb2; p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1; p.R = H(R);
     return op_launch(p, true, EPI_LINEAR, S(stream));
 }
 

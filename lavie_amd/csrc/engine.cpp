@@ -698,12 +698,16 @@ static size_t colstat_floats(size_t M, int C) { return (M / COLSTAT_REDUCE_ROWS 
 // split-K slab from the workspace, launch unless this is the dry run.  The dry run passes placeholder addresses and so gets the
 // plan of the real call.  *plan_out (optional) receives the plan.
 static int run_igemm(FwdCtx& c, IgemmParams& p, bool gather, int epilogue, float* cs_buf, GnColStat* cs_out, IgemmPlan* plan_out = nullptr) {
-    const IgemmPlan plan = igemm_plan(p, gather, epilogue);
-    p.splits = plan.splits;
-    p.colstat_out = nullptr;
+    const size_t mark = c.ws->mark();
+    IgemmPlan plan;
+    const int rc = igemm_run(p, gather, epilogue, c.s, [&](size_t bytes, float** slab) {
+        *slab = (float*)c.ws->alloc(bytes);
+        LAVIE_CHECK(c.dry || *slab != nullptr, "workspace exhausted (split-K slab)");
+        return 0;
+    }, cs_out && (c.route.mask & 32) ? cs_buf : nullptr, c.dry, &plan);
+    c.ws->release(mark);
     if (cs_out) *cs_out = GnColStat();
-    if (cs_buf && cs_out && (c.route.mask & 32) && plan.colstat_rows > 0) {
-        p.colstat_out = cs_buf;
+    if (p.colstat_out) {
         cs_out->partials = cs_buf;
         cs_out->C = p.N;
         cs_out->rows = plan.colstat_rows;
@@ -711,13 +715,6 @@ static int run_igemm(FwdCtx& c, IgemmParams& p, bool gather, int epilogue, float
         if (p.par_ups && p.splits == 1) { cs_out->nsets = 4; cs_out->set_blocks = p.M / 4 / plan.colstat_rows; }   // source-row blocks per output parity
         else { cs_out->nsets = 1; cs_out->set_blocks = cdiv(p.M, plan.colstat_rows); }                            // (split-K: the reduce kernel walks output rows)
     }
-    const size_t mark = c.ws->mark();
-    if (p.splits > 1) {
-        p.slab = (float*)c.ws->alloc((size_t)p.splits * p.M * p.N * sizeof(float));
-        LAVIE_CHECK(c.dry || p.slab != nullptr, "workspace exhausted (split-K slab)");
-    }
-    const int rc = c.dry ? 0 : launch_igemm(p, plan, c.s);
-    c.ws->release(mark);
     if (plan_out) *plan_out = plan;
     return rc;
 }
@@ -726,11 +723,9 @@ static int run_igemm(FwdCtx& c, IgemmParams& p, bool gather, int epilogue, float
 static int linear(FwdCtx& c, const half_t* A, int lda, const half_t* W, const float* bias, int N, int K, const half_t* R,
                   half_t* C, int ldc, int M, int epilogue = EPI_LINEAR, RowStats* rs = nullptr, const float* fold_s = nullptr,
                   int ldw = 0, float* cs_buf = nullptr, GnColStat* cs_out = nullptr) {
-    LAVIE_CHECK(K % IGEMM_BK == 0, "linear: K=%d must be a multiple of %d", K, IGEMM_BK);
     IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = lda; p.W = W; p.ldw = ldw > 0 ? ldw : K; p.C = C; p.ldc = ldc; p.bias = bias; p.R = R; p.ldr = ldc;
-    p.M = M; p.N = N; p.nk = K / IGEMM_BK;
+    RUN(igemm_setup_linear(&p, A, lda, W, ldw > 0 ? ldw : K, bias, C, ldc, M, N, K));
+    p.R = R;
     const bool emit = rs && !fold_s;
     p.rowstat_out = emit ? rs->partials : nullptr;
     if (fold_s) {
@@ -766,17 +761,8 @@ static int tconv(FwdCtx& c, const half_t* x, int C, const half_t* W, const float
                  const half_t* R, half_t* y, int D, int Cout, int taps, const half_t* zero, float* cs_buf = nullptr,
                  GnColStat* cs_out = nullptr) {
     IgemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.W = W; p.ldw = taps * C; p.C = y; p.ldc = Cout; p.bias = bias; p.bias2 = bias2; p.ldb2 = ldb2;
-    p.rows_per_batch = c.F * D; p.R = R; p.ldr = Cout;
-    p.tframes = c.F; p.tpix = D;
-    p.Hi = p.Ho = 1; p.Wi = p.Wo = 1; p.stride = 1;
-    p.M = c.B * c.F * D; p.N = Cout; p.zero = zero;
-    LAVIE_CHECK(C % IGEMM_BK == 0, "temporal conv: channel count %d must be a multiple of %d", C, IGEMM_BK);
-    IgemmSeg& sg = p.seg[0];
-    sg.src = x; sg.C = C; sg.c0 = 0; sg.nchunks = C / IGEMM_BK; sg.ntaps = taps;
-    p.nseg = 1;
-    p.nk = taps * sg.nchunks;
+    RUN(igemm_setup_temporal_conv(&p, x, C, W, bias, y, c.B, c.F, D, Cout, taps, zero));
+    p.bias2 = bias2; p.ldb2 = ldb2; p.rows_per_batch = c.F * D; p.R = R;
     return run_igemm(c, p, true, EPI_LINEAR, cs_buf, cs_out);      // (round 4) the GroupNorm behind a temporal conv folds its epilogue's sums too
 }
 

@@ -100,6 +100,21 @@ struct IgemmPlan {
 IgemmPlan igemm_plan(const IgemmParams& p, bool gather, int epilogue);
 // Launches the planned kernel (+ the split-K reduce).  Returns 0 or a negative status with lavie::set_error().
 int launch_igemm(const IgemmParams& p, const IgemmPlan& plan, hipStream_t stream);
+// One implicit GEMM from parameters to launch: plan it, set p.splits, point p.colstat_out at `cs_buf` when the planned launch writes
+// column statistics (else nullptr), take the split-K slab from `slab(bytes, &p.slab)` (called only when the plan splits; returns 0
+// or an error), launch unless `dry`.  *plan_out (optional) receives the plan.
+template <class SlabSource>
+int igemm_run(IgemmParams& p, bool gather, int epilogue, hipStream_t stream, SlabSource&& slab, float* cs_buf = nullptr, bool dry = false,
+              IgemmPlan* plan_out = nullptr) {
+    const IgemmPlan plan = igemm_plan(p, gather, epilogue);
+    if (plan_out) *plan_out = plan;
+    p.splits = plan.splits;
+    p.colstat_out = plan.colstat_rows > 0 ? cs_buf : nullptr;
+    p.slab = nullptr;
+    if (p.splits > 1)
+        if (const int rc = slab((size_t)p.splits * p.M * p.N * sizeof(float), &p.slab)) return rc;
+    return dry ? 0 : launch_igemm(p, plan, stream);
+}
 // 160x320 two-group ping-pong kernel (igemm_pp.hip); EPI_LINEAR only, N %% 320 == 0, the caller runs the split-K reduce.
 int launch_igemm_pp(const IgemmParams& p, bool gather, hipStream_t stream);
 int launch_igemm_pp_geglu(const IgemmParams& p, hipStream_t stream);   // 160x256 variant, GEGLU epilogue, N %% 256 == 0
@@ -118,6 +133,15 @@ int launch_igemm_patch(const IgemmParams& p, hipStream_t stream);
 int igemm_setup_conv3x3(IgemmParams* p, const half_t* const* src, const int* srcC, int nsrc, const half_t* const* sc, const int* scC,
                         int nsc, const half_t* W, int ldw, half_t* y, int NI, int Hi, int Wi, int Cout, int stride, int ups,
                         const half_t* zero, int pad_lo = 1);
+// Plain GEMM C [M, N] (ldc) = A [M, K] (lda) W [N, K]^T (ldw) + bias: fills p (zeroed first; rows_per_batch = 1, ldr = ldc).  ldc = N / 2
+// for the GEGLU epilogue.  The caller adds the optional operands: R (+ ldr), bias2 (+ ldb2, rows_per_batch), the LayerNorm fold
+// (ln_s, ln_stats) or rowstat_out.  0 or an error.
+int igemm_setup_linear(IgemmParams* p, const half_t* A, int lda, const half_t* W, int ldw, const float* bias, half_t* C, int ldc, int M,
+                       int N, int K);
+// (taps,1,1) temporal conv y [(b f d), Cout] over the frame axis of token rows x [(b f d), C] (IgemmParams temporal mode), W rows of
+// taps * C halfs: fills p (zeroed first; rows_per_batch = 1, ldr = Cout; the caller adds bias2, rows_per_batch, R).  0 or an error.
+int igemm_setup_temporal_conv(IgemmParams* p, const half_t* x, int C, const half_t* W, const float* bias, half_t* y, int B, int F, int D,
+                              int Cout, int taps, const half_t* zero);
 // parity form of conv3x3(nearest_x2(x)) (igemm_patch.hip MODE 3): fills p (geometry only; the caller sets p->slab), false = not this
 // geometry
 bool igemm_setup_parity_upsample(IgemmParams* p, const half_t* x, int C, const half_t* wpar, const float* bias, half_t* y, int NI, int Hi,

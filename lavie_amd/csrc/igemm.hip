@@ -25,6 +25,7 @@
 
 #include "igemm.h"
 #include "igemm_epilogue.h"
+#include "igemm_stage.h"
 #include "profile.h"
 
 namespace lavie {
@@ -41,7 +42,7 @@ struct IgemmTile {
     static constexpr int AP = (APIECES + NW - 1) / NW;                 // pieces per wave per stage; when the count
     static constexpr int WP = (WPIECES + NW - 1) / NW;                 // does not divide, the surplus slots re-load
     static constexpr int LOADS = AP + WP;                              // pieces 0.. (same bytes, same place: benign)
-    static constexpr int TAB_BYTES = BM * 9 * 4 + IGEMM_MAX_SEG * 6 * 4;  // GATHER: source-pixel table + segment table
+    static constexpr int TAB_BYTES = gather_tab_bytes(BM);             // GATHER: source-pixel table + segment table
     static_assert(LDS_BYTES <= 160 * 1024, "tile does not fit LDS");
 };
 
@@ -62,8 +63,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
         int bid = blockIdx.x;
         const int nwg = gridDim.x;
         split = blockIdx.y;
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+        bid = xcd_chunk(bid, nwg);
         igemm_tile_of(bid, (int)gridDim.x / n_tiles, n_tiles, (long)p.N * p.nk * IGEMM_BK, &tile_m, &tile_n);
     } else {
         // split-K = the weight-bound convolutions of the deep levels (M 1280, K 11520 .. 23040: 30 - 59 MB of weights for
@@ -72,9 +72,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
         // (x, y) grid is linearised as the hardware dispatches it, made XCD-contiguous, and walked M tile fastest, then N
         // tile, then K split: the workgroups that share a weight slice are neighbours inside one XCD's L2.
         const int nwg = gridDim.x * gridDim.y;
-        int lin = blockIdx.x + blockIdx.y * gridDim.x;
-        const int q = nwg >> 3, r = nwg & 7, xcd = lin & 7;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
+        const int lin = xcd_chunk(blockIdx.x + blockIdx.y * gridDim.x, nwg);
         const int m_tiles = (int)gridDim.x / n_tiles;
         tile_m = lin % m_tiles;
         const int rest = lin / m_tiles;
@@ -88,9 +86,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
     const int lr = lane >> 3;                       // row of this lane inside an 8-row piece
     const int kofs = ((lane & 7) ^ lr) * 8;         // source K offset (halfs) after the slot swizzle
 
-    // GATHER: per-block table of source pixels, tab[row * 9 + tap] = pixel index in the source grid or -1
-    // (out of image).  K order is segment > 64-channel chunk > tap: the 9 taps of one channel slab are fetched
-    // back to back, so the shifted re-reads of the same cache lines hit in L1/L2 instead of going to the fabric.
+    // GATHER: source-pixel and segment tables behind the stages (igemm_stage.h)
     int* tab = reinterpret_cast<int*>(smem + T::LDS_BYTES);
     const half_t* aptr[T::AP];
     int arow[T::AP];
@@ -102,30 +98,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
         aptr[i] = GATHER ? p.zero : p.A + (size_t)m * p.lda + kofs;
     }
     if constexpr (GATHER) {
-        const int hw = p.Ho * p.Wo;
-        const int Hv = p.Hi << p.ups, Wv = p.Wi << p.ups;
-        if (p.tframes > 0) {          // temporal taps: slot t of row m = the same pixel, t - T/2 frames away (or -1)
-            const int T_ = p.seg[0].ntaps;
-            for (int idx = tid; idx < T::BM * 9; idx += T::THREADS) {
-                const int row = idx / 9, tap = idx - row * 9;
-                int m = m0 + row;
-                m = m < p.M ? m : p.M - 1;
-                const int f = (m / p.tpix) % p.tframes;
-                const int ff = f + tap - (T_ >> 1);
-                tab[idx] = (tap < T_ && (unsigned)ff < (unsigned)p.tframes) ? m + (tap - (T_ >> 1)) * p.tpix : -1;
-            }
-        } else
-        for (int idx = tid; idx < T::BM * 9; idx += T::THREADS) {
-            const int row = idx / 9, tap = idx - row * 9;
-            int m = m0 + row;
-            m = m < p.M ? m : p.M - 1;
-            const int n = m / hw;
-            const int rem = m - n * hw;
-            const int y = rem / p.Wo, x = rem - y * p.Wo;
-            const int iy = y * p.stride + tap / 3 - p.pad_lo, ix = x * p.stride + tap % 3 - p.pad_lo;
-            const bool ok = (unsigned)iy < (unsigned)Hv && (unsigned)ix < (unsigned)Wv;
-            tab[idx] = ok ? (n * p.Hi + (iy >> p.ups)) * p.Wi + (ix >> p.ups) : -1;
-        }
+        gather_fill_pixels<T::BM, T::THREADS>(p, m0, tid, tab);
         __syncthreads();
     }
     const half_t* wptr[T::WP];
@@ -139,13 +112,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
     const int t_begin = (int)((long)p.nk * split / p.splits);
     const int t_end = (int)((long)p.nk * (split + 1) / p.splits);
 
-    // gather cursor (wave-uniform): segment, channel chunk inside it, tap — positioned at t_begin
-    // constant-index selects keep the segment descriptors in kernarg SGPRs (a runtime index into the by-value
-    // struct would make the compiler spill the whole parameter block to scratch)
-    // Segment descriptors live in LDS (written once with constant indices, read with the runtime segment index):
-    // a runtime index into the by-value kernel-parameter struct would make the compiler copy the whole parameter
-    // block to scratch, and scratch loads are vmcnt-counted VMEM — every one of them inside the K loop would
-    // drain the LDS-DMA pipeline (guide §5, trap (b)).  LDS reads only touch lgkmcnt.
+    // gather cursor (igemm_stage.h: why the segment descriptors are read from LDS), positioned at t_begin
     auto sgpr = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
     int* segtab = tab + T::BM * 9;                 // [IGEMM_MAX_SEG][6] : src lo, src hi, C, c0, nchunks, ntaps
     if constexpr (GATHER) {
@@ -163,16 +130,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void igemm_kernel(const IgemmParam
         }
         __syncthreads();
     }
-    auto load_seg = [&](int i) -> IgemmSeg {
-        IgemmSeg r;
-        const unsigned lo = (unsigned)sgpr(segtab[i * 6 + 0]), hi = (unsigned)sgpr(segtab[i * 6 + 1]);
-        r.src = reinterpret_cast<const half_t*>(((unsigned long long)hi << 32) | lo);
-        r.C = sgpr(segtab[i * 6 + 2]);
-        r.c0 = sgpr(segtab[i * 6 + 3]);
-        r.nchunks = sgpr(segtab[i * 6 + 4]);
-        r.ntaps = sgpr(segtab[i * 6 + 5]);
-        return r;
-    };
+    auto load_seg = [&](int i) { return gather_load_seg(segtab, i); };
     const half_t* const zero_page = reinterpret_cast<const half_t*>(
         ((unsigned long long)(unsigned)sgpr((int)(unsigned)(reinterpret_cast<unsigned long long>(p.zero) >> 32)) << 32) |
         (unsigned)sgpr((int)(unsigned)reinterpret_cast<unsigned long long>(p.zero)));

@@ -32,6 +32,7 @@
 
 #include "igemm.h"
 #include "igemm_epilogue.h"
+#include "igemm_stage.h"
 #include "profile.h"
 
 namespace lavie {
@@ -77,12 +78,7 @@ __global__ __launch_bounds__(pt::THREADS, 2) void igemm_patch_kernel(const Igemm
     const int wm = q, wn = grp;
 
     const int n_tiles = p.N / BN;
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x;
-        const int qq = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        bid = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + (bid >> 3);
-    }
+    const int bid = xcd_chunk(blockIdx.x, gridDim.x);
     int tile_m, tile_n;
     igemm_tile_of(bid, (int)gridDim.x / n_tiles, n_tiles, (long)p.N * p.nk * IGEMM_BK, &tile_m, &tile_n);
     const int m0 = tile_m * BM;
@@ -489,6 +485,30 @@ int igemm_setup_conv3x3(IgemmParams* p, const half_t* const* src, const int* src
         p->nk += sg.ntaps * sg.nchunks;
     }
     LAVIE_CHECK(p->nk * IGEMM_BK <= ldw, "conv3x3: weight row length %d is shorter than the gathered K %d", ldw, p->nk * IGEMM_BK);
+    return 0;
+}
+
+int igemm_setup_linear(IgemmParams* p, const half_t* A, int lda, const half_t* W, int ldw, const float* bias, half_t* C, int ldc, int M,
+                       int N, int K) {
+    memset(p, 0, sizeof(*p));
+    LAVIE_CHECK(K % IGEMM_BK == 0, "linear: K=%d must be a multiple of %d", K, IGEMM_BK);
+    p->A = A; p->lda = lda; p->W = W; p->ldw = ldw; p->C = C; p->ldc = ldc; p->bias = bias; p->rows_per_batch = 1; p->ldr = ldc;
+    p->M = M; p->N = N; p->nk = K / IGEMM_BK;
+    return 0;
+}
+
+int igemm_setup_temporal_conv(IgemmParams* p, const half_t* x, int C, const half_t* W, const float* bias, half_t* y, int B, int F, int D,
+                              int Cout, int taps, const half_t* zero) {
+    memset(p, 0, sizeof(*p));
+    LAVIE_CHECK(C % IGEMM_BK == 0, "temporal conv: channel count %d must be a multiple of %d", C, IGEMM_BK);
+    p->W = W; p->ldw = taps * C; p->C = y; p->ldc = Cout; p->bias = bias; p->rows_per_batch = 1; p->ldr = Cout;
+    p->tframes = F; p->tpix = D;
+    p->Hi = p->Ho = 1; p->Wi = p->Wo = 1; p->stride = 1;          // unused in temporal mode (kept valid)
+    p->M = B * F * D; p->N = Cout; p->zero = zero;
+    IgemmSeg& sg = p->seg[0];
+    sg.src = x; sg.C = C; sg.c0 = 0; sg.nchunks = C / IGEMM_BK; sg.ntaps = taps;
+    p->nseg = 1;
+    p->nk = taps * sg.nchunks;
     return 0;
 }
 

@@ -26,51 +26,32 @@
 
 #include "igemm.h"
 #include "igemm_epilogue.h"
+#include "igemm_stage.h"
 
 namespace lavie {
 
+// geometry, wave roles, fragment reads, MFMA block and phase barrier: namespace pp of igemm_stage.h (shared with igemm_ppx.hip)
 namespace pp {
-constexpr int MT = 5;
-constexpr int BM = 160, THREADS = 512;
-constexpr int A_BYTES = BM * 128;                       // one A stage: 20,480
-constexpr int A_STAGES = 3, W_STAGES = 2;
-constexpr int W_BASE = A_STAGES * A_BYTES;              // A stages first, then W stages
-constexpr int TAB_BYTES = BM * 9 * 4 + IGEMM_MAX_SEG * 6 * 4;
-// NT = 16-wide column tiles per wave: 5 -> 160x320 block tile (every EPI_LINEAR GEMM with N % 320 == 0),
-// 4 -> 160x256 (GEGLU: value / gate tile pairs need an even NT; N = 8 C is a multiple of 256)
-template <int NT>
-struct Geo {
-    static constexpr int BN = 4 * NT * 16;
-    static constexpr int HALF_ROWS = 2 * NT * 16;       // W rows read by one group
-    static constexpr int HALF_PIECES = HALF_ROWS / 8;   // 20 or 16: group 0 stages 16 of each half, group 1 the rest
-    static constexpr int W_BYTES = BN * 128;
-    static constexpr int LDS_BYTES = W_BASE + W_STAGES * W_BYTES;
-    static_assert(LDS_BYTES + TAB_BYTES <= 160 * 1024, "does not fit LDS");
-};
+constexpr int TAB_BYTES = gather_tab_bytes(BM);
+static_assert(Geo<5>::STAGE_BYTES + TAB_BYTES <= 160 * 1024, "does not fit LDS");
 }  // namespace pp
 
 template <bool GATHER, int EPI, int NT = 5>
 __global__ __launch_bounds__(pp::THREADS, 2) void igemm_pp_kernel(const IgemmParams p) {
     using namespace pp;
     using G = Geo<NT>;
-    constexpr int BN = G::BN, W_BYTES = G::W_BYTES, LDS_BYTES = G::LDS_BYTES, HALF_ROWS = G::HALF_ROWS;
+    constexpr int BN = G::BN, W_BYTES = G::W_BYTES, LDS_BYTES = G::STAGE_BYTES, HALF_ROWS = G::HALF_ROWS;
     constexpr bool G1_W = G::HALF_PIECES > 16;            // group 1 stages W pieces 16.. of each half (NT = 5 only)
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = wave >> 2;                    // 0: leading group, 1: trailing group (SIMD partners)
-    const int q = wave & 3;
-    const int wm = q >> 1, wn = grp * 2 + (q & 1);
+    const Roles role = roles(wave);
+    const int grp = role.grp, q = role.q, wm = role.wm, wn = role.wn;
 
     const int n_tiles = p.N / BN;
-    int bid = blockIdx.x;
-    {
-        const int nwg = gridDim.x;
-        const int qq = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        bid = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + (bid >> 3);
-    }
+    const int bid = xcd_chunk(blockIdx.x, gridDim.x);
     int tile_m, tile_n;
     igemm_tile_of(bid, (int)gridDim.x / n_tiles, n_tiles, (long)p.N * p.nk * IGEMM_BK, &tile_m, &tile_n);
     const int m0 = tile_m * BM;
@@ -84,33 +65,11 @@ __global__ __launch_bounds__(pp::THREADS, 2) void igemm_pp_kernel(const IgemmPar
 
     auto sgpr = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
 
-    // ---- GATHER tables (as igemm.hip): tab[row * 9 + tap] = source pixel or -1; segment descriptors
+    // ---- GATHER tables (igemm_stage.h): tab[row * 9 + tap] = source pixel or -1; segment descriptors
     int* tab = reinterpret_cast<int*>(smem + LDS_BYTES);
     int* segtab = tab + BM * 9;
     if constexpr (GATHER) {
-        const int hw = p.Ho * p.Wo;
-        const int Hv = p.Hi << p.ups, Wv = p.Wi << p.ups;
-        if (p.tframes > 0) {          // temporal taps (IgemmParams::tframes): slot t = the same pixel, t - T/2 frames away
-            const int T_ = p.seg[0].ntaps;
-            for (int idx = tid; idx < BM * 9; idx += THREADS) {
-                const int row = idx / 9, tap = idx - row * 9;
-                int m = m0 + row;
-                m = m < p.M ? m : p.M - 1;
-                const int ff = (m / p.tpix) % p.tframes + tap - (T_ >> 1);
-                tab[idx] = (tap < T_ && (unsigned)ff < (unsigned)p.tframes) ? m + (tap - (T_ >> 1)) * p.tpix : -1;
-            }
-        } else
-        for (int idx = tid; idx < BM * 9; idx += THREADS) {
-            const int row = idx / 9, tap = idx - row * 9;
-            int m = m0 + row;
-            m = m < p.M ? m : p.M - 1;
-            const int n = m / hw;
-            const int rem = m - n * hw;
-            const int y = rem / p.Wo, x = rem - y * p.Wo;
-            const int iy = y * p.stride + tap / 3 - p.pad_lo, ix = x * p.stride + tap % 3 - p.pad_lo;
-            const bool ok = (unsigned)iy < (unsigned)Hv && (unsigned)ix < (unsigned)Wv;
-            tab[idx] = ok ? (n * p.Hi + (iy >> p.ups)) * p.Wi + (ix >> p.ups) : -1;
-        }
+        gather_fill_pixels<BM, THREADS>(p, m0, tid, tab);
         if (tid == 0) {
 #pragma unroll
             for (int i = 0; i < IGEMM_MAX_SEG; ++i) {
@@ -125,16 +84,7 @@ __global__ __launch_bounds__(pp::THREADS, 2) void igemm_pp_kernel(const IgemmPar
         }
         __syncthreads();
     }
-    auto load_seg = [&](int i) -> IgemmSeg {
-        IgemmSeg r;
-        const unsigned lo = (unsigned)sgpr(segtab[i * 6 + 0]), hi = (unsigned)sgpr(segtab[i * 6 + 1]);
-        r.src = reinterpret_cast<const half_t*>(((unsigned long long)hi << 32) | lo);
-        r.C = sgpr(segtab[i * 6 + 2]);
-        r.c0 = sgpr(segtab[i * 6 + 3]);
-        r.nchunks = sgpr(segtab[i * 6 + 4]);
-        r.ntaps = sgpr(segtab[i * 6 + 5]);
-        return r;
-    };
+    auto load_seg = [&](int i) { return gather_load_seg(segtab, i); };
     const half_t* const zero_page = reinterpret_cast<const half_t*>(
         ((unsigned long long)(unsigned)sgpr((int)(unsigned)(reinterpret_cast<unsigned long long>(p.zero) >> 32)) << 32) |
         (unsigned)sgpr((int)(unsigned)reinterpret_cast<unsigned long long>(p.zero)));
@@ -243,28 +193,10 @@ __global__ __launch_bounds__(pp::THREADS, 2) void igemm_pp_kernel(const IgemmPar
     const int w_frag = W_BASE + (wn * (NT * 16) + frow) * 128;
     half8_t af[MT], wf[NT];
 
-    auto read_frags = [&](int ast, int wst, int ks) {
-        const char* abase = smem + ast * A_BYTES + a_frag;
-        const char* wbase = smem + wst * W_BYTES + w_frag;
-        const int slot = ((ks * 4 + fg) ^ fsw) * 16;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) af[mt] = *reinterpret_cast<const half8_t*>(abase + mt * 16 * 128 + slot);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) wf[nt] = *reinterpret_cast<const half8_t*>(wbase + nt * 16 * 128 + slot);
-    };
-    auto mfma_block = [&]() {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-                acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt], af[mt], acc[nt][mt], 0, 0, 0);
-    };
-    // phase boundary: nothing is scheduled across it
-    auto bar = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    const FragOfs fo{a_frag, w_frag, fsw, fg};
+    auto read_frags = [&](int ast, int wst, int ks) { pp::read_frags<NT>(smem, fo, ast, wst, ks, af, wf); };
+    auto mfma_block = [&]() { pp::mfma_block<NT>(af, wf, acc); };
+    auto bar = [&]() { phase_barrier(); };
     // counted wait: all but this wave's `N` youngest LDS-DMA pieces have landed (0 when nothing newer was issued)
     auto wait_dma = [&](bool issued, auto n_tag) {
         constexpr int N = decltype(n_tag)::value;
@@ -342,7 +274,7 @@ template <bool GATHER, int EPI = EPI_LINEAR, int NT = 5>
 static int launch_pp_t(const IgemmParams& p, hipStream_t stream) {
     using namespace pp;
     constexpr int BN = Geo<NT>::BN;
-    constexpr int lds = Geo<NT>::LDS_BYTES + (GATHER ? TAB_BYTES : 0);
+    constexpr int lds = Geo<NT>::STAGE_BYTES + (GATHER ? TAB_BYTES : 0);
     auto kern = igemm_pp_kernel<GATHER, EPI, NT>;
     static bool attr_set = false;
     if (!attr_set) {

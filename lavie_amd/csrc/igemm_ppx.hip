@@ -36,6 +36,7 @@
 
 #include "igemm.h"
 #include "igemm_epilogue.h"
+#include "igemm_stage.h"
 
 namespace lavie {
 
@@ -47,19 +48,11 @@ namespace lavie {
 // the workgroups' starts by a quarter tile period: measured and rejected)
 
 namespace ppx {
-constexpr int MT = 5;
-constexpr int BM = 160, THREADS = 512;
-constexpr int A_BYTES = BM * 128;                       // one A stage: 20,480
-constexpr int A_STAGES = 3, W_STAGES = 2;
-constexpr int W_BASE = A_STAGES * A_BYTES;
+using namespace pp;                                     // tile geometry, wave roles, fragment reads, MFMA block, phase barrier (igemm_stage.h)
 constexpr int AUX_BYTES = 7 * 1024;                     // bias 2 KiB | ln_s 2 KiB | (mean, rstd) rows 2 KiB | scratch 1 KiB
 template <int NT>
-struct Geo {
-    static constexpr int BN = 4 * NT * 16;
-    static constexpr int HALF_ROWS = 2 * NT * 16;       // W rows read by one group
-    static constexpr int HALF_PIECES = HALF_ROWS / 8;   // 20 or 16: group 0 stages 16 of each half, group 1 the rest
-    static constexpr int W_BYTES = BN * 128;
-    static constexpr int AUX_BASE = W_BASE + W_STAGES * W_BYTES;
+struct GeoX : Geo<NT> {                                 // the ping-pong stages, then two aux areas
+    static constexpr int AUX_BASE = Geo<NT>::STAGE_BYTES;
     static constexpr int LDS_BYTES = AUX_BASE + 2 * AUX_BYTES;
     static_assert(LDS_BYTES <= 160 * 1024, "does not fit LDS");
 };
@@ -131,7 +124,7 @@ __device__ __forceinline__ void vmwait(int n) {
 template <int EPI, int NT, int MODE>
 __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmParams p, const int tiles_total) {
     using namespace ppx;
-    using G = Geo<NT>;
+    using G = GeoX<NT>;
     constexpr int BN = G::BN, W_BYTES = G::W_BYTES, HALF_ROWS = G::HALF_ROWS, AUX_BASE = G::AUX_BASE;
     constexpr bool G1_W = G::HALF_PIECES > 16;            // group 1 stages W pieces 16.. of each half (NT = 5 only)
     constexpr bool LIN = EPI == EPI_LINEAR;
@@ -149,9 +142,8 @@ __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmP
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = wave >> 2;                    // 0: leading group, 1: trailing group (SIMD partners)
-    const int q = wave & 3;
-    const int wm = q >> 1, wn = grp * 2 + (q & 1);
+    const Roles role = roles(wave);
+    const int grp = role.grp, q = role.q, wm = role.wm, wn = role.wn;
     auto sgpr = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
 
     constexpr bool has_fold = MODE == 2, has_res = LIN && MODE == 1;
@@ -165,17 +157,14 @@ __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmP
     {
         const int nwg = gridDim.x, b = blockIdx.x;
         const int xcd = b & 7;
-        if (tiles_total <= nwg) {                 // one tile each: the bijective XCD chunking of igemm_pp.hip
-            const int qq = nwg >> 3, r = nwg & 7;
-            first = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + (b >> 3);
+        if (tiles_total <= nwg) {                 // one tile each: xcd_chunk over the workgroups (igemm_stage.h)
+            first = xcd_chunk(b, nwg);
             stride = 1;
             count = 1;
         } else {                                  // nwg is a multiple of 8 here (launcher)
             const int per = nwg >> 3, j = b >> 3;
-            const int qq = tiles_total >> 3, r = tiles_total & 7;
-            const int start = xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq;
-            const int size = qq + (xcd < r ? 1 : 0);
-            first = start + j;
+            const int size = (tiles_total >> 3) + (xcd < (tiles_total & 7) ? 1 : 0);      // of this XCD's chunk of the tile ids
+            first = xcd_chunk(b, tiles_total);                                             // = the chunk's start + j
             stride = per;
             count = j < size ? (size - j + per - 1) / per : 0;
         }
@@ -271,27 +260,10 @@ __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmP
     const int w_frag = W_BASE + (wn * (NT * 16) + frow) * 128;
     half8_t af[MT], wf[NT];
 
-    auto read_frags = [&](int ast, int wst, int ks) {
-        const char* abase = smem + ast * A_BYTES + a_frag;
-        const char* wbase = smem + wst * W_BYTES + w_frag;
-        const int slot = ((ks * 4 + fg) ^ fsw) * 16;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) af[mt] = *reinterpret_cast<const half8_t*>(abase + mt * 16 * 128 + slot);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) wf[nt] = *reinterpret_cast<const half8_t*>(wbase + nt * 16 * 128 + slot);
-    };
-    auto mfma_block = [&]() {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-                acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nt], af[mt], acc[nt][mt], 0, 0, 0);
-    };
-    auto bar = [&]() {                              // phase boundary: nothing is scheduled across it
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    const FragOfs fo{a_frag, w_frag, fsw, fg};
+    auto read_frags = [&](int ast, int wst, int ks) { pp::read_frags<NT>(smem, fo, ast, wst, ks, af, wf); };
+    auto mfma_block = [&]() { pp::mfma_block<NT>(af, wf, acc); };
+    auto bar = [&]() { phase_barrier(); };
 
     // ---- residual prefetch: the wave tile's rows of R, one 8-byte load per (mt, nt), issued at the start of the tile's
     // last K-tile.  Lane address = R + ((m0 + wave row) * ldr + n0 + wave column) * 2 bytes; nt * 32 bytes as immediates.
@@ -659,8 +631,8 @@ __global__ __launch_bounds__(ppx::THREADS, 2) void igemm_ppx_kernel(const IgemmP
 template <int EPI, int NT, int MODE>
 static int launch_ppx_t(const IgemmParams& p, hipStream_t stream) {
     using namespace ppx;
-    constexpr int BN = Geo<NT>::BN;
-    constexpr int lds = Geo<NT>::LDS_BYTES;
+    constexpr int BN = GeoX<NT>::BN;
+    constexpr int lds = GeoX<NT>::LDS_BYTES;
     auto kern = igemm_ppx_kernel<EPI, NT, MODE>;
     static bool attr_set = false;
     if (!attr_set) {
