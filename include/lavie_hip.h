@@ -343,6 +343,54 @@ int lavie_cfg_multistep_step(const void* eps2, float* x, float* x0_prev, void* m
 int lavie_multistep_step(const void* eps, float* x, float* x0_prev, void* model_in, long long n, float k_x, float k_eps,
                          float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream);
 
+/* Sampling around known latents (additive in ABI 8): the four steps above with the known-region replacement of the legacy
+ * inpaint / img2img loop inside the step kernel, still one launch per denoising step.  The caller pins part of the latents
+ * [P, channels, inner] (inner = frames * height * width) with a mask; after the step the pinned part holds the known clean
+ * latents at the noise level (a_next, s_next) of the timestep the step lands on, the rest keeps the step's own result.
+ * Per element, fp32, contraction off, every fused multiply-add spelled out in the source:
+ *   xm = the x' of the plain entry point of the same name, with that kernel's rounding points
+ *   xk = s_next != 0 ? fma(s_next, noise_known, a_next known) : a_next known
+ *   m  = mask[(i / (channels inner)) inner + i % inner]
+ *   x' = m == 0 ? xm : m == 1 ? xk : fma(m, xk - xm, xm);   x <- x'
+ *   model_in <- fp16(x' next_input_scale), rounded as the plain entry point rounds it (five-coefficient family: the exact
+ *               product rounded once; multistep family: fp16 of the fp32 product), one value for both guidance halves
+ *   multistep family: x0_prev <- m == 0 ? x0 : m == 1 ? known : fma(m, known - x0, x0); never read when c_prev == 0
+ * So m == 0 everywhere gives the plain entry point's bits whatever known / noise_known hold, and m == 1 gives xk whatever
+ * the model predicted: with a_next = 1, s_next = 0 (after the last step) that is `known` itself.  0 < m < 1 is a linear blend.
+ * known / mask / noise_known are read-only and must not overlap x, x0_prev or model_in; the other aliasing rules are those
+ * of the plain entry points.  No atomics, no host synchronisation, no allocation: bit-reproducible and safe in a capture.
+ * Checked on the host before any HIP call, a refused call launches nothing and names the argument: region != NULL and its
+ * struct_size; non-null eps / x / x0_prev / model_in / known / mask; noise_known != NULL unless s_next == 0; noise != NULL
+ * unless sigma == 0; channels, inner >= 1 and n == P channels inner for a whole P >= 1; finite scalars; with inner % 8 == 0
+ * (eight elements per lane, 16-byte accesses; otherwise one element per lane) every tensor read or written 16-byte aligned. */
+typedef struct lavie_known_region {
+    int struct_size;              /* sizeof this struct as the CALLER declared it; any other value is refused */
+    int channels;                 /* C of the latents: the mask is broadcast over it */
+    long long inner;              /* frames * height * width */
+    const float* known;           /* [P, channels, inner] fp32, device */
+    const float* mask;            /* [P, 1, inner] fp32 in [0, 1], device; NULL (= 1 everywhere) only for lavie_known_blend_f32 */
+    const float* noise_known;     /* [P, channels, inner] fp32, device; may be NULL iff s_next == 0 */
+    float a_next, s_next;         /* noise level the step lands on: x_t = a known + s noise */
+} lavie_known_region;
+int lavie_cfg_sampler_step_known(const void* eps2, float* x, const float* noise, void* model_in2, long long n, float guidance,
+                                 float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale, void* stream,
+                                 const lavie_known_region* region);
+int lavie_sampler_step_known(const void* eps, float* x, const float* noise, void* model_in, long long n, float k_x, float k_eps,
+                             float c_x0, float c_xt, float sigma, float next_input_scale, void* stream,
+                             const lavie_known_region* region);
+int lavie_cfg_multistep_step_known(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, float guidance,
+                                   float k_x, float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale,
+                                   void* stream, const lavie_known_region* region);
+int lavie_multistep_step_known(const void* eps, float* x, float* x0_prev, void* model_in, long long n, float k_x, float k_eps,
+                               float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream,
+                               const lavie_known_region* region);
+/* The start of such a run, no eps operand: x <- m == 0 ? x : m == 1 ? xk : fma(m, xk - x, x) with xk as above at the noise
+ * level of the FIRST timestep, and model_in <- fp16(x' input_scale) rounded once, as lavie_latents_to_scaled_model_input
+ * does: n values, or [x' | x'] (2 n) with dup != 0.  With a mask it prepares x_T of a pinned run; with region->mask == NULL
+ * (m = 1 everywhere) it is the scheduler's add_noise and starts a run at reduced strength.  Same checks as above. */
+int lavie_known_blend_f32(float* x, void* model_in, int dup, long long n, float input_scale, void* stream,
+                          const lavie_known_region* region);
+
 /* ------------------------------------------------------------------------------------------------
  * Measurement hook: HIP-event timing per kernel class on the launch stream (bench.py's roofline leg).
  * Classes: 0 conv3x3 (implicit GEMM, gathered), 1 linear/1x1/GEGLU GEMM, 2 spatial+text attention core,

@@ -33,6 +33,11 @@ class LoraTermC(C.Structure):         # lavie_lora_term
     _fields_ = [("A", c_float_p), ("B", c_float_p), ("r", c_int), ("scale", c_float)]
 
 
+class KnownRegionC(C.Structure):      # lavie_known_region
+    _fields_ = [("struct_size", c_int), ("channels", c_int), ("inner", c_ll), ("known", c_float_p), ("mask", c_float_p),
+                ("noise_known", c_float_p), ("a_next", c_float), ("s_next", c_float)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/lavie_hip.h
 SIGNATURES = {
     "lavie_last_error": (c_char_p, []),
@@ -122,6 +127,15 @@ SIGNATURES = {
                                           c_float, c_float, c_float, c_void_p]),
     "lavie_multistep_step": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float,
                                       c_float, c_void_p]),
+    "lavie_cfg_sampler_step_known": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float,
+                                              c_float, c_float, c_float, c_void_p, C.POINTER(KnownRegionC)]),
+    "lavie_sampler_step_known": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float,
+                                          c_float, c_void_p, C.POINTER(KnownRegionC)]),
+    "lavie_cfg_multistep_step_known": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float,
+                                                c_float, c_float, c_float, c_void_p, C.POINTER(KnownRegionC)]),
+    "lavie_multistep_step_known": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float,
+                                            c_float, c_float, c_void_p, C.POINTER(KnownRegionC)]),
+    "lavie_known_blend_f32": (c_int, [c_float_p, c_void_p, c_int, c_ll, c_float, c_void_p, C.POINTER(KnownRegionC)]),
     "lavie_debug_force_tile": (c_int, [c_int]),
     "lavie_debug_force_splits": (c_int, [c_int]),
     "lavie_debug_fused_mask": (c_int, [c_int]),

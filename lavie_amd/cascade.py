@@ -91,3 +91,43 @@ def _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, p
                            guidance_scale=vsr_guidance_scale, noise_level=noise_level, generator=generator)
     frames = decode_frames(vsr_vae, up, None, chunk=1) if decode_final else None
     return base, interp, up, frames
+
+
+# ------------------------------------------------------------------ clips longer than one base call: continuation by pinned overlap
+@torch.no_grad()
+def continue_clip(pipe, prev_latents: torch.Tensor, overlap: int = 4, **call_kwargs) -> torch.Tensor:
+    """One more clip after `prev_latents` [P, C, F, h, w]: a base call whose first `overlap` frames are pinned to the last `overlap`
+    frames of `prev_latents` (VideoGenPipeline's `known_latents` / `known_mask`), so they come back bit-equal and temporal attention
+    carries them into the free frames.  `call_kwargs` go to the pipeline (prompt or prompt_embeds, steps, generator, ...);
+    `video_length` defaults to 16, height / width to those of `prev_latents`.  Returns the new clip's latents, overlap included."""
+    p, c, f_prev, h, w = prev_latents.shape
+    length = int(call_kwargs.pop("video_length", 16))
+    if not 1 <= overlap < length or overlap > f_prev:
+        raise ValueError(f"overlap={overlap} must lie in 1..{min(length - 1, f_prev)} (new clip {length} frames, previous {f_prev})")
+    known = torch.zeros(p, c, length, h, w, dtype=torch.float32, device=prev_latents.device)
+    known[:, :, :overlap] = prev_latents[:, :, f_prev - overlap:]
+    mask = torch.zeros(p, 1, length, h, w, dtype=torch.float32, device=prev_latents.device)
+    mask[:, :, :overlap] = 1.0
+    scale = getattr(pipe, "vae_scale_factor", 8)
+    call_kwargs.setdefault("height", h * scale)
+    call_kwargs.setdefault("width", w * scale)
+    call_kwargs["output_type"] = "latent"
+    return pipe(video_length=length, known_latents=known, known_mask=mask, **call_kwargs).video
+
+
+@torch.no_grad()
+def text_to_long_video(pipe, prompt, num_clips: int, overlap: int = 4, **call_kwargs) -> torch.Tensor:
+    """`num_clips` base clips chained by `continue_clip`: latents [P, C, L + (num_clips - 1)(L - overlap), h, w] with L =
+    `video_length` (16), the overlap frames stored once.  `prompt` may be None when `call_kwargs` carry prompt_embeds."""
+    if num_clips < 1:
+        raise ValueError(f"num_clips={num_clips} must be >= 1")
+    length = int(call_kwargs.pop("video_length", 16))
+    if prompt is not None:
+        call_kwargs["prompt"] = prompt
+    call_kwargs["output_type"] = "latent"
+    clip = pipe(video_length=length, **call_kwargs).video
+    parts = [clip]
+    for _ in range(num_clips - 1):
+        clip = continue_clip(pipe, clip, overlap, video_length=length, **call_kwargs)
+        parts.append(clip[:, :, overlap:])
+    return torch.cat(parts, dim=2)

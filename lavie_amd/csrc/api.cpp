@@ -452,6 +452,98 @@ int lavie_multistep_step(const void* eps, float* x, float* x0_prev, void* model_
     return launch_multistep_step(H(eps), x, x0_prev, H(model_in), n, k_x, k_eps, c_x0, c_xt, c_prev, next_input_scale, S(stream));
 }
 
+// Host-side argument check of the five known-region entries (sampler_known.hip), before any HIP call.  `tensors`: what the
+// kernel reads or writes besides the region's own operands (nullptr entries = operands this call does not use).
+static int known_args(const char* who, const lavie_known_region* r, bool mask_optional, long long n, const float* scalars,
+                      int nscalars, const void* const* tensors, const char* const* names, int ntensors) {
+    LAVIE_CHECK(r, "%s: region is null", who);
+    LAVIE_CHECK(r->struct_size == (int)sizeof(lavie_known_region),
+                "%s: region->struct_size=%d but this library's lavie_known_region has %d bytes: the binding's struct layout is "
+                "out of date", who, r->struct_size, (int)sizeof(lavie_known_region));
+    for (int i = 0; i < ntensors; ++i) LAVIE_CHECK(tensors[i], "%s: %s is null", who, names[i]);
+    LAVIE_CHECK(r->known, "%s: region->known is null", who);
+    LAVIE_CHECK(r->mask || mask_optional, "%s: region->mask is null", who);
+    for (int i = 0; i < nscalars; ++i)
+        LAVIE_CHECK(__builtin_isfinite(scalars[i]), "%s: scalar argument %d (%g) is not finite", who, i, (double)scalars[i]);
+    LAVIE_CHECK(__builtin_isfinite(r->a_next) && __builtin_isfinite(r->s_next), "%s: region->a_next=%g / s_next=%g is not finite", who,
+                (double)r->a_next, (double)r->s_next);
+    LAVIE_CHECK(r->s_next == 0.f || r->noise_known, "%s: region->noise_known is null but s_next=%g", who, (double)r->s_next);
+    LAVIE_CHECK(r->channels >= 1 && r->inner >= 1, "%s: region->channels=%d inner=%lld must be >= 1", who, r->channels, r->inner);
+    const long long plane = r->inner <= (1ll << 40) ? (long long)r->channels * r->inner : 0;
+    LAVIE_CHECK(n >= 1 && plane > 0 && n % plane == 0, "%s: n=%lld is not a whole number of videos of channels=%d x inner=%lld", who, n,
+                r->channels, r->inner);
+    if (r->inner % 8 == 0) {                 // the eight-elements-per-lane form
+        for (int i = 0; i < ntensors; ++i)
+            LAVIE_CHECK(((uintptr_t)tensors[i] & 15) == 0, "%s: %s at %p is not 16-byte aligned", who, names[i], tensors[i]);
+        const void* own[3] = {r->known, r->mask, r->s_next != 0.f ? r->noise_known : nullptr};
+        const char* own_names[3] = {"region->known", "region->mask", "region->noise_known"};
+        for (int i = 0; i < 3; ++i)
+            LAVIE_CHECK(((uintptr_t)own[i] & 15) == 0, "%s: %s at %p is not 16-byte aligned", who, own_names[i], own[i]);
+    }
+    return 0;
+}
+
+static int sampler_step_known(const char* who, bool cfg, const void* eps, float* x, const float* noise, void* model_in, long long n,
+                              float guidance, float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale,
+                              void* stream, const lavie_known_region* r) {
+    const float s[7] = {guidance, k_x, k_eps, c_x0, c_xt, sigma, next_input_scale};
+    LAVIE_CHECK(sigma == 0.f || noise, "%s: noise is null but sigma=%g", who, (double)sigma);
+    const void* t[4] = {eps, x, model_in, noise};
+    const char* names[4] = {"eps", "x", "model_in", "noise"};
+    if (int rc = known_args(who, r, false, n, s, 7, t, names, sigma != 0.f ? 4 : 3)) return rc;     // sigma == 0: noise is not read
+    return launch_sampler_step_known(cfg, H(eps), x, noise, H(model_in), n, guidance, k_x, k_eps, c_x0, c_xt, sigma, next_input_scale,
+                                     r->known, r->mask, r->noise_known, r->channels, r->inner, r->a_next, r->s_next, S(stream));
+}
+
+int lavie_cfg_sampler_step_known(const void* eps2, float* x, const float* noise, void* model_in2, long long n, float guidance,
+                                 float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale, void* stream,
+                                 const lavie_known_region* region) {
+    return sampler_step_known("cfg_sampler_step_known", true, eps2, x, noise, model_in2, n, guidance, k_x, k_eps, c_x0, c_xt, sigma,
+                              next_input_scale, stream, region);
+}
+
+int lavie_sampler_step_known(const void* eps, float* x, const float* noise, void* model_in, long long n, float k_x, float k_eps,
+                             float c_x0, float c_xt, float sigma, float next_input_scale, void* stream,
+                             const lavie_known_region* region) {
+    return sampler_step_known("sampler_step_known", false, eps, x, noise, model_in, n, 1.0f, k_x, k_eps, c_x0, c_xt, sigma,
+                              next_input_scale, stream, region);
+}
+
+static int multistep_step_known(const char* who, bool cfg, const void* eps, float* x, float* x0_prev, void* model_in, long long n,
+                                float guidance, float k_x, float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale,
+                                void* stream, const lavie_known_region* r) {
+    const float s[7] = {guidance, k_x, k_eps, c_x0, c_xt, c_prev, next_input_scale};
+    const void* t[4] = {eps, x, x0_prev, model_in};
+    const char* names[4] = {"eps", "x", "x0_prev", "model_in"};
+    if (int rc = known_args(who, r, false, n, s, 7, t, names, 4)) return rc;
+    return launch_multistep_step_known(cfg, H(eps), x, x0_prev, H(model_in), n, guidance, k_x, k_eps, c_x0, c_xt, c_prev,
+                                       next_input_scale, r->known, r->mask, r->noise_known, r->channels, r->inner, r->a_next,
+                                       r->s_next, S(stream));
+}
+
+int lavie_cfg_multistep_step_known(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, float guidance,
+                                   float k_x, float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale,
+                                   void* stream, const lavie_known_region* region) {
+    return multistep_step_known("cfg_multistep_step_known", true, eps2, x, x0_prev, model_in2, n, guidance, k_x, k_eps, c_x0, c_xt,
+                                c_prev, next_input_scale, stream, region);
+}
+
+int lavie_multistep_step_known(const void* eps, float* x, float* x0_prev, void* model_in, long long n, float k_x, float k_eps,
+                               float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream,
+                               const lavie_known_region* region) {
+    return multistep_step_known("multistep_step_known", false, eps, x, x0_prev, model_in, n, 1.0f, k_x, k_eps, c_x0, c_xt, c_prev,
+                                next_input_scale, stream, region);
+}
+
+int lavie_known_blend_f32(float* x, void* model_in, int dup, long long n, float input_scale, void* stream,
+                          const lavie_known_region* region) {
+    const void* t[2] = {x, model_in};
+    const char* names[2] = {"x", "model_in"};
+    if (int rc = known_args("known_blend", region, true, n, &input_scale, 1, t, names, 2)) return rc;
+    return launch_known_blend(x, H(model_in), dup != 0, n, input_scale, region->known, region->mask, region->noise_known,
+                              region->channels, region->inner, region->a_next, region->s_next, S(stream));
+}
+
 int lavie_latents_to_scaled_model_input1(const float* x, void* model_in, long long n, float input_scale, void* stream) {
     LAVIE_CHECK(x && model_in && n > 0, "latents_to_scaled_model_input1: bad arguments");
     return launch_f32_to_f16_scaled(x, H(model_in), n, input_scale, S(stream));

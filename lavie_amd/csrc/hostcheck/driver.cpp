@@ -665,6 +665,66 @@ int main(int argc, char** argv) {
         REQUIRE(lavie_multistep_step(eps, x, hist, min2, 32, 1.f, -inf, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
         REQUIRE(lavie_hostcheck_launches() == before + 3);
     }
+    {   // the steps around known latents: accepted calls reach the (stubbed) launch in the eight-element form (inner % 8 == 0) and the
+        // one-element form; every refusal comes before a HIP call and names the argument
+        alignas(16) static unsigned short eps[2 * 48], min2[2 * 48];
+        alignas(16) static float x[48], hist[48], nz[48], known[48], noise[48], mask[24];
+        const float nan = __builtin_nanf(""), inf = __builtin_inff();
+        lavie_known_region r{};
+        r.struct_size = (int)sizeof(r);
+        r.channels = 3; r.inner = 8;                        // P = 2: n = 48
+        r.known = known; r.mask = mask; r.noise_known = noise; r.a_next = 0.8f; r.s_next = 0.6f;
+        auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+        const long before = lavie_hostcheck_launches();
+        REQUIRE(lavie_cfg_sampler_step_known(eps, x, nz, min2, 48, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 1.f, nullptr, &r) == 0);
+        REQUIRE(lavie_sampler_step_known(eps, x, nullptr, min2, 48, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 0.9f, nullptr, &r) == 0);
+        REQUIRE(lavie_cfg_multistep_step_known(eps, x, hist, min2, 48, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 1.f, nullptr, &r) == 0);
+        REQUIRE(lavie_multistep_step_known(eps, x, hist, min2, 48, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 1.f, nullptr, &r) == 0);
+        REQUIRE(lavie_known_blend_f32(x, min2, 1, 48, 0.9f, nullptr, &r) == 0);
+        lavie_known_region q = r;                           // the end of a run, the add_noise form, the one-element form off alignment
+        q.a_next = 1.f; q.s_next = 0.f; q.noise_known = nullptr;
+        REQUIRE(lavie_cfg_multistep_step_known(eps, x, hist, min2, 48, 7.5f, 1.f, 0.5f, 1.f, 0.f, 0.f, 1.f, nullptr, &q) == 0);
+        q = r; q.mask = nullptr;
+        REQUIRE(lavie_known_blend_f32(x, min2, 0, 48, 1.f, nullptr, &q) == 0);
+        q = r; q.inner = 7; q.known = known + 1; q.mask = mask + 1; q.noise_known = noise + 3;
+        REQUIRE(lavie_sampler_step_known(eps + 1, x + 1, nz + 1, min2 + 1, 42, 1.f, 0.5f, 0.3f, 0.7f, 0.2f, 1.f, nullptr, &q) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 8);
+        REQUIRE(refused(lavie_cfg_sampler_step_known(eps, x, nz, min2, 48, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 1.f, nullptr, nullptr), "region"));
+        q = r; q.struct_size -= 4;
+        REQUIRE(refused(lavie_known_blend_f32(x, min2, 1, 48, 1.f, nullptr, &q), "struct_size"));
+        REQUIRE(refused(lavie_cfg_sampler_step_known(nullptr, x, nz, min2, 48, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 1.f, nullptr, &r), "eps"));
+        REQUIRE(refused(lavie_sampler_step_known(eps, nullptr, nz, min2, 48, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 1.f, nullptr, &r), "x is null"));
+        REQUIRE(refused(lavie_sampler_step_known(eps, x, nullptr, min2, 48, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 1.f, nullptr, &r), "noise"));
+        REQUIRE(refused(lavie_multistep_step_known(eps, x, nullptr, min2, 48, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 1.f, nullptr, &r), "x0_prev"));
+        REQUIRE(refused(lavie_multistep_step_known(eps, x, hist, nullptr, 48, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 1.f, nullptr, &r), "model_in"));
+        q = r; q.known = nullptr;
+        REQUIRE(refused(lavie_known_blend_f32(x, min2, 1, 48, 1.f, nullptr, &q), "known"));
+        q = r; q.mask = nullptr;                            // only the blend takes "no mask"
+        REQUIRE(refused(lavie_multistep_step_known(eps, x, hist, min2, 48, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 1.f, nullptr, &q), "mask"));
+        q = r; q.noise_known = nullptr;
+        REQUIRE(refused(lavie_known_blend_f32(x, min2, 1, 48, 1.f, nullptr, &q), "noise_known"));
+        REQUIRE(refused(lavie_known_blend_f32(x, min2, 1, 40, 1.f, nullptr, &r), "n=40"));
+        REQUIRE(refused(lavie_known_blend_f32(x, min2, 1, 0, 1.f, nullptr, &r), "n=0"));
+        q = r; q.channels = 0;
+        REQUIRE(refused(lavie_known_blend_f32(x, min2, 1, 48, 1.f, nullptr, &q), "channels"));
+        q = r; q.inner = -8;
+        REQUIRE(refused(lavie_known_blend_f32(x, min2, 1, 48, 1.f, nullptr, &q), "inner"));
+        q = r; q.a_next = nan;
+        REQUIRE(refused(lavie_known_blend_f32(x, min2, 1, 48, 1.f, nullptr, &q), "a_next"));
+        q = r; q.s_next = inf;
+        REQUIRE(refused(lavie_cfg_multistep_step_known(eps, x, hist, min2, 48, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 1.f, nullptr, &q), "s_next"));
+        REQUIRE(refused(lavie_cfg_multistep_step_known(eps, x, hist, min2, 48, nan, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 1.f, nullptr, &r), "finite"));
+        REQUIRE(refused(lavie_cfg_sampler_step_known(eps, x, nz, min2, 48, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, inf, nullptr, &r), "finite"));
+        REQUIRE(refused(lavie_known_blend_f32(x, min2, 1, 48, nan, nullptr, &r), "finite"));
+        REQUIRE(refused(lavie_cfg_sampler_step_known(eps + 1, x, nz, min2, 48, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 1.f, nullptr, &r), "eps at"));
+        REQUIRE(refused(lavie_cfg_sampler_step_known(eps, x, nz + 1, min2, 48, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 1.f, nullptr, &r), "noise at"));
+        REQUIRE(refused(lavie_multistep_step_known(eps, x, hist + 2, min2, 48, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 1.f, nullptr, &r), "x0_prev at"));
+        q = r; q.mask = mask + 1;
+        REQUIRE(refused(lavie_known_blend_f32(x, min2, 1, 48, 1.f, nullptr, &q), "region->mask at"));
+        q = r; q.noise_known = noise + 2;
+        REQUIRE(refused(lavie_known_blend_f32(x, min2, 1, 48, 1.f, nullptr, &q), "region->noise_known at"));
+        REQUIRE(lavie_hostcheck_launches() == before + 8);
+    }
     {   // the VAE's edge convolutions and the asymmetric-pad stride-2 conv: accepted calls reach the (stubbed) launch with exactly
         // sized buffers (packing, odd Cin, ragged last tile); every refusal comes before a HIP call and names its argument
         const int N = 2, Hh = 5, Ww = 7, px = N * Hh * Ww;

@@ -106,6 +106,20 @@ int launch_cfg_multistep_step(const half_t* eps2, float* x, float* x0_prev, half
                               float kx, float ke, float c0, float ct, float cp, float in_scale, hipStream_t stream);
 int launch_multistep_step(const half_t* eps, float* x, float* x0_prev, half_t* model_in, int64_t n, float kx, float ke,
                           float c0, float ct, float cp, float in_scale, hipStream_t stream);
+// ---- sampler_known.hip : the steps above around known latents (known-region replacement inside the step kernel)
+//   x' = select(mask, plain step's x', a_next known + s_next noise_known); cfg picks the guided variant; n = P * channels * inner;
+//   with inner % 8 == 0 every tensor must be 16-byte aligned (checked by the C entry points).
+int launch_sampler_step_known(bool cfg, const half_t* eps2, float* x, const float* noise, half_t* model_in2, int64_t n,
+                              float guidance, float kx, float ke, float c0, float ct, float sigma, float in_scale,
+                              const float* known, const float* mask, const float* noise_known, int channels, int64_t inner,
+                              float a_next, float s_next, hipStream_t stream);
+int launch_multistep_step_known(bool cfg, const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n,
+                                float guidance, float kx, float ke, float c0, float ct, float cp, float in_scale,
+                                const float* known, const float* mask, const float* noise_known, int channels, int64_t inner,
+                                float a_next, float s_next, hipStream_t stream);
+// x <- select(mask, x, a_next known + s_next noise_known) (mask == nullptr: mask = 1 everywhere); model_in = fp16(x in_scale), twice when dup
+int launch_known_blend(float* x, half_t* model_in, bool dup, int64_t n, float in_scale, const float* known, const float* mask,
+                       const float* noise_known, int channels, int64_t inner, float a_next, float s_next, hipStream_t stream);
 int launch_fill_relpos_bias(const half_t* emb, const int* buckets, float* out, int heads, int F, hipStream_t stream);
 
 // ---- pack.hip : one-off weight repacking at load time

@@ -554,6 +554,101 @@ def multistep_step(eps, x, x0_prev, model_in, coeffs, next_input_scale: float = 
                "lavie_multistep_step")
 
 
+def _known_region(who, x, known, mask, noise_known, level):
+    """The lavie_known_region of a step on latents x [P, C, ...]: known / noise_known shaped as x, mask [P, 1, ...] (None only for
+    known_blend), level = (a_next, s_next) from <scheduler>.noise_level.  Returns the struct; it borrows the tensors."""
+    _chk32(x, known, mask, noise_known)
+    if x.dim() < 3:
+        raise ValueError(f"{who}: latents must be [P, C, ...], got {tuple(x.shape)}")
+    if known is None or tuple(known.shape) != tuple(x.shape):
+        raise ValueError(f"{who}: known must have the latents' shape {tuple(x.shape)}")
+    if noise_known is not None and tuple(noise_known.shape) != tuple(x.shape):
+        raise ValueError(f"{who}: noise_known must have the latents' shape {tuple(x.shape)}")
+    want = (x.shape[0], 1) + tuple(x.shape[2:])
+    if mask is not None and tuple(mask.shape) != want:
+        raise ValueError(f"{who}: mask must have shape {want}, got {tuple(mask.shape)}")
+    a, s = level
+    r = _lib.KnownRegionC()
+    r.struct_size = ctypes.sizeof(_lib.KnownRegionC)
+    r.channels = x.shape[1]
+    r.inner = math.prod(x.shape[2:])
+    r.known, r.mask, r.noise_known = known.data_ptr(), (mask.data_ptr() if mask is not None else None), \
+        (noise_known.data_ptr() if noise_known is not None else None)
+    r.a_next, r.s_next = float(a), float(s)
+    return r
+
+
+def known_blend(x, model_in, known, mask, noise_known, level, input_scale: float = 1.0):
+    """x <- select(mask, x, a known + s noise_known) in place, level = (a, s), and model_in <- fp16(x input_scale): as many
+    elements as x, or twice as many ([x | x], the guided model input).  mask None = 1 everywhere: the scheduler's add_noise."""
+    _chk16(model_in)
+    n = x.numel()
+    if model_in.numel() not in (n, 2 * n):
+        raise ValueError("known_blend: model_in must have as many elements as x, or twice as many")
+    r = _known_region("known_blend", x, known, mask, noise_known, level)
+    _lib.check(_lib.load().lavie_known_blend_f32(_p(x), _p(model_in), int(model_in.numel() == 2 * n), n, float(input_scale),
+                                                 _stream(), ctypes.byref(r)), "lavie_known_blend_f32")
+
+
+def cfg_sampler_step_known(eps2, x, noise, model_in2, guidance, coeffs, next_input_scale, known, mask, noise_known, level):
+    """cfg_ddpm_step around known latents: after the update, x <- select(mask, x', a known + s noise_known) with level = (a, s)
+    = <scheduler>.noise_level of the timestep the step lands on; model_in2 = fp16 of that x, both halves equal."""
+    _chk16(eps2, model_in2)
+    _chk32(noise)
+    n = x.numel()
+    if eps2.numel() != 2 * n or model_in2.numel() != 2 * n:
+        raise ValueError("cfg_sampler_step_known: eps2 / model_in2 must have twice as many elements as x")
+    k_x, k_e, c_x0, c_xt, sigma = coeffs
+    r = _known_region("cfg_sampler_step_known", x, known, mask, noise_known, level)
+    _lib.check(_lib.load().lavie_cfg_sampler_step_known(_p(eps2), _p(x), _p(noise), _p(model_in2), n, float(guidance), float(k_x),
+                                                        float(k_e), float(c_x0), float(c_xt), float(sigma),
+                                                        float(next_input_scale), _stream(), ctypes.byref(r)),
+               "lavie_cfg_sampler_step_known")
+
+
+def sampler_step_known(eps, x, noise, model_in, coeffs, next_input_scale, known, mask, noise_known, level):
+    """sampler_step (no guidance) around known latents; see cfg_sampler_step_known."""
+    _chk16(eps, model_in)
+    _chk32(noise)
+    n = x.numel()
+    if eps.numel() != n or model_in.numel() != n:
+        raise ValueError("sampler_step_known: eps / model_in must have as many elements as x")
+    k_x, k_e, c_x0, c_xt, sigma = coeffs
+    r = _known_region("sampler_step_known", x, known, mask, noise_known, level)
+    _lib.check(_lib.load().lavie_sampler_step_known(_p(eps), _p(x), _p(noise), _p(model_in), n, float(k_x), float(k_e),
+                                                    float(c_x0), float(c_xt), float(sigma), float(next_input_scale), _stream(),
+                                                    ctypes.byref(r)), "lavie_sampler_step_known")
+
+
+def cfg_multistep_step_known(eps2, x, x0_prev, model_in2, guidance, coeffs, next_input_scale, known, mask, noise_known, level):
+    """cfg_multistep_step around known latents; the history written is select(mask, x0, known): a pinned element's x0 is known."""
+    _chk16(eps2, model_in2)
+    _chk32(x0_prev)
+    n = x.numel()
+    if eps2.numel() != 2 * n or model_in2.numel() != 2 * n or x0_prev.numel() != n:
+        raise ValueError("cfg_multistep_step_known: eps2 / model_in2 must have twice, x0_prev as many elements as x")
+    k_x, k_e, c_x0, c_xt, c_prev = coeffs
+    r = _known_region("cfg_multistep_step_known", x, known, mask, noise_known, level)
+    _lib.check(_lib.load().lavie_cfg_multistep_step_known(_p(eps2), _p(x), _p(x0_prev), _p(model_in2), n, float(guidance),
+                                                          float(k_x), float(k_e), float(c_x0), float(c_xt), float(c_prev),
+                                                          float(next_input_scale), _stream(), ctypes.byref(r)),
+               "lavie_cfg_multistep_step_known")
+
+
+def multistep_step_known(eps, x, x0_prev, model_in, coeffs, next_input_scale, known, mask, noise_known, level):
+    """multistep_step (no guidance) around known latents; see cfg_multistep_step_known."""
+    _chk16(eps, model_in)
+    _chk32(x0_prev)
+    n = x.numel()
+    if eps.numel() != n or model_in.numel() != n or x0_prev.numel() != n:
+        raise ValueError("multistep_step_known: eps / model_in / x0_prev must have as many elements as x")
+    k_x, k_e, c_x0, c_xt, c_prev = coeffs
+    r = _known_region("multistep_step_known", x, known, mask, noise_known, level)
+    _lib.check(_lib.load().lavie_multistep_step_known(_p(eps), _p(x), _p(x0_prev), _p(model_in), n, float(k_x), float(k_e),
+                                                      float(c_x0), float(c_xt), float(c_prev), float(next_input_scale), _stream(),
+                                                      ctypes.byref(r)), "lavie_multistep_step_known")
+
+
 def latents_to_model_input1(x, model_in, input_scale: float = 1.0):
     _chk32(x)
     _chk16(model_in)

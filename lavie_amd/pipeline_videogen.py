@@ -261,9 +261,17 @@ class VideoGenPipeline:
     # ------------------------------------------------------------------ the denoise loop (662-689)
     @torch.no_grad()
     def denoise(self, latents: torch.Tensor, ctx: torch.Tensor, num_inference_steps: int, guidance_scale: float,
-                generator=None, callback: Optional[Callable] = None, callback_steps: int = 1, eta: float = 0.0) -> torch.Tensor:
+                generator=None, callback: Optional[Callable] = None, callback_steps: int = 1, eta: float = 0.0,
+                known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                known_noise: Optional[torch.Tensor] = None, start_step: int = 0) -> torch.Tensor:
         """latents fp32 [P, C, F, h, w] on the device, ctx fp16 [2P, n, d] = [negative | prompt] (guidance_scale > 1) or
-        [P, n, d] = prompt only (guidance_scale <= 1: no classifier-free guidance, :626) -> denoised fp32."""
+        [P, n, d] = prompt only (guidance_scale <= 1: no classifier-free guidance, :626) -> denoised fp32.
+        `known` (clean latents, shaped as `latents`) switches to sampling around known latents: `_denoise_known`."""
+        if known is not None:
+            return self._denoise_known(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta,
+                                       known, mask, known_noise, start_step)
+        if mask is not None or known_noise is not None or start_step != 0:
+            raise ValueError("`mask`, `known_noise` and `start_step` need `known` latents")
         dev = latents.device
         sch = self.scheduler
         sch.set_timesteps(num_inference_steps)
@@ -384,6 +392,178 @@ class VideoGenPipeline:
                 raise cleanup_error
         return x
 
+    # ------------------------------------------------------------------ the loop around known latents
+    @torch.no_grad()
+    def _denoise_known(self, latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta, known,
+                       mask, known_noise, start_step) -> torch.Tensor:
+        """The loop of `denoise` around known clean latents (the known-region replacement of diffusers' legacy inpaint /
+        img2img loop), still one step launch per denoising step: after every step the step kernel itself overwrites the part
+        `mask` pins (1 = keep `known`, 0 = free, [P, 1, F, h, w] or broadcastable to it) with `known` re-noised to the level
+        the step just reached, x_t = a known + s known_noise, and the last step lands on `known` itself.  `known_noise` is ONE
+        tensor for the whole run (drawn from `generator` before the loop when not given).
+        start_step = 0: x starts as `latents` with the pinned part replaced.  start_step > 0 (a run at reduced strength): the loop
+        runs timesteps[start_step:] and x starts as `known` noised to timesteps[start_step] everywhere, `latents` only gives the
+        shape.  mask = None pins nothing during the steps (plain img2img).
+        The step's own noise (DDPM, DDIM with eta > 0) is drawn per step as in `denoise`, without its two-slot host staging."""
+        dev = latents.device
+        sch = self.scheduler
+        sch.set_timesteps(num_inference_steps)
+        fractional = bool(getattr(sch, "fractional_timesteps", False))
+        timesteps = [float(t) if fractional else int(t) for t in sch.timesteps]
+        if not 0 <= start_step < len(timesteps):
+            raise ValueError(f"`start_step`={start_step} must lie in 0..{len(timesteps) - 1}")
+        in_scale = getattr(sch, "model_input_scale", None)
+        takes_eta = "eta" in inspect.signature(sch.coefficients).parameters
+        multistep = bool(getattr(sch, "multistep", False))
+        do_cfg = guidance_scale > 1.0
+        x = latents.to(torch.float32).contiguous().clone()
+        p = x.shape[0]
+        nb = 2 * p if do_cfg else p
+        if ctx.shape[0] != nb:
+            raise ValueError(f"ctx has {ctx.shape[0]} rows, expected {nb} for {p} latents at guidance_scale={guidance_scale}")
+        if tuple(known.shape) != tuple(x.shape):
+            raise ValueError(f"`known` has shape {tuple(known.shape)}, the latents {tuple(x.shape)}")
+        known = known.to(device=dev, dtype=torch.float32).contiguous()
+        if mask is not None:
+            mask = mask.to(device=dev, dtype=torch.float32).expand(p, 1, *x.shape[2:]).contiguous()
+        gens = generator if isinstance(generator, list) else ([generator] if generator is not None else [])
+        if isinstance(generator, list):
+            if len(gens) != p:
+                raise ValueError(f"got a list of {len(gens)} generators for {p} latents")
+            if len({g.device.type for g in gens}) != 1:
+                raise ValueError("a list of generators must live on one device type")
+        if known_noise is None:
+            known_noise = randn_tensor(tuple(x.shape), generator=generator, device=dev, dtype=torch.float32)
+        elif tuple(known_noise.shape) != tuple(x.shape):
+            raise ValueError(f"`known_noise` has shape {tuple(known_noise.shape)}, the latents {tuple(x.shape)}")
+        known_noise = known_noise.to(device=dev, dtype=torch.float32).contiguous()
+        x0_prev = torch.empty_like(x) if multistep else None
+        model_in = torch.empty((nb,) + tuple(x.shape[1:]), dtype=torch.float16, device=dev)
+        first = timesteps[start_step]
+        ops.known_blend(x, model_in, known, mask if start_step == 0 else None, known_noise, sch.noise_level(first),
+                        in_scale(first) if in_scale else 1.0)
+        self.unet.prepare(nb, x.shape[2], x.shape[3], x.shape[4], ctx.shape[1])
+        ctx = self.unet.cache_context(ctx) if hasattr(self.unet, "cache_context") else ctx
+        host_noise = bool(gens) and gens[0].device.type == "cpu"
+        noise_dev = torch.empty_like(x)
+        t_dev = torch.tensor(timesteps, dtype=torch.float32, device=dev)
+        # the step kernel writes one fp16 value into both halves of model_in, pinned or not: cfg_shared_prefix holds
+        shared = do_cfg and self.cfg_shared_prefix and hasattr(self.unet, "set_cfg_shared_input")
+        try:
+            if shared:
+                self.unet.set_cfg_shared_input(True)
+                if os.environ.get("LAVIE_DEBUG_CHECK_SHARED") == "1" and not torch.equal(model_in[:p], model_in[p:]):
+                    raise RuntimeError("cfg_shared_prefix: the two halves of the model input differ")
+            for i in range(start_step, len(timesteps)):
+                t = timesteps[i]
+                eps = self.unet(model_in, t_dev[i], encoder_hidden_states=ctx).sample
+                coeffs = sch.coefficients(t, eta) if takes_eta else sch.coefficients(t)
+                if multistep and i == start_step:
+                    coeffs = tuple(coeffs[:4]) + (0.0,)        # a late start has no x0 history yet: this step is first order
+                noise = None
+                if not multistep and coeffs[4] != 0.0:
+                    if host_noise and isinstance(generator, list):
+                        noise = torch.stack([torch.randn(x.shape[1:], generator=g, dtype=torch.float32) for g in gens]).to(dev)
+                    elif host_noise:
+                        noise = torch.randn(x.shape, generator=generator, dtype=torch.float32).to(dev)
+                    elif isinstance(generator, list):
+                        for j, g in enumerate(gens):
+                            noise_dev[j].normal_(generator=g)
+                        noise = noise_dev
+                    else:
+                        noise = noise_dev.normal_(generator=generator) if generator is not None else noise_dev.normal_()
+                last = i + 1 == len(timesteps)
+                next_scale = in_scale(timesteps[i + 1]) if in_scale and not last else 1.0
+                level = sch.noise_level(None if last else timesteps[i + 1])
+                if mask is None:                           # nothing pinned: the plain step kernels
+                    if multistep and do_cfg:
+                        ops.cfg_multistep_step(eps, x, x0_prev, model_in, guidance_scale, coeffs, next_scale)
+                    elif multistep:
+                        ops.multistep_step(eps, x, x0_prev, model_in, coeffs, next_scale)
+                    elif do_cfg:
+                        ops.cfg_ddpm_step(eps, x, noise, model_in, guidance_scale, coeffs, next_scale)
+                    else:
+                        ops.sampler_step(eps, x, noise, model_in, coeffs, next_scale)
+                elif multistep and do_cfg:
+                    ops.cfg_multistep_step_known(eps, x, x0_prev, model_in, guidance_scale, coeffs, next_scale, known, mask,
+                                                 known_noise, level)
+                elif multistep:
+                    ops.multistep_step_known(eps, x, x0_prev, model_in, coeffs, next_scale, known, mask, known_noise, level)
+                elif do_cfg:
+                    ops.cfg_sampler_step_known(eps, x, noise, model_in, guidance_scale, coeffs, next_scale, known, mask,
+                                               known_noise, level)
+                else:
+                    ops.sampler_step_known(eps, x, noise, model_in, coeffs, next_scale, known, mask, known_noise, level)
+                if callback is not None and i % callback_steps == 0:
+                    callback(i, t, x)
+        finally:
+            pending = sys.exc_info()[1]
+            cleanup_error = None
+            for undo in ((lambda: self.unet.set_cfg_shared_input(False)) if shared else None,
+                         (lambda: self.unet.cache_context(None)) if hasattr(self.unet, "cache_context") else None):
+                if undo is None:
+                    continue
+                try:
+                    undo()
+                except Exception as e:      # noqa: BLE001
+                    cleanup_error = cleanup_error or e
+            if cleanup_error is not None and pending is None:
+                raise cleanup_error
+        return x
+
+    @staticmethod
+    def strength_start(num_inference_steps: int, strength: float) -> int:
+        """First position of the timestep table a run at `strength` in (0, 1] takes: steps - int(steps * strength), the img2img
+        rule; at least one step always runs."""
+        if not 0.0 < strength <= 1.0:
+            raise ValueError(f"`strength` must lie in (0, 1] but is {strength}")
+        return min(num_inference_steps - int(num_inference_steps * strength), num_inference_steps - 1)
+
+    def check_known_inputs(self, known_latents, known_mask, video, strength, shape):
+        """The arguments of sampling around known latents, against the latent `shape` [P, C, F, h, w] of the call."""
+        if not isinstance(strength, (int, float)) or not 0.0 < strength <= 1.0:
+            raise ValueError(f"`strength` must lie in (0, 1] but is {strength}")
+        if video is not None and known_latents is not None:
+            raise ValueError("Cannot forward both `video` and `known_latents`. Please make sure to only forward one of the two.")
+        have = video is not None or known_latents is not None
+        if known_mask is not None and not have:
+            raise ValueError("`known_mask` needs `known_latents` or `video`: there is nothing to keep.")
+        if strength < 1.0 and not have:
+            raise ValueError("`strength` < 1 needs `known_latents` or `video` to start from.")
+        if known_latents is not None and tuple(known_latents.shape) != tuple(shape):
+            raise ValueError(f"Unexpected `known_latents` shape, got {tuple(known_latents.shape)}, expected {tuple(shape)}")
+        if video is not None:
+            p, _, f, h, w = shape
+            k = self.vae_scale_factor
+            pixels = ((p, f, h * k, w * k, 3), (p, 3, f, h * k, w * k))
+            want = pixels[0] if video.dtype == torch.uint8 else pixels[1]
+            if not (video.dtype == torch.uint8 or video.is_floating_point()) or tuple(video.shape) != want:
+                raise ValueError(f"`video` must be uint8 {pixels[0]} or float {pixels[1]} in [-1, 1], got {video.dtype} "
+                                 f"{tuple(video.shape)}")
+            if self.vae is None:
+                raise ValueError("no vae attached: pass `known_latents` instead of `video`")
+        if known_mask is not None:
+            want = (shape[0], 1) + tuple(shape[2:])
+            try:
+                ok = known_mask.dim() == 5 and tuple(torch.broadcast_shapes(tuple(known_mask.shape), want)) == want
+            except RuntimeError:
+                ok = False
+            if not ok:
+                raise ValueError(f"`known_mask` must be broadcastable to {want}, got {tuple(known_mask.shape)}")
+            if not bool(((known_mask >= 0) & (known_mask <= 1)).all()):
+                raise ValueError("`known_mask` values must lie in [0, 1] (1 keeps the known latents, 0 is free)")
+
+    def encode_video(self, video: torch.Tensor) -> torch.Tensor:
+        """Pixels [P, F, H, W, 3] uint8 or [P, 3, F, H, W] float in [-1, 1] -> latents [P, 4, F, H/8, W/8] fp32: the posterior
+        mode of `self.vae`, times 0.18215 (the inverse of decode_latents)."""
+        if video.dtype == torch.uint8:
+            video = video.permute(0, 4, 1, 2, 3).float() / 127.5 - 1.0
+        b, c, f, h, w = video.shape
+        param = next(self.vae.parameters())
+        frames = video.permute(0, 2, 1, 3, 4).reshape(b * f, c, h, w).to(device=param.device, dtype=param.dtype)
+        lat = torch.cat([self.vae.encode(frames[i:i + 8]).latent_dist.mode() for i in range(0, b * f, 8)], dim=0) * 0.18215
+        return lat.reshape(b, f, *lat.shape[1:]).permute(0, 2, 1, 3, 4).float().contiguous()
+
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str], None] = None, image_tensor=None, height: Optional[int] = None,
                  width: Optional[int] = None, video_length: int = 16, num_inference_steps: int = 50,
@@ -391,7 +571,9 @@ class VideoGenPipeline:
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None,
                  prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
                  output_type: Optional[str] = "pil", return_dict: bool = True, callback=None, callback_steps: int = 1,
-                 cross_attention_kwargs=None, image_embeds: Optional[torch.Tensor] = None):
+                 cross_attention_kwargs=None, image_embeds: Optional[torch.Tensor] = None,
+                 known_latents: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None,
+                 video: Optional[torch.Tensor] = None, strength: float = 1.0):
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
@@ -409,15 +591,23 @@ class VideoGenPipeline:
                                   negative_prompt_embeds, image_features).to(torch.float16).contiguous()
         latents = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.config.in_channels, video_length,
                                        height, width, torch.float32, device, generator, latents)
+        # sampling around known latents (pinned frames, video-to-video, clip continuation): `_denoise_known`
+        self.check_known_inputs(known_latents, known_mask, video, strength, latents.shape)
+        around = {}
+        if video is not None or known_latents is not None:
+            known = self.encode_video(video) if video is not None else known_latents
+            around = dict(known=known.to(device=device, dtype=torch.float32), mask=known_mask,
+                          start_step=self.strength_start(num_inference_steps, strength))
         lora_scale = (cross_attention_kwargs or {}).get("scale")
         if lora_scale is None:
-            latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta)
+            latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta,
+                                   **around)
         else:                              # diffusers' LoRA strength for this call only, restored also on an exception
             prev = self.unet.lora_scale
             self.unet.set_lora_scale(lora_scale)
             try:
                 latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps,
-                                       eta)
+                                       eta, **around)
             finally:
                 self.unet.set_lora_scale(prev)
         if output_type == "latent":

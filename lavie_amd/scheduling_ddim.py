@@ -128,6 +128,14 @@ class DDIMScheduler:
     def _variance(self, a_t: float, a_prev: float) -> float:                              # :198-207
         return ((1.0 - a_prev) / (1.0 - a_t)) * (1.0 - a_t / a_prev)
 
+    def noise_level(self, timestep=None) -> Tuple[float, float]:
+        """(a, s) of `timestep`: a sample there is a x_0 + s noise, a = sqrt(abar_t), s = sqrt(1 - abar_t).  `None` stands for
+        "after the last step": (1, 0).  What the known-region step kernels re-noise the pinned latents with."""
+        if timestep is None:
+            return 1.0, 0.0
+        ab = float(self.alphas_cumprod[int(timestep)].double())
+        return ab ** 0.5, (1.0 - ab) ** 0.5
+
     def coefficients(self, timestep: int, eta: float = 0.0) -> Tuple[float, float, float, float, float]:
         """(k_x, k_m, c_x0, c_xt, sigma) of the fused kernel form (m = the model output after guidance):
         x0 = k_x x - k_m m;  x_prev = c_x0 x0 + c_xt x + sigma z.  With a = sqrt(abar_prev), b = sqrt(1 - abar_prev -

@@ -85,6 +85,14 @@ class DDPMScheduler:
         shape = (-1,) + (1,) * (original_samples.dim() - 1)
         return ab[t].sqrt().reshape(shape) * original_samples + (1 - ab[t]).sqrt().reshape(shape) * noise
 
+    def noise_level(self, timestep=None) -> Tuple[float, float]:
+        """(a, s) of `timestep`: a sample there is a x_0 + s noise, a = sqrt(abar_t), s = sqrt(1 - abar_t).  `None` stands for
+        "after the last step": (1, 0).  What the known-region step kernels re-noise the pinned latents with."""
+        if timestep is None:
+            return 1.0, 0.0
+        ab = float(self.alphas_cumprod[int(timestep)].double())
+        return ab ** 0.5, (1.0 - ab) ** 0.5
+
     def coefficients(self, timestep: int) -> Tuple[float, float, float, float, float]:
         """(k_x, k_eps, c_x0, c_xt, sigma): x0 = k_x x - k_eps eps;  x_prev = c_x0 x0 + c_xt x + sigma z."""
         t = int(timestep)

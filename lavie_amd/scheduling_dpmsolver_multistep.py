@@ -159,6 +159,14 @@ class DPMSolverMultistepScheduler:
             raise ValueError(f"timestep {timestep} is not one of the {self.num_inference_steps} timesteps of this schedule")
         return i
 
+    def noise_level(self, timestep=None) -> Tuple[float, float]:
+        """(a, s) of `timestep`: a sample there is a x_0 + s noise, a = sqrt(abar_t), s = sqrt(1 - abar_t).  `None` stands for
+        "after the last step": (1, 0).  What the known-region step kernels re-noise the pinned latents with."""
+        if timestep is None:
+            return 1.0, 0.0
+        ab = float(self.alphas_cumprod[int(timestep)].double())
+        return ab ** 0.5, (1.0 - ab) ** 0.5
+
     def coefficients(self, timestep) -> Tuple[float, float, float, float, float]:
         """(k_x, k_eps, c_x0, c_xt, c_prev) of the step that leaves `timestep` (module docstring).  A pure function of the
         timestep table: the position of `timestep` in it says whether there is a history and what the previous h was."""

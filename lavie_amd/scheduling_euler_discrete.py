@@ -78,6 +78,13 @@ class EulerDiscreteScheduler:
     def scale_model_input(self, sample: torch.Tensor, timestep) -> torch.Tensor:
         return sample * self.model_input_scale(timestep)
 
+    def noise_level(self, timestep=None) -> Tuple[float, float]:
+        """(a, s) of `timestep`: a sample there is a x_0 + s noise.  This scheduler's x is unscaled, so a = 1 and s = sigma_t;
+        `None` stands for "after the last step": (1, 0).  What the known-region step kernels re-noise the pinned latents with."""
+        if timestep is None:
+            return 1.0, 0.0
+        return 1.0, float(self._sigmas[self._index(timestep)])
+
     def coefficients(self, timestep) -> Tuple[float, float, float, float, float]:
         """(k_x, k_eps, c_x0, c_xt, sigma_noise) of the fused kernel form; see the module docstring."""
         i = self._index(timestep)
