@@ -423,6 +423,12 @@ int lavie_debug_force_tile(int mode);
 int lavie_debug_force_splits(int s);
 /* Tuning knob: LDS bytes one temporal-attention workgroup may stage (smaller = more workgroups per CU). */
 int lavie_debug_temporal_budget(int bytes);
+/* Test hook (additive, ABI unchanged): the most workgroups the launchers of the row-resident kernels start — lavie_geglu_mlp_f16,
+ * lavie_temporal_block_f16, lavie_cross_block_f16 / lavie_cross_block_long_f16 and lavie_proj_qkv_f16, and nothing else.  0 =
+ * automatic: min(tiles, 256).  1..256 = min(tiles, max_workgroups): the kernels deal their 16-row tiles to gridDim.x workgroups in
+ * near-equal runs, 8 per pass, so a small cap walks a small input through second and later passes, which 256 workgroups reach only
+ * past 2048 tiles (32784 rows).  Results do not depend on it.  Any other value is an error and leaves the setting unchanged. */
+int lavie_debug_rowfuse_grid(int max_workgroups);
 int lavie_profile_begin(unsigned mask, int max_events);
 int lavie_profile_end(void* stream, long long* launches_host, double* ms_host, double* flops_host, double* bytes_host);
 

@@ -141,6 +141,7 @@ SIGNATURES = {
     "lavie_debug_fused_mask": (c_int, [c_int]),
     "lavie_debug_gn_producer_count": (c_ll, []),
     "lavie_debug_temporal_budget": (c_int, [c_int]),
+    "lavie_debug_rowfuse_grid": (c_int, [c_int]),
     "lavie_profile_begin": (c_int, [C.c_uint, c_int]),
     "lavie_profile_end": (c_int, [c_void_p, C.POINTER(c_ll), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                    C.POINTER(C.c_double)]),

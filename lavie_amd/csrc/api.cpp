@@ -574,6 +574,11 @@ int lavie_debug_fused_mask(int mask) {
     return 0;
 }
 int lavie_debug_temporal_budget(int bytes) { bump_debug_epoch(); temporal_set_budget(bytes); return 0; }
+int lavie_debug_rowfuse_grid(int max_workgroups) {
+    if (int rc = rowfuse_set_grid_cap(max_workgroups)) return rc;     // a rejected value changes nothing
+    bump_debug_epoch();
+    return 0;
+}
 long long lavie_debug_gn_producer_count(void) { return (long long)lavie::gn_producer_count(); }
 
 int lavie_profile_begin(unsigned mask, int max_events) { return profile_begin(mask, max_events); }

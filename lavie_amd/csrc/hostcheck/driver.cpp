@@ -17,6 +17,7 @@
 #include "../../../include/lavie_hip.h"
 
 extern "C" long lavie_hostcheck_launches();
+extern "C" long lavie_hostcheck_last_grid_x();
 extern "C" void lavie_hostcheck_trace_to(FILE* f);
 extern "C" void lavie_hostcheck_kernel_names_to(FILE* f);
 
@@ -385,7 +386,8 @@ static void run_traces(const char* path) {
 // ---- operator launch trace: IN holds one operator call per line, "<entry> key=int ..." — the entry point without lavie_ / _f16,
 // its integer arguments under the names of include/lavie_hip.h, 0 / 1 for each optional operand (bias, bias2, R, x2, sc1, sc2) and
 // force_tile / force_splits (default 0); the end and glue kernels' entries (timestep_sinusoid ... f16_to_f32) and the pack / bind steps
-// of the row-resident blocks (pack_geglu_mlp, bind_cross_block[_long]: pack + bind) likewise.  Tensors are never read.  OUT: "== <line>", then the stub's launch lines of that call, or
+// of the row-resident blocks (pack_geglu_mlp, bind_cross_block[_long]: pack + bind) likewise, and the blocks themselves (geglu_mlp, temporal_block,
+// cross_block[_long], proj_qkv), temporal_attention and group_norm[_affine] on exactly sized buffers, under rowfuse_grid / temporal_budget (default 0).  Tensors are never read.  OUT: "== <line>", then the stub's launch lines of that call, or
 // "!! refused" where the library returns an error (its message goes to stderr).  A line the driver cannot parse ends the run.
 static int run_optrace(const char* in_path, const char* out_path) {
     FILE* in = fopen(in_path, "r");
@@ -428,10 +430,12 @@ static int run_optrace(const char* in_path, const char* out_path) {
         };
         auto P = [&](const char* k) -> void* { return O(k) ? d : nullptr; };
         auto F = [&](const char* k) -> const float* { return O(k) ? fd : nullptr; };
-        const int tile = O("force_tile"), splits = O("force_splits");
+        const int tile = O("force_tile"), splits = O("force_splits"), grid_cap = O("rowfuse_grid"), budget = O("temporal_budget");
         fprintf(g_out, "== %s\n", s.c_str());
         int rc = lavie_debug_force_tile(tile);
         lavie_debug_force_splits(splits);
+        if (rc == 0) rc = lavie_debug_rowfuse_grid(grid_cap);
+        lavie_debug_temporal_budget(budget);
         if (rc == 0) {
             if (entry == "linear") {
                 const int lda = I("lda"), ldb2 = I("ldb2"), rpb = I("rows_per_batch"), ldr = I("ldr"), ldc = I("ldc"), M = I("M"), N = I("N"), K = I("K"), g = I("geglu");
@@ -510,6 +514,63 @@ static int run_optrace(const char* in_path, const char* out_path) {
                         rc = lng ? lavie_bind_cross_block_long_f16(tmpl.data(), kv.data(), B, L, C, img.data(), nullptr)
                                  : lavie_bind_cross_block_f16(tmpl.data(), kv.data(), B, L, C, img.data(), nullptr);
                 }
+            } else if (entry == "geglu_mlp") {              // the row-resident blocks, temporal attention and GroupNorm: exactly sized buffers too
+                const int M = I("M"), C = I("C");
+                const long long ib = lavie_geglu_mlp_image_bytes(C), bf = lavie_geglu_mlp_bias_floats(C);
+                if (!missing) {
+                    std::vector<unsigned short> x((size_t)M * C), y((size_t)M * C), img((size_t)(ib > 0 ? ib / 2 : 1));
+                    std::vector<float> b1img((size_t)(bf > 0 ? bf : 1)), v((size_t)C);
+                    rc = lavie_geglu_mlp_f16(x.data(), y.data(), M, C, img.data(), b1img.data(), v.data(), v.data(), v.data(), 1e-5f, nullptr);
+                }
+            } else if (entry == "temporal_block") {
+                const int B = I("B"), Fr = I("F"), D = I("D"), C = I("C"), heads = I("heads"), rot = I("rot_dim");
+                const long long ib = lavie_temporal_block_image_bytes(C, heads, Fr, rot);
+                if (!missing) {
+                    std::vector<unsigned short> x((size_t)B * Fr * D * C), y(x.size()), img((size_t)(ib > 0 ? ib / 2 : 1));
+                    std::vector<float> v((size_t)C), rb((size_t)heads * Fr * Fr), tab((size_t)Fr * (rot / 2) + 1);
+                    rc = lavie_temporal_block_f16(x.data(), y.data(), B, Fr, D, C, heads, img.data(), v.data(), v.data(), v.data(), rb.data(), tab.data(),
+                                                  tab.data(), rot, 0.1f, 1e-5f, nullptr);
+                }
+            } else if (entry == "cross_block" || entry == "cross_block_long") {
+                const int M = I("M"), rpb = I("rows_per_batch"), C = I("C"), heads = I("heads"), L = I("ctx_len");
+                const bool lng = entry == "cross_block_long";
+                const long long ib = lng ? lavie_cross_block_long_image_bytes(C, heads) : lavie_cross_block_image_bytes(C, heads);
+                if (!missing) {
+                    const size_t nb = rpb > 0 ? (size_t)(M / rpb) : 1;
+                    std::vector<unsigned short> att((size_t)M * C), x(att.size()), y(att.size()), img((nb ? nb : 1) * (size_t)(ib > 0 ? ib / 2 : 1));
+                    std::vector<float> v((size_t)C);
+                    rc = lng ? lavie_cross_block_long_f16(att.data(), x.data(), y.data(), M, rpb, C, heads, img.data(), v.data(), v.data(), v.data(), v.data(), L, 0.1f, 1e-5f, nullptr)
+                             : lavie_cross_block_f16(att.data(), x.data(), y.data(), M, rpb, C, heads, img.data(), v.data(), v.data(), v.data(), v.data(), L, 0.1f, 1e-5f, nullptr);
+                }
+            } else if (entry == "proj_qkv") {
+                const int rpd = I("rows_per_domain"), M = I("M"), C = I("C");
+                const long long ib = lavie_proj_qkv_image_bytes(C);
+                if (!missing) {
+                    const size_t doms = rpd > 0 ? (size_t)((M + rpd - 1) / rpd) : 1;
+                    std::vector<unsigned short> x((size_t)M * C), tx(x.size()), qkv((size_t)M * 3 * C), img((size_t)(ib > 0 ? ib / 2 : 1));
+                    std::vector<float> ab(doms * C * 2), v((size_t)C);
+                    rc = lavie_proj_qkv_f16(x.data(), ab.data(), rpd, img.data(), v.data(), v.data(), v.data(), 1e-5f, tx.data(), qkv.data(), M, C, nullptr);
+                }
+            } else if (entry == "temporal_attention") {
+                const int ld = I("ld"), ldo = I("ldo"), B = I("B"), Fr = I("F"), D = I("D"), heads = I("heads"), dh = I("dh"), rot = I("rot_dim");
+                if (!missing) {
+                    const size_t rows = (size_t)B * Fr * D;
+                    std::vector<unsigned short> qkv(rows * ld), o(rows * ldo);
+                    std::vector<float> bias((size_t)heads * Fr * Fr), tab((size_t)Fr * (rot / 2) + 1);
+                    rc = lavie_temporal_attention_f16(qkv.data(), ld, o.data(), ldo, B, Fr, D, heads, dh, bias.data(), rot ? tab.data() : nullptr,
+                                                      rot ? tab.data() : nullptr, rot, 0.1f, nullptr);
+                }
+            } else if (entry == "group_norm" || entry == "group_norm_affine") {
+                const bool aff = entry == "group_norm_affine";
+                const int C1 = aff ? I("C") : I("C1"), C2 = aff ? 0 : I("C2"), NB = I("NB"), Pr = I("P"), groups = I("groups"), silu = aff ? 0 : I("silu");
+                if (!missing) {
+                    const size_t rows = (size_t)NB * Pr;
+                    std::vector<unsigned short> x1(rows * C1), x2(rows * C2 + 1), y(rows * (C1 + C2));
+                    std::vector<float> v((size_t)C1 + C2), ws((size_t)lavie_group_norm_ws_floats(NB, groups)), ab((size_t)NB * (C1 + C2) * 2);
+                    rc = aff ? lavie_group_norm_affine_f16(x1.data(), C1, NB, Pr, groups, v.data(), v.data(), 1e-5f, ws.data(), ab.data(), nullptr)
+                             : lavie_group_norm_f16(x1.data(), C1, O("x2") ? x2.data() : nullptr, C2, NB, Pr, groups, v.data(), v.data(), 1e-5f, silu, ws.data(),
+                                                    y.data(), nullptr);
+                }
             } else {
                 fprintf(stderr, "hostcheck optrace: unknown entry point '%s'\n", entry.c_str());
                 return 2;
@@ -526,6 +587,8 @@ static int run_optrace(const char* in_path, const char* out_path) {
     }
     REQUIRE(lavie_debug_force_tile(0) == 0);
     lavie_debug_force_splits(0);
+    REQUIRE(lavie_debug_rowfuse_grid(0) == 0);
+    lavie_debug_temporal_budget(0);
     lavie_hostcheck_trace_to(nullptr);
     fclose(g_out);
     fclose(in);
@@ -577,6 +640,50 @@ int main(int argc, char** argv) {
     // operator-level argument checks
     REQUIRE(lavie_linear_f16(nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, 0, 16, 64, 63, 0, nullptr) != 0);
     REQUIRE(lavie_geglu_mlp_image_bytes(123) == 0);
+    {   // lavie_debug_rowfuse_grid: 0 = min(tiles, 256), 1..256 = the cap; any other value is refused and leaves the setting as it was;
+        // it reaches the four row-resident launchers and nothing else
+        const int M = 4160, C = 320;                                 // 260 tiles of 16 rows, one video of 260 tiles, 13 frames of 20
+        std::vector<unsigned short> x((size_t)M * C), y(x.size()), qkv((size_t)M * 3 * C), img((size_t)lavie_geglu_mlp_image_bytes(C) / 2),
+            ximg((size_t)lavie_cross_block_image_bytes(C, 8) / 2), limg((size_t)lavie_cross_block_long_image_bytes(C, 8) / 2),
+            timg((size_t)lavie_temporal_block_image_bytes(C, 8, 16, 32) / 2), pimg((size_t)lavie_proj_qkv_image_bytes(C) / 2);
+        std::vector<float> b1img((size_t)lavie_geglu_mlp_bias_floats(C)), v((size_t)C), rb(8 * 16 * 16), tab(16 * 16), ab((size_t)13 * C * 2),
+            ws((size_t)lavie_group_norm_ws_floats(1, 32));
+        auto grids = [&](long* g) {
+            REQUIRE(lavie_geglu_mlp_f16(x.data(), y.data(), M, C, img.data(), b1img.data(), v.data(), v.data(), v.data(), 1e-5f, nullptr) == 0);
+            g[0] = lavie_hostcheck_last_grid_x();
+            REQUIRE(lavie_temporal_block_f16(x.data(), y.data(), 1, 16, 260, C, 8, timg.data(), v.data(), v.data(), v.data(), rb.data(), tab.data(), tab.data(), 32,
+                                             0.1f, 1e-5f, nullptr) == 0);
+            g[1] = lavie_hostcheck_last_grid_x();
+            REQUIRE(lavie_cross_block_f16(x.data(), x.data(), y.data(), M, M, C, 8, ximg.data(), v.data(), v.data(), v.data(), v.data(), 77, 0.1f, 1e-5f, nullptr) == 0);
+            g[2] = lavie_hostcheck_last_grid_x();
+            REQUIRE(lavie_cross_block_long_f16(x.data(), x.data(), y.data(), M, M, C, 8, limg.data(), v.data(), v.data(), v.data(), v.data(), 154, 0.1f, 1e-5f, nullptr) == 0);
+            g[3] = lavie_hostcheck_last_grid_x();
+            REQUIRE(lavie_proj_qkv_f16(x.data(), ab.data(), 320, pimg.data(), v.data(), v.data(), v.data(), 1e-5f, y.data(), qkv.data(), M, C, nullptr) == 0);
+            g[4] = lavie_hostcheck_last_grid_x();
+        };
+        long g[5];
+        grids(g);
+        for (long v_ : g) REQUIRE(v_ == 256);
+        REQUIRE(lavie_debug_rowfuse_grid(3) == 0);
+        grids(g);
+        for (long v_ : g) REQUIRE(v_ == 3);
+        REQUIRE(lavie_debug_rowfuse_grid(257) != 0 && lavie_debug_rowfuse_grid(-1) != 0);
+        REQUIRE(strstr(lavie_last_error(), "rowfuse_grid") != nullptr);
+        grids(g);
+        for (long v_ : g) REQUIRE(v_ == 3);                             // the refused values changed nothing
+        REQUIRE(lavie_debug_rowfuse_grid(256) == 0 && lavie_debug_rowfuse_grid(1) == 0);
+        grids(g);
+        for (long v_ : g) REQUIRE(v_ == 1);
+        REQUIRE(lavie_debug_rowfuse_grid(256) == 0);
+        REQUIRE(lavie_geglu_mlp_f16(x.data(), y.data(), 48, C, img.data(), b1img.data(), v.data(), v.data(), v.data(), 1e-5f, nullptr) == 0);
+        REQUIRE(lavie_hostcheck_last_grid_x() == 3);                      // never more workgroups than tiles
+        REQUIRE(lavie_debug_rowfuse_grid(2) == 0);
+        REQUIRE(lavie_group_norm_f16(x.data(), C, nullptr, 0, 1, M, 32, v.data(), v.data(), 1e-5f, 1, ws.data(), y.data(), nullptr) == 0);
+        REQUIRE(lavie_hostcheck_last_grid_x() > 2);                       // another family's launch is not capped
+        REQUIRE(lavie_debug_rowfuse_grid(0) == 0);
+        grids(g);
+        for (long v_ : g) REQUIRE(v_ == 256);
+    }
     {   // the long fused text cross-attention (81..160 keys): sizes, and lengths / widths refused before any HIP call
         REQUIRE(lavie_cross_block_long_image_bytes(320, 8) == 840 * 1024 && lavie_cross_block_long_image_bytes(256, 8) == 0);
         std::vector<unsigned short> w(320 * 320), tmpl(840 * 512), kv(161 * 640), img(840 * 512), x(128 * 320);

@@ -56,6 +56,7 @@ hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* shmem, hip
 // Launch trace: one line per launch (kernel, grid, block, dynamic LDS) to g_trace.  The driver's `trace` mode points it at a file;
 // LAVIE_HOSTCHECK_TRACE=1 sends it to stderr.  Kernel names come from clang's registration calls.
 static long g_launches = 0;
+static unsigned g_last_grid_x = 0;     // of the latest launch (the driver's check of lavie_debug_rowfuse_grid)
 static FILE* g_trace = getenv("LAVIE_HOSTCHECK_TRACE") ? stderr : nullptr;
 static std::map<const void*, std::string>& kernel_names() { static std::map<const void*, std::string> m; return m; }
 static const char* kernel_name(const void* f) {
@@ -75,6 +76,7 @@ hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void**, size_t 
         abort();
     }
     ++g_launches;
+    g_last_grid_x = grid.x;
     if (g_trace) fprintf(g_trace, "%s %u,%u,%u %u,%u,%u %zu\n", kernel_name(f), grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
     return hipSuccess;
 }
@@ -82,6 +84,7 @@ hipError_t hipExtLaunchKernel(const void* f, dim3 grid, dim3 block, void** args,
     return hipLaunchKernel(f, grid, block, args, shmem, s);
 }
 long lavie_hostcheck_launches() { return g_launches; }
+long lavie_hostcheck_last_grid_x() { return (long)g_last_grid_x; }
 void lavie_hostcheck_trace_to(FILE* f) { g_trace = f; }
 // every kernel name the registration calls have seen, sorted, one per line (the driver's `kernels` mode)
 void lavie_hostcheck_kernel_names_to(FILE* f) {

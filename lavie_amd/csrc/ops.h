@@ -142,6 +142,11 @@ int launch_ln_fold(const half_t* W, const float* gamma, const float* beta, const
 int launch_pack_geglu_vec(const float* in, float* out, int N, hipStream_t stream);
 
 // ---- rowfuse.hip : row-resident fused transformer sub-blocks (weights streamed through LDS, rows in registers)
+// Workgroups of a row-resident launch over `work` tiles (or pixels): min(work, 256), or min(work, cap) under the test hook
+// lavie_debug_rowfuse_grid.  The kernels read gridDim.x and nothing else about the grid, so a cap of 3 walks a 50-tile input through
+// the passes a 256-workgroup launch reaches only past 2048 tiles.  rowfuse_set_grid_cap: 0 = automatic, 1..256; else an error, unchanged.
+int rowfuse_grid(int work);
+int rowfuse_set_grid_cap(int max_workgroups);
 bool geglu_mlp_supported(int C);
 size_t geglu_mlp_image_bytes(int C);
 size_t geglu_mlp_bias_floats(int C);

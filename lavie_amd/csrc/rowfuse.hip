@@ -62,6 +62,17 @@ int pack_geglu_mlp(const half_t* w1, const half_t* b1, const half_t* w2, int C, 
     return 0;
 }
 
+static int g_rowfuse_grid_cap = 0;       // lavie_debug_rowfuse_grid: 0 = automatic
+int rowfuse_set_grid_cap(int max_workgroups) {
+    LAVIE_CHECK(max_workgroups >= 0 && max_workgroups <= 256, "rowfuse_grid: %d workgroups is not 0 (automatic) or 1..256", max_workgroups);
+    g_rowfuse_grid_cap = max_workgroups;
+    return 0;
+}
+int rowfuse_grid(int work) {
+    const int cap = g_rowfuse_grid_cap > 0 ? g_rowfuse_grid_cap : 256;
+    return work < cap ? work : cap;
+}
+
 // ------------------------------------------------------------------------------------------------ device helpers
 struct GegluMlpParams {
     const half_t* x;         // [M, C] rows (ld = C)
@@ -288,7 +299,7 @@ int launch_geglu_mlp(const half_t* x, half_t* y, int M, int C, const half_t* img
         LAVIE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_set = true;
     }
-    const int grid = p.tiles < 256 ? p.tiles : 256;
+    const int grid = rowfuse_grid(p.tiles);
     if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);
     else hipLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, p);
     LAVIE_HIP(hipGetLastError());
@@ -656,7 +667,7 @@ int launch_temporal_block(const half_t* x, half_t* y, int B, int F, int D, int C
     p.x = x; p.y = y; p.img = img; p.gamma = gamma; p.beta = beta; p.bo = bo; p.relbias = relbias; p.rot_cos = rot_cos;
     p.rot_sin = rot_sin; p.D = D; p.units = B * D; p.scale = scale; p.eps = eps;
     constexpr int lds = rf::RING_BYTES + tb::TAB_BYTES;
-    const int grid = p.units < 256 ? p.units : 256;
+    const int grid = rowfuse_grid(p.units);
     auto kern = temporal_block_kernel<8>;      // LDS read-ahead depth 8
     if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc;     // once per kernel address, not per launch
     if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);

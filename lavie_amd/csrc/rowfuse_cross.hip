@@ -624,7 +624,7 @@ static int launch_impl(const half_t* att, const half_t* x, half_t* y, int M, int
     p.att = att; p.x = x; p.y = y; p.img = img; p.bo1 = bo1; p.gamma = gamma; p.beta = beta; p.bo2 = bo2;
     p.tiles = M / rf::TOK; p.tiles_per_batch = rows_per_batch / rf::TOK; p.L = L; p.scale = scale; p.eps = eps;
     constexpr int lds = rf::RING_BYTES + xb::VEC_BYTES;
-    const int grid = p.tiles < 256 ? p.tiles : 256;
+    const int grid = rowfuse_grid(p.tiles);
     auto kern = cross_block_kernel<8 + (NKT == 5 ? 0 : XB_LONG)>;      // LDS read-ahead depth 8
     if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc;     // once per kernel address, not per launch
     if (prof.active()) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), lds, stream, prof.start(), prof.stop(), 0, p);

@@ -275,7 +275,7 @@ int launch_proj_qkv(const half_t* x, const float* gn_ab, int rows_per_domain, co
     p.M = M; p.tiles = cdiv(M, rf::TOK); p.rows_per_domain = rows_per_domain; p.eps = eps;
     auto kern = proj_qkv_kernel<8>;
     if (int rc = ensure_dynamic_lds((const void*)kern, pq::LDS_BYTES)) return rc;
-    const int grid = p.tiles < 256 ? p.tiles : 256;
+    const int grid = rowfuse_grid(p.tiles);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(rf::THREADS), pq::LDS_BYTES, stream, p);
     LAVIE_HIP(hipGetLastError());
     return 0;

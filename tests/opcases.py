@@ -34,6 +34,7 @@ class Case:
         self.calls = None                     # GEMM family: the C-ABI calls `run` makes (call()), replayed on the host-only build
         self.force = None                     # (tile, splits) the case forces around its launch, whatever the variant
         self.variants = None                  # the VARIANTS the case runs under where not all six (restricted(): the reach tables)
+        self.knobs = {}                       # further switches around the launch, as `hostcheck optrace` names them: rowfuse_grid, temporal_budget
 
     @functools.cached_property
     def ref(self):
@@ -69,6 +70,12 @@ def call(entry, **ints):
 
 def with_calls(case, calls, force=None):
     case.calls, case.force = calls, force
+    return case
+
+
+def local_calls(case, calls, **knobs):
+    """with_calls for a kernel that does not depend on the GEMM choice: replayed once, under the switches it runs under itself"""
+    case.calls, case.variants, case.knobs = calls, ("auto",), {k: int(v) for k, v in knobs.items() if v}
     return case
 
 
@@ -301,7 +308,9 @@ NOT_PLANNED = {}
 WHOLE_FORWARD = "tests/test_gpu_engine.py (whole-output rel-L2 of the engine's blocks and forwards against the fp32 oracle)"
 NO_OPERATOR_ENTRY = {
     # producer-side statistics: reached only behind the engine's rowstat_out / colstat_out, which no operator entry point sets
-    "gn_fold_kernel": WHOLE_FORWARD, "gn_finalize_kernel": WHOLE_FORWARD, "rowstat_finalize_kernel": WHOLE_FORWARD,
+    # (gn_finalize_kernel is not one of them: ops.group_norm launches it whenever the producers' statistics are not used, norm.hip
+    # launch_group_norm, and every group_norm case's trace names it: LOCAL_KERNELS)
+    "gn_fold_kernel": WHOLE_FORWARD, "rowstat_finalize_kernel": WHOLE_FORWARD,
     # the chunked form of the pack (the unchunked one: pack_conv_out_case) and the packs of the GEGLU / parity operands: bit-moves
     # whose output every conv / GEGLU / parity case consumes
     "pack_conv3x3_parity_kernel": "tests/test_gpu_ops_local.py::test_upsample_conv3x3_parity (ops.pack_conv3x3_parity)",
@@ -322,10 +331,13 @@ PACK_STEP_KERNELS = {
 ENDS_KERNELS = ("timestep_sinusoid_kernel", "gemv_kernel", "add_class_emb_silu_kernel", "conv_in_kernel", "conv_out4_kernel<5>", "conv_out4_kernel<6>",
                 "conv_out_kernel", "ln_fold_kernel", "pack_conv_in_kernel", "pack_conv3x3_kernel", "pack_geglu_vec_kernel", "copy_rows_kernel",
                 "f16_to_f32_kernel", "fill_relpos_bias_kernel")
-# the fixture's other names, by the prefix of the kernels the attention, norm, row-resident, temporal and elementwise cases launch
-COVERED_ELSEWHERE = ("attention_dma_kernel<", "attention_kernel<", "attention_wide_kernel", "gn_affine_kernel", "gn_apply_kernel<", "gn_stats_kernel<",
-                     "layernorm_kernel", "geglu_mlp_kernel<", "cross_block_kernel<", "temporal_block_kernel<", "proj_qkv_kernel<",
-                     "temporal_stream_kernel<", "temporal_tile_kernel<")
+# the fixture's other names, by the prefix of the kernels the attention and LayerNorm cases launch (not replayed: their routes are
+# mirrored by attention_route) ...
+COVERED_ELSEWHERE = ("attention_dma_kernel<", "attention_kernel<", "attention_wide_kernel", "layernorm_kernel")
+# ... and of the GroupNorm, row-resident and temporal cases, which describe their calls: every such name of a forward's trace must be in
+# the replayed launches of a case (test_gemm_reach_host.py::test_local_kernels_of_a_forward_are_reached)
+LOCAL_KERNELS = ("gn_affine_kernel", "gn_apply_kernel<", "gn_stats_kernel<", "gn_finalize_kernel", "geglu_mlp_kernel<", "cross_block_kernel<",
+                 "temporal_block_kernel<", "proj_qkv_kernel<", "temporal_stream_kernel<", "temporal_attention_kernel<")
 
 
 # ------------------------------------------------------------------ 3x3 convolution family
@@ -346,6 +358,22 @@ class forced:
         lib = _lib.load()
         lib.lavie_debug_force_tile(self.restore[0])
         lib.lavie_debug_force_splits(self.restore[1])
+
+
+class grid_cap:
+    """lavie_debug_rowfuse_grid for the duration of a case: at most `cap` workgroups for the row-resident launchers, then back to 0
+    (automatic).  Takes the fixture's (tile, splits) like `forced` and leaves them alone."""
+
+    def __init__(self, cap, restore=None):
+        self.cap = cap
+
+    def __enter__(self):
+        from lavie_amd import _lib
+        _lib.check(_lib.load().lavie_debug_rowfuse_grid(self.cap), "lavie_debug_rowfuse_grid")
+
+    def __exit__(self, *exc):
+        from lavie_amd import _lib
+        _lib.load().lavie_debug_rowfuse_grid(0)
 
 
 def conv2d_any(x, w, b, stride, ups, pad):
@@ -646,10 +674,56 @@ def group_norm_case(nb, P, c1, c2=0, silu=True, eps=1e-5, offset=0.0, affine=Fal
 
     out = ((nb, ctot, 2), f32t) if affine else ((nb * P, ctot), f16)
     where = (lambda i: "(batch %d, channel %d, %s)" % (i // (2 * ctot), i // 2 % ctot, "ab"[i % 2])) if affine else oc.loc_rows(ctot)
-    return Case(f"group_norm[{tag}nb{nb},P{P},{c1}+{c2},silu{int(silu)},off{offset},aff{int(affine)}]", ins, {"y": out}, run, ref,
+    case = Case(f"group_norm[{tag}nb{nb},P{P},{c1}+{c2},silu{int(silu)},off{offset},aff{int(affine)}]", ins, {"y": out}, run, ref,
                 oc.round_c(1), model, where)
+    case.gn = (nb, P, ctot)
+    if affine:
+        return local_calls(case, [call("group_norm_affine", C=c1, NB=nb, P=P, groups=groups)])
+    return local_calls(case, [call("group_norm", C1=c1, C2=c2, NB=nb, P=P, groups=groups, silu=silu, x2=bool(c2))])
 
 
+GN_THREADS, GN_UNROLL, GN_MAX_SLABS = 256, 4, 2048
+
+
+def gn_geometry(ctot):
+    """norm.hip gn_geometry: (tx channel-vector lanes, vpt vectors per thread = the V of gn_stats_kernel<V> / gn_apply_kernel<V, SILU>,
+    ty row lanes)"""
+    assert ctot % 8 == 0 and ctot <= 4096
+    nvec, vpt = ctot // 8, 1
+    while nvec // vpt > GN_THREADS or nvec % vpt:
+        vpt += 1
+        assert vpt <= 4, ctot
+    return nvec // vpt, vpt, GN_THREADS // (nvec // vpt)
+
+
+def gn_slabs(P, NB, ty, cap_total=GN_MAX_SLABS):
+    """norm.hip gn_slabs -> (slabs = grid.x of the statistics and of the apply pass, rows per slab, whether the cap_total / NB clamp bound)"""
+    want = max(-(-P // (ty * 4)), 1)
+    cap = 1 if NB >= cap_total else cap_total // NB
+    slabs = min(want, cap)
+    quantum = ty * GN_UNROLL
+    rps = -(-(-(-P // slabs)) // quantum) * quantum
+    return -(-P // rps), rps, want > cap
+
+
+# Past one slab per pass.  The existing cases have P <= 10: one slab (two for 1280+640, ty = 1), one partial unrolled iteration.
+# Without the clamp a slab is exactly one quantum = ty * GN_UNROLL rows (gn_slabs rounds cdiv(P, slabs) <= quantum up to it), so a
+# row lane runs at most one whole unrolled iteration; more than one needs the cap_total / NB clamp to bind.
+#  case (nb, P, channels)          geometry (tx, V, ty)   slabs x rows   what it provides
+#  2 x 61 x 320                    (40, 1, 6)             3 x 24         three statistics slabs, the last ragged (13 rows): finalize folds 3 partials
+#  2 x 61 x 320 affine             (40, 1, 6)             3 x 24         the statistics-only form past one slab (gn_affine_kernel behind 3 partials)
+#  2 x 61 x 320 silu0, eps 1e-6    (40, 1, 6)             3 x 24         gn_apply_kernel<1, false> past one slab (the per-frame norm)
+#  1 x 11 x 1280+640               (240, 1, 1)            3 x 4          two sources past one slab, the group straddling them; ragged (3 rows)
+#  1 x 11 x 1280+1280              (160, 2, 1)            3 x 4          gn_stats_kernel<2> / gn_apply_kernel<2, true> (the 2560-wide skip concatenations), two sources
+#  700 x 23 x 1280                 (160, 1, 1)            2 x 12         NB = 700: 2048 / 700 = 2 < the 6 slabs wanted, the clamp binds: 12-row slabs = three whole
+#                                                                        unrolled iterations in slab 0, two and a remainder of 3 rows in the ragged slab 1 (11 rows)
+#  2 x (2 q + ty + 1) x every other width of GN_WIDTHS   each (tx, V, ty) gn_geometry tells apart at the models' widths, three slabs, the last ragged
+# V = 3 needs an odd number of 16-byte vectors above 256 (e.g. 2424 channels), V = 4 none at all below GN_MAX_C: no model width, no forward names them.
+GN_WIDTHS = (256, 320, 512, 640, 768, 960, 1024, 1280, 1536, 1920, 2048, 2560)       # block widths and skip concatenations of the base, interpolation and VSR UNets
+GN_PAST_SLAB = [dict(nb=2, P=61, c1=320, tag="slabs:"), dict(nb=2, P=61, c1=320, affine=True, tag="slabs:"),
+                dict(nb=2, P=61, c1=320, silu=False, eps=1e-6, tag="slabs:"), dict(nb=1, P=11, c1=1280, c2=640, tag="slabs:"),
+                dict(nb=1, P=11, c1=1280, c2=1280, tag="slabs:"), dict(nb=700, P=23, c1=1280, tag="clamp:")]
+GN_PAST_SLAB += [dict(nb=2, P=2 * 4 * gn_geometry(w)[2] + gn_geometry(w)[2] + 1, c1=w, tag="width:") for w in GN_WIDTHS if w not in (320,)]
 GN_CASES = [dict(nb=1, P=3, c1=64, tag="video:"), dict(nb=2, P=10, c1=320, tag="video:"),
             dict(nb=3, P=5, c1=320, silu=False, eps=1e-6, tag="frame:"), dict(nb=1, P=6, c1=1280, c2=640, tag="straddle:"),
             dict(nb=2, P=10, c1=320, affine=True), dict(nb=2, P=10, c1=320, offset=8.0, tag="offset:")]
@@ -1079,15 +1153,84 @@ def temporal_core(q, k, v, bias, cos, sin, scale, cv, rq, p_before_norm):
     return rq(e / l) @ v, (e / l) @ v.abs()
 
 
+def temporal_route(b, f, d, heads, dh, budget=0):
+    """What launch_temporal_attention launches (temporal_attention.hip, the launcher at the end of the file), as the stub names it,
+    with its grid and how the work is dealt: for the streaming kernel `ngroups` head groups, `per_group` workgroups per group walking
+    `tiles` (video, pixel) tiles at stride per_group, and the tile count of the fullest and the emptiest workgroup; for the tile kernel
+    the heads HG and pixels PT of a workgroup.  budget: lavie_debug_temporal_budget (0 = automatic)."""
+    nt = 1 if -(-f // 16) <= 1 else 4
+    fp, cw = 16 * nt, heads * dh
+    wide, narrow = (320, 256) if nt == 1 else (160, 128)
+    srl = wide if cw % wide == 0 and wide % dh == 0 else narrow if cw % narrow == 0 and narrow % dh == 0 else 0
+    if budget == 0 and srl and srl // dh <= 8:
+        pack2 = nt == 1 and f <= 8 and d % 2 == 0
+        ngroups = cw // srl
+        tiles = b * (d // 2 if pack2 else d)
+        per_group = min(max((512 if nt == 1 else 256) // ngroups, 1), tiles)
+        counts = [len(range(t0, tiles, per_group)) for t0 in range(per_group)]
+        return dict(kernel=f"temporal_stream_kernel<{nt}, {srl}, {2 if pack2 else 1}>", grid=(per_group * ngroups, 1, 1), ngroups=ngroups,
+                    per_group=per_group, tiles=tiles, fullest=max(counts), emptiest=min(counts), heads_per_group=srl // dh)
+
+    def row_stride(hg):
+        rs = hg * dh * 2 + 32
+        return rs + 32 if (rs // 32) % 2 == 0 else rs
+    want = budget if budget > 0 else (33000 if nt == 1 else 70000)
+    room = max(want, 3 * fp * 256)
+    hg = heads
+    while hg > 2 and hg % 2 == 0 and 3 * fp * row_stride(hg) > room:
+        hg //= 2
+    pt = min(max(room // (3 * fp * row_stride(hg)), 1), 4)
+    return dict(kernel=f"temporal_attention_kernel<{nt}>", grid=(b * -(-d // pt) * (heads // hg), 1, 1), HG=hg, PT=pt,
+                lds=3 * pt * fp * row_stride(hg))
+
+
+# everything launch_temporal_attention can launch (cross-checked against `hostcheck kernels` by test_gemm_reach_host.py)
+TATTN_ROUTES = ([f"temporal_stream_kernel<1, {w}, {p}>" for w in (320, 256) for p in (1, 2)] + [f"temporal_stream_kernel<4, {w}, 1>" for w in (160, 128)]
+                + ["temporal_attention_kernel<1>", "temporal_attention_kernel<4>"])
+
+
+def peaked_rows(f):
+    """one query frame per 16-frame block (the 16-row blocks of the kernels' score tiles): frame 5 of the block, or the last frame"""
+    return sorted({min(16 * blk + 5, f - 1) for blk in range(-(-f // 16))})
+
+
+def peak_bias(bias, f):
+    """the `peaked` profile: + 48 on the bias of (query frame, last frame) for the frames of peaked_rows, every head.  48 is exact in
+    fp32 next to a bias of N(0, 1) to 2^-18; the scores of N(0, 1) operands stay within a few nats."""
+    for r in peaked_rows(f):
+        bias[:, r, f - 1] += 48.0
+    return bias
+
+
+def assert_peaked(q, k, bias, cos, sin, scale, f):
+    """float64, on the values the kernel gets: in the rows of peaked_rows the last frame's logit is more than 30 nats above every other"""
+    q, k = d(q) * scale, d(k)
+    if cos is not None:
+        q, k = rot(q, d(cos), d(sin)), rot(k, d(cos), d(sin))
+    s = q @ k.transpose(-1, -2) + d(bias)[None]
+    rows = peaked_rows(f)
+    if f > 1:
+        margin = s[..., rows, f - 1] - s[..., rows, :f - 1].max(-1).values
+        assert margin.min() > 30.0, margin.min().item()
+    others = [r for r in range(f) if r not in rows]
+    if others and f > 1:
+        top2 = s[..., others, :].topk(2, -1).values
+        assert (top2[..., 0] - top2[..., 1]).median() < 10.0          # the other rows are ordinary
+
+
 @functools.lru_cache(maxsize=None)
-def temporal_attention_case(b, f, dd, c, tiled, plain=False, heads=8):
+def temporal_attention_case(b, f, dd, c, tiled, plain=False, heads=8, profile="unit"):
     """ops.temporal_attention on qkv [(b f d), 3c].  Rounding points, n = 4: q scaled (and rotated) to fp16
     (temporal_attention.hip:162-163 / :169; tiled kernel :472-473 / :477), k rotated to fp16 (:164-165; :440-441), the normalised P
-    (:216; :517), the output (:238; :539).  tiled: the tile kernel through lavie_debug_temporal_budget, else the streaming one."""
+    (:216; :517), the output (:238; :539).  tiled: the tile kernel through lavie_debug_temporal_budget (True = 33000 bytes, or the
+    budget itself), else whatever the launcher picks (temporal_route).  profile "peaked": peak_bias."""
     g = gen("tattn", b, f, dd, c, plain)
     dh = c // heads
+    budget = 33000 if tiled is True else int(tiled)
     qkv = rnd(g, b * f * dd, 3 * c)
     bias = torch.zeros(heads, f, f) if plain else rnd(g, heads, f, f, dtype=f32t)
+    if profile == "peaked":
+        bias = peak_bias(bias, f)
     cos, sin = (None, None) if plain else rotary_tables(f)
     ins = {"qkv": qkv, "bias": bias}
     if not plain:
@@ -1096,7 +1239,7 @@ def temporal_attention_case(b, f, dd, c, tiled, plain=False, heads=8):
     def run(ops, i, o):
         from lavie_amd import _lib
         lib = _lib.load()
-        lib.lavie_debug_temporal_budget(33000 if tiled else 0)
+        lib.lavie_debug_temporal_budget(budget)
         try:
             ops.temporal_attention(i["qkv"], b, f, dd, heads, i["bias"], i.get("cos"), i.get("sin"), rot_dim=0 if plain else 32, out=o["y"])
         finally:
@@ -1104,6 +1247,9 @@ def temporal_attention_case(b, f, dd, c, tiled, plain=False, heads=8):
 
     seq = lambda: qkv.reshape(b, f, dd, 3, heads, dh).permute(3, 0, 2, 4, 1, 5).reshape(3, b * dd, heads, f, dh)
     back = lambda t: t.reshape(b, dd, heads, f, dh).permute(0, 3, 1, 2, 4).reshape(b * f * dd, c)
+    if profile == "peaked":
+        qs, ks, _ = seq()
+        assert_peaked(qs, ks, bias, cos, sin, dh ** -0.5, f)
 
     def ref():
         y, sc = temporal_core(*seq(), bias, cos, sin, dh ** -0.5, d, ident, False)
@@ -1113,11 +1259,70 @@ def temporal_attention_case(b, f, dd, c, tiled, plain=False, heads=8):
         y, _ = temporal_core(*seq(), bias, cos, sin, dh ** -0.5, lambda t: t.float(), h_, False)
         return {"y": back(y).half()}
 
-    return Case(f"temporal_attention[b{b},f{f},d{dd},c{c},{'tiled' if tiled else 'stream'},plain{int(plain)}]", ins,
-                {"y": ((b * f * dd, c), f16)}, run, ref, oc.round_c(4), model, oc.loc_heads(heads, dh))
+    mode = "stream" if not budget else "tiled" if budget == 33000 else f"tiled{budget}"
+    name = f"temporal_attention[b{b},f{f},d{dd},c{c},{mode},plain{int(plain)}" + (f",h{heads}" if heads != 8 else "") + ("]" if profile == "unit" else f",{profile}]")
+    case = Case(name, ins, {"y": ((b * f * dd, c), f16)}, run, ref, oc.round_c(4), model, oc.loc_heads(heads, dh))
+    case.troute = temporal_route(b, f, dd, heads, dh, budget)
+    return local_calls(case, [call("temporal_attention", ld=3 * c, ldo=c, B=b, F=f, D=dd, heads=heads, dh=dh, rot_dim=0 if plain else 32)],
+                       temporal_budget=budget)
 
 
 TATTN_SHAPES = [(1, 1, 3, 256), (1, 2, 1, 320), (1, 17, 5, 256), (2, 16, 5, 320)]
+# Every streaming instantiation at every head / wave split it takes at the models' widths (8 heads: HG heads per 320 / 256 / 160 / 128-wide
+# group, wph waves per head), at frame counts with and without a masked tail, and with several tiles per workgroup: per_group =
+# (512 | 256) / ngroups workgroups walk a head group's B * D (packed: B * D / 2) tiles at stride per_group, so 2 per_group + 2 tiles
+# give workgroups 0 and 1 three tiles (first: wait <PIECES>, steady state: <PIECES + STORES> and issue_tile(n + 2), last: <STORES>)
+# and every other workgroup two; B = 2, so the walk t0 + n tstride crosses into the second video (t / Dt).
+#  (b, f, d, c)           instantiation                      HG  wph   tiles / per_group   fullest / emptiest   what else
+TATTN_STREAM = [
+    (2, 13, 5, 640),     # temporal_stream_kernel<1, 320, 1>    4   1     10 / 10             1 / 1                F = 13: masked tail ((2, 16, 5, 320) above: HG 8, two heads per wave)
+    (2, 16, 5, 1280),    # temporal_stream_kernel<1, 320, 1>    2   2     10 / 10             1 / 1                waves 2, 3 idle (one query block per head)
+    (5, 16, 205, 320),   # temporal_stream_kernel<1, 320, 1>    8   1     1025 / 512          3 / 2                the narrowest: 16400 rows, workgroup 0 alone has three tiles; B = 5
+    (2, 13, 129, 1280),  # temporal_stream_kernel<1, 320, 1>    2   2     258 / 128           3 / 2
+    (2, 16, 5, 256),     # temporal_stream_kernel<1, 256, 1>    8   1     10 / 10             1 / 1
+    (2, 13, 5, 512),     # temporal_stream_kernel<1, 256, 1>    4   1     10 / 10             1 / 1
+    (2, 16, 5, 1024),    # temporal_stream_kernel<1, 256, 1>    2   2     10 / 10             1 / 1
+    (2, 16, 129, 1024),  # temporal_stream_kernel<1, 256, 1>    2   2     258 / 128           3 / 2
+    (2, 8, 6, 320),      # temporal_stream_kernel<1, 320, 2>    8   1     6 / 6               1 / 1                two pixels x 8 frames per tile: the base model's F = 8 route
+    (2, 5, 6, 640),      # temporal_stream_kernel<1, 320, 2>    4   1     6 / 6               1 / 1                F = 5 < 8: masked frames inside both pixel halves
+    (2, 8, 6, 1280),     # temporal_stream_kernel<1, 320, 2>    2   2     6 / 6               1 / 1
+    (2, 5, 258, 1280),   # temporal_stream_kernel<1, 320, 2>    2   2     258 / 128           3 / 2
+    (2, 8, 6, 256),      # temporal_stream_kernel<1, 256, 2>    8   1     6 / 6               1 / 1                the VSR UNet's route
+    (2, 5, 6, 512),      # temporal_stream_kernel<1, 256, 2>    4   1     6 / 6               1 / 1
+    (2, 8, 6, 1024),     # temporal_stream_kernel<1, 256, 2>    2   2     6 / 6               1 / 1
+    (2, 8, 258, 1024),   # temporal_stream_kernel<1, 256, 2>    2   2     258 / 128           3 / 2
+    (2, 17, 5, 320),     # temporal_stream_kernel<4, 160, 1>    4   2     10 / 10             1 / 1                F = 17: one valid key in the second key tile; the interpolation model's route
+    (2, 61, 5, 640),     # temporal_stream_kernel<4, 160, 1>    2   4     10 / 10             1 / 1                F = 61
+    (2, 64, 5, 1280),    # temporal_stream_kernel<4, 160, 1>    1   8     10 / 10             1 / 1                F = 64: no masked key
+    (2, 17, 129, 320),   # temporal_stream_kernel<4, 160, 1>    4   2     258 / 128           3 / 2
+    (2, 61, 33, 1280),   # temporal_stream_kernel<4, 160, 1>    1   8     66 / 32             3 / 2
+    (2, 17, 5, 512),     # temporal_stream_kernel<4, 128, 1>    2   4     10 / 10             1 / 1                ((1, 17, 5, 256) above: HG 4, wph 2)
+    (2, 61, 5, 256),     # temporal_stream_kernel<4, 128, 1>    4   2     10 / 10             1 / 1
+    (2, 64, 5, 1024),    # temporal_stream_kernel<4, 128, 1>    1   8     10 / 10             1 / 1
+    (2, 61, 33, 1024),   # temporal_stream_kernel<4, 128, 1>    1   8     66 / 32             3 / 2
+]
+# (b, f, d, c, heads, budget): the tile kernel through a budget and through shapes the launcher sends there itself (srl == 0: head dim 48
+# tiles neither group width)
+#                                        instantiation                 HG  PT  what
+TATTN_TILE = [
+    (2, 16, 5, 256, 8, 60000),         # temporal_attention_kernel<1>    8   2   D % PT = 1: a ragged last pixel tile
+    (2, 16, 5, 320, 8, 20000),         # temporal_attention_kernel<1>    4   1   the budget halves HG
+    (2, 17, 5, 128, 4, 120000),        # temporal_attention_kernel<4>    4   2   D % PT = 1 ((1, 17, 5, 256) at 33000 above: HG halved twice, to 2)
+    (2, 16, 5, 384, 8, 0),             # temporal_attention_kernel<1>    4   1   sent there by the launcher: head dim 48; 33000 halves HG
+    (2, 17, 5, 384, 8, 0),             # temporal_attention_kernel<4>    2   1   the same at 17 frames; 70000 halves HG twice
+]
+TATTN_PEAKED = [(2, 16, 5, 320), (2, 17, 5, 320)]          # one case of each NT under the `peaked` profile (stream), and temporal_block below
+TATTN_MULTI = {"temporal_stream_kernel<1, 320, 1>": 2, "temporal_stream_kernel<1, 256, 1>": 1, "temporal_stream_kernel<1, 320, 2>": 1,
+               "temporal_stream_kernel<1, 256, 2>": 1, "temporal_stream_kernel<4, 160, 1>": 2, "temporal_stream_kernel<4, 128, 1>": 1}   # cases with 3 / 2 tiles
+
+
+def temporal_attention_cases():
+    cs = [temporal_attention_case(*sh, t) for sh in TATTN_SHAPES for t in (False, True)]
+    cs += [temporal_attention_case(1, 17, 5, 256, t, plain=True) for t in (False, True)]
+    cs += [temporal_attention_case(*sh, False) for sh in TATTN_STREAM]
+    cs += [temporal_attention_case(b, f, dd, c, bud, heads=h) for b, f, dd, c, h, bud in TATTN_TILE]
+    cs += [temporal_attention_case(*sh, False, profile="peaked") for sh in TATTN_PEAKED]
+    return cs
 
 
 def ln(x, gamma, beta, cv, eps=1e-5):
@@ -1126,21 +1331,76 @@ def ln(x, gamma, beta, cv, eps=1e-5):
     return (x - mean) * ((x - mean).pow(2).mean(-1, keepdim=True) + eps).rsqrt() * cv(gamma) + cv(beta)
 
 
-def block_case(name, ins, run, chain, n, C, in_place, outs=None, where=None):
+def block_case(name, ins, run, chain, n, C, in_place, outs=None, where=None, cap=0, calls=None, twin=None):
     """A fused block: chain(cv, rq) -> name -> (value, scale); the float64 reference runs it without roundings, the model in
-    fp32 with rq = one fp16 rounding at each counted point (the output store included)."""
+    fp32 with rq = one fp16 rounding at each counted point (the output store included).  cap: lavie_debug_rowfuse_grid around the
+    launch (grid_cap; 0 = the production grid).  twin: the out-of-place case of the same inputs, whose reference an in-place case shares."""
     outs = outs or {"y": ((ins["x"].shape[0], C), f16)}
 
     def model():
         return {k: v.half() for k, (v, _) in chain(lambda t: t.float(), h_).items()}
 
     c = {k: oc.round_c(v) for k, v in n.items()} if isinstance(n, dict) else oc.round_c(n)
-    return Case(f"{name}[inplace{int(in_place)}]", ins, outs, run, lambda: chain(d, ident), c, model,
-                where or oc.loc_rows(C), alias={"y": "x"} if in_place else None)
+    case = Case(f"{name}[inplace{int(in_place)}]", ins, outs, run, (lambda: twin().ref) if twin else (lambda: chain(d, ident)), c, model,
+                where or oc.loc_rows(C), alias={"y": "x"} if in_place else None,
+                setup=(lambda restore: grid_cap(cap, restore)) if cap else None)
+    case.chain, case.cap = chain, cap
+    return local_calls(case, calls, rowfuse_grid=cap)
+
+
+def rowfuse_walk(tiles, nwg, tiles_per_batch=None):
+    """The share rule of the row-resident kernels (rowfuse.hip geglu_mlp_kernel / temporal_block_kernel, rowfuse_pin.hip, rowfuse_cross.hip:
+    `share = tiles / nwg, rem = tiles - share * nwg, tile0 = bid * share + min(bid, rem)`): tile (or pixel unit) -> (workgroup, pass, wave).
+    A workgroup takes a contiguous run, 8 per pass, one per wave; with tiles_per_batch (cross_block) a pass also ends at a video's last
+    tile (`to_end`, rowfuse_cross.hip), since the pass streams that video's K / V image."""
+    share, rem = divmod(tiles, nwg)
+    out = [None] * tiles
+    for bid in range(nwg):
+        t, tend, ps = bid * share + min(bid, rem), bid * share + min(bid, rem) + share + (bid < rem), 0
+        while t < tend:
+            n = min(tend - t, 8)
+            if tiles_per_batch:
+                n = min(n, tiles_per_batch - t % tiles_per_batch)
+            for w in range(n):
+                out[t + w] = (bid, ps, w)
+            t, ps = t + n, ps + 1
+    assert None not in out
+    return out
+
+
+def walk_paths(walk, batch_of=None, ragged_last=False):
+    """What a walk contains, as the set of path names the multi-pass cases are chosen for (PATHS below).  batch_of: tile -> video / frame."""
+    nwg = 1 + max(w for w, _, _ in walk)
+    passes = [1 + max(p for w, p, _ in walk if w == b) for b in range(nwg)]
+    got = set()
+    if max(passes) >= 3:
+        got.add("three_passes")
+    if len(set(passes)) > 1:
+        got.add("pass_counts_differ")
+    width = {}                                                   # (workgroup, pass) -> tiles in it
+    for t, (w, p, _) in enumerate(walk):
+        width.setdefault((w, p), []).append(t)
+    if any(len(width[(b, passes[b] - 1)]) < 8 and passes[b] > 1 for b in range(nwg)):
+        got.add("idle_waves_in_last_pass")
+    if ragged_last and walk[-1][1] > 0:
+        got.add("ragged_tile_in_later_pass")
+    if batch_of:
+        if any(len({batch_of(t) for t in ts}) > 1 for ts in width.values()):
+            got.add("pass_spans_batches")
+        for b in range(nwg):
+            mine = [t for t, (w, _, _) in enumerate(walk) if w == b]
+            if len({batch_of(t) for t in mine}) > 1:
+                got.add("run_crosses_batch")
+                # a pass cut short at the boundary (fewer than 8 tiles although the run goes on) and a later pass on the next video
+                if any(len(width[(b, p)]) < 8 and p + 1 < passes[b] and batch_of(width[(b, p)][0]) != batch_of(width[(b, p + 1)][0]) for p in range(passes[b])):
+                    got.add("pass_cut_at_batch_end")
+            if mine and (mine[0] == 0 or batch_of(mine[0]) == batch_of(mine[0] - 1)) and mine[0] > 0:
+                got.add("starts_mid_batch")
+    return got
 
 
 @functools.lru_cache(maxsize=None)
-def geglu_mlp_case(M, in_place, C=320):
+def geglu_mlp_case(M, in_place, C=320, cap=0):
     """x + W2 (h gelu(g)) + b2 with (h | g) = W1 LN(x) + b1.  n = 3: LN(x) (rowfuse.hip:185-186), h gelu(g) (:224-225), the output
     (:256).  scale = |h gelu(g)| |W2| + |b2| + |x|."""
     g = gen("geglu_mlp", M)
@@ -1159,11 +1419,12 @@ def geglu_mlp_case(M, in_place, C=320):
         hg = rq(hh * gelu64(gate))
         return {"y": (cv(x) + hg @ cv(w2).t() + cv(b2), hg.abs() @ cv(w2).abs().t() + cv(b2).abs() + cv(x).abs())}
 
-    return block_case(f"geglu_mlp[M{M}]", ins, run, chain, 3, C, in_place)
+    return block_case(f"geglu_mlp[M{M}" + (f",cap{cap}]" if cap else "]"), ins, run, chain, 3, C, in_place, cap=cap,
+                      calls=[call("geglu_mlp", M=M, C=C)], twin=(lambda: geglu_mlp_case(M, False, C, cap)) if in_place else None)
 
 
 @functools.lru_cache(maxsize=None)
-def cross_block_case(B, P, L, in_place, C=320, heads=8):
+def cross_block_case(B, P, L, in_place, C=320, heads=8, cap=0):
     """x1 = x + Wo1 att + bo1; y = x1 + Wo2 attn2(LN(x1) Wq2, K, V) + bo2, K | V bound per video; the long variant above 80 keys.
     n = 5: LN(x1) (rowfuse_cross.hip:430-431), q as the MFMA operand (:488 / :496), P (:571), the attention output (:614 / :622), the
     output store (rowfuse.h:173).  scale = |o| |Wo2| + |bo2| + |att| |Wo1| + |bo1| + |x|."""
@@ -1184,18 +1445,23 @@ def cross_block_case(B, P, L, in_place, C=320, heads=8):
         img = bind(pack(i["wo1"], i["wq2"], i["wo2"]), i["kv"], B, L)
         op(i["att"], i["x"], img, i["bo1"], i["gamma"], i["beta"], i["bo2"], P, L, heads, dh ** -0.5, out=o["y"])
 
-    def chain(cv, rq):
+    def chain(cv, rq, video_of=None):
+        """video_of (injected defects): the video whose K | V each video's rows attend to, instead of their own"""
         x1 = cv(x) + cv(att) @ cv(wo1).t() + cv(bo1)
         s1 = cv(x).abs() + cv(att).abs() @ cv(wo1).abs().t() + cv(bo1).abs()
         q = rq(rq(ln(x1, gamma, beta, cv)) @ cv(wq2).t()).reshape(B, P, heads, dh).permute(0, 2, 1, 3)
-        k = cv(kv[:, :C]).reshape(B, L, heads, dh).permute(0, 2, 1, 3)
-        v = cv(kv[:, C:]).reshape(B, L, heads, dh).permute(0, 2, 1, 3)
+        kvv = kv if video_of is None else kv.reshape(B, L, 2 * C)[list(video_of)].reshape(B * L, 2 * C)
+        k = cv(kvv[:, :C]).reshape(B, L, heads, dh).permute(0, 2, 1, 3)
+        v = cv(kvv[:, C:]).reshape(B, L, heads, dh).permute(0, 2, 1, 3)
         s = q @ k.transpose(-1, -2) * dh ** -0.5
         e = torch.exp(s - s.max(-1, keepdim=True).values)
         o = rq((rq(e) @ v) / e.sum(-1, keepdim=True)).permute(0, 2, 1, 3).reshape(M, C)
         return {"y": (x1 + o @ cv(wo2).t() + cv(bo2), s1 + o.abs() @ cv(wo2).abs().t() + cv(bo2).abs())}
 
-    return block_case(f"cross_block{'_long' if long else ''}[B{B},P{P},L{L}]", ins, run, chain, 5, C, in_place)
+    entry = "cross_block_long" if long else "cross_block"
+    return block_case(f"{entry}[B{B},P{P},L{L}" + (f",cap{cap}]" if cap else "]"), ins, run, chain, 5, C, in_place, cap=cap,
+                      calls=[call(entry, M=M, rows_per_batch=P, C=C, heads=heads, ctx_len=L)],
+                      twin=(lambda: cross_block_case(B, P, L, False, C, heads, cap)) if in_place else None)
 
 
 # (videos, rows per video, keys): rows per video must be a multiple of the 16-token wave tile (cross_block_supported); 16 = the
@@ -1205,7 +1471,7 @@ CROSS_REFUSED = [(1, 1, 5), (1, 1, 100)]
 
 
 @functools.lru_cache(maxsize=None)
-def temporal_block_case(B, D, in_place, C=320, heads=8, Fr=16):
+def temporal_block_case(B, D, in_place, C=320, heads=8, Fr=16, cap=0, profile="unit"):
     """x + Wo attn_temp(LN(x)) + bo on rows (b f) d.  n = 7: LN(x) (rowfuse.hip:482-483), q scaled and rotated, k rotated, v
     (:521-523), exp() of the scores (:572), the attention output (:577-583), the output store (:641).
     scale = |o| |Wo| + |bo| + |x|."""
@@ -1216,8 +1482,14 @@ def temporal_block_case(B, D, in_place, C=320, heads=8, Fr=16):
     bo = rnd(g, C, dtype=f32t, s=0.2)
     gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
     relbias = rnd(g, heads, Fr, Fr, dtype=f32t)
+    if profile == "peaked":
+        relbias = peak_bias(relbias, Fr)
     cos, sin = rotary_tables(Fr)
     ins = dict(x=x, wq=wq, wk=wk, wv=wv, wo=wo, bo=bo, gamma=gamma, beta=beta, relbias=relbias, cos=cos, sin=sin)
+    if profile == "peaked":          # on the q and k the kernel forms: projections of the rounded LN(x), in float64
+        xn = h_(ln(x, gamma, beta, lambda t: t.float())).double()
+        sq = lambda w: (xn @ d(w).t()).reshape(B, Fr, D, heads, dh).permute(0, 2, 3, 1, 4).reshape(B * D, heads, Fr, dh)
+        assert_peaked(sq(wq), sq(wk), relbias, cos, sin, dh ** -0.5, Fr)
 
     def run(ops, i, o):
         img = ops.pack_temporal_block(i["wq"], i["wk"], i["wv"], i["wo"])
@@ -1232,11 +1504,14 @@ def temporal_block_case(B, D, in_place, C=320, heads=8, Fr=16):
         o = rq(o).reshape(B, D, heads, Fr, dh).permute(0, 3, 1, 2, 4).reshape(M, C)
         return {"y": (cv(x) + o @ cv(wo).t() + cv(bo), cv(x).abs() + o.abs() @ cv(wo).abs().t() + cv(bo).abs())}
 
-    return block_case(f"temporal_block[B{B},D{D}]", ins, run, chain, 7, C, in_place)
+    tag = (f",cap{cap}" if cap else "") + ("" if profile == "unit" else f",{profile}")
+    return block_case(f"temporal_block[B{B},D{D}{tag}]", ins, run, chain, 7, C, in_place, cap=cap,
+                      calls=[call("temporal_block", B=B, F=Fr, D=D, C=C, heads=heads, rot_dim=32)],
+                      twin=(lambda: temporal_block_case(B, D, False, C, heads, Fr, cap, profile)) if in_place else None)
 
 
 @functools.lru_cache(maxsize=None)
-def proj_qkv_case(NB, D, C=320):
+def proj_qkv_case(NB, D, C=320, cap=0):
     """tx = Wpin (a x + b) + bpin with the per-(frame, channel) GroupNorm pairs (a, b) as an input; qkv = Wqkv LN(tx).
     tx: n = 2 — a x + b (rowfuse_pin.hip:153-160), the store (rowfuse.h:173).  qkv: n = 3 — a x + b, LN(tx) taken from the fp32
     accumulators (rowfuse_pin.hip:223-224), the store."""
@@ -1263,8 +1538,68 @@ def proj_qkv_case(NB, D, C=320):
         xb2 = rq(ln(tx, ln_g, ln_b, cv))
         return {"tx": (tx, xb.abs() @ cv(wpin).abs().t() + cv(bpin).abs()), "qkv": (xb2 @ cv(wqkv).t(), xb2.abs() @ cv(wqkv).abs().t())}
 
-    return block_case(f"proj_qkv[NB{NB},D{D}]", ins, run, chain, {"tx": 2, "qkv": 3}, C, False, outs={"tx": ((M, C), f16), "qkv": ((M, 3 * C), f16)},
-                      where={"tx": oc.loc_rows(C), "qkv": oc.loc_rows(3 * C)})
+    return block_case(f"proj_qkv[NB{NB},D{D}" + (f",cap{cap}]" if cap else "]"), ins, run, chain, {"tx": 2, "qkv": 3}, C, False,
+                      outs={"tx": ((M, C), f16), "qkv": ((M, 3 * C), f16)}, where={"tx": oc.loc_rows(C), "qkv": oc.loc_rows(3 * C)}, cap=cap,
+                      calls=[call("proj_qkv", rows_per_domain=D, M=M, C=C)])
+
+
+# Past one tile per workgroup.  All four launchers start min(tiles, 256) workgroups, so every case above gives each workgroup one
+# tile and only wave 0 of it real rows; a second pass needs 2049 tiles (32784 rows).  The capped cases run the same kernels on
+# lavie_debug_rowfuse_grid workgroups (the kernels read gridDim.x and nothing else about the grid): rowfuse_walk is the share rule, PATHS
+# what the case set as a whole must contain (test_opcheck_host.py::test_multi_pass_cases_contain_every_path).
+#  case                                       tiles, shares, passes            path it provides
+#  geglu_mlp M = 795, cap 3                   50: 17 / 17 / 16, 3 / 3 / 2      first, steady-state and last pass (issue_group past PASS_GROUPS, the counted vmcnt(5) with a next
+#                                                                              pass behind it); last pass of workgroups 0, 1 = one wave of eight; pass counts differ; the ragged
+#                                                                              tile 49 (rows 784..794, the rowc clamp) is wave 7 of workgroup 2's second pass
+#  temporal_block B = 5, D = 10, cap 3        50 pixels: 17 / 17 / 16          the same three; passes of eight pixels span two videos (unit / p.D: pixels 8..15 = videos 0 | 1)
+#                                                                              (B = 2, D = 25 cuts its passes exactly at the video boundary, 17 + 8 = 25: it has no such pass)
+#  cross_block B = 4, P = 224, L = 77, cap 3  56 (14 a video): 19 / 19 / 18,   workgroup 0: tiles 0..7, 8..13 (cut at the video's end, six waves), 14..18 on video 1's image;
+#    and cross_block_long at L = 160          passes 3 / 4 / 3                 workgroup 1 starts at tile 19, mid-video 1, and runs 19..26, 27 (one tile left of video 1), 28..35,
+#                                                                              36..37; workgroup 2 starts mid-video 2.  (B = 4, P = 208 gives 3 / 3 / 3 passes: none differ)
+#  proj_qkv NB = 5, D = 160, cap 3            50 (10 a frame): 17 / 17 / 16    the same three; every full pass has waves under two frames' (a, b) pairs
+#  temporal_block B = 3, D = 683, cap 0       2049 pixels on 256 workgroups    the production launch: workgroup 0 has nine pixels = a second pass of one wave, the others eight
+# The natural grid is run for temporal_block alone: its float64 reference and scale are 1.3e10 + 3.4e9 multiply-adds, under DESIGN.md's
+# 2^34; at 32784 rows geglu_mlp needs 5.0e10 + 1.7e10, proj_qkv 2.7e10 + 2.7e10 and cross_block 2.3e10 (L = 77), all above it: their
+# natural-grid cover stays the 40960-row rel-L2 tests of tests/test_gpu_rowfuse.py.
+PATHS = {"geglu_mlp": {"three_passes", "idle_waves_in_last_pass", "pass_counts_differ", "ragged_tile_in_later_pass"},
+         "temporal_block": {"three_passes", "idle_waves_in_last_pass", "pass_counts_differ", "pass_spans_batches"},
+         "cross_block": {"three_passes", "idle_waves_in_last_pass", "pass_counts_differ", "run_crosses_batch", "pass_cut_at_batch_end", "starts_mid_batch"},
+         "cross_block_long": {"three_passes", "idle_waves_in_last_pass", "pass_counts_differ", "run_crosses_batch", "pass_cut_at_batch_end", "starts_mid_batch"},
+         "proj_qkv": {"three_passes", "idle_waves_in_last_pass", "pass_counts_differ", "pass_spans_batches"}}
+MULTI_GEGLU = [(795, 3)]                         # (M, cap)
+MULTI_TEMPORAL = [(5, 10, 3), (3, 683, 0)]       # (B, D, cap)
+MULTI_CROSS = [(4, 224, 77, 3), (4, 224, 160, 3)]   # (B, P, L, cap)
+MULTI_PROJ = [(5, 160, 3)]                       # (NB, D, cap)
+NATURAL_GRID = "temporal_block[B3,D683]"
+
+
+def multi_pass_cases(in_place=False):
+    """the multi-pass cases, out of place (or, where the block takes aliasing, in place)"""
+    cs = [geglu_mlp_case(M, in_place, cap=cap) for M, cap in MULTI_GEGLU]
+    cs += [temporal_block_case(B, D, in_place, cap=cap) for B, D, cap in MULTI_TEMPORAL]
+    cs += [cross_block_case(B, P_, L, in_place, cap=cap) for B, P_, L, cap in MULTI_CROSS]
+    return cs if in_place else cs + [proj_qkv_case(NB, D, cap=cap) for NB, D, cap in MULTI_PROJ]
+
+
+def case_walk(case):
+    """(family, walk, paths) of a block case, from the integers of its call and its cap (0: the launcher's min(tiles, 256))"""
+    entry, a = case.calls[0]
+    cap = case.cap or 256
+    if entry == "geglu_mlp":
+        tiles = -(-a["M"] // 16)
+        walk = rowfuse_walk(tiles, min(tiles, cap))
+        return entry, walk, walk_paths(walk, ragged_last=a["M"] % 16 != 0)
+    if entry == "temporal_block":
+        units = a["B"] * a["D"]
+        walk = rowfuse_walk(units, min(units, cap))
+        return entry, walk, walk_paths(walk, batch_of=lambda t: t // a["D"])
+    if entry == "proj_qkv":
+        tiles, per = -(-a["M"] // 16), a["rows_per_domain"] // 16
+        walk = rowfuse_walk(tiles, min(tiles, cap))
+        return entry, walk, walk_paths(walk, batch_of=lambda t: t // per)
+    tiles, per = a["M"] // 16, a["rows_per_batch"] // 16
+    walk = rowfuse_walk(tiles, min(tiles, cap), per)
+    return entry, walk, walk_paths(walk, batch_of=lambda t: t // per)
 
 
 # ------------------------------------------------------------------ sampler steps and lora_merge
@@ -1879,17 +2214,18 @@ def all_cases():
     cs += [temporal_conv_case(*s, t) for s in TCONV_SHAPES for t in (3, 5)] + [temporal_conv_case(*s, t, force=5) for s in TCONV_FORCED for t in (3, 5)]
     cs += [edge_in_case(*e, dt, tap) for e in EDGE_IN for dt in (f16, f32t) for tap in (False, True)]
     cs += [edge_out_case(*e, dt) for e in EDGE_OUT for dt in (f16, f32t)]
-    cs += [group_norm_case(**k) for k in GN_CASES]
+    cs += [group_norm_case(**k) for k in GN_CASES + GN_PAST_SLAB]
     cs += [layer_norm_case(*s) for s in LN_CASES]
     cs += [attention_case(*s) for s in SELF_ATTN]
     cs += [attention_case(3, 40, 320, lk=lk, kv_div=div) for lk, div in CROSS_ATTN]
     cs += [attention_case(1, l, c, heads=1) for l, c in WIDE_ATTN]
     cs += [sparse_causal_case(*s) for s in SPARSE_CAUSAL]
     cs += attention_hard_cases()
-    cs += [temporal_attention_case(*sh, False) for sh in TATTN_SHAPES] + [temporal_attention_case(1, 17, 5, 256, False, plain=True)]
+    cs += temporal_attention_cases()
     cs += [geglu_mlp_case(M, False) for M in (1, 129)] + [cross_block_case(*sh, False) for sh in CROSS_BLOCKS]
-    cs += [temporal_block_case(1, 1, False), temporal_block_case(2, 13, False)]
+    cs += [temporal_block_case(1, 1, False), temporal_block_case(2, 13, False), temporal_block_case(2, 13, False, profile="peaked")]
     cs += [proj_qkv_case(nb, dd) for nb in (1, 5) for dd in (16, 48)]
+    cs += multi_pass_cases()
     cs += [step_case(k, n) for k in STEP_KINDS for n in STEP_LENGTHS]
     cs += [lora_case(*s, ip) for s in LORA_SHAPES for ip in (False, True)]
     # the forward's ends and glue kernels (tests/test_gpu_ends_local.py)
@@ -1901,8 +2237,9 @@ def all_cases():
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lavie_amd", "csrc")
 
 
-def optrace_line(entry, ints, tile, splits):
-    return " ".join([entry] + [f"{k}={v}" for k, v in ints.items()] + [f"force_tile={tile}", f"force_splits={splits}"])
+def optrace_line(entry, ints, tile, splits, knobs=None):
+    return " ".join([entry] + [f"{k}={v}" for k, v in ints.items()] + [f"force_tile={tile}", f"force_splits={splits}"]
+                    + [f"{k}={v}" for k, v in (knobs or {}).items()])
 
 
 def hostcheck(*args):
@@ -1950,7 +2287,7 @@ def gemm_reach(cases):
     """{(case name, variant): launch lines, or None where the library refused a call} through `hostcheck optrace`: the library's own
     planner on the CPU, given the integers each case's `run` passes."""
     runs = gemm_runs(cases)
-    lines = [optrace_line(e, ints, *fs) for c, _, fs in runs for e, ints in c.calls]
+    lines = [optrace_line(e, ints, *fs, c.knobs) for c, _, fs in runs for e, ints in c.calls]
     blocks = optrace(lines)
     reach, it = {}, iter(blocks)
     for c, v, _ in runs:

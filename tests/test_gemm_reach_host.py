@@ -63,7 +63,7 @@ def test_registered_instantiations_are_reached_or_listed(reach):
 
 def test_fixture_names_are_all_accounted_for(reach, fixture_names):
     required = {n for n in fixture_names if n.startswith(GEMM)}
-    elsewhere = {n for n in fixture_names if n.startswith(C.COVERED_ELSEWHERE)}
+    elsewhere = {n for n in fixture_names if n.startswith(C.COVERED_ELSEWHERE + C.LOCAL_KERNELS)}
     ends = (set(C.ENDS_KERNELS) | set(C.PACK_STEP_KERNELS)) & fixture_names
     assert ends - names(reach) - set(C.PACK_STEP_KERNELS) == set(), "an end or glue kernel of a forward that no case launches"
     accounted = required | elsewhere | set(C.NO_OPERATOR_ENTRY) | ends
@@ -73,6 +73,67 @@ def test_fixture_names_are_all_accounted_for(reach, fixture_names):
     for name, test in C.NO_OPERATOR_ENTRY.items():
         path = test.split("::")[0].split(" ")[0]
         assert os.path.exists(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), path)), (name, path)
+
+
+def test_local_kernels_of_a_forward_are_reached(reach, fixture_names):
+    """Every GroupNorm, row-resident and temporal kernel a forward's trace names — each gn_stats_kernel<V> / gn_apply_kernel<V, SILU>
+    and gn_finalize_kernel among them — is launched by a case; gn_finalize_kernel by every group_norm case, which is why it is no
+    longer listed as having no operator entry point."""
+    required = {n for n in fixture_names if n.startswith(C.LOCAL_KERNELS)}
+    assert {"gn_finalize_kernel", "gn_stats_kernel<1>", "gn_stats_kernel<2>", "gn_apply_kernel<1, true>", "gn_apply_kernel<1, false>",
+            "gn_apply_kernel<2, true>", "temporal_block_kernel<8>", "temporal_stream_kernel<1, 320, 2>", "temporal_stream_kernel<4, 160, 1>"} <= required
+    assert required - names(reach) == set(), sorted(required - names(reach))
+    assert "gn_finalize_kernel" not in C.NO_OPERATOR_ENTRY and "gn_fold_kernel" in C.NO_OPERATOR_ENTRY
+    gn = [c for c in C.all_cases() if c.name.startswith("group_norm[")]
+    assert len(gn) == len(C.GN_CASES) + len(C.GN_PAST_SLAB)
+    for c in gn:                                  # statistics, finalize, then apply or the (a, b) pairs; grids as the Python mirror of gn_slabs says
+        lines = reach[(c.name, "auto")]
+        nb, P, ctot = c.gn
+        tx, vpt, ty = C.gn_geometry(ctot)
+        slabs = C.gn_slabs(P, nb, ty)[0]
+        assert [C.launch_name(l) for l in lines][:2] == [f"gn_stats_kernel<{vpt}>", "gn_finalize_kernel"], (c.name, lines)
+        assert C.launch_grid(lines[0]) == (slabs, nb, 1) and C.launch_grid(lines[1]) == (-(-nb * 32 // 4), 1, 1), (c.name, lines)
+        if c.calls[0][0] == "group_norm_affine":
+            assert C.launch_name(lines[2]) == "gn_affine_kernel"
+        else:
+            silu = "true" if c.calls[0][1]["silu"] else "false"
+            assert C.launch_name(lines[2]) == f"gn_apply_kernel<{vpt}, {silu}>" and C.launch_grid(lines[2]) == (slabs, nb, 1), (c.name, lines)
+
+
+def test_capped_block_cases_launch_with_their_cap(reach):
+    """Each multi-pass case launches its kernel on exactly lavie_debug_rowfuse_grid workgroups, the natural-grid case on 256, and the
+    older block cases on one workgroup per tile, as the share-rule mirror assumes."""
+    kernels = {"geglu_mlp": "geglu_mlp_kernel<320, 8>", "temporal_block": "temporal_block_kernel<8>", "cross_block": "cross_block_kernel<8>",
+               "cross_block_long": "cross_block_kernel<40>", "proj_qkv": "proj_qkv_kernel<8>"}
+    multi = C.multi_pass_cases()                  # (the in-place twins make the same call)
+    assert all(a.calls == b.calls and a.knobs == b.knobs for a, b in zip(multi, C.multi_pass_cases(in_place=True)))
+    assert {c.calls[0][0] for c in multi} == set(kernels) and [c.name for c in multi if not c.cap] == [C.NATURAL_GRID + "[inplace0]"]
+    for c in multi:
+        (line,) = reach[(c.name, "auto")]
+        fam, walk, _ = C.case_walk(c)
+        assert C.launch_name(line) == kernels[fam] and C.launch_grid(line) == (c.cap or 256, 1, 1), (c.name, line)
+        assert 1 + max(w for w, _, _ in walk) == C.launch_grid(line)[0]
+        assert c.knobs == ({"rowfuse_grid": c.cap} if c.cap else {})
+    older = [c for c in C.all_cases() if c.calls and c.calls[0][0] in kernels and c not in multi]
+    assert len(older) >= 14
+    for c in older:
+        (line,) = reach[(c.name, "auto")]
+        _, walk, _ = C.case_walk(c)
+        assert C.launch_grid(line)[0] == len(walk) and max(p for _, p, _ in walk) == 0, (c.name, line)      # one tile per workgroup: what the suite had
+
+
+def test_temporal_cases_launch_what_the_route_function_says(reach):
+    """opcases.temporal_route against the launcher itself: kernel name and grid of every temporal attention case, and TATTN_ROUTES
+    against the temporal kernels the library registers."""
+    registered = {n for n in C.registered_kernels() if n.startswith(("temporal_stream_kernel<", "temporal_attention_kernel<"))}
+    assert registered == set(C.TATTN_ROUTES), sorted(registered ^ set(C.TATTN_ROUTES))
+    cases = C.temporal_attention_cases()
+    for c in cases:
+        (line,) = reach[(c.name, "auto")]
+        assert (C.launch_name(line), C.launch_grid(line)) == (c.troute["kernel"], c.troute["grid"]), (c.name, line, c.troute)
+        if "lds" in c.troute:
+            assert int(line.rsplit(" ", 1)[1]) == c.troute["lds"], (c.name, line)
+    assert {C.launch_name(reach[(c.name, "auto")][0]) for c in cases} == set(C.TATTN_ROUTES)
 
 
 def test_end_and_glue_kernels_are_reached(reach, fixture_names):

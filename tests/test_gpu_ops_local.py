@@ -196,6 +196,61 @@ def test_proj_qkv_refuses_ragged_frames(ops, NB):
     check(ops, C.proj_qkv_case(NB, 1), refusal="1 rows per GroupNorm domain")
 
 
+# ------------------------------------------------------------------ past one tile per workgroup
+# None of these kernels depends on the GEMM choice: each case runs once, not under the six variants.
+def check_local(case):
+    assert torch.cuda.is_available(), "gpu tests need a HIP device"
+    from lavie_amd import ops as o
+    oc.check_case(o, case, forced=tuple(_forced), sync=torch.cuda.synchronize)
+
+
+def _ids(cases):
+    return [c.name for c in cases]
+
+
+@pytest.mark.parametrize("case", C.multi_pass_cases() + C.multi_pass_cases(in_place=True), ids=_ids(C.multi_pass_cases() + C.multi_pass_cases(in_place=True)))
+def test_row_resident_blocks_past_one_pass(case):
+    """opcases.PATHS: second and later passes, idle waves, ragged and boundary-crossing passes under lavie_debug_rowfuse_grid, and the
+    production grid at 2049 pixels; the cap is back at 0 afterwards."""
+    check_local(case)
+    from lavie_amd import _lib
+    assert _lib.load().lavie_debug_rowfuse_grid(0) == 0
+
+
+@pytest.mark.parametrize("in_place", [False, True])
+def test_temporal_block_peaked(in_place):
+    check_local(C.temporal_block_case(2, 13, in_place, profile="peaked"))
+
+
+_TATTN_NEW = [c for c in C.temporal_attention_cases()
+              if c.name not in {C.temporal_attention_case(*sh, t).name for sh in C.TATTN_SHAPES for t in (False, True)}
+              and c.name not in {C.temporal_attention_case(1, 17, 5, 256, t, plain=True).name for t in (False, True)}]
+
+
+@pytest.mark.parametrize("case", _TATTN_NEW, ids=_ids(_TATTN_NEW))
+def test_temporal_attention_routes(case):
+    """every instantiation launch_temporal_attention can launch (opcases.TATTN_ROUTES), at each head split, several tiles per workgroup"""
+    check_local(case)
+
+
+_GN_NEW = [C.group_norm_case(**k) for k in C.GN_PAST_SLAB]
+
+
+@pytest.mark.parametrize("case", _GN_NEW, ids=_ids(_GN_NEW))
+def test_group_norm_past_one_slab(case):
+    check_local(case)
+
+
+def test_rowfuse_grid_hook_contract():
+    from lavie_amd import _lib
+    lib = _lib.load()
+    try:
+        assert lib.lavie_debug_rowfuse_grid(3) == 0 and lib.lavie_debug_rowfuse_grid(256) == 0
+        assert lib.lavie_debug_rowfuse_grid(257) != 0 and lib.lavie_debug_rowfuse_grid(-1) != 0
+    finally:
+        assert lib.lavie_debug_rowfuse_grid(0) == 0
+
+
 @pytest.mark.parametrize("n", C.STEP_LENGTHS)
 @pytest.mark.parametrize("kind", C.STEP_KINDS)
 def test_sampler_steps(ops, kind, n):

@@ -25,9 +25,10 @@ def test_fp32_model_meets_its_bound(case):
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "lavie_hip.h")
 REPLAYED = ("linear", "linear_lnfold", "linear_lnfold_geglu", "conv3x3", "conv3x3_down", "upsample_conv3x3", "temporal_conv",   # driver.cpp run_optrace
             "timestep_sinusoid", "gemv", "pack_conv_in", "conv_in", "pack_conv_out", "conv_out", "add_class_emb_silu", "fill_relpos_bias", "ln_fold",
-            "pack_geglu_vec", "copy_rows", "f16_to_f32")
+            "pack_geglu_vec", "copy_rows", "f16_to_f32",
+            "geglu_mlp", "temporal_block", "cross_block", "cross_block_long", "proj_qkv", "temporal_attention", "group_norm", "group_norm_affine")
 OPTIONAL = ("bias", "bias2", "R", "x2", "sc1", "sc2", "bias_f16", "b")
-ALWAYS = {"conv_in": ("bias",), "conv_out": ("bias",)}          # operands of the new entries that are not optional there
+ALWAYS = {"conv_in": ("bias",), "conv_out": ("bias",), "temporal_attention": ("bias",)}          # operands of the new entries that are not optional there
 
 
 def abi_parameters(entry):
@@ -44,6 +45,8 @@ class RecordingLib:
         self.recorded = []
 
     def __getattr__(self, name):
+        if name.endswith(("_image_bytes", "_bias_floats", "_ws_floats")):          # size queries of the pack steps: any size will do
+            return lambda *args: 64
         return lambda *args: self.recorded.append((name, args)) or 0
 
 
@@ -453,6 +456,183 @@ def test_every_listed_case_of_the_end_families_is_present():
                                                   "timestep_sinusoid": 3, "add_class_emb_silu": 3, "fill_relpos_bias": 6}
     assert len({c.name for cs in fam.values() for c in cs}) == sum(len(v) for v in fam.values())
     assert {c.name for cs in fam.values() for c in cs} <= {c.name for c in CASES}
+
+
+# ------------------------------------------------------------------ past one tile per workgroup: paths, routes, slabs
+def test_multi_pass_cases_contain_every_path():
+    """The share-rule mirror (opcases.rowfuse_walk) on every capped and natural-grid block case: the case set as a whole contains
+    every path of opcases.PATHS, per block, and the candidates that do not are known not to."""
+    got = {}
+    for case in C.multi_pass_cases() + C.multi_pass_cases(in_place=True):
+        fam, walk, paths = C.case_walk(case)
+        got.setdefault(fam, set()).update(paths)
+        assert sorted(t for t, _ in enumerate(walk)) == list(range(len(walk)))
+    assert set(got) == set(C.PATHS)
+    for fam, need in C.PATHS.items():
+        assert need <= got[fam], (fam, sorted(need - got[fam]))
+    # the share rule itself, on the figures of the kernels' comments: 81920 rows on 256 workgroups = 20 tiles each = passes 8 + 8 + 4
+    walk = C.rowfuse_walk(81920 // 16, 256)
+    assert [sum(1 for w, p, _ in walk if (w, p) == (0, k)) for k in range(3)] == [8, 8, 4] and max(p for _, p, _ in walk) == 2
+    walk = C.rowfuse_walk(50, 3)
+    assert [sum(1 for w, _, _ in walk if w == b) for b in range(3)] == [17, 17, 16] and walk[49] == (2, 1, 7) and walk[16] == (0, 2, 0)
+    # B = 2, D = 25 cuts its passes at the video boundary and B = 4, P = 208 has equal pass counts: why neither is the case used
+    assert "pass_spans_batches" not in C.walk_paths(C.rowfuse_walk(50, 3), batch_of=lambda t: t // 25)
+    assert "pass_counts_differ" not in C.walk_paths(C.rowfuse_walk(52, 3, 13), batch_of=lambda t: t // 13)
+    # cross_block: workgroup 0's second pass is cut at the end of video 0 and its third streams video 1's image
+    walk = C.rowfuse_walk(56, 3, 14)
+    assert [walk[t] for t in (7, 8, 13, 14, 18, 19, 27, 28)] == [(0, 0, 7), (0, 1, 0), (0, 1, 5), (0, 2, 0), (0, 2, 4), (1, 0, 0), (1, 1, 0), (1, 2, 0)]
+    # the natural-grid case: 2049 pixels on 256 workgroups, workgroup 0 alone has a second pass
+    fam, walk, _ = C.case_walk(C.temporal_block_case(3, 683, False))
+    assert fam == "temporal_block" and len(walk) == 2049 and walk[8] == (0, 1, 0) and walk[9] == (1, 0, 0)
+    assert C.temporal_block_case(3, 683, False).name.startswith(C.NATURAL_GRID)
+
+
+def test_temporal_cases_reach_every_route_and_walk_several_tiles():
+    """temporal_route on every temporal attention case: the reached set is TATTN_ROUTES; every streaming instantiation runs at
+    each head split of the models' widths, with a masked tail and without, and in at least one case with a workgroup of three
+    tiles beside one of two; the tile kernel runs forced and unforced, with a ragged pixel tile and with a halved head group."""
+    cases = C.temporal_attention_cases()
+    assert len({c.name for c in cases}) == len(cases) and {c.name for c in cases} <= {c.name for c in CASES}
+    routes = {}
+    for c in cases:
+        routes.setdefault(c.troute["kernel"], []).append(c)
+    assert set(routes) == set(C.TATTN_ROUTES), sorted(set(routes) ^ set(C.TATTN_ROUTES))
+    dims = lambda c: dict(c.calls[0][1])
+    for name, cs in routes.items():
+        if name.startswith("temporal_stream_kernel"):
+            group = int(name.split(",")[1])
+            splits = {c.troute["heads_per_group"] for c in cs if dims(c)["heads"] == 8}
+            assert splits >= ({8, 4, 2} if group >= 256 else {4, 2, 1}), (name, splits)
+            multi = [c for c in cs if c.troute["fullest"] >= 3 and c.troute["emptiest"] < c.troute["fullest"]]
+            assert len(multi) == C.TATTN_MULTI[name] >= 1, (name, [c.name for c in multi])
+            assert any(dims(c)["B"] >= 2 and c.troute["tiles"] // dims(c)["B"] < c.troute["per_group"] * 2 for c in multi)     # the walk crosses a video
+            frames = {dims(c)["F"] for c in cs}
+            need = {17, 61, 64} if name.startswith("temporal_stream_kernel<4") else {8, 5} if name.endswith("2>") else {16, 13}
+            assert need <= frames, (name, frames)
+        else:
+            forced = [c for c in cs if c.knobs.get("temporal_budget")]
+            natural = [c for c in cs if not c.knobs.get("temporal_budget")]
+            assert forced and natural, name
+            assert any(dims(c)["D"] % c.troute["PT"] for c in cs) and any(c.troute["HG"] < dims(c)["heads"] for c in cs), name
+    peaked = [c for c in CASES if c.name.endswith(",peaked]") or ",peaked]" in c.name]
+    assert {c.troute["kernel"] for c in peaked if hasattr(c, "troute")} == {"temporal_stream_kernel<1, 320, 1>", "temporal_stream_kernel<4, 160, 1>"}
+    assert any(c.name.startswith("temporal_block") for c in peaked)
+    assert C.peaked_rows(16) == [5] and C.peaked_rows(17) == [5, 16] and C.peaked_rows(64) == [5, 21, 37, 53]
+
+
+def test_group_norm_cases_run_past_one_slab():
+    """opcases.gn_slabs / gn_geometry on the GroupNorm cases: three slabs with a ragged last one, the cap_total / NB clamp with more
+    than one whole unrolled iteration and a remainder, two sources and the affine form past one slab, every geometry of GN_WIDTHS."""
+    old = [C.group_norm_case(**k) for k in C.GN_CASES]
+    new = [C.group_norm_case(**k) for k in C.GN_PAST_SLAB]
+    shape = lambda c: (C.gn_geometry(c.gn[2]), C.gn_slabs(c.gn[1], c.gn[0], C.gn_geometry(c.gn[2])[2]))
+    assert all(shape(c)[1][0] <= 2 and not shape(c)[1][2] for c in old)              # what the suite had: one slab (two at ty = 1), never clamped
+    for c in new:
+        (tx, vpt, ty), (slabs, rps, clamped) = shape(c)
+        nb, P, _ = c.gn
+        assert slabs >= 2 and P % rps != 0, c.name                                    # more than one slab, the last ragged
+        assert slabs >= 3 or clamped, c.name
+    clamped = [c for c in new if shape(c)[1][2]]
+    assert clamped
+    for c in clamped:
+        (_, _, ty), (slabs, rps, _) = shape(c)
+        last = c.gn[1] - (slabs - 1) * rps
+        per_lane = last // ty
+        assert rps // (ty * C.GN_UNROLL) >= 2 and per_lane // C.GN_UNROLL >= 1 and per_lane % C.GN_UNROLL, c.name      # whole iterations and a remainder
+        assert (last // ty) // C.GN_UNROLL >= 2, c.name
+    assert {C.gn_geometry(w) for w in C.GN_WIDTHS} <= {shape(c)[0] for c in new}
+    assert {C.gn_geometry(w)[1:] for w in C.GN_WIDTHS} == {(1, 8), (1, 6), (1, 4), (1, 3), (1, 2), (1, 1), (2, 1)}
+    assert any(c.calls[0][1].get("x2") for c in new) and any(c.calls[0][0] == "group_norm_affine" for c in new)
+    assert C.gn_slabs(10, 2, 6) == (1, 24, False) and C.gn_slabs(23, 700, 1) == (2, 12, True) and C.gn_slabs(4096, 2, 6)[0] == 171
+
+
+# ------------------------------------------------------------------ injected defects past the first tile of a workgroup
+def bad_rows(case, got, k="y"):
+    return offenders(case, got, k).any(1).nonzero().flatten().tolist()
+
+
+def test_geglu_mlp_second_pass_with_the_first_passes_residual():
+    """Workgroup 1 of the capped case adds, in its second pass, the residual rows it loaded for its first (R[] not renewed): the
+    rows of tiles 25..32 = 400..527 carry x[row - 128] instead of x[row].  Caught at exactly those 128 rows.  Not a defect rel-L2
+    passes: a sixth of the rows is off by a whole residual — asserted as what it is."""
+    case = C.geglu_mlp_case(795, False, cap=3)
+    _, walk, _ = C.case_walk(case)
+    tiles = [t for t, (w, p, _) in enumerate(walk) if (w, p) == (1, 1)]
+    assert tiles == list(range(25, 33))
+    rows = [16 * t + r for t in tiles for r in range(16)]
+    y, x = case.model()["y"], case.inputs["x"].float()
+    bad = y.clone()
+    bad[rows] = (y[rows].float() - x[rows] + x[[r - 128 for r in rows]]).half()
+    with pytest.raises(AssertionError, match=r"geglu_mlp\[M795,cap3\]"):
+        case.check({"y": bad})
+    assert bad_rows(case, bad) == rows
+    assert rel_l2(bad, case.ref["y"][0]) > 100 * TOL_OP
+
+
+def test_cross_block_tiles_behind_the_video_boundary_on_the_previous_image():
+    """Workgroup 0's third pass (tiles 14..18, the first of video 1) computed against video 0's K | V — `imgb` not moved on after
+    the cut pass.  Caught at exactly those 80 rows, for the short and the long variant.  Not a defect rel-L2 passes at this size:
+    80 rows of 896 with another video's attention term measure 4e-2 against TOL_OP = 2e-3 — asserted as what it is."""
+    for L in (77, 160):
+        case = C.cross_block_case(4, 224, L, False, cap=3)
+        _, walk, _ = C.case_walk(case)
+        tiles = [t for t, (w, p, _) in enumerate(walk) if (w, p) == (0, 2)]
+        assert tiles == list(range(14, 19))
+        rows = [16 * t + r for t in tiles for r in range(16)]
+        y = case.model()["y"]
+        stale = case.chain(lambda t: t.float(), C.h_, video_of=(0, 0, 2, 3))["y"][0].half()
+        bad = y.clone()
+        bad[rows] = stale[rows]
+        with pytest.raises(AssertionError, match="cross_block"):
+            case.check({"y": bad})
+        assert bad_rows(case, bad) == rows
+        assert rel_l2(bad, case.ref["y"][0]) > 5 * TOL_OP
+
+
+def test_temporal_stream_third_tile_stored_to_the_second_tiles_rows():
+    """temporal_stream_kernel<1, 320, 1> at C = 1280, B = 2, D = 129, F = 13: head group 0's workgroup 0 walks tiles 0, 128, 256 =
+    (video 0, pixel 0), (0, 128), (1, 127).  Its third tile's output lands on the second tile's rows (obase taken from the previous
+    n) and its own rows keep what they held (zeros here; on the GPU the poison, which run_guarded reports as never written).
+    Caught at exactly the 2 x 13 rows of the two tiles, in the 320 columns of head group 0."""
+    b, f, dd, c = 2, 13, 129, 1280
+    case = C.temporal_attention_case(b, f, dd, c, False)
+    rt = case.troute
+    assert rt["kernel"] == "temporal_stream_kernel<1, 320, 1>" and (rt["per_group"], rt["tiles"], rt["fullest"]) == (128, 258, 3)
+    walk = list(range(0, rt["tiles"], rt["per_group"]))
+    assert walk == [0, 128, 256]
+    rows_of = lambda t: [((t // dd) * f + fr) * dd + t % dd for fr in range(f)]
+    second, third = rows_of(walk[1]), rows_of(walk[2])
+    y = case.model()["y"]
+    bad = y.clone()
+    bad[second, :320] = y[third, :320]
+    bad[third, :320] = 0
+    with pytest.raises(AssertionError, match="temporal_attention"):
+        case.check({"y": bad})
+    off = offenders(case, bad)
+    assert off.any(1).nonzero().flatten().tolist() == sorted(second + third)
+    assert not off[:, 320:].any() and off[sorted(second + third), :320].float().mean() > 0.9
+    assert rel_l2(bad, case.ref["y"][0]) > 10 * TOL_OP            # 26 rows of 3354, each wholly wrong in a quarter of its columns: 5e-2
+
+
+def test_group_norm_last_slab_left_out_of_the_sums():
+    """gn_finalize_kernel folds slabs - 1 partials of batch entry 1 (61 rows = slabs of 24, 24 and 13): sums over 48 rows divided by
+    the count of 61.  Every row of batch entry 1 is off and no row of batch entry 0."""
+    case = C.group_norm_case(nb=2, P=61, c1=320, tag="slabs:")
+    (_, _, ty), (slabs, rps, _) = C.gn_geometry(320), C.gn_slabs(61, 2, 6)
+    assert (slabs, rps) == (3, 24)
+    x, gamma, beta = case.inputs["x1"].float().reshape(2, 61, 32, 10), case.inputs["gamma"], case.inputs["beta"]
+    part = x[1, :(slabs - 1) * rps]
+    cnt = 61.0 * 10
+    mean = part.sum((0, 2)) / cnt
+    var = ((part * part).sum((0, 2)) / cnt - mean * mean).clamp_min(0)
+    a = (var + 1e-5).rsqrt().repeat_interleave(10) * gamma
+    bb = beta - mean.repeat_interleave(10) * a
+    bad = case.model()["y"].clone()
+    bad[61:] = torch.nn.functional.silu(case.inputs["x1"][61:].float() * a + bb).half()
+    with pytest.raises(AssertionError, match="group_norm"):
+        case.check({"y": bad})
+    assert bad_rows(case, bad) == list(range(61, 122))
+    assert rel_l2(bad, case.ref["y"][0]) > 10 * TOL_OP            # a fifth of the rows missing from the statistics: not a defect rel-L2 passes
 
 
 # ------------------------------------------------------------------ bands and poison, on CPU tensors
