@@ -14,6 +14,8 @@
 #include <string>
 #include <vector>
 
+#include <unistd.h>
+
 #include "../../../include/lavie_hip.h"
 
 extern "C" long lavie_hostcheck_launches();
@@ -387,7 +389,7 @@ static void run_traces(const char* path) {
 // its integer arguments under the names of include/lavie_hip.h, 0 / 1 for each optional operand (bias, bias2, R, x2, sc1, sc2) and
 // force_tile / force_splits (default 0); the end and glue kernels' entries (timestep_sinusoid ... f16_to_f32) and the pack / bind steps
 // of the row-resident blocks (pack_geglu_mlp, bind_cross_block[_long]: pack + bind) likewise, and the blocks themselves (geglu_mlp, temporal_block,
-// cross_block[_long], proj_qkv), temporal_attention and group_norm[_affine] on exactly sized buffers, under rowfuse_grid / temporal_budget (default 0).  Tensors are never read.  OUT: "== <line>", then the stub's launch lines of that call, or
+// cross_block[_long], proj_qkv), temporal_attention, group_norm[_affine], conv_edge_in / conv_edge_out and attention on exactly sized buffers, under rowfuse_grid / temporal_budget (default 0).  Tensors are never read.  OUT: "== <line>", then the stub's launch lines of that call, or
 // "!! refused" where the library returns an error (its message goes to stderr).  A line the driver cannot parse ends the run.
 static int run_optrace(const char* in_path, const char* out_path) {
     FILE* in = fopen(in_path, "r");
@@ -571,6 +573,26 @@ static int run_optrace(const char* in_path, const char* out_path) {
                              : lavie_group_norm_f16(x1.data(), C1, O("x2") ? x2.data() : nullptr, C2, NB, Pr, groups, v.data(), v.data(), 1e-5f, silu, ws.data(),
                                                     y.data(), nullptr);
                 }
+            } else if (entry == "conv_edge_in" || entry == "conv_edge_out") {     // the autoencoder's kernels: exactly sized buffers as well
+                const bool in = entry == "conv_edge_in";
+                const int dt = I(in ? "x_dtype" : "y_dtype"), N = I("N"), Cin = I("Cin"), Hh = I("H"), Ww = I("W"), Cout = I("Cout");
+                if (!missing) {
+                    const size_t px = (size_t)N * Hh * Ww, cmax = (size_t)(Cin > Cout ? Cin : Cout), cmin = (size_t)(Cin < Cout ? Cin : Cout);
+                    const long long oh = in ? 0 : lavie_conv_edge_out_image_halfs(Cin);
+                    std::vector<unsigned short> rows(px * cmax), wp(in ? (size_t)9 * ((Cin + 1) & ~1) * Cout : (size_t)(oh > 0 ? oh : 1));
+                    std::vector<float> img(px * cmin), b((size_t)Cout), tb((size_t)9 * Cout);      // the NCHW side, large enough in either dtype
+                    rc = in ? lavie_conv_edge_in_f16(img.data(), dt, wp.data(), O("bias") ? b.data() : nullptr, O("tap_bias") ? tb.data() : nullptr,
+                                                     rows.data(), N, Cin, Hh, Ww, Cout, nullptr)
+                            : lavie_conv_edge_out_f16(rows.data(), wp.data(), O("bias") ? b.data() : nullptr, img.data(), dt, N, Cin, Hh, Ww, Cout, nullptr);
+                }
+            } else if (entry == "attention") {
+                const int ldq = I("ldq"), ldk = I("ldk"), ldv = I("ldv"), ldo = I("ldo"), NB = I("NB"), Lq = I("Lq"), Lk = I("Lk"), heads = I("heads"),
+                          dh = I("dh"), div = I("kv_batch_div");
+                if (!missing) {
+                    const size_t rq = (size_t)NB * Lq, rk = (size_t)(div > 0 ? NB / div : NB) * Lk;
+                    std::vector<unsigned short> q(rq * ldq), k(rk * ldk), v(rk * ldv), o(rq * ldo);
+                    rc = lavie_attention_f16(q.data(), ldq, k.data(), ldk, v.data(), ldv, o.data(), ldo, NB, Lq, Lk, heads, dh, div, 0.05f, nullptr);
+                }
             } else {
                 fprintf(stderr, "hostcheck optrace: unknown entry point '%s'\n", entry.c_str());
                 return 2;
@@ -594,6 +616,45 @@ static int run_optrace(const char* in_path, const char* out_path) {
     fclose(in);
     printf("hostcheck: optrace written (%d calls, %ld stubbed kernel launches)\n", calls, lavie_hostcheck_launches());
     return 0;
+}
+
+static int run_optrace(const char* in_path, const char* out_path);
+
+// The autoencoder's kernels past one workgroup, through the optrace entries themselves (tests/opcases.py vae_cases(): the integers of
+// the largest case of each kernel): exactly sized buffers under the sanitizers, and the launches the walk mirrors of opcases.py state.
+static void run_vae_optrace() {
+    char in_path[] = "/tmp/hostcheck_in_XXXXXX", out_path[] = "/tmp/hostcheck_out_XXXXXX";
+    const int fi = mkstemp(in_path), fo = mkstemp(out_path);
+    REQUIRE(fi >= 0 && fo >= 0);
+    close(fo);
+    FILE* in = fdopen(fi, "w");
+    REQUIRE(in != nullptr);
+    fputs("conv_edge_out y_dtype=1 N=1 Cin=128 H=257 W=513 Cout=3 bias=1\n"
+          "conv_edge_out y_dtype=0 N=1 Cin=8 H=257 W=513 Cout=8 bias=1\n"
+          "conv_edge_out y_dtype=0 N=2 Cin=40 H=7 W=9 Cout=3 bias=1\n"
+          "conv_edge_in x_dtype=0 N=1 Cin=4 H=129 W=128 Cout=512 bias=1 tap_bias=1\n"
+          "conv_edge_in x_dtype=1 N=1 Cin=3 H=129 W=128 Cout=512 bias=1 tap_bias=0\n"
+          "attention ldq=3088 ldk=3088 ldv=3088 ldo=1024 NB=3 Lq=129 Lk=129 heads=2 dh=512 kv_batch_div=1\n"
+          "attention ldq=528 ldk=1040 ldv=1040 ldo=512 NB=4 Lq=40 Lk=97 heads=1 dh=512 kv_batch_div=2\n"
+          "attention ldq=784 ldk=784 ldv=784 ldo=256 NB=1 Lq=161 Lk=161 heads=1 dh=256 kv_batch_div=1\n"
+          "conv_edge_out y_dtype=0 N=1 Cin=12 H=2 W=2 Cout=3 bias=1\n", in);
+    fclose(in);
+    REQUIRE(run_optrace(in_path, out_path) == 0);
+    FILE* out = fopen(out_path, "r");
+    REQUIRE(out != nullptr);
+    std::string got;
+    char line[1024];
+    while (fgets(line, sizeof(line), out)) got += line;
+    fclose(out);
+    unlink(in_path);
+    unlink(out_path);
+    for (const char* want : {"conv_edge_out_kernel<4, float> 1031,1,1 256,1,1", "conv_edge_out_kernel<0, half> 1031,1,1 256,1,1", "conv_edge_out_kernel<0, half> 2,1,1",
+                             "conv_edge_in_kernel<half> 4096,1,1 256,1,1", "conv_edge_in_kernel<float> 4096,1,1 256,1,1", "attention_wide_kernel<512> 12,1,1 256,1,1",
+                             "attention_wide_kernel<512> 4,1,1", "attention_wide_kernel<256> 2,1,1", "Cout=3 bias=1\n!! refused"})
+        if (got.find(want) == std::string::npos) {
+            fprintf(stderr, "hostcheck: the optrace of the autoencoder's kernels lacks '%s':\n%s", want, got.c_str());
+            exit(2);
+        }
 }
 
 int main(int argc, char** argv) {
@@ -916,6 +977,7 @@ int main(int argc, char** argv) {
         REQUIRE(lavie_f16_to_f32(d, nullptr, f.data(), 0, nullptr) != 0 && lavie_f16_to_f32(nullptr, nullptr, f.data(), 4, nullptr) != 0);
         REQUIRE(lavie_hostcheck_launches() == accepted);
     }
+    run_vae_optrace();
     REQUIRE(lavie_upsample_conv3x3_supported(320, 32, 20, 32) >= 0);
     int buckets[16 * 16];
     REQUIRE(lavie_relpos_buckets(16, 32, 32, buckets) == 0);

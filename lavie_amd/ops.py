@@ -36,6 +36,13 @@ def _chk32(*ts):
             raise ValueError("expected contiguous fp32 device tensors")
 
 
+def _chk_cols16(*ts):
+    """attention operands: column slices of wider row-major tensors are taken"""
+    for t in ts:
+        if not (t.is_cuda and t.dtype == torch.float16 and t.stride(1) == 1):
+            raise ValueError("attention operands must be fp16 device tensors with unit column stride")
+
+
 def _out(out, shape, dtype, device, what):
     """The caller's output tensor after the checks every `out=` gets (device, dtype, contiguity, exact shape), or a new one."""
     if out is None:
@@ -438,9 +445,7 @@ def layer_norm(x, gamma, beta, eps=1e-5, out=None):
 
 def attention(q, k, v, nb, lq, lk, heads, kv_batch_div=1, scale=None, out=None):
     """q [nb*lq, *], k/v [(nb/kv_batch_div)*lk, *] may be column slices of wider row-major tensors."""
-    for t in (q, k, v):
-        if not (t.is_cuda and t.dtype == torch.float16 and t.stride(1) == 1):
-            raise ValueError("attention operands must be fp16 device tensors with unit column stride")
+    _chk_cols16(q, k, v)
     c = q.shape[1]
     dh = c // heads
     o = _out(out, (nb * lq, c), torch.float16, q.device, "attention: out")
@@ -454,9 +459,7 @@ def attention(q, k, v, nb, lq, lk, heads, kv_batch_div=1, scale=None, out=None):
 def sparse_causal_attention(q, k, v, nb, frames, d, heads, scale=None, out=None):
     """SparseCausalAttention core (interpolation/models/attention.py:609-665): q/k/v [nb*d, *] per-frame rows (column
     slices of a wider tensor allowed); frame f of a video attends to [first frame || frame max(f-1, 0)] of that video."""
-    for t in (q, k, v):
-        if not (t.is_cuda and t.dtype == torch.float16 and t.stride(1) == 1):
-            raise ValueError("attention operands must be fp16 device tensors with unit column stride")
+    _chk_cols16(q, k, v)
     c = q.shape[1]
     dh = c // heads
     o = _out(out, (nb * d, c), torch.float16, q.device, "sparse_causal_attention: out")

@@ -558,6 +558,51 @@ TCONV_SHAPES = [(1, 64, 64, 1, 7), (1, 64, 64, 2, 7), (3, 128, 64, 2, 7), (2, 64
 EDGE_IN = [(1, 3, 128, 1, 1), (1, 4, 512, 3, 5), (2, 8, 128, 7, 9)]
 EDGE_OUT = [(1, 128, 3, 1, 1), (1, 256, 4, 3, 5), (2, 512, 8, 7, 9)]
 
+# Past the first quad of a workgroup and the first grid-stride step.  The cases above have at most 126 pixels: conv_edge_out then runs
+# 8 tiles = 2 workgroups of one quad (4 waves x 16 pixels) each, conv_edge_in 126 x Cout / 8 items on at most 32 workgroups of one step.
+# edge_out_walk / edge_in_walk mirror the two launchers; each shape is the smallest that takes its path on the production grid.
+#  case                                       walk                                               path it provides
+#  conv_edge_out 1x128->3, 257x513, fp32      131841 pixels, 8241 tiles, 2061 quads, 2 a         <4, float>: every workgroup but the last walks two quads; the last (1030) has one
+#                                             workgroup, grid 1031                               tile of one pixel in wave 0, three waves that break at q = 0, all four breaking at q = 1
+#  conv_edge_out 1x8->8, 257x513, fp16        the same walk                                      <0, half_t>: the rolled loop with a single, partly guarded channel block (kq >= 1: no channel)
+#  conv_edge_out 2x40->{3,8}, 7x9, both       126 pixels, 2 workgroups                           <0, *> with two channel blocks, the last of 8 channels
+#  conv_edge_out 1x{128,256,512}->{3,4,8}, 20x16   320 pixels = 5 quads, 5 workgroups            the unrolled widths with four waves on interior pixels, all nine taps present
+#  conv_edge_in 1x4->512, 129x128, fp16, tap  16512 x 64 = 1056768 items on 4096 workgroups      workgroups 0..31 take a second grid-stride step: items >= 1048576 = pixels >= 16384 = the
+#  conv_edge_in 1x3->512, 129x128, fp32       the same                                           bottom image row, whose three lower taps and their tap biases fall outside the image
+# (n, cin, cout, h, w, dtype, tap)
+EDGE_IN_PAST = [(1, 4, 512, 129, 128, f16, True), (1, 3, 512, 129, 128, f32t, False)]
+# (n, cin, cout, h, w, dtype)
+EDGE_OUT_PAST = ([(1, 128, 3, 257, 513, f32t), (1, 8, 8, 257, 513, f16)] + [(2, 40, co, 7, 9, dt) for co, dt in ((3, f16), (8, f32t))]
+                 + [(1, 128, 3, 20, 16, f16), (1, 256, 4, 20, 16, f32t), (1, 512, 8, 20, 16, f16)])
+EDGE_OUT_TILE, EDGE_OUT_MAX_WG, EDGE_IN_MAX_WG = 16, 2048, 4096
+
+
+def edge_out_walk(M):
+    """conv_edge.hip launch_edge_out: (grid, quads_per_wg) for M pixels.  Workgroup b walks quads b * per .. b * per + per - 1, wave w of
+    quad q the tile 4 q + w, and leaves the loop at the first tile >= ntiles."""
+    ntiles = -(-M // EDGE_OUT_TILE)
+    quads = -(-ntiles // 4)
+    per = -(-quads // EDGE_OUT_MAX_WG)
+    return -(-quads // per), per
+
+
+def edge_out_tiles(M):
+    """tile -> (workgroup, step q, wave), and per workgroup the step at which each wave breaks (None: it runs all quads_per_wg steps)"""
+    grid, per = edge_out_walk(M)
+    ntiles = -(-M // EDGE_OUT_TILE)
+    where = {(b * per + q) * 4 + w: (b, q, w) for b in range(grid) for q in range(per) for w in range(4) if (b * per + q) * 4 + w < ntiles}
+    assert sorted(where) == list(range(ntiles))
+    breaks = {b: [next((q for q in range(per) if (b * per + q) * 4 + w >= ntiles), None) for w in range(4)] for b in range(grid)}
+    return where, breaks
+
+
+def edge_in_walk(M, cout):
+    """conv_edge.hip launch_conv_edge_in: (grid, [steps of each workgroup's fullest thread]) for M pixels: items = M * cout / 8, 256 a
+    workgroup and step, at most EDGE_IN_MAX_WG workgroups, item idx = (step * grid + workgroup) * 256 + thread = pixel * (cout / 8) + group"""
+    total = M * (cout // 8)
+    grid = min(-(-total // 256), EDGE_IN_MAX_WG)
+    return grid, [len(range(b * 256, total, grid * 256)) for b in range(grid)]
+
 
 @functools.lru_cache(maxsize=None)
 def edge_in_case(n, cin, cout, h, w, dtype, tap):
@@ -583,10 +628,12 @@ def edge_in_case(n, cin, cout, h, w, dtype, tap):
         return rows(y)
 
     c = oc.gemm_c(9 * cin + 10)
-    return Case(f"conv_edge_in[{n}x{cin}->{cout},{h}x{w},{str(dtype)[6:]},tap{int(tap)}]", ins, {"y": ((n * h * w, cout), f16)}, run,
+    case = Case(f"conv_edge_in[{n}x{cin}->{cout},{h}x{w},{str(dtype)[6:]},tap{int(tap)}]", ins, {"y": ((n * h * w, cout), f16)}, run,
                 lambda: {"y": (terms(d, False), terms(d, True))}, c,
                 lambda: {"y": terms(lambda t: t.float(), False).half()}, oc.loc_image(n, h, w, cout),
                 regions={"border": border_mask(n, h, w, cout)})
+    case.edge = (n * h * w, cout)
+    return local_calls(case, [call("conv_edge_in", x_dtype=dtype == f32t, N=n, Cin=cin, H=h, W=w, Cout=cout, bias=1, tap_bias=bool(tap))])
 
 
 @functools.lru_cache(maxsize=None)
@@ -607,9 +654,12 @@ def edge_out_case(n, cin, cout, h, w, dtype):
     border = torch.ones(n, cout, h, w, dtype=torch.bool)
     if h > 2 and w > 2:
         border[:, :, 1:-1, 1:-1] = False
-    return Case(f"conv_edge_out[{n}x{cin}->{cout},{h}x{w},{str(dtype)[6:]}]", ins, {"y": ((n, cout, h, w), dtype)}, run,
+    case = Case(f"conv_edge_out[{n}x{cin}->{cout},{h}x{w},{str(dtype)[6:]}]", ins, {"y": ((n, cout, h, w), dtype)}, run,
                 lambda: {"y": (terms(d, False), terms(d, True))}, oc.gemm_c(9 * cin + 1),
-                lambda: {"y": terms(lambda t: t.float(), False).to(dtype)}, oc.loc_nchw(cout, h, w), regions={"border": border.reshape(-1)})
+                lambda: {"y": terms(lambda t: t.float(), False).to(dtype)}, oc.loc_nchw(cout, h, w), regions={"border": border.reshape(-1)},
+                u=oc.U32 if dtype == f32t else oc.U16)       # the relative term is the output format's unit roundoff (opcheck.py)
+    case.edge = (n * h * w, cin)
+    return local_calls(case, [call("conv_edge_out", y_dtype=dtype == f32t, N=n, Cin=cin, H=h, W=w, Cout=cout, bias=1)])
 
 
 # ------------------------------------------------------------------ norms
@@ -724,6 +774,10 @@ GN_PAST_SLAB = [dict(nb=2, P=61, c1=320, tag="slabs:"), dict(nb=2, P=61, c1=320,
                 dict(nb=2, P=61, c1=320, silu=False, eps=1e-6, tag="slabs:"), dict(nb=1, P=11, c1=1280, c2=640, tag="slabs:"),
                 dict(nb=1, P=11, c1=1280, c2=1280, tag="slabs:"), dict(nb=700, P=23, c1=1280, tag="clamp:")]
 GN_PAST_SLAB += [dict(nb=2, P=2 * 4 * gn_geometry(w)[2] + gn_geometry(w)[2] + 1, c1=w, tag="width:") for w in GN_WIDTHS if w not in (320,)]
+# The autoencoder's width: 128 channels = 4 a group, half a 16-byte vector (gn_geometry(128) = (16, 1, 16): 16 row lanes), eps = 1e-6; in no
+# list above.  The same P rule: 2 x 145 rows = slabs of 64 / 64 / 17.  silu1: the resnet norms of the decoder's last level; silu0: the
+# form of the mid block's attention norm
+GN_VAE = [dict(nb=2, P=2 * 4 * gn_geometry(128)[2] + gn_geometry(128)[2] + 1, c1=128, silu=s_, eps=1e-6, tag="vae:") for s_ in (True, False)]
 GN_CASES = [dict(nb=1, P=3, c1=64, tag="video:"), dict(nb=2, P=10, c1=320, tag="video:"),
             dict(nb=3, P=5, c1=320, silu=False, eps=1e-6, tag="frame:"), dict(nb=1, P=6, c1=1280, c2=640, tag="straddle:"),
             dict(nb=2, P=10, c1=320, affine=True), dict(nb=2, P=10, c1=320, offset=8.0, tag="offset:")]
@@ -832,14 +886,19 @@ ATT_ROUTES = ([f"dma<{n},QT{qt},V2,4 waves>" for n in (4, 5, 8, 10) for qt in (1
 PROFILES = ["far_below", "dominant_last", "creep", "mixed_wave"]
 
 
-def profile_applies(profile, lq, lk):
-    """lk: the keys of one key sequence that can be placed freely (sparse-causal: the d tokens of a frame)."""
+def key_tile(dh):
+    """keys per tile of the kernel that serves head dim dh: attention_wide.hip AW_KEYS = 32 at 256 / 512, attention.hip's 64 below"""
+    return 32 if dh in (256, 512) else 64
+
+
+def profile_applies(profile, lq, lk, tile=64):
+    """lk: the keys of one key sequence that can be placed freely (sparse-causal: the d tokens of a frame); tile: keys per key tile."""
     if profile == "far_below":
-        return lk > 64                       # a whole first key tile below, the matching key behind it
+        return lk > tile                     # a whole first key tile below, the matching key behind it
     if profile == "creep":
-        return lk > 128                      # three key tiles
+        return lk > 2 * tile                 # three key tiles
     if profile == "mixed_wave":
-        return lk > 65 and lq >= 32          # its matching key is lk - 2 (lk - 1 is the dominant one) and must lie behind the first tile
+        return lk > tile + 1 and lq >= 32    # its matching key is lk - 2 (lk - 1 is the dominant one) and must lie behind the first tile
     return lk >= 2
 
 
@@ -856,10 +915,11 @@ def hard_rows(lq):
 MIXED_ROWS = (18, 27)        # mixed_wave: (the dominant_last row, the far_below row), both in the 16-row group 1
 
 
-def apply_profile(profile, g, q, k, dh, qsrc, first64):
+def apply_profile(profile, g, q, k, dh, qsrc, first64, tile=64):
     """Rewrites rows of q [nbq, lq, c] and k [nbk, lk, c] in place (heads packed along c).  qsrc[b]: the query batch entry whose
-    rows the dominant keys of key batch entry b are copied from; first64: the key batch entries whose keys 0..63 are the first
-    tile of a query.  Every constant is exact in fp16.  Returns what the case asserts on: far / creep rows (in every batch entry),
+    rows the dominant keys of key batch entry b are copied from; first64: the key batch entries whose keys 0..tile-1 are the first
+    tile of a query; tile: keys per key tile of the kernel (64, the default, leaves every older case its inputs bit for bit; 32 for
+    attention_wide.hip).  Every constant is exact in fp16.  Returns what the case asserts on: far / creep rows (in every batch entry),
     (key batch, row, key) triples of the dominant keys, and the index from the end of the key that matches a far_below row."""
     lq, lk, c = q.shape[1], k.shape[1], q.shape[2]
     u = (torch.randint(0, 2, (c,), generator=g) * 2 - 1).to(f16)           # one sign vector per head, side by side
@@ -868,7 +928,7 @@ def apply_profile(profile, g, q, k, dh, qsrc, first64):
 
     def far_below(rs, match):
         for b in first64:
-            k[b, :64] = (-1.25 * u.float() + 0.1 * torch.randn(64, c, generator=g)).half()
+            k[b, :tile] = (-1.25 * u.float() + 0.1 * torch.randn(tile, c, generator=g)).half()
         k[:, lk - match] = u
         # first-tile logits -20 sqrt(dh) nats (-25 sqrt(dh) below head dim 32, where -20 sqrt(dh) is above -100) as 16 x -1.25, not
         # 4 x -5: a key of magnitude 5 multiplies the rounding of Q' in the logits of the UNIT rows that see it, and the fp32 model
@@ -889,8 +949,8 @@ def apply_profile(profile, g, q, k, dh, qsrc, first64):
     elif profile == "creep":
         s = torch.tensor(5 / (math.sqrt(dh) * LOG2E)).half()
         q[:, rows] = u
-        for t in range(-(-lk // 64)):
-            k[:, min(64 * t + 3, lk - 1)] = ((t + 1) * s.float() * u.float()).half()
+        for t in range(-(-lk // tile)):
+            k[:, min(tile * t + 3, lk - 1)] = ((t + 1) * s.float() * u.float()).half()
         hard["creep"] = rows
     elif profile == "mixed_wave":
         far_below([MIXED_ROWS[1]], 2)
@@ -906,13 +966,13 @@ def apply_profile(profile, g, q, k, dh, qsrc, first64):
     return hard
 
 
-def assert_profile(hard, qh, kh, scale, dom_batches, creep_tiles, key0=0):
+def assert_profile(hard, qh, kh, scale, dom_batches, creep_tiles, key0=0, tile=64):
     """float64, on the values the kernel gets: qh [nb, heads, lq, dh], kh [nb, heads, keys, dh] as a query sees them; dom_batches:
     the query batch entries whose rows the dominant keys were copied from; key0: where the key sequence apply_profile wrote to
-    starts among the keys a query sees (sparse-causal: the previous-frame half)."""
+    starts among the keys a query sees (sparse-causal: the previous-frame half); tile: keys per key tile, as apply_profile got it."""
     s = d(qh) @ d(kh).transpose(-1, -2) * scale                             # nats
     if hard["far"]:
-        first, match = s[:, :, hard["far"], :64], s[:, :, hard["far"], s.shape[-1] - hard["match"]]
+        first, match = s[:, :, hard["far"], :tile], s[:, :, hard["far"], s.shape[-1] - hard["match"]]
         assert first.max() < -100 and match.min() > 0, (first.max().item(), match.min().item())
     for r, key in hard["dom"]:
         row = s[dom_batches, :, r]
@@ -920,14 +980,14 @@ def assert_profile(hard, qh, kh, scale, dom_batches, creep_tiles, key0=0):
         rest[..., [kk + o for _, kk in hard["dom"] for o in (0, key0)]] = -math.inf
         assert (row[..., key0 + key] - rest.max(-1).values).min() > 0, (r, key)      # it is the row's maximum
     if hard["creep"]:
-        tiles = F.pad(s[:, :, hard["creep"], :64 * creep_tiles], (0, max(64 * creep_tiles - s.shape[-1], 0)), value=-math.inf)
-        tiles = tiles.reshape(*s.shape[:2], len(hard["creep"]), creep_tiles, 64).max(-1).values * LOG2E     # best score per key tile
+        tiles = F.pad(s[:, :, hard["creep"], :tile * creep_tiles], (0, max(tile * creep_tiles - s.shape[-1], 0)), value=-math.inf)
+        tiles = tiles.reshape(*s.shape[:2], len(hard["creep"]), creep_tiles, tile).max(-1).values * LOG2E     # best score per key tile
         step = tiles[..., 1:] - tiles[..., :-1]
         assert step.min() > 3.0 and step.max() < 8.0 and (tiles[..., -1] - tiles[..., 0]).min() > 8.0, (step.min().item(), step.max().item())
 
 
 @functools.lru_cache(maxsize=None)
-def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8, profile="unit"):
+def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8, profile="unit", tile=64):
     """ops.attention on column slices of wider tensors whose other columns are NaN.  Self-attention (lk None): q | k | v are the
     thirds of one [nb*lq, 3c + 16] tensor; cross-attention: k | v are halves of a [(nb / kv_div) lk, 2c + 16] tensor.
     Rounding points: n = 3 at head dims up to 160 — Q' = fp16(Q scale log2 e) (attention.hip:437), P before the PV product
@@ -935,7 +995,8 @@ def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8, profile="unit"):
     300); n = 2 at head dims 256 / 512 (attention_wide.hip:345-346 and 398).  The round-3 softmax of the DMA kernel
     (attention.hip:638-687, P at :679-680) has no Q' rounding either: the model rounds Q' where attention_route says V2; the bound
     is round_c(3) for all of them.
-    profile: "unit" = N(0, 1) operands; the others (PROFILES, apply_profile) rewrite a few query rows and keys of those."""
+    profile: "unit" = N(0, 1) operands; the others (PROFILES, apply_profile) rewrite a few query rows and keys of those, laid out for
+    key tiles of `tile` keys (key_tile(dh) for the cases past one workgroup; the older wide cases keep 64 = two of that kernel's tiles)."""
     g = gen("attn", nb, lq, c, lk, kv_div, heads)
     dh = c // heads
     wide = dh > 160
@@ -945,9 +1006,9 @@ def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8, profile="unit"):
     q, k, v = rnd(g, nb * lq, c), rnd(g, nkv * lk_, c), rnd(g, nkv * lk_, c)
     hard = None
     if profile != "unit":
-        assert profile_applies(profile, lq, lk_), (profile, lq, lk_)
+        assert profile_applies(profile, lq, lk_, tile), (profile, lq, lk_, tile)
         hard = apply_profile(profile, gen("attn-profile", nb, lq, c, lk, kv_div, heads, profile), q.view(nb, lq, c), k.view(nkv, lk_, c),
-                             dh, [b * kv_div for b in range(nkv)], range(nkv))
+                             dh, [b * kv_div for b in range(nkv)], range(nkv), tile)
     nan = lambda r, w: torch.full((r, w), math.nan, dtype=f16)
     if cross:
         ins = {"qw": torch.cat([nan(nb * lq, 8), q, nan(nb * lq, 8)], 1), "kvw": torch.cat([k, nan(nkv * lk_, 16), v], 1)}
@@ -967,7 +1028,7 @@ def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8, profile="unit"):
 
     if hard:
         qh, kh, _ = heads_of()
-        assert_profile(hard, qh, kh, dh ** -0.5, [b * kv_div for b in range(nkv)], -(-lk_ // 64))
+        assert_profile(hard, qh, kh, dh ** -0.5, [b * kv_div for b in range(nkv)], -(-lk_ // tile), tile=tile)
 
     def ref():
         y, sc = attn_ref(*heads_of(), dh ** -0.5)
@@ -978,6 +1039,9 @@ def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8, profile="unit"):
                 lambda: {"y": merge_heads(attn_model(*heads_of(), dh ** -0.5, rounds_q(dh, lq, lk_)))}, oc.loc_heads(heads, dh))
     case.route = attention_route(dh, lq, lk_)
     case.hard = hard
+    if wide:          # the wide kernel's launch is replayed (`hostcheck optrace`): its grid is what wide_walk mirrors
+        wq, wkv = (c + 16, 2 * c + 16) if cross else (3 * c + 16, 3 * c + 16)
+        local_calls(case, [call("attention", ldq=wq, ldk=wkv, ldv=wkv, ldo=c, NB=nb, Lq=lq, Lk=lk_, heads=heads, dh=dh, kv_batch_div=kv_div)])
     return case
 
 
@@ -1021,8 +1085,43 @@ CROSS_HARD = [
     (3, 40, 77, 640, 3),                            # 80   dma<10,QT1,V2,4 waves>: V2 at 77 keys
     (1, 129, 321, 320, 1), (1, 129, 321, 640, 1),   # 40 / 80  V2, six key tiles: `creep` passes the rescale threshold twice
 ]
-# (lq = lk, c), one head: attention_wide.hip (64-key tiles, a running maximum that is always finite)
+# (lq = lk, c), one head: attention_wide.hip (32-key tiles, AW_KEYS; a running maximum that is always finite).  These two keep the
+# profiles laid out for 64 keys = two of its tiles; WIDE_PAST below lays them out for its own tile
 WIDE_HARD = [(65, 512), (33, 256)]
+
+# attention_wide.hip past one workgroup and past three key tiles.  A workgroup holds AW_QBLK = 128 queries as 4 waves x 2 query tiles
+# of 16; the grid is nqblk x heads x nb workgroups, renumbered so that blockIdx % 8 (one XCD) takes a contiguous run (wide_walk); K and
+# V each have a ring of two 32-key tiles, refilled with tile t + 2 / t + 1 while tile t is computed.  Profiles at key_tile = 32.
+# (nb, lq, lk or None = lq, c, heads, kv_div)   what it provides
+WIDE_PAST = [
+    (1, 161, None, 512, 1, 1),     # two query blocks: block 0 with all four waves full, block 1 with one query (wave 0, query tile 0, every other
+                                   # lane clamped); six key tiles: each K slot and each V slot refilled at least twice, the last tile holding one key
+    (1, 161, None, 256, 1, 1),     # the same at head dim 256 (KPP = 2, PIECES = 4 against 1 and 8)
+    (3, 129, None, 1024, 2, 1),    # nwg = 2 x 2 x 3 = 12: xq = 1, xr = 4 in the renumbering (workgroups with blockIdx % 8 >= xr); two heads, three batch entries
+    (4, 40, 97, 512, 1, 2),        # cross form, lk != lq, kv_batch_div = 2; four key tiles, the last holding one key
+]
+WIDE_QBLK = 128
+
+
+def wide_walk(nwg, nqblk, heads):
+    """attention_wide.hip:175-187: (batch entry, head, query block) of each blockIdx.  blockIdx % 8 labels the workgroups of one XCD;
+    label x takes a contiguous run of the list ordered (batch, head, query block), query block fastest — xq + 1 entries for the
+    first xr = nwg % 8 labels, xq = nwg / 8 for the others."""
+    xq, xr = nwg >> 3, nwg & 7
+    out = []
+    for bid in range(nwg):
+        x = bid & 7
+        w = (x * (xq + 1) if x < xr else xr * (xq + 1) + (x - xr) * xq) + (bid >> 3)
+        bh = w // nqblk
+        out.append((bh // heads, bh % heads, w % nqblk))
+    return out
+
+
+def wide_case_walk(case):
+    """(walk, key tiles) of a wide attention case from the integers of its call"""
+    a = case.calls[0][1]
+    nqblk = -(-a["Lq"] // WIDE_QBLK)
+    return wide_walk(nqblk * a["heads"] * a["NB"], nqblk, a["heads"]), -(-a["Lk"] // 32)
 
 
 def with_profiles(shapes, lq_of, lk_of, have_unit=()):
@@ -1034,6 +1133,12 @@ def with_profiles(shapes, lq_of, lk_of, have_unit=()):
 SELF_HARD_CASES = with_profiles(SELF_HARD, lambda s: s[1], lambda s: s[1], SELF_ATTN)
 CROSS_HARD_CASES = with_profiles(CROSS_HARD, lambda s: s[1], lambda s: s[2])
 WIDE_HARD_CASES = with_profiles(WIDE_HARD, lambda s: s[0], lambda s: s[0], WIDE_ATTN)
+WIDE_PAST_CASES = [(s, p) for s in WIDE_PAST for p in ["unit"] + PROFILES if p == "unit" or profile_applies(p, s[1], s[2] or s[1], 32)]
+
+
+def wide_past_cases():
+    return [attention_case(nb, lq, c, lk=lk, kv_div=div, heads=heads, profile=p, tile=key_tile(c // heads))
+            for (nb, lq, lk, c, heads, div), p in WIDE_PAST_CASES]
 
 
 @functools.lru_cache(maxsize=None)
@@ -2203,6 +2308,13 @@ def gemm_family_cases():
     return cs + [conv_case(**k, force=3) for k in HALO_CASES]
 
 
+def vae_cases():
+    """The cases of tests/test_gpu_vae_local.py: the autoencoder's kernels past one workgroup / one grid-stride step, GroupNorm at its width"""
+    cs = wide_past_cases()
+    cs += [edge_out_case(*e) for e in EDGE_OUT_PAST] + [edge_in_case(*e) for e in EDGE_IN_PAST]
+    return cs + [group_norm_case(**k) for k in GN_VAE]
+
+
 def all_cases():
     """Every case both test files run (the host file: the model of each against its own bound)."""
     cs = [linear_case(*s, o) for s in LINEAR_SHAPES for o in LINEAR_OPTIONS]
@@ -2215,6 +2327,7 @@ def all_cases():
     cs += [edge_in_case(*e, dt, tap) for e in EDGE_IN for dt in (f16, f32t) for tap in (False, True)]
     cs += [edge_out_case(*e, dt) for e in EDGE_OUT for dt in (f16, f32t)]
     cs += [group_norm_case(**k) for k in GN_CASES + GN_PAST_SLAB]
+    cs += vae_cases()
     cs += [layer_norm_case(*s) for s in LN_CASES]
     cs += [attention_case(*s) for s in SELF_ATTN]
     cs += [attention_case(3, 40, 320, lk=lk, kv_div=div) for lk, div in CROSS_ATTN]

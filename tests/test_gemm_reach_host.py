@@ -85,7 +85,10 @@ def test_local_kernels_of_a_forward_are_reached(reach, fixture_names):
     assert required - names(reach) == set(), sorted(required - names(reach))
     assert "gn_finalize_kernel" not in C.NO_OPERATOR_ENTRY and "gn_fold_kernel" in C.NO_OPERATOR_ENTRY
     gn = [c for c in C.all_cases() if c.name.startswith("group_norm[")]
-    assert len(gn) == len(C.GN_CASES) + len(C.GN_PAST_SLAB)
+    assert len(gn) == len(C.GN_CASES) + len(C.GN_PAST_SLAB) + len(C.GN_VAE)
+    vae = [c for c in gn if c.gn[2] == 128]
+    assert [reach[(c.name, "auto")][2].rsplit(" ", 3)[0] for c in vae] == ["gn_apply_kernel<1, true>", "gn_apply_kernel<1, false>"]
+    assert all(C.launch_grid(reach[(c.name, "auto")][0]) == (3, 2, 1) for c in vae)          # the autoencoder's width: three slabs, two batch entries
     for c in gn:                                  # statistics, finalize, then apply or the (a, b) pairs; grids as the Python mirror of gn_slabs says
         lines = reach[(c.name, "auto")]
         nb, P, ctot = c.gn
@@ -98,6 +101,54 @@ def test_local_kernels_of_a_forward_are_reached(reach, fixture_names):
         else:
             silu = "true" if c.calls[0][1]["silu"] else "false"
             assert C.launch_name(lines[2]) == f"gn_apply_kernel<{vpt}, {silu}>" and C.launch_grid(lines[2]) == (slabs, nb, 1), (c.name, lines)
+
+
+EDGE_OUT_KERNELS = {f"conv_edge_out_kernel<{ncb}, {t}>" for ncb in (0, 4, 8, 16) for t in ("float", "half")}
+EDGE_IN_KERNELS = {"conv_edge_in_kernel<float>", "conv_edge_in_kernel<half>"}
+
+
+def test_autoencoder_kernels_launch_what_the_walk_mirrors_say(reach):
+    """Kernel name and grid of every edge-conv and wide-attention case from the replay, against opcases.edge_out_walk / edge_in_walk /
+    wide_walk; every conv_edge_out and conv_edge_in instantiation is launched by some case; the grids of the issue's largest cases."""
+    cases = C.all_cases()
+    new = {c.name for c in C.vae_cases()}
+    out = [c for c in cases if c.name.startswith("conv_edge_out[")]
+    assert len(out) == 2 * len(C.EDGE_OUT) + len(C.EDGE_OUT_PAST) and {c.name for c in out if c.name in new} == {C.edge_out_case(*e).name for e in C.EDGE_OUT_PAST}
+    for c in out:
+        (line,) = reach[(c.name, "auto")]
+        a = c.calls[0][1]
+        ncb = {128: 4, 256: 8, 512: 16}.get(a["Cin"], 0)
+        grid, per = C.edge_out_walk(c.edge[0])
+        assert C.launch_name(line) == f"conv_edge_out_kernel<{ncb}, {'float' if a['y_dtype'] else 'half'}>", (c.name, line)
+        assert C.launch_grid(line) == (grid, 1, 1) and line.rsplit(" ", 2)[1] == "256,1,1", (c.name, line)
+        assert (per >= 2) == (c.edge[0] > 2048 * 64), c.name
+    assert {C.launch_name(reach[(c.name, "auto")][0]) for c in out} == EDGE_OUT_KERNELS
+    assert {C.launch_name(reach[(c.name, "auto")][0]) for c in out if c.name in new} >= {k for k in EDGE_OUT_KERNELS if "<0," in k}     # the rolled loop: new cases alone
+    (line,) = reach[("conv_edge_out[1x128->3,257x513,float32]", "auto")]
+    assert (C.launch_name(line), C.launch_grid(line)) == ("conv_edge_out_kernel<4, float>", (1031, 1, 1))
+    (line,) = reach[("conv_edge_out[1x8->8,257x513,float16]", "auto")]
+    assert (C.launch_name(line), C.launch_grid(line)) == ("conv_edge_out_kernel<0, half>", (1031, 1, 1))
+
+    inn = [c for c in cases if c.name.startswith("conv_edge_in[")]
+    assert len(inn) == 4 * len(C.EDGE_IN) + len(C.EDGE_IN_PAST)
+    for c in inn:
+        (line,) = reach[(c.name, "auto")]
+        grid, steps = C.edge_in_walk(*c.edge)
+        assert C.launch_name(line) == f"conv_edge_in_kernel<{'float' if c.calls[0][1]['x_dtype'] else 'half'}>" and C.launch_grid(line) == (grid, 1, 1), (c.name, line)
+        assert (max(steps) >= 2) == (c.name in new), c.name                      # a second grid-stride step: the new cases, and only they
+    assert {C.launch_name(reach[(c.name, "auto")][0]) for c in inn} == EDGE_IN_KERNELS
+    assert {(C.launch_name(reach[(c.name, "auto")][0]), C.launch_grid(reach[(c.name, "auto")][0])) for c in inn if c.name in new} == {(k, (4096, 1, 1)) for k in EDGE_IN_KERNELS}
+
+    wide = [c for c in cases if getattr(c, "route", None) == "wide"]
+    assert len(wide) == len(C.WIDE_ATTN) + len(C.WIDE_HARD_CASES) + len(C.WIDE_PAST_CASES)
+    for c in wide:
+        (line,) = reach[(c.name, "auto")]
+        walk, _ = C.wide_case_walk(c)
+        assert C.launch_name(line) == f"attention_wide_kernel<{c.calls[0][1]['dh']}>" and C.launch_grid(line) == (len(walk), 1, 1), (c.name, line)
+        assert (len(walk) > 1) == (c.name in new), c.name                        # what the suite had: one workgroup
+    (line,) = reach[("attention[nb3,lq129,lkNone,c1024,h2,div1]", "auto")]
+    assert (C.launch_name(line), C.launch_grid(line)) == ("attention_wide_kernel<512>", (12, 1, 1))
+    assert {C.launch_name(reach[(c.name, "auto")][0]) for c in wide if c.name in new} == {"attention_wide_kernel<512>", "attention_wide_kernel<256>"}
 
 
 def test_capped_block_cases_launch_with_their_cap(reach):

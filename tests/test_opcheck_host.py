@@ -26,8 +26,9 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 REPLAYED = ("linear", "linear_lnfold", "linear_lnfold_geglu", "conv3x3", "conv3x3_down", "upsample_conv3x3", "temporal_conv",   # driver.cpp run_optrace
             "timestep_sinusoid", "gemv", "pack_conv_in", "conv_in", "pack_conv_out", "conv_out", "add_class_emb_silu", "fill_relpos_bias", "ln_fold",
             "pack_geglu_vec", "copy_rows", "f16_to_f32",
-            "geglu_mlp", "temporal_block", "cross_block", "cross_block_long", "proj_qkv", "temporal_attention", "group_norm", "group_norm_affine")
-OPTIONAL = ("bias", "bias2", "R", "x2", "sc1", "sc2", "bias_f16", "b")
+            "geglu_mlp", "temporal_block", "cross_block", "cross_block_long", "proj_qkv", "temporal_attention", "group_norm", "group_norm_affine",
+            "conv_edge_in", "conv_edge_out", "attention")
+OPTIONAL = ("bias", "bias2", "R", "x2", "sc1", "sc2", "bias_f16", "b", "tap_bias")
 ALWAYS = {"conv_in": ("bias",), "conv_out": ("bias",), "temporal_attention": ("bias",)}          # operands of the new entries that are not optional there
 
 
@@ -66,6 +67,8 @@ def test_call_description_is_what_run_passes(case, monkeypatch):
     monkeypatch.setattr(ops, "_stream", lambda: None)
     monkeypatch.setattr(ops, "_chk16", lambda *ts: None)
     monkeypatch.setattr(ops, "_chk32", lambda *ts: None)
+    monkeypatch.setattr(ops, "_chk_cols16", lambda *ts: None)
+    monkeypatch.setattr(ops, "_edge_dtype", lambda t, what: int(t.dtype == torch.float32))
     monkeypatch.setattr(ops, "_zero_pages", {})
 
     def out_as_given(out, shape, dtype, device, what):
@@ -524,7 +527,8 @@ def test_group_norm_cases_run_past_one_slab():
     """opcases.gn_slabs / gn_geometry on the GroupNorm cases: three slabs with a ragged last one, the cap_total / NB clamp with more
     than one whole unrolled iteration and a remainder, two sources and the affine form past one slab, every geometry of GN_WIDTHS."""
     old = [C.group_norm_case(**k) for k in C.GN_CASES]
-    new = [C.group_norm_case(**k) for k in C.GN_PAST_SLAB]
+    new = [C.group_norm_case(**k) for k in C.GN_PAST_SLAB + C.GN_VAE]
+    assert C.gn_geometry(128) == (16, 1, 16) and 128 not in C.GN_WIDTHS and [(k["silu"], k["eps"], k["P"]) for k in C.GN_VAE] == [(True, 1e-6, 145), (False, 1e-6, 145)]
     shape = lambda c: (C.gn_geometry(c.gn[2]), C.gn_slabs(c.gn[1], c.gn[0], C.gn_geometry(c.gn[2])[2]))
     assert all(shape(c)[1][0] <= 2 and not shape(c)[1][2] for c in old)              # what the suite had: one slab (two at ty = 1), never clamped
     for c in new:
@@ -633,6 +637,146 @@ def test_group_norm_last_slab_left_out_of_the_sums():
         case.check({"y": bad})
     assert bad_rows(case, bad) == list(range(61, 122))
     assert rel_l2(bad, case.ref["y"][0]) > 10 * TOL_OP            # a fifth of the rows missing from the statistics: not a defect rel-L2 passes
+
+
+# ------------------------------------------------------------------ the autoencoder's kernels past one workgroup: walks and injected defects
+def test_wide_walk_is_a_bijection_and_the_cases_contain_every_path():
+    """opcases.wide_walk (attention_wide.hip:175-187) maps blockIdx onto (batch, head, query block) one to one for every grid size and
+    factorisation; the cases of WIDE_PAST contain, between them, a workgroup behind the uneven XCD labels (blockIdx % 8 >= nwg % 8 > 0),
+    a query block >= 1, a head >= 1, a block with all four waves full and one with a single query, a ring refill at t >= 2 (five key
+    tiles or more) with a last tile of one key, head dims 512 and 256, and kv_batch_div = 2 with lk != lq."""
+    for nwg in range(1, 41):
+        for nqblk in range(1, nwg + 1):
+            for heads in range(1, nwg // nqblk + 1):
+                if nwg % (nqblk * heads):
+                    continue
+                walk = C.wide_walk(nwg, nqblk, heads)
+                assert sorted(walk) == [(b, h, q) for b in range(nwg // (nqblk * heads)) for h in range(heads) for q in range(nqblk)], (nwg, nqblk, heads)
+    assert C.wide_walk(12, 2, 2) == [(0, 0, 0), (0, 1, 0), (1, 0, 0), (1, 1, 0), (2, 0, 0), (2, 0, 1), (2, 1, 0), (2, 1, 1), (0, 0, 1), (0, 1, 1), (1, 0, 1), (1, 1, 1)]
+    got = set()
+    cases = C.wide_past_cases()
+    assert {c.name for c in cases} <= {c.name for c in CASES} and len(cases) == 4 * 5           # every shape has room for every profile at tile 32
+    for c in cases:
+        a = c.calls[0][1]
+        walk, ntile = C.wide_case_walk(c)
+        nwg, xr = len(walk), len(walk) & 7
+        assert C.key_tile(a["dh"]) == 32
+        got |= {"uneven_xcd_labels"} if xr and any(bid & 7 >= xr for bid in range(nwg)) else set()
+        got |= {"query_block_1"} if any(q >= 1 for _, _, q in walk) else set()
+        got |= {"head_1"} if any(h >= 1 for _, h, _ in walk) else set()
+        got |= {"four_full_waves"} if a["Lq"] >= C.WIDE_QBLK else set()
+        got |= {"one_query_block"} if a["Lq"] % C.WIDE_QBLK == 1 else set()
+        got |= {"refill_at_t2"} if ntile >= 5 else set()               # `if (t + 2 < ntile)` at t = 2: K(4) into the slot K(2) leaves, which held K(0)
+        got |= {"last_tile_of_one_key"} if a["Lk"] % 32 == 1 else set()
+        got |= {"kv_batch_div_2"} if a["kv_batch_div"] == 2 and a["Lk"] != a["Lq"] else set()
+        got |= {f"dh{a['dh']}"}
+        # creep has room at this kernel's tile in every shape (attention_case asserts through assert_profile, on the values the kernel gets, that
+        # consecutive 32-key tile maxima rise by 3..8 log2 units and by more than 8 in all: a rescale deferred on some tiles, taken on others)
+        assert C.profile_applies("creep", a["Lq"], a["Lk"], 32) and (a["Lk"] > 128 or not C.profile_applies("creep", a["Lq"], a["Lk"]))
+        if c.hard and c.hard["creep"]:
+            assert ntile >= 4 and c.hard["creep"] == C.hard_rows(a["Lq"])
+    assert got == {"uneven_xcd_labels", "query_block_1", "head_1", "four_full_waves", "one_query_block", "refill_at_t2", "last_tile_of_one_key",
+                   "kv_batch_div_2", "dh512", "dh256"}, sorted(got)
+    assert sum(1 for c in cases if c.name.endswith(",creep]")) == 4
+    # what the suite had: one workgroup, three key tiles at most
+    old = [c for c in CASES if getattr(c, "route", None) == "wide" and c not in cases]
+    assert old and all(len(C.wide_case_walk(c)[0]) == 1 and C.wide_case_walk(c)[1] <= 3 for c in old)
+
+
+def test_edge_conv_cases_take_a_second_quad_and_a_second_step():
+    """opcases.edge_out_walk / edge_in_walk on the new cases: quads_per_wg = 2 with the in-loop break and the one-pixel tile in the last
+    workgroup; a second grid-stride step that is exactly the bottom image row; and what the older cases had."""
+    assert C.edge_out_walk(131841) == (1031, 2) and C.edge_out_walk(131072) == (2048, 1) and C.edge_out_walk(131073) == (1025, 2)
+    assert C.edge_out_walk(126) == (2, 1) and C.edge_out_walk(320) == (5, 1)
+    where, breaks = C.edge_out_tiles(131841)
+    assert len(where) == 8241 and 131841 - 8240 * 16 == 1 and where[8240] == (1030, 0, 0) and where[8239] == (1029, 1, 3)
+    assert breaks[1030] == [1, 0, 0, 0] and all(breaks[b] == [None] * 4 for b in range(1030))
+    big = [c for c in C.vae_cases() if c.name.startswith("conv_edge_out[") and C.edge_out_walk(c.edge[0])[1] == 2]
+    assert {c.name for c in big} == {"conv_edge_out[1x128->3,257x513,float32]", "conv_edge_out[1x8->8,257x513,float16]"}
+    old = [C.edge_out_case(*e, dt) for e in C.EDGE_OUT for dt in (C.f16, C.f32t)]
+    assert all(C.edge_out_walk(c.edge[0])[1] == 1 and C.edge_out_walk(c.edge[0])[0] <= 2 for c in old)
+    rolled = [c.calls[0][1]["Cin"] for c in C.vae_cases() if c.name.startswith("conv_edge_out[") and c.calls[0][1]["Cin"] not in (128, 256, 512)]
+    assert sorted(set(rolled)) == [8, 40]                                # one partly guarded block; two blocks, the last of 8 channels
+    grid, steps = C.edge_in_walk(16512, 512)
+    assert grid == 4096 and steps == [2] * 32 + [1] * 4064
+    assert 4096 * 256 // 64 == 16384 == 128 * 128 and 16512 * 64 - 4096 * 256 == 32 * 256     # the second step: the bottom row of 129 x 128, all of it
+    assert all(max(C.edge_in_walk(*c.edge)[1]) == 2 for c in C.vae_cases() if c.name.startswith("conv_edge_in["))
+    assert all(max(C.edge_in_walk(*C.edge_in_case(*e, dt, tap).edge)[1]) == 1 for e in C.EDGE_IN for dt in (C.f16, C.f32t) for tap in (False, True))
+
+
+def test_conv_edge_out_second_quad_stored_to_the_first_quads_pixels():
+    """Workgroup 515 of the 257 x 513 case stores its second quad (tiles 4124..4127) at the pixel offsets of its first (4120..4123):
+    the first quad's 64 pixels hold the second's results and the second's keep what they held (zeros here; on the GPU the poison,
+    which run_guarded reports as never written).  Caught at exactly those 128 pixels.  Not a defect rel-L2 passes: 128 of 131841
+    pixels wholly wrong measure 3e-2 against TOL_OP = 2e-3 — asserted as what it is."""
+    case = C.edge_out_case(1, 128, 3, 257, 513, C.f32t)
+    where, _ = C.edge_out_tiles(case.edge[0])
+    first, second = ([16 * t + i for t in sorted(t for t, (b, q, _) in where.items() if (b, q) == (515, k)) for i in range(16)] for k in (0, 1))
+    assert first == list(range(515 * 128, 515 * 128 + 64)) and second == list(range(515 * 128 + 64, 516 * 128))
+    y = case.model()["y"]
+    bad = y.clone().reshape(3, -1)
+    bad[:, first] = y.reshape(3, -1)[:, second]
+    bad[:, second] = 0
+    bad = bad.reshape(y.shape)
+    with pytest.raises(AssertionError, match=r"conv_edge_out\[1x128->3,257x513,float32\]"):
+        case.check({"y": bad})
+    assert offenders(case, bad).reshape(3, -1).any(0).nonzero().flatten().tolist() == first + second
+    assert 10 * TOL_OP < rel_l2(bad, case.ref["y"][0]) < 0.1
+
+
+def test_conv_edge_in_second_grid_stride_step_skipped():
+    """Workgroups 0..31 leave the loop after one step: items >= 4096 * 256 = the 128 pixels of the bottom image row are never written,
+    which run_guarded reports at pixel 16384.  With zeros there instead of the poison rel-L2 measures 9e-2: not a defect it passes."""
+    case = C.edge_in_case(1, 4, 512, 129, 128, C.f16, True)
+    grid, steps = C.edge_in_walk(*case.edge)
+    done = grid * 256 // (512 // 8)
+    assert done == 16384 and max(steps) == 2
+    y = case.model()["y"]
+
+    def fn(i, o):
+        o["y"][:done] = y[:done]
+    with pytest.raises(AssertionError, match=r"y: %d elements never written, first at offset %d .*row 16384, column 0" % (128 * 512, 16384 * 512)):
+        oc.run_guarded(fn, case.inputs, case.outputs, device="cpu")
+    bad = y.clone()
+    bad[done:] = 0
+    assert bad_rows(case, bad) == list(range(16384, 16512))
+    assert rel_l2(bad, case.ref["y"][0]) > 10 * TOL_OP
+
+
+def test_wide_attention_wave_3_rows_taken_from_wave_2():
+    """Query block 0 of the 161-token case: wave 3 (rows 96..127) stores what wave 2 computed (rows 64..95).  Caught at exactly those 32
+    rows.  Not a defect rel-L2 passes: a fifth of the rows is another row's output — asserted as what it is."""
+    for c in (512, 256):
+        case = C.attention_case(1, 161, c, heads=1, tile=32)
+        y = case.model()["y"]
+        bad = y.clone()
+        bad[96:128] = y[64:96]
+        with pytest.raises(AssertionError, match=r"attention\[nb1,lq161"):
+            case.check({"y": bad})
+        assert bad_rows(case, bad) == list(range(96, 128))
+        assert rel_l2(bad, case.ref["y"][0]) > 100 * TOL_OP
+
+
+def test_wide_attention_key_tile_read_from_the_slots_previous_occupant():
+    """The workgroup of query block 0 reads, for every key tile t >= 2, the K rows its ring slot held before: keys of tile t - 2 (the
+    refill never landed); V and the mask of the last tile are right, so the single key of tile 5 scores as key 96.  Every row of query
+    block 0 is off and the one row of query block 1 (another workgroup) is not.  Not a defect rel-L2 passes — asserted as what it is."""
+    case = C.attention_case(1, 161, 512, heads=1, tile=32)
+    walk, ntile = C.wide_case_walk(case)
+    assert walk == [(0, 0, 0), (0, 0, 1)] and ntile == 6
+    qkv = case.inputs["qkvw"]
+    q, k, v = qkv[:, :512], qkv[:, 520:1032], qkv[:, 1040:]
+    stale = k.clone()
+    for t in range(2, ntile):
+        n = min(32, 161 - 32 * t)
+        stale[32 * t:32 * t + n] = k[32 * (t - 2):32 * (t - 2) + n]
+    assert torch.equal(stale[160], k[96]) and torch.equal(stale[64:96], k[:32]) and torch.equal(stale[:64], k[:64])
+    bad = case.model()["y"].clone()
+    bad[:128] = C.attn_model(q[:128], stale, v, 512 ** -0.5, False)
+    with pytest.raises(AssertionError, match=r"attention\[nb1,lq161"):
+        case.check({"y": bad})
+    assert bad_rows(case, bad) == list(range(128))
+    assert rel_l2(bad, case.ref["y"][0]) > 100 * TOL_OP
 
 
 # ------------------------------------------------------------------ bands and poison, on CPU tensors
