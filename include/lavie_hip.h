@@ -391,6 +391,52 @@ int lavie_multistep_step_known(const void* eps, float* x, float* x0_prev, void* 
 int lavie_known_blend_f32(float* x, void* model_in, int dup, long long n, float input_scale, void* stream,
                           const lavie_known_region* region);
 
+/* Sampling a clip longer than the model's window as overlapping frame windows (additive in ABI 8; csrc/sampler_window.hip,
+ * DESIGN.md 7.9): ONE fp32 latent tensor x [P, C, F, hw] holds the whole clip, the UNet ran on W windows of L frames each
+ * (window w = frames [starts[w], starts[w] + L)), and this call fuses the windows' noise predictions where they overlap, advances
+ * the whole clip by one scheduler step and writes every window's next fp16 model input, in one launch.
+ * Per element (p, c, f, j), fp32, contraction off, over the windows that cover frame f in ascending window order:
+ *   e_w = fma(guidance, ec_w - eu_w, eu_w)              (cfg == 0: e_w = eu_w)   from eps[w][half, c, f - starts[w], j]
+ *   n_w = profile[f - starts[w]] / S                    S = the covering windows' profile values added in window order
+ *   eps = fma(n_w, e_w, eps)                            starting from 0
+ *   x', x0 = the plain step of the family from eps      family 0: lavie_cfg_sampler_step / lavie_sampler_step, aux = the step's noise
+ *                                                       (read when c4 = sigma != 0); family 1: lavie_cfg_multistep_step /
+ *                                                       lavie_multistep_step, aux = x0_prev (read when c4 = c_prev != 0, always written)
+ *   model_in[w][half, c, f - starts[w], j] = fp16(x' next_input_scale) for every covering window and both guidance halves, rounded
+ *                                            as the family's plain entry point rounds it
+ * So a frame covered by one window has n_w = 1 and eps = e_w exactly: the bits of the plain entry point; all windows that share a
+ * frame receive one fp16 value; both guidance halves of every model_in[w] are bit-equal.  No atomics, no host synchronisation,
+ * no allocation: bit-reproducible and safe in a capture.
+ * eps[w] / model_in[w]: fp16 device tensors [nb, C, L, hw], nb = 2 P with cfg ([negative | prompt]) else P.  starts_host,
+ * profile_host, eps_host and model_in_host are HOST arrays (W, L, W, W entries), read before the call returns; they travel to the
+ * kernel as launch arguments.
+ * Checked on the host before anything is dereferenced or launched, each refusal names its argument: args != NULL and its
+ * struct_size; family 0 / 1; P, C, F, hw >= 1 and P C F <= 65535; 1 <= W <= 32, 1 <= L <= 64; non-null host arrays; starts
+ * strictly ascending with starts[0] >= 0 and starts[W-1] + L <= F; every frame covered by at least 1 and at most 4 windows; every
+ * profile value finite and > 0; no null pointer in either table; x != NULL, aux != NULL unless family 0 with c4 == 0; no overlap
+ * between x, aux, any model_in[w] and any other buffer of the call (two eps tensors may overlap: they are only read); finite
+ * scalars; with hw %% 8 == 0 (eight elements per lane, 16-byte accesses; otherwise one element per lane) every tensor 16-byte
+ * aligned. */
+#define LAVIE_WINDOW_MAX_WINDOWS 32
+#define LAVIE_WINDOW_MAX_LENGTH 64
+#define LAVIE_WINDOW_MAX_COVER 4
+typedef struct lavie_window_step_args {
+    int struct_size;                  /* sizeof this struct as the CALLER declared it; any other value is refused */
+    int family;                       /* 0 five-coefficient (aux = noise), 1 multistep (aux = x0_prev) */
+    int cfg;                          /* != 0: classifier-free guidance, nb = 2 P */
+    int P, C, F;                      /* videos, latent channels, frames of the WHOLE clip */
+    long long hw;                     /* height * width of a latent frame */
+    int W, L;                         /* windows, frames per window */
+    const int* starts_host;           /* [W] first frame of each window */
+    const float* profile_host;        /* [L] weight of a window's i-th frame */
+    const void* const* eps_host;      /* [W] device pointers: the UNet's output for each window */
+    void* const* model_in_host;       /* [W] device pointers: the next model input of each window */
+    float* x;                         /* [P, C, F, hw] fp32, device, updated in place */
+    float* aux;                       /* [P, C, F, hw] fp32, device: the step's noise (family 0) or x0_prev (family 1) */
+    float guidance, k_x, k_eps, c_x0, c_xt, c4, next_input_scale;
+} lavie_window_step_args;
+int lavie_window_step(const lavie_window_step_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Measurement hook: HIP-event timing per kernel class on the launch stream (bench.py's roofline leg).
  * Classes: 0 conv3x3 (implicit GEMM, gathered), 1 linear/1x1/GEGLU GEMM, 2 spatial+text attention core,

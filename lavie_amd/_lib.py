@@ -11,6 +11,7 @@ ABI_VERSION = 8
 FUSED_DEFAULT = 0x137    # lavie_debug_fused_mask: bits 0, 1, 2, 4, 5, 8 (include/lavie_hip.h)
 MAX_LEVELS = 8
 LORA_MAX_TERMS = 8       # LAVIE_LORA_MAX_TERMS: adapters blended in one merge = slots of the engine's registry
+WINDOW_MAX_WINDOWS, WINDOW_MAX_LENGTH, WINDOW_MAX_COVER = 32, 64, 4      # LAVIE_WINDOW_MAX_*: limits of lavie_window_step
 
 c_void_p, c_int, c_float, c_ll, c_char_p = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_char_p
 c_float_p = C.c_void_p      # fp32 device pointers are passed as raw addresses
@@ -36,6 +37,14 @@ class LoraTermC(C.Structure):         # lavie_lora_term
 class KnownRegionC(C.Structure):      # lavie_known_region
     _fields_ = [("struct_size", c_int), ("channels", c_int), ("inner", c_ll), ("known", c_float_p), ("mask", c_float_p),
                 ("noise_known", c_float_p), ("a_next", c_float), ("s_next", c_float)]
+
+
+class WindowStepArgsC(C.Structure):   # lavie_window_step_args
+    _fields_ = [("struct_size", c_int), ("family", c_int), ("cfg", c_int), ("P", c_int), ("C", c_int), ("F", c_int), ("hw", c_ll),
+                ("W", c_int), ("L", c_int), ("starts_host", C.POINTER(c_int)), ("profile_host", C.POINTER(c_float)),
+                ("eps_host", C.POINTER(c_void_p)), ("model_in_host", C.POINTER(c_void_p)), ("x", c_float_p), ("aux", c_float_p),
+                ("guidance", c_float), ("k_x", c_float), ("k_eps", c_float), ("c_x0", c_float), ("c_xt", c_float), ("c4", c_float),
+                ("next_input_scale", c_float)]
 
 
 # name -> (restype, argtypes); every symbol declared in include/lavie_hip.h
@@ -136,6 +145,7 @@ SIGNATURES = {
     "lavie_multistep_step_known": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float,
                                             c_float, c_float, c_void_p, C.POINTER(KnownRegionC)]),
     "lavie_known_blend_f32": (c_int, [c_float_p, c_void_p, c_int, c_ll, c_float, c_void_p, C.POINTER(KnownRegionC)]),
+    "lavie_window_step": (c_int, [C.POINTER(WindowStepArgsC), c_void_p]),
     "lavie_debug_force_tile": (c_int, [c_int]),
     "lavie_debug_force_splits": (c_int, [c_int]),
     "lavie_debug_fused_mask": (c_int, [c_int]),

@@ -44,12 +44,14 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
                           height: int = 320, width: int = 512, base_steps: int = 50, guidance_scale: float = 7.5,
                           interp_frames: int = 61, interp_cfg_scale: float = 4.0, vsr_steps: int = 50,
                           vsr_guidance_scale: float = 7.5, noise_level: int = 150, generator=None, decode_final: bool = True,
-                          base_scheduler=None, vsr_scheduler=None):
+                          base_scheduler=None, vsr_scheduler=None, vsr_overlap: int = 0):
     """Returns (base_latents, interp_latents, vsr_latents, frames or None).  Text embeddings are passed per stage (the base
     and interpolation stages use SD-1.4's CLIP, 768 wide; the VSR stage the x4-upscaler's, 1024 wide).
     `base_scheduler` / `vsr_scheduler` replace the two diffusers-style stages' schedulers for this call (for instance a
     DPMSolverMultistepScheduler with fewer `base_steps` / `vsr_steps`); the pipelines get their own back afterwards.  The
-    interpolation stage samples with its SpacedDiffusion object and has no such switch."""
+    interpolation stage samples with its SpacedDiffusion object and has no such switch.
+    `vsr_overlap` > 0: the VSR stage samples the 61 frames as ONE run over 8-frame windows sharing that many frames with their
+    neighbours (`upscale_in_chunks(overlap=)`) instead of independent chunks; 0 = the reference's chunks."""
     swapped = [(pipe, pipe.scheduler) for pipe, sch in ((base_pipe, base_scheduler), (vsr_pipe, vsr_scheduler)) if sch is not None]
     if base_scheduler is not None:
         base_pipe.scheduler = base_scheduler
@@ -59,7 +61,7 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
         return _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, prompt_embeds, negative_prompt_embeds,
                         vsr_prompt_embeds, vsr_negative_prompt_embeds, interp_prompt_embeds, interp_negative_prompt_embeds, height,
                         width, base_steps, guidance_scale, interp_frames, interp_cfg_scale, vsr_steps, vsr_guidance_scale,
-                        noise_level, generator, decode_final)
+                        noise_level, generator, decode_final, vsr_overlap)
     finally:
         for pipe, own in swapped:
             pipe.scheduler = own
@@ -68,7 +70,7 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
 def _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, prompt_embeds, negative_prompt_embeds,
              vsr_prompt_embeds, vsr_negative_prompt_embeds, interp_prompt_embeds, interp_negative_prompt_embeds, height, width,
              base_steps, guidance_scale, interp_frames, interp_cfg_scale, vsr_steps, vsr_guidance_scale, noise_level, generator,
-             decode_final):
+             decode_final, vsr_overlap=0):
     dev = base_pipe.device
     # 1. base T2V (base/pipelines/sample.py:78-91)
     base = base_pipe(prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, height=height, width=width,
@@ -86,7 +88,7 @@ def _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, p
         x_start=copied2, use_concat=True, copy_no_mask=True).chunk(2, dim=0)[0]
     frames61 = decode_frames(vae, interp, 0.18215)
     # 3. video super-resolution in 8-frame chunks (vsr/sample.py:90-123): the decoded frames are the low-res conditioning
-    up = upscale_in_chunks(vsr_pipe, frames61, short_seq=8, prompt_embeds=vsr_prompt_embeds,
+    up = upscale_in_chunks(vsr_pipe, frames61, short_seq=8, overlap=vsr_overlap, prompt_embeds=vsr_prompt_embeds,
                            negative_prompt_embeds=vsr_negative_prompt_embeds, num_inference_steps=vsr_steps,
                            guidance_scale=vsr_guidance_scale, noise_level=noise_level, generator=generator)
     frames = decode_frames(vsr_vae, up, None, chunk=1) if decode_final else None
@@ -116,15 +118,27 @@ def continue_clip(pipe, prev_latents: torch.Tensor, overlap: int = 4, **call_kwa
 
 
 @torch.no_grad()
-def text_to_long_video(pipe, prompt, num_clips: int, overlap: int = 4, **call_kwargs) -> torch.Tensor:
-    """`num_clips` base clips chained by `continue_clip`: latents [P, C, L + (num_clips - 1)(L - overlap), h, w] with L =
-    `video_length` (16), the overlap frames stored once.  `prompt` may be None when `call_kwargs` carry prompt_embeds."""
+def text_to_long_video(pipe, prompt, num_clips: int, overlap: int = 4, method: str = "chain", **call_kwargs) -> torch.Tensor:
+    """Latents [P, C, L + (num_clips - 1)(L - overlap), h, w] with L = `video_length` (16).  `prompt` may be None when
+    `call_kwargs` carry prompt_embeds.
+    method "chain": `num_clips` base clips chained by `continue_clip`, the overlap frames stored once; clip n starts when clip
+    n - 1 has finished, and nothing later influences an earlier frame.
+    method "windows": ONE run over the whole length as `num_clips` windows of L frames at stride L - overlap, fused at every step
+    (VideoGenPipeline's `window_length` / `window_stride`): every forward keeps the trained length, the overlap frames are
+    shared in both directions."""
     if num_clips < 1:
         raise ValueError(f"num_clips={num_clips} must be >= 1")
+    if method not in ("chain", "windows"):
+        raise ValueError(f"method={method!r} must be 'chain' or 'windows'")
     length = int(call_kwargs.pop("video_length", 16))
     if prompt is not None:
         call_kwargs["prompt"] = prompt
     call_kwargs["output_type"] = "latent"
+    if method == "windows":
+        if not 0 <= overlap < length:
+            raise ValueError(f"overlap={overlap} must lie in 0..{length - 1} (window of {length} frames)")
+        total = length + (num_clips - 1) * (length - overlap)
+        return pipe(video_length=total, window_length=length, window_stride=length - overlap, **call_kwargs).video
     clip = pipe(video_length=length, **call_kwargs).video
     parts = [clip]
     for _ in range(num_clips - 1):

@@ -544,6 +544,99 @@ int lavie_known_blend_f32(float* x, void* model_in, int dup, long long n, float 
                               region->channels, region->inner, region->a_next, region->s_next, S(stream));
 }
 
+// The fused step over overlapping frame windows (sampler_window.hip).  Everything is checked here, on the host, before a table entry
+// is dereferenced or anything is launched; each refusal names its argument.
+int lavie_window_step(const lavie_window_step_args* a, void* stream) {
+    const char* who = "window_step";
+    LAVIE_CHECK(a, "%s: args is null", who);
+    LAVIE_CHECK(a->struct_size == (int)sizeof(lavie_window_step_args),
+                "%s: args->struct_size=%d but this library's lavie_window_step_args has %d bytes: the binding's struct layout is "
+                "out of date", who, a->struct_size, (int)sizeof(lavie_window_step_args));
+    LAVIE_CHECK(a->family == 0 || a->family == 1, "%s: family=%d must be 0 (five-coefficient) or 1 (multistep)", who, a->family);
+    LAVIE_CHECK(a->P >= 1 && a->C >= 1 && a->F >= 1 && a->hw >= 1, "%s: P=%d C=%d F=%d hw=%lld must be >= 1", who, a->P, a->C, a->F, a->hw);
+    LAVIE_CHECK((long long)a->P * a->C * a->F <= 65535, "%s: P C F = %lld planes, at most 65535 fit one launch", who,
+                (long long)a->P * a->C * a->F);
+    LAVIE_CHECK(a->hw <= (1ll << 40), "%s: hw=%lld is out of range", who, a->hw);
+    LAVIE_CHECK(a->W >= 1 && a->W <= LAVIE_WINDOW_MAX_WINDOWS, "%s: W=%d outside 1..%d", who, a->W, LAVIE_WINDOW_MAX_WINDOWS);
+    LAVIE_CHECK(a->L >= 1 && a->L <= LAVIE_WINDOW_MAX_LENGTH, "%s: L=%d outside 1..%d", who, a->L, LAVIE_WINDOW_MAX_LENGTH);
+    LAVIE_CHECK(a->starts_host, "%s: starts_host is null", who);
+    LAVIE_CHECK(a->profile_host, "%s: profile_host is null", who);
+    LAVIE_CHECK(a->eps_host, "%s: eps_host is null", who);
+    LAVIE_CHECK(a->model_in_host, "%s: model_in_host is null", who);
+    const int* st = a->starts_host;
+    LAVIE_CHECK(st[0] >= 0, "%s: starts[0]=%d is negative", who, st[0]);
+    for (int w = 1; w < a->W; ++w)
+        LAVIE_CHECK(st[w] > st[w - 1], "%s: starts[%d]=%d is not above starts[%d]=%d: starts must be strictly ascending", who, w, st[w],
+                    w - 1, st[w - 1]);
+    LAVIE_CHECK((long long)st[a->W - 1] + a->L <= a->F, "%s: starts[%d]=%d + L=%d runs past F=%d", who, a->W - 1, st[a->W - 1], a->L, a->F);
+    for (int f = 0, lo = 0; f < a->F; ++f) {            // lo: the first window that may still cover f
+        while (lo < a->W && st[lo] + a->L <= f) ++lo;
+        int cover = 0;
+        for (int w = lo; w < a->W && st[w] <= f; ++w) ++cover;
+        LAVIE_CHECK(cover >= 1, "%s: frame %d is uncovered by the windows (starts, L=%d)", who, f, a->L);
+        LAVIE_CHECK(cover <= LAVIE_WINDOW_MAX_COVER, "%s: frame %d has a cover count of %d windows, at most %d (starts, L=%d)", who, f, cover,
+                    LAVIE_WINDOW_MAX_COVER, a->L);
+    }
+    for (int i = 0; i < a->L; ++i)
+        LAVIE_CHECK(__builtin_isfinite(a->profile_host[i]) && a->profile_host[i] > 0.f, "%s: profile[%d]=%g must be finite and > 0", who, i,
+                    (double)a->profile_host[i]);
+    for (int w = 0; w < a->W; ++w) {
+        LAVIE_CHECK(a->eps_host[w], "%s: eps[%d] is null", who, w);
+        LAVIE_CHECK(a->model_in_host[w], "%s: model_in[%d] is null", who, w);
+    }
+    LAVIE_CHECK(a->x, "%s: x is null", who);
+    const float s[7] = {a->guidance, a->k_x, a->k_eps, a->c_x0, a->c_xt, a->c4, a->next_input_scale};
+    static const char* const snames[7] = {"guidance", "k_x", "k_eps", "c_x0", "c_xt", "c4", "next_input_scale"};
+    for (int i = 0; i < 7; ++i) LAVIE_CHECK(__builtin_isfinite(s[i]), "%s: %s (%g) is not finite", who, snames[i], (double)s[i]);
+    const bool aux_used = a->family == 1 || a->c4 != 0.f;
+    LAVIE_CHECK(!aux_used || a->aux, "%s: aux is null (%s)", who, a->family == 1 ? "the multistep family's x0_prev" : "the step's noise, c4 != 0");
+    // byte ranges: x, aux, then eps[w], then model_in[w]; a written range (x, aux, model_in) may overlap nothing, eps may overlap eps
+    const unsigned long long clip = (unsigned long long)a->P * a->C * a->F * a->hw * 4;
+    const unsigned long long win = (unsigned long long)(a->cfg ? 2 : 1) * a->P * a->C * a->L * a->hw * 2;
+    const int nr = 2 + 2 * a->W;
+    auto base = [&](int i) { return (uintptr_t)(i == 0 ? (const void*)a->x : i == 1 ? (const void*)a->aux : i < 2 + a->W ? a->eps_host[i - 2] : a->model_in_host[i - 2 - a->W]); };
+    auto bytes = [&](int i) { return i < 2 ? clip : win; };
+    auto label = [&](int i, char* buf, size_t n) {
+        if (i == 0) snprintf(buf, n, "x");
+        else if (i == 1) snprintf(buf, n, "aux");
+        else if (i < 2 + a->W) snprintf(buf, n, "eps[%d]", i - 2);
+        else snprintf(buf, n, "model_in[%d]", i - 2 - a->W);
+    };
+    for (int i = 0; i < nr; ++i) {
+        if (i == 1 && !aux_used) continue;
+        for (int j = i + 1; j < nr; ++j) {
+            if (j == 1 && !aux_used) continue;
+            const bool both_read_only = i >= 2 && i < 2 + a->W && j >= 2 && j < 2 + a->W;
+            if (both_read_only) continue;
+            const bool overlap = base(i) < base(j) + bytes(j) && base(j) < base(i) + bytes(i);
+            char bi[32], bj[32];
+            label(i, bi, sizeof bi);
+            label(j, bj, sizeof bj);
+            LAVIE_CHECK(!overlap, "%s: %s and %s overlap (aliasing)", who, bi, bj);
+        }
+    }
+    if (a->hw % 8 == 0)
+        for (int i = 0; i < nr; ++i) {
+            if (i == 1 && !aux_used) continue;
+            char bi[32];
+            label(i, bi, sizeof bi);
+            LAVIE_CHECK((base(i) & 15) == 0, "%s: %s at %p is not 16-byte aligned", who, bi, (void*)base(i));
+        }
+    WindowStepParams p{};
+    p.multistep = a->family == 1;
+    p.cfg = a->cfg != 0;
+    p.P = a->P; p.C = a->C; p.F = a->F; p.hw = a->hw; p.W = a->W; p.L = a->L;
+    p.starts = a->starts_host;
+    p.profile = a->profile_host;
+    p.eps = reinterpret_cast<const half_t* const*>(a->eps_host);
+    p.model_in = reinterpret_cast<half_t* const*>(a->model_in_host);
+    p.x = a->x;
+    p.aux = a->aux;
+    p.guidance = a->guidance; p.kx = a->k_x; p.ke = a->k_eps; p.c0 = a->c_x0; p.ct = a->c_xt; p.c4 = a->c4;
+    p.in_scale = a->next_input_scale;
+    return launch_window_step(p, S(stream));
+}
+
 int lavie_latents_to_scaled_model_input1(const float* x, void* model_in, long long n, float input_scale, void* stream) {
     LAVIE_CHECK(x && model_in && n > 0, "latents_to_scaled_model_input1: bad arguments");
     return launch_f32_to_f16_scaled(x, H(model_in), n, input_scale, S(stream));

@@ -893,6 +893,136 @@ int main(int argc, char** argv) {
         REQUIRE(refused(lavie_known_blend_f32(x, min2, 1, 48, 1.f, nullptr, &q), "region->noise_known at"));
         REQUIRE(lavie_hostcheck_launches() == before + 8);
     }
+    {   // the step over overlapping frame windows: accepted calls reach the (stubbed) launch in the eight-element and the one-element
+        // form with exactly sized buffers; every refusal comes before a table entry is dereferenced and names its argument
+        const int P = 1, C = 2, F = 13, L = 8, hw = 8, nclip = P * C * F * hw, nwin = 2 * P * C * L * hw;
+        alignas(16) static float x[nclip + 8], aux[nclip + 8];
+        alignas(16) static unsigned short e0[nwin + 8], e1[nwin + 8], m0[nwin + 8], m1[nwin + 8];
+        const float nan = __builtin_nanf(""), inf = __builtin_inff();
+        int starts[2] = {0, 5};
+        float profile[8] = {1, 2, 3, 4, 4, 3, 2, 1};
+        const void* eps[2] = {e0, e1};
+        void* min_[2] = {m0, m1};
+        lavie_window_step_args r{};
+        r.struct_size = (int)sizeof(r);
+        r.family = 0; r.cfg = 1; r.P = P; r.C = C; r.F = F; r.hw = hw; r.W = 2; r.L = L;
+        r.starts_host = starts; r.profile_host = profile; r.eps_host = eps; r.model_in_host = min_;
+        r.x = x; r.aux = aux;
+        r.guidance = 7.5f; r.k_x = 1.f; r.k_eps = 0.5f; r.c_x0 = 0.3f; r.c_xt = 0.7f; r.c4 = 0.1f; r.next_input_scale = 0.9f;
+        auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+        const long before = lavie_hostcheck_launches();
+        REQUIRE(lavie_window_step(&r, nullptr) == 0);
+        lavie_window_step_args q = r;
+        q.family = 1; q.c4 = 0.5f;                          // the multistep family, with and without history, with and without guidance
+        REQUIRE(lavie_window_step(&q, nullptr) == 0);
+        q.c4 = 0.f; q.cfg = 0;
+        REQUIRE(lavie_window_step(&q, nullptr) == 0);
+        q = r; q.c4 = 0.f; q.aux = nullptr;                 // sigma == 0: the noise is not read and may be absent
+        REQUIRE(lavie_window_step(&q, nullptr) == 0);
+        const void* eps_odd[2] = {e0 + 1, e1 + 1};          // the one-element form off alignment: hw = 7 inside the same buffers
+        void* min_odd[2] = {m0 + 1, m1 + 1};
+        q = r; q.hw = 7; q.x = x + 1; q.aux = aux + 1; q.eps_host = eps_odd; q.model_in_host = min_odd;
+        REQUIRE(lavie_window_step(&q, nullptr) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 5);
+        REQUIRE(refused(lavie_window_step(nullptr, nullptr), "args"));
+        q = r; q.struct_size -= 4;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "struct_size"));
+        q = r; q.family = 2;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "family"));
+        q = r; q.C = 0;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "C=0"));
+        q = r; q.hw = 0;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "hw=0"));
+        q = r; q.P = 4000;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "planes"));
+        q = r; q.W = 0;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "W=0"));
+        q = r; q.W = 33;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "W=33"));
+        q = r; q.L = 0;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "L=0"));
+        q = r; q.L = 65;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "L=65"));
+        q = r; q.starts_host = nullptr;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "starts_host"));
+        q = r; q.profile_host = nullptr;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "profile_host"));
+        q = r; q.eps_host = nullptr;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "eps_host"));
+        q = r; q.model_in_host = nullptr;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "model_in_host"));
+        int bad[2] = {5, 0};
+        q = r; q.starts_host = bad;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "ascending"));
+        bad[0] = 0; bad[1] = 0;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "ascending"));
+        bad[0] = -1; bad[1] = 5;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "starts[0]"));
+        bad[0] = 0; bad[1] = 6;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "past F"));
+        q = r; q.F = 12;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "past F"));
+        q = r; q.L = 4;                                     // frames 4 and 9..12 fall between / behind the windows
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "frame 4 is uncovered"));
+        int five[5] = {0, 1, 2, 3, 4};                      // frame 4 under five windows of 8 frames
+        const void* eps5[5] = {e0, e0, e0, e0, e0};
+        void* min5[5] = {m0, m0, m0, m0, m0};
+        q = r; q.W = 5; q.F = 12; q.starts_host = five; q.eps_host = eps5; q.model_in_host = min5;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "cover count of 5"));
+        float badp[8] = {1, 2, 3, 4, 4, 3, 2, 1};
+        q = r; q.profile_host = badp;
+        badp[3] = 0.f;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "profile[3]"));
+        badp[3] = -1.f;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "profile[3]"));
+        badp[3] = 4.f; badp[7] = nan;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "profile[7]"));
+        badp[7] = inf;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "profile[7]"));
+        const void* eps_null[2] = {e0, nullptr};
+        void* min_null[2] = {nullptr, m1};
+        q = r; q.eps_host = eps_null;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "eps[1] is null"));
+        q = r; q.model_in_host = min_null;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "model_in[0] is null"));
+        q = r; q.x = nullptr;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "x is null"));
+        q = r; q.aux = nullptr;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "aux is null"));
+        q = r; q.family = 1; q.c4 = 0.f; q.aux = nullptr;   // the multistep family always writes its history
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "aux is null"));
+        q = r; q.aux = x;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "x and aux overlap"));
+        q = r; q.aux = x + 8;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "x and aux overlap"));
+        void* min_same[2] = {m0, m0 + 16};
+        q = r; q.model_in_host = min_same;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "model_in[0] and model_in[1] overlap"));
+        void* min_eps[2] = {m0, e0};
+        q = r; q.model_in_host = min_eps;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "eps[0] and model_in[1] overlap"));
+        void* min_x[2] = {x, m1};
+        q = r; q.model_in_host = min_x;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "x and model_in[0] overlap"));
+        const void* eps_aux[2] = {e0, aux};
+        q = r; q.eps_host = eps_aux;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "aux and eps[1] overlap"));
+        q = r; q.guidance = nan;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "guidance"));
+        q = r; q.c4 = inf;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "c4"));
+        q = r; q.next_input_scale = nan;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "next_input_scale"));
+        q = r; q.x = x + 1;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "x at"));
+        q = r; q.eps_host = eps_odd;
+        REQUIRE(refused(lavie_window_step(&q, nullptr), "eps[0] at"));
+        REQUIRE(lavie_hostcheck_launches() == before + 5);
+        const void* eps_both[2] = {e0, e0};                  // two windows reading one prediction tensor: only read, accepted
+        q = r; q.eps_host = eps_both;
+        REQUIRE(lavie_window_step(&q, nullptr) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 6);
+    }
     {   // the VAE's edge convolutions and the asymmetric-pad stride-2 conv: accepted calls reach the (stubbed) launch with exactly
         // sized buffers (packing, odd Cin, ragged last tile); every refusal comes before a HIP call and names its argument
         const int N = 2, Hh = 5, Ww = 7, px = N * Hh * Ww;

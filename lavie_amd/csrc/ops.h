@@ -120,6 +120,28 @@ int launch_multistep_step_known(bool cfg, const half_t* eps2, float* x, float* x
 // x <- select(mask, x, a_next known + s_next noise_known) (mask == nullptr: mask = 1 everywhere); model_in = fp16(x in_scale), twice when dup
 int launch_known_blend(float* x, half_t* model_in, bool dup, int64_t n, float in_scale, const float* known, const float* mask,
                        const float* noise_known, int channels, int64_t inner, float a_next, float s_next, hipStream_t stream);
+// ---- sampler_window.hip : the same steps over overlapping frame windows of one long clip.  x / aux [P, C, F, hw] fp32 (aux: the
+//   step's noise, or x0_prev when multistep); window w covers frames [starts[w], starts[w] + L) and owns eps[w] (read) and
+//   model_in[w] (written), fp16 [nb, C, L, hw], nb = 2 P with cfg.  Per element the windows' (guided) predictions are averaged with
+//   weights profile[f - starts[w]] normalised over the covering windows, then the family's plain step runs on the whole clip and
+//   every covering window receives fp16(x' in_scale).  starts / profile / eps / model_in are HOST arrays, copied into the kernel
+//   arguments.  The caller (lavie_window_step) has validated the schedule: sorted starts inside the clip, every frame covered by
+//   1..kWindowMaxCover windows; with hw % 8 == 0 every tensor must be 16-byte aligned.
+constexpr int kWindowMaxWindows = 32, kWindowMaxLength = 64, kWindowMaxCover = 4;
+struct WindowStepParams {
+    bool multistep, cfg;
+    int P, C, F;
+    int64_t hw;
+    int W, L;
+    const int* starts;
+    const float* profile;
+    const half_t* const* eps;
+    half_t* const* model_in;
+    float* x;
+    float* aux;
+    float guidance, kx, ke, c0, ct, c4, in_scale;
+};
+int launch_window_step(const WindowStepParams& a, hipStream_t stream);
 int launch_fill_relpos_bias(const half_t* emb, const int* buckets, float* out, int heads, int F, hipStream_t stream);
 
 // ---- pack.hip : one-off weight repacking at load time

@@ -13,8 +13,8 @@
 //   model_in = fp16(x' in_scale), rounded as the kernel of the same family rounds it, one value for both guidance halves
 //   multistep family: x0_prev <- m == 0 ? x0 : m == 1 ? known : fma(m, known - x0, x0)   (a pinned element's x0 is known)
 // The two selects are exact: m == 0 returns the plain step's bits whatever known / noise_known hold (NaN included), m == 1
-// returns xk whatever the model predicted.  Contraction is off and every fused multiply-add is spelled out, as in
-// multistep_element (elementwise.hip): the compiler cannot move a rounding point.
+// returns xk whatever the model predicted.  Contraction is off and every fused multiply-add is spelled out (sampler_element.h, shared
+// with sampler_window.hip): the compiler cannot move a rounding point.
 //
 // Launch shape: blockIdx.y = the (video, channel) plane, blockIdx.x * 256 + lane = the position inside the plane, so the mask
 // index needs one scalar division per block and none per lane.  HBM-bound: with inner % 8 == 0 every lane takes eight elements
@@ -23,94 +23,15 @@
 // no allocation: capture-safe and bit-reproducible.
 #include "common.h"
 #include "ops.h"
+#include "sampler_element.h"
 
 namespace lavie {
 
-struct StepCoef { float guidance, kx, ke, c0, ct, c4; };     // c4: sigma (five-coefficient family) or c_prev (multistep family)
 struct KnownOperands { const float* known; const float* mask; const float* noise; float a, s; };
-
-// The instructions sampler_step_kernel (elementwise.hip) compiles to, spelled out: eps and x0 one fma each, x' the sum of two
-// rounded products, then one fma for the step's own noise.  tests/test_gpu_known_region.py holds m == 0 bit-equal to that kernel.
-template <bool CFG>
-__device__ __forceinline__ float five_coefficient_element(float eu, float ec, float xt, float nz, const StepCoef& c) {
-#pragma clang fp contract(off)
-    const float eps = CFG ? __builtin_fmaf(c.guidance, ec - eu, eu) : eu;
-    const float x0 = __builtin_fmaf(-c.ke, eps, c.kx * xt);
-    const float xn = c.ct * xt + c.c0 * x0;
-    return c.c4 != 0.f ? __builtin_fmaf(c.c4, nz, xn) : xn;
-}
-
-// multistep_element of elementwise.hip, restated (same test).
-template <bool CFG, bool HIST>
-__device__ __forceinline__ void multistep_known_element(float eu, float ec, float xt, float x0p, const StepCoef& c, float& x0,
-                                                        float& xn) {
-#pragma clang fp contract(off)
-    const float eps = CFG ? __builtin_fmaf(c.guidance, ec - eu, eu) : eu;
-    x0 = __builtin_fmaf(-c.ke, eps, c.kx * xt);
-    const float d = HIST ? __builtin_fmaf(c.c4, x0 - x0p, x0) : x0;
-    xn = c.ct * xt + c.c0 * d;
-}
 
 __device__ __forceinline__ float known_select(float m, float free_v, float pinned_v) {
 #pragma clang fp contract(off)
     return m == 0.f ? free_v : m == 1.f ? pinned_v : __builtin_fmaf(m, pinned_v - free_v, free_v);
-}
-
-// fp16 of the exact product v s, rounded once: the v_fma_mixlo_f16 that sampler_step_kernel and f32_to_f16_kernel compile to.
-// Written as the instruction itself because the compiler forms it from (half)(v * s) in some code shapes only (elementwise.hip,
-// scaled_f16), and the two forms of this kernel must agree with each other and with those kernels.
-__device__ __forceinline__ half_t once_rounded_f16(float v, float s) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    unsigned r = 0;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "+v"(r) : "v"(s), "v"(v));
-    return __builtin_bit_cast(half_t, (unsigned short)r);
-#else
-    return (half_t)(v * s);
-#endif
-}
-
-// fp16(fp32(v s)): what multistep_step_kernel writes (scaled_f16 of elementwise.hip).
-__device__ __forceinline__ half_t twice_rounded_f16(float v, float s) {
-    float p = v * s;
-    asm("" : "+v"(p));
-    return (half_t)p;
-}
-
-template <int W> __device__ __forceinline__ void load_f32(const float* p, float (&v)[W]) {
-    if constexpr (W == 8) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
-    } else {
-        v[0] = p[0];
-    }
-}
-template <int W> __device__ __forceinline__ void store_f32(float* p, const float (&v)[W]) {
-    if constexpr (W == 8) {
-        *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-    } else {
-        p[0] = v[0];
-    }
-}
-template <int W> __device__ __forceinline__ void load_f16(const half_t* p, float (&v)[W]) {
-    if constexpr (W == 8) {
-        const half8_t h = *reinterpret_cast<const half8_t*>(p);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (float)h[j];
-    } else {
-        v[0] = (float)p[0];
-    }
-}
-template <int W> __device__ __forceinline__ void store_f16(half_t* p, const half_t (&v)[W]) {
-    if constexpr (W == 8) {
-        half8_t h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) h[j] = v[j];
-        *reinterpret_cast<half8_t*>(p) = h;
-    } else {
-        p[0] = v[0];
-    }
 }
 
 // FAM 0: five-coefficient family (aux = the step's noise, read when c4 != 0); FAM 1: multistep family (aux = x0_prev, read when

@@ -652,6 +652,48 @@ def multistep_step_known(eps, x, x0_prev, model_in, coeffs, next_input_scale, kn
                                                       ctypes.byref(r)), "lavie_multistep_step_known")
 
 
+def window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, next_input_scale: float = 1.0, multistep: bool = False):
+    """One denoising step of a clip sampled as overlapping frame windows (lavie_window_step, csrc/sampler_window.hip).
+    x fp32 [P, C, F, ...] is the whole clip, updated in place; eps / model_in are lists with one fp16 tensor [nb, C, L, ...] per
+    window (the UNet's output for it / its next input), nb = 2 P = [negative | prompt] when `guidance` is a number, nb = P when it
+    is None; window w covers frames [starts[w], starts[w] + L); profile = L positive weights (lavie_amd.windows).  The windows'
+    predictions are averaged per frame with the normalised weights, the plain step of the family runs on the whole clip (`coeffs`
+    as cfg_ddpm_step / cfg_multistep_step take them; aux = the step's noise, or the x0_prev history when `multistep`) and every
+    window that covers a frame receives fp16(x' next_input_scale) in both guidance halves."""
+    _chk32(x, aux)
+    if x.dim() < 4:
+        raise ValueError(f"window_step: latents must be [P, C, F, ...], got {tuple(x.shape)}")
+    eps, model_in, starts, profile = list(eps), list(model_in), [int(s) for s in starts], [float(v) for v in profile]
+    n_win, length = len(starts), len(profile)
+    if not (len(eps) == len(model_in) == n_win) or n_win < 1:
+        raise ValueError(f"window_step: {len(eps)} eps and {len(model_in)} model_in tensors for {n_win} window starts")
+    _chk16(*eps, *model_in)
+    cfg = guidance is not None
+    p, c, f = x.shape[:3]
+    want = ((2 * p if cfg else p), c, length) + tuple(x.shape[3:])
+    for name, ts in (("eps", eps), ("model_in", model_in)):
+        for w, t in enumerate(ts):
+            if t is None or tuple(t.shape) != want or t.device != x.device:
+                raise ValueError(f"window_step: {name}[{w}] must be an fp16 tensor of shape {want} on {x.device}")
+    if aux is not None and (tuple(aux.shape) != tuple(x.shape) or aux.device != x.device):
+        raise ValueError(f"window_step: aux must have the latents' shape {tuple(x.shape)} on {x.device}")
+    k_x, k_e, c_x0, c_xt, c4 = coeffs
+    a = _lib.WindowStepArgsC()
+    a.struct_size = ctypes.sizeof(_lib.WindowStepArgsC)
+    a.family, a.cfg = int(bool(multistep)), int(cfg)
+    a.P, a.C, a.F, a.hw = p, c, f, math.prod(x.shape[3:])
+    a.W, a.L = n_win, length
+    starts_c, profile_c = (ctypes.c_int * n_win)(*starts), (ctypes.c_float * length)(*profile)
+    eps_c = (ctypes.c_void_p * n_win)(*[t.data_ptr() for t in eps])
+    min_c = (ctypes.c_void_p * n_win)(*[t.data_ptr() for t in model_in])
+    a.starts_host, a.profile_host, a.eps_host, a.model_in_host = starts_c, profile_c, eps_c, min_c
+    a.x, a.aux = x.data_ptr(), (aux.data_ptr() if aux is not None else None)
+    a.guidance = float(guidance) if cfg else 1.0
+    a.k_x, a.k_eps, a.c_x0, a.c_xt, a.c4 = float(k_x), float(k_e), float(c_x0), float(c_xt), float(c4)
+    a.next_input_scale = float(next_input_scale)
+    _lib.check(_lib.load().lavie_window_step(ctypes.byref(a), _stream()), "lavie_window_step")
+
+
 def latents_to_model_input1(x, model_in, input_scale: float = 1.0):
     _chk32(x)
     _chk16(model_in)

@@ -263,10 +263,21 @@ class VideoGenPipeline:
     def denoise(self, latents: torch.Tensor, ctx: torch.Tensor, num_inference_steps: int, guidance_scale: float,
                 generator=None, callback: Optional[Callable] = None, callback_steps: int = 1, eta: float = 0.0,
                 known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
-                known_noise: Optional[torch.Tensor] = None, start_step: int = 0) -> torch.Tensor:
+                known_noise: Optional[torch.Tensor] = None, start_step: int = 0, window_length: Optional[int] = None,
+                window_stride: Optional[int] = None, window_weights: str = "triangle") -> torch.Tensor:
         """latents fp32 [P, C, F, h, w] on the device, ctx fp16 [2P, n, d] = [negative | prompt] (guidance_scale > 1) or
         [P, n, d] = prompt only (guidance_scale <= 1: no classifier-free guidance, :626) -> denoised fp32.
-        `known` (clean latents, shaped as `latents`) switches to sampling around known latents: `_denoise_known`."""
+        `known` (clean latents, shaped as `latents`) switches to sampling around known latents: `_denoise_known`.
+        `window_length` below F switches to overlapping frame windows of that many frames: `_denoise_windowed`."""
+        if window_length is not None:
+            if known is not None or mask is not None or known_noise is not None or start_step != 0:
+                raise ValueError("frame windows (`window_length`) cannot be combined with known latents (`known` / `mask` / "
+                                 "`known_noise` / `start_step`)")
+            if int(window_length) < 1:
+                raise ValueError(f"`window_length`={window_length} must be >= 1")
+            if latents.shape[2] > int(window_length):
+                return self._denoise_windowed(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps,
+                                              eta, int(window_length), window_stride, window_weights)
         if known is not None:
             return self._denoise_known(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta,
                                        known, mask, known_noise, start_step)
@@ -511,6 +522,106 @@ class VideoGenPipeline:
                 raise cleanup_error
         return x
 
+    # ------------------------------------------------------------------ the loop over overlapping frame windows
+    @torch.no_grad()
+    def _denoise_windowed(self, latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta,
+                          window_length, window_stride, window_weights) -> torch.Tensor:
+        """The loop of `denoise` for a clip longer than the model's window (MultiDiffusion along the frame axis): ONE latent
+        tensor holds all F frames; per step the UNet runs on every window of `window_length` frames (starts 0, stride, 2 stride,
+        ..., the last one clamped to the clip's end: lavie_amd.windows), then ONE launch (ops.window_step) averages the windows'
+        noise predictions per frame with the normalised `window_weights` profile, advances the whole clip by one scheduler step
+        and writes every window's next fp16 model input.  `window_stride` defaults to three quarters of the window.  A frame that
+        one window covers gets the plain step's bits.  The engine is prepared and the context cached once, for the window shape.
+        The step's own noise (DDPM, DDIM with eta > 0) is drawn per step for the whole clip, as in `_denoise_known`."""
+        from . import windows
+        dev = latents.device
+        sch = self.scheduler
+        sch.set_timesteps(num_inference_steps)
+        fractional = bool(getattr(sch, "fractional_timesteps", False))
+        timesteps = [float(t) if fractional else int(t) for t in sch.timesteps]
+        in_scale = getattr(sch, "model_input_scale", None)
+        takes_eta = "eta" in inspect.signature(sch.coefficients).parameters
+        multistep = bool(getattr(sch, "multistep", False))
+        do_cfg = guidance_scale > 1.0
+        x = latents.to(torch.float32).contiguous().clone()
+        p, length = x.shape[0], window_length
+        nb = 2 * p if do_cfg else p
+        if ctx.shape[0] != nb:
+            raise ValueError(f"ctx has {ctx.shape[0]} rows, expected {nb} for {p} latents at guidance_scale={guidance_scale}")
+        stride = int(window_stride) if window_stride is not None else max(1, length - length // 4)
+        starts = windows.window_starts(x.shape[2], length, stride)
+        profile = windows.window_profile(length, window_weights)
+        gens = generator if isinstance(generator, list) else ([generator] if generator is not None else [])
+        if isinstance(generator, list):
+            if len(gens) != p:
+                raise ValueError(f"got a list of {len(gens)} generators for {p} latents")
+            if len({g.device.type for g in gens}) != 1:
+                raise ValueError("a list of generators must live on one device type")
+        host_noise = bool(gens) and gens[0].device.type == "cpu"
+        x0_prev = torch.empty_like(x) if multistep else None      # never read before the first step has written it (c_prev = 0)
+        noise_dev = torch.empty_like(x)
+        first_scale = in_scale(timesteps[0]) if in_scale else 1.0
+        win_shape = (nb, x.shape[1], length) + tuple(x.shape[3:])
+        model_in = [torch.empty(win_shape, dtype=torch.float16, device=dev) for _ in starts]
+        for s, m in zip(starts, model_in):
+            xw = x[:, :, s:s + length].contiguous()
+            (ops.latents_to_model_input if do_cfg else ops.latents_to_model_input1)(xw, m, first_scale)
+        self.unet.prepare(nb, length, x.shape[3], x.shape[4], ctx.shape[1])
+        ctx = self.unet.cache_context(ctx) if hasattr(self.unet, "cache_context") else ctx
+        t_dev = torch.tensor(timesteps, dtype=torch.float32, device=dev)
+        # all W predictions are held until the step: a UNet that hands back one buffer per shape (enable_graph) needs copies.
+        # Unknown until two forwards of one step have been seen; None = not decided yet
+        reuses_output = None
+        # the step kernel writes one fp16 value into both halves of every window's model input: cfg_shared_prefix holds
+        shared = do_cfg and self.cfg_shared_prefix and hasattr(self.unet, "set_cfg_shared_input")
+        try:
+            if shared:
+                self.unet.set_cfg_shared_input(True)
+            for i, t in enumerate(timesteps):
+                eps = []
+                for w, m in enumerate(model_in):
+                    e = self.unet(m, t_dev[i], encoder_hidden_states=ctx).sample
+                    if reuses_output is None and w == 1:
+                        reuses_output = e.data_ptr() == eps[0].data_ptr()
+                        if reuses_output:                 # the second forward has overwritten the first prediction: redo that one
+                            e = e.clone()
+                            eps[0] = self.unet(model_in[0], t_dev[i], encoder_hidden_states=ctx).sample.clone()
+                    elif reuses_output:
+                        e = e.clone()
+                    eps.append(e)
+                coeffs = sch.coefficients(t, eta) if takes_eta else sch.coefficients(t)
+                aux = x0_prev
+                if not multistep and coeffs[4] != 0.0:
+                    if host_noise and isinstance(generator, list):
+                        aux = torch.stack([torch.randn(x.shape[1:], generator=g, dtype=torch.float32) for g in gens]).to(dev)
+                    elif host_noise:
+                        aux = torch.randn(x.shape, generator=generator, dtype=torch.float32).to(dev)
+                    elif isinstance(generator, list):
+                        for j, g in enumerate(gens):
+                            noise_dev[j].normal_(generator=g)
+                        aux = noise_dev
+                    else:
+                        aux = noise_dev.normal_(generator=generator) if generator is not None else noise_dev.normal_()
+                next_scale = in_scale(timesteps[i + 1]) if in_scale and i + 1 < len(timesteps) else 1.0
+                ops.window_step(eps, x, aux, model_in, starts, profile, guidance_scale if do_cfg else None, coeffs, next_scale,
+                                multistep=multistep)
+                if callback is not None and i % callback_steps == 0:
+                    callback(i, t, x)
+        finally:
+            pending = sys.exc_info()[1]
+            cleanup_error = None
+            for undo in ((lambda: self.unet.set_cfg_shared_input(False)) if shared else None,
+                         (lambda: self.unet.cache_context(None)) if hasattr(self.unet, "cache_context") else None):
+                if undo is None:
+                    continue
+                try:
+                    undo()
+                except Exception as e:      # noqa: BLE001
+                    cleanup_error = cleanup_error or e
+            if cleanup_error is not None and pending is None:
+                raise cleanup_error
+        return x
+
     @staticmethod
     def strength_start(num_inference_steps: int, strength: float) -> int:
         """First position of the timestep table a run at `strength` in (0, 1] takes: steps - int(steps * strength), the img2img
@@ -573,7 +684,11 @@ class VideoGenPipeline:
                  output_type: Optional[str] = "pil", return_dict: bool = True, callback=None, callback_steps: int = 1,
                  cross_attention_kwargs=None, image_embeds: Optional[torch.Tensor] = None,
                  known_latents: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None,
-                 video: Optional[torch.Tensor] = None, strength: float = 1.0):
+                 video: Optional[torch.Tensor] = None, strength: float = 1.0, window_length: Optional[int] = None,
+                 window_stride: Optional[int] = None, window_weights: str = "triangle"):
+        if window_length is not None and (known_latents is not None or known_mask is not None or video is not None or strength != 1.0):
+            raise ValueError("frame windows (`window_length`) cannot be combined with `known_latents` / `known_mask` / `video` / "
+                             "`strength`")
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
@@ -598,6 +713,8 @@ class VideoGenPipeline:
             known = self.encode_video(video) if video is not None else known_latents
             around = dict(known=known.to(device=device, dtype=torch.float32), mask=known_mask,
                           start_step=self.strength_start(num_inference_steps, strength))
+        elif window_length is not None:    # clips longer than the window: overlapping frame windows, `_denoise_windowed`
+            around = dict(window_length=window_length, window_stride=window_stride, window_weights=window_weights)
         lora_scale = (cross_attention_kwargs or {}).get("scale")
         if lora_scale is None:
             latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta,

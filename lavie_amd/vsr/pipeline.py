@@ -69,11 +69,19 @@ class VideoUpscalePipeline:
     @torch.no_grad()
     def denoise(self, latents: torch.Tensor, image: torch.Tensor, ctx: torch.Tensor, noise_level: int,
                 num_inference_steps: int, guidance_scale: float, eta: float = 0.0, generator=None,
-                callback: Optional[Callable] = None, callback_steps: int = 1) -> torch.Tensor:
+                callback: Optional[Callable] = None, callback_steps: int = 1, window_length: Optional[int] = None,
+                window_stride: Optional[int] = None, window_weights: str = "triangle") -> torch.Tensor:
         """latents fp32 [P, 4, F, h, w]; image = the NOISED low-res frames [P, 3, F, h, w]; ctx fp16 [2P, n, d] =
-        [negative | prompt] -> denoised latents fp32."""
+        [negative | prompt] -> denoised latents fp32.  `window_length` below F: the clip is sampled as overlapping frame
+        windows of that many frames, fused in the step kernel (`_denoise_windowed`)."""
         if guidance_scale <= 1.0:
             raise NotImplementedError("guidance_scale <= 1 (no classifier-free guidance) is outside the fused MI355X loop")
+        if window_length is not None:
+            if int(window_length) < 1:
+                raise ValueError(f"`window_length`={window_length} must be >= 1")
+            if latents.shape[2] > int(window_length):
+                return self._denoise_windowed(latents, image, ctx, noise_level, num_inference_steps, guidance_scale, eta, generator,
+                                              callback, callback_steps, int(window_length), window_stride, window_weights)
         dev = latents.device
         sch = self.scheduler
         sch.set_timesteps(num_inference_steps)
@@ -112,12 +120,76 @@ class VideoUpscalePipeline:
         return x
 
     @torch.no_grad()
+    def _denoise_windowed(self, latents, image, ctx, noise_level, num_inference_steps, guidance_scale, eta, generator, callback,
+                          callback_steps, window_length, window_stride, window_weights) -> torch.Tensor:
+        """The loop of `denoise` for a clip longer than the model's window: ONE latent tensor holds all F frames (and one x0
+        history for a multistep scheduler); per step the UNet runs on every window of `window_length` frames with that window's
+        slice of the low-res frames (sliced once, before the loop), then ONE launch (ops.window_step) averages the windows' noise
+        predictions per frame with the normalised `window_weights` profile, advances the whole clip by one scheduler step and
+        writes every window's next fp16 model input.  `window_stride` defaults to three quarters of the window.  Unlike
+        independent chunks, neighbouring windows share their overlap frames at every step, so there is no seam between them."""
+        from .. import windows
+        dev = latents.device
+        sch = self.scheduler
+        sch.set_timesteps(num_inference_steps)
+        fractional = bool(getattr(sch, "fractional_timesteps", False))
+        timesteps = [float(t) if fractional else int(t) for t in sch.timesteps]
+        takes_eta = "eta" in inspect.signature(sch.coefficients).parameters
+        in_scale = getattr(sch, "model_input_scale", None)
+        multistep = bool(getattr(sch, "multistep", False))
+        x = latents.to(torch.float32).contiguous().clone()
+        x0_prev = torch.empty_like(x) if multistep else None
+        p, length = x.shape[0], window_length
+        stride = int(window_stride) if window_stride is not None else max(1, length - length // 4)
+        starts = windows.window_starts(x.shape[2], length, stride)
+        profile = windows.window_profile(length, window_weights)
+        first_scale = in_scale(timesteps[0]) if in_scale else 1.0
+        win_shape = (2 * p, x.shape[1], length) + tuple(x.shape[3:])
+        model_in = [torch.empty(win_shape, dtype=torch.float16, device=dev) for _ in starts]
+        low = []
+        for s, m in zip(starts, model_in):
+            ops.latents_to_model_input(x[:, :, s:s + length].contiguous(), m, first_scale)
+            img = image[:, :, s:s + length]
+            low.append(torch.cat([img, img], dim=0).to(device=dev, dtype=torch.float16).contiguous())
+        labels = torch.full((2 * p,), int(noise_level), dtype=torch.int64)
+        noise_dev = torch.empty_like(x)
+        t_dev = torch.tensor(timesteps, dtype=torch.float32, device=dev)
+        self.unet.prepare(2 * p, length, x.shape[3], x.shape[4], ctx.shape[1])
+        ctx = self.unet.cache_context(ctx)       # once for the whole clip, not once per window
+        reuses_output = None                     # does the UNet hand back one buffer per shape?  Known after two forwards of a step
+        try:
+            for i, t in enumerate(timesteps):
+                eps = []
+                for w, m in enumerate(model_in):
+                    e = self.unet(m, t_dev[i], low[w], encoder_hidden_states=ctx, class_labels=labels).sample
+                    if reuses_output is None and w == 1:
+                        reuses_output = e.data_ptr() == eps[0].data_ptr()
+                        if reuses_output:         # the second forward has overwritten the first prediction: redo that one
+                            e = e.clone()
+                            eps[0] = self.unet(model_in[0], t_dev[i], low[0], encoder_hidden_states=ctx, class_labels=labels).sample.clone()
+                    elif reuses_output:
+                        e = e.clone()
+                    eps.append(e)
+                coeffs = sch.coefficients(t, eta) if takes_eta else sch.coefficients(t)
+                aux = x0_prev
+                if not multistep and coeffs[4] != 0.0:
+                    aux = noise_dev.copy_(randn_tensor(x.shape, generator=generator, device=dev, dtype=torch.float32))
+                next_scale = in_scale(timesteps[i + 1]) if in_scale and i + 1 < len(timesteps) else 1.0
+                ops.window_step(eps, x, aux, model_in, starts, profile, guidance_scale, coeffs, next_scale, multistep=multistep)
+                if callback is not None and i % callback_steps == 0:
+                    callback(i, t, x)
+        finally:
+            self.unet.cache_context(None)
+        return x
+
+    @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str], None] = None, image: Optional[torch.Tensor] = None,
                  num_inference_steps: int = 75, guidance_scale: float = 9.0, noise_level: int = 20, negative_prompt=None,
                  num_images_per_prompt: Optional[int] = 1, eta: float = 0.0, generator=None,
                  latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
                  negative_prompt_embeds: Optional[torch.Tensor] = None, output_type: Optional[str] = "latent",
-                 return_dict: bool = True, callback=None, callback_steps: int = 1):
+                 return_dict: bool = True, callback=None, callback_steps: int = 1, window_length: Optional[int] = None,
+                 window_stride: Optional[int] = None, window_weights: str = "triangle"):
         self.check_inputs(image, noise_level, callback_steps, prompt, prompt_embeds, negative_prompt_embeds)
         if prompt is not None:
             raise NotImplementedError("text encoding is not built: pass prompt_embeds / negative_prompt_embeds")
@@ -136,7 +208,7 @@ class VideoUpscalePipeline:
             raise ValueError(f"Incorrect configuration settings! The config of `pipeline.unet` expects "
                              f"{self.unet.config.in_channels} but received 4 + {image.shape[1]} channels")
         latents = self.denoise(latents, image, ctx, noise_level, num_inference_steps, guidance_scale, eta, generator, callback,
-                               callback_steps)
+                               callback_steps, window_length, window_stride, window_weights)
         if output_type != "latent":
             if self.vae is None:
                 raise ValueError("no vae attached: use output_type='latent'")
@@ -151,11 +223,17 @@ class VideoUpscalePipeline:
         return StableDiffusionPipelineOutput(images=latents)
 
 
-def upscale_in_chunks(pipeline: VideoUpscalePipeline, vframes: torch.Tensor, short_seq: int = 8, **kw) -> torch.Tensor:
+def upscale_in_chunks(pipeline: VideoUpscalePipeline, vframes: torch.Tensor, short_seq: int = 8, overlap: int = 0, **kw) -> torch.Tensor:
     """vsr/sample.py:104-123: clips longer than `short_seq` frames go through the pipeline `short_seq` frames at a time
-    (same generator across chunks); outputs are concatenated along the frame axis."""
+    (same generator across chunks); outputs are concatenated along the frame axis.
+    overlap > 0 (not in the reference): the whole clip is ONE run over windows of `short_seq` frames that share `overlap` frames
+    with their neighbours, fused at every step (`VideoUpscalePipeline._denoise_windowed`), so the chunks no longer meet at a seam."""
     total = vframes.shape[2]
+    if not 0 <= overlap < short_seq:
+        raise ValueError(f"overlap={overlap} must lie in 0..{short_seq - 1} (short_seq={short_seq})")
     if total <= short_seq:
         return pipeline(image=vframes, **kw).images
+    if overlap > 0:
+        return pipeline(image=vframes, window_length=short_seq, window_stride=short_seq - overlap, **kw).images
     outs = [pipeline(image=vframes[:, :, s:min(total, s + short_seq)], **kw).images for s in range(0, total, short_seq)]
     return torch.cat(outs, dim=2)
