@@ -15,7 +15,7 @@ from typing import Callable, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .. import ops
+from .. import ops, sampling
 
 
 def space_timesteps(num_timesteps: int, section_counts) -> set:
@@ -158,12 +158,11 @@ class SpacedDiffusion:
             inp[k:, x.shape[1]:] = xs
         else:
             inp = model_in
-        unet.prepare(2 * k, x.shape[2], x.shape[3], x.shape[4], ctx.shape[1])
-        ctx = unet.cache_context(ctx)            # text keys / values once per clip, not once per block and step
         noise_dev = torch.empty_like(x)
         steps = list(range(self.num_timesteps))[::-1]
         t_dev = torch.tensor([float(self.timestep_map[i]) for i in steps], dtype=torch.float32, device=dev)
-        try:                                     # an exception in the loop must not leave the engine holding ctx
+        # text keys / values once per clip, not once per block and step
+        with sampling.engine_session(unet, 2 * k, x.shape[2], x.shape[3], x.shape[4], ctx) as ctx:
             for j, i in enumerate(steps):
                 if max_steps is not None and j >= max_steps:
                     break
@@ -173,8 +172,6 @@ class SpacedDiffusion:
                 coeffs = self.ddim_coefficients(i, eta)
                 step_noise = noise_dev.normal_() if coeffs[4] != 0.0 else None
                 ops.cfg_ddpm_step(eps, x, step_noise, model_in, cfg_scale, coeffs)
-        finally:
-            unet.cache_context(None)
         return torch.cat([x, x], dim=0)
 
 

@@ -13,14 +13,11 @@ widens each CFG half's context to `cat([text, mapper(image, text)], 1)`: 154 tok
 as `image_tensor` (through `clip_processor` + `clip_model.vision_model`, stock PyTorch) or as precomputed vision features
 `image_embeds`.  Without a mapper `image_tensor` is accepted and ignored, as before."""
 from dataclasses import dataclass
-import inspect
-import os
-import sys
 from typing import Callable, List, Optional, Union
 
 import torch
 
-from . import ops
+from . import ops, sampling
 from .scheduling_ddpm import DDPMScheduler, randn_tensor
 
 
@@ -43,7 +40,6 @@ class VideoGenPipeline:
         self.unet = unet
         self.scheduler = scheduler or DDPMScheduler()
         self.vae_scale_factor = 8                        # 2 ** (len(vae.config.block_out_channels) - 1) for SD-1.x
-        self._copy_stream = None
 
     def to(self, device):
         self.unet.to(device)
@@ -266,360 +262,96 @@ class VideoGenPipeline:
                 known_noise: Optional[torch.Tensor] = None, start_step: int = 0, window_length: Optional[int] = None,
                 window_stride: Optional[int] = None, window_weights: str = "triangle") -> torch.Tensor:
         """latents fp32 [P, C, F, h, w] on the device, ctx fp16 [2P, n, d] = [negative | prompt] (guidance_scale > 1) or
-        [P, n, d] = prompt only (guidance_scale <= 1: no classifier-free guidance, :626) -> denoised fp32.
-        `known` (clean latents, shaped as `latents`) switches to sampling around known latents: `_denoise_known`.
-        `window_length` below F switches to overlapping frame windows of that many frames: `_denoise_windowed`."""
+        [P, n, d] = prompt only (guidance_scale <= 1: no classifier-free guidance, :626) -> denoised fp32.  One loop, one step
+        launch per denoising step; step plan, step noise, engine session and step dispatch are lavie_amd.sampling's.
+
+        Around known latents (the known-region replacement of diffusers' legacy inpaint / img2img loop): `known` are clean
+        latents shaped as `latents`.  After every step the step kernel itself overwrites the part `mask` pins (1 = keep `known`,
+        0 = free, [P, 1, F, h, w] or broadcastable to it) with `known` re-noised to the level the step just reached,
+        x_t = a known + s known_noise, and the last step lands on `known` itself.  `known_noise` is ONE tensor for the whole run
+        (drawn from `generator` before the loop when not given).  start_step = 0: x starts as `latents` with the pinned part
+        replaced.  start_step > 0 (a run at reduced strength): the loop runs timesteps[start_step:] and x starts as `known`
+        noised to timesteps[start_step] everywhere, `latents` only gives the shape.  mask = None pins nothing during the steps
+        (plain img2img).
+
+        Frame windows, for a clip longer than the model's window (MultiDiffusion along the frame axis): with `window_length`
+        below F, ONE latent tensor holds all F frames; per step the UNet runs on every window of `window_length` frames (starts 0,
+        stride, 2 stride, ..., the last one clamped to the clip's end: lavie_amd.windows), then ONE launch (ops.window_step)
+        averages the windows' noise predictions per frame with the normalised `window_weights` profile, advances the whole clip
+        by one scheduler step and writes every window's next fp16 model input.  `window_stride` defaults to three quarters of the
+        window.  A frame that one window covers gets the plain step's bits.  The engine is prepared and the context cached once,
+        for the window shape; the step's own noise is drawn for the whole clip."""
+        windowed = False
         if window_length is not None:
             if known is not None or mask is not None or known_noise is not None or start_step != 0:
                 raise ValueError("frame windows (`window_length`) cannot be combined with known latents (`known` / `mask` / "
                                  "`known_noise` / `start_step`)")
             if int(window_length) < 1:
                 raise ValueError(f"`window_length`={window_length} must be >= 1")
-            if latents.shape[2] > int(window_length):
-                return self._denoise_windowed(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps,
-                                              eta, int(window_length), window_stride, window_weights)
-        if known is not None:
-            return self._denoise_known(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta,
-                                       known, mask, known_noise, start_step)
-        if mask is not None or known_noise is not None or start_step != 0:
+            windowed = latents.shape[2] > int(window_length)
+        if known is None and (mask is not None or known_noise is not None or start_step != 0):
             raise ValueError("`mask`, `known_noise` and `start_step` need `known` latents")
         dev = latents.device
-        sch = self.scheduler
-        sch.set_timesteps(num_inference_steps)
-        # Euler's timesteps are fractional (linspace) and reach the UNet as they are; DDPM / DDIM timesteps are integers
-        fractional = bool(getattr(sch, "fractional_timesteps", False))
-        timesteps = [float(t) if fractional else int(t) for t in sch.timesteps]
-        # scheduler.scale_model_input (pipeline_videogen.py:667) as a scalar the fused kernel applies to the fp16 model input
-        in_scale = getattr(sch, "model_input_scale", None)
-        # `eta` goes to the scheduler only if its step takes one (DDIM), as prepare_extra_step_kwargs does
-        # (pipeline_videogen.py:431-446); DDPM ignores it
-        takes_eta = "eta" in inspect.signature(sch.coefficients).parameters
-        # a multistep scheduler says so itself (DPMSolverMultistepScheduler.multistep): its fifth coefficient is c_prev, not a
-        # noise sigma, and the step kernel keeps the previous x0 prediction in a buffer beside the fp32 latents
-        multistep = bool(getattr(sch, "multistep", False))
-        do_cfg = guidance_scale > 1.0
+        plan = sampling.StepPlan(self.scheduler, num_inference_steps, eta)
+        if known is not None and not 0 <= start_step < len(plan.timesteps):
+            raise ValueError(f"`start_step`={start_step} must lie in 0..{len(plan.timesteps) - 1}")
+        guidance = guidance_scale if guidance_scale > 1.0 else None
         x = latents.to(torch.float32).contiguous().clone()
-        x0_prev = torch.empty_like(x) if multistep else None      # never read before the first step has written it (c_prev = 0)
         p = x.shape[0]
-        nb = 2 * p if do_cfg else p                        # model batch (:666)
+        nb = 2 * p if guidance else p                      # model batch (:666)
         if ctx.shape[0] != nb:
             raise ValueError(f"ctx has {ctx.shape[0]} rows, expected {nb} for {p} latents at guidance_scale={guidance_scale}")
-        model_in = torch.empty((nb,) + tuple(x.shape[1:]), dtype=torch.float16, device=dev)
-        first_scale = in_scale(timesteps[0]) if in_scale else 1.0
-        if do_cfg:
-            ops.latents_to_model_input(x, model_in, first_scale)
+        frames, starts = x.shape[2], [0]                   # frames per forward; without windows one forward sees the whole clip
+        if windowed:
+            from . import windows
+            frames = int(window_length)
+            starts = windows.window_starts(x.shape[2], frames, int(window_stride) if window_stride is not None
+                                           else max(1, frames - frames // 4))
+            profile = windows.window_profile(frames, window_weights)
+        if known is not None:
+            if tuple(known.shape) != tuple(x.shape):
+                raise ValueError(f"`known` has shape {tuple(known.shape)}, the latents {tuple(x.shape)}")
+            known = known.to(device=dev, dtype=torch.float32).contiguous()
+            if mask is not None:
+                mask = mask.to(device=dev, dtype=torch.float32).expand(p, 1, *x.shape[2:]).contiguous()
+        noise = sampling.StepNoise(x, generator)
+        if known is not None:
+            if known_noise is None:
+                known_noise = randn_tensor(tuple(x.shape), generator=generator, device=dev, dtype=torch.float32)
+            elif tuple(known_noise.shape) != tuple(x.shape):
+                raise ValueError(f"`known_noise` has shape {tuple(known_noise.shape)}, the latents {tuple(x.shape)}")
+            known_noise = known_noise.to(device=dev, dtype=torch.float32).contiguous()
+        x0_prev = torch.empty_like(x) if plan.multistep else None     # never read before the first step has written it (c_prev = 0)
+        model_in = [torch.empty((nb, x.shape[1], frames) + tuple(x.shape[3:]), dtype=torch.float16, device=dev) for _ in starts]
+        if known is not None:
+            ops.known_blend(x, model_in[0], known, mask if start_step == 0 else None, known_noise, plan.noise_level(start_step),
+                            plan.input_scale(start_step))
         else:
-            ops.latents_to_model_input1(x, model_in, first_scale)
-        self.unet.prepare(nb, x.shape[2], x.shape[3], x.shape[4], ctx.shape[1])
-        # the context is the same tensor for every step: its keys / values are computed once (the reference recomputes
-        # them in each block of each step, attention.py:177-178)
-        ctx = self.unet.cache_context(ctx) if hasattr(self.unet, "cache_context") else ctx
-
-        # per-step noise: drawn on the host only when the caller's generator lives there, then staged through
-        # two pinned slots on a side stream so that neither the device nor the host waits for the other
-        gens = generator if isinstance(generator, list) else ([generator] if generator is not None else [])
-        if isinstance(generator, list):                    # one generator per latent, as randn_tensor takes them (:504)
-            if len(gens) != p:
-                raise ValueError(f"got a list of {len(gens)} generators for {p} latents")
-            if len({g.device.type for g in gens}) != 1:
-                raise ValueError("a list of generators must live on one device type")
-        host_noise = bool(gens) and gens[0].device.type == "cpu"
-        noise_dev = torch.empty_like(x)
-        if host_noise:
-            pinned = [torch.empty(x.shape, dtype=torch.float32).pin_memory() for _ in range(2)]
-            staged = [torch.empty_like(x) for _ in range(2)]
-            copy_done = [None, None]        # slot's H2D copy finished  -> host may refill the pinned slot
-            step_done = [None, None]        # slot's consumer finished  -> side stream may overwrite the device slot
-            if self._copy_stream is None:
-                self._copy_stream = torch.cuda.Stream(device=dev)
-        main = torch.cuda.current_stream(dev)
-        t_dev = torch.tensor(timesteps, dtype=torch.float32, device=dev)
-
-        # with guidance the two halves of model_in are the same latents (written by this loop's own step kernel): the engine may
-        # compute the layers in front of the first text cross-attention once
-        shared = do_cfg and self.cfg_shared_prefix and hasattr(self.unet, "set_cfg_shared_input")
-        try:                                     # an exception in a callback or kernel must not leave the engine holding ctx
-            if shared:
-                self.unet.set_cfg_shared_input(True)
-                if os.environ.get("LAVIE_DEBUG_CHECK_SHARED") == "1" and not torch.equal(model_in[:p], model_in[p:]):
-                    raise RuntimeError("cfg_shared_prefix: the two halves of the model input differ")
-            for i, t in enumerate(timesteps):
-                eps = self.unet(model_in, t_dev[i], encoder_hidden_states=ctx).sample      # line 670
-                coeffs = sch.coefficients(t, eta) if takes_eta else sch.coefficients(t)
-                noise = None
-                slot = i & 1
-                if not multistep and coeffs[4] != 0.0:   # the step adds noise (DDPM: every step but the last; DDIM: only with eta > 0)
-                    if host_noise:
-                        if copy_done[slot] is not None:
-                            copy_done[slot].synchronize()
-                        if isinstance(generator, list):
-                            for j, g in enumerate(gens):
-                                torch.randn(x.shape[1:], generator=g, dtype=torch.float32, out=pinned[slot][j])
-                        else:
-                            torch.randn(x.shape, generator=generator, dtype=torch.float32, out=pinned[slot])
-                        if step_done[slot] is not None:
-                            self._copy_stream.wait_event(step_done[slot])
-                        with torch.cuda.stream(self._copy_stream):
-                            staged[slot].copy_(pinned[slot], non_blocking=True)
-                        copy_done[slot] = torch.cuda.Event()
-                        copy_done[slot].record(self._copy_stream)
-                        main.wait_event(copy_done[slot])
-                        noise = staged[slot]
-                    elif isinstance(generator, list):
-                        for j, g in enumerate(gens):
-                            noise_dev[j].normal_(generator=g)
-                        noise = noise_dev
-                    else:
-                        noise = noise_dev.normal_(generator=generator) if generator is not None else noise_dev.normal_()
-                next_scale = in_scale(timesteps[i + 1]) if in_scale and i + 1 < len(timesteps) else 1.0
-                if multistep:
-                    if do_cfg:
-                        ops.cfg_multistep_step(eps, x, x0_prev, model_in, guidance_scale, coeffs, next_scale)
-                    else:
-                        ops.multistep_step(eps, x, x0_prev, model_in, coeffs, next_scale)
-                elif do_cfg:
-                    ops.cfg_ddpm_step(eps, x, noise, model_in, guidance_scale, coeffs, next_scale)   # lines 667, 679-683 fused
+            for s, m in zip(starts, model_in):
+                (ops.latents_to_model_input if guidance else ops.latents_to_model_input1)(
+                    x[:, :, s:s + frames].contiguous(), m, plan.input_scale(0))
+        t_dev = plan.t_dev(dev)
+        # with guidance the two halves of every model input are the same latents (one fp16 value written into both by this loop's
+        # own step kernel, pinned or not, windowed or not): the engine may compute the layers in front of the first text
+        # cross-attention once
+        region = None
+        with sampling.engine_session(self.unet, nb, frames, x.shape[3], x.shape[4], ctx,
+                                     model_in if guidance and self.cfg_shared_prefix else None) as ctx:
+            forwards = sampling.WindowForwards(lambda w, i: self.unet(model_in[w], t_dev[i], encoder_hidden_states=ctx).sample)
+            for i in range(start_step, len(plan.timesteps)):
+                eps = forwards(len(model_in), i)                                                      # line 670
+                coeffs = plan.coeffs(i, first=start_step > 0 and i == start_step)
+                aux = x0_prev if plan.multistep else noise.draw() if plan.adds_noise(coeffs) else None
+                if windowed:
+                    ops.window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, plan.input_scale(i + 1),
+                                    multistep=plan.multistep)
                 else:
-                    ops.sampler_step(eps, x, noise, model_in, coeffs, next_scale)                    # lines 667, 683
-                if host_noise and noise is not None:
-                    step_done[slot] = torch.cuda.Event()
-                    step_done[slot].record(main)
+                    if mask is not None:                   # without a mask nothing is pinned: the plain step kernels
+                        region = (known, mask, known_noise, plan.noise_level(i + 1))
+                    sampling.step(eps[0], x, aux, model_in[0], guidance, coeffs, plan.input_scale(i + 1), plan.multistep, region)
+                noise.done()
                 if callback is not None and i % callback_steps == 0:
-                    callback(i, t, x)
-        finally:
-            # clean-up must not mask an exception raised inside the loop: each call is attempted, a failure of its own is re-raised
-            # only when the loop itself finished
-            pending = sys.exc_info()[1]
-            cleanup_error = None
-            for undo in ((lambda: self.unet.set_cfg_shared_input(False)) if shared else None,
-                         (lambda: self.unet.cache_context(None)) if hasattr(self.unet, "cache_context") else None):
-                if undo is None:
-                    continue
-                try:
-                    undo()
-                except Exception as e:      # noqa: BLE001
-                    cleanup_error = cleanup_error or e
-            if cleanup_error is not None and pending is None:
-                raise cleanup_error
-        return x
-
-    # ------------------------------------------------------------------ the loop around known latents
-    @torch.no_grad()
-    def _denoise_known(self, latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta, known,
-                       mask, known_noise, start_step) -> torch.Tensor:
-        """The loop of `denoise` around known clean latents (the known-region replacement of diffusers' legacy inpaint /
-        img2img loop), still one step launch per denoising step: after every step the step kernel itself overwrites the part
-        `mask` pins (1 = keep `known`, 0 = free, [P, 1, F, h, w] or broadcastable to it) with `known` re-noised to the level
-        the step just reached, x_t = a known + s known_noise, and the last step lands on `known` itself.  `known_noise` is ONE
-        tensor for the whole run (drawn from `generator` before the loop when not given).
-        start_step = 0: x starts as `latents` with the pinned part replaced.  start_step > 0 (a run at reduced strength): the loop
-        runs timesteps[start_step:] and x starts as `known` noised to timesteps[start_step] everywhere, `latents` only gives the
-        shape.  mask = None pins nothing during the steps (plain img2img).
-        The step's own noise (DDPM, DDIM with eta > 0) is drawn per step as in `denoise`, without its two-slot host staging."""
-        dev = latents.device
-        sch = self.scheduler
-        sch.set_timesteps(num_inference_steps)
-        fractional = bool(getattr(sch, "fractional_timesteps", False))
-        timesteps = [float(t) if fractional else int(t) for t in sch.timesteps]
-        if not 0 <= start_step < len(timesteps):
-            raise ValueError(f"`start_step`={start_step} must lie in 0..{len(timesteps) - 1}")
-        in_scale = getattr(sch, "model_input_scale", None)
-        takes_eta = "eta" in inspect.signature(sch.coefficients).parameters
-        multistep = bool(getattr(sch, "multistep", False))
-        do_cfg = guidance_scale > 1.0
-        x = latents.to(torch.float32).contiguous().clone()
-        p = x.shape[0]
-        nb = 2 * p if do_cfg else p
-        if ctx.shape[0] != nb:
-            raise ValueError(f"ctx has {ctx.shape[0]} rows, expected {nb} for {p} latents at guidance_scale={guidance_scale}")
-        if tuple(known.shape) != tuple(x.shape):
-            raise ValueError(f"`known` has shape {tuple(known.shape)}, the latents {tuple(x.shape)}")
-        known = known.to(device=dev, dtype=torch.float32).contiguous()
-        if mask is not None:
-            mask = mask.to(device=dev, dtype=torch.float32).expand(p, 1, *x.shape[2:]).contiguous()
-        gens = generator if isinstance(generator, list) else ([generator] if generator is not None else [])
-        if isinstance(generator, list):
-            if len(gens) != p:
-                raise ValueError(f"got a list of {len(gens)} generators for {p} latents")
-            if len({g.device.type for g in gens}) != 1:
-                raise ValueError("a list of generators must live on one device type")
-        if known_noise is None:
-            known_noise = randn_tensor(tuple(x.shape), generator=generator, device=dev, dtype=torch.float32)
-        elif tuple(known_noise.shape) != tuple(x.shape):
-            raise ValueError(f"`known_noise` has shape {tuple(known_noise.shape)}, the latents {tuple(x.shape)}")
-        known_noise = known_noise.to(device=dev, dtype=torch.float32).contiguous()
-        x0_prev = torch.empty_like(x) if multistep else None
-        model_in = torch.empty((nb,) + tuple(x.shape[1:]), dtype=torch.float16, device=dev)
-        first = timesteps[start_step]
-        ops.known_blend(x, model_in, known, mask if start_step == 0 else None, known_noise, sch.noise_level(first),
-                        in_scale(first) if in_scale else 1.0)
-        self.unet.prepare(nb, x.shape[2], x.shape[3], x.shape[4], ctx.shape[1])
-        ctx = self.unet.cache_context(ctx) if hasattr(self.unet, "cache_context") else ctx
-        host_noise = bool(gens) and gens[0].device.type == "cpu"
-        noise_dev = torch.empty_like(x)
-        t_dev = torch.tensor(timesteps, dtype=torch.float32, device=dev)
-        # the step kernel writes one fp16 value into both halves of model_in, pinned or not: cfg_shared_prefix holds
-        shared = do_cfg and self.cfg_shared_prefix and hasattr(self.unet, "set_cfg_shared_input")
-        try:
-            if shared:
-                self.unet.set_cfg_shared_input(True)
-                if os.environ.get("LAVIE_DEBUG_CHECK_SHARED") == "1" and not torch.equal(model_in[:p], model_in[p:]):
-                    raise RuntimeError("cfg_shared_prefix: the two halves of the model input differ")
-            for i in range(start_step, len(timesteps)):
-                t = timesteps[i]
-                eps = self.unet(model_in, t_dev[i], encoder_hidden_states=ctx).sample
-                coeffs = sch.coefficients(t, eta) if takes_eta else sch.coefficients(t)
-                if multistep and i == start_step:
-                    coeffs = tuple(coeffs[:4]) + (0.0,)        # a late start has no x0 history yet: this step is first order
-                noise = None
-                if not multistep and coeffs[4] != 0.0:
-                    if host_noise and isinstance(generator, list):
-                        noise = torch.stack([torch.randn(x.shape[1:], generator=g, dtype=torch.float32) for g in gens]).to(dev)
-                    elif host_noise:
-                        noise = torch.randn(x.shape, generator=generator, dtype=torch.float32).to(dev)
-                    elif isinstance(generator, list):
-                        for j, g in enumerate(gens):
-                            noise_dev[j].normal_(generator=g)
-                        noise = noise_dev
-                    else:
-                        noise = noise_dev.normal_(generator=generator) if generator is not None else noise_dev.normal_()
-                last = i + 1 == len(timesteps)
-                next_scale = in_scale(timesteps[i + 1]) if in_scale and not last else 1.0
-                level = sch.noise_level(None if last else timesteps[i + 1])
-                if mask is None:                           # nothing pinned: the plain step kernels
-                    if multistep and do_cfg:
-                        ops.cfg_multistep_step(eps, x, x0_prev, model_in, guidance_scale, coeffs, next_scale)
-                    elif multistep:
-                        ops.multistep_step(eps, x, x0_prev, model_in, coeffs, next_scale)
-                    elif do_cfg:
-                        ops.cfg_ddpm_step(eps, x, noise, model_in, guidance_scale, coeffs, next_scale)
-                    else:
-                        ops.sampler_step(eps, x, noise, model_in, coeffs, next_scale)
-                elif multistep and do_cfg:
-                    ops.cfg_multistep_step_known(eps, x, x0_prev, model_in, guidance_scale, coeffs, next_scale, known, mask,
-                                                 known_noise, level)
-                elif multistep:
-                    ops.multistep_step_known(eps, x, x0_prev, model_in, coeffs, next_scale, known, mask, known_noise, level)
-                elif do_cfg:
-                    ops.cfg_sampler_step_known(eps, x, noise, model_in, guidance_scale, coeffs, next_scale, known, mask,
-                                               known_noise, level)
-                else:
-                    ops.sampler_step_known(eps, x, noise, model_in, coeffs, next_scale, known, mask, known_noise, level)
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, x)
-        finally:
-            pending = sys.exc_info()[1]
-            cleanup_error = None
-            for undo in ((lambda: self.unet.set_cfg_shared_input(False)) if shared else None,
-                         (lambda: self.unet.cache_context(None)) if hasattr(self.unet, "cache_context") else None):
-                if undo is None:
-                    continue
-                try:
-                    undo()
-                except Exception as e:      # noqa: BLE001
-                    cleanup_error = cleanup_error or e
-            if cleanup_error is not None and pending is None:
-                raise cleanup_error
-        return x
-
-    # ------------------------------------------------------------------ the loop over overlapping frame windows
-    @torch.no_grad()
-    def _denoise_windowed(self, latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta,
-                          window_length, window_stride, window_weights) -> torch.Tensor:
-        """The loop of `denoise` for a clip longer than the model's window (MultiDiffusion along the frame axis): ONE latent
-        tensor holds all F frames; per step the UNet runs on every window of `window_length` frames (starts 0, stride, 2 stride,
-        ..., the last one clamped to the clip's end: lavie_amd.windows), then ONE launch (ops.window_step) averages the windows'
-        noise predictions per frame with the normalised `window_weights` profile, advances the whole clip by one scheduler step
-        and writes every window's next fp16 model input.  `window_stride` defaults to three quarters of the window.  A frame that
-        one window covers gets the plain step's bits.  The engine is prepared and the context cached once, for the window shape.
-        The step's own noise (DDPM, DDIM with eta > 0) is drawn per step for the whole clip, as in `_denoise_known`."""
-        from . import windows
-        dev = latents.device
-        sch = self.scheduler
-        sch.set_timesteps(num_inference_steps)
-        fractional = bool(getattr(sch, "fractional_timesteps", False))
-        timesteps = [float(t) if fractional else int(t) for t in sch.timesteps]
-        in_scale = getattr(sch, "model_input_scale", None)
-        takes_eta = "eta" in inspect.signature(sch.coefficients).parameters
-        multistep = bool(getattr(sch, "multistep", False))
-        do_cfg = guidance_scale > 1.0
-        x = latents.to(torch.float32).contiguous().clone()
-        p, length = x.shape[0], window_length
-        nb = 2 * p if do_cfg else p
-        if ctx.shape[0] != nb:
-            raise ValueError(f"ctx has {ctx.shape[0]} rows, expected {nb} for {p} latents at guidance_scale={guidance_scale}")
-        stride = int(window_stride) if window_stride is not None else max(1, length - length // 4)
-        starts = windows.window_starts(x.shape[2], length, stride)
-        profile = windows.window_profile(length, window_weights)
-        gens = generator if isinstance(generator, list) else ([generator] if generator is not None else [])
-        if isinstance(generator, list):
-            if len(gens) != p:
-                raise ValueError(f"got a list of {len(gens)} generators for {p} latents")
-            if len({g.device.type for g in gens}) != 1:
-                raise ValueError("a list of generators must live on one device type")
-        host_noise = bool(gens) and gens[0].device.type == "cpu"
-        x0_prev = torch.empty_like(x) if multistep else None      # never read before the first step has written it (c_prev = 0)
-        noise_dev = torch.empty_like(x)
-        first_scale = in_scale(timesteps[0]) if in_scale else 1.0
-        win_shape = (nb, x.shape[1], length) + tuple(x.shape[3:])
-        model_in = [torch.empty(win_shape, dtype=torch.float16, device=dev) for _ in starts]
-        for s, m in zip(starts, model_in):
-            xw = x[:, :, s:s + length].contiguous()
-            (ops.latents_to_model_input if do_cfg else ops.latents_to_model_input1)(xw, m, first_scale)
-        self.unet.prepare(nb, length, x.shape[3], x.shape[4], ctx.shape[1])
-        ctx = self.unet.cache_context(ctx) if hasattr(self.unet, "cache_context") else ctx
-        t_dev = torch.tensor(timesteps, dtype=torch.float32, device=dev)
-        # all W predictions are held until the step: a UNet that hands back one buffer per shape (enable_graph) needs copies.
-        # Unknown until two forwards of one step have been seen; None = not decided yet
-        reuses_output = None
-        # the step kernel writes one fp16 value into both halves of every window's model input: cfg_shared_prefix holds
-        shared = do_cfg and self.cfg_shared_prefix and hasattr(self.unet, "set_cfg_shared_input")
-        try:
-            if shared:
-                self.unet.set_cfg_shared_input(True)
-            for i, t in enumerate(timesteps):
-                eps = []
-                for w, m in enumerate(model_in):
-                    e = self.unet(m, t_dev[i], encoder_hidden_states=ctx).sample
-                    if reuses_output is None and w == 1:
-                        reuses_output = e.data_ptr() == eps[0].data_ptr()
-                        if reuses_output:                 # the second forward has overwritten the first prediction: redo that one
-                            e = e.clone()
-                            eps[0] = self.unet(model_in[0], t_dev[i], encoder_hidden_states=ctx).sample.clone()
-                    elif reuses_output:
-                        e = e.clone()
-                    eps.append(e)
-                coeffs = sch.coefficients(t, eta) if takes_eta else sch.coefficients(t)
-                aux = x0_prev
-                if not multistep and coeffs[4] != 0.0:
-                    if host_noise and isinstance(generator, list):
-                        aux = torch.stack([torch.randn(x.shape[1:], generator=g, dtype=torch.float32) for g in gens]).to(dev)
-                    elif host_noise:
-                        aux = torch.randn(x.shape, generator=generator, dtype=torch.float32).to(dev)
-                    elif isinstance(generator, list):
-                        for j, g in enumerate(gens):
-                            noise_dev[j].normal_(generator=g)
-                        aux = noise_dev
-                    else:
-                        aux = noise_dev.normal_(generator=generator) if generator is not None else noise_dev.normal_()
-                next_scale = in_scale(timesteps[i + 1]) if in_scale and i + 1 < len(timesteps) else 1.0
-                ops.window_step(eps, x, aux, model_in, starts, profile, guidance_scale if do_cfg else None, coeffs, next_scale,
-                                multistep=multistep)
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, x)
-        finally:
-            pending = sys.exc_info()[1]
-            cleanup_error = None
-            for undo in ((lambda: self.unet.set_cfg_shared_input(False)) if shared else None,
-                         (lambda: self.unet.cache_context(None)) if hasattr(self.unet, "cache_context") else None):
-                if undo is None:
-                    continue
-                try:
-                    undo()
-                except Exception as e:      # noqa: BLE001
-                    cleanup_error = cleanup_error or e
-            if cleanup_error is not None and pending is None:
-                raise cleanup_error
+                    callback(i, plan.timesteps[i], x)
         return x
 
     @staticmethod
@@ -706,14 +438,14 @@ class VideoGenPipeline:
                                   negative_prompt_embeds, image_features).to(torch.float16).contiguous()
         latents = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.config.in_channels, video_length,
                                        height, width, torch.float32, device, generator, latents)
-        # sampling around known latents (pinned frames, video-to-video, clip continuation): `_denoise_known`
+        # sampling around known latents (pinned frames, video-to-video, clip continuation): `denoise(known=)`
         self.check_known_inputs(known_latents, known_mask, video, strength, latents.shape)
         around = {}
         if video is not None or known_latents is not None:
             known = self.encode_video(video) if video is not None else known_latents
             around = dict(known=known.to(device=device, dtype=torch.float32), mask=known_mask,
                           start_step=self.strength_start(num_inference_steps, strength))
-        elif window_length is not None:    # clips longer than the window: overlapping frame windows, `_denoise_windowed`
+        elif window_length is not None:    # clips longer than the window: overlapping frame windows
             around = dict(window_length=window_length, window_stride=window_stride, window_weights=window_weights)
         lora_scale = (cross_attention_kwargs or {}).get("scale")
         if lora_scale is None:

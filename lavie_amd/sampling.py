@@ -1,0 +1,201 @@
+"""What every denoising loop of this package shares, each piece once: the step plan (timesteps and per-step scalars of a
+scheduler), the step's noise (four generator kinds, host draws staged through pinned memory), the engine session (prepare,
+cached context, shared CFG input and their non-masking clean-up), the choice among the eight fused step ops, and the forwards
+of a windowed step.  The loops (`VideoGenPipeline.denoise`, `VideoUpscalePipeline.denoise`, `SpacedDiffusion._ddim_loop_hip`)
+keep what is theirs: which tensors reach the UNet, which step family runs, and the callback."""
+import contextlib
+import inspect
+import os
+import sys
+
+import torch
+
+from . import ops
+
+
+class StepPlan:
+    """The timesteps of `scheduler` at `num_inference_steps` and the scalars of step i (a position in `timesteps`)."""
+
+    def __init__(self, scheduler, num_inference_steps: int, eta: float = 0.0):
+        scheduler.set_timesteps(num_inference_steps)
+        # Euler's timesteps are fractional (linspace) and reach the UNet as they are; DDPM / DDIM timesteps are integers
+        fractional = bool(getattr(scheduler, "fractional_timesteps", False))
+        self.timesteps = [float(t) if fractional else int(t) for t in scheduler.timesteps]
+        # a multistep scheduler says so itself (DPMSolverMultistepScheduler.multistep): its fifth coefficient is c_prev, not a
+        # noise sigma, and the step kernel keeps the previous x0 prediction in a buffer beside the fp32 latents
+        self.multistep = bool(getattr(scheduler, "multistep", False))
+        self._scheduler = scheduler
+        # `eta` goes to the scheduler only if its step takes one (DDIM), as prepare_extra_step_kwargs does
+        # (pipeline_videogen.py:431-446); DDPM ignores it
+        self._eta = (eta,) if "eta" in inspect.signature(scheduler.coefficients).parameters else ()
+        # scheduler.scale_model_input (pipeline_videogen.py:667) as a scalar the fused kernel applies to the fp16 model input
+        self._in_scale = getattr(scheduler, "model_input_scale", None)
+
+    def t_dev(self, device) -> torch.Tensor:
+        return torch.tensor(self.timesteps, dtype=torch.float32, device=device)
+
+    def coeffs(self, i: int, first: bool = False):
+        """The scheduler's five coefficients of step i.  `first`: the run starts at this step, so a multistep scheduler has no
+        x0 history yet and the step is first order (c_prev = 0; at position 0 the scheduler says so itself)."""
+        c = self._scheduler.coefficients(self.timesteps[i], *self._eta)
+        return tuple(c[:4]) + (0.0,) if first and self.multistep else c
+
+    def adds_noise(self, coeffs) -> bool:
+        """DDPM: every step but the last; DDIM: only with eta > 0; a multistep scheduler's fifth coefficient is no sigma."""
+        return not self.multistep and coeffs[4] != 0.0
+
+    def input_scale(self, i: int) -> float:
+        """Scale of the model input of step i; 1.0 without `model_input_scale` or past the last step."""
+        return self._in_scale(self.timesteps[i]) if self._in_scale and i < len(self.timesteps) else 1.0
+
+    def noise_level(self, i_next: int):
+        """(a, s) the known latents are re-noised with after the step in front of position `i_next`: (1, 0) past the end."""
+        return self._scheduler.noise_level(self.timesteps[i_next] if i_next < len(self.timesteps) else None)
+
+
+# device -> the one copy stream of every StepNoise on that device, for the life of the process.  Shared on purpose: a loop keeps
+# no stream of its own, so a pipeline call does not start on a stream the runtime has never submitted to.  Safe because nothing
+# relies on the stream's identity: each slot's copy is ordered behind that slot's last consumer and in front of its next one by
+# events that belong to the StepNoise object, so two objects on one stream can only wait for each other, never read each other.
+_side_streams = {}
+
+
+class StepNoise:
+    """Per-step fp32 noise shaped as `x`, on x's device, from `generator`: None, one generator or one per latent (as
+    randn_tensor takes them, :504), on the host or the device.  Host draws for a device tensor are staged through two pinned
+    slots on a side stream so that neither the device nor the host waits for the other: `draw()` makes the main stream wait
+    for the slot's copy, `done()` after the consuming launch lets the side stream overwrite the slot two draws later."""
+
+    def __init__(self, x: torch.Tensor, generator=None):
+        self._per_latent = isinstance(generator, list)
+        self._gens = generator if self._per_latent else [generator]
+        if self._per_latent:
+            if len(self._gens) != x.shape[0]:
+                raise ValueError(f"got a list of {len(self._gens)} generators for {x.shape[0]} latents")
+            if len({g.device.type for g in self._gens}) != 1:
+                raise ValueError("a list of generators must live on one device type")
+        self._staged = x.is_cuda and self._gens[0] is not None and self._gens[0].device.type == "cpu"
+        self._pending = None            # the slot whose consumer has not been launched yet
+        if not self._staged:            # drawn where x lives
+            self._noise = torch.empty_like(x)
+            return
+        self._pinned = [torch.empty(x.shape, dtype=torch.float32).pin_memory() for _ in range(2)]
+        self._noise = [torch.empty_like(x) for _ in range(2)]
+        self._copy_done = [None, None]  # slot's H2D copy finished  -> host may refill the pinned slot
+        self._step_done = [None, None]  # slot's consumer finished  -> side stream may overwrite the device slot
+        if x.device not in _side_streams:
+            _side_streams[x.device] = torch.cuda.Stream(device=x.device)
+        self._side = _side_streams[x.device]
+        self._main = torch.cuda.current_stream(x.device)
+        self._draws = 0
+
+    def _fill(self, out):
+        if self._per_latent:
+            for j, g in enumerate(self._gens):
+                out[j].normal_(generator=g)
+        else:
+            out.normal_(generator=self._gens[0])
+        return out
+
+    def draw(self) -> torch.Tensor:
+        if not self._staged:
+            return self._fill(self._noise)
+        slot = self._draws & 1
+        self._draws += 1
+        if self._copy_done[slot] is not None:
+            self._copy_done[slot].synchronize()
+        self._fill(self._pinned[slot])
+        if self._step_done[slot] is not None:
+            self._side.wait_event(self._step_done[slot])
+        with torch.cuda.stream(self._side):
+            self._noise[slot].copy_(self._pinned[slot], non_blocking=True)
+        self._copy_done[slot] = torch.cuda.Event()
+        self._copy_done[slot].record(self._side)
+        self._main.wait_event(self._copy_done[slot])
+        self._pending = slot
+        return self._noise[slot]
+
+    def done(self):
+        """Call after the launch that consumed the last `draw()` (harmless when the step drew none)."""
+        if self._pending is not None:
+            self._step_done[self._pending] = torch.cuda.Event()
+            self._step_done[self._pending].record(self._main)
+            self._pending = None
+
+
+@contextlib.contextmanager
+def engine_session(unet, batch: int, frames: int, height: int, width: int, ctx: torch.Tensor, shared_inputs=None):
+    """The engine prepared for [batch, C, frames, height, width] with `ctx` cached for the whole loop (its keys / values are
+    computed once; the reference recomputes them in each block of each step, attention.py:177-178); yields the context to pass
+    to the UNet.  `shared_inputs`: the loop's fp16 model inputs when both CFG halves of each hold the same latents (written by
+    the loop's own step kernel), so the engine may compute the layers in front of the first text cross-attention once;
+    LAVIE_DEBUG_CHECK_SHARED=1 checks every one of them.  A UNet without `cache_context` / `set_cfg_shared_input` runs without.
+    On exit the engine lets go of both, also after an exception in the loop, which clean-up never masks: each undo is attempted
+    and a failure of its own is re-raised only when the loop itself finished."""
+    unet.prepare(batch, frames, height, width, ctx.shape[1])
+    caches = hasattr(unet, "cache_context")
+    if caches:
+        ctx = unet.cache_context(ctx)
+    shared = shared_inputs is not None and hasattr(unet, "set_cfg_shared_input")
+    try:
+        if shared:
+            unet.set_cfg_shared_input(True)
+            if os.environ.get("LAVIE_DEBUG_CHECK_SHARED") == "1":
+                for m in shared_inputs:
+                    if not torch.equal(m[:m.shape[0] // 2], m[m.shape[0] // 2:]):
+                        raise RuntimeError("cfg_shared_prefix: the two halves of the model input differ")
+        yield ctx
+    finally:
+        pending = sys.exc_info()[1]
+        cleanup_error = None
+        for undo in ((lambda: unet.set_cfg_shared_input(False)) if shared else None,
+                     (lambda: unet.cache_context(None)) if caches else None):
+            if undo is None:
+                continue
+            try:
+                undo()
+            except Exception as e:      # noqa: BLE001
+                cleanup_error = cleanup_error or e
+        if cleanup_error is not None and pending is None:
+            raise cleanup_error
+
+
+def step(eps, x, aux, model_in, guidance_scale, coeffs, next_scale, multistep: bool, region=None):
+    """One fused scheduler step through the `ops` wrapper of its family.  `aux`: the step's noise or None (five-coefficient
+    family), the x0 history (multistep).  `guidance_scale` None: no classifier-free guidance.  `region`: None, or
+    (known, mask, known_noise, level) of a run around known latents.  The wrappers are looked up on `ops` at call time."""
+    guided = guidance_scale is not None
+    if multistep:
+        name = "cfg_multistep_step" if guided else "multistep_step"
+    elif region is not None:
+        name = "cfg_sampler_step" if guided else "sampler_step"
+    else:
+        name = "cfg_ddpm_step" if guided else "sampler_step"     # lines 667, 679-683 fused
+    if region is not None:
+        name += "_known"
+    args = (eps, x, aux, model_in) + ((guidance_scale,) if guided else ()) + (coeffs, next_scale) + tuple(region or ())
+    getattr(ops, name)(*args)
+
+
+class WindowForwards:
+    """The W noise predictions of one windowed step, all alive until the step kernel has read them.  `forward(w, i)` runs the
+    UNet on window w at step i.  A UNet that hands back one buffer per shape (enable_graph) needs copies; whether it does is
+    unknown until two forwards of one step have been seen."""
+
+    def __init__(self, forward):
+        self._forward = forward
+        self._reuses_output = None      # None = not decided yet
+
+    def __call__(self, count: int, i: int) -> list:
+        eps = []
+        for w in range(count):
+            e = self._forward(w, i)
+            if self._reuses_output is None and w == 1:
+                self._reuses_output = e.data_ptr() == eps[0].data_ptr()
+                if self._reuses_output:     # the second forward has overwritten the first prediction: redo that one
+                    e = e.clone()
+                    eps[0] = self._forward(0, i).clone()
+            elif self._reuses_output:
+                e = e.clone()
+            eps.append(e)
+        return eps

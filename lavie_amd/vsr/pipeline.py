@@ -9,13 +9,12 @@ scheduler update in its five-coefficient form and writes the next fp16 model inp
 `lavie_cfg_multistep_step` with an x0 history that lives for one call, so for one chunk).  Text encoder and VAE are stock
 PyTorch-ROCm objects a caller may attach (outside the latents metric): without them pass `prompt_embeds` and use
 `output_type="latent"`."""
-import inspect
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Union
 
 import torch
 
-from .. import ops
+from .. import ops, sampling
 from ..scheduling_ddpm import DDPMScheduler, randn_tensor
 
 
@@ -72,114 +71,59 @@ class VideoUpscalePipeline:
                 callback: Optional[Callable] = None, callback_steps: int = 1, window_length: Optional[int] = None,
                 window_stride: Optional[int] = None, window_weights: str = "triangle") -> torch.Tensor:
         """latents fp32 [P, 4, F, h, w]; image = the NOISED low-res frames [P, 3, F, h, w]; ctx fp16 [2P, n, d] =
-        [negative | prompt] -> denoised latents fp32.  `window_length` below F: the clip is sampled as overlapping frame
-        windows of that many frames, fused in the step kernel (`_denoise_windowed`)."""
-        if guidance_scale <= 1.0:
-            raise NotImplementedError("guidance_scale <= 1 (no classifier-free guidance) is outside the fused MI355X loop")
-        if window_length is not None:
-            if int(window_length) < 1:
-                raise ValueError(f"`window_length`={window_length} must be >= 1")
-            if latents.shape[2] > int(window_length):
-                return self._denoise_windowed(latents, image, ctx, noise_level, num_inference_steps, guidance_scale, eta, generator,
-                                              callback, callback_steps, int(window_length), window_stride, window_weights)
-        dev = latents.device
-        sch = self.scheduler
-        sch.set_timesteps(num_inference_steps)
-        fractional = bool(getattr(sch, "fractional_timesteps", False))
-        timesteps = [float(t) if fractional else int(t) for t in sch.timesteps]
-        takes_eta = "eta" in inspect.signature(sch.coefficients).parameters
-        in_scale = getattr(sch, "model_input_scale", None)
-        multistep = bool(getattr(sch, "multistep", False))      # DPM-Solver++: coeffs[4] is c_prev and the kernel keeps an x0 history
-        x = latents.to(torch.float32).contiguous().clone()
-        x0_prev = torch.empty_like(x) if multistep else None    # per call, so per chunk: the first step (c_prev = 0) never reads it
-        p = x.shape[0]
-        model_in = torch.empty((2 * p,) + tuple(x.shape[1:]), dtype=torch.float16, device=dev)
-        ops.latents_to_model_input(x, model_in, in_scale(timesteps[0]) if in_scale else 1.0)
-        low = torch.cat([image, image], dim=0).to(device=dev, dtype=torch.float16).contiguous()       # :641
-        labels = torch.full((2 * p,), int(noise_level), dtype=torch.int64)                              # :644
-        noise_dev = torch.empty_like(x)
-        t_dev = torch.tensor(timesteps, dtype=torch.float32, device=dev)
-        self.unet.prepare(2 * p, x.shape[2], x.shape[3], x.shape[4], ctx.shape[1])
-        ctx = self.unet.cache_context(ctx)       # text keys / values once per chunk, not once per block and step
-        try:                                     # an exception in a callback or kernel must not leave the engine holding ctx
-            for i, t in enumerate(timesteps):
-                eps = self.unet(model_in, t_dev[i], low, encoder_hidden_states=ctx, class_labels=labels).sample        # :716-718
-                coeffs = sch.coefficients(t, eta) if takes_eta else sch.coefficients(t)
-                noise = None
-                if not multistep and coeffs[4] != 0.0:
-                    noise = noise_dev.copy_(randn_tensor(x.shape, generator=generator, device=dev, dtype=torch.float32))
-                next_scale = in_scale(timesteps[i + 1]) if in_scale and i + 1 < len(timesteps) else 1.0
-                if multistep:
-                    ops.cfg_multistep_step(eps, x, x0_prev, model_in, guidance_scale, coeffs, next_scale)
-                else:
-                    ops.cfg_ddpm_step(eps, x, noise, model_in, guidance_scale, coeffs, next_scale)                      # :721-726
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, x)
-        finally:
-            self.unet.cache_context(None)
-        return x
+        [negative | prompt] -> denoised latents fp32.  Step plan, step noise, engine session and step dispatch are
+        lavie_amd.sampling's.
 
-    @torch.no_grad()
-    def _denoise_windowed(self, latents, image, ctx, noise_level, num_inference_steps, guidance_scale, eta, generator, callback,
-                          callback_steps, window_length, window_stride, window_weights) -> torch.Tensor:
-        """The loop of `denoise` for a clip longer than the model's window: ONE latent tensor holds all F frames (and one x0
+        `window_length` below F, for a clip longer than the model's window: ONE latent tensor holds all F frames (and one x0
         history for a multistep scheduler); per step the UNet runs on every window of `window_length` frames with that window's
         slice of the low-res frames (sliced once, before the loop), then ONE launch (ops.window_step) averages the windows' noise
         predictions per frame with the normalised `window_weights` profile, advances the whole clip by one scheduler step and
         writes every window's next fp16 model input.  `window_stride` defaults to three quarters of the window.  Unlike
         independent chunks, neighbouring windows share their overlap frames at every step, so there is no seam between them."""
-        from .. import windows
+        if guidance_scale <= 1.0:
+            raise NotImplementedError("guidance_scale <= 1 (no classifier-free guidance) is outside the fused MI355X loop")
+        windowed = False
+        if window_length is not None:
+            if int(window_length) < 1:
+                raise ValueError(f"`window_length`={window_length} must be >= 1")
+            windowed = latents.shape[2] > int(window_length)
         dev = latents.device
-        sch = self.scheduler
-        sch.set_timesteps(num_inference_steps)
-        fractional = bool(getattr(sch, "fractional_timesteps", False))
-        timesteps = [float(t) if fractional else int(t) for t in sch.timesteps]
-        takes_eta = "eta" in inspect.signature(sch.coefficients).parameters
-        in_scale = getattr(sch, "model_input_scale", None)
-        multistep = bool(getattr(sch, "multistep", False))
+        plan = sampling.StepPlan(self.scheduler, num_inference_steps, eta)
         x = latents.to(torch.float32).contiguous().clone()
-        x0_prev = torch.empty_like(x) if multistep else None
-        p, length = x.shape[0], window_length
-        stride = int(window_stride) if window_stride is not None else max(1, length - length // 4)
-        starts = windows.window_starts(x.shape[2], length, stride)
-        profile = windows.window_profile(length, window_weights)
-        first_scale = in_scale(timesteps[0]) if in_scale else 1.0
-        win_shape = (2 * p, x.shape[1], length) + tuple(x.shape[3:])
-        model_in = [torch.empty(win_shape, dtype=torch.float16, device=dev) for _ in starts]
+        x0_prev = torch.empty_like(x) if plan.multistep else None    # per call, so per chunk: the first step (c_prev = 0) never reads it
+        p = x.shape[0]
+        frames, starts = x.shape[2], [0]                   # frames per forward; without windows one forward sees the whole clip
+        if windowed:
+            from .. import windows
+            frames = int(window_length)
+            starts = windows.window_starts(x.shape[2], frames, int(window_stride) if window_stride is not None
+                                           else max(1, frames - frames // 4))
+            profile = windows.window_profile(frames, window_weights)
+        model_in = [torch.empty((2 * p, x.shape[1], frames) + tuple(x.shape[3:]), dtype=torch.float16, device=dev) for _ in starts]
         low = []
         for s, m in zip(starts, model_in):
-            ops.latents_to_model_input(x[:, :, s:s + length].contiguous(), m, first_scale)
-            img = image[:, :, s:s + length]
-            low.append(torch.cat([img, img], dim=0).to(device=dev, dtype=torch.float16).contiguous())
-        labels = torch.full((2 * p,), int(noise_level), dtype=torch.int64)
-        noise_dev = torch.empty_like(x)
-        t_dev = torch.tensor(timesteps, dtype=torch.float32, device=dev)
-        self.unet.prepare(2 * p, length, x.shape[3], x.shape[4], ctx.shape[1])
-        ctx = self.unet.cache_context(ctx)       # once for the whole clip, not once per window
-        reuses_output = None                     # does the UNet hand back one buffer per shape?  Known after two forwards of a step
-        try:
-            for i, t in enumerate(timesteps):
-                eps = []
-                for w, m in enumerate(model_in):
-                    e = self.unet(m, t_dev[i], low[w], encoder_hidden_states=ctx, class_labels=labels).sample
-                    if reuses_output is None and w == 1:
-                        reuses_output = e.data_ptr() == eps[0].data_ptr()
-                        if reuses_output:         # the second forward has overwritten the first prediction: redo that one
-                            e = e.clone()
-                            eps[0] = self.unet(model_in[0], t_dev[i], low[0], encoder_hidden_states=ctx, class_labels=labels).sample.clone()
-                    elif reuses_output:
-                        e = e.clone()
-                    eps.append(e)
-                coeffs = sch.coefficients(t, eta) if takes_eta else sch.coefficients(t)
-                aux = x0_prev
-                if not multistep and coeffs[4] != 0.0:
-                    aux = noise_dev.copy_(randn_tensor(x.shape, generator=generator, device=dev, dtype=torch.float32))
-                next_scale = in_scale(timesteps[i + 1]) if in_scale and i + 1 < len(timesteps) else 1.0
-                ops.window_step(eps, x, aux, model_in, starts, profile, guidance_scale, coeffs, next_scale, multistep=multistep)
+            ops.latents_to_model_input(x[:, :, s:s + frames].contiguous(), m, plan.input_scale(0))
+            img = image[:, :, s:s + frames]
+            low.append(torch.cat([img, img], dim=0).to(device=dev, dtype=torch.float16).contiguous())                 # :641
+        labels = torch.full((2 * p,), int(noise_level), dtype=torch.int64)                                            # :644
+        noise = sampling.StepNoise(x, generator)
+        t_dev = plan.t_dev(dev)
+        # text keys / values once per chunk (or once for the whole windowed clip), not once per block and step
+        with sampling.engine_session(self.unet, 2 * p, frames, x.shape[3], x.shape[4], ctx) as ctx:
+            forwards = sampling.WindowForwards(lambda w, i: self.unet(model_in[w], t_dev[i], low[w], encoder_hidden_states=ctx,
+                                                                      class_labels=labels).sample)                    # :716-718
+            for i, t in enumerate(plan.timesteps):
+                eps = forwards(len(model_in), i)
+                coeffs = plan.coeffs(i)
+                aux = x0_prev if plan.multistep else noise.draw() if plan.adds_noise(coeffs) else None
+                if windowed:
+                    ops.window_step(eps, x, aux, model_in, starts, profile, guidance_scale, coeffs, plan.input_scale(i + 1),
+                                    multistep=plan.multistep)
+                else:                                                                                                 # :721-726
+                    sampling.step(eps[0], x, aux, model_in[0], guidance_scale, coeffs, plan.input_scale(i + 1), plan.multistep)
+                noise.done()
                 if callback is not None and i % callback_steps == 0:
                     callback(i, t, x)
-        finally:
-            self.unet.cache_context(None)
         return x
 
     @torch.no_grad()
@@ -227,7 +171,7 @@ def upscale_in_chunks(pipeline: VideoUpscalePipeline, vframes: torch.Tensor, sho
     """vsr/sample.py:104-123: clips longer than `short_seq` frames go through the pipeline `short_seq` frames at a time
     (same generator across chunks); outputs are concatenated along the frame axis.
     overlap > 0 (not in the reference): the whole clip is ONE run over windows of `short_seq` frames that share `overlap` frames
-    with their neighbours, fused at every step (`VideoUpscalePipeline._denoise_windowed`), so the chunks no longer meet at a seam."""
+    with their neighbours, fused at every step (`VideoUpscalePipeline.denoise(window_length=)`), so the chunks no longer meet at a seam."""
     total = vframes.shape[2]
     if not 0 <= overlap < short_seq:
         raise ValueError(f"overlap={overlap} must lie in 0..{short_seq - 1} (short_seq={short_seq})")

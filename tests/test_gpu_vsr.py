@@ -135,8 +135,8 @@ def build_vsr(sd, **kw):
     return net.to("cuda", torch.float16)
 
 
-@pytest.fixture(scope="module")
-def small_vsr():
+def build_small_vsr():
+    """The reduced VSR model of the pipeline tests (here, test_gpu_window_fuse.py, test_gpu_sampling.py): (net, state dict)."""
     from lavie_amd import spec
     from lavie_amd.config import UNetConfig
     cfg = UNetConfig(in_channels=7, block_out_channels=(256, 512), cross_attention_dim=128, attn_levels=(False, True),
@@ -144,6 +144,11 @@ def small_vsr():
                      num_class_embeds=1000)
     sd = G.synth16(spec.param_shapes(cfg), 31)
     return build_vsr(sd, **SMALL_VSR), sd
+
+
+@pytest.fixture(scope="module")
+def small_vsr():
+    return build_small_vsr()
 
 
 @pytest.mark.parametrize("shape", [(2, 5, 8, 8, 77), (1, 8, 8, 16, 77), (3, 2, 4, 4, 10)])

@@ -242,13 +242,8 @@ def small():
 
 @pytest.fixture(scope="module")
 def small_vsr():
-    from lavie_amd import spec
-    from lavie_amd.config import UNetConfig
-    from test_gpu_vsr import SMALL_VSR, build_vsr
-    cfg = UNetConfig(in_channels=7, block_out_channels=(256, 512), cross_attention_dim=128, attn_levels=(False, True),
-                     layers_per_block=1, vsr_blocks=True, only_cross_attention=(True, False), vsr_temporal_modules=True,
-                     num_class_embeds=1000)
-    return build_vsr(G.synth16(spec.param_shapes(cfg), 31), **SMALL_VSR)
+    from test_gpu_vsr import build_small_vsr
+    return build_small_vsr()[0]
 
 
 def make_pipe(net, method):
