@@ -459,6 +459,53 @@ int lavie_debug_fused_mask(int mask);
  * above makes every such launch ALSO run the statistics pass and compare the two on the host (synchronises; an error names the
  * first (batch, group) that differs). */
 long long lavie_debug_gn_producer_count(void);
+/* Producer-side norm statistics at operator level (additive, ABI unchanged; test hooks).  The kernels that store a tensor can leave
+ * sums and sums of squares of the rounded fp16 values they stored: per (row block, channel) for a consuming GroupNorm ("column
+ * statistics": per block and channel quad four sums, then four sums of squares), per (row, 16 NT-column wave tile) for a consuming
+ * LayerNorm ("row statistics": [M][slots][2]).  In a forward the engine asks for them; the sink below asks for them on behalf of the
+ * operator-level GEMM entry points (lavie_linear_f16, lavie_linear_lnfold_f16, lavie_conv3x3_f16, lavie_conv3x3_down_f16,
+ * lavie_upsample_conv3x3_f16, lavie_temporal_conv_f16).
+ *   colstat / rowstat: device buffers of colstat_floats / rowstat_floats floats; null or 0 disarms that kind.  While armed, every such
+ *   launch whose plan writes column statistics writes them to `colstat` (a GEGLU epilogue writes none), and a plain EPI_LINEAR
+ *   launch without a LayerNorm fold writes row statistics to `rowstat` (and is therefore planned unsplit, as in the engine).  A
+ *   buffer too small for what the planned launch stores is refused before the launch; the message names the float count.
+ * lavie_debug_op_statistics_plan(colstat, rowstat): while either is non-zero, the same entry points plan as if that kind were armed,
+ *   record the plan for the query and launch NOTHING (their outputs stay untouched): how a caller sizes the sink's buffers.
+ * lavie_debug_op_statistics_last: the plan of the last such launch.  colstat_rows / colstat_span / nsets / set_blocks are what the
+ *   engine hands a consuming GroupNorm; colstat_blocks_stored >= nsets * set_blocks counts the tile padding the 128-row and
+ *   ping-pong kernels store too (a block whose rows all lie past M holds zeros); colstat_floats = colstat_blocks_stored * 2 N. */
+typedef struct lavie_op_statistics_info {
+    int struct_size;                  /* sizeof this struct as the CALLER declared it; any other value is refused */
+    int M, N, splits;                 /* of the launch */
+    int colstat_written;              /* 0 / 1 */
+    int colstat_rows, colstat_span, nsets, set_blocks;
+    int colstat_contiguous;           /* 1: block b of a set holds the set's rows [b colstat_rows, (b + 1) colstat_rows) in ascending order (the
+                                         128-row, ping-pong and persistent kernels, the split-K reduce, the halo-patch kernel's whole-row tiles and
+                                         its parity form, whose set j = the outputs of parity j); 0: only the span holds (2-D and temporal tiles) */
+    int rowstat_written;              /* 0 / 1 */
+    int rowstat_cols, rowstat_slots;  /* columns per slot; slots per row = N / rowstat_cols */
+    long long colstat_blocks_stored, colstat_floats, rowstat_floats;
+} lavie_op_statistics_info;
+int lavie_debug_op_statistics(float* colstat, long long colstat_floats, float* rowstat, long long rowstat_floats);
+int lavie_debug_op_statistics_plan(int colstat, int rowstat);
+int lavie_debug_op_statistics_last(lavie_op_statistics_info* out);
+/* lavie_group_norm_f16 with the producers' column statistics of x1 / x2 (either may be null: none).  When every given descriptor can
+ * serve the GroupNorm (C equal to the tensor's, C % 4 == 0, P a whole number of spans and of rows * nsets), one fold of the partials
+ * replaces the statistics pass and lavie_debug_gn_producer_count() grows by one; otherwise the two-pass path runs.  A descriptor
+ * whose partials_floats cannot hold nsets * set_blocks blocks, or whose set_blocks is fewer than the NB domains need, is refused. */
+typedef struct lavie_gn_producer_stats {
+    int struct_size;                  /* sizeof this struct as the CALLER declared it; any other value is refused */
+    int C;                            /* channels of the tensor */
+    const float* partials;            /* device: [nsets][set_blocks][C / 4][2][4] */
+    long long partials_floats;
+    int rows, nsets, set_blocks, span;
+} lavie_gn_producer_stats;
+int lavie_group_norm_stats_f16(const void* x1, int C1, const void* x2, int C2, int NB, int P, int groups, const float* gamma,
+                               const float* beta, float eps, int silu, float* stats_ws, void* y, const lavie_gn_producer_stats* cs1,
+                               const lavie_gn_producer_stats* cs2, void* stream);
+/* Row statistics -> (mean, rstd): partials [M][slots][2] (sum, sum of squares over row_len values per row) -> out [M][2], the
+ * ln_stats operand of lavie_linear_lnfold_f16.  Fixed summation order. */
+int lavie_rowstat_finalize_f32(const float* partials, int slots, int M, int row_len, float eps, float* out, void* stream);
 /* Test/tuning knob for the implicit-GEMM kernel choice: 0 automatic, 1 128-row kernel with the widest tile,
  * 3 160x320 ping-pong kernel wherever N % 320 == 0, 4 automatic without the ping-pong
  * kernel, 5 halo-patch conv kernel wherever the conv is eligible, 6 automatic without the halo-patch kernel,

@@ -47,6 +47,18 @@ class WindowStepArgsC(C.Structure):   # lavie_window_step_args
                 ("next_input_scale", c_float)]
 
 
+class OpStatisticsInfoC(C.Structure):   # lavie_op_statistics_info
+    _fields_ = [("struct_size", c_int), ("M", c_int), ("N", c_int), ("splits", c_int), ("colstat_written", c_int), ("colstat_rows", c_int),
+                ("colstat_span", c_int), ("nsets", c_int), ("set_blocks", c_int), ("colstat_contiguous", c_int),
+                ("rowstat_written", c_int), ("rowstat_cols", c_int),
+                ("rowstat_slots", c_int), ("colstat_blocks_stored", c_ll), ("colstat_floats", c_ll), ("rowstat_floats", c_ll)]
+
+
+class GnProducerStatsC(C.Structure):    # lavie_gn_producer_stats
+    _fields_ = [("struct_size", c_int), ("C", c_int), ("partials", c_float_p), ("partials_floats", c_ll), ("rows", c_int), ("nsets", c_int),
+                ("set_blocks", c_int), ("span", c_int)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/lavie_hip.h
 SIGNATURES = {
     "lavie_last_error": (c_char_p, []),
@@ -150,6 +162,12 @@ SIGNATURES = {
     "lavie_debug_force_splits": (c_int, [c_int]),
     "lavie_debug_fused_mask": (c_int, [c_int]),
     "lavie_debug_gn_producer_count": (c_ll, []),
+    "lavie_debug_op_statistics": (c_int, [c_float_p, c_ll, c_float_p, c_ll]),
+    "lavie_debug_op_statistics_plan": (c_int, [c_int, c_int]),
+    "lavie_debug_op_statistics_last": (c_int, [C.POINTER(OpStatisticsInfoC)]),
+    "lavie_group_norm_stats_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float_p, c_float_p, c_float,
+                                            c_int, c_float_p, c_void_p, C.POINTER(GnProducerStatsC), C.POINTER(GnProducerStatsC), c_void_p]),
+    "lavie_rowstat_finalize_f32": (c_int, [c_float_p, c_int, c_int, c_int, c_float, c_float_p, c_void_p]),
     "lavie_debug_temporal_budget": (c_int, [c_int]),
     "lavie_debug_rowfuse_grid": (c_int, [c_int]),
     "lavie_profile_begin": (c_int, [C.c_uint, c_int]),

@@ -19,8 +19,45 @@ static inline hipStream_t S(void* s) { return (hipStream_t)s; }
 // buffer owned by the library (allocated outside any stream capture; the engine uses its own workspace).
 static float* g_slab = nullptr;
 static size_t g_slab_bytes = 0;
+// The statistics sink of the operator-level GEMM launches (lavie_debug_op_statistics): while armed, op_launch hands the sink's buffers
+// to the launch as the engine's run_igemm / linear do, so that the producers' epilogue statistics can be checked per element.  The
+// engine never reads it.  g_stats_last: what the last operator launch planned and wrote (lavie_debug_op_statistics_last).
+static float* g_sink_cs = nullptr;
+static float* g_sink_rs = nullptr;
+static long long g_sink_cs_floats = 0, g_sink_rs_floats = 0;
+static int g_plan_cs = 0, g_plan_rs = 0;      // lavie_debug_op_statistics_plan: plan as if armed, launch nothing
+static lavie_op_statistics_info g_stats_last = {};
 static int op_launch(IgemmParams& p, bool gather, int epilogue, hipStream_t stream) {
-    return igemm_run(p, gather, epilogue, stream, [](size_t need, float** slab) {
+    const bool plan_only = g_plan_cs || g_plan_rs;
+    const bool want_cs = plan_only ? g_plan_cs != 0 : g_sink_cs != nullptr;
+    const bool want_rs = (plan_only ? g_plan_rs != 0 : g_sink_rs != nullptr) && !gather && epilogue == EPI_LINEAR && !p.ln_stats;
+    static float placeholder;                 // the planner reads which operands are present, never their addresses
+    if (want_rs) p.rowstat_out = plan_only ? &placeholder : g_sink_rs;
+    IgemmPlan plan = igemm_plan(p, gather, epilogue);
+    p.splits = plan.splits;
+    lavie_op_statistics_info info = {};
+    info.struct_size = (int)sizeof(info);
+    info.M = p.M; info.N = p.N; info.splits = plan.splits;
+    if (want_cs && plan.colstat_rows > 0) {
+        const GnColStat cs = gn_colstat_describe(p, plan, g_sink_cs);
+        info.colstat_written = 1;
+        info.colstat_rows = cs.rows; info.colstat_span = cs.span; info.nsets = cs.nsets; info.set_blocks = cs.set_blocks;
+        info.colstat_contiguous = plan.splits > 1 || plan.kernel == IGEMM_TILE || plan.kernel == IGEMM_PP || plan.kernel == IGEMM_PPX || plan.kernel == IGEMM_PATCH_ROWS ||
+                                  plan.kernel == IGEMM_PATCH_PARITY;
+        info.colstat_blocks_stored = (long long)gn_colstat_blocks_stored(p, plan);
+        info.colstat_floats = info.colstat_blocks_stored * 2 * p.N;
+        LAVIE_CHECK(plan_only || g_sink_cs_floats >= info.colstat_floats,
+                    "op_statistics: the column-statistics sink holds %lld floats, this launch writes %lld", g_sink_cs_floats, info.colstat_floats);
+    }
+    if (want_rs) {
+        LAVIE_CHECK(plan.rowstat_cols > 0 && p.N % plan.rowstat_cols == 0, "op_statistics: no row-statistics slots for N=%d", p.N);
+        info.rowstat_written = 1;
+        info.rowstat_cols = plan.rowstat_cols; info.rowstat_slots = p.N / plan.rowstat_cols;
+        info.rowstat_floats = (long long)p.M * info.rowstat_slots * 2;
+        LAVIE_CHECK(plan_only || g_sink_rs_floats >= info.rowstat_floats,
+                    "op_statistics: the row-statistics sink holds %lld floats, this launch writes %lld", g_sink_rs_floats, info.rowstat_floats);
+    }
+    const int rc = igemm_run(p, gather, epilogue, stream, [](size_t need, float** slab) {
         if (need > g_slab_bytes) {
             if (g_slab) { LAVIE_HIP(hipDeviceSynchronize()); LAVIE_HIP(hipFree(g_slab)); g_slab = nullptr; g_slab_bytes = 0; }
             LAVIE_HIP(hipMalloc((void**)&g_slab, need));
@@ -28,7 +65,9 @@ static int op_launch(IgemmParams& p, bool gather, int epilogue, hipStream_t stre
         }
         *slab = g_slab;
         return 0;
-    });
+    }, want_cs && !plan_only ? g_sink_cs : nullptr, plan_only);
+    if (rc == 0) g_stats_last = info;
+    return rc;
 }
 static inline const half_t* H(const void* p) { return (const half_t*)p; }
 static inline half_t* H(void* p) { return (half_t*)p; }
@@ -673,6 +712,71 @@ int lavie_debug_rowfuse_grid(int max_workgroups) {
     return 0;
 }
 long long lavie_debug_gn_producer_count(void) { return (long long)lavie::gn_producer_count(); }
+
+// ---- producer-side norm statistics at operator level (tests/statcheck.py): additive entries, the ABI number stays.  None of them
+// changes which kernels a forward enqueues, so none bumps the debug epoch.
+int lavie_debug_op_statistics(float* colstat, long long colstat_floats, float* rowstat, long long rowstat_floats) {
+    LAVIE_CHECK(colstat_floats >= 0 && rowstat_floats >= 0, "op_statistics: negative buffer size");
+    const bool cs = colstat && colstat_floats > 0, rs = rowstat && rowstat_floats > 0;
+    g_sink_cs = cs ? colstat : nullptr; g_sink_cs_floats = cs ? colstat_floats : 0;
+    g_sink_rs = rs ? rowstat : nullptr; g_sink_rs_floats = rs ? rowstat_floats : 0;
+    return 0;
+}
+int lavie_debug_op_statistics_plan(int colstat, int rowstat) {
+    g_plan_cs = colstat != 0;
+    g_plan_rs = rowstat != 0;
+    return 0;
+}
+int lavie_debug_op_statistics_last(lavie_op_statistics_info* out) {
+    LAVIE_CHECK(out, "op_statistics_last: out is null");
+    LAVIE_CHECK(out->struct_size == (int)sizeof(lavie_op_statistics_info),
+                "op_statistics_last: out->struct_size=%d but this library's lavie_op_statistics_info has %d bytes: the binding's struct "
+                "layout is out of date", out->struct_size, (int)sizeof(lavie_op_statistics_info));
+    LAVIE_CHECK(g_stats_last.struct_size != 0, "op_statistics_last: no operator-level GEMM launch so far");
+    *out = g_stats_last;
+    return 0;
+}
+
+// one producer-statistics descriptor of lavie_group_norm_stats_f16 -> GnColStat, after the checks that keep the fold's reads inside
+// `partials` whichever path launch_group_norm then takes
+static int gn_descriptor(const char* which, const lavie_gn_producer_stats* d, int NB, int P, GnColStat* cs) {
+    *cs = GnColStat();
+    if (!d) return 0;
+    LAVIE_CHECK(d->struct_size == (int)sizeof(lavie_gn_producer_stats),
+                "group_norm_stats: %s->struct_size=%d but this library's lavie_gn_producer_stats has %d bytes: the binding's struct layout "
+                "is out of date", which, d->struct_size, (int)sizeof(lavie_gn_producer_stats));
+    LAVIE_CHECK(d->partials, "group_norm_stats: %s->partials is null", which);
+    LAVIE_CHECK(d->C > 0 && d->rows > 0 && d->nsets >= 1 && d->set_blocks >= 1 && d->span > 0,
+                "group_norm_stats: %s has C=%d rows=%d nsets=%d set_blocks=%d span=%d, all must be >= 1", which, d->C, d->rows, d->nsets,
+                d->set_blocks, d->span);
+    const long long need = (long long)d->nsets * d->set_blocks * 2 * d->C;
+    LAVIE_CHECK(d->partials_floats >= need, "group_norm_stats: %s->partials_floats=%lld, %d sets of %d blocks of %d channels need %lld", which,
+                d->partials_floats, d->nsets, d->set_blocks, d->C, need);
+    const long long per_domain = (long long)d->rows * d->nsets;
+    LAVIE_CHECK(P % per_domain != 0 || (long long)NB * (P / per_domain) <= d->set_blocks,
+                "group_norm_stats: %s describes %d blocks per set, %d domains of %lld need %lld", which, d->set_blocks, NB, P / per_domain,
+                (long long)NB * (P / per_domain));
+    cs->partials = d->partials; cs->C = d->C; cs->rows = d->rows; cs->nsets = d->nsets; cs->set_blocks = d->set_blocks; cs->span = d->span;
+    return 0;
+}
+int lavie_group_norm_stats_f16(const void* x1, int C1, const void* x2, int C2, int NB, int P, int groups, const float* gamma,
+                               const float* beta, float eps, int silu, float* stats_ws, void* y, const lavie_gn_producer_stats* cs1,
+                               const lavie_gn_producer_stats* cs2, void* stream) {
+    LAVIE_CHECK(x1 && gamma && beta && stats_ws && y, "group_norm_stats: null tensor");
+    LAVIE_CHECK(NB > 0 && P > 0 && groups > 0, "group_norm_stats: empty problem");
+    if (!x2) C2 = 0;
+    GnColStat a, b;
+    if (int rc = gn_descriptor("cs1", cs1, NB, P, &a)) return rc;
+    if (int rc = gn_descriptor("cs2", x2 ? cs2 : nullptr, NB, P, &b)) return rc;
+    return launch_group_norm(H(x1), C1, H(x2), C2, NB, P, groups, gamma, beta, eps, silu != 0, stats_ws, H(y), S(stream), cs1 ? &a : nullptr,
+                             x2 && cs2 ? &b : nullptr);
+}
+int lavie_rowstat_finalize_f32(const float* partials, int slots, int M, int row_len, float eps, float* out, void* stream) {
+    LAVIE_CHECK(partials && out, "rowstat_finalize: null tensor");
+    LAVIE_CHECK(slots >= 1 && M >= 1 && row_len >= 1, "rowstat_finalize: slots=%d M=%d row_len=%d must be >= 1", slots, M, row_len);
+    LAVIE_CHECK(__builtin_isfinite(eps) && eps >= 0.f, "rowstat_finalize: eps=%g must be finite and >= 0", (double)eps);
+    return launch_rowstat_finalize(partials, slots, M, row_len, eps, out, S(stream));
+}
 
 int lavie_profile_begin(unsigned mask, int max_events) { return profile_begin(mask, max_events); }
 

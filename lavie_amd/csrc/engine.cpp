@@ -707,14 +707,7 @@ static int run_igemm(FwdCtx& c, IgemmParams& p, bool gather, int epilogue, float
     }, cs_out && (c.route.mask & 32) ? cs_buf : nullptr, c.dry, &plan);
     c.ws->release(mark);
     if (cs_out) *cs_out = GnColStat();
-    if (p.colstat_out) {
-        cs_out->partials = cs_buf;
-        cs_out->C = p.N;
-        cs_out->rows = plan.colstat_rows;
-        cs_out->span = plan.colstat_span;
-        if (p.par_ups && p.splits == 1) { cs_out->nsets = 4; cs_out->set_blocks = p.M / 4 / plan.colstat_rows; }   // source-row blocks per output parity
-        else { cs_out->nsets = 1; cs_out->set_blocks = cdiv(p.M, plan.colstat_rows); }                            // (split-K: the reduce kernel walks output rows)
-    }
+    if (p.colstat_out) *cs_out = gn_colstat_describe(p, plan, cs_buf);
     if (plan_out) *plan_out = plan;
     return rc;
 }

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <sstream>
 #include <string>
@@ -390,6 +391,9 @@ static void run_traces(const char* path) {
 // force_tile / force_splits (default 0); the end and glue kernels' entries (timestep_sinusoid ... f16_to_f32) and the pack / bind steps
 // of the row-resident blocks (pack_geglu_mlp, bind_cross_block[_long]: pack + bind) likewise, and the blocks themselves (geglu_mlp, temporal_block,
 // cross_block[_long], proj_qkv), temporal_attention, group_norm[_affine], conv_edge_in / conv_edge_out and attention on exactly sized buffers, under rowfuse_grid / temporal_budget (default 0).  Tensors are never read.  OUT: "== <line>", then the stub's launch lines of that call, or
+// stats_cs=1 / stats_rs=1 on a GEMM-family line arm the statistics sink around the call (planned first, the sink sized exactly); behind the
+// launch lines comes "## stats ..." with the plan (written or not, rows, span, sets, blocks, slots); group_norm_stats takes descriptors
+// as cs1_C / cs1_rows / cs1_nsets / cs1_set_blocks / cs1_span (cs2_ likewise) and prints "## fold=<producer-count delta>"; rowstat_finalize.
 // "!! refused" where the library returns an error (its message goes to stderr).  A line the driver cannot parse ends the run.
 static int run_optrace(const char* in_path, const char* out_path) {
     FILE* in = fopen(in_path, "r");
@@ -433,6 +437,8 @@ static int run_optrace(const char* in_path, const char* out_path) {
         auto P = [&](const char* k) -> void* { return O(k) ? d : nullptr; };
         auto F = [&](const char* k) -> const float* { return O(k) ? fd : nullptr; };
         const int tile = O("force_tile"), splits = O("force_splits"), grid_cap = O("rowfuse_grid"), budget = O("temporal_budget");
+        const int stats_cs = O("stats_cs"), stats_rs = O("stats_rs");      // the statistics sink around a GEMM-family call
+        std::function<int()> gemm;                                          // the GEMM-family call of this line, run below
         fprintf(g_out, "== %s\n", s.c_str());
         int rc = lavie_debug_force_tile(tile);
         lavie_debug_force_splits(splits);
@@ -441,27 +447,27 @@ static int run_optrace(const char* in_path, const char* out_path) {
         if (rc == 0) {
             if (entry == "linear") {
                 const int lda = I("lda"), ldb2 = I("ldb2"), rpb = I("rows_per_batch"), ldr = I("ldr"), ldc = I("ldc"), M = I("M"), N = I("N"), K = I("K"), g = I("geglu");
-                if (!missing) rc = lavie_linear_f16(d, lda, d, F("bias"), F("bias2"), ldb2, rpb, P("R"), ldr, d, ldc, M, N, K, g, nullptr);
+                if (!missing) gemm = [=] { return lavie_linear_f16(d, lda, d, F("bias"), F("bias2"), ldb2, rpb, P("R"), ldr, d, ldc, M, N, K, g, nullptr); };
             } else if (entry == "linear_lnfold" || entry == "linear_lnfold_geglu") {
                 const int M = I("M"), N = I("N"), K = I("K");
                 if (!missing)
-                    rc = entry == "linear_lnfold" ? lavie_linear_lnfold_f16(d, d, F("bias"), fd, fd, d, M, N, K, nullptr)
-                                                  : lavie_linear_lnfold_geglu_f16(d, d, F("bias"), fd, fd, d, M, N, K, nullptr);
+                    gemm = [=] { return entry == "linear_lnfold" ? lavie_linear_lnfold_f16(d, d, F("bias"), fd, fd, d, M, N, K, nullptr)
+                                                                 : lavie_linear_lnfold_geglu_f16(d, d, F("bias"), fd, fd, d, M, N, K, nullptr); };
             } else if (entry == "conv3x3") {
                 const int C1 = I("C1"), C2 = I("C2"), SC1 = I("SC1"), SC2 = I("SC2"), ldb2 = I("ldb2"), rpb = I("rows_per_batch"), NI = I("NI"), Hi = I("Hi"),
                           Wi = I("Wi"), Cout = I("Cout"), stride = I("stride"), ups = I("ups");
                 if (!missing)
-                    rc = lavie_conv3x3_f16(d, C1, P("x2"), C2, P("sc1"), SC1, P("sc2"), SC2, d, F("bias"), F("bias2"), ldb2, rpb, P("R"), d, NI, Hi, Wi,
-                                           Cout, stride, ups, d, nullptr);
+                    gemm = [=] { return lavie_conv3x3_f16(d, C1, P("x2"), C2, P("sc1"), SC1, P("sc2"), SC2, d, F("bias"), F("bias2"), ldb2, rpb, P("R"), d, NI, Hi, Wi,
+                                                          Cout, stride, ups, d, nullptr); };
             } else if (entry == "conv3x3_down") {
                 const int C = I("C"), NI = I("NI"), Hi = I("Hi"), Wi = I("Wi"), Cout = I("Cout"), stride = I("stride"), pad_lo = I("pad_lo");
-                if (!missing) rc = lavie_conv3x3_down_f16(d, C, d, F("bias"), d, NI, Hi, Wi, Cout, stride, pad_lo, d, nullptr);
+                if (!missing) gemm = [=] { return lavie_conv3x3_down_f16(d, C, d, F("bias"), d, NI, Hi, Wi, Cout, stride, pad_lo, d, nullptr); };
             } else if (entry == "upsample_conv3x3") {
                 const int NI = I("NI"), Hi = I("Hi"), Wi = I("Wi"), C = I("C");
-                if (!missing) rc = lavie_upsample_conv3x3_f16(d, d, F("bias"), d, NI, Hi, Wi, C, d, nullptr);
+                if (!missing) gemm = [=] { return lavie_upsample_conv3x3_f16(d, d, F("bias"), d, NI, Hi, Wi, C, d, nullptr); };
             } else if (entry == "temporal_conv") {
                 const int C = I("C"), ldb2 = I("ldb2"), rpb = I("rows_per_batch"), B = I("B"), Fr = I("F"), D = I("D"), Cout = I("Cout"), taps = I("taps");
-                if (!missing) rc = lavie_temporal_conv_f16(d, C, d, F("bias"), F("bias2"), ldb2, rpb, P("R"), d, B, Fr, D, Cout, taps, d, nullptr);
+                if (!missing) gemm = [=] { return lavie_temporal_conv_f16(d, C, d, F("bias"), F("bias2"), ldb2, rpb, P("R"), d, B, Fr, D, Cout, taps, d, nullptr); };
             } else if (entry == "timestep_sinusoid") {
                 const int B = I("B"), dim = I("dim");
                 if (!missing) rc = lavie_timestep_sinusoid_f32(fd, (float*)d, B, dim, nullptr);
@@ -573,6 +579,38 @@ static int run_optrace(const char* in_path, const char* out_path) {
                              : lavie_group_norm_f16(x1.data(), C1, O("x2") ? x2.data() : nullptr, C2, NB, Pr, groups, v.data(), v.data(), 1e-5f, silu, ws.data(),
                                                     y.data(), nullptr);
                 }
+            } else if (entry == "group_norm_stats") {       // producer-statistics descriptors cs1_* / cs2_* (absent: none) over exactly sized partials
+                const int C1 = I("C1"), C2 = I("C2"), NB = I("NB"), Pr = I("P"), groups = I("groups"), silu = I("silu");
+                lavie_gn_producer_stats ds[2];
+                std::vector<float> parts[2];
+                bool have[2] = {false, false};
+                for (int t = 0; t < 2; ++t) {
+                    const std::string pre = t ? "cs2_" : "cs1_";
+                    if (!a.count(pre + "rows")) continue;
+                    have[t] = true;
+                    memset(&ds[t], 0, sizeof(ds[t]));
+                    ds[t].struct_size = (int)sizeof(ds[t]);
+                    ds[t].C = I((pre + "C").c_str()); ds[t].rows = I((pre + "rows").c_str()); ds[t].nsets = I((pre + "nsets").c_str());
+                    ds[t].set_blocks = I((pre + "set_blocks").c_str()); ds[t].span = I((pre + "span").c_str());
+                    const long long n = (long long)ds[t].nsets * ds[t].set_blocks * 2 * ds[t].C;
+                    parts[t].resize((size_t)(n > 0 ? n : 1));
+                    ds[t].partials = parts[t].data(); ds[t].partials_floats = n;
+                }
+                if (!missing) {
+                    const size_t rows = (size_t)NB * Pr;
+                    std::vector<unsigned short> x1(rows * C1), x2(rows * C2 + 1), y(rows * (C1 + C2));
+                    std::vector<float> v((size_t)C1 + C2), ws((size_t)lavie_group_norm_ws_floats(NB, groups));
+                    const long long before = lavie_debug_gn_producer_count();
+                    rc = lavie_group_norm_stats_f16(x1.data(), C1, O("x2") ? x2.data() : nullptr, C2, NB, Pr, groups, v.data(), v.data(), 1e-5f, silu, ws.data(),
+                                                    y.data(), have[0] ? &ds[0] : nullptr, have[1] ? &ds[1] : nullptr, nullptr);
+                    if (rc == 0) fprintf(g_out, "## fold=%lld\n", lavie_debug_gn_producer_count() - before);
+                }
+            } else if (entry == "rowstat_finalize") {
+                const int slots = I("slots"), M = I("M"), row_len = I("row_len");
+                if (!missing) {
+                    std::vector<float> part((size_t)(M > 0 && slots > 0 ? (size_t)M * slots * 2 : 1)), out((size_t)(M > 0 ? M * 2 : 1));
+                    rc = lavie_rowstat_finalize_f32(part.data(), slots, M, row_len, 1e-5f, out.data(), nullptr);
+                }
             } else if (entry == "conv_edge_in" || entry == "conv_edge_out") {     // the autoencoder's kernels: exactly sized buffers as well
                 const bool in = entry == "conv_edge_in";
                 const int dt = I(in ? "x_dtype" : "y_dtype"), N = I("N"), Cin = I("Cin"), Hh = I("H"), Ww = I("W"), Cout = I("Cout");
@@ -599,6 +637,32 @@ static int run_optrace(const char* in_path, const char* out_path) {
             }
         }
         if (missing) return 2;
+        if (gemm && rc == 0) {
+            if (stats_cs || stats_rs) {      // plan as if armed (nothing is launched), size the sink exactly, arm it, launch, report the plan
+                lavie_op_statistics_info info;
+                memset(&info, 0, sizeof(info));
+                info.struct_size = (int)sizeof(info);
+                REQUIRE(lavie_debug_op_statistics_plan(stats_cs, stats_rs) == 0);
+                const long before = lavie_hostcheck_launches();
+                rc = gemm();
+                REQUIRE(lavie_debug_op_statistics_plan(0, 0) == 0);
+                REQUIRE(lavie_hostcheck_launches() == before);
+                if (rc == 0) {
+                    REQUIRE(lavie_debug_op_statistics_last(&info) == 0);
+                    std::vector<float> cs((size_t)(info.colstat_floats > 0 ? info.colstat_floats : 1)), rs((size_t)(info.rowstat_floats > 0 ? info.rowstat_floats : 1));
+                    REQUIRE(lavie_debug_op_statistics(stats_cs ? cs.data() : nullptr, info.colstat_floats, stats_rs ? rs.data() : nullptr, info.rowstat_floats) == 0);
+                    rc = gemm();
+                    REQUIRE(lavie_debug_op_statistics(nullptr, 0, nullptr, 0) == 0);
+                    if (rc == 0)
+                        fprintf(g_out, "## stats colstat=%d rows=%d span=%d sets=%d set_blocks=%d contiguous=%d blocks_stored=%lld cs_floats=%lld rowstat=%d cols=%d slots=%d "
+                                "rs_floats=%lld M=%d N=%d splits=%d\n", info.colstat_written, info.colstat_rows, info.colstat_span, info.nsets, info.set_blocks,
+                                info.colstat_contiguous, info.colstat_blocks_stored, info.colstat_floats, info.rowstat_written, info.rowstat_cols, info.rowstat_slots,
+                                info.rowstat_floats, info.M, info.N, info.splits);
+                }
+            } else {
+                rc = gemm();
+            }
+        }
         for (const auto& kv : a)
             if (!used.count(kv.first)) { fprintf(stderr, "hostcheck optrace: '%s' does not take %s\n", entry.c_str(), kv.first.c_str()); return 2; }
         if (rc != 0) {
@@ -1106,6 +1170,81 @@ int main(int argc, char** argv) {
         REQUIRE(lavie_copy_rows_f16(d, 7, d, 16, 3, 8, 0, nullptr) != 0 && lavie_copy_rows_f16(d, 8, d, 15, 3, 8, 8, nullptr) != 0);
         REQUIRE(lavie_f16_to_f32(d, nullptr, f.data(), 0, nullptr) != 0 && lavie_f16_to_f32(nullptr, nullptr, f.data(), 4, nullptr) != 0);
         REQUIRE(lavie_hostcheck_launches() == accepted);
+    }
+    {   // the statistics sink and the two statistics entries: exactly sized buffers; every refusal comes before a launch and names what is wrong
+        auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+        std::vector<unsigned short> d16(64);
+        void* d = d16.data();
+        lavie_op_statistics_info info;
+        memset(&info, 0, sizeof(info));
+        REQUIRE(refused(lavie_debug_op_statistics_last(nullptr), "out is null"));
+        REQUIRE(refused(lavie_debug_op_statistics_last(&info), "struct_size"));
+        info.struct_size = (int)sizeof(info);
+        const int M = 161, N = 320, K = 320;            // ping-pong under mode 3: three blocks of 80 rows announced, four stored; 128-row kernel: 64-row blocks
+        auto lin = [&] { return lavie_linear_f16(d, K, d, nullptr, nullptr, N, 0, nullptr, N, d, N, M, N, K, 0, nullptr); };
+        for (int mode : {0, 3}) {
+            REQUIRE(lavie_debug_force_tile(mode) == 0);
+            REQUIRE(lavie_debug_op_statistics_plan(1, 1) == 0);
+            long before = lavie_hostcheck_launches();
+            REQUIRE(lin() == 0 && lavie_hostcheck_launches() == before);             // planned, not launched
+            REQUIRE(lavie_debug_op_statistics_plan(0, 0) == 0);
+            REQUIRE(lavie_debug_op_statistics_last(&info) == 0);
+            REQUIRE(info.colstat_written == 1 && info.rowstat_written == 1 && info.splits == 1 && info.nsets == 1 && info.colstat_contiguous == 1);
+            REQUIRE(info.set_blocks == (M + info.colstat_rows - 1) / info.colstat_rows && info.colstat_span == info.colstat_rows);
+            REQUIRE(info.colstat_rows == (mode == 3 ? 80 : 64) && info.colstat_blocks_stored == 4 && info.colstat_floats == 4ll * 2 * N);
+            REQUIRE(info.rowstat_slots * info.rowstat_cols == N && info.rowstat_floats == 2ll * M * info.rowstat_slots);
+            std::vector<float> cs((size_t)info.colstat_floats), rs((size_t)info.rowstat_floats);
+            REQUIRE(lavie_debug_op_statistics(cs.data(), info.colstat_floats - 1, rs.data(), info.rowstat_floats) == 0);
+            before = lavie_hostcheck_launches();
+            REQUIRE(refused(lin(), "this launch writes 2560"));
+            REQUIRE(lavie_debug_op_statistics(cs.data(), info.colstat_floats, rs.data(), info.rowstat_floats - 1) == 0);
+            REQUIRE(refused(lin(), "row-statistics sink holds"));
+            REQUIRE(lavie_hostcheck_launches() == before);
+            REQUIRE(lavie_debug_op_statistics(cs.data(), info.colstat_floats, rs.data(), info.rowstat_floats) == 0);
+            REQUIRE(lin() == 0 && lavie_hostcheck_launches() == before + 1);
+            REQUIRE(refused(lavie_debug_op_statistics(cs.data(), -1, nullptr, 0), "negative"));
+            REQUIRE(lavie_debug_op_statistics(nullptr, 0, nullptr, 0) == 0);
+            REQUIRE(lin() == 0 && lavie_hostcheck_launches() == before + 2);         // disarmed: as before
+        }
+        REQUIRE(lavie_debug_force_tile(0) == 0);
+        // group_norm_stats: 2 domains of 160 rows, 320 channels, blocks of 80 rows
+        const int NB = 2, P = 160, C = 320;
+        std::vector<unsigned short> x((size_t)NB * P * C), y(x.size());
+        std::vector<float> v((size_t)C), ws((size_t)lavie_group_norm_ws_floats(NB, 32)), part((size_t)4 * 2 * C);
+        lavie_gn_producer_stats cs;
+        memset(&cs, 0, sizeof(cs));
+        cs.struct_size = (int)sizeof(cs);
+        cs.C = C; cs.partials = part.data(); cs.partials_floats = (long long)part.size(); cs.rows = 80; cs.nsets = 1; cs.set_blocks = 4; cs.span = 80;
+        auto gn = [&](const lavie_gn_producer_stats* c1) {
+            return lavie_group_norm_stats_f16(x.data(), C, nullptr, 0, NB, P, 32, v.data(), v.data(), 1e-5f, 1, ws.data(), y.data(), c1, nullptr, nullptr);
+        };
+        long long folds = lavie_debug_gn_producer_count();
+        REQUIRE(gn(&cs) == 0 && lavie_debug_gn_producer_count() == folds + 1);
+        REQUIRE(gn(nullptr) == 0 && lavie_debug_gn_producer_count() == folds + 1);
+        const long accepted = lavie_hostcheck_launches();
+        lavie_gn_producer_stats q = cs;
+        q.struct_size -= 4;
+        REQUIRE(refused(gn(&q), "struct_size"));
+        q = cs; q.partials = nullptr;
+        REQUIRE(refused(gn(&q), "partials is null"));
+        q = cs; q.rows = 0;
+        REQUIRE(refused(gn(&q), "rows=0"));
+        q = cs; q.partials_floats -= 1;
+        REQUIRE(refused(gn(&q), "partials_floats"));
+        q = cs; q.set_blocks = 3; q.partials_floats = 3ll * 2 * C;
+        REQUIRE(refused(gn(&q), "blocks per set"));
+        REQUIRE(refused(lavie_group_norm_stats_f16(nullptr, C, nullptr, 0, NB, P, 32, v.data(), v.data(), 1e-5f, 1, ws.data(), y.data(), &cs, nullptr, nullptr), "null tensor"));
+        REQUIRE(refused(lavie_group_norm_stats_f16(x.data(), C, nullptr, 0, 0, P, 32, v.data(), v.data(), 1e-5f, 1, ws.data(), y.data(), &cs, nullptr, nullptr), "empty"));
+        // rowstat_finalize
+        std::vector<float> rp((size_t)257 * 5 * 2), ro((size_t)257 * 2);
+        REQUIRE(refused(lavie_rowstat_finalize_f32(nullptr, 5, 257, 320, 1e-5f, ro.data(), nullptr), "null tensor"));
+        REQUIRE(refused(lavie_rowstat_finalize_f32(rp.data(), 5, 257, 320, 1e-5f, nullptr, nullptr), "null tensor"));
+        REQUIRE(refused(lavie_rowstat_finalize_f32(rp.data(), 0, 257, 320, 1e-5f, ro.data(), nullptr), "slots=0"));
+        REQUIRE(refused(lavie_rowstat_finalize_f32(rp.data(), 5, 0, 320, 1e-5f, ro.data(), nullptr), "M=0"));
+        REQUIRE(refused(lavie_rowstat_finalize_f32(rp.data(), 5, 257, 0, 1e-5f, ro.data(), nullptr), "row_len=0"));
+        REQUIRE(refused(lavie_rowstat_finalize_f32(rp.data(), 5, 257, 320, -1.f, ro.data(), nullptr), "eps"));
+        REQUIRE(lavie_hostcheck_launches() == accepted);
+        REQUIRE(lavie_rowstat_finalize_f32(rp.data(), 5, 257, 320, 1e-5f, ro.data(), nullptr) == 0 && lavie_hostcheck_launches() == accepted + 1);
     }
     run_vae_optrace();
     REQUIRE(lavie_upsample_conv3x3_supported(320, 32, 20, 32) >= 0);

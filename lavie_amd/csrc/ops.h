@@ -23,6 +23,27 @@ struct GnColStat {
     int span = 0;         // the rows of a block lie inside ONE aligned run of `span` tensor rows (contiguous blocks: = rows; 2-D conv
                           // tiles: one frame; temporal-conv tiles: one video): a statistics domain must be a whole number of spans
 };
+// What the launch of `p` under `plan` left in `buf` (p.colstat_out; p.splits as igemm_run set it): the one place that turns a plan into
+// a description, for the engine (run_igemm) and the operator-level statistics sink (api.cpp) alike.
+inline GnColStat gn_colstat_describe(const IgemmParams& p, const IgemmPlan& plan, const float* buf) {
+    GnColStat cs;
+    cs.partials = buf;
+    cs.C = p.N;
+    cs.rows = plan.colstat_rows;
+    cs.span = plan.colstat_span;
+    if (p.par_ups && p.splits == 1) { cs.nsets = 4; cs.set_blocks = p.M / 4 / plan.colstat_rows; }   // source-row blocks per output parity
+    else { cs.nsets = 1; cs.set_blocks = cdiv(p.M, plan.colstat_rows); }                            // (split-K: the reduce kernel walks output rows)
+    return cs;
+}
+// Blocks the launch stores, tile padding included: the 128-row and ping-pong kernels store every wave tile of their last row tile, also
+// one whose rows all lie past M (it holds zeros: rows past M contribute nothing), so a buffer needs up to one block more than the
+// nsets * set_blocks a consumer reads (engine.cpp colstat_floats has the headroom).
+inline size_t gn_colstat_blocks_stored(const IgemmParams& p, const IgemmPlan& plan) {
+    if (plan.colstat_rows <= 0) return 0;
+    if (p.splits > 1 || (plan.kernel != IGEMM_TILE && plan.kernel != IGEMM_PP)) return (size_t)cdiv(p.M, plan.colstat_rows);
+    const int bm = plan.kernel == IGEMM_TILE ? 128 : 160;
+    return (size_t)cdiv(p.M, bm) * (bm / plan.colstat_rows);
+}
 // cs1 / cs2 (optional): statistics of x1 / x2 from their producers.  When both tensors have them and every block lies inside one
 // statistics domain (P %% (rows * nsets) == 0), the statistics pass over the tensor and its finalize launch are replaced by ONE small
 // fold of the partials; otherwise the two-pass path runs.

@@ -395,6 +395,80 @@ def group_norm(x1, gamma, beta, nb, groups, eps, silu, x2=None, out=None):
     return y
 
 
+class op_statistics:
+    """The statistics sink of the operator-level GEMM entry points (lavie_debug_op_statistics) for the duration of a `with` block:
+    colstat / rowstat are fp32 device buffers (either may be None) that the launches inside write the producers' column / row
+    statistics to.  plan=(colstat, rowstat) instead: launches inside are planned as if those kinds were armed and NOT run
+    (lavie_debug_op_statistics_plan), to size the buffers from last()."""
+
+    def __init__(self, colstat=None, rowstat=None, plan=None):
+        _chk32(colstat, rowstat)
+        self.colstat, self.rowstat, self.plan = colstat, rowstat, plan
+
+    def __enter__(self):
+        lib = _lib.load()
+        if self.plan is not None:
+            _lib.check(lib.lavie_debug_op_statistics_plan(int(self.plan[0]), int(self.plan[1])), "lavie_debug_op_statistics_plan")
+        else:
+            _lib.check(lib.lavie_debug_op_statistics(_p(self.colstat), 0 if self.colstat is None else self.colstat.numel(), _p(self.rowstat),
+                                                     0 if self.rowstat is None else self.rowstat.numel()), "lavie_debug_op_statistics")
+        return self
+
+    def __exit__(self, *exc):
+        lib = _lib.load()
+        lib.lavie_debug_op_statistics_plan(0, 0)
+        lib.lavie_debug_op_statistics(None, 0, None, 0)
+
+    @staticmethod
+    def last():
+        """lavie_op_statistics_info of the last operator-level GEMM launch, as a dict"""
+        info = _lib.OpStatisticsInfoC()
+        info.struct_size = ctypes.sizeof(info)
+        _lib.check(_lib.load().lavie_debug_op_statistics_last(ctypes.byref(info)), "lavie_debug_op_statistics_last")
+        return {k: int(getattr(info, k)) for k, _ in info._fields_ if k != "struct_size"}
+
+
+def producer_stats(partials, c, rows, nsets, set_blocks, span):
+    """One lavie_gn_producer_stats descriptor of group_norm_stats: `partials` fp32 device, [nsets][set_blocks][c / 4][2][4]."""
+    _chk32(partials)
+    d = _lib.GnProducerStatsC()
+    d.struct_size = ctypes.sizeof(d)
+    d.C, d.partials, d.partials_floats = int(c), partials.data_ptr(), partials.numel()
+    d.rows, d.nsets, d.set_blocks, d.span = int(rows), int(nsets), int(set_blocks), int(span)
+    d._keep = partials
+    return d
+
+
+def group_norm_stats(x1, gamma, beta, nb, groups, eps, silu, x2=None, cs1=None, cs2=None, out=None, ws=None):
+    """group_norm with the producers' column statistics of x1 / x2 (producer_stats() descriptors or None): a fold of the partials
+    replaces the statistics pass where the descriptors can serve it (lavie_group_norm_stats_f16).  ws (optional): the fp32 scratch of
+    lavie_group_norm_ws_floats(nb, groups) floats, whose first nb * groups * 2 hold (mean, rstd) per (batch, group) afterwards."""
+    _chk16(x1, x2)
+    _chk32(gamma, beta)
+    rows = x1.shape[0]
+    c1, c2 = x1.shape[1], 0 if x2 is None else x2.shape[1]
+    y = _out(out, (rows, c1 + c2), torch.float16, x1.device, "group_norm_stats: out")
+    ws_n = _lib.load().lavie_group_norm_ws_floats(nb, groups)
+    ws = torch.empty(ws_n, dtype=torch.float32, device=x1.device) if ws is None else _out(ws, (ws_n,), torch.float32, x1.device, "group_norm_stats: ws")
+    _lib.check(_lib.load().lavie_group_norm_stats_f16(_p(x1), c1, _p(x2), c2, nb, rows // nb, groups, _p(gamma), _p(beta), float(eps),
+                                                      int(silu), _p(ws), _p(y), None if cs1 is None else ctypes.byref(cs1),
+                                                      None if cs2 is None else ctypes.byref(cs2), _stream()), "lavie_group_norm_stats_f16")
+    return y
+
+
+def rowstat_finalize(partials, row_len, eps=1e-5, out=None):
+    """Row statistics [M, slots, 2] (sum, sum of squares over row_len values per row) -> (mean, rstd) [M, 2] fp32: the ln_stats of
+    linear_lnfold (lavie_rowstat_finalize_f32)."""
+    _chk32(partials)
+    m, slots, two = partials.shape
+    if two != 2:
+        raise ValueError("rowstat_finalize: partials must be [M, slots, 2]")
+    out = _out(out, (m, 2), torch.float32, partials.device, "rowstat_finalize: out")
+    _lib.check(_lib.load().lavie_rowstat_finalize_f32(_p(partials), slots, m, int(row_len), float(eps), _p(out), _stream()),
+               "lavie_rowstat_finalize_f32")
+    return out
+
+
 def group_norm_affine(x, gamma, beta, nb, groups, eps, out=None):
     """GroupNorm statistics only: the normalisation as per-(batch, channel) pairs (a, b) with norm(x) = a x + b -> [nb, C, 2] fp32
     (lavie_group_norm_affine_f16; consumed by proj_qkv)."""

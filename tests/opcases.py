@@ -99,6 +99,7 @@ def rows(x):
 LINEAR_SHAPES = [(1, 64, 64), (127, 64, 192), (130, 192, 64), (154, 320, 320), (160, 320, 320), (161, 320, 320),
                  (320, 256, 320), (480, 640, 320)]
 LINEAR_OPTIONS = ["plain", "bias_residual", "bias2", "residual_in_place"]
+# "bias2_residual" (bias + per-batch bias + residual: every operand of the epilogue at once) is run by the statistics cases alone
 
 
 @functools.lru_cache(maxsize=None)
@@ -107,11 +108,11 @@ def linear_case(M, N, K, opt):
     a, w = rnd(g, M, K), rnd(g, N, K, s=1 / math.sqrt(K))
     ins = {"a": a, "w": w}
     rpb = (M + 1) // 2
-    if opt in ("bias_residual", "bias2"):
+    if opt in ("bias_residual", "bias2", "bias2_residual"):
         ins["bias"] = rnd(g, N, dtype=f32t)
-    if opt == "bias2":
+    if opt in ("bias2", "bias2_residual"):
         ins["bias2"] = rnd(g, -(-M // rpb), N, dtype=f32t)
-    if opt in ("bias_residual", "residual_in_place"):
+    if opt in ("bias_residual", "residual_in_place", "bias2_residual"):
         ins["r"] = rnd(g, M, N)
     b2rows = torch.arange(M) // rpb
 
@@ -307,18 +308,16 @@ NOT_PLANNED = {}
 # kernels of the launch-trace fixture that no operator entry point launches: name -> the existing test that exercises it
 WHOLE_FORWARD = "tests/test_gpu_engine.py (whole-output rel-L2 of the engine's blocks and forwards against the fp32 oracle)"
 NO_OPERATOR_ENTRY = {
-    # producer-side statistics: reached only behind the engine's rowstat_out / colstat_out, which no operator entry point sets
-    # (gn_finalize_kernel is not one of them: ops.group_norm launches it whenever the producers' statistics are not used, norm.hip
-    # launch_group_norm, and every group_norm case's trace names it: LOCAL_KERNELS)
-    "gn_fold_kernel": WHOLE_FORWARD, "rowstat_finalize_kernel": WHOLE_FORWARD,
+    # (the producer-side statistics kernels gn_fold_kernel, rowstat_finalize_kernel and splitk_reduce_cs_kernel were listed here until
+    # lavie_debug_op_statistics, lavie_group_norm_stats_f16 and lavie_rowstat_finalize_f32 reached them: stats_cases(), stats_local_cases())
     # the chunked form of the pack (the unchunked one: pack_conv_out_case) and the packs of the GEGLU / parity operands: bit-moves
     # whose output every conv / GEGLU / parity case consumes
     "pack_conv3x3_parity_kernel": "tests/test_gpu_ops_local.py::test_upsample_conv3x3_parity (ops.pack_conv3x3_parity)",
     "pack_geglu_bias_kernel": "tests/test_gpu_ops_local.py::test_geglu (ops.pack_geglu)",
     "pack_geglu_rows_kernel": "tests/test_gpu_ops_local.py::test_geglu (ops.pack_geglu)",
-    # a run-time branch of the reduce that only the engine's colstat_out selects; its sums are covered by the engine's verify pass alone
-    "splitk_reduce_cs_kernel": WHOLE_FORWARD + "; its column sums only by the engine's verify pass",
 }
+# EPI_LINEAR igemm_* instantiations that a case reaches, but none with column statistics in an unsplit launch: name -> reason
+NO_COLSTAT = {}
 # gather kernels of the row-resident blocks' pack / bind steps: launched by lavie_pack_geglu_mlp_f16 and lavie_bind_cross_block[_long]_f16
 # (`hostcheck optrace`, asserted by test_gemm_reach_host.py), which the block cases call before the kernel whose output they check
 PACK_STEP_KERNELS = {
@@ -336,7 +335,7 @@ ENDS_KERNELS = ("timestep_sinusoid_kernel", "gemv_kernel", "add_class_emb_silu_k
 COVERED_ELSEWHERE = ("attention_dma_kernel<", "attention_kernel<", "attention_wide_kernel", "layernorm_kernel")
 # ... and of the GroupNorm, row-resident and temporal cases, which describe their calls: every such name of a forward's trace must be in
 # the replayed launches of a case (test_gemm_reach_host.py::test_local_kernels_of_a_forward_are_reached)
-LOCAL_KERNELS = ("gn_affine_kernel", "gn_apply_kernel<", "gn_stats_kernel<", "gn_finalize_kernel", "geglu_mlp_kernel<", "cross_block_kernel<",
+LOCAL_KERNELS = ("gn_affine_kernel", "gn_apply_kernel<", "gn_stats_kernel<", "gn_finalize_kernel", "gn_fold_kernel", "rowstat_finalize_kernel", "geglu_mlp_kernel<", "cross_block_kernel<",
                  "temporal_block_kernel<", "proj_qkv_kernel<", "temporal_stream_kernel<", "temporal_attention_kernel<")
 
 
@@ -2305,7 +2304,7 @@ def reach_cases():
 def gemm_family_cases():
     """Every case that describes its C-ABI calls: what gemm_reach replays (the halo-patch cases under both of their forced loops)"""
     cs = [c for c in all_cases() if c.calls]
-    return cs + [conv_case(**k, force=3) for k in HALO_CASES]
+    return cs + [conv_case(**k, force=3) for k in HALO_CASES] + list(stats_cases()) + list(stats_local_cases())
 
 
 def vae_cases():
@@ -2344,6 +2343,152 @@ def all_cases():
     # the forward's ends and glue kernels (tests/test_gpu_ends_local.py)
     cs += [c for fam in ends_cases().values() for c in fam]
     return cs
+
+
+# ------------------------------------------------------------------ producer-side norm statistics (tests/statcheck.py, tests/test_gpu_stats_local.py)
+# A GEMM-family case run once more with the statistics sink of lavie_debug_op_statistics armed: "cs" column statistics (what a consuming
+# GroupNorm folds), "rs" row statistics (what a consuming LayerNorm finalizes), "cs+rs" both, as the engine's proj_out runs.  C is
+# checked against the case's own float64 reference under its own bound, the partials against float64 sums of the C that was written.
+# (base case, kind, variants): the variants whose plan (`hostcheck optrace`, asserted by test_gemm_reach_host.py) is the kernel named.
+def _lin(M, N, K, o):
+    return lambda: linear_case(M, N, K, o)
+
+
+def _cv(**k):
+    return lambda: conv_case(**k)
+
+
+STATS_TABLE = [
+    # 128-row kernel, ragged M: 64-, 160- and 128-wide tiles (one wave tile of the last row tile lies past M: a padding block)
+    (_lin(130, 192, 64, "bias2"), "cs", ("auto",)), (_lin(154, 320, 320, "bias_residual"), "cs", ("row128-tiles",)),
+    (_lin(8193, 512, 64, "bias_residual"), "cs", ("auto",)),
+    # ping-pong kernel, plain (M = 154: two blocks; M = 161: three announced, four stored) and gather
+    (_lin(154, 320, 320, "residual_in_place"), "cs", ("pingpong",)), (_lin(161, 320, 320, "bias2"), "cs", ("pingpong",)),
+    (_cv(n=1, c1=64, cout=320, h=5, w=7), "cs", ("pingpong",)),
+    # persistent kernel at 160 and 320 rows, both tile widths, with and without residual and LayerNorm fold
+    (_lin(160, 320, 320, "plain"), "cs", ("ppx-persistent",)), (_lin(160, 320, 320, "bias_residual"), "cs", ("ppx-persistent",)),
+    (_lin(320, 256, 320, "bias_residual"), "cs", ("ppx-persistent",)), (_lin(320, 256, 320, "plain"), "cs", ("ppx-persistent",)),
+    (lambda: lnfold_case(320, 320, 320), "cs", ("ppx-persistent",)), (lambda: lnfold_case(160, 256, 320), "cs", ("ppx-persistent",)),
+    # ... and past its cap of 256 workgroups: a second and a steady-state tile finish with the counted statistics stores in flight
+    (_lin(20640, 1280, 320, "bias_residual"), "cs", ("auto",)), (_lin(20640, 640, 320, "plain"), "cs", ("auto",)),
+    (_lin(20640, 1024, 320, "bias_residual"), "cs", ("auto",)), (_lin(20640, 512, 320, "plain"), "cs", ("auto",)),
+    (lambda: lnfold_case(13760, 960, 320), "cs", ("auto",)), (lambda: lnfold_case(20640, 512, 320), "cs", ("auto",)),
+    # gathered A on the 128-row kernel: stride 2, folded upsample, fused shortcut, the downsampler's pad, the 128-wide tile
+    (_cv(n=2, c1=64, cout=64, h=5, w=7, stride=2), "cs", ("auto",)), (_cv(n=3, c1=64, cout=128, h=4, w=6, ups=1), "cs", ("auto",)),
+    (_cv(n=2, c1=64, c2=64, cout=64, h=3, w=5, csc=64), "cs", ("auto", "row128-tiles")),
+    (_cv(n=1, c1=128, cout=128, h=13, w=18, stride=2, pad=(0, 1)), "cs", ("auto",)), (_cv(n=1, c1=64, cout=512, h=91, w=91), "cs", ("auto",)),
+    (_cv(n=1, c1=64, cout=320, h=5, w=7), "cs", ("row128-tiles",)),
+    # split-K: the reduce kernel with statistics writes C (32-row blocks; 2689 = 84 * 32 + 1), plain and conv
+    (_lin(2689, 512, 192, "bias2_residual"), "cs", ("split-k-3",)), (_cv(n=1, c1=64, cout=512, h=52, w=52), "cs", ("split-k-3",)),
+    # the 256-wide ping-pong tile by its grid rule, plain and on the temporal gather (the reach table's shapes)
+    (_lin(34721, 256, 640, "plain"), "cs", ("auto",)), (lambda: temporal_conv_case(1, 128, 256, 8, 4341, 5), "cs", ("auto",)),
+    # the temporal gather on the 128-row kernel, unsplit and through the reduce; the parity form (four sets of source-row blocks)
+    (lambda: temporal_conv_case(2, 64, 128, 8, 80, 3), "cs", ("auto", "split-k-3")), (lambda: temporal_conv_case(3, 128, 64, 2, 7, 5), "cs", ("auto",)),
+] + [((lambda n=n, c=c, h=h, w=w: conv_case(n=n, c1=c, cout=c, h=h, w=w, ups=1, parity=True)), "cs", ("auto",)) for n, c, h, w in PARITY_CASES] + [
+    # row statistics: each slot width (bn / 2 of the 128-row kernel: 32, 80, 64; bn / 4 of the ping-pong and persistent kernels: 80, 64)
+    (_lin(130, 192, 64, "plain"), "rs", ("auto",)), (_lin(154, 320, 320, "bias_residual"), "rs", ("row128-tiles",)),
+    (_lin(8193, 512, 64, "bias_residual"), "rs", ("auto",)), (_lin(161, 320, 320, "plain"), "rs", ("pingpong",)),
+    (_lin(34721, 256, 640, "plain"), "rs", ("auto",)), (_lin(160, 320, 320, "bias_residual"), "rs", ("ppx-persistent",)),
+    (_lin(320, 256, 320, "plain"), "rs", ("ppx-persistent",)), (_lin(20640, 640, 320, "plain"), "rs", ("auto",)),
+    (_lin(2689, 512, 192, "bias_residual"), "rs", ("split-k-3",)),          # armed row statistics: planned unsplit under forced split-K
+    # both kinds in one launch
+    (_lin(160, 320, 320, "residual_in_place"), "cs+rs", ("ppx-persistent",)), (_lin(161, 320, 320, "bias_residual"), "cs+rs", ("pingpong", "auto")),
+    (_lin(20640, 1280, 320, "residual_in_place"), "cs+rs", ("auto",)),
+]
+# the halo-patch kernel's modes (each case forces its own kernel): whole-row tiles, 2-D tiles, split-K over slabs, temporal taps 3 / 5
+STATS_FORCED = ([_cv(**k, force=5) for k in HALO_CASES]
+                + [(lambda s=s, t=t: temporal_conv_case(*s, t, force=5)) for s in TCONV_FORCED for t in (3, 5)])
+
+
+def with_stats(base, kind, variants=None):
+    """`base` run with the statistics sink armed.  The outputs "cs" / "rs" are not in `outputs`: their sizes are the plan's, which
+    depends on the variant (statcheck: ops.op_statistics(plan=...) on the GPU, the "## stats" line of the replay on the host)."""
+    import copy
+    c = copy.copy(base)
+    c.__dict__.pop("ref", None)
+    c._ref = lambda: base.ref
+    c.base, c.kind = base, kind
+    c.name = f"{base.name}+{kind}"
+    c.knobs = dict(base.knobs, **{k: 1 for k in (["stats_cs"] if "cs" in kind else []) + (["stats_rs"] if "rs" in kind else [])})
+    if variants is not None:
+        c.variants = variants
+    c.parity = None
+    if base.calls[0][0] == "upsample_conv3x3":
+        a = base.calls[0][1]
+        c.parity = (2 * a["Hi"], 2 * a["Wi"])
+
+    def run(ops, i, o):
+        with ops.op_statistics(colstat=o.get("cs"), rowstat=o.get("rs")):
+            base.run(ops, i, o)
+    c.run = run
+    return c
+
+
+# gn_fold_kernel through lavie_group_norm_stats_f16 on synthetic partials (nb, P, c1, c2, rows, nsets, parity grid of a frame, offset): one
+# block per domain and many; one tensor and two with a straddling group (60 channels per group over 1280 + 640); four parity sets; more
+# than 4 * 256 items per workgroup (70 blocks x 15..16 quads: the unrolled loop runs twice, its tail clamped); group means at 8 sigma
+GN_FOLD = [(2, 64, 320, 0, 64, 1, None, 0.0), (2, 160, 320, 0, 80, 1, None, 0.0), (2, 160, 1280, 640, 80, 1, None, 0.0),
+           (1, 2240, 1280, 640, 32, 1, None, 0.0), (2, 320, 320, 0, 80, 4, (16, 20), 0.0), (2, 160, 320, 0, 80, 1, None, 8.0)]
+# descriptors that cannot serve the GroupNorm (norm.hip gn_colstat_usable): the two-pass path runs, no producer fold is counted.  C % 4
+# != 0 cannot reach the choice: launch_group_norm refuses C % 8 != 0 before it.
+GN_UNUSABLE = {"P % span != 0": dict(span=320), "C mismatch": dict(desc_c=640)}
+ROWSTAT_FINALIZE = [(M, slots, off) for M in (1, 255, 256, 257) for slots in (1, 2, 4, 5) for off in (0.0, 8.0)]
+
+
+@functools.lru_cache(maxsize=None)
+def gn_fold_case(nb, P, c1, c2, rows, nsets, parity, offset, span=None, desc_c=None):
+    """group_norm_case's tensor, reference and bound behind ops.group_norm_stats with host-made partials (fp32 block sums of the fp16
+    tensor in a producer's layout: statcheck.model_colstat).  Outputs: y and the scratch whose head holds (mean, rstd)."""
+    import statcheck as S
+    base = group_norm_case(nb, P, c1, c2, silu=True, eps=1e-5, offset=offset, tag="fold:")
+    xs = [base.inputs["x1"]] + ([base.inputs["x2"]] if c2 else [])
+    ins = dict(base.inputs)
+    set_blocks = nb * P // (rows * nsets)
+    plan = {"rows": rows, "sets": nsets, "set_blocks": set_blocks, "contiguous": 1, "blocks_stored": nsets * set_blocks}
+    descs = []
+    for t, x in enumerate(xs):
+        part = S.model_colstat(x, plan, parity=parity)
+        if desc_c:                                     # a buffer the wider description fits
+            part = torch.cat([part] + [torch.full_like(part, float("nan"))] * (-(-desc_c // x.shape[1]) - 1))
+        ins[f"p{t + 1}"] = part
+        descs.append((part, x.shape[1], rows, nsets, set_blocks))
+    groups = 32
+
+    def run(ops, i, o):
+        d = [ops.producer_stats(i[f"p{t + 1}"], desc_c or x.shape[1], rows, nsets, set_blocks, span or rows * nsets) for t, x in enumerate(xs)]
+        ops.group_norm_stats(i["x1"], i["gamma"], i["beta"], nb, groups, 1e-5, True, x2=i.get("x2"), cs1=d[0], cs2=d[1] if c2 else None,
+                             out=o["y"], ws=o.get("ws"))
+    case = Case(f"gn_fold[nb{nb},P{P},{c1}+{c2},rows{rows},sets{nsets},off{offset},span{span},dc{desc_c}]", ins, dict(base.outputs), run,
+                lambda: base.ref, base.c, base.model, base.where)
+    case.descs, case.gn, case.groups, case.usable = descs, (nb, P, c1 + c2), groups, span is None and desc_c is None
+    d = {f"cs{t + 1}_{k}": v for t, x in enumerate(xs) for k, v in dict(C=desc_c or x.shape[1], rows=rows, nsets=nsets, set_blocks=set_blocks, span=span or rows * nsets).items()}
+    return local_calls(case, [call("group_norm_stats", C1=c1, C2=c2, NB=nb, P=P, groups=groups, silu=1, x2=bool(c2), **d)])
+
+
+@functools.lru_cache(maxsize=None)
+def rowstat_finalize_case(M, slots, offset, cols=64):
+    import statcheck as S
+    g = gen("rowstat_finalize", M, slots, offset)
+    x = (torch.randn(M, slots * cols, generator=g) * (0.5 + torch.rand(M, 1, generator=g)) + offset).half()
+    part = S.model_rowstat(x, {"slots": slots, "cols": cols})
+
+    def run(ops, i, o):
+        ops.rowstat_finalize(i["p"], slots * cols, 1e-5, out=o["out"])
+    case = Case(f"rowstat_finalize[M{M},slots{slots},off{offset}]", {"p": part}, {"out": ((M, 2), f32t)}, run, lambda: {}, 0.0, None,
+                lambda i: "(row %d, %s)" % (i // 2, ("mean", "rstd")[i % 2]))
+    case.row_len = slots * cols
+    return local_calls(case, [call("rowstat_finalize", slots=slots, M=M, row_len=slots * cols)])
+
+
+def stats_local_cases():
+    cs = [gn_fold_case(*s) for s in GN_FOLD] + [gn_fold_case(2, 160, 320, 0, 80, 1, None, 0.0, **kw) for kw in GN_UNUSABLE.values()]
+    return cs + [rowstat_finalize_case(*s) for s in ROWSTAT_FINALIZE]
+
+
+@functools.lru_cache(maxsize=None)
+def stats_cases():
+    cs = [with_stats(mk(), kind, variants) for mk, kind, variants in STATS_TABLE]
+    return cs + [with_stats(mk(), "cs") for mk in STATS_FORCED]
 
 
 # ------------------------------------------------------------------ which kernels the GEMM-family cases reach
@@ -2407,8 +2552,15 @@ def gemm_reach(cases):
         launches = []
         for _ in c.calls:
             launches += next(it)[1]
+        NOTES[(c.name, v)] = [l for l in launches if l.startswith("## ")]
+        launches = [l for l in launches if not l.startswith("## ")]
         reach[(c.name, v)] = None if "!! refused" in launches else launches
     return reach
+
+
+# (case name, variant) -> the "## ..." lines of the last gemm_reach that replayed it: the statistics plan of a launch with the sink
+# armed ("## stats ...", statcheck.parse_stats_line), the producer-count delta of a group_norm_stats call ("## fold=n")
+NOTES = {}
 
 
 def optrace(lines):

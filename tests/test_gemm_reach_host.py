@@ -9,6 +9,7 @@ import shutil
 import pytest
 
 import opcases as C
+import statcheck as S
 
 pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_plan_trace.txt.gz")
@@ -83,7 +84,11 @@ def test_local_kernels_of_a_forward_are_reached(reach, fixture_names):
     assert {"gn_finalize_kernel", "gn_stats_kernel<1>", "gn_stats_kernel<2>", "gn_apply_kernel<1, true>", "gn_apply_kernel<1, false>",
             "gn_apply_kernel<2, true>", "temporal_block_kernel<8>", "temporal_stream_kernel<1, 320, 2>", "temporal_stream_kernel<4, 160, 1>"} <= required
     assert required - names(reach) == set(), sorted(required - names(reach))
-    assert "gn_finalize_kernel" not in C.NO_OPERATOR_ENTRY and "gn_fold_kernel" in C.NO_OPERATOR_ENTRY
+    assert "gn_finalize_kernel" not in C.NO_OPERATOR_ENTRY
+    # the producer-side statistics kernels: a forward's trace names all three, the statistics cases launch all three
+    stats = {"gn_fold_kernel", "rowstat_finalize_kernel", "splitk_reduce_cs_kernel"}
+    assert stats <= fixture_names and stats <= names(reach) and not (stats & set(C.NO_OPERATOR_ENTRY))
+    assert stats <= names(reach, lambda key: key[0].startswith(("gn_fold[", "rowstat_finalize[")) or "+cs" in key[0])
     gn = [c for c in C.all_cases() if c.name.startswith("group_norm[")]
     assert len(gn) == len(C.GN_CASES) + len(C.GN_PAST_SLAB) + len(C.GN_VAE)
     vae = [c for c in gn if c.gn[2] == 128]
@@ -265,6 +270,49 @@ def test_reach_table_entries(reach):
     for n, c, h, w in C.PARITY_CASES:
         name = C.conv_case(n=n, c1=c, cout=c, h=h, w=w, ups=1, parity=True).name
         assert all(C.launch_name(reach[(name, v)][0]) == "igemm_patch_kernel<0, 5, 3>" for v in C.VARIANTS)
+
+
+def epi_linear(name):
+    """whether an igemm_* instantiation has the EPI_LINEAR epilogue: the template argument that holds EPI (0 = linear)"""
+    args = [a.strip() for a in name[name.index("<") + 1:-1].split(",")]
+    return args[{"igemm_kernel": 6, "igemm_pp_kernel": 1, "igemm_ppx_kernel": 0, "igemm_patch_kernel": 0}[name[:name.index("<")]]] == "0"
+
+
+def test_every_linear_instantiation_is_reached_with_column_statistics(reach):
+    """Every EPI_LINEAR igemm_* instantiation some case reaches is also launched UNSPLIT with the statistics sink armed and the plan
+    writing column statistics (split-K leaves them to the reduce kernel: the instantiation's own epilogue branch does not run), or is
+    excused by name in opcases.NO_COLSTAT; the reduce kernel with statistics is reached behind a plain GEMM, a gathered one and the
+    halo-patch kernel."""
+    linear = {n for n in names(reach) if n.startswith("igemm_") and epi_linear(n)}
+    assert len(linear) >= 19, sorted(linear)
+    with_cs, reduce_behind = set(), set()
+    for key, launches in reach.items():
+        notes = [S.parse_stats_line(l) for l in C.NOTES.get(key, []) if l.startswith("## stats ")]
+        if not notes or not notes[0]["colstat"]:
+            continue
+        ks = [C.launch_name(l) for l in launches if C.launch_name(l).startswith(("igemm_", "splitk_reduce"))]
+        if notes[0]["splits"] == 1:
+            assert len(ks) == 1, (key, ks)
+            with_cs.add(ks[0])
+        else:
+            assert ks[1:] == ["splitk_reduce_cs_kernel"] and notes[0]["rows"] == 32 and notes[0]["contiguous"] == 1, (key, ks, notes)
+            reduce_behind.add(ks[0])
+    assert linear - with_cs - set(C.NO_COLSTAT) == set(), sorted(linear - with_cs - set(C.NO_COLSTAT))
+    assert not (set(C.NO_COLSTAT) & with_cs) and set(C.NO_COLSTAT) <= linear and all(len(r) > 20 for r in C.NO_COLSTAT.values())
+    assert {"igemm_kernel<2, 2, 4, 4, 2, false, 0>", "igemm_kernel<2, 2, 4, 4, 2, true, 0>", "igemm_patch_kernel<0, 4, 1>"} <= reduce_behind
+    # row statistics: each kernel family, each slot width the planner yields
+    rs = {}
+    for key, launches in reach.items():
+        notes = [S.parse_stats_line(l) for l in C.NOTES.get(key, []) if l.startswith("## stats ")]
+        if notes and notes[0]["rowstat"]:
+            assert notes[0]["splits"] == 1 and len(launches) == 1, (key, launches)
+            rs.setdefault(C.launch_name(launches[0]).split("<")[0], set()).add(notes[0]["cols"])
+    assert rs == {"igemm_kernel": {32, 64, 80}, "igemm_pp_kernel": {64, 80}, "igemm_ppx_kernel": {64, 80}}, rs
+    # the fold runs for every usable descriptor and for no other
+    for c in C.stats_local_cases():
+        if c.name.startswith("gn_fold["):
+            assert C.NOTES[(c.name, "auto")] == ["## fold=%d" % c.usable], (c.name, C.NOTES[(c.name, "auto")])
+            assert ("gn_fold_kernel" in {C.launch_name(l) for l in reach[(c.name, "auto")]}) == c.usable
 
 
 def test_removing_a_new_case_is_noticed(cases):

@@ -27,8 +27,9 @@ REPLAYED = ("linear", "linear_lnfold", "linear_lnfold_geglu", "conv3x3", "conv3x
             "timestep_sinusoid", "gemv", "pack_conv_in", "conv_in", "pack_conv_out", "conv_out", "add_class_emb_silu", "fill_relpos_bias", "ln_fold",
             "pack_geglu_vec", "copy_rows", "f16_to_f32",
             "geglu_mlp", "temporal_block", "cross_block", "cross_block_long", "proj_qkv", "temporal_attention", "group_norm", "group_norm_affine",
-            "conv_edge_in", "conv_edge_out", "attention")
+            "conv_edge_in", "conv_edge_out", "attention", "group_norm_stats", "rowstat_finalize")
 OPTIONAL = ("bias", "bias2", "R", "x2", "sc1", "sc2", "bias_f16", "b", "tap_bias")
+DESCRIPTORS = ("cs1", "cs2")          # lavie_gn_producer_stats operands: their integer fields are described as cs1_<field> / cs2_<field>
 ALWAYS = {"conv_in": ("bias",), "conv_out": ("bias",), "temporal_attention": ("bias",)}          # operands of the new entries that are not optional there
 
 
@@ -75,7 +76,21 @@ def test_call_description_is_what_run_passes(case, monkeypatch):
         assert out is not None and tuple(out.shape) == tuple(shape) and out.dtype == dtype, what
         return out
     monkeypatch.setattr(ops, "_out", out_as_given)
-    case.run(ops, case.inputs, {k: torch.empty(shape, dtype=dt) for k, (shape, dt) in case.outputs.items()})
+    outs = {k: torch.empty(shape, dtype=dt) for k, (shape, dt) in case.outputs.items()}
+    kind = getattr(case, "kind", "")                   # a statistics case: the sink's buffers are further outputs (sized by the plan on a GPU)
+    if "cs" in kind:
+        outs["cs"] = torch.empty(8)
+    if "rs" in kind:
+        outs["rs"] = torch.empty(1, 1, 2)
+    case.run(ops, case.inputs, outs)
+    armed = [args for name, args in lib.recorded if name == "lavie_debug_op_statistics"]
+    assert {k: v for k, v in case.knobs.items() if k.startswith("stats_")} == ({} if not kind else {k: 1 for k, on in (("stats_cs", "cs" in kind), ("stats_rs", "rs" in kind)) if on})
+    if kind:                                           # armed with exactly the kinds the knobs name, around the launch, then disarmed
+        assert [(a[0] is not None and a[1] > 0, a[2] is not None and a[3] > 0) for a in armed] == [("cs" in kind, "rs" in kind), (False, False)]
+        order = [name for name, _ in lib.recorded if name == "lavie_debug_op_statistics" or re.sub(r"^lavie_|_f16$", "", name) in REPLAYED]
+        assert order[0] == order[-1] == "lavie_debug_op_statistics" and len(order) == 3, order
+    else:
+        assert armed == []
     passed = []
     for name, args in lib.recorded:
         entry = re.sub(r"^lavie_|_f16$|_f32$", "", name) if name != "lavie_f16_to_f32" else "f16_to_f32"
@@ -85,6 +100,11 @@ def test_call_description_is_what_run_passes(case, monkeypatch):
         assert len(params) == len(args), (name, len(params), len(args))
         ints = {p: int(a) for (p, is_int), a in zip(params, args) if is_int}
         ints.update({p: int(a is not None) for (p, _), a in zip(params, args) if p in OPTIONAL and p not in ALWAYS.get(entry, ())})
+        for (p, _), a in zip(params, args):
+            if p in DESCRIPTORS and a is not None:     # ctypes.byref(descriptor)
+                d = a._obj
+                assert d.struct_size == __import__("ctypes").sizeof(d) and d.partials and d.partials_floats > 0
+                ints.update({f"{p}_{f}": int(getattr(d, f)) for f in ("C", "rows", "nsets", "set_blocks", "span")})
         passed.append((entry, ints))
     assert len(passed) == len(case.calls) >= 1, (passed, case.calls)
     for (entry, ints), (want_entry, want) in zip(passed, case.calls):
