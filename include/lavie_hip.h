@@ -437,6 +437,59 @@ typedef struct lavie_window_step_args {
 } lavie_window_step_args;
 int lavie_window_step(const lavie_window_step_args* args, void* stream);
 
+/* Guidance from a per-latent table (additive in ABI 8; csrc/sampler_guidance.hip): a guidance scale of its own
+ * for every latent of a batched call, and guidance rescale (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are
+ * Flawed"; diffusers' rescale_noise_cfg) inside the fused step.  eps = [negative | prompt], fp16 [2 P, per]; for latent p:
+ *   e_i   = fma(g_p, ec_i - eu_i, eu_i)                     fp32, the value the step kernels themselves form
+ *   s_t   = std(ec), s_e = std(e) over the latent's per elements, unbiased (per - 1)
+ *   f_p   = rescale s_t / s_e + (1 - rescale)               in double, stored as fp32
+ *   eps_i = f_p e_i                                         one fp32 multiply, then the plain step of the family from eps
+ * s_e == 0 gives f_p = 1 (diffusers gives NaN there); a NaN or infinity among a latent's predictions makes that latent's f_p NaN and
+ * no other's.  lavie_guidance_table writes table[W][P] = (fp32 g_p, fp32 f_p) in two launches: per-chunk fp32 sums of ec, ec^2,
+ * e, e^2 (a chunk = 2048 elements whatever P or the grid; partials[W P][chunks][4]), then one workgroup per latent that adds the
+ * chunks in ascending order with a fixed tree in double.  rescale == 0 writes f_p = 1 in one launch and touches no partials.
+ * g_p = guidance_dev[p] (P floats on the device) or, with guidance_dev == NULL, `guidance`.  moments != NULL also receives the
+ * four double sums per latent.  W > 1: one eps tensor per frame window, each with statistics of its own.  No floating-point
+ * atomics, fixed order of additions, no host synchronisation, no allocation: bit-reproducible and safe in a capture; partials,
+ * table and moments are the caller's, lavie_guidance_partials_floats gives the partials' size (-1 for arguments out of range).
+ * Checked on the host before anything is dereferenced or launched, each refusal names its argument: args != NULL and its
+ * struct_size; 1 <= W <= 32, P >= 1, W P <= 65535; per >= 2; non-null eps_host and entries, 16-byte aligned when per %% 8 == 0
+ * (16-byte loads; otherwise one element per lane, same arithmetic); finite guidance; rescale in [0, 1]; table != NULL; with
+ * rescale != 0 partials != NULL, 16-byte aligned and partials_floats large enough. */
+typedef struct lavie_guidance_table_args {
+    int struct_size;                  /* sizeof this struct as the CALLER declared it; any other value is refused */
+    int W, P;                         /* eps tensors (1 without windows), latents in each */
+    long long per;                    /* elements of one latent */
+    const void* const* eps_host;      /* [W] HOST array of device pointers, fp16 [2 P, per] each */
+    const float* guidance_dev;        /* [P] fp32, device, or NULL: every latent takes `guidance` */
+    float guidance, rescale;
+    float* partials;                  /* device workspace, see above; may be NULL iff rescale == 0 */
+    long long partials_floats;
+    float* table;                     /* [W][P][2] fp32, device, written */
+    double* moments;                  /* [W][P][4] fp64, device, written; may be NULL */
+} lavie_guidance_table_args;
+long long lavie_guidance_partials_floats(int latents, long long per);
+int lavie_guidance_table(const lavie_guidance_table_args* args, void* stream);
+/* The guided steps above with (g, f) = table[i / per] in place of the `guidance` argument and eps = f e; everything else, the
+ * rounding points included, is the entry point of the same name without `_scaled`, so a table of (g, 1) gives that entry point's
+ * bits in x, x0_prev and model_in.  table: fp32 [P][2] on the device ([W][P][2] for the windowed step, which then needs cfg != 0),
+ * as lavie_guidance_table writes it.  Checked on the host like their plain forms, and: table != NULL; per >= 2 and n == P per for a
+ * whole P in 1..65535 (the known-region forms take per = channels inner from the region); 16-byte alignment of every tensor when
+ * per %% 8 == 0 (eight elements per lane; otherwise one). */
+int lavie_cfg_sampler_step_scaled(const void* eps2, float* x, const float* noise, void* model_in2, long long n, const float* table,
+                                  long long per, float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale,
+                                  void* stream);
+int lavie_cfg_multistep_step_scaled(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, const float* table,
+                                    long long per, float k_x, float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale,
+                                    void* stream);
+int lavie_cfg_sampler_step_known_scaled(const void* eps2, float* x, const float* noise, void* model_in2, long long n, const float* table,
+                                        float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale, void* stream,
+                                        const lavie_known_region* region);
+int lavie_cfg_multistep_step_known_scaled(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, const float* table,
+                                          float k_x, float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale,
+                                          void* stream, const lavie_known_region* region);
+int lavie_window_step_scaled(const lavie_window_step_args* args, const float* table, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Measurement hook: HIP-event timing per kernel class on the launch stream (bench.py's roofline leg).
  * Classes: 0 conv3x3 (implicit GEMM, gathered), 1 linear/1x1/GEGLU GEMM, 2 spatial+text attention core,

@@ -47,6 +47,12 @@ class WindowStepArgsC(C.Structure):   # lavie_window_step_args
                 ("next_input_scale", c_float)]
 
 
+class GuidanceTableArgsC(C.Structure):   # lavie_guidance_table_args
+    _fields_ = [("struct_size", c_int), ("W", c_int), ("P", c_int), ("per", c_ll), ("eps_host", C.POINTER(c_void_p)),
+                ("guidance_dev", c_float_p), ("guidance", c_float), ("rescale", c_float), ("partials", c_float_p),
+                ("partials_floats", c_ll), ("table", c_float_p), ("moments", c_void_p)]
+
+
 class OpStatisticsInfoC(C.Structure):   # lavie_op_statistics_info
     _fields_ = [("struct_size", c_int), ("M", c_int), ("N", c_int), ("splits", c_int), ("colstat_written", c_int), ("colstat_rows", c_int),
                 ("colstat_span", c_int), ("nsets", c_int), ("set_blocks", c_int), ("colstat_contiguous", c_int),
@@ -158,6 +164,17 @@ SIGNATURES = {
                                             c_float, c_float, c_void_p, C.POINTER(KnownRegionC)]),
     "lavie_known_blend_f32": (c_int, [c_float_p, c_void_p, c_int, c_ll, c_float, c_void_p, C.POINTER(KnownRegionC)]),
     "lavie_window_step": (c_int, [C.POINTER(WindowStepArgsC), c_void_p]),
+    "lavie_guidance_partials_floats": (c_ll, [c_int, c_ll]),
+    "lavie_guidance_table": (c_int, [C.POINTER(GuidanceTableArgsC), c_void_p]),
+    "lavie_cfg_sampler_step_scaled": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float_p, c_ll, c_float, c_float, c_float,
+                                               c_float, c_float, c_float, c_void_p]),
+    "lavie_cfg_multistep_step_scaled": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float_p, c_ll, c_float, c_float,
+                                                 c_float, c_float, c_float, c_float, c_void_p]),
+    "lavie_cfg_sampler_step_known_scaled": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float_p, c_float, c_float, c_float,
+                                                     c_float, c_float, c_float, c_void_p, C.POINTER(KnownRegionC)]),
+    "lavie_cfg_multistep_step_known_scaled": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float_p, c_float, c_float,
+                                                       c_float, c_float, c_float, c_float, c_void_p, C.POINTER(KnownRegionC)]),
+    "lavie_window_step_scaled": (c_int, [C.POINTER(WindowStepArgsC), c_float_p, c_void_p]),
     "lavie_debug_force_tile": (c_int, [c_int]),
     "lavie_debug_force_splits": (c_int, [c_int]),
     "lavie_debug_fused_mask": (c_int, [c_int]),

@@ -44,14 +44,17 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
                           height: int = 320, width: int = 512, base_steps: int = 50, guidance_scale: float = 7.5,
                           interp_frames: int = 61, interp_cfg_scale: float = 4.0, vsr_steps: int = 50,
                           vsr_guidance_scale: float = 7.5, noise_level: int = 150, generator=None, decode_final: bool = True,
-                          base_scheduler=None, vsr_scheduler=None, vsr_overlap: int = 0):
+                          base_scheduler=None, vsr_scheduler=None, vsr_overlap: int = 0, base_guidance_rescale: float = 0.0,
+                          vsr_guidance_rescale: float = 0.0):
     """Returns (base_latents, interp_latents, vsr_latents, frames or None).  Text embeddings are passed per stage (the base
     and interpolation stages use SD-1.4's CLIP, 768 wide; the VSR stage the x4-upscaler's, 1024 wide).
     `base_scheduler` / `vsr_scheduler` replace the two diffusers-style stages' schedulers for this call (for instance a
     DPMSolverMultistepScheduler with fewer `base_steps` / `vsr_steps`); the pipelines get their own back afterwards.  The
     interpolation stage samples with its SpacedDiffusion object and has no such switch.
     `vsr_overlap` > 0: the VSR stage samples the 61 frames as ONE run over 8-frame windows sharing that many frames with their
-    neighbours (`upscale_in_chunks(overlap=)`) instead of independent chunks; 0 = the reference's chunks."""
+    neighbours (`upscale_in_chunks(overlap=)`) instead of independent chunks; 0 = the reference's chunks.
+    `base_guidance_rescale` / `vsr_guidance_rescale`: the `guidance_rescale` of the two diffusers-style stages (0 = off).  The
+    interpolation stage's own guidance loop (`forward_with_cfg`) has no such switch."""
     swapped = [(pipe, pipe.scheduler) for pipe, sch in ((base_pipe, base_scheduler), (vsr_pipe, vsr_scheduler)) if sch is not None]
     if base_scheduler is not None:
         base_pipe.scheduler = base_scheduler
@@ -61,7 +64,7 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
         return _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, prompt_embeds, negative_prompt_embeds,
                         vsr_prompt_embeds, vsr_negative_prompt_embeds, interp_prompt_embeds, interp_negative_prompt_embeds, height,
                         width, base_steps, guidance_scale, interp_frames, interp_cfg_scale, vsr_steps, vsr_guidance_scale,
-                        noise_level, generator, decode_final, vsr_overlap)
+                        noise_level, generator, decode_final, vsr_overlap, base_guidance_rescale, vsr_guidance_rescale)
     finally:
         for pipe, own in swapped:
             pipe.scheduler = own
@@ -70,12 +73,14 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
 def _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, prompt_embeds, negative_prompt_embeds,
              vsr_prompt_embeds, vsr_negative_prompt_embeds, interp_prompt_embeds, interp_negative_prompt_embeds, height, width,
              base_steps, guidance_scale, interp_frames, interp_cfg_scale, vsr_steps, vsr_guidance_scale, noise_level, generator,
-             decode_final, vsr_overlap=0):
+             decode_final, vsr_overlap=0, base_guidance_rescale=0.0, vsr_guidance_rescale=0.0):
     dev = base_pipe.device
+    base_kw = dict(guidance_rescale=base_guidance_rescale) if base_guidance_rescale else {}       # absent = the calls without it
+    vsr_kw = dict(guidance_rescale=vsr_guidance_rescale) if vsr_guidance_rescale else {}
     # 1. base T2V (base/pipelines/sample.py:78-91)
     base = base_pipe(prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, height=height, width=width,
                      video_length=16, num_inference_steps=base_steps, guidance_scale=guidance_scale, generator=generator,
-                     output_type="latent").video
+                     output_type="latent", **base_kw).video
     frames16 = decode_frames(vae, base, 0.18215)
     # 2. interpolation 16 -> 61 frames (interpolation/sample.py:135-174)
     copied = interpolation_condition(vae, frames16, interp_frames)
@@ -90,7 +95,7 @@ def _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, p
     # 3. video super-resolution in 8-frame chunks (vsr/sample.py:90-123): the decoded frames are the low-res conditioning
     up = upscale_in_chunks(vsr_pipe, frames61, short_seq=8, overlap=vsr_overlap, prompt_embeds=vsr_prompt_embeds,
                            negative_prompt_embeds=vsr_negative_prompt_embeds, num_inference_steps=vsr_steps,
-                           guidance_scale=vsr_guidance_scale, noise_level=noise_level, generator=generator)
+                           guidance_scale=vsr_guidance_scale, noise_level=noise_level, generator=generator, **vsr_kw)
     frames = decode_frames(vsr_vae, up, None, chunk=1) if decode_final else None
     return base, interp, up, frames
 

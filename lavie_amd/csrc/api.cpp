@@ -524,14 +524,14 @@ static int known_args(const char* who, const lavie_known_region* r, bool mask_op
 
 static int sampler_step_known(const char* who, bool cfg, const void* eps, float* x, const float* noise, void* model_in, long long n,
                               float guidance, float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale,
-                              void* stream, const lavie_known_region* r) {
+                              void* stream, const lavie_known_region* r, const float* table = nullptr) {
     const float s[7] = {guidance, k_x, k_eps, c_x0, c_xt, sigma, next_input_scale};
     LAVIE_CHECK(sigma == 0.f || noise, "%s: noise is null but sigma=%g", who, (double)sigma);
     const void* t[4] = {eps, x, model_in, noise};
     const char* names[4] = {"eps", "x", "model_in", "noise"};
     if (int rc = known_args(who, r, false, n, s, 7, t, names, sigma != 0.f ? 4 : 3)) return rc;     // sigma == 0: noise is not read
     return launch_sampler_step_known(cfg, H(eps), x, noise, H(model_in), n, guidance, k_x, k_eps, c_x0, c_xt, sigma, next_input_scale,
-                                     r->known, r->mask, r->noise_known, r->channels, r->inner, r->a_next, r->s_next, S(stream));
+                                     r->known, r->mask, r->noise_known, r->channels, r->inner, r->a_next, r->s_next, table, S(stream));
 }
 
 int lavie_cfg_sampler_step_known(const void* eps2, float* x, const float* noise, void* model_in2, long long n, float guidance,
@@ -550,14 +550,14 @@ int lavie_sampler_step_known(const void* eps, float* x, const float* noise, void
 
 static int multistep_step_known(const char* who, bool cfg, const void* eps, float* x, float* x0_prev, void* model_in, long long n,
                                 float guidance, float k_x, float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale,
-                                void* stream, const lavie_known_region* r) {
+                                void* stream, const lavie_known_region* r, const float* table = nullptr) {
     const float s[7] = {guidance, k_x, k_eps, c_x0, c_xt, c_prev, next_input_scale};
     const void* t[4] = {eps, x, x0_prev, model_in};
     const char* names[4] = {"eps", "x", "x0_prev", "model_in"};
     if (int rc = known_args(who, r, false, n, s, 7, t, names, 4)) return rc;
     return launch_multistep_step_known(cfg, H(eps), x, x0_prev, H(model_in), n, guidance, k_x, k_eps, c_x0, c_xt, c_prev,
                                        next_input_scale, r->known, r->mask, r->noise_known, r->channels, r->inner, r->a_next,
-                                       r->s_next, S(stream));
+                                       r->s_next, table, S(stream));
 }
 
 int lavie_cfg_multistep_step_known(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, float guidance,
@@ -585,8 +585,7 @@ int lavie_known_blend_f32(float* x, void* model_in, int dup, long long n, float 
 
 // The fused step over overlapping frame windows (sampler_window.hip).  Everything is checked here, on the host, before a table entry
 // is dereferenced or anything is launched; each refusal names its argument.
-int lavie_window_step(const lavie_window_step_args* a, void* stream) {
-    const char* who = "window_step";
+static int window_step(const char* who, const lavie_window_step_args* a, const float* table, void* stream) {
     LAVIE_CHECK(a, "%s: args is null", who);
     LAVIE_CHECK(a->struct_size == (int)sizeof(lavie_window_step_args),
                 "%s: args->struct_size=%d but this library's lavie_window_step_args has %d bytes: the binding's struct layout is "
@@ -673,7 +672,107 @@ int lavie_window_step(const lavie_window_step_args* a, void* stream) {
     p.aux = a->aux;
     p.guidance = a->guidance; p.kx = a->k_x; p.ke = a->k_eps; p.c0 = a->c_x0; p.ct = a->c_xt; p.c4 = a->c4;
     p.in_scale = a->next_input_scale;
+    p.table = table;
     return launch_window_step(p, S(stream));
+}
+
+int lavie_window_step(const lavie_window_step_args* a, void* stream) { return window_step("window_step", a, nullptr, stream); }
+
+// ---- Guidance from a per-latent table (sampler_guidance.hip): the table itself, then the five steps that read it.
+long long lavie_guidance_partials_floats(int latents, long long per) {
+    if (latents < 1 || per < 2 || per > (1ll << 40)) return -1;
+    return (long long)latents * guidance_chunks(per) * 4;
+}
+
+int lavie_guidance_table(const lavie_guidance_table_args* a, void* stream) {
+    const char* who = "guidance_table";
+    LAVIE_CHECK(a, "%s: args is null", who);
+    LAVIE_CHECK(a->struct_size == (int)sizeof(lavie_guidance_table_args),
+                "%s: args->struct_size=%d but this library's lavie_guidance_table_args has %d bytes: the binding's struct layout is "
+                "out of date", who, a->struct_size, (int)sizeof(lavie_guidance_table_args));
+    LAVIE_CHECK(a->W >= 1 && a->W <= LAVIE_WINDOW_MAX_WINDOWS, "%s: W=%d outside 1..%d", who, a->W, LAVIE_WINDOW_MAX_WINDOWS);
+    LAVIE_CHECK(a->P >= 1 && (long long)a->W * a->P <= 65535, "%s: P=%d: W P must be in 1..65535", who, a->P);
+    LAVIE_CHECK(a->per >= 2 && a->per <= (1ll << 40), "%s: per=%lld must be >= 2 (an unbiased deviation needs two elements)", who, a->per);
+    LAVIE_CHECK(a->eps_host, "%s: eps_host is null", who);
+    for (int w = 0; w < a->W; ++w) {
+        LAVIE_CHECK(a->eps_host[w], "%s: eps[%d] is null", who, w);
+        LAVIE_CHECK(a->per % 8 != 0 || ((uintptr_t)a->eps_host[w] & 15) == 0, "%s: eps[%d] at %p is not 16-byte aligned", who, w, a->eps_host[w]);
+    }
+    LAVIE_CHECK(__builtin_isfinite(a->guidance), "%s: guidance (%g) is not finite", who, (double)a->guidance);
+    LAVIE_CHECK(a->rescale >= 0.f && a->rescale <= 1.f, "%s: rescale=%g must be in [0, 1]", who, (double)a->rescale);
+    LAVIE_CHECK(a->table, "%s: table is null", who);
+    if (a->rescale != 0.f) {
+        const long long need = lavie_guidance_partials_floats(a->W * a->P, a->per);
+        LAVIE_CHECK(a->partials, "%s: partials is null but rescale=%g", who, (double)a->rescale);
+        LAVIE_CHECK(a->partials_floats >= need, "%s: partials_floats=%lld, W P chunks 4 = %lld needed", who, a->partials_floats, need);
+        LAVIE_CHECK(((uintptr_t)a->partials & 15) == 0, "%s: partials at %p is not 16-byte aligned", who, (const void*)a->partials);
+    }
+    LAVIE_CHECK(((uintptr_t)a->moments & 7) == 0, "%s: moments at %p is not 8-byte aligned", who, (const void*)a->moments);
+    return launch_guidance_table(reinterpret_cast<const half_t* const*>(a->eps_host), a->W, a->P, a->per, a->guidance_dev, a->guidance,
+                                 a->rescale, a->partials, a->table, a->moments, S(stream));
+}
+
+// Host-side argument check of the two plain scaled steps, before any HIP call: those of multistep_args, plus the table and the latent size.
+static int scaled_args(const char* who, const void* eps, const float* x, const float* aux, bool aux_used, const void* model_in,
+                       long long n, const float* table, long long per, const float* scalars, int nscalars) {
+    LAVIE_CHECK(eps && x && model_in, "%s: null argument", who);
+    LAVIE_CHECK(table, "%s: table is null", who);
+    LAVIE_CHECK(per >= 2 && per <= (1ll << 40), "%s: per=%lld must be >= 2", who, per);
+    LAVIE_CHECK(n >= 1 && n % per == 0, "%s: n=%lld is not a whole number of latents of per=%lld", who, n, per);
+    LAVIE_CHECK(n / per <= 65535, "%s: n / per = %lld latents, at most 65535 fit one launch", who, n / per);
+    for (int i = 0; i < nscalars; ++i)
+        LAVIE_CHECK(__builtin_isfinite(scalars[i]), "%s: scalar argument %d (%g) is not finite", who, i, (double)scalars[i]);
+    if (per % 8 == 0) {
+        const void* ptrs[4] = {eps, x, model_in, aux_used ? aux : nullptr};
+        for (const void* p : ptrs)
+            LAVIE_CHECK(((uintptr_t)p & 15) == 0, "%s: tensor at %p is not 16-byte aligned", who, p);
+    }
+    return 0;
+}
+
+int lavie_cfg_sampler_step_scaled(const void* eps2, float* x, const float* noise, void* model_in2, long long n, const float* table,
+                                  long long per, float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale,
+                                  void* stream) {
+    const char* who = "cfg_sampler_step_scaled";
+    const float s[6] = {k_x, k_eps, c_x0, c_xt, sigma, next_input_scale};
+    LAVIE_CHECK(sigma == 0.f || noise, "%s: noise is null but sigma=%g", who, (double)sigma);
+    if (int rc = scaled_args(who, eps2, x, noise, sigma != 0.f, model_in2, n, table, per, s, 6)) return rc;
+    return launch_cfg_sampler_step_scaled(H(eps2), x, noise, H(model_in2), n, per, table, k_x, k_eps, c_x0, c_xt, sigma,
+                                          next_input_scale, S(stream));
+}
+
+int lavie_cfg_multistep_step_scaled(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, const float* table,
+                                    long long per, float k_x, float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale,
+                                    void* stream) {
+    const char* who = "cfg_multistep_step_scaled";
+    const float s[6] = {k_x, k_eps, c_x0, c_xt, c_prev, next_input_scale};
+    LAVIE_CHECK(x0_prev, "%s: x0_prev is null", who);
+    if (int rc = scaled_args(who, eps2, x, x0_prev, true, model_in2, n, table, per, s, 6)) return rc;
+    return launch_cfg_multistep_step_scaled(H(eps2), x, x0_prev, H(model_in2), n, per, table, k_x, k_eps, c_x0, c_xt, c_prev,
+                                            next_input_scale, S(stream));
+}
+
+int lavie_cfg_sampler_step_known_scaled(const void* eps2, float* x, const float* noise, void* model_in2, long long n, const float* table,
+                                        float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale, void* stream,
+                                        const lavie_known_region* region) {
+    LAVIE_CHECK(table, "cfg_sampler_step_known_scaled: table is null");
+    return sampler_step_known("cfg_sampler_step_known_scaled", true, eps2, x, noise, model_in2, n, 1.0f, k_x, k_eps, c_x0, c_xt, sigma,
+                              next_input_scale, stream, region, table);
+}
+
+int lavie_cfg_multistep_step_known_scaled(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, const float* table,
+                                          float k_x, float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale,
+                                          void* stream, const lavie_known_region* region) {
+    LAVIE_CHECK(table, "cfg_multistep_step_known_scaled: table is null");
+    return multistep_step_known("cfg_multistep_step_known_scaled", true, eps2, x, x0_prev, model_in2, n, 1.0f, k_x, k_eps, c_x0, c_xt,
+                                c_prev, next_input_scale, stream, region, table);
+}
+
+int lavie_window_step_scaled(const lavie_window_step_args* a, const float* table, void* stream) {
+    const char* who = "window_step_scaled";
+    LAVIE_CHECK(table, "%s: table is null", who);
+    LAVIE_CHECK(!a || a->cfg != 0, "%s: cfg=0: the table holds guidance scales, the call must be guided", who);
+    return window_step(who, a, table, stream);
 }
 
 int lavie_latents_to_scaled_model_input1(const float* x, void* model_in, long long n, float input_scale, void* stream) {

@@ -1087,6 +1087,140 @@ int main(int argc, char** argv) {
         REQUIRE(lavie_window_step(&q, nullptr) == 0);
         REQUIRE(lavie_hostcheck_launches() == before + 6);
     }
+    {   // guidance from a per-latent table: the table's two launches (one when rescale == 0), the five steps that read it in the
+        // eight-element and the one-element form with exactly sized buffers; every refusal comes before a launch and names its argument
+        const int P = 2, C = 2, inner = 12, per = C * inner, n = P * per;
+        alignas(16) static unsigned short eps[2 * n], min2[2 * n];
+        alignas(16) static float x[n], nz[n], hist[n], known[n], mask[P * inner], noise[n];
+        alignas(16) static float table[2 * 2 * P], gdev[P] = {5.f, 9.f};
+        alignas(16) static double moments[4 * P];
+        auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+        const long long need = lavie_guidance_partials_floats(P, per);
+        REQUIRE(need == P * 1 * 4 && lavie_guidance_partials_floats(1, 655360) == 320 * 4 && lavie_guidance_partials_floats(3, 2049) == 3 * 2 * 4);
+        REQUIRE(lavie_guidance_partials_floats(0, 8) == -1 && lavie_guidance_partials_floats(1, 1) == -1);
+        std::vector<float> partials((size_t)need + 4);
+        float* part = partials.data() + (((uintptr_t)partials.data() & 15) ? (16 - ((uintptr_t)partials.data() & 15)) / 4 : 0);
+        const void* srcs[1] = {eps};
+        lavie_guidance_table_args g{};
+        g.struct_size = (int)sizeof(g);
+        g.W = 1; g.P = P; g.per = per; g.eps_host = srcs; g.guidance_dev = gdev; g.guidance = 7.5f; g.rescale = 0.7f;
+        g.partials = part; g.partials_floats = need; g.table = table; g.moments = moments;
+        const long before = lavie_hostcheck_launches();
+        REQUIRE(lavie_guidance_table(&g, nullptr) == 0);                       // moments + fold
+        lavie_guidance_table_args h = g;
+        h.rescale = 0.f; h.partials = nullptr; h.partials_floats = 0; h.guidance_dev = nullptr; h.moments = nullptr;
+        REQUIRE(lavie_guidance_table(&h, nullptr) == 0);                       // the fold alone
+        h = g; h.per = per - 1; h.eps_host = srcs;                             // one element per lane: no alignment asked of eps
+        const void* odd[1] = {eps + 1};
+        h.eps_host = odd;
+        REQUIRE(lavie_guidance_table(&h, nullptr) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 5);
+        REQUIRE(refused(lavie_guidance_table(nullptr, nullptr), "args"));
+        h = g; h.struct_size -= 8;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "struct_size"));
+        h = g; h.W = 0;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "W=0"));
+        h = g; h.W = 33;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "W=33"));
+        h = g; h.P = 0;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "P=0"));
+        h = g; h.P = 70000;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "P=70000"));
+        h = g; h.per = 1;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "per=1"));
+        h = g; h.eps_host = nullptr;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "eps_host"));
+        const void* none[1] = {nullptr};
+        h = g; h.eps_host = none;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "eps[0] is null"));
+        h = g; h.eps_host = odd;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "eps[0] at"));
+        h = g; h.guidance = __builtin_nanf("");
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "guidance"));
+        h = g; h.rescale = 1.5f;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "rescale=1.5"));
+        h = g; h.rescale = -0.1f;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "rescale"));
+        h = g; h.rescale = __builtin_nanf("");
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "rescale"));
+        h = g; h.table = nullptr;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "table is null"));
+        h = g; h.partials = nullptr;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "partials is null"));
+        h = g; h.partials_floats = need - 1;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "partials_floats"));
+        h = g; h.partials = part + 1;
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "partials at"));
+        h = g; h.moments = (double*)((char*)moments + 4);
+        REQUIRE(refused(lavie_guidance_table(&h, nullptr), "moments at"));
+        REQUIRE(lavie_hostcheck_launches() == before + 5);
+        // the two plain scaled steps
+        REQUIRE(lavie_cfg_sampler_step_scaled(eps, x, nz, min2, n, table, per, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr) == 0);
+        REQUIRE(lavie_cfg_sampler_step_scaled(eps, x, nullptr, min2, n, table, per, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 0.9f, nullptr) == 0);
+        REQUIRE(lavie_cfg_multistep_step_scaled(eps, x, hist, min2, n, table, per, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 1.f, nullptr) == 0);
+        REQUIRE(lavie_cfg_multistep_step_scaled(eps, x, hist, min2, n, table, per, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 1.f, nullptr) == 0);
+        REQUIRE(lavie_cfg_sampler_step_scaled(eps + 1, x + 1, nz + 1, min2 + 1, 2 * 21, table, 21, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 10);
+        REQUIRE(refused(lavie_cfg_sampler_step_scaled(eps, x, nz, min2, n, nullptr, per, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr), "table is null"));
+        REQUIRE(refused(lavie_cfg_sampler_step_scaled(nullptr, x, nz, min2, n, table, per, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr), "null argument"));
+        REQUIRE(refused(lavie_cfg_sampler_step_scaled(eps, x, nullptr, min2, n, table, per, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr), "noise is null"));
+        REQUIRE(refused(lavie_cfg_sampler_step_scaled(eps, x, nz, min2, n, table, 1, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr), "per=1"));
+        REQUIRE(refused(lavie_cfg_sampler_step_scaled(eps, x, nz, min2, n - 1, table, per, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr), "whole number"));
+        REQUIRE(refused(lavie_cfg_sampler_step_scaled(eps, x, nz, min2, 0, table, per, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr), "n=0"));
+        REQUIRE(refused(lavie_cfg_sampler_step_scaled(eps, x, nz, min2, n, table, per, 1.f, __builtin_nanf(""), 0.3f, 0.7f, 0.1f, 0.9f, nullptr), "finite"));
+        REQUIRE(refused(lavie_cfg_sampler_step_scaled(eps, x + 1, nz, min2, n, table, per, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr), "16-byte"));
+        REQUIRE(refused(lavie_cfg_multistep_step_scaled(eps, x, nullptr, min2, n, table, per, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 1.f, nullptr), "x0_prev"));
+        REQUIRE(refused(lavie_cfg_multistep_step_scaled(eps, x, hist + 2, min2, n, table, per, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 1.f, nullptr), "16-byte"));
+        // the two steps around known latents
+        lavie_known_region r{};
+        r.struct_size = (int)sizeof(r);
+        r.channels = C; r.inner = inner; r.known = known; r.mask = mask; r.noise_known = noise; r.a_next = 0.9f; r.s_next = 0.4f;
+        REQUIRE(lavie_cfg_sampler_step_known_scaled(eps, x, nz, min2, n, table, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &r) == 0);
+        REQUIRE(lavie_cfg_multistep_step_known_scaled(eps, x, hist, min2, n, table, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 1.f, nullptr, &r) == 0);
+        REQUIRE(lavie_cfg_multistep_step_known_scaled(eps, x, hist, min2, n, table, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 1.f, nullptr, &r) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 13);
+        REQUIRE(refused(lavie_cfg_sampler_step_known_scaled(eps, x, nz, min2, n, nullptr, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &r), "table is null"));
+        REQUIRE(refused(lavie_cfg_multistep_step_known_scaled(eps, x, hist, min2, n, nullptr, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 1.f, nullptr, &r), "table is null"));
+        REQUIRE(refused(lavie_cfg_sampler_step_known_scaled(eps, x, nz, min2, n, table, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, nullptr), "region"));
+        // the windowed step: P 1, C 2, F 6, L 4, starts 0 and 2, hw 8 then 3
+        {
+            const int hw = 8, nclip = 1 * 2 * 6 * hw, nwin = 2 * 1 * 2 * 4 * hw;
+            alignas(16) static float wx[nclip], waux[nclip], wtable[2 * 1 * 2] = {7.5f, 1.f, 7.5f, 0.9f};
+            alignas(16) static unsigned short e0[nwin], e1[nwin], m0[nwin], m1[nwin];
+            int starts[2] = {0, 2};
+            float profile[4] = {1, 2, 2, 1};
+            const void* weps[2] = {e0, e1};
+            void* wmin[2] = {m0, m1};
+            lavie_window_step_args a{};
+            a.struct_size = (int)sizeof(a);
+            a.family = 0; a.cfg = 1; a.P = 1; a.C = 2; a.F = 6; a.hw = hw; a.W = 2; a.L = 4;
+            a.starts_host = starts; a.profile_host = profile; a.eps_host = weps; a.model_in_host = wmin; a.x = wx; a.aux = waux;
+            a.guidance = 1.f; a.k_x = 1.f; a.k_eps = 0.5f; a.c_x0 = 0.3f; a.c_xt = 0.7f; a.c4 = 0.1f; a.next_input_scale = 0.9f;
+            REQUIRE(lavie_window_step_scaled(&a, wtable, nullptr) == 0);
+            lavie_window_step_args b = a;
+            b.family = 1; b.c4 = 0.5f;
+            REQUIRE(lavie_window_step_scaled(&b, wtable, nullptr) == 0);
+            b.c4 = 0.f;
+            REQUIRE(lavie_window_step_scaled(&b, wtable, nullptr) == 0);
+            b = a; b.hw = 3;
+            REQUIRE(lavie_window_step_scaled(&b, wtable, nullptr) == 0);
+            const void* both[2] = {e0, e1};
+            lavie_guidance_table_args t = g;
+            t.W = 2; t.P = 1; t.per = 2 * 4 * hw; t.eps_host = both; t.guidance_dev = nullptr; t.table = wtable; t.moments = nullptr;
+            std::vector<float> wpart((size_t)lavie_guidance_partials_floats(2, t.per) + 4);
+            t.partials = wpart.data() + (((uintptr_t)wpart.data() & 15) ? (16 - ((uintptr_t)wpart.data() & 15)) / 4 : 0);
+            t.partials_floats = lavie_guidance_partials_floats(2, t.per);
+            REQUIRE(lavie_guidance_table(&t, nullptr) == 0);
+            REQUIRE(lavie_hostcheck_launches() == before + 19);
+            REQUIRE(refused(lavie_window_step_scaled(&a, nullptr, nullptr), "table is null"));
+            REQUIRE(refused(lavie_window_step_scaled(nullptr, wtable, nullptr), "args"));
+            b = a; b.cfg = 0;
+            REQUIRE(refused(lavie_window_step_scaled(&b, wtable, nullptr), "cfg=0"));
+            b = a; b.W = 0;
+            REQUIRE(refused(lavie_window_step_scaled(&b, wtable, nullptr), "W=0"));
+            REQUIRE(lavie_hostcheck_launches() == before + 19);
+        }
+    }
     {   // the VAE's edge convolutions and the asymmetric-pad stride-2 conv: accepted calls reach the (stubbed) launch with exactly
         // sized buffers (packing, odd Cin, ragged last tile); every refusal comes before a HIP call and names its argument
         const int N = 2, Hh = 5, Ww = 7, px = N * Hh * Ww;

@@ -129,15 +129,16 @@ int launch_multistep_step(const half_t* eps, float* x, float* x0_prev, half_t* m
                           float c0, float ct, float cp, float in_scale, hipStream_t stream);
 // ---- sampler_known.hip : the steps above around known latents (known-region replacement inside the step kernel)
 //   x' = select(mask, plain step's x', a_next known + s_next noise_known); cfg picks the guided variant; n = P * channels * inner;
-//   with inner % 8 == 0 every tensor must be 16-byte aligned (checked by the C entry points).
+//   with inner % 8 == 0 every tensor must be 16-byte aligned (checked by the C entry points).  table != nullptr (cfg only): guidance
+//   and rescale factor per latent from table[P][2] (sampler_guidance.hip) instead of `guidance`.
 int launch_sampler_step_known(bool cfg, const half_t* eps2, float* x, const float* noise, half_t* model_in2, int64_t n,
                               float guidance, float kx, float ke, float c0, float ct, float sigma, float in_scale,
                               const float* known, const float* mask, const float* noise_known, int channels, int64_t inner,
-                              float a_next, float s_next, hipStream_t stream);
+                              float a_next, float s_next, const float* table, hipStream_t stream);
 int launch_multistep_step_known(bool cfg, const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n,
                                 float guidance, float kx, float ke, float c0, float ct, float cp, float in_scale,
                                 const float* known, const float* mask, const float* noise_known, int channels, int64_t inner,
-                                float a_next, float s_next, hipStream_t stream);
+                                float a_next, float s_next, const float* table, hipStream_t stream);
 // x <- select(mask, x, a_next known + s_next noise_known) (mask == nullptr: mask = 1 everywhere); model_in = fp16(x in_scale), twice when dup
 int launch_known_blend(float* x, half_t* model_in, bool dup, int64_t n, float in_scale, const float* known, const float* mask,
                        const float* noise_known, int channels, int64_t inner, float a_next, float s_next, hipStream_t stream);
@@ -161,8 +162,25 @@ struct WindowStepParams {
     float* x;
     float* aux;
     float guidance, kx, ke, c0, ct, c4, in_scale;
+    const float* table;     // nullptr, or [W][P][2] (guidance, rescale factor) per window and latent (sampler_guidance.hip); needs cfg
 };
 int launch_window_step(const WindowStepParams& a, hipStream_t stream);
+// ---- sampler_guidance.hip : guidance scale and guidance-rescale factor per latent, from device memory.
+//   launch_guidance_table: eps[w] = fp16 [2 P, per] of window w (W = 1 without windows); writes partials (guidance_chunks(per) * 4
+//   floats per latent, untouched when phi == 0), table[W][P] = (g_p, f_p) and, if given, moments[W][P] = the four double sums
+//   (ec, ec^2, e, e^2).  g_p = guidance_dev[p] (device, may be nullptr) or `guidance`.  Two launches (one when phi == 0).
+//   The scaled steps are the guided plain steps with (g, f) = table[i / per] and eps = f e; n = P per; with per % 8 == 0 every
+//   tensor must be 16-byte aligned (checked by the C entry points).
+constexpr int kGuidanceChunk = 2048;
+int64_t guidance_chunks(int64_t per);
+int launch_guidance_table(const half_t* const* eps, int W, int P, int64_t per, const float* guidance_dev, float guidance, float phi,
+                          float* partials, float* table, double* moments, hipStream_t stream);
+int launch_cfg_sampler_step_scaled(const half_t* eps2, float* x, const float* noise, half_t* model_in2, int64_t n, int64_t per,
+                                   const float* table, float kx, float ke, float c0, float ct, float sigma, float in_scale,
+                                   hipStream_t stream);
+int launch_cfg_multistep_step_scaled(const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n, int64_t per,
+                                     const float* table, float kx, float ke, float c0, float ct, float cp, float in_scale,
+                                     hipStream_t stream);
 int launch_fill_relpos_bias(const half_t* emb, const int* buckets, float* out, int heads, int F, hipStream_t stream);
 
 // ---- pack.hip : one-off weight repacking at load time

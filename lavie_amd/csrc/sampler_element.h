@@ -1,8 +1,8 @@
 // Per-element arithmetic and vector accesses shared by the step kernels that restate the plain sampler steps of elementwise.hip
 // with something folded in (sampler_known.hip: the known-region replacement; sampler_window.hip: the fusion of overlapping frame
-// windows).  Contraction is off and every fused multiply-add is spelled out, as in multistep_element (elementwise.hip): the
-// compiler cannot move a rounding point, so a kernel built from these pieces gives the plain kernel's bits wherever its own
-// addition is the identity.
+// windows; sampler_guidance.hip: guidance scale and rescale factor per latent from a table).  Contraction is off and every fused
+// multiply-add is spelled out, as in multistep_element (elementwise.hip): the compiler cannot move a rounding point, so a kernel
+// built from these pieces gives the plain kernel's bits wherever its own addition is the identity.
 #pragma once
 #include "common.h"
 
@@ -14,6 +14,13 @@ struct StepCoef { float guidance, kx, ke, c0, ct, c4; };     // c4: sigma (five-
 template <bool CFG> __device__ __forceinline__ float guided_eps(float eu, float ec, float guidance) {
 #pragma clang fp contract(off)
     return CFG ? __builtin_fmaf(guidance, ec - eu, eu) : eu;
+}
+
+// The guided eps of a latent whose (guidance, factor) pair comes from a table (sampler_guidance.hip): guided_eps<true> times the
+// latent's rescale factor, one fp32 multiply.  f == 1 returns guided_eps<true>'s bits.
+__device__ __forceinline__ float scaled_guided_eps(float eu, float ec, float guidance, float f) {
+#pragma clang fp contract(off)
+    return f * guided_eps<true>(eu, ec, guidance);
 }
 
 // The instructions sampler_step_kernel (elementwise.hip) compiles to, spelled out, from eps on: x0 one fma, x' the sum of two

@@ -36,16 +36,25 @@ __device__ __forceinline__ float known_select(float m, float free_v, float pinne
 
 // FAM 0: five-coefficient family (aux = the step's noise, read when c4 != 0); FAM 1: multistep family (aux = x0_prev, read when
 // HIST, always written); FAM 2: the start blend (no eps, xm = x; CFG = write the model input twice).  W = elements per lane.
-template <int FAM, bool CFG, bool HIST, int W>
+// TAB: the latent's guidance scale and rescale factor come from table[latent] = (g, f) (sampler_guidance.hip) and eps = f e;
+// `table` is the LAST kernel argument, so the forms without it keep their argument offsets and their instruction text.
+template <int FAM, bool CFG, bool HIST, int W, bool TAB = false>
 __global__ __launch_bounds__(256) void known_step_kernel(const half_t* __restrict__ eps2, float* __restrict__ x,
                                                          float* __restrict__ aux, half_t* __restrict__ model_in2, long n,
-                                                         int channels, long inner, StepCoef c, KnownOperands k, float in_scale) {
+                                                         int channels, long inner, StepCoef c, KnownOperands k, float in_scale,
+                                                         const float* __restrict__ table) {
     const long j0 = ((long)blockIdx.x * 256 + threadIdx.x) * W;
     if (j0 >= inner) return;
     const long i = (long)blockIdx.y * inner + j0;                       // element in [P, C, inner]
     const long mi = (long)(blockIdx.y / (unsigned)channels) * inner + j0;     // its mask element in [P, 1, inner]
     float xt[W], eu[W], ec[W], ax[W], kn[W], nk[W], m[W], xn[W], hist[W];
     half_t h[W];
+    float g = 0.f, f = 0.f;
+    if constexpr (TAB) {
+        const unsigned p = blockIdx.y / (unsigned)channels;
+        g = table[2 * p];
+        f = table[2 * p + 1];
+    }
     load_f32<W>(x + i, xt);
     load_f32<W>(k.known + i, kn);
     if (k.s != 0.f) load_f32<W>(k.noise + i, nk);
@@ -60,7 +69,11 @@ __global__ __launch_bounds__(256) void known_step_kernel(const half_t* __restric
 #pragma clang fp contract(off)
         const float mj = k.mask ? m[j] : 1.f;
         float x0 = 0.f, xm;
-        if (FAM == 0) xm = five_coefficient_element<CFG>(eu[j], CFG ? ec[j] : 0.f, xt[j], c.c4 != 0.f ? ax[j] : 0.f, c);
+        if constexpr (TAB) {
+            const float eps = scaled_guided_eps(eu[j], ec[j], g, f);
+            if (FAM == 0) xm = five_coefficient_from_eps(eps, xt[j], c.c4 != 0.f ? ax[j] : 0.f, c);
+            else multistep_from_eps<HIST>(eps, xt[j], HIST ? ax[j] : 0.f, c, x0, xm);
+        } else if (FAM == 0) xm = five_coefficient_element<CFG>(eu[j], CFG ? ec[j] : 0.f, xt[j], c.c4 != 0.f ? ax[j] : 0.f, c);
         else if (FAM == 1) multistep_known_element<CFG, HIST>(eu[j], CFG ? ec[j] : 0.f, xt[j], HIST ? ax[j] : 0.f, c, x0, xm);
         else xm = xt[j];
         const float xk = k.s != 0.f ? __builtin_fmaf(k.s, nk[j], k.a * kn[j]) : k.a * kn[j];
@@ -74,18 +87,19 @@ __global__ __launch_bounds__(256) void known_step_kernel(const half_t* __restric
     if (CFG) store_f16<W>(model_in2 + n + i, h);
 }
 
-template <int FAM, bool CFG, bool HIST>
+template <int FAM, bool CFG, bool HIST, bool TAB = false>
 static int launch_known(const half_t* eps2, float* x, float* aux, half_t* model_in2, int64_t n, const StepCoef& c,
-                        const KnownOperands& k, int channels, int64_t inner, float in_scale, hipStream_t stream) {
+                        const KnownOperands& k, int channels, int64_t inner, float in_scale, hipStream_t stream,
+                        const float* table = nullptr) {
     const int64_t planes = n / inner;
     LAVIE_CHECK(planes >= 1 && planes <= 65535, "known-region step: %lld (video, channel) planes do not fit one launch",
                 (long long)planes);
     const bool vec = inner % 8 == 0;
     const int64_t blocks = ((vec ? inner / 8 : inner) + 255) / 256;
     LAVIE_CHECK(blocks <= 0x7fffffff, "known-region step: inner=%lld does not fit one launch", (long long)inner);
-    auto kern = vec ? known_step_kernel<FAM, CFG, HIST, 8> : known_step_kernel<FAM, CFG, HIST, 1>;
+    auto kern = vec ? known_step_kernel<FAM, CFG, HIST, 8, TAB> : known_step_kernel<FAM, CFG, HIST, 1, TAB>;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, eps2, x, aux, model_in2, (long)n,
-                       channels, (long)inner, c, k, in_scale);
+                       channels, (long)inner, c, k, in_scale, table);
     LAVIE_HIP(hipGetLastError());
     return 0;
 }
@@ -93,10 +107,11 @@ static int launch_known(const half_t* eps2, float* x, float* aux, half_t* model_
 int launch_sampler_step_known(bool cfg, const half_t* eps2, float* x, const float* noise, half_t* model_in2, int64_t n,
                               float guidance, float kx, float ke, float c0, float ct, float sigma, float in_scale,
                               const float* known, const float* mask, const float* noise_known, int channels, int64_t inner,
-                              float a_next, float s_next, hipStream_t stream) {
+                              float a_next, float s_next, const float* table, hipStream_t stream) {
     const StepCoef c{guidance, kx, ke, c0, ct, sigma};
     const KnownOperands k{known, mask, noise_known, a_next, s_next};
     float* aux = const_cast<float*>(noise);              // FAM 0 only reads it
+    if (table) return launch_known<0, true, false, true>(eps2, x, aux, model_in2, n, c, k, channels, inner, in_scale, stream, table);
     return cfg ? launch_known<0, true, false>(eps2, x, aux, model_in2, n, c, k, channels, inner, in_scale, stream)
                : launch_known<0, false, false>(eps2, x, aux, model_in2, n, c, k, channels, inner, in_scale, stream);
 }
@@ -104,9 +119,12 @@ int launch_sampler_step_known(bool cfg, const half_t* eps2, float* x, const floa
 int launch_multistep_step_known(bool cfg, const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n,
                                 float guidance, float kx, float ke, float c0, float ct, float cp, float in_scale,
                                 const float* known, const float* mask, const float* noise_known, int channels, int64_t inner,
-                                float a_next, float s_next, hipStream_t stream) {
+                                float a_next, float s_next, const float* table, hipStream_t stream) {
     const StepCoef c{guidance, kx, ke, c0, ct, cp};
     const KnownOperands k{known, mask, noise_known, a_next, s_next};
+    if (table)
+        return cp != 0.f ? launch_known<1, true, true, true>(eps2, x, x0_prev, model_in2, n, c, k, channels, inner, in_scale, stream, table)
+                         : launch_known<1, true, false, true>(eps2, x, x0_prev, model_in2, n, c, k, channels, inner, in_scale, stream, table);
     if (cfg)
         return cp != 0.f ? launch_known<1, true, true>(eps2, x, x0_prev, model_in2, n, c, k, channels, inner, in_scale, stream)
                          : launch_known<1, true, false>(eps2, x, x0_prev, model_in2, n, c, k, channels, inner, in_scale, stream);

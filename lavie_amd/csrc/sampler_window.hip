@@ -36,9 +36,16 @@ static_assert(sizeof(WindowTable) < 1024, "the window table travels as a kernel 
 struct WindowShape { int P, C, F, W, L; long hw; };
 
 // FAM 0: five-coefficient family; FAM 1: multistep family.  V = elements per lane.
-template <int FAM, bool CFG, bool HIST, int V>
+// TAB: e_w = f fma(g, ec_w - eu_w, eu_w) with (g, f) = table[w][p] (sampler_guidance.hip): every window's prediction is rescaled
+// from that window's own statistics before the windows are averaged.  The table pointer is a parameter PACK, empty or one
+// `const float*`: with the empty pack the kernel's argument list, and with it its instruction text, is what it was without the table
+// (an unused trailing pointer moved the scheduling of the argument loads of the guided forms).
+template <int FAM, bool CFG, bool HIST, int V, typename... Table>
 __global__ __launch_bounds__(256) void window_step_kernel(float* __restrict__ x, float* __restrict__ aux, WindowTable t, WindowShape s,
-                                                          StepCoef c, float in_scale) {
+                                                          StepCoef c, float in_scale, Table... table_arg) {
+    constexpr bool TAB = sizeof...(Table) != 0;
+    const float* table = nullptr;
+    if constexpr (TAB) table = (table_arg, ...);
     const long j0 = ((long)blockIdx.x * 256 + threadIdx.x) * V;
     if (j0 >= s.hw) return;
     // the plane: all of this is block-uniform
@@ -70,10 +77,16 @@ __global__ __launch_bounds__(256) void window_step_kernel(float* __restrict__ x,
         const long wi = (((long)p * s.C + ch) * s.L + (f - t.start[w])) * s.hw + j0;       // element in [nb, C, L, hw], first half
         load_f16<V>(t.eps[w] + wi, eu);
         if (CFG) load_f16<V>(t.eps[w] + half_stride + wi, ec);
+        float gw = 0.f, fw = 0.f;           // block-uniform: the pair of (window, latent)
+        if constexpr (TAB) {
+            gw = table[2 * (w * s.P + p)];
+            fw = table[2 * (w * s.P + p) + 1];
+        }
 #pragma unroll
         for (int j = 0; j < V; ++j) {
 #pragma clang fp contract(off)
-            eps[j] = __builtin_fmaf(nw, guided_eps<CFG>(eu[j], CFG ? ec[j] : 0.f, c.guidance), eps[j]);
+            if constexpr (TAB) eps[j] = __builtin_fmaf(nw, scaled_guided_eps(eu[j], ec[j], gw, fw), eps[j]);
+            else eps[j] = __builtin_fmaf(nw, guided_eps<CFG>(eu[j], CFG ? ec[j] : 0.f, c.guidance), eps[j]);
         }
     }
 #pragma unroll
@@ -92,7 +105,7 @@ __global__ __launch_bounds__(256) void window_step_kernel(float* __restrict__ x,
     }
 }
 
-template <int FAM, bool CFG, bool HIST>
+template <int FAM, bool CFG, bool HIST, bool TAB = false>
 static int launch_window(const WindowStepParams& a, hipStream_t stream) {
     const int64_t planes = (int64_t)a.P * a.C * a.F;
     LAVIE_CHECK(planes >= 1 && planes <= 65535, "window step: P C F = %lld (video, channel, frame) planes do not fit one launch",
@@ -110,13 +123,22 @@ static int launch_window(const WindowStepParams& a, hipStream_t stream) {
     for (int i = 0; i < a.L; ++i) t.profile[i] = a.profile[i];
     const WindowShape s{a.P, a.C, a.F, a.W, a.L, (long)a.hw};
     const StepCoef c{a.guidance, a.kx, a.ke, a.c0, a.ct, a.c4};
-    auto kern = vec ? window_step_kernel<FAM, CFG, HIST, 8> : window_step_kernel<FAM, CFG, HIST, 1>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, a.x, a.aux, t, s, c, a.in_scale);
+    if constexpr (TAB) {
+        auto kern = vec ? window_step_kernel<FAM, CFG, HIST, 8, const float*> : window_step_kernel<FAM, CFG, HIST, 1, const float*>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, a.x, a.aux, t, s, c, a.in_scale, a.table);
+    } else {
+        auto kern = vec ? window_step_kernel<FAM, CFG, HIST, 8> : window_step_kernel<FAM, CFG, HIST, 1>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, a.x, a.aux, t, s, c, a.in_scale);
+    }
     LAVIE_HIP(hipGetLastError());
     return 0;
 }
 
 int launch_window_step(const WindowStepParams& a, hipStream_t stream) {
+    if (a.table) {                  // guided by definition: the table holds the guidance scales
+        if (!a.multistep) return launch_window<0, true, false, true>(a, stream);
+        return a.c4 != 0.f ? launch_window<1, true, true, true>(a, stream) : launch_window<1, true, false, true>(a, stream);
+    }
     if (!a.multistep)
         return a.cfg ? launch_window<0, true, false>(a, stream) : launch_window<0, false, false>(a, stream);
     if (a.cfg) return a.c4 != 0.f ? launch_window<1, true, true>(a, stream) : launch_window<1, true, false>(a, stream);

@@ -726,6 +726,124 @@ def multistep_step_known(eps, x, x0_prev, model_in, coeffs, next_input_scale, kn
                                                       ctypes.byref(r)), "lavie_multistep_step_known")
 
 
+def guidance_partials_floats(latents: int, per: int) -> int:
+    """fp32 elements of the workspace `guidance_table` needs for `latents` latents (windows x P) of `per` elements each."""
+    n = _lib.load().lavie_guidance_partials_floats(int(latents), int(per))
+    if n < 0:
+        raise ValueError(f"guidance_partials_floats: latents={latents} per={per} out of range (latents >= 1, per >= 2)")
+    return n
+
+
+def guidance_table(eps2, latents, guidance, rescale, workspace=None, out=None, moments_out=None):
+    """The per-latent (guidance scale, rescale factor) table the `*_scaled` steps read (lavie_guidance_table, csrc/sampler_guidance.hip).
+    eps2: the fp16 model output [2 P, ...] = [negative | prompt] of P = `latents` latents, or a list of W of them (one per frame window,
+    each with statistics of its own).  guidance: one number for every latent, or P of them: a sequence, or an fp32 device tensor [P]
+    (a sequence is copied to the device on every call; a loop passes the tensor).  rescale = phi in [0, 1]: f_p = phi std(ec) / std(e)
+    + (1 - phi) with e = the guided prediction; 0 writes f_p = 1 without reading eps2.  workspace: fp32 device tensor of at least
+    guidance_partials_floats(W P, per) elements (allocated when None and rescale != 0).  out: fp32 [P, 2], or [W, P, 2] for a list;
+    moments_out: fp64 of out's shape with 4 in place of 2, receives the double sums of ec, ec^2, e, e^2.  Returns the table.
+    No host synchronisation; with workspace and out given and guidance no host sequence, no allocation either."""
+    windows = isinstance(eps2, (list, tuple))
+    eps = list(eps2) if windows else [eps2]
+    _chk16(*eps)
+    p = int(latents)
+    if not eps or p < 1 or any(t is None or t.shape[0] != 2 * p or t.numel() != eps[0].numel() or t.device != eps[0].device for t in eps):
+        raise ValueError(f"guidance_table: every eps2 must be an fp16 device tensor [2 * {p}, ...] of one size")
+    dev, per = eps[0].device, eps[0].numel() // (2 * p)
+    phi = float(rescale)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"guidance_table: rescale={rescale} must be in [0, 1]")
+    g_dev, g = None, 1.0
+    if isinstance(guidance, torch.Tensor):
+        g_dev = guidance
+    elif isinstance(guidance, (list, tuple)):
+        g_dev = torch.tensor([float(v) for v in guidance], dtype=torch.float32, device=dev)
+    else:
+        g = float(guidance)
+    if g_dev is not None:
+        _chk32(g_dev)
+        if g_dev.numel() != p or g_dev.device != dev:
+            raise ValueError(f"guidance_table: got {g_dev.numel()} guidance scales for {p} latents")
+    shape = (len(eps), p) if windows else (p,)
+    table = _out(out, shape + (2,), torch.float32, dev, "guidance_table: out")
+    if moments_out is not None:
+        _out(moments_out, shape + (4,), torch.float64, dev, "guidance_table: moments_out")
+    need = guidance_partials_floats(len(eps) * p, per) if phi != 0.0 else 0
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.float32, device=dev)
+    if need:
+        _chk32(workspace)
+        if workspace.numel() < need or workspace.device != dev:
+            raise ValueError(f"guidance_table: workspace has {workspace.numel()} elements, {need} needed")
+    a = _lib.GuidanceTableArgsC()
+    a.struct_size = ctypes.sizeof(_lib.GuidanceTableArgsC)
+    a.W, a.P, a.per = len(eps), p, per
+    eps_c = (ctypes.c_void_p * len(eps))(*[t.data_ptr() for t in eps])
+    a.eps_host = eps_c
+    a.guidance_dev, a.guidance, a.rescale = (g_dev.data_ptr() if g_dev is not None else None), g, phi
+    a.partials, a.partials_floats = (workspace.data_ptr() if need else None), (workspace.numel() if need else 0)
+    a.table, a.moments = table.data_ptr(), (moments_out.data_ptr() if moments_out is not None else None)
+    _lib.check(_lib.load().lavie_guidance_table(ctypes.byref(a), _stream()), "lavie_guidance_table")
+    return table
+
+
+def _scaled_operands(who, eps2, x, aux, model_in2, table):
+    """Checks shared by the `*_scaled` steps; returns (n, per)."""
+    _chk16(eps2, model_in2)
+    _chk32(x, aux, table)
+    n = x.numel()
+    if eps2.numel() != 2 * n or model_in2.numel() != 2 * n or (aux is not None and aux.numel() != n):
+        raise ValueError(f"{who}: eps2 / model_in2 must have twice, noise / x0_prev as many elements as x")
+    if table is None or tuple(table.shape) != (x.shape[0], 2) or table.device != x.device:
+        raise ValueError(f"{who}: table must be an fp32 tensor [{x.shape[0]}, 2] on {x.device}")
+    return n, n // x.shape[0]
+
+
+def cfg_sampler_step_scaled(eps2, x, noise, model_in2, table, coeffs, next_input_scale: float = 1.0):
+    """cfg_ddpm_step with latent p's guidance scale and rescale factor read from table[p] (`guidance_table`): eps = f_p e.
+    x [P, ...], noise and model_in2 are the plain step's operands, updated in place."""
+    n, per = _scaled_operands("cfg_sampler_step_scaled", eps2, x, noise, model_in2, table)
+    k_x, k_e, c_x0, c_xt, sigma = coeffs
+    _lib.check(_lib.load().lavie_cfg_sampler_step_scaled(_p(eps2), _p(x), _p(noise), _p(model_in2), n, _p(table), per, float(k_x),
+                                                         float(k_e), float(c_x0), float(c_xt), float(sigma),
+                                                         float(next_input_scale), _stream()), "lavie_cfg_sampler_step_scaled")
+
+
+def cfg_multistep_step_scaled(eps2, x, x0_prev, model_in2, table, coeffs, next_input_scale: float = 1.0):
+    """cfg_multistep_step with (guidance, rescale factor) per latent from `table`; see cfg_sampler_step_scaled."""
+    if x0_prev is None:
+        raise ValueError("cfg_multistep_step_scaled: x0_prev is needed")
+    n, per = _scaled_operands("cfg_multistep_step_scaled", eps2, x, x0_prev, model_in2, table)
+    k_x, k_e, c_x0, c_xt, c_prev = coeffs
+    _lib.check(_lib.load().lavie_cfg_multistep_step_scaled(_p(eps2), _p(x), _p(x0_prev), _p(model_in2), n, _p(table), per, float(k_x),
+                                                           float(k_e), float(c_x0), float(c_xt), float(c_prev),
+                                                           float(next_input_scale), _stream()), "lavie_cfg_multistep_step_scaled")
+
+
+def cfg_sampler_step_known_scaled(eps2, x, noise, model_in2, table, coeffs, next_input_scale, known, mask, noise_known, level):
+    """cfg_sampler_step_known with (guidance, rescale factor) per latent from `table`; see cfg_sampler_step_scaled."""
+    n, _ = _scaled_operands("cfg_sampler_step_known_scaled", eps2, x, noise, model_in2, table)
+    k_x, k_e, c_x0, c_xt, sigma = coeffs
+    r = _known_region("cfg_sampler_step_known_scaled", x, known, mask, noise_known, level)
+    _lib.check(_lib.load().lavie_cfg_sampler_step_known_scaled(_p(eps2), _p(x), _p(noise), _p(model_in2), n, _p(table), float(k_x),
+                                                               float(k_e), float(c_x0), float(c_xt), float(sigma),
+                                                               float(next_input_scale), _stream(), ctypes.byref(r)),
+               "lavie_cfg_sampler_step_known_scaled")
+
+
+def cfg_multistep_step_known_scaled(eps2, x, x0_prev, model_in2, table, coeffs, next_input_scale, known, mask, noise_known, level):
+    """cfg_multistep_step_known with (guidance, rescale factor) per latent from `table`; see cfg_sampler_step_scaled."""
+    if x0_prev is None:
+        raise ValueError("cfg_multistep_step_known_scaled: x0_prev is needed")
+    n, _ = _scaled_operands("cfg_multistep_step_known_scaled", eps2, x, x0_prev, model_in2, table)
+    k_x, k_e, c_x0, c_xt, c_prev = coeffs
+    r = _known_region("cfg_multistep_step_known_scaled", x, known, mask, noise_known, level)
+    _lib.check(_lib.load().lavie_cfg_multistep_step_known_scaled(_p(eps2), _p(x), _p(x0_prev), _p(model_in2), n, _p(table), float(k_x),
+                                                                 float(k_e), float(c_x0), float(c_xt), float(c_prev),
+                                                                 float(next_input_scale), _stream(), ctypes.byref(r)),
+               "lavie_cfg_multistep_step_known_scaled")
+
+
 def window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, next_input_scale: float = 1.0, multistep: bool = False):
     """One denoising step of a clip sampled as overlapping frame windows (lavie_window_step, csrc/sampler_window.hip).
     x fp32 [P, C, F, ...] is the whole clip, updated in place; eps / model_in are lists with one fp16 tensor [nb, C, L, ...] per
@@ -734,6 +852,22 @@ def window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, next_i
     predictions are averaged per frame with the normalised weights, the plain step of the family runs on the whole clip (`coeffs`
     as cfg_ddpm_step / cfg_multistep_step take them; aux = the step's noise, or the x0_prev history when `multistep`) and every
     window that covers a frame receives fp16(x' next_input_scale) in both guidance halves."""
+    a, _keep = _window_args(eps, x, aux, model_in, starts, profile, guidance, coeffs, next_input_scale, multistep)
+    _lib.check(_lib.load().lavie_window_step(ctypes.byref(a), _stream()), "lavie_window_step")
+
+
+def window_step_scaled(eps, x, aux, model_in, starts, profile, table, coeffs, next_input_scale: float = 1.0, multistep: bool = False):
+    """window_step under guidance with (guidance, rescale factor) of window w and latent p read from table[w, p] (`guidance_table` on
+    the list of predictions): each window's guided prediction is multiplied by its own factor before the windows are averaged."""
+    a, _keep = _window_args(eps, x, aux, model_in, starts, profile, 1.0, coeffs, next_input_scale, multistep)
+    _chk32(table)
+    if table is None or tuple(table.shape) != (a.W, a.P, 2) or table.device != x.device:
+        raise ValueError(f"window_step_scaled: table must be an fp32 tensor [{a.W}, {a.P}, 2] on {x.device}")
+    _lib.check(_lib.load().lavie_window_step_scaled(ctypes.byref(a), _p(table), _stream()), "lavie_window_step_scaled")
+
+
+def _window_args(eps, x, aux, model_in, starts, profile, guidance, coeffs, next_input_scale, multistep):
+    """The checked lavie_window_step_args of window_step / window_step_scaled, and the host arrays it borrows."""
     _chk32(x, aux)
     if x.dim() < 4:
         raise ValueError(f"window_step: latents must be [P, C, F, ...], got {tuple(x.shape)}")
@@ -765,7 +899,7 @@ def window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, next_i
     a.guidance = float(guidance) if cfg else 1.0
     a.k_x, a.k_eps, a.c_x0, a.c_xt, a.c4 = float(k_x), float(k_e), float(c_x0), float(c_xt), float(c4)
     a.next_input_scale = float(next_input_scale)
-    _lib.check(_lib.load().lavie_window_step(ctypes.byref(a), _stream()), "lavie_window_step")
+    return a, (starts_c, profile_c, eps_c, min_c)
 
 
 def latents_to_model_input1(x, model_in, input_scale: float = 1.0):

@@ -123,6 +123,7 @@ class VideoGenPipeline:
         """Builds (pipeline, call_kwargs, cfg) from the keys base/pipelines/sample.py reads off its OmegaConf object:
         `sample_method` + `beta_start` / `beta_end` / `beta_schedule` choose and configure the scheduler (sample.py:44-63),
         `video_length`, `image_size`, `num_sampling_steps`, `guidance_scale` become the `__call__` keywords of sample.py:83-89,
+        an optional `guidance_rescale` (not a key of the reference) becomes the keyword of that name,
         `seed` is returned in cfg for torch.manual_seed (sample.py:22-23).  `use_fp16` and
         `enable_xformers_memory_efficient_attention` are read by nobody in sample.py and are ignored here as well.
         PyYAML's safe loader replaces omegaconf (absent from the image); interpolation / `${...}` references are not resolved."""
@@ -152,6 +153,8 @@ class VideoGenPipeline:
         call_kwargs = dict(video_length=int(cfg.get("video_length", 16)), height=int(size[0]), width=int(size[1]),
                            num_inference_steps=int(cfg.get("num_sampling_steps", 50)),
                            guidance_scale=float(cfg.get("guidance_scale", 7.5)))
+        if "guidance_rescale" in cfg:
+            call_kwargs["guidance_rescale"] = float(cfg["guidance_rescale"])
         pipe = VideoGenPipeline(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet, scheduler=scheduler)
         return pipe, call_kwargs, cfg
 
@@ -260,10 +263,17 @@ class VideoGenPipeline:
                 generator=None, callback: Optional[Callable] = None, callback_steps: int = 1, eta: float = 0.0,
                 known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
                 known_noise: Optional[torch.Tensor] = None, start_step: int = 0, window_length: Optional[int] = None,
-                window_stride: Optional[int] = None, window_weights: str = "triangle") -> torch.Tensor:
+                window_stride: Optional[int] = None, window_weights: str = "triangle",
+                guidance_rescale: float = 0.0) -> torch.Tensor:
         """latents fp32 [P, C, F, h, w] on the device, ctx fp16 [2P, n, d] = [negative | prompt] (guidance_scale > 1) or
         [P, n, d] = prompt only (guidance_scale <= 1: no classifier-free guidance, :626) -> denoised fp32.  One loop, one step
         launch per denoising step; step plan, step noise, engine session and step dispatch are lavie_amd.sampling's.
+
+        `guidance_scale` may be a sequence with one value > 1 per latent; `guidance_rescale` = phi in (0, 1] rescales every
+        latent's guided prediction to phi std(prompt prediction) / std(guided prediction) + (1 - phi) (diffusers'
+        rescale_noise_cfg; ignored without guidance).  Either one adds the two small launches of `ops.guidance_table` in front of
+        the step, which then reads scale and factor per latent from device memory (`sampling.GuidanceTable`); a windowed step
+        rescales each window's prediction from that window's own statistics before the windows are averaged.
 
         Around known latents (the known-region replacement of diffusers' legacy inpaint / img2img loop): `known` are clean
         latents shaped as `latents`.  After every step the step kernel itself overwrites the part `mask` pins (1 = keep `known`,
@@ -295,12 +305,8 @@ class VideoGenPipeline:
         plan = sampling.StepPlan(self.scheduler, num_inference_steps, eta)
         if known is not None and not 0 <= start_step < len(plan.timesteps):
             raise ValueError(f"`start_step`={start_step} must lie in 0..{len(plan.timesteps) - 1}")
-        guidance = guidance_scale if guidance_scale > 1.0 else None
         x = latents.to(torch.float32).contiguous().clone()
         p = x.shape[0]
-        nb = 2 * p if guidance else p                      # model batch (:666)
-        if ctx.shape[0] != nb:
-            raise ValueError(f"ctx has {ctx.shape[0]} rows, expected {nb} for {p} latents at guidance_scale={guidance_scale}")
         frames, starts = x.shape[2], [0]                   # frames per forward; without windows one forward sees the whole clip
         if windowed:
             from . import windows
@@ -308,6 +314,11 @@ class VideoGenPipeline:
             starts = windows.window_starts(x.shape[2], frames, int(window_stride) if window_stride is not None
                                            else max(1, frames - frames // 4))
             profile = windows.window_profile(frames, window_weights)
+        # None, the scalar itself, or the table route with its buffers, allocated here once for the loop
+        guidance = sampling.guidance_of(guidance_scale, guidance_rescale, x, frames, len(starts))
+        nb = 2 * p if guidance is not None else p          # model batch (:666)
+        if ctx.shape[0] != nb:
+            raise ValueError(f"ctx has {ctx.shape[0]} rows, expected {nb} for {p} latents at guidance_scale={guidance_scale}")
         if known is not None:
             if tuple(known.shape) != tuple(x.shape):
                 raise ValueError(f"`known` has shape {tuple(known.shape)}, the latents {tuple(x.shape)}")
@@ -328,7 +339,7 @@ class VideoGenPipeline:
                             plan.input_scale(start_step))
         else:
             for s, m in zip(starts, model_in):
-                (ops.latents_to_model_input if guidance else ops.latents_to_model_input1)(
+                (ops.latents_to_model_input if guidance is not None else ops.latents_to_model_input1)(
                     x[:, :, s:s + frames].contiguous(), m, plan.input_scale(0))
         t_dev = plan.t_dev(dev)
         # with guidance the two halves of every model input are the same latents (one fp16 value written into both by this loop's
@@ -336,15 +347,15 @@ class VideoGenPipeline:
         # cross-attention once
         region = None
         with sampling.engine_session(self.unet, nb, frames, x.shape[3], x.shape[4], ctx,
-                                     model_in if guidance and self.cfg_shared_prefix else None) as ctx:
+                                     model_in if guidance is not None and self.cfg_shared_prefix else None) as ctx:
             forwards = sampling.WindowForwards(lambda w, i: self.unet(model_in[w], t_dev[i], encoder_hidden_states=ctx).sample)
             for i in range(start_step, len(plan.timesteps)):
                 eps = forwards(len(model_in), i)                                                      # line 670
                 coeffs = plan.coeffs(i, first=start_step > 0 and i == start_step)
                 aux = x0_prev if plan.multistep else noise.draw() if plan.adds_noise(coeffs) else None
                 if windowed:
-                    ops.window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, plan.input_scale(i + 1),
-                                    multistep=plan.multistep)
+                    sampling.window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, plan.input_scale(i + 1),
+                                         plan.multistep)
                 else:
                     if mask is not None:                   # without a mask nothing is pinned: the plain step kernels
                         region = (known, mask, known_noise, plan.noise_level(i + 1))
@@ -417,7 +428,10 @@ class VideoGenPipeline:
                  cross_attention_kwargs=None, image_embeds: Optional[torch.Tensor] = None,
                  known_latents: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None,
                  video: Optional[torch.Tensor] = None, strength: float = 1.0, window_length: Optional[int] = None,
-                 window_stride: Optional[int] = None, window_weights: str = "triangle"):
+                 window_stride: Optional[int] = None, window_weights: str = "triangle", guidance_rescale: float = 0.0):
+        """`guidance_scale`: one number, or a sequence with one value > 1 per prompt (repeated per `num_images_per_prompt`; a
+        sequence always means guidance is on).  `guidance_rescale` in [0, 1]: diffusers' rescale_noise_cfg inside the fused step;
+        ignored with a scalar `guidance_scale` <= 1, as in diffusers.  See `denoise`."""
         if window_length is not None and (known_latents is not None or known_mask is not None or video is not None or strength != 1.0):
             raise ValueError("frame windows (`window_length`) cannot be combined with `known_latents` / `known_mask` / `video` / "
                              "`strength`")
@@ -431,7 +445,10 @@ class VideoGenPipeline:
         else:
             batch_size = prompt_embeds.shape[0]
         device = self.device
-        do_cfg = guidance_scale > 1.0
+        do_cfg, scales, guidance_rescale = sampling.check_guidance(guidance_scale, guidance_rescale, batch_size,
+                                                                   num_images_per_prompt or 1)
+        if scales is not None:
+            guidance_scale = scales                # one value per latent
         # image conditioning only with a mapper attached; without one the image is ignored, as the upstream pipeline does
         image_features = self._image_features(image_tensor, image_embeds, device) if self.mapper is not None else None
         ctx = self._encode_prompt(prompt, device, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds,
@@ -447,16 +464,17 @@ class VideoGenPipeline:
                           start_step=self.strength_start(num_inference_steps, strength))
         elif window_length is not None:    # clips longer than the window: overlapping frame windows
             around = dict(window_length=window_length, window_stride=window_stride, window_weights=window_weights)
+        rescale = dict(guidance_rescale=guidance_rescale) if guidance_rescale else {}      # absent = today's call
         lora_scale = (cross_attention_kwargs or {}).get("scale")
         if lora_scale is None:
             latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta,
-                                   **around)
+                                   **around, **rescale)
         else:                              # diffusers' LoRA strength for this call only, restored also on an exception
             prev = self.unet.lora_scale
             self.unet.set_lora_scale(lora_scale)
             try:
                 latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps,
-                                       eta, **around)
+                                       eta, **around, **rescale)
             finally:
                 self.unet.set_lora_scale(prev)
         if output_type == "latent":

@@ -1,10 +1,12 @@
 """What every denoising loop of this package shares, each piece once: the step plan (timesteps and per-step scalars of a
 scheduler), the step's noise (four generator kinds, host draws staged through pinned memory), the engine session (prepare,
-cached context, shared CFG input and their non-masking clean-up), the choice among the eight fused step ops, and the forwards
-of a windowed step.  The loops (`VideoGenPipeline.denoise`, `VideoUpscalePipeline.denoise`, `SpacedDiffusion._ddim_loop_hip`)
-keep what is theirs: which tensors reach the UNet, which step family runs, and the callback."""
+cached context, shared CFG input and their non-masking clean-up), the guidance arguments and the per-latent guidance table, the
+choice among the fused step ops, and the forwards of a windowed step.  The loops (`VideoGenPipeline.denoise`,
+`VideoUpscalePipeline.denoise`, `SpacedDiffusion._ddim_loop_hip`) keep what is theirs: which tensors reach the UNet, which step
+family runs, and the callback."""
 import contextlib
 import inspect
+import math
 import os
 import sys
 
@@ -160,10 +162,69 @@ def engine_session(unet, batch: int, frames: int, height: int, width: int, ctx: 
             raise cleanup_error
 
 
+def check_guidance(guidance_scale, guidance_rescale, count: int, repeat: int = 1):
+    """The guidance arguments of a pipeline call -> (guided, scales, rescale).  `guidance_scale`: one number (guidance is on when
+    it is > 1), or a sequence with one value for each of the `count` prompts, every one > 1 (a sequence always means guidance is
+    on), as a list, a tuple or a tensor of one dimension or more; `scales` is then the list with every value repeated `repeat`
+    times (latents are prompt-major), else None.
+    `guidance_rescale` = phi in [0, 1] (Lin et al., diffusers' rescale_noise_cfg); without guidance it is ignored, as in
+    diffusers, and comes back as 0."""
+    phi = float(guidance_rescale)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"`guidance_rescale` must lie in [0, 1] but is {guidance_rescale}")
+    if isinstance(guidance_scale, torch.Tensor) and guidance_scale.dim() > 0:      # a 0-dim tensor is one number, as it always was
+        guidance_scale = guidance_scale.flatten().tolist()
+    if isinstance(guidance_scale, (list, tuple)):
+        scales = [float(v) for v in guidance_scale]
+        if len(scales) != count:
+            raise ValueError(f"`guidance_scale` has {len(scales)} values for {count} prompts")
+        if not all(v > 1.0 for v in scales):
+            raise ValueError(f"every value of a `guidance_scale` sequence must be > 1, got {scales}")
+        return True, [v for v in scales for _ in range(int(repeat))], phi
+    guided = guidance_scale > 1.0
+    return guided, None, phi if guided else 0.0
+
+
+class GuidanceTable:
+    """The table route of a guided loop: guidance scales per latent (`scales`: a list, or one number) and / or guidance rescale
+    (`rescale` > 0).  Holds what `ops.guidance_table` needs, allocated once per loop beside the noise buffers: the scales on the
+    device, the partial-sum workspace and the table itself, [P, 2] or, for `windows` > 1 forwards per step, [W, P, 2] with `per`
+    the elements of one latent of one forward.  Calling it with the step's predictions enqueues the table's two launches."""
+
+    def __init__(self, scales, rescale: float, latents: int, per: int, device, windows: int = 1):
+        self.latents, self.rescale, self.windowed = int(latents), float(rescale), windows > 1
+        self.scales = torch.tensor(scales, dtype=torch.float32, device=device) if isinstance(scales, (list, tuple)) else float(scales)
+        self.table = torch.empty(((windows,) if self.windowed else ()) + (self.latents, 2), dtype=torch.float32, device=device)
+        self.workspace = torch.empty(ops.guidance_partials_floats(windows * self.latents, per), dtype=torch.float32,
+                                     device=device) if self.rescale != 0.0 else None
+
+    def __call__(self, eps: list) -> torch.Tensor:
+        return ops.guidance_table(eps if self.windowed else eps[0], self.latents, self.scales, self.rescale, self.workspace,
+                                  self.table)
+
+
+def guidance_of(guidance_scale, guidance_rescale, x: torch.Tensor, frames: int, windows: int = 1):
+    """What a loop over latents x [P, C, F, h, w] hands to `step` / `window_step` as guidance: None (no guidance), the scalar
+    `guidance_scale` itself (today's launches), or a GuidanceTable when `guidance_rescale` > 0 or `guidance_scale` is a sequence
+    with one value per latent.  `frames`: frames of one forward."""
+    guided, scales, phi = check_guidance(guidance_scale, guidance_rescale, x.shape[0])
+    if not guided:
+        return None
+    if scales is None and phi == 0.0:
+        return guidance_scale
+    per = x.shape[1] * frames * math.prod(x.shape[3:])
+    return GuidanceTable(scales if scales is not None else guidance_scale, phi, x.shape[0], per, x.device, windows)
+
+
 def step(eps, x, aux, model_in, guidance_scale, coeffs, next_scale, multistep: bool, region=None):
     """One fused scheduler step through the `ops` wrapper of its family.  `aux`: the step's noise or None (five-coefficient
-    family), the x0 history (multistep).  `guidance_scale` None: no classifier-free guidance.  `region`: None, or
-    (known, mask, known_noise, level) of a run around known latents.  The wrappers are looked up on `ops` at call time."""
+    family), the x0 history (multistep).  `guidance_scale` None: no classifier-free guidance; a GuidanceTable: the table is
+    computed from `eps` and the `_scaled` wrapper of the family reads it.  `region`: None, or (known, mask, known_noise, level) of
+    a run around known latents.  The wrappers are looked up on `ops` at call time."""
+    if isinstance(guidance_scale, GuidanceTable):
+        name = ("cfg_multistep_step" if multistep else "cfg_sampler_step") + ("_known" if region is not None else "") + "_scaled"
+        getattr(ops, name)(eps, x, aux, model_in, guidance_scale([eps]), coeffs, next_scale, *(region or ()))
+        return
     guided = guidance_scale is not None
     if multistep:
         name = "cfg_multistep_step" if guided else "multistep_step"
@@ -175,6 +236,15 @@ def step(eps, x, aux, model_in, guidance_scale, coeffs, next_scale, multistep: b
         name += "_known"
     args = (eps, x, aux, model_in) + ((guidance_scale,) if guided else ()) + (coeffs, next_scale) + tuple(region or ())
     getattr(ops, name)(*args)
+
+
+def window_step(eps, x, aux, model_in, starts, profile, guidance_scale, coeffs, next_scale, multistep: bool):
+    """One fused step over frame windows: `ops.window_step`, or with a GuidanceTable one `ops.guidance_table` call over all
+    windows' predictions followed by `ops.window_step_scaled`."""
+    if isinstance(guidance_scale, GuidanceTable):
+        ops.window_step_scaled(eps, x, aux, model_in, starts, profile, guidance_scale(eps), coeffs, next_scale, multistep=multistep)
+    else:
+        ops.window_step(eps, x, aux, model_in, starts, profile, guidance_scale, coeffs, next_scale, multistep=multistep)
 
 
 class WindowForwards:

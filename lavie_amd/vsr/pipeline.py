@@ -69,7 +69,8 @@ class VideoUpscalePipeline:
     def denoise(self, latents: torch.Tensor, image: torch.Tensor, ctx: torch.Tensor, noise_level: int,
                 num_inference_steps: int, guidance_scale: float, eta: float = 0.0, generator=None,
                 callback: Optional[Callable] = None, callback_steps: int = 1, window_length: Optional[int] = None,
-                window_stride: Optional[int] = None, window_weights: str = "triangle") -> torch.Tensor:
+                window_stride: Optional[int] = None, window_weights: str = "triangle",
+                guidance_rescale: float = 0.0) -> torch.Tensor:
         """latents fp32 [P, 4, F, h, w]; image = the NOISED low-res frames [P, 3, F, h, w]; ctx fp16 [2P, n, d] =
         [negative | prompt] -> denoised latents fp32.  Step plan, step noise, engine session and step dispatch are
         lavie_amd.sampling's.
@@ -79,9 +80,10 @@ class VideoUpscalePipeline:
         slice of the low-res frames (sliced once, before the loop), then ONE launch (ops.window_step) averages the windows' noise
         predictions per frame with the normalised `window_weights` profile, advances the whole clip by one scheduler step and
         writes every window's next fp16 model input.  `window_stride` defaults to three quarters of the window.  Unlike
-        independent chunks, neighbouring windows share their overlap frames at every step, so there is no seam between them."""
-        if guidance_scale <= 1.0:
-            raise NotImplementedError("guidance_scale <= 1 (no classifier-free guidance) is outside the fused MI355X loop")
+        independent chunks, neighbouring windows share their overlap frames at every step, so there is no seam between them.
+
+        `guidance_scale` may be a sequence with one value > 1 per latent, `guidance_rescale` in (0, 1] is diffusers'
+        rescale_noise_cfg inside the fused step: see VideoGenPipeline.denoise."""
         windowed = False
         if window_length is not None:
             if int(window_length) < 1:
@@ -99,6 +101,10 @@ class VideoUpscalePipeline:
             starts = windows.window_starts(x.shape[2], frames, int(window_stride) if window_stride is not None
                                            else max(1, frames - frames // 4))
             profile = windows.window_profile(frames, window_weights)
+        # the scalar itself, or the table route with its buffers, allocated here once for the loop
+        guidance = sampling.guidance_of(guidance_scale, guidance_rescale, x, frames, len(starts))
+        if guidance is None:
+            raise NotImplementedError("guidance_scale <= 1 (no classifier-free guidance) is outside the fused MI355X loop")
         model_in = [torch.empty((2 * p, x.shape[1], frames) + tuple(x.shape[3:]), dtype=torch.float16, device=dev) for _ in starts]
         low = []
         for s, m in zip(starts, model_in):
@@ -117,10 +123,10 @@ class VideoUpscalePipeline:
                 coeffs = plan.coeffs(i)
                 aux = x0_prev if plan.multistep else noise.draw() if plan.adds_noise(coeffs) else None
                 if windowed:
-                    ops.window_step(eps, x, aux, model_in, starts, profile, guidance_scale, coeffs, plan.input_scale(i + 1),
-                                    multistep=plan.multistep)
+                    sampling.window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, plan.input_scale(i + 1),
+                                         plan.multistep)
                 else:                                                                                                 # :721-726
-                    sampling.step(eps[0], x, aux, model_in[0], guidance_scale, coeffs, plan.input_scale(i + 1), plan.multistep)
+                    sampling.step(eps[0], x, aux, model_in[0], guidance, coeffs, plan.input_scale(i + 1), plan.multistep)
                 noise.done()
                 if callback is not None and i % callback_steps == 0:
                     callback(i, t, x)
@@ -133,7 +139,9 @@ class VideoUpscalePipeline:
                  latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
                  negative_prompt_embeds: Optional[torch.Tensor] = None, output_type: Optional[str] = "latent",
                  return_dict: bool = True, callback=None, callback_steps: int = 1, window_length: Optional[int] = None,
-                 window_stride: Optional[int] = None, window_weights: str = "triangle"):
+                 window_stride: Optional[int] = None, window_weights: str = "triangle", guidance_rescale: float = 0.0):
+        """`guidance_scale`: one number > 1, or a sequence with one value > 1 per prompt (repeated per `num_images_per_prompt`);
+        `guidance_rescale` in [0, 1]: diffusers' rescale_noise_cfg inside the fused step.  See `denoise`."""
         self.check_inputs(image, noise_level, callback_steps, prompt, prompt_embeds, negative_prompt_embeds)
         if prompt is not None:
             raise NotImplementedError("text encoding is not built: pass prompt_embeds / negative_prompt_embeds")
@@ -141,6 +149,10 @@ class VideoUpscalePipeline:
             raise ValueError("negative_prompt_embeds is required for classifier-free guidance")
         device = self.device
         batch = prompt_embeds.shape[0] * (num_images_per_prompt or 1)
+        _, scales, guidance_rescale = sampling.check_guidance(guidance_scale, guidance_rescale, prompt_embeds.shape[0],
+                                                              num_images_per_prompt or 1)
+        if scales is not None:
+            guidance_scale = scales                # one value per latent
         ctx = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0).to(device, torch.float16).contiguous()
         image = image.to(device=device, dtype=torch.float32)
         # 5. add noise to the low-res frames at `noise_level` (:629-633)
@@ -152,7 +164,8 @@ class VideoUpscalePipeline:
             raise ValueError(f"Incorrect configuration settings! The config of `pipeline.unet` expects "
                              f"{self.unet.config.in_channels} but received 4 + {image.shape[1]} channels")
         latents = self.denoise(latents, image, ctx, noise_level, num_inference_steps, guidance_scale, eta, generator, callback,
-                               callback_steps, window_length, window_stride, window_weights)
+                               callback_steps, window_length, window_stride, window_weights,
+                               **(dict(guidance_rescale=guidance_rescale) if guidance_rescale else {}))
         if output_type != "latent":
             if self.vae is None:
                 raise ValueError("no vae attached: use output_type='latent'")
