@@ -180,6 +180,22 @@ typedef struct lavie_lora_term {
 } lavie_lora_term;
 int lavie_lora_merge_multi_f16(const void* W0, const lavie_lora_term* terms, int n_terms, void* out, int N, int K, void* stream);
 
+/* FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net"; diffusers' apply_freeu / fourier_filter) on the two operands of a decoder
+ * concat (additive in ABI 8).  h [(n y x), C_h] and skip [(n y x), C2] are fp16 channels-last row matrices of NI images of H x W.
+ *   h_out    = h with channels [0, C_h / 2) scaled: fp16_rne(float(b) * h); the other channels keep their bits
+ *   skip_out = skip with the 2 x 2 block around the centre of every (image, channel)'s shifted 2-D spectrum scaled by s, i.e. the mode
+ *              set ky in {0, -1 mod H} x kx in {0, -1 mod W} (1 mode at 1 x 1, 2 at 1 x W or H x 1, else 4), without an FFT:
+ *              out = in + (s - 1) / (H W) sum_k [cos phi_k A_k + sin phi_k B_k], A_k / B_k the fp32 cosine / sine sums of the image;
+ *              formed in fp32, rounded once to fp16
+ * s == 1 / b == 1: that tensor keeps its bits.  h_out may be h and skip_out may be skip (in place: the upper half of h is not touched).
+ * Sums run slab by slab in a fixed order without atomics: two runs give the same bits, and an image's result does not depend on how
+ * many images the call holds.  workspace: lavie_freeu_workspace_bytes(C2, NI, H, W) bytes (may be NULL when s == 1).  At most two
+ * launches, no allocation, no synchronisation (capturable).  Any H, W >= 1; C_h %% 16 == 0, C2 %% 8 == 0, b and s finite and > 0, every
+ * pointer 16-byte aligned: anything else is refused before anything is written. */
+long long lavie_freeu_workspace_bytes(int C2, int NI, int H, int W);      /* 0 for a shape lavie_freeu_f16 refuses */
+int lavie_freeu_f16(const void* h, int C_h, const void* skip, int C2, int NI, int H, int W, float b, float s, void* h_out,
+                    void* skip_out, void* workspace, void* stream);
+
 /* Fused feed-forward sub-block (ABI 5): y = x + W2 (h * gelu(g)) + b2 with (h, g) = W1 LayerNorm(x) + b1 — the
  * `hidden_states = self.ff(self.norm3(hidden_states)) + hidden_states` line of BasicTransformerBlock
  * (/root/reference/base/models/attention.py:558; FeedForward / GEGLU spec /root/reference/vsr/models/diffusers_attention.py:
@@ -644,6 +660,12 @@ int lavie_unet_cache_context(lavie_unet_t h, const void* ctx, int B, int ctx_len
 /* A/B switch (default on): fold every LayerNorm of the transformer blocks into the epilogues of the GEMM that
  * produces its input (row statistics) and the GEMM that consumes its output (gamma folded into the weights). */
 int lavie_unet_set_ln_fold(lavie_unet_t h, int on);
+/* FreeU inside the forward (diffusers' enable_freeu(s1, s2, b1, b2), same argument order; additive in ABI 8): in up block i in {0, 1},
+ * in front of EVERY resnet of the block, the running activation and the popped skip go through lavie_freeu_f16 with (b_{i+1}, s_{i+1}),
+ * in place; the resnet (norm1 and the shortcut included) sees the modified pair.  A stage with b == 1 and s == 1 launches nothing, so
+ * (1, 1, 1, 1), the default, is the plain forward, bit for bit.  Every value must be finite and > 0: otherwise an error and no change.
+ * Holds for every forward that follows, eager or captured (a change re-captures); it needs no new workspace after lavie_unet_prepare. */
+int lavie_unet_set_freeu(lavie_unet_t h, float s1, float s2, float b1, float b2);
 /* Classifier-free guidance (pipeline_videogen.py:666: `torch.cat([latents] * 2)`) runs the UNet on the SAME latents twice with
  * different text.  on = 1: the caller vouches that sample[b] == sample[b + B/2] for every b < B/2 (B even) in the forwards that
  * follow; the layers in front of the first text cross-attention (conv_in, down_blocks.0.resnets.0, and the GroupNorm / proj_in /

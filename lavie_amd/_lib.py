@@ -103,6 +103,9 @@ SIGNATURES = {
     "lavie_f16_to_f32": (c_int, [c_void_p, c_void_p, c_float_p, c_ll, c_void_p]),
     "lavie_lora_merge_f16": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "lavie_lora_merge_multi_f16": (c_int, [c_void_p, C.POINTER(LoraTermC), c_int, c_void_p, c_int, c_int, c_void_p]),
+    "lavie_freeu_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
+    "lavie_freeu_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
     "lavie_geglu_mlp_image_bytes": (c_ll, [c_int]),
     "lavie_geglu_mlp_bias_floats": (c_ll, [c_int]),
     "lavie_pack_geglu_mlp_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float_p, c_void_p]),
@@ -208,6 +211,7 @@ SIGNATURES = {
     "lavie_unet_lora_clear_slot": (c_int, [c_void_p, c_int, c_char_p, c_void_p]),
     "lavie_unet_lora_set_slot_weight": (c_int, [c_void_p, c_int, c_float]),
     "lavie_unet_set_cfg_shared_input": (c_int, [c_void_p, c_int]),
+    "lavie_unet_set_freeu": (c_int, [c_void_p, c_float, c_float, c_float, c_float]),
     "lavie_unet_weight_bytes": (c_ll, [c_void_p]),
     "lavie_unet_workspace_bytes": (c_ll, [c_void_p]),
     "lavie_unet_forward": (c_int, [c_void_p, c_void_p, c_float_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

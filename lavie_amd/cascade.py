@@ -45,7 +45,7 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
                           interp_frames: int = 61, interp_cfg_scale: float = 4.0, vsr_steps: int = 50,
                           vsr_guidance_scale: float = 7.5, noise_level: int = 150, generator=None, decode_final: bool = True,
                           base_scheduler=None, vsr_scheduler=None, vsr_overlap: int = 0, base_guidance_rescale: float = 0.0,
-                          vsr_guidance_rescale: float = 0.0):
+                          vsr_guidance_rescale: float = 0.0, base_freeu: Optional[dict] = None, vsr_freeu: Optional[dict] = None):
     """Returns (base_latents, interp_latents, vsr_latents, frames or None).  Text embeddings are passed per stage (the base
     and interpolation stages use SD-1.4's CLIP, 768 wide; the VSR stage the x4-upscaler's, 1024 wide).
     `base_scheduler` / `vsr_scheduler` replace the two diffusers-style stages' schedulers for this call (for instance a
@@ -54,13 +54,19 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
     `vsr_overlap` > 0: the VSR stage samples the 61 frames as ONE run over 8-frame windows sharing that many frames with their
     neighbours (`upscale_in_chunks(overlap=)`) instead of independent chunks; 0 = the reference's chunks.
     `base_guidance_rescale` / `vsr_guidance_rescale`: the `guidance_rescale` of the two diffusers-style stages (0 = off).  The
-    interpolation stage's own guidance loop (`forward_with_cfg`) has no such switch."""
+    interpolation stage's own guidance loop (`forward_with_cfg`) has no such switch.
+    `base_freeu` / `vsr_freeu`: dict(s1=, s2=, b1=, b2=) for `enable_freeu` on that stage's UNet during this call; the UNet gets the
+    setting it had back afterwards.  None = the UNet's own setting."""
+    freeu_was = [(pipe.unet, pipe.unet.freeu) for pipe, fu in ((base_pipe, base_freeu), (vsr_pipe, vsr_freeu)) if fu is not None]
     swapped = [(pipe, pipe.scheduler) for pipe, sch in ((base_pipe, base_scheduler), (vsr_pipe, vsr_scheduler)) if sch is not None]
     if base_scheduler is not None:
         base_pipe.scheduler = base_scheduler
     if vsr_scheduler is not None:
         vsr_pipe.scheduler = vsr_scheduler
     try:
+        for pipe, fu in ((base_pipe, base_freeu), (vsr_pipe, vsr_freeu)):
+            if fu is not None:
+                pipe.unet.enable_freeu(fu["s1"], fu["s2"], fu["b1"], fu["b2"])
         return _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, prompt_embeds, negative_prompt_embeds,
                         vsr_prompt_embeds, vsr_negative_prompt_embeds, interp_prompt_embeds, interp_negative_prompt_embeds, height,
                         width, base_steps, guidance_scale, interp_frames, interp_cfg_scale, vsr_steps, vsr_guidance_scale,
@@ -68,6 +74,8 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
     finally:
         for pipe, own in swapped:
             pipe.scheduler = own
+        for unet, was in freeu_was:
+            unet.enable_freeu(*was)
 
 
 def _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, prompt_embeds, negative_prompt_embeds,

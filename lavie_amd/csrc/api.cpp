@@ -127,6 +127,15 @@ int lavie_lora_merge_multi_f16(const void* W0, const lavie_lora_term* terms, int
     return launch_lora_merge_multi(H(W0), t, n_terms, H(out), N, K, S(stream));
 }
 
+long long lavie_freeu_workspace_bytes(int C2, int NI, int H, int W) {
+    if (C2 < 8 || C2 % 8 != 0 || NI < 1 || NI > 65535 || H < 1 || W < 1 || (long long)H * W > (1 << 24)) return 0;
+    return (long long)(freeu_workspace_floats(C2, NI, H, W) * sizeof(float));
+}
+int lavie_freeu_f16(const void* h, int C_h, const void* skip, int C2, int NI, int Hh, int W, float b, float s, void* h_out, void* skip_out,
+                    void* workspace, void* stream) {
+    return launch_freeu(H(h), C_h, H(skip), C2, NI, Hh, W, b, s, H(h_out), H(skip_out), (float*)workspace, S(stream));
+}
+
 long long lavie_geglu_mlp_image_bytes(int C) { return geglu_mlp_supported(C) ? (long long)geglu_mlp_image_bytes(C) : 0; }
 long long lavie_geglu_mlp_bias_floats(int C) { return geglu_mlp_supported(C) ? (long long)geglu_mlp_bias_floats(C) : 0; }
 int lavie_pack_geglu_mlp_f16(const void* w1, const void* b1_f16, const void* w2, int C, void* img, float* b1img, void* stream) {
@@ -972,6 +981,10 @@ int lavie_unet_set_cfg_shared_input(lavie_unet_t h, int on) {
     LAVIE_CHECK(h, "set_cfg_shared_input: null handle");
     h->net.set_cfg_shared_input(on != 0);
     return 0;
+}
+int lavie_unet_set_freeu(lavie_unet_t h, float s1, float s2, float b1, float b2) {
+    LAVIE_CHECK(h, "set_freeu: null handle");
+    return h->net.set_freeu(s1, s2, b1, b2);
 }
 int lavie_unet_set_ln_fold(lavie_unet_t h, int on) {
     LAVIE_CHECK(h, "set_ln_fold: null handle");

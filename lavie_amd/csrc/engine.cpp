@@ -1217,8 +1217,22 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
     for (int i = 0; i < L; ++i) {
         const int l = L - 1 - i;
         for (int j = 0; j < cfg.layers_per_block + 1; ++j) {
-            const Act sk = skips.back();
+            Act sk = skips.back();
             skips.pop_back();
+            if (i < 2) {
+                // FreeU (diffusers apply_freeu), in place: both tensors have this resnet as their one consumer left.  Its mode-sum
+                // partials are taken from the workspace whether FreeU is on or off (so prepare()'s plan covers a setting made after
+                // it) and given back at once: the resnet's buffers lie over them, behind the launches in stream order.  A tensor
+                // FreeU changes no longer has its producer's GroupNorm statistics: norm1 runs the statistics pass, as behind conv_in
+                const size_t fmark = c.ws->mark();
+                WS(freeu_ws, float, freeu_workspace_floats(sk.C, NI, Hs[l], Ws[l]));
+                if (freeu_b_[i] != 1.f || freeu_s_[i] != 1.f) {
+                    LAUNCH(launch_freeu(x.p, x.C, sk.p, sk.C, NI, Hs[l], Ws[l], freeu_b_[i], freeu_s_[i], x.p, sk.p, freeu_ws, c.s));
+                    if (freeu_b_[i] != 1.f) x.cs = GnColStat();
+                    if (freeu_s_[i] != 1.f) sk.cs = GnColStat();
+                }
+                c.ws->release(fmark);
+            }
             RUN(resnet(c, l, &sk));
             if (cfg.attn_levels[l]) RUN(transformer(l, false));
         }
@@ -1271,6 +1285,16 @@ int UNet::prepare(int B, int F, int H, int W, int ctx_len) {
         ++graph_gen_;
         RUN(ws_.init_fixed(need));
     }
+    return 0;
+}
+
+int UNet::set_freeu(float s1, float s2, float b1, float b2) {
+    const float v[4] = {s1, s2, b1, b2};
+    for (float f : v)
+        LAVIE_CHECK(__builtin_isfinite(f) && f > 0.f, "set_freeu: s1=%g s2=%g b1=%g b2=%g must all be finite and > 0", (double)s1, (double)s2,
+                    (double)b1, (double)b2);
+    freeu_s_[0] = s1; freeu_s_[1] = s2; freeu_b_[0] = b1; freeu_b_[1] = b2;
+    ++graph_gen_;                                   // a captured forward holds the old setting's launches
     return 0;
 }
 

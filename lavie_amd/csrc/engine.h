@@ -159,6 +159,9 @@ public:
     long long workspace_bytes() const { return (long long)ws_.total_bytes(); }
     void set_ln_fold(bool on) { ln_fold_ = on; ++graph_gen_; }
     void set_cfg_shared_input(bool on) { cfg_shared_input_ = on; ++graph_gen_; }
+    // FreeU (freeu.hip) in front of every resnet of up blocks 0 and 1: stage i scales the first half of the running activation's
+    // channels by b[i] and the skip's lowest modes by s[i]; (1, 1) = the stage launches nothing.  Values must be finite and > 0.
+    int set_freeu(float s1, float s2, float b1, float b2);
     // Low-rank adapters on the attention projections (to_q / to_k / to_v / to_out.0 of attn1 / attn2 / attn_temp).  set / clear /
     // set_scale only record (the set copies the caller's tensors on `stream`); apply merges every target of the blocks touched since
     // the last apply and re-derives those blocks' images in place: device addresses never change, captured graphs stay valid.
@@ -234,6 +237,7 @@ private:
     // the first text cross-attention are computed for the first half and copied
     bool cfg_shared_input_ = false;
     bool ln_fold_ = true;                           // LayerNorm folded into the producer / consumer GEMM epilogues
+    float freeu_s_[2] = {1.f, 1.f}, freeu_b_[2] = {1.f, 1.f};      // set_freeu: read by run() in the up walk (decoder only)
 
     DeviceArena weights_, ws_;
     // packed model

@@ -5,6 +5,7 @@
 // `hostcheck trace FILE` instead writes the launch trace of the cases in run_traces() to FILE (tests/golden/make_golden_trace.py).
 // `hostcheck optrace IN OUT` replays the operator calls listed in IN (run_optrace()) and writes their launches to OUT;
 // `hostcheck kernels OUT` lists every registered kernel name (tests/opcases.py: gemm_reach()).
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -107,6 +108,30 @@ static void run_model(const lavie_unet_config& cfg, int B, int F, int H, int W, 
         free(ctx2);
     }
     REQUIRE(lavie_hostcheck_launches() > before + 50);
+    {   // FreeU: decoder-only launches in front of the resnets of up blocks 0 and 1, inside the workspace prepare() planned; a refused
+        // value leaves the setting in force; (1, 1, 1, 1) is the plain forward again
+        auto launches = [&]() {
+            const long b = lavie_hostcheck_launches();
+            REQUIRE((labels ? lavie_unet_forward_labels(h, x, t, ctx, lab.data(), y, B, F, H, W, 77, nullptr)
+                            : lavie_unet_forward(h, x, t, ctx, y, B, F, H, W, 77, nullptr)) == 0);
+            return lavie_hostcheck_launches() - b;
+        };
+        const long long ws_bytes = lavie_unet_workspace_bytes(h);
+        const long off = launches();
+        REQUIRE(lavie_unet_set_freeu(h, 0.9f, 0.2f, 1.5f, 1.6f) == 0);
+        const long on = launches();
+        REQUIRE(on > off);
+        REQUIRE(lavie_unet_set_freeu(h, 0.f, 0.2f, 1.5f, 1.6f) != 0 && lavie_unet_set_freeu(h, 0.9f, -1.f, 1.5f, 1.6f) != 0 &&
+                lavie_unet_set_freeu(h, 0.9f, 0.2f, NAN, 1.6f) != 0 && lavie_unet_set_freeu(h, 0.9f, 0.2f, 1.5f, INFINITY) != 0 &&
+                lavie_unet_set_freeu(nullptr, 1.f, 1.f, 1.f, 1.f) != 0);
+        REQUIRE(launches() == on);
+        REQUIRE(lavie_unet_set_freeu(h, 1.f, 1.f, 1.5f, 1.f) == 0);     // b1 alone: stage 0's apply launches, no sums, stage 1 nothing
+        const long b1_only = launches();
+        REQUIRE(b1_only > off && b1_only < on);
+        REQUIRE(lavie_unet_set_freeu(h, 1.f, 1.f, 1.f, 1.f) == 0);
+        REQUIRE(launches() == off);
+        REQUIRE(lavie_unet_workspace_bytes(h) == ws_bytes);
+    }
     if (check_switches) {   // a rejected switch value leaves the one in force: the launch count of a forward tells them apart
         auto launches = [&]() {
             const long b = lavie_hostcheck_launches();
@@ -390,7 +415,7 @@ static void run_traces(const char* path) {
 // its integer arguments under the names of include/lavie_hip.h, 0 / 1 for each optional operand (bias, bias2, R, x2, sc1, sc2) and
 // force_tile / force_splits (default 0); the end and glue kernels' entries (timestep_sinusoid ... f16_to_f32) and the pack / bind steps
 // of the row-resident blocks (pack_geglu_mlp, bind_cross_block[_long]: pack + bind) likewise, and the blocks themselves (geglu_mlp, temporal_block,
-// cross_block[_long], proj_qkv), temporal_attention, group_norm[_affine], conv_edge_in / conv_edge_out and attention on exactly sized buffers, under rowfuse_grid / temporal_budget (default 0).  Tensors are never read.  OUT: "== <line>", then the stub's launch lines of that call, or
+// cross_block[_long], proj_qkv), temporal_attention, group_norm[_affine], conv_edge_in / conv_edge_out, attention and freeu (b_milli / s_milli: the factors in thousandths) on exactly sized buffers, under rowfuse_grid / temporal_budget (default 0).  Tensors are never read.  OUT: "== <line>", then the stub's launch lines of that call, or
 // stats_cs=1 / stats_rs=1 on a GEMM-family line arm the statistics sink around the call (planned first, the sink sized exactly); behind the
 // launch lines comes "## stats ..." with the plan (written or not, rows, span, sets, blocks, slots); group_norm_stats takes descriptors
 // as cs1_C / cs1_rows / cs1_nsets / cs1_set_blocks / cs1_span (cs2_ likewise) and prints "## fold=<producer-count delta>"; rowstat_finalize.
@@ -622,6 +647,16 @@ static int run_optrace(const char* in_path, const char* out_path) {
                     rc = in ? lavie_conv_edge_in_f16(img.data(), dt, wp.data(), O("bias") ? b.data() : nullptr, O("tap_bias") ? tb.data() : nullptr,
                                                      rows.data(), N, Cin, Hh, Ww, Cout, nullptr)
                             : lavie_conv_edge_out_f16(rows.data(), wp.data(), O("bias") ? b.data() : nullptr, img.data(), dt, N, Cin, Hh, Ww, Cout, nullptr);
+                }
+            } else if (entry == "freeu") {                  // b / s in thousandths (the replay takes integers); in_place: h_out = h, skip_out = skip
+                const int Ch = I("C_h"), C2 = I("C2"), NI = I("NI"), Hh = I("H"), Ww = I("W"), bm = I("b_milli"), sm = I("s_milli"), inpl = O("in_place");
+                if (!missing) {
+                    const size_t px = (size_t)(NI > 0 ? NI : 0) * (Hh > 0 ? Hh : 0) * (Ww > 0 ? Ww : 0);
+                    const long long wb = lavie_freeu_workspace_bytes(C2, NI, Hh, Ww);
+                    std::vector<unsigned short> h(px * (Ch > 0 ? Ch : 0) + 8), sk(px * (C2 > 0 ? C2 : 0) + 8), ho(h.size()), so(sk.size());
+                    std::vector<float> ws((size_t)(wb > 0 ? wb / 4 : 1) + 4);
+                    rc = lavie_freeu_f16(h.data(), Ch, sk.data(), C2, NI, Hh, Ww, bm / 1000.f, sm / 1000.f, inpl ? h.data() : ho.data(),
+                                         inpl ? sk.data() : so.data(), ws.data(), nullptr);
                 }
             } else if (entry == "attention") {
                 const int ldq = I("ldq"), ldk = I("ldk"), ldv = I("ldv"), ldo = I("ldo"), NB = I("NB"), Lq = I("Lq"), Lk = I("Lk"), heads = I("heads"),

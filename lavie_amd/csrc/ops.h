@@ -264,6 +264,20 @@ struct LoraTerm {
 };
 int launch_lora_merge_multi(const half_t* W0, const LoraTerm* terms, int n_terms, half_t* out, int N, int K, hipStream_t stream);
 
+// ---- freeu.hip: FreeU on the two operands of a decoder concat (diffusers apply_freeu / fourier_filter): h_out = h with channels
+// [0, C_h / 2) scaled by b; skip_out = skip with the modes ky in {0, -1} x kx in {0, -1} of every image's 2-D spectrum scaled by s
+// (per image and channel: out = in + (s - 1) / (H W) sum_k [cos phi_k A_k + sin phi_k B_k] from seven fp32 mode sums).  h [(n y x), C_h],
+// skip [(n y x), C2] fp16, C_h % 16 == 0, C2 % 8 == 0, 16-byte aligned; h_out / skip_out may alias their inputs (in place: the upper half
+// of h is not touched).  s == 1 / b == 1: that tensor keeps its bits (copied when out of place), no sums run.  workspace:
+// freeu_workspace_floats() floats (unused when s == 1).  At most two launches: the sums (a workgroup walks slabs_per_run slabs of
+// kFreeuSlab pixels of 64 channels of one image; `runs` partials per image, folded in ascending order by the apply kernel) and the apply.
+constexpr int kFreeuSlab = 32, kFreeuMaxRuns = 8, kFreeuMinRunSlabs = 4, kFreeuSums = 7;
+struct FreeuGeom { int P, nslabs, slabs_per_run, runs; };
+FreeuGeom freeu_geom(int H, int W);                 // from the image size alone: an image's sums do not depend on the batch around it
+size_t freeu_workspace_floats(int C2, int NI, int H, int W);
+int launch_freeu(const half_t* h, int C_h, const half_t* skip, int C2, int NI, int H, int W, float b, float s, half_t* h_out,
+                 half_t* skip_out, float* workspace, hipStream_t stream);
+
 // host-only helper (no GPU): T5-style bucket of (query i, key j), attention.py:681-699
 void relpos_bucket_table(int F, int num_buckets, int max_distance, int* out);
 

@@ -1106,3 +1106,25 @@ def lora_merge_multi(w0: torch.Tensor, terms, out: Optional[torch.Tensor] = None
     lib = _lib.load()
     _lib.check(lib.lavie_lora_merge_multi_f16(_p(w0), arr, len(terms), _p(out), N, K, _stream()), "lavie_lora_merge_multi_f16")
     return out
+
+
+def freeu(h: torch.Tensor, skip: torch.Tensor, ni: int, height: int, width: int, b: float, s: float, out=None):
+    """FreeU on the two operands of a decoder concat (lavie_freeu_f16; diffusers' apply_freeu / fourier_filter).  h [(ni height width),
+    C_h], skip [(ni height width), C2], fp16 rows.  Returns (h_out, skip_out): h with its first C_h / 2 channels scaled by b, skip with
+    the four lowest modes of every (image, channel)'s 2-D spectrum scaled by s.  out = (h_out, skip_out), either None (a new tensor) or
+    the input itself (in place)."""
+    _chk16(h, skip)
+    rows = ni * height * width
+    if h.dim() != 2 or skip.dim() != 2 or h.shape[0] != rows or skip.shape[0] != rows:
+        raise ValueError(f"freeu: h {tuple(h.shape)} / skip {tuple(skip.shape)} are not [{ni} * {height} * {width}, C] row matrices")
+    h_out, skip_out = out if out is not None else (None, None)
+    _chk16(h_out, skip_out)
+    h_out = _out(h_out, h.shape, torch.float16, h.device, "freeu: h_out")
+    skip_out = _out(skip_out, skip.shape, torch.float16, skip.device, "freeu: skip_out")
+    lib = _lib.load()
+    c_h, c2 = h.shape[1], skip.shape[1]
+    ws_bytes = lib.lavie_freeu_workspace_bytes(c2, ni, height, width)
+    ws = torch.empty(max(int(ws_bytes) // 4, 4), dtype=torch.float32, device=h.device)
+    _lib.check(lib.lavie_freeu_f16(_p(h), c_h, _p(skip), c2, ni, height, width, float(b), float(s), _p(h_out), _p(skip_out), _p(ws),
+                                   _stream()), "lavie_freeu_f16")
+    return h_out, skip_out

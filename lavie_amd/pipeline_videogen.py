@@ -76,6 +76,13 @@ class VideoGenPipeline:
         """Removes every adapter."""
         self.unet.unload_lora()
 
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """diffusers' enable_freeu: forwarded to the UNet (UNet3DConditionModel.enable_freeu), where the setting lives."""
+        self.unet.enable_freeu(s1, s2, b1, b2)
+
+    def disable_freeu(self):
+        self.unet.disable_freeu()
+
     def load_mapper(self, path_or_sd, num_heads: int = 12):
         """The fork's saved image mapper (`mapper.pt`, fine_tuning.py:701) -> self.mapper on the pipeline's device, eval mode.
         Works with a LoRA adapter loaded as well: that pair is the fork's sampling configuration."""
@@ -124,6 +131,7 @@ class VideoGenPipeline:
         `sample_method` + `beta_start` / `beta_end` / `beta_schedule` choose and configure the scheduler (sample.py:44-63),
         `video_length`, `image_size`, `num_sampling_steps`, `guidance_scale` become the `__call__` keywords of sample.py:83-89,
         an optional `guidance_rescale` (not a key of the reference) becomes the keyword of that name,
+        an optional `freeu: {s1:, s2:, b1:, b2:}` (not a key of the reference either) is set on the UNet (enable_freeu),
         `seed` is returned in cfg for torch.manual_seed (sample.py:22-23).  `use_fp16` and
         `enable_xformers_memory_efficient_attention` are read by nobody in sample.py and are ignored here as well.
         PyYAML's safe loader replaces omegaconf (absent from the image); interpolation / `${...}` references are not resolved."""
@@ -156,6 +164,9 @@ class VideoGenPipeline:
         if "guidance_rescale" in cfg:
             call_kwargs["guidance_rescale"] = float(cfg["guidance_rescale"])
         pipe = VideoGenPipeline(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet, scheduler=scheduler)
+        if "freeu" in cfg:                      # {s1:, s2:, b1:, b2:}, all four: the setting goes onto the model
+            fu = cfg["freeu"]
+            pipe.enable_freeu(fu["s1"], fu["s2"], fu["b1"], fu["b2"])
         return pipe, call_kwargs, cfg
 
     @property

@@ -242,6 +242,8 @@ class UNet3DConditionModel(nn.Module):
                     _lib.check(lib.lavie_unet_set_param(handle, name.encode(), ctypes.c_void_p(t.data_ptr()), t.numel()),
                                f"lavie_unet_set_param({name})")
                 _lib.check(lib.lavie_unet_finalize(handle, stream), "lavie_unet_finalize")
+                if self.freeu != (1.0, 1.0, 1.0, 1.0):
+                    _lib.check(lib.lavie_unet_set_freeu(handle, *self.freeu), "lavie_unet_set_freeu")
                 if self._lora:
                     keep += self._lora_register(handle, stream)
                     _lib.check(lib.lavie_unet_lora_set_scale(handle, float(self._lora_scale)), "lavie_unet_lora_set_scale")
@@ -513,6 +515,27 @@ class UNet3DConditionModel(nn.Module):
         build the duplicated input themselves switch it on around their steps and off afterwards."""
         handle = self._ensure_engine()
         _lib.check(_lib.load().lavie_unet_set_cfg_shared_input(handle, 1 if on else 0), "lavie_unet_set_cfg_shared_input")
+
+    # ------------------------------------------------------------------ FreeU (diffusers' enable_freeu / disable_freeu)
+    @property
+    def freeu(self):
+        """(s1, s2, b1, b2) in force; (1, 1, 1, 1) = off."""
+        return self.__dict__.get("_freeu", (1.0, 1.0, 1.0, 1.0))
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
+        """FreeU (Si et al.), diffusers' names and argument order: in up block i in {0, 1}, in front of every resnet, the first half
+        of the running activation's channels is scaled by b_{i+1} and the four lowest modes of the skip's 2-D spectrum by s_{i+1}
+        (lavie_unet_set_freeu; the launches run inside the engine's forward).  Every value must be finite and > 0; (1, 1, 1, 1) is off.
+        The setting lives on the model: it holds for every forward that follows, through every pipeline, until disable_freeu()."""
+        vals = tuple(float(v) for v in (s1, s2, b1, b2))
+        if not all(math.isfinite(v) and v > 0.0 for v in vals):
+            raise ValueError(f"enable_freeu: s1={s1} s2={s2} b1={b1} b2={b2} must all be finite and > 0")
+        if self.__dict__.get("_engine"):
+            _lib.check(_lib.load().lavie_unet_set_freeu(self._engine, *vals), "lavie_unet_set_freeu")
+        self.__dict__["_freeu"] = vals
+
+    def disable_freeu(self) -> None:
+        self.enable_freeu(1.0, 1.0, 1.0, 1.0)
 
     def enable_graph(self, on: bool = True) -> None:
         """Replay the forward from a hipGraph (lavie_unet_forward_graph).  While on, the timestep and the output live in

@@ -32,6 +32,13 @@ class VideoUpscalePipeline:
         self.low_res_scheduler = low_res_scheduler or DDPMScheduler(beta_schedule="squaredcos_cap_v2")
         self.max_noise_level = max_noise_level
 
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """diffusers' enable_freeu: forwarded to the UNet (UNet3DConditionModel.enable_freeu), where the setting lives."""
+        self.unet.enable_freeu(s1, s2, b1, b2)
+
+    def disable_freeu(self):
+        self.unet.disable_freeu()
+
     @property
     def device(self):
         return self.unet.device
