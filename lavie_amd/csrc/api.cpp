@@ -453,143 +453,175 @@ int lavie_f16_to_f32(const void* a, const void* b, float* dst, long long n, void
     return b ? launch_add_f16_to_f32(H(a), H(b), dst, n, S(stream)) : launch_f16_to_f32(H(a), dst, n, S(stream));
 }
 
-int lavie_cfg_ddpm_step(const void* eps2, float* x, const float* noise, void* model_in2, long long n, float guidance,
-                        float k_x, float k_eps, float c_x0, float c_xt, float sigma, void* stream) {
-    LAVIE_CHECK(eps2 && x && model_in2 && n > 0, "cfg_ddpm_step: bad arguments");
-    return launch_cfg_ddpm_step(H(eps2), x, noise, H(model_in2), n, guidance, k_x, k_eps, c_x0, c_xt, sigma, 1.0f, S(stream));
-}
-
-int lavie_cfg_sampler_step(const void* eps2, float* x, const float* noise, void* model_in2, long long n, float guidance,
-                           float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale, void* stream) {
-    LAVIE_CHECK(eps2 && x && model_in2 && n > 0, "cfg_sampler_step: bad arguments");
-    return launch_cfg_ddpm_step(H(eps2), x, noise, H(model_in2), n, guidance, k_x, k_eps, c_x0, c_xt, sigma, next_input_scale,
-                                S(stream));
-}
-
-int lavie_sampler_step(const void* eps, float* x, const float* noise, void* model_in, long long n, float k_x, float k_eps,
-                       float c_x0, float c_xt, float sigma, float next_input_scale, void* stream) {
-    LAVIE_CHECK(eps && x && model_in && n > 0, "sampler_step: bad arguments");
-    return launch_sampler_step(H(eps), x, noise, H(model_in), n, k_x, k_eps, c_x0, c_xt, sigma, next_input_scale, S(stream));
-}
-
-// Host-side argument check of the two multistep entries, before any HIP call: the kernel uses 16-byte accesses on all four tensors.
-static int multistep_args(const char* who, const void* eps, const float* x, const float* x0_prev, const void* model_in,
-                          long long n, const float* scalars, int nscalars) {
-    LAVIE_CHECK(eps && x && x0_prev && model_in, "%s: null argument", who);
-    LAVIE_CHECK(n >= 1, "%s: n=%lld must be >= 1", who, n);
-    for (int i = 0; i < nscalars; ++i)
-        LAVIE_CHECK(__builtin_isfinite(scalars[i]), "%s: scalar argument %d (%g) is not finite", who, i, (double)scalars[i]);
-    const void* ptrs[4] = {eps, x, x0_prev, model_in};
-    for (const void* p : ptrs)
-        LAVIE_CHECK(((uintptr_t)p & 15) == 0, "%s: tensor at %p is not 16-byte aligned", who, p);
+// ---- The fused scheduler steps.  Every entry fills a StepArgs (ops.h), runs the one checker below and calls launch_step; what is
+// checked follows from the arguments, not from the entry: all on the host, before any HIP call.
+static int check_aligned(const char* who, const char* name, const void* p) {
+    LAVIE_CHECK(((uintptr_t)p & 15) == 0, "%s: %s at %p is not 16-byte aligned", who, name, p);
     return 0;
 }
 
-int lavie_cfg_multistep_step(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, float guidance, float k_x,
-                             float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream) {
-    const float s[7] = {guidance, k_x, k_eps, c_x0, c_xt, c_prev, next_input_scale};
-    if (int rc = multistep_args("cfg_multistep_step", eps2, x, x0_prev, model_in2, n, s, 7)) return rc;
-    return launch_cfg_multistep_step(H(eps2), x, x0_prev, H(model_in2), n, guidance, k_x, k_eps, c_x0, c_xt, c_prev,
-                                     next_input_scale, S(stream));
+// guidance, the five coefficients and the next step's input scale; c4_name: what the caller calls the fifth coefficient
+static int check_coefficients(const char* who, const StepCoef& c, float in_scale, const char* c4_name) {
+    const float s[7] = {c.guidance, c.kx, c.ke, c.c0, c.ct, c.c4, in_scale};
+    const char* const names[7] = {"guidance", "k_x", "k_eps", "c_x0", "c_xt", c4_name, "next_input_scale"};
+    for (int i = 0; i < 7; ++i) LAVIE_CHECK(__builtin_isfinite(s[i]), "%s: %s (%g) is not finite", who, names[i], (double)s[i]);
+    return 0;
 }
 
-int lavie_multistep_step(const void* eps, float* x, float* x0_prev, void* model_in, long long n, float k_x, float k_eps,
-                         float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream) {
-    const float s[6] = {k_x, k_eps, c_x0, c_xt, c_prev, next_input_scale};
-    if (int rc = multistep_args("multistep_step", eps, x, x0_prev, model_in, n, s, 6)) return rc;
-    return launch_multistep_step(H(eps), x, x0_prev, H(model_in), n, k_x, k_eps, c_x0, c_xt, c_prev, next_input_scale, S(stream));
-}
-
-// Host-side argument check of the five known-region entries (sampler_known.hip), before any HIP call.  `tensors`: what the
-// kernel reads or writes besides the region's own operands (nullptr entries = operands this call does not use).
-static int known_args(const char* who, const lavie_known_region* r, bool mask_optional, long long n, const float* scalars,
-                      int nscalars, const void* const* tensors, const char* const* names, int ntensors) {
+// region -> the launcher's operands in `k` and `a`; a null region or one of another layout is refused before a field is read
+static int fill_region(const char* who, const lavie_known_region* r, KnownOperands* k, StepArgs* a) {
     LAVIE_CHECK(r, "%s: region is null", who);
     LAVIE_CHECK(r->struct_size == (int)sizeof(lavie_known_region),
                 "%s: region->struct_size=%d but this library's lavie_known_region has %d bytes: the binding's struct layout is "
                 "out of date", who, r->struct_size, (int)sizeof(lavie_known_region));
-    for (int i = 0; i < ntensors; ++i) LAVIE_CHECK(tensors[i], "%s: %s is null", who, names[i]);
-    LAVIE_CHECK(r->known, "%s: region->known is null", who);
-    LAVIE_CHECK(r->mask || mask_optional, "%s: region->mask is null", who);
-    for (int i = 0; i < nscalars; ++i)
-        LAVIE_CHECK(__builtin_isfinite(scalars[i]), "%s: scalar argument %d (%g) is not finite", who, i, (double)scalars[i]);
-    LAVIE_CHECK(__builtin_isfinite(r->a_next) && __builtin_isfinite(r->s_next), "%s: region->a_next=%g / s_next=%g is not finite", who,
-                (double)r->a_next, (double)r->s_next);
-    LAVIE_CHECK(r->s_next == 0.f || r->noise_known, "%s: region->noise_known is null but s_next=%g", who, (double)r->s_next);
-    LAVIE_CHECK(r->channels >= 1 && r->inner >= 1, "%s: region->channels=%d inner=%lld must be >= 1", who, r->channels, r->inner);
-    const long long plane = r->inner <= (1ll << 40) ? (long long)r->channels * r->inner : 0;
-    LAVIE_CHECK(n >= 1 && plane > 0 && n % plane == 0, "%s: n=%lld is not a whole number of videos of channels=%d x inner=%lld", who, n,
-                r->channels, r->inner);
-    if (r->inner % 8 == 0) {                 // the eight-elements-per-lane form
-        for (int i = 0; i < ntensors; ++i)
-            LAVIE_CHECK(((uintptr_t)tensors[i] & 15) == 0, "%s: %s at %p is not 16-byte aligned", who, names[i], tensors[i]);
-        const void* own[3] = {r->known, r->mask, r->s_next != 0.f ? r->noise_known : nullptr};
-        const char* own_names[3] = {"region->known", "region->mask", "region->noise_known"};
-        for (int i = 0; i < 3; ++i)
-            LAVIE_CHECK(((uintptr_t)own[i] & 15) == 0, "%s: %s at %p is not 16-byte aligned", who, own_names[i], own[i]);
+    *k = KnownOperands{r->known, r->mask, r->noise_known, r->a_next, r->s_next};
+    a->known = k; a->channels = r->channels; a->inner = r->inner;
+    return 0;
+}
+
+// the region's own operands (sampler_known.hip), for the steps and for the start blend (the one caller whose mask is optional)
+static int check_region(const char* who, const StepArgs& a, bool mask_optional) {
+    const KnownOperands& k = *a.known;
+    LAVIE_CHECK(k.known, "%s: region->known is null", who);
+    LAVIE_CHECK(k.mask || mask_optional, "%s: region->mask is null", who);
+    LAVIE_CHECK(__builtin_isfinite(k.a) && __builtin_isfinite(k.s), "%s: region->a_next=%g / s_next=%g is not finite", who, (double)k.a,
+                (double)k.s);
+    LAVIE_CHECK(k.s == 0.f || k.noise, "%s: region->noise_known is null but s_next=%g", who, (double)k.s);
+    LAVIE_CHECK(a.channels >= 1 && a.inner >= 1, "%s: region->channels=%d inner=%lld must be >= 1", who, a.channels, (long long)a.inner);
+    const long long plane = a.inner <= (1ll << 40) ? (long long)a.channels * a.inner : 0;
+    LAVIE_CHECK(a.n >= 1 && plane > 0 && a.n % plane == 0, "%s: n=%lld is not a whole number of videos of channels=%d x inner=%lld", who,
+                (long long)a.n, a.channels, (long long)a.inner);
+    if (a.inner % 8 == 0) {                 // the eight-elements-per-lane form
+        if (int rc = check_aligned(who, "region->known", k.known)) return rc;
+        if (int rc = check_aligned(who, "region->mask", k.mask)) return rc;
+        if (int rc = check_aligned(who, "region->noise_known", k.s != 0.f ? k.noise : nullptr)) return rc;
     }
     return 0;
 }
 
-static int sampler_step_known(const char* who, bool cfg, const void* eps, float* x, const float* noise, void* model_in, long long n,
-                              float guidance, float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale,
-                              void* stream, const lavie_known_region* r, const float* table = nullptr) {
-    const float s[7] = {guidance, k_x, k_eps, c_x0, c_xt, sigma, next_input_scale};
-    LAVIE_CHECK(sigma == 0.f || noise, "%s: noise is null but sigma=%g", who, (double)sigma);
-    const void* t[4] = {eps, x, model_in, noise};
-    const char* names[4] = {"eps", "x", "model_in", "noise"};
-    if (int rc = known_args(who, r, false, n, s, 7, t, names, sigma != 0.f ? 4 : 3)) return rc;     // sigma == 0: noise is not read
-    return launch_sampler_step_known(cfg, H(eps), x, noise, H(model_in), n, guidance, k_x, k_eps, c_x0, c_xt, sigma, next_input_scale,
-                                     r->known, r->mask, r->noise_known, r->channels, r->inner, r->a_next, r->s_next, table, S(stream));
+// scalars = false: the three plain five-coefficient entries take their scalars as they come, as they always have
+static int check_step(const char* who, const StepArgs& a, bool scalars = true) {
+    const bool aux_used = a.multistep || a.c.c4 != 0.f;     // the history is always written; the noise is read when sigma != 0
+    const void* const t[4] = {a.eps, a.x, a.model_in, aux_used ? a.aux : nullptr};
+    const char* const names[4] = {"eps", "x", "model_in", a.multistep ? "x0_prev" : "noise"};
+    for (int i = 0; i < 3; ++i) LAVIE_CHECK(t[i], "%s: null argument: %s is null", who, names[i]);
+    if (a.multistep) LAVIE_CHECK(a.aux, "%s: null argument: x0_prev is null", who);
+    else LAVIE_CHECK(!aux_used || a.aux, "%s: noise is null but sigma=%g", who, (double)a.c.c4);
+    LAVIE_CHECK(a.n >= 1, "%s: n=%lld must be >= 1", who, (long long)a.n);
+    if (scalars)
+        if (int rc = check_coefficients(who, a.c, a.in_scale, a.multistep ? "c_prev" : "sigma")) return rc;
+    if (a.known)
+        if (int rc = check_region(who, a, false)) return rc;
+    if (a.table && !a.known) {              // grid.y = the latents of `per` elements; around known latents it is the region's planes
+        LAVIE_CHECK(a.per >= 2 && a.per <= (1ll << 40), "%s: per=%lld must be >= 2", who, (long long)a.per);
+        LAVIE_CHECK(a.n % a.per == 0, "%s: n=%lld is not a whole number of latents of per=%lld", who, (long long)a.n, (long long)a.per);
+        LAVIE_CHECK(a.n / a.per <= 65535, "%s: n / per = %lld latents, at most 65535 fit one launch", who, (long long)(a.n / a.per));
+    }
+    // 16-byte accesses: the eight-element form of the kernel that will run.  The plain five-coefficient kernel has none; the plain
+    // multistep kernel counts as one whatever n is (its vector body is empty under guidance with n % 8 != 0, the rule was never relaxed)
+    const bool vec8 = a.known ? a.inner % 8 == 0 : a.table ? a.per % 8 == 0 : a.multistep;
+    if (vec8)
+        for (int i = 0; i < 4; ++i)
+            if (int rc = check_aligned(who, names[i], t[i])) return rc;
+    return 0;
+}
+
+static StepArgs step_args(bool multistep, bool cfg, const void* eps, float* x, const float* aux, void* model_in, long long n, float guidance,
+                          float k_x, float k_eps, float c_x0, float c_xt, float c4, float in_scale, const float* table = nullptr,
+                          long long per = 0) {
+    StepArgs a{};
+    a.multistep = multistep; a.cfg = cfg;
+    a.eps = H(eps); a.x = x; a.aux = const_cast<float*>(aux); a.model_in = H(model_in); a.n = n;     // the noise is only read
+    a.c = StepCoef{guidance, k_x, k_eps, c_x0, c_xt, c4}; a.in_scale = in_scale;
+    a.table = table; a.per = per;
+    return a;
+}
+
+static int run_step(const char* who, const StepArgs& a, void* stream, bool scalars = true) {
+    if (int rc = check_step(who, a, scalars)) return rc;
+    return launch_step(a, S(stream));
+}
+
+static int run_step_known(const char* who, StepArgs a, const lavie_known_region* region, void* stream) {
+    KnownOperands k;
+    if (int rc = fill_region(who, region, &k, &a)) return rc;
+    return run_step(who, a, stream);
+}
+
+int lavie_cfg_ddpm_step(const void* eps2, float* x, const float* noise, void* model_in2, long long n, float guidance,
+                        float k_x, float k_eps, float c_x0, float c_xt, float sigma, void* stream) {
+    return run_step("cfg_ddpm_step", step_args(false, true, eps2, x, noise, model_in2, n, guidance, k_x, k_eps, c_x0, c_xt, sigma, 1.0f),
+                    stream, false);
+}
+
+int lavie_cfg_sampler_step(const void* eps2, float* x, const float* noise, void* model_in2, long long n, float guidance,
+                           float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale, void* stream) {
+    return run_step("cfg_sampler_step", step_args(false, true, eps2, x, noise, model_in2, n, guidance, k_x, k_eps, c_x0, c_xt, sigma,
+                                                  next_input_scale), stream, false);
+}
+
+int lavie_sampler_step(const void* eps, float* x, const float* noise, void* model_in, long long n, float k_x, float k_eps,
+                       float c_x0, float c_xt, float sigma, float next_input_scale, void* stream) {
+    return run_step("sampler_step", step_args(false, false, eps, x, noise, model_in, n, 1.0f, k_x, k_eps, c_x0, c_xt, sigma,
+                                              next_input_scale), stream, false);
+}
+
+int lavie_cfg_multistep_step(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, float guidance, float k_x,
+                             float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream) {
+    return run_step("cfg_multistep_step", step_args(true, true, eps2, x, x0_prev, model_in2, n, guidance, k_x, k_eps, c_x0, c_xt, c_prev,
+                                                    next_input_scale), stream);
+}
+
+int lavie_multistep_step(const void* eps, float* x, float* x0_prev, void* model_in, long long n, float k_x, float k_eps,
+                         float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream) {
+    return run_step("multistep_step", step_args(true, false, eps, x, x0_prev, model_in, n, 1.0f, k_x, k_eps, c_x0, c_xt, c_prev,
+                                                next_input_scale), stream);
 }
 
 int lavie_cfg_sampler_step_known(const void* eps2, float* x, const float* noise, void* model_in2, long long n, float guidance,
                                  float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale, void* stream,
                                  const lavie_known_region* region) {
-    return sampler_step_known("cfg_sampler_step_known", true, eps2, x, noise, model_in2, n, guidance, k_x, k_eps, c_x0, c_xt, sigma,
-                              next_input_scale, stream, region);
+    return run_step_known("cfg_sampler_step_known", step_args(false, true, eps2, x, noise, model_in2, n, guidance, k_x, k_eps, c_x0, c_xt,
+                                                              sigma, next_input_scale), region, stream);
 }
 
 int lavie_sampler_step_known(const void* eps, float* x, const float* noise, void* model_in, long long n, float k_x, float k_eps,
                              float c_x0, float c_xt, float sigma, float next_input_scale, void* stream,
                              const lavie_known_region* region) {
-    return sampler_step_known("sampler_step_known", false, eps, x, noise, model_in, n, 1.0f, k_x, k_eps, c_x0, c_xt, sigma,
-                              next_input_scale, stream, region);
-}
-
-static int multistep_step_known(const char* who, bool cfg, const void* eps, float* x, float* x0_prev, void* model_in, long long n,
-                                float guidance, float k_x, float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale,
-                                void* stream, const lavie_known_region* r, const float* table = nullptr) {
-    const float s[7] = {guidance, k_x, k_eps, c_x0, c_xt, c_prev, next_input_scale};
-    const void* t[4] = {eps, x, x0_prev, model_in};
-    const char* names[4] = {"eps", "x", "x0_prev", "model_in"};
-    if (int rc = known_args(who, r, false, n, s, 7, t, names, 4)) return rc;
-    return launch_multistep_step_known(cfg, H(eps), x, x0_prev, H(model_in), n, guidance, k_x, k_eps, c_x0, c_xt, c_prev,
-                                       next_input_scale, r->known, r->mask, r->noise_known, r->channels, r->inner, r->a_next,
-                                       r->s_next, table, S(stream));
+    return run_step_known("sampler_step_known", step_args(false, false, eps, x, noise, model_in, n, 1.0f, k_x, k_eps, c_x0, c_xt, sigma,
+                                                          next_input_scale), region, stream);
 }
 
 int lavie_cfg_multistep_step_known(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, float guidance,
                                    float k_x, float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale,
                                    void* stream, const lavie_known_region* region) {
-    return multistep_step_known("cfg_multistep_step_known", true, eps2, x, x0_prev, model_in2, n, guidance, k_x, k_eps, c_x0, c_xt,
-                                c_prev, next_input_scale, stream, region);
+    return run_step_known("cfg_multistep_step_known", step_args(true, true, eps2, x, x0_prev, model_in2, n, guidance, k_x, k_eps, c_x0,
+                                                                c_xt, c_prev, next_input_scale), region, stream);
 }
 
 int lavie_multistep_step_known(const void* eps, float* x, float* x0_prev, void* model_in, long long n, float k_x, float k_eps,
                                float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream,
                                const lavie_known_region* region) {
-    return multistep_step_known("multistep_step_known", false, eps, x, x0_prev, model_in, n, 1.0f, k_x, k_eps, c_x0, c_xt, c_prev,
-                                next_input_scale, stream, region);
+    return run_step_known("multistep_step_known", step_args(true, false, eps, x, x0_prev, model_in, n, 1.0f, k_x, k_eps, c_x0, c_xt,
+                                                            c_prev, next_input_scale), region, stream);
 }
 
 int lavie_known_blend_f32(float* x, void* model_in, int dup, long long n, float input_scale, void* stream,
                           const lavie_known_region* region) {
-    const void* t[2] = {x, model_in};
-    const char* names[2] = {"x", "model_in"};
-    if (int rc = known_args("known_blend", region, true, n, &input_scale, 1, t, names, 2)) return rc;
-    return launch_known_blend(x, H(model_in), dup != 0, n, input_scale, region->known, region->mask, region->noise_known,
-                              region->channels, region->inner, region->a_next, region->s_next, S(stream));
+    const char* who = "known_blend";
+    StepArgs a{};
+    KnownOperands k;
+    a.x = x; a.model_in = H(model_in); a.n = n;
+    if (int rc = fill_region(who, region, &k, &a)) return rc;
+    LAVIE_CHECK(x, "%s: x is null", who);
+    LAVIE_CHECK(model_in, "%s: model_in is null", who);
+    LAVIE_CHECK(__builtin_isfinite(input_scale), "%s: input_scale (%g) is not finite", who, (double)input_scale);
+    if (int rc = check_region(who, a, true)) return rc;
+    if (a.inner % 8 == 0) {
+        if (int rc = check_aligned(who, "x", x)) return rc;
+        if (int rc = check_aligned(who, "model_in", model_in)) return rc;
+    }
+    return launch_known_blend(x, a.model_in, dup != 0, n, input_scale, k.known, k.mask, k.noise, a.channels, a.inner, k.a, k.s, S(stream));
 }
 
 // The fused step over overlapping frame windows (sampler_window.hip).  Everything is checked here, on the host, before a table entry
@@ -632,9 +664,8 @@ static int window_step(const char* who, const lavie_window_step_args* a, const f
         LAVIE_CHECK(a->model_in_host[w], "%s: model_in[%d] is null", who, w);
     }
     LAVIE_CHECK(a->x, "%s: x is null", who);
-    const float s[7] = {a->guidance, a->k_x, a->k_eps, a->c_x0, a->c_xt, a->c4, a->next_input_scale};
-    static const char* const snames[7] = {"guidance", "k_x", "k_eps", "c_x0", "c_xt", "c4", "next_input_scale"};
-    for (int i = 0; i < 7; ++i) LAVIE_CHECK(__builtin_isfinite(s[i]), "%s: %s (%g) is not finite", who, snames[i], (double)s[i]);
+    const StepCoef c{a->guidance, a->k_x, a->k_eps, a->c_x0, a->c_xt, a->c4};
+    if (int rc = check_coefficients(who, c, a->next_input_scale, "c4")) return rc;
     const bool aux_used = a->family == 1 || a->c4 != 0.f;
     LAVIE_CHECK(!aux_used || a->aux, "%s: aux is null (%s)", who, a->family == 1 ? "the multistep family's x0_prev" : "the step's noise, c4 != 0");
     // byte ranges: x, aux, then eps[w], then model_in[w]; a written range (x, aux, model_in) may overlap nothing, eps may overlap eps
@@ -667,7 +698,7 @@ static int window_step(const char* who, const lavie_window_step_args* a, const f
             if (i == 1 && !aux_used) continue;
             char bi[32];
             label(i, bi, sizeof bi);
-            LAVIE_CHECK((base(i) & 15) == 0, "%s: %s at %p is not 16-byte aligned", who, bi, (void*)base(i));
+            if (int rc = check_aligned(who, bi, (void*)base(i))) return rc;
         }
     WindowStepParams p{};
     p.multistep = a->family == 1;
@@ -679,7 +710,7 @@ static int window_step(const char* who, const lavie_window_step_args* a, const f
     p.model_in = reinterpret_cast<half_t* const*>(a->model_in_host);
     p.x = a->x;
     p.aux = a->aux;
-    p.guidance = a->guidance; p.kx = a->k_x; p.ke = a->k_eps; p.c0 = a->c_x0; p.ct = a->c_xt; p.c4 = a->c4;
+    p.c = c;
     p.in_scale = a->next_input_scale;
     p.table = table;
     return launch_window_step(p, S(stream));
@@ -721,60 +752,36 @@ int lavie_guidance_table(const lavie_guidance_table_args* a, void* stream) {
                                  a->rescale, a->partials, a->table, a->moments, S(stream));
 }
 
-// Host-side argument check of the two plain scaled steps, before any HIP call: those of multistep_args, plus the table and the latent size.
-static int scaled_args(const char* who, const void* eps, const float* x, const float* aux, bool aux_used, const void* model_in,
-                       long long n, const float* table, long long per, const float* scalars, int nscalars) {
-    LAVIE_CHECK(eps && x && model_in, "%s: null argument", who);
-    LAVIE_CHECK(table, "%s: table is null", who);
-    LAVIE_CHECK(per >= 2 && per <= (1ll << 40), "%s: per=%lld must be >= 2", who, per);
-    LAVIE_CHECK(n >= 1 && n % per == 0, "%s: n=%lld is not a whole number of latents of per=%lld", who, n, per);
-    LAVIE_CHECK(n / per <= 65535, "%s: n / per = %lld latents, at most 65535 fit one launch", who, n / per);
-    for (int i = 0; i < nscalars; ++i)
-        LAVIE_CHECK(__builtin_isfinite(scalars[i]), "%s: scalar argument %d (%g) is not finite", who, i, (double)scalars[i]);
-    if (per % 8 == 0) {
-        const void* ptrs[4] = {eps, x, model_in, aux_used ? aux : nullptr};
-        for (const void* p : ptrs)
-            LAVIE_CHECK(((uintptr_t)p & 15) == 0, "%s: tensor at %p is not 16-byte aligned", who, p);
-    }
-    return 0;
-}
-
 int lavie_cfg_sampler_step_scaled(const void* eps2, float* x, const float* noise, void* model_in2, long long n, const float* table,
                                   long long per, float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale,
                                   void* stream) {
-    const char* who = "cfg_sampler_step_scaled";
-    const float s[6] = {k_x, k_eps, c_x0, c_xt, sigma, next_input_scale};
-    LAVIE_CHECK(sigma == 0.f || noise, "%s: noise is null but sigma=%g", who, (double)sigma);
-    if (int rc = scaled_args(who, eps2, x, noise, sigma != 0.f, model_in2, n, table, per, s, 6)) return rc;
-    return launch_cfg_sampler_step_scaled(H(eps2), x, noise, H(model_in2), n, per, table, k_x, k_eps, c_x0, c_xt, sigma,
-                                          next_input_scale, S(stream));
+    LAVIE_CHECK(table, "cfg_sampler_step_scaled: table is null");
+    return run_step("cfg_sampler_step_scaled", step_args(false, true, eps2, x, noise, model_in2, n, 1.0f, k_x, k_eps, c_x0, c_xt, sigma,
+                                                         next_input_scale, table, per), stream);
 }
 
 int lavie_cfg_multistep_step_scaled(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, const float* table,
                                     long long per, float k_x, float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale,
                                     void* stream) {
-    const char* who = "cfg_multistep_step_scaled";
-    const float s[6] = {k_x, k_eps, c_x0, c_xt, c_prev, next_input_scale};
-    LAVIE_CHECK(x0_prev, "%s: x0_prev is null", who);
-    if (int rc = scaled_args(who, eps2, x, x0_prev, true, model_in2, n, table, per, s, 6)) return rc;
-    return launch_cfg_multistep_step_scaled(H(eps2), x, x0_prev, H(model_in2), n, per, table, k_x, k_eps, c_x0, c_xt, c_prev,
-                                            next_input_scale, S(stream));
+    LAVIE_CHECK(table, "cfg_multistep_step_scaled: table is null");
+    return run_step("cfg_multistep_step_scaled", step_args(true, true, eps2, x, x0_prev, model_in2, n, 1.0f, k_x, k_eps, c_x0, c_xt,
+                                                           c_prev, next_input_scale, table, per), stream);
 }
 
 int lavie_cfg_sampler_step_known_scaled(const void* eps2, float* x, const float* noise, void* model_in2, long long n, const float* table,
                                         float k_x, float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale, void* stream,
                                         const lavie_known_region* region) {
     LAVIE_CHECK(table, "cfg_sampler_step_known_scaled: table is null");
-    return sampler_step_known("cfg_sampler_step_known_scaled", true, eps2, x, noise, model_in2, n, 1.0f, k_x, k_eps, c_x0, c_xt, sigma,
-                              next_input_scale, stream, region, table);
+    return run_step_known("cfg_sampler_step_known_scaled", step_args(false, true, eps2, x, noise, model_in2, n, 1.0f, k_x, k_eps, c_x0,
+                                                                     c_xt, sigma, next_input_scale, table), region, stream);
 }
 
 int lavie_cfg_multistep_step_known_scaled(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, const float* table,
                                           float k_x, float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale,
                                           void* stream, const lavie_known_region* region) {
     LAVIE_CHECK(table, "cfg_multistep_step_known_scaled: table is null");
-    return multistep_step_known("cfg_multistep_step_known_scaled", true, eps2, x, x0_prev, model_in2, n, 1.0f, k_x, k_eps, c_x0, c_xt,
-                                c_prev, next_input_scale, stream, region, table);
+    return run_step_known("cfg_multistep_step_known_scaled", step_args(true, true, eps2, x, x0_prev, model_in2, n, 1.0f, k_x, k_eps, c_x0,
+                                                                       c_xt, c_prev, next_input_scale, table), region, stream);
 }
 
 int lavie_window_step_scaled(const lavie_window_step_args* a, const float* table, void* stream) {

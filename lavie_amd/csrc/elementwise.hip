@@ -358,20 +358,11 @@ __global__ void sampler_step_kernel(const half_t* __restrict__ eps2, float* __re
     if (CFG) model_in2[n + i] = h;
 }
 
-int launch_cfg_ddpm_step(const half_t* eps2, float* x, const float* noise, half_t* model_in2, int64_t n, float guidance,
-                         float kx, float ke, float c0, float ct, float sigma, float in_scale, hipStream_t stream) {
-    LAVIE_CHECK(sigma == 0.f || noise != nullptr, "ddpm step: sigma != 0 needs a noise tensor");
-    hipLaunchKernelGGL(sampler_step_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, eps2, x, noise,
-                       model_in2, (long)n, guidance, kx, ke, c0, ct, sigma, in_scale);
-    LAVIE_HIP(hipGetLastError());
-    return 0;
-}
-
-int launch_sampler_step(const half_t* eps, float* x, const float* noise, half_t* model_in, int64_t n, float kx, float ke,
-                        float c0, float ct, float sigma, float in_scale, hipStream_t stream) {
-    LAVIE_CHECK(sigma == 0.f || noise != nullptr, "sampler step: sigma != 0 needs a noise tensor");
-    hipLaunchKernelGGL(sampler_step_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, eps, x, noise,
-                       model_in, (long)n, 1.0f, kx, ke, c0, ct, sigma, in_scale);
+static int launch_five_coefficient(const StepArgs& a, hipStream_t stream) {
+    LAVIE_CHECK(a.c.c4 == 0.f || a.aux != nullptr, "sampler step: sigma != 0 needs a noise tensor");
+    auto kern = a.cfg ? sampler_step_kernel<true> : sampler_step_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, stream, a.eps, a.x, (const float*)a.aux, a.model_in,
+                       (long)a.n, a.c.guidance, a.c.kx, a.c.ke, a.c.c0, a.c.ct, a.c.c4, a.in_scale);
     LAVIE_HIP(hipGetLastError());
     return 0;
 }
@@ -459,29 +450,27 @@ __global__ __launch_bounds__(256) void multistep_step_kernel(const half_t* __res
 }
 
 template <bool CFG>
-static int launch_multistep(const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n, float guidance,
-                            float kx, float ke, float c0, float ct, float cp, float in_scale, hipStream_t stream) {
+static int launch_multistep(const StepArgs& a, hipStream_t stream) {
     // under guidance the cond halves start n elements in: 16-byte aligned only when n % 8 == 0 (every latent shape of the
     // pipelines); otherwise every lane takes one element
-    const long nvec = (!CFG || n % 8 == 0) ? (long)(n / 8) : 0;
-    const int64_t lanes = nvec + (n - nvec * 8);
+    const long nvec = (!CFG || a.n % 8 == 0) ? (long)(a.n / 8) : 0;
+    const int64_t lanes = nvec + (a.n - nvec * 8);
     const int64_t blocks = (lanes + 255) / 256;
-    LAVIE_CHECK(blocks <= 0x7fffffff, "multistep step: n=%lld does not fit one launch", (long long)n);
-    auto kern = cp != 0.f ? multistep_step_kernel<CFG, true> : multistep_step_kernel<CFG, false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, stream, eps2, x, x0_prev, model_in2, (long)n, nvec,
-                       guidance, kx, ke, c0, ct, cp, in_scale);
+    LAVIE_CHECK(blocks <= 0x7fffffff, "multistep step: n=%lld does not fit one launch", (long long)a.n);
+    auto kern = a.c.c4 != 0.f ? multistep_step_kernel<CFG, true> : multistep_step_kernel<CFG, false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, stream, a.eps, a.x, a.aux, a.model_in, (long)a.n, nvec,
+                       a.c.guidance, a.c.kx, a.c.ke, a.c.c0, a.c.ct, a.c.c4, a.in_scale);
     LAVIE_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_cfg_multistep_step(const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n, float guidance,
-                              float kx, float ke, float c0, float ct, float cp, float in_scale, hipStream_t stream) {
-    return launch_multistep<true>(eps2, x, x0_prev, model_in2, n, guidance, kx, ke, c0, ct, cp, in_scale, stream);
+int launch_step_plain(const StepArgs& a, hipStream_t stream) {
+    if (!a.multistep) return launch_five_coefficient(a, stream);
+    return a.cfg ? launch_multistep<true>(a, stream) : launch_multistep<false>(a, stream);
 }
 
-int launch_multistep_step(const half_t* eps, float* x, float* x0_prev, half_t* model_in, int64_t n, float kx, float ke,
-                          float c0, float ct, float cp, float in_scale, hipStream_t stream) {
-    return launch_multistep<false>(eps, x, x0_prev, model_in, n, 1.0f, kx, ke, c0, ct, cp, in_scale, stream);
+int launch_step(const StepArgs& a, hipStream_t stream) {
+    return a.known ? launch_step_known(a, stream) : a.table ? launch_step_scaled(a, stream) : launch_step_plain(a, stream);
 }
 
 template <bool DUP>

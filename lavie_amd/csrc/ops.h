@@ -110,35 +110,36 @@ int launch_conv_edge_out(const half_t* x, const half_t* wp, const float* bias, v
                          hipStream_t stream);
 int launch_pack_conv_edge_out(const half_t* w, half_t* out, int Cout, int Cin, hipStream_t stream);
 long long conv_edge_out_image_halfs(int Cin);
-// Classifier-free guidance + DDPM ancestral step (pipeline_videogen.py:679-683):
-//   eps = eps_u + s (eps_c - eps_u); x0 = kx x - ke eps; x' = c0 x0 + ct x + sigma noise
-//   writes x' (fp32, in place allowed) and the duplicated fp16 model input [2, n] for the next step.
-int launch_cfg_ddpm_step(const half_t* eps2, float* x, const float* noise, half_t* model_in2, int64_t n, float guidance,
-                         float kx, float ke, float c0, float ct, float sigma, float in_scale, hipStream_t stream);
+// ---- the fused scheduler steps (elementwise.hip, sampler_known.hip, sampler_guidance.hip): StepArgs is the one description of a step
+// from the C entry points down to the launch.  Per element, fp32 (pipeline_videogen.py:679-683, scheduling_dpmsolver_multistep.py):
+//   eps = cfg ? eps_u + g (eps_c - eps_u) : eps_u;  x0 = kx x - ke eps
+//   five-coefficient family: x' = c0 x0 + ct x + sigma noise                     (aux = the step's noise, read when c4 = sigma != 0)
+//   multistep family (DPM-Solver++ 2M): D = cp != 0 ? x0 + cp (x0 - x0_prev) : x0;  x' = c0 D + ct x;  x0_prev <- x0
+//                                                                                 (aux = x0_prev, read when c4 = cp != 0, always written)
+//   x <- x' in place; model_in <- fp16(x' in_scale), [2, n] = both guidance halves with cfg (eps is [2, n] then as well).
+//   known != nullptr: x' = select(mask, x', a known + s noise) inside the step (sampler_known.hip); n = P * channels * inner.
+//   table != nullptr (cfg only): (g, rescale factor f) per latent from table[P][2] and eps = f eps (sampler_guidance.hip); n = P per
+//   (with `known` the latent is the plane's video and `per` is not read).
+//   Every tensor must be 16-byte aligned where the eight-element form runs: the multistep family without `known` / `table`, inner % 8
+//   == 0 with `known`, per % 8 == 0 with `table` alone (checked by the C entry points).
+struct StepCoef { float guidance, kx, ke, c0, ct, c4; };     // c4: sigma (five-coefficient family) or c_prev (multistep family)
+struct KnownOperands { const float* known; const float* mask; const float* noise; float a, s; };     // mask == nullptr: 1 everywhere (blend only)
+struct StepArgs {
+    bool multistep, cfg;
+    const half_t* eps; float* x; float* aux;          // aux: the step's noise (five-coefficient) or x0_prev (multistep)
+    half_t* model_in; int64_t n;
+    StepCoef c; float in_scale;                       // c.guidance = 1 without cfg and with a table
+    const KnownOperands* known; int channels; int64_t inner;   // known == nullptr: no region
+    const float* table; int64_t per;                            // table == nullptr: scalar guidance
+};
+int launch_step(const StepArgs& a, hipStream_t stream);              // picks the file by (known, table)
+int launch_step_plain(const StepArgs& a, hipStream_t stream);        // elementwise.hip
+int launch_step_known(const StepArgs& a, hipStream_t stream);        // sampler_known.hip
+int launch_step_scaled(const StepArgs& a, hipStream_t stream);       // sampler_guidance.hip
 int launch_add_class_emb_silu(float* emb, const half_t* table, const int* labels_host, int B, int N, hipStream_t stream);
 int launch_f32_to_f16_dup2(const float* x, half_t* out2, int64_t n, float in_scale, hipStream_t stream);
-int launch_sampler_step(const half_t* eps, float* x, const float* noise, half_t* model_in, int64_t n, float kx, float ke,
-                        float c0, float ct, float sigma, float in_scale, hipStream_t stream);
 int launch_f32_to_f16_scaled(const float* x, half_t* out, int64_t n, float in_scale, hipStream_t stream);
-// Guidance + multistep (DPM-Solver++ 2M) step: the five-coefficient form with the previous x0 prediction as history:
-//   x0 = kx x - ke eps; D = cp != 0 ? x0 + cp (x0 - x0_prev) : x0; x' = c0 D + ct x; x0_prev <- x0 (never read when cp == 0).
-//   eps2 / x / x0_prev / model_in2 must be 16-byte aligned (checked by the C entry points).
-int launch_cfg_multistep_step(const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n, float guidance,
-                              float kx, float ke, float c0, float ct, float cp, float in_scale, hipStream_t stream);
-int launch_multistep_step(const half_t* eps, float* x, float* x0_prev, half_t* model_in, int64_t n, float kx, float ke,
-                          float c0, float ct, float cp, float in_scale, hipStream_t stream);
-// ---- sampler_known.hip : the steps above around known latents (known-region replacement inside the step kernel)
-//   x' = select(mask, plain step's x', a_next known + s_next noise_known); cfg picks the guided variant; n = P * channels * inner;
-//   with inner % 8 == 0 every tensor must be 16-byte aligned (checked by the C entry points).  table != nullptr (cfg only): guidance
-//   and rescale factor per latent from table[P][2] (sampler_guidance.hip) instead of `guidance`.
-int launch_sampler_step_known(bool cfg, const half_t* eps2, float* x, const float* noise, half_t* model_in2, int64_t n,
-                              float guidance, float kx, float ke, float c0, float ct, float sigma, float in_scale,
-                              const float* known, const float* mask, const float* noise_known, int channels, int64_t inner,
-                              float a_next, float s_next, const float* table, hipStream_t stream);
-int launch_multistep_step_known(bool cfg, const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n,
-                                float guidance, float kx, float ke, float c0, float ct, float cp, float in_scale,
-                                const float* known, const float* mask, const float* noise_known, int channels, int64_t inner,
-                                float a_next, float s_next, const float* table, hipStream_t stream);
+// ---- sampler_known.hip : the blend that starts a run around known latents (the steps around them: StepArgs::known)
 // x <- select(mask, x, a_next known + s_next noise_known) (mask == nullptr: mask = 1 everywhere); model_in = fp16(x in_scale), twice when dup
 int launch_known_blend(float* x, half_t* model_in, bool dup, int64_t n, float in_scale, const float* known, const float* mask,
                        const float* noise_known, int channels, int64_t inner, float a_next, float s_next, hipStream_t stream);
@@ -161,7 +162,8 @@ struct WindowStepParams {
     half_t* const* model_in;
     float* x;
     float* aux;
-    float guidance, kx, ke, c0, ct, c4, in_scale;
+    StepCoef c;
+    float in_scale;
     const float* table;     // nullptr, or [W][P][2] (guidance, rescale factor) per window and latent (sampler_guidance.hip); needs cfg
 };
 int launch_window_step(const WindowStepParams& a, hipStream_t stream);
@@ -169,21 +171,14 @@ int launch_window_step(const WindowStepParams& a, hipStream_t stream);
 //   launch_guidance_table: eps[w] = fp16 [2 P, per] of window w (W = 1 without windows); writes partials (guidance_chunks(per) * 4
 //   floats per latent, untouched when phi == 0), table[W][P] = (g_p, f_p) and, if given, moments[W][P] = the four double sums
 //   (ec, ec^2, e, e^2).  g_p = guidance_dev[p] (device, may be nullptr) or `guidance`.  Two launches (one when phi == 0).
-//   The scaled steps are the guided plain steps with (g, f) = table[i / per] and eps = f e; n = P per; with per % 8 == 0 every
-//   tensor must be 16-byte aligned (checked by the C entry points).
+//   The scaled steps (StepArgs::table) are the guided plain steps with (g, f) = table[i / per] and eps = f e.
 constexpr int kGuidanceChunk = 2048;
 int64_t guidance_chunks(int64_t per);
 int launch_guidance_table(const half_t* const* eps, int W, int P, int64_t per, const float* guidance_dev, float guidance, float phi,
                           float* partials, float* table, double* moments, hipStream_t stream);
-int launch_cfg_sampler_step_scaled(const half_t* eps2, float* x, const float* noise, half_t* model_in2, int64_t n, int64_t per,
-                                   const float* table, float kx, float ke, float c0, float ct, float sigma, float in_scale,
-                                   hipStream_t stream);
-int launch_cfg_multistep_step_scaled(const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n, int64_t per,
-                                     const float* table, float kx, float ke, float c0, float ct, float cp, float in_scale,
-                                     hipStream_t stream);
 int launch_fill_relpos_bias(const half_t* emb, const int* buckets, float* out, int heads, int F, hipStream_t stream);
 
-// ---- pack.hip : one-off weight repacking at load time
+// ---- elementwise.hip : one-off weight repacking at load time
 // chunked = true: K order (64-channel slab, tap, channel) for the implicit GEMM; false: (tap, channel) for conv_out
 int launch_pack_conv3x3(const half_t* w, half_t* out, int Cout, int Cin, int ld_out, int col0, bool chunked,
                         hipStream_t stream);

@@ -5,10 +5,9 @@
 // built from these pieces gives the plain kernel's bits wherever its own addition is the identity.
 #pragma once
 #include "common.h"
+#include "ops.h"      // StepCoef
 
 namespace lavie {
-
-struct StepCoef { float guidance, kx, ke, c0, ct, c4; };     // c4: sigma (five-coefficient family) or c_prev (multistep family)
 
 // eps = eps_u + g (eps_c - eps_u) as one fma; without guidance eps_u itself
 template <bool CFG> __device__ __forceinline__ float guided_eps(float eu, float ec, float guidance) {

@@ -159,33 +159,22 @@ __global__ __launch_bounds__(256) void scaled_step_kernel(const half_t* __restri
 }
 
 template <int FAM, bool HIST>
-static int launch_scaled(const half_t* eps2, float* x, float* aux, half_t* model_in2, int64_t n, int64_t per, const float* table,
-                         const StepCoef& c, float in_scale, hipStream_t stream) {
-    const int64_t latents = n / per;
+static int launch_scaled(const StepArgs& a, hipStream_t stream) {
+    const int64_t latents = a.n / a.per;
     LAVIE_CHECK(latents >= 1 && latents <= 65535, "scaled step: %lld latents do not fit one launch", (long long)latents);
-    const bool vec = per % 8 == 0;
-    const int64_t blocks = ((vec ? per / 8 : per) + 255) / 256;
-    LAVIE_CHECK(blocks <= 0x7fffffff, "scaled step: per=%lld does not fit one launch", (long long)per);
+    const bool vec = a.per % 8 == 0;
+    const int64_t blocks = ((vec ? a.per / 8 : a.per) + 255) / 256;
+    LAVIE_CHECK(blocks <= 0x7fffffff, "scaled step: per=%lld does not fit one launch", (long long)a.per);
     auto kern = vec ? scaled_step_kernel<FAM, HIST, 8> : scaled_step_kernel<FAM, HIST, 1>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)latents), dim3(256), 0, stream, eps2, x, aux, model_in2, (long)n,
-                       (long)per, table, c, in_scale);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)latents), dim3(256), 0, stream, a.eps, a.x, a.aux, a.model_in, (long)a.n,
+                       (long)a.per, a.table, a.c, a.in_scale);
     LAVIE_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_cfg_sampler_step_scaled(const half_t* eps2, float* x, const float* noise, half_t* model_in2, int64_t n, int64_t per,
-                                   const float* table, float kx, float ke, float c0, float ct, float sigma, float in_scale,
-                                   hipStream_t stream) {
-    const StepCoef c{1.f, kx, ke, c0, ct, sigma};
-    return launch_scaled<0, false>(eps2, x, const_cast<float*>(noise), model_in2, n, per, table, c, in_scale, stream);     // FAM 0 only reads aux
-}
-
-int launch_cfg_multistep_step_scaled(const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n, int64_t per,
-                                     const float* table, float kx, float ke, float c0, float ct, float cp, float in_scale,
-                                     hipStream_t stream) {
-    const StepCoef c{1.f, kx, ke, c0, ct, cp};
-    return cp != 0.f ? launch_scaled<1, true>(eps2, x, x0_prev, model_in2, n, per, table, c, in_scale, stream)
-                     : launch_scaled<1, false>(eps2, x, x0_prev, model_in2, n, per, table, c, in_scale, stream);
+int launch_step_scaled(const StepArgs& a, hipStream_t stream) {
+    if (!a.multistep) return launch_scaled<0, false>(a, stream);
+    return a.c.c4 != 0.f ? launch_scaled<1, true>(a, stream) : launch_scaled<1, false>(a, stream);
 }
 
 }  // namespace lavie

@@ -27,8 +27,6 @@
 
 namespace lavie {
 
-struct KnownOperands { const float* known; const float* mask; const float* noise; float a, s; };
-
 __device__ __forceinline__ float known_select(float m, float free_v, float pinned_v) {
 #pragma clang fp contract(off)
     return m == 0.f ? free_v : m == 1.f ? pinned_v : __builtin_fmaf(m, pinned_v - free_v, free_v);
@@ -88,56 +86,40 @@ __global__ __launch_bounds__(256) void known_step_kernel(const half_t* __restric
 }
 
 template <int FAM, bool CFG, bool HIST, bool TAB = false>
-static int launch_known(const half_t* eps2, float* x, float* aux, half_t* model_in2, int64_t n, const StepCoef& c,
-                        const KnownOperands& k, int channels, int64_t inner, float in_scale, hipStream_t stream,
-                        const float* table = nullptr) {
-    const int64_t planes = n / inner;
+static int launch_known(const StepArgs& a, hipStream_t stream) {
+    const int64_t planes = a.n / a.inner;
     LAVIE_CHECK(planes >= 1 && planes <= 65535, "known-region step: %lld (video, channel) planes do not fit one launch",
                 (long long)planes);
-    const bool vec = inner % 8 == 0;
-    const int64_t blocks = ((vec ? inner / 8 : inner) + 255) / 256;
-    LAVIE_CHECK(blocks <= 0x7fffffff, "known-region step: inner=%lld does not fit one launch", (long long)inner);
+    const bool vec = a.inner % 8 == 0;
+    const int64_t blocks = ((vec ? a.inner / 8 : a.inner) + 255) / 256;
+    LAVIE_CHECK(blocks <= 0x7fffffff, "known-region step: inner=%lld does not fit one launch", (long long)a.inner);
     auto kern = vec ? known_step_kernel<FAM, CFG, HIST, 8, TAB> : known_step_kernel<FAM, CFG, HIST, 1, TAB>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, eps2, x, aux, model_in2, (long)n,
-                       channels, (long)inner, c, k, in_scale, table);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, a.eps, a.x, a.aux, a.model_in, (long)a.n,
+                       a.channels, (long)a.inner, a.c, *a.known, a.in_scale, a.table);
     LAVIE_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_sampler_step_known(bool cfg, const half_t* eps2, float* x, const float* noise, half_t* model_in2, int64_t n,
-                              float guidance, float kx, float ke, float c0, float ct, float sigma, float in_scale,
-                              const float* known, const float* mask, const float* noise_known, int channels, int64_t inner,
-                              float a_next, float s_next, const float* table, hipStream_t stream) {
-    const StepCoef c{guidance, kx, ke, c0, ct, sigma};
-    const KnownOperands k{known, mask, noise_known, a_next, s_next};
-    float* aux = const_cast<float*>(noise);              // FAM 0 only reads it
-    if (table) return launch_known<0, true, false, true>(eps2, x, aux, model_in2, n, c, k, channels, inner, in_scale, stream, table);
-    return cfg ? launch_known<0, true, false>(eps2, x, aux, model_in2, n, c, k, channels, inner, in_scale, stream)
-               : launch_known<0, false, false>(eps2, x, aux, model_in2, n, c, k, channels, inner, in_scale, stream);
-}
-
-int launch_multistep_step_known(bool cfg, const half_t* eps2, float* x, float* x0_prev, half_t* model_in2, int64_t n,
-                                float guidance, float kx, float ke, float c0, float ct, float cp, float in_scale,
-                                const float* known, const float* mask, const float* noise_known, int channels, int64_t inner,
-                                float a_next, float s_next, const float* table, hipStream_t stream) {
-    const StepCoef c{guidance, kx, ke, c0, ct, cp};
-    const KnownOperands k{known, mask, noise_known, a_next, s_next};
-    if (table)
-        return cp != 0.f ? launch_known<1, true, true, true>(eps2, x, x0_prev, model_in2, n, c, k, channels, inner, in_scale, stream, table)
-                         : launch_known<1, true, false, true>(eps2, x, x0_prev, model_in2, n, c, k, channels, inner, in_scale, stream, table);
-    if (cfg)
-        return cp != 0.f ? launch_known<1, true, true>(eps2, x, x0_prev, model_in2, n, c, k, channels, inner, in_scale, stream)
-                         : launch_known<1, true, false>(eps2, x, x0_prev, model_in2, n, c, k, channels, inner, in_scale, stream);
-    return cp != 0.f ? launch_known<1, false, true>(eps2, x, x0_prev, model_in2, n, c, k, channels, inner, in_scale, stream)
-                     : launch_known<1, false, false>(eps2, x, x0_prev, model_in2, n, c, k, channels, inner, in_scale, stream);
+// the instantiation of a step: the family, guidance (a table is guided by definition), and for the multistep family whether the
+// history is read
+int launch_step_known(const StepArgs& a, hipStream_t stream) {
+    const bool hist = a.c.c4 != 0.f;
+    if (!a.multistep) {
+        if (a.table) return launch_known<0, true, false, true>(a, stream);
+        return a.cfg ? launch_known<0, true, false>(a, stream) : launch_known<0, false, false>(a, stream);
+    }
+    if (a.table) return hist ? launch_known<1, true, true, true>(a, stream) : launch_known<1, true, false, true>(a, stream);
+    if (a.cfg) return hist ? launch_known<1, true, true>(a, stream) : launch_known<1, true, false>(a, stream);
+    return hist ? launch_known<1, false, true>(a, stream) : launch_known<1, false, false>(a, stream);
 }
 
 int launch_known_blend(float* x, half_t* model_in, bool dup, int64_t n, float in_scale, const float* known, const float* mask,
                        const float* noise_known, int channels, int64_t inner, float a_next, float s_next, hipStream_t stream) {
-    const StepCoef c{};
     const KnownOperands k{known, mask, noise_known, a_next, s_next};
-    return dup ? launch_known<2, true, false>(nullptr, x, nullptr, model_in, n, c, k, channels, inner, in_scale, stream)
-               : launch_known<2, false, false>(nullptr, x, nullptr, model_in, n, c, k, channels, inner, in_scale, stream);
+    StepArgs a{};                   // no eps, no aux, no table, coefficients zero
+    a.x = x; a.model_in = model_in; a.n = n; a.in_scale = in_scale;
+    a.known = &k; a.channels = channels; a.inner = inner;
+    return dup ? launch_known<2, true, false>(a, stream) : launch_known<2, false, false>(a, stream);
 }
 
 }  // namespace lavie

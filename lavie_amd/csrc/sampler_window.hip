@@ -122,13 +122,12 @@ static int launch_window(const WindowStepParams& a, hipStream_t stream) {
     }
     for (int i = 0; i < a.L; ++i) t.profile[i] = a.profile[i];
     const WindowShape s{a.P, a.C, a.F, a.W, a.L, (long)a.hw};
-    const StepCoef c{a.guidance, a.kx, a.ke, a.c0, a.ct, a.c4};
     if constexpr (TAB) {
         auto kern = vec ? window_step_kernel<FAM, CFG, HIST, 8, const float*> : window_step_kernel<FAM, CFG, HIST, 1, const float*>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, a.x, a.aux, t, s, c, a.in_scale, a.table);
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, a.x, a.aux, t, s, a.c, a.in_scale, a.table);
     } else {
         auto kern = vec ? window_step_kernel<FAM, CFG, HIST, 8> : window_step_kernel<FAM, CFG, HIST, 1>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, a.x, a.aux, t, s, c, a.in_scale);
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, a.x, a.aux, t, s, a.c, a.in_scale);
     }
     LAVIE_HIP(hipGetLastError());
     return 0;
@@ -137,12 +136,12 @@ static int launch_window(const WindowStepParams& a, hipStream_t stream) {
 int launch_window_step(const WindowStepParams& a, hipStream_t stream) {
     if (a.table) {                  // guided by definition: the table holds the guidance scales
         if (!a.multistep) return launch_window<0, true, false, true>(a, stream);
-        return a.c4 != 0.f ? launch_window<1, true, true, true>(a, stream) : launch_window<1, true, false, true>(a, stream);
+        return a.c.c4 != 0.f ? launch_window<1, true, true, true>(a, stream) : launch_window<1, true, false, true>(a, stream);
     }
     if (!a.multistep)
         return a.cfg ? launch_window<0, true, false>(a, stream) : launch_window<0, false, false>(a, stream);
-    if (a.cfg) return a.c4 != 0.f ? launch_window<1, true, true>(a, stream) : launch_window<1, true, false>(a, stream);
-    return a.c4 != 0.f ? launch_window<1, false, true>(a, stream) : launch_window<1, false, false>(a, stream);
+    if (a.cfg) return a.c.c4 != 0.f ? launch_window<1, true, true>(a, stream) : launch_window<1, true, false>(a, stream);
+    return a.c.c4 != 0.f ? launch_window<1, false, true>(a, stream) : launch_window<1, false, false>(a, stream);
 }
 
 }  // namespace lavie

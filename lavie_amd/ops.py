@@ -572,17 +572,41 @@ def temporal_attention(qkv, b, frames, d, heads, bias, rot_cos, rot_sin, rot_dim
     return o
 
 
+def _step(entry, who, eps, x, aux, model_in, coeffs, next_input_scale, *, guidance=None, table=None, region=None, counts=True):
+    """The body of every scheduler-step wrapper: dtype, element-count and shape checks, then the C entry `entry` with its operands
+    in the order the entries share: eps, x, aux, model_in, n, [guidance | table, [per]], the five coefficients, next_input_scale,
+    the stream, [the region].  The wrapper's name `who` says the form: cfg_ = eps / model_in hold both guidance halves, multistep =
+    aux is the x0_prev history (else the step's noise, which may be None), _scaled = guidance from `table` [P, 2].
+    region = (known, mask, noise_known, level) of a step around known latents."""
+    guided, multistep, scaled = who.startswith("cfg_"), "multistep" in who, who.endswith("_scaled")
+    if scaled and multistep and aux is None:
+        raise ValueError(f"{who}: x0_prev is needed")
+    _chk16(eps, model_in)
+    _chk32(x, aux, table)
+    n = x.numel()
+    m = 2 * n if guided else n
+    if counts and (eps.numel() != m or model_in.numel() != m or ((multistep or scaled) and aux is not None and aux.numel() != n)):
+        if scaled:
+            raise ValueError(f"{who}: eps2 / model_in2 must have twice, noise / x0_prev as many elements as x")
+        if guided:
+            raise ValueError(f"{who}: eps2 / model_in2 must have twice" + (", x0_prev" if multistep else "") + " as many elements as x")
+        raise ValueError(f"{who}: eps / model_in" + (" / x0_prev" if multistep else "") + " must have as many elements as x")
+    if scaled and (table is None or tuple(table.shape) != (x.shape[0], 2) or table.device != x.device):
+        raise ValueError(f"{who}: table must be an fp32 tensor [{x.shape[0]}, 2] on {x.device}")
+    k_x, k_e, c_x0, c_xt, c4 = coeffs
+    if scaled:
+        how = (_p(table), n // x.shape[0]) if region is None else (_p(table),)
+    else:
+        how = (float(guidance),) if guided else ()
+    tail = () if region is None else (ctypes.byref(_known_region(who, x, *region)),)
+    _lib.check(getattr(_lib.load(), entry)(_p(eps), _p(x), _p(aux), _p(model_in), n, *how, float(k_x), float(k_e), float(c_x0), float(c_xt),
+                                           float(c4), float(next_input_scale), _stream(), *tail), entry)
+
+
 def cfg_ddpm_step(eps2, x, noise, model_in2, guidance, coeffs, next_input_scale: float = 1.0):
     """Fused CFG + scheduler update; `coeffs` = (k_x, k_eps, c_x0, c_xt, sigma) from <scheduler>.coefficients;
     `next_input_scale` = the scheduler's scale_model_input factor of the next step (1 for DDPM / DDIM)."""
-    _chk16(eps2, model_in2)
-    _chk32(x, noise)
-    k_x, k_e, c_x0, c_xt, sigma = coeffs
-    n = x.numel()
-    _lib.check(_lib.load().lavie_cfg_sampler_step(_p(eps2), _p(x), _p(noise), _p(model_in2), n, float(guidance), float(k_x),
-                                                  float(k_e), float(c_x0), float(c_xt), float(sigma),
-                                                  float(next_input_scale), _stream()),
-               "lavie_cfg_sampler_step")
+    _step("lavie_cfg_sampler_step", "cfg_ddpm_step", eps2, x, noise, model_in2, coeffs, next_input_scale, guidance=guidance, counts=False)
 
 
 def latents_to_model_input(x, model_in2, input_scale: float = 1.0):
@@ -593,42 +617,18 @@ def latents_to_model_input(x, model_in2, input_scale: float = 1.0):
 
 def sampler_step(eps, x, noise, model_in, coeffs, next_input_scale: float = 1.0):
     """Scheduler update without classifier-free guidance (guidance_scale <= 1): eps / model_in are fp16 of x's size."""
-    _chk16(eps, model_in)
-    _chk32(x, noise)
-    if eps.numel() != x.numel() or model_in.numel() != x.numel():
-        raise ValueError("sampler_step: eps / model_in must have as many elements as x")
-    k_x, k_e, c_x0, c_xt, sigma = coeffs
-    _lib.check(_lib.load().lavie_sampler_step(_p(eps), _p(x), _p(noise), _p(model_in), x.numel(), float(k_x), float(k_e),
-                                              float(c_x0), float(c_xt), float(sigma), float(next_input_scale), _stream()),
-               "lavie_sampler_step")
+    _step("lavie_sampler_step", "sampler_step", eps, x, noise, model_in, coeffs, next_input_scale)
 
 
 def cfg_multistep_step(eps2, x, x0_prev, model_in2, guidance, coeffs, next_input_scale: float = 1.0):
     """Fused CFG + multistep (DPM-Solver++ 2M) update; `coeffs` = (k_x, k_eps, c_x0, c_xt, c_prev) from a multistep scheduler's
     `coefficients`; `x0_prev` = fp32 history of x's size, rewritten every step and read only when c_prev != 0."""
-    _chk16(eps2, model_in2)
-    _chk32(x, x0_prev)
-    n = x.numel()
-    if eps2.numel() != 2 * n or model_in2.numel() != 2 * n or x0_prev.numel() != n:
-        raise ValueError("cfg_multistep_step: eps2 / model_in2 must have twice, x0_prev as many elements as x")
-    k_x, k_e, c_x0, c_xt, c_prev = coeffs
-    _lib.check(_lib.load().lavie_cfg_multistep_step(_p(eps2), _p(x), _p(x0_prev), _p(model_in2), n, float(guidance), float(k_x),
-                                                    float(k_e), float(c_x0), float(c_xt), float(c_prev),
-                                                    float(next_input_scale), _stream()),
-               "lavie_cfg_multistep_step")
+    _step("lavie_cfg_multistep_step", "cfg_multistep_step", eps2, x, x0_prev, model_in2, coeffs, next_input_scale, guidance=guidance)
 
 
 def multistep_step(eps, x, x0_prev, model_in, coeffs, next_input_scale: float = 1.0):
     """The multistep update without classifier-free guidance (guidance_scale <= 1): eps / model_in are fp16 of x's size."""
-    _chk16(eps, model_in)
-    _chk32(x, x0_prev)
-    n = x.numel()
-    if eps.numel() != n or model_in.numel() != n or x0_prev.numel() != n:
-        raise ValueError("multistep_step: eps / model_in / x0_prev must have as many elements as x")
-    k_x, k_e, c_x0, c_xt, c_prev = coeffs
-    _lib.check(_lib.load().lavie_multistep_step(_p(eps), _p(x), _p(x0_prev), _p(model_in), n, float(k_x), float(k_e),
-                                                float(c_x0), float(c_xt), float(c_prev), float(next_input_scale), _stream()),
-               "lavie_multistep_step")
+    _step("lavie_multistep_step", "multistep_step", eps, x, x0_prev, model_in, coeffs, next_input_scale)
 
 
 def _known_region(who, x, known, mask, noise_known, level):
@@ -670,60 +670,26 @@ def known_blend(x, model_in, known, mask, noise_known, level, input_scale: float
 def cfg_sampler_step_known(eps2, x, noise, model_in2, guidance, coeffs, next_input_scale, known, mask, noise_known, level):
     """cfg_ddpm_step around known latents: after the update, x <- select(mask, x', a known + s noise_known) with level = (a, s)
     = <scheduler>.noise_level of the timestep the step lands on; model_in2 = fp16 of that x, both halves equal."""
-    _chk16(eps2, model_in2)
-    _chk32(noise)
-    n = x.numel()
-    if eps2.numel() != 2 * n or model_in2.numel() != 2 * n:
-        raise ValueError("cfg_sampler_step_known: eps2 / model_in2 must have twice as many elements as x")
-    k_x, k_e, c_x0, c_xt, sigma = coeffs
-    r = _known_region("cfg_sampler_step_known", x, known, mask, noise_known, level)
-    _lib.check(_lib.load().lavie_cfg_sampler_step_known(_p(eps2), _p(x), _p(noise), _p(model_in2), n, float(guidance), float(k_x),
-                                                        float(k_e), float(c_x0), float(c_xt), float(sigma),
-                                                        float(next_input_scale), _stream(), ctypes.byref(r)),
-               "lavie_cfg_sampler_step_known")
+    _step("lavie_cfg_sampler_step_known", "cfg_sampler_step_known", eps2, x, noise, model_in2, coeffs, next_input_scale,
+          guidance=guidance, region=(known, mask, noise_known, level))
 
 
 def sampler_step_known(eps, x, noise, model_in, coeffs, next_input_scale, known, mask, noise_known, level):
     """sampler_step (no guidance) around known latents; see cfg_sampler_step_known."""
-    _chk16(eps, model_in)
-    _chk32(noise)
-    n = x.numel()
-    if eps.numel() != n or model_in.numel() != n:
-        raise ValueError("sampler_step_known: eps / model_in must have as many elements as x")
-    k_x, k_e, c_x0, c_xt, sigma = coeffs
-    r = _known_region("sampler_step_known", x, known, mask, noise_known, level)
-    _lib.check(_lib.load().lavie_sampler_step_known(_p(eps), _p(x), _p(noise), _p(model_in), n, float(k_x), float(k_e),
-                                                    float(c_x0), float(c_xt), float(sigma), float(next_input_scale), _stream(),
-                                                    ctypes.byref(r)), "lavie_sampler_step_known")
+    _step("lavie_sampler_step_known", "sampler_step_known", eps, x, noise, model_in, coeffs, next_input_scale,
+          region=(known, mask, noise_known, level))
 
 
 def cfg_multistep_step_known(eps2, x, x0_prev, model_in2, guidance, coeffs, next_input_scale, known, mask, noise_known, level):
     """cfg_multistep_step around known latents; the history written is select(mask, x0, known): a pinned element's x0 is known."""
-    _chk16(eps2, model_in2)
-    _chk32(x0_prev)
-    n = x.numel()
-    if eps2.numel() != 2 * n or model_in2.numel() != 2 * n or x0_prev.numel() != n:
-        raise ValueError("cfg_multistep_step_known: eps2 / model_in2 must have twice, x0_prev as many elements as x")
-    k_x, k_e, c_x0, c_xt, c_prev = coeffs
-    r = _known_region("cfg_multistep_step_known", x, known, mask, noise_known, level)
-    _lib.check(_lib.load().lavie_cfg_multistep_step_known(_p(eps2), _p(x), _p(x0_prev), _p(model_in2), n, float(guidance),
-                                                          float(k_x), float(k_e), float(c_x0), float(c_xt), float(c_prev),
-                                                          float(next_input_scale), _stream(), ctypes.byref(r)),
-               "lavie_cfg_multistep_step_known")
+    _step("lavie_cfg_multistep_step_known", "cfg_multistep_step_known", eps2, x, x0_prev, model_in2, coeffs, next_input_scale,
+          guidance=guidance, region=(known, mask, noise_known, level))
 
 
 def multistep_step_known(eps, x, x0_prev, model_in, coeffs, next_input_scale, known, mask, noise_known, level):
     """multistep_step (no guidance) around known latents; see cfg_multistep_step_known."""
-    _chk16(eps, model_in)
-    _chk32(x0_prev)
-    n = x.numel()
-    if eps.numel() != n or model_in.numel() != n or x0_prev.numel() != n:
-        raise ValueError("multistep_step_known: eps / model_in / x0_prev must have as many elements as x")
-    k_x, k_e, c_x0, c_xt, c_prev = coeffs
-    r = _known_region("multistep_step_known", x, known, mask, noise_known, level)
-    _lib.check(_lib.load().lavie_multistep_step_known(_p(eps), _p(x), _p(x0_prev), _p(model_in), n, float(k_x), float(k_e),
-                                                      float(c_x0), float(c_xt), float(c_prev), float(next_input_scale), _stream(),
-                                                      ctypes.byref(r)), "lavie_multistep_step_known")
+    _step("lavie_multistep_step_known", "multistep_step_known", eps, x, x0_prev, model_in, coeffs, next_input_scale,
+          region=(known, mask, noise_known, level))
 
 
 def guidance_partials_floats(latents: int, per: int) -> int:
@@ -787,61 +753,27 @@ def guidance_table(eps2, latents, guidance, rescale, workspace=None, out=None, m
     return table
 
 
-def _scaled_operands(who, eps2, x, aux, model_in2, table):
-    """Checks shared by the `*_scaled` steps; returns (n, per)."""
-    _chk16(eps2, model_in2)
-    _chk32(x, aux, table)
-    n = x.numel()
-    if eps2.numel() != 2 * n or model_in2.numel() != 2 * n or (aux is not None and aux.numel() != n):
-        raise ValueError(f"{who}: eps2 / model_in2 must have twice, noise / x0_prev as many elements as x")
-    if table is None or tuple(table.shape) != (x.shape[0], 2) or table.device != x.device:
-        raise ValueError(f"{who}: table must be an fp32 tensor [{x.shape[0]}, 2] on {x.device}")
-    return n, n // x.shape[0]
-
-
 def cfg_sampler_step_scaled(eps2, x, noise, model_in2, table, coeffs, next_input_scale: float = 1.0):
     """cfg_ddpm_step with latent p's guidance scale and rescale factor read from table[p] (`guidance_table`): eps = f_p e.
     x [P, ...], noise and model_in2 are the plain step's operands, updated in place."""
-    n, per = _scaled_operands("cfg_sampler_step_scaled", eps2, x, noise, model_in2, table)
-    k_x, k_e, c_x0, c_xt, sigma = coeffs
-    _lib.check(_lib.load().lavie_cfg_sampler_step_scaled(_p(eps2), _p(x), _p(noise), _p(model_in2), n, _p(table), per, float(k_x),
-                                                         float(k_e), float(c_x0), float(c_xt), float(sigma),
-                                                         float(next_input_scale), _stream()), "lavie_cfg_sampler_step_scaled")
+    _step("lavie_cfg_sampler_step_scaled", "cfg_sampler_step_scaled", eps2, x, noise, model_in2, coeffs, next_input_scale, table=table)
 
 
 def cfg_multistep_step_scaled(eps2, x, x0_prev, model_in2, table, coeffs, next_input_scale: float = 1.0):
     """cfg_multistep_step with (guidance, rescale factor) per latent from `table`; see cfg_sampler_step_scaled."""
-    if x0_prev is None:
-        raise ValueError("cfg_multistep_step_scaled: x0_prev is needed")
-    n, per = _scaled_operands("cfg_multistep_step_scaled", eps2, x, x0_prev, model_in2, table)
-    k_x, k_e, c_x0, c_xt, c_prev = coeffs
-    _lib.check(_lib.load().lavie_cfg_multistep_step_scaled(_p(eps2), _p(x), _p(x0_prev), _p(model_in2), n, _p(table), per, float(k_x),
-                                                           float(k_e), float(c_x0), float(c_xt), float(c_prev),
-                                                           float(next_input_scale), _stream()), "lavie_cfg_multistep_step_scaled")
+    _step("lavie_cfg_multistep_step_scaled", "cfg_multistep_step_scaled", eps2, x, x0_prev, model_in2, coeffs, next_input_scale, table=table)
 
 
 def cfg_sampler_step_known_scaled(eps2, x, noise, model_in2, table, coeffs, next_input_scale, known, mask, noise_known, level):
     """cfg_sampler_step_known with (guidance, rescale factor) per latent from `table`; see cfg_sampler_step_scaled."""
-    n, _ = _scaled_operands("cfg_sampler_step_known_scaled", eps2, x, noise, model_in2, table)
-    k_x, k_e, c_x0, c_xt, sigma = coeffs
-    r = _known_region("cfg_sampler_step_known_scaled", x, known, mask, noise_known, level)
-    _lib.check(_lib.load().lavie_cfg_sampler_step_known_scaled(_p(eps2), _p(x), _p(noise), _p(model_in2), n, _p(table), float(k_x),
-                                                               float(k_e), float(c_x0), float(c_xt), float(sigma),
-                                                               float(next_input_scale), _stream(), ctypes.byref(r)),
-               "lavie_cfg_sampler_step_known_scaled")
+    _step("lavie_cfg_sampler_step_known_scaled", "cfg_sampler_step_known_scaled", eps2, x, noise, model_in2, coeffs, next_input_scale,
+          table=table, region=(known, mask, noise_known, level))
 
 
 def cfg_multistep_step_known_scaled(eps2, x, x0_prev, model_in2, table, coeffs, next_input_scale, known, mask, noise_known, level):
     """cfg_multistep_step_known with (guidance, rescale factor) per latent from `table`; see cfg_sampler_step_scaled."""
-    if x0_prev is None:
-        raise ValueError("cfg_multistep_step_known_scaled: x0_prev is needed")
-    n, _ = _scaled_operands("cfg_multistep_step_known_scaled", eps2, x, x0_prev, model_in2, table)
-    k_x, k_e, c_x0, c_xt, c_prev = coeffs
-    r = _known_region("cfg_multistep_step_known_scaled", x, known, mask, noise_known, level)
-    _lib.check(_lib.load().lavie_cfg_multistep_step_known_scaled(_p(eps2), _p(x), _p(x0_prev), _p(model_in2), n, _p(table), float(k_x),
-                                                                 float(k_e), float(c_x0), float(c_xt), float(c_prev),
-                                                                 float(next_input_scale), _stream(), ctypes.byref(r)),
-               "lavie_cfg_multistep_step_known_scaled")
+    _step("lavie_cfg_multistep_step_known_scaled", "cfg_multistep_step_known_scaled", eps2, x, x0_prev, model_in2, coeffs, next_input_scale,
+          table=table, region=(known, mask, noise_known, level))
 
 
 def window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, next_input_scale: float = 1.0, multistep: bool = False):

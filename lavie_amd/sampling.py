@@ -222,20 +222,22 @@ def step(eps, x, aux, model_in, guidance_scale, coeffs, next_scale, multistep: b
     computed from `eps` and the `_scaled` wrapper of the family reads it.  `region`: None, or (known, mask, known_noise, level) of
     a run around known latents.  The wrappers are looked up on `ops` at call time."""
     if isinstance(guidance_scale, GuidanceTable):
-        name = ("cfg_multistep_step" if multistep else "cfg_sampler_step") + ("_known" if region is not None else "") + "_scaled"
-        getattr(ops, name)(eps, x, aux, model_in, guidance_scale([eps]), coeffs, next_scale, *(region or ()))
-        return
-    guided = guidance_scale is not None
-    if multistep:
-        name = "cfg_multistep_step" if guided else "multistep_step"
-    elif region is not None:
-        name = "cfg_sampler_step" if guided else "sampler_step"
+        kind, guidance = "table", (guidance_scale([eps]),)
     else:
-        name = "cfg_ddpm_step" if guided else "sampler_step"     # lines 667, 679-683 fused
-    if region is not None:
-        name += "_known"
-    args = (eps, x, aux, model_in) + ((guidance_scale,) if guided else ()) + (coeffs, next_scale) + tuple(region or ())
-    getattr(ops, name)(*args)
+        kind, guidance = ("scalar", (guidance_scale,)) if guidance_scale is not None else ("none", ())
+    name = STEP_WRAPPERS[bool(multistep), kind, region is not None]
+    getattr(ops, name)(eps, x, aux, model_in, *guidance, coeffs, next_scale, *(region or ()))
+
+
+# (multistep, guidance kind, region) -> the `ops` wrapper of `step`
+STEP_WRAPPERS = {
+    (False, "none", False): "sampler_step",                 (False, "none", True): "sampler_step_known",
+    (False, "scalar", False): "cfg_ddpm_step",              (False, "scalar", True): "cfg_sampler_step_known",     # lines 667, 679-683 fused
+    (False, "table", False): "cfg_sampler_step_scaled",     (False, "table", True): "cfg_sampler_step_known_scaled",
+    (True, "none", False): "multistep_step",                (True, "none", True): "multistep_step_known",
+    (True, "scalar", False): "cfg_multistep_step",          (True, "scalar", True): "cfg_multistep_step_known",
+    (True, "table", False): "cfg_multistep_step_scaled",    (True, "table", True): "cfg_multistep_step_known_scaled",
+}
 
 
 def window_step(eps, x, aux, model_in, starts, profile, guidance_scale, coeffs, next_scale, multistep: bool):
