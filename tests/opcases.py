@@ -103,7 +103,8 @@ LINEAR_OPTIONS = ["plain", "bias_residual", "bias2", "residual_in_place"]
 
 
 @functools.lru_cache(maxsize=None)
-def linear_case(M, N, K, opt):
+def linear_case(M, N, K, opt, force=None):
+    """force: (tile mode, splits) forced around the launch, whatever the variant (splits = 1: unsplit where the cost rule would split)"""
     g = gen("linear", M, N, K, opt)
     a, w = rnd(g, M, K), rnd(g, N, K, s=1 / math.sqrt(K))
     ins = {"a": a, "w": w}
@@ -131,11 +132,13 @@ def linear_case(M, N, K, opt):
             y = y + p(cv(ins["r"]))
         return y
 
-    case = Case(f"linear[{M}x{N}x{K},{opt}]", ins, {"y": ((M, N), f16)}, run, lambda: {"y": (terms(d, False), terms(d, True))},
+    name = f"linear[{M}x{N}x{K},{opt}]" if force is None else f"linear[{M}x{N}x{K},{opt},f{force[0]},k{force[1]}]"
+    case = Case(name, ins, {"y": ((M, N), f16)}, run, lambda: {"y": (terms(d, False), terms(d, True))},
                 oc.gemm_c(K + 3), lambda: {"y": terms(lambda t: t.float(), False).half()}, oc.loc_rows(N),
-                alias={"y": "r"} if opt == "residual_in_place" else None)
+                alias={"y": "r"} if opt == "residual_in_place" else None,
+                setup=(lambda restore: forced(*force, restore)) if force is not None else None)
     return with_calls(case, [call("linear", lda=K, ldb2=N, rows_per_batch=rpb if "bias2" in ins else 0, ldr=N, ldc=N, M=M, N=N, K=K, geglu=0,
-                                  bias="bias" in ins, bias2="bias2" in ins, R="r" in ins)])
+                                  bias="bias" in ins, bias2="bias2" in ins, R="r" in ins)], force)
 
 
 def gelu64(x):
@@ -285,13 +288,29 @@ def lnfold_geglu_case(M, C):
 #                                                      workgroup's second tile (its first + 32) lies in another column tile and every aux piece differs between the two
 #  igemm_ppx_kernel<1, 4, 0> / <1, 4, 2>   geglu / lnfold_geglu 5120x320                         auto, ppx-persistent   32 x 10 = 320 tiles of 160x256; the automatic
 #                                                      rule counts 320-wide tiles for GEGLU too (ppx_shape: 32 x 8 = 256 >= 256), so M = 4160 (260 tiles) stays on the 128-row kernel
+#  at model depth (deep_cases(), PARITY_SPLIT_CASES; grids and split factors asserted from the trace by test_gemm_reach_host.py):
+#  case                                             variant                     kernel                                  splits
+#  parity 2x1280, 10x16                             auto                        igemm_patch_kernel<0, 5, 3> + reduce_cs  4 (planned; grid 8, 4, 4)
+#  parity 14x640, 10x16                             auto                        igemm_patch_kernel<0, 5, 3> + reduce_cs  2 (planned; grid 28, 2, 4)
+#  conv 1x192+128->320, 5x7 (nk 45), sc(192, 128) (nk 50)   the six variants    128-row gather <2, 2, 4, 5, 2, true, 0> / ping-pong gather <true, 0, 5>   1, 2, 3, automatic
+#  conv 1x192+128->320, 5x7, sc(192, 128)           forced 1 / 3                the same two kernels                    1, 3 (t_begin 16, 33), 10 (t_begin 45: the first shortcut tile), 25 (46, 48)
+#  conv 5x192+128->320, 8x8 and 1x..., 10x96        forced 5                   igemm_patch_kernel<0, 5, 0> / <0, 5, 1>  1, 2 ([0,2) [2,5)), 3 ([0,1) [1,3) [3,5)), 5
+#  linear 130x192x5120 bias_residual (80 K-tiles)   auto                        128-row kernel + reduce                 6 (the cost rule; ranges of 13 / 14 K-tiles)
+#  linear 640x1280x5120 bias_residual               auto                        128-row kernel + reduce                 5 (the cost rule, at the product's level-3 width)
+#  linear 160x320x5120 bias_residual                forced (1, 1) (3, 1) (7, 1) 128-row / ping-pong / persistent        1: one 80-tile K loop per kernel
+#  geglu 160x1280 (20 K-tiles, the family's longest in the model: C = 1280)   the six variants     GEGLU kernels        1
 #  TOO_LARGE: none
 BIG = ("auto", "ppx-persistent")
+# 80 K-tiles (K = 5120, the level-3 feed-forward output GEMM): (M, N, K, option, variants or None = all six)
+DEEP_LINEAR = [(130, 192, 5120, "bias_residual", None), (160, 320, 5120, "bias_residual", None), (640, 1280, 5120, "bias_residual", ("auto",))]
+DEEP_AUTO = ["linear[130x192x5120,bias_residual]", "linear[640x1280x5120,bias_residual]"]      # `auto` must plan more than 3 splits
+DEEP_UNSPLIT = [(1, 1), (3, 1), (7, 1)]                   # (tile mode, force_splits = 1) around linear 160x320x5120: one unsplit pass per kernel
 # (M, N, K, option, variants or None = all six)
 REACH_LINEAR = [(20640, 1280, 320, "bias_residual", BIG), (20640, 1280, 320, "residual_in_place", BIG), (20640, 1024, 320, "bias_residual", BIG), (20640, 640, 320, "plain", BIG),
                 (20640, 512, 320, "plain", BIG), (34721, 256, 640, "plain", ("auto",)), (2689, 512, 192, "bias_residual", None)]
 REACH_LNFOLD = [(160, 320, 320, None), (160, 256, 320, None), (320, 320, 320, None), (320, 256, 320, None), (13760, 960, 320, BIG), (20640, 512, 320, BIG)]
-REACH_GEGLU = [(160, 320, None), (2233, 512, ("auto",)), (5120, 320, BIG)]
+# (160, 1280): C = 1280 is the widest feed-forward of the model, K = 20 K-tiles: the longest K loop the GEGLU epilogue sees
+REACH_GEGLU = [(160, 320, None), (2233, 512, ("auto",)), (5120, 320, BIG), (160, 1280, None)]
 REACH_LNFOLD_GEGLU = [(129, 64, None), (154, 320, None), (160, 320, None), (2233, 512, ("auto",)), (5120, 320, BIG)]
 # tiles of the persistent kernel each past-the-cap case must have (name prefix -> (tile width, least tile count))
 PAST_CAP = {"linear[20640x1280x320,bias_residual]": (320, 513), "linear[20640x1280x320,residual_in_place]": (320, 513),
@@ -404,9 +423,10 @@ def lines_mask(n, h, w, c, ys, xs):
 @functools.lru_cache(maxsize=None)
 def conv_case(n, c1, cout, h, w, stride=1, ups=0, pad=None, c2=0, csc=0, extras=False, force=None, splits=0, parity=False):
     """extras: per-frame bias2 + residual (the halo-patch test's form); csc: fused 1x1 shortcut over two raw sources of csc
-    channels each + bias2 (the ResnetBlock3D form); force: (tile mode, splits) forced around the launch."""
+    channels each (or a pair (sc1, sc2) of unequal widths) + bias2 (the ResnetBlock3D form); force: (tile mode, splits) forced around the launch."""
     g = gen("conv", n, c1, cout, h, w, stride, ups, pad, c2, csc, extras, parity)
     cin = c1 + c2
+    csc1, csc2 = csc if isinstance(csc, tuple) else (csc, csc)      # (sc1, sc2): shortcut sources of unequal width
     x1 = rnd(g, n, c1, h, w)
     x2 = rnd(g, n, c2, h, w) if c2 else None
     wt = rnd(g, cout, cin, 3, 3, s=1 / math.sqrt(9 * cin))
@@ -416,8 +436,8 @@ def conv_case(n, c1, cout, h, w, stride=1, ups=0, pad=None, c2=0, csc=0, extras=
         ins["x2"] = rows(x2)
     s1 = s2 = ws = None
     if csc:
-        s1, s2 = rnd(g, n, csc, h, w), rnd(g, n, csc, h, w)
-        ws = rnd(g, cout, 2 * csc, 1, 1, s=1 / math.sqrt(2 * csc))
+        s1, s2 = rnd(g, n, csc1, h, w), rnd(g, n, csc2, h, w)
+        ws = rnd(g, cout, csc1 + csc2, 1, 1, s=1 / math.sqrt(csc1 + csc2))
         ins.update(s1=rows(s1), s2=rows(s2), ws=ws)
     probe = conv2d_any(torch.zeros(1, 1, h, w), torch.zeros(1, 1, 3, 3), None, stride, ups, pad)
     ho, wo = probe.shape[2:]
@@ -468,7 +488,7 @@ def conv_case(n, c1, cout, h, w, stride=1, ups=0, pad=None, c2=0, csc=0, extras=
             y = y + p(cv(res))
         return rows(y)
 
-    c = oc.gemm_c((4 if parity else 9) * cin + 2 * csc + 3)
+    c = oc.gemm_c((4 if parity else 9) * cin + csc1 + csc2 + 3)
     regions = {"border": border_mask(n, ho, wo, cout)}
     if parity:
         for py in (0, 1):
@@ -496,7 +516,7 @@ def conv_case(n, c1, cout, h, w, stride=1, ups=0, pad=None, c2=0, csc=0, extras=
     elif pad is not None:
         calls = [call("conv3x3_down", C=c1, NI=n, Hi=h, Wi=w, Cout=cout, stride=stride, pad_lo=pad[0], bias=1)]
     else:
-        calls = [call("conv3x3", C1=c1, C2=c2, SC1=csc, SC2=csc, ldb2=cout, rows_per_batch=rpb if "b2" in ins else 0, NI=n, Hi=h, Wi=w,
+        calls = [call("conv3x3", C1=c1, C2=c2, SC1=csc1, SC2=csc2, ldb2=cout, rows_per_batch=rpb if "b2" in ins else 0, NI=n, Hi=h, Wi=w,
                       Cout=cout, stride=stride, ups=ups, bias=1, bias2="b2" in ins, R="r" in ins, x2=bool(c2), sc1=bool(csc), sc2=bool(csc))]
     return with_calls(case, calls, (force, splits) if force is not None else None)
 
@@ -507,7 +527,43 @@ CONV_CASES = [dict(n=1, c1=64, cout=64, h=1, w=1), dict(n=1, c1=64, cout=64, h=3
               dict(n=1, c1=128, cout=128, h=13, w=18, stride=2, pad=(0, 1)), dict(n=1, c1=128, cout=128, h=2, w=2, stride=2, pad=(0, 1)),
               # the gathered ping-pong kernel (`pingpong`) and the 128-wide tile of the 128-row kernel (`split-k-3`): the reach table above
               dict(n=1, c1=64, cout=320, h=5, w=7), dict(n=1, c1=64, cout=512, h=52, w=52)]
-HALO_CASES = [dict(n=5, c1=64, cout=160, h=8, w=8, extras=True), dict(n=1, c1=64, cout=160, h=40, w=16, extras=True),
+# Two sources of unequal width, 192 + 128 channels = 3 + 2 slabs of 64 (the product's convs concatenate 1280 + 640, 640 + 320): with more
+# than one slab in a segment the (segment, slab, tap) cursor's slab-major, tap-minor order differs from its transpose, and a split-K
+# range can begin inside a segment that is not the first.  K-tiles: 27 + 18 (nk = 45), with the fused shortcut over 192 + 128 raw
+# channels 27 + 18 + 3 + 2 (nk = 50).  cout = 320: the 160-wide tile of the 128-row gather kernel, and the ping-pong gather kernel under
+# mode 3.  Where each split begins is computed by kloop_position and asserted by tests/test_gemm_reach_host.py.
+SEG = dict(n=1, c1=192, c2=128, cout=320, h=5, w=7)
+SEG_SC = dict(SEG, csc=(192, 128))
+CONV_CASES += [SEG, SEG_SC]                               # under the six variants; then forced (tile mode, splits): unsplit, 3 and 10 splits
+SEG_FORCED = [(t, s) for t in (1, 3) for s in (1, 3, 10, 25)]      # 25: ranges of 2 K-tiles, t_begin 46 and 48 inside the shortcut segments
+# the halo-patch kernel (9-tap segments only) over the same 3 + 2 slabs, split over whole slabs: whole-row tiles and 2-D tiles; unsplit
+# (force_splits = 1), [0,2) [2,5), [0,1) [1,3) [3,5), and one slab a range: [4,5) begins inside segment 1
+# (cout = 320, two 160-wide column tiles: the planner leaves N % 64 != 0 unsplit, so cout = 160 as in HALO_CASES would never split)
+HALO_SEG_CASES = [dict(n=5, c1=192, c2=128, cout=320, h=8, w=8, extras=True), dict(n=1, c1=192, c2=128, cout=320, h=10, w=96, extras=True)]
+HALO_SEG_SPLITS = (1, 2, 3, 5)
+
+
+def kloop_segments(ints):
+    """[(nchunks, ntaps)] of a conv3x3 call: its 9-tap sources, then its 1-tap shortcut sources, sources of 0 channels skipped
+    (igemm_setup_conv3x3)"""
+    return [(ints[k] // 64, taps) for k, taps in (("C1", 9), ("C2", 9), ("SC1", 1), ("SC2", 1)) if ints.get(k)]
+
+
+def kloop_position(segs, t):
+    """(segment, slab, tap) of K-tile t of the flattened K loop: segment-major, then slab-major, tap-minor (igemm.hip:138-148)"""
+    for i, (nchunks, ntaps) in enumerate(segs):
+        if t < nchunks * ntaps:
+            return i, t // ntaps, t % ntaps
+        t -= nchunks * ntaps
+    raise IndexError(t)
+
+
+def split_begins(nk, s):
+    """t_begin of each split-K range of nk K-tiles under s splits (igemm.hip:112)"""
+    return [nk * i // s for i in range(s)]
+
+
+HALO_CASES =[dict(n=5, c1=64, cout=160, h=8, w=8, extras=True), dict(n=1, c1=64, cout=160, h=40, w=16, extras=True),
               dict(n=1, c1=128, cout=256, h=20, w=128, extras=True), dict(n=2, c1=64, c2=64, cout=256, h=10, w=96, extras=True, splits=2),
               # the 128-wide tile on whole image rows and the 160-wide one on 10 x 32 tiles (the reach table above)
               dict(n=1, c1=64, cout=128, h=40, w=8, extras=True), dict(n=1, c1=64, cout=160, h=10, w=96, extras=True)]
@@ -515,6 +571,19 @@ HALO_CASES = [dict(n=5, c1=64, cout=160, h=8, w=8, extras=True), dict(n=1, c1=64
 # (2, 320, 10, 8) and (1, 320, 5, 8) are all refused (test_upsample_conv3x3_parity asserts it)
 PARITY_CASES = [(2, 320, 10, 16), (32, 320, 5, 8)]
 PARITY_REFUSED = [(2, 160, 10, 16), (1, 320, 10, 16), (2, 320, 5, 16), (2, 320, 10, 8), (1, 320, 5, 8)]
+# The parity form under split-K (igemm.hip plan_splits, the par_ups branch: wgs = source tiles x (C / 160) x 4 parities; 1 split from 218
+# workgroups, 2 where 2 wgs >= 218 and nchunks >= 10, else 4 where nchunks >= 20; force_splits does not apply), the smallest geometry of
+# each factor.  Both cases above have nchunks = 5 and run unsplit.  (n, c, h, w, splits the planner must choose):
+#  (2, 1280, 10, 16)   one 320-row source tile per parity, 1 x 8 x 4 = 32 workgroups, nchunks = 20 -> 4 splits (the base UNet's first
+#                      upsampler at 16 frames plans 4).  Reference in its 4-tap form: 1280 rows x 1280 x 5120 = 8.4e9 multiply-adds
+#  (14, 640, 10, 16)   7 source tiles, 7 x 4 x 4 = 112 workgroups (2 x 112 >= 218), nchunks = 10 -> 2 splits.  8960 rows x 640 x 2560 =
+#                      1.47e10 multiply-adds, under the 2^34 = 1.72e10 of TOO_LARGE
+# The reduce behind the launch writes the column statistics: 32-row contiguous blocks of output rows in ONE set, not four parity sets.
+PARITY_SPLIT_CASES = [(2, 1280, 10, 16, 4), (14, 640, 10, 16, 2)]
+
+
+def parity_case(n, c, h, w):
+    return conv_case(n=n, c1=c, cout=c, h=h, w=w, ups=1, parity=True)
 
 
 @functools.lru_cache(maxsize=None)
@@ -2301,6 +2370,16 @@ def reach_cases():
     return cs
 
 
+def deep_cases():
+    """The cases at model depth (tests/test_gpu_ops_local.py::test_deep_reduction_case): 80 K-tiles under the automatic split and unsplit
+    on each kernel; unequal multi-slab segments under forced splits, on the gather kernels and on the halo-patch kernel"""
+    cs = [restricted(linear_case(M, N, K, o), v) for M, N, K, o, v in DEEP_LINEAR]
+    cs += [linear_case(160, 320, 5120, "bias_residual", force=f) for f in DEEP_UNSPLIT]
+    cs += [conv_case(**SEG_SC, force=t, splits=s) for t, s in SEG_FORCED]
+    cs += [conv_case(**k, force=5, splits=s) for k in HALO_SEG_CASES for s in HALO_SEG_SPLITS]
+    return cs
+
+
 def gemm_family_cases():
     """Every case that describes its C-ABI calls: what gemm_reach replays (the halo-patch cases under both of their forced loops)"""
     cs = [c for c in all_cases() if c.calls]
@@ -2322,6 +2401,7 @@ def all_cases():
     cs += [conv_case(**k) for k in CONV_CASES]
     cs += [conv_case(**k, force=5) for k in HALO_CASES]            # force = 3 has the same model and reference
     cs += [conv_case(n=n, c1=c, cout=c, h=h, w=w, ups=1, parity=True) for n, c, h, w in PARITY_CASES]
+    cs += [restricted(parity_case(n, c, h, w), ("auto",)) for n, c, h, w, _ in PARITY_SPLIT_CASES] + deep_cases()
     cs += [temporal_conv_case(*s, t) for s in TCONV_SHAPES for t in (3, 5)] + [temporal_conv_case(*s, t, force=5) for s in TCONV_FORCED for t in (3, 5)]
     cs += [edge_in_case(*e, dt, tap) for e in EDGE_IN for dt in (f16, f32t) for tap in (False, True)]
     cs += [edge_out_case(*e, dt) for e in EDGE_OUT for dt in (f16, f32t)]
@@ -2385,6 +2465,8 @@ STATS_TABLE = [
     # the temporal gather on the 128-row kernel, unsplit and through the reduce; the parity form (four sets of source-row blocks)
     (lambda: temporal_conv_case(2, 64, 128, 8, 80, 3), "cs", ("auto", "split-k-3")), (lambda: temporal_conv_case(3, 128, 64, 2, 7, 5), "cs", ("auto",)),
 ] + [((lambda n=n, c=c, h=h, w=w: conv_case(n=n, c1=c, cout=c, h=h, w=w, ups=1, parity=True)), "cs", ("auto",)) for n, c, h, w in PARITY_CASES] + [
+    # the parity form under split-K: the reduce writes the statistics, 32-row blocks of output rows in one set
+    ((lambda n=n, c=c, h=h, w=w: parity_case(n, c, h, w)), "cs", ("auto",)) for n, c, h, w, _ in PARITY_SPLIT_CASES] + [
     # row statistics: each slot width (bn / 2 of the 128-row kernel: 32, 80, 64; bn / 4 of the ping-pong and persistent kernels: 80, 64)
     (_lin(130, 192, 64, "plain"), "rs", ("auto",)), (_lin(154, 320, 320, "bias_residual"), "rs", ("row128-tiles",)),
     (_lin(8193, 512, 64, "bias_residual"), "rs", ("auto",)), (_lin(161, 320, 320, "plain"), "rs", ("pingpong",)),

@@ -19,6 +19,8 @@ NAN32 = 0x7FC5A5A5           # fp32 quiet NaN with a recognisable payload
 SENTINEL = 12345.0           # the finite poison (fp16 stores it as 12344)
 BAND_BYTES = 64 * 1024       # a multiple of 512: the payload keeps the allocator's alignment
 
+WORST = {}                   # label -> worst observed |err| / bound of a whole-tensor check (reported, never read by an assertion)
+
 _INT = {torch.float16: torch.int16, torch.float32: torch.int32, torch.int32: torch.int32}
 _NAN = {torch.float16: NAN16, torch.float32: NAN32}
 
@@ -160,6 +162,8 @@ def assert_elementwise(got, ref64, scale64, c, where=None, label="", mask=None, 
     assert got.numel() == ref.numel() == scale.numel(), (got.numel(), ref.numel(), scale.numel())
     bound = u * ref.abs() + c * scale
     err = (got - ref).abs()
+    if mask is None and label and got.numel():
+        WORST[label] = max(WORST.get(label, 0.0), float((err / bound.clamp_min(1e-300)).nan_to_num(nan=math.inf).max()))
     bad = ~(err <= bound)                                            # a NaN in `got` is an offender
     if mask is not None:
         bad &= mask.reshape(-1)

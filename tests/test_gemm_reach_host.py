@@ -270,6 +270,92 @@ def test_reach_table_entries(reach):
     for n, c, h, w in C.PARITY_CASES:
         name = C.conv_case(n=n, c1=c, cout=c, h=h, w=w, ups=1, parity=True).name
         assert all(C.launch_name(reach[(name, v)][0]) == "igemm_patch_kernel<0, 5, 3>" for v in C.VARIANTS)
+        assert all(len(reach[(name, v)]) == 1 and C.launch_grid(reach[(name, v)][0]) == (n * h * w // 320 * (c // 160), 1, 4) for v in C.VARIANTS)    # unsplit
+    assert [s for *_, s in C.PARITY_SPLIT_CASES] == [4, 2]
+    for n, c, h, w, splits in C.PARITY_SPLIT_CASES:        # the planner's own factor (force_splits does not apply), then the reduce
+        case = C.parity_case(n, c, h, w)
+        assert case.variants == ("auto",)
+        lines = reach[(case.name, "auto")]
+        assert [C.launch_name(l) for l in lines] == ["igemm_patch_kernel<0, 5, 3>", "splitk_reduce_kernel"], (case.name, lines)
+        assert C.launch_grid(lines[0]) == (n * h * w // 320 * (c // 160), splits, 4), (case.name, lines)
+        assert c // 64 >= 5 * splits                        # nchunks: whole slabs per split, as many as the unsplit cases have in all
+        armed = reach[(case.name + "+cs", "auto")]           # with the sink armed: the same launch, the reduce with statistics behind it
+        assert [C.launch_name(l) for l in armed] == ["igemm_patch_kernel<0, 5, 3>", "splitk_reduce_cs_kernel"] and C.launch_grid(armed[0]) == C.launch_grid(lines[0])
+        (note,) = C.NOTES[(case.name + "+cs", "auto")]
+        plan = S.parse_stats_line(note)
+        assert (plan["splits"], plan["rows"], plan["span"], plan["sets"], plan["set_blocks"], plan["contiguous"]) == (splits, 32, 32, 1, 4 * n * h * w // 32, 1), plan
+
+
+def test_deep_k_linear_cases_split_by_the_cost_rule(reach):
+    """80 K-tiles: `auto` launches the 128-row kernel with the factor the planner's cost rule yields — more than the 3 any forced variant
+    reaches — over ranges of unequal length where nk % s != 0, the reduce behind it; the three forced cases run one unsplit 80-tile K
+    loop on the 128-row, the ping-pong and the persistent kernel; the GEGLU case runs 20 K-tiles on each GEGLU kernel."""
+    factors = {}
+    for name in C.DEEP_AUTO:
+        lines = reach[(name, "auto")]
+        assert [C.launch_name(l).split("<")[0] for l in lines] == ["igemm_kernel", "splitk_reduce_kernel"], (name, lines)
+        factors[name] = C.launch_grid(lines[0])[1]
+        assert factors[name] > 3, (name, lines)
+    assert 80 % factors[C.DEEP_AUTO[0]] != 0               # t_begin / t_end over ranges of unequal length
+    assert len(set(factors.values())) == 2, factors        # two different numbers of slabs under the fixed-order sum
+    assert factors == {C.DEEP_AUTO[0]: 6, C.DEEP_AUTO[1]: 5}, factors           # (what the trace shows today: 13 / 14 K-tiles and 16 a range)
+    wide = "linear[160x320x5120,bias_residual]"
+    pp = reach[(wide, "pingpong")]                          # the ping-pong kernel under the same automatic factor
+    assert C.launch_name(pp[0]) == "igemm_pp_kernel<false, 0, 5>" and C.launch_grid(pp[0])[1] > 3 and C.launch_name(pp[1]) == "splitk_reduce_kernel"
+    unsplit = {f: reach[(C.linear_case(160, 320, 5120, "bias_residual", force=f).name, "forced")] for f in C.DEEP_UNSPLIT}
+    assert all(len(l) == 1 and C.launch_grid(l[0])[1] == 1 for l in unsplit.values()), unsplit
+    assert [C.launch_name(l[0]) for l in unsplit.values()] == ["igemm_kernel<2, 2, 4, 5, 2, false, 0>", "igemm_pp_kernel<false, 0, 5>", "igemm_ppx_kernel<0, 5, 1>"]
+    geglu = {v: [C.launch_name(l) for l in reach[("geglu[160x1280]", v)]] for v in C.VARIANTS}
+    assert {k[0] for k in geglu.values()} == {"igemm_kernel<2, 2, 4, 4, 2, false, 1>", "igemm_pp_kernel<false, 1, 4>", "igemm_ppx_kernel<1, 4, 0>"} and all(len(k) == 1 for k in geglu.values())
+
+
+def test_forced_splits_begin_inside_segments(reach):
+    """Where each split-K range of the 192 + 128 cases begins, from nk, the segment table of the call and the factor (the kernels'
+    cursor arithmetic, opcases.kloop_position), and the factor itself from the grid of the trace."""
+    sc = C.conv_case(**C.SEG_SC)
+    segs = C.kloop_segments(sc.calls[0][1])
+    assert segs == [(3, 9), (2, 9), (3, 1), (2, 1)]
+    nk = sum(a * b for a, b in segs)
+    assert nk == 50 and C.kloop_segments(C.conv_case(**C.SEG).calls[0][1]) == [(3, 9), (2, 9)]
+    begins = set()
+    for tile, s in C.SEG_FORCED:
+        case = C.conv_case(**C.SEG_SC, force=tile, splits=s)
+        lines = reach[(case.name, "forced")]
+        kernel = {1: "igemm_kernel<2, 2, 4, 5, 2, true, 0>", 3: "igemm_pp_kernel<true, 0, 5>"}[tile]
+        assert C.launch_name(lines[0]) == kernel and C.launch_grid(lines[0])[1] == s, (case.name, lines)
+        assert [C.launch_name(l) for l in lines[1:]] == (["splitk_reduce_kernel"] if s > 1 else []), (case.name, lines)
+        assert case.calls == sc.calls
+        begins |= {(tile, C.kloop_position(segs, t)) for t in C.split_begins(nk, s)[1:]}
+    for tile in (1, 3):
+        at = [p for t, p in begins if t == tile]
+        assert any(seg == 0 and slab >= 1 and tap > 0 for seg, slab, tap in at), at          # inside segment 0, past its first slab, not at a slab's first tap
+        assert any(seg == 1 and (slab, tap) != (0, 0) for seg, slab, tap in at), at           # inside segment 1
+        assert any(seg == 1 and slab >= 1 and tap > 0 for seg, slab, tap in at), at           # ... and inside its second slab
+        assert (2, 0, 0) in at and any(seg == 2 and slab > 0 for seg, slab, tap in at) and any(seg == 3 for seg, slab, tap in at), at    # at and inside the shortcuts
+    assert [C.kloop_position(segs, t) for t in C.split_begins(nk, 3)] == [(0, 0, 0), (0, 1, 7), (1, 0, 6)]
+    assert [C.kloop_position(segs, t) for t in C.split_begins(nk, 10)][6:] == [(1, 0, 3), (1, 0, 8), (1, 1, 4), (2, 0, 0)]
+    # the same operands under the six variants: whatever factor the variant yields, the launch is the gather kernel it names
+    for v, (tile, s) in C.VARIANTS.items():
+        lines = reach[(sc.name, v)]
+        assert C.launch_name(lines[0]) in ("igemm_kernel<2, 2, 4, 5, 2, true, 0>", "igemm_kernel<2, 2, 4, 2, 2, true, 0>", "igemm_pp_kernel<true, 0, 5>"), (v, lines)
+        assert not s or C.launch_grid(lines[0])[1] == s
+    # the halo-patch kernel splits over whole slabs (igemm_patch.hip:90-91): 5 slabs of 9 taps
+    assert [[5 * i // s for i in range(s + 1)] for s in C.HALO_SEG_SPLITS] == [[0, 5], [0, 2, 5], [0, 1, 3, 5], [0, 1, 2, 3, 4, 5]]
+    for kw, kernel in zip(C.HALO_SEG_CASES, ("igemm_patch_kernel<0, 5, 0>", "igemm_patch_kernel<0, 5, 1>")):
+        for s in C.HALO_SEG_SPLITS:
+            case = C.conv_case(**kw, force=5, splits=s)
+            hsegs = C.kloop_segments(case.calls[0][1])
+            assert hsegs == [(3, 9), (2, 9)]
+            lines = reach[(case.name, "forced")]
+            assert C.launch_name(lines[0]) == kernel and C.launch_grid(lines[0])[1] == s and len(lines) == (2 if s > 1 else 1), (case.name, lines)
+            starts = [C.kloop_position(hsegs, 9 * (5 * i // s)) for i in range(s)]
+            assert all(tap == 0 for _, _, tap in starts)
+            if s == 2:
+                assert starts == [(0, 0, 0), (0, 2, 0)]      # the second range begins inside segment 0 and crosses into segment 1
+            if s == 3:
+                assert starts == [(0, 0, 0), (0, 1, 0), (1, 0, 0)] and 5 * 2 // 3 == 3     # [1, 3) crosses the boundary; [3, 5) is segment 1
+            if s == 5:
+                assert starts[4] == (1, 1, 0)                # a range that begins inside segment 1 (no factor below 5 has one)
 
 
 def epi_linear(name):
@@ -299,7 +385,8 @@ def test_every_linear_instantiation_is_reached_with_column_statistics(reach):
             reduce_behind.add(ks[0])
     assert linear - with_cs - set(C.NO_COLSTAT) == set(), sorted(linear - with_cs - set(C.NO_COLSTAT))
     assert not (set(C.NO_COLSTAT) & with_cs) and set(C.NO_COLSTAT) <= linear and all(len(r) > 20 for r in C.NO_COLSTAT.values())
-    assert {"igemm_kernel<2, 2, 4, 4, 2, false, 0>", "igemm_kernel<2, 2, 4, 4, 2, true, 0>", "igemm_patch_kernel<0, 4, 1>"} <= reduce_behind
+    assert {"igemm_kernel<2, 2, 4, 4, 2, false, 0>", "igemm_kernel<2, 2, 4, 4, 2, true, 0>", "igemm_patch_kernel<0, 4, 1>",
+            "igemm_patch_kernel<0, 5, 3>"} <= reduce_behind
     # row statistics: each kernel family, each slot width the planner yields
     rs = {}
     for key, launches in reach.items():

@@ -99,6 +99,36 @@ def test_upsample_conv3x3_parity(ops, n, c, h, w):
     check(ops, C.conv_case(n=n, c1=c, cout=c, h=h, w=w, ups=1, parity=True))
 
 
+@pytest.mark.parametrize("n,c,h,w,splits", C.PARITY_SPLIT_CASES)
+def test_upsample_conv3x3_parity_split(n, c, h, w, splits):
+    """the parity form under the split-K factor its planner chooses (force_splits does not apply to it: one run, not six): fp32 slabs
+    written from four parities, then the fixed-order reduce; y per element, the parity{py}{px}, border and seam regions on their own"""
+    assert torch.cuda.is_available(), "gpu tests need a HIP device"
+    from lavie_amd import _lib, ops as o
+    assert _lib.load().lavie_upsample_conv3x3_supported(n, h, w, c) == 1
+    case = C.parity_case(n, c, h, w)
+    assert {"parity00", "parity01", "parity10", "parity11", "border", "seams"} <= set(case.regions)
+    with o.op_statistics(plan=(True, False)):            # the plan of this launch, from the library: nothing is launched
+        case.run(o, {k: v.cuda() for k, v in case.inputs.items()}, {"y": torch.empty(case.outputs["y"][0], dtype=torch.float16, device="cuda")})
+    assert o.op_statistics.last()["splits"] == splits
+    check_local(case)
+
+
+def deep_runs():
+    """(case, variant, (tile, splits)) of opcases.deep_cases(): the forced cases under their own mode, the others under their variants"""
+    return [pytest.param(c, v, fs, id=f"{c.name}-{v}") for c, v, fs in C.gemm_runs(C.deep_cases())]
+
+
+@pytest.mark.parametrize("case,variant,fs", deep_runs())
+def test_deep_reduction_case(case, variant, fs):
+    """80 K-tiles under the automatic split-K factor and unsplit on each kernel; 3 + 2 slab segments with forced splits that begin inside
+    a segment and at the shortcut segments (tests/test_gemm_reach_host.py asserts factor, grid and where each split begins)"""
+    assert torch.cuda.is_available(), "gpu tests need a HIP device"
+    from lavie_amd import ops as o
+    with C.forced(*fs, tuple(_forced)):
+        oc.check_case(o, case, forced=fs, sync=torch.cuda.synchronize)
+
+
 @pytest.mark.parametrize("taps", [3, 5])
 @pytest.mark.parametrize("b,cin,cout,f,d", C.TCONV_SHAPES)
 def test_temporal_conv(ops, b, cin, cout, f, d, taps):
@@ -261,3 +291,15 @@ def test_sampler_steps(ops, kind, n):
 @pytest.mark.parametrize("N,K,r", C.LORA_SHAPES)
 def test_lora_merge(ops, N, K, r, in_place):
     check(ops, C.lora_case(N, K, r, in_place))
+
+
+def test_worst_fractions_at_model_depth_are_reported(capsys):
+    """runs last in this file: prints the worst observed |err| / bound of every case at model depth that ran (opcheck.WORST; nothing is
+    asserted on it beyond what each check above already did)"""
+    new = {c.name for c in C.deep_cases()} | {C.parity_case(*s[:4]).name for s in C.PARITY_SPLIT_CASES}
+    new |= {C.conv_case(**C.SEG).name, C.conv_case(**C.SEG_SC).name, C.geglu_case(160, 1280).name}
+    seen = {k: v for k, v in oc.WORST.items() if k.rsplit(":", 1)[0] in new}
+    with capsys.disabled():
+        for k, v in sorted(seen.items()):
+            print(f"\nworst fraction of bound: {k}: {v:.3f}", end="")
+    assert all(v <= 1.0 for v in seen.values())

@@ -7,6 +7,7 @@ import re
 
 import pytest
 import torch
+import torch.nn.functional as F
 
 import opcases as C
 import opcheck as oc
@@ -268,6 +269,107 @@ def test_attention_far_below_rows_never_rescaled(far_below, n_rows):
     bad_tokens = (~((bad.double() - case.ref["y"][0]).abs() <= oc.U16 * case.ref["y"][0].abs() + case.c * case.ref["y"][1])).any(1).nonzero().flatten().tolist()
     assert bad_tokens == rows, bad_tokens                       # the hard rows and nothing else
     assert rel_l2(bad, case.ref["y"][0]) > 100 * TOL_OP
+
+
+# ------------------------------------------------------------------ split-K and multi-slab segments at model depth
+def nchw(rows_, n, h, w):
+    return rows_.reshape(n, h, w, -1).permute(0, 3, 1, 2).to(torch.float64)
+
+
+def ktile_term(x, wt, c_off, a_slab, a_tap, w_slab, w_tap):
+    """One K-tile of a 3x3 conv as rows [n h w, cout], float64: the 64 channels of slab `a_slab` of source x [n, c, h, w] read at tap
+    `a_tap` (ky * 3 + kx, zeros outside the image), times the weights wt[:, c_off + 64 w_slab ..., w_tap]."""
+    n, _, h, w = x.shape
+    dy, dx = a_tap // 3 - 1, a_tap % 3 - 1
+    xs = F.pad(x[:, 64 * a_slab:64 * a_slab + 64], (1, 1, 1, 1))[:, :, 1 + dy:1 + dy + h, 1 + dx:1 + dx + w]
+    wk = wt[:, c_off + 64 * w_slab:c_off + 64 * w_slab + 64, w_tap // 3, w_tap % 3].to(torch.float64)
+    return torch.einsum("nchw,oc->nhwo", xs, wk).reshape(n * h * w, -1)
+
+
+def rejected(case, bad64):
+    with pytest.raises(AssertionError, match="outside the bound"):
+        case.check({"y": bad64.half()})
+    return offenders(case, bad64.half())
+
+
+def test_split_k_range_without_its_first_k_tile():
+    """conv 192 + 128 with both shortcuts under 3 splits: the second range begins at K-tile 16 = (segment 0, slab 1, tap 7).  A cursor that
+    starts one tile late (or a prologue that never issues tile t_begin) leaves that tile's products out: every output with that
+    neighbour inside the image is off."""
+    case = C.conv_case(**C.SEG_SC, force=1, splits=3)
+    ints = case.calls[0][1]
+    segs = C.kloop_segments(ints)
+    assert C.kloop_position(segs, C.split_begins(50, 3)[1]) == (0, 1, 7)
+    x1 = nchw(case.inputs["x1"], 1, 5, 7)
+    ref = case.ref["y"][0]
+    case.check({"y": ref.half()})
+    off = rejected(case, ref - ktile_term(x1, case.inputs["wt"], 0, 1, 7, 1, 7))
+    pix = off.reshape(5, 7, -1)
+    assert pix[:4].any(-1).all() and pix[:4].float().mean() > 0.5 and not pix[4].any()      # tap 7 = (dy +1, dx 0): the bottom row has no such neighbour
+
+
+def transposed_segment_1(case, n, h, w, c1, c2):
+    """The reference with segment 1 (the second 9-tap source) gathered tap-major, slab-minor against weights packed slab-major,
+    tap-minor: K-tile j of the segment reads (tap j // nslab, slab j % nslab) where the weights hold (slab j // 9, tap j % 9)."""
+    x2, wt, nslab = nchw(case.inputs["x2"], n, h, w), case.inputs["wt"], c2 // 64
+    bad = case.ref["y"][0].clone()
+    for j in range(9 * nslab):
+        bad -= ktile_term(x2, wt, c1, j // 9, j % 9, j // 9, j % 9)
+        bad += ktile_term(x2, wt, c1, j % nslab, j // nslab, j // 9, j % 9)
+    return bad
+
+
+def test_slab_and_tap_order_transposed_within_the_second_segment():
+    """Caught at the 192 + 128 cases, split or not; NOT caught by the 64 + 64 case the suite had, whose segments are one slab each:
+    there the transposed order is the same order, and the defective reference is the reference."""
+    for case in (C.conv_case(**C.SEG_SC, force=1, splits=1), C.conv_case(**C.SEG)):
+        off = rejected(case, transposed_segment_1(case, 1, 5, 7, 192, 128))
+        assert off.float().mean() > 0.9
+    old = C.conv_case(n=2, c1=64, c2=64, cout=64, h=3, w=5, csc=64)
+    assert old in [C.conv_case(**k) for k in C.CONV_CASES]
+    same = transposed_segment_1(old, 2, 3, 5, 64, 64)
+    assert float((same - old.ref["y"][0]).abs().max()) <= 1e-12 * float(old.ref["y"][0].abs().max())
+    old.check({"y": same.half()})                           # passes: the old case cannot tell the two orders apart
+
+
+@pytest.fixture(scope="module")
+def parity4():
+    n, c, h, w, splits = C.PARITY_SPLIT_CASES[0]
+    assert splits == 4
+    return C.parity_case(n, c, h, w), (n, c, h, w)
+
+
+def test_reduce_that_leaves_out_one_of_four_slabs(parity4):
+    """The 4-split parity case: slab 3 holds the products of slabs 15..19 of the source = channels 960..1279.  A reduce that sums three
+    slabs (a slab stride or a loop bound off by one) leaves them out of every output element."""
+    case, (n, c, h, w) = parity4
+    x = nchw(case.inputs["x1"], n, h, w).float()
+    up = x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+    lo = c - c // 4
+    part = C.rows(F.conv2d(up[:, lo:], case.inputs["wt"][:, lo:].float(), padding=1)).to(torch.float64)
+    ref = case.ref["y"][0]
+    case.check({"y": ref.half()})
+    off = rejected(case, ref - part)
+    assert off.float().mean() > 0.9
+    for r in ("parity00", "parity01", "parity10", "parity11"):       # and each parity region names it on its own
+        with pytest.raises(AssertionError, match=":" + r):
+            oc.assert_elementwise((ref - part).half(), *case.ref["y"], case.c, where=case.where, label="x:" + r, mask=case.regions[r])
+
+
+def test_parity_split_statistics_as_four_sets_instead_of_one(parity4):
+    """Behind a split parity launch the reduce writes 32-row blocks of output rows in one set.  The unsplit parity kernel's layout
+    — four sets, one per output parity — fills a buffer of the same size with other sums: rejected by check_colstat."""
+    import statcheck as S
+    case, (n, c, h, w) = parity4
+    y = case.ref["y"][0].half()
+    M = y.shape[0]
+    plan = {"rows": 32, "span": 32, "sets": 1, "set_blocks": M // 32, "contiguous": 1, "blocks_stored": M // 32, "cs_floats": M // 32 * 2 * c}
+    S.check_colstat(y, S.model_colstat(y, plan), plan)
+    four = dict(plan, sets=4, set_blocks=M // 4 // 32)
+    bad = S.model_colstat(y, four, parity=(2 * h, 2 * w))
+    assert bad.numel() == plan["cs_floats"]
+    with pytest.raises(AssertionError, match="span sums"):
+        S.check_colstat(y, bad, plan)
 
 
 # ------------------------------------------------------------------ the persistent kernel past its first tile

@@ -24,16 +24,23 @@ def plan_of(reach, case, variant):
     return S.parse_stats_line(line)
 
 
+PARITY_SPLIT = {C.parity_case(n, c, h, w).name + "+cs" for n, c, h, w, _ in C.PARITY_SPLIT_CASES}
+
+
 def small(case):
     (M, N), _ = case.outputs["y"]
-    return M * N <= 3_000_000
+    return M * N <= 3_000_000 or case.name in PARITY_SPLIT          # (the 2-split parity case has 5.7e6 outputs: modelled all the same)
 
 
 def test_host_model_meets_every_bound(reach):
     """every statistics case whose output is small: the fp32 model of C, its fp32 block / slot sums, checked like the kernel's"""
-    n = 0
+    n, split_parity = 0, []
     for c, v, _ in C.gemm_runs(C.stats_cases()):
         plan = plan_of(reach, c, v)
+        if c.name in PARITY_SPLIT:      # the reduce behind the parity launch: 32-row contiguous blocks of OUTPUT rows in one set, not four parity sets
+            assert (plan["rows"], plan["span"], plan["sets"], plan["contiguous"], plan["set_blocks"]) == (32, 32, 1, 1, plan["M"] // 32), (c.name, plan)
+            assert plan["splits"] == {C.parity_case(*s[:4]).name + "+cs": s[4] for s in C.PARITY_SPLIT_CASES}[c.name] and c.parity is not None
+            split_parity.append(c.name)
         assert plan["colstat"] == ("cs" in c.kind) and plan["rowstat"] == ("rs" in c.kind) and plan["splits"] >= 1, (c.name, v, plan)
         if plan["colstat"]:
             assert plan["set_blocks"] == (-(-plan["M"] // plan["rows"]) if plan["sets"] == 1 else plan["M"] // 4 // plan["rows"]), plan
@@ -47,7 +54,7 @@ def test_host_model_meets_every_bound(reach):
         if plan["rowstat"]:
             S.check_rowstat(y, S.model_rowstat(y, plan), plan, label=c.name)
             n += 1
-    assert n >= 30
+    assert n >= 32 and sorted(split_parity) == sorted(PARITY_SPLIT)
 
 
 def test_armed_row_statistics_plan_an_unsplit_launch(reach):
