@@ -507,6 +507,32 @@ int lavie_cfg_multistep_step_known_scaled(const void* eps2, float* x, float* x0_
 int lavie_window_step_scaled(const lavie_window_step_args* args, const float* table, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Perturbed-attention guidance (PAG: Ahn et al., "Self-Rectifying Diffusion Sampling with Perturbed-Attention Guidance"; diffusers'
+ * AnimateDiffPAGPipeline) inside the fused step (sampler_pag.hip; additive in ABI 8).  The four steps carry the arguments of their
+ * plain namesakes plus `pag_scale`, and eps / model_in hold one part more, the perturbed prediction last: fp16 [3, n] = [negative |
+ * prompt | perturbed] for the cfg_ entries, [2, n] = [prompt | perturbed] for the others (the output of ONE forward whose trailing
+ * batch entries ran under lavie_unet_set_pag).  Per element, fp32, every fused multiply-add spelled out:
+ *   e   = cfg ? fma(guidance, ec - eu, eu) : ec
+ *   eps = pag_scale != 0 ? fma(pag_scale, ec - ep, e) : e        (pag_scale == 0: the perturbed part is not read)
+ *   then the family's plain step unchanged: x <- x' in place (multistep: x0_prev <- x0), and the family's rounding of
+ *   x' * next_input_scale as ONE fp16 value written to all three (two) parts of model_in.
+ * pag_scale == 0 gives the bits of the plain namesake; ep == ec gives its values.  Eight elements per lane with 16-byte accesses
+ * when n % 8 == 0 (eps, x, the noise that is read / x0_prev, model_in must then be 16-byte aligned: every part is), else one element
+ * per lane with the same arithmetic.  No atomics, no host synchronisation, no allocation: safe inside a stream capture.
+ * Refused with a message naming the argument, nothing launched: a null tensor, n < 1, a non-finite scalar, pag_scale < 0, a
+ * misaligned tensor in the eight-element form.
+ * PAG is not combined with the known-region (_known), frame-window (lavie_window_step) or table (_scaled) forms. */
+int lavie_cfg_pag_sampler_step(const void* eps3, float* x, const float* noise, void* model_in3, long long n, float guidance, float k_x,
+                               float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale, float pag_scale, void* stream);
+int lavie_pag_sampler_step(const void* eps2, float* x, const float* noise, void* model_in2, long long n, float k_x, float k_eps, float c_x0,
+                           float c_xt, float sigma, float next_input_scale, float pag_scale, void* stream);
+int lavie_cfg_pag_multistep_step(const void* eps3, float* x, float* x0_prev, void* model_in3, long long n, float guidance, float k_x,
+                                 float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale, float pag_scale,
+                                 void* stream);
+int lavie_pag_multistep_step(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, float k_x, float k_eps, float c_x0,
+                             float c_xt, float c_prev, float next_input_scale, float pag_scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Measurement hook: HIP-event timing per kernel class on the launch stream (bench.py's roofline leg).
  * Classes: 0 conv3x3 (implicit GEMM, gathered), 1 linear/1x1/GEGLU GEMM, 2 spatial+text attention core,
  * 3 temporal attention core, 4 GroupNorm, 5 LayerNorm, 6 other, 7 the halo-patch conv kernel alone (a subset of
@@ -666,6 +692,21 @@ int lavie_unet_set_ln_fold(lavie_unet_t h, int on);
  * (1, 1, 1, 1), the default, is the plain forward, bit for bit.  Every value must be finite and > 0: otherwise an error and no change.
  * Holds for every forward that follows, eager or captured (a change re-captures); it needs no new workspace after lavie_unet_prepare. */
 int lavie_unet_set_freeu(lavie_unet_t h, float s1, float s2, float b1, float b2);
+/* Perturbed-attention guidance inside the forward (additive in ABI 8; the handle must be finalized).  `layers_host`: n_layers
+ * prefixes of transformer names as the state dict spells them ("mid_block", "down_blocks.2", "up_blocks.1.attentions.0", ...): a
+ * transformer is selected when its prefix (mid_block.attentions.0, ...) starts with an entry followed by '.' or the end of the name.
+ * `perturbed`: the number of TRAILING batch entries whose attn1 is perturbed in the selected blocks, in every forward that follows:
+ * there attn1(x) = to_out(to_v(norm1(x))), the identity map on values, no softmax (the q|k|v projection runs on all rows, the
+ * attention kernel on the leading (B - perturbed) F frames, the perturbed rows receive the V columns through a strided row copy;
+ * to_out and everything behind it are unchanged).  n_layers == 0 or perturbed == 0 switches it off (the default): off is the plain
+ * forward, launch for launch and bit for bit.  Refused with a message naming the argument, nothing changed: an entry that selects no
+ * transformer; a selected transformer whose attn1 is not the plain spatial self-attention (the interpolation model's sparse-causal
+ * blocks, the VSR model's only_cross_attention levels); perturbed < 0.  A forward (or lavie_unet_transformer_forward) with
+ * B <= perturbed is refused.  While it is on, lavie_unet_set_cfg_shared_input(1) is ignored (plain forward: this is where the shared
+ * input does not apply; letting the perturbed entries share the down path with their prompt twins is not implemented).  Holds on
+ * every kernel route, eager or captured (a change re-captures); it needs no new workspace after lavie_unet_prepare.  With B <= 8 a
+ * forward serves at most 2 prompts as [negative | prompt | perturbed], 4 as [prompt | perturbed]. */
+int lavie_unet_set_pag(lavie_unet_t h, const char* const* layers_host, int n_layers, int perturbed);
 /* Classifier-free guidance (pipeline_videogen.py:666: `torch.cat([latents] * 2)`) runs the UNet on the SAME latents twice with
  * different text.  on = 1: the caller vouches that sample[b] == sample[b + B/2] for every b < B/2 (B even) in the forwards that
  * follow; the layers in front of the first text cross-attention (conv_in, down_blocks.0.resnets.0, and the GroupNorm / proj_in /

@@ -178,6 +178,14 @@ SIGNATURES = {
     "lavie_cfg_multistep_step_known_scaled": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float_p, c_float, c_float,
                                                        c_float, c_float, c_float, c_float, c_void_p, C.POINTER(KnownRegionC)]),
     "lavie_window_step_scaled": (c_int, [C.POINTER(WindowStepArgsC), c_float_p, c_void_p]),
+    "lavie_cfg_pag_sampler_step": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float,
+                                            c_float, c_float, c_float, c_void_p]),
+    "lavie_pag_sampler_step": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float,
+                                        c_float, c_float, c_void_p]),
+    "lavie_cfg_pag_multistep_step": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float,
+                                              c_float, c_float, c_float, c_void_p]),
+    "lavie_pag_multistep_step": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float,
+                                          c_float, c_float, c_void_p]),
     "lavie_debug_force_tile": (c_int, [c_int]),
     "lavie_debug_force_splits": (c_int, [c_int]),
     "lavie_debug_fused_mask": (c_int, [c_int]),
@@ -212,6 +220,7 @@ SIGNATURES = {
     "lavie_unet_lora_set_slot_weight": (c_int, [c_void_p, c_int, c_float]),
     "lavie_unet_set_cfg_shared_input": (c_int, [c_void_p, c_int]),
     "lavie_unet_set_freeu": (c_int, [c_void_p, c_float, c_float, c_float, c_float]),
+    "lavie_unet_set_pag": (c_int, [c_void_p, C.POINTER(c_char_p), c_int, c_int]),
     "lavie_unet_weight_bytes": (c_ll, [c_void_p]),
     "lavie_unet_workspace_bytes": (c_ll, [c_void_p]),
     "lavie_unet_forward": (c_int, [c_void_p, c_void_p, c_float_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -45,7 +45,9 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
                           interp_frames: int = 61, interp_cfg_scale: float = 4.0, vsr_steps: int = 50,
                           vsr_guidance_scale: float = 7.5, noise_level: int = 150, generator=None, decode_final: bool = True,
                           base_scheduler=None, vsr_scheduler=None, vsr_overlap: int = 0, base_guidance_rescale: float = 0.0,
-                          vsr_guidance_rescale: float = 0.0, base_freeu: Optional[dict] = None, vsr_freeu: Optional[dict] = None):
+                          vsr_guidance_rescale: float = 0.0, base_freeu: Optional[dict] = None, vsr_freeu: Optional[dict] = None,
+                          base_pag_scale: float = 0.0, base_pag_adaptive_scale: float = 0.0,
+                          base_pag_applied_layers=("mid_block",)):
     """Returns (base_latents, interp_latents, vsr_latents, frames or None).  Text embeddings are passed per stage (the base
     and interpolation stages use SD-1.4's CLIP, 768 wide; the VSR stage the x4-upscaler's, 1024 wide).
     `base_scheduler` / `vsr_scheduler` replace the two diffusers-style stages' schedulers for this call (for instance a
@@ -56,7 +58,9 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
     `base_guidance_rescale` / `vsr_guidance_rescale`: the `guidance_rescale` of the two diffusers-style stages (0 = off).  The
     interpolation stage's own guidance loop (`forward_with_cfg`) has no such switch.
     `base_freeu` / `vsr_freeu`: dict(s1=, s2=, b1=, b2=) for `enable_freeu` on that stage's UNet during this call; the UNet gets the
-    setting it had back afterwards.  None = the UNet's own setting."""
+    setting it had back afterwards.  None = the UNet's own setting.
+    `base_pag_scale` / `base_pag_adaptive_scale` / `base_pag_applied_layers`: perturbed-attention guidance in the base stage (the
+    keywords of `VideoGenPipeline.__call__`; 0 = off, the calls without them).  The other two stages have no such switch."""
     freeu_was = [(pipe.unet, pipe.unet.freeu) for pipe, fu in ((base_pipe, base_freeu), (vsr_pipe, vsr_freeu)) if fu is not None]
     swapped = [(pipe, pipe.scheduler) for pipe, sch in ((base_pipe, base_scheduler), (vsr_pipe, vsr_scheduler)) if sch is not None]
     if base_scheduler is not None:
@@ -70,7 +74,9 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
         return _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, prompt_embeds, negative_prompt_embeds,
                         vsr_prompt_embeds, vsr_negative_prompt_embeds, interp_prompt_embeds, interp_negative_prompt_embeds, height,
                         width, base_steps, guidance_scale, interp_frames, interp_cfg_scale, vsr_steps, vsr_guidance_scale,
-                        noise_level, generator, decode_final, vsr_overlap, base_guidance_rescale, vsr_guidance_rescale)
+                        noise_level, generator, decode_final, vsr_overlap, base_guidance_rescale, vsr_guidance_rescale,
+                        dict(pag_scale=base_pag_scale, pag_adaptive_scale=base_pag_adaptive_scale,
+                             pag_applied_layers=base_pag_applied_layers) if base_pag_scale else {})
     finally:
         for pipe, own in swapped:
             pipe.scheduler = own
@@ -81,9 +87,10 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
 def _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, prompt_embeds, negative_prompt_embeds,
              vsr_prompt_embeds, vsr_negative_prompt_embeds, interp_prompt_embeds, interp_negative_prompt_embeds, height, width,
              base_steps, guidance_scale, interp_frames, interp_cfg_scale, vsr_steps, vsr_guidance_scale, noise_level, generator,
-             decode_final, vsr_overlap=0, base_guidance_rescale=0.0, vsr_guidance_rescale=0.0):
+             decode_final, vsr_overlap=0, base_guidance_rescale=0.0, vsr_guidance_rescale=0.0, base_pag=None):
     dev = base_pipe.device
     base_kw = dict(guidance_rescale=base_guidance_rescale) if base_guidance_rescale else {}       # absent = the calls without it
+    base_kw.update(base_pag or {})
     vsr_kw = dict(guidance_rescale=vsr_guidance_rescale) if vsr_guidance_rescale else {}
     # 1. base T2V (base/pipelines/sample.py:78-91)
     base = base_pipe(prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, height=height, width=width,

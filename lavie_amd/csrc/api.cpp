@@ -517,12 +517,19 @@ static int check_step(const char* who, const StepArgs& a, bool scalars = true) {
         LAVIE_CHECK(a.n % a.per == 0, "%s: n=%lld is not a whole number of latents of per=%lld", who, (long long)a.n, (long long)a.per);
         LAVIE_CHECK(a.n / a.per <= 65535, "%s: n / per = %lld latents, at most 65535 fit one launch", who, (long long)(a.n / a.per));
     }
+    if (a.eps_pag) {                        // perturbed-attention guidance (sampler_pag.hip): the third operand's scale
+        LAVIE_CHECK(!a.known && !a.table, "%s: pag_scale is not combined with a known region or a guidance table", who);
+        LAVIE_CHECK(__builtin_isfinite(a.pag_scale), "%s: pag_scale (%g) is not finite", who, (double)a.pag_scale);
+        LAVIE_CHECK(a.pag_scale >= 0.f, "%s: pag_scale=%g must be >= 0", who, (double)a.pag_scale);
+    }
     // 16-byte accesses: the eight-element form of the kernel that will run.  The plain five-coefficient kernel has none; the plain
     // multistep kernel counts as one whatever n is (its vector body is empty under guidance with n % 8 != 0, the rule was never relaxed)
-    const bool vec8 = a.known ? a.inner % 8 == 0 : a.table ? a.per % 8 == 0 : a.multistep;
-    if (vec8)
+    const bool vec8 = a.known ? a.inner % 8 == 0 : a.table ? a.per % 8 == 0 : a.eps_pag ? a.n % 8 == 0 : a.multistep;
+    if (vec8) {
         for (int i = 0; i < 4; ++i)
             if (int rc = check_aligned(who, names[i], t[i])) return rc;
+        if (int rc = check_aligned(who, "eps (its perturbed part)", a.eps_pag)) return rc;
+    }
     return 0;
 }
 
@@ -540,6 +547,13 @@ static StepArgs step_args(bool multistep, bool cfg, const void* eps, float* x, c
 static int run_step(const char* who, const StepArgs& a, void* stream, bool scalars = true) {
     if (int rc = check_step(who, a, scalars)) return rc;
     return launch_step(a, S(stream));
+}
+
+// perturbed-attention guidance: eps / model_in hold one part more than the plain namesake's, the perturbed prediction last
+static int run_step_pag(const char* who, StepArgs a, float pag_scale, void* stream) {
+    if (a.eps && a.n >= 1 && a.n <= (1ll << 40)) a.eps_pag = a.eps + (a.cfg ? 2 : 1) * a.n;      // (else check_step refuses the call)
+    a.pag_scale = pag_scale;
+    return run_step(who, a, stream);
 }
 
 static int run_step_known(const char* who, StepArgs a, const lavie_known_region* region, void* stream) {
@@ -576,6 +590,31 @@ int lavie_multistep_step(const void* eps, float* x, float* x0_prev, void* model_
                          float c_x0, float c_xt, float c_prev, float next_input_scale, void* stream) {
     return run_step("multistep_step", step_args(true, false, eps, x, x0_prev, model_in, n, 1.0f, k_x, k_eps, c_x0, c_xt, c_prev,
                                                 next_input_scale), stream);
+}
+
+int lavie_cfg_pag_sampler_step(const void* eps3, float* x, const float* noise, void* model_in3, long long n, float guidance, float k_x,
+                               float k_eps, float c_x0, float c_xt, float sigma, float next_input_scale, float pag_scale, void* stream) {
+    return run_step_pag("cfg_pag_sampler_step", step_args(false, true, eps3, x, noise, model_in3, n, guidance, k_x, k_eps, c_x0, c_xt, sigma,
+                                                          next_input_scale), pag_scale, stream);
+}
+
+int lavie_pag_sampler_step(const void* eps2, float* x, const float* noise, void* model_in2, long long n, float k_x, float k_eps, float c_x0,
+                           float c_xt, float sigma, float next_input_scale, float pag_scale, void* stream) {
+    return run_step_pag("pag_sampler_step", step_args(false, false, eps2, x, noise, model_in2, n, 1.0f, k_x, k_eps, c_x0, c_xt, sigma,
+                                                      next_input_scale), pag_scale, stream);
+}
+
+int lavie_cfg_pag_multistep_step(const void* eps3, float* x, float* x0_prev, void* model_in3, long long n, float guidance, float k_x,
+                                 float k_eps, float c_x0, float c_xt, float c_prev, float next_input_scale, float pag_scale,
+                                 void* stream) {
+    return run_step_pag("cfg_pag_multistep_step", step_args(true, true, eps3, x, x0_prev, model_in3, n, guidance, k_x, k_eps, c_x0, c_xt,
+                                                            c_prev, next_input_scale), pag_scale, stream);
+}
+
+int lavie_pag_multistep_step(const void* eps2, float* x, float* x0_prev, void* model_in2, long long n, float k_x, float k_eps, float c_x0,
+                             float c_xt, float c_prev, float next_input_scale, float pag_scale, void* stream) {
+    return run_step_pag("pag_multistep_step", step_args(true, false, eps2, x, x0_prev, model_in2, n, 1.0f, k_x, k_eps, c_x0, c_xt, c_prev,
+                                                        next_input_scale), pag_scale, stream);
 }
 
 int lavie_cfg_sampler_step_known(const void* eps2, float* x, const float* noise, void* model_in2, long long n, float guidance,
@@ -992,6 +1031,10 @@ int lavie_unet_set_cfg_shared_input(lavie_unet_t h, int on) {
 int lavie_unet_set_freeu(lavie_unet_t h, float s1, float s2, float b1, float b2) {
     LAVIE_CHECK(h, "set_freeu: null handle");
     return h->net.set_freeu(s1, s2, b1, b2);
+}
+int lavie_unet_set_pag(lavie_unet_t h, const char* const* layers_host, int n_layers, int perturbed) {
+    LAVIE_CHECK(h, "set_pag: null handle");
+    return h->net.set_pag(layers_host, n_layers, perturbed);
 }
 int lavie_unet_set_ln_fold(lavie_unet_t h, int on) {
     LAVIE_CHECK(h, "set_ln_fold: null handle");

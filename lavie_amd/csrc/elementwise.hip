@@ -470,7 +470,8 @@ int launch_step_plain(const StepArgs& a, hipStream_t stream) {
 }
 
 int launch_step(const StepArgs& a, hipStream_t stream) {
-    return a.known ? launch_step_known(a, stream) : a.table ? launch_step_scaled(a, stream) : launch_step_plain(a, stream);
+    return a.known ? launch_step_known(a, stream) : a.table ? launch_step_scaled(a, stream) : a.eps_pag ? launch_step_pag(a, stream)
+                                                                                             : launch_step_plain(a, stream);
 }
 
 template <bool DUP>

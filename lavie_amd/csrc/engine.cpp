@@ -615,6 +615,7 @@ struct Route {
     int mask;               // fused_mask(): bits 0, 1, 2, 8 the row-resident kernels, 4 the parity upsample convs, 5 producer-side GroupNorm statistics
     bool shared;            // set_cfg_shared_input: the layers in front of the first text cross-attention run on half the batch
     bool ln_fold;           // set_ln_fold: LayerNorm folded into the producer / consumer GEMM epilogues
+    int pag = 0;            // set_pag: trailing batch entries whose attn1 is the identity on values in the selected blocks (0 = off)
 };
 
 struct FwdCtx {
@@ -919,6 +920,10 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
     // Tp rows) and `tx` / `att` are copied to the second
     const int NIp = shared_prefix ? NI / 2 : NI, Tp = shared_prefix ? T / 2 : T;
     LAVIE_CHECK(!shared_prefix || (!t.tres.present && !t.attn1_cross && c.B % 2 == 0), "transformer: shared prefix on an unsupported block");
+    // perturbed-attention guidance (set_pag, which vouches for the plain self-attention branch): the last pagF frames take no softmax
+    const int pagF = c.route.pag > 0 && ti < pag_sel_.size() && pag_sel_[ti] ? c.route.pag * c.F : 0;
+    LAVIE_CHECK(pagF == 0 || (!shared_prefix && !t.attn1_cross && !cfg_.sparse_causal_attn1 && pagF < NI),
+                "transformer: perturbed attention on an unsupported block or batch (B=%d, perturbed=%d)", c.B, c.route.pag);
     WS(gn_ab, float, (size_t)NI * C * 2);        // (planned whether or not the fused head runs: the plan must not depend on it)
     // LayerNorm folding: the GEMM that produces the residual stream `tx` also emits per-row (sum, sum^2) partials of
     // its fp16 output, and the projection that consumes LN(tx) runs on raw `tx` with gamma folded into its weights,
@@ -974,12 +979,17 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
         if (!c.dry) {
             AttnParams a;
             a.q = wide; a.ldq = 3 * C; a.k = wide + C; a.ldk = 3 * C; a.v = wide + 2 * C; a.ldv = 3 * C;
-            a.o = att; a.ldo = C; a.NBq = NIp; a.Lq = D; a.Lk = D; a.heads = heads; a.dh = dh; a.kv_batch_div = 1; a.scale = scale;
+            a.o = att; a.ldo = C; a.NBq = NIp - pagF; a.Lq = D; a.Lk = D; a.heads = heads; a.dh = dh; a.kv_batch_div = 1; a.scale = scale;
             if (cfg_.sparse_causal_attn1) {      // keys/values = first frame || previous frame (interpolation attention.py:630-639)
                 a.Lk = 2 * D;
                 a.sc_frames = c.F;
             }
             RUN(launch_attention(a, c.s));
+            // the perturbed entries: attention = the identity on values, so their rows of `att` are the V columns of q | k | v
+            if (pagF) {
+                const size_t r0 = (size_t)(NI - pagF) * D;
+                RUN(launch_copy_rows(wide + r0 * 3 * C + 2 * C, 3 * C, att + r0 * C, C, pagF * D, C, 0, c.s));
+            }
         }
     }
     if (!shared_prefix) TRACE("block.attn1 q(kv)", wide, T, t.attn1_cross ? C : 3 * C);
@@ -1133,9 +1143,10 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
     const bool shared_ok = c.B % 2 == 0 && cfg.attn_levels[0] && cfg.layers_per_block >= 1 && !tmod && !cfg.vsr_blocks &&
                            cfg.num_class_embeds == 0 && !cfg.sparse_causal_attn1 && !transformers_[0].attn1_cross && !transformers_[0].tres.present;
     // a caller that left the switch on for a batch or model it cannot apply to gets an error, not a silently different amount of work
-    LAVIE_CHECK(!c.route.shared || shared_ok || c.dry, "forward: set_cfg_shared_input(1) needs an even batch (B=%d) and the base UNet "
+    LAVIE_CHECK(!c.route.shared || shared_ok || c.dry || c.route.pag > 0, "forward: set_cfg_shared_input(1) needs an even batch (B=%d) and the base UNet "
                 "(attention in the first down block, no VSR / interpolation variants)", c.B);
-    const bool shared = c.route.shared && shared_ok;
+    // (while perturbed-attention guidance is on the switch is ignored, include/lavie_hip.h: the batch is [.. | prompt | perturbed])
+    const bool shared = c.route.shared && shared_ok && c.route.pag == 0;
     if (shared && !c.dry && debug_check_shared()) {
         // LAVIE_DEBUG_CHECK_SHARED=1: verify the caller's promise (sample[b] == sample[b + B/2], equal timesteps) before trusting it
         const size_t half_bytes = (size_t)(c.B / 2) * cfg.in_channels * c.F * prep_H_ * prep_W_ * sizeof(half_t);
@@ -1274,7 +1285,9 @@ int UNet::prepare(int B, int F, int H, int W, int ctx_len) {
         if ((variant & 1) && B % 2 != 0) continue;
         DeviceArena plan;
         plan.init_virtual();
-        FwdCtx c{nullptr, &plan, true, Route{masks[variant >> 1], (variant & 1) != 0, ln_fold_}, B, F, ctx_len, nullptr};
+        // (Route::pag = 0: perturbed-attention guidance runs every GEMM on all rows and takes nothing from the workspace that the plain
+        // branch does not, so the plan holds for a setting made before or after; with it the shared-input variants would go unplanned)
+        FwdCtx c{nullptr, &plan, true, Route{masks[variant >> 1], (variant & 1) != 0, ln_fold_, 0}, B, F, ctx_len, nullptr};
         prep_H_ = H; prep_W_ = W;
         RUN(run(c, nullptr, nullptr, nullptr, nullptr));
         if (plan.peak() > peak) peak = plan.peak();
@@ -1296,6 +1309,45 @@ int UNet::set_freeu(float s1, float s2, float b1, float b2) {
     freeu_s_[0] = s1; freeu_s_[1] = s2; freeu_b_[0] = b1; freeu_b_[1] = b2;
     ++graph_gen_;                                   // a captured forward holds the old setting's launches
     return 0;
+}
+
+int UNet::set_pag(const char* const* layers, int n_layers, int perturbed) {
+    LAVIE_CHECK(n_layers >= 0 && (n_layers == 0 || layers != nullptr), "set_pag: n_layers=%d with layers_host %s", n_layers,
+                layers ? "given" : "null");
+    LAVIE_CHECK(perturbed >= 0, "set_pag: perturbed=%d must be >= 0", perturbed);
+    std::vector<char> sel(transformers_.size(), 0);
+    for (int i = 0; i < n_layers; ++i) {
+        LAVIE_CHECK(layers[i] != nullptr && layers[i][0] != 0, "set_pag: layers_host[%d] is null or empty", i);
+        const std::string e = layers[i];
+        int hits = 0;
+        for (size_t ti = 0; ti < transformers_.size(); ++ti) {
+            const TransformerW& t = transformers_[ti];
+            if (t.prefix.compare(0, e.size(), e) != 0 || (t.prefix.size() > e.size() && t.prefix[e.size()] != '.')) continue;
+            LAVIE_CHECK(!t.attn1_cross && !cfg_.sparse_causal_attn1,
+                        "set_pag: layers_host[%d]='%s' selects %s, whose attn1 is not the plain spatial self-attention (%s)", i, layers[i],
+                        t.prefix.c_str(), t.attn1_cross ? "only_cross_attention level" : "sparse-causal attention");
+            sel[ti] = 1;
+            ++hits;
+        }
+        LAVIE_CHECK(hits > 0, "set_pag: layers_host[%d]='%s' selects no transformer (prefixes are spelled as in the state dict: "
+                    "mid_block, down_blocks.2, up_blocks.1.attentions.0, ...)", i, layers[i]);
+    }
+    LAVIE_CHECK(finalized_, "set_pag: call lavie_unet_finalize first");
+    const bool on = n_layers > 0 && perturbed > 0;
+    if (on) pag_sel_ = sel; else pag_sel_.clear();
+    pag_perturbed_ = on ? perturbed : 0;
+    ++graph_gen_;                                   // a captured forward holds the old setting's launches
+    return 0;
+}
+
+int UNet::pag_route(const char* who, int B) const {
+    if (pag_perturbed_ == 0) return 0;
+    if (B <= pag_perturbed_) {
+        set_error("%s: B=%d but perturbed=%d batch entries take the perturbed attention (lavie_unet_set_pag): B must be larger", who, B,
+                  pag_perturbed_);
+        return -1;
+    }
+    return pag_perturbed_;
 }
 
 void UNet::drop_graph() {
@@ -1351,7 +1403,9 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* ct
     LAVIE_CHECK(ws_.total_bytes() > 0, "forward: call lavie_unet_prepare first");
     RUN(ensure_tables(F, stream));
     ws_.release(0);
-    FwdCtx c{stream, &ws_, false, Route{fused_mask(), cfg_shared_input_, ln_fold_}, B, F, ctx_len, nullptr};
+    const int pag = pag_route("forward", B);
+    if (pag < 0) return -1;
+    FwdCtx c{stream, &ws_, false, Route{fused_mask(), cfg_shared_input_, ln_fold_, pag}, B, F, ctx_len, nullptr};
     c.labels = class_labels_host;
     prep_H_ = H; prep_W_ = W;
     return run(c, sample, timesteps, ctx, out);
@@ -1631,11 +1685,13 @@ int UNet::transformer_forward(const char* prefix, half_t* x, const half_t* ctx, 
     for (const TransformerW& cand : transformers_) if (cand.prefix == prefix) t = &cand;
     LAVIE_CHECK(t != nullptr, "transformer_forward: no Transformer3DModel with prefix '%s'", prefix);
     LAVIE_CHECK(F >= 1 && F <= 64, "transformer_forward: F=%d unsupported", F);
+    const int pag = pag_route("transformer_forward", B);
+    if (pag < 0) return -1;
     RUN(ensure_tables(F, stream));
     DeviceArena local;
     const size_t T = (size_t)B * F * H * W;
     RUN(local.init_fixed(T * t->C * 7 * sizeof(half_t) + (size_t)B * ctx_len * 2 * t->C * sizeof(half_t) + (4 << 20)));
-    FwdCtx c{stream, &local, false, Route{fused_mask(), cfg_shared_input_, ln_fold_}, B, F, ctx_len, nullptr};
+    FwdCtx c{stream, &local, false, Route{fused_mask(), cfg_shared_input_, ln_fold_, pag}, B, F, ctx_len, nullptr};
     c.gn_ws = (float*)local.alloc(gn_workspace_floats(B * F, cfg_.norm_groups) * sizeof(float));
     RUN(run_transformer(c, *t, x, ctx, H, W));
     LAVIE_HIP(hipStreamSynchronize(stream));

@@ -162,6 +162,13 @@ public:
     // FreeU (freeu.hip) in front of every resnet of up blocks 0 and 1: stage i scales the first half of the running activation's
     // channels by b[i] and the skip's lowest modes by s[i]; (1, 1) = the stage launches nothing.  Values must be finite and > 0.
     int set_freeu(float s1, float s2, float b1, float b2);
+    // Perturbed-attention guidance (Ahn et al.; diffusers' PAG pipelines): in the transformers whose prefix starts with an entry of
+    // `layers` (followed by '.' or the end), attn1 of the last `perturbed` batch entries is the identity map on values,
+    // to_out(to_v(norm1(x))): the softmax runs on the leading entries only and the V columns are copied for the rest.  n_layers == 0
+    // or perturbed == 0: off.  Refused, nothing changed: an entry that selects nothing, a selected block whose attn1 is not the plain
+    // spatial self-attention, perturbed < 0.  While on, set_cfg_shared_input is ignored (the perturbed entries differ from the first
+    // self-attention on) and a forward needs B > perturbed.
+    int set_pag(const char* const* layers, int n_layers, int perturbed);
     // Low-rank adapters on the attention projections (to_q / to_k / to_v / to_out.0 of attn1 / attn2 / attn_temp).  set / clear /
     // set_scale only record (the set copies the caller's tensors on `stream`); apply merges every target of the blocks touched since
     // the last apply and re-derives those blocks' images in place: device addresses never change, captured graphs stay valid.
@@ -238,6 +245,9 @@ private:
     bool cfg_shared_input_ = false;
     bool ln_fold_ = true;                           // LayerNorm folded into the producer / consumer GEMM epilogues
     float freeu_s_[2] = {1.f, 1.f}, freeu_b_[2] = {1.f, 1.f};      // set_freeu: read by run() in the up walk (decoder only)
+    std::vector<char> pag_sel_;                     // set_pag: per transformer, attn1 perturbed; empty = off
+    int pag_perturbed_ = 0;                         // trailing batch entries it applies to; read where a call enters, as the switches above
+    int pag_route(const char* who, int B) const;    // the Route::pag of a call on B entries (0 = off), or -1 after refusing B <= perturbed
 
     DeviceArena weights_, ws_;
     // packed model

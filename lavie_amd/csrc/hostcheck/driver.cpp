@@ -132,6 +132,59 @@ static void run_model(const lavie_unet_config& cfg, int B, int F, int H, int W, 
         REQUIRE(launches() == off);
         REQUIRE(lavie_unet_workspace_bytes(h) == ws_bytes);
     }
+    {   // perturbed-attention guidance: one strided row copy more per selected transformer, inside the workspace prepare() planned; a
+        // refused call names its argument and leaves the setting in force; off is the plain forward again
+        auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+        auto forward = [&]() {
+            return labels ? lavie_unet_forward_labels(h, x, t, ctx, lab.data(), y, B, F, H, W, 77, nullptr)
+                          : lavie_unet_forward(h, x, t, ctx, y, B, F, H, W, 77, nullptr);
+        };
+        auto launches = [&]() {
+            const long b = lavie_hostcheck_launches();
+            REQUIRE(forward() == 0);
+            return lavie_hostcheck_launches() - b;
+        };
+        const char* mid[1] = {"mid_block"};
+        const char* two[2] = {"mid_block", "down_blocks.0.attentions.1"};
+        const char* almost[1] = {"mid_bloc"};               // a prefix of the name, but not up to a '.'
+        const char* level0[1] = {"down_blocks.0"};
+        const char* empty[1] = {""};
+        const long long ws_bytes = lavie_unet_workspace_bytes(h);
+        const long off = launches();
+        REQUIRE(refused(lavie_unet_set_pag(nullptr, mid, 1, 1), "null handle"));
+        REQUIRE(refused(lavie_unet_set_pag(h, mid, 1, -1), "perturbed=-1"));
+        REQUIRE(refused(lavie_unet_set_pag(h, almost, 1, 1), "selects no transformer"));
+        REQUIRE(refused(lavie_unet_set_pag(h, empty, 1, 1), "layers_host[0]"));
+        REQUIRE(refused(lavie_unet_set_pag(h, nullptr, 1, 1), "layers_host"));
+        REQUIRE(refused(lavie_unet_set_pag(h, mid, -1, 1), "n_layers=-1"));
+        REQUIRE(launches() == off);
+        if (cfg.sparse_causal_attn1) {
+            REQUIRE(refused(lavie_unet_set_pag(h, mid, 1, 1), "plain spatial self-attention"));
+            REQUIRE(launches() == off);
+        } else {
+            if (cfg.vsr_blocks && cfg.only_cross_attention[0])       // attn1 of that level attends to the text
+                REQUIRE(refused(lavie_unet_set_pag(h, level0, 1, 1), "plain spatial self-attention"));
+            REQUIRE(lavie_unet_set_pag(h, mid, 1, 1) == 0);
+            if (B > 1) {
+                REQUIRE(launches() == off + 1);
+                REQUIRE(refused(lavie_unet_set_pag(h, almost, 1, 1), "selects no transformer") && launches() == off + 1);
+                REQUIRE(lavie_unet_set_cfg_shared_input(h, 1) == 0);          // ignored while PAG is on
+                REQUIRE(launches() == off + 1);
+                REQUIRE(lavie_unet_set_cfg_shared_input(h, 0) == 0);
+                if (!cfg.vsr_blocks) {
+                    REQUIRE(lavie_unet_set_pag(h, two, 2, 1) == 0);
+                    REQUIRE(launches() == off + 2);
+                }
+                REQUIRE(lavie_unet_set_pag(h, mid, 1, B) == 0);
+            }
+            REQUIRE(refused(forward(), "perturbed="));                        // B <= perturbed
+            REQUIRE(lavie_unet_set_pag(h, mid, 1, 0) == 0);                   // perturbed == 0: off
+            REQUIRE(launches() == off);
+            REQUIRE(lavie_unet_set_pag(h, mid, 1, 1) == 0 && lavie_unet_set_pag(h, nullptr, 0, 0) == 0);
+            REQUIRE(launches() == off);
+        }
+        REQUIRE(lavie_unet_workspace_bytes(h) == ws_bytes);
+    }
     if (check_switches) {   // a rejected switch value leaves the one in force: the launch count of a forward tells them apart
         auto launches = [&]() {
             const long b = lavie_hostcheck_launches();
@@ -1255,6 +1308,44 @@ int main(int argc, char** argv) {
             REQUIRE(refused(lavie_window_step_scaled(&b, wtable, nullptr), "W=0"));
             REQUIRE(lavie_hostcheck_launches() == before + 19);
         }
+    }
+    {   // the four steps with perturbed-attention guidance: both launch forms with exactly sized buffers; every refusal comes before a
+        // launch and names its argument
+        const int n = 48;
+        alignas(16) static unsigned short eps[3 * n + 8], min3[3 * n + 8];
+        alignas(16) static float x[n + 4], nz[n + 4], hist[n + 4];
+        const float nan = __builtin_nanf("");
+        auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+        const long before = lavie_hostcheck_launches();
+        REQUIRE(lavie_cfg_pag_sampler_step(eps, x, nz, min3, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr) == 0);
+        REQUIRE(lavie_cfg_pag_sampler_step(eps, x, nullptr, min3, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 0.9f, 0.f, nullptr) == 0);
+        REQUIRE(lavie_pag_sampler_step(eps, x, nz, min3, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr) == 0);
+        REQUIRE(lavie_cfg_pag_multistep_step(eps, x, hist, min3, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 0.9f, 3.f, nullptr) == 0);
+        REQUIRE(lavie_pag_multistep_step(eps, x, hist, min3, n, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 0.9f, 3.f, nullptr) == 0);
+        // one element per lane: no alignment asked of anything
+        REQUIRE(lavie_cfg_pag_sampler_step(eps + 1, x + 1, nz + 1, min3 + 1, n - 1, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr) == 0);
+        REQUIRE(lavie_pag_multistep_step(eps + 1, x + 1, hist + 1, min3 + 1, n - 3, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 0.9f, 3.f, nullptr) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 7);
+        REQUIRE(refused(lavie_cfg_pag_sampler_step(nullptr, x, nz, min3, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr), "eps is null"));
+        REQUIRE(refused(lavie_cfg_pag_sampler_step(eps, nullptr, nz, min3, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr), "x is null"));
+        REQUIRE(refused(lavie_pag_sampler_step(eps, x, nz, nullptr, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr), "model_in is null"));
+        REQUIRE(refused(lavie_pag_sampler_step(eps, x, nullptr, min3, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr), "noise is null"));
+        REQUIRE(refused(lavie_cfg_pag_multistep_step(eps, x, nullptr, min3, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 0.9f, 3.f, nullptr), "x0_prev is null"));
+        REQUIRE(refused(lavie_cfg_pag_sampler_step(eps, x, nz, min3, 0, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr), "n=0"));
+        REQUIRE(refused(lavie_pag_multistep_step(eps, x, hist, min3, -8, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 0.9f, 3.f, nullptr), "n=-8"));
+        REQUIRE(refused(lavie_cfg_pag_sampler_step(eps, x, nz, min3, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nan, nullptr), "pag_scale"));
+        REQUIRE(refused(lavie_cfg_pag_sampler_step(eps, x, nz, min3, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, INFINITY, nullptr), "pag_scale"));
+        REQUIRE(refused(lavie_cfg_pag_sampler_step(eps, x, nz, min3, n, nan, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr), "guidance"));
+        REQUIRE(refused(lavie_pag_sampler_step(eps, x, nz, min3, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, nan, 3.f, nullptr), "next_input_scale"));
+        REQUIRE(refused(lavie_pag_multistep_step(eps, x, hist, min3, n, 1.f, 0.5f, 0.3f, 0.7f, nan, 0.9f, 3.f, nullptr), "c_prev"));
+        REQUIRE(refused(lavie_pag_sampler_step(eps, x, nz, min3, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, -0.5f, nullptr), "pag_scale=-0.5"));
+        REQUIRE(refused(lavie_cfg_pag_multistep_step(eps, x, hist, min3, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.5f, 0.9f, -1.f, nullptr), "pag_scale=-1"));
+        REQUIRE(refused(lavie_cfg_pag_sampler_step(eps + 1, x, nz, min3, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr), "eps at"));
+        REQUIRE(refused(lavie_cfg_pag_sampler_step(eps, x + 1, nz, min3, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr), "x at"));
+        REQUIRE(refused(lavie_pag_sampler_step(eps, x, nz + 2, min3, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr), "noise at"));
+        REQUIRE(refused(lavie_pag_sampler_step(eps, x, nz, min3 + 4, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, 3.f, nullptr), "model_in at"));
+        REQUIRE(refused(lavie_pag_multistep_step(eps, x, hist + 1, min3, n, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 0.9f, 3.f, nullptr), "x0_prev at"));
+        REQUIRE(lavie_hostcheck_launches() == before + 7);
     }
     {   // the VAE's edge convolutions and the asymmetric-pad stride-2 conv: accepted calls reach the (stubbed) launch with exactly
         // sized buffers (packing, odd Cin, ragged last tile); every refusal comes before a HIP call and names its argument

@@ -110,7 +110,7 @@ int launch_conv_edge_out(const half_t* x, const half_t* wp, const float* bias, v
                          hipStream_t stream);
 int launch_pack_conv_edge_out(const half_t* w, half_t* out, int Cout, int Cin, hipStream_t stream);
 long long conv_edge_out_image_halfs(int Cin);
-// ---- the fused scheduler steps (elementwise.hip, sampler_known.hip, sampler_guidance.hip): StepArgs is the one description of a step
+// ---- the fused scheduler steps (elementwise.hip, sampler_known.hip, sampler_guidance.hip, sampler_pag.hip): StepArgs is the one description of a step
 // from the C entry points down to the launch.  Per element, fp32 (pipeline_videogen.py:679-683, scheduling_dpmsolver_multistep.py):
 //   eps = cfg ? eps_u + g (eps_c - eps_u) : eps_u;  x0 = kx x - ke eps
 //   five-coefficient family: x' = c0 x0 + ct x + sigma noise                     (aux = the step's noise, read when c4 = sigma != 0)
@@ -120,8 +120,11 @@ long long conv_edge_out_image_halfs(int Cin);
 //   known != nullptr: x' = select(mask, x', a known + s noise) inside the step (sampler_known.hip); n = P * channels * inner.
 //   table != nullptr (cfg only): (g, rescale factor f) per latent from table[P][2] and eps = f eps (sampler_guidance.hip); n = P per
 //   (with `known` the latent is the plane's video and `per` is not read).
+//   eps_pag != nullptr (sampler_pag.hip; not with `known` / `table`): perturbed-attention guidance.  eps holds one part more, [neg |
+//   prompt | perturbed] with cfg, [prompt | perturbed] without; eps_pag = its last part.  e = cfg ? fma(g, ec - eu, eu) : ec, then
+//   eps = pag_scale != 0 ? fma(pag_scale, ec - ep, e) : e; model_in gets the ONE fp16 value in all three (two) parts.
 //   Every tensor must be 16-byte aligned where the eight-element form runs: the multistep family without `known` / `table`, inner % 8
-//   == 0 with `known`, per % 8 == 0 with `table` alone (checked by the C entry points).
+//   == 0 with `known`, per % 8 == 0 with `table` alone, n % 8 == 0 with `eps_pag` (checked by the C entry points).
 struct StepCoef { float guidance, kx, ke, c0, ct, c4; };     // c4: sigma (five-coefficient family) or c_prev (multistep family)
 struct KnownOperands { const float* known; const float* mask; const float* noise; float a, s; };     // mask == nullptr: 1 everywhere (blend only)
 struct StepArgs {
@@ -131,11 +134,13 @@ struct StepArgs {
     StepCoef c; float in_scale;                       // c.guidance = 1 without cfg and with a table
     const KnownOperands* known; int channels; int64_t inner;   // known == nullptr: no region
     const float* table; int64_t per;                            // table == nullptr: scalar guidance
+    const half_t* eps_pag; float pag_scale;                     // eps_pag == nullptr: no perturbed-attention guidance
 };
-int launch_step(const StepArgs& a, hipStream_t stream);              // picks the file by (known, table)
+int launch_step(const StepArgs& a, hipStream_t stream);              // picks the file by (known, table, eps_pag)
 int launch_step_plain(const StepArgs& a, hipStream_t stream);        // elementwise.hip
 int launch_step_known(const StepArgs& a, hipStream_t stream);        // sampler_known.hip
 int launch_step_scaled(const StepArgs& a, hipStream_t stream);       // sampler_guidance.hip
+int launch_step_pag(const StepArgs& a, hipStream_t stream);          // sampler_pag.hip
 int launch_add_class_emb_silu(float* emb, const half_t* table, const int* labels_host, int B, int N, hipStream_t stream);
 int launch_f32_to_f16_dup2(const float* x, half_t* out2, int64_t n, float in_scale, hipStream_t stream);
 int launch_f32_to_f16_scaled(const float* x, half_t* out, int64_t n, float in_scale, hipStream_t stream);

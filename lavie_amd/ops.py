@@ -572,13 +572,29 @@ def temporal_attention(qkv, b, frames, d, heads, bias, rot_cos, rot_sin, rot_dim
     return o
 
 
-def _step(entry, who, eps, x, aux, model_in, coeffs, next_input_scale, *, guidance=None, table=None, region=None, counts=True):
+def _step(entry, who, eps, x, aux, model_in, coeffs, next_input_scale, *, guidance=None, table=None, region=None, counts=True,
+          pag_scale=None):
     """The body of every scheduler-step wrapper: dtype, element-count and shape checks, then the C entry `entry` with its operands
     in the order the entries share: eps, x, aux, model_in, n, [guidance | table, [per]], the five coefficients, next_input_scale,
     the stream, [the region].  The wrapper's name `who` says the form: cfg_ = eps / model_in hold both guidance halves, multistep =
     aux is the x0_prev history (else the step's noise, which may be None), _scaled = guidance from `table` [P, 2].
-    region = (known, mask, noise_known, level) of a step around known latents."""
+    region = (known, mask, noise_known, level) of a step around known latents.  pag_scale (the _pag_ wrappers): eps / model_in hold
+    one part more, the perturbed prediction last, and the scale follows next_input_scale."""
     guided, multistep, scaled = who.startswith("cfg_"), "multistep" in who, who.endswith("_scaled")
+    if pag_scale is not None:
+        parts = 3 if guided else 2
+        _chk16(eps, model_in)
+        _chk32(x, aux)
+        if multistep and aux is None:
+            raise ValueError(f"{who}: x0_prev is needed")
+        if eps.numel() != parts * x.numel() or model_in.numel() != parts * x.numel() or (aux is not None and aux.numel() != x.numel()):
+            raise ValueError(f"{who}: eps / model_in must have {parts} times, " + ("x0_prev" if multistep else "noise") +
+                             " as many elements as x")
+        k_x, k_e, c_x0, c_xt, c4 = coeffs
+        how = (float(guidance),) if guided else ()
+        _lib.check(getattr(_lib.load(), entry)(_p(eps), _p(x), _p(aux), _p(model_in), x.numel(), *how, float(k_x), float(k_e), float(c_x0),
+                                               float(c_xt), float(c4), float(next_input_scale), float(pag_scale), _stream()), entry)
+        return
     if scaled and multistep and aux is None:
         raise ValueError(f"{who}: x0_prev is needed")
     _chk16(eps, model_in)
@@ -629,6 +645,29 @@ def cfg_multistep_step(eps2, x, x0_prev, model_in2, guidance, coeffs, next_input
 def multistep_step(eps, x, x0_prev, model_in, coeffs, next_input_scale: float = 1.0):
     """The multistep update without classifier-free guidance (guidance_scale <= 1): eps / model_in are fp16 of x's size."""
     _step("lavie_multistep_step", "multistep_step", eps, x, x0_prev, model_in, coeffs, next_input_scale)
+
+
+def cfg_pag_sampler_step(eps3, x, noise, model_in3, guidance, pag_scale, coeffs, next_input_scale: float = 1.0):
+    """Fused CFG + perturbed-attention guidance + five-coefficient update (lavie_cfg_pag_sampler_step): eps3 / model_in3 fp16 [3, n] =
+    [negative | prompt | perturbed], eps = u + g (c - u) + pag_scale (c - p); model_in3 gets the next input in all three parts."""
+    _step("lavie_cfg_pag_sampler_step", "cfg_pag_sampler_step", eps3, x, noise, model_in3, coeffs, next_input_scale, guidance=guidance,
+          pag_scale=pag_scale)
+
+
+def pag_sampler_step(eps2, x, noise, model_in2, pag_scale, coeffs, next_input_scale: float = 1.0):
+    """The same without classifier-free guidance: eps2 / model_in2 fp16 [2, n] = [prompt | perturbed], eps = c + pag_scale (c - p)."""
+    _step("lavie_pag_sampler_step", "pag_sampler_step", eps2, x, noise, model_in2, coeffs, next_input_scale, pag_scale=pag_scale)
+
+
+def cfg_pag_multistep_step(eps3, x, x0_prev, model_in3, guidance, pag_scale, coeffs, next_input_scale: float = 1.0):
+    """cfg_pag_sampler_step for the multistep family (DPM-Solver++ 2M): `x0_prev` as in cfg_multistep_step."""
+    _step("lavie_cfg_pag_multistep_step", "cfg_pag_multistep_step", eps3, x, x0_prev, model_in3, coeffs, next_input_scale,
+          guidance=guidance, pag_scale=pag_scale)
+
+
+def pag_multistep_step(eps2, x, x0_prev, model_in2, pag_scale, coeffs, next_input_scale: float = 1.0):
+    """pag_sampler_step for the multistep family."""
+    _step("lavie_pag_multistep_step", "pag_multistep_step", eps2, x, x0_prev, model_in2, coeffs, next_input_scale, pag_scale=pag_scale)
 
 
 def _known_region(who, x, known, mask, noise_known, level):

@@ -132,6 +132,7 @@ class VideoGenPipeline:
         `video_length`, `image_size`, `num_sampling_steps`, `guidance_scale` become the `__call__` keywords of sample.py:83-89,
         an optional `guidance_rescale` (not a key of the reference) becomes the keyword of that name,
         an optional `freeu: {s1:, s2:, b1:, b2:}` (not a key of the reference either) is set on the UNet (enable_freeu),
+        optional `pag_scale` / `pag_adaptive_scale` / `pag_applied_layers` (a name or a list of names) become the keywords of those names,
         `seed` is returned in cfg for torch.manual_seed (sample.py:22-23).  `use_fp16` and
         `enable_xformers_memory_efficient_attention` are read by nobody in sample.py and are ignored here as well.
         PyYAML's safe loader replaces omegaconf (absent from the image); interpolation / `${...}` references are not resolved."""
@@ -163,6 +164,10 @@ class VideoGenPipeline:
                            guidance_scale=float(cfg.get("guidance_scale", 7.5)))
         if "guidance_rescale" in cfg:
             call_kwargs["guidance_rescale"] = float(cfg["guidance_rescale"])
+        for key, conv in (("pag_scale", float), ("pag_adaptive_scale", float),       # perturbed-attention guidance (not keys of the reference)
+                          ("pag_applied_layers", lambda v: (v,) if isinstance(v, str) else tuple(v))):
+            if key in cfg:
+                call_kwargs[key] = conv(cfg[key])
         pipe = VideoGenPipeline(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet, scheduler=scheduler)
         if "freeu" in cfg:                      # {s1:, s2:, b1:, b2:}, all four: the setting goes onto the model
             fu = cfg["freeu"]
@@ -275,7 +280,8 @@ class VideoGenPipeline:
                 known: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
                 known_noise: Optional[torch.Tensor] = None, start_step: int = 0, window_length: Optional[int] = None,
                 window_stride: Optional[int] = None, window_weights: str = "triangle",
-                guidance_rescale: float = 0.0) -> torch.Tensor:
+                guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
+                pag_applied_layers=("mid_block",)) -> torch.Tensor:
         """latents fp32 [P, C, F, h, w] on the device, ctx fp16 [2P, n, d] = [negative | prompt] (guidance_scale > 1) or
         [P, n, d] = prompt only (guidance_scale <= 1: no classifier-free guidance, :626) -> denoised fp32.  One loop, one step
         launch per denoising step; step plan, step noise, engine session and step dispatch are lavie_amd.sampling's.
@@ -301,7 +307,18 @@ class VideoGenPipeline:
         averages the windows' noise predictions per frame with the normalised `window_weights` profile, advances the whole clip
         by one scheduler step and writes every window's next fp16 model input.  `window_stride` defaults to three quarters of the
         window.  A frame that one window covers gets the plain step's bits.  The engine is prepared and the context cached once,
-        for the window shape; the step's own noise is drawn for the whole clip."""
+        for the window shape; the step's own noise is drawn for the whole clip.
+
+        Perturbed-attention guidance (Ahn et al.; diffusers' AnimateDiffPAGPipeline): with `pag_scale` > 0 one more copy of the
+        prompt-conditioned latents rides in the batch, ctx = [negative | prompt | prompt] ([3P, n, d]; [prompt | prompt] without
+        classifier-free guidance), and in the transformers `pag_applied_layers` selects (state-dict prefixes, `UNet.set_pag`) the
+        spatial self-attention of that last part is the identity on values.  The step folds the third prediction in,
+        eps = e_cfg + s_t (eps_prompt - eps_perturbed), s_t = max(pag_scale - pag_adaptive_scale (1000 - t), 0), in the one launch
+        (ops.cfg_pag_sampler_step and kin).  The UNet's PAG setting is made for the loop and restored afterwards, also after an
+        exception.  Not combined with known latents, frame windows, `guidance_rescale` > 0 or a `guidance_scale` sequence; at most
+        2 prompts per call with guidance, 4 without (the engine's batch limit of 8).  pag_scale = 0 is the call without it."""
+        pag = self.check_pag(pag_scale, pag_adaptive_scale, latents.shape[0], guidance_scale, guidance_rescale,
+                             known=known, mask=mask, known_noise=known_noise, window_length=window_length)
         windowed = False
         if window_length is not None:
             if known is not None or mask is not None or known_noise is not None or start_step != 0:
@@ -328,8 +345,12 @@ class VideoGenPipeline:
         # None, the scalar itself, or the table route with its buffers, allocated here once for the loop
         guidance = sampling.guidance_of(guidance_scale, guidance_rescale, x, frames, len(starts))
         nb = 2 * p if guidance is not None else p          # model batch (:666)
+        if pag:                                             # [negative | prompt | perturbed] or [prompt | perturbed]
+            nb += p
+            guidance = sampling.PagGuidance(guidance, pag_scale)
         if ctx.shape[0] != nb:
-            raise ValueError(f"ctx has {ctx.shape[0]} rows, expected {nb} for {p} latents at guidance_scale={guidance_scale}")
+            raise ValueError(f"ctx has {ctx.shape[0]} rows, expected {nb} for {p} latents at guidance_scale={guidance_scale}" +
+                             (f", pag_scale={pag_scale}" if pag else ""))
         if known is not None:
             if tuple(known.shape) != tuple(x.shape):
                 raise ValueError(f"`known` has shape {tuple(known.shape)}, the latents {tuple(x.shape)}")
@@ -348,6 +369,9 @@ class VideoGenPipeline:
         if known is not None:
             ops.known_blend(x, model_in[0], known, mask if start_step == 0 else None, known_noise, plan.noise_level(start_step),
                             plan.input_scale(start_step))
+        elif pag:                                           # one fp16 value in every part, as the step kernel writes it
+            for part in model_in[0].view(nb // p, -1):
+                ops.latents_to_model_input1(x, part, plan.input_scale(0))
         else:
             for s, m in zip(starts, model_in):
                 (ops.latents_to_model_input if guidance is not None else ops.latents_to_model_input1)(
@@ -357,11 +381,29 @@ class VideoGenPipeline:
         # own step kernel, pinned or not, windowed or not): the engine may compute the layers in front of the first text
         # cross-attention once
         region = None
+        pag_was = self.unet.pag if pag else None           # the model's own setting comes back after the loop, whatever happens in it
+        try:
+            if pag:
+                self.unet.set_pag(pag_applied_layers, p)
+            x = self._denoise_loop(x, ctx, nb, frames, starts, model_in, guidance, plan, noise, x0_prev, t_dev, start_step, windowed,
+                                   profile if windowed else None, known, mask, known_noise, region, callback, callback_steps,
+                                   pag_scale, pag_adaptive_scale)
+        finally:
+            if pag_was is not None:
+                self.unet.set_pag(*pag_was)
+        return x
+
+    def _denoise_loop(self, x, ctx, nb, frames, starts, model_in, guidance, plan, noise, x0_prev, t_dev, start_step, windowed, profile,
+                      known, mask, known_noise, region, callback, callback_steps, pag_scale, pag_adaptive_scale):
+        """The engine session and the steps of `denoise`, on the buffers it has set up."""
+        pag = isinstance(guidance, sampling.PagGuidance)
         with sampling.engine_session(self.unet, nb, frames, x.shape[3], x.shape[4], ctx,
-                                     model_in if guidance is not None and self.cfg_shared_prefix else None) as ctx:
+                                     model_in if guidance is not None and self.cfg_shared_prefix and not pag else None) as ctx:
             forwards = sampling.WindowForwards(lambda w, i: self.unet(model_in[w], t_dev[i], encoder_hidden_states=ctx).sample)
             for i in range(start_step, len(plan.timesteps)):
                 eps = forwards(len(model_in), i)                                                      # line 670
+                if pag:
+                    guidance.pag_scale = sampling.pag_scale_at(pag_scale, pag_adaptive_scale, plan.timesteps[i])
                 coeffs = plan.coeffs(i, first=start_step > 0 and i == start_step)
                 aux = x0_prev if plan.multistep else noise.draw() if plan.adds_noise(coeffs) else None
                 if windowed:
@@ -375,6 +417,32 @@ class VideoGenPipeline:
                 if callback is not None and i % callback_steps == 0:
                     callback(i, plan.timesteps[i], x)
         return x
+
+    @staticmethod
+    def check_pag(pag_scale, pag_adaptive_scale, prompts: int, guidance_scale, guidance_rescale, **others) -> bool:
+        """The perturbed-attention-guidance arguments of a call on `prompts` latents -> whether PAG is on (pag_scale > 0).  `others`:
+        the call's arguments PAG is not combined with, by name (None = absent).  Raises before anything reaches the engine."""
+        pag_scale, pag_adaptive_scale = float(pag_scale), float(pag_adaptive_scale)
+        if not (pag_scale >= 0.0 and pag_scale != float("inf")):
+            raise ValueError(f"`pag_scale` must be finite and >= 0 but is {pag_scale}")
+        if not (pag_adaptive_scale >= 0.0 and pag_adaptive_scale != float("inf")):
+            raise ValueError(f"`pag_adaptive_scale` must be finite and >= 0 but is {pag_adaptive_scale}")
+        if pag_scale == 0.0:
+            return False
+        for name, value in others.items():
+            if value is not None:
+                raise ValueError(f"`pag_scale` > 0 cannot be combined with `{name}`")
+        if isinstance(guidance_scale, (list, tuple)) or (isinstance(guidance_scale, torch.Tensor) and guidance_scale.dim() > 0):
+            raise ValueError("`pag_scale` > 0 cannot be combined with a `guidance_scale` sequence (one value per prompt)")
+        guided = guidance_scale > 1.0
+        if float(guidance_rescale) > 0.0:
+            raise ValueError("`pag_scale` > 0 cannot be combined with `guidance_rescale` > 0")
+        most = 2 if guided else 4
+        if prompts > most:
+            raise ValueError(f"`pag_scale` > 0 serves at most {most} prompts per call {'with' if guided else 'without'} guidance "
+                             f"(the engine's batch limit of 8 holds {'[negative | prompt | perturbed]' if guided else '[prompt | perturbed]'}), "
+                             f"got {prompts}")
+        return True
 
     @staticmethod
     def strength_start(num_inference_steps: int, strength: float) -> int:
@@ -439,10 +507,12 @@ class VideoGenPipeline:
                  cross_attention_kwargs=None, image_embeds: Optional[torch.Tensor] = None,
                  known_latents: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None,
                  video: Optional[torch.Tensor] = None, strength: float = 1.0, window_length: Optional[int] = None,
-                 window_stride: Optional[int] = None, window_weights: str = "triangle", guidance_rescale: float = 0.0):
+                 window_stride: Optional[int] = None, window_weights: str = "triangle", guidance_rescale: float = 0.0,
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid_block",)):
         """`guidance_scale`: one number, or a sequence with one value > 1 per prompt (repeated per `num_images_per_prompt`; a
         sequence always means guidance is on).  `guidance_rescale` in [0, 1]: diffusers' rescale_noise_cfg inside the fused step;
-        ignored with a scalar `guidance_scale` <= 1, as in diffusers.  See `denoise`."""
+        ignored with a scalar `guidance_scale` <= 1, as in diffusers.  `pag_scale` > 0: perturbed-attention guidance in the
+        transformers `pag_applied_layers` names, fading by `pag_adaptive_scale` per timestep below 1000.  See `denoise`."""
         if window_length is not None and (known_latents is not None or known_mask is not None or video is not None or strength != 1.0):
             raise ValueError("frame windows (`window_length`) cannot be combined with `known_latents` / `known_mask` / `video` / "
                              "`strength`")
@@ -456,6 +526,8 @@ class VideoGenPipeline:
         else:
             batch_size = prompt_embeds.shape[0]
         device = self.device
+        pag = self.check_pag(pag_scale, pag_adaptive_scale, batch_size * (num_images_per_prompt or 1), guidance_scale, guidance_rescale,
+                             known_latents=known_latents, video=video, known_mask=known_mask, window_length=window_length)
         do_cfg, scales, guidance_rescale = sampling.check_guidance(guidance_scale, guidance_rescale, batch_size,
                                                                    num_images_per_prompt or 1)
         if scales is not None:
@@ -464,6 +536,8 @@ class VideoGenPipeline:
         image_features = self._image_features(image_tensor, image_embeds, device) if self.mapper is not None else None
         ctx = self._encode_prompt(prompt, device, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds,
                                   negative_prompt_embeds, image_features).to(torch.float16).contiguous()
+        if pag:                                # [negative | prompt | prompt] or [prompt | prompt]: the last part rides perturbed
+            ctx = torch.cat([ctx, ctx[-(ctx.shape[0] // (2 if do_cfg else 1)):]]).contiguous()
         latents = self.prepare_latents(batch_size * num_images_per_prompt, self.unet.config.in_channels, video_length,
                                        height, width, torch.float32, device, generator, latents)
         # sampling around known latents (pinned frames, video-to-video, clip continuation): `denoise(known=)`
@@ -476,6 +550,8 @@ class VideoGenPipeline:
         elif window_length is not None:    # clips longer than the window: overlapping frame windows
             around = dict(window_length=window_length, window_stride=window_stride, window_weights=window_weights)
         rescale = dict(guidance_rescale=guidance_rescale) if guidance_rescale else {}      # absent = today's call
+        if pag:
+            rescale.update(pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale, pag_applied_layers=pag_applied_layers)
         lora_scale = (cross_attention_kwargs or {}).get("scale")
         if lora_scale is None:
             latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta,

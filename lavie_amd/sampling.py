@@ -216,12 +216,32 @@ def guidance_of(guidance_scale, guidance_rescale, x: torch.Tensor, frames: int, 
     return GuidanceTable(scales if scales is not None else guidance_scale, phi, x.shape[0], per, x.device, windows)
 
 
+class PagGuidance:
+    """The guidance of a step with perturbed-attention guidance: `guidance_scale` (a number, or None without classifier-free
+    guidance) and the step's PAG scale, which the loop sets before each step (`pag_scale_at`)."""
+
+    def __init__(self, guidance_scale, pag_scale: float):
+        self.guidance_scale, self.pag_scale = guidance_scale, float(pag_scale)
+
+
+def pag_scale_at(pag_scale: float, pag_adaptive_scale: float, timestep) -> float:
+    """The PAG scale of the step at `timestep`: max(pag_scale - pag_adaptive_scale (1000 - t), 0), diffusers' _get_pag_scale (the
+    scale fades as sampling proceeds when pag_adaptive_scale > 0)."""
+    return max(float(pag_scale) - float(pag_adaptive_scale) * (1000.0 - float(timestep)), 0.0)
+
+
 def step(eps, x, aux, model_in, guidance_scale, coeffs, next_scale, multistep: bool, region=None):
     """One fused scheduler step through the `ops` wrapper of its family.  `aux`: the step's noise or None (five-coefficient
     family), the x0 history (multistep).  `guidance_scale` None: no classifier-free guidance; a GuidanceTable: the table is
     computed from `eps` and the `_scaled` wrapper of the family reads it.  `region`: None, or (known, mask, known_noise, level) of
-    a run around known latents.  The wrappers are looked up on `ops` at call time."""
-    if isinstance(guidance_scale, GuidanceTable):
+    a run around known latents.  A PagGuidance: eps / model_in hold the perturbed part as well and the `pag` wrappers run.  The
+    wrappers are looked up on `ops` at call time."""
+    if isinstance(guidance_scale, PagGuidance):
+        if region is not None:
+            raise ValueError("perturbed-attention guidance is not combined with a known region")
+        g = guidance_scale.guidance_scale
+        kind, guidance = ("pag_cfg", (g, guidance_scale.pag_scale)) if g is not None else ("pag", (guidance_scale.pag_scale,))
+    elif isinstance(guidance_scale, GuidanceTable):
         kind, guidance = "table", (guidance_scale([eps]),)
     else:
         kind, guidance = ("scalar", (guidance_scale,)) if guidance_scale is not None else ("none", ())
@@ -237,6 +257,9 @@ STEP_WRAPPERS = {
     (True, "none", False): "multistep_step",                (True, "none", True): "multistep_step_known",
     (True, "scalar", False): "cfg_multistep_step",          (True, "scalar", True): "cfg_multistep_step_known",
     (True, "table", False): "cfg_multistep_step_scaled",    (True, "table", True): "cfg_multistep_step_known_scaled",
+    # perturbed-attention guidance, with and without classifier-free guidance (no region form)
+    (False, "pag", False): "pag_sampler_step",              (False, "pag_cfg", False): "cfg_pag_sampler_step",
+    (True, "pag", False): "pag_multistep_step",             (True, "pag_cfg", False): "cfg_pag_multistep_step",
 }
 
 

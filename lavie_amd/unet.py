@@ -244,6 +244,8 @@ class UNet3DConditionModel(nn.Module):
                 _lib.check(lib.lavie_unet_finalize(handle, stream), "lavie_unet_finalize")
                 if self.freeu != (1.0, 1.0, 1.0, 1.0):
                     _lib.check(lib.lavie_unet_set_freeu(handle, *self.freeu), "lavie_unet_set_freeu")
+                if self.pag != ((), 0):
+                    self._set_pag_engine(lib, handle, *self.pag)
                 if self._lora:
                     keep += self._lora_register(handle, stream)
                     _lib.check(lib.lavie_unet_lora_set_scale(handle, float(self._lora_scale)), "lavie_unet_lora_set_scale")
@@ -536,6 +538,40 @@ class UNet3DConditionModel(nn.Module):
 
     def disable_freeu(self) -> None:
         self.enable_freeu(1.0, 1.0, 1.0, 1.0)
+
+    # ------------------------------------------------------------------ perturbed-attention guidance (diffusers' PAG pipelines)
+    @property
+    def pag(self):
+        """(layers, perturbed) in force; ((), 0) = off."""
+        return self.__dict__.get("_pag", ((), 0))
+
+    @staticmethod
+    def _set_pag_engine(lib, handle, layers, perturbed) -> None:
+        arr = (ctypes.c_char_p * max(len(layers), 1))(*[name.encode() for name in layers])
+        _lib.check(lib.lavie_unet_set_pag(handle, arr, len(layers), int(perturbed)), "lavie_unet_set_pag")
+
+    def set_pag(self, layers, perturbed: int) -> None:
+        """Perturbed-attention guidance (Ahn et al.) in the forwards that follow: in every transformer whose state-dict prefix starts
+        with an entry of `layers` ("mid_block", "down_blocks.2", "up_blocks.1.attentions.0", ...), attn1 of the last `perturbed` batch
+        entries is the identity map on values, to_out(to_v(norm1(x))) (lavie_unet_set_pag).  No layers or perturbed = 0 is off.  The
+        setting lives on the model until disable_pag(); the pipeline makes it for the length of one call."""
+        layers = (layers,) if isinstance(layers, str) else tuple(str(name) for name in layers)
+        perturbed = int(perturbed)
+        if perturbed < 0:
+            raise ValueError(f"set_pag: perturbed={perturbed} must be >= 0")
+        if not layers or perturbed == 0:
+            layers, perturbed = (), 0
+        if self.__dict__.get("_engine"):
+            self._set_pag_engine(_lib.load(), self._engine, layers, perturbed)
+        else:                               # no engine yet: the names are checked against the module tree, as the engine will
+            known = {name.split(".transformer_blocks.")[0] for name, _ in self.named_parameters() if ".transformer_blocks." in name}
+            for entry in layers:
+                if not any(k == entry or k.startswith(entry + ".") for k in known):
+                    raise ValueError(f"set_pag: layers entry {entry!r} selects no transformer")
+        self.__dict__["_pag"] = (layers, perturbed)
+
+    def disable_pag(self) -> None:
+        self.set_pag((), 0)
 
     def enable_graph(self, on: bool = True) -> None:
         """Replay the forward from a hipGraph (lavie_unet_forward_graph).  While on, the timestep and the output live in
