@@ -564,11 +564,7 @@ int UNet::finalize(hipStream_t s) {
 }
 
 int UNet::ensure_tables(int F, hipStream_t s) {
-    auto it = tables_.find(F);
-    if (it != tables_.end()) {          // built before: switching clip length costs nothing and allocates nothing
-        cur_tables_ = &it->second;
-        return 0;
-    }
+    if (tables_.count(F)) return 0;     // built before: switching clip length costs nothing and allocates nothing
     FrameTables ft;
     const int rp = cfg_.rotary_dim / 2;
     std::vector<float> hc((size_t)F * rp), hs((size_t)F * rp);
@@ -604,13 +600,13 @@ int UNet::ensure_tables(int F, hipStream_t s) {
         }
     }
     LAVIE_HIP(hipStreamSynchronize(s));
-    cur_tables_ = &tables_.emplace(F, std::move(ft)).first->second;
+    tables_.emplace(F, std::move(ft));
     return 0;
 }
 
 // ------------------------------------------------------------------ forward
-// The switches that decide which kernels a call runs, as one value: read once at the entry point (forward, cache_context,
-// resnet_forward, transformer_forward) or enumerated by prepare() for its dry runs; nothing below reads the switches themselves
+// The switches that decide which kernels a call runs, as one value: read once where the call enters (call_ctx()) or enumerated by
+// prepare() for its dry runs; nothing below reads the switches themselves
 struct Route {
     int mask;               // fused_mask(): bits 0, 1, 2, 8 the row-resident kernels, 4 the parity upsample convs, 5 producer-side GroupNorm statistics
     bool shared;            // set_cfg_shared_input: the layers in front of the first text cross-attention run on half the batch
@@ -623,10 +619,21 @@ struct FwdCtx {
     DeviceArena* ws;
     bool dry;               // plan only: allocate, launch nothing
     Route route;
-    int B, F, ctx_len;
-    float* gn_ws;           // GroupNorm scratch, gn_workspace_floats(B*F, groups) floats
+    int B, F, H, W, ctx_len;       // H x W: the latent size the call enters with (level 0)
+    const FrameTables* tables;     // of this F; nullptr: none built (a call that runs no temporal attention, a dry run)
+    bool text_cached, text_bound;  // text K / V: cached (cache_context) for this very ctx tensor and shape / bound into the fused kernel's images
+    float* gn_ws = nullptr;        // GroupNorm scratch, gn_workspace_floats(B*F, groups) floats
     const int* labels = nullptr;   // VSR noise level per video (host), num_class_embeds > 0
 };
+
+FwdCtx UNet::call_ctx(hipStream_t s, DeviceArena* ws, int B, int F, int H, int W, const half_t* ctx, int ctx_len, int pag,
+                      const Route* planned) const {
+    const bool dry = planned != nullptr;
+    const auto ft = tables_.find(F);
+    const bool cached = !dry && kv_ctx_ != nullptr && kv_ctx_ == ctx && kv_B_ == B && kv_len_ == ctx_len;
+    return FwdCtx{s, ws, dry, dry ? *planned : Route{fused_mask(), cfg_shared_input_, ln_fold_, pag}, B, F, H, W, ctx_len,
+                  ft == tables_.end() ? nullptr : &ft->second, cached, cached && xb_bound_};
+}
 
 #define LAUNCH(expr)              \
     do {                          \
@@ -691,34 +698,41 @@ struct RowStats {
     bool pending = false;  // `partials` are newer than `stats`
 };
 
-// GroupNorm statistics from the producing kernel (igemm.h colstat_out, round 4).  Every tensor a GroupNorm may read gets a small
-// buffer next to it (same workspace lifetime); the launcher that writes the tensor fills it and describes it in a GnColStat that
-// travels WITH the tensor through the wiring below (explicitly, never keyed by address: workspace addresses are reused).
+// GroupNorm statistics from the producing kernel (igemm.h colstat_out, round 4): the buffer of an Act (engine.h) for a [M, C] tensor
 static size_t colstat_floats(size_t M, int C) { return (M / COLSTAT_REDUCE_ROWS + 8) * (size_t)C * 2; }
-// One implicit GEMM on the forward's stream: plan it, describe its column statistics (cs_buf / cs_out, when asked for), take the
-// split-K slab from the workspace, launch unless this is the dry run.  The dry run passes placeholder addresses and so gets the
-// plan of the real call.  *plan_out (optional) receives the plan.
-static int run_igemm(FwdCtx& c, IgemmParams& p, bool gather, int epilogue, float* cs_buf, GnColStat* cs_out, IgemmPlan* plan_out = nullptr) {
+// A new [rows, C] tensor and its statistics buffer, from the workspace
+static int ws_act(FwdCtx& c, size_t rows, int C, Act* a) {
+    WS(p, half_t, rows * C);
+    WS(cs, float, colstat_floats(rows, C));
+    *a = Act{p, C, GnColStat(), cs};
+    return 0;
+}
+// One implicit GEMM on the forward's stream: plan it, take the split-K slab from the workspace, launch unless this is the dry run.
+// The dry run passes placeholder addresses and so gets the plan of the real call.  *plan_out (optional) receives the plan.
+// THE place that resets the statistics the output tensor carried (out; nullptr: no tensor a GroupNorm reads) and, where it has a
+// buffer, has the epilogue fill it and describes the new ones in out->cs.
+static int run_igemm(FwdCtx& c, IgemmParams& p, bool gather, int epilogue, Act* out, IgemmPlan* plan_out = nullptr) {
     const size_t mark = c.ws->mark();
     IgemmPlan plan;
     const int rc = igemm_run(p, gather, epilogue, c.s, [&](size_t bytes, float** slab) {
         *slab = (float*)c.ws->alloc(bytes);
         LAVIE_CHECK(c.dry || *slab != nullptr, "workspace exhausted (split-K slab)");
         return 0;
-    }, cs_out && (c.route.mask & 32) ? cs_buf : nullptr, c.dry, &plan);
+    }, out && (c.route.mask & 32) ? out->csbuf : nullptr, c.dry, &plan);
     c.ws->release(mark);
-    if (cs_out) *cs_out = GnColStat();
-    if (p.colstat_out) *cs_out = gn_colstat_describe(p, plan, cs_buf);
+    if (out) out->cs = p.colstat_out ? gn_colstat_describe(p, plan, out->csbuf) : GnColStat();
     if (plan_out) *plan_out = plan;
     return rc;
 }
 
-// rs with fold_s (the row sums of LayerNorm-folded weights W): the GEMM consumes the rows' statistics; rs alone: its epilogue emits them
-static int linear(FwdCtx& c, const half_t* A, int lda, const half_t* W, const float* bias, int N, int K, const half_t* R,
-                  half_t* C, int ldc, int M, int epilogue = EPI_LINEAR, RowStats* rs = nullptr, const float* fold_s = nullptr,
-                  int ldw = 0, float* cs_buf = nullptr, GnColStat* cs_out = nullptr) {
+// C[M, w.N] = A[M, w.K] w^T + bias (+ R); the GEGLU epilogue writes [M, w.N / 2].  What the epilogue leaves besides, both stated
+// by every caller: rs = LayerNorm statistics of the output rows (with fold_s, the row sums of LayerNorm-folded weights, the GEMM
+// consumes the statistics of its input rows instead); gn = the tensor C is the contents of, for its GroupNorm statistics
+static int linear(FwdCtx& c, const half_t* A, const LinW& w, const half_t* R, half_t* C, int M, RowStats* rs, Act* gn,
+                  int epilogue = EPI_LINEAR, const float* fold_s = nullptr) {
+    const int N = w.N, K = w.K, ldc = epilogue == EPI_GEGLU ? N / 2 : N;
     IgemmParams p;
-    RUN(igemm_setup_linear(&p, A, lda, W, ldw > 0 ? ldw : K, bias, C, ldc, M, N, K));
+    RUN(igemm_setup_linear(&p, A, K, w.w, K, w.b, C, ldc, M, N, K));
     p.R = R;
     const bool emit = rs && !fold_s;
     p.rowstat_out = emit ? rs->partials : nullptr;
@@ -730,8 +744,11 @@ static int linear(FwdCtx& c, const half_t* A, int lda, const half_t* W, const fl
         }
         p.ln_stats = rs->stats;
     }
+    // column statistics describe a plain dense output only: behind any other epilogue the tensor is left with none
+    const bool dense = epilogue == EPI_LINEAR && ldc == N;
+    if (gn && !dense) gn->cs = GnColStat();
     IgemmPlan plan;
-    RUN(run_igemm(c, p, false, epilogue, epilogue == EPI_LINEAR && ldc == N ? cs_buf : nullptr, cs_out, &plan));
+    RUN(run_igemm(c, p, false, epilogue, dense ? gn : nullptr, &plan));
     if (emit) {
         rs->slots = N / plan.rowstat_cols;      // one slot per wave tile of the kernel that ran
         rs->row_len = N; rs->rows = M; rs->pending = true;
@@ -739,76 +756,71 @@ static int linear(FwdCtx& c, const half_t* A, int lda, const half_t* W, const fl
     return 0;
 }
 
-// 3x3 conv (pad 1) over `nsrc` channel-concatenated sources, plus optional centre-tap shortcut sources.
-static int conv3x3(FwdCtx& c, const half_t* const* src, const int* srcC, int nsrc, const half_t* const* sc, const int* scC,
-                   int nsc, const half_t* W, int ldw, const float* bias, const float* bias2, int ldb2, int rows_per_batch,
-                   const half_t* R, half_t* y, int NI, int Hi, int Wi, int Cout, int stride, int ups, const half_t* zero,
-                   float* cs_buf = nullptr, GnColStat* cs_out = nullptr) {
+// 3x3 conv (pad 1) of x [.., C], plus the optional centre-tap shortcut sources sc1 | sc2 (nullptr: none) as further K segments.
+static int conv3x3(FwdCtx& c, const half_t* x, int C, const Act* sc1, const Act* sc2, const half_t* W, int ldw, const float* bias,
+                   const float* bias2, int ldb2, int rows_per_batch, const half_t* R, Act* y, int NI, int Hi, int Wi, int stride,
+                   int ups, const half_t* zero) {
+    const half_t* sc[2] = {sc1 ? sc1->p : nullptr, sc2 ? sc2->p : nullptr};
+    const int scC[2] = {sc1 ? sc1->C : 0, sc2 ? sc2->C : 0};      // (a source of no channels is no segment)
     IgemmParams p;
-    RUN(igemm_setup_conv3x3(&p, src, srcC, nsrc, sc, scC, nsc, W, ldw, y, NI, Hi, Wi, Cout, stride, ups, zero));
+    RUN(igemm_setup_conv3x3(&p, &x, &C, 1, sc, scC, 2, W, ldw, y->p, NI, Hi, Wi, y->C, stride, ups, zero));
     p.bias = bias; p.bias2 = bias2; p.ldb2 = ldb2; p.rows_per_batch = rows_per_batch; p.R = R;
-    return run_igemm(c, p, true, EPI_LINEAR, cs_buf, cs_out);
+    return run_igemm(c, p, true, EPI_LINEAR, y);
 }
 
 // (taps,1,1) temporal conv over the frame axis of token rows [(b f d), C] (IgemmParams temporal mode; 128-row kernel).
 static int tconv(FwdCtx& c, const half_t* x, int C, const half_t* W, const float* bias, const float* bias2, int ldb2,
-                 const half_t* R, half_t* y, int D, int Cout, int taps, const half_t* zero, float* cs_buf = nullptr,
-                 GnColStat* cs_out = nullptr) {
+                 const half_t* R, Act* y, int D, int taps, const half_t* zero) {
     IgemmParams p;
-    RUN(igemm_setup_temporal_conv(&p, x, C, W, bias, y, c.B, c.F, D, Cout, taps, zero));
+    RUN(igemm_setup_temporal_conv(&p, x, C, W, bias, y->p, c.B, c.F, D, y->C, taps, zero));
     p.bias2 = bias2; p.ldb2 = ldb2; p.rows_per_batch = c.F * D; p.R = R;
-    return run_igemm(c, p, true, EPI_LINEAR, cs_buf, cs_out);      // (round 4) the GroupNorm behind a temporal conv folds its epilogue's sums too
+    return run_igemm(c, p, true, EPI_LINEAR, y);      // (round 4) the GroupNorm behind a temporal conv folds its epilogue's sums too
 }
 
 // ResnetBlock3DCNN (vsr/models/resnet.py:283-315): y = x + conv2(silu(gn(conv1(silu(gn(x))) + temb))); GroupNorm statistics
 // span the whole video (5-D input), eps 1e-6; bias2 = the block's rows of the fused time-embedding projection or nullptr
-// (attention.py:350: temb_channels=None).  y may alias x.
-int UNet::run_temporal_res(FwdCtx& c, const TemporalResW& r, const half_t* x, half_t* y, int C, int D, const float* bias2,
-                           int ldb2, const GnColStat* x_cs, float* y_csbuf, GnColStat* y_cs) {
+// (attention.py:350: temb_channels=None).  y may be x itself (in place): norm1 has taken x's statistics, and in stream order read
+// their buffer, long before conv2's epilogue replaces them.
+int UNet::run_temporal_res(FwdCtx& c, const TemporalResW& r, const Act& x, Act* y, int D, const float* bias2, int ldb2) {
+    const int C = x.C;
     const size_t M = (size_t)c.B * c.F * D;
     const int P = c.F * D;
     const size_t mark = c.ws->mark();
     WS(nrm, half_t, M * C);
-    WS(h1, half_t, M * C);
-    WS(h1cs, float, colstat_floats(M, C));
-    GnColStat h1_cs;
-    // x_cs (may be null / empty): statistics the producer of x left; y_csbuf / y_cs (may be null): where conv2's go.  y may alias x
-    // and y_csbuf the buffer x_cs points into: norm1's fold has read it (stream order) long before conv2's epilogue writes it
-    LAUNCH(launch_group_norm(x, C, nullptr, 0, c.B, P, cfg_.norm_groups, r.n1.g, r.n1.b, 1e-6f, true, c.gn_ws, nrm, c.s, x_cs));
+    Act h1;
+    RUN(ws_act(c, M, C, &h1));
+    LAUNCH(launch_group_norm(x.p, C, nullptr, 0, c.B, P, cfg_.norm_groups, r.n1.g, r.n1.b, 1e-6f, true, c.gn_ws, nrm, c.s, &x.cs));
     TRACE("tres.norm1", nrm, M, C);
-    RUN(tconv(c, nrm, C, r.w1, r.b1, bias2, ldb2, nullptr, h1, D, C, r.taps1, zero_page_, h1cs, &h1_cs));
-    TRACE("tres.conv1", h1, M, C);
-    LAUNCH(launch_group_norm(h1, C, nullptr, 0, c.B, P, cfg_.norm_groups, r.n2.g, r.n2.b, 1e-6f, true, c.gn_ws, nrm, c.s, &h1_cs));
+    RUN(tconv(c, nrm, C, r.w1, r.b1, bias2, ldb2, nullptr, &h1, D, r.taps1, zero_page_));
+    TRACE("tres.conv1", h1.p, M, C);
+    LAUNCH(launch_group_norm(h1.p, C, nullptr, 0, c.B, P, cfg_.norm_groups, r.n2.g, r.n2.b, 1e-6f, true, c.gn_ws, nrm, c.s, &h1.cs));
     TRACE("tres.norm2", nrm, M, C);
-    if (y_cs) *y_cs = GnColStat();
-    RUN(tconv(c, nrm, C, r.w2, r.b2, nullptr, 0, x, y, D, C, 3, zero_page_, y_csbuf, y_cs));
-    TRACE("tres.conv2", y, M, C);
+    RUN(tconv(c, nrm, C, r.w2, r.b2, nullptr, 0, x.p, y, D, 3, zero_page_));
+    TRACE("tres.conv2", y->p, M, C);
     c.ws->release(mark);
     return 0;
 }
 
 // TemporalModule3D.forward (vsr/models/temporal_module.py:153-178): y = x + shift_conv(resblocks_3d_s(resblocks_3d_t(x))).
 // y must not alias x when x is still referenced as a skip tensor.
-int UNet::run_temporal_module(FwdCtx& c, const TemporalModuleW& m, const half_t* x, half_t* y, const float* tproj,
-                              int ld_tproj, int H, int W, const GnColStat* x_cs, float* y_csbuf, GnColStat* y_cs) {
+int UNet::run_temporal_module(FwdCtx& c, const TemporalModuleW& m, const Act& x, Act* y, const float* tproj, int ld_tproj, int H, int W) {
     const int C = m.C, D = H * W;
     const size_t M = (size_t)c.B * c.F * D;
     const size_t mark = c.ws->mark();
-    WS(h1, half_t, M * C);
-    WS(h2, half_t, M * C);
+    WS(h1p, half_t, M * C);
+    WS(h2p, half_t, M * C);
     WS(h1cs, float, colstat_floats(M, C));
-    GnColStat h1_cs;
-    RUN(run_temporal_res(c, m.t, x, h1, C, D, tproj + m.t_temb_off, ld_tproj, x_cs, h1cs, &h1_cs));
-    RUN(run_resnet(c, m.s, h1, C, nullptr, 0, tproj + m.s.temb_off, ld_tproj, h2, H, W, &h1_cs));
-    RUN(linear(c, h2, C, m.shift.w, m.shift.b, C, C, x, y, C, (int)M, EPI_LINEAR, nullptr, nullptr, 0, y_csbuf, y_cs));
-    TRACE("tmodule.shift", y, M, C);
+    Act h1{h1p, C, GnColStat(), h1cs}, h2{h2p, C};      // (h2's one consumer is no GroupNorm)
+    RUN(run_temporal_res(c, m.t, x, &h1, D, tproj + m.t_temb_off, ld_tproj));
+    RUN(run_resnet(c, m.s, h1, nullptr, tproj + m.s.temb_off, ld_tproj, &h2, H, W));
+    RUN(linear(c, h2.p, m.shift, x.p, y->p, (int)M, nullptr, y));
+    TRACE("tmodule.shift", y->p, M, C);
     c.ws->release(mark);
     return 0;
 }
 
-int UNet::run_resnet(FwdCtx& c, const ResnetW& r, const half_t* x1, int C1, const half_t* x2, int C2, const float* tproj,
-                     int ld_tproj, half_t* y, int H, int W, const GnColStat* cs1, const GnColStat* cs2, float* y_csbuf,
-                     GnColStat* y_cs) {
+int UNet::run_resnet(FwdCtx& c, const ResnetW& r, const Act& x1, const Act* x2, const float* tproj, int ld_tproj, Act* y, int H, int W) {
+    const int C1 = x1.C, C2 = x2 ? x2->C : 0;
     LAVIE_CHECK(C1 + C2 == r.cin, "resnet %s: got %d+%d input channels, expected %d", r.prefix.c_str(), C1, C2, r.cin);
     const int G = cfg_.norm_groups;
     const int NI = c.B * c.F;
@@ -816,37 +828,25 @@ int UNet::run_resnet(FwdCtx& c, const ResnetW& r, const half_t* x1, int C1, cons
     const size_t M = (size_t)NI * H * W;
     const size_t mark = c.ws->mark();
     WS(nrm, half_t, M * r.cin);
-    WS(h1, half_t, M * r.cout);
+    WS(h1p, half_t, M * r.cout);
     WS(n2, half_t, M * r.cout);
     WS(h1cs, float, colstat_floats(M, r.cout));      // GroupNorm statistics of h1, written by conv1's epilogue
-    GnColStat h1_cs;
-    if (y_cs) *y_cs = GnColStat();
+    Act h1{h1p, r.cout, GnColStat(), h1cs};
     const float eps = r.eps > 0.f ? r.eps : cfg_.norm_eps;
-    // norm1: statistics from the producers of x1 / x2 where they left them (cs1 / cs2), else the statistics pass
-    LAUNCH(launch_group_norm(x1, C1, x2, C2, c.B, P, G, r.n1.g, r.n1.b, eps, true, c.gn_ws, nrm, c.s, cs1, cs2));
+    // norm1: statistics from the producers of x1 / x2 where they left them, else the statistics pass
+    LAUNCH(launch_group_norm(x1.p, C1, x2 ? x2->p : nullptr, C2, c.B, P, G, r.n1.g, r.n1.b, eps, true, c.gn_ws, nrm, c.s, &x1.cs,
+                             x2 ? &x2->cs : nullptr));
     TRACE("resnet.norm1", nrm, M, r.cin);
-    {
-        const half_t* src[1] = {nrm};
-        const int srcC[1] = {r.cin};
-        RUN(conv3x3(c, src, srcC, 1, nullptr, nullptr, 0, r.w1, 9 * r.cin, r.b1, tproj, ld_tproj, P, nullptr, h1, NI, H, W,
-                    r.cout, 1, 0, zero_page_, h1cs, &h1_cs));
-    }
-    TRACE("resnet.conv1", h1, M, r.cout);
-    LAUNCH(launch_group_norm(h1, r.cout, nullptr, 0, c.B, P, G, r.n2.g, r.n2.b, eps, true, c.gn_ws, n2, c.s, &h1_cs));
+    RUN(conv3x3(c, nrm, r.cin, nullptr, nullptr, r.w1, 9 * r.cin, r.b1, tproj, ld_tproj, P, nullptr, &h1, NI, H, W, 1, 0, zero_page_));
+    TRACE("resnet.conv1", h1.p, M, r.cout);
+    LAUNCH(launch_group_norm(h1.p, r.cout, nullptr, 0, c.B, P, G, r.n2.g, r.n2.b, eps, true, c.gn_ws, n2, c.s, &h1.cs));
     TRACE("resnet.norm2", n2, M, r.cout);
-    {
-        const half_t* src[1] = {n2};
-        const int srcC[1] = {r.cout};
-        const half_t* sc[2] = {x1, x2};
-        const int scC[2] = {C1, C2};
-        const int nsc = r.shortcut ? (x2 ? 2 : 1) : 0;
-        // The 1x1 conv_shortcut rides in conv2 as extra centre-tap K segments — which keeps conv2 off the halo-patch kernel (it
-        // takes 9-tap segments only).  Running the shortcut as its own GEMM in front of a halo-patch conv2 was measured slower
-        // (round 3, profiles/r03_ab_split_shortcut.txt: forward 21.33 -> 21.41 ms) and is not built.
-        RUN(conv3x3(c, src, srcC, 1, sc, scC, nsc, r.w2, r.ldw2, r.b2, nullptr, 0, 1, r.shortcut ? nullptr : x1, y, NI, H, W,
-                    r.cout, 1, 0, zero_page_, y_csbuf, y_cs));
-    }
-    TRACE("resnet.conv2", y, M, r.cout);
+    // The 1x1 conv_shortcut rides in conv2 as extra centre-tap K segments — which keeps conv2 off the halo-patch kernel (it
+    // takes 9-tap segments only).  Running the shortcut as its own GEMM in front of a halo-patch conv2 was measured slower
+    // (round 3, profiles/r03_ab_split_shortcut.txt: forward 21.33 -> 21.41 ms) and is not built.
+    RUN(conv3x3(c, n2, r.cout, r.shortcut ? &x1 : nullptr, r.shortcut ? x2 : nullptr, r.w2, r.ldw2, r.b2, nullptr, 0, 1,
+                r.shortcut ? nullptr : x1.p, y, NI, H, W, 1, 0, zero_page_));
+    TRACE("resnet.conv2", y->p, M, r.cout);
     c.ws->release(mark);
     return 0;
 }
@@ -889,8 +889,7 @@ static BlockRoute block_route(const lavie_unet_config& cfg, const TransformerW& 
     return b;
 }
 
-int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const half_t* ctx, int H, int W, bool shared_prefix,
-                          GnColStat* x_cs, float* x_csbuf) {
+int UNet::run_transformer(FwdCtx& c, const TransformerW& t, Act& x, const half_t* ctx, int H, int W, bool shared_prefix) {
     const int C = t.C, G = cfg_.norm_groups, heads = cfg_.heads, dh = C / heads;
     const int NI = c.B * c.F, D = H * W;
     const int T = NI * D;
@@ -903,17 +902,14 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
     WS(wide, half_t, (size_t)T * 4 * C);          // qkv [T,3C] / GEGLU output [T,4C] / q2 [T,C]
     WS(kv2, half_t, (size_t)c.B * c.ctx_len * 2 * C);
     const size_t ti = &t - transformers_.data();
-    // text K/V computed once per context by cache_context(): valid for this very ctx tensor and shape only
-    const bool kv_cached = !c.dry && kv_ctx_ != nullptr && kv_ctx_ == ctx && kv_B_ == c.B && kv_len_ == c.ctx_len && ti < kv2_cache_.size();
-    const BlockRoute br = block_route(cfg_, t, c.route, c.F, D, c.ctx_len, kv_cached && xb_bound_ && xb_img_[ti] != nullptr);
+    const BlockRoute br = block_route(cfg_, t, c.route, c.F, D, c.ctx_len, c.text_bound && xb_img_[ti] != nullptr);
     const bool fold = c.route.ln_fold;
 
     // VSR: ResnetBlock3DCNN (3,1,1) on the block input, before the residual is taken (vsr/models/attention.py:395-400)
     if (t.tres.present) {
         // in place; conv2's epilogue leaves the new statistics where the old ones were (the per-frame GroupNorm below takes them only
         // if its frames are whole blocks: the temporal tiles of the halo-patch kernel span a video, GnColStat::span)
-        GnColStat in_cs = x_cs ? *x_cs : GnColStat();
-        RUN(run_temporal_res(c, t.tres, x, x, C, D, nullptr, 0, &in_cs, x_csbuf, x_cs));
+        RUN(run_temporal_res(c, t.tres, x, &x, D, nullptr, 0));
     }
     // shared_prefix (set_cfg_shared_input; base block only): both halves of the batch are identical up to the text
     // cross-attention, so GroupNorm, proj_in, the qkv projection and the self-attention run on the first half (NIp frames,
@@ -939,18 +935,17 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
     // THE projection behind a LayerNorm, `rows` rows of tx -> wide.  Folded: one GEMM on the raw rows that takes their statistics;
     // otherwise the LayerNorm into `ln`, then the plain GEMM
     auto ln_proj = [&](const LnProj& p, bool folded, int rows, int epilogue = EPI_LINEAR) -> int {
-        const int ldc = epilogue == EPI_GEGLU ? p.N / 2 : p.N;
-        if (folded) return linear(c, tx, C, p.fw, p.fb, p.N, C, nullptr, wide, ldc, rows, epilogue, &rs, p.fs);
+        if (folded) return linear(c, tx, LinW{p.fw, p.fb, p.N, C}, nullptr, wide, rows, &rs, nullptr, epilogue, p.fs);
         LAUNCH(launch_layernorm(tx, (t.*p.ln).g, (t.*p.ln).b, ln, rows, C, 1e-5f, c.s));
-        return linear(c, ln, C, p.w, p.b, p.N, C, nullptr, wide, ldc, rows, epilogue);
+        return linear(c, ln, LinW{p.w, p.b, p.N, C}, nullptr, wide, rows, nullptr, nullptr, epilogue);
     };
     // Text attention through GEMMs (attn2; attn1 of the VSR only_cross_attention levels): q of every token, K | V once per video,
     // from the cache or computed here
-    auto text_attention = [&](const LnProj& q, const half_t* wkv, const std::vector<half_t*>& cache) -> int {
+    auto text_attention = [&](const LnProj& q, half_t* wkv, const std::vector<half_t*>& cache) -> int {
         RUN(ln_proj(q, fold, T));
         const half_t* kvc = kv2;
-        if (kv_cached) kvc = cache[ti];
-        else RUN(linear(c, ctx, X, wkv, nullptr, 2 * C, X, nullptr, kv2, 2 * C, c.B * c.ctx_len));
+        if (c.text_cached) kvc = cache[ti];
+        else RUN(linear(c, ctx, LinW{wkv, nullptr, 2 * C, X}, nullptr, kv2, c.B * c.ctx_len, nullptr, nullptr));
         if (!c.dry) {
             AttnParams a;
             a.q = wide; a.ldq = C; a.k = kvc; a.ldk = 2 * C; a.v = kvc + C; a.ldv = 2 * C;
@@ -961,12 +956,12 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
     };
     if (br.fused_head) {
         // Round 4: the norm's statistics become per-(frame, channel) scale / shift pairs and nothing between x and (tx, qkv) touches memory
-        LAUNCH(launch_group_norm(x, C, nullptr, 0, NIp, D, G, t.gn.g, t.gn.b, 1e-6f, false, c.gn_ws, nullptr, c.s, x_cs, nullptr, gn_ab));
-        LAUNCH(launch_proj_qkv(x, gn_ab, D, t.pq_img, t.pin.b, t.ln1.g, t.ln1.b, 1e-5f, tx, wide, Tp, C, c.s));
+        LAUNCH(launch_group_norm(x.p, C, nullptr, 0, NIp, D, G, t.gn.g, t.gn.b, 1e-6f, false, c.gn_ws, nullptr, c.s, &x.cs, nullptr, gn_ab));
+        LAUNCH(launch_proj_qkv(x.p, gn_ab, D, t.pq_img, t.pin.b, t.ln1.g, t.ln1.b, 1e-5f, tx, wide, Tp, C, c.s));
     } else {
         // per-frame GroupNorm (eps 1e-6) + 1x1 proj_in (attention.py:369-373)
-        LAUNCH(launch_group_norm(x, C, nullptr, 0, NIp, D, G, t.gn.g, t.gn.b, 1e-6f, false, c.gn_ws, ln, c.s, x_cs));
-        RUN(linear(c, ln, C, t.pin.w, t.pin.b, C, C, nullptr, tx, C, Tp, EPI_LINEAR, emit(br.emit_pin)));
+        LAUNCH(launch_group_norm(x.p, C, nullptr, 0, NIp, D, G, t.gn.g, t.gn.b, 1e-6f, false, c.gn_ws, ln, c.s, &x.cs));
+        RUN(linear(c, ln, t.pin, nullptr, tx, Tp, emit(br.emit_pin), nullptr));
     }
     if (!shared_prefix) TRACE("block.proj_in", tx, T, C);
 
@@ -1002,21 +997,21 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
     if (br.text != CROSS_NONE) {
         LAUNCH(launch_cross_block(br.text, att, tx, tx, T, c.F * D, C, heads, xb_img_[ti], t.o1.b, t.ln2.g, t.ln2.b, t.o2.b, c.ctx_len, scale, 1e-5f, c.s));
     } else {       // ... or GEMMs
-        RUN(linear(c, att, C, t.o1.w, t.o1.b, C, C, tx, tx, C, T, EPI_LINEAR, emit(br.emit_o1)));
+        RUN(linear(c, att, t.o1, tx, tx, T, emit(br.emit_o1), nullptr));
         TRACE("block.attn1.to_out", tx, T, C);
 
         // text cross-attention (attention.py:524-534); K/V once per video instead of once per frame (364)
         RUN(text_attention(t.q2, t.wkv2, kv2_cache_));
         TRACE("block.attn2", att, T, C);
-        RUN(linear(c, att, C, t.o2.w, t.o2.b, C, C, tx, tx, C, T, EPI_LINEAR, emit(br.emit_o2)));
+        RUN(linear(c, att, t.o2, tx, tx, T, emit(br.emit_o2), nullptr));
     }
     TRACE("block.after text", tx, T, C);
 
     auto temporal = [&]() -> int {
         // temporal self-attention over frames, tokens stay in (b f) d order (attention.py:548-555)
         if (br.fused_t) {      // norm_temp -> q|k|v -> rotary / bias / softmax / PV -> to_out -> + residual in ONE kernel, in place
-            LAUNCH(launch_temporal_block(tx, tx, c.B, c.F, D, C, heads, t.tb_img, t.lnt.g, t.lnt.b, t.ot.b, cur_tables_->relbias[ti],
-                                         cur_tables_->rot_cos, cur_tables_->rot_sin, cfg_.rotary_dim, scale, 1e-5f, c.s));
+            LAUNCH(launch_temporal_block(tx, tx, c.B, c.F, D, C, heads, t.tb_img, t.lnt.g, t.lnt.b, t.ot.b, c.tables->relbias[ti],
+                                         c.tables->rot_cos, c.tables->rot_sin, cfg_.rotary_dim, scale, 1e-5f, c.s));
             return 0;
         }
         RUN(ln_proj(t.qkvt, br.fold_t, T));
@@ -1025,12 +1020,12 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
         if (!c.dry) {
             TemporalParams tp;
             tp.qkv = wide; tp.ld = 3 * C; tp.o = att; tp.ldo = C; tp.B = c.B; tp.F = c.F; tp.D = D; tp.heads = heads; tp.dh = dh;
-            tp.bias = cur_tables_->relbias[ti]; tp.rot_cos = cur_tables_->rot_cos; tp.rot_sin = cur_tables_->rot_sin; tp.rot_dim = cfg_.temporal_plain ? 0 : cfg_.rotary_dim; tp.scale = scale;
+            tp.bias = c.tables->relbias[ti]; tp.rot_cos = c.tables->rot_cos; tp.rot_sin = c.tables->rot_sin; tp.rot_dim = cfg_.temporal_plain ? 0 : cfg_.rotary_dim; tp.scale = scale;
             RUN(launch_temporal_attention(tp, c.s));
         }
         TRACE("temporal.qkv", wide, T, 3 * C);
         TRACE("temporal.attention", att, T, C);
-        RUN(linear(c, att, C, t.ot.w, t.ot.b, C, C, tx, tx, C, T, EPI_LINEAR, emit(br.emit_ot)));
+        RUN(linear(c, att, t.ot, tx, tx, T, emit(br.emit_ot), nullptr));
         return 0;
     };
     auto feed_forward = [&]() -> int {
@@ -1044,7 +1039,7 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
         }
         RUN(ln_proj(t.ff1, br.fold_ff, T, EPI_GEGLU));
         // (K = 4C: the planner may pick another kernel than for the K = C producers, hence a slot count per producer)
-        RUN(linear(c, wide, 4 * C, t.ff2.w, t.ff2.b, C, 4 * C, tx, tx, C, T, EPI_LINEAR, emit(br.emit_ff2)));
+        RUN(linear(c, wide, t.ff2, tx, tx, T, emit(br.emit_ff2), nullptr));
         return 0;
     };
     // base block order: temporal -> feed-forward (attention.py:548-560); interpolation block: feed-forward -> temporal
@@ -1062,26 +1057,22 @@ int UNet::run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const hal
     }
 
     // 1x1 proj_out + residual, in place on the block input (attention.py:394-401)
-    // (its epilogue leaves the GroupNorm statistics of the block's output for the next resnet / skip consumer: x_cs is rewritten)
-    RUN(linear(c, tx, C, t.pout.w, t.pout.b, C, C, x, x, C, T, EPI_LINEAR, nullptr, nullptr, 0, x_csbuf, x_cs));
-    TRACE("block.proj_out", x, T, C);
+    // (its epilogue leaves the GroupNorm statistics of the block's output for the next resnet / skip consumer: x.cs is rewritten)
+    RUN(linear(c, tx, t.pout, x.p, x.p, T, nullptr, &x));
+    TRACE("block.proj_out", x.p, T, C);
     c.ws->release(mark);
     return 0;
 }
 
-int UNet::run_conv(FwdCtx& c, const half_t* x, int C, const SamplerW& w, half_t* y, int Hi, int Wi, int stride, int ups, float* cs_buf,
-                   GnColStat* cs_out) {
-    if (cs_out) *cs_out = GnColStat();
-    const half_t* src[1] = {x};
-    const int srcC[1] = {C};
+int UNet::run_conv(FwdCtx& c, const Act& x, const SamplerW& w, Act* y, int Hi, int Wi, int stride, int ups) {
+    const int C = x.C;
     if (ups && stride == 1 && w.wpar && (c.route.mask & 16)) {
         // Upsample3D (resnet.py:44-79): the 3x3 conv of the nearest-x2 image as four 2x2 convs on the source image, one per
         // output parity, on the halo-patch kernel (igemm_patch.hip MODE 3): 4 C instead of 9 C multiply-adds per output element
         IgemmParams p;
-        if (igemm_setup_parity_upsample(&p, x, C, w.wpar, w.b, y, c.B * c.F, Hi, Wi, zero_page_)) return run_igemm(c, p, true, EPI_LINEAR, cs_buf, cs_out);
+        if (igemm_setup_parity_upsample(&p, x.p, C, w.wpar, w.b, y->p, c.B * c.F, Hi, Wi, zero_page_)) return run_igemm(c, p, true, EPI_LINEAR, y);
     }
-    return conv3x3(c, src, srcC, 1, nullptr, nullptr, 0, w.w, 9 * C, w.b, nullptr, 0, 1, nullptr, y, c.B * c.F, Hi, Wi, C, stride,
-                   ups, zero_page_, cs_buf, cs_out);
+    return conv3x3(c, x.p, C, nullptr, nullptr, w.w, 9 * C, w.b, nullptr, 0, 1, nullptr, y, c.B * c.F, Hi, Wi, stride, ups, zero_page_);
 }
 
 int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const half_t* ctx, half_t* out) {
@@ -1123,15 +1114,12 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
 
     std::vector<int> Hs(L), Ws(L);
     for (int l = 0; l < L; ++l) {
-        Hs[l] = l == 0 ? prep_H_ : (Hs[l - 1] - 1) / 2 + 1;
-        Ws[l] = l == 0 ? prep_W_ : (Ws[l - 1] - 1) / 2 + 1;
+        Hs[l] = l == 0 ? c.H : (Hs[l - 1] - 1) / 2 + 1;
+        Ws[l] = l == 0 ? c.W : (Ws[l - 1] - 1) / 2 + 1;
     }
-    // prep_H_/prep_W_ hold the CURRENT call's size while run() executes (set by forward()/prepare())
     auto rows = [&](int l) { return (size_t)NI * Hs[l] * Ws[l]; };
 
-    // An activation travels with the GroupNorm statistics its producer left (and the buffer they are in): the running one and the skips
-    struct Act { half_t* p; int C; GnColStat cs; float* csbuf; };
-    Act x{};
+    Act x;      // the running activation; the skips keep theirs
     std::vector<Act> skips;
     size_t ri = 0, ti = 0, mi = 0;
     const bool tmod = cfg.vsr_temporal_modules != 0;
@@ -1149,7 +1137,7 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
     const bool shared = c.route.shared && shared_ok && c.route.pag == 0;
     if (shared && !c.dry && debug_check_shared()) {
         // LAVIE_DEBUG_CHECK_SHARED=1: verify the caller's promise (sample[b] == sample[b + B/2], equal timesteps) before trusting it
-        const size_t half_bytes = (size_t)(c.B / 2) * cfg.in_channels * c.F * prep_H_ * prep_W_ * sizeof(half_t);
+        const size_t half_bytes = (size_t)(c.B / 2) * cfg.in_channels * c.F * c.H * c.W * sizeof(half_t);
         std::vector<char> h0(half_bytes), h1(half_bytes);
         std::vector<float> ts(c.B);
         LAVIE_HIP(hipStreamSynchronize(c.s));
@@ -1170,38 +1158,34 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
     // The steps of the walk below: each takes a new tensor and its statistics buffer from the workspace, runs on x, and advances x
     auto resnet = [&](FwdCtx& cc, int l, const Act* skip) -> int {
         const ResnetW& r = resnets_[ri++];
-        WS(y, half_t, rows(l) * r.cout);
-        WS(ycs, float, colstat_floats(rows(l), r.cout));
-        Act ny{y, r.cout, GnColStat(), ycs};
-        RUN(run_resnet(cc, r, x.p, x.C, skip ? skip->p : nullptr, skip ? skip->C : 0, tproj + r.temb_off, tproj_.N, y, Hs[l], Ws[l], &x.cs,
-                       skip ? &skip->cs : nullptr, ycs, &ny.cs));
-        x = ny;
+        Act y;
+        RUN(ws_act(c, rows(l), r.cout, &y));
+        RUN(run_resnet(cc, r, x, skip, tproj + r.temb_off, tproj_.N, &y, Hs[l], Ws[l]));
+        x = y;
         return 0;
     };
     auto transformer = [&](int l, bool shared_prefix) {      // in place on x
-        return run_transformer(c, transformers_[ti++], x.p, ctx, Hs[l], Ws[l], shared_prefix, &x.cs, x.csbuf);
+        return run_transformer(c, transformers_[ti++], x, ctx, Hs[l], Ws[l], shared_prefix);
     };
     auto resample = [&](const SamplerW& w, int l, int l_out) -> int {      // down: stride 2; up: nearest x2 in front of the conv
-        WS(y, half_t, rows(l_out) * x.C);
-        WS(ycs, float, colstat_floats(rows(l_out), x.C));
-        Act ny{y, x.C, GnColStat(), ycs};
-        RUN(run_conv(c, x.p, x.C, w, y, Hs[l], Ws[l], l_out > l ? 2 : 1, l_out < l ? 1 : 0, ycs, &ny.cs));
-        x = ny;
+        Act y;
+        RUN(ws_act(c, rows(l_out), x.C, &y));
+        RUN(run_conv(c, x, w, &y, Hs[l], Ws[l], l_out > l ? 2 : 1, l_out < l ? 1 : 0));
+        x = y;
         return 0;
     };
     auto temporal_module = [&](int l) -> int {      // VSR; into a NEW buffer: x itself may stay alive as a skip
-        WS(yt, half_t, rows(l) * x.C);
-        WS(ytcs, float, colstat_floats(rows(l), x.C));
-        Act ny{yt, x.C, GnColStat(), ytcs};
-        RUN(run_temporal_module(c, tmods_[mi++], x.p, yt, tproj, tproj_.N, Hs[l], Ws[l], &x.cs, ytcs, &ny.cs));
-        x = ny;
+        Act y;
+        RUN(ws_act(c, rows(l), x.C, &y));
+        RUN(run_temporal_module(c, tmods_[mi++], x, &y, tproj, tproj_.N, Hs[l], Ws[l]));
+        x = y;
         return 0;
     };
 
     WS(x0, half_t, rows(0) * C0);
     LAUNCH(launch_conv_in(sample, conv_in_w_, conv_in_b_, x0, ch.B, cfg.in_channels, c.F, Hs[0], Ws[0], C0, c.s));
     RUN(dup_half(x0, rows(0), C0));
-    x = Act{x0, C0, GnColStat(), nullptr};           // conv_in leaves no statistics: its two consumers run the statistics pass
+    x = Act{x0, C0};           // conv_in leaves no statistics: its two consumers run the statistics pass
     skips.push_back(x);
 
     for (int l = 0; l < L; ++l) {
@@ -1287,8 +1271,8 @@ int UNet::prepare(int B, int F, int H, int W, int ctx_len) {
         plan.init_virtual();
         // (Route::pag = 0: perturbed-attention guidance runs every GEMM on all rows and takes nothing from the workspace that the plain
         // branch does not, so the plan holds for a setting made before or after; with it the shared-input variants would go unplanned)
-        FwdCtx c{nullptr, &plan, true, Route{masks[variant >> 1], (variant & 1) != 0, ln_fold_, 0}, B, F, ctx_len, nullptr};
-        prep_H_ = H; prep_W_ = W;
+        const Route route{masks[variant >> 1], (variant & 1) != 0, ln_fold_, 0};
+        FwdCtx c = call_ctx(nullptr, &plan, B, F, H, W, nullptr, ctx_len, 0, &route);
         RUN(run(c, nullptr, nullptr, nullptr, nullptr));
         if (plan.peak() > peak) peak = plan.peak();
     }
@@ -1405,9 +1389,8 @@ int UNet::forward(const half_t* sample, const float* timesteps, const half_t* ct
     ws_.release(0);
     const int pag = pag_route("forward", B);
     if (pag < 0) return -1;
-    FwdCtx c{stream, &ws_, false, Route{fused_mask(), cfg_shared_input_, ln_fold_, pag}, B, F, ctx_len, nullptr};
+    FwdCtx c = call_ctx(stream, &ws_, B, F, H, W, ctx, ctx_len, pag);
     c.labels = class_labels_host;
-    prep_H_ = H; prep_W_ = W;
     return run(c, sample, timesteps, ctx, out);
 }
 
@@ -1456,11 +1439,11 @@ int UNet::cache_context(const half_t* ctx, int B, int ctx_len, hipStream_t strea
         xb_img_bytes_ = xb_bytes;
     }
     ws_.release(0);
-    FwdCtx c{stream, &ws_, false, Route{fused_mask(), cfg_shared_input_, ln_fold_}, B, 1, ctx_len, nullptr};
+    FwdCtx c = call_ctx(stream, &ws_, B, 1, 0, 0, ctx, ctx_len, /*pag (attn1 only)=*/0);
     for (size_t i = 0; i < transformers_.size(); ++i) {
         const TransformerW& t = transformers_[i];
-        RUN(linear(c, ctx, X, t.wkv2, nullptr, 2 * t.C, X, nullptr, kv2_cache_[i], 2 * t.C, (int)rows));
-        if (t.attn1_cross) RUN(linear(c, ctx, X, t.wkv1, nullptr, 2 * t.C, X, nullptr, kv1_cache_[i], 2 * t.C, (int)rows));
+        RUN(linear(c, ctx, LinW{t.wkv2, nullptr, 2 * t.C, X}, nullptr, kv2_cache_[i], (int)rows, nullptr, nullptr));
+        if (t.attn1_cross) RUN(linear(c, ctx, LinW{t.wkv1, nullptr, 2 * t.C, X}, nullptr, kv1_cache_[i], (int)rows, nullptr, nullptr));
     }
     // the fused cross-attention kernel streams K / V with its weights: one image per video, written here once per context
     xb_bound_ = false;
@@ -1669,11 +1652,13 @@ int UNet::resnet_forward(const char* prefix, const half_t* x1, int C1, const hal
     DeviceArena local;
     const size_t M = (size_t)B * F * H * W;
     RUN(local.init_fixed((M * (r->cin + 2 * r->cout)) * sizeof(half_t) + (size_t)B * r->cout * 4 + colstat_floats(M, r->cout) * sizeof(float) + (4 << 20)));
-    FwdCtx c{stream, &local, false, Route{fused_mask(), cfg_shared_input_, ln_fold_}, B, F, 0, nullptr};
+    FwdCtx c = call_ctx(stream, &local, B, F, H, W, nullptr, 0, /*pag (attn1 only)=*/0);
     c.gn_ws = (float*)local.alloc(gn_workspace_floats(B * F, cfg_.norm_groups) * sizeof(float));
     float* tproj = (float*)local.alloc((size_t)B * r->cout * sizeof(float));
     RUN(launch_gemv(temb, tproj_.w + (size_t)r->temb_off * tproj_.K, tproj_.b + r->temb_off, tproj, B, r->cout, tproj_.K, 1, 0, stream));
-    RUN(run_resnet(c, *r, x1, C1, C2 ? x2 : nullptr, C2, tproj, r->cout, y, H, W));
+    const Act a1{const_cast<half_t*>(x1), C1}, a2{const_cast<half_t*>(x2), C2};      // (no producer statistics in, none asked for out)
+    Act ay{y, r->cout};
+    RUN(run_resnet(c, *r, a1, C2 ? &a2 : nullptr, tproj, r->cout, &ay, H, W));
     LAVIE_HIP(hipStreamSynchronize(stream));     // the private workspace dies with this frame
     return 0;
 }
@@ -1691,9 +1676,10 @@ int UNet::transformer_forward(const char* prefix, half_t* x, const half_t* ctx, 
     DeviceArena local;
     const size_t T = (size_t)B * F * H * W;
     RUN(local.init_fixed(T * t->C * 7 * sizeof(half_t) + (size_t)B * ctx_len * 2 * t->C * sizeof(half_t) + (4 << 20)));
-    FwdCtx c{stream, &local, false, Route{fused_mask(), cfg_shared_input_, ln_fold_, pag}, B, F, ctx_len, nullptr};
+    FwdCtx c = call_ctx(stream, &local, B, F, H, W, ctx, ctx_len, pag);
     c.gn_ws = (float*)local.alloc(gn_workspace_floats(B * F, cfg_.norm_groups) * sizeof(float));
-    RUN(run_transformer(c, *t, x, ctx, H, W));
+    Act ax{x, t->C};
+    RUN(run_transformer(c, *t, ax, ctx, H, W));
     LAVIE_HIP(hipStreamSynchronize(stream));
     return 0;
 }

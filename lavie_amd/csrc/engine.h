@@ -108,7 +108,26 @@ struct TemporalModuleW {
     LinW shift;
 };
 
-struct FwdCtx;   // per-call state (engine.cpp), the call's Route (its switches, as one value) among it
+struct Route;    // the switches that decide which kernels a call runs, as one value (engine.cpp)
+struct FwdCtx;   // per-call state (engine.cpp): stream, workspace, shape, the call's Route, its frame tables, the state of the text cache
+
+// An activation of the forward: [rows, C] fp16 and the GroupNorm statistics its producer left.  Every tensor a GroupNorm may read
+// has a small buffer next to it (same workspace lifetime); the GEMM that writes the tensor fills the buffer and describes it in `cs`,
+// and the description travels with the tensor, never keyed by address (workspace addresses are reused).  An input is a const Act&
+// (a second, optional one a const Act*); an output is an Act* whose p and csbuf the caller has set and whose cs the producer
+// fills; a step that works in place takes an Act&.
+struct Act {
+    half_t* p = nullptr;
+    int C = 0;
+    GnColStat cs;                                   // empty: the producer left none, a GroupNorm runs its statistics pass
+    float* csbuf = nullptr;                         // where a producer of p leaves them; nullptr: it is asked for none
+};
+
+// per-F tables, built once per clip length and kept (the VSR chunk driver alternates F = 8 and F = 5)
+struct FrameTables {
+    float* rot_cos = nullptr; float* rot_sin = nullptr;
+    std::vector<float*> relbias;                    // one [heads, F, F] per transformer
+};
 
 // One registered low-rank adapter target (lavie_unet_lora_*): the projection's rows inside the packed weights and what they are
 // rebuilt from: one base copy, and per registry slot the adapter that slot holds on this target.  Every buffer is the engine's own:
@@ -194,26 +213,24 @@ private:
     int lora_target(const char* name, int* ti, int* attn, int* proj) const;
     void lora_free(LoraSlot& s);
     int pack_temporal_res(const std::string& prefix, int C, int taps1, TemporalResW* out, hipStream_t s);
-    int run_temporal_res(FwdCtx& c, const TemporalResW& r, const half_t* x, half_t* y, int C, int D, const float* bias2, int ldb2,
-                         const GnColStat* x_cs = nullptr, float* y_csbuf = nullptr, GnColStat* y_cs = nullptr);
-    int run_temporal_module(FwdCtx& c, const TemporalModuleW& m, const half_t* x, half_t* y, const float* tproj, int ld_tproj,
-                            int H, int W, const GnColStat* x_cs = nullptr, float* y_csbuf = nullptr, GnColStat* y_cs = nullptr);
+    int run_temporal_res(FwdCtx& c, const TemporalResW& r, const Act& x, Act* y, int D, const float* bias2, int ldb2);
+    int run_temporal_module(FwdCtx& c, const TemporalModuleW& m, const Act& x, Act* y, const float* tproj, int ld_tproj, int H, int W);
     int pack_sampler(const std::string& prefix, int C, SamplerW* out, hipStream_t s, bool up = false);
     int ensure_tables(int F, hipStream_t s);
+    // THE per-call state of a call that enters with this shape and context: every entry point builds it here (Route = the switches
+    // in force, `pag` = pag_route() where the call runs attn1), and so do prepare()'s dry runs (`planned`: the Route it enumerates)
+    FwdCtx call_ctx(hipStream_t s, DeviceArena* ws, int B, int F, int H, int W, const half_t* ctx, int ctx_len, int pag,
+                    const Route* planned = nullptr) const;
 
     int run(FwdCtx& c, const half_t* sample, const float* timesteps, const half_t* ctx, half_t* out);
-    // cs1 / cs2: GroupNorm statistics the producers of x1 / x2 left (nullptr / empty = none: the statistics pass runs); y_csbuf / y_cs:
-    // where the block's last conv leaves the statistics of y for ITS consumers (engine.cpp colstat_plan)
-    int run_resnet(FwdCtx& c, const ResnetW& r, const half_t* x1, int C1, const half_t* x2, int C2, const float* tproj,
-                   int ld_tproj, half_t* y, int H, int W, const GnColStat* cs1 = nullptr, const GnColStat* cs2 = nullptr,
-                   float* y_csbuf = nullptr, GnColStat* y_cs = nullptr);
+    // x2: the skip tensor concatenated behind x1, or nullptr.  norm1 takes the statistics x1 / x2 carry; conv2's epilogue leaves y's
+    int run_resnet(FwdCtx& c, const ResnetW& r, const Act& x1, const Act* x2, const float* tproj, int ld_tproj, Act* y, int H, int W);
     // Sequences the launches of one block from its route (engine.cpp block_route(): decided once per call from c.route, the shape and
-    // whether the text K / V are cached and bound).  shared_prefix: the part in front of the text cross-attention runs on the first half
-    // of the batch.  x_cs: in = statistics of the block input (for its per-frame GroupNorm), out = of the block output (proj_out's epilogue)
-    int run_transformer(FwdCtx& c, const TransformerW& t, half_t* x, const half_t* ctx, int H, int W, bool shared_prefix = false,
-                        GnColStat* x_cs = nullptr, float* x_csbuf = nullptr);
-    int run_conv(FwdCtx& c, const half_t* x, int C, const SamplerW& w, half_t* y, int Hi, int Wi, int stride, int ups,
-                 float* cs_buf = nullptr, GnColStat* cs_out = nullptr);
+    // whether the text K / V are cached and bound).  In place on x: its statistics feed the block's per-frame GroupNorm and are
+    // replaced by those of the block output (proj_out's epilogue).  shared_prefix: the part in front of the text cross-attention runs
+    // on the first half of the batch
+    int run_transformer(FwdCtx& c, const TransformerW& t, Act& x, const half_t* ctx, int H, int W, bool shared_prefix = false);
+    int run_conv(FwdCtx& c, const Act& x, const SamplerW& w, Act* y, int Hi, int Wi, int stride, int ups);
 
     struct GraphKey {
         const void *sample = nullptr, *t = nullptr, *ctx = nullptr, *out = nullptr, *kv_ctx = nullptr;
@@ -238,8 +255,7 @@ private:
     std::unordered_map<std::string, size_t> index_;
     std::vector<const half_t*> given_;
     bool finalized_ = false;
-    // The two per-handle switches of a call's Route: read where a call enters (forward, cache_context, resnet_forward,
-    // transformer_forward) and by prepare(), nowhere below.
+    // The two per-handle switches of a call's Route: read by call_ctx() and by prepare(), nowhere below.
     // the caller promises sample[b] == sample[b + B/2] (classifier-free guidance on duplicated latents): the layers in front of
     // the first text cross-attention are computed for the first half and copied
     bool cfg_shared_input_ = false;
@@ -261,13 +277,7 @@ private:
     std::vector<TemporalModuleW> tmods_;            // VSR: down 0..L-1, mid, up 0..L-1
     half_t* class_emb_ = nullptr;                   // [num_class_embeds][time_embed_dim] fp16 (state-dict tensor)
     half_t* zero_page_ = nullptr;
-    // per-F tables, built once per clip length and kept (the VSR chunk driver alternates F = 8 and F = 5)
-    struct FrameTables {
-        float* rot_cos = nullptr; float* rot_sin = nullptr;
-        std::vector<float*> relbias;                // one [heads, F, F] per transformer
-    };
-    std::unordered_map<int, FrameTables> tables_;
-    const FrameTables* cur_tables_ = nullptr;       // the entry of the running forward's F
+    std::unordered_map<int, FrameTables> tables_;   // by F (ensure_tables)
     // cached text K/V (cache_context): one [B * ctx_len, 2C] buffer per transformer (attn2; attn1 on VSR cross levels)
     std::vector<half_t*> kv2_cache_, kv1_cache_;
     size_t kv_cache_rows_ = 0;                      // rows the buffers were allocated for
@@ -286,8 +296,6 @@ private:
     float lora_scale_ = 1.f;                        // global adapter scale
     float lora_weight_[kLoraMaxTerms] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};    // per-slot blend weight
     std::vector<char> lora_dirty_;                  // per transformer: touched since the last apply
-    // spatial size of the running call (set by prepare()/forward() before run())
-    int prep_H_ = 0, prep_W_ = 0;
 };
 
 }  // namespace lavie

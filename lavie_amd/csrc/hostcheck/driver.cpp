@@ -23,6 +23,7 @@
 extern "C" long lavie_hostcheck_launches();
 extern "C" long lavie_hostcheck_last_grid_x();
 extern "C" void lavie_hostcheck_trace_to(FILE* f);
+extern "C" void lavie_hostcheck_trace_copies(int on);
 extern "C" void lavie_hostcheck_kernel_names_to(FILE* f);
 
 #define REQUIRE(cond)                                                                          \
@@ -368,6 +369,7 @@ static void run_traces(const char* path) {
     g_out = fopen(path, "w");
     REQUIRE(g_out != nullptr);
     lavie_hostcheck_trace_to(g_out);
+    lavie_hostcheck_trace_copies(1);
     {   // base model at the production shape (cached context, shared prefix): every force_tile mode, forced split-K, fused mask 0x30
         const lavie_unet_config cfg = production_config();
         trace_case("base finalize");
@@ -452,6 +454,33 @@ static void run_traces(const char* path) {
             Model m(c.cfg);
             trace_forward(c.cfg, m, c.B, c.F, c.H, c.W, c.cached, c.shared);
         }
+    }
+    {   // what else a forward decides, on the reduced base model: perturbed-attention guidance (three entries, the last one perturbed in
+        // one level-0 and the mid-block transformer) and FreeU, each followed by the plain forward again; and the two block entry
+        // points, which build their own per-call state and workspace: a resnet with two inputs and a shortcut, one transformer
+        const lavie_unet_config cfg = base_config();
+        Model m(cfg);
+        const char* layers[2] = {"down_blocks.0.attentions.0", "mid_block"};
+        REQUIRE(lavie_unet_set_pag(m.h, layers, 2, 1) == 0);
+        trace_case("reduced base pag");
+        trace_forward(cfg, m, 3, 16, 16, 16, true, false);
+        REQUIRE(lavie_unet_set_pag(m.h, nullptr, 0, 0) == 0);
+        trace_case("reduced base pag off");
+        trace_forward(cfg, m, 3, 16, 16, 16, true, false);
+        REQUIRE(lavie_unet_set_freeu(m.h, 0.9f, 0.2f, 1.5f, 1.6f) == 0);
+        trace_case("reduced base freeu");
+        trace_forward(cfg, m, 2, 16, 16, 16, true, true);
+        REQUIRE(lavie_unet_set_freeu(m.h, 1.f, 1.f, 1.f, 1.f) == 0);
+        trace_case("reduced base freeu off");
+        trace_forward(cfg, m, 2, 16, 16, 16, true, true);
+        const int B = 2, F = 16, H = 16, W = 16, C0 = cfg.block_out_channels[0], C1 = cfg.block_out_channels[1];
+        std::vector<unsigned short> x((size_t)B * F * H * W * C0), ctx((size_t)B * 77 * cfg.cross_attention_dim);
+        std::vector<float> temb((size_t)B * C0 * 4);
+        trace_case("reduced base resnet_forward");       // up_blocks.0.resnets.0: 640 + 640 -> 640 channels at level 1; one video of two frames (its private workspace leaves 4 MiB for split-K slabs)
+        REQUIRE(lavie_unet_resnet_forward(m.h, "up_blocks.0.resnets.0", x.data(), C1, x.data(), C1, temb.data(), x.data(), 1, 2, H / 2, W / 2,
+                                          nullptr) == 0);
+        trace_case("reduced base transformer_forward");
+        REQUIRE(lavie_unet_transformer_forward(m.h, "down_blocks.0.attentions.0", x.data(), ctx.data(), B, F, H, W, 77, nullptr) == 0);
     }
     for (int mode = 0; mode <= 9; ++mode) {
         REQUIRE(lavie_debug_force_tile(mode) == 0);

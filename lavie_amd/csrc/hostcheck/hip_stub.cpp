@@ -21,7 +21,12 @@ hipError_t hipMalloc(void** p, size_t n) {
 }
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memmove(d, s, n); return hipSuccess; }
-hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memmove(d, s, n); return hipSuccess; }
+static void trace_copy(size_t n, hipMemcpyKind kind);
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t) {
+    trace_copy(n, kind);
+    memmove(d, s, n);
+    return hipSuccess;
+}
 hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }
 hipError_t hipMemcpyFromSymbol(void* d, const void*, size_t n, size_t, hipMemcpyKind) { memset(d, 0, n); return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
@@ -58,6 +63,12 @@ hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* shmem, hip
 static long g_launches = 0;
 static unsigned g_last_grid_x = 0;     // of the latest launch (the driver's check of lavie_debug_rowfuse_grid)
 static FILE* g_trace = getenv("LAVIE_HOSTCHECK_TRACE") ? stderr : nullptr;
+// The driver's `trace` mode also records every asynchronous device-to-device copy, as "copy BYTES" (no addresses): the forward
+// enqueues some, next to its launches.  Off elsewhere: to the readers of an operator trace every line is a launch.
+static bool g_trace_copies = false;
+static void trace_copy(size_t n, hipMemcpyKind kind) {
+    if (g_trace && g_trace_copies && kind == hipMemcpyDeviceToDevice) fprintf(g_trace, "copy %zu\n", n);
+}
 static std::map<const void*, std::string>& kernel_names() { static std::map<const void*, std::string> m; return m; }
 static const char* kernel_name(const void* f) {
     auto it = kernel_names().find(f);
@@ -86,6 +97,7 @@ hipError_t hipExtLaunchKernel(const void* f, dim3 grid, dim3 block, void** args,
 long lavie_hostcheck_launches() { return g_launches; }
 long lavie_hostcheck_last_grid_x() { return (long)g_last_grid_x; }
 void lavie_hostcheck_trace_to(FILE* f) { g_trace = f; }
+void lavie_hostcheck_trace_copies(int on) { g_trace_copies = on != 0; }
 // every kernel name the registration calls have seen, sorted, one per line (the driver's `kernels` mode)
 void lavie_hostcheck_kernel_names_to(FILE* f) {
     std::map<std::string, int> names;

@@ -1,6 +1,7 @@
 """Generates tests/golden/gemm_plan_trace.txt.gz: the launch trace of the host-only sanitizer build (lavie_amd/csrc/hostcheck,
 `hostcheck trace FILE`), one line per kernel launch (kernel, grid, block, dynamic LDS bytes) under a "== case" line per case of
-driver.cpp's run_traces(), and one "workspace BYTES" line after every lavie_unet_prepare.  The cases:
+driver.cpp's run_traces(), one "workspace BYTES" line after every lavie_unet_prepare and one "copy BYTES" line per asynchronous
+device-to-device copy (the shared prefix's duplications, finalize's packing copies).  The cases:
 * the base model at the production shape (B = 2, F = 16, 40 x 64, cached 77-token context, shared prefix) under every force_tile
   mode, forced split-K 2 and 3 and fused mask 0x30;
 * the routes of a forward, on a second base model at that shape: F = 8 (no fused temporal block); fused masks 0, 0x136, 0x135,
@@ -9,7 +10,9 @@ driver.cpp's run_traces(), and one "workspace BYTES" line after every lavie_unet
   text cross-attention);
 * the interpolation model (F = 61; feed-forward before temporal) under the default mask, 0x136 and 0x133, and the VSR UNet (F = 8 at
   320 x 512);
-* the reduced variants of `make asan`;
+* the reduced variants of `make asan`; on the reduced base model also perturbed-attention guidance (B = 3, one perturbed entry, a
+  level-0 and the mid-block transformer) and FreeU, each followed by the plain forward again, and the two block entry points
+  (lavie_unet_resnet_forward on a resnet with a skip input and a shortcut, lavie_unet_transformer_forward);
 * lavie_linear_f16 / lavie_conv3x3_f16 / lavie_upsample_conv3x3_f16 at level shapes under every force_tile mode.
 
 It pins every kernel choice, grid (split-K factor = grid.y of the GEMM launches) and tile of the implicit-GEMM planner, which

@@ -351,7 +351,10 @@ ENDS_KERNELS = ("timestep_sinusoid_kernel", "gemv_kernel", "add_class_emb_silu_k
                 "f16_to_f32_kernel", "fill_relpos_bias_kernel")
 # the fixture's other names, by the prefix of the kernels the attention and LayerNorm cases launch (not replayed: their routes are
 # mirrored by attention_route) ...
-COVERED_ELSEWHERE = ("attention_dma_kernel<", "attention_kernel<", "attention_wide_kernel", "layernorm_kernel")
+# ... and the FreeU kernels of the trace's FreeU case, whose launches tests/freeucases.py mirrors (test_freeu_host.py) and whose output
+# tests/test_gpu_freeu_local.py checks per element
+COVERED_ELSEWHERE = ("attention_dma_kernel<", "attention_kernel<", "attention_wide_kernel", "layernorm_kernel", "freeu_apply_kernel",
+                     "freeu_sums_kernel")
 # ... and of the GroupNorm, row-resident and temporal cases, which describe their calls: every such name of a forward's trace must be in
 # the replayed launches of a case (test_gemm_reach_host.py::test_local_kernels_of_a_forward_are_reached)
 LOCAL_KERNELS = ("gn_affine_kernel", "gn_apply_kernel<", "gn_stats_kernel<", "gn_finalize_kernel", "gn_fold_kernel", "rowstat_finalize_kernel", "geglu_mlp_kernel<", "cross_block_kernel<",

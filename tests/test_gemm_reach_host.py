@@ -29,7 +29,7 @@ def reach(cases):
 @pytest.fixture(scope="module")
 def fixture_names():
     with gzip.open(FIXTURE, "rt") as f:
-        return {C.launch_name(l) for l in f.read().splitlines() if not l.startswith(("== ", "workspace ", "!! "))}
+        return {C.launch_name(l) for l in f.read().splitlines() if not l.startswith(("== ", "workspace ", "!! ", "copy "))}
 
 
 def names(reach, keep=lambda key: True):
