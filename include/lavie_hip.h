@@ -765,6 +765,37 @@ int lavie_unet_forward_graph(lavie_unet_t h, const void* sample, const float* ti
 int lavie_unet_forward_labels(lavie_unet_t h, const void* sample, const float* timesteps, const void* ctx,
                               const int* class_labels_host, void* out, int B, int F, int H, int W, int ctx_len, void* stream);
 
+/* Layer cache (feature caching as in DeepCache, Ma et al., CVPR 2024; additive in ABI 8).  The hidden state that enters the last,
+ * full-resolution layers of the decoder changes slowly from one denoising step to the next, so a sampler may run the whole network
+ * only every N-th step.  For a depth d in 1..layers_per_block the forward's list of steps has two cuts: A behind layer d - 1 of down
+ * level 0 (its resnet, its transformer, the push of its skip) and B in front of layer layers_per_block - d of the last up block
+ * (behind the upsampler into level 0 and, in the VSR model, the temporal module that follows it).  The cache holds the running
+ * activation at B, rows(0) x C fp16 (C = block_out_channels[0]; [1] for d = layers_per_block) and its GroupNorm column statistics,
+ * in one allocation outside the workspace that lavie_unet_prepare sizes for its shape.
+ *   set_layer_cache: depth 0 switches it off and frees the allocation, 1..layers_per_block selects the cuts.  Refused for a model
+ *     with fewer than three levels.  Every call marks a held cache invalid, and so does lavie_unet_prepare with another shape.
+ *   layer_cache_bytes: the size of the allocation now (0: off, or no prepare yet); -1 for a null handle.
+ *   forward_cached: lavie_unet_forward / _labels (class_labels_host NULL for a model without class embedding) with a mode:
+ *     LAVIE_LAYER_CACHE_OFF      the plain forward, launch for launch; the cache is neither read nor written.
+ *     LAVIE_LAYER_CACHE_REFRESH  the full walk, launch for launch and bit for bit the plain forward, except that the producer of the
+ *                                tensor at B stores it into the cache; records (B, F, H, W, ctx_len, depth).
+ *     LAVIE_LAYER_CACHE_REUSE    the shallow walk: the time embedding, conv_in, d down layers, the cached tensor, d + 1 up layers (with
+ *                                the d + 1 skips of this call, in the order the full walk pops them), the trailing VSR temporal module,
+ *                                conv_norm_out and conv_out.  Refused, nothing launched: depth 0, no valid cache, a recorded tuple
+ *                                that differs from this call's, a capturing stream (a refresh is refused there too).
+ *   The shared CFG prefix lies in front of A and works in every mode; FreeU and perturbed-attention guidance act in layers a reuse call
+ *   does not run.  Weights, adapters, the context's contents, FreeU or PAG changed between a refresh and a reuse are the caller's
+ *   business: the cached tensor is whatever the refresh computed.  Refresh and reuse calls of one handle belong on one stream.
+ *   lavie_unet_forward_graph has no cached form. */
+#define LAVIE_LAYER_CACHE_OFF 0
+#define LAVIE_LAYER_CACHE_REFRESH 1
+#define LAVIE_LAYER_CACHE_REUSE 2
+int lavie_unet_set_layer_cache(lavie_unet_t h, int depth);
+long long lavie_unet_layer_cache_bytes(lavie_unet_t h);
+int lavie_unet_forward_cached(lavie_unet_t h, const void* sample, const float* timesteps, const void* ctx,
+                              const int* class_labels_host /* NULL for models without class embedding */, void* out, int B, int F,
+                              int H, int W, int ctx_len, int mode, void* stream);
+
 /* Finer engine seams for parity tests (same packed weights as the whole model):
  * ResnetBlock3D.forward (resnet.py:177-207) and Transformer3DModel.forward (attention.py:358-407)
  * of the block whose state-dict prefix is `prefix` (e.g. "down_blocks.0.resnets.0").

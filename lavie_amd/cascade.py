@@ -47,7 +47,8 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
                           base_scheduler=None, vsr_scheduler=None, vsr_overlap: int = 0, base_guidance_rescale: float = 0.0,
                           vsr_guidance_rescale: float = 0.0, base_freeu: Optional[dict] = None, vsr_freeu: Optional[dict] = None,
                           base_pag_scale: float = 0.0, base_pag_adaptive_scale: float = 0.0,
-                          base_pag_applied_layers=("mid_block",)):
+                          base_pag_applied_layers=("mid_block",), base_cache_interval: Optional[int] = None,
+                          vsr_cache_interval: Optional[int] = None, base_cache_depth: int = 1, vsr_cache_depth: int = 1):
     """Returns (base_latents, interp_latents, vsr_latents, frames or None).  Text embeddings are passed per stage (the base
     and interpolation stages use SD-1.4's CLIP, 768 wide; the VSR stage the x4-upscaler's, 1024 wide).
     `base_scheduler` / `vsr_scheduler` replace the two diffusers-style stages' schedulers for this call (for instance a
@@ -60,7 +61,11 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
     `base_freeu` / `vsr_freeu`: dict(s1=, s2=, b1=, b2=) for `enable_freeu` on that stage's UNet during this call; the UNet gets the
     setting it had back afterwards.  None = the UNet's own setting.
     `base_pag_scale` / `base_pag_adaptive_scale` / `base_pag_applied_layers`: perturbed-attention guidance in the base stage (the
-    keywords of `VideoGenPipeline.__call__`; 0 = off, the calls without them).  The other two stages have no such switch."""
+    keywords of `VideoGenPipeline.__call__`; 0 = off, the calls without them).  The other two stages have no such switch.
+    `base_cache_interval` / `vsr_cache_interval` (with `base_cache_depth` / `vsr_cache_depth`): the layer cache of the two
+    diffusers-style stages, the `cache_interval` / `cache_depth` of their pipelines: the whole UNet on every N-th step only; every VSR
+    chunk starts with a full step.  None or 1 = the calls without it.  Not with `vsr_overlap` > 0 (frame windows).  The interpolation
+    stage's loop has no such switch."""
     freeu_was = [(pipe.unet, pipe.unet.freeu) for pipe, fu in ((base_pipe, base_freeu), (vsr_pipe, vsr_freeu)) if fu is not None]
     swapped = [(pipe, pipe.scheduler) for pipe, sch in ((base_pipe, base_scheduler), (vsr_pipe, vsr_scheduler)) if sch is not None]
     if base_scheduler is not None:
@@ -76,7 +81,9 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
                         width, base_steps, guidance_scale, interp_frames, interp_cfg_scale, vsr_steps, vsr_guidance_scale,
                         noise_level, generator, decode_final, vsr_overlap, base_guidance_rescale, vsr_guidance_rescale,
                         dict(pag_scale=base_pag_scale, pag_adaptive_scale=base_pag_adaptive_scale,
-                             pag_applied_layers=base_pag_applied_layers) if base_pag_scale else {})
+                             pag_applied_layers=base_pag_applied_layers) if base_pag_scale else {},
+                        dict(cache_interval=base_cache_interval, cache_depth=base_cache_depth) if base_cache_interval not in (None, 1) else {},
+                        dict(cache_interval=vsr_cache_interval, cache_depth=vsr_cache_depth) if vsr_cache_interval not in (None, 1) else {})
     finally:
         for pipe, own in swapped:
             pipe.scheduler = own
@@ -87,11 +94,14 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
 def _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, prompt_embeds, negative_prompt_embeds,
              vsr_prompt_embeds, vsr_negative_prompt_embeds, interp_prompt_embeds, interp_negative_prompt_embeds, height, width,
              base_steps, guidance_scale, interp_frames, interp_cfg_scale, vsr_steps, vsr_guidance_scale, noise_level, generator,
-             decode_final, vsr_overlap=0, base_guidance_rescale=0.0, vsr_guidance_rescale=0.0, base_pag=None):
+             decode_final, vsr_overlap=0, base_guidance_rescale=0.0, vsr_guidance_rescale=0.0, base_pag=None, base_cache=None,
+             vsr_cache=None):
     dev = base_pipe.device
     base_kw = dict(guidance_rescale=base_guidance_rescale) if base_guidance_rescale else {}       # absent = the calls without it
     base_kw.update(base_pag or {})
+    base_kw.update(base_cache or {})
     vsr_kw = dict(guidance_rescale=vsr_guidance_rescale) if vsr_guidance_rescale else {}
+    vsr_kw.update(vsr_cache or {})
     # 1. base T2V (base/pipelines/sample.py:78-91)
     base = base_pipe(prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, height=height, width=width,
                      video_length=16, num_inference_steps=base_steps, guidance_scale=guidance_scale, generator=generator,
@@ -121,7 +131,8 @@ def continue_clip(pipe, prev_latents: torch.Tensor, overlap: int = 4, **call_kwa
     """One more clip after `prev_latents` [P, C, F, h, w]: a base call whose first `overlap` frames are pinned to the last `overlap`
     frames of `prev_latents` (VideoGenPipeline's `known_latents` / `known_mask`), so they come back bit-equal and temporal attention
     carries them into the free frames.  `call_kwargs` go to the pipeline (prompt or prompt_embeds, steps, generator, ...);
-    `video_length` defaults to 16, height / width to those of `prev_latents`.  Returns the new clip's latents, overlap included."""
+    `video_length` defaults to 16, height / width to those of `prev_latents`; `cache_interval` / `cache_depth` (the layer cache) go
+    through like the rest.  Returns the new clip's latents, overlap included."""
     p, c, f_prev, h, w = prev_latents.shape
     length = int(call_kwargs.pop("video_length", 16))
     if not 1 <= overlap < length or overlap > f_prev:
@@ -145,7 +156,9 @@ def text_to_long_video(pipe, prompt, num_clips: int, overlap: int = 4, method: s
     n - 1 has finished, and nothing later influences an earlier frame.
     method "windows": ONE run over the whole length as `num_clips` windows of L frames at stride L - overlap, fused at every step
     (VideoGenPipeline's `window_length` / `window_stride`): every forward keeps the trained length, the overlap frames are
-    shared in both directions."""
+    shared in both directions.
+    `cache_interval` / `cache_depth` in `call_kwargs` (the layer cache) reach every clip's call with method "chain"; "windows" refuses
+    them, as the pipeline does."""
     if num_clips < 1:
         raise ValueError(f"num_clips={num_clips} must be >= 1")
     if method not in ("chain", "windows"):

@@ -1063,6 +1063,20 @@ int lavie_unet_forward_labels(lavie_unet_t h, const void* sample, const float* t
     return h->net.forward(H(sample), timesteps, H(ctx), H(out), B, F, Hh, W, ctx_len, S(stream), class_labels_host);
 }
 
+int lavie_unet_set_layer_cache(lavie_unet_t h, int depth) {
+    LAVIE_CHECK(h, "set_layer_cache: null handle");
+    return h->net.set_layer_cache(depth);
+}
+long long lavie_unet_layer_cache_bytes(lavie_unet_t h) { return h ? h->net.layer_cache_bytes() : -1; }
+
+int lavie_unet_forward_cached(lavie_unet_t h, const void* sample, const float* timesteps, const void* ctx, const int* class_labels_host,
+                              void* out, int B, int F, int Hh, int W, int ctx_len, int mode, void* stream) {
+    LAVIE_CHECK(h, "forward_cached: null handle");
+    LAVIE_CHECK(mode >= LAVIE_LAYER_CACHE_OFF && mode <= LAVIE_LAYER_CACHE_REUSE, "forward_cached: mode=%d must be 0 (off), 1 (refresh) or 2 (reuse)",
+                mode);
+    return h->net.forward(H(sample), timesteps, H(ctx), H(out), B, F, Hh, W, ctx_len, S(stream), class_labels_host, mode);
+}
+
 int lavie_unet_resnet_forward(lavie_unet_t h, const char* prefix, const void* x1, int C1, const void* x2, int C2,
                               const float* temb, void* y, int B, int F, int Hh, int W, void* stream) {
     LAVIE_CHECK(h && prefix && x1 && temb && y, "resnet_forward: null argument");

@@ -101,6 +101,7 @@ UNet::~UNet() {
     if (cap_stream_) (void)hipStreamDestroy(cap_stream_);
     if (kv_block_) (void)hipFree(kv_block_);
     if (xbl_block_) (void)hipFree(xbl_block_);
+    if (lc_block_) (void)hipFree(lc_block_);
     for (auto& kv : lora_) {
         for (LoraSlot& s : kv.second.slot) lora_free(s);
         if (kv.second.base) (void)hipFree(kv.second.base);
@@ -624,6 +625,8 @@ struct FwdCtx {
     bool text_cached, text_bound;  // text K / V: cached (cache_context) for this very ctx tensor and shape / bound into the fused kernel's images
     float* gn_ws = nullptr;        // GroupNorm scratch, gn_workspace_floats(B*F, groups) floats
     const int* labels = nullptr;   // VSR noise level per video (host), num_class_embeds > 0
+    int lc_mode = LAVIE_LAYER_CACHE_OFF;      // layer cache: what this call does with it, and the depth of its cuts (0 with OFF)
+    int lc_depth = 0;
 };
 
 FwdCtx UNet::call_ctx(hipStream_t s, DeviceArena* ws, int B, int F, int H, int W, const half_t* ctx, int ctx_len, int pag,
@@ -1124,6 +1127,27 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
     size_t ri = 0, ti = 0, mi = 0;
     const bool tmod = cfg.vsr_temporal_modules != 0;
 
+    // Layer cache (set_layer_cache): cut A lies behind layer lcd - 1 of down level 0, cut B in front of layer layers_per_block - lcd
+    // of the last up block.  A refresh call is the full walk whose producer of the running activation at B writes it into the cache
+    // block instead of the workspace (`to_cache`: the next new tensor); a reuse call walks the same list of steps, but between the
+    // cuts (`deep`) a step only advances its counter and the skip stack holds placeholders, and at B the cached tensor becomes x.
+    const int lpb = cfg.layers_per_block;
+    const int lcd = c.lc_mode != LAVIE_LAYER_CACHE_OFF ? c.lc_depth : 0;
+    const bool refresh = c.lc_mode == LAVIE_LAYER_CACHE_REFRESH, reuse = c.lc_mode == LAVIE_LAYER_CACHE_REUSE;
+    bool deep = false, to_cache = false;
+    Act filled;                 // refresh: the tensor at B as its producer left it
+    auto new_act = [&](size_t nrows, int C, Act* a) -> int {
+        if (!to_cache) return ws_act(c, nrows, C, a);
+        to_cache = false;
+        // (a dry run has no block: placeholder addresses, as the virtual arena hands out)
+        half_t* p = c.dry ? (half_t*)(uintptr_t)256 : (half_t*)lc_block_;
+        const size_t act_bytes = (nrows * C * sizeof(half_t) + 255) & ~(size_t)255;
+        LAVIE_CHECK(c.dry || (lc_block_ && act_bytes + colstat_floats(nrows, C) * sizeof(float) <= lc_bytes_),
+                    "forward: the layer cache holds %zu B, this shape needs more: call lavie_unet_prepare for it", lc_bytes_);
+        *a = Act{p, C, GnColStat(), (float*)((char*)p + (c.dry ? 0 : act_bytes))};
+        return 0;
+    };
+
     // Classifier-free guidance runs the UNet on the latents twice with different text: up to the first text cross-attention
     // (conv_in, the first resnet, and GroupNorm / proj_in / self-attention of the first transformer block) the two halves of the
     // batch are the same computation.  With set_cfg_shared_input the caller vouches for sample[b] == sample[b + B/2]; those
@@ -1158,26 +1182,31 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
     // The steps of the walk below: each takes a new tensor and its statistics buffer from the workspace, runs on x, and advances x
     auto resnet = [&](FwdCtx& cc, int l, const Act* skip) -> int {
         const ResnetW& r = resnets_[ri++];
+        if (deep) return 0;
         Act y;
-        RUN(ws_act(c, rows(l), r.cout, &y));
+        RUN(new_act(rows(l), r.cout, &y));
         RUN(run_resnet(cc, r, x, skip, tproj + r.temb_off, tproj_.N, &y, Hs[l], Ws[l]));
         x = y;
         return 0;
     };
     auto transformer = [&](int l, bool shared_prefix) {      // in place on x
-        return run_transformer(c, transformers_[ti++], x, ctx, Hs[l], Ws[l], shared_prefix);
+        const TransformerW& t = transformers_[ti++];
+        return deep ? 0 : run_transformer(c, t, x, ctx, Hs[l], Ws[l], shared_prefix);
     };
     auto resample = [&](const SamplerW& w, int l, int l_out) -> int {      // down: stride 2; up: nearest x2 in front of the conv
+        if (deep) return 0;
         Act y;
-        RUN(ws_act(c, rows(l_out), x.C, &y));
+        RUN(new_act(rows(l_out), x.C, &y));
         RUN(run_conv(c, x, w, &y, Hs[l], Ws[l], l_out > l ? 2 : 1, l_out < l ? 1 : 0));
         x = y;
         return 0;
     };
     auto temporal_module = [&](int l) -> int {      // VSR; into a NEW buffer: x itself may stay alive as a skip
+        const TemporalModuleW& m = tmods_[mi++];
+        if (deep) return 0;
         Act y;
-        RUN(ws_act(c, rows(l), x.C, &y));
-        RUN(run_temporal_module(c, tmods_[mi++], x, &y, tproj, tproj_.N, Hs[l], Ws[l]));
+        RUN(new_act(rows(l), x.C, &y));
+        RUN(run_temporal_module(c, m, x, &y, tproj, tproj_.N, Hs[l], Ws[l]));
         x = y;
         return 0;
     };
@@ -1198,6 +1227,7 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
             if (cfg.attn_levels[l]) RUN(transformer(l, first));
             else if (first) x.cs = GnColStat();
             skips.push_back(x);
+            if (reuse && l == 0 && j + 1 == lcd) deep = true;      // cut A
         }
         if (l + 1 < L) {
             RUN(resample(downs_[l], l, l + 1));
@@ -1212,9 +1242,18 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
     for (int i = 0; i < L; ++i) {
         const int l = L - 1 - i;
         for (int j = 0; j < cfg.layers_per_block + 1; ++j) {
+            if (lcd > 0 && i == L - 1 && j == lpb - lcd) {          // cut B
+                if (refresh) filled = x;
+                if (reuse) {
+                    x = c.dry ? Act{(half_t*)(uintptr_t)256, lc_channels(lcd)} : lc_act_;
+                    deep = false;
+                }
+            }
+            // refresh: the resnet in front of B (and the transformer behind it, in place) produces the cached tensor
+            if (refresh && i == L - 1 && j + 1 == lpb - lcd) to_cache = true;
             Act sk = skips.back();
             skips.pop_back();
-            if (i < 2) {
+            if (i < 2 && !deep) {
                 // FreeU (diffusers apply_freeu), in place: both tensors have this resnet as their one consumer left.  Its mode-sum
                 // partials are taken from the workspace whether FreeU is on or off (so prepare()'s plan covers a setting made after
                 // it) and given back at once: the resnet's buffers lie over them, behind the launches in stream order.  A tensor
@@ -1231,7 +1270,12 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
             RUN(resnet(c, l, &sk));
             if (cfg.attn_levels[l]) RUN(transformer(l, false));
         }
+        // refresh at the full depth: B lies in front of the last up block, its tensor comes from the upsampler into level 0 or, in the
+        // VSR model, from the temporal module behind it
+        const bool into_b = refresh && lcd == lpb && i == L - 2;
+        if (into_b && !tmod) to_cache = true;
         if (i + 1 < L) RUN(resample(ups_[i], l, l - 1));
+        if (into_b && tmod) to_cache = true;
         if (tmod) RUN(temporal_module(i + 1 < L ? l - 1 : l));      // after the upsampler (vsr/models/unet.py:575-590)
     }
     // conv_norm_out + SiLU + conv_out (unet.py:504-506), back to the caller's NCFHW layout
@@ -1241,6 +1285,7 @@ int UNet::run(FwdCtx& c, const half_t* sample, const float* timesteps, const hal
         LAUNCH(launch_group_norm(x.p, C0, nullptr, 0, c.B, P, G, norm_out_.g, norm_out_.b, cfg.norm_eps, true, c.gn_ws, nrm, c.s, &x.cs));
         LAUNCH(launch_conv_out(nrm, conv_out_w_, conv_out_b_, out, c.B, C0, c.F, Hs[0], Ws[0], cfg.out_channels, c.s));
     }
+    if (refresh && !c.dry) lc_act_ = filled;
     return 0;
 }
 
@@ -1275,7 +1320,23 @@ int UNet::prepare(int B, int F, int H, int W, int ctx_len) {
         FwdCtx c = call_ctx(nullptr, &plan, B, F, H, W, nullptr, ctx_len, 0, &route);
         RUN(run(c, nullptr, nullptr, nullptr, nullptr));
         if (plan.peak() > peak) peak = plan.peak();
+        // The shallow walk of a layer-cache reuse call, at every depth the model admits (so a depth set after prepare() is covered): its
+        // allocations are a subsequence of the full walk's, so its peak cannot exceed the one above; it is planned all the same and the
+        // relation is checked, so a step added to one walk only does not go unnoticed.  (A refresh call takes one tensor less.)
+        for (int depth = 1; cfg_.num_levels >= 3 && depth <= cfg_.layers_per_block; ++depth) {
+            DeviceArena shallow;
+            shallow.init_virtual();
+            FwdCtx cs = call_ctx(nullptr, &shallow, B, F, H, W, nullptr, ctx_len, 0, &route);
+            cs.lc_mode = LAVIE_LAYER_CACHE_REUSE;
+            cs.lc_depth = depth;
+            RUN(run(cs, nullptr, nullptr, nullptr, nullptr));
+            LAVIE_CHECK(shallow.peak() <= plan.peak(), "prepare: the shallow walk at depth %d plans %zu B, more than the full walk's %zu B",
+                        depth, shallow.peak(), plan.peak());
+        }
     }
+    if (B != lc_shape_[0] || F != lc_shape_[1] || H != lc_shape_[2] || W != lc_shape_[3]) lc_key_[0] = 0;      // another shape: a held cache is invalid
+    lc_shape_[0] = B; lc_shape_[1] = F; lc_shape_[2] = H; lc_shape_[3] = W;
+    RUN(ensure_layer_cache());
     const size_t need = peak + (1 << 20);
     if (need > ws_.total_bytes()) {
         drop_graph();                               // the captured addresses die with the old workspace
@@ -1283,6 +1344,39 @@ int UNet::prepare(int B, int F, int H, int W, int ctx_len) {
         RUN(ws_.init_fixed(need));
     }
     return 0;
+}
+
+int UNet::ensure_layer_cache() {
+    size_t need = 0;
+    if (lc_depth_ > 0 && lc_shape_[0] > 0) {
+        const size_t rows0 = (size_t)lc_shape_[0] * lc_shape_[1] * lc_shape_[2] * lc_shape_[3];
+        const int C = lc_channels(lc_depth_);
+        need = ((rows0 * C * sizeof(half_t) + 255) & ~(size_t)255) + colstat_floats(rows0, C) * sizeof(float);
+    }
+    if (need == lc_bytes_) return 0;
+    lc_key_[0] = 0;
+    lc_act_ = Act();
+    if (lc_block_) {
+        LAVIE_HIP(hipDeviceSynchronize());          // a forward in flight may still read it
+        (void)hipFree(lc_block_);
+        lc_block_ = nullptr;
+        lc_bytes_ = 0;
+    }
+    if (need > 0) {
+        LAVIE_HIP(hipMalloc(&lc_block_, need));
+        lc_bytes_ = need;
+    }
+    return 0;
+}
+
+int UNet::set_layer_cache(int depth) {
+    LAVIE_CHECK(depth >= 0 && depth <= cfg_.layers_per_block, "set_layer_cache: depth=%d must be 0 (off) or 1..%d (layers_per_block)", depth,
+                cfg_.layers_per_block);
+    LAVIE_CHECK(depth == 0 || cfg_.num_levels >= 3, "set_layer_cache: the model has %d levels, the layer cache needs 3 or more (FreeU's two "
+                "deepest up blocks must stay below level 0)", cfg_.num_levels);
+    lc_key_[0] = 0;
+    lc_depth_ = depth;
+    return ensure_layer_cache();
 }
 
 int UNet::set_freeu(float s1, float s2, float b1, float b2) {
@@ -1380,18 +1474,41 @@ int UNet::forward_graph(const half_t* sample, const float* timesteps, const half
 }
 
 int UNet::forward(const half_t* sample, const float* timesteps, const half_t* ctx, half_t* out, int B, int F, int H, int W,
-                  int ctx_len, hipStream_t stream, const int* class_labels_host) {
+                  int ctx_len, hipStream_t stream, const int* class_labels_host, int layer_cache) {
     LAVIE_CHECK(finalized_, "forward: call lavie_unet_finalize first");
     LAVIE_CHECK(sample && timesteps && ctx && out, "forward: null tensor");
     RUN(check_shape(cfg_, B, F, H, W, ctx_len));
     LAVIE_CHECK(ws_.total_bytes() > 0, "forward: call lavie_unet_prepare first");
+    const int key[6] = {B, F, H, W, ctx_len, lc_depth_};
+    if (layer_cache != LAVIE_LAYER_CACHE_OFF) {
+        const char* what = layer_cache == LAVIE_LAYER_CACHE_REUSE ? "reuse" : "refresh";
+        LAVIE_CHECK(layer_cache == LAVIE_LAYER_CACHE_REFRESH || layer_cache == LAVIE_LAYER_CACHE_REUSE,
+                    "forward_cached: mode=%d must be 0 (off), 1 (refresh) or 2 (reuse)", layer_cache);
+        LAVIE_CHECK(lc_depth_ > 0, "forward_cached: %s needs a layer cache: call lavie_unet_set_layer_cache with a depth >= 1", what);
+        // the cache's contents and its record belong to the order of execution, which a captured call has none of yet
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        LAVIE_HIP(hipStreamIsCapturing(stream, &cap));
+        LAVIE_CHECK(cap == hipStreamCaptureStatusNone, "forward_cached: %s on a capturing stream is not supported", what);
+        if (layer_cache == LAVIE_LAYER_CACHE_REUSE) {
+            LAVIE_CHECK(lc_key_[0] != 0, "forward_cached: reuse without a valid layer cache: run a refresh forward (mode 1) first");
+            LAVIE_CHECK(memcmp(key, lc_key_, sizeof(key)) == 0,
+                        "forward_cached: reuse with B=%d F=%d H=%d W=%d ctx_len=%d depth=%d, but the cache was filled with B=%d F=%d H=%d W=%d "
+                        "ctx_len=%d depth=%d", B, F, H, W, ctx_len, lc_depth_, lc_key_[0], lc_key_[1], lc_key_[2], lc_key_[3], lc_key_[4], lc_key_[5]);
+        } else {
+            lc_key_[0] = 0;                         // invalid until the walk has been enqueued whole
+        }
+    }
     RUN(ensure_tables(F, stream));
     ws_.release(0);
     const int pag = pag_route("forward", B);
     if (pag < 0) return -1;
     FwdCtx c = call_ctx(stream, &ws_, B, F, H, W, ctx, ctx_len, pag);
     c.labels = class_labels_host;
-    return run(c, sample, timesteps, ctx, out);
+    c.lc_mode = layer_cache;
+    c.lc_depth = layer_cache != LAVIE_LAYER_CACHE_OFF ? lc_depth_ : 0;
+    RUN(run(c, sample, timesteps, ctx, out));
+    if (layer_cache == LAVIE_LAYER_CACHE_REFRESH) memcpy(lc_key_, key, sizeof(key));
+    return 0;
 }
 
 int UNet::cache_context(const half_t* ctx, int B, int ctx_len, hipStream_t stream) {

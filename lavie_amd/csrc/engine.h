@@ -159,8 +159,10 @@ public:
     int set_param(const char* name, const void* data, long long numel);
     int finalize(hipStream_t stream);
     int prepare(int B, int F, int H, int W, int ctx_len);
+    // layer_cache: LAVIE_LAYER_CACHE_OFF (the plain forward), _REFRESH (the full walk, filling the layer cache) or _REUSE (the
+    // shallow walk on the cached activation); see set_layer_cache
     int forward(const half_t* sample, const float* timesteps, const half_t* ctx, half_t* out, int B, int F, int H, int W,
-                int ctx_len, hipStream_t stream, const int* class_labels_host);
+                int ctx_len, hipStream_t stream, const int* class_labels_host, int layer_cache = 0);
     int resnet_forward(const char* prefix, const half_t* x1, int C1, const half_t* x2, int C2, const float* temb, half_t* y,
                        int B, int F, int H, int W, hipStream_t stream);
     int transformer_forward(const char* prefix, half_t* x, const half_t* ctx, int B, int F, int H, int W, int ctx_len,
@@ -188,6 +190,11 @@ public:
     // spatial self-attention, perturbed < 0.  While on, set_cfg_shared_input is ignored (the perturbed entries differ from the first
     // self-attention on) and a forward needs B > perturbed.
     int set_pag(const char* const* layers, int n_layers, int perturbed);
+    // Layer cache (DeepCache): depth d in 1..layers_per_block puts cut A behind layer d - 1 of down level 0 and cut B in
+    // front of layer layers_per_block - d of the last up block; a refresh forward keeps the running activation at B, a reuse forward
+    // runs only the steps in front of A and behind B on it.  0 = off, the cache is freed.  Any call marks a held cache invalid.
+    int set_layer_cache(int depth);
+    long long layer_cache_bytes() const { return (long long)lc_bytes_; }
     // Low-rank adapters on the attention projections (to_q / to_k / to_v / to_out.0 of attn1 / attn2 / attn_temp).  set / clear /
     // set_scale only record (the set copies the caller's tensors on `stream`); apply merges every target of the blocks touched since
     // the last apply and re-derives those blocks' images in place: device addresses never change, captured graphs stay valid.
@@ -264,6 +271,17 @@ private:
     std::vector<char> pag_sel_;                     // set_pag: per transformer, attn1 perturbed; empty = off
     int pag_perturbed_ = 0;                         // trailing batch entries it applies to; read where a call enters, as the switches above
     int pag_route(const char* who, int B) const;    // the Route::pag of a call on B entries (0 = off), or -1 after refusing B <= perturbed
+    // layer cache (set_layer_cache): ONE hipMalloc'd block outside the workspace, sized by prepare() for its shape: the activation at
+    // cut B [rows(0), C] fp16 and its statistics buffer.  lc_act_ is the tensor as its producer in the last refresh forward left it;
+    // lc_key_ = (B, F, H, W, ctx_len, depth) of that forward, all 0 = invalid
+    int lc_depth_ = 0;
+    void* lc_block_ = nullptr;
+    size_t lc_bytes_ = 0;
+    Act lc_act_;
+    int lc_key_[6] = {0, 0, 0, 0, 0, 0};
+    int lc_shape_[4] = {0, 0, 0, 0};                // B, F, H, W of the latest prepare()
+    int lc_channels(int depth) const { return cfg_.block_out_channels[depth == cfg_.layers_per_block ? 1 : 0]; }
+    int ensure_layer_cache();                       // (re)allocates the block for lc_shape_ and lc_depth_; invalidates on a change
 
     DeviceArena weights_, ws_;
     // packed model

@@ -365,6 +365,82 @@ static lavie_unet_config production_config() {        // the base model: 4 level
     return c;
 }
 
+// The layer cache's entries: argument refusals, the states in which a reuse call is refused, and what each mode launches (a refresh call
+// launches what the plain forward does, a reuse call fewer, the deeper the cut the more), on three-level models at reduced widths
+static void run_layer_cache(bool vsr) {
+    lavie_unet_config cfg = base_config();
+    cfg.num_levels = 3;
+    cfg.block_out_channels[2] = 640; cfg.attn_levels[1] = 1; cfg.attn_levels[2] = 0;
+    if (vsr) {
+        cfg.in_channels = 8; cfg.block_out_channels[0] = 256; cfg.block_out_channels[1] = 512; cfg.block_out_channels[2] = 512;
+        cfg.vsr_blocks = 1; cfg.only_cross_attention[0] = 1; cfg.vsr_temporal_modules = 1; cfg.num_class_embeds = 10;
+    }
+    auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+    {   // fewer than three levels: refused
+        Model two(base_config());
+        REQUIRE(refused(lavie_unet_set_layer_cache(two.h, 1), "levels"));
+        REQUIRE(lavie_unet_set_layer_cache(two.h, 0) == 0 && lavie_unet_layer_cache_bytes(two.h) == 0);
+    }
+    Model m(cfg);
+    const int B = 2, F = 4, H = 8, W = 8, L = 77;
+    std::vector<unsigned short> x((size_t)B * cfg.in_channels * F * H * W), y((size_t)B * cfg.out_channels * F * H * W);
+    std::vector<unsigned short> ctx((size_t)B * L * cfg.cross_attention_dim);
+    std::vector<float> t(B, 500.f);
+    std::vector<int> lab(B, 3);
+    const int* labels = vsr ? lab.data() : nullptr;
+    auto fwd = [&](int mode, int b = B) {
+        return lavie_unet_forward_cached(m.h, x.data(), t.data(), ctx.data(), labels, y.data(), b, F, H, W, L, mode, nullptr);
+    };
+    auto launches = [&](int mode) {
+        const long b = lavie_hostcheck_launches();
+        REQUIRE(fwd(mode) == 0);
+        return lavie_hostcheck_launches() - b;
+    };
+    REQUIRE(refused(lavie_unet_set_layer_cache(nullptr, 1), "null handle") && lavie_unet_layer_cache_bytes(nullptr) == -1);
+    REQUIRE(refused(lavie_unet_set_layer_cache(m.h, -1), "depth=-1"));
+    REQUIRE(refused(lavie_unet_set_layer_cache(m.h, cfg.layers_per_block + 1), "depth=3"));
+    REQUIRE(lavie_unet_set_layer_cache(m.h, 1) == 0);
+    REQUIRE(lavie_unet_layer_cache_bytes(m.h) == 0);                       // no shape yet: prepare() allocates
+    REQUIRE(lavie_unet_prepare(m.h, B, F, H, W, L) == 0);
+    const long long rows0 = (long long)B * F * H * W;
+    REQUIRE(lavie_unet_layer_cache_bytes(m.h) >= rows0 * cfg.block_out_channels[0] * 2);
+    REQUIRE(refused(lavie_unet_forward_cached(nullptr, x.data(), t.data(), ctx.data(), labels, y.data(), B, F, H, W, L, 0, nullptr), "null handle"));
+    REQUIRE(refused(fwd(3), "mode=3") && refused(fwd(-1), "mode=-1"));
+    REQUIRE(refused(fwd(LAVIE_LAYER_CACHE_REUSE), "refresh"));            // reuse before any refresh
+    REQUIRE(fwd(LAVIE_LAYER_CACHE_OFF) == 0);                             // (the first forward builds the per-F tables)
+    REQUIRE(refused(fwd(LAVIE_LAYER_CACHE_REUSE), "refresh"));            // a plain forward fills nothing
+    const long plain = launches(LAVIE_LAYER_CACHE_OFF);
+    REQUIRE(launches(LAVIE_LAYER_CACHE_REFRESH) == plain);                // the full walk, launch for launch
+    const long shallow1 = launches(LAVIE_LAYER_CACHE_REUSE);
+    REQUIRE(shallow1 > 0 && shallow1 < plain);
+    REQUIRE(launches(LAVIE_LAYER_CACHE_OFF) == plain && launches(LAVIE_LAYER_CACHE_REUSE) == shallow1);      // a plain forward in between keeps it
+    REQUIRE(refused(fwd(LAVIE_LAYER_CACHE_REUSE, 1), "B=1"));             // another batch than the recorded one
+    REQUIRE(launches(LAVIE_LAYER_CACHE_REUSE) == shallow1);
+    if (!vsr) {     // the shared CFG prefix lies in front of cut A: the same saving in a reuse call as in the plain forward
+        REQUIRE(lavie_unet_cache_context(m.h, ctx.data(), B, L, nullptr) == 0);
+        const long plain_c = launches(LAVIE_LAYER_CACHE_OFF);
+        REQUIRE(lavie_unet_set_cfg_shared_input(m.h, 1) == 0);
+        REQUIRE(launches(LAVIE_LAYER_CACHE_REFRESH) == launches(LAVIE_LAYER_CACHE_OFF));
+        REQUIRE(launches(LAVIE_LAYER_CACHE_REUSE) < plain_c);
+        REQUIRE(lavie_unet_set_cfg_shared_input(m.h, 0) == 0);
+        REQUIRE(lavie_unet_cache_context(m.h, nullptr, 0, 0, nullptr) == 0);
+    }
+    REQUIRE(lavie_unet_set_layer_cache(m.h, 2) == 0);                      // another depth: the held cache is invalid
+    REQUIRE(lavie_unet_layer_cache_bytes(m.h) >= rows0 * cfg.block_out_channels[1] * 2);      // B now lies behind the upsampler: level 1's width
+    REQUIRE(refused(fwd(LAVIE_LAYER_CACHE_REUSE), "refresh"));
+    REQUIRE(launches(LAVIE_LAYER_CACHE_REFRESH) == plain);
+    const long shallow2 = launches(LAVIE_LAYER_CACHE_REUSE);
+    REQUIRE(shallow2 > shallow1 && shallow2 < plain);
+    REQUIRE(lavie_unet_prepare(m.h, B, F, H, W, L) == 0);                  // the same shape again: kept
+    REQUIRE(launches(LAVIE_LAYER_CACHE_REUSE) == shallow2);
+    REQUIRE(lavie_unet_prepare(m.h, B, F, 2 * H, W, L) == 0);              // another shape: invalid
+    REQUIRE(refused(fwd(LAVIE_LAYER_CACHE_REUSE), "refresh"));
+    REQUIRE(launches(LAVIE_LAYER_CACHE_REFRESH) == plain && launches(LAVIE_LAYER_CACHE_REUSE) == shallow2);
+    REQUIRE(lavie_unet_set_layer_cache(m.h, 0) == 0 && lavie_unet_layer_cache_bytes(m.h) == 0);
+    REQUIRE(refused(fwd(LAVIE_LAYER_CACHE_REUSE), "set_layer_cache") && refused(fwd(LAVIE_LAYER_CACHE_REFRESH), "set_layer_cache"));
+    REQUIRE(launches(LAVIE_LAYER_CACHE_OFF) == plain);
+}
+
 static void run_traces(const char* path) {
     g_out = fopen(path, "w");
     REQUIRE(g_out != nullptr);
@@ -879,6 +955,8 @@ int main(int argc, char** argv) {
         c.vsr_blocks = 1; c.only_cross_attention[0] = 1; c.vsr_temporal_modules = 1; c.num_class_embeds = 10;
         run_model(c, 2, 4, 8, 8, true);
     }
+    run_layer_cache(false);
+    run_layer_cache(true);
     // operator-level argument checks
     REQUIRE(lavie_linear_f16(nullptr, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, 0, 16, 64, 63, 0, nullptr) != 0);
     REQUIRE(lavie_geglu_mlp_image_bytes(123) == 0);

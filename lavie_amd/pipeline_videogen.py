@@ -133,6 +133,7 @@ class VideoGenPipeline:
         an optional `guidance_rescale` (not a key of the reference) becomes the keyword of that name,
         an optional `freeu: {s1:, s2:, b1:, b2:}` (not a key of the reference either) is set on the UNet (enable_freeu),
         optional `pag_scale` / `pag_adaptive_scale` / `pag_applied_layers` (a name or a list of names) become the keywords of those names,
+        optional `cache_interval` / `cache_depth` (the layer cache; not keys of the reference) become the keywords of those names,
         `seed` is returned in cfg for torch.manual_seed (sample.py:22-23).  `use_fp16` and
         `enable_xformers_memory_efficient_attention` are read by nobody in sample.py and are ignored here as well.
         PyYAML's safe loader replaces omegaconf (absent from the image); interpolation / `${...}` references are not resolved."""
@@ -168,6 +169,9 @@ class VideoGenPipeline:
                           ("pag_applied_layers", lambda v: (v,) if isinstance(v, str) else tuple(v))):
             if key in cfg:
                 call_kwargs[key] = conv(cfg[key])
+        for key in ("cache_interval", "cache_depth"):
+            if key in cfg:
+                call_kwargs[key] = int(cfg[key])
         pipe = VideoGenPipeline(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet, scheduler=scheduler)
         if "freeu" in cfg:                      # {s1:, s2:, b1:, b2:}, all four: the setting goes onto the model
             fu = cfg["freeu"]
@@ -281,7 +285,7 @@ class VideoGenPipeline:
                 known_noise: Optional[torch.Tensor] = None, start_step: int = 0, window_length: Optional[int] = None,
                 window_stride: Optional[int] = None, window_weights: str = "triangle",
                 guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                pag_applied_layers=("mid_block",)) -> torch.Tensor:
+                pag_applied_layers=("mid_block",), cache_interval: Optional[int] = None, cache_depth: int = 1) -> torch.Tensor:
         """latents fp32 [P, C, F, h, w] on the device, ctx fp16 [2P, n, d] = [negative | prompt] (guidance_scale > 1) or
         [P, n, d] = prompt only (guidance_scale <= 1: no classifier-free guidance, :626) -> denoised fp32.  One loop, one step
         launch per denoising step; step plan, step noise, engine session and step dispatch are lavie_amd.sampling's.
@@ -316,7 +320,15 @@ class VideoGenPipeline:
         eps = e_cfg + s_t (eps_prompt - eps_perturbed), s_t = max(pag_scale - pag_adaptive_scale (1000 - t), 0), in the one launch
         (ops.cfg_pag_sampler_step and kin).  The UNet's PAG setting is made for the loop and restored afterwards, also after an
         exception.  Not combined with known latents, frame windows, `guidance_rescale` > 0 or a `guidance_scale` sequence; at most
-        2 prompts per call with guidance, 4 without (the engine's batch limit of 8).  pag_scale = 0 is the call without it."""
+        2 prompts per call with guidance, 4 without (the engine's batch limit of 8).  pag_scale = 0 is the call without it.
+
+        Layer cache (DeepCache; `UNet.enable_layer_cache`): with `cache_interval` = N > 1 the whole UNet runs on the executed steps
+        0, N, 2N, ... (the first step a run takes always refreshes, also when `start_step` > 0) and the steps between run only the
+        first `cache_depth` layers of the first down block and the last `cache_depth` + 1 of the last up block on the activation the
+        latest full step left.  An approximation whose quality at a given N is the caller's trade-off.  The UNet's own setting
+        comes back after the loop.  Not combined with frame windows.  None or 1 is the call without it."""
+        cache_interval = sampling.check_layer_cache(cache_interval, cache_depth,
+                                                    window_length is not None and latents.shape[2] > int(window_length))
         pag = self.check_pag(pag_scale, pag_adaptive_scale, latents.shape[0], guidance_scale, guidance_rescale,
                              known=known, mask=mask, known_noise=known_noise, window_length=window_length)
         windowed = False
@@ -385,21 +397,25 @@ class VideoGenPipeline:
         try:
             if pag:
                 self.unet.set_pag(pag_applied_layers, p)
-            x = self._denoise_loop(x, ctx, nb, frames, starts, model_in, guidance, plan, noise, x0_prev, t_dev, start_step, windowed,
-                                   profile if windowed else None, known, mask, known_noise, region, callback, callback_steps,
-                                   pag_scale, pag_adaptive_scale)
+            with sampling.layer_cache_session(self.unet, cache_interval, cache_depth):
+                x = self._denoise_loop(x, ctx, nb, frames, starts, model_in, guidance, plan, noise, x0_prev, t_dev, start_step, windowed,
+                                       profile if windowed else None, known, mask, known_noise, region, callback, callback_steps,
+                                       pag_scale, pag_adaptive_scale, cache_interval)
         finally:
             if pag_was is not None:
                 self.unet.set_pag(*pag_was)
         return x
 
     def _denoise_loop(self, x, ctx, nb, frames, starts, model_in, guidance, plan, noise, x0_prev, t_dev, start_step, windowed, profile,
-                      known, mask, known_noise, region, callback, callback_steps, pag_scale, pag_adaptive_scale):
+                      known, mask, known_noise, region, callback, callback_steps, pag_scale, pag_adaptive_scale, cache_interval=1):
         """The engine session and the steps of `denoise`, on the buffers it has set up."""
         pag = isinstance(guidance, sampling.PagGuidance)
         with sampling.engine_session(self.unet, nb, frames, x.shape[3], x.shape[4], ctx,
                                      model_in if guidance is not None and self.cfg_shared_prefix and not pag else None) as ctx:
-            forwards = sampling.WindowForwards(lambda w, i: self.unet(model_in[w], t_dev[i], encoder_hidden_states=ctx).sample)
+            def forward(w, i):                 # (the keyword only where the cache is on: any UNet-shaped callable serves without)
+                mode = sampling.layer_cache_mode(i - start_step, cache_interval)
+                return self.unet(model_in[w], t_dev[i], encoder_hidden_states=ctx, **({"layer_cache": mode} if mode else {})).sample
+            forwards = sampling.WindowForwards(forward)
             for i in range(start_step, len(plan.timesteps)):
                 eps = forwards(len(model_in), i)                                                      # line 670
                 if pag:
@@ -508,11 +524,14 @@ class VideoGenPipeline:
                  known_latents: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None,
                  video: Optional[torch.Tensor] = None, strength: float = 1.0, window_length: Optional[int] = None,
                  window_stride: Optional[int] = None, window_weights: str = "triangle", guidance_rescale: float = 0.0,
-                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid_block",)):
+                 pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid_block",),
+                 cache_interval: Optional[int] = None, cache_depth: int = 1):
         """`guidance_scale`: one number, or a sequence with one value > 1 per prompt (repeated per `num_images_per_prompt`; a
         sequence always means guidance is on).  `guidance_rescale` in [0, 1]: diffusers' rescale_noise_cfg inside the fused step;
         ignored with a scalar `guidance_scale` <= 1, as in diffusers.  `pag_scale` > 0: perturbed-attention guidance in the
-        transformers `pag_applied_layers` names, fading by `pag_adaptive_scale` per timestep below 1000.  See `denoise`."""
+        transformers `pag_applied_layers` names, fading by `pag_adaptive_scale` per timestep below 1000.  `cache_interval` = N > 1: the layer cache, the whole UNet on every
+        N-th step only, at `cache_depth`; not with `window_length`.  See `denoise`."""
+        sampling.check_layer_cache(cache_interval, cache_depth, window_length is not None and video_length > int(window_length))
         if window_length is not None and (known_latents is not None or known_mask is not None or video is not None or strength != 1.0):
             raise ValueError("frame windows (`window_length`) cannot be combined with `known_latents` / `known_mask` / `video` / "
                              "`strength`")
@@ -552,6 +571,8 @@ class VideoGenPipeline:
         rescale = dict(guidance_rescale=guidance_rescale) if guidance_rescale else {}      # absent = today's call
         if pag:
             rescale.update(pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale, pag_applied_layers=pag_applied_layers)
+        if cache_interval not in (None, 1):
+            rescale.update(cache_interval=cache_interval, cache_depth=cache_depth)
         lora_scale = (cross_attention_kwargs or {}).get("scale")
         if lora_scale is None:
             latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta,

@@ -162,6 +162,50 @@ def engine_session(unet, batch: int, frames: int, height: int, width: int, ctx: 
             raise cleanup_error
 
 
+def check_layer_cache(cache_interval, cache_depth=1, windowed: bool = False) -> int:
+    """The layer-cache arguments of a pipeline call -> the interval in force: 1 = off (`cache_interval` None or 1: the call without
+    it), N > 1 = the whole UNet runs on every N-th executed step and the shallow walk on the steps between (`layer_cache_mode`).
+    Not combined with frame windows: a windowed step runs several forwards, each of which would need a cache of its own."""
+    if cache_interval is None:
+        return 1
+    if isinstance(cache_interval, bool) or not isinstance(cache_interval, int) or cache_interval < 1:
+        raise ValueError(f"`cache_interval` must be an integer >= 1 (or None) but is {cache_interval!r}")
+    if isinstance(cache_depth, bool) or not isinstance(cache_depth, int) or cache_depth < 1:
+        raise ValueError(f"`cache_depth` must be an integer >= 1 but is {cache_depth!r}")
+    if cache_interval > 1 and windowed:
+        raise ValueError("`cache_interval` > 1 cannot be combined with frame windows (`window_length`): every window's forward "
+                         "would need a layer cache of its own")
+    return cache_interval
+
+
+def layer_cache_mode(executed: int, cache_interval: int):
+    """The `layer_cache` argument of the UNet forward of the `executed`-th step a loop runs (0 = its first, wherever in the timestep
+    table it starts): None without caching, "refresh" iff executed % cache_interval == 0, else "reuse"."""
+    if cache_interval <= 1:
+        return None
+    return "refresh" if executed % cache_interval == 0 else "reuse"
+
+
+@contextlib.contextmanager
+def layer_cache_session(unet, cache_interval: int, cache_depth: int = 1):
+    """The UNet's layer cache switched on at `cache_depth` for one loop (cache_interval > 1) and put back to the model's own setting
+    afterwards, also after an exception; what the loop cached is dropped either way.  cache_interval <= 1: nothing is touched."""
+    if cache_interval <= 1:
+        yield
+        return
+    if not hasattr(unet, "enable_layer_cache"):
+        raise ValueError(f"`cache_interval` > 1: {type(unet).__name__} has no layer cache")
+    was = unet.layer_cache
+    unet.enable_layer_cache(cache_depth)
+    try:
+        yield
+    finally:
+        if was:
+            unet.enable_layer_cache(was)
+        else:
+            unet.disable_layer_cache()
+
+
 def check_guidance(guidance_scale, guidance_rescale, count: int, repeat: int = 1):
     """The guidance arguments of a pipeline call -> (guided, scales, rescale).  `guidance_scale`: one number (guidance is on when
     it is > 1), or a sequence with one value for each of the `count` prompts, every one > 1 (a sequence always means guidance is

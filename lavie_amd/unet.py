@@ -246,6 +246,8 @@ class UNet3DConditionModel(nn.Module):
                     _lib.check(lib.lavie_unet_set_freeu(handle, *self.freeu), "lavie_unet_set_freeu")
                 if self.pag != ((), 0):
                     self._set_pag_engine(lib, handle, *self.pag)
+                if self.layer_cache:
+                    _lib.check(lib.lavie_unet_set_layer_cache(handle, self.layer_cache), "lavie_unet_set_layer_cache")
                 if self._lora:
                     keep += self._lora_register(handle, stream)
                     _lib.check(lib.lavie_unet_lora_set_scale(handle, float(self._lora_scale)), "lavie_unet_lora_set_scale")
@@ -573,6 +575,51 @@ class UNet3DConditionModel(nn.Module):
     def disable_pag(self) -> None:
         self.set_pag((), 0)
 
+    # ------------------------------------------------------------------ layer cache (DeepCache)
+    LAYER_CACHE_MODES = {None: 0, "refresh": 1, "reuse": 2}
+
+    @property
+    def layer_cache(self) -> int:
+        """The depth of the layer cache's cuts; 0 = off."""
+        return self.__dict__.get("_layer_cache", 0)
+
+    def enable_layer_cache(self, depth: int = 1) -> None:
+        """Feature caching across denoising steps (DeepCache, Ma et al.): forward(layer_cache="refresh") runs the whole network and
+        keeps the activation that enters the last `depth` + 1 layers of the last up block; forward(layer_cache="reuse") runs only the
+        first `depth` layers of the first down block and those up layers on it (lavie_unet_set_layer_cache).  depth in
+        1..layers_per_block; the model needs three levels or more.  A call drops what is cached.  The cached tensor is whatever the
+        refresh computed: weights, adapters, FreeU or PAG changed before a reuse are the caller's business."""
+        depth = int(depth)
+        if not 1 <= depth <= self.cfg.layers_per_block:
+            raise ValueError(f"enable_layer_cache: depth={depth} must be in 1..{self.cfg.layers_per_block} (layers_per_block)")
+        if len(self.cfg.block_out_channels) < 3:
+            raise ValueError(f"enable_layer_cache: the model has {len(self.cfg.block_out_channels)} levels, the layer cache needs 3")
+        self._set_layer_cache(depth)
+
+    def disable_layer_cache(self) -> None:
+        self._set_layer_cache(0)
+
+    def _set_layer_cache(self, depth: int) -> None:
+        if self.__dict__.get("_engine"):
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().lavie_unet_set_layer_cache(self._engine, depth), "lavie_unet_set_layer_cache")
+        self.__dict__["_layer_cache"] = depth
+
+    def layer_cache_bytes(self) -> int:
+        """Device bytes the cache holds now (allocated by prepare / the first forward of a shape)."""
+        handle = self.__dict__.get("_engine")
+        return int(_lib.load().lavie_unet_layer_cache_bytes(handle)) if handle else 0
+
+    def _layer_cache_mode(self, layer_cache) -> int:
+        """forward's `layer_cache` argument as the engine's mode, after the checks that need no engine."""
+        if layer_cache not in self.LAYER_CACHE_MODES:
+            raise ValueError(f"layer_cache={layer_cache!r} must be None, 'refresh' or 'reuse'")
+        if layer_cache is not None and not self.layer_cache:
+            raise RuntimeError(f"layer_cache={layer_cache!r} needs enable_layer_cache(depth) first")
+        if layer_cache is not None and self.__dict__.get("_graph"):
+            raise RuntimeError("the layer cache has no graph-replayed form: enable_graph(False) first")
+        return self.LAYER_CACHE_MODES[layer_cache]
+
     def enable_graph(self, on: bool = True) -> None:
         """Replay the forward from a hipGraph (lavie_unet_forward_graph).  While on, the timestep and the output live in
         per-shape buffers owned by this module, so the captured addresses repeat from call to call: the returned tensor is
@@ -586,7 +633,9 @@ class UNet3DConditionModel(nn.Module):
     @torch.no_grad()
     def forward(self, sample: torch.Tensor, timestep: Union[torch.Tensor, float, int],
                 encoder_hidden_states: torch.Tensor = None, class_labels: Optional[torch.Tensor] = None,
-                attention_mask: Optional[torch.Tensor] = None, use_image_num: int = 0, return_dict: bool = True):
+                attention_mask: Optional[torch.Tensor] = None, use_image_num: int = 0, return_dict: bool = True,
+                layer_cache: Optional[str] = None):
+        mode = self._layer_cache_mode(layer_cache)
         if class_labels is not None or attention_mask is not None or use_image_num:
             raise NotImplementedError("class_labels / attention_mask / use_image_num are outside the MI355X path")
         if sample.dim() != 5:
@@ -624,9 +673,14 @@ class UNet3DConditionModel(nn.Module):
             entry, what = lib.lavie_unet_forward, "lavie_unet_forward"
         with torch.cuda.device(dev):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(entry(handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(t.data_ptr()),
-                             ctypes.c_void_p(ctx.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                             b, f, h, w, n_ctx, stream), what)
+            if mode:
+                _lib.check(lib.lavie_unet_forward_cached(handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(t.data_ptr()),
+                                                         ctypes.c_void_p(ctx.data_ptr()), None, ctypes.c_void_p(out.data_ptr()),
+                                                         b, f, h, w, n_ctx, mode, stream), "lavie_unet_forward_cached")
+            else:
+                _lib.check(entry(handle, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(t.data_ptr()),
+                                 ctypes.c_void_p(ctx.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                 b, f, h, w, n_ctx, stream), what)
         if not return_dict:
             return (out,)
         return UNet3DConditionOutput(sample=out)

@@ -77,7 +77,7 @@ class VideoUpscalePipeline:
                 num_inference_steps: int, guidance_scale: float, eta: float = 0.0, generator=None,
                 callback: Optional[Callable] = None, callback_steps: int = 1, window_length: Optional[int] = None,
                 window_stride: Optional[int] = None, window_weights: str = "triangle",
-                guidance_rescale: float = 0.0) -> torch.Tensor:
+                guidance_rescale: float = 0.0, cache_interval: Optional[int] = None, cache_depth: int = 1) -> torch.Tensor:
         """latents fp32 [P, 4, F, h, w]; image = the NOISED low-res frames [P, 3, F, h, w]; ctx fp16 [2P, n, d] =
         [negative | prompt] -> denoised latents fp32.  Step plan, step noise, engine session and step dispatch are
         lavie_amd.sampling's.
@@ -90,7 +90,13 @@ class VideoUpscalePipeline:
         independent chunks, neighbouring windows share their overlap frames at every step, so there is no seam between them.
 
         `guidance_scale` may be a sequence with one value > 1 per latent, `guidance_rescale` in (0, 1] is diffusers'
-        rescale_noise_cfg inside the fused step: see VideoGenPipeline.denoise."""
+        rescale_noise_cfg inside the fused step: see VideoGenPipeline.denoise.
+
+        `cache_interval` = N > 1: the layer cache (DeepCache; `UNet.enable_layer_cache` at `cache_depth`): the whole UNet runs on
+        steps 0, N, 2N, ... of this call, so every chunk starts with a refresh, the shallow walk on the steps between.  Not
+        combined with frame windows.  None or 1 is the call without it."""
+        cache_interval = sampling.check_layer_cache(cache_interval, cache_depth,
+                                                    window_length is not None and latents.shape[2] > int(window_length))
         windowed = False
         if window_length is not None:
             if int(window_length) < 1:
@@ -122,9 +128,13 @@ class VideoUpscalePipeline:
         noise = sampling.StepNoise(x, generator)
         t_dev = plan.t_dev(dev)
         # text keys / values once per chunk (or once for the whole windowed clip), not once per block and step
-        with sampling.engine_session(self.unet, 2 * p, frames, x.shape[3], x.shape[4], ctx) as ctx:
-            forwards = sampling.WindowForwards(lambda w, i: self.unet(model_in[w], t_dev[i], low[w], encoder_hidden_states=ctx,
-                                                                      class_labels=labels).sample)                    # :716-718
+        with sampling.layer_cache_session(self.unet, cache_interval, cache_depth), \
+                sampling.engine_session(self.unet, 2 * p, frames, x.shape[3], x.shape[4], ctx) as ctx:
+            def forward(w, i):                                                                                        # :716-718
+                mode = sampling.layer_cache_mode(i, cache_interval)
+                return self.unet(model_in[w], t_dev[i], low[w], encoder_hidden_states=ctx, class_labels=labels,
+                                 **({"layer_cache": mode} if mode else {})).sample
+            forwards = sampling.WindowForwards(forward)
             for i, t in enumerate(plan.timesteps):
                 eps = forwards(len(model_in), i)
                 coeffs = plan.coeffs(i)
@@ -146,9 +156,11 @@ class VideoUpscalePipeline:
                  latents: Optional[torch.Tensor] = None, prompt_embeds: Optional[torch.Tensor] = None,
                  negative_prompt_embeds: Optional[torch.Tensor] = None, output_type: Optional[str] = "latent",
                  return_dict: bool = True, callback=None, callback_steps: int = 1, window_length: Optional[int] = None,
-                 window_stride: Optional[int] = None, window_weights: str = "triangle", guidance_rescale: float = 0.0):
+                 window_stride: Optional[int] = None, window_weights: str = "triangle", guidance_rescale: float = 0.0,
+                 cache_interval: Optional[int] = None, cache_depth: int = 1):
         """`guidance_scale`: one number > 1, or a sequence with one value > 1 per prompt (repeated per `num_images_per_prompt`);
-        `guidance_rescale` in [0, 1]: diffusers' rescale_noise_cfg inside the fused step.  See `denoise`."""
+        `guidance_rescale` in [0, 1]: diffusers' rescale_noise_cfg inside the fused step; `cache_interval` = N > 1: the layer cache,
+        the whole UNet on every N-th step only, at `cache_depth` (not with `window_length`).  See `denoise`."""
         self.check_inputs(image, noise_level, callback_steps, prompt, prompt_embeds, negative_prompt_embeds)
         if prompt is not None:
             raise NotImplementedError("text encoding is not built: pass prompt_embeds / negative_prompt_embeds")
@@ -172,7 +184,8 @@ class VideoUpscalePipeline:
                              f"{self.unet.config.in_channels} but received 4 + {image.shape[1]} channels")
         latents = self.denoise(latents, image, ctx, noise_level, num_inference_steps, guidance_scale, eta, generator, callback,
                                callback_steps, window_length, window_stride, window_weights,
-                               **(dict(guidance_rescale=guidance_rescale) if guidance_rescale else {}))
+                               **(dict(guidance_rescale=guidance_rescale) if guidance_rescale else {}),
+                               **(dict(cache_interval=cache_interval, cache_depth=cache_depth) if cache_interval not in (None, 1) else {}))
         if output_type != "latent":
             if self.vae is None:
                 raise ValueError("no vae attached: use output_type='latent'")
@@ -191,7 +204,9 @@ def upscale_in_chunks(pipeline: VideoUpscalePipeline, vframes: torch.Tensor, sho
     """vsr/sample.py:104-123: clips longer than `short_seq` frames go through the pipeline `short_seq` frames at a time
     (same generator across chunks); outputs are concatenated along the frame axis.
     overlap > 0 (not in the reference): the whole clip is ONE run over windows of `short_seq` frames that share `overlap` frames
-    with their neighbours, fused at every step (`VideoUpscalePipeline.denoise(window_length=)`), so the chunks no longer meet at a seam."""
+    with their neighbours, fused at every step (`VideoUpscalePipeline.denoise(window_length=)`), so the chunks no longer meet at a seam.
+    `cache_interval` / `cache_depth` in `kw` (the layer cache) reach every chunk's call, so each chunk starts with a full step; with
+    overlap > 0 on a clip longer than `short_seq` the pipeline refuses them."""
     total = vframes.shape[2]
     if not 0 <= overlap < short_seq:
         raise ValueError(f"overlap={overlap} must lie in 0..{short_seq - 1} (short_seq={short_seq})")

@@ -78,7 +78,8 @@ class UNet3DVSRModel(_BaseUNet):
     # ------------------------------------------------------------------ forward (vsr/models/unet.py:408-600)
     @torch.no_grad()
     def forward(self, sample: torch.Tensor, timestep, low_res: torch.Tensor, encoder_hidden_states: torch.Tensor = None,
-                class_labels=20, low_res_clean=None, attention_mask=None, return_dict: bool = True):
+                class_labels=20, low_res_clean=None, attention_mask=None, return_dict: bool = True, layer_cache=None):
+        mode = self._layer_cache_mode(layer_cache)
         if attention_mask is not None or low_res_clean is not None:
             raise NotImplementedError("attention_mask / low_res_clean are outside the MI355X path")
         if sample.dim() != 5 or low_res.dim() != 5:
@@ -113,6 +114,12 @@ class UNet3DVSRModel(_BaseUNet):
                 if bool((labels > self.max_noise_level).any()):          # :498-499
                     raise ValueError(f"`noise_level` has to be <= {self.max_noise_level} but is {class_labels}")
                 arr = (ctypes.c_int * b)(*[int(v) for v in labels])
+            else:
+                arr = None
+            if mode:
+                _lib.check(lib.lavie_unet_forward_cached(*args, arr, ctypes.c_void_p(out.data_ptr()), b, f, h, w, n_ctx, mode, stream),
+                           "lavie_unet_forward_cached")
+            elif arr is not None:
                 _lib.check(lib.lavie_unet_forward_labels(*args, arr, ctypes.c_void_p(out.data_ptr()), b, f, h, w, n_ctx, stream),
                            "lavie_unet_forward_labels")
             else:
