@@ -196,6 +196,43 @@ long long lavie_freeu_workspace_bytes(int C2, int NI, int H, int W);      /* 0 f
 int lavie_freeu_f16(const void* h, int C_h, const void* skip, int C2, int NI, int H, int W, float b, float s, void* h_out,
                     void* skip_out, void* workspace, void* stream);
 
+/* FreeInit's frequency mix (Wu et al., "FreeInit: Bridging Initialization Gap in Video Diffusion Models"; diffusers' FreeInitMixin;
+ * additive in ABI 8; csrc/freq_mix.hip).  For each of `images` fp32 volumes [F, H, W] (the (video, channel) planes of
+ * latents [P, C, F, H, W]):
+ *   d           = fma(a, x0, fma(s, e0, -(r z)))                      the sampled latents re-noised to (a, s), minus the fresh noise
+ *   out         = fma(Re IFFT3(filter .* FFT3(d)), 1 / (F H W), r z)   unnormalised forward and inverse transforms over (F, H, W)
+ *   model_in[j] = fp16(out input_scale), j < dup                      rounded once, as lavie_latents_to_scaled_model_input1; copy j lies
+ *                                                                     j dup_stride elements behind model_in
+ * filter: fp32 [F, H, W] in FFT-native order (frequency 0 first), shared by all images.  It must be even in frequency,
+ * filter[-k] = filter[k] (the caller takes the even part of a filter that is not, which is what the real part of the transform
+ * keeps): the kernel computes the real part only.  A separable direct DFT in fp32, six launches; twiddles are tables rounded
+ * from fp64, indexed by (k n) mod N.  Every sum runs in ascending order in one accumulator, without atomics: two calls give equal
+ * bits and an image has the bits of its single-image call.  out may be x0; no other overlap is allowed.  No allocation, no
+ * synchronisation (capturable).  workspace: lavie_freq_mix_workspace_bytes() bytes, 8-byte aligned.
+ * Checked before anything is launched, each refusal names its argument: args != NULL and its struct_size; 1 <= images <= 65535,
+ * 1 <= F <= 256, 1 <= H, W <= 128; non-null x0 / e0 / z / filter / out / workspace; workspace_bytes; finite a, s, r and input_scale;
+ * with model_in: 1 <= dup <= 3 and dup_stride >= images F H W. */
+#define LAVIE_FREQ_MIX_MAX_F 256
+#define LAVIE_FREQ_MIX_MAX_HW 128
+typedef struct lavie_freq_mix_args {
+    int struct_size;                  /* sizeof this struct as the CALLER declared it; any other value is refused */
+    int images, F, H, W;              /* volumes (videos x channels) and the three transformed axes */
+    const float* x0;                  /* [images, F, H, W] fp32, device: the latents a sampling run returned */
+    const float* e0;                  /* the same shape: the unit noise the first run started from */
+    const float* z;                   /* the same shape: fresh unit noise */
+    const float* filter;              /* [F, H, W] fp32, device, FFT-native order, even in frequency */
+    float a, s, r;                    /* noise level (a, s) of the last training timestep; r = init_noise_sigma */
+    float* out;                       /* [images, F, H, W] fp32, device; may be x0 */
+    void* model_in;                   /* fp16, device, or NULL: dup copies of fp16(out input_scale) */
+    int dup;                          /* 1..3 copies (read only with model_in) */
+    long long dup_stride;             /* elements between two copies, >= images F H W */
+    float input_scale;
+    void* workspace;                  /* device */
+    long long workspace_bytes;
+} lavie_freq_mix_args;
+long long lavie_freq_mix_workspace_bytes(int images, int F, int H, int W);   /* 0 for a shape the op refuses */
+int lavie_freq_mix_f32(const lavie_freq_mix_args* args, void* stream);
+
 /* Fused feed-forward sub-block (ABI 5): y = x + W2 (h * gelu(g)) + b2 with (h, g) = W1 LayerNorm(x) + b1 — the
  * `hidden_states = self.ff(self.norm3(hidden_states)) + hidden_states` line of BasicTransformerBlock
  * (/root/reference/base/models/attention.py:558; FeedForward / GEGLU spec /root/reference/vsr/models/diffusers_attention.py:

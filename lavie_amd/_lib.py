@@ -53,6 +53,13 @@ class GuidanceTableArgsC(C.Structure):   # lavie_guidance_table_args
                 ("partials_floats", c_ll), ("table", c_float_p), ("moments", c_void_p)]
 
 
+class FreqMixArgsC(C.Structure):      # lavie_freq_mix_args
+    _fields_ = [("struct_size", c_int), ("images", c_int), ("F", c_int), ("H", c_int), ("W", c_int), ("x0", c_float_p), ("e0", c_float_p),
+                ("z", c_float_p), ("filter", c_float_p), ("a", c_float), ("s", c_float), ("r", c_float), ("out", c_float_p),
+                ("model_in", c_void_p), ("dup", c_int), ("dup_stride", c_ll), ("input_scale", c_float), ("workspace", c_void_p),
+                ("workspace_bytes", c_ll)]
+
+
 class OpStatisticsInfoC(C.Structure):   # lavie_op_statistics_info
     _fields_ = [("struct_size", c_int), ("M", c_int), ("N", c_int), ("splits", c_int), ("colstat_written", c_int), ("colstat_rows", c_int),
                 ("colstat_span", c_int), ("nsets", c_int), ("set_blocks", c_int), ("colstat_contiguous", c_int),
@@ -106,6 +113,8 @@ SIGNATURES = {
     "lavie_freeu_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
     "lavie_freeu_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
+    "lavie_freq_mix_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
+    "lavie_freq_mix_f32": (c_int, [C.POINTER(FreqMixArgsC), c_void_p]),
     "lavie_geglu_mlp_image_bytes": (c_ll, [c_int]),
     "lavie_geglu_mlp_bias_floats": (c_ll, [c_int]),
     "lavie_pack_geglu_mlp_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float_p, c_void_p]),

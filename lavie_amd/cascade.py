@@ -11,6 +11,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from .free_init import coerce
 from .vsr.pipeline import upscale_in_chunks
 
 
@@ -48,7 +49,8 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
                           vsr_guidance_rescale: float = 0.0, base_freeu: Optional[dict] = None, vsr_freeu: Optional[dict] = None,
                           base_pag_scale: float = 0.0, base_pag_adaptive_scale: float = 0.0,
                           base_pag_applied_layers=("mid_block",), base_cache_interval: Optional[int] = None,
-                          vsr_cache_interval: Optional[int] = None, base_cache_depth: int = 1, vsr_cache_depth: int = 1):
+                          vsr_cache_interval: Optional[int] = None, base_cache_depth: int = 1, vsr_cache_depth: int = 1,
+                          base_free_init=None):
     """Returns (base_latents, interp_latents, vsr_latents, frames or None).  Text embeddings are passed per stage (the base
     and interpolation stages use SD-1.4's CLIP, 768 wide; the VSR stage the x4-upscaler's, 1024 wide).
     `base_scheduler` / `vsr_scheduler` replace the two diffusers-style stages' schedulers for this call (for instance a
@@ -65,7 +67,10 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
     `base_cache_interval` / `vsr_cache_interval` (with `base_cache_depth` / `vsr_cache_depth`): the layer cache of the two
     diffusers-style stages, the `cache_interval` / `cache_depth` of their pipelines: the whole UNet on every N-th step only; every VSR
     chunk starts with a full step.  None or 1 = the calls without it.  Not with `vsr_overlap` > 0 (frame windows).  The interpolation
-    stage's loop has no such switch."""
+    stage's loop has no such switch.
+    `base_free_init`: a FreeInit (lavie_amd.free_init) or a mapping of its keywords for the base stage's call (the `free_init` keyword
+    of `VideoGenPipeline.__call__`); None = the base pipeline's own setting.  The VSR pipeline and the interpolation sampler have no
+    FreeInit."""
     freeu_was = [(pipe.unet, pipe.unet.freeu) for pipe, fu in ((base_pipe, base_freeu), (vsr_pipe, vsr_freeu)) if fu is not None]
     swapped = [(pipe, pipe.scheduler) for pipe, sch in ((base_pipe, base_scheduler), (vsr_pipe, vsr_scheduler)) if sch is not None]
     if base_scheduler is not None:
@@ -83,7 +88,8 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
                         dict(pag_scale=base_pag_scale, pag_adaptive_scale=base_pag_adaptive_scale,
                              pag_applied_layers=base_pag_applied_layers) if base_pag_scale else {},
                         dict(cache_interval=base_cache_interval, cache_depth=base_cache_depth) if base_cache_interval not in (None, 1) else {},
-                        dict(cache_interval=vsr_cache_interval, cache_depth=vsr_cache_depth) if vsr_cache_interval not in (None, 1) else {})
+                        dict(cache_interval=vsr_cache_interval, cache_depth=vsr_cache_depth) if vsr_cache_interval not in (None, 1) else {},
+                        base_free_init)
     finally:
         for pipe, own in swapped:
             pipe.scheduler = own
@@ -95,11 +101,13 @@ def _cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, vae, vsr_vae, p
              vsr_prompt_embeds, vsr_negative_prompt_embeds, interp_prompt_embeds, interp_negative_prompt_embeds, height, width,
              base_steps, guidance_scale, interp_frames, interp_cfg_scale, vsr_steps, vsr_guidance_scale, noise_level, generator,
              decode_final, vsr_overlap=0, base_guidance_rescale=0.0, vsr_guidance_rescale=0.0, base_pag=None, base_cache=None,
-             vsr_cache=None):
+             vsr_cache=None, base_free_init=None):
     dev = base_pipe.device
     base_kw = dict(guidance_rescale=base_guidance_rescale) if base_guidance_rescale else {}       # absent = the calls without it
     base_kw.update(base_pag or {})
     base_kw.update(base_cache or {})
+    if base_free_init is not None:
+        base_kw["free_init"] = base_free_init
     vsr_kw = dict(guidance_rescale=vsr_guidance_rescale) if vsr_guidance_rescale else {}
     vsr_kw.update(vsr_cache or {})
     # 1. base T2V (base/pipelines/sample.py:78-91)
@@ -132,7 +140,8 @@ def continue_clip(pipe, prev_latents: torch.Tensor, overlap: int = 4, **call_kwa
     frames of `prev_latents` (VideoGenPipeline's `known_latents` / `known_mask`), so they come back bit-equal and temporal attention
     carries them into the free frames.  `call_kwargs` go to the pipeline (prompt or prompt_embeds, steps, generator, ...);
     `video_length` defaults to 16, height / width to those of `prev_latents`; `cache_interval` / `cache_depth` (the layer cache) go
-    through like the rest.  Returns the new clip's latents, overlap included."""
+    through like the rest.  FreeInit (`free_init` in `call_kwargs`, or enabled on the pipeline) is refused: the clip's start is pinned,
+    not noise.  Returns the new clip's latents, overlap included."""
     p, c, f_prev, h, w = prev_latents.shape
     length = int(call_kwargs.pop("video_length", 16))
     if not 1 <= overlap < length or overlap > f_prev:
@@ -158,7 +167,10 @@ def text_to_long_video(pipe, prompt, num_clips: int, overlap: int = 4, method: s
     (VideoGenPipeline's `window_length` / `window_stride`): every forward keeps the trained length, the overlap frames are
     shared in both directions.
     `cache_interval` / `cache_depth` in `call_kwargs` (the layer cache) reach every clip's call with method "chain"; "windows" refuses
-    them, as the pipeline does."""
+    them, as the pipeline does.
+    `free_init` in `call_kwargs` (or FreeInit enabled on the pipeline) goes to the calls that start from noise: the one run of
+    "windows", whose filter spans the whole length, and a "chain" of one clip.  A longer chain pins every later clip's overlap and is
+    refused before anything is sampled."""
     if num_clips < 1:
         raise ValueError(f"num_clips={num_clips} must be >= 1")
     if method not in ("chain", "windows"):
@@ -172,6 +184,10 @@ def text_to_long_video(pipe, prompt, num_clips: int, overlap: int = 4, method: s
             raise ValueError(f"overlap={overlap} must lie in 0..{length - 1} (window of {length} frames)")
         total = length + (num_clips - 1) * (length - overlap)
         return pipe(video_length=total, window_length=length, window_stride=length - overlap, **call_kwargs).video
+    setting = call_kwargs.get("free_init")
+    if num_clips > 1 and coerce(setting if setting is not None else getattr(pipe, "free_init", None)) is not None:
+        raise ValueError("FreeInit cannot be combined with method 'chain' over several clips: every clip after the first starts from "
+                         "a pinned overlap, not from noise (use method 'windows')")
     clip = pipe(video_length=length, **call_kwargs).video
     parts = [clip]
     for _ in range(num_clips - 1):

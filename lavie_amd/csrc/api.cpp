@@ -136,6 +136,57 @@ int lavie_freeu_f16(const void* h, int C_h, const void* skip, int C2, int NI, in
     return launch_freeu(H(h), C_h, H(skip), C2, NI, Hh, W, b, s, H(h_out), H(skip_out), (float*)workspace, S(stream));
 }
 
+// FreeInit's frequency mix (freq_mix.hip): everything is checked here before anything is launched; each refusal names its argument.
+long long lavie_freq_mix_workspace_bytes(int images, int F, int Hh, int W) {
+    return (long long)(freq_mix_workspace_floats(images, F, Hh, W) * sizeof(float));
+}
+int lavie_freq_mix_f32(const lavie_freq_mix_args* a, void* stream) {
+    const char* who = "freq_mix";
+    LAVIE_CHECK(a, "%s: args is null", who);
+    LAVIE_CHECK(a->struct_size == (int)sizeof(lavie_freq_mix_args),
+                "%s: args->struct_size=%d but this library's lavie_freq_mix_args has %d bytes: the binding's struct layout is "
+                "out of date", who, a->struct_size, (int)sizeof(lavie_freq_mix_args));
+    LAVIE_CHECK(a->images >= 1 && a->images <= kFreqMixMaxImages, "%s: images=%d outside 1..%d", who, a->images, kFreqMixMaxImages);
+    LAVIE_CHECK(a->F >= 1 && a->F <= LAVIE_FREQ_MIX_MAX_F, "%s: F=%d outside 1..%d", who, a->F, LAVIE_FREQ_MIX_MAX_F);
+    LAVIE_CHECK(a->H >= 1 && a->H <= LAVIE_FREQ_MIX_MAX_HW, "%s: H=%d outside 1..%d", who, a->H, LAVIE_FREQ_MIX_MAX_HW);
+    LAVIE_CHECK(a->W >= 1 && a->W <= LAVIE_FREQ_MIX_MAX_HW, "%s: W=%d outside 1..%d", who, a->W, LAVIE_FREQ_MIX_MAX_HW);
+    LAVIE_CHECK(a->x0, "%s: x0 is null", who);
+    LAVIE_CHECK(a->e0, "%s: e0 is null", who);
+    LAVIE_CHECK(a->z, "%s: z is null", who);
+    LAVIE_CHECK(a->filter, "%s: filter is null", who);
+    LAVIE_CHECK(a->out, "%s: out is null", who);
+    LAVIE_CHECK(a->workspace, "%s: workspace is null", who);
+    const long long total = (long long)a->images * a->F * a->H * a->W;
+    const long long need = lavie_freq_mix_workspace_bytes(a->images, a->F, a->H, a->W);
+    LAVIE_CHECK(a->workspace_bytes >= need, "%s: workspace_bytes=%lld, %lld needed", who, a->workspace_bytes, need);
+    LAVIE_CHECK(((uintptr_t)a->workspace & 7) == 0, "%s: workspace at %p is not 8-byte aligned", who, a->workspace);
+    LAVIE_CHECK(__builtin_isfinite(a->a) && __builtin_isfinite(a->s) && __builtin_isfinite(a->r), "%s: a=%g s=%g r=%g must be finite", who,
+                (double)a->a, (double)a->s, (double)a->r);
+    if (a->model_in) {
+        LAVIE_CHECK(a->dup >= 1 && a->dup <= 3, "%s: dup=%d outside 1..3", who, a->dup);
+        LAVIE_CHECK(a->dup_stride >= total && a->dup_stride <= (1ll << 40), "%s: dup_stride=%lld must be >= images F H W = %lld", who,
+                    a->dup_stride, total);
+        LAVIE_CHECK(__builtin_isfinite(a->input_scale), "%s: input_scale (%g) is not finite", who, (double)a->input_scale);
+    }
+    // out is written while z is still being read, and after e0 / filter / the workspace have been: it may be x0 and nothing else
+    const uintptr_t ob = (uintptr_t)a->out, oe = ob + (uintptr_t)total * 4;
+    auto overlaps = [&](const void* p, long long bytes) { return (uintptr_t)p < oe && ob < (uintptr_t)p + (uintptr_t)bytes; };
+    LAVIE_CHECK(!overlaps(a->e0, total * 4), "%s: out and e0 overlap (aliasing)", who);
+    LAVIE_CHECK(!overlaps(a->z, total * 4), "%s: out and z overlap (aliasing)", who);
+    LAVIE_CHECK(!overlaps(a->filter, total / a->images * 4), "%s: out and filter overlap (aliasing)", who);
+    LAVIE_CHECK(!overlaps(a->workspace, need), "%s: out and workspace overlap (aliasing)", who);
+    LAVIE_CHECK(a->out == a->x0 || !overlaps(a->x0, total * 4), "%s: out and x0 overlap without being equal (aliasing)", who);
+    FreqMixParams p{};
+    p.x0 = a->x0; p.e0 = a->e0; p.z = a->z; p.filter = a->filter;
+    p.a = a->a; p.s = a->s; p.r = a->r;
+    p.out = a->out;
+    p.model_in = (half_t*)a->model_in;
+    p.dup = a->dup; p.dup_stride = a->dup_stride; p.in_scale = a->input_scale;
+    p.workspace = (float*)a->workspace;
+    p.images = a->images; p.F = a->F; p.H = a->H; p.W = a->W;
+    return launch_freq_mix(p, S(stream));
+}
+
 long long lavie_geglu_mlp_image_bytes(int C) { return geglu_mlp_supported(C) ? (long long)geglu_mlp_image_bytes(C) : 0; }
 long long lavie_geglu_mlp_bias_floats(int C) { return geglu_mlp_supported(C) ? (long long)geglu_mlp_bias_floats(C) : 0; }
 int lavie_pack_geglu_mlp_f16(const void* w1, const void* b1_f16, const void* w2, int C, void* img, float* b1img, void* stream) {

@@ -278,6 +278,28 @@ size_t freeu_workspace_floats(int C2, int NI, int H, int W);
 int launch_freeu(const half_t* h, int C_h, const half_t* skip, int C2, int NI, int H, int W, float b, float s, half_t* h_out,
                  half_t* skip_out, float* workspace, hipStream_t stream);
 
+// ---- freq_mix.hip: FreeInit's frequency mix on `images` fp32 volumes [F, H, W]:
+//   out = r z + Re IFFT3(filter .* FFT3(a x0 + s e0 - r z)), filter real [F, H, W] in FFT-native order and even in frequency (the host
+//   takes the even part), shared by all images; model_in (may be nullptr) receives fp16(out in_scale), rounded once, in `dup` copies
+//   `dup_stride` elements apart.  A separable direct fp32 DFT in six launches, twiddles from fp64 host tables; out may alias x0.
+//   workspace: freq_mix_workspace_floats() floats, 8-byte aligned.  Fixed summation order, no atomics: bit-reproducible, and an image
+//   has the bits of its single-image call.
+constexpr int kFreqMixMaxF = 256, kFreqMixMaxHW = 128, kFreqMixMaxImages = 65535;
+struct FreqMixParams {
+    const float *x0, *e0, *z, *filter;
+    float a, s, r;
+    float* out;
+    half_t* model_in;
+    int dup;
+    int64_t dup_stride;
+    float in_scale;
+    float* workspace;
+    int images, F, H, W;
+};
+bool freq_mix_supported(int images, int F, int H, int W);
+size_t freq_mix_workspace_floats(int images, int F, int H, int W);      // 0 for an unsupported shape
+int launch_freq_mix(const FreqMixParams& p, hipStream_t stream);
+
 // host-only helper (no GPU): T5-style bucket of (query i, key j), attention.py:681-699
 void relpos_bucket_table(int F, int num_buckets, int max_distance, int* out);
 

@@ -1099,3 +1099,48 @@ def freeu(h: torch.Tensor, skip: torch.Tensor, ni: int, height: int, width: int,
     _lib.check(lib.lavie_freeu_f16(_p(h), c_h, _p(skip), c2, ni, height, width, float(b), float(s), _p(h_out), _p(skip_out), _p(ws),
                                    _stream()), "lavie_freeu_f16")
     return h_out, skip_out
+
+
+def freq_mix_workspace_bytes(images: int, f: int, h: int, w: int) -> int:
+    """Bytes of workspace `freq_mix` needs for `images` volumes [f, h, w]; 0 for a shape it refuses."""
+    return int(_lib.load().lavie_freq_mix_workspace_bytes(int(images), int(f), int(h), int(w)))
+
+
+def freq_mix(x0, e0, z, filt, a: float, s: float, r: float, out=None, model_in=None, input_scale: float = 1.0, workspace=None):
+    """FreeInit's frequency mix (lavie_freq_mix_f32, csrc/freq_mix.hip): out = r z + Re IFFT3(filt .* FFT3(a x0 + s e0 - r z)) over the
+    last three axes of fp32 [..., F, H, W] tensors x0 / e0 / z; `filt` fp32 [F, H, W] in FFT-native order, even in frequency
+    (lavie_amd.free_init.freq_filter), shared by every leading index.  out: None (a new tensor), or an fp32 tensor of x0's shape,
+    which may be x0 itself.  model_in: None, or an fp16 tensor holding 1 to 3 copies of x0's shape along its first axis
+    ([dup * P, C, F, H, W] for latents [P, C, F, H, W]); every copy receives fp16(out input_scale), rounded once.  workspace: None, or a
+    device tensor of at least freq_mix_workspace_bytes() bytes.  Returns out."""
+    _chk32(x0, e0, z, filt, out)
+    _chk16(model_in)
+    if x0.dim() < 3:
+        raise ValueError(f"freq_mix: the operands must be [..., F, H, W], got {tuple(x0.shape)}")
+    f, h, w = x0.shape[-3:]
+    images = math.prod(x0.shape[:-3])
+    for name, t in (("e0", e0), ("z", z)):
+        if tuple(t.shape) != tuple(x0.shape) or t.device != x0.device:
+            raise ValueError(f"freq_mix: {name} must have x0's shape {tuple(x0.shape)} on {x0.device}")
+    if tuple(filt.shape) != (f, h, w) or filt.device != x0.device:
+        raise ValueError(f"freq_mix: the filter must be an fp32 tensor {(f, h, w)} on {x0.device}, got {tuple(filt.shape)}")
+    out = _out(out, x0.shape, torch.float32, x0.device, "freq_mix: out")
+    args = _lib.FreqMixArgsC()
+    args.struct_size = ctypes.sizeof(_lib.FreqMixArgsC)
+    args.images, args.F, args.H, args.W = images, f, h, w
+    args.x0, args.e0, args.z, args.filter, args.out = x0.data_ptr(), e0.data_ptr(), z.data_ptr(), filt.data_ptr(), out.data_ptr()
+    args.a, args.s, args.r = float(a), float(s), float(r)
+    if model_in is not None:
+        dup, rest = divmod(model_in.numel(), x0.numel())
+        if model_in.device != x0.device or rest or not 1 <= dup <= 3:
+            raise ValueError(f"freq_mix: model_in must hold 1 to 3 copies of {tuple(x0.shape)} on {x0.device}, got {tuple(model_in.shape)}")
+        args.model_in, args.dup, args.dup_stride, args.input_scale = model_in.data_ptr(), dup, x0.numel(), float(input_scale)
+    lib = _lib.load()
+    need = int(lib.lavie_freq_mix_workspace_bytes(images, f, h, w))
+    if workspace is None:
+        workspace = torch.empty(max(need // 4, 4), dtype=torch.float32, device=x0.device)
+    elif not (workspace.is_cuda and workspace.device == x0.device and workspace.is_contiguous()):
+        raise ValueError(f"freq_mix: workspace must be a contiguous tensor on {x0.device}")
+    args.workspace, args.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    _lib.check(lib.lavie_freq_mix_f32(ctypes.byref(args), _stream()), "lavie_freq_mix_f32")
+    return out

@@ -17,6 +17,7 @@ from typing import Callable, List, Optional, Union
 
 import torch
 
+from . import free_init as free_init_mod
 from . import ops, sampling
 from .scheduling_ddpm import DDPMScheduler, randn_tensor
 
@@ -40,6 +41,7 @@ class VideoGenPipeline:
         self.unet = unet
         self.scheduler = scheduler or DDPMScheduler()
         self.vae_scale_factor = 8                        # 2 ** (len(vae.config.block_out_channels) - 1) for SD-1.x
+        self.free_init = None                            # enable_free_init / disable_free_init
 
     def to(self, device):
         self.unet.to(device)
@@ -82,6 +84,17 @@ class VideoGenPipeline:
 
     def disable_freeu(self):
         self.unet.disable_freeu()
+
+    def enable_free_init(self, num_iters: int = 3, use_fast_sampling: bool = False, method: str = "butterworth", order: int = 4,
+                         spatial_stop_frequency: float = 0.25, temporal_stop_frequency: float = 0.25):
+        """diffusers' enable_free_init (FreeInitMixin), same names and defaults: every later `__call__` / `denoise` samples
+        `num_iters` times and refines the initial noise in between (lavie_amd.free_init; `denoise`).  The setting lives on the
+        pipeline; a `free_init=` keyword of a call overrides it for that call."""
+        self.free_init = free_init_mod.FreeInit(num_iters, use_fast_sampling, method, order, spatial_stop_frequency,
+                                                temporal_stop_frequency)
+
+    def disable_free_init(self):
+        self.free_init = None
 
     def load_mapper(self, path_or_sd, num_heads: int = 12):
         """The fork's saved image mapper (`mapper.pt`, fine_tuning.py:701) -> self.mapper on the pipeline's device, eval mode.
@@ -134,6 +147,8 @@ class VideoGenPipeline:
         an optional `freeu: {s1:, s2:, b1:, b2:}` (not a key of the reference either) is set on the UNet (enable_freeu),
         optional `pag_scale` / `pag_adaptive_scale` / `pag_applied_layers` (a name or a list of names) become the keywords of those names,
         optional `cache_interval` / `cache_depth` (the layer cache; not keys of the reference) become the keywords of those names,
+        an optional `free_init: {num_iters:, use_fast_sampling:, method:, order:, spatial_stop_frequency:, temporal_stop_frequency:}`
+        (not a key of the reference) is set on the pipeline (enable_free_init),
         `seed` is returned in cfg for torch.manual_seed (sample.py:22-23).  `use_fp16` and
         `enable_xformers_memory_efficient_attention` are read by nobody in sample.py and are ignored here as well.
         PyYAML's safe loader replaces omegaconf (absent from the image); interpolation / `${...}` references are not resolved."""
@@ -176,6 +191,8 @@ class VideoGenPipeline:
         if "freeu" in cfg:                      # {s1:, s2:, b1:, b2:}, all four: the setting goes onto the model
             fu = cfg["freeu"]
             pipe.enable_freeu(fu["s1"], fu["s2"], fu["b1"], fu["b2"])
+        if "free_init" in cfg:                  # any of FreeInit's keywords; the rest keep diffusers' defaults: set on the pipeline
+            pipe.enable_free_init(**dict(cfg["free_init"] or {}))
         return pipe, call_kwargs, cfg
 
     @property
@@ -285,7 +302,8 @@ class VideoGenPipeline:
                 known_noise: Optional[torch.Tensor] = None, start_step: int = 0, window_length: Optional[int] = None,
                 window_stride: Optional[int] = None, window_weights: str = "triangle",
                 guidance_rescale: float = 0.0, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                pag_applied_layers=("mid_block",), cache_interval: Optional[int] = None, cache_depth: int = 1) -> torch.Tensor:
+                pag_applied_layers=("mid_block",), cache_interval: Optional[int] = None, cache_depth: int = 1,
+                free_init=None) -> torch.Tensor:
         """latents fp32 [P, C, F, h, w] on the device, ctx fp16 [2P, n, d] = [negative | prompt] (guidance_scale > 1) or
         [P, n, d] = prompt only (guidance_scale <= 1: no classifier-free guidance, :626) -> denoised fp32.  One loop, one step
         launch per denoising step; step plan, step noise, engine session and step dispatch are lavie_amd.sampling's.
@@ -326,7 +344,21 @@ class VideoGenPipeline:
         0, N, 2N, ... (the first step a run takes always refreshes, also when `start_step` > 0) and the steps between run only the
         first `cache_depth` layers of the first down block and the last `cache_depth` + 1 of the last up block on the activation the
         latest full step left.  An approximation whose quality at a given N is the caller's trade-off.  The UNet's own setting
-        comes back after the loop.  Not combined with frame windows.  None or 1 is the call without it."""
+        comes back after the loop.  Not combined with frame windows.  None or 1 is the call without it.
+
+        FreeInit (Wu et al.; diffusers' enable_free_init; lavie_amd.free_init): with `free_init` (a FreeInit or a mapping of its
+        keywords) of num_iters = N > 1 the loop runs N times inside ONE engine session, on the same buffers.  Between two
+        iterations one call of ops.freq_mix re-noises the result to the last training timestep with the noise the call started
+        from (`latents` = init_noise_sigma e0), keeps its low spatio-temporal frequencies, takes the high ones from fresh noise
+        drawn from `generator`, and writes the next iteration's fp32 latents and fp16 model input itself (with frame windows the
+        filter spans the whole clip and every window's input is then cut from the mixed clip as at the start of a run).  Every
+        iteration starts at position 0 of its own timestep table (`use_fast_sampling`: FreeInit.steps_at steps), so a multistep
+        history and the layer cache restart with it, and `callback`'s step index restarts as well.  Not combined with known
+        latents: the run's start is not noise there.  None or num_iters = 1 is the call without it, launch for launch."""
+        free = free_init_mod.coerce(free_init if free_init is not None else getattr(self, "free_init", None))
+        if free is not None and (known is not None or mask is not None or known_noise is not None or start_step != 0):
+            raise ValueError("FreeInit (`free_init`) cannot be combined with known latents (`known` / `mask` / `known_noise` / "
+                             "`start_step`): the run's start is not noise there")
         cache_interval = sampling.check_layer_cache(cache_interval, cache_depth,
                                                     window_length is not None and latents.shape[2] > int(window_length))
         pag = self.check_pag(pag_scale, pag_adaptive_scale, latents.shape[0], guidance_scale, guidance_rescale,
@@ -342,7 +374,7 @@ class VideoGenPipeline:
         if known is None and (mask is not None or known_noise is not None or start_step != 0):
             raise ValueError("`mask`, `known_noise` and `start_step` need `known` latents")
         dev = latents.device
-        plan = sampling.StepPlan(self.scheduler, num_inference_steps, eta)
+        plan = sampling.StepPlan(self.scheduler, free.steps_at(0, num_inference_steps) if free else num_inference_steps, eta)
         if known is not None and not 0 <= start_step < len(plan.timesteps):
             raise ValueError(f"`start_step`={start_step} must lie in 0..{len(plan.timesteps) - 1}")
         x = latents.to(torch.float32).contiguous().clone()
@@ -370,6 +402,10 @@ class VideoGenPipeline:
             if mask is not None:
                 mask = mask.to(device=dev, dtype=torch.float32).expand(p, 1, *x.shape[2:]).contiguous()
         noise = sampling.StepNoise(x, generator)
+        refine = None
+        if free is not None:                                # the state of the iterations, beside the noise buffers
+            refine = free_init_mod.FreeInitRun(free, self.scheduler, x, generator,
+                                               lambda it: sampling.StepPlan(self.scheduler, free.steps_at(it, num_inference_steps), eta))
         if known is not None:
             if known_noise is None:
                 known_noise = randn_tensor(tuple(x.shape), generator=generator, device=dev, dtype=torch.float32)
@@ -400,38 +436,52 @@ class VideoGenPipeline:
             with sampling.layer_cache_session(self.unet, cache_interval, cache_depth):
                 x = self._denoise_loop(x, ctx, nb, frames, starts, model_in, guidance, plan, noise, x0_prev, t_dev, start_step, windowed,
                                        profile if windowed else None, known, mask, known_noise, region, callback, callback_steps,
-                                       pag_scale, pag_adaptive_scale, cache_interval)
+                                       pag_scale, pag_adaptive_scale, cache_interval, refine)
         finally:
             if pag_was is not None:
                 self.unet.set_pag(*pag_was)
         return x
 
     def _denoise_loop(self, x, ctx, nb, frames, starts, model_in, guidance, plan, noise, x0_prev, t_dev, start_step, windowed, profile,
-                      known, mask, known_noise, region, callback, callback_steps, pag_scale, pag_adaptive_scale, cache_interval=1):
-        """The engine session and the steps of `denoise`, on the buffers it has set up."""
+                      known, mask, known_noise, region, callback, callback_steps, pag_scale, pag_adaptive_scale, cache_interval=1,
+                      refine=None):
+        """The engine session and the steps of `denoise`, on the buffers it has set up.  `refine`: None, or the FreeInitRun of a
+        call that samples several times; every iteration after the first runs the steps of its own plan on the mixed latents."""
         pag = isinstance(guidance, sampling.PagGuidance)
+        iterations = refine.setting.num_iters if refine is not None else 1
         with sampling.engine_session(self.unet, nb, frames, x.shape[3], x.shape[4], ctx,
                                      model_in if guidance is not None and self.cfg_shared_prefix and not pag else None) as ctx:
             def forward(w, i):                 # (the keyword only where the cache is on: any UNet-shaped callable serves without)
                 mode = sampling.layer_cache_mode(i - start_step, cache_interval)
                 return self.unet(model_in[w], t_dev[i], encoder_hidden_states=ctx, **({"layer_cache": mode} if mode else {})).sample
             forwards = sampling.WindowForwards(forward)
-            for i in range(start_step, len(plan.timesteps)):
-                eps = forwards(len(model_in), i)                                                      # line 670
-                if pag:
-                    guidance.pag_scale = sampling.pag_scale_at(pag_scale, pag_adaptive_scale, plan.timesteps[i])
-                coeffs = plan.coeffs(i, first=start_step > 0 and i == start_step)
-                aux = x0_prev if plan.multistep else noise.draw() if plan.adds_noise(coeffs) else None
-                if windowed:
-                    sampling.window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, plan.input_scale(i + 1),
-                                         plan.multistep)
-                else:
-                    if mask is not None:                   # without a mask nothing is pinned: the plain step kernels
-                        region = (known, mask, known_noise, plan.noise_level(i + 1))
-                    sampling.step(eps[0], x, aux, model_in[0], guidance, coeffs, plan.input_scale(i + 1), plan.multistep, region)
-                noise.done()
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, plan.timesteps[i], x)
+            for iteration in range(iterations):
+                if iteration > 0:
+                    # the next iteration's plan first: its first input scale goes into the mix, which leaves x and, without
+                    # windows, every part of the model input as a step would (windows: cut from the mixed clip as at a run's start)
+                    plan = refine.plan_at(iteration)
+                    t_dev = plan.t_dev(x.device)
+                    refine.remix(x, None if windowed else model_in[0], plan.input_scale(0))
+                    if windowed:
+                        for s, m in zip(starts, model_in):
+                            (ops.latents_to_model_input if guidance is not None else ops.latents_to_model_input1)(
+                                x[:, :, s:s + frames].contiguous(), m, plan.input_scale(0))
+                for i in range(start_step, len(plan.timesteps)):
+                    eps = forwards(len(model_in), i)                                                      # line 670
+                    if pag:
+                        guidance.pag_scale = sampling.pag_scale_at(pag_scale, pag_adaptive_scale, plan.timesteps[i])
+                    coeffs = plan.coeffs(i, first=start_step > 0 and i == start_step)
+                    aux = x0_prev if plan.multistep else noise.draw() if plan.adds_noise(coeffs) else None
+                    if windowed:
+                        sampling.window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, plan.input_scale(i + 1),
+                                             plan.multistep)
+                    else:
+                        if mask is not None:                   # without a mask nothing is pinned: the plain step kernels
+                            region = (known, mask, known_noise, plan.noise_level(i + 1))
+                        sampling.step(eps[0], x, aux, model_in[0], guidance, coeffs, plan.input_scale(i + 1), plan.multistep, region)
+                    noise.done()
+                    if callback is not None and i % callback_steps == 0:
+                        callback(i, plan.timesteps[i], x)
         return x
 
     @staticmethod
@@ -525,13 +575,19 @@ class VideoGenPipeline:
                  video: Optional[torch.Tensor] = None, strength: float = 1.0, window_length: Optional[int] = None,
                  window_stride: Optional[int] = None, window_weights: str = "triangle", guidance_rescale: float = 0.0,
                  pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0, pag_applied_layers=("mid_block",),
-                 cache_interval: Optional[int] = None, cache_depth: int = 1):
-        """`guidance_scale`: one number, or a sequence with one value > 1 per prompt (repeated per `num_images_per_prompt`; a
+                 cache_interval: Optional[int] = None, cache_depth: int = 1, free_init=None):
+        """`free_init`: a FreeInit (or a mapping of its keywords) for this call instead of the pipeline's own setting
+        (enable_free_init); not with `known_latents` / `known_mask` / `video` / `strength` < 1.
+        `guidance_scale`: one number, or a sequence with one value > 1 per prompt (repeated per `num_images_per_prompt`; a
         sequence always means guidance is on).  `guidance_rescale` in [0, 1]: diffusers' rescale_noise_cfg inside the fused step;
         ignored with a scalar `guidance_scale` <= 1, as in diffusers.  `pag_scale` > 0: perturbed-attention guidance in the
         transformers `pag_applied_layers` names, fading by `pag_adaptive_scale` per timestep below 1000.  `cache_interval` = N > 1: the layer cache, the whole UNet on every
         N-th step only, at `cache_depth`; not with `window_length`.  See `denoise`."""
         sampling.check_layer_cache(cache_interval, cache_depth, window_length is not None and video_length > int(window_length))
+        free = free_init_mod.coerce(free_init if free_init is not None else getattr(self, "free_init", None))
+        if free is not None and (known_latents is not None or known_mask is not None or video is not None or strength != 1.0):
+            raise ValueError("FreeInit (`free_init` / enable_free_init) cannot be combined with `known_latents` / `known_mask` / `video` "
+                             "/ `strength`: the run's start is not noise there")
         if window_length is not None and (known_latents is not None or known_mask is not None or video is not None or strength != 1.0):
             raise ValueError("frame windows (`window_length`) cannot be combined with `known_latents` / `known_mask` / `video` / "
                              "`strength`")
@@ -573,6 +629,8 @@ class VideoGenPipeline:
             rescale.update(pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale, pag_applied_layers=pag_applied_layers)
         if cache_interval not in (None, 1):
             rescale.update(cache_interval=cache_interval, cache_depth=cache_depth)
+        if free_init is not None:              # (the pipeline's own setting is read by `denoise` itself)
+            rescale.update(free_init=free_init)
         lora_scale = (cross_attention_kwargs or {}).get("scale")
         if lora_scale is None:
             latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta,
