@@ -12,13 +12,14 @@ Image conditioning (the fork's inference.py:248-353): with a `mapper` (lavie_amd
 widens each CFG half's context to `cat([text, mapper(image, text)], 1)`: 154 tokens for a 77-token prompt.  The image comes
 as `image_tensor` (through `clip_processor` + `clip_model.vision_model`, stock PyTorch) or as precomputed vision features
 `image_embeds`.  Without a mapper `image_tensor` is accepted and ignored, as before."""
+import contextlib
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Union
 
 import torch
 
 from . import free_init as free_init_mod
-from . import ops, sampling
+from . import ops, sampling          # noqa: F401  (`ops`: the device ops, as callers of this module reach them)
 from .scheduling_ddpm import DDPMScheduler, randn_tensor
 
 
@@ -31,6 +32,14 @@ class VideoGenPipeline:
     # With guidance the UNet input is the latents twice (line 666): let the engine compute the layers in front of the first text
     # cross-attention once per step (UNet3DConditionModel.set_cfg_shared_input).  False = both halves computed, as the reference does.
     cfg_shared_prefix = True
+
+    # how `denoise` and `__call__` speak to sampling.check_features: the order in which each has always judged its features, and
+    # its own words for FreeInit and for the known-latents arguments
+    DENOISE = sampling.Surface(("free_init", "cache", "pag", "window_length"), "FreeInit (`free_init`)",
+                               "known latents (`known` / `mask` / `known_noise` / `start_step`)")
+    CALL = sampling.Surface(("cache", "free_init", "window_length"), "FreeInit (`free_init` / enable_free_init)",
+                            "`known_latents` / `known_mask` / `video` / `strength`")
+    CALL_PAG = sampling.Surface(("pag",))
 
     def __init__(self, vae=None, text_encoder=None, tokenizer=None, unet=None, scheduler=None, clip_model=None,
                  clip_processor=None, mapper=None):
@@ -306,7 +315,8 @@ class VideoGenPipeline:
                 free_init=None) -> torch.Tensor:
         """latents fp32 [P, C, F, h, w] on the device, ctx fp16 [2P, n, d] = [negative | prompt] (guidance_scale > 1) or
         [P, n, d] = prompt only (guidance_scale <= 1: no classifier-free guidance, :626) -> denoised fp32.  One loop, one step
-        launch per denoising step; step plan, step noise, engine session and step dispatch are lavie_amd.sampling's.
+        launch per denoising step: the loop and its buffers are lavie_amd.sampling's (`Run`), which features combine is
+        `sampling.check_features`'s; what is this pipeline's own are the context, the PAG setting and the order of the sessions.
 
         `guidance_scale` may be a sequence with one value > 1 per latent; `guidance_rescale` = phi in (0, 1] rescales every
         latent's guided prediction to phi std(prompt prediction) / std(guided prediction) + (1 - phi) (diffusers'
@@ -355,160 +365,57 @@ class VideoGenPipeline:
         iteration starts at position 0 of its own timestep table (`use_fast_sampling`: FreeInit.steps_at steps), so a multistep
         history and the layer cache restart with it, and `callback`'s step index restarts as well.  Not combined with known
         latents: the run's start is not noise there.  None or num_iters = 1 is the call without it, launch for launch."""
-        free = free_init_mod.coerce(free_init if free_init is not None else getattr(self, "free_init", None))
-        if free is not None and (known is not None or mask is not None or known_noise is not None or start_step != 0):
-            raise ValueError("FreeInit (`free_init`) cannot be combined with known latents (`known` / `mask` / `known_noise` / "
-                             "`start_step`): the run's start is not noise there")
-        cache_interval = sampling.check_layer_cache(cache_interval, cache_depth,
-                                                    window_length is not None and latents.shape[2] > int(window_length))
-        pag = self.check_pag(pag_scale, pag_adaptive_scale, latents.shape[0], guidance_scale, guidance_rescale,
-                             known=known, mask=mask, known_noise=known_noise, window_length=window_length)
-        windowed = False
-        if window_length is not None:
-            if known is not None or mask is not None or known_noise is not None or start_step != 0:
-                raise ValueError("frame windows (`window_length`) cannot be combined with known latents (`known` / `mask` / "
-                                 "`known_noise` / `start_step`)")
-            if int(window_length) < 1:
-                raise ValueError(f"`window_length`={window_length} must be >= 1")
-            windowed = latents.shape[2] > int(window_length)
+        free, cache_interval, pag = sampling.check_features(
+            self.DENOISE, latents.shape[2], latents.shape[0], known=dict(known=known, mask=mask, known_noise=known_noise),
+            late_start=start_step != 0, window_length=window_length, guidance=(guidance_scale, guidance_rescale),
+            pag=(pag_scale, pag_adaptive_scale), cache=(cache_interval, cache_depth),
+            free_init=free_init if free_init is not None else self.free_init)
+        geometry = sampling.window_geometry(latents.shape[2], window_length, window_stride, window_weights)
         if known is None and (mask is not None or known_noise is not None or start_step != 0):
             raise ValueError("`mask`, `known_noise` and `start_step` need `known` latents")
-        dev = latents.device
-        plan = sampling.StepPlan(self.scheduler, free.steps_at(0, num_inference_steps) if free else num_inference_steps, eta)
+
+        def plan_at(iteration):                            # every FreeInit iteration has a plan of its own (`use_fast_sampling`)
+            return sampling.StepPlan(self.scheduler, free.steps_at(iteration, num_inference_steps) if free else num_inference_steps, eta)
+        plan = plan_at(0)
         if known is not None and not 0 <= start_step < len(plan.timesteps):
             raise ValueError(f"`start_step`={start_step} must lie in 0..{len(plan.timesteps) - 1}")
-        x = latents.to(torch.float32).contiguous().clone()
-        p = x.shape[0]
-        frames, starts = x.shape[2], [0]                   # frames per forward; without windows one forward sees the whole clip
-        if windowed:
-            from . import windows
-            frames = int(window_length)
-            starts = windows.window_starts(x.shape[2], frames, int(window_stride) if window_stride is not None
-                                           else max(1, frames - frames // 4))
-            profile = windows.window_profile(frames, window_weights)
         # None, the scalar itself, or the table route with its buffers, allocated here once for the loop
-        guidance = sampling.guidance_of(guidance_scale, guidance_rescale, x, frames, len(starts))
-        nb = 2 * p if guidance is not None else p          # model batch (:666)
-        if pag:                                             # [negative | prompt | perturbed] or [prompt | perturbed]
-            nb += p
-            guidance = sampling.PagGuidance(guidance, pag_scale)
+        guidance = sampling.guidance_of(guidance_scale, guidance_rescale, latents, geometry.frames, len(geometry.starts))
+        p = latents.shape[0]
+        nb = p * ((2 if guidance is not None else 1) + (1 if pag else 0))      # [negative |] prompt [| perturbed]  (:666)
         if ctx.shape[0] != nb:
             raise ValueError(f"ctx has {ctx.shape[0]} rows, expected {nb} for {p} latents at guidance_scale={guidance_scale}" +
                              (f", pag_scale={pag_scale}" if pag else ""))
-        if known is not None:
-            if tuple(known.shape) != tuple(x.shape):
-                raise ValueError(f"`known` has shape {tuple(known.shape)}, the latents {tuple(x.shape)}")
-            known = known.to(device=dev, dtype=torch.float32).contiguous()
-            if mask is not None:
-                mask = mask.to(device=dev, dtype=torch.float32).expand(p, 1, *x.shape[2:]).contiguous()
-        noise = sampling.StepNoise(x, generator)
-        refine = None
-        if free is not None:                                # the state of the iterations, beside the noise buffers
-            refine = free_init_mod.FreeInitRun(free, self.scheduler, x, generator,
-                                               lambda it: sampling.StepPlan(self.scheduler, free.steps_at(it, num_inference_steps), eta))
-        if known is not None:
-            if known_noise is None:
-                known_noise = randn_tensor(tuple(x.shape), generator=generator, device=dev, dtype=torch.float32)
-            elif tuple(known_noise.shape) != tuple(x.shape):
-                raise ValueError(f"`known_noise` has shape {tuple(known_noise.shape)}, the latents {tuple(x.shape)}")
-            known_noise = known_noise.to(device=dev, dtype=torch.float32).contiguous()
-        x0_prev = torch.empty_like(x) if plan.multistep else None     # never read before the first step has written it (c_prev = 0)
-        model_in = [torch.empty((nb, x.shape[1], frames) + tuple(x.shape[3:]), dtype=torch.float16, device=dev) for _ in starts]
-        if known is not None:
-            ops.known_blend(x, model_in[0], known, mask if start_step == 0 else None, known_noise, plan.noise_level(start_step),
-                            plan.input_scale(start_step))
-        elif pag:                                           # one fp16 value in every part, as the step kernel writes it
-            for part in model_in[0].view(nb // p, -1):
-                ops.latents_to_model_input1(x, part, plan.input_scale(0))
-        else:
-            for s, m in zip(starts, model_in):
-                (ops.latents_to_model_input if guidance is not None else ops.latents_to_model_input1)(
-                    x[:, :, s:s + frames].contiguous(), m, plan.input_scale(0))
-        t_dev = plan.t_dev(dev)
-        # with guidance the two halves of every model input are the same latents (one fp16 value written into both by this loop's
+        run = sampling.Run(latents, geometry, plan, guidance, nb, generator, pag=(pag_scale, pag_adaptive_scale) if pag else None,
+                           known=(known, mask, known_noise, start_step) if known is not None else None, cache_interval=cache_interval)
+        if free is not None:                                # the state of the iterations, beside the run's buffers
+            run.free = free_init_mod.FreeInitRun(free, self.scheduler, run.x, generator, plan_at)
+        run.fill(plan.input_scale(start_step))
+        # with guidance the two halves of every model input are the same latents (one fp16 value written into both by the loop's
         # own step kernel, pinned or not, windowed or not): the engine may compute the layers in front of the first text
         # cross-attention once
-        region = None
+        shared = run.model_in if run.guided and self.cfg_shared_prefix and not pag else None
         pag_was = self.unet.pag if pag else None           # the model's own setting comes back after the loop, whatever happens in it
         try:
             if pag:
                 self.unet.set_pag(pag_applied_layers, p)
-            with sampling.layer_cache_session(self.unet, cache_interval, cache_depth):
-                x = self._denoise_loop(x, ctx, nb, frames, starts, model_in, guidance, plan, noise, x0_prev, t_dev, start_step, windowed,
-                                       profile if windowed else None, known, mask, known_noise, region, callback, callback_steps,
-                                       pag_scale, pag_adaptive_scale, cache_interval, refine)
+            with sampling.layer_cache_session(self.unet, cache_interval, cache_depth), \
+                    sampling.engine_session(self.unet, run.batch, run.frames, *run.x.shape[3:], ctx, shared) as ctx:
+                def forward(w, i, layer_cache_mode):                                                         # line 670
+                    return self.unet(run.model_in[w], run.t_dev[i], encoder_hidden_states=ctx,
+                                     **sampling.forward_keywords(layer_cache_mode)).sample
+                return run.loop(forward, callback, callback_steps)
         finally:
             if pag_was is not None:
                 self.unet.set_pag(*pag_was)
-        return x
-
-    def _denoise_loop(self, x, ctx, nb, frames, starts, model_in, guidance, plan, noise, x0_prev, t_dev, start_step, windowed, profile,
-                      known, mask, known_noise, region, callback, callback_steps, pag_scale, pag_adaptive_scale, cache_interval=1,
-                      refine=None):
-        """The engine session and the steps of `denoise`, on the buffers it has set up.  `refine`: None, or the FreeInitRun of a
-        call that samples several times; every iteration after the first runs the steps of its own plan on the mixed latents."""
-        pag = isinstance(guidance, sampling.PagGuidance)
-        iterations = refine.setting.num_iters if refine is not None else 1
-        with sampling.engine_session(self.unet, nb, frames, x.shape[3], x.shape[4], ctx,
-                                     model_in if guidance is not None and self.cfg_shared_prefix and not pag else None) as ctx:
-            def forward(w, i):                 # (the keyword only where the cache is on: any UNet-shaped callable serves without)
-                mode = sampling.layer_cache_mode(i - start_step, cache_interval)
-                return self.unet(model_in[w], t_dev[i], encoder_hidden_states=ctx, **({"layer_cache": mode} if mode else {})).sample
-            forwards = sampling.WindowForwards(forward)
-            for iteration in range(iterations):
-                if iteration > 0:
-                    # the next iteration's plan first: its first input scale goes into the mix, which leaves x and, without
-                    # windows, every part of the model input as a step would (windows: cut from the mixed clip as at a run's start)
-                    plan = refine.plan_at(iteration)
-                    t_dev = plan.t_dev(x.device)
-                    refine.remix(x, None if windowed else model_in[0], plan.input_scale(0))
-                    if windowed:
-                        for s, m in zip(starts, model_in):
-                            (ops.latents_to_model_input if guidance is not None else ops.latents_to_model_input1)(
-                                x[:, :, s:s + frames].contiguous(), m, plan.input_scale(0))
-                for i in range(start_step, len(plan.timesteps)):
-                    eps = forwards(len(model_in), i)                                                      # line 670
-                    if pag:
-                        guidance.pag_scale = sampling.pag_scale_at(pag_scale, pag_adaptive_scale, plan.timesteps[i])
-                    coeffs = plan.coeffs(i, first=start_step > 0 and i == start_step)
-                    aux = x0_prev if plan.multistep else noise.draw() if plan.adds_noise(coeffs) else None
-                    if windowed:
-                        sampling.window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, plan.input_scale(i + 1),
-                                             plan.multistep)
-                    else:
-                        if mask is not None:                   # without a mask nothing is pinned: the plain step kernels
-                            region = (known, mask, known_noise, plan.noise_level(i + 1))
-                        sampling.step(eps[0], x, aux, model_in[0], guidance, coeffs, plan.input_scale(i + 1), plan.multistep, region)
-                    noise.done()
-                    if callback is not None and i % callback_steps == 0:
-                        callback(i, plan.timesteps[i], x)
-        return x
 
     @staticmethod
     def check_pag(pag_scale, pag_adaptive_scale, prompts: int, guidance_scale, guidance_rescale, **others) -> bool:
         """The perturbed-attention-guidance arguments of a call on `prompts` latents -> whether PAG is on (pag_scale > 0).  `others`:
-        the call's arguments PAG is not combined with, by name (None = absent).  Raises before anything reaches the engine."""
-        pag_scale, pag_adaptive_scale = float(pag_scale), float(pag_adaptive_scale)
-        if not (pag_scale >= 0.0 and pag_scale != float("inf")):
-            raise ValueError(f"`pag_scale` must be finite and >= 0 but is {pag_scale}")
-        if not (pag_adaptive_scale >= 0.0 and pag_adaptive_scale != float("inf")):
-            raise ValueError(f"`pag_adaptive_scale` must be finite and >= 0 but is {pag_adaptive_scale}")
-        if pag_scale == 0.0:
-            return False
-        for name, value in others.items():
-            if value is not None:
-                raise ValueError(f"`pag_scale` > 0 cannot be combined with `{name}`")
-        if isinstance(guidance_scale, (list, tuple)) or (isinstance(guidance_scale, torch.Tensor) and guidance_scale.dim() > 0):
-            raise ValueError("`pag_scale` > 0 cannot be combined with a `guidance_scale` sequence (one value per prompt)")
-        guided = guidance_scale > 1.0
-        if float(guidance_rescale) > 0.0:
-            raise ValueError("`pag_scale` > 0 cannot be combined with `guidance_rescale` > 0")
-        most = 2 if guided else 4
-        if prompts > most:
-            raise ValueError(f"`pag_scale` > 0 serves at most {most} prompts per call {'with' if guided else 'without'} guidance "
-                             f"(the engine's batch limit of 8 holds {'[negative | prompt | perturbed]' if guided else '[prompt | perturbed]'}), "
-                             f"got {prompts}")
-        return True
+        the call's arguments PAG is not combined with, by name (None = absent).  Raises before anything reaches the engine.
+        (sampling.check_features, with PAG as the only feature judged.)"""
+        return sampling.check_features(sampling.Surface(("pag",)), 0, prompts, known=others, guidance=(guidance_scale, guidance_rescale),
+                                       pag=(pag_scale, pag_adaptive_scale))[2]
 
     @staticmethod
     def strength_start(num_inference_steps: int, strength: float) -> int:
@@ -563,6 +470,20 @@ class VideoGenPipeline:
         lat = torch.cat([self.vae.encode(frames[i:i + 8]).latent_dist.mode() for i in range(0, b * f, 8)], dim=0) * 0.18215
         return lat.reshape(b, f, *lat.shape[1:]).permute(0, 2, 1, 3, 4).float().contiguous()
 
+    @contextlib.contextmanager
+    def _lora_scale(self, scale):
+        """diffusers' LoRA strength (`cross_attention_kwargs["scale"]`) for one call only, restored also on an exception; None
+        leaves the UNet alone."""
+        if scale is None:
+            yield
+            return
+        was = self.unet.lora_scale
+        self.unet.set_lora_scale(scale)
+        try:
+            yield
+        finally:
+            self.unet.set_lora_scale(was)
+
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str], None] = None, image_tensor=None, height: Optional[int] = None,
                  width: Optional[int] = None, video_length: int = 16, num_inference_steps: int = 50,
@@ -583,26 +504,17 @@ class VideoGenPipeline:
         ignored with a scalar `guidance_scale` <= 1, as in diffusers.  `pag_scale` > 0: perturbed-attention guidance in the
         transformers `pag_applied_layers` names, fading by `pag_adaptive_scale` per timestep below 1000.  `cache_interval` = N > 1: the layer cache, the whole UNet on every
         N-th step only, at `cache_depth`; not with `window_length`.  See `denoise`."""
-        sampling.check_layer_cache(cache_interval, cache_depth, window_length is not None and video_length > int(window_length))
-        free = free_init_mod.coerce(free_init if free_init is not None else getattr(self, "free_init", None))
-        if free is not None and (known_latents is not None or known_mask is not None or video is not None or strength != 1.0):
-            raise ValueError("FreeInit (`free_init` / enable_free_init) cannot be combined with `known_latents` / `known_mask` / `video` "
-                             "/ `strength`: the run's start is not noise there")
-        if window_length is not None and (known_latents is not None or known_mask is not None or video is not None or strength != 1.0):
-            raise ValueError("frame windows (`window_length`) cannot be combined with `known_latents` / `known_mask` / `video` / "
-                             "`strength`")
+        judged = dict(known=dict(known_latents=known_latents, video=video, known_mask=known_mask), late_start=strength != 1.0,
+                      window_length=window_length, guidance=(guidance_scale, guidance_rescale), pag=(pag_scale, pag_adaptive_scale),
+                      cache=(cache_interval, cache_depth), free_init=free_init if free_init is not None else self.free_init)
+        sampling.check_features(self.CALL, video_length, **judged)
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps, negative_prompt, prompt_embeds, negative_prompt_embeds)
-        if prompt is not None and isinstance(prompt, str):
-            batch_size = 1
-        elif prompt is not None:
-            batch_size = len(prompt)
-        else:
-            batch_size = prompt_embeds.shape[0]
+        batch_size = 1 if isinstance(prompt, str) else len(prompt) if prompt is not None else prompt_embeds.shape[0]
         device = self.device
-        pag = self.check_pag(pag_scale, pag_adaptive_scale, batch_size * (num_images_per_prompt or 1), guidance_scale, guidance_rescale,
-                             known_latents=known_latents, video=video, known_mask=known_mask, window_length=window_length)
+        # PAG's count needs the prompts, so it is judged here, behind `check_inputs`, as it always was
+        pag = sampling.check_features(self.CALL_PAG, video_length, batch_size * (num_images_per_prompt or 1), **judged)[2]
         do_cfg, scales, guidance_rescale = sampling.check_guidance(guidance_scale, guidance_rescale, batch_size,
                                                                    num_images_per_prompt or 1)
         if scales is not None:
@@ -617,36 +529,24 @@ class VideoGenPipeline:
                                        height, width, torch.float32, device, generator, latents)
         # sampling around known latents (pinned frames, video-to-video, clip continuation): `denoise(known=)`
         self.check_known_inputs(known_latents, known_mask, video, strength, latents.shape)
-        around = {}
+        features = {}                          # a feature's keywords reach `denoise` only when the feature is on: absent = the call without it
         if video is not None or known_latents is not None:
             known = self.encode_video(video) if video is not None else known_latents
-            around = dict(known=known.to(device=device, dtype=torch.float32), mask=known_mask,
-                          start_step=self.strength_start(num_inference_steps, strength))
+            features.update(known=known.to(device=device, dtype=torch.float32), mask=known_mask,
+                            start_step=self.strength_start(num_inference_steps, strength))
         elif window_length is not None:    # clips longer than the window: overlapping frame windows
-            around = dict(window_length=window_length, window_stride=window_stride, window_weights=window_weights)
-        rescale = dict(guidance_rescale=guidance_rescale) if guidance_rescale else {}      # absent = today's call
+            features.update(window_length=window_length, window_stride=window_stride, window_weights=window_weights)
+        if guidance_rescale:
+            features.update(guidance_rescale=guidance_rescale)
         if pag:
-            rescale.update(pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale, pag_applied_layers=pag_applied_layers)
+            features.update(pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale, pag_applied_layers=pag_applied_layers)
         if cache_interval not in (None, 1):
-            rescale.update(cache_interval=cache_interval, cache_depth=cache_depth)
+            features.update(cache_interval=cache_interval, cache_depth=cache_depth)
         if free_init is not None:              # (the pipeline's own setting is read by `denoise` itself)
-            rescale.update(free_init=free_init)
-        lora_scale = (cross_attention_kwargs or {}).get("scale")
-        if lora_scale is None:
-            latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta,
-                                   **around, **rescale)
-        else:                              # diffusers' LoRA strength for this call only, restored also on an exception
-            prev = self.unet.lora_scale
-            self.unet.set_lora_scale(lora_scale)
-            try:
-                latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps,
-                                       eta, **around, **rescale)
-            finally:
-                self.unet.set_lora_scale(prev)
-        if output_type == "latent":
-            video = latents
-        else:
-            video = self.decode_latents(latents)
+            features.update(free_init=free_init)
+        with self._lora_scale((cross_attention_kwargs or {}).get("scale")):
+            latents = self.denoise(latents, ctx, num_inference_steps, guidance_scale, generator, callback, callback_steps, eta, **features)
+        video = latents if output_type == "latent" else self.decode_latents(latents)
         if not return_dict:
             return (video,)
         return StableDiffusionPipelineOutput(video=video)

@@ -1,18 +1,25 @@
-"""What every denoising loop of this package shares, each piece once: the step plan (timesteps and per-step scalars of a
-scheduler), the step's noise (four generator kinds, host draws staged through pinned memory), the engine session (prepare,
-cached context, shared CFG input and their non-masking clean-up), the guidance arguments and the per-latent guidance table, the
-choice among the fused step ops, and the forwards of a windowed step.  The loops (`VideoGenPipeline.denoise`,
-`VideoUpscalePipeline.denoise`, `SpacedDiffusion._ddim_loop_hip`) keep what is theirs: which tensors reach the UNet, which step
-family runs, and the callback."""
+"""The denoising loop of this package, once.  `Run` holds what a loop over one clip owns (fp32 latents, window geometry, one fp16
+model input per window, x0 history, step noise, the current step plan, guidance, known region, layer-cache interval, FreeInit
+state), fills the model inputs (`Run.fill`) and runs the FreeInit iterations and their steps (`Run.loop`).  `check_features` judges
+which sampling features a call combines, from the one table `REFUSED`.  Beside them the pieces a loop is made of, each once: the
+step plan, the step's noise (four generator kinds, host draws staged through pinned memory), the engine and layer-cache sessions,
+the guidance arguments and the per-latent guidance table, the choice among the fused step ops, the forwards of a windowed step.
+A pipeline (`VideoGenPipeline.denoise`, `VideoUpscalePipeline.denoise`) says only what is its own: which tensors reach the UNet
+(`forward(w, i, layer_cache_mode)`), the sessions around the loop and their order, and its checks of its own arguments.
+`SpacedDiffusion._ddim_loop_hip` keeps its own schedule and arithmetic and takes the engine session only."""
 import contextlib
 import inspect
 import math
 import os
 import sys
 
+from collections import namedtuple
+
 import torch
 
-from . import ops
+from . import free_init as free_init_mod
+from . import ops, windows
+from .scheduling_ddpm import randn_tensor
 
 
 class StepPlan:
@@ -173,8 +180,7 @@ def check_layer_cache(cache_interval, cache_depth=1, windowed: bool = False) -> 
     if isinstance(cache_depth, bool) or not isinstance(cache_depth, int) or cache_depth < 1:
         raise ValueError(f"`cache_depth` must be an integer >= 1 but is {cache_depth!r}")
     if cache_interval > 1 and windowed:
-        raise ValueError("`cache_interval` > 1 cannot be combined with frame windows (`window_length`): every window's forward "
-                         "would need a layer cache of its own")
+        raise ValueError(REFUSED["cache", "windowed"])
     return cache_interval
 
 
@@ -274,6 +280,74 @@ def pag_scale_at(pag_scale: float, pag_adaptive_scale: float, timestep) -> float
     return max(float(pag_scale) - float(pag_adaptive_scale) * (1000.0 - float(timestep)), 0.0)
 
 
+def check_pag_scales(pag_scale, pag_adaptive_scale) -> bool:
+    """The two numbers of perturbed-attention guidance -> whether it is on (pag_scale > 0)."""
+    pag_scale, pag_adaptive_scale = float(pag_scale), float(pag_adaptive_scale)
+    if not (pag_scale >= 0.0 and pag_scale != float("inf")):
+        raise ValueError(f"`pag_scale` must be finite and >= 0 but is {pag_scale}")
+    if not (pag_adaptive_scale >= 0.0 and pag_adaptive_scale != float("inf")):
+        raise ValueError(f"`pag_adaptive_scale` must be finite and >= 0 but is {pag_adaptive_scale}")
+    return pag_scale > 0.0
+
+
+# Which sampling features are not combined: (feature, what it refuses) -> the refusal.  One feature's rows are judged in the order
+# they stand here.  `known`: any known-latents argument, a late start or reduced strength among them; `argument`: a known-latents
+# tensor or `window_length` is given (what PAG refuses, naming the first, {argument}); `window_length`: that argument is given;
+# `windowed`: it is below the clip's length, so windows are in force.  {known} / {free_init} are the caller's words (`Surface`).
+REFUSED = {
+    ("free_init", "known"): "{free_init} cannot be combined with {known}: the run's start is not noise there",
+    ("cache", "windowed"): "`cache_interval` > 1 cannot be combined with frame windows (`window_length`): every window's forward "
+                           "would need a layer cache of its own",
+    ("pag", "argument"): "`pag_scale` > 0 cannot be combined with `{argument}`",
+    ("pag", "sequence"): "`pag_scale` > 0 cannot be combined with a `guidance_scale` sequence (one value per prompt)",
+    ("pag", "rescale"): "`pag_scale` > 0 cannot be combined with `guidance_rescale` > 0",
+    ("window_length", "known"): "frame windows (`window_length`) cannot be combined with {known}",
+}
+
+# How one caller of `check_features` speaks: the features it judges, in the order it has always judged them (of two refusals that
+# apply to one call the earlier feature's is raised), and its words for FreeInit and for the known-latents arguments in a refusal.
+Surface = namedtuple("Surface", "order free_init known", defaults=("", ""))
+
+
+def check_features(surface, clip_frames: int, prompts: int = 0, known=None, late_start: bool = False, window_length=None,
+                   guidance=(1.0, 0.0), pag=(0.0, 0.0), cache=(None, 1), free_init=None):
+    """The sampling features of one call on a clip of `clip_frames` frames and `prompts` latents, as far as `surface.order` names
+    them: each feature's own arguments through its validator, then every pair of `REFUSED` that the call combines refused ->
+    (the FreeInit setting or None, the layer-cache interval in force, whether PAG is on).  A feature outside the order is neither
+    validated nor refused and comes back as off.  known: the caller's known-latents tensors by argument name (None = absent);
+    late_start: the run starts past position 0 or below full strength; guidance = (guidance_scale, guidance_rescale), looked at
+    only for PAG's rows (`check_guidance` stays where each caller has it); pag = (pag_scale, pag_adaptive_scale); cache =
+    (cache_interval, cache_depth).  Raises before anything reaches the engine."""
+    given = dict(known or {})
+    given.setdefault("window_length", window_length)
+    argument = next((name for name, value in given.items() if value is not None), None)
+    scale, rescale = guidance
+    on = {"argument": argument is not None, "known": late_start or any(value is not None for value in (known or {}).values()),
+          "window_length": window_length is not None, "windowed": window_length is not None and clip_frames > int(window_length),
+          "sequence": isinstance(scale, (list, tuple)) or (isinstance(scale, torch.Tensor) and scale.dim() > 0),
+          "rescale": "pag" in surface.order and float(rescale) > 0.0, "pag": False}
+    free, interval = None, 1
+    for feature in surface.order:
+        if feature == "free_init":
+            free = free_init_mod.coerce(free_init)
+            on[feature] = free is not None
+        elif feature == "cache":
+            interval = check_layer_cache(*cache)
+            on[feature] = interval > 1
+        elif feature == "pag":
+            on[feature] = check_pag_scales(*pag)
+        for (first, second), text in REFUSED.items():
+            if first == feature and on[first] and on[second]:
+                raise ValueError(text.format(free_init=surface.free_init, known=surface.known, argument=argument))
+        if feature == "pag" and on["pag"]:                  # the engine's batch limit of 8
+            guided = scale > 1.0
+            most, parts = (2, "[negative | prompt | perturbed]") if guided else (4, "[prompt | perturbed]")
+            if prompts > most:
+                raise ValueError(f"`pag_scale` > 0 serves at most {most} prompts per call {'with' if guided else 'without'} guidance "
+                                 f"(the engine's batch limit of 8 holds {parts}), got {prompts}")
+    return free, interval, on["pag"]
+
+
 def step(eps, x, aux, model_in, guidance_scale, coeffs, next_scale, multistep: bool, region=None):
     """One fused scheduler step through the `ops` wrapper of its family.  `aux`: the step's noise or None (five-coefficient
     family), the x0 history (multistep).  `guidance_scale` None: no classifier-free guidance; a GuidanceTable: the table is
@@ -338,3 +412,114 @@ class WindowForwards:
                 e = e.clone()
             eps.append(e)
         return eps
+
+
+# Which frames each UNet forward of a step sees: `frames` per forward, the windows' first frames, the weight profile of one window
+# (None without windows) and whether windows are in force.
+Windows = namedtuple("Windows", "frames starts profile windowed")
+
+
+def window_geometry(clip_frames: int, window_length=None, window_stride=None, window_weights: str = "triangle"):
+    """The windows of a clip of `clip_frames` frames (lavie_amd.windows).  `window_length` None or not below the clip's length: one
+    forward sees the whole clip.  `window_stride` defaults to three quarters of the window."""
+    frames = clip_frames if window_length is None else int(window_length)
+    if window_length is not None and frames < 1:
+        raise ValueError(f"`window_length`={window_length} must be >= 1")
+    if clip_frames <= frames:
+        return Windows(clip_frames, [0], None, False)
+    starts = windows.window_starts(clip_frames, frames, int(window_stride) if window_stride is not None else max(1, frames - frames // 4))
+    return Windows(frames, starts, windows.window_profile(frames, window_weights), True)
+
+
+class Run:
+    """What a denoising loop over one clip owns, allocated once in front of the loop, and the loop itself.
+    latents [P, C, F, h, w] (copied to fp32 `x`); `geometry`: the clip's Windows; `plan`: the StepPlan of the first (or only)
+    iteration; `guidance`: what `guidance_of` made for this clip and geometry (None, the scalar, or a GuidanceTable); `batch`: the
+    model batch, P times the parts [negative |] prompt [| perturbed]; `generator`: of the steps' noise and of `known_noise` when
+    that is drawn here; pag: None or (pag_scale, pag_adaptive_scale); known: None or (known, mask, known_noise, start_step), the
+    known region of `VideoGenPipeline.denoise`; `cache_interval`: the layer cache's, 1 = off.  `free`: None, or the FreeInitRun a
+    pipeline with FreeInit sets once `x` exists; it also makes the plans of the later iterations."""
+
+    def __init__(self, latents, geometry, plan: StepPlan, guidance, batch: int, generator=None, pag=None, known=None,
+                 cache_interval: int = 1):
+        self.x = x = latents.to(torch.float32).contiguous().clone()
+        self.frames, self.starts, self.profile, self.windowed = geometry
+        self.plan, self.batch, self.pag, self.cache_interval, self.free = plan, batch, pag, cache_interval, None
+        self.guided = guidance is not None
+        self.guidance = PagGuidance(guidance, pag[0]) if pag else guidance
+        self.start_step, self.region = 0, None
+        if known is not None:
+            known, mask, known_noise, self.start_step = known
+            if tuple(known.shape) != tuple(x.shape):
+                raise ValueError(f"`known` has shape {tuple(known.shape)}, the latents {tuple(x.shape)}")
+            if mask is not None:
+                mask = mask.to(device=x.device, dtype=torch.float32).expand(x.shape[0], 1, *x.shape[2:]).contiguous()
+        self.noise = StepNoise(x, generator)
+        if known is not None:
+            if known_noise is None:
+                known_noise = randn_tensor(tuple(x.shape), generator=generator, device=x.device, dtype=torch.float32)
+            elif tuple(known_noise.shape) != tuple(x.shape):
+                raise ValueError(f"`known_noise` has shape {tuple(known_noise.shape)}, the latents {tuple(x.shape)}")
+            self.region = tuple(None if t is None else t.to(device=x.device, dtype=torch.float32).contiguous()
+                                for t in (known, mask, known_noise))
+        self.x0_prev = torch.empty_like(x) if plan.multistep else None     # never read before the first step has written it (c_prev = 0)
+        self.model_in = [torch.empty((self.batch, x.shape[1], self.frames) + tuple(x.shape[3:]), dtype=torch.float16, device=x.device)
+                         for _ in self.starts]
+        self.t_dev = plan.t_dev(x.device)
+
+    def fill(self, scale: float):
+        """Every model input from x at `scale`, as the step kernel leaves it: at the start of a run (around known latents x is
+        first blended with them at the start position's noise level) and, with windows, after a FreeInit mix."""
+        x, model_in = self.x, self.model_in
+        if self.region is not None:
+            known, mask, known_noise = self.region
+            ops.known_blend(x, model_in[0], known, mask if self.start_step == 0 else None, known_noise,
+                            self.plan.noise_level(self.start_step), scale)
+        elif self.pag:                                      # one fp16 value in every part
+            for part in model_in[0].view(self.batch // x.shape[0], -1):
+                ops.latents_to_model_input1(x, part, scale)
+        else:
+            to_input = ops.latents_to_model_input if self.guided else ops.latents_to_model_input1
+            for s, m in zip(self.starts, model_in):
+                to_input(x[:, :, s:s + self.frames].contiguous(), m, scale)
+
+    def loop(self, forward, callback=None, callback_steps: int = 1) -> torch.Tensor:
+        """The FreeInit iterations (one without) and the steps of each, inside the caller's sessions -> x.  `forward(w, i,
+        layer_cache_mode)` runs the UNet on `model_in[w]` at `t_dev[i]` and hands back its prediction; the mode is None without
+        the layer cache (`forward_keywords`).  `callback(i, t, x)` after every `callback_steps`-th position."""
+        x, model_in, noise, guidance, start = self.x, self.model_in, self.noise, self.guidance, self.start_step
+        plan, masked, interval = self.plan, self.region is not None and self.region[1] is not None, self.cache_interval
+        forwards = WindowForwards(lambda w, i: forward(w, i, layer_cache_mode(i - start, interval)))
+        region = None
+        for iteration in range(self.free.setting.num_iters if self.free is not None else 1):
+            if iteration > 0:
+                # the next iteration's plan first: its first input scale goes into the mix, which leaves x and, without windows,
+                # every part of the model input as a step would (windows: cut from the mixed clip as at a run's start)
+                self.plan = plan = self.free.plan_at(iteration)
+                self.t_dev = plan.t_dev(x.device)
+                self.free.remix(x, None if self.windowed else model_in[0], plan.input_scale(0))
+                if self.windowed:
+                    self.fill(plan.input_scale(0))
+            for i in range(start, len(plan.timesteps)):
+                eps = forwards(len(model_in), i)
+                if self.pag:
+                    guidance.pag_scale = pag_scale_at(*self.pag, plan.timesteps[i])
+                coeffs = plan.coeffs(i, first=start > 0 and i == start)
+                aux = self.x0_prev if plan.multistep else noise.draw() if plan.adds_noise(coeffs) else None
+                if self.windowed:
+                    window_step(eps, x, aux, model_in, self.starts, self.profile, guidance, coeffs, plan.input_scale(i + 1),
+                                plan.multistep)
+                else:
+                    if masked:                              # without a mask nothing is pinned: the plain step kernels
+                        region = self.region + (plan.noise_level(i + 1),)
+                    step(eps[0], x, aux, model_in[0], guidance, coeffs, plan.input_scale(i + 1), plan.multistep, region)
+                noise.done()
+                if callback is not None and i % callback_steps == 0:
+                    callback(i, plan.timesteps[i], x)
+        return x
+
+
+def forward_keywords(layer_cache_mode) -> dict:
+    """The keywords a loop's forward adds to its UNet call: `layer_cache` only where the cache is on, so that any UNet-shaped
+    callable serves without it."""
+    return {"layer_cache": layer_cache_mode} if layer_cache_mode else {}

@@ -14,7 +14,7 @@ from typing import Callable, List, Optional, Union
 
 import torch
 
-from .. import ops, sampling
+from .. import sampling
 from ..scheduling_ddpm import DDPMScheduler, randn_tensor
 
 
@@ -79,8 +79,8 @@ class VideoUpscalePipeline:
                 window_stride: Optional[int] = None, window_weights: str = "triangle",
                 guidance_rescale: float = 0.0, cache_interval: Optional[int] = None, cache_depth: int = 1) -> torch.Tensor:
         """latents fp32 [P, 4, F, h, w]; image = the NOISED low-res frames [P, 3, F, h, w]; ctx fp16 [2P, n, d] =
-        [negative | prompt] -> denoised latents fp32.  Step plan, step noise, engine session and step dispatch are
-        lavie_amd.sampling's.
+        [negative | prompt] -> denoised latents fp32.  The loop and its buffers are lavie_amd.sampling's (`Run`); this
+        pipeline's own are the low-res frames and the class labels of its forward.
 
         `window_length` below F, for a clip longer than the model's window: ONE latent tensor holds all F frames (and one x0
         history for a multistep scheduler); per step the UNet runs on every window of `window_length` frames with that window's
@@ -95,59 +95,29 @@ class VideoUpscalePipeline:
         `cache_interval` = N > 1: the layer cache (DeepCache; `UNet.enable_layer_cache` at `cache_depth`): the whole UNet runs on
         steps 0, N, 2N, ... of this call, so every chunk starts with a refresh, the shallow walk on the steps between.  Not
         combined with frame windows.  None or 1 is the call without it."""
-        cache_interval = sampling.check_layer_cache(cache_interval, cache_depth,
-                                                    window_length is not None and latents.shape[2] > int(window_length))
-        windowed = False
-        if window_length is not None:
-            if int(window_length) < 1:
-                raise ValueError(f"`window_length`={window_length} must be >= 1")
-            windowed = latents.shape[2] > int(window_length)
-        dev = latents.device
+        _, cache_interval, _ = sampling.check_features(sampling.Surface(("cache",)), latents.shape[2], window_length=window_length,
+                                                       cache=(cache_interval, cache_depth))
+        geometry = sampling.window_geometry(latents.shape[2], window_length, window_stride, window_weights)
         plan = sampling.StepPlan(self.scheduler, num_inference_steps, eta)
-        x = latents.to(torch.float32).contiguous().clone()
-        x0_prev = torch.empty_like(x) if plan.multistep else None    # per call, so per chunk: the first step (c_prev = 0) never reads it
-        p = x.shape[0]
-        frames, starts = x.shape[2], [0]                   # frames per forward; without windows one forward sees the whole clip
-        if windowed:
-            from .. import windows
-            frames = int(window_length)
-            starts = windows.window_starts(x.shape[2], frames, int(window_stride) if window_stride is not None
-                                           else max(1, frames - frames // 4))
-            profile = windows.window_profile(frames, window_weights)
         # the scalar itself, or the table route with its buffers, allocated here once for the loop
-        guidance = sampling.guidance_of(guidance_scale, guidance_rescale, x, frames, len(starts))
+        guidance = sampling.guidance_of(guidance_scale, guidance_rescale, latents, geometry.frames, len(geometry.starts))
         if guidance is None:
             raise NotImplementedError("guidance_scale <= 1 (no classifier-free guidance) is outside the fused MI355X loop")
-        model_in = [torch.empty((2 * p, x.shape[1], frames) + tuple(x.shape[3:]), dtype=torch.float16, device=dev) for _ in starts]
-        low = []
-        for s, m in zip(starts, model_in):
-            ops.latents_to_model_input(x[:, :, s:s + frames].contiguous(), m, plan.input_scale(0))
-            img = image[:, :, s:s + frames]
-            low.append(torch.cat([img, img], dim=0).to(device=dev, dtype=torch.float16).contiguous())                 # :641
-        labels = torch.full((2 * p,), int(noise_level), dtype=torch.int64)                                            # :644
-        noise = sampling.StepNoise(x, generator)
-        t_dev = plan.t_dev(dev)
+        # one x0 history per call, so per chunk
+        run = sampling.Run(latents, geometry, plan, guidance, 2 * latents.shape[0], generator, cache_interval=cache_interval)
+        run.fill(plan.input_scale(0))
+        low = []                                            # every window's slice of the low-res frames, for both halves  (:641)
+        for s in run.starts:
+            img = image[:, :, s:s + run.frames]
+            low.append(torch.cat([img, img], dim=0).to(device=run.x.device, dtype=torch.float16).contiguous())
+        labels = torch.full((run.batch,), int(noise_level), dtype=torch.int64)                                        # :644
         # text keys / values once per chunk (or once for the whole windowed clip), not once per block and step
         with sampling.layer_cache_session(self.unet, cache_interval, cache_depth), \
-                sampling.engine_session(self.unet, 2 * p, frames, x.shape[3], x.shape[4], ctx) as ctx:
-            def forward(w, i):                                                                                        # :716-718
-                mode = sampling.layer_cache_mode(i, cache_interval)
-                return self.unet(model_in[w], t_dev[i], low[w], encoder_hidden_states=ctx, class_labels=labels,
-                                 **({"layer_cache": mode} if mode else {})).sample
-            forwards = sampling.WindowForwards(forward)
-            for i, t in enumerate(plan.timesteps):
-                eps = forwards(len(model_in), i)
-                coeffs = plan.coeffs(i)
-                aux = x0_prev if plan.multistep else noise.draw() if plan.adds_noise(coeffs) else None
-                if windowed:
-                    sampling.window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, plan.input_scale(i + 1),
-                                         plan.multistep)
-                else:                                                                                                 # :721-726
-                    sampling.step(eps[0], x, aux, model_in[0], guidance, coeffs, plan.input_scale(i + 1), plan.multistep)
-                noise.done()
-                if callback is not None and i % callback_steps == 0:
-                    callback(i, t, x)
-        return x
+                sampling.engine_session(self.unet, run.batch, run.frames, *run.x.shape[3:], ctx) as ctx:
+            def forward(w, i, layer_cache_mode):                                                                      # :716-718
+                return self.unet(run.model_in[w], run.t_dev[i], low[w], encoder_hidden_states=ctx, class_labels=labels,
+                                 **sampling.forward_keywords(layer_cache_mode)).sample
+            return run.loop(forward, callback, callback_steps)                                                        # :721-726
 
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str], None] = None, image: Optional[torch.Tensor] = None,
@@ -182,10 +152,13 @@ class VideoUpscalePipeline:
         if 4 + image.shape[1] != self.unet.config.in_channels:                                       # :692-701
             raise ValueError(f"Incorrect configuration settings! The config of `pipeline.unet` expects "
                              f"{self.unet.config.in_channels} but received 4 + {image.shape[1]} channels")
+        features = {}                          # a feature's keywords reach `denoise` only when the feature is on
+        if guidance_rescale:
+            features.update(guidance_rescale=guidance_rescale)
+        if cache_interval not in (None, 1):
+            features.update(cache_interval=cache_interval, cache_depth=cache_depth)
         latents = self.denoise(latents, image, ctx, noise_level, num_inference_steps, guidance_scale, eta, generator, callback,
-                               callback_steps, window_length, window_stride, window_weights,
-                               **(dict(guidance_rescale=guidance_rescale) if guidance_rescale else {}),
-                               **(dict(cache_interval=cache_interval, cache_depth=cache_depth) if cache_interval not in (None, 1) else {}))
+                               callback_steps, window_length, window_stride, window_weights, **features)
         if output_type != "latent":
             if self.vae is None:
                 raise ValueError("no vae attached: use output_type='latent'")
