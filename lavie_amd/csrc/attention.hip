@@ -18,14 +18,12 @@
 //    padded in LDS only — HBM traffic stays at the true head width.
 #include <utility>
 
-#include "common.h"
-#include "ops.h"
+#include "attention_frag.h"
 #include "profile.h"
 
 namespace lavie {
 
 constexpr int ATT_KEYS = 64;   // keys per tile
-constexpr float RESCALE_THR = 8.0f;   // log2 units: running max moves only when a row grows by > 2^8
 
 template <int DHP>
 struct AttTile {
@@ -80,9 +78,7 @@ __global__ __launch_bounds__(256, (DHP == 64 && QT == 2) ? 3 : 1) void attention
     half8_t qf[QT][T::KS];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
-        int q = q0 + qt * 16 + li;
-        q = q < p.Lq ? q : p.Lq - 1;
-        const half_t* qrow = p.q + ((size_t)qb * p.Lq + q) * p.ldq + head * dh;
+        const half_t* qrow = att_q_row(p, qb, head, dh, q0 + qt * 16 + li);
 #pragma unroll
         for (int ks = 0; ks < T::KS; ++ks) {
             const int d = ks * 32 + g * 8;
@@ -93,11 +89,7 @@ __global__ __launch_bounds__(256, (DHP == 64 && QT == 2) ? 3 : 1) void attention
 
     const half_t* kbase = p.k + (SC ? (size_t)0 : (size_t)kvb * p.Lk * p.ldk) + head * dh;
     const half_t* vbase = p.v + (SC ? (size_t)0 : (size_t)kvb * p.Lk * p.ldv) + head * dh;
-    // sparse-causal: first token row of the two key segments of this batch entry
-    const int sc_D = p.Lk >> 1;
-    const int sc_f = SC ? qb % p.sc_frames : 0;
-    const int sc_row0 = (qb - sc_f) * sc_D;
-    const int sc_row1 = (qb - (sc_f > 0 ? 1 : 0)) * sc_D - sc_D;      // row of key j >= D is sc_row1 + j
+    const AttScRows<SC> sc(p, qb);
     // staging plan of this thread, fixed for the whole loop (no per-tile index arithmetic): piece i covers
     // 16 bytes of key `pkey[i]` of the tile; a negative key marks an unused slot
     const int npiece = ATT_KEYS * nch;
@@ -122,8 +114,7 @@ __global__ __launch_bounds__(256, (DHP == 64 && QT == 2) ? 3 : 1) void attention
             if (pkey[i] >= 0) {
                 if (key0 + pkey[i] < p.Lk) {
                     if constexpr (SC) {
-                        const int j = key0 + pkey[i];
-                        const size_t row = (size_t)(j < sc_D ? sc_row0 + j : sc_row1 + j);
+                        const size_t row = sc.row(key0 + pkey[i]);
                         rk[i] = *reinterpret_cast<const half8_t*>(kbase + row * p.ldk + kofs_g[i]);
                         rv[i] = *reinterpret_cast<const half8_t*>(vbase + row * p.ldv + vofs_g[i]);
                     } else {
@@ -206,19 +197,7 @@ __global__ __launch_bounds__(256, (DHP == 64 && QT == 2) ? 3 : 1) void attention
         // sums and O stay in fp32) and the O-wide rescale runs on a handful of tiles instead of every tile.
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
-            float mx = fmaxf(fmaxf(s[0][qt][0], s[0][qt][1]), fmaxf(s[0][qt][2], s[0][qt][3]));
-#pragma unroll
-            for (int kt = 1; kt < 4; ++kt)
-                mx = fmaxf(mx, fmaxf(fmaxf(s[kt][qt][0], s[kt][qt][1]), fmaxf(s[kt][qt][2], s[kt][qt][3])));
-            {   // max over the four 16-lane groups holding the same query: two half-swaps instead of ds_bpermute
-                const unsigned u = __float_as_uint(mx);
-                const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-                mx = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-                const unsigned v = __float_as_uint(mx);
-                const auto b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-                mx = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-            }
-            const float mxs = mx * sl2;
+            const float mxs = att_group_max(att_lane_max<true>(s, qt)) * sl2;
             if (__builtin_amdgcn_ballot_w64(mxs > m_run[qt] + RESCALE_THR) != 0) {
                 const float m_new = fmaxf(m_run[qt], mxs);
                 const float alpha = __builtin_amdgcn_exp2f(m_run[qt] - m_new);   // first tile: exp2(-inf) = 0
@@ -237,13 +216,7 @@ __global__ __launch_bounds__(256, (DHP == 64 && QT == 2) ? 3 : 1) void attention
                     e[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][qt][r], sl2, nm));
                     if constexpr (!LSUM) psum += e[r];
                 }
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
-                const half2_t h0 = __builtin_convertvector((f32x2){e[0], e[1]}, half2_t);
-                const half2_t h1 = __builtin_convertvector((f32x2){e[2], e[3]}, half2_t);
-                pb[kt >> 1][qt][(kt & 1) * 4 + 0] = h0[0];
-                pb[kt >> 1][qt][(kt & 1) * 4 + 1] = h0[1];
-                pb[kt >> 1][qt][(kt & 1) * 4 + 2] = h1[0];
-                pb[kt >> 1][qt][(kt & 1) * 4 + 3] = h1[1];
+                att_pack4(pb[kt >> 1][qt], kt, e[0], e[1], e[2], e[3]);
             }
             if constexpr (!LSUM) l_run[qt] += psum;           // per-lane partial; reduced over g at the end
         }
@@ -305,21 +278,6 @@ __global__ __launch_bounds__(256, (DHP == 64 && QT == 2) ? 3 : 1) void attention
     }
 }
 
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-
-// hardware-transposed 8-byte LDS read at a compile-time offset, untracked by the compiler (see attention_dma_kernel)
-template <int OFF>
-__device__ __forceinline__ u32x2_t lds_read_tr16_asm(unsigned addr) {
-    u32x2_t r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-    return r;
-}
-template <int OFF>
-__device__ __forceinline__ u32x2_t lds_read_b64_asm(unsigned addr) {
-    u32x2_t r;
-    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-    return r;
-}
 // the V^T fragments of 32 keys: output tile dt = columns 16 dt .. 16 dt + 15, keys +0..15 (lo) and +16..31 (hi)
 template <int BASE, int RS, int N, int... DTs>
 __device__ __forceinline__ void att_read_v(unsigned addr, u32x2_t (&lo)[N], u32x2_t (&hi)[N], std::integer_sequence<int, DTs...>) {
@@ -354,9 +312,7 @@ __device__ __forceinline__ void att_wait_lds(u32x2_t (&lo)[N], u32x2_t (&hi)[N],
 //    carries the LSUM column of ones — by pointing those lanes' source address at it (the source address is per lane).
 //  * K columns past dh need no zeros: the Q fragment is zero there, and 0 * finite = 0.
 //  * every wave issues the same number of pieces per tile (R / 2; R is even), so one counted wait serves all.
-#ifndef ATT_DMA_OCC5
-#define ATT_DMA_OCC5 4      // waves per SIMD asked for at head dim 40 (128 VGPRs, 4 x 37 KiB of LDS per CU)
-#endif
+constexpr int ATT_DMA_OCC5 = 4;      // waves per SIMD asked for at head dim 40 (128 VGPRs, 4 x 37 KiB of LDS per CU)
 __device__ __attribute__((aligned(16))) half_t g_att_pad_page[16] = {(half_t)1.0f, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 // NCH = dh / 8 = 16-byte chunks a key row really has (the model's head dims: 5, 10, 20); the row holds R >= NCH (+ 1 for the
@@ -417,9 +373,7 @@ __global__ __launch_bounds__(64 * NW, (NCH == 5 && QT == 2) ? ATT_DMA_OCC5 : 1) 
     half4_t qtail[QT];               // TAIL16: Q[q = li][dims 32 KS32 + 4 g .. +3] (zero past the head dim)
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
-        int q = q0 + qt * 16 + li;
-        q = q < p.Lq ? q : p.Lq - 1;
-        const half_t* qrow = p.q + ((size_t)qb * p.Lq + q) * p.ldq + head * dh;
+        const half_t* qrow = att_q_row(p, qb, head, dh, q0 + qt * 16 + li);
 #pragma unroll
         for (int ks = 0; ks < T::KS32; ++ks) {
             const int d = ks * 32 + g * 8;
@@ -442,10 +396,7 @@ __global__ __launch_bounds__(64 * NW, (NCH == 5 && QT == 2) ? ATT_DMA_OCC5 : 1) 
 
     const half_t* kbase = p.k + (SC ? (size_t)0 : (size_t)kvb * p.Lk * p.ldk) + head * dh;
     const half_t* vbase = p.v + (SC ? (size_t)0 : (size_t)kvb * p.Lk * p.ldv) + head * dh;
-    const int sc_D = p.Lk >> 1;
-    const int sc_f = SC ? qb % p.sc_frames : 0;
-    const int sc_row0 = (qb - sc_f) * sc_D;
-    const int sc_row1 = (qb - (sc_f > 0 ? 1 : 0)) * sc_D - sc_D;      // row of key j >= D is sc_row1 + j
+    const AttScRows<SC> sc(p, qb);
     // ---- this wave's pieces: piece x of 2 R (0 .. R-1 = K, R .. 2R-1 = V) for x = wave, wave + 4, ...; lane l of piece x
     // is chunk (x % R) * 64 + l of its operand's tile: key = chunk / R, column chunk = chunk % R
     int pkey[PIECES], pch[PIECES];
@@ -468,7 +419,7 @@ __global__ __launch_bounds__(64 * NW, (NCH == 5 && QT == 2) ? ATT_DMA_OCC5 : 1) 
             int key = key0 + pkey[i];
             key = key < p.Lk ? key : p.Lk - 1;                // keys past Lk: any finite row (their scores are masked)
             size_t row;
-            if constexpr (SC) row = (size_t)(key < sc_D ? sc_row0 + key : sc_row1 + key);
+            if constexpr (SC) row = sc.row(key);
             else row = (size_t)key;
             const half_t* src = is_v ? vbase + row * p.ldv + pch[i] * 8 : kbase + row * p.ldk + pch[i] * 8;
             if (pch[i] >= nch) src = (is_v && LSUM && pch[i] == nch) ? pad_one : pad_zero;
@@ -569,16 +520,7 @@ __global__ __launch_bounds__(64 * NW, (NCH == 5 && QT == 2) ? ATT_DMA_OCC5 : 1) 
             // the branch (m_run = -inf there)
             float mxl[QT];
 #pragma unroll
-            for (int qt = 0; qt < QT; ++qt) {
-                float mx = fmaxf(fmaxf(s[0][qt][0], s[0][qt][1]), s[0][qt][2]);
-                mx = fmaxf(fmaxf(mx, s[0][qt][3]), s[1][qt][0]);
-                mx = fmaxf(fmaxf(mx, s[1][qt][1]), s[1][qt][2]);
-                mx = fmaxf(fmaxf(mx, s[1][qt][3]), s[2][qt][0]);
-                mx = fmaxf(fmaxf(mx, s[2][qt][1]), s[2][qt][2]);
-                mx = fmaxf(fmaxf(mx, s[2][qt][3]), s[3][qt][0]);
-                mx = fmaxf(fmaxf(mx, s[3][qt][1]), s[3][qt][2]);
-                mxl[qt] = fmaxf(mx, s[3][qt][3]);
-            }
+            for (int qt = 0; qt < QT; ++qt) mxl[qt] = att_lane_max<false>(s, qt);
             float mxa = mxl[0];
 #pragma unroll
             for (int qt = 1; qt < QT; ++qt) mxa = fmaxf(mxa, mxl[qt]);
@@ -587,13 +529,7 @@ __global__ __launch_bounds__(64 * NW, (NCH == 5 && QT == 2) ? ATT_DMA_OCC5 : 1) 
                 // O (and l), shift this tile's scores and the accumulator initialiser
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) {
-                    float mx = mxl[qt];
-                    const unsigned u = __float_as_uint(mx);
-                    const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-                    mx = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-                    const unsigned v = __float_as_uint(mx);
-                    const auto b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-                    mx = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+                    const float mx = att_group_max(mxl[qt]);
                     // first tile: the maximum itself (it may be far below 0: fp16 P must not underflow); later: only growth
                     // (a fully masked / -inf first tile keeps delta finite: 0)
                     float delta = t == 0 ? mx : fmaxf(mx, 0.f);
@@ -623,67 +559,37 @@ __global__ __launch_bounds__(64 * NW, (NCH == 5 && QT == 2) ? ATT_DMA_OCC5 : 1) 
                         e[r] = __builtin_amdgcn_exp2f(s[kt][qt][r]);
                         if constexpr (!LSUM) psum += e[r];
                     }
-                    typedef float f32x2 __attribute__((ext_vector_type(2)));
-                    const half2_t h0 = __builtin_convertvector((f32x2){e[0], e[1]}, half2_t);
-                    const half2_t h1 = __builtin_convertvector((f32x2){e[2], e[3]}, half2_t);
-                    pb[kt >> 1][qt][(kt & 1) * 4 + 0] = h0[0];
-                    pb[kt >> 1][qt][(kt & 1) * 4 + 1] = h0[1];
-                    pb[kt >> 1][qt][(kt & 1) * 4 + 2] = h1[0];
-                    pb[kt >> 1][qt][(kt & 1) * 4 + 3] = h1[1];
+                    att_pack4(pb[kt >> 1][qt], kt, e[0], e[1], e[2], e[3]);
                 }
                 if constexpr (!LSUM) l_run[qt] += psum;
             }
-        }
-        // ---- online softmax per query column, deferred rescale (as the register-staged kernel)
+        } else {
+            // ---- round-3 softmax per query column, deferred rescale (as the register-staged kernel); the in-lane maximum as a chain
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-            if constexpr (V2) break;        // handled below, both query tiles under ONE decision
-
-            // a chain of three-input maxima (v_max3_f32: 8 slots for the 16 scores; the pairwise tree took 13)
-            float mx = fmaxf(fmaxf(s[0][qt][0], s[0][qt][1]), s[0][qt][2]);
-            mx = fmaxf(fmaxf(mx, s[0][qt][3]), s[1][qt][0]);
-            mx = fmaxf(fmaxf(mx, s[1][qt][1]), s[1][qt][2]);
-            mx = fmaxf(fmaxf(mx, s[1][qt][3]), s[2][qt][0]);
-            mx = fmaxf(fmaxf(mx, s[2][qt][1]), s[2][qt][2]);
-            mx = fmaxf(fmaxf(mx, s[2][qt][3]), s[3][qt][0]);
-            mx = fmaxf(fmaxf(mx, s[3][qt][1]), s[3][qt][2]);
-            mx = fmaxf(mx, s[3][qt][3]);
-            {
-                const unsigned u = __float_as_uint(mx);
-                const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-                mx = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-                const unsigned v = __float_as_uint(mx);
-                const auto b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-                mx = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-            }
-            const float mxs = mx * sl2;
-            if (__builtin_amdgcn_ballot_w64(mxs > m_run[qt] + RESCALE_THR) != 0) {
-                const float m_new = fmaxf(m_run[qt], mxs);
-                const float alpha = __builtin_amdgcn_exp2f(m_run[qt] - m_new);   // first tile: exp2(-inf) = 0
-                m_run[qt] = m_new;
-                if constexpr (!LSUM) l_run[qt] *= alpha;
+            for (int qt = 0; qt < QT; ++qt) {
+                const float mxs = att_group_max(att_lane_max<false>(s, qt)) * sl2;
+                if (__builtin_amdgcn_ballot_w64(mxs > m_run[qt] + RESCALE_THR) != 0) {
+                    const float m_new = fmaxf(m_run[qt], mxs);
+                    const float alpha = __builtin_amdgcn_exp2f(m_run[qt] - m_new);   // first tile: exp2(-inf) = 0
+                    m_run[qt] = m_new;
+                    if constexpr (!LSUM) l_run[qt] *= alpha;
 #pragma unroll
-                for (int dt = 0; dt < T::DT; ++dt) o[dt][qt] *= alpha;
-            }
-            const float nm = -m_run[qt];
-            float psum = 0.f;
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt) {
-                float e[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    e[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][qt][r], sl2, nm));
-                    if constexpr (!LSUM) psum += e[r];
+                    for (int dt = 0; dt < T::DT; ++dt) o[dt][qt] *= alpha;
                 }
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
-                const half2_t h0 = __builtin_convertvector((f32x2){e[0], e[1]}, half2_t);
-                const half2_t h1 = __builtin_convertvector((f32x2){e[2], e[3]}, half2_t);
-                pb[kt >> 1][qt][(kt & 1) * 4 + 0] = h0[0];
-                pb[kt >> 1][qt][(kt & 1) * 4 + 1] = h0[1];
-                pb[kt >> 1][qt][(kt & 1) * 4 + 2] = h1[0];
-                pb[kt >> 1][qt][(kt & 1) * 4 + 3] = h1[1];
+                const float nm = -m_run[qt];
+                float psum = 0.f;
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt) {
+                    float e[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        e[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][qt][r], sl2, nm));
+                        if constexpr (!LSUM) psum += e[r];
+                    }
+                    att_pack4(pb[kt >> 1][qt], kt, e[0], e[1], e[2], e[3]);
+                }
+                if constexpr (!LSUM) l_run[qt] += psum;           // per-lane partial; reduced over g at the end
             }
-            if constexpr (!LSUM) l_run[qt] += psum;           // per-lane partial; reduced over g at the end
         }
 
         // ---- O^T[dim, q] += V^T P^T  (V^T fragments by hardware-transposed LDS reads)
@@ -745,78 +651,99 @@ __global__ __launch_bounds__(64 * NW, (NCH == 5 && QT == 2) ? ATT_DMA_OCC5 : 1) 
         }
     }
 }
+// ------------------------------------------------------------------------------------------------------------------
+// Which instantiation serves a problem.  att_route is the only place that decides; ATT_TABLE is the only place that instantiates.
+enum AttKind { ATT_REG, ATT_DMA, ATT_WIDE };
+struct AttRoute {
+    AttKind kind;
+    int dim;               // reg: DHP (head dim padded to 64 / 96 / 160); dma: NCH = head dim / 8; wide: the head dim
+    int QT, NBUF;          // 16-query tiles per wave; dma: key-tile buffers
+    bool LSUM, SC, V2;     // row sums on the matrix pipe; sparse-causal keys; dma: the round-4 softmax
+    int NW, NDT;           // dma: waves per workgroup; reg: compile-time output-tile count (0 = run time)
+    bool operator==(const AttRoute& r) const {
+        return kind == r.kind && dim == r.dim && QT == r.QT && NBUF == r.NBUF && LSUM == r.LSUM && SC == r.SC && V2 == r.V2 && NW == r.NW && NDT == r.NDT;
+    }
+};
 
-template <int NCH, int QT, int NBUF, bool LSUM, bool SC>
+static AttRoute att_route(const AttnParams& p) {
+    if (p.dh == 256 || p.dh == 512) return {ATT_WIDE, p.dh, 2, 0, false, false, false, 4, 0};      // attention_wide.hip (the VAE mid block's single head)
+    const bool sc = p.sc_frames > 0;
+    const int qt = p.Lq > 64 * 3 ? 2 : 1;     // >= 2 full 128-row blocks: use 32 rows per wave
+    // LDS-DMA staging for the model's head dims, and the VSR stage's (no sparse-causal attention there)
+    if (p.dh == 40 || p.dh == 80 || p.dh == 160 || (!sc && (p.dh == 32 || p.dh == 64 || p.dh == 128))) {
+        const int nch = p.dh / 8;
+        // V2 = the round-4 softmax; V2 false = the round-2/3 one (scale + maximum applied by v_fma, cross-lane maximum every tile):
+        // head dims 128 / 160 keep that (they are MFMA-bound, and the four initialiser registers per query tile would push the
+        // 32-row instantiations past 256 VGPRs = from two waves per SIMD to one), and so does the 77-key text cross-attention at head
+        // dim 40 (two key tiles, the first of which always takes the rescale branch — measured 41 -> 46 us at level 0, round 4)
+        const bool short_keys = nch == 5 && p.Lk <= 2 * ATT_KEYS;
+        const bool v2 = nch <= 10 && !short_keys;
+        // level-0 self-attention (2560 keys): 8 waves = 256 queries per workgroup
+        const int nw = nch == 5 && qt == 2 && v2 && p.Lq % (8 * qt * 16) == 0 ? 8 : 4;
+        return {ATT_DMA, nch, qt, nch >= 16 ? 2 : 3, nch == 5, sc, v2, nw, 0};     // head dim 40 is off the 16 grid: LSUM
+    }
+    // the register-staged kernels take the others: head dims off the 16 grid with the row sums on the matrix pipe, head dim 64 (of
+    // sparse-causal attention: the plain one is above) with a compile-time output-tile count
+    const int dhp = p.dh <= 64 ? 64 : p.dh <= 96 ? 96 : 160;
+    return {ATT_REG, dhp, qt, 0, dhp < 160 && p.dh % 16 != 0, sc, false, 4, p.dh == 64 ? 4 : 0};
+}
+
+template <int NCH, int QT, int NBUF, bool LSUM, bool SC, bool V2, int NW>
 static int launch_att_dma(const AttnParams& p, hipStream_t stream) {
     using T = AttDmaTile<NCH, LSUM>;
     constexpr int lds = NBUF * 2 * T::TILE_BYTES + 1024;     // + slack: the last row's MFMA-width reads run past the tile
-    // V2 = the round-4 softmax; V2 false = the round-2/3 one (scale + maximum applied by v_fma, cross-lane maximum every tile)
-    // (head dims 128 / 160 keep that: they are MFMA-bound, and the four initialiser registers per query tile would push the
-    // 32-row instantiations past 256 VGPRs = from two waves per SIMD to one)
-    constexpr bool V2_OK = NCH <= 10;
-    // (and the 77-key text cross-attention at head dim 40: two key tiles, the first of which always takes the rescale branch —
-    // measured 41 -> 46 us at level 0, round 4)
-    const bool short_keys = NCH == 5 && p.Lk <= 2 * ATT_KEYS;
-    if constexpr (NCH == 5 && QT == 2) {
-        // level-0 self-attention (2560 keys): 8 waves = 256 queries per workgroup
-        if (!short_keys && p.Lq % (8 * QT * 16) == 0) {
-            auto kern8 = attention_dma_kernel<NCH, QT, NBUF, LSUM, SC, true, 8>;
-            if (int rc = ensure_dynamic_lds((const void*)kern8, lds)) return rc;
-            hipLaunchKernelGGL(kern8, dim3(p.Lq / (8 * QT * 16), p.heads, p.NBq), dim3(512), lds, stream, p);
-            LAVIE_HIP(hipGetLastError());
-            return 0;
-        }
-    }
-    auto kern = (!V2_OK || short_keys) ? attention_dma_kernel<NCH, QT, NBUF, LSUM, SC, false>
-                                       : attention_dma_kernel<NCH, QT, NBUF, LSUM, SC, V2_OK>;
+    auto kern = attention_dma_kernel<NCH, QT, NBUF, LSUM, SC, V2, NW>;
     if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc;
-    dim3 grid(cdiv(p.Lq, 4 * QT * 16), p.heads, p.NBq);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, p);
+    hipLaunchKernelGGL(kern, dim3(cdiv(p.Lq, NW * QT * 16), p.heads, p.NBq), dim3(64 * NW), lds, stream, p);
     LAVIE_HIP(hipGetLastError());
     return 0;
 }
 
-template <int DHP, int QT, bool LSUM = false, bool SC = false, int NDT = 0>
+template <int DHP, int QT, bool LSUM, bool SC, int NDT>
 static int launch_att(const AttnParams& p, hipStream_t stream) {
     using T = AttTile<DHP>;
     auto kern = attention_kernel<DHP, QT, LSUM, SC, NDT>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        LAVIE_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES));
-        attr_set = true;
-    }
-    dim3 grid(cdiv(p.Lq, 4 * QT * 16), p.heads, p.NBq);
-    hipLaunchKernelGGL(kern, grid, dim3(256), T::LDS_BYTES, stream, p);
+    if (int rc = ensure_dynamic_lds((const void*)kern, T::LDS_BYTES)) return rc;
+    hipLaunchKernelGGL(kern, dim3(cdiv(p.Lq, 4 * QT * 16), p.heads, p.NBq), dim3(256), T::LDS_BYTES, stream, p);
     LAVIE_HIP(hipGetLastError());
     return 0;
 }
 
-// Kernel choice by head dim: LDS-DMA staging for the model's head dims (and the VSR stage's); the register-staged kernels take
-// the others (head dim 64 of sparse-causal attention with a compile-time output-tile count).
-template <bool SC>
-static int dispatch_att(const AttnParams& p, bool big, bool lsum, hipStream_t stream) {
-    if (p.dh == 40 && lsum) return big ? launch_att_dma<5, 2, 3, true, SC>(p, stream) : launch_att_dma<5, 1, 3, true, SC>(p, stream);
-    if (p.dh == 80) return big ? launch_att_dma<10, 2, 3, false, SC>(p, stream) : launch_att_dma<10, 1, 3, false, SC>(p, stream);
-    if (p.dh == 160) return big ? launch_att_dma<20, 2, 2, false, SC>(p, stream) : launch_att_dma<20, 1, 2, false, SC>(p, stream);
-    if constexpr (!SC) {           // the VSR stage's head dims (no sparse-causal attention there)
-        if (p.dh == 32) return big ? launch_att_dma<4, 2, 3, false, false>(p, stream) : launch_att_dma<4, 1, 3, false, false>(p, stream);
-        if (p.dh == 64) return big ? launch_att_dma<8, 2, 3, false, false>(p, stream) : launch_att_dma<8, 1, 3, false, false>(p, stream);
-        if (p.dh == 128) return big ? launch_att_dma<16, 2, 2, false, false>(p, stream) : launch_att_dma<16, 1, 2, false, false>(p, stream);
-    }
-    if (p.dh <= 64) {
-        if (lsum) return big ? launch_att<64, 2, true, SC>(p, stream) : launch_att<64, 1, true, SC>(p, stream);
-        if (p.dh == 64) return big ? launch_att<64, 2, false, SC, 4>(p, stream) : launch_att<64, 1, false, SC, 4>(p, stream);
-        return big ? launch_att<64, 2, false, SC>(p, stream) : launch_att<64, 1, false, SC>(p, stream);
-    }
-    if (p.dh <= 96) {
-        if (lsum) return big ? launch_att<96, 2, true, SC>(p, stream) : launch_att<96, 1, true, SC>(p, stream);
-        return big ? launch_att<96, 2, false, SC>(p, stream) : launch_att<96, 1, false, SC>(p, stream);
-    }
-    return big ? launch_att<160, 2, false, SC>(p, stream) : launch_att<160, 1, false, SC>(p, stream);
-}
+struct AttEntry {
+    AttRoute route;
+    int (*launch)(const AttnParams&, hipStream_t);
+};
+template <int NCH, int QT, int NBUF, bool LSUM, bool SC, bool V2, int NW = 4>
+constexpr AttEntry att_dma() { return {{ATT_DMA, NCH, QT, NBUF, LSUM, SC, V2, NW, 0}, launch_att_dma<NCH, QT, NBUF, LSUM, SC, V2, NW>}; }
+template <int DHP, int QT, bool LSUM, bool SC, int NDT = 0>
+constexpr AttEntry att_reg() { return {{ATT_REG, DHP, QT, 0, LSUM, SC, false, 4, NDT}, launch_att<DHP, QT, LSUM, SC, NDT>}; }
+
+// Every route att_route can return, and nothing else (sparse-causal short_keys at QT 2 cannot happen: QT 2 needs Lq > 192, Lk = 2 Lq).
+static const AttEntry ATT_TABLE[] = {
+    // head dim 40: <NCH, QT, NBUF, LSUM, SC, V2, NW>
+    att_dma<5, 1, 3, true, false, true>(), att_dma<5, 2, 3, true, false, true>(), att_dma<5, 2, 3, true, false, true, 8>(),
+    att_dma<5, 1, 3, true, false, false>(), att_dma<5, 2, 3, true, false, false>(),
+    att_dma<5, 1, 3, true, true, true>(), att_dma<5, 2, 3, true, true, true>(), att_dma<5, 2, 3, true, true, true, 8>(),
+    att_dma<5, 1, 3, true, true, false>(),
+    // head dims 80 and 160
+    att_dma<10, 1, 3, false, false, true>(), att_dma<10, 2, 3, false, false, true>(), att_dma<10, 1, 3, false, true, true>(), att_dma<10, 2, 3, false, true, true>(),
+    att_dma<20, 1, 2, false, false, false>(), att_dma<20, 2, 2, false, false, false>(), att_dma<20, 1, 2, false, true, false>(), att_dma<20, 2, 2, false, true, false>(),
+    // the VSR stage's head dims 32, 64, 128
+    att_dma<4, 1, 3, false, false, true>(), att_dma<4, 2, 3, false, false, true>(), att_dma<8, 1, 3, false, false, true>(), att_dma<8, 2, 3, false, false, true>(),
+    att_dma<16, 1, 2, false, false, false>(), att_dma<16, 2, 2, false, false, false>(),
+    // register-staged: <DHP, QT, LSUM, SC, NDT>
+    att_reg<64, 1, true, false>(), att_reg<64, 2, true, false>(), att_reg<64, 1, true, true>(), att_reg<64, 2, true, true>(),
+    att_reg<64, 1, false, false>(), att_reg<64, 2, false, false>(), att_reg<64, 1, false, true>(), att_reg<64, 2, false, true>(),
+    att_reg<64, 1, false, true, 4>(), att_reg<64, 2, false, true, 4>(),
+    att_reg<96, 1, true, false>(), att_reg<96, 2, true, false>(), att_reg<96, 1, true, true>(), att_reg<96, 2, true, true>(),
+    att_reg<96, 1, false, false>(), att_reg<96, 2, false, false>(), att_reg<96, 1, false, true>(), att_reg<96, 2, false, true>(),
+    att_reg<160, 1, false, false>(), att_reg<160, 2, false, false>(), att_reg<160, 1, false, true>(), att_reg<160, 2, false, true>(),
+    // head dims 256 / 512
+    {{ATT_WIDE, 256, 2, 0, false, false, false, 4, 0}, launch_attention_wide}, {{ATT_WIDE, 512, 2, 0, false, false, false, 4, 0}, launch_attention_wide},
+};
 
 int launch_attention(const AttnParams& p, hipStream_t stream) {
-    const bool wide = p.dh == 256 || p.dh == 512;      // attention_wide.hip (the VAE mid block's single head)
+    const bool wide = p.dh == 256 || p.dh == 512;
     LAVIE_CHECK((p.dh % 8 == 0 && p.dh >= 8 && p.dh <= 160) || wide,
                 "attention: head dim %d unsupported (multiple of 8 up to 160, or 256, or 512)", p.dh);
     LAVIE_CHECK(p.Lq > 0 && p.Lk > 0 && p.NBq > 0 && p.heads > 0 && p.kv_batch_div > 0, "attention: empty problem");
@@ -826,16 +753,16 @@ int launch_attention(const AttnParams& p, hipStream_t stream) {
                       2.0 * (2.0 * tok_q * width + 2.0 * ((double)p.NBq / p.kv_batch_div) * p.Lk * width));
     if (wide) {
         LAVIE_CHECK(p.sc_frames == 0, "sparse-causal attention: head dim %d unsupported (multiple of 8, <= 160)", p.dh);
-        return launch_attention_wide(p, stream);
-    }
-    const bool big = p.Lq > 64 * 3;     // >= 2 full 128-row blocks: use 32 rows per wave
-    if (p.sc_frames > 0) {
+    } else if (p.sc_frames > 0) {
         LAVIE_CHECK(p.Lk == 2 * p.Lq && p.kv_batch_div == 1 && p.NBq % p.sc_frames == 0,
                     "sparse-causal attention: needs Lk = 2 Lq, kv_batch_div = 1, NB %% frames = 0 (Lq=%d Lk=%d NB=%d frames=%d)",
                     p.Lq, p.Lk, p.NBq, p.sc_frames);
-        return dispatch_att<true>(p, big, p.dh % 16 != 0, stream);
     }
-    return dispatch_att<false>(p, big, p.dh % 16 != 0, stream);     // head dims off the 16 grid: row sums on the matrix pipe
+    const AttRoute route = att_route(p);
+    for (const AttEntry& e : ATT_TABLE)
+        if (e.route == route) return e.launch(p, stream);
+    LAVIE_CHECK(false, "attention: no kernel for head dim %d (Lq=%d Lk=%d frames=%d)", p.dh, p.Lq, p.Lk, p.sc_frames);
+    return -1;
 }
 
 }  // namespace lavie

@@ -24,8 +24,7 @@
 //    for the 32 CUs behind it.
 #include <utility>
 
-#include "common.h"
-#include "ops.h"
+#include "attention_frag.h"
 #include "profile.h"
 
 namespace lavie {
@@ -34,9 +33,6 @@ constexpr int AW_KEYS = 32;           // keys per tile
 constexpr int AW_QT = 2;              // 16-query tiles per wave
 constexpr int AW_WAVES = 4;
 constexpr int AW_QBLK = AW_WAVES * AW_QT * 16;
-constexpr float AW_RESCALE_THR = 8.0f;   // log2 units, as attention.hip
-
-typedef unsigned aw_u32x2 __attribute__((ext_vector_type(2)));
 
 template <int DH>
 struct AwTile {
@@ -51,13 +47,6 @@ struct AwTile {
     static_assert(CH == 64 || CH == 32, "head dims 512 / 256");
 };
 
-template <int OFF>
-__device__ __forceinline__ aw_u32x2 aw_read_tr16(unsigned addr) {
-    aw_u32x2 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-    return r;
-}
-
 // The file is built with the MFMA results in AGPRs (no -amdgpu-mfma-vgpr-form): at head dim 512 the O accumulators are all
 // 256 of them, and the Q fragments, scores and K / V fragments need the 256 VGPRs.  The score tiles must then stay out of
 // the AGPRs, so their MFMAs are inline asm on VGPRs: in place (vDst = SrcC), in program order, and the vector ALU reads the
@@ -68,24 +57,17 @@ __device__ __forceinline__ void aw_mfma_v(f32x4& acc, const half8_t& a, const ha
 __device__ __forceinline__ void aw_mfma_v0(f32x4& acc, const half8_t& a, const half8_t& b) {      // first k-step: C = 0
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
 }
-typedef unsigned aw_u32x4 __attribute__((ext_vector_type(4)));
-template <int OFF>
-__device__ __forceinline__ aw_u32x4 aw_read_b128(unsigned addr) {
-    aw_u32x4 r;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-    return r;
-}
 // Score product, step N = 2 ks + kt (k-step ks of key block kt): K fragments come AW_KDEPTH steps ahead through a ring of
 // registers; the counted wait leaves the younger reads in flight and the fragment passes through it.  (Left to the
 // compiler, every ds_read_b128 was followed by lgkmcnt(0) and its two MFMAs.)
 constexpr int AW_KDEPTH = 6;
 template <int DH, int N>
-__device__ __forceinline__ void aw_qk_read(const unsigned (&ka)[4], aw_u32x4 (&kf)[AW_KDEPTH]) {
+__device__ __forceinline__ void aw_qk_read(const unsigned (&ka)[4], u32x4_t (&kf)[AW_KDEPTH]) {
     constexpr int ks = N >> 1, kt = N & 1;
-    kf[N % AW_KDEPTH] = aw_read_b128<(ks >> 2) * 256 + kt * 16 * AwTile<DH>::RS>(ka[ks & 3]);
+    kf[N % AW_KDEPTH] = lds_read_b128_asm<(ks >> 2) * 256 + kt * 16 * AwTile<DH>::RS>(ka[ks & 3]);
 }
 template <int DH, int N>
-__device__ __forceinline__ void aw_qk(const unsigned (&ka)[4], aw_u32x4 (&kf)[AW_KDEPTH], f32x4 (&s)[2][AW_QT],
+__device__ __forceinline__ void aw_qk(const unsigned (&ka)[4], u32x4_t (&kf)[AW_KDEPTH], f32x4 (&s)[2][AW_QT],
                                       const half8_t (&qf)[AW_QT][AwTile<DH>::KS]) {
     constexpr int NS = 2 * AwTile<DH>::KS, ks = N >> 1, kt = N & 1;
     constexpr int LEFT = NS - 1 - N < AW_KDEPTH - 1 ? NS - 1 - N : AW_KDEPTH - 1;
@@ -102,7 +84,7 @@ __device__ __forceinline__ void aw_qk(const unsigned (&ka)[4], aw_u32x4 (&kf)[AW
     if constexpr (N + 1 < NS) aw_qk<DH, N + 1>(ka, kf, s, qf);
 }
 template <int DH, int... Ns>
-__device__ __forceinline__ void aw_qk_prime(const unsigned (&ka)[4], aw_u32x4 (&kf)[AW_KDEPTH], std::integer_sequence<int, Ns...>) {
+__device__ __forceinline__ void aw_qk_prime(const unsigned (&ka)[4], u32x4_t (&kf)[AW_KDEPTH], std::integer_sequence<int, Ns...>) {
     (aw_qk_read<DH, Ns>(ka, kf), ...);
 }
 // O accumulators: only ever touched as whole AGPR tuples by inline asm inside the key loop (see the kernel)
@@ -125,22 +107,22 @@ __device__ __forceinline__ void aw_drain_scores(f32x4 (&s)[2][AW_QT]) {
 
 // V^T fragments of output tiles dt = (G >> 1) * 8 + (G & 1) * 4 + j, j = 0..3: keys +0..15 (lo) and +16..31 (hi)
 template <int DH, int G>
-__device__ __forceinline__ void aw_read_v(const unsigned (&va)[8], aw_u32x2 (&lo)[4], aw_u32x2 (&hi)[4]) {
+__device__ __forceinline__ void aw_read_v(const unsigned (&va)[8], u32x2_t (&lo)[4], u32x2_t (&hi)[4]) {
     constexpr int OFF = (G >> 1) * 256, RS = AwTile<DH>::RS;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        lo[j] = aw_read_tr16<OFF>(va[(G & 1) * 4 + j]);
-        hi[j] = aw_read_tr16<OFF + 16 * RS>(va[(G & 1) * 4 + j]);
+        lo[j] = lds_read_tr16_asm<OFF>(va[(G & 1) * 4 + j]);
+        hi[j] = lds_read_tr16_asm<OFF + 16 * RS>(va[(G & 1) * 4 + j]);
     }
 }
 
 // group G of the P V product: the reads of group G + 1 are issued first, the counted wait leaves exactly those in flight and
 // the fragments of group G pass THROUGH it, so no MFMA that reads them can be scheduled above it
 template <int DH, int G>
-__device__ __forceinline__ void aw_pv(const unsigned (&va)[8], aw_u32x2 (&lo)[4], aw_u32x2 (&hi)[4],
+__device__ __forceinline__ void aw_pv(const unsigned (&va)[8], u32x2_t (&lo)[4], u32x2_t (&hi)[4],
                                       f32x4 (&o)[AwTile<DH>::DT][AW_QT], const half8_t (&pb)[AW_QT]) {
     constexpr bool MORE = G + 1 < AwTile<DH>::NG;
-    aw_u32x2 nlo[4], nhi[4];
+    u32x2_t nlo[4], nhi[4];
     if constexpr (MORE) {
         aw_read_v<DH, G + 1>(va, nlo, nhi);
         asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(lo[0]), "+v"(hi[0]), "+v"(lo[1]), "+v"(hi[1]), "+v"(lo[2]), "+v"(hi[2]), "+v"(lo[3]), "+v"(hi[3])::"memory");
@@ -275,7 +257,7 @@ __global__ __launch_bounds__(64 * AW_WAVES, 1) void attention_wide_kernel(const 
             unsigned kat[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) kat[j] = ka[j] + ktile;
-            aw_u32x4 kf[AW_KDEPTH];
+            u32x4_t kf[AW_KDEPTH];
             aw_qk_prime<DH>(kat, kf, std::make_integer_sequence<int, AW_KDEPTH>{});
             aw_qk<DH, 0>(kat, kf, s, qf);
         }
@@ -298,24 +280,15 @@ __global__ __launch_bounds__(64 * AW_WAVES, 1) void attention_wide_kernel(const 
         float mxl[AW_QT];
 #pragma unroll
         for (int qt = 0; qt < AW_QT; ++qt) {
-            float mx = fmaxf(fmaxf(s[0][qt][0], s[0][qt][1]), s[0][qt][2]);
-            mx = fmaxf(fmaxf(mx, s[0][qt][3]), s[1][qt][0]);
-            mx = fmaxf(fmaxf(mx, s[1][qt][1]), s[1][qt][2]);
-            mxl[qt] = fmaxf(mx, s[1][qt][3]) * sl2;          // (scale > 0)
+            mxl[qt] = att_lane_max<false>(s, qt) * sl2;          // (scale > 0)
         }
         bool grow = t == 0;
 #pragma unroll
-        for (int qt = 0; qt < AW_QT; ++qt) grow = grow || mxl[qt] > m_run[qt] + AW_RESCALE_THR;
+        for (int qt = 0; qt < AW_QT; ++qt) grow = grow || mxl[qt] > m_run[qt] + RESCALE_THR;
         if (__builtin_amdgcn_ballot_w64(grow) != 0) {
 #pragma unroll
             for (int qt = 0; qt < AW_QT; ++qt) {
-                float mx = mxl[qt];        // over the four lane groups that hold the query's 32 keys
-                const unsigned u = __float_as_uint(mx);
-                const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-                mx = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-                const unsigned v = __float_as_uint(mx);
-                const auto b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-                mx = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+                const float mx = att_group_max(mxl[qt]);        // over the four lane groups that hold the query's 32 keys
                 if (t == 0) {
                     // first tile: O and l are zero, nothing to rescale; the tile holds at least one real key, so mx is finite
                     m_run[qt] = mx;
@@ -341,13 +314,7 @@ __global__ __launch_bounds__(64 * AW_WAVES, 1) void attention_wide_kernel(const 
                     e[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kt][qt][r], sl2, nm));
                     psum += e[r];
                 }
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
-                const half2_t h0 = __builtin_convertvector((f32x2){e[0], e[1]}, half2_t);
-                const half2_t h1 = __builtin_convertvector((f32x2){e[2], e[3]}, half2_t);
-                pb[qt][kt * 4 + 0] = h0[0];
-                pb[qt][kt * 4 + 1] = h0[1];
-                pb[qt][kt * 4 + 2] = h1[0];
-                pb[qt][kt * 4 + 3] = h1[1];
+                att_pack4(pb[qt], kt, e[0], e[1], e[2], e[3]);
             }
             l_run[qt] += psum;           // per-lane partial; reduced over g at the end
         }
@@ -368,7 +335,7 @@ __global__ __launch_bounds__(64 * AW_WAVES, 1) void attention_wide_kernel(const 
             unsigned vat[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) vat[j] = va[j] + vtile;
-            aw_u32x2 lo[4], hi[4];
+            u32x2_t lo[4], hi[4];
             aw_read_v<DH, 0>(vat, lo, hi);
             aw_pv<DH, 0>(vat, lo, hi, o, pb);
         }
@@ -380,10 +347,7 @@ __global__ __launch_bounds__(64 * AW_WAVES, 1) void attention_wide_kernel(const 
 #pragma unroll
     for (int qt = 0; qt < AW_QT; ++qt) {
         __builtin_amdgcn_sched_barrier(0);      // one query tile's accumulators out of the AGPRs at a time
-        float l = l_run[qt];
-        l += __shfl_xor(l, 16, 64);
-        l += __shfl_xor(l, 32, 64);
-        const float inv = 1.0f / l;
+        const float inv = 1.0f / att_sum_groups(l_run[qt]);
         // (the lane index is taken afresh: kept from the top of the kernel for this use alone, it is spilled across the key loop)
         unsigned zero = 0;
         asm volatile("" : "+v"(zero));

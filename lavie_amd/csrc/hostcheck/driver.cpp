@@ -573,7 +573,7 @@ static void run_traces(const char* path) {
 // its integer arguments under the names of include/lavie_hip.h, 0 / 1 for each optional operand (bias, bias2, R, x2, sc1, sc2) and
 // force_tile / force_splits (default 0); the end and glue kernels' entries (timestep_sinusoid ... f16_to_f32) and the pack / bind steps
 // of the row-resident blocks (pack_geglu_mlp, bind_cross_block[_long]: pack + bind) likewise, and the blocks themselves (geglu_mlp, temporal_block,
-// cross_block[_long], proj_qkv), temporal_attention, group_norm[_affine], conv_edge_in / conv_edge_out, attention and freeu (b_milli / s_milli: the factors in thousandths) on exactly sized buffers, under rowfuse_grid / temporal_budget (default 0).  Tensors are never read.  OUT: "== <line>", then the stub's launch lines of that call, or
+// cross_block[_long], proj_qkv), temporal_attention, group_norm[_affine], conv_edge_in / conv_edge_out, attention, sparse_causal_attention and freeu (b_milli / s_milli: the factors in thousandths) on exactly sized buffers, under rowfuse_grid / temporal_budget (default 0).  Tensors are never read.  OUT: "== <line>", then the stub's launch lines of that call, or
 // stats_cs=1 / stats_rs=1 on a GEMM-family line arm the statistics sink around the call (planned first, the sink sized exactly); behind the
 // launch lines comes "## stats ..." with the plan (written or not, rows, span, sets, blocks, slots); group_norm_stats takes descriptors
 // as cs1_C / cs1_rows / cs1_nsets / cs1_set_blocks / cs1_span (cs2_ likewise) and prints "## fold=<producer-count delta>"; rowstat_finalize.
@@ -823,6 +823,13 @@ static int run_optrace(const char* in_path, const char* out_path) {
                     const size_t rq = (size_t)NB * Lq, rk = (size_t)(div > 0 ? NB / div : NB) * Lk;
                     std::vector<unsigned short> q(rq * ldq), k(rk * ldk), v(rk * ldv), o(rq * ldo);
                     rc = lavie_attention_f16(q.data(), ldq, k.data(), ldk, v.data(), ldv, o.data(), ldo, NB, Lq, Lk, heads, dh, div, 0.05f, nullptr);
+                }
+            } else if (entry == "sparse_causal_attention") {
+                const int ldq = I("ldq"), ldk = I("ldk"), ldv = I("ldv"), ldo = I("ldo"), NB = I("NB"), frames = I("frames"), D = I("D"), heads = I("heads"), dh = I("dh");
+                if (!missing) {
+                    const size_t rows = (size_t)NB * D;
+                    std::vector<unsigned short> q(rows * ldq), k(rows * ldk), v(rows * ldv), o(rows * ldo);
+                    rc = lavie_sparse_causal_attention_f16(q.data(), ldq, k.data(), ldk, v.data(), ldv, o.data(), ldo, NB, frames, D, heads, dh, 0.05f, nullptr);
                 }
             } else {
                 fprintf(stderr, "hostcheck optrace: unknown entry point '%s'\n", entry.c_str());

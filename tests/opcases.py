@@ -349,12 +349,18 @@ PACK_STEP_KERNELS = {
 ENDS_KERNELS = ("timestep_sinusoid_kernel", "gemv_kernel", "add_class_emb_silu_kernel", "conv_in_kernel", "conv_out4_kernel<5>", "conv_out4_kernel<6>",
                 "conv_out_kernel", "ln_fold_kernel", "pack_conv_in_kernel", "pack_conv3x3_kernel", "pack_geglu_vec_kernel", "copy_rows_kernel",
                 "f16_to_f32_kernel", "fill_relpos_bias_kernel")
-# the fixture's other names, by the prefix of the kernels the attention and LayerNorm cases launch (not replayed: their routes are
-# mirrored by attention_route) ...
+# the fixture's attention kernels: each must be in the replayed launches of an attention case (test_gemm_reach_host.py), whose
+# kernel is the one attention_route names (test_opcheck_host.py)
+ATTENTION_KERNELS = ("attention_dma_kernel<", "attention_kernel<", "attention_wide_kernel")
+# ... except these, which a forward launches and no per-element case does (ATT_ROUTES has the sparse-causal twins off head dim 40
+# at one query-tile count only): name -> the existing test that exercises it
+ATTENTION_NO_CASE = {
+    "attention_dma_kernel<10, 2, 3, false, true, true, 4>": "tests/test_gemm_plan_trace.py (sparse-causal head dim 80 at more than 192 tokens: in the interpolation forward's launch trace; its QT 1 twin has the per-element cases)",
+}
+# the fixture's other names, by the prefix of the kernel the LayerNorm cases launch (not replayed) ...
 # ... and the FreeU kernels of the trace's FreeU case, whose launches tests/freeucases.py mirrors (test_freeu_host.py) and whose output
 # tests/test_gpu_freeu_local.py checks per element
-COVERED_ELSEWHERE = ("attention_dma_kernel<", "attention_kernel<", "attention_wide_kernel", "layernorm_kernel", "freeu_apply_kernel",
-                     "freeu_sums_kernel")
+COVERED_ELSEWHERE = ("layernorm_kernel", "freeu_apply_kernel", "freeu_sums_kernel")
 # ... and of the GroupNorm, row-resident and temporal cases, which describe their calls: every such name of a forward's trace must be in
 # the replayed launches of a case (test_gemm_reach_host.py::test_local_kernels_of_a_forward_are_reached)
 LOCAL_KERNELS = ("gn_affine_kernel", "gn_apply_kernel<", "gn_stats_kernel<", "gn_finalize_kernel", "gn_fold_kernel", "rowstat_finalize_kernel", "geglu_mlp_kernel<", "cross_block_kernel<",
@@ -918,24 +924,37 @@ def merge_heads(t):
 
 
 def attention_route(dh, lq, lk, sc=False):
-    """The instantiation launch_attention picks (attention.hip:818-839 -> dispatch_att :797-816 -> launch_att_dma :750-777), as
+    """The instantiation launch_attention picks (attention.hip: att_route, the one function that decides, and ATT_TABLE), as
     a name: what the comment tables below and test_opcheck_host.py::test_attention_cases_reach_every_instantiation go by, and what
-    decides whether the model rounds Q' (only the V2 softmax does, attention.hip:432-440).  lk = the keys a query sees."""
+    decides whether the model rounds Q' (only the V2 softmax does: the Q' scaling in attention_dma_kernel).  lk = the keys a query sees."""
     if dh in (256, 512):
-        return "wide"                                                   # attention.hip:819, :829 -> attention_wide.hip
-    qt = 2 if lq > 64 * 3 else 1                                        # `big`, attention.hip:831
+        return "wide"                                                   # att_route: ATT_WIDE -> attention_wide.hip
+    qt = 2 if lq > 64 * 3 else 1                                        # att_route: qt
     tag = ",sc" if sc else ""
-    nch = {40: 5, 80: 10, 160: 20}.get(dh) or (None if sc else {32: 4, 64: 8, 128: 16}.get(dh))      # :798-804
+    nch = {40: 5, 80: 10, 160: 20}.get(dh) or (None if sc else {32: 4, 64: 8, 128: 16}.get(dh))      # att_route: the LDS-DMA head dims
     if nch:
-        short_keys = nch == 5 and lk <= 2 * 64                          # :759
-        if nch == 5 and qt == 2 and not short_keys and lq % 256 == 0:   # :760-762
+        short_keys = nch == 5 and lk <= 2 * 64                          # att_route: short_keys
+        if nch == 5 and qt == 2 and not short_keys and lq % 256 == 0:   # att_route: nw
             return f"dma<{nch},QT2,V2,8 waves{tag}>"
-        v2 = nch <= 10 and not short_keys                               # :756, :770
+        v2 = nch <= 10 and not short_keys                               # att_route: v2
         return f"dma<{nch},QT{qt},{'V2' if v2 else 'round-3'},4 waves{tag}>"
-    lsum = dh % 16 != 0                                                 # :836 / :838
-    dhp = 64 if dh <= 64 else 96 if dh <= 96 else 160                   # :806-815
-    ndt = ",NDT4" if dh == 64 else ""                                   # :808 (sparse-causal only: plain dh 64 is on the DMA kernel)
+    lsum = dh % 16 != 0                                                 # att_route: the register-staged kernels' LSUM
+    dhp = 64 if dh <= 64 else 96 if dh <= 96 else 160                   # att_route: dhp
+    ndt = ",NDT4" if dh == 64 else ""                                   # att_route: NDT (sparse-causal only: plain dh 64 is on the DMA kernel)
     return f"reg<{dhp},QT{qt},{'lsum' if lsum else 'sum'}{ndt}{tag}>"
+
+
+def route_kernel(route, dh):
+    """The kernel name the launch stub records for a route name: the row of attention.hip's ATT_TABLE that att_route's result selects."""
+    if route == "wide":
+        return f"attention_wide_kernel<{dh}>"
+    kind, args = route[:-1].split("<")
+    args = args.split(",")
+    sc = "true" if args[-1] == "sc" else "false"
+    if kind == "dma":
+        nch, qt, v2, nw = int(args[0]), args[1][2:], "true" if args[2] == "V2" else "false", args[3].split()[0]
+        return f"attention_dma_kernel<{nch}, {qt}, {2 if nch >= 16 else 3}, {'true' if nch == 5 else 'false'}, {sc}, {v2}, {nw}>"
+    return f"attention_kernel<{args[0]}, {args[1][2:]}, {'true' if args[2] == 'lsum' else 'false'}, {sc}, {4 if 'NDT4' in args else 0}>"
 
 
 def rounds_q(dh, lq, lk, sc=False):
@@ -944,7 +963,7 @@ def rounds_q(dh, lq, lk, sc=False):
 
 # Every instantiation ops.attention / ops.sparse_causal_attention can reach, at QT 1 and QT 2 where the plain kernels have both and
 # at one of them for the sparse-causal twins off the interpolation model's head dims (40).  Not reachable, so not listed:
-# launch_att<64, *, false, false, 4> (attention.hip:808 without SC: plain head dim 64 is taken by the DMA kernel at :803 first) and
+# attention_kernel<64, *, false, false, 4> (att_route's NDT without SC: plain head dim 64 is among the LDS-DMA head dims) and
 # dma<5,QT2,round-3,sc> (QT 2 needs lq > 192, sparse-causal has lk = 2 lq, short_keys needs lk <= 128).
 ATT_ROUTES = ([f"dma<{n},QT{qt},V2,4 waves>" for n in (4, 5, 8, 10) for qt in (1, 2)] + ["dma<5,QT2,V2,8 waves>"]
               + [f"dma<{n},QT{qt},round-3,4 waves>" for n in (5, 16, 20) for qt in (1, 2)]
@@ -1061,10 +1080,11 @@ def assert_profile(hard, qh, kh, scale, dom_batches, creep_tiles, key0=0, tile=6
 def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8, profile="unit", tile=64):
     """ops.attention on column slices of wider tensors whose other columns are NaN.  Self-attention (lk None): q | k | v are the
     thirds of one [nb*lq, 3c + 16] tensor; cross-attention: k | v are halves of a [(nb / kv_div) lk, 2c + 16] tensor.
-    Rounding points: n = 3 at head dims up to 160 — Q' = fp16(Q scale log2 e) (attention.hip:437), P before the PV product
-    (attention.hip:627-628; 241-242 in the register-staged kernel, which has no Q' rounding), the output store (attention.hip:741 /
-    300); n = 2 at head dims 256 / 512 (attention_wide.hip:345-346 and 398).  The round-3 softmax of the DMA kernel
-    (attention.hip:638-687, P at :679-680) has no Q' rounding either: the model rounds Q' where attention_route says V2; the bound
+    Rounding points: n = 3 at head dims up to 160 — Q' = fp16(Q scale log2 e) (attention_dma_kernel's `if constexpr (V2)` after
+    the Q load), P before the PV product (att_pack4 in attention_frag.h, for every kernel; the register-staged kernel has no Q'
+    rounding), the output store (the normalise-and-store epilogue of both kernels); n = 2 at head dims 256 / 512 (att_pack4 and
+    attention_wide_kernel's epilogue).  The round-3 softmax of the DMA kernel (the else arm of its `if constexpr (V2)`, P through
+    att_pack4 as well) has no Q' rounding either: the model rounds Q' where attention_route says V2; the bound
     is round_c(3) for all of them.
     profile: "unit" = N(0, 1) operands; the others (PROFILES, apply_profile) rewrite a few query rows and keys of those, laid out for
     key tiles of `tile` keys (key_tile(dh) for the cases past one workgroup; the older wide cases keep 64 = two of that kernel's tiles)."""
@@ -1110,10 +1130,10 @@ def attention_case(nb, lq, c, lk=None, kv_div=1, heads=8, profile="unit", tile=6
                 lambda: {"y": merge_heads(attn_model(*heads_of(), dh ** -0.5, rounds_q(dh, lq, lk_)))}, oc.loc_heads(heads, dh))
     case.route = attention_route(dh, lq, lk_)
     case.hard = hard
-    if wide:          # the wide kernel's launch is replayed (`hostcheck optrace`): its grid is what wide_walk mirrors
-        wq, wkv = (c + 16, 2 * c + 16) if cross else (3 * c + 16, 3 * c + 16)
-        local_calls(case, [call("attention", ldq=wq, ldk=wkv, ldv=wkv, ldo=c, NB=nb, Lq=lq, Lk=lk_, heads=heads, dh=dh, kv_batch_div=kv_div)])
-    return case
+    # the launch is replayed (`hostcheck optrace`): the kernel must be the one the route names (test_opcheck_host.py), the wide
+    # kernel's grid what wide_walk mirrors
+    wq, wkv = (c + 16, 2 * c + 16) if cross else (3 * c + 16, 3 * c + 16)
+    return local_calls(case, [call("attention", ldq=wq, ldk=wkv, ldv=wkv, ldo=c, NB=nb, Lq=lq, Lk=lk_, heads=heads, dh=dh, kv_batch_div=kv_div)])
 
 
 SELF_ATTN = [(1, 1, 256), (2, 33, 320), (1, 65, 320), (1, 129, 1280)]
@@ -1121,38 +1141,39 @@ CROSS_ATTN = [(lk, div) for lk in (1, 10, 77) for div in (1, 3)]
 WIDE_ATTN = [(1, 512), (33, 512), (65, 512), (33, 256)]
 
 # The smallest shape that reaches each instantiation, 8 heads; run under every profile that applies (profile_applies).
-# QT 2 from lq = 193 (attention.hip:831), the 8-wave kernel at lq % 256 == 0 (:762), V2 at head dim 40 from lk = 129 (:759).
-# (nb, lq, c)              head dim   instantiation (attention_route)           decided at
+# All decided in attention.hip's att_route: QT 2 from lq = 193 (qt), the 8-wave kernel at lq % 256 == 0 (nw), V2 at head dim 40
+# from lk = 129 (short_keys).
+# (nb, lq, c)              head dim   instantiation (attention_route)
 SELF_HARD = [
-    (1, 129, 320),       # 40         dma<5,QT1,V2,4 waves>   three key tiles, the last holding one key    :798, :759, :770
-    (1, 193, 320),       # 40         dma<5,QT2,V2,4 waves>                                                :831, :762
-    (2, 256, 320),       # 40         dma<5,QT2,V2,8 waves>                                                :762-763
-    (1, 65, 640),        # 80         dma<10,QT1,V2,4 waves>  (every key count: short_keys is head dim 40's)  :799, :756
+    (1, 129, 320),       # 40         dma<5,QT1,V2,4 waves>   three key tiles, the last holding one key
+    (1, 193, 320),       # 40         dma<5,QT2,V2,4 waves>
+    (2, 256, 320),       # 40         dma<5,QT2,V2,8 waves>
+    (1, 65, 640),        # 80         dma<10,QT1,V2,4 waves>  (every key count: short_keys is head dim 40's)
     (1, 193, 640),       # 80         dma<10,QT2,V2,4 waves>
-    (1, 129, 256),       # 32         dma<4,QT1,V2,4 waves>                                                :802
+    (1, 129, 256),       # 32         dma<4,QT1,V2,4 waves>
     (1, 193, 256),       # 32         dma<4,QT2,V2,4 waves>
-    (1, 129, 512),       # 64         dma<8,QT1,V2,4 waves>                                                :803
+    (1, 129, 512),       # 64         dma<8,QT1,V2,4 waves>
     (1, 193, 512),       # 64         dma<8,QT2,V2,4 waves>
-    (1, 129, 1024),      # 128        dma<16,QT1,round-3,4 waves>                                          :804, :756
+    (1, 129, 1024),      # 128        dma<16,QT1,round-3,4 waves>
     (1, 193, 1024),      # 128        dma<16,QT2,round-3,4 waves>
-    (1, 129, 1280),      # 160        dma<20,QT1,round-3,4 waves>   (its unit case is SELF_ATTN's)         :800
+    (1, 129, 1280),      # 160        dma<20,QT1,round-3,4 waves>   (its unit case is SELF_ATTN's)
     (1, 193, 1280),      # 160        dma<20,QT2,round-3,4 waves>
-    (1, 65, 192),        # 24         reg<64,QT1,lsum>                                                     :807
+    (1, 65, 192),        # 24         reg<64,QT1,lsum>
     (1, 193, 192),       # 24         reg<64,QT2,lsum>
-    (1, 65, 384),        # 48         reg<64,QT1,sum>                                                      :809
+    (1, 65, 384),        # 48         reg<64,QT1,sum>
     (1, 193, 384),       # 48         reg<64,QT2,sum>
-    (1, 65, 576),        # 72         reg<96,QT1,lsum>                                                     :812
+    (1, 65, 576),        # 72         reg<96,QT1,lsum>
     (1, 193, 576),       # 72         reg<96,QT2,lsum>   (not in the issue's list: the QT 2 form of the one above)
-    (1, 65, 768),        # 96         reg<96,QT1,sum>                                                      :813
+    (1, 65, 768),        # 96         reg<96,QT1,sum>
     (1, 193, 768),       # 96         reg<96,QT2,sum>
-    (1, 65, 1152),       # 144        reg<160,QT1,sum>                                                     :815
+    (1, 65, 1152),       # 144        reg<160,QT1,sum>
     (1, 193, 1152),      # 144        reg<160,QT2,sum>   (not in the issue's list: the QT 2 form of the one above)
 ]
 # (nb, lq, lk, c, kv_div)
 CROSS_HARD = [
-    (3, 40, 128, 320, 1), (3, 40, 128, 320, 3),     # 40   dma<5,QT1,round-3,4 waves>: lk = 2 * 64 is still short_keys       :759
+    (3, 40, 128, 320, 1), (3, 40, 128, 320, 3),     # 40   dma<5,QT1,round-3,4 waves>: lk = 2 * 64 is still short_keys
     (3, 40, 129, 320, 1), (3, 40, 129, 320, 3),     # 40   dma<5,QT1,V2,4 waves>: one key past it
-    (3, 193, 77, 320, 3),                           # 40   dma<5,QT2,round-3,4 waves>: short_keys wins over QT 2 and 8 waves  :762, :770
+    (3, 193, 77, 320, 3),                           # 40   dma<5,QT2,round-3,4 waves>: short_keys wins over QT 2 and 8 waves
     (3, 40, 77, 640, 3),                            # 80   dma<10,QT1,V2,4 waves>: V2 at 77 keys
     (1, 129, 321, 320, 1), (1, 129, 321, 640, 1),   # 40 / 80  V2, six key tiles: `creep` passes the rescale threshold twice
 ]
@@ -1175,7 +1196,7 @@ WIDE_QBLK = 128
 
 
 def wide_walk(nwg, nqblk, heads):
-    """attention_wide.hip:175-187: (batch entry, head, query block) of each blockIdx.  blockIdx % 8 labels the workgroups of one XCD;
+    """attention_wide_kernel's "workgroup order" block: (batch entry, head, query block) of each blockIdx.  blockIdx % 8 labels the workgroups of one XCD;
     label x takes a contiguous run of the list ordered (batch, head, query block), query block fastest — xq + 1 entries for the
     first xr = nwg % 8 labels, xq = nwg / 8 for the others."""
     xq, xr = nwg >> 3, nwg & 7
@@ -1256,21 +1277,21 @@ def sparse_causal_case(frames, dd, c=320, heads=8, videos=2, profile="unit"):
                 lambda: {"y": merge_heads(attn_model(*heads_of(), dh ** -0.5, rounds_q(dh, dd, 2 * dd, True)))}, oc.loc_heads(heads, dh))
     case.route = attention_route(dh, dd, 2 * dd, True)
     case.hard = hard
-    return case
+    return local_calls(case, [call("sparse_causal_attention", ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, NB=nb, frames=frames, D=dd, heads=heads, dh=dh)])
 
 
 SPARSE_CAUSAL = [(1, 5), (3, 5), (2, 65)]
 # (frames, d, c)           head dim   instantiation                                   decided at
 SC_HARD = [
-    (2, 65, 320),        # 40         dma<5,QT1,V2,4 waves,sc>  (130 keys; (1, 5) and (3, 5) above: round-3, 10 keys)   :798, :759
-    (2, 193, 320),       # 40         dma<5,QT2,V2,4 waves,sc>                                                         :831
-    (2, 256, 320),       # 40         dma<5,QT2,V2,8 waves,sc>                                                         :762
-    (2, 65, 640),        # 80         dma<10,QT1,V2,4 waves,sc>                                                        :799
-    (2, 65, 1280),       # 160        dma<20,QT1,round-3,4 waves,sc>                                                   :800
-    (2, 65, 512),        # 64         reg<64,QT1,sum,NDT4,sc>   (the DMA kernel's :803 is not compiled for SC)          :808
+    (2, 65, 320),        # 40         dma<5,QT1,V2,4 waves,sc>  (130 keys; (1, 5) and (3, 5) above: round-3, 10 keys)
+    (2, 193, 320),       # 40         dma<5,QT2,V2,4 waves,sc>
+    (2, 256, 320),       # 40         dma<5,QT2,V2,8 waves,sc>
+    (2, 65, 640),        # 80         dma<10,QT1,V2,4 waves,sc>
+    (2, 65, 1280),       # 160        dma<20,QT1,round-3,4 waves,sc>
+    (2, 65, 512),        # 64         reg<64,QT1,sum,NDT4,sc>   (ATT_TABLE has no sparse-causal DMA row at head dim 64)
     (2, 193, 512),       # 64         reg<64,QT2,sum,NDT4,sc>
     # not in the issue's list: the sparse-causal twins of the register-staged instantiations, which dispatch_att<true> selects
-    # for head dims the interpolation model does not have (24, 48, 72, 96, 128)                                       :806-815
+    # for head dims the interpolation model does not have (24, 48, 72, 96, 128)
     (2, 65, 192),        # 24         reg<64,QT1,lsum,sc>
     (2, 65, 384),        # 48         reg<64,QT1,sum,sc>
     (2, 65, 576),        # 72         reg<96,QT1,lsum,sc>

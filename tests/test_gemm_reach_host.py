@@ -67,7 +67,11 @@ def test_fixture_names_are_all_accounted_for(reach, fixture_names):
     elsewhere = {n for n in fixture_names if n.startswith(C.COVERED_ELSEWHERE + C.LOCAL_KERNELS)}
     ends = (set(C.ENDS_KERNELS) | set(C.PACK_STEP_KERNELS)) & fixture_names
     assert ends - names(reach) - set(C.PACK_STEP_KERNELS) == set(), "an end or glue kernel of a forward that no case launches"
-    accounted = required | elsewhere | set(C.NO_OPERATOR_ENTRY) | ends
+    attention = {n for n in fixture_names if n.startswith(C.ATTENTION_KERNELS)}
+    missing = attention - names(reach) - set(C.ATTENTION_NO_CASE)
+    assert len(attention) >= 15 and missing == set(), "an attention kernel of a forward that no case launches: %s" % sorted(missing)
+    assert set(C.ATTENTION_NO_CASE) <= attention and not (set(C.ATTENTION_NO_CASE) & names(reach)), "an exception that is reached, or that no forward launches, is none"
+    accounted = required | elsewhere | attention | set(C.NO_OPERATOR_ENTRY) | ends
     assert accounted == fixture_names, sorted(fixture_names - accounted)
     assert set(C.NO_OPERATOR_ENTRY) <= fixture_names and not (set(C.NO_OPERATOR_ENTRY) & elsewhere)
     assert not (set(C.NO_OPERATOR_ENTRY) & names(reach)), "a kernel listed as having no operator entry point was launched by one"

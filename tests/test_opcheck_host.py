@@ -28,7 +28,7 @@ REPLAYED = ("linear", "linear_lnfold", "linear_lnfold_geglu", "conv3x3", "conv3x
             "timestep_sinusoid", "gemv", "pack_conv_in", "conv_in", "pack_conv_out", "conv_out", "add_class_emb_silu", "fill_relpos_bias", "ln_fold",
             "pack_geglu_vec", "copy_rows", "f16_to_f32",
             "geglu_mlp", "temporal_block", "cross_block", "cross_block_long", "proj_qkv", "temporal_attention", "group_norm", "group_norm_affine",
-            "conv_edge_in", "conv_edge_out", "attention", "group_norm_stats", "rowstat_finalize")
+            "conv_edge_in", "conv_edge_out", "attention", "sparse_causal_attention", "group_norm_stats", "rowstat_finalize")
 OPTIONAL = ("bias", "bias2", "R", "x2", "sc1", "sc2", "bias_f16", "b", "tap_bias")
 DESCRIPTORS = ("cs1", "cs2")          # lavie_gn_producer_stats operands: their integer fields are described as cs1_<field> / cs2_<field>
 ALWAYS = {"conv_in": ("bias",), "conv_out": ("bias",), "temporal_attention": ("bias",)}          # operands of the new entries that are not optional there
@@ -226,6 +226,20 @@ def test_attention_cases_reach_every_instantiation():
         need = {r for r in C.ATT_ROUTES if "V2" in r and not (profile in ("creep", "mixed_wave") and "QT1" in r and "sc" in r)}
         # (sparse-causal QT 1 is d = 65: two key tiles a half, and token d - 2 lies in the first of them)
         assert need <= got, (profile, sorted(need - got))
+
+
+@pytest.mark.skipif(__import__("shutil").which("hipcc") is None, reason="hipcc not on PATH")
+def test_attention_cases_launch_the_kernel_their_route_names():
+    """opcases.attention_route against the library itself: every attention case's call is replayed on the host-only build (`hostcheck
+    optrace`), and the one kernel launch_attention launched under the stub is the instantiation the route names (route_kernel)."""
+    cases = [c for c in CASES if hasattr(c, "route")]
+    assert {c.route for c in cases} == set(C.ATT_ROUTES) and all(c.calls and len(c.calls) == 1 for c in cases)
+    reach = C.gemm_reach(cases)
+    for c in cases:
+        launches = reach[(c.name, "auto")]
+        assert launches is not None and len(launches) == 1, (c.name, launches)
+        assert C.launch_name(launches[0]) == C.route_kernel(c.route, c.calls[0][1]["dh"]), (c.name, c.route, launches[0])
+    assert len({C.launch_name(reach[(c.name, "auto")][0]) for c in cases}) == len(C.ATT_ROUTES) + 1      # "wide" is two kernels
 
 
 @pytest.fixture(scope="module")
