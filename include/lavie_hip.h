@@ -842,6 +842,59 @@ int lavie_unet_resnet_forward(lavie_unet_t h, const char* prefix, const void* x1
 int lavie_unet_transformer_forward(lavie_unet_t h, const char* prefix, void* x_inout, const void* ctx, int B, int F, int H,
                                    int W, int ctx_len, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Text encoder: transformers' CLIPTextModel (additive in ABI 8)
+ * ---------------------------------------------------------------------------------------------- */
+/* Causal self-attention over packed rows: qkv [NB L, ld] holds q | k | v of a token side by side (each heads * dh wide, head h at
+ * columns h dh of its part); row b L + i attends to rows b L + j, j <= i:  o [NB L, ldo] = softmax_j(scale q_i k_j) v_j.
+ * (CLIPAttention under the causal mask of CLIPTextTransformer.)  1 <= L <= 128, dh 32 or 64, NB >= 1, ld >= 3 heads dh, ldo >=
+ * heads dh, both multiples of 8, both tensors 16-byte aligned: anything else is refused with a message naming the argument and
+ * nothing is launched.  Fixed summation order, no atomics; a batch entry has the bits of its single-entry call. */
+int lavie_causal_attention_f16(const void* qkv, int ld, void* o, int ldo, int NB, int L, int heads, int dh, float scale, void* stream);
+/* out [B L, C] = fp16(float(tok_table[ids[r]]) + float(pos_table[r % L])), one rounding (CLIPTextEmbeddings).  ids_dev int32 [B L];
+ * tok_table fp16 [V, C]; pos_table fp16 [P, C] with P >= L, which the caller vouches for; C % 8 == 0; tables and out 16-byte
+ * aligned.  The kernel clamps an id into [0, V): no id reads outside the table.  A caller that holds the ids on the host should
+ * validate them there (the Python wrapper raises). */
+int lavie_token_embed_f16(const int* ids_dev, const void* tok_table, const void* pos_table, void* out, int B, int L, int C, int V,
+                          void* stream);
+/* x[0, n) <- act(x) in place, computed in fp32 with one rounding.  kind 0: x sigmoid(1.702 x) (CLIP's quick_gelu); kind 1: erf-GELU. */
+#define LAVIE_TEXT_ACT_QUICK_GELU 0
+#define LAVIE_TEXT_ACT_GELU 1
+int lavie_act_f16(void* x, long long n, int kind, void* stream);
+
+typedef struct lavie_text_s* lavie_text_t;
+typedef struct lavie_text_config {
+    int struct_size;       /* sizeof(lavie_text_config) as the caller declared it; any other value is refused (as lavie_unet_create) */
+    int vocab_size;
+    int hidden;            /* a multiple of 128, <= 2048 */
+    int intermediate;      /* a multiple of 128 */
+    int layers;
+    int heads;             /* hidden / heads must be 32 or 64 */
+    int max_positions;     /* rows of the position table, <= 128 */
+    int act;               /* LAVIE_TEXT_ACT_* */
+    float eps;             /* layer_norm_eps */
+} lavie_text_config;
+int lavie_text_config_size(void);
+int lavie_text_create(const lavie_text_config* cfg, lavie_text_t* out);
+int lavie_text_destroy(lavie_text_t h);
+/* The state-dict contract: names are the keys of transformers' CLIPTextModel.state_dict()
+ * (text_model.embeddings.token_embedding.weight, text_model.encoder.layers.0.self_attn.q_proj.weight, ...). */
+int lavie_text_num_params(lavie_text_t h);
+int lavie_text_param_info(lavie_text_t h, int i, const char** name, long long* numel);
+/* One fp16 tensor, borrowed until lavie_text_finalize returns and the stream drains. */
+int lavie_text_set_param(lavie_text_t h, const char* name, const void* data_f16, long long numel);
+/* Copies the weights into the handle's own allocation (q | k | v fused, biases and norm vectors fp32) and allocates the workspace of
+ * the largest call (B = 16, L = max_positions).  Allocates; not stream-ordered. */
+int lavie_text_finalize(lavie_text_t h, void* stream);
+/* Bytes of the handle's workspace that lavie_text_encode(h, ., B, L, ...) uses; -1 for a shape it refuses. */
+long long lavie_text_workspace_bytes(lavie_text_t h, int B, int L);
+/* ids_dev int32 [B, L] -> out_f16 [B, L, hidden] = last_hidden_state (the final LayerNorm applied).  1 <= B <= 16, 1 <= L <=
+ * max_positions.  Enqueues 2 + 8 layers launches on `stream`; no allocation, no synchronisation (capturable).  Two calls on the
+ * same ids agree bit for bit; the [L, hidden] block of a prompt has the same bits at every B and every position in the batch (the
+ * GEMMs run one fixed tile geometry without split-K whatever B is); rows <= i do not depend on the ids behind position i.  Ids are
+ * clamped into [0, vocab_size) by the embedding kernel. */
+int lavie_text_encode(lavie_text_t h, const int* ids_dev, int B, int L, void* out_f16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,11 @@ class GnProducerStatsC(C.Structure):    # lavie_gn_producer_stats
                 ("set_blocks", c_int), ("span", c_int)]
 
 
+class TextConfigC(C.Structure):        # lavie_text_config
+    _fields_ = [("struct_size", c_int), ("vocab_size", c_int), ("hidden", c_int), ("intermediate", c_int), ("layers", c_int),
+                ("heads", c_int), ("max_positions", c_int), ("act", c_int), ("eps", c_float)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/lavie_hip.h
 SIGNATURES = {
     "lavie_last_error": (c_char_p, []),
@@ -246,6 +251,18 @@ SIGNATURES = {
                                            c_int, c_int, c_int, c_void_p]),
     "lavie_unet_transformer_forward": (c_int, [c_void_p, c_char_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                                 c_void_p]),
+    "lavie_causal_attention_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "lavie_token_embed_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "lavie_act_f16": (c_int, [c_void_p, c_ll, c_int, c_void_p]),
+    "lavie_text_config_size": (c_int, []),
+    "lavie_text_create": (c_int, [C.POINTER(TextConfigC), C.POINTER(c_void_p)]),
+    "lavie_text_destroy": (c_int, [c_void_p]),
+    "lavie_text_num_params": (c_int, [c_void_p]),
+    "lavie_text_param_info": (c_int, [c_void_p, c_int, C.POINTER(c_char_p), C.POINTER(c_ll)]),
+    "lavie_text_set_param": (c_int, [c_void_p, c_char_p, c_void_p, c_ll]),
+    "lavie_text_finalize": (c_int, [c_void_p, c_void_p]),
+    "lavie_text_workspace_bytes": (c_ll, [c_void_p, c_int, c_int]),
+    "lavie_text_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

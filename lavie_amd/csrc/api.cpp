@@ -5,12 +5,18 @@
 
 #include "engine.h"
 #include "profile.h"
+#include "text_engine.h"
 
 using namespace lavie;
 
 struct lavie_unet_s {
     UNet net;
     explicit lavie_unet_s(const lavie_unet_config& c) : net(c) {}
+};
+
+struct lavie_text_s {
+    TextEncoder enc;
+    explicit lavie_text_s(const lavie_text_config& c) : enc(c) {}
 };
 
 static inline hipStream_t S(void* s) { return (hipStream_t)s; }
@@ -1138,6 +1144,72 @@ int lavie_unet_transformer_forward(lavie_unet_t h, const char* prefix, void* x_i
                                    int W, int ctx_len, void* stream) {
     LAVIE_CHECK(h && prefix && x_inout && ctx, "transformer_forward: null argument");
     return h->net.transformer_forward(prefix, H(x_inout), H(ctx), B, F, Hh, W, ctx_len, S(stream));
+}
+
+// ---- text encoder (text_encoder.hip, text_engine.cpp)
+int lavie_causal_attention_f16(const void* qkv, int ld, void* o, int ldo, int NB, int L, int heads, int dh, float scale, void* stream) {
+    return launch_causal_attention(H(qkv), ld, H(o), ldo, NB, L, heads, dh, scale, S(stream));
+}
+
+int lavie_token_embed_f16(const int* ids_dev, const void* tok_table, const void* pos_table, void* out, int B, int L, int C, int V,
+                          void* stream) {
+    return launch_token_embed(ids_dev, H(tok_table), H(pos_table), H(out), B, L, C, V, S(stream));
+}
+
+int lavie_act_f16(void* x, long long n, int kind, void* stream) { return launch_act(H(x), n, kind, S(stream)); }
+
+int lavie_text_config_size(void) { return (int)sizeof(lavie_text_config); }
+
+int lavie_text_create(const lavie_text_config* cfg, lavie_text_t* out) {
+    LAVIE_CHECK(cfg && out, "text_create: null argument");
+    LAVIE_CHECK(cfg->struct_size == (int)sizeof(lavie_text_config),
+                "text_create: cfg->struct_size=%d but this library's lavie_text_config has %d bytes (ABI %d): the binding's struct "
+                "layout is out of date", cfg->struct_size, (int)sizeof(lavie_text_config), LAVIE_ABI_VERSION);
+    lavie_text_s* h = new (std::nothrow) lavie_text_s(*cfg);
+    LAVIE_CHECK(h != nullptr, "text_create: out of host memory");
+    if (int rc = h->enc.validate_config()) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+int lavie_text_destroy(lavie_text_t h) {
+    delete h;
+    return 0;
+}
+
+int lavie_text_num_params(lavie_text_t h) { return h ? (int)h->enc.params().size() : -1; }
+
+int lavie_text_param_info(lavie_text_t h, int i, const char** name, long long* numel) {
+    LAVIE_CHECK(h && i >= 0 && i < (int)h->enc.params().size(), "text_param_info: index %d out of range", i);
+    if (name) *name = h->enc.params()[i].name.c_str();
+    if (numel) *numel = h->enc.params()[i].numel;
+    return 0;
+}
+
+int lavie_text_set_param(lavie_text_t h, const char* name, const void* data_f16, long long numel) {
+    LAVIE_CHECK(h && name, "text_set_param: null argument");
+    return h->enc.set_param(name, data_f16, numel);
+}
+
+int lavie_text_finalize(lavie_text_t h, void* stream) {
+    LAVIE_CHECK(h, "text_finalize: null handle");
+    return h->enc.finalize(S(stream));
+}
+
+long long lavie_text_workspace_bytes(lavie_text_t h, int B, int L) {
+    if (!h) {
+        set_error("text_workspace_bytes: null handle");
+        return -1;
+    }
+    return h->enc.workspace_bytes(B, L);
+}
+
+int lavie_text_encode(lavie_text_t h, const int* ids_dev, int B, int L, void* out_f16, void* stream) {
+    LAVIE_CHECK(h, "text_encode: null handle");
+    return h->enc.encode(ids_dev, B, L, out_f16, S(stream));
 }
 
 }  // extern "C"

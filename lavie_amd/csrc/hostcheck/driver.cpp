@@ -1043,6 +1043,96 @@ int main(int argc, char** argv) {
                                                   1, 512, 0.05f, nullptr) != 0);
         REQUIRE(lavie_hostcheck_launches() == before + 4);
     }
+    {   // the text encoder: every refusal of its three operators and of lavie_text_* names the argument and launches
+        // nothing; an accepted encode walks 2 + 8 layers launches inside the handle's own allocation (exactly sized: the sanitizers' to judge)
+        auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+        const int C = 128, I = 256, V = 50, P = 77, Lyr = 2, heads = 4;
+        std::vector<unsigned short> qkv(2 * 128 * 3 * C + 8), o(2 * 128 * C + 8), big(64 * 1024);
+        std::vector<int> ids(16 * P, 3);
+        const long before = lavie_hostcheck_launches();
+        auto att = [&](void* q, int ld, void* out, int ldo, int NB, int L, int h, int dh, float sc) {
+            return lavie_causal_attention_f16(q, ld, out, ldo, NB, L, h, dh, sc, nullptr);
+        };
+        REQUIRE(refused(att(qkv.data(), 3 * C, o.data(), C, 1, 129, heads, 32, 0.1f), "L=129"));
+        REQUIRE(refused(att(qkv.data(), 3 * C, o.data(), C, 1, 0, heads, 32, 0.1f), "L=0"));
+        REQUIRE(refused(att(qkv.data(), 3 * C, o.data(), C, 1, 77, heads, 40, 0.1f), "dh=40"));
+        REQUIRE(refused(att(qkv.data(), 3 * C, o.data(), C, 0, 77, heads, 32, 0.1f), "NB=0"));
+        REQUIRE(refused(att(qkv.data(), 3 * C - 8, o.data(), C, 1, 77, heads, 32, 0.1f), "ld=376"));
+        REQUIRE(refused(att(qkv.data(), 3 * C + 4, o.data(), C, 1, 77, heads, 32, 0.1f), "ld=388"));
+        REQUIRE(refused(att(qkv.data(), 3 * C, o.data(), C - 8, 1, 77, heads, 32, 0.1f), "ldo=120"));
+        REQUIRE(refused(att(nullptr, 3 * C, o.data(), C, 1, 77, heads, 32, 0.1f), "null"));
+        REQUIRE(refused(att(qkv.data() + 1, 3 * C, o.data(), C, 1, 77, heads, 32, 0.1f), "aligned"));
+        REQUIRE(refused(att(qkv.data(), 3 * C, o.data(), C, 1, 77, heads, 32, INFINITY), "scale"));
+        REQUIRE(refused(lavie_token_embed_f16(ids.data(), big.data(), big.data(), o.data(), 1, 4, 100, V, nullptr), "C=100"));
+        REQUIRE(refused(lavie_token_embed_f16(ids.data(), big.data(), big.data(), o.data(), 1, 4, C, 0, nullptr), "V=0"));
+        REQUIRE(refused(lavie_token_embed_f16(ids.data(), big.data(), big.data(), o.data(), 0, 4, C, V, nullptr), "B=0"));
+        REQUIRE(refused(lavie_token_embed_f16(nullptr, big.data(), big.data(), o.data(), 1, 4, C, V, nullptr), "null"));
+        REQUIRE(refused(lavie_act_f16(big.data(), 0, 0, nullptr), "n=0"));
+        REQUIRE(refused(lavie_act_f16(big.data(), 8, 2, nullptr), "kind=2"));
+        REQUIRE(refused(lavie_act_f16(nullptr, 8, 0, nullptr), "null"));
+        REQUIRE(lavie_hostcheck_launches() == before);
+        REQUIRE(att(qkv.data(), 3 * C + 8, o.data(), C + 8, 2, 128, heads, 32, 0.1f) == 0);
+        REQUIRE(lavie_token_embed_f16(ids.data(), big.data(), big.data(), o.data(), 2, 4, C, V, nullptr) == 0);
+        REQUIRE(lavie_act_f16(big.data(), 4099, 1, nullptr) == 0 && lavie_act_f16(big.data() + 1, 7, 0, nullptr) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 4);
+
+        lavie_text_config cfg = {};
+        cfg.struct_size = lavie_text_config_size();
+        cfg.vocab_size = V; cfg.hidden = C; cfg.intermediate = I; cfg.layers = Lyr; cfg.heads = heads; cfg.max_positions = P;
+        cfg.act = LAVIE_TEXT_ACT_QUICK_GELU; cfg.eps = 1e-5f;
+        lavie_text_t h = nullptr;
+        auto create_with = [&](auto&& change) { lavie_text_config c = cfg; change(c); return lavie_text_create(&c, &h); };
+        REQUIRE(refused(create_with([](lavie_text_config& c) { c.struct_size -= 4; }), "struct_size"));
+        REQUIRE(refused(create_with([](lavie_text_config& c) { c.hidden = 96; }), "hidden=96"));
+        REQUIRE(refused(create_with([](lavie_text_config& c) { c.intermediate = 200; }), "intermediate=200"));
+        REQUIRE(refused(create_with([](lavie_text_config& c) { c.layers = 0; }), "layers=0"));
+        REQUIRE(refused(create_with([](lavie_text_config& c) { c.heads = 1; }), "heads=1"));
+        REQUIRE(refused(create_with([](lavie_text_config& c) { c.max_positions = 129; }), "max_positions=129"));
+        REQUIRE(refused(create_with([](lavie_text_config& c) { c.act = 2; }), "act=2"));
+        REQUIRE(refused(create_with([](lavie_text_config& c) { c.vocab_size = 0; }), "vocab_size=0"));
+        REQUIRE(refused(create_with([](lavie_text_config& c) { c.eps = 0.f; }), "eps"));
+        REQUIRE(refused(lavie_text_create(nullptr, &h), "null") && h == nullptr);
+        REQUIRE(lavie_text_create(&cfg, &h) == 0 && h != nullptr);
+        REQUIRE(lavie_text_num_params(h) == 2 + 16 * Lyr + 2 && lavie_text_num_params(nullptr) == -1);
+        REQUIRE(refused(lavie_text_param_info(h, 99, nullptr, nullptr), "out of range"));
+        REQUIRE(refused(lavie_text_set_param(h, "text_model.nope", big.data(), 8), "unknown state-dict key"));
+        REQUIRE(refused(lavie_text_encode(h, ids.data(), 1, P, o.data(), nullptr), "not finalized"));
+        REQUIRE(refused(lavie_text_finalize(h, nullptr), "was never set"));
+        std::vector<std::vector<unsigned short>> held;
+        for (int i = 0; i < lavie_text_num_params(h); ++i) {
+            const char* name = nullptr;
+            long long numel = 0;
+            REQUIRE(lavie_text_param_info(h, i, &name, &numel) == 0 && name && numel > 0);
+            held.emplace_back((size_t)numel, (unsigned short)0x2e66);
+            REQUIRE(refused(lavie_text_set_param(h, name, held.back().data(), numel + 1), "expected"));
+            REQUIRE(refused(lavie_text_set_param(h, name, nullptr, numel), "null data"));
+            REQUIRE(lavie_text_set_param(h, name, held.back().data(), numel) == 0);
+        }
+        REQUIRE(lavie_text_finalize(h, nullptr) == 0);
+        REQUIRE(refused(lavie_text_finalize(h, nullptr), "finalized already"));
+        REQUIRE(refused(lavie_text_set_param(h, "text_model.final_layer_norm.bias", big.data(), C), "finalized"));
+        held.clear();                                                      // the loan has ended: the handle reads its own copies
+        REQUIRE(lavie_text_workspace_bytes(h, 0, P) == -1 && strstr(lavie_last_error(), "B=0"));
+        REQUIRE(lavie_text_workspace_bytes(h, 17, P) == -1 && strstr(lavie_last_error(), "B=17"));
+        REQUIRE(lavie_text_workspace_bytes(h, 1, P + 1) == -1 && strstr(lavie_last_error(), "L=78"));
+        REQUIRE(lavie_text_workspace_bytes(nullptr, 1, 1) == -1);
+        REQUIRE(lavie_text_workspace_bytes(h, 16, P) == (long long)16 * P * (2 * C + 3 * C) * 2);
+        std::vector<unsigned short> out((size_t)16 * P * C);
+        const long e0 = lavie_hostcheck_launches();
+        REQUIRE(refused(lavie_text_encode(h, ids.data(), 0, P, out.data(), nullptr), "B=0"));
+        REQUIRE(refused(lavie_text_encode(h, ids.data(), 17, P, out.data(), nullptr), "B=17"));
+        REQUIRE(refused(lavie_text_encode(h, ids.data(), 1, P + 1, out.data(), nullptr), "L=78"));
+        REQUIRE(refused(lavie_text_encode(h, nullptr, 1, P, out.data(), nullptr), "ids_dev"));
+        REQUIRE(refused(lavie_text_encode(h, ids.data(), 1, P, nullptr, nullptr), "out_f16"));
+        REQUIRE(refused(lavie_text_encode(nullptr, ids.data(), 1, P, out.data(), nullptr), "null handle"));
+        REQUIRE(lavie_hostcheck_launches() == e0);
+        for (int B : {1, 16}) {
+            const long b0 = lavie_hostcheck_launches();
+            REQUIRE(lavie_text_encode(h, ids.data(), B, P, out.data(), nullptr) == 0);
+            REQUIRE(lavie_hostcheck_launches() == b0 + 2 + 8 * Lyr);       // no split-K reduce, no second kernel at the larger batch
+        }
+        REQUIRE(lavie_text_destroy(h) == 0 && lavie_text_destroy(nullptr) == 0);
+    }
     {   // round 4 operators: widths that are not built, null tensors, a frame height that is not a whole number of 16-row tiles
         REQUIRE(lavie_proj_qkv_image_bytes(256) == 0 && lavie_proj_qkv_image_bytes(320) > 0);
         std::vector<unsigned short> x(64 * 320), wq(3 * 320 * 320), wp(320 * 320), tx(64 * 320), qkv(64 * 960);

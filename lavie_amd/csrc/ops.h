@@ -300,6 +300,18 @@ bool freq_mix_supported(int images, int F, int H, int W);
 size_t freq_mix_workspace_floats(int images, int F, int H, int W);      // 0 for an unsupported shape
 int launch_freq_mix(const FreqMixParams& p, hipStream_t stream);
 
+// ---- text_encoder.hip: what a CLIP text transformer needs beyond LayerNorm and Linear
+// Causal self-attention over packed rows qkv [NB L, ld] (q | k | v, heads side by side, each heads * dh wide): row b L + i attends to
+// rows b L + j, j <= i; o [NB L, ldo].  1 <= L <= kCausalMaxL, dh 32 or 64, ld and ldo multiples of 8, both tensors 16-byte aligned.
+// One workgroup per (batch entry, head), K and V in LDS, one pass; an entry has the bits of its single-entry call.
+constexpr int kCausalMaxL = 128;
+int launch_causal_attention(const half_t* qkv, int ld, half_t* o, int ldo, int NB, int L, int heads, int dh, float scale, hipStream_t stream);
+// out [B L, C] = fp16(float(tok[ids[r]]) + float(pos[r % L])), one rounding; ids int32 [B L] on the device, clamped into [0, V) by the
+// kernel (a caller that can see the ids validates them first); tok [V, C], pos [>= L, C]; C % 8 == 0, tables and out 16-byte aligned
+int launch_token_embed(const int* ids, const half_t* tok, const half_t* pos, half_t* out, int B, int L, int C, int V, hipStream_t stream);
+// x[0, n) <- act(x) in place, fp32 arithmetic, one rounding: kind 0 = x sigmoid(1.702 x) (CLIP's quick_gelu), 1 = erf-GELU (gelu_erf_f)
+int launch_act(half_t* x, int64_t n, int kind, hipStream_t stream);
+
 // host-only helper (no GPU): T5-style bucket of (query i, key j), attention.py:681-699
 void relpos_bucket_table(int F, int num_buckets, int max_distance, int* out);
 

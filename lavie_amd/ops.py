@@ -530,6 +530,56 @@ def attention(q, k, v, nb, lq, lk, heads, kv_batch_div=1, scale=None, out=None):
     return o
 
 
+def causal_attention(qkv, nb, l, heads, dh, scale=None, out=None):
+    """Causal self-attention over packed rows: qkv [nb*l, ld] holds q | k | v (each heads*dh wide) in its first 3*heads*dh columns;
+    row i of a batch entry attends to its rows j <= i.  out [nb*l, ldo >= heads*dh] (a new one is exactly heads*dh wide)."""
+    if not (qkv.is_cuda and qkv.dtype == torch.float16 and qkv.dim() == 2 and qkv.stride(1) == 1):
+        raise ValueError("causal_attention: qkv must be a 2-D fp16 device tensor with unit column stride")
+    if out is None:
+        out = torch.empty((max(nb * l, 0), heads * dh), dtype=torch.float16, device=qkv.device)
+    elif not (out.is_cuda and out.device == qkv.device and out.dtype == torch.float16 and out.dim() == 2 and out.stride(1) == 1):
+        raise ValueError("causal_attention: out must be a 2-D fp16 tensor with unit column stride on the device of qkv")
+    if qkv.shape[0] < nb * l or out.shape[0] < nb * l:
+        raise ValueError(f"causal_attention: nb * l = {nb * l} rows, but qkv has {qkv.shape[0]} and out {out.shape[0]}")
+    scale = dh ** -0.5 if scale is None else scale
+    _lib.check(_lib.load().lavie_causal_attention_f16(_p(qkv), qkv.stride(0), _p(out), out.stride(0), nb, l, heads, dh, float(scale),
+                                                      _stream()), "lavie_causal_attention_f16")
+    return out
+
+
+def token_embed(ids, tok_table, pos_table, out=None):
+    """CLIPTextEmbeddings: out [b*l, c] = fp16(tok_table[ids].float() + pos_table[position].float()).  ids [b, l] integers, on the
+    host or the device; validated here (an id outside [0, V) raises; the kernel would clamp it)."""
+    _chk16(tok_table, pos_table)
+    if ids.dim() != 2 or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError("token_embed: ids must be a [b, l] int32 / int64 tensor")
+    b, l = ids.shape
+    v, c = tok_table.shape
+    if l > pos_table.shape[0]:
+        raise ValueError(f"token_embed: l = {l} exceeds the {pos_table.shape[0]} rows of the position table")
+    if pos_table.shape[1] != c:
+        raise ValueError("token_embed: the two tables differ in width")
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= v):
+        raise ValueError(f"token_embed: ids must lie in [0, {v}), got [{int(ids.min())}, {int(ids.max())}]")
+    ids32 = ids.to(device=tok_table.device, dtype=torch.int32).contiguous()
+    out = _out(out, (b * l, c), torch.float16, tok_table.device, "token_embed: out")
+    _lib.check(_lib.load().lavie_token_embed_f16(_p(ids32), _p(tok_table), _p(pos_table), _p(out), b, l, c, v, _stream()),
+               "lavie_token_embed_f16")
+    return out
+
+
+ACT_KINDS = {"quick_gelu": 0, "gelu": 1}
+
+
+def act(x, kind):
+    """In place: kind "quick_gelu" = x * sigmoid(1.702 x), "gelu" = erf-GELU; fp32 arithmetic, one rounding.  Returns x."""
+    if kind not in ACT_KINDS:
+        raise ValueError(f"act: kind {kind!r} is not one of {sorted(ACT_KINDS)}")
+    _chk16(x)
+    _lib.check(_lib.load().lavie_act_f16(_p(x), x.numel(), ACT_KINDS[kind], _stream()), "lavie_act_f16")
+    return x
+
+
 def sparse_causal_attention(q, k, v, nb, frames, d, heads, scale=None, out=None):
     """SparseCausalAttention core (interpolation/models/attention.py:609-665): q/k/v [nb*d, *] per-frame rows (column
     slices of a wider tensor allowed); frame f of a video attends to [first frame || frame max(f-1, 0)] of that video."""

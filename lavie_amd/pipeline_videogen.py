@@ -59,6 +59,24 @@ class VideoGenPipeline:
                 m.to(device)
         return self
 
+    # ------------------------------------------------------------------ the text encoder on the engine
+    def enable_engine_text_encoder(self):
+        """Wraps the attached stock CLIPTextModel in a HipCLIPTextModel (its weights copied to the engine, rounded to fp16): `prompt=`
+        then runs on the engine, bit-reproducible and with a prompt's embeddings independent of the batch it is encoded in.
+        disable_engine_text_encoder puts the stock module back."""
+        from .text_encoder import HipCLIPTextModel
+        if self.text_encoder is None:
+            raise ValueError("no text_encoder attached")
+        if not isinstance(self.text_encoder, HipCLIPTextModel):
+            self.text_encoder = HipCLIPTextModel.from_stock(self.text_encoder, device=self.device)
+
+    def disable_engine_text_encoder(self):
+        from .text_encoder import HipCLIPTextModel
+        if isinstance(self.text_encoder, HipCLIPTextModel):
+            if self.text_encoder._stock is None:
+                raise ValueError("the engine text encoder was not built from a stock module: nothing to put back")
+            self.text_encoder = self.text_encoder._stock
+
     # ------------------------------------------------------------------ memory knobs of the reference pipeline object
     # base/pipelines/sample.py:72 calls enable_xformers_memory_efficient_attention() unconditionally; the diffusers base class also
     # offers attention slicing and the pipeline VAE slicing / tiling (pipeline_videogen.py:174-204).  They trade speed for memory in
