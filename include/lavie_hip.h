@@ -895,6 +895,100 @@ long long lavie_text_workspace_bytes(lavie_text_t h, int B, int L);
  * clamped into [0, vocab_size) by the embedding kernel. */
 int lavie_text_encode(lavie_text_t h, const int* ids_dev, int B, int L, void* out_f16, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Image conditioning: transformers' CLIPVisionModel and the fork's MappingNetwork (additive in ABI 8)
+ * ---------------------------------------------------------------------------------------------- */
+/* Bidirectional attention over short sequences with separate query and key lengths: o [NB Lq, ldo] = softmax_j(scale q_i k_j) v_j over
+ * j < Lk; q [NB Lq, ldq], k [NB Lk, ldk], v [NB Lk, ldv], head h at columns h dh of each.  Three pointers with their own pitches: columns
+ * of one fused q | k | v tensor (the vision tower, the mapper's self-attention) or q from one tensor and k | v from another (its
+ * cross-attention).  1 <= Lq <= 320, 1 <= Lk <= 320, dh 32 or 64, NB >= 1, every pitch a multiple of 8 and >= heads dh, every tensor
+ * 16-byte aligned: anything else is refused with a message naming the argument and nothing is launched.  Fixed summation order, no
+ * atomics; an entry has the bits of its single-entry call. */
+int lavie_short_attention_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int NB, int Lq,
+                              int Lk, int heads, int dh, float scale, void* stream);
+/* CLIPVisionEmbeddings.  pixel_values [B, 3, S, S] NCHW, x_dtype 0 = fp16, 1 = fp32 (as lavie_conv_edge_in_f16), S = G P;
+ * out [B, 1 + G^2, C] fp16: row 0 = class_embedding + position 0, row 1 + g = patch g (row-major over the grid) through the P x P
+ * stride-P convolution (no bias) + position 1 + g.  wp: the conv weight packed by lavie_pack_patch_embed_f16 ([C, 3, P, P] ->
+ * [C, lavie_patch_embed_k(P)], K = 3 P^2 zero-padded to a multiple of 64); workspace: lavie_patch_embed_workspace_bytes(B, S, P)
+ * bytes, 16-byte aligned.  C a multiple of 128 up to 2048.  Rounding points: a pixel to fp16 (fp32 input only), the store.  No read
+ * outside pixel_values; an image's rows do not depend on B. */
+int lavie_patch_embed_k(int P);
+long long lavie_patch_embed_workspace_bytes(int B, int S, int P);
+int lavie_pack_patch_embed_f16(const void* w, void* out, int C, int P, void* stream);
+int lavie_patch_embed_f16(const void* pixel_values, int x_dtype, const void* wp, const void* class_embedding, const void* pos_table,
+                          void* out, void* workspace, int B, int S, int P, int C, void* stream);
+/* x[0, n) <- max(x, 0) in place, exact: negative values become +0, -0 and +0 keep their bits (torch.relu).  The activation of
+ * nn.TransformerDecoderLayer.  (A kind of its own entry: lavie_act_f16 keeps refusing every kind but 0 and 1.) */
+#define LAVIE_TEXT_ACT_RELU 2
+int lavie_relu_f16(void* x, long long n, void* stream);
+
+typedef struct lavie_vision_s* lavie_vision_t;
+typedef struct lavie_vision_config {
+    int struct_size;       /* sizeof(lavie_vision_config) as the caller declared it; any other value is refused */
+    int hidden;            /* a multiple of 128, <= 2048 */
+    int intermediate;      /* a multiple of 128 */
+    int layers;
+    int heads;             /* hidden / heads must be 32 or 64 */
+    int image_size;        /* a multiple of patch_size; 1 + (image_size / patch_size)^2 tokens, <= 320 */
+    int patch_size;
+    int act;               /* LAVIE_TEXT_ACT_QUICK_GELU or LAVIE_TEXT_ACT_GELU */
+    float eps;             /* layer_norm_eps */
+} lavie_vision_config;
+int lavie_vision_config_size(void);
+int lavie_vision_create(const lavie_vision_config* cfg, lavie_vision_t* out);
+int lavie_vision_destroy(lavie_vision_t h);
+/* The state-dict contract: names are the keys of transformers' CLIPVisionModel.state_dict(), listed with the classic vision_model.
+ * prefix (vision_model.embeddings.class_embedding, vision_model.pre_layrnorm.weight, ...); lavie_vision_set_param takes them with or
+ * without the prefix.  post_layernorm.weight / .bias are accepted and ignored (they belong to the pooled output, which is not built)
+ * and are not listed. */
+int lavie_vision_num_params(lavie_vision_t h);
+int lavie_vision_param_info(lavie_vision_t h, int i, const char** name, long long* numel);
+/* One fp16 tensor, borrowed until lavie_vision_finalize returns and the stream drains. */
+int lavie_vision_set_param(lavie_vision_t h, const char* name, const void* data_f16, long long numel);
+/* Copies the weights into the handle's own allocation (q | k | v fused, the patch weight packed, biases and norm vectors fp32) and
+ * allocates the workspace of the largest call (B = 16).  Allocates; not stream-ordered. */
+int lavie_vision_finalize(lavie_vision_t h, void* stream);
+/* Bytes of the handle's workspace that lavie_vision_encode(h, ., ., B, ...) uses; -1 for a batch it refuses. */
+long long lavie_vision_workspace_bytes(lavie_vision_t h, int B);
+/* pixel_values [B, 3, image_size, image_size] (x_dtype 0 = fp16, 1 = fp32) -> out_f16 [B, tokens, hidden] = last_hidden_state of
+ * CLIPVisionTransformer: embeddings, pre_layrnorm, the layers; post_layernorm is NOT applied (as in transformers).  1 <= B <= 16.
+ * Enqueues 2 + B + 8 layers launches on `stream`; no allocation, no synchronisation (capturable).  Two calls agree bit for bit; an
+ * image's [tokens, hidden] block has the same bits at every B and every position in the batch. */
+int lavie_vision_encode(lavie_vision_t h, const void* pixel_values, int x_dtype, int B, void* out_f16, void* stream);
+
+typedef struct lavie_mapper_s* lavie_mapper_t;
+typedef struct lavie_mapper_config {
+    int struct_size;       /* sizeof(lavie_mapper_config) as the caller declared it; any other value is refused */
+    int input_dim;         /* width of the vision features, a multiple of 64 */
+    int output_dim;        /* width of the text embeddings, a multiple of 128, <= 2048 */
+    int layers;
+    int heads;             /* output_dim / heads must be 32 or 64 */
+    int dim_feedforward;   /* a multiple of 128 */
+    int seq_in;            /* vision tokens, <= 320 */
+    int seq_out;           /* text tokens, <= 320 */
+    float eps;             /* of the three LayerNorms of a layer */
+} lavie_mapper_config;
+int lavie_mapper_config_size(void);
+int lavie_mapper_create(const lavie_mapper_config* cfg, lavie_mapper_t* out);
+int lavie_mapper_destroy(lavie_mapper_t h);
+/* Names are the keys of MappingNetwork.state_dict() (image_proj.weight, image_pos_embedding, text_pos_embedding,
+ * transformer_decoder.layers.0.self_attn.in_proj_weight, ...).  text_proj.weight / .bias are accepted and ignored (the reference's
+ * forward never uses them) and are not listed. */
+int lavie_mapper_num_params(lavie_mapper_t h);
+int lavie_mapper_param_info(lavie_mapper_t h, int i, const char** name, long long* numel);
+int lavie_mapper_set_param(lavie_mapper_t h, const char* name, const void* data_f16, long long numel);
+int lavie_mapper_finalize(lavie_mapper_t h, void* stream);
+/* Bytes of the handle's workspace that an encode of B prompts (and up to B images) uses; -1 for a batch it refuses. */
+long long lavie_mapper_workspace_bytes(lavie_mapper_t h, int B);
+/* MappingNetwork.forward: image_feats fp16 [Bi, seq_in, input_dim], text fp16 [B, seq_out, output_dim] -> rows row0 .. row0 + seq_out - 1
+ * of out fp16 [B, ld_out_rows, output_dim]; the other rows of out are not touched.  ld_out_rows = 154, row0 = 77 puts the result
+ * behind the text tokens of a context buffer the caller has filled (ready for lavie_unet_cache_context); the plain form is
+ * ld_out_rows = seq_out, row0 = 0.  Bi is 1 (one image for every prompt) or B; 1 <= B <= 16.  Enqueues Bi + B + 13 layers launches; no
+ * allocation, no synchronisation (capturable).  Two calls agree bit for bit; a prompt's block has the same bits at every B and
+ * position, and with Bi = 1 the bits of Bi = B with the image repeated. */
+int lavie_mapper_encode(lavie_mapper_t h, const void* image_feats, int Bi, const void* text, int B, void* out, int ld_out_rows, int row0,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,9 @@ Hand-written gfx950 HIP kernels behind a C-ABI library (`lavie_amd/csrc`, `inclu
 plus the host-side mirror of the reference's `UNet3DConditionModel.forward` /
 `VideoGenPipeline` / DDPM-scheduler surface.  There is no CPU fallback: importing the compute
 entry points without the built library raises.
+
+The encoders that feed the UNet its context run on the engine as well: `lavie_amd.text_encoder.HipCLIPTextModel`,
+`lavie_amd.image_encoder.HipCLIPVisionModel` and `HipMappingNetwork` (imported on use: they need the built library).
 """
 from .config import UNetConfig, BASE_CONFIG  # noqa: F401
 

@@ -77,6 +77,16 @@ class TextConfigC(C.Structure):        # lavie_text_config
                 ("heads", c_int), ("max_positions", c_int), ("act", c_int), ("eps", c_float)]
 
 
+class VisionConfigC(C.Structure):      # lavie_vision_config
+    _fields_ = [("struct_size", c_int), ("hidden", c_int), ("intermediate", c_int), ("layers", c_int), ("heads", c_int),
+                ("image_size", c_int), ("patch_size", c_int), ("act", c_int), ("eps", c_float)]
+
+
+class MapperConfigC(C.Structure):      # lavie_mapper_config
+    _fields_ = [("struct_size", c_int), ("input_dim", c_int), ("output_dim", c_int), ("layers", c_int), ("heads", c_int),
+                ("dim_feedforward", c_int), ("seq_in", c_int), ("seq_out", c_int), ("eps", c_float)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/lavie_hip.h
 SIGNATURES = {
     "lavie_last_error": (c_char_p, []),
@@ -263,6 +273,32 @@ SIGNATURES = {
     "lavie_text_finalize": (c_int, [c_void_p, c_void_p]),
     "lavie_text_workspace_bytes": (c_ll, [c_void_p, c_int, c_int]),
     "lavie_text_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "lavie_short_attention_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                           c_int, c_float, c_void_p]),
+    "lavie_patch_embed_k": (c_int, [c_int]),
+    "lavie_patch_embed_workspace_bytes": (c_ll, [c_int, c_int, c_int]),
+    "lavie_pack_patch_embed_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "lavie_patch_embed_f16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                       c_void_p]),
+    "lavie_relu_f16": (c_int, [c_void_p, c_ll, c_void_p]),
+    "lavie_vision_config_size": (c_int, []),
+    "lavie_vision_create": (c_int, [C.POINTER(VisionConfigC), C.POINTER(c_void_p)]),
+    "lavie_vision_destroy": (c_int, [c_void_p]),
+    "lavie_vision_num_params": (c_int, [c_void_p]),
+    "lavie_vision_param_info": (c_int, [c_void_p, c_int, C.POINTER(c_char_p), C.POINTER(c_ll)]),
+    "lavie_vision_set_param": (c_int, [c_void_p, c_char_p, c_void_p, c_ll]),
+    "lavie_vision_finalize": (c_int, [c_void_p, c_void_p]),
+    "lavie_vision_workspace_bytes": (c_ll, [c_void_p, c_int]),
+    "lavie_vision_encode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "lavie_mapper_config_size": (c_int, []),
+    "lavie_mapper_create": (c_int, [C.POINTER(MapperConfigC), C.POINTER(c_void_p)]),
+    "lavie_mapper_destroy": (c_int, [c_void_p]),
+    "lavie_mapper_num_params": (c_int, [c_void_p]),
+    "lavie_mapper_param_info": (c_int, [c_void_p, c_int, C.POINTER(c_char_p), C.POINTER(c_ll)]),
+    "lavie_mapper_set_param": (c_int, [c_void_p, c_char_p, c_void_p, c_ll]),
+    "lavie_mapper_finalize": (c_int, [c_void_p, c_void_p]),
+    "lavie_mapper_workspace_bytes": (c_ll, [c_void_p, c_int]),
+    "lavie_mapper_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
 }
 
 _lib = None

@@ -4,6 +4,7 @@
 #include <new>
 
 #include "engine.h"
+#include "image_engine.h"
 #include "profile.h"
 #include "text_engine.h"
 
@@ -17,6 +18,16 @@ struct lavie_unet_s {
 struct lavie_text_s {
     TextEncoder enc;
     explicit lavie_text_s(const lavie_text_config& c) : enc(c) {}
+};
+
+struct lavie_vision_s {
+    VisionEncoder enc;
+    explicit lavie_vision_s(const lavie_vision_config& c) : enc(c) {}
+};
+
+struct lavie_mapper_s {
+    ImageMapper net;
+    explicit lavie_mapper_s(const lavie_mapper_config& c) : net(c) {}
 };
 
 static inline hipStream_t S(void* s) { return (hipStream_t)s; }
@@ -1210,6 +1221,138 @@ long long lavie_text_workspace_bytes(lavie_text_t h, int B, int L) {
 int lavie_text_encode(lavie_text_t h, const int* ids_dev, int B, int L, void* out_f16, void* stream) {
     LAVIE_CHECK(h, "text_encode: null handle");
     return h->enc.encode(ids_dev, B, L, out_f16, S(stream));
+}
+
+// ---- image conditioning (image_encoder.hip, image_engine.cpp)
+int lavie_short_attention_f16(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int NB, int Lq,
+                              int Lk, int heads, int dh, float scale, void* stream) {
+    return launch_short_attention(H(q), ldq, H(k), ldk, H(v), ldv, H(o), ldo, NB, Lq, Lk, heads, dh, scale, false, S(stream));
+}
+
+int lavie_patch_embed_k(int P) { return P >= 1 && P <= 64 ? patch_embed_k(P) : -1; }
+
+long long lavie_patch_embed_workspace_bytes(int B, int S_, int P) { return patch_embed_workspace_bytes(B, S_, P); }
+
+int lavie_pack_patch_embed_f16(const void* w, void* out, int C, int P, void* stream) {
+    return launch_pack_patch_embed(H(w), H(out), C, P, S(stream));
+}
+
+int lavie_patch_embed_f16(const void* pixel_values, int x_dtype, const void* wp, const void* class_embedding, const void* pos_table,
+                          void* out, void* workspace, int B, int S_, int P, int C, void* stream) {
+    LAVIE_CHECK(x_dtype == 0 || x_dtype == 1, "patch_embed: x_dtype=%d (0 = fp16, 1 = fp32)", x_dtype);
+    return launch_patch_embed(pixel_values, x_dtype == 1, H(wp), H(class_embedding), H(pos_table), H(out), H(workspace), B, S_, P, C,
+                              S(stream));
+}
+
+int lavie_relu_f16(void* x, long long n, void* stream) { return launch_relu(H(x), n, S(stream)); }
+
+int lavie_vision_config_size(void) { return (int)sizeof(lavie_vision_config); }
+
+int lavie_vision_create(const lavie_vision_config* cfg, lavie_vision_t* out) {
+    LAVIE_CHECK(cfg && out, "vision_create: null argument");
+    LAVIE_CHECK(cfg->struct_size == (int)sizeof(lavie_vision_config),
+                "vision_create: cfg->struct_size=%d but this library's lavie_vision_config has %d bytes (ABI %d): the binding's struct "
+                "layout is out of date", cfg->struct_size, (int)sizeof(lavie_vision_config), LAVIE_ABI_VERSION);
+    lavie_vision_s* h = new (std::nothrow) lavie_vision_s(*cfg);
+    LAVIE_CHECK(h != nullptr, "vision_create: out of host memory");
+    if (int rc = h->enc.validate_config()) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+int lavie_vision_destroy(lavie_vision_t h) {
+    delete h;
+    return 0;
+}
+
+int lavie_vision_num_params(lavie_vision_t h) { return h ? (int)h->enc.params().size() : -1; }
+
+int lavie_vision_param_info(lavie_vision_t h, int i, const char** name, long long* numel) {
+    LAVIE_CHECK(h && i >= 0 && i < (int)h->enc.params().size(), "vision_param_info: index %d out of range", i);
+    if (name) *name = h->enc.params()[i].name.c_str();
+    if (numel) *numel = h->enc.params()[i].numel;
+    return 0;
+}
+
+int lavie_vision_set_param(lavie_vision_t h, const char* name, const void* data_f16, long long numel) {
+    LAVIE_CHECK(h && name, "vision_set_param: null argument");
+    return h->enc.set_param(name, data_f16, numel);
+}
+
+int lavie_vision_finalize(lavie_vision_t h, void* stream) {
+    LAVIE_CHECK(h, "vision_finalize: null handle");
+    return h->enc.finalize(S(stream));
+}
+
+long long lavie_vision_workspace_bytes(lavie_vision_t h, int B) {
+    if (!h) {
+        set_error("vision_workspace_bytes: null handle");
+        return -1;
+    }
+    return h->enc.workspace_bytes(B);
+}
+
+int lavie_vision_encode(lavie_vision_t h, const void* pixel_values, int x_dtype, int B, void* out_f16, void* stream) {
+    LAVIE_CHECK(h, "vision_encode: null handle");
+    return h->enc.encode(pixel_values, x_dtype, B, out_f16, S(stream));
+}
+
+int lavie_mapper_config_size(void) { return (int)sizeof(lavie_mapper_config); }
+
+int lavie_mapper_create(const lavie_mapper_config* cfg, lavie_mapper_t* out) {
+    LAVIE_CHECK(cfg && out, "mapper_create: null argument");
+    LAVIE_CHECK(cfg->struct_size == (int)sizeof(lavie_mapper_config),
+                "mapper_create: cfg->struct_size=%d but this library's lavie_mapper_config has %d bytes (ABI %d): the binding's struct "
+                "layout is out of date", cfg->struct_size, (int)sizeof(lavie_mapper_config), LAVIE_ABI_VERSION);
+    lavie_mapper_s* h = new (std::nothrow) lavie_mapper_s(*cfg);
+    LAVIE_CHECK(h != nullptr, "mapper_create: out of host memory");
+    if (int rc = h->net.validate_config()) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+int lavie_mapper_destroy(lavie_mapper_t h) {
+    delete h;
+    return 0;
+}
+
+int lavie_mapper_num_params(lavie_mapper_t h) { return h ? (int)h->net.params().size() : -1; }
+
+int lavie_mapper_param_info(lavie_mapper_t h, int i, const char** name, long long* numel) {
+    LAVIE_CHECK(h && i >= 0 && i < (int)h->net.params().size(), "mapper_param_info: index %d out of range", i);
+    if (name) *name = h->net.params()[i].name.c_str();
+    if (numel) *numel = h->net.params()[i].numel;
+    return 0;
+}
+
+int lavie_mapper_set_param(lavie_mapper_t h, const char* name, const void* data_f16, long long numel) {
+    LAVIE_CHECK(h && name, "mapper_set_param: null argument");
+    return h->net.set_param(name, data_f16, numel);
+}
+
+int lavie_mapper_finalize(lavie_mapper_t h, void* stream) {
+    LAVIE_CHECK(h, "mapper_finalize: null handle");
+    return h->net.finalize(S(stream));
+}
+
+long long lavie_mapper_workspace_bytes(lavie_mapper_t h, int B) {
+    if (!h) {
+        set_error("mapper_workspace_bytes: null handle");
+        return -1;
+    }
+    return h->net.workspace_bytes(B);
+}
+
+int lavie_mapper_encode(lavie_mapper_t h, const void* image_feats, int Bi, const void* text, int B, void* out, int ld_out_rows, int row0,
+                        void* stream) {
+    LAVIE_CHECK(h, "mapper_encode: null handle");
+    return h->net.encode(image_feats, Bi, text, B, out, ld_out_rows, row0, S(stream));
 }
 
 }  // extern "C"

@@ -1133,6 +1133,177 @@ int main(int argc, char** argv) {
         }
         REQUIRE(lavie_text_destroy(h) == 0 && lavie_text_destroy(nullptr) == 0);
     }
+    {   // image conditioning: every refusal of the new operators and of lavie_vision_* / lavie_mapper_* names the
+        // argument and launches nothing; accepted encodes walk their launches inside the handles' own, exactly sized allocations
+        auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+        const int C = 128;
+        std::vector<unsigned short> q(2 * 320 * 3 * C + 8), o(2 * 320 * C + 8), big(64 * 1024);
+        const long before = lavie_hostcheck_launches();
+        auto att = [&](void* qp, int ldq, int ldk, int ldv, int ldo, int NB, int Lq, int Lk, int h, int dh, float sc) {
+            return lavie_short_attention_f16(qp, ldq, q.data() + C, ldk, q.data() + 2 * C, ldv, o.data(), ldo, NB, Lq, Lk, h, dh, sc, nullptr);
+        };
+        REQUIRE(refused(att(q.data(), 3 * C, 3 * C, 3 * C, C, 1, 321, 77, 4, 32, 0.1f), "Lq=321"));
+        REQUIRE(refused(att(q.data(), 3 * C, 3 * C, 3 * C, C, 1, 77, 321, 4, 32, 0.1f), "Lk=321"));
+        REQUIRE(refused(att(q.data(), 3 * C, 3 * C, 3 * C, C, 1, 77, 0, 4, 32, 0.1f), "Lk=0"));
+        REQUIRE(refused(att(q.data(), 3 * C, 3 * C, 3 * C, C, 1, 0, 77, 4, 32, 0.1f), "Lq=0"));
+        REQUIRE(refused(att(q.data(), 3 * C, 3 * C, 3 * C, C, 1, 77, 77, 4, 40, 0.1f), "dh=40"));
+        REQUIRE(refused(att(q.data(), 3 * C, 3 * C, 3 * C, C, 0, 77, 77, 4, 32, 0.1f), "NB=0"));
+        REQUIRE(refused(att(q.data(), 3 * C + 4, 3 * C, 3 * C, C, 1, 77, 77, 4, 32, 0.1f), "ldq=388"));
+        REQUIRE(refused(att(q.data(), 3 * C, C - 8, 3 * C, C, 1, 77, 77, 4, 32, 0.1f), "ldk=120"));
+        REQUIRE(refused(att(q.data(), 3 * C, 3 * C, 3 * C + 2, C, 1, 77, 77, 4, 32, 0.1f), "ldv=386"));
+        REQUIRE(refused(att(q.data(), 3 * C, 3 * C, 3 * C, C + 4, 1, 77, 77, 4, 32, 0.1f), "ldo=132"));
+        REQUIRE(refused(att(nullptr, 3 * C, 3 * C, 3 * C, C, 1, 77, 77, 4, 32, 0.1f), "null"));
+        REQUIRE(refused(att(q.data() + 1, 3 * C, 3 * C, 3 * C, C, 1, 77, 77, 4, 32, 0.1f), "aligned"));
+        REQUIRE(refused(att(q.data(), 3 * C, 3 * C, 3 * C, C, 1, 77, 77, 4, 32, INFINITY), "scale"));
+        REQUIRE(refused(lavie_relu_f16(big.data(), 0, nullptr), "n=0") && refused(lavie_relu_f16(nullptr, 8, nullptr), "null"));
+        REQUIRE(lavie_patch_embed_k(14) == 640 && lavie_patch_embed_k(16) == 768 && lavie_patch_embed_k(0) == -1);
+        REQUIRE(lavie_patch_embed_workspace_bytes(2, 56, 14) == 2 * 16 * 640 * 2 && lavie_patch_embed_workspace_bytes(1, 57, 14) == -1);
+        std::vector<float> px(2 * 3 * 56 * 56);
+        std::vector<unsigned short> wp(C * 640), emb(2 * 17 * C), cols(2 * 16 * 640);
+        auto pe = [&](void* x, int dt, int B, int S, int P, int Cc) {
+            return lavie_patch_embed_f16(x, dt, wp.data(), big.data(), big.data(), emb.data(), cols.data(), B, S, P, Cc, nullptr);
+        };
+        REQUIRE(refused(pe(px.data(), 2, 2, 56, 14, C), "x_dtype=2"));
+        REQUIRE(refused(pe(px.data(), 1, 0, 56, 14, C), "B=0"));
+        REQUIRE(refused(pe(px.data(), 1, 2, 57, 14, C), "S=57"));
+        REQUIRE(refused(pe(px.data(), 1, 2, 56, 0, C), "P=0"));
+        REQUIRE(refused(pe(px.data(), 1, 2, 56, 14, 96), "C=96"));
+        REQUIRE(refused(pe(nullptr, 1, 2, 56, 14, C), "null"));
+        REQUIRE(refused(lavie_pack_patch_embed_f16(big.data(), wp.data(), 96, 14, nullptr), "C=96"));
+        REQUIRE(lavie_hostcheck_launches() == before);
+        REQUIRE(att(q.data(), 3 * C + 8, 3 * C + 8, 3 * C + 8, C + 8, 2, 319, 320, 4, 32, 0.1f) == 0);
+        REQUIRE(lavie_relu_f16(big.data(), 4099, nullptr) == 0 && lavie_relu_f16(big.data() + 1, 7, nullptr) == 0);
+        REQUIRE(lavie_pack_patch_embed_f16(big.data(), wp.data(), C, 14, nullptr) == 0);
+        REQUIRE(pe(px.data(), 1, 2, 56, 14, C) == 0);                      // the gather + one GEMM per image
+        REQUIRE(lavie_hostcheck_launches() == before + 1 + 2 + 1 + 1 + 2);
+
+        const int I = 256, Lyr = 2, heads = 4, T = 17;
+        lavie_vision_config vc = {};
+        vc.struct_size = lavie_vision_config_size();
+        vc.hidden = C; vc.intermediate = I; vc.layers = Lyr; vc.heads = heads; vc.image_size = 56; vc.patch_size = 14;
+        vc.act = LAVIE_TEXT_ACT_QUICK_GELU; vc.eps = 1e-5f;
+        lavie_vision_t vh = nullptr;
+        auto vcreate = [&](auto&& change) { lavie_vision_config c = vc; change(c); return lavie_vision_create(&c, &vh); };
+        REQUIRE(refused(vcreate([](lavie_vision_config& c) { c.struct_size -= 4; }), "struct_size"));
+        REQUIRE(refused(vcreate([](lavie_vision_config& c) { c.hidden = 96; }), "hidden=96"));
+        REQUIRE(refused(vcreate([](lavie_vision_config& c) { c.intermediate = 200; }), "intermediate=200"));
+        REQUIRE(refused(vcreate([](lavie_vision_config& c) { c.layers = 0; }), "layers=0"));
+        REQUIRE(refused(vcreate([](lavie_vision_config& c) { c.heads = 1; }), "heads=1"));
+        REQUIRE(refused(vcreate([](lavie_vision_config& c) { c.image_size = 57; }), "image_size=57"));
+        REQUIRE(refused(vcreate([](lavie_vision_config& c) { c.image_size = 336; }), "577 tokens"));
+        REQUIRE(refused(vcreate([](lavie_vision_config& c) { c.patch_size = 0; }), "patch_size=0"));
+        REQUIRE(refused(vcreate([](lavie_vision_config& c) { c.act = 2; }), "act=2"));
+        REQUIRE(refused(vcreate([](lavie_vision_config& c) { c.eps = 0.f; }), "eps"));
+        REQUIRE(refused(lavie_vision_create(nullptr, &vh), "null") && vh == nullptr);
+        REQUIRE(lavie_vision_create(&vc, &vh) == 0 && vh != nullptr);
+        REQUIRE(lavie_vision_num_params(vh) == 5 + 16 * Lyr && lavie_vision_num_params(nullptr) == -1);
+        REQUIRE(refused(lavie_vision_param_info(vh, 99, nullptr, nullptr), "out of range"));
+        REQUIRE(refused(lavie_vision_set_param(vh, "vision_model.nope", big.data(), 8), "unknown state-dict key"));
+        REQUIRE(lavie_vision_set_param(vh, "post_layernorm.weight", big.data(), C) == 0);                  // accepted and ignored,
+        REQUIRE(lavie_vision_set_param(vh, "vision_model.post_layernorm.bias", big.data(), C) == 0);       // in either spelling
+        REQUIRE(refused(lavie_vision_encode(vh, px.data(), 1, 1, emb.data(), nullptr), "not finalized"));
+        REQUIRE(refused(lavie_vision_finalize(vh, nullptr), "was never set"));
+        std::vector<std::vector<unsigned short>> held;
+        for (int i = 0; i < lavie_vision_num_params(vh); ++i) {
+            const char* name = nullptr;
+            long long numel = 0;
+            REQUIRE(lavie_vision_param_info(vh, i, &name, &numel) == 0 && name && numel > 0);
+            held.emplace_back((size_t)numel, (unsigned short)0x2e66);
+            REQUIRE(refused(lavie_vision_set_param(vh, name, held.back().data(), numel + 1), "expected"));
+            REQUIRE(refused(lavie_vision_set_param(vh, name, nullptr, numel), "null data"));
+            // every other tensor under the flat spelling of transformers 5
+            REQUIRE(lavie_vision_set_param(vh, (i & 1) ? name + strlen("vision_model.") : name, held.back().data(), numel) == 0);
+        }
+        REQUIRE(lavie_vision_finalize(vh, nullptr) == 0);
+        REQUIRE(refused(lavie_vision_finalize(vh, nullptr), "finalized already"));
+        REQUIRE(refused(lavie_vision_set_param(vh, "pre_layrnorm.bias", big.data(), C), "finalized"));
+        held.clear();
+        REQUIRE(lavie_vision_workspace_bytes(vh, 0) == -1 && strstr(lavie_last_error(), "B=0"));
+        REQUIRE(lavie_vision_workspace_bytes(vh, 17) == -1 && strstr(lavie_last_error(), "B=17"));
+        REQUIRE(lavie_vision_workspace_bytes(nullptr, 1) == -1);
+        REQUIRE(lavie_vision_workspace_bytes(vh, 16) == (long long)16 * T * (2 * C + 3 * C) * 2 + 16 * 16 * 640 * 2);
+        std::vector<float> pxl((size_t)16 * 3 * 56 * 56);
+        std::vector<unsigned short> vout((size_t)16 * T * C);
+        const long v0 = lavie_hostcheck_launches();
+        REQUIRE(refused(lavie_vision_encode(vh, pxl.data(), 1, 0, vout.data(), nullptr), "B=0"));
+        REQUIRE(refused(lavie_vision_encode(vh, pxl.data(), 1, 17, vout.data(), nullptr), "B=17"));
+        REQUIRE(refused(lavie_vision_encode(vh, pxl.data(), 3, 1, vout.data(), nullptr), "x_dtype=3"));
+        REQUIRE(refused(lavie_vision_encode(vh, nullptr, 1, 1, vout.data(), nullptr), "pixel_values"));
+        REQUIRE(refused(lavie_vision_encode(vh, pxl.data(), 1, 1, nullptr, nullptr), "out_f16"));
+        REQUIRE(refused(lavie_vision_encode(nullptr, pxl.data(), 1, 1, vout.data(), nullptr), "null handle"));
+        REQUIRE(lavie_hostcheck_launches() == v0);
+        for (int B : {1, 16}) {
+            const long b0 = lavie_hostcheck_launches();
+            REQUIRE(lavie_vision_encode(vh, pxl.data(), 1, B, vout.data(), nullptr) == 0);
+            REQUIRE(lavie_hostcheck_launches() == b0 + 2 + B + 8 * Lyr);
+        }
+        REQUIRE(lavie_vision_destroy(vh) == 0 && lavie_vision_destroy(nullptr) == 0);
+
+        const int Si = 17, So = 7, FF = 256;
+        lavie_mapper_config mc = {};
+        mc.struct_size = lavie_mapper_config_size();
+        mc.input_dim = C; mc.output_dim = C; mc.layers = Lyr; mc.heads = heads; mc.dim_feedforward = FF; mc.seq_in = Si; mc.seq_out = So;
+        mc.eps = 1e-5f;
+        lavie_mapper_t mh = nullptr;
+        auto mcreate = [&](auto&& change) { lavie_mapper_config c = mc; change(c); return lavie_mapper_create(&c, &mh); };
+        REQUIRE(refused(mcreate([](lavie_mapper_config& c) { c.struct_size += 4; }), "struct_size"));
+        REQUIRE(refused(mcreate([](lavie_mapper_config& c) { c.input_dim = 100; }), "input_dim=100"));
+        REQUIRE(refused(mcreate([](lavie_mapper_config& c) { c.output_dim = 96; }), "output_dim=96"));
+        REQUIRE(refused(mcreate([](lavie_mapper_config& c) { c.layers = 0; }), "layers=0"));
+        REQUIRE(refused(mcreate([](lavie_mapper_config& c) { c.heads = 3; }), "heads=3"));
+        REQUIRE(refused(mcreate([](lavie_mapper_config& c) { c.dim_feedforward = 200; }), "dim_feedforward=200"));
+        REQUIRE(refused(mcreate([](lavie_mapper_config& c) { c.seq_in = 321; }), "seq_in=321"));
+        REQUIRE(refused(mcreate([](lavie_mapper_config& c) { c.seq_out = 0; }), "seq_out=0"));
+        REQUIRE(refused(mcreate([](lavie_mapper_config& c) { c.eps = -1.f; }), "eps"));
+        REQUIRE(refused(lavie_mapper_create(&mc, nullptr), "null"));
+        REQUIRE(lavie_mapper_create(&mc, &mh) == 0 && mh != nullptr);
+        REQUIRE(lavie_mapper_num_params(mh) == 4 + 18 * Lyr && lavie_mapper_num_params(nullptr) == -1);
+        REQUIRE(refused(lavie_mapper_param_info(mh, 99, nullptr, nullptr), "out of range"));
+        REQUIRE(refused(lavie_mapper_set_param(mh, "nope", big.data(), 8), "unknown state-dict key"));
+        REQUIRE(lavie_mapper_set_param(mh, "text_proj.weight", big.data(), C * C) == 0 && lavie_mapper_set_param(mh, "text_proj.bias", big.data(), C) == 0);
+        REQUIRE(refused(lavie_mapper_encode(mh, big.data(), 1, big.data(), 1, vout.data(), So, 0, nullptr), "not finalized"));
+        REQUIRE(refused(lavie_mapper_finalize(mh, nullptr), "was never set"));
+        for (int i = 0; i < lavie_mapper_num_params(mh); ++i) {
+            const char* name = nullptr;
+            long long numel = 0;
+            REQUIRE(lavie_mapper_param_info(mh, i, &name, &numel) == 0 && name && numel > 0);
+            held.emplace_back((size_t)numel, (unsigned short)0x2e66);
+            REQUIRE(refused(lavie_mapper_set_param(mh, name, held.back().data(), numel - 1), "expected"));
+            REQUIRE(refused(lavie_mapper_set_param(mh, name, nullptr, numel), "null data"));
+            REQUIRE(lavie_mapper_set_param(mh, name, held.back().data(), numel) == 0);
+        }
+        REQUIRE(lavie_mapper_finalize(mh, nullptr) == 0);
+        REQUIRE(refused(lavie_mapper_finalize(mh, nullptr), "finalized already"));
+        REQUIRE(refused(lavie_mapper_set_param(mh, "image_proj.bias", big.data(), C), "finalized"));
+        held.clear();
+        REQUIRE(lavie_mapper_workspace_bytes(mh, 0) == -1 && strstr(lavie_last_error(), "B=0"));
+        REQUIRE(lavie_mapper_workspace_bytes(mh, 17) == -1 && strstr(lavie_last_error(), "B=17"));
+        REQUIRE(lavie_mapper_workspace_bytes(nullptr, 1) == -1);
+        REQUIRE(lavie_mapper_workspace_bytes(mh, 16) == (long long)16 * Si * 3 * C * 2 + (long long)16 * So * (3 * C + 3 * C) * 2);
+        std::vector<unsigned short> img((size_t)16 * Si * C), txt((size_t)16 * So * C), ctx((size_t)16 * 2 * So * C);
+        const long m0 = lavie_hostcheck_launches();
+        auto enc = [&](void* im, int Bi, void* tx, int B, void* out, int ld, int r0) {
+            return lavie_mapper_encode(mh, im, Bi, tx, B, out, ld, r0, nullptr);
+        };
+        REQUIRE(refused(enc(img.data(), 1, txt.data(), 0, ctx.data(), So, 0), "B=0"));
+        REQUIRE(refused(enc(img.data(), 1, txt.data(), 17, ctx.data(), So, 0), "B=17"));
+        REQUIRE(refused(enc(img.data(), 2, txt.data(), 3, ctx.data(), So, 0), "Bi=2"));
+        REQUIRE(refused(enc(img.data(), 0, txt.data(), 3, ctx.data(), So, 0), "Bi=0"));
+        REQUIRE(refused(enc(img.data(), 1, txt.data(), 1, ctx.data(), 2 * So, So + 1), "row0=8"));
+        REQUIRE(refused(enc(img.data(), 1, txt.data(), 1, ctx.data(), 2 * So, -1), "row0=-1"));
+        REQUIRE(refused(enc(nullptr, 1, txt.data(), 1, ctx.data(), So, 0), "image_feats"));
+        REQUIRE(refused(enc(img.data(), 1, nullptr, 1, ctx.data(), So, 0), "text is null"));
+        REQUIRE(refused(enc(img.data(), 1, txt.data(), 1, nullptr, So, 0), "out is null"));
+        REQUIRE(refused(lavie_mapper_encode(nullptr, img.data(), 1, txt.data(), 1, ctx.data(), So, 0, nullptr), "null handle"));
+        REQUIRE(lavie_hostcheck_launches() == m0);
+        for (int Bi : {1, 16}) {
+            const long b0 = lavie_hostcheck_launches();
+            REQUIRE(enc(img.data(), Bi, txt.data(), 16, ctx.data(), 2 * So, So) == 0);      // behind the text rows of a context buffer
+            REQUIRE(lavie_hostcheck_launches() == b0 + Bi + 16 + 13 * Lyr);
+        }
+        REQUIRE(enc(img.data(), 1, txt.data(), 1, ctx.data(), So, 0) == 0);
+        REQUIRE(lavie_mapper_destroy(mh) == 0 && lavie_mapper_destroy(nullptr) == 0);
+    }
     {   // round 4 operators: widths that are not built, null tensors, a frame height that is not a whole number of 16-row tiles
         REQUIRE(lavie_proj_qkv_image_bytes(256) == 0 && lavie_proj_qkv_image_bytes(320) > 0);
         std::vector<unsigned short> x(64 * 320), wq(3 * 320 * 320), wp(320 * 320), tx(64 * 320), qkv(64 * 960);

@@ -312,6 +312,28 @@ int launch_token_embed(const int* ids, const half_t* tok, const half_t* pos, hal
 // x[0, n) <- act(x) in place, fp32 arithmetic, one rounding: kind 0 = x sigmoid(1.702 x) (CLIP's quick_gelu), 1 = erf-GELU (gelu_erf_f)
 int launch_act(half_t* x, int64_t n, int kind, hipStream_t stream);
 
+// ---- image_encoder.hip: what the CLIP vision tower and the image mapper need beyond the text encoder's operators
+// Bidirectional attention over short sequences: o [NB Lq, ldo] = softmax_j(scale q_i k_j) v_j, j < Lk; q [NB Lq, ldq], k [NB Lk, ldk],
+// v [NB Lk, ldv], heads side by side in the first heads * dh columns of each.  1 <= Lq, Lk <= kShortMaxL, dh 32 or 64, pitches multiples
+// of 8, 16-byte aligned tensors.  kv_shared: every entry reads the keys and values of entry 0 (k, v hold one entry).  K and V of a head
+// in LDS, one pass; an entry has the bits of its single-entry call.
+constexpr int kShortMaxL = 320;
+int launch_short_attention(const half_t* q, int ldq, const half_t* k, int ldk, const half_t* v, int ldv, half_t* o, int ldo, int NB, int Lq,
+                           int Lk, int heads, int dh, float scale, bool kv_shared, hipStream_t stream);
+// CLIPVisionEmbeddings.  px [B, 3, S, S] NCHW (fp16 or fp32), S = G P; out [B, 1 + G^2, C]: row 0 = fp16(cls + pos[0]), row 1 + g =
+// patch g (row-major over the grid) through the bias-free P x P stride-P conv + pos[1 + g], fp32 sum, one rounding.  wp: the conv
+// weight [C, 3 P^2] zero-padded to patch_embed_k(P) columns (launch_pack_patch_embed); cols: patch_embed_workspace_bytes(B, S, P) of
+// workspace (the gathered patches).  C a multiple of 128 up to 2048.  One gather launch + one pinned GEMM per image.
+int patch_embed_k(int P);
+long long patch_embed_workspace_bytes(int B, int S, int P);      // -1 for a geometry that is refused
+int launch_pack_patch_embed(const half_t* w, half_t* out, int C, int P, hipStream_t stream);
+int launch_patch_embed(const void* px, bool px_f32, const half_t* wp, const half_t* cls, const half_t* pos, half_t* out, half_t* cols, int B,
+                       int S, int P, int C, hipStream_t stream);
+// out [B L, C] = fp16(float(x[r]) + float(pos[r % L])), one rounding; C % 8 == 0, 16-byte aligned tensors
+int launch_add_rows(const half_t* x, const half_t* pos, half_t* out, int B, int L, int C, hipStream_t stream);
+// x[0, n) <- max(x, 0) in place, exact: a negative value becomes +0, everything else keeps its bits (torch.relu)
+int launch_relu(half_t* x, int64_t n, hipStream_t stream);
+
 // host-only helper (no GPU): T5-style bucket of (query i, key j), attention.py:681-699
 void relpos_bucket_table(int F, int num_buckets, int max_distance, int* out);
 

@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "onepass_attention.h"
 #include "ops.h"
 
 namespace lavie {
@@ -33,15 +34,12 @@ namespace {
 
 constexpr int kCaKeys = kCausalMaxL;          // keys (and queries) a workgroup can hold
 constexpr int kCaVPitch = kCaKeys + 8;        // row pitch of V^T in halfs: 272 bytes, 8-byte reads at 8-byte offsets
-constexpr float kLog2e = 1.4426950408889634f;
 
 template <int DH>
 __global__ __launch_bounds__(256) void causal_attention_kernel(const half_t* __restrict__ qkv, int ld, half_t* __restrict__ o, int ldo,
                                                                int L, int heads, float scale_log2) {
     constexpr int KP = DH + 8;                // K row pitch in halfs: 144 / 80 bytes, 16-byte aligned rows
     constexpr int DC = DH / 32;               // 32-dim chunks of the QK^T contraction
-    constexpr int DT = DH / 16;               // 16-row tiles of O^T
-    constexpr int PIECES = DH / 8;            // 16-byte pieces of a head row
     __shared__ __attribute__((aligned(16))) half_t Ks[kCaKeys * KP];
     __shared__ __attribute__((aligned(16))) half_t Vt[DH * kCaVPitch];
 
@@ -51,18 +49,7 @@ __global__ __launch_bounds__(256) void causal_attention_kernel(const half_t* __r
     const int nqt = cdiv(L, 16);
     const int lpad = cdiv(L, 32) * 32;        // the PV product walks whole 32-key chunks
 
-    for (int idx = threadIdx.x; idx < lpad * PIECES; idx += 256) {
-        const int j = idx / PIECES, c8 = idx - j * PIECES;
-        half8_t kv = {0, 0, 0, 0, 0, 0, 0, 0}, vv = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (j < L) {
-            const half_t* row = base + (size_t)j * ld + c8 * 8;
-            kv = *reinterpret_cast<const half8_t*>(row + C);
-            vv = *reinterpret_cast<const half8_t*>(row + 2 * C);
-        }
-        *reinterpret_cast<half8_t*>(&Ks[j * KP + c8 * 8]) = kv;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) Vt[(c8 * 8 + e) * kCaVPitch + j] = vv[e];
-    }
+    onepass_stage_kv<DH>(Ks, Vt, kCaVPitch, base + C, ld, base + 2 * C, ld, L, lpad);
     __syncthreads();
 
     const int lane = threadIdx.x & 63, g = lane >> 4, li = lane & 15;
@@ -122,25 +109,7 @@ __global__ __launch_bounds__(256) void causal_attention_kernel(const half_t* __r
         l += __shfl_xor(l, 32, 64);
         const float inv = 1.0f / l;                                  // l >= 1: the maximum's own term
         // O^T = V^T P^T over the 32-key chunks 0 .. qt / 2
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (2 * j <= qt) {
-                    const half_t* vrow = &Vt[(16 * dt + li) * kCaVPitch + 32 * j + 4 * g];
-                    const half4_t v0 = *reinterpret_cast<const half4_t*>(vrow);
-                    const half4_t v1 = *reinterpret_cast<const half4_t*>(vrow + 16);
-                    const half8_t vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pb[j], acc, 0, 0, 0);
-                }
-            if (i < L) {
-                half4_t out;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) out[r] = (half_t)(acc[r] * inv);
-                *reinterpret_cast<half4_t*>(o + ((size_t)b * L + i) * ldo + head * DH + 16 * dt + 4 * g) = out;
-            }
-        }
+        onepass_pv_store<DH, 4>(Vt, kCaVPitch, pb, qt / 2 + 1, inv, g, li, o + ((size_t)b * L + (i < L ? i : L - 1)) * ldo + head * DH, i < L);
     }
 }
 
@@ -183,8 +152,6 @@ __global__ __launch_bounds__(256) void act_kernel(half_t* __restrict__ x, long n
         for (long i = i0; i < end; ++i) x[i] = act_one<KIND>(x[i]);
     }
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 

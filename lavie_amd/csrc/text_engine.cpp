@@ -10,8 +10,8 @@
 
 #include <math.h>
 
-#include "igemm.h"
 #include "ops.h"
+#include "pinned_linear.h"
 
 namespace lavie {
 
@@ -20,31 +20,6 @@ namespace lavie {
         int rc_ = (expr);         \
         if (rc_ != 0) return rc_; \
     } while (0)
-
-namespace {
-
-constexpr int kPinBn = 128;      // the one tile width of the encoder's GEMMs: hidden and intermediate are multiples of it
-
-size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-// C [M, N] = A [M, K] W [N, K]^T + bias (+ R, which may alias C) on the pinned plan
-int pinned_linear(const half_t* A, const half_t* W, const float* bias, const half_t* R, half_t* C, int M, int N, int K, hipStream_t s) {
-    IgemmParams p;
-    RUN(igemm_setup_linear(&p, A, K, W, K, bias, C, N, M, N, K));
-    p.R = R;
-    p.ldr = N;
-    p.splits = 1;
-    IgemmPlan plan = {};
-    plan.kernel = IGEMM_TILE;
-    plan.bn = kPinBn;
-    plan.splits = 1;
-    plan.rowstat_cols = kPinBn / 2;
-    plan.gather = false;
-    plan.epilogue = EPI_LINEAR;
-    return launch_igemm(p, plan, s);
-}
-
-}  // namespace
 
 TextEncoder::TextEncoder(const lavie_text_config& cfg) : cfg_(cfg) {
     const long long C = cfg.hidden, I = cfg.intermediate;

@@ -4,8 +4,9 @@ CLIP ViT-L/14 vision features [B, 257, 1024] are projected to the text width, gi
 12-layer post-norm transformer decoder whose queries are the prompt's text embeddings (+ their own positions).  The output
 [B, 77, 768] is appended to the prompt's embeddings: the UNet sees a 154-token context.
 
-Stock torch.nn, like the CLIP text encoder: it runs twice per video (conditional and unconditional prompt), not per
-denoising step.  Parameter names and shapes are the reference's, so the `mapper.pt` that fine_tuning.py saves loads as is."""
+Stock torch.nn: it runs twice per video (conditional and unconditional prompt), not per denoising step.  The same network on
+the engine, bit-reproducible and behind the C ABI, is lavie_amd.image_encoder.HipMappingNetwork; this module is
+its reference and the loader of its checkpoints.  Parameter names and shapes are the reference's, so the `mapper.pt` that fine_tuning.py saves loads as is."""
 from typing import Mapping, Union
 
 import torch
@@ -13,7 +14,8 @@ import torch.nn as nn
 
 
 class MappingNetwork(nn.Module):
-    def __init__(self, input_dim=1024, output_dim=768, num_layers=12, num_heads=12, seq_len_in=257, seq_len_out=77):
+    def __init__(self, input_dim=1024, output_dim=768, num_layers=12, num_heads=12, seq_len_in=257, seq_len_out=77,
+                 dim_feedforward=2048):
         super().__init__()
         self.image_proj = nn.Linear(input_dim, output_dim)
         self.text_proj = nn.Linear(output_dim, output_dim)          # built and saved by the reference; unused by forward
@@ -21,7 +23,7 @@ class MappingNetwork(nn.Module):
         self.text_pos_embedding = nn.Parameter(torch.randn(1, seq_len_out, output_dim))
         # nn.TransformerDecoderLayer defaults, as the reference builds it: post-norm, ReLU, dim_feedforward 2048, eps 1e-5,
         # sequence-first tensors; dropout is inactive in eval mode
-        layer = nn.TransformerDecoderLayer(d_model=output_dim, nhead=num_heads)
+        layer = nn.TransformerDecoderLayer(d_model=output_dim, nhead=num_heads, dim_feedforward=dim_feedforward)
         self.transformer_decoder = nn.TransformerDecoder(layer, num_layers=num_layers)
         self.eval()
 
@@ -46,7 +48,8 @@ class MappingNetwork(nn.Module):
         output_dim, input_dim = sd["image_proj.weight"].shape
         layers = {int(k.split(".")[2]) for k in sd if k.startswith("transformer_decoder.layers.")}
         net = cls(input_dim=input_dim, output_dim=output_dim, num_layers=max(layers) + 1 if layers else 0, num_heads=num_heads,
-                  seq_len_in=sd["image_pos_embedding"].shape[1], seq_len_out=sd["text_pos_embedding"].shape[1])
+                  seq_len_in=sd["image_pos_embedding"].shape[1], seq_len_out=sd["text_pos_embedding"].shape[1],
+                  dim_feedforward=sd["transformer_decoder.layers.0.linear1.weight"].shape[0] if layers else 2048)
         want = net.state_dict()
         missing = sorted(set(want) - set(sd))
         extra = sorted(set(sd) - set(want))

@@ -580,6 +580,77 @@ def act(x, kind):
     return x
 
 
+def _chk_rows16(what, *ts):
+    for t in ts:
+        if not (t.is_cuda and t.dtype == torch.float16 and t.dim() == 2 and t.stride(1) == 1):
+            raise ValueError(f"{what} must be 2-D fp16 device tensors with unit column stride")
+
+
+def short_attention(q, k, v, nb, lq, lk, heads, dh, scale=None, out=None):
+    """Bidirectional attention over short sequences (lq, lk <= 320; dh 32 / 64): q [nb*lq, *], k and v [nb*lk, *] hold their heads
+    in their first heads*dh columns and may be column slices of wider tensors, each with its own pitch (q | k | v of one fused
+    tensor, or q from one tensor and k | v from another).  out [nb*lq, ldo >= heads*dh] (a new one is exactly heads*dh wide)."""
+    _chk_rows16("short_attention: q, k and v", q, k, v)
+    if out is None:
+        out = torch.empty((max(nb * lq, 0), heads * dh), dtype=torch.float16, device=q.device)
+    else:
+        _chk_rows16("short_attention: out", out)
+    if q.shape[0] < nb * lq or out.shape[0] < nb * lq or k.shape[0] < nb * lk or v.shape[0] < nb * lk:
+        raise ValueError(f"short_attention: nb * lq = {nb * lq} query rows and nb * lk = {nb * lk} key rows, but q has {q.shape[0]}, "
+                         f"out {out.shape[0]}, k {k.shape[0]}, v {v.shape[0]}")
+    if min(q.shape[1], k.shape[1], v.shape[1], out.shape[1]) < heads * dh:
+        raise ValueError(f"short_attention: every tensor needs heads * dh = {heads * dh} columns")
+    scale = dh ** -0.5 if scale is None else scale
+    _lib.check(_lib.load().lavie_short_attention_f16(_p(q), q.stride(0), _p(k), k.stride(0), _p(v), v.stride(0), _p(out), out.stride(0),
+                                                     nb, lq, lk, heads, dh, float(scale), _stream()), "lavie_short_attention_f16")
+    return out
+
+
+def pack_patch_embed(weight):
+    """CLIPVisionEmbeddings.patch_embedding.weight [c, 3, p, p] -> [c, lavie_patch_embed_k(p)]: K = 3 p^2 zero-padded to a multiple of 64."""
+    _chk16(weight)
+    c, three, p, p2 = weight.shape
+    if three != 3 or p != p2:
+        raise ValueError(f"pack_patch_embed: weight must be [c, 3, p, p], got {tuple(weight.shape)}")
+    lib = _lib.load()
+    kp = lib.lavie_patch_embed_k(p)
+    if kp < 0:
+        raise ValueError(f"pack_patch_embed: patch size {p} is outside 1..64")
+    out = torch.empty((c, kp), dtype=torch.float16, device=weight.device)
+    _lib.check(lib.lavie_pack_patch_embed_f16(_p(weight), _p(out), c, p, _stream()), "lavie_pack_patch_embed_f16")
+    return out
+
+
+def patch_embed(pixel_values, wp, class_embedding, pos_table, patch, out=None):
+    """CLIPVisionEmbeddings: pixel_values [b, 3, s, s] (fp16 or fp32, NCHW, read in place), wp from pack_patch_embed, class_embedding
+    [c], pos_table [1 + (s/patch)^2, c] -> [b, 1 + (s/patch)^2, c] fp16; see lavie_patch_embed_f16."""
+    _chk16(wp, class_embedding, pos_table)
+    flag = _edge_dtype(pixel_values, "patch_embed: pixel_values")
+    if pixel_values.dim() != 4 or pixel_values.shape[1] != 3 or pixel_values.shape[2] != pixel_values.shape[3]:
+        raise ValueError(f"patch_embed: pixel_values must be [b, 3, s, s], got {tuple(pixel_values.shape)}")
+    b, _, s, _ = pixel_values.shape
+    c = class_embedding.numel()
+    lib = _lib.load()
+    nbytes = lib.lavie_patch_embed_workspace_bytes(b, s, patch)
+    if nbytes < 0 or patch < 1 or patch > 64:
+        raise ValueError(f"patch_embed: image size {s} is not a multiple of the patch size {patch}")
+    g = s // patch
+    if tuple(pos_table.shape) != (1 + g * g, c) or tuple(wp.shape) != (c, lib.lavie_patch_embed_k(patch)):
+        raise ValueError(f"patch_embed: pos_table must be [{1 + g * g}, {c}] and wp the pack_patch_embed image of [{c}, 3, {patch}, {patch}]")
+    ws = torch.empty(nbytes // 2, dtype=torch.float16, device=wp.device)
+    y = _out(out, (b, 1 + g * g, c), torch.float16, wp.device, "patch_embed: out")
+    _lib.check(lib.lavie_patch_embed_f16(_p(pixel_values), flag, _p(wp), _p(class_embedding), _p(pos_table), _p(y), _p(ws), b, s, patch, c,
+                                         _stream()), "lavie_patch_embed_f16")
+    return y
+
+
+def relu(x):
+    """In place: max(x, 0), exact (negative values become +0; -0, +0 and NaN keep their bits, as torch.relu).  Returns x."""
+    _chk16(x)
+    _lib.check(_lib.load().lavie_relu_f16(_p(x), x.numel(), _stream()), "lavie_relu_f16")
+    return x
+
+
 def sparse_causal_attention(q, k, v, nb, frames, d, heads, scale=None, out=None):
     """SparseCausalAttention core (interpolation/models/attention.py:609-665): q/k/v [nb*d, *] per-frame rows (column
     slices of a wider tensor allowed); frame f of a video attends to [first frame || frame max(f-1, 0)] of that video."""

@@ -10,7 +10,8 @@ PyTorch-ROCm `tokenizer`/`text_encoder`/`vae` objects to use them, or work with 
 
 Image conditioning (the fork's inference.py:248-353): with a `mapper` (lavie_amd.mapping.MappingNetwork) attached, an image
 widens each CFG half's context to `cat([text, mapper(image, text)], 1)`: 154 tokens for a 77-token prompt.  The image comes
-as `image_tensor` (through `clip_processor` + `clip_model.vision_model`, stock PyTorch) or as precomputed vision features
+as `image_tensor` (through `clip_processor` + `clip_model.vision_model`: stock PyTorch, or the engine's HipCLIPVisionModel /
+HipMappingNetwork of lavie_amd.image_encoder, see enable_engine_image_encoder) or as precomputed vision features
 `image_embeds`.  Without a mapper `image_tensor` is accepted and ignored, as before."""
 import contextlib
 from dataclasses import dataclass
@@ -123,12 +124,43 @@ class VideoGenPipeline:
     def disable_free_init(self):
         self.free_init = None
 
-    def load_mapper(self, path_or_sd, num_heads: int = 12):
+    def load_mapper(self, path_or_sd, num_heads: int = 12, engine: bool = False):
         """The fork's saved image mapper (`mapper.pt`, fine_tuning.py:701) -> self.mapper on the pipeline's device, eval mode.
-        Works with a LoRA adapter loaded as well: that pair is the fork's sampling configuration."""
+        Works with a LoRA adapter loaded as well: that pair is the fork's sampling configuration.  engine=True: the same network
+        on the engine (HipMappingNetwork) instead of torch.nn."""
         from .mapping import MappingNetwork
-        self.mapper = MappingNetwork.from_checkpoint(path_or_sd, num_heads=num_heads).to(self.device)
+        net = MappingNetwork.from_checkpoint(path_or_sd, num_heads=num_heads)      # validates keys and shapes for either form
+        if engine:
+            from .image_encoder import HipMappingNetwork
+            self.mapper = HipMappingNetwork.from_stock(net, device=self.device)
+            self.mapper._stock = net.to(self.device)
+        else:
+            self.mapper = net.to(self.device)
         return self.mapper
+
+    # ------------------------------------------------------------------ image conditioning on the engine (DESIGN.md 7.17)
+    def enable_engine_image_encoder(self):
+        """Wraps the attached stock `clip_model` (a CLIPModel or a CLIPVisionModel) and `mapper` (a MappingNetwork) in
+        HipCLIPVisionModel / HipMappingNetwork (weights copied to the engine, rounded to fp16): `image_tensor=` then runs on the
+        engine, bit-reproducible and with an image's tokens independent of the batch.  Either part may be absent or wrapped
+        already.  `clip_processor` (resize, crop, normalise) stays the caller's, as the tokenizer does.
+        disable_engine_image_encoder puts the stock objects back."""
+        from .image_encoder import HipCLIPVisionModel, HipMappingNetwork
+        if self.clip_model is None and self.mapper is None:
+            raise ValueError("no clip_model or mapper attached")
+        if self.clip_model is not None and not isinstance(self.clip_model, HipCLIPVisionModel):
+            self.clip_model = HipCLIPVisionModel.from_stock(self.clip_model, device=self.device)
+        if self.mapper is not None and not isinstance(self.mapper, HipMappingNetwork):
+            self.mapper = HipMappingNetwork.from_stock(self.mapper, device=self.device)
+
+    def disable_engine_image_encoder(self):
+        from .image_encoder import HipCLIPVisionModel, HipMappingNetwork
+        for attr, cls in (("clip_model", HipCLIPVisionModel), ("mapper", HipMappingNetwork)):
+            obj = getattr(self, attr)
+            if isinstance(obj, cls):
+                if obj._stock is None:
+                    raise ValueError(f"the engine {attr} was not built from a stock module: nothing to put back")
+                setattr(self, attr, obj._stock)
 
     def enable_xformers_memory_efficient_attention(self, attention_op=None):
         """No-op: attn1 / attn2 always run the fused online-softmax kernel (attention.hip); nothing to switch on."""
@@ -239,16 +271,25 @@ class VideoGenPipeline:
         pixels = self.clip_processor(images=image_tensor, return_tensors="pt").pixel_values
         # a CLIPModel (the fork's object) holds the tower as .vision_model; a CLIPVisionModel may be the tower itself
         vision = getattr(self.clip_model, "vision_model", self.clip_model)
-        pixels = pixels.to(device=next(vision.parameters()).device, dtype=next(vision.parameters()).dtype)
+        pixels = pixels.to(**self._home(vision))
         return vision(pixel_values=pixels).last_hidden_state.to(device=device)
+
+    @staticmethod
+    def _home(module):
+        """device and dtype a part wants its inputs in: its own .device / .dtype (the engine objects) or its first parameter's"""
+        if isinstance(getattr(module, "device", None), torch.device) and isinstance(getattr(module, "dtype", None), torch.dtype):
+            return dict(device=module.device, dtype=module.dtype)
+        param = next(module.parameters())
+        return dict(device=param.device, dtype=param.dtype)
 
     def _widen(self, embeds, image_features):
         """cat([embeds, mapper(image, embeds)], 1) (inference.py:299-306, 339-345); one image broadcasts over the prompts."""
         if image_features.shape[0] not in (1, embeds.shape[0]):
             raise ValueError(f"got {image_features.shape[0]} images for {embeds.shape[0]} prompts (expected 1 or one per prompt)")
-        img = image_features.expand(embeds.shape[0], -1, -1)
-        param = next(self.mapper.parameters())
-        mapped = self.mapper(img.to(device=param.device, dtype=param.dtype), embeds.to(device=param.device, dtype=param.dtype))
+        # the engine mapper reads one image for every prompt itself (same bits as the repeated image, one memory projection)
+        img = image_features if getattr(self.mapper, "broadcasts_image", False) else image_features.expand(embeds.shape[0], -1, -1)
+        home = self._home(self.mapper)
+        mapped = self.mapper(img.to(**home), embeds.to(**home))
         return torch.cat([embeds, mapped.to(device=embeds.device, dtype=embeds.dtype)], dim=1)
 
     def _encode_prompt(self, prompt, device, num_images_per_prompt, do_cfg, negative_prompt, prompt_embeds,
