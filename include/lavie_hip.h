@@ -989,6 +989,48 @@ long long lavie_mapper_workspace_bytes(lavie_mapper_t h, int B);
 int lavie_mapper_encode(lavie_mapper_t h, const void* image_feats, int Bi, const void* text, int B, void* out, int ld_out_rows, int row0,
                         void* stream);
 
+/* ---- Seeded engine noise (csrc/philox.h, csrc/sampler_noise.hip).  A standard normal as a pure function of (a latent's 64-bit seed,
+ * a 64-bit draw number, the element's flat index e inside ONE latent [C, F, h, w]): no generator state exists anywhere, and a latent
+ * has the same noise alone, in any batch, on any rank and under any window split.
+ *   words = Philox4x32-10(key = (lo, hi of seed), counter = (lo, hi of e >> 2, lo, hi of draw)), multipliers 0xD2511F53 / 0xCD9E8D57,
+ *   key increments 0x9E3779B9 / 0xBB67AE85; (w0, w1) give elements 4 (e >> 2) + 0, 1 and (w2, w3) give + 2, 3; for a pair (a, b)
+ *   u1 = ((a >> 8) + 1) 2^-24, u2 = (b >> 8) 2^-24, r = sqrt(-2 ln u1), first = r cos(2 pi u2), second = r sin(2 pi u2), in fp32.
+ * The stream is this library's own: no equality with torch's or any other library's generator is claimed. */
+#define LAVIE_NOISE_MAX_SEEDS 16
+/* The integer part on the host: out[4] = Philox4x32-10(key[2], counter[4]).  Needs no device. */
+int lavie_philox4x32_host(const unsigned int* key, const unsigned int* counter, unsigned int* out);
+/* out fp32 [P, per] (device): row p = elements first_element .. first_element + per - 1 of latent seeds_host[p] at `draw`.  1 <= P <=
+ * LAVIE_NOISE_MAX_SEEDS, per >= 1, first_element >= 0, first_element + per <= 2^62.  Sixteen-byte stores, eight elements per lane,
+ * when first_element % 4 == 0, per % 8 == 0 and out is 16-byte aligned; otherwise one element per lane: the same bits.  One launch,
+ * no allocation, no synchronisation (capturable); seeds_host is read before the call returns. */
+int lavie_philox_normal_f32(float* out, const unsigned long long* seeds_host, int P, long long per, long long first_element,
+                            unsigned long long draw, void* stream);
+/* The key of a step whose noise is made inside the step kernel. */
+typedef struct lavie_noise_key {
+    int struct_size;                         /* sizeof(lavie_noise_key) as the caller declared it; any other value is refused */
+    int count;                               /* latents P, 1..LAVIE_NOISE_MAX_SEEDS */
+    const unsigned long long* seeds_host;    /* [count], read before the call returns: the seeds travel as kernel arguments */
+    long long per;                           /* elements of one latent */
+    unsigned long long draw;
+} lavie_noise_key;
+/* lavie_sampler_step / lavie_cfg_sampler_step with noise[i] = the normal of (seeds[i / per], draw, i % per), read when sigma != 0: x and
+ * model_in have the bits of lavie_philox_normal_f32 (first_element 0) followed by the plain entry.  There is no noise operand; n = count
+ * per.  Like the plain entries these have no alignment rule and take their scalars as they come: eight elements per lane when per % 8
+ * == 0 and eps, x and model_in are 16-byte aligned, otherwise one, the same bits.  The known-region, table and PAG steps have no seeded
+ * form: they take the materialised tensor. */
+int lavie_sampler_step_seeded(const void* eps, float* x, void* model_in, long long n, float k_x, float k_eps, float c_x0, float c_xt,
+                              float sigma, float next_input_scale, void* stream, const lavie_noise_key* key);
+int lavie_cfg_sampler_step_seeded(const void* eps2, float* x, void* model_in2, long long n, float guidance, float k_x, float k_eps,
+                                  float c_x0, float c_xt, float sigma, float next_input_scale, void* stream, const lavie_noise_key* key);
+/* lavie_window_step for the five-coefficient family (family = 0) with the step's noise made in the kernel: the element's index is its
+ * index in the WHOLE clip [C, F, hw] (key->per = C F hw, key->count = P), so the windows do not enter it.  args->aux is not read. */
+int lavie_window_step_seeded(const lavie_window_step_args* args, const lavie_noise_key* key, void* stream);
+/* Test hook (additive, ABI unchanged): what the step launchers answer to a noise key beside an operand that has no seeded form, which
+ * no entry above can pass them.  combine 1: a known region, 2: a guidance table, 3: a perturbed part, 4: the multistep family (plain
+ * steps); 5: a guidance table, 6: the multistep family (window step).  Always non-zero with the launcher's refusal in
+ * lavie_last_error(); touches no device and launches nothing. */
+int lavie_debug_noise_key_refusal(int combine);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@ WINDOW_MAX_WINDOWS, WINDOW_MAX_LENGTH, WINDOW_MAX_COVER = 32, 64, 4      # LAVIE
 
 c_void_p, c_int, c_float, c_ll, c_char_p = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_char_p
 c_float_p = C.c_void_p      # fp32 device pointers are passed as raw addresses
+c_ull = C.c_ulonglong
+NOISE_MAX_SEEDS = 16        # LAVIE_NOISE_MAX_SEEDS: latents of one seeded launch
 
 
 class UNetConfigC(C.Structure):
@@ -45,6 +47,10 @@ class WindowStepArgsC(C.Structure):   # lavie_window_step_args
                 ("eps_host", C.POINTER(c_void_p)), ("model_in_host", C.POINTER(c_void_p)), ("x", c_float_p), ("aux", c_float_p),
                 ("guidance", c_float), ("k_x", c_float), ("k_eps", c_float), ("c_x0", c_float), ("c_xt", c_float), ("c4", c_float),
                 ("next_input_scale", c_float)]
+
+
+class NoiseKeyC(C.Structure):         # lavie_noise_key
+    _fields_ = [("struct_size", c_int), ("count", c_int), ("seeds_host", C.POINTER(c_ull)), ("per", c_ll), ("draw", c_ull)]
 
 
 class GuidanceTableArgsC(C.Structure):   # lavie_guidance_table_args
@@ -299,6 +305,14 @@ SIGNATURES = {
     "lavie_mapper_finalize": (c_int, [c_void_p, c_void_p]),
     "lavie_mapper_workspace_bytes": (c_ll, [c_void_p, c_int]),
     "lavie_mapper_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "lavie_philox4x32_host": (c_int, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "lavie_philox_normal_f32": (c_int, [c_float_p, C.POINTER(c_ull), c_int, c_ll, c_ll, c_ull, c_void_p]),
+    "lavie_sampler_step_seeded": (c_int, [c_void_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float, c_float,
+                                           c_void_p, C.POINTER(NoiseKeyC)]),
+    "lavie_cfg_sampler_step_seeded": (c_int, [c_void_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float, c_float,
+                                               c_float, c_void_p, C.POINTER(NoiseKeyC)]),
+    "lavie_window_step_seeded": (c_int, [C.POINTER(WindowStepArgsC), C.POINTER(NoiseKeyC), c_void_p]),
+    "lavie_debug_noise_key_refusal": (c_int, [c_int]),
 }
 
 _lib = None

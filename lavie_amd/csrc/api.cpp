@@ -569,7 +569,7 @@ static int check_region(const char* who, const StepArgs& a, bool mask_optional) 
 
 // scalars = false: the three plain five-coefficient entries take their scalars as they come, as they always have
 static int check_step(const char* who, const StepArgs& a, bool scalars = true) {
-    const bool aux_used = a.multistep || a.c.c4 != 0.f;     // the history is always written; the noise is read when sigma != 0
+    const bool aux_used = a.multistep || (a.c.c4 != 0.f && !a.key);     // the history is always written; the noise is read when sigma != 0 (and no key makes it)
     const void* const t[4] = {a.eps, a.x, a.model_in, aux_used ? a.aux : nullptr};
     const char* const names[4] = {"eps", "x", "model_in", a.multistep ? "x0_prev" : "noise"};
     for (int i = 0; i < 3; ++i) LAVIE_CHECK(t[i], "%s: null argument: %s is null", who, names[i]);
@@ -591,6 +591,7 @@ static int check_step(const char* who, const StepArgs& a, bool scalars = true) {
         LAVIE_CHECK(a.pag_scale >= 0.f, "%s: pag_scale=%g must be >= 0", who, (double)a.pag_scale);
     }
     // 16-byte accesses: the eight-element form of the kernel that will run.  The plain five-coefficient kernel has none; the plain
+    // seeded one (StepArgs::key) neither: it takes eight elements per lane only where its tensors are aligned.  The plain
     // multistep kernel counts as one whatever n is (its vector body is empty under guidance with n % 8 != 0, the rule was never relaxed)
     const bool vec8 = a.known ? a.inner % 8 == 0 : a.table ? a.per % 8 == 0 : a.eps_pag ? a.n % 8 == 0 : a.multistep;
     if (vec8) {
@@ -733,7 +734,7 @@ int lavie_known_blend_f32(float* x, void* model_in, int dup, long long n, float 
 
 // The fused step over overlapping frame windows (sampler_window.hip).  Everything is checked here, on the host, before a table entry
 // is dereferenced or anything is launched; each refusal names its argument.
-static int window_step(const char* who, const lavie_window_step_args* a, const float* table, void* stream) {
+static int window_step(const char* who, const lavie_window_step_args* a, const float* table, void* stream, const NoiseKey* key = nullptr) {
     LAVIE_CHECK(a, "%s: args is null", who);
     LAVIE_CHECK(a->struct_size == (int)sizeof(lavie_window_step_args),
                 "%s: args->struct_size=%d but this library's lavie_window_step_args has %d bytes: the binding's struct layout is "
@@ -773,7 +774,10 @@ static int window_step(const char* who, const lavie_window_step_args* a, const f
     LAVIE_CHECK(a->x, "%s: x is null", who);
     const StepCoef c{a->guidance, a->k_x, a->k_eps, a->c_x0, a->c_xt, a->c4};
     if (int rc = check_coefficients(who, c, a->next_input_scale, "c4")) return rc;
-    const bool aux_used = a->family == 1 || a->c4 != 0.f;
+    LAVIE_CHECK(!key || a->family == 0, "%s: family=%d: the multistep family draws no noise and takes no noise key", who, a->family);
+    LAVIE_CHECK(!key || (key->count == a->P && key->per == (long long)a->C * a->F * a->hw), "%s: key->count=%d per=%lld, the clip has P=%d "
+                "latents of C F hw=%lld elements", who, key ? key->count : 0, key ? key->per : 0ll, a->P, (long long)a->C * a->F * a->hw);
+    const bool aux_used = a->family == 1 || (a->c4 != 0.f && !key);
     LAVIE_CHECK(!aux_used || a->aux, "%s: aux is null (%s)", who, a->family == 1 ? "the multistep family's x0_prev" : "the step's noise, c4 != 0");
     // byte ranges: x, aux, then eps[w], then model_in[w]; a written range (x, aux, model_in) may overlap nothing, eps may overlap eps
     const unsigned long long clip = (unsigned long long)a->P * a->C * a->F * a->hw * 4;
@@ -820,10 +824,115 @@ static int window_step(const char* who, const lavie_window_step_args* a, const f
     p.c = c;
     p.in_scale = a->next_input_scale;
     p.table = table;
+    p.key = key;
     return launch_window_step(p, S(stream));
 }
 
 int lavie_window_step(const lavie_window_step_args* a, void* stream) { return window_step("window_step", a, nullptr, stream); }
+
+// ---- Seeded engine noise (philox.h, sampler_noise.hip).
+int lavie_philox4x32_host(const unsigned int* key, const unsigned int* counter, unsigned int* out) {
+    LAVIE_CHECK(key && counter && out, "philox4x32_host: null argument");
+    uint32_t w[4];
+    philox4x32_10(key[0], key[1], counter[0], counter[1], counter[2], counter[3], w);
+    for (int i = 0; i < 4; ++i) out[i] = w[i];
+    return 0;
+}
+
+// the caller's key -> the kernel argument; a null key or one of another layout is refused before a field is read
+static int fill_key(const char* who, const lavie_noise_key* k, NoiseKey* key) {
+    LAVIE_CHECK(k, "%s: key is null", who);
+    LAVIE_CHECK(k->struct_size == (int)sizeof(lavie_noise_key),
+                "%s: key->struct_size=%d but this library's lavie_noise_key has %d bytes: the binding's struct layout is out of date", who,
+                k->struct_size, (int)sizeof(lavie_noise_key));
+    LAVIE_CHECK(k->count >= 1 && k->count <= LAVIE_NOISE_MAX_SEEDS, "%s: key->count=%d outside 1..%d", who, k->count, LAVIE_NOISE_MAX_SEEDS);
+    LAVIE_CHECK(k->seeds_host, "%s: key->seeds_host is null", who);
+    LAVIE_CHECK(k->per >= 1 && k->per <= (1ll << 40), "%s: key->per=%lld must be in 1..2^40", who, k->per);
+    *key = NoiseKey{};
+    for (int p = 0; p < k->count; ++p) key->seed[p] = k->seeds_host[p];
+    key->draw = k->draw; key->per = k->per; key->count = k->count;
+    return 0;
+}
+
+int lavie_philox_normal_f32(float* out, const unsigned long long* seeds_host, int P, long long per, long long first_element,
+                            unsigned long long draw, void* stream) {
+    const char* who = "philox_normal";
+    LAVIE_CHECK(out, "%s: out is null", who);
+    LAVIE_CHECK(seeds_host, "%s: seeds_host is null", who);
+    LAVIE_CHECK(P >= 1 && P <= LAVIE_NOISE_MAX_SEEDS, "%s: P=%d outside 1..%d", who, P, LAVIE_NOISE_MAX_SEEDS);
+    LAVIE_CHECK(per >= 1 && per <= (1ll << 40), "%s: per=%lld must be in 1..2^40", who, per);
+    LAVIE_CHECK(first_element >= 0 && first_element <= (1ll << 62) - per, "%s: first_element=%lld must be >= 0 and first_element + per <= 2^62",
+                who, first_element);
+    LAVIE_CHECK(((uintptr_t)out & 3) == 0, "%s: out at %p is not 4-byte aligned", who, (const void*)out);
+    NoiseKey key{};
+    for (int p = 0; p < P; ++p) key.seed[p] = seeds_host[p];
+    key.draw = draw; key.per = per; key.count = P;
+    return launch_philox_normal(out, key, first_element, S(stream));
+}
+
+static int run_step_seeded(const char* who, StepArgs a, const lavie_noise_key* k, void* stream) {
+    NoiseKey key;
+    if (int rc = fill_key(who, k, &key)) return rc;
+    LAVIE_CHECK(a.n == key.count * key.per, "%s: n=%lld is not key->count=%d latents of key->per=%lld elements", who, (long long)a.n, key.count,
+                key.per);
+    a.key = &key;
+    return run_step(who, a, stream, false);        // the scalars as they come, as the plain entries these mirror take them
+}
+
+int lavie_sampler_step_seeded(const void* eps, float* x, void* model_in, long long n, float k_x, float k_eps, float c_x0, float c_xt,
+                              float sigma, float next_input_scale, void* stream, const lavie_noise_key* key) {
+    return run_step_seeded("sampler_step_seeded", step_args(false, false, eps, x, nullptr, model_in, n, 1.0f, k_x, k_eps, c_x0, c_xt, sigma,
+                                                            next_input_scale), key, stream);
+}
+
+int lavie_cfg_sampler_step_seeded(const void* eps2, float* x, void* model_in2, long long n, float guidance, float k_x, float k_eps,
+                                  float c_x0, float c_xt, float sigma, float next_input_scale, void* stream, const lavie_noise_key* key) {
+    return run_step_seeded("cfg_sampler_step_seeded", step_args(false, true, eps2, x, nullptr, model_in2, n, guidance, k_x, k_eps, c_x0, c_xt,
+                                                                sigma, next_input_scale), key, stream);
+}
+
+int lavie_window_step_seeded(const lavie_window_step_args* a, const lavie_noise_key* k, void* stream) {
+    NoiseKey key;
+    if (int rc = fill_key("window_step_seeded", k, &key)) return rc;
+    return window_step("window_step_seeded", a, nullptr, stream, &key);
+}
+
+// Test hook: the launchers' own refusals of a noise key beside an operand that has no seeded form.  No C entry can form these
+// combinations (the seeded entries take no region, table or perturbed part), so the hook builds the launcher's record itself and
+// hands back what the launcher answers.  The key holds no latent (count 0): whatever the launcher decides, nothing is launched.
+int lavie_debug_noise_key_refusal(int combine) {
+    static float f32[8];
+    static half_t f16[8];
+    NoiseKey key{};
+    key.per = 8;
+    if (combine >= 1 && combine <= 4) {
+        StepArgs a{};
+        KnownOperands k{f32, f32, f32, 1.f, 0.f};
+        a.cfg = true; a.eps = f16; a.x = f32; a.model_in = f16; a.n = 8; a.c = StepCoef{7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.f}; a.in_scale = 1.f;
+        a.key = &key;
+        if (combine == 1) { a.known = &k; a.channels = 1; a.inner = 8; }
+        if (combine == 2) { a.table = f32; a.per = 8; }
+        if (combine == 3) a.eps_pag = f16;
+        if (combine == 4) { a.multistep = true; a.aux = f32; }
+        return launch_step(a, nullptr);
+    }
+    if (combine == 5 || combine == 6) {
+        static const int starts[1] = {0};
+        static const float profile[1] = {1.f};
+        const half_t* eps[1] = {f16};
+        half_t* model_in[1] = {f16};
+        WindowStepParams p{};
+        p.cfg = true; p.P = 1; p.C = 1; p.F = 1; p.hw = 8; p.W = 1; p.L = 1;
+        p.starts = starts; p.profile = profile; p.eps = eps; p.model_in = model_in; p.x = f32; p.aux = f32;
+        p.c = StepCoef{7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.f}; p.in_scale = 1.f;
+        p.key = &key;
+        if (combine == 5) p.table = f32;
+        if (combine == 6) p.multistep = true;
+        return launch_window_step(p, nullptr);
+    }
+    LAVIE_CHECK(false, "debug_noise_key_refusal: combine=%d outside 1..6", combine);
+    return 0;
+}
 
 // ---- Guidance from a per-latent table (sampler_guidance.hip): the table itself, then the five steps that read it.
 long long lavie_guidance_partials_floats(int latents, long long per) {

@@ -470,6 +470,13 @@ int launch_step_plain(const StepArgs& a, hipStream_t stream) {
 }
 
 int launch_step(const StepArgs& a, hipStream_t stream) {
+    if (a.key) {        // seeded engine noise is fused into the plain five-coefficient steps only; the others take the materialised tensor
+        LAVIE_CHECK(!a.known, "sampler step: a noise key is not combined with `known` (a known region): pass the materialised noise");
+        LAVIE_CHECK(!a.table, "sampler step: a noise key is not combined with `table` (a guidance table): pass the materialised noise");
+        LAVIE_CHECK(!a.eps_pag, "sampler step: a noise key is not combined with `eps_pag` (perturbed-attention guidance): pass the "
+                                "materialised noise");
+        return launch_step_seeded(a, stream);
+    }
     return a.known ? launch_step_known(a, stream) : a.table ? launch_step_scaled(a, stream) : a.eps_pag ? launch_step_pag(a, stream)
                                                                                              : launch_step_plain(a, stream);
 }

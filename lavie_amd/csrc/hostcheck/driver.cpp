@@ -1684,6 +1684,104 @@ int main(int argc, char** argv) {
             REQUIRE(lavie_hostcheck_launches() == before + 19);
         }
     }
+    {   // seeded engine noise: the host Philox against Random123's known answers, the materialised form, the two seeded plain steps
+        // and the seeded window step in both launch forms; every refusal comes before a launch and names its argument
+        const int P = 2, per = 24, n = P * per;
+        alignas(16) static unsigned short eps[2 * n + 8], min2[2 * n + 8];
+        alignas(16) static float x[n + 4], out[n + 4];
+        auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+        const unsigned kat_key[3][2] = {{0u, 0u}, {0xffffffffu, 0xffffffffu}, {0xa4093822u, 0x299f31d0u}};
+        const unsigned kat_ctr[3][4] = {{0u, 0u, 0u, 0u}, {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu},
+                                        {0x243f6a88u, 0x85a308d3u, 0x13198a2e, 0x03707344u}};
+        const unsigned kat_out[3][4] = {{0x6627e8d5u, 0xe169c58du, 0xbc57ac4cu, 0x9b00dbd8u}, {0x408f276du, 0x41c83b0eu, 0xa20bc7c6u, 0x6d5451fdu},
+                                        {0xd16cfe09u, 0x94fdccebu, 0x5001e420u, 0x24126ea1u}};
+        for (int i = 0; i < 3; ++i) {
+            unsigned w[4] = {1, 2, 3, 4};
+            REQUIRE(lavie_philox4x32_host(kat_key[i], kat_ctr[i], w) == 0 && memcmp(w, kat_out[i], sizeof w) == 0);
+        }
+        REQUIRE(refused(lavie_philox4x32_host(nullptr, kat_ctr[0], nullptr), "null"));
+        unsigned long long seeds[17] = {1, 2, 3};
+        const long before = lavie_hostcheck_launches();
+        REQUIRE(lavie_philox_normal_f32(out, seeds, P, per, 0, 5, nullptr) == 0);                      // eight elements per lane
+        REQUIRE(lavie_philox_normal_f32(out + 1, seeds, 1, 7, (1ll << 34) - 3, ~0ull, nullptr) == 0);   // one
+        REQUIRE(lavie_hostcheck_launches() == before + 2);
+        REQUIRE(refused(lavie_philox_normal_f32(nullptr, seeds, P, per, 0, 0, nullptr), "out is null"));
+        REQUIRE(refused(lavie_philox_normal_f32(out, nullptr, P, per, 0, 0, nullptr), "seeds_host is null"));
+        REQUIRE(refused(lavie_philox_normal_f32(out, seeds, 0, per, 0, 0, nullptr), "P=0"));
+        REQUIRE(refused(lavie_philox_normal_f32(out, seeds, 17, per, 0, 0, nullptr), "P=17"));
+        REQUIRE(refused(lavie_philox_normal_f32(out, seeds, P, 0, 0, 0, nullptr), "per=0"));
+        REQUIRE(refused(lavie_philox_normal_f32(out, seeds, P, per, -1, 0, nullptr), "first_element=-1"));
+        REQUIRE(refused(lavie_philox_normal_f32(out, seeds, P, per, (1ll << 62) - per + 1, 0, nullptr), "first_element"));
+        REQUIRE(refused(lavie_philox_normal_f32((float*)((char*)out + 2), seeds, P, per, 0, 0, nullptr), "4-byte"));
+        lavie_noise_key k{};
+        k.struct_size = (int)sizeof(k);
+        k.count = P; k.seeds_host = seeds; k.per = per; k.draw = 3;
+        REQUIRE(lavie_cfg_sampler_step_seeded(eps, x, min2, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &k) == 0);
+        REQUIRE(lavie_sampler_step_seeded(eps, x, min2, n, 1.f, 0.5f, 0.3f, 0.7f, 0.f, 0.9f, nullptr, &k) == 0);
+        lavie_noise_key odd = k;
+        odd.count = 1; odd.per = 21;                                                                    // one element per lane: any alignment
+        REQUIRE(lavie_cfg_sampler_step_seeded(eps + 1, x + 1, min2 + 1, 21, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &odd) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 5);
+        REQUIRE(refused(lavie_cfg_sampler_step_seeded(eps, x, min2, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, nullptr), "key is null"));
+        lavie_noise_key q = k;
+        q.struct_size -= 8;
+        REQUIRE(refused(lavie_sampler_step_seeded(eps, x, min2, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &q), "struct_size"));
+        q = k; q.count = 17;
+        REQUIRE(refused(lavie_sampler_step_seeded(eps, x, min2, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &q), "key->count=17"));
+        q = k; q.count = 0;
+        REQUIRE(refused(lavie_sampler_step_seeded(eps, x, min2, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &q), "key->count=0"));
+        q = k; q.seeds_host = nullptr;
+        REQUIRE(refused(lavie_sampler_step_seeded(eps, x, min2, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &q), "seeds_host is null"));
+        q = k; q.per = 0;
+        REQUIRE(refused(lavie_sampler_step_seeded(eps, x, min2, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &q), "key->per=0"));
+        REQUIRE(refused(lavie_sampler_step_seeded(eps, x, min2, n - 1, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &k), "is not key->count=2"));
+        REQUIRE(refused(lavie_sampler_step_seeded(nullptr, x, min2, n, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &k), "eps is null"));
+        REQUIRE(lavie_hostcheck_launches() == before + 5);
+        // no alignment rule and the scalars as they come, as the plain entries: an offset view and a NaN coefficient are launched
+        REQUIRE(lavie_cfg_sampler_step_seeded(eps + 8, x + 1, min2 + 8, n, 7.5f, 1.f, 0.5f, 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &k) == 0);
+        REQUIRE(lavie_sampler_step_seeded(eps, x, min2, n, 1.f, __builtin_nanf(""), 0.3f, 0.7f, 0.1f, 0.9f, nullptr, &k) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 7);
+        // the launchers' own refusals of a key beside an operand without a seeded form, by name; nothing is launched
+        const char* const words[7] = {"", "not combined with `known`", "not combined with `table`", "not combined with `eps_pag`",
+                                      "seeded sampler step: the multistep family", "window step: a noise key is not combined with `table`",
+                                      "window step: the multistep family"};
+        for (int combine = 1; combine <= 6; ++combine) REQUIRE(refused(lavie_debug_noise_key_refusal(combine), words[combine]));
+        REQUIRE(refused(lavie_debug_noise_key_refusal(0), "combine=0") && refused(lavie_debug_noise_key_refusal(7), "combine=7"));
+        REQUIRE(lavie_hostcheck_launches() == before + 7);
+        {   // the windowed step: P 1, C 2, F 6, L 4, starts 0 and 2, hw 8 then 3; aux is not read and may be null
+            const int hw = 8, nclip = 1 * 2 * 6 * hw, nwin = 2 * 1 * 2 * 4 * hw;
+            alignas(16) static float wx[nclip];
+            alignas(16) static unsigned short e0[nwin], e1[nwin], m0[nwin], m1[nwin];
+            int starts[2] = {0, 2};
+            float profile[4] = {1, 2, 2, 1};
+            const void* weps[2] = {e0, e1};
+            void* wmin[2] = {m0, m1};
+            lavie_window_step_args a{};
+            a.struct_size = (int)sizeof(a);
+            a.family = 0; a.cfg = 1; a.P = 1; a.C = 2; a.F = 6; a.hw = hw; a.W = 2; a.L = 4;
+            a.starts_host = starts; a.profile_host = profile; a.eps_host = weps; a.model_in_host = wmin; a.x = wx; a.aux = nullptr;
+            a.guidance = 7.5f; a.k_x = 1.f; a.k_eps = 0.5f; a.c_x0 = 0.3f; a.c_xt = 0.7f; a.c4 = 0.1f; a.next_input_scale = 0.9f;
+            lavie_noise_key wk = k;
+            wk.count = 1; wk.per = nclip;
+            REQUIRE(lavie_window_step_seeded(&a, &wk, nullptr) == 0);
+            lavie_window_step_args b = a;
+            b.cfg = 0; b.hw = 3;
+            wk.per = 2 * 6 * 3;
+            REQUIRE(lavie_window_step_seeded(&b, &wk, nullptr) == 0);
+            REQUIRE(lavie_hostcheck_launches() == before + 9);
+            REQUIRE(refused(lavie_window_step_seeded(&a, &wk, nullptr), "key->count=1 per=36"));
+            wk.per = nclip;
+            REQUIRE(refused(lavie_window_step_seeded(&a, nullptr, nullptr), "key is null"));
+            REQUIRE(refused(lavie_window_step_seeded(nullptr, &wk, nullptr), "args"));
+            wk.count = 2;
+            REQUIRE(refused(lavie_window_step_seeded(&a, &wk, nullptr), "the clip has P=1"));
+            wk.count = 1;
+            b = a; b.family = 1;
+            REQUIRE(refused(lavie_window_step_seeded(&b, &wk, nullptr), "takes no noise key"));
+            REQUIRE(refused(lavie_window_step(&a, nullptr), "aux is null"));                            // without a key the noise is needed
+            REQUIRE(lavie_hostcheck_launches() == before + 9);
+        }
+    }
     {   // the four steps with perturbed-attention guidance: both launch forms with exactly sized buffers; every refusal comes before a
         // launch and names its argument
         const int n = 48;

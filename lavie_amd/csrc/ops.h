@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "igemm.h"
+#include "philox.h"
 
 namespace lavie {
 
@@ -123,6 +124,8 @@ long long conv_edge_out_image_halfs(int Cin);
 //   eps_pag != nullptr (sampler_pag.hip; not with `known` / `table`): perturbed-attention guidance.  eps holds one part more, [neg |
 //   prompt | perturbed] with cfg, [prompt | perturbed] without; eps_pag = its last part.  e = cfg ? fma(g, ec - eu, eu) : ec, then
 //   eps = pag_scale != 0 ? fma(pag_scale, ec - ep, e) : e; model_in gets the ONE fp16 value in all three (two) parts.
+//   key != nullptr (sampler_noise.hip; plain five-coefficient steps only): noise[i] = the normal of (key->seed[i / per], key->draw,
+//   i % per) made in registers (philox.h), read when sigma != 0; aux is not read.  Eight elements per lane when key->per % 8 == 0.
 //   Every tensor must be 16-byte aligned where the eight-element form runs: the multistep family without `known` / `table`, inner % 8
 //   == 0 with `known`, per % 8 == 0 with `table` alone, n % 8 == 0 with `eps_pag` (checked by the C entry points).
 struct StepCoef { float guidance, kx, ke, c0, ct, c4; };     // c4: sigma (five-coefficient family) or c_prev (multistep family)
@@ -135,12 +138,19 @@ struct StepArgs {
     const KnownOperands* known; int channels; int64_t inner;   // known == nullptr: no region
     const float* table; int64_t per;                            // table == nullptr: scalar guidance
     const half_t* eps_pag; float pag_scale;                     // eps_pag == nullptr: no perturbed-attention guidance
+    const NoiseKey* key;    // philox.h; nullptr: no key.  Plain five-coefficient steps only (launch_step refuses it with known / table /
+                            // eps_pag): with c4 != 0 the noise is made in registers and aux may be null; n = key->count * key->per
 };
 int launch_step(const StepArgs& a, hipStream_t stream);              // picks the file by (known, table, eps_pag)
 int launch_step_plain(const StepArgs& a, hipStream_t stream);        // elementwise.hip
 int launch_step_known(const StepArgs& a, hipStream_t stream);        // sampler_known.hip
 int launch_step_scaled(const StepArgs& a, hipStream_t stream);       // sampler_guidance.hip
 int launch_step_pag(const StepArgs& a, hipStream_t stream);          // sampler_pag.hip
+int launch_step_seeded(const StepArgs& a, hipStream_t stream);       // sampler_noise.hip (StepArgs::key)
+// ---- sampler_noise.hip : out [P, per] fp32, row p = the normals of elements first .. first + per - 1 of latent (key.seed[p], key.draw)
+// (philox.h); key.count = P <= kNoiseMaxSeeds, key.per = per.  The eight-element form runs when first % 4 == 0, per % 8 == 0 and out
+// is 16-byte aligned, else every lane makes one element: the same bits.
+int launch_philox_normal(float* out, const NoiseKey& key, long long first, hipStream_t stream);
 int launch_add_class_emb_silu(float* emb, const half_t* table, const int* labels_host, int B, int N, hipStream_t stream);
 int launch_f32_to_f16_dup2(const float* x, half_t* out2, int64_t n, float in_scale, hipStream_t stream);
 int launch_f32_to_f16_scaled(const float* x, half_t* out, int64_t n, float in_scale, hipStream_t stream);
@@ -170,6 +180,8 @@ struct WindowStepParams {
     StepCoef c;
     float in_scale;
     const float* table;     // nullptr, or [W][P][2] (guidance, rescale factor) per window and latent (sampler_guidance.hip); needs cfg
+    const NoiseKey* key;    // nullptr, or the step's noise made in registers (five-coefficient family, no table): aux may be null;
+                            // an element's index is its index in the WHOLE clip [C, F, hw] (key->per = C F hw), so the windows do not enter it
 };
 int launch_window_step(const WindowStepParams& a, hipStream_t stream);
 // ---- sampler_guidance.hip : guidance scale and guidance-rescale factor per latent, from device memory.

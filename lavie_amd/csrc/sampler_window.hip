@@ -20,7 +20,10 @@
 // HBM-bound: with hw % 8 == 0 every lane takes eight elements with 16-byte accesses, otherwise one, same arithmetic.  No atomics,
 // no host synchronisation, no allocation: capture-safe and bit-reproducible.
 #include "common.h"
+#include <type_traits>
+
 #include "ops.h"
+#include "philox.h"
 #include "sampler_element.h"
 
 namespace lavie {
@@ -40,10 +43,15 @@ struct WindowShape { int P, C, F, W, L; long hw; };
 // from that window's own statistics before the windows are averaged.  The table pointer is a parameter PACK, empty or one
 // `const float*`: with the empty pack the kernel's argument list, and with it its instruction text, is what it was without the table
 // (an unused trailing pointer moved the scheduling of the argument loads of the guided forms).
+// The pack may instead hold one NoiseKey (philox.h; FAM 0 without a table): with c4 != 0 the step's noise is the function of
+// philox.h at (seed[p], draw, the element's index in the WHOLE clip [C, F, hw]) and aux is not read.  The windows do not enter the
+// index: the step has the bits of window_step fed the materialised clip noise (launch_philox_normal, tests/test_gpu_noise.py).
+template <typename T, typename... Ts> struct pack_holds { static constexpr bool value = (std::is_same<T, Ts>::value || ...); };
 template <int FAM, bool CFG, bool HIST, int V, typename... Table>
 __global__ __launch_bounds__(256) void window_step_kernel(float* __restrict__ x, float* __restrict__ aux, WindowTable t, WindowShape s,
                                                           StepCoef c, float in_scale, Table... table_arg) {
-    constexpr bool TAB = sizeof...(Table) != 0;
+    constexpr bool TAB = pack_holds<const float*, Table...>::value, SEEDED = pack_holds<NoiseKey, Table...>::value;
+    static_assert(sizeof...(Table) <= 1 && (!SEEDED || FAM == 0), "nothing, a table or a noise key");
     const float* table = nullptr;
     if constexpr (TAB) table = (table_arg, ...);
     const long j0 = ((long)blockIdx.x * 256 + threadIdx.x) * V;
@@ -68,7 +76,10 @@ __global__ __launch_bounds__(256) void window_step_kernel(float* __restrict__ x,
     float xt[V], ax[V], eps[V], eu[V], ec[V], xn[V], hist[V];
     half_t h[V];
     load_f32<V>(x + i, xt);
-    if (FAM == 0 ? c.c4 != 0.f : HIST) load_f32<V>(aux + i, ax);
+    if constexpr (SEEDED) {
+        const NoiseKey& key = (table_arg, ...);
+        if (c.c4 != 0.f) philox_normals<V>(key.seed[p], key.draw, (unsigned long long)(((long)ch * s.F + f) * s.hw + j0), ax);
+    } else if (FAM == 0 ? c.c4 != 0.f : HIST) load_f32<V>(aux + i, ax);
 #pragma unroll
     for (int j = 0; j < V; ++j) eps[j] = 0.f;
     for (int k = 0; k < ncov; ++k) {
@@ -105,7 +116,7 @@ __global__ __launch_bounds__(256) void window_step_kernel(float* __restrict__ x,
     }
 }
 
-template <int FAM, bool CFG, bool HIST, bool TAB = false>
+template <int FAM, bool CFG, bool HIST, bool TAB = false, bool SEEDED = false>
 static int launch_window(const WindowStepParams& a, hipStream_t stream) {
     const int64_t planes = (int64_t)a.P * a.C * a.F;
     LAVIE_CHECK(planes >= 1 && planes <= 65535, "window step: P C F = %lld (video, channel, frame) planes do not fit one launch",
@@ -125,6 +136,9 @@ static int launch_window(const WindowStepParams& a, hipStream_t stream) {
     if constexpr (TAB) {
         auto kern = vec ? window_step_kernel<FAM, CFG, HIST, 8, const float*> : window_step_kernel<FAM, CFG, HIST, 1, const float*>;
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, a.x, a.aux, t, s, a.c, a.in_scale, a.table);
+    } else if constexpr (SEEDED) {
+        auto kern = vec ? window_step_kernel<FAM, CFG, HIST, 8, NoiseKey> : window_step_kernel<FAM, CFG, HIST, 1, NoiseKey>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, a.x, a.aux, t, s, a.c, a.in_scale, *a.key);
     } else {
         auto kern = vec ? window_step_kernel<FAM, CFG, HIST, 8> : window_step_kernel<FAM, CFG, HIST, 1>;
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)planes), dim3(256), 0, stream, a.x, a.aux, t, s, a.c, a.in_scale);
@@ -134,6 +148,13 @@ static int launch_window(const WindowStepParams& a, hipStream_t stream) {
 }
 
 int launch_window_step(const WindowStepParams& a, hipStream_t stream) {
+    if (a.key) {
+        LAVIE_CHECK(!a.multistep, "window step: the multistep family draws no noise and takes no noise key");
+        LAVIE_CHECK(!a.table, "window step: a noise key is not combined with `table` (a guidance table): pass the materialised noise");
+        LAVIE_CHECK(a.key->count == a.P && a.key->per == (long long)a.C * a.F * a.hw, "window step: the noise key holds count=%d per=%lld, "
+                    "the clip P=%d and C F hw=%lld", a.key->count, a.key->per, a.P, (long long)a.C * a.F * a.hw);
+        return a.cfg ? launch_window<0, true, false, false, true>(a, stream) : launch_window<0, false, false, false, true>(a, stream);
+    }
     if (a.table) {                  // guided by definition: the table holds the guidance scales
         if (!a.multistep) return launch_window<0, true, false, true>(a, stream);
         return a.c.c4 != 0.f ? launch_window<1, true, true, true>(a, stream) : launch_window<1, true, false, true>(a, stream);

@@ -958,6 +958,87 @@ def window_step_scaled(eps, x, aux, model_in, starts, profile, table, coeffs, ne
     _lib.check(_lib.load().lavie_window_step_scaled(ctypes.byref(a), _p(table), _stream()), "lavie_window_step_scaled")
 
 
+# ------------------------------------------------------------------ seeded engine noise (csrc/philox.h, csrc/sampler_noise.hip)
+_U64 = (1 << 64) - 1
+
+
+def philox4x32(key, counter):
+    """Philox4x32-10 of (key[2], counter[4]) on the host (lavie_philox4x32_host): four 32-bit words.  Needs no device."""
+    k, c, out = (ctypes.c_uint * 2)(*key), (ctypes.c_uint * 4)(*counter), (ctypes.c_uint * 4)()
+    _lib.check(_lib.load().lavie_philox4x32_host(k, c, out), "lavie_philox4x32_host")
+    return list(out)
+
+
+def philox_normal(seeds, per: int, draw: int, first_element: int = 0, out=None, device="cuda"):
+    """Standard normals fp32 [P, per]: row p = elements first_element .. first_element + per - 1 of the latent with seed seeds[p] at draw
+    number `draw` (lavie_philox_normal_f32).  A value is a pure function of (seed, draw, element), so a row does not depend on the other
+    rows, and a slice of a latent equals that range of the whole.  `out`: any fp32 tensor of P per elements whose memory is contiguous
+    (its data pointer may be unaligned: every lane then makes one element, the same bits).  More than NOISE_MAX_SEEDS rows take one
+    launch per sixteen."""
+    seeds = [int(s) & _U64 for s in seeds]
+    p, per = len(seeds), int(per)
+    if p < 1 or per < 1:
+        raise ValueError(f"philox_normal: {p} seeds and per={per} must be >= 1")
+    if out is None:
+        out = torch.empty((p, per), dtype=torch.float32, device=device)
+    _chk32(out)
+    if out.numel() != p * per:
+        raise ValueError(f"philox_normal: out has {out.numel()} elements for {p} latents of {per}")
+    for p0 in range(0, p, _lib.NOISE_MAX_SEEDS):
+        part = seeds[p0:p0 + _lib.NOISE_MAX_SEEDS]
+        _lib.check(_lib.load().lavie_philox_normal_f32(out.data_ptr() + 4 * p0 * per, (ctypes.c_ulonglong * len(part))(*part), len(part), per,
+                                                       int(first_element), int(draw) & _U64, _stream()), "lavie_philox_normal_f32")
+    return out
+
+
+def _noise_key(who, key, latents: int, per: int):
+    """lavie_noise_key of `key` (anything with `.seeds`, one per latent, and `.draw`: noise.NoiseKey) and the array it borrows."""
+    seeds = [int(s) & _U64 for s in key.seeds]
+    if len(seeds) != latents:
+        raise ValueError(f"{who}: the noise key holds {len(seeds)} seeds for {latents} latents")
+    if latents > _lib.NOISE_MAX_SEEDS:
+        raise ValueError(f"{who}: a seeded step serves at most {_lib.NOISE_MAX_SEEDS} latents, got {latents}")
+    k = _lib.NoiseKeyC()
+    k.struct_size = ctypes.sizeof(_lib.NoiseKeyC)
+    seeds_c = (ctypes.c_ulonglong * latents)(*seeds)
+    k.count, k.seeds_host, k.per, k.draw = latents, seeds_c, per, int(key.draw) & _U64
+    return k, seeds_c
+
+
+def _step_seeded(entry, who, eps, x, key, model_in, coeffs, next_input_scale, guidance=None):
+    guided = guidance is not None
+    _chk16(eps, model_in)
+    _chk32(x)
+    n = x.numel()
+    m = 2 * n if guided else n
+    if eps.numel() != m or model_in.numel() != m:
+        raise ValueError(f"{who}: eps / model_in must have {'twice ' if guided else ''}as many elements as x")
+    k, _keep = _noise_key(who, key, x.shape[0], n // x.shape[0])
+    k_x, k_e, c_x0, c_xt, c4 = coeffs
+    how = (float(guidance),) if guided else ()
+    _lib.check(getattr(_lib.load(), entry)(_p(eps), _p(x), _p(model_in), n, *how, float(k_x), float(k_e), float(c_x0), float(c_xt), float(c4),
+                                           float(next_input_scale), _stream(), ctypes.byref(k)), entry)
+
+
+def sampler_step_seeded(eps, x, key, model_in, coeffs, next_input_scale: float = 1.0):
+    """sampler_step with the step's noise made inside the kernel from `key` (seeds of the latents x[p], draw number): x and model_in
+    get the bits of `philox_normal(key.seeds, x[0].numel(), key.draw)` followed by sampler_step.  No noise tensor exists."""
+    _step_seeded("lavie_sampler_step_seeded", "sampler_step_seeded", eps, x, key, model_in, coeffs, next_input_scale)
+
+
+def cfg_sampler_step_seeded(eps2, x, key, model_in2, guidance, coeffs, next_input_scale: float = 1.0):
+    """cfg_ddpm_step with the step's noise made inside the kernel from `key`, as sampler_step_seeded."""
+    _step_seeded("lavie_cfg_sampler_step_seeded", "cfg_sampler_step_seeded", eps2, x, key, model_in2, coeffs, next_input_scale, guidance)
+
+
+def window_step_seeded(eps, x, key, model_in, starts, profile, guidance, coeffs, next_input_scale: float = 1.0):
+    """window_step of the five-coefficient family with the step's noise made inside the kernel from `key`: an element's index is its
+    index in the whole clip, so x and model_in get the bits of window_step fed `philox_normal(key.seeds, x[0].numel(), key.draw)`."""
+    a, _keep = _window_args(eps, x, None, model_in, starts, profile, guidance, coeffs, next_input_scale, False)
+    k, _seeds = _noise_key("window_step_seeded", key, x.shape[0], x.numel() // x.shape[0])
+    _lib.check(_lib.load().lavie_window_step_seeded(ctypes.byref(a), ctypes.byref(k), _stream()), "lavie_window_step_seeded")
+
+
 def _window_args(eps, x, aux, model_in, starts, profile, guidance, coeffs, next_input_scale, multistep):
     """The checked lavie_window_step_args of window_step / window_step_scaled, and the host arrays it borrows."""
     _chk32(x, aux)

@@ -208,7 +208,8 @@ class VideoGenPipeline:
         optional `cache_interval` / `cache_depth` (the layer cache; not keys of the reference) become the keywords of those names,
         an optional `free_init: {num_iters:, use_fast_sampling:, method:, order:, spatial_stop_frequency:, temporal_stop_frequency:}`
         (not a key of the reference) is set on the pipeline (enable_free_init),
-        `seed` is returned in cfg for torch.manual_seed (sample.py:22-23).  `use_fp16` and
+        `seed` is returned in cfg for torch.manual_seed (sample.py:22-23); with `noise: engine` (not a key of the reference) it also
+        becomes `generator=noise.PhiloxGenerator(seed)`, seeded engine noise (`noise: torch`, the default, adds nothing).  `use_fp16` and
         `enable_xformers_memory_efficient_attention` are read by nobody in sample.py and are ignored here as well.
         PyYAML's safe loader replaces omegaconf (absent from the image); interpolation / `${...}` references are not resolved."""
         if isinstance(path_or_dict, dict):
@@ -246,6 +247,12 @@ class VideoGenPipeline:
         for key in ("cache_interval", "cache_depth"):
             if key in cfg:
                 call_kwargs[key] = int(cfg[key])
+        kind = cfg.get("noise", "torch")
+        if kind not in ("torch", "engine"):
+            raise ValueError(f"`noise` must be 'torch' or 'engine' but is {kind!r}")
+        if kind == "engine":
+            from .noise import PhiloxGenerator
+            call_kwargs["generator"] = PhiloxGenerator(int(cfg.get("seed", 0)))
         pipe = VideoGenPipeline(vae=vae, text_encoder=text_encoder, tokenizer=tokenizer, unet=unet, scheduler=scheduler)
         if "freeu" in cfg:                      # {s1:, s2:, b1:, b2:}, all four: the setting goes onto the model
             fu = cfg["freeu"]

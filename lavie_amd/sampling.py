@@ -18,7 +18,8 @@ from collections import namedtuple
 import torch
 
 from . import free_init as free_init_mod
-from . import ops, windows
+from . import _lib, ops, windows
+from .noise import NoiseKey, PhiloxGenerator
 from .scheduling_ddpm import randn_tensor
 
 
@@ -69,13 +70,33 @@ class StepPlan:
 _side_streams = {}
 
 
+class SeededNoise:
+    """What `StepNoise.draw()` hands the loop for a `noise.PhiloxGenerator`: the step's key, not a tensor.  `step` / `window_step`
+    pass `key` to a fused seeded step where one exists; for the others `tensor()` materialises the same values (ops.philox_normal)
+    into the one buffer the StepNoise allocates on first use and keeps for the run."""
+
+    def __init__(self, key: NoiseKey, owner):
+        self.key, self._owner = key, owner
+
+    def tensor(self) -> torch.Tensor:
+        return self._owner.materialise(self.key)
+
+
 class StepNoise:
     """Per-step fp32 noise shaped as `x`, on x's device, from `generator`: None, one generator or one per latent (as
     randn_tensor takes them, :504), on the host or the device.  Host draws for a device tensor are staged through two pinned
     slots on a side stream so that neither the device nor the host waits for the other: `draw()` makes the main stream wait
-    for the slot's copy, `done()` after the consuming launch lets the side stream overwrite the slot two draws later."""
+    for the slot's copy, `done()` after the consuming launch lets the side stream overwrite the slot two draws later.
+    A `noise.PhiloxGenerator`: `draw()` hands out a SeededNoise (the key of the draw); there are no buffers, no side stream and no
+    events, and nothing is allocated unless a step without a fused seeded form asks for the tensor."""
 
     def __init__(self, x: torch.Tensor, generator=None):
+        self._philox = generator if isinstance(generator, PhiloxGenerator) else None
+        if self._philox is not None:
+            self._shape, self._device, self._buffer = tuple(x.shape), x.device, None
+            self._philox.seeds(x.shape[0])          # a seed list of another length is refused here, in front of the loop
+            self._staged, self._pending = False, None
+            return
         self._per_latent = isinstance(generator, list)
         self._gens = generator if self._per_latent else [generator]
         if self._per_latent:
@@ -106,7 +127,16 @@ class StepNoise:
             out.normal_(generator=self._gens[0])
         return out
 
-    def draw(self) -> torch.Tensor:
+    def materialise(self, key: NoiseKey) -> torch.Tensor:
+        """The tensor of a seeded draw, in the run's one buffer."""
+        if self._buffer is None:
+            self._buffer = torch.empty(self._shape, dtype=torch.float32, device=self._device)
+        ops.philox_normal(key.seeds, math.prod(self._shape[1:]), key.draw, out=self._buffer)
+        return self._buffer
+
+    def draw(self):
+        if self._philox is not None:
+            return SeededNoise(self._philox.key(self._shape[0]), self)
         if not self._staged:
             return self._fill(self._noise)
         slot = self._draws & 1
@@ -363,9 +393,17 @@ def step(eps, x, aux, model_in, guidance_scale, coeffs, next_scale, multistep: b
         kind, guidance = "table", (guidance_scale([eps]),)
     else:
         kind, guidance = ("scalar", (guidance_scale,)) if guidance_scale is not None else ("none", ())
+    if isinstance(aux, SeededNoise):            # seeded engine noise: the key where a fused form exists, else the materialised tensor
+        if kind in STEP_SEEDED and region is None and not multistep and x.shape[0] <= _lib.NOISE_MAX_SEEDS:
+            getattr(ops, STEP_SEEDED[kind])(eps, x, aux.key, model_in, *guidance, coeffs, next_scale)
+            return
+        aux = aux.tensor()
     name = STEP_WRAPPERS[bool(multistep), kind, region is not None]
     getattr(ops, name)(eps, x, aux, model_in, *guidance, coeffs, next_scale, *(region or ()))
 
+
+# guidance kind -> the `ops` wrapper of a plain five-coefficient step that makes its noise from a key (no region, no table, no PAG)
+STEP_SEEDED = {"none": "sampler_step_seeded", "scalar": "cfg_sampler_step_seeded"}
 
 # (multistep, guidance kind, region) -> the `ops` wrapper of `step`
 STEP_WRAPPERS = {
@@ -383,7 +421,13 @@ STEP_WRAPPERS = {
 
 def window_step(eps, x, aux, model_in, starts, profile, guidance_scale, coeffs, next_scale, multistep: bool):
     """One fused step over frame windows: `ops.window_step`, or with a GuidanceTable one `ops.guidance_table` call over all
-    windows' predictions followed by `ops.window_step_scaled`."""
+    windows' predictions followed by `ops.window_step_scaled`.  A SeededNoise as `aux`: `ops.window_step_seeded` takes its key; under
+    a GuidanceTable the tensor is materialised."""
+    if isinstance(aux, SeededNoise):
+        if not isinstance(guidance_scale, GuidanceTable) and not multistep and x.shape[0] <= _lib.NOISE_MAX_SEEDS:
+            ops.window_step_seeded(eps, x, aux.key, model_in, starts, profile, guidance_scale, coeffs, next_scale)
+            return
+        aux = aux.tensor()
     if isinstance(guidance_scale, GuidanceTable):
         ops.window_step_scaled(eps, x, aux, model_in, starts, profile, guidance_scale(eps), coeffs, next_scale, multistep=multistep)
     else:

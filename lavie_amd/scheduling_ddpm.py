@@ -14,6 +14,8 @@ from typing import Optional, Tuple, Union
 
 import torch
 
+from .noise import PhiloxGenerator
+
 
 @dataclass
 class DDPMSchedulerOutput:
@@ -25,7 +27,9 @@ def randn_tensor(shape, generator=None, device=None, dtype=torch.float32):
     """Noise helper with diffusers' contract (pipeline_videogen.py:504): a CPU generator draws on the
     CPU and the result is moved, so trajectories are reproducible across devices."""
     device = torch.device(device) if device is not None else torch.device("cpu")
-    if isinstance(generator, (list, tuple)):               # one generator per batch entry, results concatenated
+    if isinstance(generator, PhiloxGenerator):                  # noise.PhiloxGenerator: seeded engine noise, one draw for all latents
+        return generator.randn(shape, device).to(dtype)
+    if isinstance(generator, (list, tuple)):             # one generator per batch entry, results concatenated
         if len(generator) != shape[0]:
             raise ValueError(f"got {len(generator)} generators for a batch of {shape[0]}")
         return torch.cat([randn_tensor((1,) + tuple(shape[1:]), g, device, dtype) for g in generator], dim=0)
