@@ -1031,6 +1031,49 @@ int lavie_window_step_seeded(const lavie_window_step_args* args, const lavie_noi
  * lavie_last_error(); touches no device and launches nothing. */
 int lavie_debug_noise_key_refusal(int combine);
 
+/* ------------------------------------------------------------------------------------------------
+ * CLIP image processor, feature heads and CLIPSIM (additive in ABI 8): pixels and token ids in, context or score out
+ * ---------------------------------------------------------------------------------------------- */
+/* One axis of Pillow's 8-bit bicubic resampling from `in` samples to `out`, on the host (needs no device): first tap xmin_out[out],
+ * tap count count_out[out] and int32 coefficients coeff_out[out, ksize] (scaled by 2^22, zero behind the taps) of every output.
+ * Returns ksize = 2 ceil(2 max(in / out, 1)) + 1 (> 0), also when all three pointers are null (the size query); -1 with a message for
+ * in or out outside 1..65535 or in / out > 32.  Output x of a row u is clip(0, 255, (2^21 + sum_t u[xmin + t] coeff[x, t]) >> 22). */
+int lavie_clip_resample_table_host(int in, int out, int* xmin_out, int* count_out, int* coeff_out);
+typedef struct lavie_clip_preprocess_config {
+    int struct_size;       /* sizeof(lavie_clip_preprocess_config) as the caller declared it; any other value is refused */
+    int size;              /* the short edge after the resize (CLIPImageProcessor.size["shortest_edge"]); CLIP: 224 */
+    int crop;              /* the centre crop's edge (crop_size); CLIP: 224 */
+    float mean[3];         /* image_mean; CLIP: 0.48145466, 0.4578275, 0.40821073 */
+    float std[3];          /* image_std;  CLIP: 0.26862954, 0.26130258, 0.27577711 */
+} lavie_clip_preprocess_config;
+/* Bytes of the workspace lavie_clip_preprocess_u8 needs for B images [H, W, 3] (the uint8 image between the two passes, only the
+ * source rows and the columns the crop keeps); -1 with a message for a shape that entry refuses. */
+long long lavie_clip_preprocess_workspace_bytes(int B, int H, int W, int size, int crop);
+/* CLIPImageProcessor (resize the short edge to `size` with Pillow's bicubic filter, centre crop, rescale by 1 / 255, normalise):
+ * in_u8 uint8 [B, H, W, 3] on the device, rows row_pitch >= 3 W bytes apart, images image_pitch bytes apart (not read when B = 1)
+ * -> out [B, 3, crop, crop], out_dtype 1 = fp32 with the bits of the stock processor's pixel_values, 0 = fp16, one rounding of that
+ * value.  cfg null: CLIP's defaults.  The long edge goes to int(size long / short); the crop starts at (resized - crop) / 2.
+ * Refused by name, nothing launched: B < 1, a short edge below 8, a scale (source / resized) above 32, crop greater than a resized
+ * edge (the stock processor pads there), row_pitch below 3 W, image_pitch below one image, a workspace too small, std of 0.
+ * Every refusal comes before the device is touched.  Two launches on `stream`.  The coefficient tables of a (device, H, W, size,
+ * crop, mean, std) are made on the host and uploaded the first time that key is seen on the current device (an allocation and a
+ * blocking copy: not capturable), then cached.  Only the rows and columns the crop keeps
+ * are computed, and no byte outside an image's [H, 3 W] is read.  An image's output does not depend on B or on its position. */
+int lavie_clip_preprocess_u8(const void* in_u8, int B, int H, int W, long long row_pitch, long long image_pitch, void* out, int out_dtype,
+                             const lavie_clip_preprocess_config* cfg, void* workspace, long long workspace_bytes, void* stream);
+/* out fp32 [B, D] = normalise?(w LN?(x[b, row_b, :])): CLIPModel.get_image_features / get_text_features on a tower's hidden states,
+ * L2-normalised when normalize != 0.  x fp16 [B, L, C]; w fp16 [D, C] (visual_projection / text_projection, no bias).  Row: with
+ * ids_dev (int32 [B, L], device) the row CLIPTextTransformer pools -- eos_token_id == 2: the first maximum of the ids, otherwise the
+ * first position equal to eos_token_id, row 0 when there is none -- else `row`.  ln_gamma / ln_beta fp32 [C] (post_layernorm) or
+ * both null.  LayerNorm, projection and norm accumulate in fp32 in a fixed order; nothing is rounded to fp16.  C and D multiples of
+ * 128 up to 2048.  One workgroup per item: an item's bits do not depend on B or on its position.  One launch, capturable. */
+int lavie_clip_embed_f16(const void* x, int B, int L, int C, const int* ids_dev, int eos_token_id, int row, const float* ln_gamma,
+                         const float* ln_beta, float eps, const void* w, int D, int normalize, float* out, void* stream);
+/* frames == 0: out fp32 [N, P] = scale <img_n, txt_p> (logits_per_image with scale = exp(logit_scale)).  frames >= 1, N = P frames:
+ * out [P] = (100 / frames) sum_f <img_{p frames + f}, txt_p>, the dot products those of the matrix form, added in frame order
+ * (CLIPSIM on normalised features).  img fp32 [N, D], txt fp32 [P, D].  Fixed order, no atomics.  One launch, capturable. */
+int lavie_clip_similarity_f32(const float* img, const float* txt, float* out, int N, int P, int D, int frames, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

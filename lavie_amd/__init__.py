@@ -7,7 +7,18 @@ entry points without the built library raises.
 
 The encoders that feed the UNet its context run on the engine as well: `lavie_amd.text_encoder.HipCLIPTextModel`,
 `lavie_amd.image_encoder.HipCLIPVisionModel` and `HipMappingNetwork` (imported on use: they need the built library).
+`lavie_amd.HipCLIPImageProcessor` and `lavie_amd.ClipScorer` (lavie_amd.clip_score) turn uint8 pixels and token ids into
+pixel_values, CLIP features and CLIPSIM scores; they too are imported on first use.
 """
 from .config import UNetConfig, BASE_CONFIG  # noqa: F401
 
 __version__ = "0.1.0"
+
+_LAZY = {"HipCLIPImageProcessor": "clip_score", "ClipScorer": "clip_score"}
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        import importlib
+        return getattr(importlib.import_module("." + _LAZY[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -93,6 +93,10 @@ class MapperConfigC(C.Structure):      # lavie_mapper_config
                 ("dim_feedforward", c_int), ("seq_in", c_int), ("seq_out", c_int), ("eps", c_float)]
 
 
+class ClipPreprocessConfigC(C.Structure):   # lavie_clip_preprocess_config
+    _fields_ = [("struct_size", c_int), ("size", c_int), ("crop", c_int), ("mean", c_float * 3), ("std", c_float * 3)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/lavie_hip.h
 SIGNATURES = {
     "lavie_last_error": (c_char_p, []),
@@ -313,6 +317,13 @@ SIGNATURES = {
                                                c_float, c_void_p, C.POINTER(NoiseKeyC)]),
     "lavie_window_step_seeded": (c_int, [C.POINTER(WindowStepArgsC), C.POINTER(NoiseKeyC), c_void_p]),
     "lavie_debug_noise_key_refusal": (c_int, [c_int]),
+    "lavie_clip_resample_table_host": (c_int, [c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
+    "lavie_clip_preprocess_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int, c_int]),
+    "lavie_clip_preprocess_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_ll, c_ll, c_void_p, c_int, C.POINTER(ClipPreprocessConfigC), c_void_p,
+                                         c_ll, c_void_p]),
+    "lavie_clip_embed_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float_p, c_float_p, c_float, c_void_p, c_int,
+                                     c_int, c_float_p, c_void_p]),
+    "lavie_clip_similarity_f32": (c_int, [c_float_p, c_float_p, c_float_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
 }
 
 _lib = None

@@ -1464,4 +1464,34 @@ int lavie_mapper_encode(lavie_mapper_t h, const void* image_feats, int Bi, const
     return h->net.encode(image_feats, Bi, text, B, out, ld_out_rows, row0, S(stream));
 }
 
+// ---- CLIP image processor, feature heads, CLIPSIM (clip_engine.cpp, clip_preprocess.hip, clip_embed.hip)
+int lavie_clip_resample_table_host(int in, int out, int* xmin_out, int* count_out, int* coeff_out) {
+    return clip_resample_table_host(in, out, xmin_out, count_out, coeff_out);
+}
+
+long long lavie_clip_preprocess_workspace_bytes(int B, int H, int W, int size, int crop) {
+    return clip_preprocess_workspace_bytes(B, H, W, size, crop);
+}
+
+int lavie_clip_preprocess_u8(const void* in_u8, int B, int H, int W, long long row_pitch, long long image_pitch, void* out, int out_dtype,
+                             const lavie_clip_preprocess_config* cfg, void* workspace, long long workspace_bytes, void* stream) {
+    static const lavie_clip_preprocess_config clip = {(int)sizeof(lavie_clip_preprocess_config), 224, 224,
+                                                      {0.48145466f, 0.4578275f, 0.40821073f}, {0.26862954f, 0.26130258f, 0.27577711f}};
+    if (!cfg) cfg = &clip;
+    LAVIE_CHECK(cfg->struct_size == (int)sizeof(lavie_clip_preprocess_config),
+                "clip_preprocess: cfg->struct_size=%d but this library's lavie_clip_preprocess_config has %d bytes: the binding's struct "
+                "layout is out of date", cfg->struct_size, (int)sizeof(lavie_clip_preprocess_config));
+    return clip_preprocess(in_u8, B, H, W, row_pitch, image_pitch, out, out_dtype, cfg->size, cfg->crop, cfg->mean, cfg->std, workspace,
+                           workspace_bytes, S(stream));
+}
+
+int lavie_clip_embed_f16(const void* x, int B, int L, int C, const int* ids_dev, int eos_token_id, int row, const float* ln_gamma,
+                         const float* ln_beta, float eps, const void* w, int D, int normalize, float* out, void* stream) {
+    return launch_clip_embed(H(x), B, L, C, ids_dev, eos_token_id, row, ln_gamma, ln_beta, eps, H(w), D, normalize != 0, out, S(stream));
+}
+
+int lavie_clip_similarity_f32(const float* img, const float* txt, float* out, int N, int P, int D, int frames, float scale, void* stream) {
+    return launch_clip_similarity(img, txt, out, N, P, D, frames, scale, S(stream));
+}
+
 }  // extern "C"

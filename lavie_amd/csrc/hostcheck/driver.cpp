@@ -1979,6 +1979,68 @@ int main(int argc, char** argv) {
         REQUIRE(lavie_hostcheck_launches() == accepted);
         REQUIRE(lavie_rowstat_finalize_f32(rp.data(), 5, 257, 320, 1e-5f, ro.data(), nullptr) == 0 && lavie_hostcheck_launches() == accepted + 1);
     }
+    {   // CLIP image processor, feature heads, CLIPSIM: the host tables at two shapes, the refusals by their texts, two accepted calls
+        auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+        const int shapes[2][2] = {{53, 320}, {2048, 358}};
+        for (const auto& io : shapes) {
+            const int in = io[0], out = io[1], ks = lavie_clip_resample_table_host(in, out, nullptr, nullptr, nullptr);
+            REQUIRE(ks == (in < out ? 5 : 2 * (int)ceil(2.0 * in / out) + 1));
+            std::vector<int> xmin(out), cnt(out), coeff((size_t)out * ks);
+            REQUIRE(lavie_clip_resample_table_host(in, out, xmin.data(), cnt.data(), coeff.data()) == ks);
+            for (int x = 0; x < out; ++x) {
+                long sum = 0;
+                for (int t = 0; t < ks; ++t) sum += coeff[(size_t)x * ks + t];
+                REQUIRE(xmin[x] >= 0 && cnt[x] >= 1 && cnt[x] <= ks && xmin[x] + cnt[x] <= in && labs(sum - (1l << 22)) <= ks);
+            }
+        }
+        REQUIRE(refused(lavie_clip_resample_table_host(0, 8, nullptr, nullptr, nullptr), "in=0"));
+        REQUIRE(refused(lavie_clip_resample_table_host(330, 10, nullptr, nullptr, nullptr), "above 32"));
+        std::vector<int> one(8);
+        REQUIRE(refused(lavie_clip_resample_table_host(8, 8, one.data(), nullptr, nullptr), "all given or all null"));
+        const int H = 64, W = 48, B = 2;
+        std::vector<unsigned char> img((size_t)B * H * 3 * W);
+        std::vector<float> px((size_t)B * 3 * 224 * 224);
+        const long long need = lavie_clip_preprocess_workspace_bytes(B, H, W, 224, 224);
+        REQUIRE(need > 0);
+        std::vector<unsigned char> ws((size_t)need);
+        auto pre = [&](int b, int h, int w, long long pitch, long long ipitch, int dt, const lavie_clip_preprocess_config* c, long long wsb) {
+            return lavie_clip_preprocess_u8(img.data(), b, h, w, pitch, ipitch, px.data(), dt, c, ws.data(), wsb, nullptr);
+        };
+        const long before = lavie_hostcheck_launches();
+        REQUIRE(pre(B, H, W, 3 * W, 3ll * W * H, 1, nullptr, need) == 0 && pre(1, H, W, 3 * W, 0, 0, nullptr, need) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 4);
+        REQUIRE(refused(pre(0, H, W, 3 * W, 3ll * W * H, 1, nullptr, need), "B=0"));
+        REQUIRE(refused(pre(B, 7, W, 3 * W, 3ll * W * H, 1, nullptr, need), "short edge 7 is below 8"));
+        REQUIRE(refused(pre(B, H, W, 3 * W - 1, 3ll * W * H, 1, nullptr, need), "row_pitch=143 is below 3 W = 144"));
+        REQUIRE(refused(pre(B, H, W, 3 * W, 100, 1, nullptr, need), "image_pitch=100"));
+        REQUIRE(refused(pre(B, H, W, 3 * W, 3ll * W * H, 2, nullptr, need), "out_dtype=2"));
+        REQUIRE(refused(pre(B, H, W, 3 * W, 3ll * W * H, 1, nullptr, need - 256), "the workspace holds"));
+        lavie_clip_preprocess_config c = {(int)sizeof(lavie_clip_preprocess_config), 8, 8, {0.5f, 0.5f, 0.5f}, {0.5f, 0.5f, 0.5f}};
+        REQUIRE(lavie_clip_preprocess_workspace_bytes(1, 300, 300, 8, 8) == -1 && strstr(lavie_last_error(), "is above 32") != nullptr);
+        c.size = 32; c.crop = 64;
+        REQUIRE(refused(pre(1, H, W, 3 * W, 0, 1, &c, need), "crop=64 is greater than the resized edge 32"));
+        c.crop = 32; c.std[1] = 0.f;
+        REQUIRE(refused(pre(1, H, W, 3 * W, 0, 1, &c, need), "std[1]"));
+        c.std[1] = 0.5f; c.struct_size += 4;
+        REQUIRE(refused(pre(1, H, W, 3 * W, 0, 1, &c, need), "struct_size"));
+        REQUIRE(lavie_hostcheck_launches() == before + 4);
+        std::vector<unsigned short> x16((size_t)2 * 77 * 128), w16((size_t)128 * 128);
+        std::vector<float> f(2 * 128), vec(128);
+        std::vector<int> ids(2 * 77);
+        auto emb = [&](int b, int l, int cc, int d, int row, const float* g, const float* bt) {
+            return lavie_clip_embed_f16(x16.data(), b, l, cc, nullptr, 2, row, g, bt, 1e-5f, w16.data(), d, 1, f.data(), nullptr);
+        };
+        REQUIRE(emb(2, 77, 128, 128, 0, vec.data(), vec.data()) == 0);
+        REQUIRE(lavie_clip_embed_f16(x16.data(), 2, 77, 128, ids.data(), 49407, 0, nullptr, nullptr, 0.f, w16.data(), 128, 0, f.data(), nullptr) == 0);
+        REQUIRE(refused(emb(0, 77, 128, 128, 0, nullptr, nullptr), "B=0") && refused(emb(2, 77, 192, 128, 0, nullptr, nullptr), "C=192"));
+        REQUIRE(refused(emb(2, 77, 128, 2176, 0, nullptr, nullptr), "D=2176") && refused(emb(2, 77, 128, 128, 77, nullptr, nullptr), "row=77"));
+        REQUIRE(refused(emb(2, 77, 128, 128, 0, vec.data(), nullptr), "both ln_weight and ln_bias"));
+        REQUIRE(lavie_clip_similarity_f32(f.data(), f.data(), f.data(), 2, 2, 128, 0, 14.f, nullptr) == 0);
+        REQUIRE(lavie_clip_similarity_f32(f.data(), f.data(), f.data(), 2, 1, 128, 2, 1.f, nullptr) == 0);
+        REQUIRE(refused(lavie_clip_similarity_f32(f.data(), f.data(), f.data(), 8, 2, 128, 3, 1.f, nullptr), "N = P frames"));
+        REQUIRE(refused(lavie_clip_similarity_f32(f.data(), nullptr, f.data(), 2, 2, 128, 0, 1.f, nullptr), "null tensor"));
+        REQUIRE(lavie_hostcheck_launches() == before + 8);
+    }
     run_vae_optrace();
     REQUIRE(lavie_upsample_conv3x3_supported(320, 32, 20, 32) >= 0);
     int buckets[16 * 16];

@@ -151,6 +151,25 @@ int launch_step_seeded(const StepArgs& a, hipStream_t stream);       // sampler_
 // (philox.h); key.count = P <= kNoiseMaxSeeds, key.per = per.  The eight-element form runs when first % 4 == 0, per % 8 == 0 and out
 // is 16-byte aligned, else every lane makes one element: the same bits.
 int launch_philox_normal(float* out, const NoiseKey& key, long long first, hipStream_t stream);
+// ---- clip_preprocess.hip : the two passes of Pillow's 8-bit bicubic resampling over the rows and columns a centre crop keeps, and
+// the normalisation by table.  The tables (device int32: first tap, tap count, [crop, ksize] coefficients per kept output; lut = 768
+// fp32) are made by clip_engine.cpp.  mid: uint8 [B, rows, crop, 3], source rows row0 .. row0 + rows - 1; ymin is relative to row0.
+int launch_clip_resample_h(const uint8_t* in, long long row_pitch, long long image_pitch, uint8_t* mid, int B, int row0, int rows, int crop,
+                           const int* xmin, const int* cnt, const int* coeff, int ksize, hipStream_t stream);
+int launch_clip_resample_v(const uint8_t* mid, void* out, bool out_f32, int B, int rows, int crop, const int* ymin, const int* cnt,
+                           const int* coeff, int ksize, const float* lut, hipStream_t stream);
+// ---- clip_engine.cpp : the host side of the image processor (geometry, refusals, tables in double, the cache of uploaded tables)
+int clip_resample_table_host(int in, int out, int* xmin_out, int* count_out, int* coeff_out);     // returns ksize, or -1
+long long clip_preprocess_workspace_bytes(int B, int H, int W, int size, int crop);
+int clip_preprocess(const void* in_u8, int B, int H, int W, long long row_pitch, long long image_pitch, void* out, int out_dtype, int size,
+                    int crop, const float* mean3, const float* std3, void* workspace, long long workspace_bytes, hipStream_t stream);
+// ---- clip_embed.hip : out fp32 [B, D] = normalise?(W LN?(x[b, row_b, :])); x fp16 [B, L, C], W fp16 [D, C]; ids_dev (int32 [B, L]) picks
+// the row as CLIPTextTransformer does, otherwise `row`; gamma / beta fp32 [C] or both null.  C, D multiples of 128 up to 2048.
+constexpr int kClipEmbedMaxWidth = 2048;
+int launch_clip_embed(const half_t* x, int B, int L, int C, const int* ids_dev, int eos_token_id, int row, const float* gamma, const float* beta,
+                      float eps, const half_t* W, int D, bool normalize, float* out, hipStream_t stream);
+// frames == 0: out [N, P] = scale <img_n, txt_p>; frames >= 1 (N = P frames): out [P] = (100 / frames) sum_f <img_{p frames + f}, txt_p>
+int launch_clip_similarity(const float* img, const float* txt, float* out, int N, int P, int D, int frames, float scale, hipStream_t stream);
 int launch_add_class_emb_silu(float* emb, const half_t* table, const int* labels_host, int B, int N, hipStream_t stream);
 int launch_f32_to_f16_dup2(const float* x, half_t* out2, int64_t n, float in_scale, hipStream_t stream);
 int launch_f32_to_f16_scaled(const float* x, half_t* out, int64_t n, float in_scale, hipStream_t stream);

@@ -1346,3 +1346,75 @@ def freq_mix(x0, e0, z, filt, a: float, s: float, r: float, out=None, model_in=N
     args.workspace, args.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
     _lib.check(lib.lavie_freq_mix_f32(ctypes.byref(args), _stream()), "lavie_freq_mix_f32")
     return out
+
+
+# ------------------------------------------------------------------ CLIP image processor, feature heads, CLIPSIM
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def clip_preprocess(images, size=224, crop=224, mean=CLIP_MEAN, std=CLIP_STD, dtype=torch.float32, out=None):
+    """CLIPImageProcessor on the device (lavie_clip_preprocess_u8): images uint8 [b, h, w, 3] with unit stride over (w, 3) -- rows and
+    images may be further apart, as views of a wider buffer are -- -> [b, 3, crop, crop]: fp32 with the stock processor's bits, or
+    fp16, one rounding of those."""
+    if not (images.is_cuda and images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3):
+        raise ValueError("clip_preprocess: images must be a uint8 device tensor [b, h, w, 3]")
+    b, h, w, _ = images.shape
+    if b < 1:
+        raise ValueError("clip_preprocess: empty batch")
+    if images.stride(3) != 1 or images.stride(2) != 3:
+        raise ValueError("clip_preprocess: the pixels of a row must be contiguous")
+    if dtype not in (torch.float16, torch.float32):
+        raise ValueError(f"clip_preprocess: dtype {dtype} is not fp32 or fp16")
+    lib = _lib.load()
+    cfg = _lib.ClipPreprocessConfigC()
+    cfg.struct_size, cfg.size, cfg.crop = ctypes.sizeof(cfg), int(size), int(crop)
+    cfg.mean[:], cfg.std[:] = [float(v) for v in mean], [float(v) for v in std]
+    nbytes = lib.lavie_clip_preprocess_workspace_bytes(b, h, w, int(size), int(crop))
+    if nbytes < 0:
+        _lib.check(-1, "lavie_clip_preprocess_workspace_bytes")
+    with torch.cuda.device(images.device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=images.device)
+        out = _out(out, (b, 3, int(crop), int(crop)), dtype, images.device, "clip_preprocess: out")
+        _lib.check(lib.lavie_clip_preprocess_u8(_p(images), b, h, w, images.stride(1), images.stride(0), _p(out), int(dtype == torch.float32),
+                                                ctypes.byref(cfg), _p(ws), nbytes, _stream()), "lavie_clip_preprocess_u8")
+    return out
+
+
+def clip_embed(x, weight, ids=None, eos_token_id=2, row=0, ln_weight=None, ln_bias=None, eps=1e-5, normalize=True, out=None):
+    """fp32 [b, d] = normalise?(weight LN?(x[b, row_b])) (lavie_clip_embed_f16): x fp16 [b, l, c], weight fp16 [d, c]; ids (integer
+    [b, l]) picks the row CLIPTextTransformer pools, otherwise `row`; ln_weight / ln_bias [c]: post_layernorm."""
+    _chk16(x, weight)
+    if x.dim() != 3 or weight.dim() != 2 or weight.shape[1] != x.shape[2]:
+        raise ValueError(f"clip_embed: x must be [b, l, c] and weight [d, c], got {tuple(x.shape)} and {tuple(weight.shape)}")
+    b, l, c = x.shape
+    d = weight.shape[0]
+    if (ln_weight is None) != (ln_bias is None):
+        raise ValueError("clip_embed: ln_weight and ln_bias come together")
+    g = None if ln_weight is None else ln_weight.to(device=x.device, dtype=torch.float32).contiguous()
+    bt = None if ln_bias is None else ln_bias.to(device=x.device, dtype=torch.float32).contiguous()
+    if g is not None and (g.numel() != c or bt.numel() != c):
+        raise ValueError(f"clip_embed: ln_weight and ln_bias must have {c} elements")
+    ids32 = None
+    if ids is not None:
+        if tuple(ids.shape) != (b, l):
+            raise ValueError(f"clip_embed: ids must be [{b}, {l}], got {tuple(ids.shape)}")
+        ids32 = ids.to(device=x.device, dtype=torch.int32).contiguous()
+    out = _out(out, (b, d), torch.float32, x.device, "clip_embed: out")
+    _lib.check(_lib.load().lavie_clip_embed_f16(_p(x), b, l, c, _p(ids32), int(eos_token_id), int(row), _p(g), _p(bt), float(eps), _p(weight), d,
+                                                int(bool(normalize)), _p(out), _stream()), "lavie_clip_embed_f16")
+    return out
+
+
+def clip_similarity(image_features, text_features, frames=0, scale=1.0, out=None):
+    """frames = 0: fp32 [n, p] = scale <img_n, txt_p>; frames >= 1 (n = p frames): CLIPSIM [p] = (100 / frames) sum_f <img_{p frames + f},
+    txt_p> in frame order (lavie_clip_similarity_f32)."""
+    _chk32(image_features, text_features)
+    if image_features.dim() != 2 or text_features.dim() != 2 or image_features.shape[1] != text_features.shape[1]:
+        raise ValueError(f"clip_similarity: features must be [n, d] and [p, d], got {tuple(image_features.shape)} and {tuple(text_features.shape)}")
+    n, d = image_features.shape
+    p = text_features.shape[0]
+    out = _out(out, (p,) if frames else (n, p), torch.float32, image_features.device, "clip_similarity: out")
+    _lib.check(_lib.load().lavie_clip_similarity_f32(_p(image_features), _p(text_features), _p(out), n, p, d, int(frames), float(scale),
+                                                     _stream()), "lavie_clip_similarity_f32")
+    return out

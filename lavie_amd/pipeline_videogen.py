@@ -139,13 +139,20 @@ class VideoGenPipeline:
         return self.mapper
 
     # ------------------------------------------------------------------ image conditioning on the engine
-    def enable_engine_image_encoder(self):
+    def enable_engine_image_encoder(self, processor=False):
         """Wraps the attached stock `clip_model` (a CLIPModel or a CLIPVisionModel) and `mapper` (a MappingNetwork) in
         HipCLIPVisionModel / HipMappingNetwork (weights copied to the engine, rounded to fp16): `image_tensor=` then runs on the
         engine, bit-reproducible and with an image's tokens independent of the batch.  Either part may be absent or wrapped
-        already.  `clip_processor` (resize, crop, normalise) stays the caller's, as the tokenizer does.
-        disable_engine_image_encoder puts the stock objects back."""
+        already.  `clip_processor` (resize, crop, normalise) stays the caller's, as the tokenizer does, unless processor=True: then
+        the attached stock CLIPImageProcessor is wrapped in HipCLIPImageProcessor (the same pixel_values bit for bit,
+        from uint8 images, on the device).  disable_engine_image_encoder puts the stock objects back."""
         from .image_encoder import HipCLIPVisionModel, HipMappingNetwork
+        if processor:
+            from .clip_score import HipCLIPImageProcessor
+            if self.clip_processor is None:
+                raise ValueError("processor=True, but no clip_processor is attached")
+            if not isinstance(self.clip_processor, HipCLIPImageProcessor):
+                self.clip_processor = HipCLIPImageProcessor.from_stock(self.clip_processor, device=self.device)
         if self.clip_model is None and self.mapper is None:
             raise ValueError("no clip_model or mapper attached")
         if self.clip_model is not None and not isinstance(self.clip_model, HipCLIPVisionModel):
@@ -155,6 +162,9 @@ class VideoGenPipeline:
 
     def disable_engine_image_encoder(self):
         from .image_encoder import HipCLIPVisionModel, HipMappingNetwork
+        from .clip_score import HipCLIPImageProcessor
+        if isinstance(self.clip_processor, HipCLIPImageProcessor) and self.clip_processor._stock is not None:
+            self.clip_processor = self.clip_processor._stock
         for attr, cls in (("clip_model", HipCLIPVisionModel), ("mapper", HipMappingNetwork)):
             obj = getattr(self, attr)
             if isinstance(obj, cls):
