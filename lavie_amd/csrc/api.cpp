@@ -26,11 +26,68 @@ struct lavie_vision_s {
 };
 
 struct lavie_mapper_s {
-    ImageMapper net;
-    explicit lavie_mapper_s(const lavie_mapper_config& c) : net(c) {}
+    ImageMapper enc;
+    explicit lavie_mapper_s(const lavie_mapper_config& c) : enc(c) {}
 };
 
 static inline hipStream_t S(void* s) { return (hipStream_t)s; }
+
+// The lifecycle of the text, vision and mapper handles, written once: Handle is lavie_<name>_s, Cfg its lavie_<name>_config
+template <class Handle, class Cfg>
+static int encoder_create(const char* name, const Cfg* cfg, Handle** out) {
+    LAVIE_CHECK(cfg && out, "%s_create: null argument", name);
+    LAVIE_CHECK(cfg->struct_size == (int)sizeof(Cfg),
+                "%s_create: cfg->struct_size=%d but this library's lavie_%s_config has %d bytes (ABI %d): the binding's struct "
+                "layout is out of date", name, cfg->struct_size, name, (int)sizeof(Cfg), LAVIE_ABI_VERSION);
+    Handle* h = new (std::nothrow) Handle(*cfg);
+    LAVIE_CHECK(h != nullptr, "%s_create: out of host memory", name);
+    if (int rc = h->enc.validate_config()) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+template <class Handle>
+static int encoder_destroy(Handle* h) {
+    delete h;
+    return 0;
+}
+
+template <class Handle>
+static int encoder_num_params(Handle* h) {
+    return h ? (int)h->enc.params().size() : -1;
+}
+
+template <class Handle>
+static int encoder_param_info(const char* name, Handle* h, int i, const char** pname, long long* numel) {
+    LAVIE_CHECK(h && i >= 0 && i < (int)h->enc.params().size(), "%s_param_info: index %d out of range", name, i);
+    if (pname) *pname = h->enc.params()[i].name.c_str();
+    if (numel) *numel = h->enc.params()[i].numel;
+    return 0;
+}
+
+template <class Handle>
+static int encoder_set_param(const char* name, Handle* h, const char* key, const void* data_f16, long long numel) {
+    LAVIE_CHECK(h && key, "%s_set_param: null argument", name);
+    return h->enc.set_param(key, data_f16, numel);
+}
+
+template <class Handle>
+static int encoder_finalize(const char* name, Handle* h, void* stream) {
+    LAVIE_CHECK(h, "%s_finalize: null handle", name);
+    return h->enc.finalize(S(stream));
+}
+
+template <class Handle, class... Shape>
+static long long encoder_workspace_bytes(const char* name, Handle* h, Shape... shape) {
+    if (!h) {
+        set_error("%s_workspace_bytes: null handle", name);
+        return -1;
+    }
+    return h->enc.workspace_bytes(shape...);
+}
 
 // Operator-level entry points have no workspace argument: the split-K slab comes from a grow-only scratch
 // buffer owned by the library (allocated outside any stream capture; the engine uses its own workspace).
@@ -1280,52 +1337,15 @@ int lavie_act_f16(void* x, long long n, int kind, void* stream) { return launch_
 
 int lavie_text_config_size(void) { return (int)sizeof(lavie_text_config); }
 
-int lavie_text_create(const lavie_text_config* cfg, lavie_text_t* out) {
-    LAVIE_CHECK(cfg && out, "text_create: null argument");
-    LAVIE_CHECK(cfg->struct_size == (int)sizeof(lavie_text_config),
-                "text_create: cfg->struct_size=%d but this library's lavie_text_config has %d bytes (ABI %d): the binding's struct "
-                "layout is out of date", cfg->struct_size, (int)sizeof(lavie_text_config), LAVIE_ABI_VERSION);
-    lavie_text_s* h = new (std::nothrow) lavie_text_s(*cfg);
-    LAVIE_CHECK(h != nullptr, "text_create: out of host memory");
-    if (int rc = h->enc.validate_config()) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return 0;
-}
-
-int lavie_text_destroy(lavie_text_t h) {
-    delete h;
-    return 0;
-}
-
-int lavie_text_num_params(lavie_text_t h) { return h ? (int)h->enc.params().size() : -1; }
-
-int lavie_text_param_info(lavie_text_t h, int i, const char** name, long long* numel) {
-    LAVIE_CHECK(h && i >= 0 && i < (int)h->enc.params().size(), "text_param_info: index %d out of range", i);
-    if (name) *name = h->enc.params()[i].name.c_str();
-    if (numel) *numel = h->enc.params()[i].numel;
-    return 0;
-}
-
+int lavie_text_create(const lavie_text_config* cfg, lavie_text_t* out) { return encoder_create("text", cfg, out); }
+int lavie_text_destroy(lavie_text_t h) { return encoder_destroy(h); }
+int lavie_text_num_params(lavie_text_t h) { return encoder_num_params(h); }
+int lavie_text_param_info(lavie_text_t h, int i, const char** name, long long* numel) { return encoder_param_info("text", h, i, name, numel); }
 int lavie_text_set_param(lavie_text_t h, const char* name, const void* data_f16, long long numel) {
-    LAVIE_CHECK(h && name, "text_set_param: null argument");
-    return h->enc.set_param(name, data_f16, numel);
+    return encoder_set_param("text", h, name, data_f16, numel);
 }
-
-int lavie_text_finalize(lavie_text_t h, void* stream) {
-    LAVIE_CHECK(h, "text_finalize: null handle");
-    return h->enc.finalize(S(stream));
-}
-
-long long lavie_text_workspace_bytes(lavie_text_t h, int B, int L) {
-    if (!h) {
-        set_error("text_workspace_bytes: null handle");
-        return -1;
-    }
-    return h->enc.workspace_bytes(B, L);
-}
+int lavie_text_finalize(lavie_text_t h, void* stream) { return encoder_finalize("text", h, stream); }
+long long lavie_text_workspace_bytes(lavie_text_t h, int B, int L) { return encoder_workspace_bytes("text", h, B, L); }
 
 int lavie_text_encode(lavie_text_t h, const int* ids_dev, int B, int L, void* out_f16, void* stream) {
     LAVIE_CHECK(h, "text_encode: null handle");
@@ -1357,52 +1377,15 @@ int lavie_relu_f16(void* x, long long n, void* stream) { return launch_relu(H(x)
 
 int lavie_vision_config_size(void) { return (int)sizeof(lavie_vision_config); }
 
-int lavie_vision_create(const lavie_vision_config* cfg, lavie_vision_t* out) {
-    LAVIE_CHECK(cfg && out, "vision_create: null argument");
-    LAVIE_CHECK(cfg->struct_size == (int)sizeof(lavie_vision_config),
-                "vision_create: cfg->struct_size=%d but this library's lavie_vision_config has %d bytes (ABI %d): the binding's struct "
-                "layout is out of date", cfg->struct_size, (int)sizeof(lavie_vision_config), LAVIE_ABI_VERSION);
-    lavie_vision_s* h = new (std::nothrow) lavie_vision_s(*cfg);
-    LAVIE_CHECK(h != nullptr, "vision_create: out of host memory");
-    if (int rc = h->enc.validate_config()) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return 0;
-}
-
-int lavie_vision_destroy(lavie_vision_t h) {
-    delete h;
-    return 0;
-}
-
-int lavie_vision_num_params(lavie_vision_t h) { return h ? (int)h->enc.params().size() : -1; }
-
-int lavie_vision_param_info(lavie_vision_t h, int i, const char** name, long long* numel) {
-    LAVIE_CHECK(h && i >= 0 && i < (int)h->enc.params().size(), "vision_param_info: index %d out of range", i);
-    if (name) *name = h->enc.params()[i].name.c_str();
-    if (numel) *numel = h->enc.params()[i].numel;
-    return 0;
-}
-
+int lavie_vision_create(const lavie_vision_config* cfg, lavie_vision_t* out) { return encoder_create("vision", cfg, out); }
+int lavie_vision_destroy(lavie_vision_t h) { return encoder_destroy(h); }
+int lavie_vision_num_params(lavie_vision_t h) { return encoder_num_params(h); }
+int lavie_vision_param_info(lavie_vision_t h, int i, const char** name, long long* numel) { return encoder_param_info("vision", h, i, name, numel); }
 int lavie_vision_set_param(lavie_vision_t h, const char* name, const void* data_f16, long long numel) {
-    LAVIE_CHECK(h && name, "vision_set_param: null argument");
-    return h->enc.set_param(name, data_f16, numel);
+    return encoder_set_param("vision", h, name, data_f16, numel);
 }
-
-int lavie_vision_finalize(lavie_vision_t h, void* stream) {
-    LAVIE_CHECK(h, "vision_finalize: null handle");
-    return h->enc.finalize(S(stream));
-}
-
-long long lavie_vision_workspace_bytes(lavie_vision_t h, int B) {
-    if (!h) {
-        set_error("vision_workspace_bytes: null handle");
-        return -1;
-    }
-    return h->enc.workspace_bytes(B);
-}
+int lavie_vision_finalize(lavie_vision_t h, void* stream) { return encoder_finalize("vision", h, stream); }
+long long lavie_vision_workspace_bytes(lavie_vision_t h, int B) { return encoder_workspace_bytes("vision", h, B); }
 
 int lavie_vision_encode(lavie_vision_t h, const void* pixel_values, int x_dtype, int B, void* out_f16, void* stream) {
     LAVIE_CHECK(h, "vision_encode: null handle");
@@ -1411,57 +1394,20 @@ int lavie_vision_encode(lavie_vision_t h, const void* pixel_values, int x_dtype,
 
 int lavie_mapper_config_size(void) { return (int)sizeof(lavie_mapper_config); }
 
-int lavie_mapper_create(const lavie_mapper_config* cfg, lavie_mapper_t* out) {
-    LAVIE_CHECK(cfg && out, "mapper_create: null argument");
-    LAVIE_CHECK(cfg->struct_size == (int)sizeof(lavie_mapper_config),
-                "mapper_create: cfg->struct_size=%d but this library's lavie_mapper_config has %d bytes (ABI %d): the binding's struct "
-                "layout is out of date", cfg->struct_size, (int)sizeof(lavie_mapper_config), LAVIE_ABI_VERSION);
-    lavie_mapper_s* h = new (std::nothrow) lavie_mapper_s(*cfg);
-    LAVIE_CHECK(h != nullptr, "mapper_create: out of host memory");
-    if (int rc = h->net.validate_config()) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return 0;
-}
-
-int lavie_mapper_destroy(lavie_mapper_t h) {
-    delete h;
-    return 0;
-}
-
-int lavie_mapper_num_params(lavie_mapper_t h) { return h ? (int)h->net.params().size() : -1; }
-
-int lavie_mapper_param_info(lavie_mapper_t h, int i, const char** name, long long* numel) {
-    LAVIE_CHECK(h && i >= 0 && i < (int)h->net.params().size(), "mapper_param_info: index %d out of range", i);
-    if (name) *name = h->net.params()[i].name.c_str();
-    if (numel) *numel = h->net.params()[i].numel;
-    return 0;
-}
-
+int lavie_mapper_create(const lavie_mapper_config* cfg, lavie_mapper_t* out) { return encoder_create("mapper", cfg, out); }
+int lavie_mapper_destroy(lavie_mapper_t h) { return encoder_destroy(h); }
+int lavie_mapper_num_params(lavie_mapper_t h) { return encoder_num_params(h); }
+int lavie_mapper_param_info(lavie_mapper_t h, int i, const char** name, long long* numel) { return encoder_param_info("mapper", h, i, name, numel); }
 int lavie_mapper_set_param(lavie_mapper_t h, const char* name, const void* data_f16, long long numel) {
-    LAVIE_CHECK(h && name, "mapper_set_param: null argument");
-    return h->net.set_param(name, data_f16, numel);
+    return encoder_set_param("mapper", h, name, data_f16, numel);
 }
-
-int lavie_mapper_finalize(lavie_mapper_t h, void* stream) {
-    LAVIE_CHECK(h, "mapper_finalize: null handle");
-    return h->net.finalize(S(stream));
-}
-
-long long lavie_mapper_workspace_bytes(lavie_mapper_t h, int B) {
-    if (!h) {
-        set_error("mapper_workspace_bytes: null handle");
-        return -1;
-    }
-    return h->net.workspace_bytes(B);
-}
+int lavie_mapper_finalize(lavie_mapper_t h, void* stream) { return encoder_finalize("mapper", h, stream); }
+long long lavie_mapper_workspace_bytes(lavie_mapper_t h, int B) { return encoder_workspace_bytes("mapper", h, B); }
 
 int lavie_mapper_encode(lavie_mapper_t h, const void* image_feats, int Bi, const void* text, int B, void* out, int ld_out_rows, int row0,
                         void* stream) {
     LAVIE_CHECK(h, "mapper_encode: null handle");
-    return h->net.encode(image_feats, Bi, text, B, out, ld_out_rows, row0, S(stream));
+    return h->enc.encode(image_feats, Bi, text, B, out, ld_out_rows, row0, S(stream));
 }
 
 // ---- CLIP image processor, feature heads, CLIPSIM (clip_engine.cpp, clip_preprocess.hip, clip_embed.hip)

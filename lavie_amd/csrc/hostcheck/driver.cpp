@@ -1096,6 +1096,12 @@ int main(int argc, char** argv) {
         REQUIRE(lavie_text_num_params(h) == 2 + 16 * Lyr + 2 && lavie_text_num_params(nullptr) == -1);
         REQUIRE(refused(lavie_text_param_info(h, 99, nullptr, nullptr), "out of range"));
         REQUIRE(refused(lavie_text_set_param(h, "text_model.nope", big.data(), 8), "unknown state-dict key"));
+        REQUIRE(refused(lavie_text_set_param(h, "final_layer_norm.bias", big.data(), C), "unknown state-dict key"));      // no flat spelling
+        {
+            const char *first = nullptr, *last = nullptr;
+            REQUIRE(lavie_text_param_info(h, 0, &first, nullptr) == 0 && lavie_text_param_info(h, 2 + 16 * Lyr + 1, &last, nullptr) == 0);
+            REQUIRE(!strcmp(first, "text_model.embeddings.token_embedding.weight") && !strcmp(last, "text_model.final_layer_norm.bias"));
+        }
         REQUIRE(refused(lavie_text_encode(h, ids.data(), 1, P, o.data(), nullptr), "not finalized"));
         REQUIRE(refused(lavie_text_finalize(h, nullptr), "was never set"));
         std::vector<std::vector<unsigned short>> held;
@@ -1199,6 +1205,10 @@ int main(int argc, char** argv) {
         REQUIRE(lavie_vision_num_params(vh) == 5 + 16 * Lyr && lavie_vision_num_params(nullptr) == -1);
         REQUIRE(refused(lavie_vision_param_info(vh, 99, nullptr, nullptr), "out of range"));
         REQUIRE(refused(lavie_vision_set_param(vh, "vision_model.nope", big.data(), 8), "unknown state-dict key"));
+        {
+            const char* first = nullptr;
+            REQUIRE(lavie_vision_param_info(vh, 0, &first, nullptr) == 0 && !strcmp(first, "vision_model.embeddings.class_embedding"));
+        }
         REQUIRE(lavie_vision_set_param(vh, "post_layernorm.weight", big.data(), C) == 0);                  // accepted and ignored,
         REQUIRE(lavie_vision_set_param(vh, "vision_model.post_layernorm.bias", big.data(), C) == 0);       // in either spelling
         REQUIRE(refused(lavie_vision_encode(vh, px.data(), 1, 1, emb.data(), nullptr), "not finalized"));

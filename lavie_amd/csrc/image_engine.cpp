@@ -1,7 +1,6 @@
 // CLIPVisionTransformer (transformers modeling_clip.py) up to last_hidden_state and the fork's MappingNetwork
 // (base/pipelines/mapping.py:61-97 of the reference: nn.TransformerDecoder, post-norm, ReLU) on the engine's operators.
-// Vision, on rows x [B T, C]:   x = pre_layrnorm(embeddings(pixels)); per layer
-//   h = LN1(x); qkv = h Wqkv^T + b; h = attention(q, k, v); x = h Wo^T + bo + x; h = LN2(x); m = act(h W1^T + b1); x = m W2^T + b2 + x
+// Vision, on rows x [B T, C]:   x = pre_layrnorm(embeddings(pixels)); then the CLIP layers of encoder_parts.h
 //   (post_layernorm belongs to the pooled output and is not applied to last_hidden_state)
 // Mapper, on rows x [B So, C]:  mem = image Wimg^T + b + image_pos; x = text + text_pos; per layer
 //   qkv = x Wsa^T + b; a = attention(q, k, v); t = a Wo^T + bo + x; x = norm1(t)
@@ -15,36 +14,12 @@
 #include <math.h>
 
 #include "ops.h"
-#include "pinned_linear.h"
 
 namespace lavie {
-
-#define RUN(expr)                 \
-    do {                          \
-        int rc_ = (expr);         \
-        if (rc_ != 0) return rc_; \
-    } while (0)
 
 namespace {
 
 constexpr size_t H = sizeof(half_t);
-
-// hands out 256-byte pieces of a block; with base = nullptr it only counts
-struct Carver {
-    char* base;
-    size_t used = 0;
-    template <class T>
-    T* take(size_t count) {
-        T* r = base ? (T*)(base + used) : nullptr;
-        used += up256(count * sizeof(T));
-        return r;
-    }
-};
-
-int copy16(half_t* dst, const half_t* src, size_t n, hipStream_t s) {
-    LAVIE_HIP(hipMemcpyAsync(dst, src, n * H, hipMemcpyDeviceToDevice, s));
-    return 0;
-}
 
 int check_batch(const char* who, int B) {
     LAVIE_CHECK(B >= 1 && B <= kImageMaxBatch, "%s: B=%d must be 1..%d", who, B, kImageMaxBatch);
@@ -53,197 +28,88 @@ int check_batch(const char* who, int B) {
 
 }  // namespace
 
-// ------------------------------------------------------------------ the parameter table
-void ParamTable::add(const std::string& name, long long numel) {
-    index_[name] = (int)params_.size();
-    params_.push_back({name, numel, nullptr});
-}
-
-int ParamTable::set(const char* who, const char* prefix, const char* name, const void* data, long long numel) {
-    std::string key = name;
-    const std::string pre = prefix;
-    if (!pre.empty() && key.compare(0, pre.size(), pre) != 0) key = pre + key;
-    for (const std::string& ig : ignored_)
-        if (key == ig) return 0;
-    auto it = index_.find(key);
-    LAVIE_CHECK(it != index_.end(), "%s: unknown state-dict key '%s'", who, name);
-    Param& pi = params_[it->second];
-    LAVIE_CHECK(pi.numel == numel, "%s: '%s' has %lld elements, expected %lld", who, name, numel, pi.numel);
-    LAVIE_CHECK(data != nullptr, "%s: '%s' null data", who, name);
-    pi.src = (const half_t*)data;
-    return 0;
-}
-
-int ParamTable::all_set(const char* who) const {
-    for (const Param& p : params_) LAVIE_CHECK(p.src != nullptr, "%s: '%s' was never set", who, p.name.c_str());
-    return 0;
-}
-
-void ParamTable::release() {
-    for (Param& p : params_) p.src = nullptr;      // the loan ends when the stream drains
-}
-
 // ------------------------------------------------------------------ the vision tower
-static const char* kVis = "vision_model.";
+static const std::string kVis = "vision_model.";
 
-VisionEncoder::VisionEncoder(const lavie_vision_config& cfg) : cfg_(cfg) {
-    const long long C = cfg.hidden, I = cfg.intermediate;
+VisionEncoder::VisionEncoder(const lavie_vision_config& cfg)
+    : cfg_(cfg), shape_{cfg.hidden, cfg.intermediate, cfg.layers, cfg.heads, cfg.act, cfg.eps} {
+    const long long C = cfg.hidden;
     if (cfg.layers < 0 || cfg.layers > 1024 || cfg.patch_size < 1 || cfg.patch_size > 64 || cfg.image_size < 1 || cfg.image_size > 1024) return;
-    const std::string v = kVis;
-    table_.add(v + "embeddings.class_embedding", C);
-    table_.add(v + "embeddings.patch_embedding.weight", C * 3 * cfg.patch_size * cfg.patch_size);
-    table_.add(v + "embeddings.position_embedding.weight", (long long)tokens() * C);
-    table_.add(v + "pre_layrnorm.weight", C);
-    table_.add(v + "pre_layrnorm.bias", C);
-    for (int i = 0; i < cfg.layers; ++i) {
-        const std::string p = v + "encoder.layers." + std::to_string(i) + ".";
-        for (const char* proj : {"k_proj", "v_proj", "q_proj", "out_proj"}) {
-            table_.add(p + "self_attn." + proj + ".weight", C * C);
-            table_.add(p + "self_attn." + proj + ".bias", C);
-        }
-        table_.add(p + "layer_norm1.weight", C);
-        table_.add(p + "layer_norm1.bias", C);
-        table_.add(p + "mlp.fc1.weight", I * C);
-        table_.add(p + "mlp.fc1.bias", I);
-        table_.add(p + "mlp.fc2.weight", C * I);
-        table_.add(p + "mlp.fc2.bias", C);
-        table_.add(p + "layer_norm2.weight", C);
-        table_.add(p + "layer_norm2.bias", C);
-    }
-    table_.ignore(v + "post_layernorm.weight");      // the pooled output's norm: not part of last_hidden_state
-    table_.ignore(v + "post_layernorm.bias");
-}
-
-VisionEncoder::~VisionEncoder() {
-    if (block_) (void)hipFree(block_);
+    table_.add(kVis + "embeddings.class_embedding", C);
+    table_.add(kVis + "embeddings.patch_embedding.weight", C * 3 * cfg.patch_size * cfg.patch_size);
+    table_.add(kVis + "embeddings.position_embedding.weight", (long long)tokens() * C);
+    table_.add(kVis + "pre_layrnorm.weight", C);
+    table_.add(kVis + "pre_layrnorm.bias", C);
+    for (int i = 0; i < cfg.layers; ++i) list_clip_layer(table_, kVis + "encoder.layers." + std::to_string(i) + ".", shape_);
+    table_.ignore(kVis + "post_layernorm.weight");      // the pooled output's norm: not part of last_hidden_state
+    table_.ignore(kVis + "post_layernorm.bias");
 }
 
 int VisionEncoder::validate_config() const {
     const lavie_vision_config& c = cfg_;
-    LAVIE_CHECK(c.hidden >= kPinBn && c.hidden % kPinBn == 0 && c.hidden <= 2048, "vision_create: hidden=%d must be a multiple of %d up to 2048",
-                c.hidden, kPinBn);
-    LAVIE_CHECK(c.intermediate >= kPinBn && c.intermediate % kPinBn == 0 && c.intermediate <= 16384,
-                "vision_create: intermediate=%d must be a multiple of %d up to 16384", c.intermediate, kPinBn);
-    LAVIE_CHECK(c.layers >= 1 && c.layers <= 64, "vision_create: layers=%d must be 1..64", c.layers);
-    LAVIE_CHECK(c.heads >= 1 && c.hidden % c.heads == 0 && (c.hidden / c.heads == 32 || c.hidden / c.heads == 64),
-                "vision_create: heads=%d gives a head dim of hidden / heads that is not 32 or 64 (hidden=%d)", c.heads, c.hidden);
+    RUN(check_clip_shape("vision_create", shape_));
     LAVIE_CHECK(c.patch_size >= 1 && c.patch_size <= 64, "vision_create: patch_size=%d must be 1..64", c.patch_size);
     LAVIE_CHECK(c.image_size >= c.patch_size && c.image_size <= 1024 && c.image_size % c.patch_size == 0,
                 "vision_create: image_size=%d must be a multiple of patch_size=%d up to 1024", c.image_size, c.patch_size);
     LAVIE_CHECK(tokens() <= kShortMaxL, "vision_create: image_size=%d / patch_size=%d gives %d tokens, more than %d", c.image_size, c.patch_size,
                 tokens(), kShortMaxL);
-    LAVIE_CHECK(c.act == LAVIE_TEXT_ACT_QUICK_GELU || c.act == LAVIE_TEXT_ACT_GELU, "vision_create: act=%d is neither quick_gelu (0) nor gelu (1)",
-                c.act);
-    LAVIE_CHECK(isfinite(c.eps) && c.eps > 0.f, "vision_create: eps must be finite and > 0");
     return 0;
 }
 
 int VisionEncoder::set_param(const char* name, const void* data, long long numel) {
-    LAVIE_CHECK(!finalized_, "vision_set_param: the handle is finalized");
-    return table_.set("vision_set_param", kVis, name, data, numel);
+    RUN(check_open(block_, "vision_set_param"));
+    return table_.set("vision_set_param", kVis.c_str(), name, data, numel);
 }
 
 int VisionEncoder::finalize(hipStream_t s) {
-    LAVIE_CHECK(!finalized_, "vision_finalize: the handle is finalized already");
+    RUN(check_open(block_, "vision_finalize", " already"));
     RUN(table_.all_set("vision_finalize"));
-    const size_t C = cfg_.hidden, I = cfg_.intermediate, T = tokens(), P = cfg_.patch_size, Kp = patch_embed_k(cfg_.patch_size);
-    const long long ws = workspace_bytes(kImageMaxBatch);
-    if (ws < 0) return -1;
+    const size_t C = cfg_.hidden, T = tokens(), Kp = patch_embed_k(cfg_.patch_size);
     layers_.resize(cfg_.layers);
-    auto carve = [&](char* base) {
+    RUN(allocate(block_, workspace_bytes(kImageMaxBatch), [&](char* base) {
         Carver c{base};
         wpatch_ = c.take<half_t>(C * Kp);
         cls_ = c.take<half_t>(C);
         pos_ = c.take<half_t>(T * C);
         preg_ = c.take<float>(C);
         preb_ = c.take<float>(C);
-        for (Layer& l : layers_) {
-            l.wqkv = c.take<half_t>(3 * C * C);
-            l.wo = c.take<half_t>(C * C);
-            l.w1 = c.take<half_t>(I * C);
-            l.w2 = c.take<half_t>(C * I);
-            l.bqkv = c.take<float>(3 * C);
-            l.bo = c.take<float>(C);
-            l.b1 = c.take<float>(I);
-            l.b2 = c.take<float>(C);
-            l.ln1g = c.take<float>(C);
-            l.ln1b = c.take<float>(C);
-            l.ln2g = c.take<float>(C);
-            l.ln2b = c.take<float>(C);
-        }
+        for (ClipLayer& l : layers_) carve_clip_layer(c, l, shape_);
         return c.used;
-    };
-    const size_t weights = carve(nullptr);
-    if (block_) { (void)hipFree(block_); block_ = nullptr; }      // a finalize that failed half way
-    LAVIE_HIP(hipMalloc((void**)&block_, weights + (size_t)ws));
-    carve(block_);
-    ws_ = block_ + weights;
-    const std::string v = kVis;
-    auto src = [&](const std::string& n) { return table_.src(v + n); };
-    auto to32 = [&](float* dst, const std::string& n, size_t count) { return launch_f16_to_f32(src(n), dst, (int64_t)count, s); };
-    RUN(launch_pack_patch_embed(src("embeddings.patch_embedding.weight"), wpatch_, (int)C, (int)P, s));
-    RUN(copy16(cls_, src("embeddings.class_embedding"), C, s));
-    RUN(copy16(pos_, src("embeddings.position_embedding.weight"), T * C, s));
-    RUN(to32(preg_, "pre_layrnorm.weight", C));
-    RUN(to32(preb_, "pre_layrnorm.bias", C));
-    for (int i = 0; i < cfg_.layers; ++i) {
-        Layer& l = layers_[i];
-        const std::string p = "encoder.layers." + std::to_string(i) + ".";
-        const char* qkv[3] = {"q_proj", "k_proj", "v_proj"};
-        for (int j = 0; j < 3; ++j) {
-            RUN(copy16(l.wqkv + j * C * C, src(p + "self_attn." + qkv[j] + ".weight"), C * C, s));
-            RUN(to32(l.bqkv + j * C, p + "self_attn." + qkv[j] + ".bias", C));
-        }
-        RUN(copy16(l.wo, src(p + "self_attn.out_proj.weight"), C * C, s));
-        RUN(to32(l.bo, p + "self_attn.out_proj.bias", C));
-        RUN(copy16(l.w1, src(p + "mlp.fc1.weight"), I * C, s));
-        RUN(to32(l.b1, p + "mlp.fc1.bias", I));
-        RUN(copy16(l.w2, src(p + "mlp.fc2.weight"), C * I, s));
-        RUN(to32(l.b2, p + "mlp.fc2.bias", C));
-        RUN(to32(l.ln1g, p + "layer_norm1.weight", C));
-        RUN(to32(l.ln1b, p + "layer_norm1.bias", C));
-        RUN(to32(l.ln2g, p + "layer_norm2.weight", C));
-        RUN(to32(l.ln2b, p + "layer_norm2.bias", C));
-    }
+    }));
+    RUN(launch_pack_patch_embed(table_.src(kVis + "embeddings.patch_embedding.weight"), wpatch_, (int)C, cfg_.patch_size, s));
+    RUN(copy16(cls_, table_.src(kVis + "embeddings.class_embedding"), C, s));
+    RUN(copy16(pos_, table_.src(kVis + "embeddings.position_embedding.weight"), T * C, s));
+    RUN(launch_f16_to_f32(table_.src(kVis + "pre_layrnorm.weight"), preg_, (int64_t)C, s));
+    RUN(launch_f16_to_f32(table_.src(kVis + "pre_layrnorm.bias"), preb_, (int64_t)C, s));
+    for (int i = 0; i < cfg_.layers; ++i)
+        RUN(pack_clip_layer(table_, kVis + "encoder.layers." + std::to_string(i) + ".", layers_[i], shape_, s));
     table_.release();
-    finalized_ = true;
+    block_.finalized = true;
     return 0;
 }
 
-// x [M, C] | h [M, C] | wide [M, max(3 C, I)] | the gathered patches
+// the CLIP layers' workspace | the gathered patches
 long long VisionEncoder::workspace_bytes(int B) const {
     if (check_batch("vision_workspace_bytes", B)) return -1;
-    const size_t M = (size_t)B * tokens(), C = cfg_.hidden, I = cfg_.intermediate, wide = 3 * C > I ? 3 * C : I;
-    return (long long)(2 * up256(M * C * H) + up256(M * wide * H)) + patch_embed_workspace_bytes(B, cfg_.image_size, cfg_.patch_size);
+    Carver c{nullptr};
+    carve_clip_workspace(c, (size_t)B * tokens(), shape_);
+    return (long long)c.used + patch_embed_workspace_bytes(B, cfg_.image_size, cfg_.patch_size);
 }
 
 int VisionEncoder::encode(const void* px, int x_dtype, int B, void* out, hipStream_t s) {
-    LAVIE_CHECK(finalized_, "vision_encode: the handle is not finalized");
+    LAVIE_CHECK(block_.finalized, "vision_encode: the handle is not finalized");
     LAVIE_CHECK(px != nullptr, "vision_encode: pixel_values is null");
     LAVIE_CHECK(out != nullptr, "vision_encode: out_f16 is null");
     LAVIE_CHECK(x_dtype == 0 || x_dtype == 1, "vision_encode: x_dtype=%d (0 = fp16, 1 = fp32)", x_dtype);
     RUN(check_batch("vision_encode", B));
-    const int T = tokens(), M = B * T, C = cfg_.hidden, I = cfg_.intermediate, heads = cfg_.heads, dh = C / heads;
-    const size_t mc = up256((size_t)M * C * H), wide_c = 3 * C > I ? 3 * C : I;
-    half_t* x = (half_t*)ws_;
-    half_t* h = (half_t*)(ws_ + mc);
-    half_t* wide = (half_t*)(ws_ + 2 * mc);
-    half_t* cols = (half_t*)(ws_ + 2 * mc + up256((size_t)M * wide_c * H));
-    const float scale = 1.0f / sqrtf((float)dh);
-    RUN(launch_patch_embed(px, x_dtype == 1, wpatch_, cls_, pos_, h, cols, B, cfg_.image_size, cfg_.patch_size, C, s));
-    RUN(launch_layernorm(h, preg_, preb_, x, M, C, cfg_.eps, s));
-    for (size_t i = 0; i < layers_.size(); ++i) {
-        const Layer& l = layers_[i];
-        half_t* last = i + 1 == layers_.size() ? (half_t*)out : x;      // the last residual sum is last_hidden_state
-        RUN(launch_layernorm(x, l.ln1g, l.ln1b, h, M, C, cfg_.eps, s));
-        RUN(pinned_linear(h, l.wqkv, l.bqkv, nullptr, wide, M, 3 * C, C, s));
-        RUN(launch_short_attention(wide, 3 * C, wide + C, 3 * C, wide + 2 * C, 3 * C, h, C, B, T, T, heads, dh, scale, false, s));
-        RUN(pinned_linear(h, l.wo, l.bo, x, x, M, C, C, s));
-        RUN(launch_layernorm(x, l.ln2g, l.ln2b, h, M, C, cfg_.eps, s));
-        RUN(pinned_linear(h, l.w1, l.b1, nullptr, wide, M, I, C, s));
-        RUN(launch_act(wide, (int64_t)M * I, cfg_.act, s));
-        RUN(pinned_linear(wide, l.w2, l.b2, x, last, M, C, I, s));
-    }
+    const int T = tokens(), C = cfg_.hidden;
+    Carver c{block_.ws};
+    const ClipWorkspace w = carve_clip_workspace(c, (size_t)B * T, shape_);
+    half_t* cols = (half_t*)(block_.ws + c.used);
+    RUN(launch_patch_embed(px, x_dtype == 1, wpatch_, cls_, pos_, w.h, cols, B, cfg_.image_size, cfg_.patch_size, C, s));
+    RUN(launch_layernorm(w.h, preg_, preb_, w.x, B * T, C, cfg_.eps, s));
+    for (size_t i = 0; i < layers_.size(); ++i)      // the last residual sum is last_hidden_state
+        RUN(run_clip_layer(layers_[i], shape_, w, B, T, false, i + 1 == layers_.size() ? (half_t*)out : w.x, s));
     return 0;
 }
 
@@ -276,10 +142,6 @@ ImageMapper::ImageMapper(const lavie_mapper_config& cfg) : cfg_(cfg) {
     table_.ignore("text_proj.bias");
 }
 
-ImageMapper::~ImageMapper() {
-    if (block_) (void)hipFree(block_);
-}
-
 int ImageMapper::validate_config() const {
     const lavie_mapper_config& c = cfg_;
     LAVIE_CHECK(c.input_dim >= IGEMM_BK && c.input_dim % IGEMM_BK == 0 && c.input_dim <= 16384,
@@ -298,18 +160,16 @@ int ImageMapper::validate_config() const {
 }
 
 int ImageMapper::set_param(const char* name, const void* data, long long numel) {
-    LAVIE_CHECK(!finalized_, "mapper_set_param: the handle is finalized");
+    RUN(check_open(block_, "mapper_set_param"));
     return table_.set("mapper_set_param", "", name, data, numel);
 }
 
 int ImageMapper::finalize(hipStream_t s) {
-    LAVIE_CHECK(!finalized_, "mapper_finalize: the handle is finalized already");
+    RUN(check_open(block_, "mapper_finalize", " already"));
     RUN(table_.all_set("mapper_finalize"));
     const size_t C = cfg_.output_dim, D = cfg_.input_dim, FF = cfg_.dim_feedforward;
-    const long long ws = workspace_bytes(kImageMaxBatch);
-    if (ws < 0) return -1;
     layers_.resize(cfg_.layers);
-    auto carve = [&](char* base) {
+    RUN(allocate(block_, workspace_bytes(kImageMaxBatch), [&](char* base) {
         Carver c{base};
         wimg_ = c.take<half_t>(C * D);
         ipos_ = c.take<half_t>((size_t)cfg_.seq_in * C);
@@ -331,12 +191,7 @@ int ImageMapper::finalize(hipStream_t s) {
             for (float** n : {&l.n1g, &l.n1b, &l.n2g, &l.n2b, &l.n3g, &l.n3b}) *n = c.take<float>(C);
         }
         return c.used;
-    };
-    const size_t weights = carve(nullptr);
-    if (block_) { (void)hipFree(block_); block_ = nullptr; }
-    LAVIE_HIP(hipMalloc((void**)&block_, weights + (size_t)ws));
-    carve(block_);
-    ws_ = block_ + weights;
+    }));
     auto src = [&](const std::string& n) { return table_.src(n); };
     auto to32 = [&](float* dst, const std::string& n, size_t count) { return launch_f16_to_f32(src(n), dst, (int64_t)count, s); };
     RUN(copy16(wimg_, src("image_proj.weight"), C * D, s));
@@ -366,7 +221,7 @@ int ImageMapper::finalize(hipStream_t s) {
         RUN(to32(l.n3b, p + "norm3.bias", C));
     }
     table_.release();
-    finalized_ = true;
+    block_.finalized = true;
     return 0;
 }
 
@@ -379,7 +234,7 @@ long long ImageMapper::workspace_bytes(int B) const {
 }
 
 int ImageMapper::encode(const void* image_feats, int Bi, const void* text, int B, void* out, int ld_out_rows, int row0, hipStream_t s) {
-    LAVIE_CHECK(finalized_, "mapper_encode: the handle is not finalized");
+    LAVIE_CHECK(block_.finalized, "mapper_encode: the handle is not finalized");
     LAVIE_CHECK(image_feats != nullptr, "mapper_encode: image_feats is null");
     LAVIE_CHECK(text != nullptr, "mapper_encode: text is null");
     LAVIE_CHECK(out != nullptr, "mapper_encode: out is null");
@@ -390,7 +245,7 @@ int ImageMapper::encode(const void* image_feats, int Bi, const void* text, int B
                 "mapper_encode: row0=%d + seq_out=%d rows do not fit ld_out_rows=%d", row0, So, ld_out_rows);
     const int heads = cfg_.heads, dh = C / heads, Mi = Bi * Si, Mo = B * So;
     // the carve of the workspace follows workspace_bytes(B): an encode at B uses no byte past it
-    Carver c{ws_};
+    Carver c{block_.ws};
     const size_t wide_c = 3 * C > FF ? 3 * C : FF;
     half_t* mem = c.take<half_t>((size_t)B * Si * C);
     half_t* kv = c.take<half_t>((size_t)B * Si * 2 * C);

@@ -13,6 +13,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib, ops
+from ._engine_object import LastHiddenState, _EngineObject, _load, clip_config_dict, clip_layer_keys
 
 ACTS = ops.ACT_KINDS                  # hidden_act -> lavie_vision_config.act
 MAX_BATCH = 16                        # lavie_vision_encode, lavie_mapper_encode: 1 <= B <= 16
@@ -27,15 +28,8 @@ MAPPER_IGNORED = ("text_proj.weight", "text_proj.bias")        # built and saved
 def vision_state_dict_keys(config: dict):
     """The keys the engine expects, in its order: those of CLIPVisionModel(config).state_dict() minus VISION_IGNORED."""
     v = "vision_model."
-    keys = [v + "embeddings.class_embedding", v + "embeddings.patch_embedding.weight", v + "embeddings.position_embedding.weight",
-            v + "pre_layrnorm.weight", v + "pre_layrnorm.bias"]
-    for i in range(int(config["num_hidden_layers"])):
-        p = f"{v}encoder.layers.{i}."
-        for proj in ("k_proj", "v_proj", "q_proj", "out_proj"):
-            keys += [f"{p}self_attn.{proj}.weight", f"{p}self_attn.{proj}.bias"]
-        keys += [f"{p}layer_norm1.weight", f"{p}layer_norm1.bias", f"{p}mlp.fc1.weight", f"{p}mlp.fc1.bias",
-                 f"{p}mlp.fc2.weight", f"{p}mlp.fc2.bias", f"{p}layer_norm2.weight", f"{p}layer_norm2.bias"]
-    return keys
+    return [v + "embeddings.class_embedding", v + "embeddings.patch_embedding.weight", v + "embeddings.position_embedding.weight",
+            v + "pre_layrnorm.weight", v + "pre_layrnorm.bias"] + clip_layer_keys(v, config["num_hidden_layers"])
 
 
 def normalize_vision_keys(sd: dict) -> dict:
@@ -55,14 +49,7 @@ def vision_config_dict(config) -> dict:
     """The eight fields the engine reads, from a transformers CLIPVisionConfig (or a CLIPConfig holding one) or a dict."""
     if not isinstance(config, dict) and getattr(config, "vision_config", None) is not None:
         config = config.vision_config
-    get = config.get if isinstance(config, dict) else lambda k, d=None: getattr(config, k, d)
-    cfg = {k: get(k) for k in VISION_CONFIG_KEYS}
-    cfg["hidden_act"] = cfg["hidden_act"] or "quick_gelu"
-    cfg["layer_norm_eps"] = 1e-5 if cfg["layer_norm_eps"] is None else cfg["layer_norm_eps"]
-    missing = [k for k, v in cfg.items() if v is None]
-    if missing:
-        raise ValueError(f"vision tower config lacks {missing}")
-    return cfg
+    return clip_config_dict(config, VISION_CONFIG_KEYS, "vision tower")
 
 
 def vision_config_c(cfg: dict) -> "_lib.VisionConfigC":
@@ -76,59 +63,13 @@ def vision_config_c(cfg: dict) -> "_lib.VisionConfigC":
     return c
 
 
-class VisionEncoderOutput(tuple):
+class VisionEncoderOutput(LastHiddenState):
     """`out[0]` and `out.last_hidden_state`, as the stock model's output offers them; the pooled output is not built."""
-
-    def __new__(cls, last_hidden_state):
-        return super().__new__(cls, (last_hidden_state,))
-
-    @property
-    def last_hidden_state(self):
-        return self[0]
 
     @property
     def pooler_output(self):
         raise NotImplementedError("HipCLIPVisionModel: `pooler_output` is not built (post_layernorm of the class token belongs to "
                                   "the pooled output; the mapper reads last_hidden_state)")
-
-
-def _load(lib, prefix, h, want, sd, device):
-    """set_param for every key of `want`, finalize, and the end of the loan"""
-    with torch.cuda.device(device):
-        held = []
-        for k in want:
-            t = sd[k].detach().to(device=device, dtype=torch.float16).contiguous()
-            held.append(t)
-            _lib.check(getattr(lib, prefix + "_set_param")(h, k.encode(), ctypes.c_void_p(t.data_ptr()), t.numel()), prefix + "_set_param")
-        _lib.check(getattr(lib, prefix + "_finalize")(h, ops._stream()), prefix + "_finalize")
-        torch.cuda.current_stream().synchronize()      # the tensors were borrowed until the stream drains
-    del held
-
-
-class _EngineObject:
-    """What the pipelines ask of every part: .to(device), .eval(), .parameters(); the engine copy stays where it was built."""
-    _destroy = None
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                getattr(_lib.load(), self._destroy)(self._h)
-            except Exception:
-                pass
-            self._h = None
-
-    def to(self, device=None, *args, **kwargs):
-        if device is not None and not isinstance(device, torch.dtype):
-            d = torch.device(device)
-            if d.type != "cuda" or (d.index is not None and self.device.index is not None and d.index != self.device.index):
-                raise ValueError(f"{type(self).__name__} was built on {self.device} and cannot move to {d}")
-        return self
-
-    def eval(self):
-        return self
-
-    def parameters(self):
-        return iter(())
 
 
 class HipCLIPVisionModel(_EngineObject):

@@ -10,6 +10,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib, ops
+from ._engine_object import LastHiddenState, _EngineObject, _load, clip_config_dict, clip_layer_keys
 
 ACTS = ops.ACT_KINDS                  # hidden_act -> lavie_text_config.act
 MAX_BATCH = 16                        # lavie_text_encode: 1 <= B <= 16
@@ -20,14 +21,9 @@ IGNORED_KEYS = ("text_model.embeddings.position_ids",)      # a buffer of older 
 
 def state_dict_keys(config: dict):
     """The keys the engine expects, in its order: those of CLIPTextModel(config).state_dict() (see normalize_keys)."""
-    keys = ["text_model.embeddings.token_embedding.weight", "text_model.embeddings.position_embedding.weight"]
-    for i in range(int(config["num_hidden_layers"])):
-        p = f"text_model.encoder.layers.{i}."
-        for proj in ("k_proj", "v_proj", "q_proj", "out_proj"):
-            keys += [f"{p}self_attn.{proj}.weight", f"{p}self_attn.{proj}.bias"]
-        keys += [f"{p}layer_norm1.weight", f"{p}layer_norm1.bias", f"{p}mlp.fc1.weight", f"{p}mlp.fc1.bias",
-                 f"{p}mlp.fc2.weight", f"{p}mlp.fc2.bias", f"{p}layer_norm2.weight", f"{p}layer_norm2.bias"]
-    return keys + ["text_model.final_layer_norm.weight", "text_model.final_layer_norm.bias"]
+    return (["text_model.embeddings.token_embedding.weight", "text_model.embeddings.position_embedding.weight"]
+            + clip_layer_keys("text_model.", config["num_hidden_layers"])
+            + ["text_model.final_layer_norm.weight", "text_model.final_layer_norm.bias"])
 
 
 def normalize_keys(sd: dict) -> dict:
@@ -43,14 +39,7 @@ def normalize_keys(sd: dict) -> dict:
 
 def config_dict(config) -> dict:
     """The eight fields the engine reads, from a transformers CLIPTextConfig or a dict with its names."""
-    get = config.get if isinstance(config, dict) else lambda k, d=None: getattr(config, k, d)
-    cfg = {k: get(k) for k in CONFIG_KEYS}
-    cfg["hidden_act"] = cfg["hidden_act"] or "quick_gelu"
-    cfg["layer_norm_eps"] = 1e-5 if cfg["layer_norm_eps"] is None else cfg["layer_norm_eps"]
-    missing = [k for k, v in cfg.items() if v is None]
-    if missing:
-        raise ValueError(f"text encoder config lacks {missing}")
-    return cfg
+    return clip_config_dict(config, CONFIG_KEYS, "text encoder")
 
 
 def config_c(cfg: dict) -> "_lib.TextConfigC":
@@ -64,18 +53,13 @@ def config_c(cfg: dict) -> "_lib.TextConfigC":
     return c
 
 
-class TextEncoderOutput(tuple):
-    """`out[0]` and `out.last_hidden_state`, as the stock model's output offers them."""
-
-    def __new__(cls, last_hidden_state):
-        return super().__new__(cls, (last_hidden_state,))
-
-    @property
-    def last_hidden_state(self):
-        return self[0]
+class TextEncoderOutput(LastHiddenState):
+    """What `HipCLIPTextModel.__call__` returns."""
 
 
-class HipCLIPTextModel:
+class HipCLIPTextModel(_EngineObject):
+    _destroy = "lavie_text_destroy"
+
     def __init__(self, state_dict, config, device="cuda"):
         """state_dict: CLIPTextModel.state_dict() (any float dtype; rounded to fp16 here); config: CLIPTextConfig or dict."""
         self._cfg = config_dict(config)
@@ -96,15 +80,7 @@ class HipCLIPTextModel:
         h = ctypes.c_void_p()
         _lib.check(lib.lavie_text_create(ctypes.byref(c), ctypes.byref(h)), "lavie_text_create")
         self._h = h
-        with torch.cuda.device(self.device):
-            held = []
-            for k in want:
-                t = sd[k].detach().to(device=self.device, dtype=torch.float16).contiguous()
-                held.append(t)
-                _lib.check(lib.lavie_text_set_param(h, k.encode(), ctypes.c_void_p(t.data_ptr()), t.numel()), "lavie_text_set_param")
-            _lib.check(lib.lavie_text_finalize(h, ops._stream()), "lavie_text_finalize")
-            torch.cuda.current_stream().synchronize()      # the tensors were borrowed until the stream drains
-        del held
+        _load(lib, "lavie_text", h, want, sd, self.device)
 
     @classmethod
     def from_stock(cls, clip_text_model, device=None):
@@ -118,28 +94,6 @@ class HipCLIPTextModel:
     @classmethod
     def from_state_dict(cls, sd, config_dict, device="cuda"):
         return cls(sd, config_dict, device=device)
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                _lib.load().lavie_text_destroy(self._h)
-            except Exception:
-                pass
-            self._h = None
-
-    def to(self, device=None, *args, **kwargs):
-        """The pipelines call .to(device) on every part: the engine copy stays where it was built; another device is refused."""
-        if device is not None and not isinstance(device, torch.dtype):
-            d = torch.device(device)
-            if d.type != "cuda" or (d.index is not None and self.device.index is not None and d.index != self.device.index):
-                raise ValueError(f"HipCLIPTextModel was built on {self.device} and cannot move to {d}")
-        return self
-
-    def eval(self):
-        return self
-
-    def parameters(self):
-        return iter(())
 
     def workspace_bytes(self, b, l):
         n = _lib.load().lavie_text_workspace_bytes(self._h, b, l)
