@@ -1074,6 +1074,70 @@ int lavie_clip_embed_f16(const void* x, int B, int L, int C, const int* ids_dev,
  * (CLIPSIM on normalised features).  img fp32 [N, D], txt fp32 [P, D].  Fixed order, no atomics.  One launch, capturable. */
 int lavie_clip_similarity_f32(const float* img, const float* txt, float* out, int N, int P, int D, int frames, float scale, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * FVD on the engine (additive in ABI 8): 3-D convolutions, the R3D-18 feature extractor, the video processor
+ * ---------------------------------------------------------------------------------------------- */
+/* Halfs of the packed weights of a Conv3d [Cout, Cin, kt, kh, kw]: Cout rows of kt kh kw Cin halfs rounded up to a multiple of 64;
+ * -1 for an extent outside 1..7 or a width outside 1..4096. */
+long long lavie_conv3d_packed_halfs(int Cout, int Cin, int kt, int kh, int kw);
+/* w fp16 [Cout, Cin, kt, kh, kw] -> out fp16 [Cout][kt][kh][kw][Cin], each row zero-padded to a multiple of 64 halfs. */
+int lavie_conv3d_pack(const void* w_f16, void* out_f16, int Cout, int Cin, int kt, int kh, int kw, void* stream);
+/* y = relu?(conv3d(x) + bias + residual) on channels-last fp16 rows: x [N, T, H, W, Cin] -> y [N, To, Ho, Wo, Cout], extents
+ * floor((n - 1) / stride) + 1.  Built: ksize 3 (kernel (3,3,3), padding 1) with stride 1 or 2 on all three axes, and ksize 1 (kernel
+ * (1,1,1), no padding) with stride 2; Cin and Cout each 64, 128, 256 or 512; everything else is refused by name.  wp: lavie_conv3d_pack's
+ * image; bias fp32 [Cout] (required); residual fp16 [N To Ho Wo, Cout] or null, may be y itself.  fp32 accumulation over the taps in
+ * (t, h, w) order, channels inside a tap, taps outside the volume contributing zeros; bias, residual and ReLU in fp32; one fp16
+ * rounding.  One tile geometry, no split-K, no atomics: an output row's bits depend on its own inputs only.  One launch, capturable. */
+int lavie_conv3d_f16(const void* x, const void* wp, const float* bias, const void* residual, int relu, void* y, int N, int T, int H, int W,
+                     int Cin, int Cout, int ksize, int stride, void* stream);
+/* The stem of a video ResNet: Conv3d(3, 64, kernel (3,7,7), stride (1,2,2), padding (1,3,3)) + bias (+ ReLU) from pixels to
+ * channels-last fp16 rows y [N, T, Ho, Wo, 64].  Pixel (n, t, c, h, w) is read at element n stride_n + t stride_t + c stride_c + h W + w
+ * of `pixels` (x_dtype 0 = fp16, 1 = fp32, rounded to fp16 on the way in): frames-major planar [N T, 3, H, W] is (3 T H W, 3 H W, H W),
+ * channels-first [N, 3, T, H, W] is (3 T H W, H W, T H W); each stride at least H W.  wp: lavie_conv3d_pack(w, ., 64, 3, 3, 7, 7): 448
+ * halfs per row, 441 of them weights. */
+int lavie_conv3d_stem_f16(const void* pixels, int x_dtype, long long stride_n, long long stride_t, long long stride_c, const void* wp,
+                          const float* bias, int relu, void* y, int N, int T, int H, int W, void* stream);
+/* out fp32 [N, C] = the mean over the rows of x fp16 [N, rows, C] (AdaptiveAvgPool3d(1) of channels-last rows): per (n, c) four
+ * sequential fp32 partials (rows r = g, g + 4, ...) summed (p0 + p1) + (p2 + p3), then one division.  No atomics.  N up to 65535. */
+int lavie_mean_rows_f32(const void* x, float* out, int N, int rows, int C, void* stream);
+
+/* R3D-18 without its classifier (torchvision's r3d_18 layout: stem, layer1 .. layer4 of two basic blocks, mean over positions).
+ * Lifecycle as lavie_vision_*: create, set_param for every tensor, finalize, then features.  Parameters are fp32 DEVICE tensors,
+ * borrowed until finalize's work on `stream` has drained.  Names: stem.0.weight, stem.1.{weight, bias, running_mean, running_var},
+ * layerL.B.conv{1,2}.0.weight, layerL.B.conv{1,2}.1.*, layerL.0.downsample.{0.weight, 1.*} (L = 2..4); also with the numeric prefixes
+ * of nn.Sequential(*children[:-1]) ("0." = stem, "1." .. "4." = layer1 .. layer4).  fc.* and *.num_batches_tracked are accepted and
+ * ignored; any other name, and a wrong element count, is refused by name.  finalize folds every BatchNorm (eps 1e-5) into its conv:
+ * scale = weight / sqrt(running_var + eps) in double, conv weight times scale rounded once to fp16, shift = bias - running_mean scale
+ * kept in fp32; a tensor never set is refused by name. */
+typedef struct lavie_r3d_s* lavie_r3d_t;
+int lavie_r3d_create(lavie_r3d_t* out);
+int lavie_r3d_destroy(lavie_r3d_t h);
+int lavie_r3d_num_params(lavie_r3d_t h);
+int lavie_r3d_param_info(lavie_r3d_t h, int i, const char** name, long long* numel);
+int lavie_r3d_set_param(lavie_r3d_t h, const char* name, const void* data_f32, long long numel);
+int lavie_r3d_finalize(lavie_r3d_t h, void* stream);
+/* Bytes of the workspace lavie_r3d_features(h, ..., N, T, H, W, ...) uses; -1 with a message for a shape it refuses. */
+long long lavie_r3d_workspace_bytes(lavie_r3d_t h, int N, int T, int H, int W);
+/* out_f32 [N, 512] = the features of N clips of T frames H x W, any extents >= 1 (the model's own: 16 x 224 x 224).  pixels, x_dtype
+ * and the three strides as lavie_conv3d_stem_f16.  Refused by name, nothing launched: a null handle or tensor, a handle that is not
+ * finalized, an extent below 1, N above 65535, strides below H W, a workspace below lavie_r3d_workspace_bytes.  21 launches on
+ * `stream`, capturable.  A clip's features have the same bits at every N and at every position in the batch. */
+int lavie_r3d_features(lavie_r3d_t h, const void* pixels, int x_dtype, long long stride_n, long long stride_t, long long stride_c, int N,
+                       int T, int H, int W, float* out_f32, void* workspace, long long workspace_bytes, void* stream);
+
+/* One axis of Pillow's 8-bit BILINEAR resampling (support max(in / out, 1)); everything else as lavie_clip_resample_table_host.
+ * Returns ksize = 2 ceil(max(in / out, 1)) + 1. */
+int lavie_video_resample_table_host(int in, int out, int* xmin_out, int* count_out, int* coeff_out);
+long long lavie_video_preprocess_workspace_bytes(int B, int H, int W, int crop, int size);
+/* The per-frame transform of the FVD evaluation: centre crop of `crop` x `crop` pixels (offsets round-half-even((n - crop) / 2), as
+ * torchvision's CenterCrop), Pillow's bilinear resize of that square to size x size, rescale by 1 / 255, normalise.  in_u8 uint8
+ * [B, H, W, 3] -> out [B, 3, size, size]; pitches, out_dtype, workspace, the table cache and the refusals as lavie_clip_preprocess_u8,
+ * with these differences: a crop greater than H or W is refused (the stock transform pads there), the scale is crop / size.  mean and
+ * std point at three floats each (host).  fp32 output has the bits of Pillow followed by (v / 255 - mean) / std in fp32. */
+int lavie_video_preprocess_u8(const void* in_u8, int B, int H, int W, long long row_pitch, long long image_pitch, void* out, int out_dtype,
+                              int crop, int size, const float* mean3, const float* std3, void* workspace, long long workspace_bytes,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,13 +8,15 @@ entry points without the built library raises.
 The encoders that feed the UNet its context run on the engine as well: `lavie_amd.text_encoder.HipCLIPTextModel`,
 `lavie_amd.image_encoder.HipCLIPVisionModel` and `HipMappingNetwork` (imported on use: they need the built library).
 `lavie_amd.HipCLIPImageProcessor` and `lavie_amd.ClipScorer` (lavie_amd.clip_score) turn uint8 pixels and token ids into
-pixel_values, CLIP features and CLIPSIM scores; they too are imported on first use.
+pixel_values, CLIP features and CLIPSIM scores; they too are imported on first use.  `lavie_amd.HipR3D18`, `VideoProcessor`,
+`FvdScorer`, `FrechetStats` and `frechet_distance` (lavie_amd.fvd) score clip quality by FVD on R3D-18 features.
 """
 from .config import UNetConfig, BASE_CONFIG  # noqa: F401
 
 __version__ = "0.1.0"
 
-_LAZY = {"HipCLIPImageProcessor": "clip_score", "ClipScorer": "clip_score"}
+_LAZY = {"HipCLIPImageProcessor": "clip_score", "ClipScorer": "clip_score", "HipR3D18": "fvd", "VideoProcessor": "fvd", "FvdScorer": "fvd",
+         "FrechetStats": "fvd", "frechet_distance": "fvd"}
 
 
 def __getattr__(name):

@@ -324,6 +324,26 @@ SIGNATURES = {
     "lavie_clip_embed_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float_p, c_float_p, c_float, c_void_p, c_int,
                                      c_int, c_float_p, c_void_p]),
     "lavie_clip_similarity_f32": (c_int, [c_float_p, c_float_p, c_float_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "lavie_conv3d_packed_halfs": (c_ll, [c_int, c_int, c_int, c_int, c_int]),
+    "lavie_conv3d_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "lavie_conv3d_f16": (c_int, [c_void_p, c_void_p, c_float_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                 c_int, c_void_p]),
+    "lavie_conv3d_stem_f16": (c_int, [c_void_p, c_int, c_ll, c_ll, c_ll, c_void_p, c_float_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                      c_void_p]),
+    "lavie_mean_rows_f32": (c_int, [c_void_p, c_float_p, c_int, c_int, c_int, c_void_p]),
+    "lavie_r3d_create": (c_int, [C.POINTER(c_void_p)]),
+    "lavie_r3d_destroy": (c_int, [c_void_p]),
+    "lavie_r3d_num_params": (c_int, [c_void_p]),
+    "lavie_r3d_param_info": (c_int, [c_void_p, c_int, C.POINTER(c_char_p), C.POINTER(c_ll)]),
+    "lavie_r3d_set_param": (c_int, [c_void_p, c_char_p, c_void_p, c_ll]),
+    "lavie_r3d_finalize": (c_int, [c_void_p, c_void_p]),
+    "lavie_r3d_workspace_bytes": (c_ll, [c_void_p, c_int, c_int, c_int, c_int]),
+    "lavie_r3d_features": (c_int, [c_void_p, c_void_p, c_int, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_int, c_float_p, c_void_p, c_ll,
+                                   c_void_p]),
+    "lavie_video_resample_table_host": (c_int, [c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
+    "lavie_video_preprocess_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int, c_int]),
+    "lavie_video_preprocess_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_ll, c_ll, c_void_p, c_int, c_int, c_int, C.POINTER(c_float),
+                                          C.POINTER(c_float), c_void_p, c_ll, c_void_p]),
 }
 
 _lib = None

@@ -6,6 +6,7 @@
 #include "engine.h"
 #include "image_engine.h"
 #include "profile.h"
+#include "r3d_engine.h"
 #include "text_engine.h"
 
 using namespace lavie;
@@ -28,6 +29,10 @@ struct lavie_vision_s {
 struct lavie_mapper_s {
     ImageMapper enc;
     explicit lavie_mapper_s(const lavie_mapper_config& c) : enc(c) {}
+};
+
+struct lavie_r3d_s {
+    R3dEngine enc;
 };
 
 static inline hipStream_t S(void* s) { return (hipStream_t)s; }
@@ -1438,6 +1443,65 @@ int lavie_clip_embed_f16(const void* x, int B, int L, int C, const int* ids_dev,
 
 int lavie_clip_similarity_f32(const float* img, const float* txt, float* out, int N, int P, int D, int frames, float scale, void* stream) {
     return launch_clip_similarity(img, txt, out, N, P, D, frames, scale, S(stream));
+}
+
+// ---- FVD: 3-D convolutions, the R3D-18 engine, the video processor (conv3d.hip, r3d_engine.cpp, clip_engine.cpp)
+long long lavie_conv3d_packed_halfs(int Cout, int Cin, int kt, int kh, int kw) { return conv3d_packed_halfs(Cout, Cin, kt, kh, kw); }
+
+int lavie_conv3d_pack(const void* w_f16, void* out_f16, int Cout, int Cin, int kt, int kh, int kw, void* stream) {
+    return launch_conv3d_pack(H(w_f16), H(out_f16), Cout, Cin, kt, kh, kw, S(stream));
+}
+
+int lavie_conv3d_f16(const void* x, const void* wp, const float* bias, const void* residual, int relu, void* y, int N, int T, int H_, int W,
+                     int Cin, int Cout, int ksize, int stride, void* stream) {
+    return launch_conv3d(H(x), H(wp), bias, H(residual), relu != 0, H(y), N, T, H_, W, Cin, Cout, ksize, stride, S(stream));
+}
+
+int lavie_conv3d_stem_f16(const void* pixels, int x_dtype, long long stride_n, long long stride_t, long long stride_c, const void* wp,
+                          const float* bias, int relu, void* y, int N, int T, int H_, int W, void* stream) {
+    LAVIE_CHECK(x_dtype == 0 || x_dtype == 1, "conv3d_stem: x_dtype=%d (0 = fp16, 1 = fp32)", x_dtype);
+    return launch_conv3d_stem(pixels, x_dtype == 1, stride_n, stride_t, stride_c, H(wp), bias, relu != 0, H(y), N, T, H_, W, S(stream));
+}
+
+int lavie_mean_rows_f32(const void* x, float* out, int N, int rows, int C, void* stream) {
+    return launch_mean_rows(H(x), out, N, rows, C, S(stream));
+}
+
+int lavie_r3d_create(lavie_r3d_t* out) {
+    LAVIE_CHECK(out, "r3d_create: null argument");
+    lavie_r3d_s* h = new (std::nothrow) lavie_r3d_s();
+    LAVIE_CHECK(h != nullptr, "r3d_create: out of host memory");
+    *out = h;
+    return 0;
+}
+int lavie_r3d_destroy(lavie_r3d_t h) { return encoder_destroy(h); }
+int lavie_r3d_num_params(lavie_r3d_t h) { return encoder_num_params(h); }
+int lavie_r3d_param_info(lavie_r3d_t h, int i, const char** name, long long* numel) { return encoder_param_info("r3d", h, i, name, numel); }
+int lavie_r3d_set_param(lavie_r3d_t h, const char* name, const void* data_f32, long long numel) {
+    return encoder_set_param("r3d", h, name, data_f32, numel);
+}
+int lavie_r3d_finalize(lavie_r3d_t h, void* stream) { return encoder_finalize("r3d", h, stream); }
+long long lavie_r3d_workspace_bytes(lavie_r3d_t h, int N, int T, int H_, int W) { return encoder_workspace_bytes("r3d", h, N, T, H_, W); }
+
+int lavie_r3d_features(lavie_r3d_t h, const void* pixels, int x_dtype, long long stride_n, long long stride_t, long long stride_c, int N,
+                       int T, int H_, int W, float* out_f32, void* workspace, long long workspace_bytes, void* stream) {
+    LAVIE_CHECK(h, "r3d_features: null handle");
+    return h->enc.features(pixels, x_dtype, stride_n, stride_t, stride_c, N, T, H_, W, out_f32, workspace, workspace_bytes, S(stream));
+}
+
+int lavie_video_resample_table_host(int in, int out, int* xmin_out, int* count_out, int* coeff_out) {
+    return video_resample_table_host(in, out, xmin_out, count_out, coeff_out);
+}
+
+long long lavie_video_preprocess_workspace_bytes(int B, int H_, int W, int crop, int size) {
+    return video_preprocess_workspace_bytes(B, H_, W, crop, size);
+}
+
+int lavie_video_preprocess_u8(const void* in_u8, int B, int H_, int W, long long row_pitch, long long image_pitch, void* out, int out_dtype,
+                              int crop, int size, const float* mean3, const float* std3, void* workspace, long long workspace_bytes,
+                              void* stream) {
+    return video_preprocess(in_u8, B, H_, W, row_pitch, image_pitch, out, out_dtype, crop, size, mean3, std3, workspace, workspace_bytes,
+                            S(stream));
 }
 
 }  // extern "C"

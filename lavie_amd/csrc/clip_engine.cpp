@@ -33,17 +33,30 @@ double bicubic(double x) {
     return 0.0;
 }
 
-int axis_ksize(int in, int out) {
+// Pillow's bilinear (triangle) filter, support 1.0: the video processor's resize
+double bilinear(double x) {
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return 1.0 - x;
+    return 0.0;
+}
+
+struct Filter {
+    double (*fn)(double);
+    double support;
+};
+const Filter kBicubic = {bicubic, 2.0}, kBilinear = {bilinear, 1.0};
+
+int axis_ksize(int in, int out, const Filter& f = kBicubic) {
     const double scale = (double)in / (double)out;
     const double fs = scale < 1.0 ? 1.0 : scale;
-    return (int)ceil(2.0 * fs) * 2 + 1;
+    return (int)ceil(f.support * fs) * 2 + 1;
 }
 
 // outputs [first, first + n) of the axis: xmin[n], cnt[n], coeff[n, ksize] (zero behind the taps)
-void axis_table(int in, int out, int first, int n, int* xmin_out, int* cnt_out, int* coeff_out) {
+void axis_table(int in, int out, int first, int n, int* xmin_out, int* cnt_out, int* coeff_out, const Filter& f = kBicubic) {
     const double scale = (double)in / (double)out;
     const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = 2.0 * fs;
+    const double support = f.support * fs;
     const int ksize = (int)ceil(support) * 2 + 1;
     std::vector<double> w((size_t)ksize);
     for (int i = 0; i < n; ++i) {
@@ -56,7 +69,7 @@ void axis_table(int in, int out, int first, int n, int* xmin_out, int* cnt_out, 
         const int cnt = xmax - xmin;
         double ww = 0.0;
         for (int x = 0; x < cnt; ++x) {
-            w[x] = bicubic((x + xmin - center + 0.5) / fs);
+            w[x] = f.fn((x + xmin - center + 0.5) / fs);
             ww += w[x];
         }
         int* k = coeff_out + (size_t)i * ksize;
@@ -107,7 +120,7 @@ int geometry(const char* who, int H, int W, int size, int crop, Geometry* g) {
 }
 
 struct PlanKey {
-    int device, H, W, size, crop;
+    int device, H, W, size, crop, mode;      // mode 0: the CLIP processor (resize, then crop); 1: the video processor (crop, then resize)
     float ms[6];
     bool operator<(const PlanKey& o) const { return memcmp(this, &o, sizeof(PlanKey)) < 0; }
 };
@@ -139,13 +152,15 @@ std::mutex g_mutex;
 std::map<PlanKey, std::shared_ptr<const Plan>>& g_plans = *new std::map<PlanKey, std::shared_ptr<const Plan>>();
 constexpr size_t kMaxPlans = 64;
 
-// g: the geometry of (H, W, size, crop), already validated by the caller
-int get_plan(const char* who, const Geometry& g, int H, int W, int size, int crop, const float* mean, const float* std_,
-             std::shared_ptr<const Plan>* out) {
+// g: the geometry of (H, W, size, crop), already validated by the caller.  nout = outputs per axis (the tables' length);
+// fill(hx, hc, hk, vy, vc, vk) writes the two axes' tables in source coordinates.
+template <class Fill>
+int get_plan(const char* who, int mode, const Geometry& g, int nout, int H, int W, int size, int crop, const float* mean, const float* std_,
+             Fill&& fill, std::shared_ptr<const Plan>* out) {
     PlanKey key;
     memset(&key, 0, sizeof(key));
     LAVIE_HIP(hipGetDevice(&key.device));
-    key.H = H; key.W = W; key.size = size; key.crop = crop;
+    key.H = H; key.W = W; key.size = size; key.crop = crop; key.mode = mode;
     for (int c = 0; c < 3; ++c) { key.ms[c] = mean[c]; key.ms[3 + c] = std_[c]; }
     std::lock_guard<std::mutex> lock(g_mutex);
     auto it = g_plans.find(key);
@@ -153,18 +168,17 @@ int get_plan(const char* who, const Geometry& g, int H, int W, int size, int cro
         *out = it->second;
         return 0;
     }
-    const size_t n_h = (size_t)crop * g.ks_h, n_v = (size_t)crop * g.ks_v;
-    std::vector<int> host(4 * (size_t)crop + n_h + n_v + 768);
+    const size_t n_h = (size_t)nout * g.ks_h, n_v = (size_t)nout * g.ks_v;
+    std::vector<int> host(4 * (size_t)nout + n_h + n_v + 768);
     int* hx = host.data();
-    int* hc = hx + crop;
-    int* hk = hc + crop;
+    int* hc = hx + nout;
+    int* hk = hc + nout;
     int* vy = hk + n_h;
-    int* vc = vy + crop;
-    int* vk = vc + crop;
+    int* vc = vy + nout;
+    int* vk = vc + nout;
     float lut[768];
-    axis_table(W, g.out_w, g.x0, crop, hx, hc, hk);
-    axis_table(H, g.out_h, g.y0, crop, vy, vc, vk);
-    for (int i = 0; i < crop; ++i) {
+    fill(hx, hc, hk, vy, vc, vk);
+    for (int i = 0; i < nout; ++i) {
         LAVIE_CHECK(hx[i] >= 0 && hc[i] >= 1 && hx[i] + hc[i] <= W && hc[i] <= g.ks_h, "%s: internal: column taps [%d, +%d) leave [0, %d)", who,
                     hx[i], hc[i], W);
         LAVIE_CHECK(vy[i] >= g.row0 && vc[i] >= 1 && vy[i] + vc[i] <= g.row0 + g.rows && vc[i] <= g.ks_v,
@@ -187,13 +201,32 @@ int get_plan(const char* who, const Geometry& g, int H, int W, int size, int cro
         set_error("%s: uploading the tables failed: %s", who, hipGetErrorString(e));
         return -2;
     }
-    p->hx = p->dev; p->hc = p->hx + crop; p->hk = p->hc + crop; p->vy = p->hk + n_h; p->vc = p->vy + crop; p->vk = p->vc + crop;
+    p->hx = p->dev; p->hc = p->hx + nout; p->hk = p->hc + nout; p->vy = p->hk + n_h; p->vc = p->vy + nout; p->vk = p->vc + nout;
     p->lut = reinterpret_cast<const float*>(p->vk + n_v);
     g_plans.emplace(key, p);
     *out = p;
     return 0;
 }
 
+// Python's round() of diff / 2 (half to even), as torchvision's CenterCrop computes its offsets
+int centre_offset(int diff) { return (diff & 1) ? ((diff >> 1) + ((diff >> 1) & 1)) : diff >> 1; }
+
+// the video processor: rows [y0, y0 + crop) x columns [x0, x0 + crop) of the frame, resized to size x size by the bilinear filter
+int video_geometry(const char* who, int H, int W, int crop, int size, Geometry* g) {
+    LAVIE_CHECK(H >= 1 && W >= 1 && H <= 65535 && W <= 65535, "%s: H=%d W=%d must be in 1..65535", who, H, W);
+    LAVIE_CHECK(size >= 1 && size <= 16384, "%s: size=%d must be in 1..16384", who, size);
+    LAVIE_CHECK(crop >= 1, "%s: crop=%d must be at least 1", who, crop);
+    LAVIE_CHECK(crop <= H && crop <= W, "%s: crop=%d is greater than the frame %d x %d (the stock transform pads there: not built)", who, crop,
+                H, W);
+    LAVIE_CHECK((double)crop / size <= 32.0, "%s: scale %.3f is above 32 (crop=%d to size=%d)", who, (double)crop / size, crop, size);
+    g->out_h = g->out_w = size;
+    g->y0 = centre_offset(H - crop);
+    g->x0 = centre_offset(W - crop);
+    g->ks_h = g->ks_v = axis_ksize(crop, size, kBilinear);
+    g->row0 = g->y0;              // the horizontal pass runs over every row of the crop
+    g->rows = crop;
+    return 0;
+}
 size_t mid_bytes(int B, const Geometry& g, int crop) { return ((size_t)B * g.rows * crop * 3 + 255) / 256 * 256; }
 
 }  // namespace
@@ -240,12 +273,73 @@ int clip_preprocess(const void* in_u8, int B, int H, int W, long long row_pitch,
     LAVIE_CHECK(workspace != nullptr && workspace_bytes >= need, "%s: the workspace holds %lld bytes, this call needs %lld", who,
                 workspace ? workspace_bytes : 0ll, need);
     std::shared_ptr<const Plan> p;                     // every refusal is behind us: only now is the device touched
-    if (int rc = get_plan(who, g, H, W, size, crop, mean, std_, &p)) return rc;
+    auto fill = [&](int* hx, int* hc, int* hk, int* vy, int* vc, int* vk) {
+        axis_table(W, g.out_w, g.x0, crop, hx, hc, hk);
+        axis_table(H, g.out_h, g.y0, crop, vy, vc, vk);
+    };
+    if (int rc = get_plan(who, 0, g, crop, H, W, size, crop, mean, std_, fill, &p)) return rc;
     uint8_t* mid = (uint8_t*)workspace;
     if (int rc = launch_clip_resample_h((const uint8_t*)in_u8, row_pitch, B == 1 ? 0 : image_pitch, mid, B, p->g.row0, p->g.rows, crop, p->hx, p->hc,
                                         p->hk, p->g.ks_h, stream))
         return rc;
     return launch_clip_resample_v(mid, out, out_dtype == 1, B, p->g.rows, crop, p->vy, p->vc, p->vk, p->g.ks_v, p->lut, stream);
+}
+
+// ---- the video processor: torchvision's CenterCrop(crop) then Resize(size) on a PIL image, per frame
+int video_resample_table_host(int in, int out, int* xmin_out, int* count_out, int* coeff_out) {
+    const char* who = "video_resample_table_host";
+    LAVIE_CHECK(in >= 1 && in <= 65535 && out >= 1 && out <= 65535, "%s: in=%d out=%d must be in 1..65535", who, in, out);
+    LAVIE_CHECK((double)in / (double)out <= 32.0, "%s: scale %.3f is above 32", who, (double)in / (double)out);
+    const int ksize = axis_ksize(in, out, kBilinear);
+    if (xmin_out == nullptr && count_out == nullptr && coeff_out == nullptr) return ksize;       // the size query
+    LAVIE_CHECK(xmin_out && count_out && coeff_out, "%s: xmin_out, count_out and coeff_out are all given or all null", who);
+    axis_table(in, out, 0, out, xmin_out, count_out, coeff_out, kBilinear);
+    return ksize;
+}
+
+long long video_preprocess_workspace_bytes(int B, int H, int W, int crop, int size) {
+    const char* who = "video_preprocess_workspace_bytes";
+    Geometry g;
+    if (B < 1 || B > 65535) {
+        set_error("%s: B=%d must be in 1..65535", who, B);
+        return -1;
+    }
+    if (video_geometry(who, H, W, crop, size, &g)) return -1;
+    return (long long)mid_bytes(B, g, size);
+}
+
+int video_preprocess(const void* in_u8, int B, int H, int W, long long row_pitch, long long image_pitch, void* out, int out_dtype, int crop,
+                     int size, const float* mean, const float* std_, void* workspace, long long workspace_bytes, hipStream_t stream) {
+    const char* who = "video_preprocess";
+    LAVIE_CHECK(in_u8 && out, "%s: null tensor", who);
+    LAVIE_CHECK(mean && std_, "%s: null mean or std", who);
+    LAVIE_CHECK(B >= 1 && B <= 65535, "%s: B=%d must be in 1..65535", who, B);
+    LAVIE_CHECK(out_dtype == 0 || out_dtype == 1, "%s: out_dtype=%d (0 = fp16, 1 = fp32)", who, out_dtype);
+    LAVIE_CHECK(H >= 1 && W >= 1 && H <= 65535 && W <= 65535, "%s: H=%d W=%d must be in 1..65535", who, H, W);
+    LAVIE_CHECK(row_pitch >= 3ll * W, "%s: row_pitch=%lld is below 3 W = %d", who, row_pitch, 3 * W);
+    LAVIE_CHECK(B == 1 || image_pitch >= (long long)(H - 1) * row_pitch + 3ll * W,
+                "%s: image_pitch=%lld is below the %lld bytes of one image", who, image_pitch, (long long)(H - 1) * row_pitch + 3ll * W);
+    for (int c = 0; c < 3; ++c)
+        LAVIE_CHECK(isfinite(mean[c]) && isfinite(std_[c]) && std_[c] != 0.f, "%s: mean[%d]=%g std[%d]=%g must be finite, std not 0", who, c,
+                    mean[c], c, std_[c]);
+    LAVIE_CHECK(((uintptr_t)out & (out_dtype == 1 ? 3 : 1)) == 0, "%s: out is not aligned to its element size", who);
+    Geometry g;
+    if (int rc = video_geometry(who, H, W, crop, size, &g)) return rc;
+    const long long need = (long long)mid_bytes(B, g, size);
+    LAVIE_CHECK(workspace != nullptr && workspace_bytes >= need, "%s: the workspace holds %lld bytes, this call needs %lld", who,
+                workspace ? workspace_bytes : 0ll, need);
+    std::shared_ptr<const Plan> p;
+    auto fill = [&](int* hx, int* hc, int* hk, int* vy, int* vc, int* vk) {      // the cropped square's tables, moved to frame coordinates
+        axis_table(crop, size, 0, size, hx, hc, hk, kBilinear);
+        axis_table(crop, size, 0, size, vy, vc, vk, kBilinear);
+        for (int i = 0; i < size; ++i) { hx[i] += g.x0; vy[i] += g.y0; }
+    };
+    if (int rc = get_plan(who, 1, g, size, H, W, size, crop, mean, std_, fill, &p)) return rc;
+    uint8_t* mid = (uint8_t*)workspace;
+    if (int rc = launch_clip_resample_h((const uint8_t*)in_u8, row_pitch, B == 1 ? 0 : image_pitch, mid, B, p->g.row0, p->g.rows, size, p->hx,
+                                        p->hc, p->hk, p->g.ks_h, stream))
+        return rc;
+    return launch_clip_resample_v(mid, out, out_dtype == 1, B, p->g.rows, size, p->vy, p->vc, p->vk, p->g.ks_v, p->lut, stream);
 }
 
 }  // namespace lavie

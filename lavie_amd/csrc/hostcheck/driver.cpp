@@ -2051,6 +2051,140 @@ int main(int argc, char** argv) {
         REQUIRE(refused(lavie_clip_similarity_f32(f.data(), nullptr, f.data(), 2, 2, 128, 0, 1.f, nullptr), "null tensor"));
         REQUIRE(lavie_hostcheck_launches() == before + 8);
     }
+    {   // FVD: the 3-D conv operators, lavie_r3d_* and the video processor: every refusal names its argument and comes
+        // before a launch; accepted calls reach the (stubbed) launch with exactly sized buffers
+        auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+        const long before = lavie_hostcheck_launches();
+        REQUIRE(lavie_conv3d_packed_halfs(64, 3, 3, 7, 7) == 64 * 448 && lavie_conv3d_packed_halfs(128, 64, 3, 3, 3) == 128 * 27 * 64);
+        REQUIRE(lavie_conv3d_packed_halfs(64, 64, 9, 3, 3) == -1 && lavie_conv3d_packed_halfs(0, 64, 3, 3, 3) == -1);
+        const int N = 2, T = 3, Hh = 5, Ww = 7;
+        std::vector<unsigned short> w16((size_t)128 * 64 * 27), wp((size_t)128 * 27 * 64), x((size_t)N * T * Hh * Ww * 64);
+        std::vector<unsigned short> y((size_t)N * T * Hh * Ww * 128), ys((size_t)N * 2 * 3 * 4 * 128);
+        std::vector<float> bias(128);
+        REQUIRE(lavie_conv3d_pack(w16.data(), wp.data(), 128, 64, 3, 3, 3, nullptr) == 0);
+        REQUIRE(refused(lavie_conv3d_pack(nullptr, wp.data(), 128, 64, 3, 3, 3, nullptr), "null tensor"));
+        REQUIRE(refused(lavie_conv3d_pack(w16.data(), wp.data(), 128, 64, 3, 8, 3, nullptr), "bad shape"));
+        auto conv = [&](const void* xx, const void* ww, const float* bb, void* yy, int n, int t, int cin, int cout, int ks, int st) {
+            return lavie_conv3d_f16(xx, ww, bb, nullptr, 1, yy, n, t, Hh, Ww, cin, cout, ks, st, nullptr);
+        };
+        REQUIRE(conv(x.data(), wp.data(), bias.data(), y.data(), N, T, 64, 128, 3, 1) == 0);
+        REQUIRE(conv(x.data(), wp.data(), bias.data(), ys.data(), N, T, 64, 128, 3, 2) == 0);
+        REQUIRE(conv(x.data(), wp.data(), bias.data(), ys.data(), N, T, 64, 128, 1, 2) == 0);
+        REQUIRE(lavie_conv3d_f16(x.data(), wp.data(), bias.data(), y.data(), 0, y.data(), N, T, Hh, Ww, 64, 128, 3, 1, nullptr) == 0);
+        REQUIRE(refused(conv(nullptr, wp.data(), bias.data(), y.data(), N, T, 64, 128, 3, 1), "null tensor"));
+        REQUIRE(refused(conv(x.data(), wp.data(), nullptr, y.data(), N, T, 64, 128, 3, 1), "null tensor"));
+        REQUIRE(refused(conv(x.data(), wp.data(), bias.data(), y.data(), N, T, 96, 128, 3, 1), "Cin=96"));
+        REQUIRE(refused(conv(x.data(), wp.data(), bias.data(), y.data(), N, T, 64, 1024, 3, 1), "Cout=1024"));
+        REQUIRE(refused(conv(x.data(), wp.data(), bias.data(), y.data(), N, T, 64, 128, 3, 3), "stride 3 is not built"));
+        REQUIRE(refused(conv(x.data(), wp.data(), bias.data(), y.data(), N, T, 64, 128, 1, 1), "(1,1,1) stride 1 is not built"));
+        REQUIRE(refused(conv(x.data(), wp.data(), bias.data(), y.data(), N, T, 64, 128, 5, 1), "(5,5,5)"));
+        REQUIRE(refused(conv(x.data(), wp.data(), bias.data(), y.data(), N, 0, 64, 128, 3, 1), "T=0"));
+        REQUIRE(refused(conv(x.data(), wp.data(), bias.data(), y.data(), 0, T, 64, 128, 3, 1), "N=0"));
+        std::vector<float> px((size_t)N * 3 * T * Hh * Ww);
+        std::vector<unsigned short> sw((size_t)64 * 448), sy((size_t)N * T * 3 * 4 * 64);
+        const long long plane = Hh * Ww;
+        auto stem = [&](const void* p, int dt, long long sn, long long st, long long sc, int n, int t) {
+            return lavie_conv3d_stem_f16(p, dt, sn, st, sc, sw.data(), bias.data(), 1, sy.data(), n, t, Hh, Ww, nullptr);
+        };
+        REQUIRE(stem(px.data(), 1, 3 * T * plane, plane, T * plane, N, T) == 0);           // channels-first
+        REQUIRE(stem(px.data(), 0, 3 * T * plane, 3 * plane, plane, N, T) == 0);           // frames-major planar (as fp16: half the bytes)
+        REQUIRE(refused(stem(nullptr, 1, 3 * T * plane, plane, T * plane, N, T), "null tensor"));
+        REQUIRE(refused(stem(px.data(), 2, 3 * T * plane, plane, T * plane, N, T), "x_dtype=2"));
+        REQUIRE(refused(stem(px.data(), 1, 3 * T * plane, plane - 1, T * plane, N, T), "strides"));
+        REQUIRE(refused(stem(px.data(), 1, 3 * T * plane, plane, T * plane, N, 0), "T=0"));
+        REQUIRE(refused(stem(px.data(), 1, 3 * T * plane, plane, T * plane, 0, T), "N=0"));
+        std::vector<float> feat((size_t)N * 512);
+        REQUIRE(lavie_mean_rows_f32(y.data(), feat.data(), N, T * Hh * Ww, 128, nullptr) == 0);
+        REQUIRE(refused(lavie_mean_rows_f32(nullptr, feat.data(), N, 4, 128, nullptr), "null tensor"));
+        REQUIRE(refused(lavie_mean_rows_f32(y.data(), feat.data(), N, 0, 128, nullptr), "rows=0"));
+        REQUIRE(refused(lavie_mean_rows_f32(y.data(), feat.data(), 0, 4, 128, nullptr), "N=0"));
+        REQUIRE(lavie_hostcheck_launches() == before + 8);
+
+        lavie_r3d_t rh = nullptr;
+        REQUIRE(refused(lavie_r3d_create(nullptr), "null") && lavie_r3d_create(&rh) == 0 && rh != nullptr);
+        REQUIRE(lavie_r3d_num_params(rh) == 100 && lavie_r3d_num_params(nullptr) == -1);
+        REQUIRE(refused(lavie_r3d_param_info(rh, 100, nullptr, nullptr), "out of range"));
+        std::vector<float> big((size_t)512 * 512 * 27);                        // the largest tensor; every parameter borrows it
+        REQUIRE(refused(lavie_r3d_set_param(rh, "layer1.0.downsample.0.weight", big.data(), 64 * 64), "unknown state-dict key"));
+        REQUIRE(refused(lavie_r3d_set_param(rh, "5.0.conv1.0.weight", big.data(), 8), "unknown state-dict key"));
+        REQUIRE(refused(lavie_r3d_set_param(nullptr, "stem.0.weight", big.data(), 8), "null argument"));
+        REQUIRE(refused(lavie_r3d_set_param(rh, nullptr, big.data(), 8), "null argument"));
+        REQUIRE(lavie_r3d_set_param(rh, "fc.weight", big.data(), 400 * 512) == 0);                    // accepted and ignored
+        REQUIRE(lavie_r3d_set_param(rh, "2.0.conv1.1.num_batches_tracked", big.data(), 1) == 0);      // likewise, numeric prefix
+        REQUIRE(refused(lavie_r3d_features(rh, px.data(), 1, 3 * T * plane, plane, T * plane, N, T, Hh, Ww, feat.data(), big.data(), 1 << 20, nullptr),
+                        "not finalized"));
+        REQUIRE(refused(lavie_r3d_finalize(rh, nullptr), "was never set"));
+        REQUIRE(refused(lavie_r3d_finalize(nullptr, nullptr), "null handle"));
+        for (int i = 0; i < lavie_r3d_num_params(rh); ++i) {
+            const char* name = nullptr;
+            long long numel = 0;
+            REQUIRE(lavie_r3d_param_info(rh, i, &name, &numel) == 0 && name && numel > 0 && numel <= (long long)big.size());
+            REQUIRE(refused(lavie_r3d_set_param(rh, name, big.data(), numel + 1), "expected"));
+            REQUIRE(refused(lavie_r3d_set_param(rh, name, nullptr, numel), "null data"));
+            std::string key = name;                                            // every other one under its nn.Sequential prefix
+            if (i & 1) key = key.compare(0, 4, "stem") == 0 ? "0" + key.substr(4) : key.substr(5);
+            REQUIRE(lavie_r3d_set_param(rh, key.c_str(), big.data(), numel) == 0);
+        }
+        const long packs = lavie_hostcheck_launches();
+        REQUIRE(lavie_r3d_finalize(rh, nullptr) == 0 && lavie_hostcheck_launches() == packs + 20);
+        REQUIRE(refused(lavie_r3d_finalize(rh, nullptr), "finalized already"));
+        REQUIRE(refused(lavie_r3d_set_param(rh, "stem.1.bias", big.data(), 64), "finalized"));
+        REQUIRE(lavie_r3d_workspace_bytes(nullptr, 1, 1, 1, 1) == -1);
+        REQUIRE(lavie_r3d_workspace_bytes(rh, 0, T, Hh, Ww) == -1 && strstr(lavie_last_error(), "N=0"));
+        REQUIRE(lavie_r3d_workspace_bytes(rh, N, T, 0, Ww) == -1 && strstr(lavie_last_error(), "H=0"));
+        REQUIRE(lavie_r3d_workspace_bytes(rh, 1, 1, 1, 1) == 2 * 512 * 2 + 512 * 2);        // one row: the 512-channel level is the largest
+        const long long need = lavie_r3d_workspace_bytes(rh, N, T, Hh, Ww);
+        REQUIRE(need == 2 * (long long)N * T * 3 * 4 * 64 * 2 + (long long)N * 2 * 2 * 2 * 128 * 2);
+        std::vector<char> ws((size_t)need);
+        auto features = [&](const void* p, int dt, long long st, int n, int t, float* out, void* w, long long bytes) {
+            return lavie_r3d_features(rh, p, dt, 3 * T * plane, st, T * plane, n, t, Hh, Ww, out, w, bytes, nullptr);
+        };
+        const long fwd = lavie_hostcheck_launches();
+        REQUIRE(features(px.data(), 1, plane, N, T, feat.data(), ws.data(), need) == 0 && lavie_hostcheck_launches() == fwd + 21);
+        REQUIRE(refused(features(px.data(), 1, plane, N, T, feat.data(), ws.data(), need - 1), "the workspace holds"));
+        REQUIRE(refused(features(px.data(), 1, plane, N, T, feat.data(), nullptr, need), "the workspace holds 0 bytes"));
+        REQUIRE(refused(features(nullptr, 1, plane, N, T, feat.data(), ws.data(), need), "pixels is null"));
+        REQUIRE(refused(features(px.data(), 1, plane, N, T, nullptr, ws.data(), need), "out_f32 is null"));
+        REQUIRE(refused(features(px.data(), 3, plane, N, T, feat.data(), ws.data(), need), "x_dtype=3"));
+        REQUIRE(refused(features(px.data(), 1, plane, 0, T, feat.data(), ws.data(), need), "N=0"));
+        REQUIRE(refused(features(px.data(), 1, plane, N, 0, feat.data(), ws.data(), need), "T=0"));
+        REQUIRE(refused(features(px.data(), 1, plane - 1, N, T, feat.data(), ws.data(), need), "strides"));
+        REQUIRE(refused(lavie_r3d_features(nullptr, px.data(), 1, 3 * T * plane, plane, T * plane, N, T, Hh, Ww, feat.data(), ws.data(), need, nullptr),
+                        "null handle"));
+        REQUIRE(lavie_hostcheck_launches() == fwd + 21);
+        REQUIRE(lavie_r3d_destroy(rh) == 0 && lavie_r3d_destroy(nullptr) == 0);
+
+        int xmin[28], cnt[28], coeff[28 * 5];
+        REQUIRE(lavie_video_resample_table_host(34, 28, nullptr, nullptr, nullptr) == 5);
+        REQUIRE(lavie_video_resample_table_host(34, 28, xmin, cnt, coeff) == 5 && xmin[0] == 0 && xmin[27] + cnt[27] == 34);
+        REQUIRE(lavie_video_resample_table_host(34, 28, xmin, nullptr, coeff) == -1 && strstr(lavie_last_error(), "all given or all null"));
+        REQUIRE(lavie_video_resample_table_host(0, 28, nullptr, nullptr, nullptr) == -1 && strstr(lavie_last_error(), "in=0"));
+        const int VH = 40, VW = 64;
+        const float mean[3] = {0.485f, 0.456f, 0.406f}, sd[3] = {0.229f, 0.224f, 0.225f}, sd0[3] = {0.229f, 0.f, 0.225f};
+        const long long vneed = lavie_video_preprocess_workspace_bytes(2, VH, VW, 34, 28);
+        REQUIRE(vneed == (2 * 34 * 28 * 3 + 255) / 256 * 256);
+        REQUIRE(lavie_video_preprocess_workspace_bytes(0, VH, VW, 34, 28) == -1 && strstr(lavie_last_error(), "B=0"));
+        REQUIRE(lavie_video_preprocess_workspace_bytes(2, VH, VW, 41, 28) == -1 && strstr(lavie_last_error(), "crop=41 is greater than the frame"));
+        std::vector<unsigned char> frames((size_t)2 * VH * VW * 3), mid((size_t)vneed);
+        std::vector<float> vout((size_t)2 * 3 * 28 * 28);
+        auto pre = [&](const void* in, int b, long long pitch, int dt, int crop, int size, const float* m, const float* s, long long bytes) {
+            return lavie_video_preprocess_u8(in, b, VH, VW, pitch, (long long)VH * VW * 3, vout.data(), dt, crop, size, m, s, mid.data(), bytes, nullptr);
+        };
+        const long vbefore = lavie_hostcheck_launches();
+        REQUIRE(pre(frames.data(), 2, 3 * VW, 1, 34, 28, mean, sd, vneed) == 0 && pre(frames.data(), 1, 3 * VW, 0, 34, 28, mean, sd, vneed) == 0);
+        REQUIRE(lavie_hostcheck_launches() == vbefore + 4);
+        REQUIRE(refused(pre(nullptr, 2, 3 * VW, 1, 34, 28, mean, sd, vneed), "null tensor"));
+        REQUIRE(refused(pre(frames.data(), 2, 3 * VW, 1, 34, 28, nullptr, sd, vneed), "null mean or std"));
+        REQUIRE(refused(pre(frames.data(), 0, 3 * VW, 1, 34, 28, mean, sd, vneed), "B=0"));
+        REQUIRE(refused(pre(frames.data(), 2, 3 * VW - 1, 1, 34, 28, mean, sd, vneed), "row_pitch"));
+        REQUIRE(refused(pre(frames.data(), 2, 3 * VW, 2, 34, 28, mean, sd, vneed), "out_dtype=2"));
+        REQUIRE(refused(pre(frames.data(), 2, 3 * VW, 1, 41, 28, mean, sd, vneed), "crop=41 is greater than the frame"));
+        REQUIRE(refused(pre(frames.data(), 2, 3 * VW, 1, 34, 0, mean, sd, vneed), "size=0"));
+        REQUIRE(refused(pre(frames.data(), 2, 3 * VW, 1, 34, 1, mean, sd, vneed), "above 32"));
+        REQUIRE(refused(pre(frames.data(), 2, 3 * VW, 1, 34, 28, mean, sd0, vneed), "std[1]"));
+        REQUIRE(refused(pre(frames.data(), 2, 3 * VW, 1, 34, 28, mean, sd, vneed - 1), "the workspace holds"));
+        REQUIRE(lavie_hostcheck_launches() == vbefore + 4);
+    }
     run_vae_optrace();
     REQUIRE(lavie_upsample_conv3x3_supported(320, 32, 20, 32) >= 0);
     int buckets[16 * 16];

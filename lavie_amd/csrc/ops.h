@@ -170,6 +170,30 @@ int launch_clip_embed(const half_t* x, int B, int L, int C, const int* ids_dev, 
                       float eps, const half_t* W, int D, bool normalize, float* out, hipStream_t stream);
 // frames == 0: out [N, P] = scale <img_n, txt_p>; frames >= 1 (N = P frames): out [P] = (100 / frames) sum_f <img_{p frames + f}, txt_p>
 int launch_clip_similarity(const float* img, const float* txt, float* out, int N, int P, int D, int frames, float scale, hipStream_t stream);
+// ---- clip_engine.cpp : the video processor of the FVD evaluator: centre crop of `crop` pixels FIRST, then Pillow's
+// 8-bit bilinear resize of the cropped square to size x size, then the table; new host tables in front of the two kernels above
+int video_resample_table_host(int in, int out, int* xmin_out, int* count_out, int* coeff_out);    // returns ksize, or -1
+long long video_preprocess_workspace_bytes(int B, int H, int W, int crop, int size);
+int video_preprocess(const void* in_u8, int B, int H, int W, long long row_pitch, long long image_pitch, void* out, int out_dtype, int crop,
+                     int size, const float* mean3, const float* std3, void* workspace, long long workspace_bytes, hipStream_t stream);
+// ---- conv3d.hip : nn.Conv3d of the video ResNet on channels-last fp16 rows [N, T, H, W, C] (the file's header).  Packed weights
+// [Cout][kpad], k = tap * Cin + ci, kpad = taps * Cin rounded up to 64 (conv3d_packed_halfs = Cout * kpad, -1 for a refused shape).
+// fold_pack: fp32 weights with the following BatchNorm folded in (scale in double, one fp16 rounding; shift fp32 [Cout]).
+long long conv3d_packed_halfs(int Cout, int Cin, int kt, int kh, int kw);
+int launch_conv3d_pack(const half_t* w, half_t* out, int Cout, int Cin, int kt, int kh, int kw, hipStream_t stream);
+int launch_conv3d_fold_pack(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, double eps,
+                            half_t* out, float* shift, int Cout, int Cin, int kt, int kh, int kw, hipStream_t stream);
+// output extents floor((n - 1) / stride) + 1 of the geometries that are built; anything else is refused by name
+int conv3d_out_shape(int T, int H, int W, int ksize, int stride, int* To, int* Ho, int* Wo);
+int conv3d_stem_out_shape(int T, int H, int W, int* To, int* Ho, int* Wo);
+// y = relu?(conv(x) + bias + R): ksize 3 (pad 1, stride 1 | 2) or 1 (stride 2); Cin, Cout in {64, 128, 256, 512}; R [rows out, Cout] or
+// null, may alias y
+int launch_conv3d(const half_t* x, const half_t* wp, const float* bias, const half_t* R, bool relu, half_t* y, int N, int T, int H, int W,
+                  int Cin, int Cout, int ksize, int stride, hipStream_t stream);
+// the (3,7,7) / (1,2,2) / (1,3,3) stem, 3 -> 64: pixel (n, t, c, h, w) at px[n stride_n + t stride_t + c stride_c + h W + w]
+int launch_conv3d_stem(const void* px, bool px_f32, long long stride_n, long long stride_t, long long stride_c, const half_t* wp,
+                       const float* bias, bool relu, half_t* y, int N, int T, int H, int W, hipStream_t stream);
+int launch_mean_rows(const half_t* x, float* out, int N, int rows, int C, hipStream_t stream);
 int launch_add_class_emb_silu(float* emb, const half_t* table, const int* labels_host, int B, int N, hipStream_t stream);
 int launch_f32_to_f16_dup2(const float* x, half_t* out2, int64_t n, float in_scale, hipStream_t stream);
 int launch_f32_to_f16_scaled(const float* x, half_t* out, int64_t n, float in_scale, hipStream_t stream);

@@ -1418,3 +1418,120 @@ def clip_similarity(image_features, text_features, frames=0, scale=1.0, out=None
     _lib.check(_lib.load().lavie_clip_similarity_f32(_p(image_features), _p(text_features), _p(out), n, p, d, int(frames), float(scale),
                                                      _stream()), "lavie_clip_similarity_f32")
     return out
+
+
+# ------------------------------------------------------------------ FVD: 3-D convolutions, mean over rows, video processor
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+
+
+def pack_conv3d(weight):
+    """nn.Conv3d weight [cout, cin, kt, kh, kw] (fp16, device) -> [cout, kpad]: rows in [kt][kh][kw][cin] order, zero-padded to a
+    multiple of 64 halfs (lavie_conv3d_pack)."""
+    _chk16(weight)
+    if weight.dim() != 5:
+        raise ValueError(f"pack_conv3d: weight must be [cout, cin, kt, kh, kw], got {tuple(weight.shape)}")
+    cout, cin, kt, kh, kw = weight.shape
+    lib = _lib.load()
+    halfs = lib.lavie_conv3d_packed_halfs(cout, cin, kt, kh, kw)
+    if halfs < 0:
+        raise ValueError(f"pack_conv3d: shape {tuple(weight.shape)} is outside what lavie_conv3d_pack takes")
+    out = torch.empty((cout, halfs // cout), dtype=torch.float16, device=weight.device)
+    _lib.check(lib.lavie_conv3d_pack(_p(weight), _p(out), cout, cin, kt, kh, kw, _stream()), "lavie_conv3d_pack")
+    return out
+
+
+def conv3d(x, wp, bias, ksize=3, stride=1, residual=None, relu=False, out=None):
+    """relu?(conv3d(x) + bias + residual) on channels-last rows (lavie_conv3d_f16): x fp16 [n, t, h, w, cin], wp from pack_conv3d,
+    bias fp32 [cout], residual fp16 [n, to, ho, wo, cout] -> fp16 [n, to, ho, wo, cout].  ksize 3 (pad 1, stride 1 | 2) or 1 (stride 2)."""
+    _chk16(x, wp, residual)
+    _chk32(bias)
+    if x.dim() != 5 or wp.dim() != 2 or bias.dim() != 1:
+        raise ValueError(f"conv3d: x must be [n, t, h, w, cin], wp [cout, kpad] and bias [cout], got {tuple(x.shape)}, {tuple(wp.shape)}, "
+                         f"{tuple(bias.shape)}")
+    n, t, h, w, cin = x.shape
+    cout = wp.shape[0]
+    if bias.numel() != cout or wp.shape[1] != -(-(ksize ** 3 * cin) // 64) * 64:
+        raise ValueError(f"conv3d: wp {tuple(wp.shape)} and bias {tuple(bias.shape)} do not belong to a ({ksize},{ksize},{ksize}) conv "
+                         f"{cin} -> {cout}")
+    if stride < 1 or min(n, t, h, w) < 1:
+        raise ValueError(f"conv3d: bad stride {stride} or empty extent in {tuple(x.shape)}")
+    shape = (n, (t - 1) // stride + 1, (h - 1) // stride + 1, (w - 1) // stride + 1, cout)
+    if residual is not None and tuple(residual.shape) != shape:
+        raise ValueError(f"conv3d: residual must be {shape}, got {tuple(residual.shape)}")
+    y = _out(out, shape, torch.float16, x.device, "conv3d: out")
+    _lib.check(_lib.load().lavie_conv3d_f16(_p(x), _p(wp), _p(bias), _p(residual), int(bool(relu)), _p(y), n, t, h, w, cin, cout, int(ksize),
+                                            int(stride), _stream()), "lavie_conv3d_f16")
+    return y
+
+
+def _stem_strides(pixels, layout, what):
+    """(n, t, h, w, stride_n, stride_t, stride_c) of a pixel tensor read in place: rows contiguous, the other axes at any stride that
+    holds a plane"""
+    if layout not in ("ncthw", "ntchw"):
+        raise ValueError(f"{what}: layout {layout!r} is neither 'ncthw' nor 'ntchw'")
+    if not (pixels.is_cuda and pixels.dtype in (torch.float16, torch.float32) and pixels.dim() == 5):
+        raise ValueError(f"{what}: pixels must be a 5-D fp16 or fp32 device tensor")
+    v = pixels if layout == "ntchw" else pixels.permute(0, 2, 1, 3, 4)
+    n, t, c, h, w = v.shape
+    if c != 3:
+        raise ValueError(f"{what}: pixels must have 3 channels ({layout}), got {tuple(pixels.shape)}")
+    if min(n, t, h, w) < 1:
+        raise ValueError(f"{what}: empty extent in {tuple(pixels.shape)}")
+    if v.stride(4) != 1 or v.stride(3) != w or min(v.stride(0), v.stride(1), v.stride(2)) < h * w:
+        raise ValueError(f"{what}: the h x w planes of pixels must be contiguous and must not overlap (strides {tuple(pixels.stride())})")
+    return n, t, h, w, v.stride(0), v.stride(1), v.stride(2)
+
+
+def conv3d_stem(pixels, wp, bias, relu=True, layout="ncthw", out=None):
+    """The (3,7,7) / (1,2,2) / (1,3,3) stem conv 3 -> 64 (lavie_conv3d_stem_f16): pixels fp16 or fp32, [n, 3, t, h, w] ('ncthw') or
+    [n, t, 3, h, w] ('ntchw'), read in place through their strides; wp = pack_conv3d of [64, 3, 3, 7, 7]; bias fp32 [64]
+    -> fp16 rows [n, t, ceil(h / 2), ceil(w / 2), 64]."""
+    _chk16(wp)
+    _chk32(bias)
+    n, t, h, w, sn, st, sc = _stem_strides(pixels, layout, "conv3d_stem")
+    if tuple(wp.shape) != (64, 448) or bias.numel() != 64:
+        raise ValueError(f"conv3d_stem: wp must be the pack_conv3d image [64, 448] of [64, 3, 3, 7, 7] and bias [64], got {tuple(wp.shape)}, "
+                         f"{tuple(bias.shape)}")
+    y = _out(out, (n, t, (h - 1) // 2 + 1, (w - 1) // 2 + 1, 64), torch.float16, pixels.device, "conv3d_stem: out")
+    _lib.check(_lib.load().lavie_conv3d_stem_f16(_p(pixels), int(pixels.dtype == torch.float32), sn, st, sc, _p(wp), _p(bias), int(bool(relu)),
+                                                 _p(y), n, t, h, w, _stream()), "lavie_conv3d_stem_f16")
+    return y
+
+
+def mean_rows(x, out=None):
+    """fp16 [n, rows, c] -> fp32 [n, c], the mean over rows in a fixed order (lavie_mean_rows_f32)."""
+    _chk16(x)
+    if x.dim() != 3 or min(x.shape) < 1:
+        raise ValueError(f"mean_rows: x must be a non-empty [n, rows, c], got {tuple(x.shape)}")
+    n, rows, c = x.shape
+    out = _out(out, (n, c), torch.float32, x.device, "mean_rows: out")
+    _lib.check(_lib.load().lavie_mean_rows_f32(_p(x), _p(out), n, rows, c, _stream()), "lavie_mean_rows_f32")
+    return out
+
+
+def video_preprocess(frames, crop=270, size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, dtype=torch.float32, out=None):
+    """Per frame: centre crop of crop x crop, Pillow's bilinear resize to size x size, (v / 255 - mean) / std
+    (lavie_video_preprocess_u8): frames uint8 [b, h, w, 3] with unit stride over (w, 3) -> [b, 3, size, size], fp32 with the bits of
+    Pillow + fp32 normalisation, or fp16, one rounding of those."""
+    if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3):
+        raise ValueError("video_preprocess: frames must be a uint8 device tensor [b, h, w, 3]")
+    b, h, w, _ = frames.shape
+    if b < 1:
+        raise ValueError("video_preprocess: empty batch")
+    if frames.stride(3) != 1 or frames.stride(2) != 3:
+        raise ValueError("video_preprocess: the pixels of a row must be contiguous")
+    if dtype not in (torch.float16, torch.float32):
+        raise ValueError(f"video_preprocess: dtype {dtype} is not fp32 or fp16")
+    lib = _lib.load()
+    mean3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    std3 = (ctypes.c_float * 3)(*[float(v) for v in std])
+    nbytes = lib.lavie_video_preprocess_workspace_bytes(b, h, w, int(crop), int(size))
+    if nbytes < 0:
+        _lib.check(-1, "lavie_video_preprocess_workspace_bytes")
+    with torch.cuda.device(frames.device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=frames.device)
+        out = _out(out, (b, 3, int(size), int(size)), dtype, frames.device, "video_preprocess: out")
+        _lib.check(lib.lavie_video_preprocess_u8(_p(frames), b, h, w, frames.stride(1), frames.stride(0), _p(out), int(dtype == torch.float32),
+                                                 int(crop), int(size), mean3, std3, _p(ws), nbytes, _stream()), "lavie_video_preprocess_u8")
+    return out
