@@ -989,6 +989,20 @@ long long lavie_mapper_workspace_bytes(lavie_mapper_t h, int B);
 int lavie_mapper_encode(lavie_mapper_t h, const void* image_feats, int Bi, const void* text, int B, void* out, int ld_out_rows, int row0,
                         void* stream);
 
+/* ---- The encoders' own launches at operator level (additive in ABI 8): what lavie_text_*, lavie_vision_* and
+ * lavie_mapper_* launch without the planner of lavie_linear_f16, for per-element checks.
+ * C [M, N] (ldc) = A [M, K] (lda) W [N, K]^T + bias [N] (+ R [M, N] (ldr), which may alias C) on the one pinned plan of the encoders:
+ * the 128-row kernel at 128 columns, no split-K, whatever M, N and K are; fp32 sum over K in an order that depends on K alone, bias and
+ * residual in fp32, one fp16 rounding.  A row's bits do not depend on M or on where the row lies.  lavie_debug_force_tile / _splits do
+ * not reach it and lavie_debug_op_statistics_last does not record it.  Refused by name, nothing launched: a null A, W, bias or C,
+ * M < 1, N not a multiple of 128, K not a multiple of 64, lda < K or not a multiple of 8, ldc (ldr) < N or not a multiple of 4, a
+ * tensor that is not 16-byte aligned.  One launch, capturable. */
+int lavie_pinned_linear_f16(const void* A, int lda, const void* W, const float* bias, const void* R, int ldr, void* C, int ldc, int M, int N,
+                            int K, void* stream);
+/* out fp16 [B, L, C] = fp16(float(x [B, L, C]) + float(pos [L, C])), one rounding: the mapper's target rows plus their positions.
+ * C a multiple of 8, 16-byte aligned tensors; a null tensor, B < 1 or L < 1 is refused by name. */
+int lavie_add_rows_f16(const void* x, const void* pos, void* out, int B, int L, int C, void* stream);
+
 /* ---- Seeded engine noise (csrc/philox.h, csrc/sampler_noise.hip).  A standard normal as a pure function of (a latent's 64-bit seed,
  * a 64-bit draw number, the element's flat index e inside ONE latent [C, F, h, w]): no generator state exists anywhere, and a latent
  * has the same noise alone, in any batch, on any rank and under any window split.
@@ -1082,6 +1096,12 @@ int lavie_clip_similarity_f32(const float* img, const float* txt, float* out, in
 long long lavie_conv3d_packed_halfs(int Cout, int Cin, int kt, int kh, int kw);
 /* w fp16 [Cout, Cin, kt, kh, kw] -> out fp16 [Cout][kt][kh][kw][Cin], each row zero-padded to a multiple of 64 halfs. */
 int lavie_conv3d_pack(const void* w_f16, void* out_f16, int Cout, int Cin, int kt, int kh, int kw, void* stream);
+/* The same pack from fp32 weights with the BatchNorm3d behind the conv folded in, as lavie_r3d_finalize runs it: scale = gamma /
+ * sqrt(var + eps) in double, out_f16 = fp16(w scale), rounded once from the double product, in lavie_conv3d_pack's layout;
+ * shift_f32 [Cout] = fp32(beta - mean scale), the bias of the folded conv.  w fp32 [Cout, Cin, kt, kh, kw]; gamma, beta, mean, var
+ * fp32 [Cout].  A null tensor and a shape lavie_conv3d_packed_halfs refuses are refused by name. */
+int lavie_conv3d_fold_pack_f32(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, double eps,
+                               void* out_f16, float* shift_f32, int Cout, int Cin, int kt, int kh, int kw, void* stream);
 /* y = relu?(conv3d(x) + bias + residual) on channels-last fp16 rows: x [N, T, H, W, Cin] -> y [N, To, Ho, Wo, Cout], extents
  * floor((n - 1) / stride) + 1.  Built: ksize 3 (kernel (3,3,3), padding 1) with stride 1 or 2 on all three axes, and ksize 1 (kernel
  * (1,1,1), no padding) with stride 2; Cin and Cout each 64, 128, 256 or 512; everything else is refused by name.  wp: lavie_conv3d_pack's

@@ -309,6 +309,8 @@ SIGNATURES = {
     "lavie_mapper_finalize": (c_int, [c_void_p, c_void_p]),
     "lavie_mapper_workspace_bytes": (c_ll, [c_void_p, c_int]),
     "lavie_mapper_encode": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "lavie_pinned_linear_f16": (c_int, [c_void_p, c_int, c_void_p, c_float_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "lavie_add_rows_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "lavie_philox4x32_host": (c_int, [C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "lavie_philox_normal_f32": (c_int, [c_float_p, C.POINTER(c_ull), c_int, c_ll, c_ll, c_ull, c_void_p]),
     "lavie_sampler_step_seeded": (c_int, [c_void_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float, c_float,
@@ -326,6 +328,8 @@ SIGNATURES = {
     "lavie_clip_similarity_f32": (c_int, [c_float_p, c_float_p, c_float_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "lavie_conv3d_packed_halfs": (c_ll, [c_int, c_int, c_int, c_int, c_int]),
     "lavie_conv3d_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "lavie_conv3d_fold_pack_f32": (c_int, [c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, C.c_double, c_void_p, c_float_p, c_int, c_int,
+                                           c_int, c_int, c_int, c_void_p]),
     "lavie_conv3d_f16": (c_int, [c_void_p, c_void_p, c_float_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_int, c_void_p]),
     "lavie_conv3d_stem_f16": (c_int, [c_void_p, c_int, c_ll, c_ll, c_ll, c_void_p, c_float_p, c_int, c_void_p, c_int, c_int, c_int, c_int,

@@ -194,6 +194,23 @@ int lavie_linear_lnfold_geglu_f16(const void* A, const void* Wf, const float* bi
     return op_launch(p, false, EPI_GEGLU, S(stream));
 }
 
+// The encoders' pinned plan (pinned_linear.h) at operator level: the inline function the text encoder, the vision tower and the mapper
+// call, behind the refusals check_clip_shape and their workspace carves keep them from needing.  No planner, no force switch, no
+// statistics sink: lavie_debug_op_statistics_last does not see this launch.
+int lavie_pinned_linear_f16(const void* A, int lda, const void* W, const float* bias, const void* R, int ldr, void* C, int ldc, int M, int N,
+                            int K, void* stream) {
+    LAVIE_CHECK(A && W && bias && C, "pinned_linear: null tensor");
+    LAVIE_CHECK(M >= 1, "pinned_linear: M=%d must be at least 1", M);
+    LAVIE_CHECK(N >= kPinBn && N % kPinBn == 0, "pinned_linear: N=%d must be a multiple of %d", N, kPinBn);
+    LAVIE_CHECK(K >= IGEMM_BK && K % IGEMM_BK == 0, "pinned_linear: K=%d must be a multiple of %d", K, IGEMM_BK);
+    LAVIE_CHECK(lda >= K && lda % 8 == 0, "pinned_linear: lda=%d must be a multiple of 8 and at least K=%d", lda, K);
+    LAVIE_CHECK(ldc >= N && ldc % 4 == 0, "pinned_linear: ldc=%d must be a multiple of 4 and at least N=%d", ldc, N);
+    LAVIE_CHECK(!R || (ldr >= N && ldr % 4 == 0), "pinned_linear: ldr=%d must be a multiple of 4 and at least N=%d", ldr, N);
+    auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    LAVIE_CHECK(aligned(A) && aligned(W) && aligned(bias) && aligned(C) && aligned(R), "pinned_linear: the tensors must be 16-byte aligned");
+    return pinned_linear(H(A), lda, H(W), bias, H(R), ldr, H(C), ldc, M, N, K, S(stream));
+}
+
 int lavie_lora_merge_f16(const void* W0, const float* A, const float* B, void* out, int N, int K, int r, float scale, void* stream) {
     return launch_lora_merge(H(W0), A, B, H(out), N, K, r, scale, S(stream));
 }
@@ -1415,6 +1432,11 @@ int lavie_mapper_encode(lavie_mapper_t h, const void* image_feats, int Bi, const
     return h->enc.encode(image_feats, Bi, text, B, out, ld_out_rows, row0, S(stream));
 }
 
+// the mapper's first launch: its target rows plus their positions
+int lavie_add_rows_f16(const void* x, const void* pos, void* out, int B, int L, int C, void* stream) {
+    return launch_add_rows(H(x), H(pos), H(out), B, L, C, S(stream));
+}
+
 // ---- CLIP image processor, feature heads, CLIPSIM (clip_engine.cpp, clip_preprocess.hip, clip_embed.hip)
 int lavie_clip_resample_table_host(int in, int out, int* xmin_out, int* count_out, int* coeff_out) {
     return clip_resample_table_host(in, out, xmin_out, count_out, coeff_out);
@@ -1450,6 +1472,12 @@ long long lavie_conv3d_packed_halfs(int Cout, int Cin, int kt, int kh, int kw) {
 
 int lavie_conv3d_pack(const void* w_f16, void* out_f16, int Cout, int Cin, int kt, int kh, int kw, void* stream) {
     return launch_conv3d_pack(H(w_f16), H(out_f16), Cout, Cin, kt, kh, kw, S(stream));
+}
+
+// the pack lavie_r3d_finalize runs for every conv: the BatchNorm behind it folded in
+int lavie_conv3d_fold_pack_f32(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, double eps,
+                               void* out_f16, float* shift_f32, int Cout, int Cin, int kt, int kh, int kw, void* stream) {
+    return launch_conv3d_fold_pack(w, gamma, beta, mean, var, eps, H(out_f16), shift_f32, Cout, Cin, kt, kh, kw, S(stream));
 }
 
 int lavie_conv3d_f16(const void* x, const void* wp, const float* bias, const void* residual, int relu, void* y, int N, int T, int H_, int W,

@@ -2099,6 +2099,67 @@ int main(int argc, char** argv) {
         REQUIRE(refused(lavie_mean_rows_f32(y.data(), feat.data(), N, 0, 128, nullptr), "rows=0"));
         REQUIRE(refused(lavie_mean_rows_f32(y.data(), feat.data(), 0, 4, 128, nullptr), "N=0"));
         REQUIRE(lavie_hostcheck_launches() == before + 8);
+        {   // the folded pack at operator level: every refusal before the launch
+            std::vector<float> w32((size_t)128 * 64 * 27), bn(128), shift(128);
+            auto fold = [&](const float* w, const float* g, const float* v, void* out, float* sh, int kh) {
+                return lavie_conv3d_fold_pack_f32(w, g, bn.data(), bn.data(), v, 1e-5, out, sh, 128, 64, 3, kh, 3, nullptr);
+            };
+            const long at = lavie_hostcheck_launches();
+            REQUIRE(fold(w32.data(), bn.data(), bn.data(), wp.data(), shift.data(), 3) == 0 && lavie_hostcheck_launches() == at + 1);
+            REQUIRE(refused(fold(nullptr, bn.data(), bn.data(), wp.data(), shift.data(), 3), "null tensor"));
+            REQUIRE(refused(fold(w32.data(), bn.data(), bn.data(), nullptr, shift.data(), 3), "null tensor"));
+            REQUIRE(refused(fold(w32.data(), nullptr, bn.data(), wp.data(), shift.data(), 3), "null BatchNorm tensor"));
+            REQUIRE(refused(fold(w32.data(), bn.data(), nullptr, wp.data(), shift.data(), 3), "null BatchNorm tensor"));
+            REQUIRE(refused(fold(w32.data(), bn.data(), bn.data(), wp.data(), nullptr, 3), "null BatchNorm tensor"));
+            REQUIRE(refused(fold(w32.data(), bn.data(), bn.data(), wp.data(), shift.data(), 8), "bad shape"));
+            REQUIRE(lavie_hostcheck_launches() == at + 1);
+        }
+        {   // the encoders' own launches at operator level: lavie_pinned_linear_f16 refuses what check_clip_shape keeps
+            // the encoders from forming, lavie_add_rows_f16 what the mapper's config does; accepted calls launch once
+            const int M = 77, Nn = 256, K = 128;
+            void* buf = nullptr;
+            REQUIRE(posix_memalign(&buf, 16, (size_t)2 * (M * (K + 64) + Nn * K + 2 * M * (Nn + 128)) + 4 * Nn) == 0);
+            memset(buf, 0, (size_t)2 * (M * (K + 64) + Nn * K + 2 * M * (Nn + 128)) + 4 * Nn);
+            unsigned short* a = (unsigned short*)buf;
+            unsigned short* w = a + M * (K + 64);
+            unsigned short* c = w + Nn * K;
+            unsigned short* r = c + M * (Nn + 128);
+            const float* b = (const float*)(r + M * (Nn + 128));
+            auto pin = [&](const void* A, int lda, const void* W, const float* bias, const void* R, int ldr, void* C, int ldc, int m, int n, int k) {
+                return lavie_pinned_linear_f16(A, lda, W, bias, R, ldr, C, ldc, m, n, k, nullptr);
+            };
+            const long at = lavie_hostcheck_launches();
+            REQUIRE(pin(a, K, w, b, nullptr, 0, c, Nn, M, Nn, K) == 0);
+            REQUIRE(pin(a, K, w, b, c, Nn, c, Nn, M, Nn, K) == 0);                                   // R aliasing C
+            REQUIRE(pin(a + 64, K + 64, w, b, r + 128, Nn + 128, c + 128, Nn + 128, M, Nn, K) == 0); // column blocks of wider buffers
+            REQUIRE(pin(a, K, w, b, r, Nn + 128, c, Nn, 1, Nn, K) == 0);
+            REQUIRE(lavie_hostcheck_launches() == at + 4);
+            REQUIRE(refused(pin(nullptr, K, w, b, nullptr, 0, c, Nn, M, Nn, K), "null tensor"));
+            REQUIRE(refused(pin(a, K, nullptr, b, nullptr, 0, c, Nn, M, Nn, K), "null tensor"));
+            REQUIRE(refused(pin(a, K, w, nullptr, nullptr, 0, c, Nn, M, Nn, K), "null tensor"));
+            REQUIRE(refused(pin(a, K, w, b, nullptr, 0, nullptr, Nn, M, Nn, K), "null tensor"));
+            REQUIRE(refused(pin(a, K, w, b, nullptr, 0, c, Nn, 0, Nn, K), "M=0"));
+            REQUIRE(refused(pin(a, K, w, b, nullptr, 0, c, 192, M, 192, K), "N=192"));
+            REQUIRE(refused(pin(a, K, w, b, nullptr, 0, c, 64, M, 64, K), "N=64"));
+            REQUIRE(refused(pin(a, 96, w, b, nullptr, 0, c, Nn, M, Nn, 96), "K=96"));
+            REQUIRE(refused(pin(a, K, w, b, nullptr, 0, c, Nn, M, Nn, 0), "K=0"));
+            REQUIRE(refused(pin(a, K - 8, w, b, nullptr, 0, c, Nn, M, Nn, K), "lda=120"));
+            REQUIRE(refused(pin(a, K + 4, w, b, nullptr, 0, c, Nn, M, Nn, K), "lda=132"));
+            REQUIRE(refused(pin(a, K, w, b, nullptr, 0, c, Nn - 4, M, Nn, K), "ldc=252"));
+            REQUIRE(refused(pin(a, K, w, b, r, Nn + 2, c, Nn, M, Nn, K), "ldr=258"));
+            REQUIRE(refused(pin(a + 4, K, w, b, nullptr, 0, c, Nn, M, Nn, K), "16-byte aligned"));
+            REQUIRE(refused(pin(a, K, w, b, r + 4, Nn + 128, c, Nn, M, Nn, K), "16-byte aligned"));
+            REQUIRE(lavie_hostcheck_launches() == at + 4);
+            auto add = [&](const void* x, const void* pos, void* out, int bb, int l, int cc) { return lavie_add_rows_f16(x, pos, out, bb, l, cc, nullptr); };
+            REQUIRE(add(a, w, c, 3, 7, 128) == 0 && add(a, w, c, 1, 1, 8) == 0 && lavie_hostcheck_launches() == at + 6);
+            REQUIRE(refused(add(nullptr, w, c, 3, 7, 128), "null tensor") && refused(add(a, nullptr, c, 3, 7, 128), "null tensor"));
+            REQUIRE(refused(add(a, w, nullptr, 3, 7, 128), "null tensor"));
+            REQUIRE(refused(add(a, w, c, 3, 7, 100), "C=100") && refused(add(a, w, c, 3, 7, 0), "C=0"));
+            REQUIRE(refused(add(a, w, c, 0, 7, 128), "B=0") && refused(add(a, w, c, 3, 0, 128), "L=0"));
+            REQUIRE(refused(add(a + 4, w, c, 3, 7, 128), "16-byte aligned"));
+            REQUIRE(lavie_hostcheck_launches() == at + 6);
+            free(buf);
+        }
 
         lavie_r3d_t rh = nullptr;
         REQUIRE(refused(lavie_r3d_create(nullptr), "null") && lavie_r3d_create(&rh) == 0 && rh != nullptr);

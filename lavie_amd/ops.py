@@ -79,6 +79,47 @@ def linear(a, weight, bias=None, residual=None, bias2=None, rows_per_batch=0, ge
     return out
 
 
+def _rows16(t, rows, cols, what):
+    """leading dimension of a [rows, cols] fp16 operand that may be a column block of a wider row-major buffer"""
+    if not (t.is_cuda and t.dtype == torch.float16 and t.dim() == 2 and t.stride(1) == 1):
+        raise ValueError(f"{what} must be a 2-D fp16 device tensor with unit column stride")
+    if tuple(t.shape) != (rows, cols):
+        raise ValueError(f"{what} must have shape {(rows, cols)}, got {tuple(t.shape)}")
+    if t.stride(0) < cols:
+        raise ValueError(f"{what}: rows {t.stride(0)} halfs apart overlap at {cols} columns")
+    return t.stride(0)
+
+
+def pinned_linear(a, weight, bias, residual=None, out=None):
+    """a[M,K] @ weight[N,K]^T + bias fp32[N] (+ residual[M,N]) on the encoders' pinned plan (lavie_pinned_linear_f16): no planner, the
+    same kernel and summation order at every M.  a, residual and out may be column blocks of wider buffers (unit column stride, any row
+    stride); residual may be out itself."""
+    _chk16(weight)
+    _chk32(bias)
+    if weight.dim() != 2 or a.dim() != 2 or bias is None or bias.numel() != weight.shape[0]:
+        raise ValueError("pinned_linear: a must be [M, K], weight [N, K] and bias fp32 [N]")
+    M, (N, K) = a.shape[0], weight.shape
+    lda = _rows16(a, M, K, "pinned_linear: a")
+    ldr = N if residual is None else _rows16(residual, M, N, "pinned_linear: residual")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float16, device=a.device)
+    ldc = _rows16(out, M, N, "pinned_linear: out")
+    _lib.check(_lib.load().lavie_pinned_linear_f16(_p(a), lda, _p(weight), _p(bias), _p(residual), ldr, _p(out), ldc, M, N, K, _stream()),
+               "lavie_pinned_linear_f16")
+    return out
+
+
+def add_rows(x, pos, out=None):
+    """fp16(float(x [b, l, c]) + float(pos [l, c])), one rounding (lavie_add_rows_f16): the mapper's target rows plus their positions."""
+    _chk16(x, pos)
+    if x.dim() != 3 or pos.dim() != 2 or tuple(pos.shape) != tuple(x.shape[1:]):
+        raise ValueError(f"add_rows: x must be [b, l, c] and pos [l, c], got {tuple(x.shape)} and {tuple(pos.shape)}")
+    b, l, c = x.shape
+    out = _out(out, x.shape, torch.float16, x.device, "add_rows: out")
+    _lib.check(_lib.load().lavie_add_rows_f16(_p(x), _p(pos), _p(out), b, l, c, _stream()), "lavie_add_rows_f16")
+    return out
+
+
 def linear_lnfold(a, weight_folded, bias, ln_s, ln_stats, geglu=False, out=None):
     """rstd_m (a @ weight_folded^T - mean_m ln_s) + bias: a projection behind a LayerNorm, the norm folded into the GEMM epilogue
     (weight_folded = W * gamma, ln_s = its row sums, bias = W beta (+ b), ln_stats [M, 2] = (mean, rstd) of the rows of `a`).
@@ -1439,6 +1480,27 @@ def pack_conv3d(weight):
     out = torch.empty((cout, halfs // cout), dtype=torch.float16, device=weight.device)
     _lib.check(lib.lavie_conv3d_pack(_p(weight), _p(out), cout, cin, kt, kh, kw, _stream()), "lavie_conv3d_pack")
     return out
+
+
+def pack_conv3d_fold(weight, gamma, beta, mean, var, eps=1e-5, out=None, shift=None):
+    """nn.Conv3d weight fp32 [cout, cin, kt, kh, kw] with the BatchNorm3d (gamma, beta, running mean, running var: fp32 [cout]) behind
+    it folded in -> (pack_conv3d's image of fp16(weight * gamma / sqrt(var + eps)), one rounding from the double product, and the fp32
+    bias beta - mean * gamma / sqrt(var + eps)) (lavie_conv3d_fold_pack_f32)."""
+    _chk32(weight, gamma, beta, mean, var)
+    if weight.dim() != 5:
+        raise ValueError(f"pack_conv3d_fold: weight must be [cout, cin, kt, kh, kw], got {tuple(weight.shape)}")
+    cout, cin, kt, kh, kw = weight.shape
+    if any(t is None or tuple(t.shape) != (cout,) for t in (gamma, beta, mean, var)):
+        raise ValueError(f"pack_conv3d_fold: gamma, beta, mean and var must each be fp32 [{cout}]")
+    lib = _lib.load()
+    halfs = lib.lavie_conv3d_packed_halfs(cout, cin, kt, kh, kw)
+    if halfs < 0:
+        raise ValueError(f"pack_conv3d_fold: shape {tuple(weight.shape)} is outside what lavie_conv3d_fold_pack_f32 takes")
+    out = _out(out, (cout, halfs // cout), torch.float16, weight.device, "pack_conv3d_fold: out")
+    shift = _out(shift, (cout,), torch.float32, weight.device, "pack_conv3d_fold: shift")
+    _lib.check(lib.lavie_conv3d_fold_pack_f32(_p(weight), _p(gamma), _p(beta), _p(mean), _p(var), float(eps), _p(out), _p(shift), cout, cin,
+                                              kt, kh, kw, _stream()), "lavie_conv3d_fold_pack_f32")
+    return out, shift
 
 
 def conv3d(x, wp, bias, ksize=3, stride=1, residual=None, relu=False, out=None):

@@ -997,3 +997,145 @@ def test_assert_elementwise_reports_count_and_worst_and_rejects_nan():
     got[0, 0] = float("nan")
     with pytest.raises(AssertionError, match=r"1 of 6 elements.*\(row 0, column 0\)"):
         oc.assert_elementwise(got, ref, ref, 1.0, where=oc.loc_rows(3))
+
+
+# ------------------------------------------------------------------ the launches only the encoder and FVD objects reach (enccases.py)
+import enccases as E            # noqa: E402
+
+
+def pinned_offenders(case, bad64):
+    """the defective float64 result, stored as the kernel stores it, is rejected by the case's own check; returns where"""
+    got = bad64.half()
+    with pytest.raises(AssertionError, match="outside the bound"):
+        case.check({"y": got})
+    return case.offenders(got)
+
+
+def exactly(case, off, bad64, region):
+    """Rejected at exactly the affected elements: no element outside `region`, and inside it every element the defect moves by more
+    than the stored value can hide (its own rounding on top of the bound); what is left is a fraction of a percent whose defective
+    value rounds to the right fp16 number or its neighbour."""
+    ref, scale = case.ref
+    visible = (bad64 - ref).abs() > 2.01 * oc.U16 * ref.abs() + case.c * scale
+    assert not (off & ~region).any() and not (visible & ~region).any()
+    assert (off | ~visible).all()
+    assert off[region].float().mean() > 0.99 and off[region.any(1)].any(1).all() and off[:, region.any(0)].any(0).all()
+
+
+def test_pinned_reference_passes_its_own_check_and_the_case_list_is_the_issues():
+    for case in (E.pinned_case(77, 128, 256), E.pinned_case(77, 384, 128, "table"), E.pinned_case(77, 384, 128, "sigma8")):
+        case.check({"y": case.ref[0].half()})
+        case.check({"y": case.model()}, label="model ")
+    names = [c.name for c in E.pinned_cases()]
+    assert len(names) == len(set(names)) == 2 * 16 + 6 * 5 + 2 * 6 - 2          # (77, separate) of the two form pairs is a ragged case too
+    assert len(E.ragged_cases()) == 32 and len(E.edge_cases()) == 30 and len(E.form_cases()) == 12
+    assert {(c.N, c.K) for c in E.ragged_cases()} == {p for pairs in E.PAIRS.values() for p in pairs} and len(E.PAIRS) == 4
+    assert max(c.K for c in E.ragged_cases()) == 4096 == max(c.N for c in E.ragged_cases())
+
+
+def test_pinned_last_k_tile_dropped():
+    """K = 256 = four K-tiles, the loop ending one tile early: every element misses 64 of its products"""
+    case = E.pinned_case(77, 128, 256)
+    a, w = case.inputs["a"].double(), case.inputs["w"].double()
+    bad = case.ref[0] - a[:, 192:] @ w[:, 192:].t()
+    exactly(case, pinned_offenders(case, bad), bad, torch.ones(77, 128, dtype=torch.bool))
+    assert rel_l2(bad.half(), case.ref[0]) > 10 * TOL_OP        # (a quarter of the terms: not a defect rel-L2 passes)
+
+
+def test_pinned_bias_of_the_neighbouring_column_tile():
+    """the second 128-column tile finished with the first tile's bias quads: its columns and no others"""
+    case = E.pinned_case(77, 384, 128)
+    bias = case.inputs["bias"].double()
+    bad = case.ref[0].clone()
+    bad[:, 128:256] += bias[:128] - bias[128:256]
+    region = torch.zeros(77, 384, dtype=torch.bool)
+    region[:, 128:256] = True
+    exactly(case, pinned_offenders(case, bad), bad, region)
+
+
+def test_pinned_residual_row_of_the_next_block():
+    """M = 2 x 77: block 0 adds the residual rows of block 1 (a row offset taken from the wrong image): rows 0..76 and no others"""
+    case = E.pinned_case(154, 384, 128)
+    r = case.inputs["r"].double()
+    bad = case.ref[0].clone()
+    bad[:77] += r[77:] - r[:77]
+    region = torch.zeros(154, 384, dtype=torch.bool)
+    region[:77] = True
+    exactly(case, pinned_offenders(case, bad), bad, region)
+
+
+def test_pinned_clamped_row_stored_to_the_row_behind_a_ragged_tile():
+    """Rows 77..127 of the one tile are clamped to row M - 1 = 76 for their loads; stored unguarded, row 76's values land on row 77:
+    behind the tensor.  Every value inside is right: only the guard band sees it, and names the row.  With the output a column block
+    of a wider buffer the same store lands in the band too."""
+    for form, width in (("separate", 128), ("c_block", 128 + 2 * E.BLOCK)):
+        case = E.pinned_case(77, 128, 128, form)
+        y = case.ref[0].half()
+        col0 = E.BLOCK if form == "c_block" else 0
+
+        def fn(i, o):
+            o["y"][:, col0:col0 + 128] = y
+            torch.as_strided(o["y"], (78, width), (width, 1))[77, col0:col0 + 128] = y[76]
+        with pytest.raises(AssertionError, match=r"y .*guard band damaged in 128 elements, first at offset %d .*row 77, column %d" % (77 * width + col0, col0)):
+            oc.run_guarded(fn, case.inputs, case.outputs, device="cpu", partial=case.partial)
+        got = oc.run_guarded(lambda i, o: o["y"][:, col0:col0 + 128].copy_(y), case.inputs, case.outputs, device="cpu", partial=case.partial)
+        case.check(got)                                           # without the stray store: nothing to report
+
+
+def test_pinned_store_into_the_columns_beside_a_column_block():
+    case = E.pinned_case(77, 128, 128, "c_block")
+    y = case.ref[0].half()
+
+    def fn(i, o):
+        o["y"][:, E.BLOCK:E.BLOCK + 128] = y
+        o["y"][5, E.BLOCK + 128] = 1.0
+    with pytest.raises(AssertionError, match=r"y: 1 elements outside the written region were stored to, first at offset .*row 5, column %d" % (E.BLOCK + 128)):
+        oc.run_guarded(fn, case.inputs, case.outputs, device="cpu", partial=case.partial)
+
+
+def fold_bits_rejected(case, **defect):
+    out, shift = E.fold_reference(**case["arrays"], **defect)
+    cin = case["inputs"]["w"].shape[1]
+    bad = torch.from_numpy(out)
+    with pytest.raises(AssertionError, match="differ in their bits") as e:
+        oc.assert_bits(bad, case["out"], where=E.loc_packed(cin, case["kpad"]), label="fold")
+    return bad.view(torch.int16) != case["out"].view(torch.int16), torch.from_numpy(shift), str(e.value)
+
+
+@pytest.mark.parametrize("label", [gm[0] for gm in E.FOLD_GEOMETRIES])
+def test_fold_defects_are_rejected_bit_for_bit(label):
+    case = E.fold_case(label)
+    cout, cin = case["inputs"]["w"].shape[:2]
+    taps = case["k"] // cin
+    oc.assert_bits(torch.from_numpy(E.fold_reference(**case["arrays"])[0]), case["out"])
+    assert case["double_rounding_differs"] >= 1
+    # eps left out: the channel with var = 0 becomes inf (NaN where the weight is 0); the others move by 5e-6 relative: a few elements each
+    diff, shift, _ = fold_bits_rejected(case, use_eps=False)
+    assert diff[E.VAR0_CHANNEL, :case["k"]].all() and not diff[:, case["k"]:].any()
+    assert (shift.view(torch.int32) != case["shift"].view(torch.int32))[E.VAR0_CHANNEL]
+    # fp32 as an intermediate rounding: exactly the elements counted, the planted ones among them, and the shift untouched
+    diff, shift, msg = fold_bits_rejected(case, via_fp32=True)
+    assert int(diff.sum()) == case["double_rounding_differs"] and f"{case['double_rounding_differs']} of" in msg
+    assert all(diff[co, 0] for co in (0, E.VAR0_CHANNEL, E.NEG_GAMMA_CHANNEL)) and "(cout 0, tap 0, cin 0)" in msg
+    assert torch.equal(shift, case["shift"])
+    # tap and ci exchanged: [Cout][Cin][taps] copied through.  One tap: the two orders are one order, the defect is none
+    if taps == 1:
+        oc.assert_bits(torch.from_numpy(E.fold_reference(**case["arrays"], swap=True)[0]), case["out"])
+    else:
+        diff, _, msg = fold_bits_rejected(case, swap=True)
+        assert diff[:, :case["k"]].float().mean() > 0.9 and "(cout 0, tap 0, cin 1)" in msg          # element 1 holds (tap 1, cin 0)'s weight
+    # the sign of a negative gamma reaches the weights: element 0 of that row is (tap 0, cin 0) in either layout
+    assert float(case["out"][E.NEG_GAMMA_CHANNEL, 0]) * float(case["arrays"]["w"][E.NEG_GAMMA_CHANNEL].reshape(-1)[0]) < 0
+    assert float(case["out"][0, 0]) * float(case["arrays"]["w"][0].reshape(-1)[0]) > 0
+
+
+def test_add_rows_sum_converted_by_truncation_is_rejected():
+    """the fp32 sum cut to fp16 toward zero instead of rounded to nearest (a conversion built from shifts): off by one unit in a
+    quarter of the elements (many sums of two fp16 values are fp16 values themselves), far inside the tolerance of a model test,
+    rejected by the bit comparison"""
+    case = E.add_rows_case(2, 77, 768)
+    x, pos = case["inputs"]["x"], case["inputs"]["pos"]
+    trunc = ((x.float() + pos.float()).view(torch.int32) & ~0x1FFF).view(torch.float32).half()
+    assert 0.1 < float((trunc != case["want"]).float().mean()) < 0.5 and rel_l2(trunc, case["want"].double()) < TOL_OP
+    with pytest.raises(AssertionError, match="differ in their bits"):
+        oc.assert_bits(trunc, case["want"], label="add_rows")
