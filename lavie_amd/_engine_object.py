@@ -1,4 +1,4 @@
-"""What the engine-backed encoders share (text_encoder.py, image_encoder.py): the object the pipelines handle as a part, the
+"""What the engine-backed encoders share (text_encoder.py, image_encoder.py, fvd.py): the object the pipelines handle as a part, the
 loading of a handle's weights, and the CLIP layer's keys and config reader of the text encoder and the vision tower."""
 import ctypes
 
@@ -39,12 +39,12 @@ class LastHiddenState(tuple):
         return self[0]
 
 
-def _load(lib, prefix, h, want, sd, device):
-    """set_param for every key of `want`, finalize, and the end of the loan"""
+def _load(lib, prefix, h, want, sd, device, dtype=torch.float16):
+    """set_param for every key of `want` (as `dtype`, the one the handle reads), finalize, and the end of the loan"""
     with torch.cuda.device(device):
         held = []
         for k in want:
-            t = sd[k].detach().to(device=device, dtype=torch.float16).contiguous()
+            t = sd[k].detach().to(device=device, dtype=dtype).contiguous()
             held.append(t)
             _lib.check(getattr(lib, prefix + "_set_param")(h, k.encode(), ctypes.c_void_p(t.data_ptr()), t.numel()), prefix + "_set_param")
         _lib.check(getattr(lib, prefix + "_finalize")(h, ops._stream()), prefix + "_finalize")

@@ -6,40 +6,6 @@
 
 namespace lavie {
 
-void ParamTable::add(const std::string& name, long long numel) {
-    index_[name] = (int)params_.size();
-    params_.push_back({name, numel, nullptr});
-}
-
-int ParamTable::set(const char* who, const char* prefix, const char* name, const void* data, long long numel) {
-    std::string key = name;
-    const std::string pre = prefix;
-    if (!pre.empty() && key.compare(0, pre.size(), pre) != 0) key = pre + key;
-    for (const std::string& ig : ignored_)
-        if (key == ig) return 0;
-    auto it = index_.find(key);
-    LAVIE_CHECK(it != index_.end(), "%s: unknown state-dict key '%s'", who, name);
-    Param& pi = params_[it->second];
-    LAVIE_CHECK(pi.numel == numel, "%s: '%s' has %lld elements, expected %lld", who, name, numel, pi.numel);
-    LAVIE_CHECK(data != nullptr, "%s: '%s' null data", who, name);
-    pi.src = (const half_t*)data;
-    return 0;
-}
-
-int ParamTable::all_set(const char* who) const {
-    for (const Param& p : params_) LAVIE_CHECK(p.src != nullptr, "%s: '%s' was never set", who, p.name.c_str());
-    return 0;
-}
-
-void ParamTable::release() {
-    for (Param& p : params_) p.src = nullptr;      // the loan ends when the stream drains
-}
-
-int copy16(half_t* dst, const half_t* src, size_t n, hipStream_t s) {
-    LAVIE_HIP(hipMemcpyAsync(dst, src, n * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-    return 0;
-}
-
 int check_clip_shape(const char* who, const ClipShape& c) {
     LAVIE_CHECK(c.hidden >= kPinBn && c.hidden % kPinBn == 0 && c.hidden <= 2048, "%s: hidden=%d must be a multiple of %d up to 2048", who,
                 c.hidden, kPinBn);

@@ -42,12 +42,6 @@ int ensure_dynamic_lds(const void* kernel, int bytes) {
     return 0;
 }
 
-#define RUN(expr)                 \
-    do {                          \
-        int rc_ = (expr);         \
-        if (rc_ != 0) return rc_; \
-    } while (0)
-
 // ------------------------------------------------------------------ arena
 DeviceArena::~DeviceArena() { free_all(); }
 
@@ -131,15 +125,10 @@ int UNet::validate_config() {
 
 void UNet::build_param_list() {
     const lavie_unet_config& c = cfg_;
-    auto add = [&](const std::string& name, std::vector<int> shape) {
-        long long n = 1;
-        for (int s : shape) n *= s;
-        index_[name] = params_.size();
-        params_.push_back({name, shape, n});
-    };
-    auto affine = [&](const std::string& p, int ch) { add(p + ".weight", {ch}); add(p + ".bias", {ch}); };
-    auto conv = [&](const std::string& p, int cin, int cout, int k) { add(p + ".weight", {cout, cin, k, k}); add(p + ".bias", {cout}); };
-    auto lin = [&](const std::string& p, int cin, int cout, bool bias) { add(p + ".weight", {cout, cin}); if (bias) add(p + ".bias", {cout}); };
+    auto add = [&](const std::string& name, long long numel) { table_.add(name, numel); };
+    auto affine = [&](const std::string& p, int ch) { add(p + ".weight", ch); add(p + ".bias", ch); };
+    auto conv = [&](const std::string& p, long long cin, long long cout, int k) { add(p + ".weight", cout * cin * k * k); add(p + ".bias", cout); };
+    auto lin = [&](const std::string& p, long long cin, long long cout, bool bias) { add(p + ".weight", cout * cin); if (bias) add(p + ".bias", cout); };
     const int temb = c.block_out_channels[0] * 4;
     int temb_total = 0;
     auto resnet = [&](const std::string& p, int cin, int cout) {
@@ -158,7 +147,7 @@ void UNet::build_param_list() {
         lin(p + ".to_q", ch, ch, false); lin(p + ".to_k", kv, ch, false); lin(p + ".to_v", kv, ch, false);
         lin(p + ".to_out.0", ch, ch, true);
     };
-    auto conv_t = [&](const std::string& p, int cin, int cout, int taps) { add(p + ".weight", {cout, cin, taps, 1, 1}); add(p + ".bias", {cout}); };
+    auto conv_t = [&](const std::string& p, long long cin, long long cout, int taps) { add(p + ".weight", cout * cin * taps); add(p + ".bias", cout); };
     auto transformer = [&](const std::string& p, int ch, int level) {
         const bool vsr = c.vsr_blocks != 0;
         const bool cross1 = vsr && level >= 0 && c.only_cross_attention[level] != 0;
@@ -178,8 +167,10 @@ void UNet::build_param_list() {
         affine(b + ".norm2", ch);
         attention(b + ".attn_" + tname, ch, ch);
         if (!c.temporal_plain) {
-            add(b + ".attn_" + tname + ".time_rel_pos_bias.relative_attention_bias.weight", {c.rel_buckets, c.heads});
-            add(b + ".attn_" + tname + ".rotary_emb.freqs", {c.rotary_dim / 2});
+            add(b + ".attn_" + tname + ".time_rel_pos_bias.relative_attention_bias.weight", (long long)c.rel_buckets * c.heads);
+            // listed so that the loader sends it, never read: angles are always derived in fp32 from rotary_dim (SURVEY.md §8c
+            // decision; an fp16 copy of freqs would be lossy)
+            table_.add(b + ".attn_" + tname + ".rotary_emb.freqs", c.rotary_dim / 2, /*required=*/false);
         }
         affine(b + ".norm_" + tname, ch);
         lin(b + ".ff.net.0.proj", ch, 8 * ch, true);
@@ -216,8 +207,8 @@ void UNet::build_param_list() {
     const bool tmod = c.vsr_temporal_modules != 0;
     const int* widths = c.block_out_channels;
     const int L = c.num_levels;
-    if (c.num_class_embeds > 0) add("class_embedding.weight", {c.num_class_embeds, temb});
-    if (c.vsr_blocks && !c.temporal_plain) add("temporal_rotary_emb.freqs", {c.rotary_dim / 2});   // accepted, ignored
+    if (c.num_class_embeds > 0) add("class_embedding.weight", (long long)c.num_class_embeds * temb);
+    if (c.vsr_blocks && !c.temporal_plain) table_.add("temporal_rotary_emb.freqs", c.rotary_dim / 2, /*required=*/false);   // as rotary_emb.freqs
     conv("conv_in", c.in_channels, widths[0], 3);
     lin("time_embedding.linear_1", widths[0], temb, true);
     lin("time_embedding.linear_2", temb, temb, true);
@@ -256,98 +247,63 @@ void UNet::build_param_list() {
     }
     affine("conv_norm_out", widths[0]);
     conv("conv_out", widths[0], c.out_channels, 3);
-    given_.assign(params_.size(), nullptr);
     tproj_.N = temb_total;
     tproj_.K = temb;
 }
 
-int UNet::set_param(const char* name, const void* data, long long numel) {
-    auto it = index_.find(name);
-    LAVIE_CHECK(it != index_.end(), "set_param: unknown state-dict key '%s'", name);
-    const ParamInfo& pi = params_[it->second];
-    LAVIE_CHECK(pi.numel == numel, "set_param: '%s' has %lld elements, expected %lld", name, numel, pi.numel);
-    LAVIE_CHECK(data != nullptr, "set_param: '%s' null data", name);
-    given_[it->second] = (const half_t*)data;
-    return 0;
-}
-
-const half_t* UNet::given(const std::string& name) const {
-    auto it = index_.find(name);
-    return it == index_.end() ? nullptr : given_[it->second];
-}
-
 // ------------------------------------------------------------------ weight packing
-#define NEED(ptr, name) LAVIE_CHECK((ptr) != nullptr, "finalize: missing state-dict tensor '%s'", (name).c_str())
+// finalize has checked that every required tensor is set, so table_.src() of a key cannot fail below: a key that is listed under a
+// condition is looked up under the same condition
 #define WALLOC(var, type, count)                                                                  \
     do {                                                                                          \
         (var) = (type*)weights_.alloc((size_t)(count) * sizeof(type));                            \
         LAVIE_CHECK((var) != nullptr, "finalize: out of device memory (%zu B; hip: %s)", (size_t)(count) * sizeof(type), hipGetErrorString(hipGetLastError())); \
     } while (0)
 
+int UNet::pack_f32(const std::string& key, size_t n, float** out, hipStream_t s) {
+    WALLOC(*out, float, n);
+    return launch_f16_to_f32(table_.src(key), *out, (int64_t)n, s);
+}
+
+int UNet::pack_copy(const std::string& key, size_t n, half_t** out, hipStream_t s) {
+    WALLOC(*out, half_t, n);
+    return copy16(*out, table_.src(key), n, s);
+}
+
 int UNet::pack_norm(const std::string& prefix, int C, NormW* out, hipStream_t s) {
-    const half_t* g = given(prefix + ".weight");
-    const half_t* b = given(prefix + ".bias");
-    NEED(g, prefix + ".weight");
-    NEED(b, prefix + ".bias");
     out->C = C;
-    WALLOC(out->g, float, C);
-    WALLOC(out->b, float, C);
-    RUN(launch_f16_to_f32(g, out->g, C, s));
-    RUN(launch_f16_to_f32(b, out->b, C, s));
-    return 0;
+    RUN(pack_f32(prefix + ".weight", C, &out->g, s));
+    return pack_f32(prefix + ".bias", C, &out->b, s);
 }
 
 int UNet::pack_linear(const std::string& prefix, int N, int K, bool bias, LinW* out, hipStream_t s) {
-    const half_t* w = given(prefix + ".weight");
-    NEED(w, prefix + ".weight");
     out->N = N;
     out->K = K;
-    WALLOC(out->w, half_t, (size_t)N * K);
-    LAVIE_HIP(hipMemcpyAsync(out->w, w, (size_t)N * K * sizeof(half_t), hipMemcpyDeviceToDevice, s));
     out->b = nullptr;
-    if (bias) {
-        const half_t* b = given(prefix + ".bias");
-        NEED(b, prefix + ".bias");
-        WALLOC(out->b, float, N);
-        RUN(launch_f16_to_f32(b, out->b, N, s));
-    }
-    return 0;
+    RUN(pack_copy(prefix + ".weight", (size_t)N * K, &out->w, s));
+    return bias ? pack_f32(prefix + ".bias", N, &out->b, s) : 0;
 }
 
 int UNet::pack_resnet(ResnetW* r, hipStream_t s) {
     const std::string& p = r->prefix;
     RUN(pack_norm(p + ".norm1", r->cin, &r->n1, s));
     RUN(pack_norm(p + ".norm2", r->cout, &r->n2, s));
-    const half_t* w1 = given(p + ".conv1.weight");
-    const half_t* b1 = given(p + ".conv1.bias");
-    const half_t* w2 = given(p + ".conv2.weight");
-    const half_t* b2 = given(p + ".conv2.bias");
-    NEED(w1, p + ".conv1.weight"); NEED(b1, p + ".conv1.bias"); NEED(w2, p + ".conv2.weight"); NEED(b2, p + ".conv2.bias");
     WALLOC(r->w1, half_t, (size_t)r->cout * 9 * r->cin);
-    RUN(launch_pack_conv3x3(w1, r->w1, r->cout, r->cin, 9 * r->cin, 0, true, s));
-    WALLOC(r->b1, float, r->cout);
-    RUN(launch_f16_to_f32(b1, r->b1, r->cout, s));
+    RUN(launch_pack_conv3x3(table_.src(p + ".conv1.weight"), r->w1, r->cout, r->cin, 9 * r->cin, 0, true, s));
+    RUN(pack_f32(p + ".conv1.bias", r->cout, &r->b1, s));
     r->ldw2 = 9 * r->cout + (r->shortcut ? r->cin : 0);
     WALLOC(r->w2, half_t, (size_t)r->cout * r->ldw2);
-    RUN(launch_pack_conv3x3(w2, r->w2, r->cout, r->cout, r->ldw2, 0, true, s));
-    WALLOC(r->b2, float, r->cout);
+    RUN(launch_pack_conv3x3(table_.src(p + ".conv2.weight"), r->w2, r->cout, r->cout, r->ldw2, 0, true, s));
     if (r->shortcut) {
-        const half_t* ws = given(p + ".conv_shortcut.weight");
-        const half_t* bs = given(p + ".conv_shortcut.bias");
-        NEED(ws, p + ".conv_shortcut.weight"); NEED(bs, p + ".conv_shortcut.bias");
-        RUN(launch_copy_rows(ws, r->cin, r->w2, r->ldw2, r->cout, r->cin, 9 * r->cout, s));
-        RUN(launch_add_f16_to_f32(b2, bs, r->b2, r->cout, s));
+        WALLOC(r->b2, float, r->cout);
+        RUN(launch_copy_rows(table_.src(p + ".conv_shortcut.weight"), r->cin, r->w2, r->ldw2, r->cout, r->cin, 9 * r->cout, s));
+        RUN(launch_add_f16_to_f32(table_.src(p + ".conv2.bias"), table_.src(p + ".conv_shortcut.bias"), r->b2, r->cout, s));
     } else {
-        RUN(launch_f16_to_f32(b2, r->b2, r->cout, s));
+        RUN(pack_f32(p + ".conv2.bias", r->cout, &r->b2, s));
     }
     // fused time_emb_proj rows
-    const half_t* wt = given(p + ".time_emb_proj.weight");
-    const half_t* bt = given(p + ".time_emb_proj.bias");
-    NEED(wt, p + ".time_emb_proj.weight"); NEED(bt, p + ".time_emb_proj.bias");
-    LAVIE_HIP(hipMemcpyAsync(tproj_.w + (size_t)r->temb_off * tproj_.K, wt, (size_t)r->cout * tproj_.K * sizeof(half_t),
-                             hipMemcpyDeviceToDevice, s));
-    RUN(launch_f16_to_f32(bt, tproj_.b + r->temb_off, r->cout, s));
-    return 0;
+    RUN(copy16(tproj_.w + (size_t)r->temb_off * tproj_.K, table_.src(p + ".time_emb_proj.weight"), (size_t)r->cout * tproj_.K, s));
+    return launch_f16_to_f32(table_.src(p + ".time_emb_proj.bias"), tproj_.b + r->temb_off, r->cout, s);
 }
 
 int UNet::pack_transformer(TransformerW* t, hipStream_t s) {
@@ -365,12 +321,8 @@ int UNet::pack_transformer(TransformerW* t, hipStream_t s) {
     RUN(pack_norm(b + ".norm3", C, &t->ln3, s));
     auto fuse = [&](const std::string& a, const char* const* names, int count, int K, half_t** out) -> int {
         WALLOC(*out, half_t, (size_t)count * C * K);
-        for (int i = 0; i < count; ++i) {
-            const std::string key = a + "." + names[i] + ".weight";
-            const half_t* w = given(key);
-            NEED(w, key);
-            LAVIE_HIP(hipMemcpyAsync(*out + (size_t)i * C * K, w, (size_t)C * K * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-        }
+        for (int i = 0; i < count; ++i)
+            RUN(copy16(*out + (size_t)i * C * K, table_.src(a + "." + names[i] + ".weight"), (size_t)C * K, s));
         return 0;
     };
     static const char* const qkv[] = {"to_q", "to_k", "to_v"};
@@ -389,25 +341,15 @@ int UNet::pack_transformer(TransformerW* t, hipStream_t s) {
     RUN(pack_linear(b + ".attn2.to_out.0", C, C, true, &t->o2, s));
     RUN(fuse(b + ".attn_" + tname, qkv, 3, C, &t->qkvt.w));
     RUN(pack_linear(b + ".attn_" + tname + ".to_out.0", C, C, true, &t->ot, s));
-    if (!cfg_.temporal_plain) {
-        const std::string key = b + ".attn_" + tname + ".time_rel_pos_bias.relative_attention_bias.weight";
-        const half_t* e = given(key);
-        NEED(e, key);
-        const size_t n = (size_t)cfg_.rel_buckets * cfg_.heads;
-        WALLOC(t->relemb, half_t, n);
-        LAVIE_HIP(hipMemcpyAsync(t->relemb, e, n * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-        // `...rotary_emb.freqs` is accepted by set_param and ignored: angles are always derived in
-        // fp32 from rotary_dim (SURVEY.md §8c decision; an fp16 copy of freqs would be lossy).
-    }
-    {
-        const half_t* w = given(b + ".ff.net.0.proj.weight");
-        const half_t* bias = given(b + ".ff.net.0.proj.bias");
-        NEED(w, b + ".ff.net.0.proj.weight"); NEED(bias, b + ".ff.net.0.proj.bias");
-        WALLOC(t->ff1.w, half_t, (size_t)8 * C * C);
-        WALLOC(t->ff1.b, float, 8 * C);
-        RUN(launch_pack_geglu_rows(w, t->ff1.w, 8 * C, C, s));
-        RUN(launch_pack_geglu_bias(bias, t->ff1.b, 8 * C, s));
-    }
+    if (!cfg_.temporal_plain)
+        RUN(pack_copy(b + ".attn_" + tname + ".time_rel_pos_bias.relative_attention_bias.weight", (size_t)cfg_.rel_buckets * cfg_.heads,
+                      &t->relemb, s));
+    const half_t* ff1_w = table_.src(b + ".ff.net.0.proj.weight");
+    const half_t* ff1_b = table_.src(b + ".ff.net.0.proj.bias");
+    WALLOC(t->ff1.w, half_t, (size_t)8 * C * C);
+    WALLOC(t->ff1.b, float, 8 * C);
+    RUN(launch_pack_geglu_rows(ff1_w, t->ff1.w, 8 * C, C, s));
+    RUN(launch_pack_geglu_bias(ff1_b, t->ff1.b, 8 * C, s));
     RUN(pack_linear(b + ".ff.net.2", C, 4 * C, true, &t->ff2, s));
     // derived images and LayerNorm folds of the attention projections: allocated here, filled by derive_transformer() from the
     // packed copies above, which lora_apply() rewrites in place and fills again through the same function
@@ -418,13 +360,9 @@ int UNet::pack_transformer(TransformerW* t, hipStream_t s) {
     if (!t->attn1_cross && !cfg_.vsr_blocks && proj_qkv_supported(C))                  // fused GroupNorm -> proj_in -> norm1 -> q|k|v
         WALLOC(t->pq_img, half_t, proj_qkv_image_bytes(C) / sizeof(half_t));
     if (geglu_mlp_supported(C)) {      // fused norm3 -> feed-forward -> residual kernel: weight image in MFMA-fragment order
-        const half_t* w1 = given(b + ".ff.net.0.proj.weight");
-        const half_t* b1 = given(b + ".ff.net.0.proj.bias");
-        const half_t* w2 = given(b + ".ff.net.2.weight");
-        NEED(w2, b + ".ff.net.2.weight");
         WALLOC(t->ff_img, half_t, geglu_mlp_image_bytes(C) / sizeof(half_t));
         WALLOC(t->ff_b1img, float, geglu_mlp_bias_floats(C));
-        RUN(pack_geglu_mlp(w1, b1, w2, C, t->ff_img, t->ff_b1img, s));
+        RUN(pack_geglu_mlp(ff1_w, ff1_b, table_.src(b + ".ff.net.2.weight"), C, t->ff_img, t->ff_b1img, s));
     }
 
     // LayerNorm-folded projections (norm1 -> attn1 qkv, norm2 -> attn2 q, norm_temp -> attn_temp qkv, norm3 -> GEGLU)
@@ -438,11 +376,9 @@ int UNet::pack_transformer(TransformerW* t, hipStream_t s) {
     RUN(derive_transformer(*t, s));
     {
         // GEGLU: fold in the checkpoint's row order, then apply the value/gate interleave to W', s and b'
-        const half_t* w = given(b + ".ff.net.0.proj.weight");
-        const half_t* bias = given(b + ".ff.net.0.proj.bias");
         LnProj tmp = t->ff1;
         RUN(fold_alloc(&tmp));
-        RUN(launch_ln_fold(w, t->ln3.g, t->ln3.b, bias, tmp.fw, tmp.fs, tmp.fb, 8 * C, C, s));
+        RUN(launch_ln_fold(ff1_w, t->ln3.g, t->ln3.b, ff1_b, tmp.fw, tmp.fs, tmp.fb, 8 * C, C, s));
         RUN(fold_alloc(&t->ff1));
         RUN(launch_pack_geglu_rows(tmp.fw, t->ff1.fw, 8 * C, C, s));
         RUN(launch_pack_geglu_vec(tmp.fs, t->ff1.fs, 8 * C, s));
@@ -471,32 +407,20 @@ int UNet::pack_temporal_res(const std::string& prefix, int C, int taps1, Tempora
     out->taps1 = taps1;
     RUN(pack_norm(prefix + ".norm1", C, &out->n1, s));
     RUN(pack_norm(prefix + ".norm2", C, &out->n2, s));
-    const half_t* w1 = given(prefix + ".conv1.weight");
-    const half_t* b1 = given(prefix + ".conv1.bias");
-    const half_t* w2 = given(prefix + ".conv2.weight");
-    const half_t* b2 = given(prefix + ".conv2.bias");
-    NEED(w1, prefix + ".conv1.weight"); NEED(b1, prefix + ".conv1.bias");
-    NEED(w2, prefix + ".conv2.weight"); NEED(b2, prefix + ".conv2.bias");
     WALLOC(out->w1, half_t, (size_t)C * taps1 * C);
     WALLOC(out->w2, half_t, (size_t)C * 3 * C);
-    WALLOC(out->b1, float, C);
-    WALLOC(out->b2, float, C);
-    RUN(launch_pack_conv_taps(w1, out->w1, C, C, taps1, taps1 * C, 0, true, s));
-    RUN(launch_pack_conv_taps(w2, out->w2, C, C, 3, 3 * C, 0, true, s));
-    RUN(launch_f16_to_f32(b1, out->b1, C, s));
-    RUN(launch_f16_to_f32(b2, out->b2, C, s));
-    return 0;
+    RUN(launch_pack_conv_taps(table_.src(prefix + ".conv1.weight"), out->w1, C, C, taps1, taps1 * C, 0, true, s));
+    RUN(launch_pack_conv_taps(table_.src(prefix + ".conv2.weight"), out->w2, C, C, 3, 3 * C, 0, true, s));
+    RUN(pack_f32(prefix + ".conv1.bias", C, &out->b1, s));
+    return pack_f32(prefix + ".conv2.bias", C, &out->b2, s);
 }
 
 int UNet::pack_sampler(const std::string& prefix, int C, SamplerW* out, hipStream_t s, bool up) {
-    const half_t* w = given(prefix + ".weight");
-    const half_t* b = given(prefix + ".bias");
-    NEED(w, prefix + ".weight"); NEED(b, prefix + ".bias");
+    const half_t* w = table_.src(prefix + ".weight");
     out->C = C;
     WALLOC(out->w, half_t, (size_t)C * 9 * C);
-    WALLOC(out->b, float, C);
     RUN(launch_pack_conv3x3(w, out->w, C, C, 9 * C, 0, true, s));
-    RUN(launch_f16_to_f32(b, out->b, C, s));
+    RUN(pack_f32(prefix + ".bias", C, &out->b, s));
     if (up && C % 160 == 0) {          // conv(nearest_x2(x)) as four 2x2 convs on x: weights of coinciding taps summed once, here
         WALLOC(out->wpar, half_t, (size_t)4 * C * 4 * C);
         RUN(launch_pack_conv3x3_parity(w, out->wpar, C, C, s));
@@ -507,27 +431,34 @@ int UNet::pack_sampler(const std::string& prefix, int C, SamplerW* out, hipStrea
 int UNet::finalize(hipStream_t s) {
     RUN(validate_config());
     LAVIE_CHECK(!finalized_, "finalize: already finalized");
+    RUN(table_.all_set("finalize"));      // a missing tensor is refused here, before anything is allocated or enqueued
+    if (const int rc = pack_model(s)) {
+        // out of memory or a HIP error half way: give the arena back, so that a retry starts from nothing.  hipFree waits for the
+        // copies and pack kernels already enqueued into it
+        weights_.free_all();
+        downs_.clear();
+        ups_.clear();
+        return rc;
+    }
+    lora_dirty_.assign(transformers_.size(), 0);
+    table_.release();                     // the caller's tensors are read by what is enqueued on s: theirs again once s has drained
+    finalized_ = true;
+    return 0;
+}
+
+int UNet::pack_model(hipStream_t s) {
     const lavie_unet_config& c = cfg_;
     const int C0 = c.block_out_channels[0];
     WALLOC(zero_page_, half_t, 256);
     LAVIE_HIP(hipMemsetAsync(zero_page_, 0, 512, s));
-    {   // conv_in / conv_out / conv_norm_out
-        const half_t* w = given("conv_in.weight");
-        const half_t* b = given("conv_in.bias");
-        NEED(w, std::string("conv_in.weight")); NEED(b, std::string("conv_in.bias"));
-        WALLOC(conv_in_w_, half_t, (size_t)9 * c.in_channels * C0);
-        WALLOC(conv_in_b_, float, C0);
-        RUN(launch_pack_conv_in(w, conv_in_w_, C0, c.in_channels, s));
-        RUN(launch_f16_to_f32(b, conv_in_b_, C0, s));
-        const half_t* wo = given("conv_out.weight");
-        const half_t* bo = given("conv_out.bias");
-        NEED(wo, std::string("conv_out.weight")); NEED(bo, std::string("conv_out.bias"));
-        WALLOC(conv_out_w_, half_t, (size_t)c.out_channels * 9 * C0);
-        WALLOC(conv_out_b_, float, c.out_channels);
-        RUN(launch_pack_conv3x3(wo, conv_out_w_, c.out_channels, C0, 9 * C0, 0, false, s));
-        RUN(launch_f16_to_f32(bo, conv_out_b_, c.out_channels, s));
-        RUN(pack_norm("conv_norm_out", C0, &norm_out_, s));
-    }
+    // conv_in / conv_out / conv_norm_out
+    WALLOC(conv_in_w_, half_t, (size_t)9 * c.in_channels * C0);
+    RUN(launch_pack_conv_in(table_.src("conv_in.weight"), conv_in_w_, C0, c.in_channels, s));
+    RUN(pack_f32("conv_in.bias", C0, &conv_in_b_, s));
+    WALLOC(conv_out_w_, half_t, (size_t)c.out_channels * 9 * C0);
+    RUN(launch_pack_conv3x3(table_.src("conv_out.weight"), conv_out_w_, c.out_channels, C0, 9 * C0, 0, false, s));
+    RUN(pack_f32("conv_out.bias", c.out_channels, &conv_out_b_, s));
+    RUN(pack_norm("conv_norm_out", C0, &norm_out_, s));
     RUN(pack_linear("time_embedding.linear_1", C0 * 4, C0, true, &time1_, s));
     RUN(pack_linear("time_embedding.linear_2", C0 * 4, C0 * 4, true, &time2_, s));
     WALLOC(tproj_.w, half_t, (size_t)tproj_.N * tproj_.K);
@@ -535,23 +466,14 @@ int UNet::finalize(hipStream_t s) {
     for (ResnetW& r : resnets_) RUN(pack_resnet(&r, s));
     for (TransformerW& t : transformers_) RUN(pack_transformer(&t, s));
     for (TemporalModuleW& m : tmods_) {
-        RUN(pack_temporal_res(m.prefix + ".resblocks_3d_t", m.C, 5, &m.t, s));
-        const half_t* wt = given(m.prefix + ".resblocks_3d_t.time_emb_proj.weight");
-        const half_t* bt = given(m.prefix + ".resblocks_3d_t.time_emb_proj.bias");
-        NEED(wt, m.prefix + ".resblocks_3d_t.time_emb_proj.weight"); NEED(bt, m.prefix + ".resblocks_3d_t.time_emb_proj.bias");
-        LAVIE_HIP(hipMemcpyAsync(tproj_.w + (size_t)m.t_temb_off * tproj_.K, wt, (size_t)m.C * tproj_.K * sizeof(half_t),
-                                 hipMemcpyDeviceToDevice, s));
-        RUN(launch_f16_to_f32(bt, tproj_.b + m.t_temb_off, m.C, s));
+        const std::string t = m.prefix + ".resblocks_3d_t";
+        RUN(pack_temporal_res(t, m.C, 5, &m.t, s));
+        RUN(copy16(tproj_.w + (size_t)m.t_temb_off * tproj_.K, table_.src(t + ".time_emb_proj.weight"), (size_t)m.C * tproj_.K, s));
+        RUN(launch_f16_to_f32(table_.src(t + ".time_emb_proj.bias"), tproj_.b + m.t_temb_off, m.C, s));
         RUN(pack_resnet(&m.s, s));
         RUN(pack_linear(m.prefix + ".shift_conv", m.C, m.C, true, &m.shift, s));
     }
-    if (c.num_class_embeds > 0) {
-        const half_t* e = given("class_embedding.weight");
-        NEED(e, std::string("class_embedding.weight"));
-        const size_t n = (size_t)c.num_class_embeds * C0 * 4;
-        WALLOC(class_emb_, half_t, n);
-        LAVIE_HIP(hipMemcpyAsync(class_emb_, e, n * sizeof(half_t), hipMemcpyDeviceToDevice, s));
-    }
+    if (c.num_class_embeds > 0) RUN(pack_copy("class_embedding.weight", (size_t)c.num_class_embeds * C0 * 4, &class_emb_, s));
     const int L = c.num_levels;
     downs_.resize(L > 1 ? L - 1 : 0);
     ups_.resize(L > 1 ? L - 1 : 0);
@@ -559,8 +481,6 @@ int UNet::finalize(hipStream_t s) {
         RUN(pack_sampler("down_blocks." + std::to_string(l) + ".downsamplers.0.conv", c.block_out_channels[l], &downs_[l], s));
     for (int i = 0; i + 1 < L; ++i)
         RUN(pack_sampler("up_blocks." + std::to_string(i) + ".upsamplers.0.conv", c.block_out_channels[L - 1 - i], &ups_[i], s, /*up=*/true));
-    lora_dirty_.assign(transformers_.size(), 0);
-    finalized_ = true;
     return 0;
 }
 
@@ -1599,7 +1519,7 @@ int UNet::ensure_long_templates(hipStream_t stream) {
 // `name` is `<transformer>.transformer_blocks.0.<attn1 | attn2 | attn_temp(oral)>.<to_q | to_k | to_v | to_out.0>.weight`: attn = 0 / 1 / 2,
 // proj = 0 .. 3.  Host only: the C ABI refuses a bad name before any HIP call.
 int UNet::lora_target(const char* name, int* ti, int* attn, int* proj) const {
-    LAVIE_CHECK(index_.count(name) != 0, "lora: unknown state-dict key '%s'", name);
+    LAVIE_CHECK(table_.find(name) != nullptr, "lora: unknown state-dict key '%s'", name);
     const std::string tname = cfg_.vsr_blocks ? "attn_temporal" : "attn_temp";
     const char* const attns[3] = {"attn1", "attn2", tname.c_str()};
     static const char* const projs[4] = {"to_q", "to_k", "to_v", "to_out.0"};
@@ -1641,11 +1561,10 @@ int UNet::lora_set_slot(int slot, const char* name, const half_t* base, const fl
     auto found = lora_.find(name);
     if (found == lora_.end()) {
         const TransformerW& t = transformers_[ti];
-        const ParamInfo& pi = params_[index_.at(name)];
         LoraEntry e;
         e.ti = ti;
-        e.N = pi.shape[0];
-        e.K = pi.shape[1];
+        e.N = t.C;                                  // every target is [C][K]: K = C, or the text width behind to_k / to_v
+        e.K = (int)(table_.find(name)->numel / e.N);
         const size_t nk = (size_t)e.N * e.K;
         if (proj == 3) e.dst = attn == 0 ? t.o1.w : attn == 1 ? t.o2.w : t.ot.w;
         else if (attn == 0 && t.attn1_cross) e.dst = proj == 0 ? t.qkv1.w : t.wkv1 + (proj - 1) * nk;

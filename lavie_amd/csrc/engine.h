@@ -8,6 +8,7 @@
 #include "../../include/lavie_hip.h"
 #include "common.h"
 #include "ops.h"
+#include "weight_parts.h"
 
 namespace lavie {
 
@@ -30,12 +31,6 @@ private:
     size_t cap_ = 0, off_ = 0, peak_ = 0, total_ = 0;
     bool fixed_ = false, virtual_ = false;
     static constexpr size_t kChunk = 512ull << 20;
-};
-
-struct ParamInfo {
-    std::string name;
-    std::vector<int> shape;
-    long long numel;
 };
 
 struct NormW { float* g = nullptr; float* b = nullptr; int C = 0; };
@@ -155,8 +150,8 @@ public:
     explicit UNet(const lavie_unet_config& cfg);
     ~UNet();
     int validate_config();
-    const std::vector<ParamInfo>& params() const { return params_; }
-    int set_param(const char* name, const void* data, long long numel);
+    const std::vector<ParamTable::Param>& params() const { return table_.params(); }
+    int set_param(const char* name, const void* data, long long numel) { return table_.set("set_param", "", name, data, numel); }
     int finalize(hipStream_t stream);
     int prepare(int B, int F, int H, int W, int ctx_len);
     // layer_cache: LAVIE_LAYER_CACHE_OFF (the plain forward), _REFRESH (the full walk, filling the layer cache) or _REUSE (the
@@ -211,7 +206,10 @@ public:
 
 private:
     void build_param_list();
-    const half_t* given(const std::string& name) const;
+    int pack_model(hipStream_t s);                  // finalize's body: everything it allocates and enqueues
+    // a listed tensor into a fresh piece of the weight arena: n floats converted from fp16 / n halves copied
+    int pack_f32(const std::string& key, size_t n, float** out, hipStream_t s);
+    int pack_copy(const std::string& key, size_t n, half_t** out, hipStream_t s);
     int pack_norm(const std::string& prefix, int C, NormW* out, hipStream_t s);
     int pack_linear(const std::string& prefix, int N, int K, bool bias, LinW* out, hipStream_t s);
     int pack_resnet(ResnetW* r, hipStream_t s);
@@ -258,9 +256,7 @@ private:
     unsigned long graph_gen_ = 0;
 
     lavie_unet_config cfg_;
-    std::vector<ParamInfo> params_;
-    std::unordered_map<std::string, size_t> index_;
-    std::vector<const half_t*> given_;
+    ParamTable table_;                              // the state-dict tensors, lent by set_param until finalize has packed them
     bool finalized_ = false;
     // The two per-handle switches of a call's Route: read by call_ctx() and by prepare(), nowhere below.
     // the caller promises sample[b] == sample[b + B/2] (classifier-free guidance on duplicated latents): the layers in front of

@@ -301,6 +301,57 @@ struct Model {      // a finalized engine with zero weights
     }
 };
 
+// A handle that lacks one tensor: finalize refuses it by name before anything is allocated; with the tensor supplied, the second
+// finalize enqueues exactly what the finalize of a handle that was complete from the start enqueues.  The `...rotary_emb.freqs`
+// keys are never sent to it: they are listed, and nothing asks for them.
+static void run_withheld_tensor(const lavie_unet_config& cfg, const char* withheld) {
+    auto trace_of = [](const std::function<void()>& body) {
+        FILE* f = tmpfile();
+        REQUIRE(f != nullptr);
+        lavie_hostcheck_trace_to(f);
+        lavie_hostcheck_trace_copies(1);
+        body();
+        lavie_hostcheck_trace_copies(0);
+        lavie_hostcheck_trace_to(nullptr);
+        std::string text((size_t)ftell(f), '\0');
+        rewind(f);
+        REQUIRE(fread(&text[0], 1, text.size(), f) == text.size());
+        fclose(f);
+        return text;
+    };
+    const std::string complete = trace_of([&] { Model m(cfg); });
+    REQUIRE(!complete.empty());
+    lavie_unet_t h = nullptr;
+    REQUIRE(lavie_unet_create(&cfg, &h) == 0);
+    std::vector<void*> bufs;
+    void* late = nullptr;
+    long long late_numel = 0;
+    for (int i = 0; i < lavie_unet_num_params(h); ++i) {
+        const char* name = nullptr;
+        long long numel = 0;
+        REQUIRE(lavie_unet_param_info(h, i, &name, &numel) == 0);
+        const size_t len = strlen(name);
+        if (len >= 16 && strcmp(name + len - 16, "rotary_emb.freqs") == 0) continue;
+        bufs.push_back(calloc((size_t)numel, 2));
+        if (strcmp(name, withheld) == 0) {
+            late = bufs.back();
+            late_numel = numel;
+        } else {
+            REQUIRE(lavie_unet_set_param(h, name, bufs.back(), numel) == 0);
+        }
+    }
+    REQUIRE(late != nullptr);
+    const long before = lavie_hostcheck_launches();
+    REQUIRE(lavie_unet_finalize(h, nullptr) != 0 && strstr(lavie_last_error(), "was never set") && strstr(lavie_last_error(), withheld));
+    REQUIRE(lavie_unet_weight_bytes(h) == 0 && lavie_hostcheck_launches() == before);
+    REQUIRE(lavie_unet_set_param(h, withheld, late, late_numel) == 0);
+    const std::string second = trace_of([&] { REQUIRE(lavie_unet_finalize(h, nullptr) == 0); });
+    REQUIRE(second == complete);
+    REQUIRE(lavie_unet_weight_bytes(h) > 0);
+    REQUIRE(lavie_unet_destroy(h) == 0);
+    for (void* p : bufs) free(p);
+}
+
 // prepare for the shape (the switches in force decide the workspace plan; its size is recorded), then one forward: cached context
 // and shared classifier-free-guidance prefix where the variant allows them, labels for a class-embedded model
 static void trace_forward(const lavie_unet_config& cfg, Model& m, int B, int F, int H, int W, bool cached, bool shared, int ctx_len = 77) {
@@ -961,7 +1012,9 @@ int main(int argc, char** argv) {
         c.in_channels = 8; c.block_out_channels[0] = 256; c.block_out_channels[1] = 512; c.attn_levels[1] = 1;
         c.vsr_blocks = 1; c.only_cross_attention[0] = 1; c.vsr_temporal_modules = 1; c.num_class_embeds = 10;
         run_model(c, 2, 4, 8, 8, true);
+        run_withheld_tensor(c, "class_embedding.weight");           // listed under a condition, packed late
     }
+    run_withheld_tensor(base_config(), "mid_block.attentions.0.transformer_blocks.0.attn_temp.to_out.0.bias");
     run_layer_cache(false);
     run_layer_cache(true);
     // operator-level argument checks

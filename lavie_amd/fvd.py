@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from ._engine_object import _EngineObject, _load
 
 IMAGENET_MEAN, IMAGENET_STD = ops.IMAGENET_MEAN, ops.IMAGENET_STD
 BN_EPS = 1e-5
@@ -78,7 +79,9 @@ def fold_batchnorm(weight, gamma, beta, mean, var, eps=BN_EPS):
     return w, (beta.double() - mean.double() * scale).to(torch.float32)
 
 
-class HipR3D18:
+class HipR3D18(_EngineObject):
+    _destroy = "lavie_r3d_destroy"
+
     def __init__(self, state_dict, device="cuda"):
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -88,14 +91,7 @@ class HipR3D18:
         handle = ctypes.c_void_p()
         _lib.check(lib.lavie_r3d_create(ctypes.byref(handle)), "lavie_r3d_create")
         self._h = handle
-        with torch.cuda.device(self.device):
-            keep = []
-            for name, value in sd.items():
-                t = value.detach().to(device=self.device, dtype=torch.float32).contiguous()
-                keep.append(t)
-                _lib.check(lib.lavie_r3d_set_param(self._h, name.encode(), ctypes.c_void_p(t.data_ptr()), t.numel()), "lavie_r3d_set_param")
-            _lib.check(lib.lavie_r3d_finalize(self._h, ops._stream()), "lavie_r3d_finalize")
-            torch.cuda.current_stream().synchronize()      # the loan of `keep` ends here
+        _load(lib, "lavie_r3d", handle, sd.keys(), sd, self.device, dtype=torch.float32)
 
     @classmethod
     def from_state_dict(cls, sd, device="cuda"):
@@ -106,14 +102,6 @@ class HipR3D18:
         """a torchvision r3d_18, or the nn.Sequential of its children without fc"""
         dev = device or next(module.parameters()).device
         return cls(module.state_dict(), device=dev if torch.device(dev).type == "cuda" else "cuda")
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.load().lavie_r3d_destroy(h)
-            except Exception:
-                pass
 
     @torch.no_grad()
     def __call__(self, pixel_values, layout="ncthw"):

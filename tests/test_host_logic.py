@@ -151,6 +151,39 @@ def test_engine_param_inventory_matches_spec():
         lib.lavie_unet_destroy(handle)
 
 
+def test_engine_param_inventory_is_the_recorded_one():
+    """lavie_unet_param_info for the base, interpolation and VSR variants: order, names and element counts equal the lists recorded in
+    tests/golden/unet_param_inventory.json (the `...rotary_emb.freqs` keys, which nothing reads, included)."""
+    import hashlib
+    import json
+    lib = _lib.load()
+    with open(os.path.join(ROOT, "tests", "golden", "unet_param_inventory.json")) as f:
+        recorded = json.load(f)
+    for tag in ("base", "interpolation", "vsr"):
+        cfg = _lib.UNetConfigC()
+        cfg.struct_size = ctypes.sizeof(_lib.UNetConfigC)
+        for key, value in recorded[tag]["config"].items():
+            if isinstance(value, list):
+                for i, v in enumerate(value):
+                    getattr(cfg, key)[i] = v
+            else:
+                setattr(cfg, key, value)
+        cfg.num_levels = len(recorded[tag]["config"]["block_out_channels"])
+        handle = ctypes.c_void_p()
+        assert lib.lavie_unet_create(ctypes.byref(cfg), ctypes.byref(handle)) == 0, tag
+        try:
+            lines = []
+            for i in range(lib.lavie_unet_num_params(handle)):
+                name, numel = ctypes.c_char_p(), ctypes.c_longlong()
+                assert lib.lavie_unet_param_info(handle, i, ctypes.byref(name), ctypes.byref(numel)) == 0
+                lines.append(f"{name.value.decode()} {numel.value}\n")
+        finally:
+            lib.lavie_unet_destroy(handle)
+        assert len(lines) == recorded[tag]["count"], tag
+        assert any(line.startswith("mid_block.attentions.0.") and "rotary_emb.freqs " in line for line in lines) == (tag != "interpolation")
+        assert hashlib.sha256("".join(lines).encode()).hexdigest() == recorded[tag]["sha256"], tag
+
+
 def test_facade_surface_and_errors():
     from lavie_amd.unet import UNet3DConditionModel
     net = UNet3DConditionModel(sample_size=8, block_out_channels=(256, 512), cross_attention_dim=128,
