@@ -1045,6 +1045,42 @@ int lavie_window_step_seeded(const lavie_window_step_args* args, const lavie_noi
  * lavie_last_error(); touches no device and launches nothing. */
 int lavie_debug_noise_key_refusal(int combine);
 
+/* ---- The denoising objective evaluated forward (additive in ABI 8; csrc/denoise_loss.hip): the noised model input
+ * in front of the UNet and the mean squared error against the regenerated target behind it, with the noise of `key` made in
+ * registers on both sides.  For latent p of key->count, element e of key->per, in fp32 with every rounding point fixed:
+ *   n = the normal of (seeds[p], draw, e); with offset_hw != 0: n = fma(offset_coef, m, n), m = the normal of element e / offset_hw
+ *   of (seeds[p], offset_draw), one value per plane of offset_hw elements (a [B, C, F, 1, 1] term);
+ *   a = a_host[p] = sqrt(abar_t), s = s_host[p] = sqrt(1 - abar_t) of the latent's timestep, computed by the caller. */
+typedef struct lavie_denoise_args {
+    int struct_size;                 /* sizeof(lavie_denoise_args) as the caller declared it; any other value is refused */
+    int x0_dtype;                    /* 0 = fp16, 1 = fp32 */
+    const void* x0;                  /* [count, per] (device): the clean latents, already scaled by the VAE factor */
+    const float* a_host;             /* [count], read before the call returns */
+    const float* s_host;             /* [count], read before the call returns */
+    float offset_coef;               /* read when offset_hw != 0 */
+    unsigned long long offset_draw;
+    long long offset_hw;             /* 0: no offset noise; otherwise it must divide key->per */
+} lavie_denoise_args;
+#define LAVIE_LOSS_EPSILON 0
+#define LAVIE_LOSS_V_PREDICTION 1
+#define LAVIE_LOSS_SAMPLE 2
+/* model_in fp16 [count, per] = fp16 of fma(s, n, a x0), rounded once; with s == 0 fp16 of a x0 and no noise is made.  Eight elements per
+ * lane when per % 8 == 0 and x0 and model_in are 16-byte aligned, otherwise one: the same bits.  Refused by name, nothing launched: a
+ * null args, key, x0, a_host, s_host or model_in, a struct of another size, x0_dtype outside 0..1, count outside
+ * 1..LAVIE_NOISE_MAX_SEEDS, per < 1, offset_hw < 0 or not dividing per, a level that is not finite, a tensor that is not aligned to its
+ * element.  One launch, no allocation, capturable.  A latent's bits do not depend on count or on its position. */
+int lavie_noisy_latents_seeded(const lavie_denoise_args* args, const lavie_noise_key* key, void* model_in, void* stream);
+/* fp32 elements of the workspace of the entry below for P latents of `per` elements; -1 for P < 1 or per outside 1..2^40. */
+long long lavie_denoising_loss_workspace_floats(int P, long long per);
+/* out fp32 [count] (device) = the mean over the latent of the squared difference of pred fp16 [count, per] and the target: n
+ * (LAVIE_LOSS_EPSILON), fma(a, n, -(s x0)) (LAVIE_LOSS_V_PREDICTION) or x0 (LAVIE_LOSS_SAMPLE), n having the bits the entry above
+ * used.  Fixed order of additions: fp32 sums of depth 17 over chunks of 2048 elements into `workspace`, then a second launch adds a
+ * latent's chunks in index order in double and divides by per.  No atomics: two calls agree bit for bit, and a latent's value does not
+ * depend on count or on its position.  Refusals as above, and: a null pred, out or workspace, workspace_floats below the query's
+ * answer, kind outside 0..2.  Two launches, capturable. */
+int lavie_denoising_loss_f32(const lavie_denoise_args* args, const lavie_noise_key* key, const void* pred, int kind, float* out,
+                             float* workspace, long long workspace_floats, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * CLIP image processor, feature heads and CLIPSIM (additive in ABI 8): pixels and token ids in, context or score out
  * ---------------------------------------------------------------------------------------------- */

@@ -53,6 +53,11 @@ class NoiseKeyC(C.Structure):         # lavie_noise_key
     _fields_ = [("struct_size", c_int), ("count", c_int), ("seeds_host", C.POINTER(c_ull)), ("per", c_ll), ("draw", c_ull)]
 
 
+class DenoiseArgsC(C.Structure):        # lavie_denoise_args
+    _fields_ = [("struct_size", c_int), ("x0_dtype", c_int), ("x0", c_void_p), ("a_host", C.POINTER(c_float)), ("s_host", C.POINTER(c_float)),
+                ("offset_coef", c_float), ("offset_draw", c_ull), ("offset_hw", c_ll)]
+
+
 class GuidanceTableArgsC(C.Structure):   # lavie_guidance_table_args
     _fields_ = [("struct_size", c_int), ("W", c_int), ("P", c_int), ("per", c_ll), ("eps_host", C.POINTER(c_void_p)),
                 ("guidance_dev", c_float_p), ("guidance", c_float), ("rescale", c_float), ("partials", c_float_p),
@@ -319,6 +324,9 @@ SIGNATURES = {
                                                c_float, c_void_p, C.POINTER(NoiseKeyC)]),
     "lavie_window_step_seeded": (c_int, [C.POINTER(WindowStepArgsC), C.POINTER(NoiseKeyC), c_void_p]),
     "lavie_debug_noise_key_refusal": (c_int, [c_int]),
+    "lavie_noisy_latents_seeded": (c_int, [C.POINTER(DenoiseArgsC), C.POINTER(NoiseKeyC), c_void_p, c_void_p]),
+    "lavie_denoising_loss_workspace_floats": (c_ll, [c_int, c_ll]),
+    "lavie_denoising_loss_f32": (c_int, [C.POINTER(DenoiseArgsC), C.POINTER(NoiseKeyC), c_void_p, c_int, c_float_p, c_float_p, c_ll, c_void_p]),
     "lavie_clip_resample_table_host": (c_int, [c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
     "lavie_clip_preprocess_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int, c_int]),
     "lavie_clip_preprocess_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_ll, c_ll, c_void_p, c_int, C.POINTER(ClipPreprocessConfigC), c_void_p,

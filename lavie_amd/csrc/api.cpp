@@ -1013,6 +1013,69 @@ int lavie_debug_noise_key_refusal(int combine) {
     return 0;
 }
 
+// ---- The denoising objective evaluated forward (denoise_loss.hip): the noised model input and the loss against the regenerated target.
+static int fill_denoise(const char* who, const lavie_denoise_args* a, const lavie_noise_key* k, NoiseKey* key, NoiseLevels* lv,
+                        OffsetNoise* off) {
+    LAVIE_CHECK(a, "%s: args is null", who);
+    LAVIE_CHECK(a->struct_size == (int)sizeof(lavie_denoise_args),
+                "%s: args->struct_size=%d but this library's lavie_denoise_args has %d bytes: the binding's struct layout is out of date", who,
+                a->struct_size, (int)sizeof(lavie_denoise_args));
+    if (int rc = fill_key(who, k, key)) return rc;
+    LAVIE_CHECK(a->x0_dtype == 0 || a->x0_dtype == 1, "%s: x0_dtype=%d outside 0..1", who, a->x0_dtype);
+    LAVIE_CHECK(a->x0, "%s: x0 is null", who);
+    LAVIE_CHECK(((uintptr_t)a->x0 & (a->x0_dtype ? 3 : 1)) == 0, "%s: x0 at %p is not aligned to its element", who, a->x0);
+    LAVIE_CHECK(a->a_host && a->s_host, "%s: %s is null", who, a->a_host ? "s_host" : "a_host");
+    LAVIE_CHECK(a->offset_hw >= 0 && (a->offset_hw == 0 || key->per % a->offset_hw == 0), "%s: offset_hw=%lld must be 0 or divide per=%lld",
+                who, a->offset_hw, key->per);
+    *lv = NoiseLevels{};
+    for (int p = 0; p < key->count; ++p) {
+        LAVIE_CHECK(__builtin_isfinite(a->a_host[p]) && __builtin_isfinite(a->s_host[p]), "%s: level %d (a=%g, s=%g) is not finite", who, p,
+                    (double)a->a_host[p], (double)a->s_host[p]);
+        lv->a[p] = a->a_host[p];
+        lv->s[p] = a->s_host[p];
+    }
+    *off = OffsetNoise{0.f, 0ull, 0ll};
+    if (a->offset_hw != 0) {
+        LAVIE_CHECK(__builtin_isfinite(a->offset_coef), "%s: offset_coef (%g) is not finite", who, (double)a->offset_coef);
+        *off = OffsetNoise{a->offset_coef, a->offset_draw, a->offset_hw};
+    }
+    return 0;
+}
+
+int lavie_noisy_latents_seeded(const lavie_denoise_args* a, const lavie_noise_key* k, void* model_in, void* stream) {
+    const char* who = "noisy_latents_seeded";
+    NoiseKey key;
+    NoiseLevels lv;
+    OffsetNoise off;
+    if (int rc = fill_denoise(who, a, k, &key, &lv, &off)) return rc;
+    LAVIE_CHECK(model_in, "%s: model_in is null", who);
+    LAVIE_CHECK(((uintptr_t)model_in & 1) == 0, "%s: model_in at %p is not 2-byte aligned", who, model_in);
+    return launch_noisy_latents(a->x0, a->x0_dtype == 1, static_cast<half_t*>(model_in), key, lv, off, S(stream));
+}
+
+long long lavie_denoising_loss_workspace_floats(int P, long long per) {
+    if (P < 1 || per < 1 || per > (1ll << 40)) return -1;
+    return (long long)P * denoising_loss_chunks(per);
+}
+
+int lavie_denoising_loss_f32(const lavie_denoise_args* a, const lavie_noise_key* k, const void* pred, int kind, float* out, float* workspace,
+                             long long workspace_floats, void* stream) {
+    const char* who = "denoising_loss";
+    NoiseKey key;
+    NoiseLevels lv;
+    OffsetNoise off;
+    if (int rc = fill_denoise(who, a, k, &key, &lv, &off)) return rc;
+    LAVIE_CHECK(pred, "%s: pred is null", who);
+    LAVIE_CHECK(((uintptr_t)pred & 1) == 0, "%s: pred at %p is not 2-byte aligned", who, pred);
+    LAVIE_CHECK(kind >= 0 && kind <= 2, "%s: kind=%d outside 0..2", who, kind);
+    LAVIE_CHECK(out, "%s: out is null", who);
+    LAVIE_CHECK(workspace, "%s: workspace is null", who);
+    LAVIE_CHECK((((uintptr_t)out | (uintptr_t)workspace) & 3) == 0, "%s: out / workspace is not 4-byte aligned", who);
+    const long long need = lavie_denoising_loss_workspace_floats(key.count, key.per);
+    LAVIE_CHECK(workspace_floats >= need, "%s: workspace_floats=%lld, P chunks = %lld needed", who, workspace_floats, need);
+    return launch_denoising_loss(static_cast<const half_t*>(pred), a->x0, a->x0_dtype == 1, key, lv, off, kind, workspace, out, S(stream));
+}
+
 // ---- Guidance from a per-latent table (sampler_guidance.hip): the table itself, then the five steps that read it.
 long long lavie_guidance_partials_floats(int latents, long long per) {
     if (latents < 1 || per < 2 || per > (1ll << 40)) return -1;

@@ -151,6 +151,20 @@ int launch_step_seeded(const StepArgs& a, hipStream_t stream);       // sampler_
 // (philox.h); key.count = P <= kNoiseMaxSeeds, key.per = per.  The eight-element form runs when first % 4 == 0, per % 8 == 0 and out
 // is 16-byte aligned, else every lane makes one element: the same bits.
 int launch_philox_normal(float* out, const NoiseKey& key, long long first, hipStream_t stream);
+// ---- denoise_loss.hip : the ends of the denoising objective evaluated forward.  lv.a[p] = sqrt(abar_t), lv.s[p] = sqrt(1 - abar_t) of
+// latent p; off.hw != 0: offset noise, n += coef m with m the normal of element e / hw of (key.seed[p], off.draw) (hw divides key.per).
+//   launch_noisy_latents: model_in fp16 [P, per] = once-rounded fma(s, n, a x0); x0 [P, per] fp32 or fp16.
+//   launch_denoising_loss: out fp32 [P] = mean over the latent of (pred - target)^2, target by `kind`; partials holds
+//   key.count * denoising_loss_chunks(key.per) floats.  Two launches, fixed order of additions.
+struct NoiseLevels { float a[kNoiseMaxSeeds]; float s[kNoiseMaxSeeds]; };
+struct OffsetNoise { float coef; unsigned long long draw; long long hw; };
+constexpr int kLossEpsilon = 0, kLossVPrediction = 1, kLossSample = 2;
+constexpr int kLossChunk = 2048;
+int64_t denoising_loss_chunks(int64_t per);
+int launch_noisy_latents(const void* x0, bool x0_f32, half_t* model_in, const NoiseKey& key, const NoiseLevels& lv, const OffsetNoise& off,
+                         hipStream_t stream);
+int launch_denoising_loss(const half_t* pred, const void* x0, bool x0_f32, const NoiseKey& key, const NoiseLevels& lv, const OffsetNoise& off,
+                          int kind, float* partials, float* out, hipStream_t stream);
 // ---- clip_preprocess.hip : the two passes of Pillow's 8-bit bicubic resampling over the rows and columns a centre crop keeps, and
 // the normalisation by table.  The tables (device int32: first tap, tap count, [crop, ksize] coefficients per kept output; lut = 768
 // fp32) are made by clip_engine.cpp.  mid: uint8 [B, rows, crop, 3], source rows row0 .. row0 + rows - 1; ymin is relative to row0.

@@ -10,6 +10,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .noise import NoiseKey
 
 
 def _stream():
@@ -1078,6 +1079,85 @@ def window_step_seeded(eps, x, key, model_in, starts, profile, guidance, coeffs,
     a, _keep = _window_args(eps, x, None, model_in, starts, profile, guidance, coeffs, next_input_scale, False)
     k, _seeds = _noise_key("window_step_seeded", key, x.shape[0], x.numel() // x.shape[0])
     _lib.check(_lib.load().lavie_window_step_seeded(ctypes.byref(a), ctypes.byref(k), _stream()), "lavie_window_step_seeded")
+
+
+# ------------------------------------------------------------------ the denoising objective evaluated forward (csrc/denoise_loss.hip)
+LOSS_KINDS = {"epsilon": 0, "v_prediction": 1, "sample": 2}
+
+
+def _denoise_args(who, x0, seeds, draw, levels, offset):
+    """The checked (lavie_denoise_args, lavie_noise_key, P, per) of `noisy_latents` / `denoising_loss`, and the host arrays they borrow.
+    levels: P pairs (a, s); offset: None or (coef, draw_offset, hw)."""
+    if not (isinstance(x0, torch.Tensor) and x0.is_cuda and x0.dtype in (torch.float16, torch.float32) and x0.dim() >= 2):
+        raise ValueError(f"{who}: x0 must be an fp16 or fp32 device tensor [P, ...]")
+    if not x0.is_contiguous():
+        raise ValueError(f"{who}: x0 must be contiguous")
+    p = x0.shape[0]
+    per = x0.numel() // p if p else 0
+    if p < 1 or per < 1:
+        raise ValueError(f"{who}: x0 {tuple(x0.shape)} holds no element")
+    levels = [(float(a), float(s)) for a, s in levels]
+    if len(levels) != p:
+        raise ValueError(f"{who}: got {len(levels)} noise levels for {p} latents")
+    key = NoiseKey([int(s) & _U64 for s in seeds], int(draw))
+    k, seeds_c = _noise_key(who, key, p, per)
+    a = _lib.DenoiseArgsC()
+    a.struct_size = ctypes.sizeof(_lib.DenoiseArgsC)
+    a.x0_dtype, a.x0 = int(x0.dtype == torch.float32), x0.data_ptr()
+    a_c, s_c = (ctypes.c_float * p)(*[l[0] for l in levels]), (ctypes.c_float * p)(*[l[1] for l in levels])
+    a.a_host, a.s_host = a_c, s_c
+    if offset is not None:
+        coef, draw_offset, hw = float(offset[0]), int(offset[1]) & _U64, int(offset[2])
+        if hw < 1 or per % hw != 0:
+            raise ValueError(f"{who}: offset hw={hw} must divide per={per}")
+        if coef != 0.0:                            # coef == 0 adds nothing: the call without offset
+            a.offset_coef, a.offset_draw, a.offset_hw = coef, draw_offset, hw
+    return a, k, p, per, (seeds_c, a_c, s_c)
+
+
+def noisy_latents(x0, seeds, draw, levels, offset=None, out=None):
+    """The model input of the denoising objective (lavie_noisy_latents_seeded): out fp16, x0's shape [P, ...] = fp16(fma(s_p, n, a_p x0)),
+    rounded once, with n the normal of (seeds[p], draw, element) made in the kernel (the bits of `philox_normal`) and levels[p] = (a_p,
+    s_p) = (sqrt(abar_t), sqrt(1 - abar_t)).  offset = (coef, draw_offset, hw): n += coef m, m the normal of element e // hw of (seeds[p],
+    draw_offset): one value per plane of hw elements.  x0 fp16 or fp32, at most NOISE_MAX_SEEDS latents.  No noise tensor exists."""
+    a, k, p, per, _keep = _denoise_args("noisy_latents", x0, seeds, draw, levels, offset)
+    if out is None:
+        out = torch.empty(x0.shape, dtype=torch.float16, device=x0.device)
+    if not (out.is_cuda and out.device == x0.device and out.dtype == torch.float16 and out.numel() == p * per and out.is_contiguous()):
+        raise ValueError(f"noisy_latents: out must be a contiguous fp16 tensor of {p * per} elements on {x0.device}")
+    _lib.check(_lib.load().lavie_noisy_latents_seeded(ctypes.byref(a), ctypes.byref(k), _p(out), _stream()), "lavie_noisy_latents_seeded")
+    return out
+
+
+def denoising_loss_workspace_floats(latents: int, per: int) -> int:
+    """fp32 elements of the workspace `denoising_loss` needs for `latents` latents of `per` elements each."""
+    n = _lib.load().lavie_denoising_loss_workspace_floats(int(latents), int(per))
+    if n < 0:
+        raise ValueError(f"denoising_loss_workspace_floats: latents={latents} per={per} out of range")
+    return n
+
+
+def denoising_loss(pred, x0, seeds, draw, levels, kind, offset=None, workspace=None, out=None):
+    """fp32 [P]: the mean over latent p of (pred - target)^2 (lavie_denoising_loss_f32).  pred fp16 of x0's element count; target = n
+    (`kind` "epsilon"), a_p n - s_p x0 ("v_prediction") or x0 ("sample"), with n regenerated in the kernel from (seeds, draw, offset): the
+    bits `noisy_latents` used.  Sums in a fixed order: two calls agree bit for bit and a latent's value does not depend on P or on its
+    position.  workspace: fp32 device tensor of at least denoising_loss_workspace_floats(P, per) elements (allocated when None)."""
+    if kind not in LOSS_KINDS:
+        raise ValueError(f"denoising_loss: kind {kind!r} is not one of {sorted(LOSS_KINDS)}")
+    a, k, p, per, _keep = _denoise_args("denoising_loss", x0, seeds, draw, levels, offset)
+    if not (isinstance(pred, torch.Tensor) and pred.is_cuda and pred.device == x0.device and pred.dtype == torch.float16
+            and pred.numel() == p * per and pred.is_contiguous()):
+        raise ValueError(f"denoising_loss: pred must be a contiguous fp16 tensor of {p * per} elements on {x0.device}")
+    need = denoising_loss_workspace_floats(p, per)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=x0.device)
+    _chk32(workspace)
+    if workspace.numel() < need or workspace.device != x0.device:
+        raise ValueError(f"denoising_loss: workspace has {workspace.numel()} elements, {need} needed")
+    out = _out(out, (p,), torch.float32, x0.device, "denoising_loss: out")
+    _lib.check(_lib.load().lavie_denoising_loss_f32(ctypes.byref(a), ctypes.byref(k), _p(pred), LOSS_KINDS[kind], _p(out), _p(workspace),
+                                                    workspace.numel(), _stream()), "lavie_denoising_loss_f32")
+    return out
 
 
 def _window_args(eps, x, aux, model_in, starts, profile, guidance, coeffs, next_input_scale, multistep):

@@ -546,6 +546,45 @@ class VideoGenPipeline:
         lat = torch.cat([self.vae.encode(frames[i:i + 8]).latent_dist.mode() for i in range(0, b * f, 8)], dim=0) * 0.18215
         return lat.reshape(b, f, *lat.shape[1:]).permute(0, 2, 1, 3, 4).float().contiguous()
 
+    # keywords of `__call__` that only mean something in a sampling run: `denoising_loss` refuses them by name
+    SAMPLING_ONLY = {"window_length": "frame windows", "window_stride": "frame windows", "window_weights": "frame windows",
+                     "known_latents": "known latents", "known_mask": "known latents", "strength": "known latents",
+                     "pag_scale": "perturbed-attention guidance", "pag_adaptive_scale": "perturbed-attention guidance",
+                     "pag_applied_layers": "perturbed-attention guidance", "cache_interval": "the layer cache",
+                     "cache_depth": "the layer cache", "free_init": "FreeInit"}
+
+    @torch.no_grad()
+    def denoising_loss(self, video: Optional[torch.Tensor] = None, latents: Optional[torch.Tensor] = None, prompt=None,
+                       prompt_embeds: Optional[torch.Tensor] = None, image_tensor=None, image_embeds: Optional[torch.Tensor] = None,
+                       timesteps=None, seed=0, snr_gamma=None, noise_offset: float = 0.0, prediction_type=None, **sampling_only):
+        """The training objective evaluated forward on held-out clips (lavie_amd.denoising_loss.DenoisingLoss.evaluate): the clips are
+        encoded as `encode_video` does (or `latents` [P, 4, F, h, w], already scaled, are taken), the context comes from the paths
+        `__call__` uses (prompt or prompt_embeds, widened by the mapper when one is attached and an image is given; one prompt serves
+        every clip), noise of `seed` (an int, a list with one per clip, or a PhiloxGenerator) is added at `timesteps` (one int, or one
+        per clip) and the UNet's prediction is scored against the target.  The active LoRA adapters and scales apply: the engine serves
+        them merged.  No guidance is involved.  Options of a sampling run (frame windows, known latents, PAG, the layer cache,
+        FreeInit) are refused by name."""
+        from .denoising_loss import DenoisingLoss
+        from .noise import PhiloxGenerator
+        for name in sampling_only:
+            if name not in self.SAMPLING_ONLY:
+                raise TypeError(f"denoising_loss() got an unexpected keyword argument {name!r}")
+            raise ValueError(f"denoising_loss: `{name}` ({self.SAMPLING_ONLY[name]}) only means something in a sampling run")
+        if (video is None) == (latents is None):
+            raise ValueError("denoising_loss: pass exactly one of `video` and `latents`")
+        if (prompt is None) == (prompt_embeds is None):
+            raise ValueError("denoising_loss: pass exactly one of `prompt` and `prompt_embeds`")
+        if timesteps is None:
+            raise ValueError("denoising_loss: `timesteps` is required (one int, or one per clip)")
+        device = self.device
+        x0 = self.encode_video(video) if video is not None else latents
+        x0 = x0.to(device=device).contiguous()
+        image_features = self._image_features(image_tensor, image_embeds, device) if self.mapper is not None else None
+        ctx = self._encode_prompt(prompt, device, 1, False, None, prompt_embeds, None, image_features).to(torch.float16).contiguous()
+        generator = seed if isinstance(seed, PhiloxGenerator) else PhiloxGenerator(seed)
+        scorer = DenoisingLoss(self.unet, self.scheduler, snr_gamma=snr_gamma, noise_offset=noise_offset, prediction_type=prediction_type)
+        return scorer.evaluate(x0, ctx, timesteps, generator)
+
     @contextlib.contextmanager
     def _lora_scale(self, scale):
         """diffusers' LoRA strength (`cross_attention_kwargs["scale"]`) for one call only, restored also on an exception; None
