@@ -543,6 +543,42 @@ int lavie_cfg_multistep_step_known_scaled(const void* eps2, float* x, float* x0_
                                           void* stream, const lavie_known_region* region);
 int lavie_window_step_scaled(const lavie_window_step_args* args, const float* table, void* stream);
 
+/* UniPC (Zhao et al., arXiv:2302.04867; lavie_amd/scheduling_unipc_multistep.py; csrc/sampler_unipc.hip), additive in
+ * ABI 8: one launch per denoising step runs guidance, the x0 prediction, the corrector that recomputes the sample the model was
+ * just evaluated at, the predictor to the next timestep, the history writes and the next fp16 model input.  The corrector reuses
+ * the model output the predictor needs anyway, so it costs no UNet forward.  Per element, fp32, contraction off, in this order:
+ *   eps = eps_u + guidance (eps_c - eps_u)          (cfg entries; _scaled: (g, f) = table[i / per] and eps = f eps, as above)
+ *   m   = k_x x - k_eps eps                         one fma on the rounded product k_x x
+ *   xc  = corr != 0 ? c_l x_last + c_0 m + c_1 m1 + c_2 m2 : x        the rounded product c_l x_last, then one fma per term in
+ *                                                                     this order; a term whose coefficient is 0 is skipped
+ *   x'  = p_x xc + p_0 m + p_1 m1                   the sum of the two rounded products, then one fma for p_1 m1 unless p_1 == 0
+ *   x_last <- xc;  m2 <- m1;  m1 <- m;  x <- x';  model_in <- fp16(fp32(x' next_input_scale))    ([x' | x'] for the cfg entries)
+ * x_last (the previous corrected sample), m1, m2 (the two previous x0 predictions): fp32 device buffers of the caller, n elements
+ * each, updated in place.  A buffer is read only when a coefficient that multiplies it is in force and non-zero (x_last: corr and
+ * c_l; m1: corr and c_1, or p_1; m2: corr and c_2); otherwise it is written and NEVER read, so all three may be uninitialised at
+ * the first step (corr = 0, p_1 = 0).  When m1 is not read, m2 receives m (no later step can need that value).
+ * With corr = 0 and p_1 = 0, x and model_in have the bits of lavie_multistep_step(k_x, k_eps, c_x0 = p_0, c_xt = p_x, c_prev = 0).
+ * No noise operand, no atomics, no host synchronisation, no allocation: bit-reproducible and safe inside a stream capture.
+ * Checked on the host before any HIP call, a refused call launches nothing and names its argument: coeffs.struct_size; non-null
+ * eps / x / x_last / m1 / m2 / model_in (and table); n >= 1; finite scalars; x, x_last, m1, m2 pairwise disjoint; _scaled: per >=
+ * 2 and n == P per for a whole P in 1..65535; with n % 8 == 0 (_scaled: per % 8 == 0; eight elements per lane, 16-byte accesses;
+ * otherwise one element per lane, same arithmetic) every tensor 16-byte aligned. */
+typedef struct lavie_unipc_coeffs {
+    int struct_size;                  /* sizeof this struct as the CALLER declared it; any other value is refused */
+    int corr;                         /* != 0: the corrector runs (every step but a run's first) */
+    float guidance;                   /* lavie_cfg_unipc_step only; finite everywhere */
+    float k_x, k_eps;
+    float c_l, c_0, c_1, c_2;         /* corrector: x_last, m, m1, m2 */
+    float p_x, p_0, p_1;              /* predictor: xc, m, m1 */
+    float next_input_scale;
+} lavie_unipc_coeffs;
+int lavie_unipc_step(const void* eps, float* x, float* x_last, float* m1, float* m2, void* model_in, long long n,
+                     lavie_unipc_coeffs coeffs, void* stream);
+int lavie_cfg_unipc_step(const void* eps2, float* x, float* x_last, float* m1, float* m2, void* model_in2, long long n,
+                         lavie_unipc_coeffs coeffs, void* stream);
+int lavie_cfg_unipc_step_scaled(const void* eps2, float* x, float* x_last, float* m1, float* m2, void* model_in2, long long n,
+                                const float* table, long long per, lavie_unipc_coeffs coeffs, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Perturbed-attention guidance (PAG: Ahn et al., "Self-Rectifying Diffusion Sampling with Perturbed-Attention Guidance"; diffusers'
  * AnimateDiffPAGPipeline) inside the fused step (sampler_pag.hip; additive in ABI 8).  The four steps carry the arguments of their

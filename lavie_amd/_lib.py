@@ -49,6 +49,12 @@ class WindowStepArgsC(C.Structure):   # lavie_window_step_args
                 ("next_input_scale", c_float)]
 
 
+class UnipcCoeffsC(C.Structure):      # lavie_unipc_coeffs (passed by value)
+    _fields_ = [("struct_size", c_int), ("corr", c_int), ("guidance", c_float), ("k_x", c_float), ("k_eps", c_float), ("c_l", c_float),
+                ("c_0", c_float), ("c_1", c_float), ("c_2", c_float), ("p_x", c_float), ("p_0", c_float), ("p_1", c_float),
+                ("next_input_scale", c_float)]
+
+
 class NoiseKeyC(C.Structure):         # lavie_noise_key
     _fields_ = [("struct_size", c_int), ("count", c_int), ("seeds_host", C.POINTER(c_ull)), ("per", c_ll), ("draw", c_ull)]
 
@@ -221,6 +227,10 @@ SIGNATURES = {
                                             c_float, c_float, c_float, c_void_p]),
     "lavie_pag_sampler_step": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float,
                                         c_float, c_float, c_void_p]),
+    "lavie_unipc_step": (c_int, [c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_void_p, c_ll, UnipcCoeffsC, c_void_p]),
+    "lavie_cfg_unipc_step": (c_int, [c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_void_p, c_ll, UnipcCoeffsC, c_void_p]),
+    "lavie_cfg_unipc_step_scaled": (c_int, [c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, c_void_p, c_ll, c_float_p, c_ll,
+                                            UnipcCoeffsC, c_void_p]),
     "lavie_cfg_pag_multistep_step": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float,
                                               c_float, c_float, c_float, c_void_p]),
     "lavie_pag_multistep_step": (c_int, [c_void_p, c_float_p, c_float_p, c_void_p, c_ll, c_float, c_float, c_float, c_float, c_float,

@@ -54,8 +54,9 @@ def text_to_video_cascade(base_pipe, interp_unet, interp_diffusion, vsr_pipe, va
     """Returns (base_latents, interp_latents, vsr_latents, frames or None).  Text embeddings are passed per stage (the base
     and interpolation stages use SD-1.4's CLIP, 768 wide; the VSR stage the x4-upscaler's, 1024 wide).
     `base_scheduler` / `vsr_scheduler` replace the two diffusers-style stages' schedulers for this call (for instance a
-    DPMSolverMultistepScheduler with fewer `base_steps` / `vsr_steps`); the pipelines get their own back afterwards.  The
-    interpolation stage samples with its SpacedDiffusion object and has no such switch.
+    DPMSolverMultistepScheduler or a UniPCMultistepScheduler with fewer `base_steps` / `vsr_steps`); the pipelines get their own back
+    afterwards.  The interpolation stage samples with its SpacedDiffusion object and has no such switch.  A UniPCMultistepScheduler
+    is not combined with `vsr_overlap` > 0 (frame windows) or `base_free_init`: the stage's call refuses by name.
     `vsr_overlap` > 0: the VSR stage samples the 61 frames as ONE run over 8-frame windows sharing that many frames with their
     neighbours (`upscale_in_chunks(overlap=)`) instead of independent chunks; 0 = the reference's chunks.
     `base_guidance_rescale` / `vsr_guidance_rescale`: the `guidance_rescale` of the two diffusers-style stages (0 = off).  The

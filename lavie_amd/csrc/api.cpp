@@ -1142,6 +1142,57 @@ int lavie_cfg_multistep_step_known_scaled(const void* eps2, float* x, float* x0_
                                                                        c_xt, c_prev, next_input_scale, table), region, stream);
 }
 
+// ---- the UniPC step (sampler_unipc.hip): every refusal on the host, before any HIP call, naming its argument
+static int run_unipc(const char* who, bool cfg, const void* eps, float* x, float* x_last, float* m1, float* m2, void* model_in,
+                     long long n, const float* table, long long per, const lavie_unipc_coeffs& k, void* stream) {
+    LAVIE_CHECK(k.struct_size == (int)sizeof(lavie_unipc_coeffs),
+                "%s: coeffs.struct_size=%d but this library's lavie_unipc_coeffs has %d bytes: the binding's struct layout is out of "
+                "date", who, k.struct_size, (int)sizeof(lavie_unipc_coeffs));
+    const void* const t[6] = {eps, x, x_last, m1, m2, model_in};
+    const char* const names[6] = {"eps", "x", "x_last", "m1", "m2", "model_in"};
+    for (int i = 0; i < 6; ++i) LAVIE_CHECK(t[i], "%s: null argument: %s is null", who, names[i]);
+    LAVIE_CHECK(n >= 1 && n <= (1ll << 40), "%s: n=%lld must be >= 1", who, n);
+    const float s[11] = {k.guidance, k.k_x, k.k_eps, k.c_l, k.c_0, k.c_1, k.c_2, k.p_x, k.p_0, k.p_1, k.next_input_scale};
+    const char* const snames[11] = {"guidance", "k_x", "k_eps", "c_l", "c_0", "c_1", "c_2", "p_x", "p_0", "p_1", "next_input_scale"};
+    for (int i = 0; i < 11; ++i) LAVIE_CHECK(__builtin_isfinite(s[i]), "%s: %s (%g) is not finite", who, snames[i], (double)s[i]);
+    if (table) {
+        LAVIE_CHECK(per >= 2 && per <= (1ll << 40), "%s: per=%lld must be >= 2", who, per);
+        LAVIE_CHECK(n % per == 0, "%s: n=%lld is not a whole number of latents of per=%lld", who, n, per);
+        LAVIE_CHECK(n / per <= 65535, "%s: n / per = %lld latents, at most 65535 fit one launch", who, n / per);
+    }
+    // the four fp32 tensors are each read and rewritten at the same element only, so none may share a byte with another
+    for (int i = 1; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j) {
+            const uintptr_t a = (uintptr_t)t[i], b = (uintptr_t)t[j], bytes = (uintptr_t)n * 4;
+            LAVIE_CHECK(a + bytes <= b || b + bytes <= a, "%s: %s and %s overlap", who, names[i], names[j]);
+        }
+    if ((table ? per : n) % 8 == 0)          // the eight-elements-per-lane form: 16-byte accesses
+        for (int i = 0; i < 6; ++i)
+            if (int rc = check_aligned(who, names[i], t[i])) return rc;
+    UnipcArgs a{};
+    a.cfg = cfg; a.eps = H(eps); a.x = x; a.x_last = x_last; a.m1 = m1; a.m2 = m2; a.model_in = H(model_in); a.n = n;
+    a.c = UnipcCoef{table ? 1.0f : k.guidance, k.k_x, k.k_eps, k.c_l, k.c_0, k.c_1, k.c_2, k.p_x, k.p_0, k.p_1, k.next_input_scale,
+                    k.corr != 0};
+    a.table = table; a.per = per;
+    return launch_unipc_step(a, S(stream));
+}
+
+int lavie_unipc_step(const void* eps, float* x, float* x_last, float* m1, float* m2, void* model_in, long long n,
+                     lavie_unipc_coeffs coeffs, void* stream) {
+    return run_unipc("unipc_step", false, eps, x, x_last, m1, m2, model_in, n, nullptr, 0, coeffs, stream);
+}
+
+int lavie_cfg_unipc_step(const void* eps2, float* x, float* x_last, float* m1, float* m2, void* model_in2, long long n,
+                         lavie_unipc_coeffs coeffs, void* stream) {
+    return run_unipc("cfg_unipc_step", true, eps2, x, x_last, m1, m2, model_in2, n, nullptr, 0, coeffs, stream);
+}
+
+int lavie_cfg_unipc_step_scaled(const void* eps2, float* x, float* x_last, float* m1, float* m2, void* model_in2, long long n,
+                                const float* table, long long per, lavie_unipc_coeffs coeffs, void* stream) {
+    LAVIE_CHECK(table, "cfg_unipc_step_scaled: table is null");
+    return run_unipc("cfg_unipc_step_scaled", true, eps2, x, x_last, m1, m2, model_in2, n, table, per, coeffs, stream);
+}
+
 int lavie_window_step_scaled(const lavie_window_step_args* a, const float* table, void* stream) {
     const char* who = "window_step_scaled";
     LAVIE_CHECK(table, "%s: table is null", who);

@@ -1423,6 +1423,56 @@ int main(int argc, char** argv) {
         REQUIRE(lavie_multistep_step(eps, x, hist, min2, 32, 1.f, -inf, 1.f, 0.f, 0.f, 1.f, nullptr) != 0);
         REQUIRE(lavie_hostcheck_launches() == before + 3);
     }
+    {   // the UniPC step: accepted calls reach the (stubbed) launch in the eight-element form, the one-element form and the table form;
+        // every refusal comes before a HIP call and names the argument
+        alignas(16) static unsigned short eps[2 * 48], min2[2 * 48];
+        alignas(16) static float x[48], xl[48], m1[48], m2[48 + 8], table[4] = {7.5f, 1.f, 5.f, 0.9f};
+        const float nan = __builtin_nanf(""), inf = __builtin_inff();
+        auto refused = [&](int rc, const char* word) { return rc != 0 && strstr(lavie_last_error(), word) != nullptr; };
+        lavie_unipc_coeffs k{};
+        k.struct_size = (int)sizeof(k); k.corr = 1; k.guidance = 7.5f; k.k_x = 1.f; k.k_eps = 0.5f;
+        k.c_l = 0.9f; k.c_0 = 0.05f; k.c_1 = 0.04f; k.c_2 = 0.01f; k.p_x = 0.8f; k.p_0 = 0.3f; k.p_1 = -0.1f; k.next_input_scale = 1.f;
+        const long before = lavie_hostcheck_launches();
+        REQUIRE(lavie_cfg_unipc_step(eps, x, xl, m1, m2, min2, 48, k, nullptr) == 0);
+        REQUIRE(lavie_cfg_unipc_step(eps, x, xl, m1, m2, min2, 37, k, nullptr) == 0);
+        REQUIRE(lavie_unipc_step(eps + 1, x + 1, xl + 1, m1 + 1, m2 + 1, min2 + 1, 37, k, nullptr) == 0);      // one element per lane: no alignment rule
+        REQUIRE(lavie_cfg_unipc_step_scaled(eps, x, xl, m1, m2, min2, 48, table, 24, k, nullptr) == 0);
+        REQUIRE(lavie_cfg_unipc_step_scaled(eps, x, xl, m1, m2, min2, 30, table, 15, k, nullptr) == 0);
+        lavie_unipc_coeffs first = k;
+        first.corr = 0; first.p_1 = 0.f;
+        REQUIRE(lavie_unipc_step(eps, x, xl, m1, m2, min2, 48, first, nullptr) == 0);
+        REQUIRE(lavie_hostcheck_launches() == before + 6);
+        lavie_unipc_coeffs q = k;
+        q.struct_size = (int)sizeof(k) - 4;
+        REQUIRE(refused(lavie_cfg_unipc_step(eps, x, xl, m1, m2, min2, 48, q, nullptr), "struct_size"));
+        REQUIRE(refused(lavie_cfg_unipc_step(nullptr, x, xl, m1, m2, min2, 48, k, nullptr), "eps is null"));
+        REQUIRE(refused(lavie_cfg_unipc_step(eps, nullptr, xl, m1, m2, min2, 48, k, nullptr), "x is null"));
+        REQUIRE(refused(lavie_cfg_unipc_step(eps, x, nullptr, m1, m2, min2, 48, k, nullptr), "x_last is null"));
+        REQUIRE(refused(lavie_unipc_step(eps, x, xl, nullptr, m2, min2, 48, first, nullptr), "m1 is null"));
+        REQUIRE(refused(lavie_unipc_step(eps, x, xl, m1, nullptr, min2, 48, first, nullptr), "m2 is null"));
+        REQUIRE(refused(lavie_unipc_step(eps, x, xl, m1, m2, nullptr, 48, k, nullptr), "model_in is null"));
+        REQUIRE(refused(lavie_cfg_unipc_step_scaled(eps, x, xl, m1, m2, min2, 48, nullptr, 24, k, nullptr), "table is null"));
+        REQUIRE(refused(lavie_cfg_unipc_step(eps, x, xl, m1, m2, min2, 0, k, nullptr), "n=0"));
+        REQUIRE(refused(lavie_unipc_step(eps, x, xl, m1, m2, min2, -8, k, nullptr), "n=-8"));
+        float* const fields[11] = {&q.guidance, &q.k_x, &q.k_eps, &q.c_l, &q.c_0, &q.c_1, &q.c_2, &q.p_x, &q.p_0, &q.p_1, &q.next_input_scale};
+        for (int i = 0; i < 11; ++i) {
+            q = k;
+            *fields[i] = i % 3 == 0 ? nan : i % 3 == 1 ? inf : -inf;
+            REQUIRE(refused(lavie_cfg_unipc_step(eps, x, xl, m1, m2, min2, 48, q, nullptr), "not finite"));
+        }
+        REQUIRE(refused(lavie_cfg_unipc_step(eps + 1, x, xl, m1, m2, min2, 40, k, nullptr), "eps at"));
+        REQUIRE(refused(lavie_cfg_unipc_step(eps, x + 1, xl, m1, m2, min2, 40, k, nullptr), "x at"));
+        REQUIRE(refused(lavie_cfg_unipc_step(eps, x, xl + 2, m1, m2, min2, 40, k, nullptr), "x_last at"));
+        REQUIRE(refused(lavie_unipc_step(eps, x, xl, m1 + 3, m2, min2, 40, k, nullptr), "m1 at"));
+        REQUIRE(refused(lavie_unipc_step(eps, x, xl, m1, m2 + 1, min2, 40, k, nullptr), "m2 at"));
+        REQUIRE(refused(lavie_unipc_step(eps, x, xl, m1, m2, min2 + 4, 40, k, nullptr), "model_in at"));
+        REQUIRE(refused(lavie_cfg_unipc_step_scaled(eps, x, xl + 1, m1, m2, min2, 48, table, 24, k, nullptr), "16-byte"));
+        REQUIRE(refused(lavie_unipc_step(eps, x, x, m1, m2, min2, 48, k, nullptr), "x and x_last overlap"));
+        REQUIRE(refused(lavie_unipc_step(eps, x, xl, m1, m1 + 8, min2, 40, k, nullptr), "m1 and m2 overlap"));
+        REQUIRE(refused(lavie_cfg_unipc_step_scaled(eps, x, xl, m1, m2, min2, 48, table, 1, k, nullptr), "per=1"));
+        REQUIRE(refused(lavie_cfg_unipc_step_scaled(eps, x, xl, m1, m2, min2, 48, table, 36, k, nullptr), "whole number"));
+        REQUIRE(lavie_hostcheck_launches() == before + 6);
+    }
     {   // the steps around known latents: accepted calls reach the (stubbed) launch in the eight-element form (inner % 8 == 0) and the
         // one-element form; every refusal comes before a HIP call and names the argument
         alignas(16) static unsigned short eps[2 * 48], min2[2 * 48];

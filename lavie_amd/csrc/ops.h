@@ -147,6 +147,19 @@ int launch_step_known(const StepArgs& a, hipStream_t stream);        // sampler_
 int launch_step_scaled(const StepArgs& a, hipStream_t stream);       // sampler_guidance.hip
 int launch_step_pag(const StepArgs& a, hipStream_t stream);          // sampler_pag.hip
 int launch_step_seeded(const StepArgs& a, hipStream_t stream);       // sampler_noise.hip (StepArgs::key)
+// ---- sampler_unipc.hip : the UniPC predictor-corrector step (scheduling_unipc_multistep.py), a family of its own: three fp32
+// history buffers (the previous corrected sample and the two previous x0 predictions) instead of StepArgs::aux.  Per element:
+//   m = kx x - ke eps;  xc = corr ? cl x_last + c0 m + c1 m1 + c2 m2 : x;  x' = px xc + p0 m + p1 m1
+//   x_last <- xc;  m2 <- m1;  m1 <- m;  x <- x';  model_in <- fp16(x' in_scale)      (rounding points: the file's header)
+// cfg: eps / model_in are [2, n]; table != nullptr (cfg only): (g, f) per latent of `per` elements, n = P per.
+struct UnipcCoef { float guidance, kx, ke, cl, c0, c1, c2, px, p0, p1, in_scale; int corr; };
+struct UnipcArgs {
+    bool cfg;
+    const half_t* eps; float* x; float* x_last; float* m1; float* m2; half_t* model_in; int64_t n;
+    UnipcCoef c;
+    const float* table; int64_t per;
+};
+int launch_unipc_step(const UnipcArgs& a, hipStream_t stream);
 // ---- sampler_noise.hip : out [P, per] fp32, row p = the normals of elements first .. first + per - 1 of latent (key.seed[p], key.draw)
 // (philox.h); key.count = P <= kNoiseMaxSeeds, key.per = per.  The eight-element form runs when first % 4 == 0, per % 8 == 0 and out
 // is 16-byte aligned, else every lane makes one element: the same bits.

@@ -978,6 +978,47 @@ def cfg_multistep_step_known_scaled(eps2, x, x0_prev, model_in2, table, coeffs, 
           table=table, region=(known, mask, noise_known, level))
 
 
+def _unipc(entry, who, eps, x, history, model_in, coeffs, next_input_scale, guidance=1.0, table=None):
+    """The body of the three UniPC step wrappers (csrc/sampler_unipc.hip): `history` = (x_last, m1, m2), fp32 tensors of x's size
+    that the launch rewrites; `coeffs` = (k_x, k_eps, corr, c_l, c_0, c_1, c_2, p_x, p_0, p_1), UniPCMultistepScheduler.coefficients."""
+    guided = who.startswith("cfg_")
+    if history is None or len(history) != 3 or any(t is None for t in history):
+        raise ValueError(f"{who}: history must be the three fp32 tensors (x_last, m1, m2)")
+    x_last, m1, m2 = history
+    _chk16(eps, model_in)
+    _chk32(x, x_last, m1, m2, table)
+    n = x.numel()
+    m = 2 * n if guided else n
+    if eps.numel() != m or model_in.numel() != m or any(t.numel() != n for t in history):
+        raise ValueError(f"{who}: eps / model_in must have " + ("twice" if guided else "as many elements as x") +
+                         (", x_last / m1 / m2 as many elements as x" if guided else ", and so must x_last / m1 / m2"))
+    if table is not None and (tuple(table.shape) != (x.shape[0], 2) or table.device != x.device):
+        raise ValueError(f"{who}: table must be an fp32 tensor [{x.shape[0]}, 2] on {x.device}")
+    k_x, k_e, corr, c_l, c_0, c_1, c_2, p_x, p_0, p_1 = coeffs
+    c = _lib.UnipcCoeffsC(ctypes.sizeof(_lib.UnipcCoeffsC), int(bool(corr)), float(guidance), float(k_x), float(k_e), float(c_l),
+                          float(c_0), float(c_1), float(c_2), float(p_x), float(p_0), float(p_1), float(next_input_scale))
+    how = () if table is None else (_p(table), n // x.shape[0])
+    _lib.check(getattr(_lib.load(), entry)(_p(eps), _p(x), _p(x_last), _p(m1), _p(m2), _p(model_in), n, *how, c, _stream()), entry)
+
+
+def unipc_step(eps, x, history, model_in, coeffs, next_input_scale: float = 1.0):
+    """The fused UniPC predictor-corrector step without classifier-free guidance: eps / model_in are fp16 of x's size."""
+    _unipc("lavie_unipc_step", "unipc_step", eps, x, history, model_in, coeffs, next_input_scale)
+
+
+def cfg_unipc_step(eps2, x, history, model_in2, guidance, coeffs, next_input_scale: float = 1.0):
+    """Fused CFG + UniPC step: guidance, x0 prediction, corrector, predictor, the three history writes and the next fp16 model
+    input [x' | x'] in one launch.  A history tensor is read only when a coefficient that multiplies it is non-zero."""
+    _unipc("lavie_cfg_unipc_step", "cfg_unipc_step", eps2, x, history, model_in2, coeffs, next_input_scale, guidance=guidance)
+
+
+def cfg_unipc_step_scaled(eps2, x, history, model_in2, table, coeffs, next_input_scale: float = 1.0):
+    """cfg_unipc_step with (guidance, rescale factor) per latent from `table` [P, 2] (`guidance_table`)."""
+    if table is None:
+        raise ValueError("cfg_unipc_step_scaled: table is needed")
+    _unipc("lavie_cfg_unipc_step_scaled", "cfg_unipc_step_scaled", eps2, x, history, model_in2, coeffs, next_input_scale, table=table)
+
+
 def window_step(eps, x, aux, model_in, starts, profile, guidance, coeffs, next_input_scale: float = 1.0, multistep: bool = False):
     """One denoising step of a clip sampled as overlapping frame windows (lavie_window_step, csrc/sampler_window.hip).
     x fp32 [P, C, F, ...] is the whole clip, updated in place; eps / model_in are lists with one fp16 tensor [nb, C, L, ...] per

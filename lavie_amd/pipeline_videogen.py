@@ -445,7 +445,7 @@ class VideoGenPipeline:
             self.DENOISE, latents.shape[2], latents.shape[0], known=dict(known=known, mask=mask, known_noise=known_noise),
             late_start=start_step != 0, window_length=window_length, guidance=(guidance_scale, guidance_rescale),
             pag=(pag_scale, pag_adaptive_scale), cache=(cache_interval, cache_depth),
-            free_init=free_init if free_init is not None else self.free_init)
+            free_init=free_init if free_init is not None else self.free_init, unipc=bool(getattr(self.scheduler, "unipc", False)))
         geometry = sampling.window_geometry(latents.shape[2], window_length, window_stride, window_weights)
         if known is None and (mask is not None or known_noise is not None or start_step != 0):
             raise ValueError("`mask`, `known_noise` and `start_step` need `known` latents")
@@ -621,7 +621,8 @@ class VideoGenPipeline:
         N-th step only, at `cache_depth`; not with `window_length`.  See `denoise`."""
         judged = dict(known=dict(known_latents=known_latents, video=video, known_mask=known_mask), late_start=strength != 1.0,
                       window_length=window_length, guidance=(guidance_scale, guidance_rescale), pag=(pag_scale, pag_adaptive_scale),
-                      cache=(cache_interval, cache_depth), free_init=free_init if free_init is not None else self.free_init)
+                      cache=(cache_interval, cache_depth), free_init=free_init if free_init is not None else self.free_init,
+                      unipc=bool(getattr(self.scheduler, "unipc", False)))
         sampling.check_features(self.CALL, video_length, **judged)
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor

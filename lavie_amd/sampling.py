@@ -34,6 +34,9 @@ class StepPlan:
         # a multistep scheduler says so itself (DPMSolverMultistepScheduler.multistep): its fifth coefficient is c_prev, not a
         # noise sigma, and the step kernel keeps the previous x0 prediction in a buffer beside the fp32 latents
         self.multistep = bool(getattr(scheduler, "multistep", False))
+        # UniPCMultistepScheduler says `unipc`: its `coefficients` are the ten scalars of the predictor-corrector step kernel, which
+        # keeps the previous corrected sample and two x0 predictions in three buffers beside the fp32 latents
+        self.unipc = bool(getattr(scheduler, "unipc", False))
         self._scheduler = scheduler
         # `eta` goes to the scheduler only if its step takes one (DDIM), as prepare_extra_step_kwargs does
         # (pipeline_videogen.py:431-446); DDPM ignores it
@@ -52,7 +55,7 @@ class StepPlan:
 
     def adds_noise(self, coeffs) -> bool:
         """DDPM: every step but the last; DDIM: only with eta > 0; a multistep scheduler's fifth coefficient is no sigma."""
-        return not self.multistep and coeffs[4] != 0.0
+        return not self.multistep and not self.unipc and coeffs[4] != 0.0
 
     def input_scale(self, i: int) -> float:
         """Scale of the model input of step i; 1.0 without `model_input_scale` or past the last step."""
@@ -332,6 +335,12 @@ REFUSED = {
     ("pag", "sequence"): "`pag_scale` > 0 cannot be combined with a `guidance_scale` sequence (one value per prompt)",
     ("pag", "rescale"): "`pag_scale` > 0 cannot be combined with `guidance_rescale` > 0",
     ("window_length", "known"): "frame windows (`window_length`) cannot be combined with {known}",
+    # the UniPC sampler (`unipc`: the call's scheduler is a UniPCMultistepScheduler), judged in front of every other feature
+    ("unipc", "known"): "the UniPC sampler (UniPCMultistepScheduler) cannot be combined with {known}: its step kernel has no "
+                        "known-region form and a run that starts late has no history",
+    ("unipc", "window_length"): "the UniPC sampler (UniPCMultistepScheduler) cannot be combined with frame windows (`window_length`)",
+    ("unipc", "pag"): "the UniPC sampler (UniPCMultistepScheduler) cannot be combined with `pag_scale` > 0",
+    ("unipc", "free_init"): "the UniPC sampler (UniPCMultistepScheduler) cannot be combined with {free_init}",
 }
 
 # How one caller of `check_features` speaks: the features it judges, in the order it has always judged them (of two refusals that
@@ -340,14 +349,24 @@ Surface = namedtuple("Surface", "order free_init known", defaults=("", ""))
 
 
 def check_features(surface, clip_frames: int, prompts: int = 0, known=None, late_start: bool = False, window_length=None,
-                   guidance=(1.0, 0.0), pag=(0.0, 0.0), cache=(None, 1), free_init=None):
+                   guidance=(1.0, 0.0), pag=(0.0, 0.0), cache=(None, 1), free_init=None, unipc: bool = False):
     """The sampling features of one call on a clip of `clip_frames` frames and `prompts` latents, as far as `surface.order` names
     them: each feature's own arguments through its validator, then every pair of `REFUSED` that the call combines refused ->
     (the FreeInit setting or None, the layer-cache interval in force, whether PAG is on).  A feature outside the order is neither
     validated nor refused and comes back as off.  known: the caller's known-latents tensors by argument name (None = absent);
     late_start: the run starts past position 0 or below full strength; guidance = (guidance_scale, guidance_rescale), looked at
     only for PAG's rows (`check_guidance` stays where each caller has it); pag = (pag_scale, pag_adaptive_scale); cache =
-    (cache_interval, cache_depth).  Raises before anything reaches the engine."""
+    (cache_interval, cache_depth).  unipc: the call samples with UniPC, which claims guidance, the guidance table, the layer cache and
+    seeded initial latents only; every other feature the call asks for is refused first, whatever the surface's order.  Raises
+    before anything reaches the engine."""
+    if unipc:
+        asked = {"known": late_start or any(value is not None for value in (known or {}).values()),
+                 "window_length": window_length is not None, "pag": float(pag[0]) > 0.0,
+                 "free_init": free_init_mod.coerce(free_init) is not None}
+        for what, is_on in asked.items():
+            if is_on:
+                raise ValueError(REFUSED["unipc", what].format(free_init=surface.free_init or "FreeInit (`free_init`)",
+                                                               known=surface.known or "known latents"))
     given = dict(known or {})
     given.setdefault("window_length", window_length)
     argument = next((name for name, value in given.items() if value is not None), None)
@@ -401,6 +420,21 @@ def step(eps, x, aux, model_in, guidance_scale, coeffs, next_scale, multistep: b
     name = STEP_WRAPPERS[bool(multistep), kind, region is not None]
     getattr(ops, name)(eps, x, aux, model_in, *guidance, coeffs, next_scale, *(region or ()))
 
+
+def unipc_step(eps, x, history, model_in, guidance_scale, coeffs, next_scale):
+    """One fused UniPC step through its `ops` wrapper.  `history`: the run's (x_last, m1, m2).  `guidance_scale` as in `step`:
+    None, a number, or a GuidanceTable (computed from `eps` first); nothing else is combined with this sampler."""
+    if isinstance(guidance_scale, GuidanceTable):
+        kind, guidance = "table", (guidance_scale([eps]),)
+    elif isinstance(guidance_scale, PagGuidance):
+        raise ValueError(REFUSED["unipc", "pag"])
+    else:
+        kind, guidance = ("scalar", (guidance_scale,)) if guidance_scale is not None else ("none", ())
+    getattr(ops, UNIPC_WRAPPERS[kind])(eps, x, history, model_in, *guidance, coeffs, next_scale)
+
+
+# guidance kind -> the `ops` wrapper of `unipc_step`
+UNIPC_WRAPPERS = {"none": "unipc_step", "scalar": "cfg_unipc_step", "table": "cfg_unipc_step_scaled"}
 
 # guidance kind -> the `ops` wrapper of a plain five-coefficient step that makes its noise from a key (no region, no table, no PAG)
 STEP_SEEDED = {"none": "sampler_step_seeded", "scalar": "cfg_sampler_step_seeded"}
@@ -507,6 +541,12 @@ class Run:
             self.region = tuple(None if t is None else t.to(device=x.device, dtype=torch.float32).contiguous()
                                 for t in (known, mask, known_noise))
         self.x0_prev = torch.empty_like(x) if plan.multistep else None     # never read before the first step has written it (c_prev = 0)
+        # UniPC: (x_last, m1, m2), none of them read before a step has written it; a Run is one chunk, one clip, one call, so every
+        # one of them starts with a fresh history: position 0 has no corrector and a first-order predictor
+        self.unipc_history = tuple(torch.empty_like(x) for _ in range(3)) if plan.unipc else None
+        if plan.unipc and (self.windowed or pag or known is not None):
+            what = "window_length" if self.windowed else "pag" if pag else "known"
+            raise ValueError(REFUSED["unipc", what].format(known="known latents", free_init="FreeInit"))
         self.model_in = [torch.empty((self.batch, x.shape[1], self.frames) + tuple(x.shape[3:]), dtype=torch.float16, device=x.device)
                          for _ in self.starts]
         self.t_dev = plan.t_dev(x.device)
@@ -535,6 +575,8 @@ class Run:
         plan, masked, interval = self.plan, self.region is not None and self.region[1] is not None, self.cache_interval
         forwards = WindowForwards(lambda w, i: forward(w, i, layer_cache_mode(i - start, interval)))
         region = None
+        if plan.unipc and self.free is not None:
+            raise ValueError(REFUSED["unipc", "free_init"].format(free_init="FreeInit (`free_init`)"))
         for iteration in range(self.free.setting.num_iters if self.free is not None else 1):
             if iteration > 0:
                 # the next iteration's plan first: its first input scale goes into the mix, which leaves x and, without windows,
@@ -550,7 +592,9 @@ class Run:
                     guidance.pag_scale = pag_scale_at(*self.pag, plan.timesteps[i])
                 coeffs = plan.coeffs(i, first=start > 0 and i == start)
                 aux = self.x0_prev if plan.multistep else noise.draw() if plan.adds_noise(coeffs) else None
-                if self.windowed:
+                if plan.unipc:
+                    unipc_step(eps[0], x, self.unipc_history, model_in[0], guidance, coeffs, plan.input_scale(i + 1))
+                elif self.windowed:
                     window_step(eps, x, aux, model_in, self.starts, self.profile, guidance, coeffs, plan.input_scale(i + 1),
                                 plan.multistep)
                 else:

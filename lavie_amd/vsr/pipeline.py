@@ -96,7 +96,8 @@ class VideoUpscalePipeline:
         steps 0, N, 2N, ... of this call, so every chunk starts with a refresh, the shallow walk on the steps between.  Not
         combined with frame windows.  None or 1 is the call without it."""
         _, cache_interval, _ = sampling.check_features(sampling.Surface(("cache",)), latents.shape[2], window_length=window_length,
-                                                       cache=(cache_interval, cache_depth))
+                                                       cache=(cache_interval, cache_depth),
+                                                       unipc=bool(getattr(self.scheduler, "unipc", False)))
         geometry = sampling.window_geometry(latents.shape[2], window_length, window_stride, window_weights)
         plan = sampling.StepPlan(self.scheduler, num_inference_steps, eta)
         # the scalar itself, or the table route with its buffers, allocated here once for the loop
